@@ -17,6 +17,16 @@ N>1: one process per GPU (torch.distributed / RCCL); every rank runs an independ
 merged with one asynchronous all_gather (north-star hand-off to the estimator).
 
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times exactly --steps steps and prints the line; --dump-outputs DIR also
+writes the result members of the last timed step as DIR/<name>.npy.  --full adds everything else the line
+can carry: the repeated passes, the per-kernel passes and roofline, the side passes (host-resident events,
+one batch in flight, the other LK mode, few host CPUs), the C5-shape legs, the CPU baselines and lk_modes.
+
+The stream: the first STREAM_POOL batches are generated (SceneStream / PoissonStream, seeded); later steps
+replay them in order with every timestamp moved on by the pool's duration per round, so the set-up does not
+grow with --steps (STREAM_POOL is a multiple of the scene's 24-batch ego-motion period: the static scene is
+where it was, only the independent movers and the noise jump at a wrap).
 """
 import argparse
 import json
@@ -30,6 +40,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8 TB/s spec
+STREAM_POOL = 48  # distinct batches generated per run (~0.2 s of host time each); later steps replay them
 
 
 # The per-kernel timers' slots are named after the kernel FUNCTION each one brackets (esvio_fe_kernel_name =
@@ -155,7 +166,7 @@ def parse():
                          "every batch time-sliced over the N GPUs for the SAE update")
     ap.add_argument("--repeats", type=int, default=0,
                     help="times the timed --steps region is run over the continued stream (the first "
-                         "is the headline ms_per_step; all are reported); 0 = 5 up to 30 steps, else 3")
+                         "is the headline ms_per_step; all are reported); 0 = 1, with --full 5 up to 30 steps, else 3")
     ap.add_argument("--max-cnt", type=int, default=300)
     ap.add_argument("--torch-exchange", action="store_true",
                     help="merge the tracked corners through torch.distributed (TrackExchange) also over "
@@ -170,7 +181,44 @@ def parse():
                     help="skip the extra pass with the events in host memory (host_resident_events)")
     ap.add_argument("--dist-backend", default="nccl",
                     help="torch.distributed backend (nccl = RCCL; gloo only for dry runs of the N>1 path)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the repeated passes (--repeats 0 = 5 up to 30 steps, else 3), the "
+                         "per-kernel passes and roofline, the side passes, the C5-shape legs, the CPU baselines and "
+                         "lk_modes; a plain run times --steps steps once and skips all of them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to its caller (the tracker's result members, "
+                         "float32 / float64) as DIR/<name>.npy")
     return ap.parse_args()
+
+
+def shift_events_np(ev, shift_us):
+    """a copy of an EVENT_DTYPE array with every timestamp moved on by shift_us microseconds"""
+    out = ev.view(np.uint8).copy().view(ev.dtype)  # (byte copy: the padding too, so runs match byte for byte)
+    ns = out["sec"].astype(np.int64) * 1_000_000_000 + out["nsec"].astype(np.int64) + int(shift_us) * 1000
+    out["sec"] = (ns // 1_000_000_000).astype(np.uint32)
+    out["nsec"] = (ns % 1_000_000_000).astype(np.uint32)
+    return out
+
+
+def shift_events_dev(t, shift_us):
+    """shift_events_np on a device tensor of the events' bytes (a new tensor): sec / nsec are the 2nd and 3rd
+    32-bit words of each 16-byte event (both < 2^31 here)"""
+    import torch
+    out = t.clone()
+    w = out.view(torch.int32).view(-1, 4)
+    ns = w[:, 1].to(torch.int64) * 1_000_000_000 + w[:, 2].to(torch.int64) + int(shift_us) * 1000
+    w[:, 1] = torch.div(ns, 1_000_000_000, rounding_mode="floor").to(torch.int32)
+    w[:, 2] = torch.remainder(ns, 1_000_000_000).to(torch.int32)
+    return out
+
+
+def dump_outputs(ft, directory):
+    """the tracker's result members after the last timed step (ids / counts as float64, points as float32)"""
+    os.makedirs(directory, exist_ok=True)
+    for name in sorted(ft._RESULTS):
+        a = np.asarray(getattr(ft, name))
+        a = a.astype(np.float64) if a.dtype.kind in "iu" else a.astype(np.float32)
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def usable_cpus():
@@ -338,9 +386,12 @@ def main():
     from esvio_amd.synth import PoissonStream, SceneStream
 
     W, H = args.width, args.height
-    repeats = args.repeats if args.repeats > 0 else (5 if args.steps <= 30 else 3)
+    if args.repeats > 0:
+        repeats = args.repeats
+    else:
+        repeats = (5 if args.steps <= 30 else 3) if args.full else 1
     n_frames = args.warmup + args.steps * repeats
-    n_prof = 0 if args.no_profile_pass else min(args.steps, 30)
+    n_prof = 0 if args.no_profile_pass or not args.full else min(args.steps, 30)
     # ---- synthetic stream (per rank: an independent rig, different seed), resident in HBM
     cam_split = args.split == "camera" and world > 1
     time_split = args.split == "time" and multi
@@ -350,13 +401,26 @@ def main():
     stream_seed = args.seed + (0 if one_rig else 1000 * rank)
     scene = (PoissonStream(W, H, rate=args.rate, batch_hz=args.batch_hz, seed=stream_seed) if args.stream == "poisson"
              else SceneStream(W, H, rate=args.rate, batch_hz=args.batch_hz, seed=stream_seed))
+    # frames past the pool: the pool's batches again, timestamps moved on by whole pool durations (module
+    # docstring); their host copies are made only where a pass of --full reads them
     host_batches, dev_batches = [], []
-    for _ in range(n_frames):
-        L, R, _ = scene.next_batch()
-        host_batches.append((L, R, len(L), len(R), event_times(L)[-1]))
-        tl = torch.from_numpy(L.view(np.uint8).reshape(-1)).cuda()
-        tr = torch.from_numpy(R.view(np.uint8).reshape(-1)).cuda()
-        dev_batches.append((tl, tr, len(L), len(R), event_times(L)[-1]))
+    n_pool = min(n_frames, STREAM_POOL)
+    for i in range(n_frames):
+        if i < n_pool:
+            L, R, _ = scene.next_batch()
+            tl = torch.from_numpy(L.view(np.uint8).reshape(-1)).cuda()
+            tr = torch.from_numpy(R.view(np.uint8).reshape(-1)).cuda()
+        else:
+            k, shift_us = i % n_pool, (i // n_pool) * n_pool * scene.dur_us
+            L0, R0 = host_batches[k][:2]
+            if args.full:
+                L, R = shift_events_np(L0, shift_us), shift_events_np(R0, shift_us)
+            else:
+                L, R = shift_events_np(L0[-1:], shift_us), None  # (the last event gives t_last)
+            tl, tr = shift_events_dev(dev_batches[k][0], shift_us), shift_events_dev(dev_batches[k][1], shift_us)
+        nl, nr = int(tl.numel()) // 16, int(tr.numel()) // 16
+        host_batches.append((L, R, nl, nr, event_times(L)[-1]))
+        dev_batches.append((tl, tr, nl, nr, event_times(L)[-1]))
     torch.cuda.synchronize()
 
     cfg = FE.make_config(W, H, device=dev_index, max_cnt=args.max_cnt, min_dist=10, flow_back=1, f_ransac=1,
@@ -529,8 +593,8 @@ def main():
     gc.disable()
     for i in range(args.warmup):
         main_run.step(i)
-    # ---- the timed region: EXACTLY --steps steps (pass 0 is the headline); the same region is then
-    # repeated over the continued stream (passes 1..R-1) so that the spread can be reported.  Every
+    # ---- the timed region: EXACTLY --steps steps (pass 0 is the headline); with --full (or --repeats R) the
+    # same region is then repeated over the continued stream (passes 1..R-1) so that the spread can be reported.  Every
     # step's wall time is kept (one perf_counter per step), and the library's own per-call record
     # (esvio_fe_latency_stats) names where the slowest call of each pass spent its time.
     passes = []
@@ -588,6 +652,8 @@ def main():
             print("bench: pass %d per-step ms:" % r, " ".join("%.3f" % v for v in sm), file=sys.stderr)
             print("bench: pass %d library latency: %s; ransac tail %s" % (r, lib_lat[r], ransac_tails[r]), file=sys.stderr)
     n_tracks = (len(ft.ids), len(ft.ids_right))
+    if args.dump_outputs and rank == 0:  # (the last timed step's results, completed by finish() in lazy mode)
+        dump_outputs(ft, args.dump_outputs)
     # The passes below are other trackers, one after the other, each alone in the process like this one was: the
     # runtime has four hardware queues per priority level and PROCESS, and an idle tracker's streams keep theirs
     # (measured: the host-resident replay pass beside the idle main tracker 0.23 ms/step, alone 0.16)
@@ -704,7 +770,7 @@ def main():
                                        allocs=lt["max_allocs"], index=lt["max_call"])
         return out, ev, th
 
-    extra = rank == 0 and world == 1 and not one_rig and not args.no_host_pass
+    extra = args.full and rank == 0 and world == 1 and not one_rig and not args.no_host_pass
     # ---- the same replay schedule with the events in HOST memory (what the drop-in binding of
     # INTEGRATION.md passes): every batch then crosses PCIe inside the call that prefetches it
     host_res = None
@@ -784,7 +850,7 @@ def main():
     # own, ~2 us of each figure is the pair).  SURVEY.md section 8d's accounting: ingest 16 B/event
     # (k_tile_hist), SAE update 32 B/event (k_tile_apply); the partition's own traffic is extra.
     sae_chain = None
-    if rank == 0 and world == 1 and not args.no_sae_pass:
+    if args.full and rank == 0 and world == 1 and not args.no_sae_pass:
         sae_chain = {"note": "createSAE_left/right alone, 1280x720 stereo, 100 Mev/s per camera, one 1/30 s batch per launch "
                              "chain; HIP-event pairs around every launch; algorithmic bytes per SURVEY 8d "
                              "(k_tile_scatter: its own 16 B in + 8 B out per event, not in SURVEY's table)"}
@@ -831,7 +897,7 @@ def main():
     # camera and batch), plain calls, device-resident: where the event-proportional kernels are HBM-bound.  Three
     # timed steps; then the same three with the per-launch event pairs on, for the kernels' live durations.
     c5_leg = None
-    if rank == 0 and world == 1 and not args.no_sae_pass and (W, H) != (1280, 720):
+    if args.full and rank == 0 and world == 1 and not args.no_sae_pass and (W, H) != (1280, 720):
         st5 = SceneStream(1280, 720, rate=1e8, batch_hz=args.batch_hz, seed=args.seed)
         nw5, ns5 = 2, 3
         bat = []
@@ -902,7 +968,7 @@ def main():
 
     # ---- CPU baseline: the oracle (single-threaded port of the reference path) on a bounded sample
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_frames > 0:  # (the CPU baseline is an N = 1 figure)
+    if args.full and rank == 0 and world == 1 and args.cpu_frames > 0:  # (the CPU baseline is an N = 1 figure)
         from oracle import oracle as O
         ocfg = O.make_config(W, H, max_cnt=args.max_cnt, min_dist=10, flow_back=1, f_ransac=1,
                              lk_accum=args.lk_accum, equalize=args.equalize)
@@ -960,7 +1026,7 @@ def main():
     # oracle's exact mode — bit-identical to the GPU default by the -m gpu tests — against the oracle's
     # x86 float order at the tracker's points, temporal and stereo calls)
     lk_modes = None
-    if rank == 0 and world == 1 and args.cpu_frames > 0 and not args.mc:
+    if args.full and rank == 0 and world == 1 and args.cpu_frames > 0 and not args.mc:
         from oracle import oracle as O
         tr_l = O.Tracker(O.make_config(W, H, max_cnt=args.max_cnt, min_dist=10, flow_back=1, f_ransac=1, lk_accum=1,
                                        equalize=args.equalize))
