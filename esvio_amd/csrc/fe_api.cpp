@@ -137,6 +137,7 @@ int esvio_fe_destroy(esvio_fe_handle c) {
   if (c->x_pin_recv) (void)hipHostFree(c->x_pin_recv);
   void* ptrs[] = {c->x_send, c->x_recv, c->d_part, c->d_warp, c->d_tile, c->L2s, c->S2s, c->slice_stage, c->L2, c->S2, c->d_ev, c->keys[0], c->keys[1], c->vals[0], c->vals[1], c->hist, c->sae_marks,
                   c->d_rejected, c->d_res, c->d_ptsD, c->d_flags, c->d_pub_slots, c->d_pub_done, c->d_chain, c->d_lane_gate, c->d_gftt_cov, c->d_gftt_rowsum, c->d_gftt_eig, c->d_gftt_max,
+                  c->d_fast_m, c->d_fast_xy, c->d_fast_score, c->d_fast_cnt, c->d_fast_det, c->d_fast_grp, c->d_fast_cxy, c->d_fast_cscore, c->d_fast_tot, c->d_fast_img,
                   c->d_mask_bits, c->d_sel_idx, c->d_sel_bitmap, c->d_eq_tmp,
                   c->tmp_pyr[0].mem, c->tmp_pyr[1].mem, c->med_tmp[0].mem, c->med_tmp[1].mem, c->d_lut,
                   c->d_minmax};
@@ -310,6 +311,7 @@ int esvio_fe_create(const esvio_fe_config* cfg, esvio_fe_handle* out) {
   // (the per-pixel dedup of the Arc* candidates pays only where the selection digs deep into its list: fe_stages.cpp run_arc)
   c->dedup_enabled = getenv("ESVIO_FE_NO_DEDUP") == nullptr && (cfg->max_cnt > 500 || getenv("ESVIO_FE_DEDUP") != nullptr);
   c->fuse_ts_pyr = getenv("ESVIO_FE_NO_FUSE") == nullptr;
+  c->fast_lds = getenv("ESVIO_FE_FAST_LDS") != nullptr;
   c->select_one_wave = getenv("ESVIO_FE_SELECT_SERIAL") != nullptr;
   if (const char* v = getenv("ESVIO_FE_SAE_EV_MIN")) c->sae_ev_min = (size_t)strtoull(v, nullptr, 10);
   c->tiled = make_tile_geom(c->W, c->H, &c->tgeom) && getenv("ESVIO_FE_SAE_SORT") == nullptr;
@@ -1045,6 +1047,39 @@ int esvio_fe_good_features_to_track(esvio_fe_handle c, const uint8_t* img, int m
   *n_out = k;
   if (c->prof_on) resolve_profile(c);
   return 0;
+}
+
+// FAST on the time surface (or a caller's image): fast.h:22-47 of the reference's vendored library
+int esvio_fe_fast_corners(esvio_fe_handle c, int cam, const uint8_t* img, int space, int arc, int barrier,
+                          int nonmax, int16_t* out_xy, int32_t* out_score, int32_t capacity, int32_t* n_out,
+                          int32_t* n_detected) {
+  if (!c || !n_out) return ESVIO_FE_EINVAL;
+  *n_out = 0;
+  if (n_detected) *n_detected = 0;
+  if (arc != 9 && arc != 10) return fail(c, ESVIO_FE_EINVAL, "fast_corners: arc must be 9 or 10 (got %d)", arc);
+  if (barrier < 0 || barrier > 255) return fail(c, ESVIO_FE_EINVAL, "fast_corners: barrier must be in 0..255 (got %d)", barrier);
+  if (nonmax != 0 && nonmax != 1) return fail(c, ESVIO_FE_EINVAL, "fast_corners: nonmax must be 0 or 1");
+  if (arc == 9 && (nonmax || out_score))
+    return fail(c, ESVIO_FE_EINVAL, "fast_corners: the reference scores FAST-10 only: arc 9 has neither non-max nor scores");
+  if (capacity < 0 || (capacity > 0 && !out_xy)) return fail(c, ESVIO_FE_EINVAL, "fast_corners: capacity %d without out_xy", capacity);
+  if (!img && cam != 0 && cam != 1) return fail(c, ESVIO_FE_EINVAL, "fast_corners: cam must be 0 or 1");
+  if (img && space != ESVIO_FE_HOST && space != ESVIO_FE_DEVICE) return fail(c, ESVIO_FE_EINVAL, "fast_corners: bad memory space");
+  HIPCHK(c, hipSetDevice(c->dev));
+  const uint8_t* src = img;
+  int stride = c->W;
+  if (!img) {  // the plane esvio_fe_get_time_surface copies out, read where it lies; the main stream is behind
+               // whatever rendered it (a prefetched batch's images are waited for when its track call takes it up)
+    const PyrDesc& d = raw_ts_desc(c, cam);
+    src = px00(d);
+    stride = d.stride[0];
+  } else if (space == ESVIO_FE_HOST) {
+    const size_t bytes = (size_t)c->W * c->H;
+    if (!c->d_fast_img)
+      if (int rc = dev_alloc(c, &c->d_fast_img, bytes)) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->d_fast_img, img, bytes, hipMemcpyHostToDevice, cur_stream(c)));
+    src = c->d_fast_img;
+  }
+  return fast_run(c, src, stride, arc, barrier, nonmax != 0, out_xy, out_score, capacity, n_out, n_detected);
 }
 
 int esvio_fe_track_image(esvio_fe_handle c, double cur_time, const uint8_t* img_left,

@@ -69,7 +69,7 @@ const char* const kKernelNames[K_COUNT] = {
     "k_tile_hist", "k_tile_scan", "k_tile_scatter", "k_tile_apply", "k_sae_keys", "k_radix_pass", "k_sae_apply",
     "k_time_surface4", "k_time_surface", "k_median", "k_clahe", "k_norm_pyr", "k_pyr3", "k_pyr_down", "k_pyr_pad",
     "k_scharr", "k_pad_scharr", "k_lk_f32", "k_lk", "k_arc_map", "k_arc_ev", "k_dedup", "k_compact", "k_select_mw",
-    "k_select", "k_select_gbm"};
+    "k_select", "k_select_gbm", "k_fast_score", "k_fast_collect"};
 
 struct KStat {
   double ms = 0;
@@ -360,6 +360,13 @@ struct esvio_fe_ctx {
   float* d_gftt_eig = nullptr;
   uint32_t* d_gftt_max = nullptr;
   int32_t* d_sel_idx = nullptr;
+  // esvio_fe_fast_corners scratch, allocated on first use: the score map, the per-block lists, their
+  // counts (+ k_compact's group sums), the compacted list and {total, detected before non-max}
+  uint8_t* d_fast_m = nullptr;
+  uint32_t *d_fast_xy = nullptr, *d_fast_score = nullptr, *d_fast_cnt = nullptr, *d_fast_det = nullptr, *d_fast_grp = nullptr;
+  uint32_t *d_fast_cxy = nullptr, *d_fast_cscore = nullptr, *d_fast_tot = nullptr;
+  uint8_t* d_fast_img = nullptr;  // a caller's host image (linear, width*height)
+  bool fast_lds = false;          // (ESVIO_FE_FAST_LDS=1: k_fast_score's LDS-tiled form, for the A/B in KERNELS.md)
   // pinned host staging (layout: pin_of())
   uint8_t* h_img = nullptr;  // copy_level0_in's staging ring: pinned host side ...
   uint8_t* d_img = nullptr;  // ... and its device side (linear images)

@@ -19,6 +19,66 @@ void euclid_halfwidths(double md, int8_t* hw /*[kMaxDiscR+1]*/, int* radius) {
   }
 }
 
+// fast::fast_corner_detect_9 / _10 (+ fast_corner_score_10, fast_nonmax_3x3) of the reference's vendored FAST
+// (dependences/fast_neon-master/include/fast/fast.h:22-47) on a device image.  Buffers of its own, allocated on
+// the first call: nothing the tracker or a prefetched batch uses is touched.
+int fast_run(esvio_fe_ctx* c, const uint8_t* img, int stride, int arc, int barrier, bool nonmax, int16_t* out_xy,
+             int32_t* out_score, int32_t capacity, int32_t* n_out, int32_t* n_detected) {
+  const size_t P = (size_t)c->W * c->H;
+  const uint32_t nblk = (uint32_t)((P + kArcBlock - 1) / kArcBlock);
+  if (!c->d_fast_m) {
+    if (int rc = dev_alloc(c, &c->d_fast_xy, (size_t)nblk * kArcBlock)) return rc;
+    if (int rc = dev_alloc(c, &c->d_fast_score, (size_t)nblk * kArcBlock)) return rc;
+    if (int rc = dev_alloc(c, &c->d_fast_cnt, nblk)) return rc;
+    if (int rc = dev_alloc(c, &c->d_fast_det, nblk)) return rc;
+    if (int rc = dev_alloc(c, &c->d_fast_grp, nblk / 64 + 1)) return rc;
+    if (int rc = dev_alloc(c, &c->d_fast_cxy, P)) return rc;
+    if (int rc = dev_alloc(c, &c->d_fast_cscore, P)) return rc;
+    if (int rc = dev_alloc(c, &c->d_fast_tot, 2)) return rc;
+    if (int rc = dev_alloc(c, &c->d_fast_m, P)) return rc;  // (last: the test above means "all of them")
+  }
+  hipStream_t s = cur_stream(c);
+  FastArgs a{};
+  a.img = img;
+  a.stride = stride;
+  a.W = c->W;
+  a.H = c->H;
+  a.arc = arc;
+  a.barrier = barrier;
+  a.nonmax = nonmax ? 1 : 0;
+  a.lds = c->fast_lds ? 1 : 0;
+  a.m = c->d_fast_m;
+  a.cand_xy = c->d_fast_xy;
+  a.cand_score = c->d_fast_score;
+  a.cand_cnt = c->d_fast_cnt;
+  a.det_cnt = c->d_fast_det;
+  a.n_detected = (n_detected && nonmax) ? c->d_fast_tot + 1 : nullptr;  // (without non-max it is the total)
+  {
+    ScopedKernel k(c, K_FAST_SCORE, 2 * P);  // the image read once, the map written
+    launch_fast_score(s, a);
+  }
+  {
+    ScopedKernel k(c, K_FAST_COLLECT, P);
+    launch_fast_collect(s, a);
+  }
+  {
+    ScopedKernel k(c, K_COMPACT, 0);
+    launch_compact(s, c->d_fast_xy, c->d_fast_score, c->d_fast_cnt, nblk, c->d_fast_cxy, c->d_fast_cscore, c->d_fast_tot,
+                   c->d_fast_grp);
+  }
+  uint32_t tot[2] = {0, 0};
+  HIPCHK(c, hipMemcpyAsync(tot, c->d_fast_tot, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  const size_t k = std::min<size_t>(tot[0], capacity > 0 ? (size_t)capacity : 0);
+  if (k && out_xy) HIPCHK(c, hipMemcpyAsync(out_xy, c->d_fast_cxy, k * 4, hipMemcpyDeviceToHost, s));  // x | y<<16 = int16 x, y
+  if (k && out_score) HIPCHK(c, hipMemcpyAsync(out_score, c->d_fast_cscore, k * 4, hipMemcpyDeviceToHost, s));
+  if (k) HIPCHK(c, hipStreamSynchronize(s));
+  *n_out = (int32_t)tot[0];
+  if (n_detected) *n_detected = (int32_t)(nonmax ? tot[1] : tot[0]);
+  if (c->prof_on) resolve_profile(c);
+  return 0;
+}
+
 // cv::goodFeaturesToTrack on the level-0 image of pyramid `d` (padded, so no border arithmetic);
 // up to max_corners corners are written at out_pts[out_base ..], counts mirrored to host_counts.
 // `use_mask`: d_mask_bits holds the blocked pixels.  Synchronises the stream once (the number of

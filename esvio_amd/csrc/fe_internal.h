@@ -145,6 +145,10 @@ int exchange_flush(esvio_fe_ctx* c);
 void euclid_halfwidths(double md, int8_t* hw /*[kMaxDiscR+1]*/, int* radius);
 int gftt_run(esvio_fe_ctx* c, const PyrDesc& d, int max_corners, double quality, double min_distance,
              bool use_mask, float2* out_pts, int out_base, int* host_counts);
+// FAST-9/10 (+ score_10, 3x3 non-max) of the W x H image at `img` (device memory, rows `stride` bytes apart) on
+// the current stream; synchronises it.  Up to `capacity` corners in raster order go to out_xy / out_score (host).
+int fast_run(esvio_fe_ctx* c, const uint8_t* img, int stride, int arc, int barrier, bool nonmax, int16_t* out_xy,
+             int32_t* out_score, int32_t capacity, int32_t* n_out, int32_t* n_detected);
 int track_image_impl(esvio_fe_ctx* c, double cur_time, const uint8_t* img_left, const uint8_t* img_right,
                      bool PUB_THIS_FRAME);
 

@@ -68,6 +68,8 @@ enum KernelId {
   K_SELECT_MW,
   K_SELECT,
   K_SELECT_GBM,
+  K_FAST_SCORE,      // (appended: the ids above keep their meaning)
+  K_FAST_COLLECT,
   K_COUNT
 };
 
@@ -403,6 +405,37 @@ void launch_gftt_collect(hipStream_t s, const GfttArgs& a);
 void launch_gftt_sortprep(hipStream_t s, const uint32_t* comp_xy, const uint32_t* comp_val, uint32_t n,
                           uint32_t* keys, uint32_t* vals, uint32_t* ghist, uint32_t* lookback,
                           uint32_t lookback_words);
+
+// ---- FAST-9/10 on an 8-bit image (the time surface) -----------------------------------------
+// fast::fast_corner_detect_9 / _10, fast_corner_score_10 and fast_nonmax_3x3 of the reference's vendored
+// library (dependences/fast_neon-master/include/fast/fast.h:22-47), as closed forms:
+//   ring p[0..15]: the radius-3 Bresenham circle from (0,3) through (3,0), (0,-3), (-3,0); c the centre
+//   score_N = max over the 16 starts s of max(min_{k<N}(p[s+k] - c), min_{k<N}(c - p[s+k])) - 1
+//   corner  <=> 3 <= x < W-3, 3 <= y < H-3 and score_N >= barrier; the list is in raster order
+//   nonmax  keeps a corner iff none of its 8 neighbours is a corner with a score >= its own
+// Integer-only: the results are exact, and pinned to vectors the reference's compiled code produced
+// (tests/golden/fast_ref_*.npz).
+//   k_fast_score<N>  byte map m = score_N + 1 where the pixel is a corner at `barrier`, else 0
+//   k_fast_collect   (3x3 non-max on m) -> per-block ordered lists (x | y<<16, score); block b owns pixels
+//                    [b*kArcBlock, (b+1)*kArcBlock) in row-major order, so k_compact's concatenation in
+//                    block order is raster order; no atomics: k_fast_sum adds up the per-block counts before non-max
+struct FastArgs {
+  const uint8_t* img;   // pixel (0,0); rows `stride` bytes apart (a pyramid's padded level 0, or stride = W)
+  int stride;
+  int W, H;
+  int arc;              // 9 or 10
+  int barrier;          // 0..255
+  int nonmax;
+  int lds;              // != 0: k_fast_score reads its tile + 3-pixel halo through LDS (see KERNELS.md)
+  uint8_t* m;           // [W*H]
+  uint32_t* cand_xy;    // [nblk*kArcBlock]
+  uint32_t* cand_score; // [nblk*kArcBlock]
+  uint32_t* cand_cnt;   // [nblk]
+  uint32_t* det_cnt;    // [nblk] corners before non-max
+  uint32_t* n_detected; // [1] their sum (k_fast_sum), or NULL: not wanted
+};
+void launch_fast_score(hipStream_t s, const FastArgs& a);
+void launch_fast_collect(hipStream_t s, const FastArgs& a);
 
 struct SelectArgs {
   const uint32_t* comp_xy;   // compacted candidates in stream order

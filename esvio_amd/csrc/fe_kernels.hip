@@ -3541,6 +3541,166 @@ void launch_gftt_sortprep(hipStream_t s, const uint32_t* comp_xy, const uint32_t
                      ghist, lookback, lookback_words);
 }
 
+// ============================================================================ FAST-9/10
+// (fe_kernels.h: FastArgs.)  One pixel per thread, a 64 x 4 tile per block.  Most pixels of a time surface
+// are flat, so the exact score is the rare path: a window of N >= 9 consecutive ring positions always
+// holds at least two of the four compass points, so a pixel with fewer than two of them beyond the barrier
+// on one side is out after 5 bytes; the others build the 16-bit brighter / darker masks and look for a run
+// of N set bits (doubling: runs of 2, 4, 8, then 8+1 / 8+2), and only a pixel that has one computes its
+// score — the sliding minimum and maximum over the circular window by the same doubling steps.
+template <int N>
+__device__ __forceinline__ bool fast_has_run(uint32_t mask16) {
+  const uint32_t m = mask16 | (mask16 << 16);
+  const uint32_t r2 = m & (m >> 1);
+  const uint32_t r4 = r2 & (r2 >> 2);
+  const uint32_t r8 = r4 & (r4 >> 4);
+  const uint32_t rn = N == 9 ? (r8 & (m >> 8)) : (r8 & (r2 >> 8));
+  return (rn & 0xffffu) != 0;
+}
+
+constexpr int kFastTileW = 64, kFastTileH = 4, kFastLdsStride = kFastTileW + 8;
+
+template <int N, bool LDS>
+__global__ __launch_bounds__(256) void k_fast_score(FastArgs a) {
+  constexpr int dx[16] = {0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1};
+  constexpr int dy[16] = {3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1, 0, 1, 2, 3};
+  __shared__ uint8_t tile[LDS ? (kFastTileH + 6) * kFastLdsStride : 1];
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const int x = blockIdx.x * kFastTileW + tx, y = blockIdx.y * kFastTileH + ty;
+  const int W = a.W, H = a.H;
+  if (LDS) {  // tile + 3-pixel halo; positions outside the image are clamped (no border pixel reads them)
+    const int x0 = blockIdx.x * kFastTileW - 3, y0 = blockIdx.y * kFastTileH - 3;
+    for (int i = threadIdx.x; i < (kFastTileH + 6) * (kFastTileW + 6); i += 256) {
+      const int r = i / (kFastTileW + 6), col = i - r * (kFastTileW + 6);
+      const int gx = min(max(x0 + col, 0), W - 1), gy = min(max(y0 + r, 0), H - 1);
+      tile[r * kFastLdsStride + col] = a.img[(size_t)gy * a.stride + gx];
+    }
+    __syncthreads();
+  }
+  if (x >= W || y >= H) return;
+  uint32_t out = 0;
+  if (x >= 3 && x < W - 3 && y >= 3 && y < H - 3) {
+    const uint8_t* p = LDS ? tile + (ty + 3) * kFastLdsStride + tx + 3 : a.img + (size_t)y * a.stride + x;
+    const int ps = LDS ? kFastLdsStride : a.stride;
+    const int c = p[0], b = a.barrier;
+    int d[16];
+#pragma unroll
+    for (int k = 0; k < 16; k += 4) d[k] = (int)p[dy[k] * ps + dx[k]] - c;
+    const int nb = (d[0] > b) + (d[4] > b) + (d[8] > b) + (d[12] > b);
+    const int nd = (d[0] < -b) + (d[4] < -b) + (d[8] < -b) + (d[12] < -b);
+    if (nb >= 2 || nd >= 2) {
+#pragma unroll
+      for (int k = 0; k < 16; k++)
+        if (k & 3) d[k] = (int)p[dy[k] * ps + dx[k]] - c;
+      uint32_t mb = 0, md = 0;
+#pragma unroll
+      for (int k = 0; k < 16; k++) {
+        mb |= (uint32_t)(d[k] > b) << k;
+        md |= (uint32_t)(d[k] < -b) << k;
+      }
+      if (fast_has_run<N>(mb) || fast_has_run<N>(md)) {
+        int lo2[16], hi2[16], lo4[16], hi4[16], lo8[16], hi8[16];
+#pragma unroll
+        for (int k = 0; k < 16; k++) {
+          lo2[k] = min(d[k], d[(k + 1) & 15]);
+          hi2[k] = max(d[k], d[(k + 1) & 15]);
+        }
+#pragma unroll
+        for (int k = 0; k < 16; k++) {
+          lo4[k] = min(lo2[k], lo2[(k + 2) & 15]);
+          hi4[k] = max(hi2[k], hi2[(k + 2) & 15]);
+        }
+#pragma unroll
+        for (int k = 0; k < 16; k++) {
+          lo8[k] = min(lo4[k], lo4[(k + 4) & 15]);
+          hi8[k] = max(hi4[k], hi4[(k + 4) & 15]);
+        }
+        int best = -256;
+#pragma unroll
+        for (int k = 0; k < 16; k++) {
+          const int lo = min(lo8[k], N == 9 ? d[(k + 8) & 15] : lo2[(k + 8) & 15]);  // min of (p - c) over the window
+          const int hi = max(hi8[k], N == 9 ? d[(k + 8) & 15] : hi2[(k + 8) & 15]);  // -min of (c - p)
+          best = max(best, max(lo, -hi));
+        }
+        out = (uint32_t)best;  // = score + 1; the pixel passes at b, so b + 1 <= best <= 255
+      }
+    }
+  }
+  a.m[(size_t)y * W + x] = (uint8_t)out;
+}
+
+void launch_fast_score(hipStream_t s, const FastArgs& a) {
+  const dim3 grid((a.W + kFastTileW - 1) / kFastTileW, (a.H + kFastTileH - 1) / kFastTileH);
+  if (a.arc == 9) {
+    if (a.lds) launch_k(k_fast_score<9, true>, grid, dim3(256), 0, s, a);
+    else launch_k(k_fast_score<9, false>, grid, dim3(256), 0, s, a);
+  } else {
+    if (a.lds) launch_k(k_fast_score<10, true>, grid, dim3(256), 0, s, a);
+    else launch_k(k_fast_score<10, false>, grid, dim3(256), 0, s, a);
+  }
+}
+
+// m > 0 only inside the 3-pixel border, so a corner's eight neighbours are always inside the image
+__global__ __launch_bounds__(kArcBlock) void k_fast_collect(FastArgs a) {
+  __shared__ uint32_t wave_cnt[kArcBlock / 64], wave_det[kArcBlock / 64];
+  const int wave = threadIdx.x >> 6, lane = lane_id();
+  const uint32_t i = blockIdx.x * kArcBlock + threadIdx.x;
+  const int W = a.W;
+  uint32_t v = 0;
+  if (i < (uint32_t)W * (uint32_t)a.H) v = a.m[i];
+  bool take = v != 0;
+  const unsigned long long det = __ballot(take);
+  if (take && a.nonmax) {
+    const uint8_t* q = a.m + i;
+    uint32_t nmax = max(max((uint32_t)q[-1], (uint32_t)q[1]), max((uint32_t)q[-W], (uint32_t)q[W]));
+    nmax = max(nmax, max(max((uint32_t)q[-W - 1], (uint32_t)q[-W + 1]), max((uint32_t)q[W - 1], (uint32_t)q[W + 1])));
+    take = nmax < v;  // an equal neighbour suppresses, as the library's `scores[j] >= score`
+  }
+  const unsigned long long mb = __ballot(take);
+  if (lane == 0) {
+    wave_cnt[wave] = __popcll(mb);
+    wave_det[wave] = __popcll(det);
+  }
+  __syncthreads();
+  uint32_t base = 0;
+  for (int w = 0; w < wave; w++) base += wave_cnt[w];
+  if (take) {
+    const uint32_t y = i / (uint32_t)W, x = i - y * (uint32_t)W;
+    const uint32_t pos = base + __popcll(mb & ((1ull << lane) - 1ull));
+    a.cand_xy[(size_t)blockIdx.x * kArcBlock + pos] = x | (y << 16);
+    a.cand_score[(size_t)blockIdx.x * kArcBlock + pos] = v - 1;
+  }
+  if (threadIdx.x == 0) {
+    uint32_t t = 0, dsum = 0;
+    for (int w = 0; w < kArcBlock / 64; w++) {
+      t += wave_cnt[w];
+      dsum += wave_det[w];
+    }
+    a.cand_cnt[blockIdx.x] = t;
+    a.det_cnt[blockIdx.x] = dsum;
+  }
+}
+
+// the count before non-max: one block adds up the per-block counts (one atomic per block into a single word
+// cost ~10 ns per block, 36 of k_fast_collect's 45 us at 1280 x 720)
+__global__ __launch_bounds__(256) void k_fast_sum(const uint32_t* __restrict__ det_cnt, uint32_t nblk,
+                                                  uint32_t* __restrict__ out) {
+  __shared__ uint32_t part[4];
+  uint32_t s = 0;
+  for (uint32_t j = threadIdx.x; j < nblk; j += 256) s += det_cnt[j];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  if (lane_id() == 0) part[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) *out = part[0] + part[1] + part[2] + part[3];
+}
+
+void launch_fast_collect(hipStream_t s, const FastArgs& a) {
+  const uint32_t nblk = ((uint32_t)a.W * a.H + kArcBlock - 1) / kArcBlock;
+  launch_k(k_fast_collect, dim3(nblk), dim3(kArcBlock), 0, s, a);
+  if (a.n_detected) launch_k(k_fast_sum, dim3(1), dim3(256), 0, s, (const uint32_t*)a.det_cnt, nblk, a.n_detected);
+}
+
 // ============================================================================ greedy selection
 // Event_FeaturesToTrack (feature_tracker.cpp:13-38): candidates in stream order; accept iff the
 // pixel is not blocked; stamp cv::circle(r = MIN_DIST, filled) [OpenCV midpoint disc]; stop at

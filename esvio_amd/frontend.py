@@ -78,7 +78,7 @@ ABI_SYMBOLS = [
     "esvio_fe_calc_optical_flow_pyr_lk", "esvio_fe_comm_init", "esvio_fe_comm_unique_id", "esvio_fe_create",
     "esvio_fe_create_sae", "esvio_fe_create_sae_stereo", "esvio_fe_create_sae_stereo_mc", "esvio_fe_destroy",
     "esvio_fe_exchange_begin", "esvio_fe_exchange_end", "esvio_fe_exchange_tracks", "esvio_fe_export_image",
-    "esvio_fe_features_to_track", "esvio_fe_find_fundamental_mat", "esvio_fe_finish", "esvio_fe_get_sae",
+    "esvio_fe_fast_corners", "esvio_fe_features_to_track", "esvio_fe_find_fundamental_mat", "esvio_fe_finish", "esvio_fe_get_sae",
     "esvio_fe_get_time_surface", "esvio_fe_good_features_to_track", "esvio_fe_import_image", "esvio_fe_is_corner",
     "esvio_fe_last_error", "esvio_fe_mem_alloc", "esvio_fe_mem_free", "esvio_fe_mem_upload",
     "esvio_fe_pack_track_records", "esvio_fe_register_host_buffer", "esvio_fe_reserve", "esvio_fe_reset",
@@ -183,6 +183,8 @@ def load_library(build_if_missing=True):
     L.esvio_fe_get_time_surface.argtypes = [vp, i, vp]
     L.esvio_fe_export_image.argtypes = [vp, i, vp, i]
     L.esvio_fe_import_image.argtypes = [vp, i, vp, i]
+    L.esvio_fe_fast_corners.argtypes = [vp, i, vp, i, i, i, i, vp, vp, C.c_int32, C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_int32)]
     L.esvio_fe_set_profiling.argtypes = [vp, i]
     L.esvio_fe_kernel_name.restype = C.c_char_p
     L.esvio_fe_kernel_name.argtypes = [i]
@@ -621,6 +623,36 @@ class FeatureTracker:
         out = np.empty((self.cfg.height, self.cfg.width), np.uint8)
         self._hd.check(self._hd.L.esvio_fe_get_time_surface(self._hd.h, cam, _p(out)))
         return out
+
+    def fast_corners(self, img=None, cam=0, arc=10, barrier=20, nonmax=True, capacity=None, want_count=False):
+        """FAST-9/10 corners (the reference's vendored fast::fast_corner_detect_9/_10, fast_corner_score_10,
+        fast_nonmax_3x3) of the current time surface of `cam` (img None), of a numpy (H,W) u8 image or of a
+        device image given as int pointer -> (xy int16[n,2] in raster order, score int32[n] or None for arc 9).
+        capacity: room for that many corners only (the first ones); default: call again if the first guess
+        was too small.  want_count: also return (n_out, n_detected), the full counts after / before non-max."""
+        hd = self._hd
+        if img is None:
+            ptr, space, keep = None, HOST, None
+        elif isinstance(img, np.ndarray):
+            keep = np.ascontiguousarray(img, np.uint8)
+            if keep.shape != (self.cfg.height, self.cfg.width):
+                raise ValueError("image must be (height, width) of the handle")
+            ptr, space = _p(keep), HOST
+        else:
+            ptr, space, keep = C.c_void_p(int(img)), DEVICE, None
+        cap = 4096 if capacity is None else int(capacity)
+        n, nd = C.c_int32(0), C.c_int32(0)
+        while True:
+            xy = np.empty((max(cap, 1), 2), np.int16)
+            sc = np.empty(max(cap, 1), np.int32) if arc == 10 else None
+            hd.check(hd.L.esvio_fe_fast_corners(hd.h, cam, ptr, space, arc, barrier, 1 if nonmax else 0, _p(xy),
+                                                _p(sc) if sc is not None else None, cap, C.byref(n), C.byref(nd)))
+            if capacity is not None or n.value <= cap:
+                break
+            cap = n.value
+        k = min(n.value, cap)
+        out = (xy[:k].copy(), sc[:k].copy() if sc is not None else None)
+        return out + ((n.value, nd.value),) if want_count else out
 
     # ---- camera split (right camera on another GPU)
     def export_image(self, cam, dst=None):

@@ -310,6 +310,32 @@ int esvio_fe_finish(esvio_fe_handle h, esvio_fe_tracks* out);
 /* FeatureTracker::gettimesurface() tap (feature_tracker.cpp:894): current left/right image */
 int esvio_fe_get_time_surface(esvio_fe_handle h, int cam, uint8_t* out);
 
+/* ---- FAST corners on the time surface --------------------------------------------------- */
+/* fast::fast_corner_detect_9 / fast_corner_detect_10, fast_corner_score_10 and fast_nonmax_3x3 of the FAST
+ * detector the reference vendors (dependences/fast_neon-master/include/fast/fast.h:22-47; the plain C++
+ * functions, not the SSE2 / NEON ones) — the common alternative to Arc* in event front-ends, on the image
+ * where it already lies.  (The reference's own FAST pass over the published time surface,
+ * pose_graph/src/keyframe.cpp:138, is cv::FAST: other scores, another non-max; not this.)
+ * Integer-only and exact: this stage is tested against outputs of the reference's compiled code.
+ *
+ * img == NULL: the handle's current time surface of camera `cam` — the plane esvio_fe_get_time_surface
+ * returns — read in place on the device.  Otherwise img is width*height bytes of the handle's own size in
+ * `space` (ESVIO_FE_HOST: copied to the device first; ESVIO_FE_DEVICE: read in place) and `cam` is ignored.
+ * arc: 9 or 10.  barrier: 0..255 (a ring pixel counts when it differs from the centre by MORE than barrier).
+ * nonmax 0: every detected corner; out_score (optional) = fast_corner_score_10, arc 10 only.
+ * nonmax 1: the survivors of fast_nonmax_3x3 over score_10 (corners[idx[i]] of the library), arc 10 only.
+ * The library has no score for arc 9: arc 9 with nonmax or out_score is ESVIO_FE_EINVAL.
+ * Corners come in the library's order, raster order (y, then x): out_xy[2*i] = x, out_xy[2*i + 1] = y.
+ * *n_out is always the full count; at most `capacity` entries — the first ones — are written, and the call
+ * returns ESVIO_FE_OK either way: *n_out > capacity means "call again with room for *n_out".
+ * *n_detected (optional): the count before non-max.
+ * The call orders itself after the work that renders the plane it reads, waits for its own results and
+ * touches nothing of the tracker: made between two esvio_fe_track_event calls (announced batches or not)
+ * it changes no later result.  Its scratch (17 bytes per pixel) is allocated by the first call. */
+int esvio_fe_fast_corners(esvio_fe_handle h, int cam, const uint8_t* img, int space, int arc, int barrier,
+                          int nonmax, int16_t* out_xy, int32_t* out_score, int32_t capacity,
+                          int32_t* n_out, int32_t* n_detected);
+
 /* ---- camera split across GPUs (BASELINE config C4) ----------------------- */
 /* The left and right cameras have disjoint SAE state (sae_/sae_latest_ vs sae_right/
  * sae_latest_right, event_detector.h:74-79), so a second GPU can own the right camera: it runs
