@@ -37,19 +37,14 @@ nccl_allgather_fn rccl_all_gather() {
 }
 int exchange_buffers(esvio_fe_ctx* c, int world) {
   const size_t cnt = (size_t)2 * std::max(c->cfg.max_cnt, 1) * 8;
-  if (!c->x_send) {
-    if (int rc = dev_alloc(c, &c->x_send, cnt)) return rc;
-    HIPCHK(c, hipHostMalloc((void**)&c->x_pin, cnt * sizeof(float), hipHostMallocDefault));
+  if (!c->x_pin) {
+    if (int rc = c->x_send.alloc(c, cnt)) return rc;
+    if (int rc = c->x_pin.alloc(c, cnt)) return rc;
   }
-  if ((size_t)world * cnt > c->x_recv_cap) {
-    if (c->x_recv) (void)hipFree(c->x_recv);
-    if (c->x_pin_recv) (void)hipHostFree(c->x_pin_recv);
-    c->x_recv = nullptr;
-    c->x_pin_recv = nullptr;
-    c->x_recv_cap = 0;
-    if (int rc = dev_alloc(c, &c->x_recv, (size_t)world * cnt)) return rc;
-    HIPCHK(c, hipHostMalloc((void**)&c->x_pin_recv, (size_t)world * cnt * sizeof(float), hipHostMallocDefault));
-    c->x_recv_cap = (size_t)world * cnt;
+  if ((size_t)world * cnt > c->x_pin_recv.cap) {  // (the pair's second: both are there)
+    c->x_pin_recv.release();
+    if (int rc = c->x_recv.alloc(c, (size_t)world * cnt)) return rc;
+    if (int rc = c->x_pin_recv.alloc(c, (size_t)world * cnt)) return rc;
   }
   return 0;
 }
@@ -57,6 +52,62 @@ int exchange_buffers(esvio_fe_ctx* c, int world) {
 
 
 // ==================================================================================== C ABI
+// the ESVIO_FE_TRACE summary of a handle's life
+static void print_trace_summary(const esvio_fe_ctx* c) {
+  if (!c->trace || !c->phase_frames) return;
+  static const char* nm[8] = {"enqueue sae+ts+pyr", "enqueue temporal LK", "sync A", "host filter",
+                              "host ransac", "host mask + enqueue detect/stereo", "sync B", "host tail"};
+  for (int pub = 0; pub < 2; pub++) {
+    if (!c->phase_count[pub]) continue;
+    double tot = 0;
+    fprintf(stderr, "[esvio_fe trace] %llu %s frames, ms/frame:", (unsigned long long)c->phase_count[pub],
+            pub ? "published" : "unpublished");
+    for (int i = 0; i < 8; i++) {
+      fprintf(stderr, " %s=%.3f", nm[i], c->phase_ms[pub][i] / c->phase_count[pub]);
+      tot += c->phase_ms[pub][i] / c->phase_count[pub];
+    }
+    fprintf(stderr, " | total=%.3f\n", tot);
+  }
+  if (c->phase_count[1]) {
+    static const char* pn[6] = {"Event_setMask", "points + k_select launch", "speculative + chained LK launches",
+                                "previous frame's right-camera tail", "stereo LK of new corners launch",
+                                "next batch's prefetch launches"};
+    fprintf(stderr, "[esvio_fe trace] published frames, parts of 'host mask + enqueue', ms/frame:");
+    for (int i = 0; i < 6; i++) fprintf(stderr, " %s=%.3f", pn[i], c->pub_ms[i] / c->phase_count[1]);
+    fprintf(stderr, "\n");
+  }
+  fprintf(stderr, "[esvio_fe trace]");
+  fprintf(stderr, "\n[esvio_fe trace] findFundamentalMat alone: %.3f ms per published frame (slowest call %.3f ms, "
+          "%.3f without it); the two liftProjective batches before it: %.3f ms",
+          c->phase_count[1] ? c->tr_fm_ms / c->phase_count[1] : 0.0, c->tr_fm_max_ms,
+          c->phase_count[1] > 1 ? (c->tr_fm_ms - c->tr_fm_max_ms) / (c->phase_count[1] - 1) : 0.0,
+          c->phase_count[1] ? c->tr_lift_ms / c->phase_count[1] : 0.0);
+  for (int pub = 0; pub < 2; pub++)
+    if (c->phase_count[pub])
+      fprintf(stderr, "\n[esvio_fe trace] %s frames, host bookkeeping, ms/frame: left undistort + velocity=%.4f previous "
+              "frames' right tails=%.4f this frame's right tail=%.4f copies + profile + exchange=%.4f",
+              pub ? "published" : "unpublished", c->tail_ms[pub][0] / c->phase_count[pub],
+              c->tail_ms[pub][1] / c->phase_count[pub], c->tail_ms[pub][2] / c->phase_count[pub],
+              c->tail_ms[pub][3] / c->phase_count[pub]);
+  fprintf(stderr, "\n[esvio_fe trace] rejectWithF_event calls by point count: %llu with < 8 (skipped), %llu with "
+          "8..14 (LMedS, 300 hypotheses), %llu with >= 15 (RANSAC)", (unsigned long long)c->tr_fm_class[0],
+          (unsigned long long)c->tr_fm_class[1], (unsigned long long)c->tr_fm_class[2]);
+  if (c->tr_gpu_n)
+    fprintf(stderr, "\n[esvio_fe trace] device: k_select %.1f us; select end -> next frame's temporal LK done "
+            "%.1f us, -> chained one done %.1f us (its frame's pyramids: %.1f us); host: select launch -> "
+            "chained results read %.1f us",
+            1e3 * c->tr_gpu_sel / c->tr_gpu_n, 1e3 * c->tr_gpu_spec / c->tr_gpu_n,
+            1e3 * c->tr_gpu_chain / c->tr_gpu_n, 1e3 * c->tr_gpu_pyr / c->tr_gpu_n,
+            1e3 * c->tr_host_chain / c->tr_gpu_n);
+  fprintf(stderr, "\n[esvio_fe trace] chained temporal LK: %llu launched, %llu used, %llu cancelled",
+          (unsigned long long)c->tr_chain_launch, (unsigned long long)c->tr_chain_used,
+          (unsigned long long)c->tr_chain_cancel);
+  fprintf(stderr, "\n[esvio_fe trace] survivors/frame=%.1f; detect frames=%llu: candidates/frame=%.0f new/frame=%.1f\n",
+          (double)c->tr_surv / c->phase_frames, (unsigned long long)c->tr_detect,
+          c->tr_detect ? (double)c->tr_cand / c->tr_detect : 0.0,
+          c->tr_detect ? (double)c->tr_new / c->tr_detect : 0.0);
+}
+
 extern "C" {
 
 const char* esvio_fe_version(void) { return "esvio_fe 0.1 (gfx950)"; }
@@ -67,133 +118,17 @@ int esvio_fe_destroy(esvio_fe_handle c) {
   if (!c) return ESVIO_FE_EINVAL;
   (void)hipSetDevice(c->dev);
   (void)launcher_set(c, false);
-  if (c->stream3) (void)hipStreamSynchronize(c->stream3);
-  if (c->stream4) (void)hipStreamSynchronize(c->stream4);
-  if (c->stream6) (void)hipStreamSynchronize(c->stream6);
-  if (c->stream2) (void)hipStreamSynchronize(c->stream2);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
+  for (hipStream_t st : {(hipStream_t)c->stream3, (hipStream_t)c->stream4, (hipStream_t)c->stream6,
+                         (hipStream_t)c->stream2, (hipStream_t)c->stream})
+    if (st) (void)hipStreamSynchronize(st);
   host::ransac_pool_destroy(c->pool);
   c->pool = nullptr;
   stager_destroy(c);
-  if (c->trace && c->phase_frames) {
-    static const char* nm[8] = {"enqueue sae+ts+pyr", "enqueue temporal LK", "sync A", "host filter",
-                                "host ransac", "host mask + enqueue detect/stereo", "sync B", "host tail"};
-    for (int pub = 0; pub < 2; pub++) {
-      if (!c->phase_count[pub]) continue;
-      double tot = 0;
-      fprintf(stderr, "[esvio_fe trace] %llu %s frames, ms/frame:", (unsigned long long)c->phase_count[pub],
-              pub ? "published" : "unpublished");
-      for (int i = 0; i < 8; i++) {
-        fprintf(stderr, " %s=%.3f", nm[i], c->phase_ms[pub][i] / c->phase_count[pub]);
-        tot += c->phase_ms[pub][i] / c->phase_count[pub];
-      }
-      fprintf(stderr, " | total=%.3f\n", tot);
-    }
-    if (c->phase_count[1]) {
-      static const char* pn[6] = {"Event_setMask", "points + k_select launch", "speculative + chained LK launches",
-                                  "previous frame's right-camera tail", "stereo LK of new corners launch",
-                                  "next batch's prefetch launches"};
-      fprintf(stderr, "[esvio_fe trace] published frames, parts of 'host mask + enqueue', ms/frame:");
-      for (int i = 0; i < 6; i++) fprintf(stderr, " %s=%.3f", pn[i], c->pub_ms[i] / c->phase_count[1]);
-      fprintf(stderr, "\n");
-    }
-    fprintf(stderr, "[esvio_fe trace]");
-    fprintf(stderr, "\n[esvio_fe trace] findFundamentalMat alone: %.3f ms per published frame (slowest call %.3f ms, "
-            "%.3f without it); the two liftProjective batches before it: %.3f ms",
-            c->phase_count[1] ? c->tr_fm_ms / c->phase_count[1] : 0.0, c->tr_fm_max_ms,
-            c->phase_count[1] > 1 ? (c->tr_fm_ms - c->tr_fm_max_ms) / (c->phase_count[1] - 1) : 0.0,
-            c->phase_count[1] ? c->tr_lift_ms / c->phase_count[1] : 0.0);
-    for (int pub = 0; pub < 2; pub++)
-      if (c->phase_count[pub])
-        fprintf(stderr, "\n[esvio_fe trace] %s frames, host bookkeeping, ms/frame: left undistort + velocity=%.4f previous "
-                "frames' right tails=%.4f this frame's right tail=%.4f copies + profile + exchange=%.4f",
-                pub ? "published" : "unpublished", c->tail_ms[pub][0] / c->phase_count[pub],
-                c->tail_ms[pub][1] / c->phase_count[pub], c->tail_ms[pub][2] / c->phase_count[pub],
-                c->tail_ms[pub][3] / c->phase_count[pub]);
-    fprintf(stderr, "\n[esvio_fe trace] rejectWithF_event calls by point count: %llu with < 8 (skipped), %llu with "
-            "8..14 (LMedS, 300 hypotheses), %llu with >= 15 (RANSAC)", (unsigned long long)c->tr_fm_class[0],
-            (unsigned long long)c->tr_fm_class[1], (unsigned long long)c->tr_fm_class[2]);
-    if (c->tr_gpu_n)
-      fprintf(stderr, "\n[esvio_fe trace] device: k_select %.1f us; select end -> next frame's temporal LK done "
-              "%.1f us, -> chained one done %.1f us (its frame's pyramids: %.1f us); host: select launch -> "
-              "chained results read %.1f us",
-              1e3 * c->tr_gpu_sel / c->tr_gpu_n, 1e3 * c->tr_gpu_spec / c->tr_gpu_n,
-              1e3 * c->tr_gpu_chain / c->tr_gpu_n, 1e3 * c->tr_gpu_pyr / c->tr_gpu_n,
-              1e3 * c->tr_host_chain / c->tr_gpu_n);
-    fprintf(stderr, "\n[esvio_fe trace] chained temporal LK: %llu launched, %llu used, %llu cancelled",
-            (unsigned long long)c->tr_chain_launch, (unsigned long long)c->tr_chain_used,
-            (unsigned long long)c->tr_chain_cancel);
-    fprintf(stderr, "\n[esvio_fe trace] survivors/frame=%.1f; detect frames=%llu: candidates/frame=%.0f new/frame=%.1f\n",
-            (double)c->tr_surv / c->phase_frames, (unsigned long long)c->tr_detect,
-            c->tr_detect ? (double)c->tr_cand / c->tr_detect : 0.0,
-            c->tr_detect ? (double)c->tr_new / c->tr_detect : 0.0);
-  }
+  print_trace_summary(c);
   if (c->x_pending) (void)hipEventSynchronize(c->x_done);
-  if (c->x_comm)
+  if (c->x_comm)  // (before the stream it runs on)
     if (nccl_destroy_fn destroy = rccl_sym<nccl_destroy_fn>("ncclCommDestroy")) (void)destroy(c->x_comm);
-  if (c->x_stream) (void)hipStreamDestroy(c->x_stream);
-  if (c->x_done) (void)hipEventDestroy(c->x_done);
-  if (c->x_pin) (void)hipHostFree(c->x_pin);
-  if (c->x_pin_recv) (void)hipHostFree(c->x_pin_recv);
-  void* ptrs[] = {c->x_send, c->x_recv, c->d_part, c->d_warp, c->d_tile, c->L2s, c->S2s, c->slice_stage, c->L2, c->S2, c->d_ev, c->keys[0], c->keys[1], c->vals[0], c->vals[1], c->hist, c->sae_marks,
-                  c->d_rejected, c->d_res, c->d_ptsD, c->d_flags, c->d_pub_slots, c->d_pub_done, c->d_chain, c->d_lane_gate, c->d_gftt_cov, c->d_gftt_rowsum, c->d_gftt_eig, c->d_gftt_max,
-                  c->d_fast_m, c->d_fast_xy, c->d_fast_score, c->d_fast_cnt, c->d_fast_det, c->d_fast_grp, c->d_fast_cxy, c->d_fast_cscore, c->d_fast_tot, c->d_fast_img,
-                  c->d_mask_bits, c->d_sel_idx, c->d_sel_bitmap, c->d_eq_tmp,
-                  c->tmp_pyr[0].mem, c->tmp_pyr[1].mem, c->med_tmp[0].mem, c->med_tmp[1].mem, c->d_lut,
-                  c->d_minmax};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  for (auto& cs : c->cand)
-    for (void* p : {(void*)cs.xy, (void*)cs.idx, (void*)cs.cnt, (void*)cs.grp, (void*)cs.comp_xy, (void*)cs.comp_idx,
-                    (void*)cs.total})
-      if (p) (void)hipFree(p);
-  for (uint32_t* p : c->d_first)
-    if (p) (void)hipFree(p);
-  for (uint32_t* p : c->d_cmap)
-    if (p) (void)hipFree(p);
-  for (uint8_t* p : c->d_touched)
-    if (p) (void)hipFree(p);
-  for (PyrStore& ps : c->pyr)
-    if (ps.mem) (void)hipFree(ps.mem);
-  for (auto& rb : c->raw)
-    for (PyrStore& ps : rb)
-      if (ps.mem) (void)hipFree(ps.mem);
-  for (int i = 0; i < kPrefetchDepth; i++) {
-    if (c->d_evp[i]) (void)hipFree(c->d_evp[i]);
-    if (c->ev_lane_done[i]) (void)hipEventDestroy(c->ev_lane_done[i]);
-    if (c->ev_lane_arc[i]) (void)hipEventDestroy(c->ev_lane_arc[i]);
-  }
-  if (c->h_img) (void)hipHostFree(c->h_img);
-  if (c->d_img) (void)hipFree(c->d_img);
-  if (c->h_pin) (void)hipHostFree(c->h_pin);
-  if (c->h_spec) (void)hipHostFree(c->h_spec);
-  if (c->stream3) (void)hipStreamDestroy(c->stream3);
-  if (c->stream4) (void)hipStreamDestroy(c->stream4);
-  if (c->stream6) (void)hipStreamDestroy(c->stream6);
-  for (auto& r : c->pending) {
-    (void)hipEventDestroy(r.a);
-    (void)hipEventDestroy(r.b);
-  }
-  for (auto e : c->ev_pool) (void)hipEventDestroy(e);
-  if (c->stream2) {
-    (void)hipStreamSynchronize(c->stream2);
-    (void)hipStreamDestroy(c->stream2);
-  }
-  if (c->ev_planes_free) (void)hipEventDestroy(c->ev_planes_free);
-  if (c->ev_imgs_ready) (void)hipEventDestroy(c->ev_imgs_ready);
-  if (c->ev_arc_side) (void)hipEventDestroy(c->ev_arc_side);
-  if (c->ev_sae_left) (void)hipEventDestroy(c->ev_sae_left);
-  if (c->ev_right_ready) (void)hipEventDestroy(c->ev_right_ready);
-  if (c->ev_pts_ready) (void)hipEventDestroy(c->ev_pts_ready);
-  if (c->ev_spec_done) (void)hipEventDestroy(c->ev_spec_done);
-  if (c->ev_chain_done) (void)hipEventDestroy(c->ev_chain_done);
-  if (c->ev_dbg_sel_start) (void)hipEventDestroy(c->ev_dbg_sel_start);
-  if (c->ev_sel_host) (void)hipEventDestroy(c->ev_sel_host);
-  for (hipEvent_t e : c->ev_lks_done)
-    if (e) (void)hipEventDestroy(e);
-  if (c->ev_lknew_done) (void)hipEventDestroy(c->ev_lknew_done);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
+  delete c;  // (every buffer, event and stream: fe_res.h)
   return 0;
 }
 
@@ -251,39 +186,35 @@ int esvio_fe_create(const esvio_fe_config* cfg, esvio_fe_handle* out) {
   }
   int prio_least = 0, prio_greatest = 0;
   (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-  const bool streams_ok =
-      hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, prio_greatest) == hipSuccess &&
-      hipStreamCreateWithPriority(&c->stream2, hipStreamNonBlocking, prio_least) == hipSuccess &&
-      hipStreamCreateWithPriority(&c->stream3, hipStreamNonBlocking, prio_greatest) == hipSuccess &&
-      hipStreamCreateWithPriority(&c->stream4, hipStreamNonBlocking, prio_least) == hipSuccess;
-  if (!streams_ok ||
-      hipEventCreateWithFlags(&c->ev_pts_ready, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_spec_done, c->trace ? 0 : hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_chain_done, c->trace ? 0 : hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_dbg_sel_start, 0) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_sel_host, c->trace ? 0 : hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_lks_done[0], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_lks_done[1], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_lknew_done, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_planes_free, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_imgs_ready, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_arc_side, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_sae_left, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_right_ready, hipEventDisableTiming) != hipSuccess)
+  if (c->stream.create(hipStreamNonBlocking, prio_greatest) != hipSuccess ||
+      c->stream2.create(hipStreamNonBlocking, prio_least) != hipSuccess ||
+      c->stream3.create(hipStreamNonBlocking, prio_greatest) != hipSuccess ||
+      c->stream4.create(hipStreamNonBlocking, prio_least) != hipSuccess)
     return bail(ESVIO_FE_EHIP);
-  for (int i = 0; i < kPrefetchDepth; i++)
-    if (hipEventCreateWithFlags(&c->ev_lane_done[i], c->trace ? 0 : hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_lane_arc[i], hipEventDisableTiming) != hipSuccess)
-      return bail(ESVIO_FE_EHIP);
+  {
+    const unsigned timed = c->trace ? 0 : hipEventDisableTiming;  // (the trace reads intervals off these)
+    const std::pair<Event*, unsigned> evs[] = {
+        {&c->ev_pts_ready, hipEventDisableTiming},  {&c->ev_spec_done, timed},
+        {&c->ev_chain_done, timed},                 {&c->ev_dbg_sel_start, 0},
+        {&c->ev_sel_host, timed},                   {&c->ev_lks_done[0], hipEventDisableTiming},
+        {&c->ev_lks_done[1], hipEventDisableTiming}, {&c->ev_lknew_done, hipEventDisableTiming},
+        {&c->ev_planes_free, hipEventDisableTiming}, {&c->ev_imgs_ready, hipEventDisableTiming},
+        {&c->ev_arc_side, hipEventDisableTiming},   {&c->ev_sae_left, hipEventDisableTiming},
+        {&c->ev_right_ready, hipEventDisableTiming}};
+    for (const auto& ef : evs)
+      if (ef.first->create(ef.second) != hipSuccess) return bail(ESVIO_FE_EHIP);
+    for (int i = 0; i < kPrefetchDepth; i++)
+      if (c->ev_lane_done[i].create(timed) != hipSuccess || c->ev_lane_arc[i].create() != hipSuccess)
+        return bail(ESVIO_FE_EHIP);
+  }
   const size_t M = cfg->max_cnt;
   int rc = 0;
-  if ((rc = dev_alloc(c, &c->L2, (size_t)2 * c->P))) return bail(rc);
-  if ((rc = dev_alloc(c, &c->S2, (size_t)2 * c->P))) return bail(rc);
-  if ((rc = dev_alloc(c, &c->d_rejected, 1))) return bail(rc);
+  if ((rc = c->L2.alloc(c, (size_t)2 * c->P))) return bail(rc);
+  if ((rc = c->S2.alloc(c, (size_t)2 * c->P))) return bail(rc);
+  if ((rc = c->d_rejected.alloc(c, 1))) return bail(rc);
   {
     const ResLayout L = res_layout(M);
-    c->res_bytes = L.total;
-    if ((rc = dev_alloc(c, &c->d_res, c->res_bytes))) return bail(rc);
+    if ((rc = c->d_res.alloc(c, L.total))) return bail(rc);
     c->d_ptsB = (float2*)(c->d_res + L.B1[0]);
     c->d_ptsC = (float2*)(c->d_res + L.C1[0]);
     c->d_stA = c->d_res + L.SA1[0];
@@ -296,13 +227,12 @@ int esvio_fe_create(const esvio_fe_config* cfg, esvio_fe_handle* out) {
     c->spec_bytes = std::max<size_t>(M, 1) * 16 + 2 * stM + 64;  // results + the wait-expired flag
     c->spec_bytes = (c->spec_bytes + 255) / 256 * 256;
     // (twice: the speculative launch's block, then the chained launch's)
-    if (hipHostMalloc((void**)&c->h_spec, 2 * c->spec_bytes, hipHostMallocDefault) != hipSuccess ||
-        hipHostGetDevicePointer((void**)&c->z_spec, c->h_spec, 0) != hipSuccess)
-      return bail(ESVIO_FE_EHIP);
+    if ((rc = c->h_spec.alloc(c, 2 * c->spec_bytes))) return bail(rc);
+    if (hipHostGetDevicePointer((void**)&c->z_spec, c->h_spec, 0) != hipSuccess) return bail(ESVIO_FE_EHIP);
     std::memset(c->h_spec, 0, 2 * c->spec_bytes);
   }
-  if ((rc = dev_alloc(c, &c->d_chain, 2 * std::max<size_t>(M, 1)))) return bail(rc);
-  if ((rc = dev_alloc(c, &c->d_lane_gate, 16))) return bail(rc);
+  if ((rc = c->d_chain.alloc(c, 2 * std::max<size_t>(M, 1)))) return bail(rc);
+  if ((rc = c->d_lane_gate.alloc(c, 16))) return bail(rc);
   c->stage_threads = stager_threads_from_env();
   if (const char* v = getenv("ESVIO_FE_FAULT")) esvio_fe_debug_inject(c, atoi(v));
   if (const char* e = getenv("ESVIO_FE_STEREO_SPLIT")) c->stereo_split_env = atoi(e) != 0;  // (else: fe_track.cpp decides)
@@ -316,25 +246,25 @@ int esvio_fe_create(const esvio_fe_config* cfg, esvio_fe_handle* out) {
   if (const char* v = getenv("ESVIO_FE_SAE_EV_MIN")) c->sae_ev_min = (size_t)strtoull(v, nullptr, 10);
   c->tiled = make_tile_geom(c->W, c->H, &c->tgeom) && getenv("ESVIO_FE_SAE_SORT") == nullptr;
   for (int i = 0; i < kRightSlots; i++)
-    if ((rc = dev_alloc(c, &c->d_first[i], (size_t)c->P))) return bail(rc);
+    if ((rc = c->d_first[i].alloc(c, (size_t)c->P))) return bail(rc);
   for (int i = 0; i < kRightSlots; i++) {
     const size_t words = arc_bitmap_words(c->W, c->H);
-    if ((rc = dev_alloc(c, &c->d_cmap[i], words))) return bail(rc);
-    if ((rc = dev_alloc(c, &c->d_touched[i], arc_flag_bytes(c->W, c->H)))) return bail(rc);
+    if ((rc = c->d_cmap[i].alloc(c, words))) return bail(rc);
+    if ((rc = c->d_touched[i].alloc(c, arc_flag_bytes(c->W, c->H)))) return bail(rc);
     if (hipMemsetAsync(c->d_cmap[i], 0, words * 4, cur_stream(c)) != hipSuccess ||
         hipMemsetAsync(c->d_touched[i], 0, arc_flag_bytes(c->W, c->H), cur_stream(c)) != hipSuccess)
       return bail(ESVIO_FE_EHIP);
   }
-  if ((rc = dev_alloc(c, &c->d_pub_slots, std::max<size_t>(M, 1)))) return bail(rc);
-  if ((rc = dev_alloc(c, &c->d_pub_done, 1))) return bail(rc);
+  if ((rc = c->d_pub_slots.alloc(c, std::max<size_t>(M, 1)))) return bail(rc);
+  if ((rc = c->d_pub_done.alloc(c, 1))) return bail(rc);
   if (hipMemsetAsync(c->d_lane_gate, 0, 64, cur_stream(c)) != hipSuccess ||
       hipMemsetAsync(c->d_chain, 0, std::max<size_t>(M, 1) * 16, cur_stream(c)) != hipSuccess ||
       hipMemsetAsync(c->d_pub_slots, 0, std::max<size_t>(M, 1) * 8, cur_stream(c)) != hipSuccess ||
       hipMemsetAsync(c->d_pub_done, 0, 8, cur_stream(c)) != hipSuccess)
     return bail(ESVIO_FE_EHIP);
-  if ((rc = dev_alloc(c, &c->d_ptsD, M))) return bail(rc);
-  if ((rc = dev_alloc(c, &c->d_sel_idx, M))) return bail(rc);
-  if ((rc = dev_alloc(c, &c->d_mask_bits, (size_t)c->H * ((c->W + 31) / 32)))) return bail(rc);
+  if ((rc = c->d_ptsD.alloc(c, M))) return bail(rc);
+  if ((rc = c->d_sel_idx.alloc(c, M))) return bail(rc);
+  if ((rc = c->d_mask_bits.alloc(c, (size_t)c->H * ((c->W + 31) / 32)))) return bail(rc);
   for (PyrStore& ps : c->pyr)
     if ((rc = pyr_alloc(c, ps, c->W, c->H, 3))) return bail(rc);
   if (cfg->median_blur_kernel_size > 0)
@@ -344,18 +274,16 @@ int esvio_fe_create(const esvio_fe_config* cfg, esvio_fe_handle* out) {
     for (auto& rb : c->raw)
       for (PyrStore& ps : rb)
         if ((rc = pyr_alloc(c, ps, c->W, c->H, 0))) return bail(rc);
-    if ((rc = dev_alloc(c, &c->d_lut, (size_t)2 * 64 * 256))) return bail(rc);
+    if ((rc = c->d_lut.alloc(c, (size_t)2 * 64 * 256))) return bail(rc);
     // (CLAHE scratch: d_lut, d_minmax and d_eq_tmp are single buffers shared by the main stream and the
     // prefetch stream; rendering on one is ordered behind the other's through ev_planes_free /
     // ev_lane_done, like the SAE planes they are derived from)
-    if ((rc = dev_alloc(c, &c->d_eq_tmp, (size_t)2 * c->P))) return bail(rc);
-    if ((rc = dev_alloc(c, &c->d_minmax, 4))) return bail(rc);
+    if ((rc = c->d_eq_tmp.alloc(c, (size_t)2 * c->P))) return bail(rc);
+    if ((rc = c->d_minmax.alloc(c, 4))) return bail(rc);
   }
-  c->h_pin_bytes = pin_bytes(*cfg);
-  if (hipHostMalloc((void**)&c->h_pin, c->h_pin_bytes, hipHostMallocDefault) != hipSuccess ||
-      hipHostGetDevicePointer((void**)&c->z_res, c->h_pin, 0) != hipSuccess)
-    return bail(ESVIO_FE_EHIP);
-  std::memset(c->h_pin, 0, c->h_pin_bytes);
+  if ((rc = c->h_pin.alloc(c, pin_bytes(*cfg)))) return bail(rc);
+  if (hipHostGetDevicePointer((void**)&c->z_res, c->h_pin, 0) != hipSuccess) return bail(ESVIO_FE_EHIP);
+  std::memset(c->h_pin, 0, c->h_pin.cap);
   {
     const ResLayout L = res_layout(std::max<size_t>(M, 1));
     c->z_counts = (int*)(c->z_res + L.CNT);
@@ -374,9 +302,10 @@ int esvio_fe_create(const esvio_fe_config* cfg, esvio_fe_handle* out) {
   // One kernel of this library on every stream, now: the runtime loads the code object with the first
   // launch from it and creates a stream's hardware queue with the stream's first use — 2.0-2.4 ms that
   // would otherwise sit inside the first esvio_fe_track_event call (profiles/r04_stall_forensics.md).
-  for (hipStream_t st : {c->stream, c->stream2, c->stream3, c->stream4}) {
-    launch_fill_f64(st, (double*)c->d_rejected, 1, 0.0);
-    if (hipStreamSynchronize(st) != hipSuccess) return bail(ESVIO_FE_EHIP);
+  const hipStream_t st[4] = {c->stream, c->stream2, c->stream3, c->stream4};
+  for (hipStream_t s : st) {
+    launch_fill_f64(s, (double*)c->d_rejected, 1, 0.0);
+    if (hipStreamSynchronize(s) != hipSuccess) return bail(ESVIO_FE_EHIP);
   }
   // ... and a burst of launches chained across the streams by events, nothing of it awaited until the end.  What it
   // is for: in one cold bench process of ten ONE track call around frame 20 of the first timed pass took 1.6-4.7 ms,
@@ -386,18 +315,15 @@ int esvio_fe_create(const esvio_fe_config* cfg, esvio_fe_handle* out) {
   // ~25 cross-stream waits in flight, this puts 4 x 96 launches and as many waits in flight at once — and 30 cold
   // processes then ran without one call above 0.6 ms (profiles/r05_stall_hunt_after.txt).
   {
-    const hipStream_t st[4] = {c->stream, c->stream2, c->stream3, c->stream4};
-    hipEvent_t ev[4] = {};  // (events of the warm-up's own: the handle's stay unrecorded until a frame records them)
+    Event ev[4];  // (events of the warm-up's own: the handle's stay unrecorded until a frame records them)
     bool ok = true;
-    for (int i = 0; i < 4; i++) ok = ok && hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) == hipSuccess;
+    for (int i = 0; i < 4; i++) ok = ok && ev[i].create() == hipSuccess;
     for (int r = 0; ok && r < 96; r++)
       for (int i = 0; ok && i < 4; i++) {
         launch_spin(st[i], r == 0 ? 20000 : 0);  // (the first round's kernels hold everything behind them for 200 us)
         ok = hipEventRecord(ev[i], st[i]) == hipSuccess && hipStreamWaitEvent(st[(i + 1) & 3], ev[i], 0) == hipSuccess;
       }
     for (int i = 0; i < 4; i++) ok = (hipStreamSynchronize(st[i]) == hipSuccess) && ok;
-    for (int i = 0; i < 4; i++)
-      if (ev[i]) (void)hipEventDestroy(ev[i]);
     if (!ok) return bail(ESVIO_FE_EHIP);
   }
   if ((rc = stereo_split_prepare(c))) return bail(rc);  // (ESVIO_FE_STEREO_SPLIT=1)
@@ -453,7 +379,7 @@ int esvio_fe_reset(esvio_fe_handle c) {
   c->cur_stage = -1;
   // (a call that failed with ESVIO_FE_EINTERNAL: the expired wait's flag, the sort's scratch words)
   pin_of(c).counts[3] = 0;
-  if (c->hist) HIPCHK(c, hipMemsetAsync(c->hist, 0, c->hist_cap * 4, cur_stream(c)));
+  if (c->hist) HIPCHK(c, hipMemsetAsync(c->hist, 0, c->hist.cap * 4, cur_stream(c)));
   std::memset(c->h_spec, 0, 2 * c->spec_bytes);
   c->spec_valid = false;
   c->chain_valid = false;
@@ -513,10 +439,9 @@ int esvio_fe_create_sae_stereo_mc(esvio_fe_handle c, const esvio_fe_event* left,
 // ---- one stream time-sliced across GPUs -----------------------------------------
 namespace {
 int slice_scratch(esvio_fe_ctx* c) {
-  if (c->L2s) return 0;
-  if (int rc = dev_alloc(c, &c->L2s, (size_t)2 * c->P)) return rc;
-  if (int rc = dev_alloc(c, &c->S2s, (size_t)2 * c->P)) return rc;
-  return 0;
+  if (c->S2s) return 0;  // (the second of the two: both are there)
+  if (int rc = c->L2s.alloc(c, (size_t)2 * c->P)) return rc;
+  return c->S2s.alloc(c, (size_t)2 * c->P);
 }
 // device address of `k` consecutive plane sets given in `space` (host ones are staged)
 int slice_planes_in(esvio_fe_ctx* c, const double* p, size_t sets, int space, const double** dev) {
@@ -526,13 +451,8 @@ int slice_planes_in(esvio_fe_ctx* c, const double* p, size_t sets, int space, co
     return 0;
   }
   if (space != ESVIO_FE_HOST) return fail(c, ESVIO_FE_EINVAL, "bad memory space %d", space);
-  if (nd > c->slice_stage_doubles) {
-    if (c->slice_stage) (void)hipFree(c->slice_stage);
-    c->slice_stage = nullptr;
-    c->slice_stage_doubles = 0;
-    if (int rc = dev_alloc(c, &c->slice_stage, nd)) return rc;
-    c->slice_stage_doubles = nd;
-  }
+  if (nd > c->slice_stage.cap)
+    if (int rc = c->slice_stage.alloc(c, nd)) return rc;
   HIPCHK(c, hipMemcpyAsync(c->slice_stage, p, nd * 8, hipMemcpyHostToDevice, cur_stream(c)));
   *dev = c->slice_stage;
   return 0;
@@ -1075,7 +995,7 @@ int esvio_fe_fast_corners(esvio_fe_handle c, int cam, const uint8_t* img, int sp
   } else if (space == ESVIO_FE_HOST) {
     const size_t bytes = (size_t)c->W * c->H;
     if (!c->d_fast_img)
-      if (int rc = dev_alloc(c, &c->d_fast_img, bytes)) return rc;
+      if (int rc = c->d_fast_img.alloc(c, bytes)) return rc;
     HIPCHK(c, hipMemcpyAsync(c->d_fast_img, img, bytes, hipMemcpyHostToDevice, cur_stream(c)));
     src = c->d_fast_img;
   }
@@ -1154,7 +1074,7 @@ int esvio_fe_exchange_tracks(esvio_fe_handle c, void* nccl_comm, int world, floa
   // communicator: whatever that one still has packed or in flight goes first and is waited for
   if (int rc = exchange_flush(c)) return rc;
   if (c->x_pending) HIPCHK(c, hipEventSynchronize(c->x_done));
-  if (c->x_pending && (size_t)world * cnt > c->x_recv_cap)
+  if (c->x_pending && (size_t)world * cnt > c->x_pin_recv.cap)
     c->x_pending = false;  // (its gathered block is dropped with the buffer that is about to grow)
   if (int rc = exchange_buffers(c, world)) return rc;
   if (int rc = esvio_fe_pack_track_records(c, c->x_pin, nullptr)) return rc;
@@ -1190,9 +1110,9 @@ int esvio_fe_comm_init(esvio_fe_handle c, const uint8_t id[128], int rank, int w
   if (nrc != 0 || !comm) return fail(c, ESVIO_FE_EHIP, "ncclCommInitRank failed: %d", nrc);
   c->x_comm = comm;
   c->x_world = world;
-  if (!c->x_stream) {
-    HIPCHK(c, hipStreamCreateWithFlags(&c->x_stream, hipStreamNonBlocking));
-    HIPCHK(c, hipEventCreateWithFlags(&c->x_done, hipEventDisableTiming));
+  if (!c->x_done) {  // (the second of the two)
+    if (!c->x_stream) HIPCHK(c, c->x_stream.create());
+    HIPCHK(c, c->x_done.create());
   }
   return exchange_buffers(c, world);
 }
@@ -1429,13 +1349,8 @@ int esvio_fe_reserve(esvio_fe_handle c, size_t max_left, size_t max_right, int h
       if (int rc = stager_reserve(c, n)) return rc;
     } else {
       for (int lane = 0; lane < kPrefetchDepth; lane++)
-        if (n > c->evp_cap[lane]) {
-          if (c->d_evp[lane]) (void)hipFree(c->d_evp[lane]);
-          c->d_evp[lane] = nullptr;
-          c->evp_cap[lane] = 0;
-          if (int rc = dev_alloc(c, &c->d_evp[lane], n + n / 4)) return rc;
-          c->evp_cap[lane] = n + n / 4;
-        }
+        if (n > c->d_evp[lane].cap)
+          if (int rc = c->d_evp[lane].alloc(c, n + n / 4)) return rc;
     }
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));

@@ -30,6 +30,7 @@
 #include "fe_host.h"
 #include "fe_kernels.h"
 #include "fe_mc.h"
+#include "fe_res.h"
 
 using namespace esvio;
 
@@ -79,7 +80,7 @@ struct KStat {
 
 struct ProfRec {
   int id;
-  hipEvent_t a, b;
+  Event a, b;
   uint64_t bytes;
 };
 
@@ -125,8 +126,7 @@ constexpr int kRightSlots = 1 + kPrefetchDepth;  // cur, prefetched...
 
 struct PyrStore {
   PyrDesc d{};
-  void* mem = nullptr;
-  size_t bytes = 0;
+  DevBuf<uint8_t> mem;
   int w = 0, h = 0, max_level = -1;
 };
 
@@ -134,15 +134,20 @@ struct PyrStore {
 }  // namespace esvio
 using namespace esvio::fe;
 
+// Every device buffer, pinned block, event and stream below is a member that releases itself (fe_res.h).  The
+// members' destruction order — the reverse of their declaration — carries no dependency: esvio_fe_destroy deletes the
+// handle only after its threads have stopped and every stream is idle, and the one step that has an order (the
+// RCCL communicator before the stream it runs on) is written out there.  Pointers INTO a block (d_ptsA...d_counts
+// into d_res, z_* into h_pin / h_spec) stay raw: only the block is owned.
 struct esvio_fe_ctx {
   esvio_fe_config cfg{};
   int dev = 0;
-  hipStream_t stream = nullptr;   // main stream
-  hipStream_t stream2 = nullptr;  // prefetch stream (next batch's SAE update / images)
-  hipStream_t stream3 = nullptr;  // speculative temporal LK of the next frame
+  Stream stream;   // main stream
+  Stream stream2;  // prefetch stream (next batch's SAE update / images)
+  Stream stream3;  // speculative temporal LK of the next frame
   // stereo LK of the temporal survivors: nothing on the frame's chain reads its results before the
   // right-camera tail, and on the main stream it would hold up the corner selection behind it
-  hipStream_t stream4 = nullptr;
+  Stream stream4;
   // ... of an UNPUBLISHED frame (stereo_stream() below).  The chained temporal LK of the frame after next sits on
   // stream4 from the published call that launched it until its last point is done; the unpublished frame's stereo
   // LK queued behind it, the next published frame's behind that, and the published call waited 35-45 us for its
@@ -150,7 +155,7 @@ struct esvio_fe_ctx {
   // of its own both waits are gone — cycle 272 -> 246 us in the trace, 0.131 -> 0.119 ms/step.  (WHICH launches
   // share a stream matters more than how many streams there are: the published frame's stereo LK and the chained
   // launch on the new stream instead — `k_select_mw` 17 -> 40 us, cycle 300 us; KERNELS.md.)
-  hipStream_t stream6 = nullptr;
+  Stream stream6;
   std::vector<double> pre_lx, pre_ly;  // prev_pts lifted through the left camera model under the temporal LK's wait
   bool pre_lift_valid = false;
   bool stereo_unpub = false;  // the frame being tracked publishes nothing (and stereo_split is on)
@@ -158,15 +163,15 @@ struct esvio_fe_ctx {
   int stereo_split_env = -1;
   bool stereo_split = false;
   int n_queue_conflicts = 0;  // pairs of the handle's streams found on one hardware queue (ESVIO_FE_QUEUE_PROBE)
-  hipEvent_t ev_planes_free = nullptr;
+  Event ev_planes_free;
   // a plain (not announced) call: the frame's images are built (main stream) -> its Arc* pass on the
   // prefetch stream and its stereo LK on stream4 start beside the temporal LK; the Arc* pass is done
-  hipEvent_t ev_imgs_ready = nullptr, ev_arc_side = nullptr;
+  Event ev_imgs_ready, ev_arc_side;
   // ... split by camera: the left camera's update + image on the main stream (ev_imgs_ready: the LEFT image
   // then), the right camera's behind it on the stereo stream — behind ev_sae_left (the one partition
   // scratch) and, for a batch in pageable memory, behind the right array's own DMA; ev_right_ready: done
-  hipEvent_t ev_sae_left = nullptr, ev_right_ready = nullptr;
-  hipEvent_t ev_pts_ready = nullptr, ev_spec_done = nullptr, ev_sel_host = nullptr;
+  Event ev_sae_left, ev_right_ready;
+  Event ev_pts_ready, ev_spec_done, ev_sel_host;
   std::string err;
   int W = 0, H = 0;
   uint32_t P = 0;
@@ -175,24 +180,21 @@ struct esvio_fe_ctx {
   std::vector<int> hw;  // disc half-widths for min_dist
 
   // ---- device state
-  double2* L2 = nullptr;  // [2P] {L[0],L[1]} per (cam,pixel)
-  double2* S2 = nullptr;  // [2P] {S[0],S[1]}
-  EventRec* d_ev = nullptr;
-  size_t ev_cap = 0;
-  uint32_t *keys[2] = {nullptr, nullptr}, *vals[2] = {nullptr, nullptr}, *hist = nullptr;
-  size_t sort_cap = 0, hist_cap = 0;
+  DevBuf<double2> L2;  // [2P] {L[0],L[1]} per (cam,pixel)
+  DevBuf<double2> S2;  // [2P] {S[0],S[1]}
+  DevBuf<EventRec> d_ev;
+  DevBuf<uint32_t> keys[2], vals[2], hist;
+  size_t sort_cap = 0;  // of keys, vals and sae_marks (ensure_sort_capacity)
   size_t sae_ev_min = (size_t)1 << 20;  // batches of at least this many events: k_sae_apply_ev
   // tiled SAE update (default; ESVIO_FE_SAE_SORT=1 or a sensor too large for one digit: the radix
   // sort form above)
   bool tiled = false;
   TileGeom tgeom{};
-  EventRec* d_part = nullptr;  // the batch's events partitioned by bucket
-  uint32_t* d_warp = nullptr;  // [part_cap] motion compensation: the pixel each event is warped to
-  size_t part_cap = 0;
-  uint32_t* d_tile = nullptr;  // TileScratch
-  size_t tile_cap = 0;
-  uint8_t* sae_marks = nullptr;         // [sort_cap] its per-event "stores L / stores S" marks
-  unsigned long long* d_rejected = nullptr;
+  DevBuf<EventRec> d_part;  // the batch's events partitioned by bucket
+  DevBuf<uint32_t> d_warp;  // [d_part.cap] motion compensation: the pixel each event is warped to
+  DevBuf<uint32_t> d_tile;  // TileScratch
+  DevBuf<uint8_t> sae_marks;         // [sort_cap] its per-event "stores L / stores S" marks
+  DevBuf<unsigned long long> d_rejected;
   // left: slots 0..kLeftSlots-1 rotate (prev, cur, up to kPrefetchDepth being prefetched);
   // right: the kRightSlots after them (cur + prefetched)
   PyrStore pyr[kLeftSlots + kRightSlots];
@@ -201,19 +203,18 @@ struct esvio_fe_ctx {
   bool ext_right_pending = false;  // esvio_fe_import_image(cam=1) done for the next frame
   // time-sliced stream (esvio_fe_sae_slice_*): scratch planes a slice is applied to, and the one-shot
   // "the planes already hold the next frame's batch" set by esvio_fe_sae_slice_commit
-  double2 *L2s = nullptr, *S2s = nullptr;
-  double* slice_stage = nullptr;  // device staging for host-side slice planes
-  size_t slice_stage_doubles = 0;
+  DevBuf<double2> L2s, S2s;
+  DevBuf<double> slice_stage;  // device staging for host-side slice planes
   bool ext_sae_pending = false;
   // esvio_fe_exchange_tracks: send / receive buffers of the all-gather and the pinned pack area
-  float *x_send = nullptr, *x_recv = nullptr, *x_pin = nullptr, *x_pin_recv = nullptr;
-  size_t x_recv_cap = 0;
+  DevBuf<float> x_send, x_recv;
+  PinBuf<float> x_pin, x_pin_recv;
   // esvio_fe_comm_init: the handle's own RCCL communicator, the side stream the asynchronous
   // exchange runs on and the event that marks its end
   void* x_comm = nullptr;
   int x_world = 0;
-  hipStream_t x_stream = nullptr;
-  hipEvent_t x_done = nullptr;
+  Stream x_stream;
+  Event x_done;
   bool x_pending = false;
   bool x_auto = false;      // esvio_fe_set_auto_exchange: every published frame's records are exchanged
   bool x_deferred = false;  // packed records waiting to be enqueued (by the next call, under its device wait)
@@ -242,21 +243,20 @@ struct esvio_fe_ctx {
   } lim;
   bool lazy_late = false;  // ESVIO_FE_FAULT_LAZY_LATE (test): the lazy completions always at their latest point
   uint64_t n_spec_expired = 0, n_chain_expired = 0;  // speculative / chained temporal LK launches redone
-  EventRec* d_evp[kPrefetchDepth] = {};  // host-event staging, one per prefetch lane (stager off)
-  size_t evp_cap[kPrefetchDepth] = {};
-  hipEvent_t ev_lane_done[kPrefetchDepth] = {}, ev_lane_arc[kPrefetchDepth] = {};
+  DevBuf<EventRec> d_evp[kPrefetchDepth];  // host-event staging, one per prefetch lane (stager off)
+  Event ev_lane_done[kPrefetchDepth], ev_lane_arc[kPrefetchDepth];
   PyrStore tmp_pyr[2];  // standalone LK / pyramid taps on arbitrary host images
   PyrStore med_tmp[2];  // median_blur_kernel_size > 0: the surfaces before cv::medianBlur
   // equalize: raw time surfaces (single padded level each, left/right) + CLAHE scratch
   PyrStore raw[kRightSlots][2];  // [buffer][cam], rotating like the right pyramids
   int raw_cur = 0;
-  uint8_t* d_lut = nullptr;
-  int* d_minmax = nullptr;
+  DevBuf<uint8_t> d_lut;
+  DevBuf<int> d_minmax;
   // device-side point / status buffers of the standalone entry points (LK, featuresToTrack) and the
   // selection counters; one allocation with the layout of ResLayout
-  uint8_t* d_res = nullptr;
-  size_t res_bytes = 0;
-  float2 *d_ptsA = nullptr, *d_ptsB = nullptr, *d_ptsC = nullptr, *d_ptsD = nullptr;
+  DevBuf<uint8_t> d_res;
+  DevBuf<float2> d_ptsD;
+  float2 *d_ptsA = nullptr, *d_ptsB = nullptr, *d_ptsC = nullptr;
   uint8_t *d_stA = nullptr, *d_stB = nullptr;
   int* d_counts = nullptr;  // [0]=n_out (select) [1]=n_total (kept + new: the LK kernels' n_ptr)
   // The per-frame path works on the pinned host block itself (device-visible): the LK kernels read
@@ -274,7 +274,7 @@ struct esvio_fe_ctx {
   // ---- speculative temporal LK of the next frame (replay mode): once this frame's kept points
   // and new corners are final, next frame's calcOpticalFlowPyrLK(cur -> next) pair is launched on
   // stream3 against the prefetched pyramids, so it overlaps this frame's stereo LK and host tail
-  uint8_t* h_spec = nullptr;  // pinned, device-visible: [ptsB | ptsC | stA | stB] of that launch
+  PinBuf<uint8_t> h_spec;  // pinned, device-visible: [ptsB | ptsC | stA | stB] of that launch
   size_t spec_bytes = 0;
   bool spec_valid = false;
   int spec_n = 0;             // number of points of that launch (= the next frame's prev_pts.size())
@@ -284,9 +284,9 @@ struct esvio_fe_ctx {
   // producer's wave of the same index publishes its forward result (LkArgs::chain_*).  Results:
   // second half of h_spec, indexed like the producer's points; the intermediate frame's temporal
   // filter gives the map from the final frame's prev_pts to those indices.
-  unsigned long long* d_chain = nullptr;  // [2 * max_cnt] published forward results
+  DevBuf<unsigned long long> d_chain;  // [2 * max_cnt] published forward results
   // one word per prefetch lane: the serial number of the last prefetch sequence that has RUN there (LkArgs::gate_*)
-  uint32_t* d_lane_gate = nullptr;
+  DevBuf<uint32_t> d_lane_gate;
   uint32_t gate_seq = 0;
   // LK launches whose waves WAIT on the device for another kernel's results (the speculative temporal launch for
   // k_select's corners, a chained launch for its producer's points) hold their CU while they wait — in the float-order
@@ -306,10 +306,10 @@ struct esvio_fe_ctx {
   bool chain_map_ok = false;
   std::vector<int> chain_map;  // final frame's prev_pts[j] = producer point chain_map[j]
   uint64_t frame_no = 0;       // trackEvent calls so far
-  hipEvent_t ev_chain_done = nullptr;
+  Event ev_chain_done;
   // k_select publishes each new corner as it accepts it; the speculative launch, already resident,
   // picks them up one by one instead of starting after the whole selection
-  unsigned long long *d_pub_slots = nullptr, *d_pub_done = nullptr;
+  DevBuf<unsigned long long> d_pub_slots, d_pub_done;
   uint32_t pub_seq = 0;
   // ---- lazy stereo of new corners (esvio_fe_set_lazy_new_stereo): a published frame returns
   // without waiting for the stereo LK of the corners it has just detected; their right-camera
@@ -331,49 +331,46 @@ struct esvio_fe_ctx {
     std::vector<int> ids;       // the frame's ids / left points (no new corners: nothing published)
     std::vector<P2f> left;
   } pend_right;
-  hipEvent_t ev_lks_done[2] = {nullptr, nullptr}, ev_lknew_done = nullptr;
+  Event ev_lks_done[2], ev_lknew_done;
   host::RansacPool* pool = nullptr;  // esvio_fe_set_host_threads
   // arc / select
-  uint8_t* d_flags = nullptr;
+  DevBuf<uint8_t> d_flags;
   // per-block ordered candidate lists written by k_arc; two sets so that the Arc* of a prefetched
   // batch (prefetch stream) never overwrites the set the current frame's selection still reads
   struct CandSet {
-    uint32_t *xy = nullptr, *idx = nullptr, *cnt = nullptr;
+    DevBuf<uint32_t> xy, idx, cnt;
     // ... and their ordered compaction into one stream (k_compact, launched right behind k_arc)
-    uint32_t *comp_xy = nullptr, *comp_idx = nullptr, *total = nullptr, *grp = nullptr;
-    size_t cap = 0;
+    DevBuf<uint32_t> comp_xy, comp_idx, total, grp;
+    size_t cap = 0;  // of the set (grow_cand_set)
   } cand[kRightSlots];
   // per-pixel earliest candidate of a set's latest Arc* pass (ArcArgs::first_map / launch_dedup)
-  uint32_t* d_first[kRightSlots] = {};
+  DevBuf<uint32_t> d_first[kRightSlots];
   // per-pixel, per-polarity result of the event-independent part of isCorner (k_arc_map), one map
   // per candidate set
-  uint32_t* d_cmap[kRightSlots] = {};
-  uint8_t* d_touched[kRightSlots] = {};  // (pixel, polarity) pairs a batch's left events hit
+  DevBuf<uint32_t> d_cmap[kRightSlots];
+  DevBuf<uint8_t> d_touched[kRightSlots];  // (pixel, polarity) pairs a batch's left events hit
   uint32_t first_epoch[kRightSlots] = {};  // Arc* passes into the set so far
   bool dedup_enabled = true;               // (ESVIO_FE_NO_DEDUP=1, test-only: the path batches >= 2^20 events take)
   bool fuse_ts_pyr = true;                 // (ESVIO_FE_NO_FUSE=1, test-only: k_time_surface + 3 x k_pyr_down, the median / equalize path)
   int cand_cur = 0;
-  size_t arc_cap = 0;
-  uint32_t* d_mask_bits = nullptr;
+  DevBuf<uint32_t> d_mask_bits;
   // goodFeaturesToTrack scratch (image front-end), allocated on first use
-  float4 *d_gftt_cov = nullptr, *d_gftt_rowsum = nullptr;
-  float* d_gftt_eig = nullptr;
-  uint32_t* d_gftt_max = nullptr;
-  int32_t* d_sel_idx = nullptr;
+  DevBuf<float4> d_gftt_cov, d_gftt_rowsum;
+  DevBuf<float> d_gftt_eig;
+  DevBuf<uint32_t> d_gftt_max;
+  DevBuf<int32_t> d_sel_idx;
   // esvio_fe_fast_corners scratch, allocated on first use: the score map, the per-block lists, their
   // counts (+ k_compact's group sums), the compacted list and {total, detected before non-max}
-  uint8_t* d_fast_m = nullptr;
-  uint32_t *d_fast_xy = nullptr, *d_fast_score = nullptr, *d_fast_cnt = nullptr, *d_fast_det = nullptr, *d_fast_grp = nullptr;
-  uint32_t *d_fast_cxy = nullptr, *d_fast_cscore = nullptr, *d_fast_tot = nullptr;
-  uint8_t* d_fast_img = nullptr;  // a caller's host image (linear, width*height)
+  DevBuf<uint8_t> d_fast_m;
+  DevBuf<uint32_t> d_fast_xy, d_fast_score, d_fast_cnt, d_fast_det, d_fast_grp;
+  DevBuf<uint32_t> d_fast_cxy, d_fast_cscore, d_fast_tot;
+  DevBuf<uint8_t> d_fast_img;  // a caller's host image (linear, width*height)
   bool fast_lds = false;          // (ESVIO_FE_FAST_LDS=1: k_fast_score's LDS-tiled form, for the A/B in KERNELS.md)
   // pinned host staging (layout: pin_of())
-  uint8_t* h_img = nullptr;  // copy_level0_in's staging ring: pinned host side ...
-  uint8_t* d_img = nullptr;  // ... and its device side (linear images)
-  size_t img_stage_bytes = 0;
+  PinBuf<uint8_t> h_img;  // copy_level0_in's staging ring: pinned host side ...
+  DevBuf<uint8_t> d_img;  // ... and its device side (linear images)
   unsigned img_stage_next = 0;
-  uint8_t* h_pin = nullptr;
-  size_t h_pin_bytes = 0;
+  PinBuf<uint8_t> h_pin;
 
   // ---- FeatureTracker state (feature_tracker.h:119-173)
   int n_id = 0;
@@ -387,10 +384,10 @@ struct esvio_fe_ctx {
 
   // ---- host phase trace (ESVIO_FE_TRACE=1): stage, sae+ts enqueue, sync A, host A, enqueue B,
   // sync B, host B
-  uint8_t* d_eq_tmp = nullptr;  // equalize: the two CLAHE outputs before normalisation (linear W x H each)
+  DevBuf<uint8_t> d_eq_tmp;  // equalize: the two CLAHE outputs before normalisation (linear W x H each)
   bool select_ok = true;  // the greedy selection's bitmap fits LDS
   bool select_one_wave = false;  // (ESVIO_FE_SELECT_SERIAL=1, test-only: the one-wave selection kernel)
-  uint32_t* d_sel_bitmap = nullptr;  // ... else it lives here (k_select_gbm)
+  DevBuf<uint32_t> d_sel_bitmap;  // ... else it lives here (k_select_gbm)
   bool trace = false;
   double phase_ms[2][8] = {};  // [published?][phase]
   double pub_ms[6] = {};       // published frames: the parts of "host mask + enqueue detect/stereo"
@@ -402,7 +399,7 @@ struct esvio_fe_ctx {
   double tr_fm_max_ms = 0, tr_lift_ms = 0;  // ... its slowest call; the two liftProjective batches
   uint64_t tr_chain_launch = 0, tr_chain_used = 0, tr_chain_cancel = 0, tr_spec_used = 0;
   // (trace only) device-side intervals of the published frame's chain, from timing events
-  hipEvent_t ev_dbg_sel_start = nullptr;
+  Event ev_dbg_sel_start;
   double tr_gpu_sel = 0, tr_gpu_spec = 0, tr_gpu_chain = 0, tr_host_chain = 0, tr_gpu_pyr = 0;
   int tr_lane = -1;  // prefetch lane of the frame being tracked
   uint64_t tr_gpu_n = 0;
@@ -434,7 +431,7 @@ struct esvio_fe_ctx {
   bool prof_on = false;
   KStat stats[K_COUNT];
   std::vector<ProfRec> pending;
-  std::vector<hipEvent_t> ev_pool;
+  std::vector<Event> ev_pool;
 };
 
 namespace esvio {
@@ -481,15 +478,25 @@ inline int fail(esvio_fe_ctx* c, int code, const char* fmt, ...) {
                   __FILE__, __LINE__);                                                       \
   } while (0)
 
+// every hipMalloc / hipHostMalloc of a handle (Buf::alloc, fe_res.h)
+inline int res_alloc(esvio_fe_ctx* c, void** p, size_t bytes, bool pinned) {
+  if (pinned)
+    HIPCHK(c, hipHostMalloc(p, bytes, hipHostMallocDefault));
+  else
+    HIPCHK(c, hipMalloc(p, bytes));
+  c->n_allocs++;
+  return 0;
+}
+
 // ---------------------------------------------------------------- profiling
-inline hipEvent_t get_event(esvio_fe_ctx* c) {
+inline Event get_event(esvio_fe_ctx* c) {
+  Event e;
   if (!c->ev_pool.empty()) {
-    hipEvent_t e = c->ev_pool.back();
+    e = std::move(c->ev_pool.back());
     c->ev_pool.pop_back();
-    return e;
+  } else {
+    (void)e.create(0);
   }
-  hipEvent_t e;
-  (void)hipEventCreate(&e);
   return e;
 }
 
@@ -497,7 +504,7 @@ struct ScopedKernel {  // brackets one launch with HIP events on the handle's st
   esvio_fe_ctx* c;
   int id;
   uint64_t bytes;
-  hipEvent_t a = nullptr, b = nullptr;
+  Event a, b;
   ScopedKernel(esvio_fe_ctx* ctx, int kid, uint64_t alg_bytes) : c(ctx), id(kid), bytes(alg_bytes) {
     if (c->prof_on) {
       a = get_event(c);
@@ -508,7 +515,7 @@ struct ScopedKernel {  // brackets one launch with HIP events on the handle's st
   ~ScopedKernel() {
     if (a) {
       (void)hipEventRecord(b, cur_stream(c));
-      c->pending.push_back(ProfRec{id, a, b, bytes});
+      c->pending.push_back(ProfRec{id, std::move(a), std::move(b), bytes});
     }
   }
 };
@@ -519,7 +526,7 @@ inline void resolve_profile(esvio_fe_ctx* c) {  // main stream idle; prefetch-st
     float ms = 0;
     const hipError_t e = hipEventElapsedTime(&ms, r.a, r.b);
     if (e == hipErrorNotReady) {
-      keep.push_back(r);
+      keep.push_back(std::move(r));
       continue;
     }
     if (e == hipSuccess) {
@@ -527,8 +534,8 @@ inline void resolve_profile(esvio_fe_ctx* c) {  // main stream idle; prefetch-st
       c->stats[r.id].launches++;
       c->stats[r.id].bytes += r.bytes;
     }
-    c->ev_pool.push_back(r.a);
-    c->ev_pool.push_back(r.b);
+    c->ev_pool.push_back(std::move(r.a));
+    c->ev_pool.push_back(std::move(r.b));
   }
   c->pending.swap(keep);
   (void)hipGetLastError();

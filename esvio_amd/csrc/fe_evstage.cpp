@@ -122,14 +122,14 @@ struct Slot {
   std::atomic<uint32_t> n_chunks{0};  // of the batch being staged
   std::atomic<uint32_t> next{0};      // the next chunk nobody has taken (>= n_chunks: none left)
   int n_groups = 0;
-  uint8_t* pin = nullptr;
-  EventRec* dev = nullptr;
-  size_t cap = 0;  // events
-  hipEvent_t copied = nullptr, pf_done = nullptr, main_done = nullptr, aux_done = nullptr;
+  PinBuf<uint8_t> pin;   // [16 * cap]
+  DevBuf<EventRec> dev;  // [cap]
+  size_t cap = 0;  // events, of both (slot_capacity)
+  Event copied, pf_done, main_done, aux_done;
   bool pf_rec = false, main_rec = false, aux_rec = false;
   // by_camera staging (a plain call that starts on the left camera while the right one is still on its
   // way): the left array is a DMA of its own, `copiedL` is recorded behind it
-  hipEvent_t copiedL = nullptr;
+  Event copiedL;
   int n_left_groups = 0;             // groups [0, n_left_groups) are the left array's (0: not by camera, or a pinned source)
   std::atomic<bool> left_enq{false}; // the left array's DMA is enqueued and copiedL recorded
   uint32_t n_left_chunks = 0;        // chunks [0, n_left_chunks) are the left array's (by_camera)
@@ -138,8 +138,7 @@ struct Slot {
   // size, a group = whole chunks of one array): one {base second, packed?} pair per chunk, pinned, read by the kernel
   bool pack = false;
   uint32_t pack_epc = 0;             // events per chunk
-  uint32_t* desc = nullptr;          // [2 * desc_cap]
-  size_t desc_cap = 0;
+  PinBuf<uint32_t> desc;             // {base second, packed?} per chunk
   std::chrono::steady_clock::time_point t_begin;  // (trace) when stager_begin opened the batch for taking
   bool in_use = false;
   std::atomic<int> state{0};  // 0 idle, 1 staging, 2 every DMA enqueued and `copied` recorded, -1 failed
@@ -155,9 +154,11 @@ struct Slot {
 // the same bytes, a group's DMA moves the same bytes, `copied` recorded again only moves the event
 // later — so the calling thread, when it waits for a batch (stager_attach), finishes whatever a helper
 // has started and not finished instead of waiting for that helper.
+// (the members release themselves, fe_res.h; stager_destroy deletes the stager once its threads have stopped and its
+// stream is idle, so their order carries no dependency)
 struct EventStager {
   esvio_fe_ctx* c = nullptr;
-  hipStream_t stream = nullptr;
+  Stream stream;
   Slot slot[kStageSlots];
   std::vector<std::thread> threads;
   std::mutex mu;  // (only the sleeping helpers' condition variable)
@@ -170,12 +171,12 @@ struct EventStager {
   // A thread's first HIP calls cost milliseconds (measured: 7 ms inside the call whose DMA a RANSAC helper
   // was the first to enqueue): every thread that may enqueue a DMA does one dummy copy + event record on the
   // copy stream before it takes its first chunk
-  hipEvent_t gate_ev[4] = {};                    // behind the last four DMAs
+  Event gate_ev[4];                    // behind the last four DMAs
   std::atomic<uint32_t> gate_n{0}, gate_rec[4];  // DMAs issued; gate_rec[t & 3] == t + 1: DMA t's event is recorded
   std::atomic<uint64_t> gate_expired{0};
-  uint8_t* warm_pin = nullptr;
-  void* warm_dev = nullptr;
-  hipEvent_t warm_ev = nullptr;
+  PinBuf<uint8_t> warm_pin;
+  DevBuf<uint8_t> warm_dev;
+  Event warm_ev;
   void warm_thread() {
     (void)hipSetDevice(c->dev);
     if (warm_pin && warm_dev && hipMemcpyAsync(warm_dev, warm_pin, 16, hipMemcpyHostToDevice, stream) != hipSuccess) (void)hipGetLastError();
@@ -417,39 +418,24 @@ static int stager_get(esvio_fe_ctx* c, EventStager** out) {
     st->c = c;
     st->pending = &c->stage_pending;
     c->stage_pending.store(0, std::memory_order_release);
-    if (hipStreamCreateWithFlags(&st->stream, hipStreamNonBlocking) != hipSuccess) {
-      delete st;
-      return fail(c, ESVIO_FE_EHIP, "hipStreamCreate (event staging) failed");
-    }
-    for (Slot& s : st->slot)
-      if (hipEventCreateWithFlags(&s.copied, hipEventDisableTiming) != hipSuccess ||
-          hipEventCreateWithFlags(&s.copiedL, hipEventDisableTiming) != hipSuccess ||
-          hipEventCreateWithFlags(&s.pf_done, hipEventDisableTiming) != hipSuccess ||
-          hipEventCreateWithFlags(&s.aux_done, hipEventDisableTiming) != hipSuccess ||
-          hipEventCreateWithFlags(&s.main_done, hipEventDisableTiming) != hipSuccess) {
-        c->stager = st;
-        stager_destroy(c);
-        return fail(c, ESVIO_FE_EHIP, "hipEventCreate (event staging) failed");
-      }
+    c->stager = st;  // (from here on a failure leaves through stager_destroy)
     constexpr size_t kWarmBytes = 64;
-    if (hipHostMalloc((void**)&st->warm_pin, kWarmBytes, hipHostMallocDefault) != hipSuccess || hipMalloc(&st->warm_dev, kWarmBytes) != hipSuccess ||
-        hipEventCreateWithFlags(&st->warm_ev, hipEventDisableTiming) != hipSuccess) {
-      c->stager = st;
-      stager_destroy(c);
-      return fail(c, ESVIO_FE_EHIP, "allocation (event staging) failed");
-    }
-    std::memset(st->warm_pin, 0, kWarmBytes);
+    bool ok = st->stream.create() == hipSuccess;
+    for (Slot& s : st->slot)
+      ok = ok && s.copied.create() == hipSuccess && s.copiedL.create() == hipSuccess && s.pf_done.create() == hipSuccess &&
+           s.aux_done.create() == hipSuccess && s.main_done.create() == hipSuccess;
+    ok = ok && st->warm_pin.alloc(c, kWarmBytes) == 0 && st->warm_dev.alloc(c, kWarmBytes) == 0 && st->warm_ev.create() == hipSuccess;
     for (int i = 0; i < 4; i++) {
       st->gate_rec[i].store(0, std::memory_order_relaxed);
-      if (hipEventCreateWithFlags(&st->gate_ev[i], hipEventDisableTiming) != hipSuccess) {
-        c->stager = st;
-        stager_destroy(c);
-        return fail(c, ESVIO_FE_EHIP, "hipEventCreate (event staging) failed");
-      }
+      ok = ok && st->gate_ev[i].create() == hipSuccess;
     }
+    if (!ok) {
+      stager_destroy(c);
+      return fail(c, ESVIO_FE_EHIP, "stream, event or allocation (event staging) failed");
+    }
+    std::memset(st->warm_pin, 0, kWarmBytes);
     if (const char* v = getenv("ESVIO_FE_STAGE_PACK")) st->pack_enabled = atoi(v) != 0;
     for (int i = 0; i < c->stage_threads; i++) st->threads.emplace_back([st] { st->worker(); });
-    c->stager = st;
     stager_share_pool(c);  // the RANSAC helpers, spinning between jobs anyway, take chunks as well
   }
   *out = c->stager;
@@ -473,16 +459,11 @@ static bool host_range_is_pinned(const void* p, size_t len) {
 
 static int slot_capacity(esvio_fe_ctx* c, Slot& s, size_t n) {
   if (n <= s.cap) return 0;
-  // (the device buffer's previous readers: hipFree waits for the device)
-  if (s.dev) (void)hipFree(s.dev);
-  if (s.pin) (void)hipHostFree(s.pin);
-  s.dev = nullptr;
-  s.pin = nullptr;
   s.cap = 0;
+  s.pin.release();
   const size_t cap = std::max<size_t>(n + n / 4, 1 << 16);
-  if (int rc = dev_alloc(c, &s.dev, cap)) return rc;
-  HIPCHK(c, hipHostMalloc((void**)&s.pin, cap * 16, hipHostMallocDefault));
-  c->n_allocs++;
+  if (int rc = s.dev.alloc(c, cap)) return rc;
+  if (int rc = s.pin.alloc(c, cap * 16)) return rc;
   s.cap = cap;
   return 0;
 }
@@ -493,14 +474,8 @@ static int slot_chunks(esvio_fe_ctx* c, Slot& s, size_t chunks) {
     s.chunk_cap = chunks + 4 + chunks / 4;
     s.chunk.reset(new Chunk[s.chunk_cap]);
   }
-  if (s.chunk_cap > s.desc_cap) {
-    if (s.desc) (void)hipHostFree(s.desc);
-    s.desc = nullptr;
-    s.desc_cap = 0;
-    HIPCHK(c, hipHostMalloc((void**)&s.desc, s.chunk_cap * 8, hipHostMallocDefault));
-    c->n_allocs++;
-    s.desc_cap = s.chunk_cap;
-  }
+  if (2 * s.chunk_cap > s.desc.cap)
+    if (int rc = s.desc.alloc(c, 2 * s.chunk_cap)) return rc;
   return 0;
 }
 
@@ -853,25 +828,7 @@ void stager_destroy(esvio_fe_ctx* c) {
             "the batch's opening, the left array's last group enqueued after %.1f us, the batch's after %.1f us\n",
             st->chunk_ns.load() / 1e3 / st->chunk_cnt.load(), (unsigned long long)st->chunk_cnt.load(), st->first_take_ns.load() / 1e3 / st->batches,
             st->left_sent_ns.load() / 1e3 / std::max<uint64_t>(1, st->left_calls), st->all_sent_ns.load() / 1e3 / st->batches);
-  if (st->stream) {
-    (void)hipStreamSynchronize(st->stream);
-    (void)hipStreamDestroy(st->stream);
-  }
-  if (st->warm_ev) (void)hipEventDestroy(st->warm_ev);
-  for (hipEvent_t ev : st->gate_ev)
-    if (ev) (void)hipEventDestroy(ev);
-  if (st->warm_dev) (void)hipFree(st->warm_dev);
-  if (st->warm_pin) (void)hipHostFree(st->warm_pin);
-  for (Slot& s : st->slot) {
-    if (s.copied) (void)hipEventDestroy(s.copied);
-    if (s.copiedL) (void)hipEventDestroy(s.copiedL);
-    if (s.aux_done) (void)hipEventDestroy(s.aux_done);
-    if (s.pf_done) (void)hipEventDestroy(s.pf_done);
-    if (s.main_done) (void)hipEventDestroy(s.main_done);
-    if (s.dev) (void)hipFree(s.dev);
-    if (s.pin) (void)hipHostFree(s.pin);
-    if (s.desc) (void)hipHostFree(s.desc);
-  }
+  if (st->stream) (void)hipStreamSynchronize(st->stream);
   delete st;
   c->stager = nullptr;
 }

@@ -27,15 +27,15 @@ int fast_run(esvio_fe_ctx* c, const uint8_t* img, int stride, int arc, int barri
   const size_t P = (size_t)c->W * c->H;
   const uint32_t nblk = (uint32_t)((P + kArcBlock - 1) / kArcBlock);
   if (!c->d_fast_m) {
-    if (int rc = dev_alloc(c, &c->d_fast_xy, (size_t)nblk * kArcBlock)) return rc;
-    if (int rc = dev_alloc(c, &c->d_fast_score, (size_t)nblk * kArcBlock)) return rc;
-    if (int rc = dev_alloc(c, &c->d_fast_cnt, nblk)) return rc;
-    if (int rc = dev_alloc(c, &c->d_fast_det, nblk)) return rc;
-    if (int rc = dev_alloc(c, &c->d_fast_grp, nblk / 64 + 1)) return rc;
-    if (int rc = dev_alloc(c, &c->d_fast_cxy, P)) return rc;
-    if (int rc = dev_alloc(c, &c->d_fast_cscore, P)) return rc;
-    if (int rc = dev_alloc(c, &c->d_fast_tot, 2)) return rc;
-    if (int rc = dev_alloc(c, &c->d_fast_m, P)) return rc;  // (last: the test above means "all of them")
+    if (int rc = c->d_fast_xy.alloc(c, (size_t)nblk * kArcBlock)) return rc;
+    if (int rc = c->d_fast_score.alloc(c, (size_t)nblk * kArcBlock)) return rc;
+    if (int rc = c->d_fast_cnt.alloc(c, nblk)) return rc;
+    if (int rc = c->d_fast_det.alloc(c, nblk)) return rc;
+    if (int rc = c->d_fast_grp.alloc(c, nblk / 64 + 1)) return rc;
+    if (int rc = c->d_fast_cxy.alloc(c, P)) return rc;
+    if (int rc = c->d_fast_cscore.alloc(c, P)) return rc;
+    if (int rc = c->d_fast_tot.alloc(c, 2)) return rc;
+    if (int rc = c->d_fast_m.alloc(c, P)) return rc;  // (last: the test above means "all of them")
   }
   hipStream_t s = cur_stream(c);
   FastArgs a{};
@@ -86,11 +86,11 @@ int fast_run(esvio_fe_ctx* c, const uint8_t* img, int stride, int arc, int barri
 int gftt_run(esvio_fe_ctx* c, const PyrDesc& d, int max_corners, double quality, double min_distance,
              bool use_mask, float2* out_pts, int out_base, int* host_counts) {
   const size_t P = (size_t)c->W * c->H;
-  if (!c->d_gftt_cov) {
-    if (int rc = dev_alloc(c, &c->d_gftt_cov, P)) return rc;
-    if (int rc = dev_alloc(c, &c->d_gftt_rowsum, P)) return rc;
-    if (int rc = dev_alloc(c, &c->d_gftt_eig, P)) return rc;
-    if (int rc = dev_alloc(c, &c->d_gftt_max, 1)) return rc;
+  if (!c->d_gftt_max) {  // (the last one: "all of them")
+    if (int rc = c->d_gftt_cov.alloc(c, P)) return rc;
+    if (int rc = c->d_gftt_rowsum.alloc(c, P)) return rc;
+    if (int rc = c->d_gftt_eig.alloc(c, P)) return rc;
+    if (int rc = c->d_gftt_max.alloc(c, 1)) return rc;
   }
   const int set = c->cand_cur;
   if (int rc = ensure_cand_capacity(c, set, P)) return rc;
@@ -103,7 +103,7 @@ int gftt_run(esvio_fe_ctx* c, const PyrDesc& d, int max_corners, double quality,
   g.cov = c->d_gftt_cov;
   g.rowsum = c->d_gftt_rowsum;
   g.eig = c->d_gftt_eig;
-  g.mask_bits = use_mask ? c->d_mask_bits : nullptr;
+  g.mask_bits = use_mask ? c->d_mask_bits.p : nullptr;
   g.wpr = (c->W + 31) / 32;
   g.max_key = c->d_gftt_max;
   g.quality = quality;
@@ -163,7 +163,7 @@ int gftt_run(esvio_fe_ctx* c, const PyrDesc& d, int max_corners, double quality,
   size_t lds = select_lds_bytes(c);
   if (!c->select_ok) {  // a frame camera's size: the min-distance bitmap goes to device memory
     if (!c->d_sel_bitmap)
-      if (int rc = dev_alloc(c, &c->d_sel_bitmap, (size_t)c->H * sa.wpr + 4)) return rc;
+      if (int rc = c->d_sel_bitmap.alloc(c, (size_t)c->H * sa.wpr + 4)) return rc;
     sa.gbitmap = c->d_sel_bitmap;
     lds = select_tables_lds_bytes(c);
   }

@@ -7,13 +7,6 @@ namespace fe {
 
 // ---------------------------------------------------------------- small templates / layouts
 template <class T>
-int dev_alloc(esvio_fe_ctx* c, T** p, size_t count) {
-  HIPCHK(c, hipMalloc((void**)p, std::max<size_t>(count, 1) * sizeof(T)));
-  c->n_allocs++;
-  return 0;
-}
-
-template <class T>
 void reduce_vector(std::vector<T>& v, const std::vector<uint8_t>& status) {  // :56-81
   int j = 0;
   for (int i = 0; i < int(v.size()); i++)

@@ -8,62 +8,50 @@ namespace fe {
 
 // ---------------------------------------------------------------- memory
 
-int ensure_event_capacity(esvio_fe_ctx* c, size_t n) {
-  if (n <= c->ev_cap) return 0;
-  size_t cap = std::max<size_t>(n + n / 4, 1 << 16);
-  if (c->d_ev) (void)hipFree(c->d_ev);
-  c->d_ev = nullptr;
-  c->ev_cap = 0;
-  if (int rc = dev_alloc(c, &c->d_ev, cap)) return rc;
-  c->ev_cap = cap;
+int ensure_event_capacity(esvio_fe_ctx* c, size_t n) { return c->d_ev.grow(c, n); }
+
+// keys, vals and sae_marks share one capacity (sort_cap: set once all five are there)
+static int grow_sort_buffers(esvio_fe_ctx* c, size_t cap) {
+  c->sort_cap = 0;
+  for (int i = 0; i < 2; i++) {
+    c->keys[i].release();
+    c->vals[i].release();
+  }
+  for (int i = 0; i < 2; i++) {
+    if (int rc = c->keys[i].alloc(c, cap)) return rc;
+    if (int rc = c->vals[i].alloc(c, cap)) return rc;
+  }
+  if (int rc = c->sae_marks.alloc(c, cap)) return rc;
+  c->sort_cap = cap;
   return 0;
 }
 
 int ensure_sort_capacity(esvio_fe_ctx* c, size_t n) {
-  if (n > c->sort_cap) {
-    size_t cap = std::max<size_t>(n + n / 4, 1 << 16);
-    for (int i = 0; i < 2; i++) {
-      if (c->keys[i]) (void)hipFree(c->keys[i]);
-      if (c->vals[i]) (void)hipFree(c->vals[i]);
-      c->keys[i] = c->vals[i] = nullptr;
-    }
-    c->sort_cap = 0;
-    for (int i = 0; i < 2; i++) {
-      if (int rc = dev_alloc(c, &c->keys[i], cap)) return rc;
-      if (int rc = dev_alloc(c, &c->vals[i], cap)) return rc;
-    }
-    c->sort_cap = cap;
-    if (c->sae_marks) (void)hipFree(c->sae_marks);
-    c->sae_marks = nullptr;
-    if (int rc = dev_alloc(c, &c->sae_marks, cap)) return rc;
-  }
+  if (n > c->sort_cap)
+    if (int rc = grow_sort_buffers(c, std::max<size_t>(n + n / 4, 1 << 16))) return rc;
   // [ghist + tickets | lookback for every pass]
   const size_t head = ((size_t)kRadixMaxPasses << kRadixMaxBits) + 64;
   size_t hneed = head + (size_t)kRadixMaxPasses * (radix_blocks((uint32_t)c->sort_cap) << kRadixMaxBits);
-  if (hneed > c->hist_cap) {
-    if (c->hist) (void)hipFree(c->hist);
-    c->hist = nullptr;
-    c->hist_cap = 0;
-    if (int rc = dev_alloc(c, &c->hist, hneed)) return rc;
-    HIPCHK(c, hipMemsetAsync(c->hist, 0, hneed * 4, cur_stream(c)));
-    c->hist_cap = hneed;
+  if (hneed > c->hist.cap) {
+    if (int rc = c->hist.alloc(c, hneed)) return rc;
+    const hipError_t zeroed = hipMemsetAsync(c->hist, 0, hneed * 4, cur_stream(c));
+    if (zeroed != hipSuccess) c->hist.release();  // (not zeroed is not there)
+    HIPCHK(c, zeroed);
   }
   return 0;
 }
 
+// the seven arrays of a candidate set share one capacity (cap: set once all of them are there)
 static int grow_cand_set(esvio_fe_ctx* c, int set, size_t cap) {
   esvio_fe_ctx::CandSet& s = c->cand[set];
-  void* ptrs[] = {s.xy, s.idx, s.cnt, s.comp_xy, s.comp_idx, s.total, s.grp};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
   s = esvio_fe_ctx::CandSet();
-  if (int rc = dev_alloc(c, &s.xy, cap)) return rc;
-  if (int rc = dev_alloc(c, &s.idx, cap)) return rc;
-  if (int rc = dev_alloc(c, &s.cnt, cap / kArcBlock)) return rc;
-  if (int rc = dev_alloc(c, &s.grp, cap / kArcBlock / 64 + 2)) return rc;
-  if (int rc = dev_alloc(c, &s.comp_xy, cap)) return rc;
-  if (int rc = dev_alloc(c, &s.comp_idx, cap)) return rc;
-  if (int rc = dev_alloc(c, &s.total, 1)) return rc;
+  if (int rc = s.xy.alloc(c, cap)) return rc;
+  if (int rc = s.idx.alloc(c, cap)) return rc;
+  if (int rc = s.cnt.alloc(c, cap / kArcBlock)) return rc;
+  if (int rc = s.grp.alloc(c, cap / kArcBlock / 64 + 2)) return rc;
+  if (int rc = s.comp_xy.alloc(c, cap)) return rc;
+  if (int rc = s.comp_idx.alloc(c, cap)) return rc;
+  if (int rc = s.total.alloc(c, 1)) return rc;
   s.cap = cap;
   return 0;
 }
@@ -85,20 +73,13 @@ int ensure_cand_capacity(esvio_fe_ctx* c, int set, size_t n) {
 // per-event flags (standalone isCorner) and candidate set `set`
 int ensure_arc_capacity(esvio_fe_ctx* c, size_t n, int set) {
   if (int rc = ensure_cand_capacity(c, set, n)) return rc;
-  if (n <= c->arc_cap) return 0;
-  size_t cap = std::max<size_t>(n + n / 4, 1 << 16);
-  cap = (cap + kArcBlock - 1) / kArcBlock * kArcBlock;
-  if (c->d_flags) (void)hipFree(c->d_flags);
-  c->d_flags = nullptr;
-  c->arc_cap = 0;
-  if (int rc = dev_alloc(c, &c->d_flags, cap)) return rc;
-  c->arc_cap = cap;
-  return 0;
+  if (n <= c->d_flags.cap) return 0;
+  const size_t cap = std::max<size_t>(n + n / 4, 1 << 16);
+  return c->d_flags.alloc(c, (cap + kArcBlock - 1) / kArcBlock * kArcBlock);
 }
 
 int pyr_alloc(esvio_fe_ctx* c, PyrStore& ps, int w, int h, int max_level) {
   if (ps.mem && ps.w == w && ps.h == h && ps.max_level == max_level) return 0;
-  if (ps.mem) (void)hipFree(ps.mem);
   ps = PyrStore();
   const int levels = pyr_levels(w, h, kLkWin, max_level);
   size_t off = 0, img_off[kMaxLevels], der_off[kMaxLevels];
@@ -115,12 +96,11 @@ int pyr_alloc(esvio_fe_ctx* c, PyrStore& ps, int w, int h, int max_level) {
     lw = (lw + 1) / 2;
     lh = (lh + 1) / 2;
   }
-  HIPCHK(c, hipMalloc(&ps.mem, off));
-  c->n_allocs++;
+  if (int rc = ps.mem.alloc(c, off)) return rc;
   HIPCHK(c, hipMemsetAsync(ps.mem, 0, off, cur_stream(c)));  // derivative borders stay 0 forever
   for (int l = 0; l <= levels; l++) {
-    ps.d.img[l] = (uint8_t*)ps.mem + img_off[l];
-    ps.d.deriv[l] = (int16_t*)((uint8_t*)ps.mem + der_off[l]);
+    ps.d.img[l] = ps.mem + img_off[l];
+    ps.d.deriv[l] = (int16_t*)(ps.mem + der_off[l]);
   }
   for (int l = levels + 1; l < kMaxLevels; l++) {
     ps.d.img[l] = ps.d.img[levels];
@@ -130,7 +110,6 @@ int pyr_alloc(esvio_fe_ctx* c, PyrStore& ps, int w, int h, int max_level) {
     ps.d.stride[l] = ps.d.stride[levels];
   }
   ps.d.levels = levels;
-  ps.bytes = off;
   ps.w = w;
   ps.h = h;
   ps.max_level = max_level;
@@ -191,28 +170,17 @@ McParams make_mc_params(const esvio_fe_motion* m) {
 
 // the partition's buffers for batches of up to n events (d_warp only once a motion-compensated batch comes)
 int ensure_part_capacity(esvio_fe_ctx* c, size_t n, bool mc) {
-  if (n > c->part_cap) {
-    const size_t cap = std::max<size_t>(n + n / 4, 1 << 16);
-    if (c->d_part) (void)hipFree(c->d_part);
-    if (c->d_warp) (void)hipFree(c->d_warp);
-    c->d_part = nullptr;
-    c->d_warp = nullptr;
-    c->part_cap = 0;
-    if (int rc = dev_alloc(c, &c->d_part, cap)) return rc;
-    c->part_cap = cap;
+  if (n > c->d_part.cap) {
+    c->d_warp.release();  // (sized like d_part)
+    if (int rc = c->d_part.grow(c, n)) return rc;
   }
   if (mc && !c->d_warp)  // the motion-compensated overload: 4 B per event for the warped pixels
-    if (int rc = dev_alloc(c, &c->d_warp, c->part_cap)) return rc;
-  const size_t nblk_cap = (c->part_cap + 2047) / 2048 + 2;  // (2048 events per scatter block at least; each camera's last block may be short)
+    if (int rc = c->d_warp.alloc(c, c->d_part.cap)) return rc;
+  const size_t nblk_cap = (c->d_part.cap + 2047) / 2048 + 2;  // (2048 events per scatter block at least; each camera's last block may be short)
   const size_t head = (size_t)3 * kTileMaxBins + 64 + 4 * (size_t)kTileMaxGroups;
   const size_t need = head + (nblk_cap + 2 * (size_t)kTileMaxGroups) * kTileMaxBins;
-  if (need > c->tile_cap) {
-    if (c->d_tile) (void)hipFree(c->d_tile);
-    c->d_tile = nullptr;
-    c->tile_cap = 0;
-    if (int rc = dev_alloc(c, &c->d_tile, need)) return rc;
-    c->tile_cap = need;
-  }
+  if (need > c->d_tile.cap)
+    if (int rc = c->d_tile.alloc(c, need)) return rc;
   return 0;
 }
 
@@ -220,7 +188,7 @@ int sae_update_tiled(esvio_fe_ctx* c, const EventRec* evL, uint32_t nL, const Ev
                      double2* L2, double2* S2, uint8_t* arc_touched, const McParams* mc) {
   const uint32_t n = nL + nR;
   if (int rc = ensure_part_capacity(c, n, mc != nullptr)) return rc;
-  const size_t nblk_cap = (c->part_cap + 2047) / 2048 + 2;
+  const size_t nblk_cap = (c->d_part.cap + 2047) / 2048 + 2;
   const size_t head = (size_t)3 * kTileMaxBins + 64 + 4 * (size_t)kTileMaxGroups;
   TileScratch sc;
   sc.meta = c->d_tile + 3 * kTileMaxBins + 32;  // (the 32 free words behind tile_order)
@@ -234,7 +202,7 @@ int sae_update_tiled(esvio_fe_ctx* c, const EventRec* evL, uint32_t nL, const Ev
   {
     {
       ScopedKernel k(c, K_TILE_HIST, (uint64_t)n * 16);  // ingest: the raw records, read once
-      launch_tile_hist(cur_stream(c), evL, nL, evR, nR, c->tgeom, sc, c->d_rejected, mc, mc ? c->d_warp : nullptr);
+      launch_tile_hist(cur_stream(c), evL, nL, evR, nR, c->tgeom, sc, c->d_rejected, mc, mc ? c->d_warp.p : nullptr);
     }
     {
       ScopedKernel k(c, K_TILE_SCAN, 0);  // (the count matrices: not in SURVEY's accounting)
@@ -242,7 +210,7 @@ int sae_update_tiled(esvio_fe_ctx* c, const EventRec* evL, uint32_t nL, const Ev
     }
     {
       ScopedKernel k(c, K_TILE_SCATTER, (uint64_t)n * 24);  // the partition's own traffic: 16 B in, 8 B out (16 for wide records)
-      launch_tile_scatter(cur_stream(c), evL, nL, evR, nR, c->tgeom, sc, c->d_part, mc ? c->d_warp : nullptr);
+      launch_tile_scatter(cur_stream(c), evL, nL, evR, nR, c->tgeom, sc, c->d_part, mc ? c->d_warp.p : nullptr);
     }
   }
   {
@@ -265,7 +233,7 @@ int sae_update(esvio_fe_ctx* c, const EventRec* evL, uint32_t nL, const EventRec
   if (c->tiled) {
     // (motion compensation: the update happens at the warped pixels, Arc* is asked about the events'
     // own pixels (feature_tracker.cpp:698 -> :13-38), so the tiles' touched flags are not Arc*'s)
-    uint8_t* mark = arc_set >= 0 && nL && !mc ? c->d_touched[arc_set] : nullptr;
+    uint8_t* mark = arc_set >= 0 && nL && !mc ? c->d_touched[arc_set].p : nullptr;
     if (arc_marked) *arc_marked = mark != nullptr;
     return sae_update_tiled(c, evL, nL, evR, nR, L2, S2, mark, mc);
   }
@@ -313,20 +281,12 @@ int stage_events(esvio_fe_ctx* c, const esvio_fe_event* left, size_t nL,
     return 0;
   }
   if (space != ESVIO_FE_HOST) return fail(c, ESVIO_FE_EINVAL, "bad memory space %d", space);
-  EventRec** buf = lane >= 0 ? &c->d_evp[lane] : &c->d_ev;
-  size_t* cap = lane >= 0 ? &c->evp_cap[lane] : &c->ev_cap;
-  if (nL + nR > *cap) {
-    const size_t ncap = std::max<size_t>(nL + nR + (nL + nR) / 4, 1 << 16);
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr;
-    *cap = 0;
-    if (int rc = dev_alloc(c, buf, ncap)) return rc;
-    *cap = ncap;
-  }
-  if (nL) HIPCHK(c, hipMemcpyAsync(*buf, left, nL * 16, hipMemcpyHostToDevice, cur_stream(c)));
-  if (nR) HIPCHK(c, hipMemcpyAsync(*buf + nL, right, nR * 16, hipMemcpyHostToDevice, cur_stream(c)));
-  *dL = *buf;
-  *dR = *buf + nL;
+  DevBuf<EventRec>& buf = lane >= 0 ? c->d_evp[lane] : c->d_ev;
+  if (int rc = buf.grow(c, nL + nR)) return rc;
+  if (nL) HIPCHK(c, hipMemcpyAsync(buf, left, nL * 16, hipMemcpyHostToDevice, cur_stream(c)));
+  if (nR) HIPCHK(c, hipMemcpyAsync(buf + nL, right, nR * 16, hipMemcpyHostToDevice, cur_stream(c)));
+  *dL = buf;
+  *dR = buf + nL;
   return 0;
 }
 
@@ -507,19 +467,13 @@ static int image_stage_slot(esvio_fe_ctx* c, size_t bytes, size_t* off) {
   constexpr int kSlots = 4;  // (a frame stages at most two images; a slot is reused two frames later,
                              // and every call that stages an image waits for its stream before it returns
                              // or, on the way in, before the next trackImage call can come)
-  if (!c->h_img || c->img_stage_bytes < bytes) {
+  if (!c->d_img || c->d_img.cap < kSlots * bytes) {  // (the pair's second: both are there)
     HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
-    if (c->h_img) (void)hipHostFree(c->h_img);
-    if (c->d_img) (void)hipFree(c->d_img);
-    c->h_img = nullptr;
-    c->d_img = nullptr;
-    c->img_stage_bytes = 0;
-    HIPCHK(c, hipHostMalloc((void**)&c->h_img, kSlots * bytes, hipHostMallocDefault));
-    c->n_allocs++;
-    if (int rc = dev_alloc(c, &c->d_img, kSlots * bytes)) return rc;
-    c->img_stage_bytes = bytes;
+    c->d_img.release();
+    if (int rc = c->h_img.alloc(c, kSlots * bytes)) return rc;
+    if (int rc = c->d_img.alloc(c, kSlots * bytes)) return rc;
   }
-  *off = (size_t)(c->img_stage_next++ % kSlots) * c->img_stage_bytes;
+  *off = (size_t)(c->img_stage_next++ % kSlots) * (c->d_img.cap / kSlots);
   return 0;
 }
 
@@ -816,7 +770,7 @@ void run_select(esvio_fe_ctx* c, int set, int max_corners, float2* out_pts, int 
   }
   size_t lds = select_lds_bytes(c);
   if (!c->select_ok) {  // the bitmap does not fit LDS: it lives in device memory (slower, same result)
-    if (!c->d_sel_bitmap && dev_alloc(c, &c->d_sel_bitmap, (size_t)c->H * s.wpr + 4) != 0) return;
+    if (!c->d_sel_bitmap && c->d_sel_bitmap.alloc(c, (size_t)c->H * s.wpr + 4) != 0) return;
     s.gbitmap = c->d_sel_bitmap;
     lds = select_tables_lds_bytes(c);
   }
@@ -840,12 +794,12 @@ void run_arc(esvio_fe_ctx* c, const EventRec* ev, uint32_t n, const PyrDesc* ts,
   a.ts = ts ? ts->img[0] : nullptr;  // RAW left time surface (:26)
   a.ts_stride = ts ? ts->stride[0] : 0;
   a.ts_lk_threshold = c->cfg.ts_lk_threshold;
-  a.mask_bits = use_mask ? c->d_mask_bits : nullptr;
+  a.mask_bits = use_mask ? c->d_mask_bits.p : nullptr;
   a.wpr = (c->W + 31) / 32;
-  a.flags = want_flags ? c->d_flags : nullptr;
-  a.cand_xy = want_cand ? c->cand[set].xy : nullptr;
-  a.cand_idx = want_cand ? c->cand[set].idx : nullptr;
-  a.cand_cnt = want_cand ? c->cand[set].cnt : nullptr;
+  a.flags = want_flags ? c->d_flags.p : nullptr;
+  a.cand_xy = want_cand ? c->cand[set].xy.p : nullptr;
+  a.cand_idx = want_cand ? c->cand[set].idx.p : nullptr;
+  a.cand_cnt = want_cand ? c->cand[set].cnt.p : nullptr;
   // Only a pixel's earliest candidate can be accepted (a later one finds the pixel blocked whatever happened to the
   // first): an atomicMin per candidate here + k_dedup halve the list k_select walks.  That paid with the one-wave
   // k_select (54 against 57 us at 0.17 M left events); k_select_mw does not care until it has to dig through the

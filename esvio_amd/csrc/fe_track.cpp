@@ -151,7 +151,7 @@ int stereo_split_prepare(esvio_fe_ctx* c) {
   if (c->stream6) return 0;
   const bool wanted = c->stereo_split_env >= 0 ? c->stereo_split_env != 0 : (c->cfg.lk_accum == 2 && c->launcher != nullptr);
   if (!wanted) return 0;
-  HIPCHK(c, hipStreamCreateWithFlags(&c->stream6, hipStreamNonBlocking));
+  HIPCHK(c, c->stream6.create());
   launch_spin(c->stream6, 0);
   HIPCHK(c, hipStreamSynchronize(c->stream6));
   return 0;
@@ -292,7 +292,7 @@ int prefetch_next(esvio_fe_ctx* c, bool wait_planes, bool must_take_first) {
     // capacities are the calling thread's business (growing frees buffers: nothing handed over may still
     // be about to use them)
     const size_t n = b.nL + b.nR;
-    const bool grows = (c->tiled ? n > c->part_cap || (b.has_motion && !c->d_warp) : n > c->sort_cap) ||
+    const bool grows = (c->tiled ? n > c->d_part.cap || (b.has_motion && !c->d_warp) : n > c->sort_cap) ||
                        (b.arc_done && b.nL > c->cand[b.cand].cap);
     if ((grows || !async) && c->launcher)
       if ((rc = launcher_drain(c))) break;

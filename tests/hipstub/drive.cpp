@@ -3,7 +3,9 @@
 // staging helpers), the launch thread switched on and off mid-stream, 0..7 RANSAC helpers, lazy mode on and off,
 // plain calls in between, calls that must fail (a published frame announced as unpublished), esvio_fe_reset with
 // batches announced and in flight, handles created and destroyed.  The device is fake (fake_device.cpp): what is
-// under test is every thread the library starts and every hand-over between them.
+// under test is every thread the library starts and every hand-over between them.  Before that, handles of a few
+// configurations pass once through every entry point that allocates on first use (first_use_pass); after the last
+// esvio_fe_destroy the stub's count of live device blocks, pinned blocks, events and streams is printed.
 //   drive <seed> <frames>      exit 0: done; the sanitizer reports on stderr
 #include <cstdio>
 #include <cstdlib>
@@ -14,6 +16,7 @@
 #if __has_include("esvio_fe_test.h")  // (trees from before the header was split have the taps in esvio_fe.h)
 #include "esvio_fe_test.h"
 extern "C" void hipstub_arm_faults(int on);  // tests/hipstub/hip_stub.cpp
+extern "C" void hipstub_live(long out[4]);
 #endif
 
 static uint32_t rs;
@@ -42,6 +45,85 @@ static void make_batch(Batch& b, int W, int H, int frame, int n) {
   b.t = (double)sec + 1e-9 * (double)b.L.back().nsec;
 }
 
+// One handle through the entry points that allocate on first use (the stub kernels do nothing: the point is the
+// allocations and the teardown).  Returns the number of calls that failed.
+static int first_use_pass(esvio_fe_config c, int W, int H, bool images) {
+  c.width = W; c.height = H;
+  for (int k = 0; k < 2; k++) { c.cam[k].fx = c.cam[k].fy = 0.9 * W; c.cam[k].cx = W / 2.0; c.cam[k].cy = H / 2.0; }
+  const int M = c.max_cnt;
+  const size_t P = (size_t)W * H;
+  esvio_fe_handle h = nullptr;
+  if (esvio_fe_create(&c, &h) != ESVIO_FE_OK) return 1;
+  int bad = 0;
+#define OK(call)                                                                                \
+  do {                                                                                          \
+    if ((call) != ESVIO_FE_OK) {                                                                \
+      bad++;                                                                                    \
+      fprintf(stderr, "first_use_pass %dx%d: %s: %s\n", W, H, #call, esvio_fe_last_error(h));   \
+    }                                                                                           \
+  } while (0)
+  std::vector<int32_t> ids((size_t)M), cnt((size_t)M), idr((size_t)M);
+  std::vector<float> f2[6];
+  for (auto& v : f2) v.resize(2 * (size_t)M);
+  esvio_fe_tracks t;
+  std::memset(&t, 0, sizeof(t));
+  t.ids = ids.data(); t.track_cnt = cnt.data(); t.cur_pts = f2[0].data(); t.cur_un_pts = f2[1].data();
+  t.pts_velocity = f2[2].data(); t.ids_right = idr.data(); t.cur_right_pts = f2[3].data();
+  t.cur_un_right_pts = f2[4].data(); t.right_pts_velocity = f2[5].data();
+  std::vector<uint8_t> img(P, 7), img2(P, 9), st((size_t)M);
+  std::vector<float> xy(2 * (size_t)M, 40.f), xy2(2 * (size_t)M);
+  int32_t n = 0, n_det = 0, lw = 0, lh = 0, nl = 0;
+  OK(esvio_fe_set_profiling(h, 1));  // (the profiling event pool and its pending records)
+  if (images) {
+    std::vector<int16_t> fxy(2 * 64);
+    std::vector<int32_t> fsc(64);
+    OK(esvio_fe_fast_corners(h, 0, nullptr, ESVIO_FE_HOST, 10, 20, 1, fxy.data(), fsc.data(), 64, &n, &n_det));
+    OK(esvio_fe_fast_corners(h, 0, img.data(), ESVIO_FE_HOST, 9, 20, 0, fxy.data(), nullptr, 64, &n, &n_det));
+    OK(esvio_fe_good_features_to_track(h, img.data(), M, 0.01, 10.0, nullptr, xy2.data(), &n, nullptr));
+    OK(esvio_fe_calc_optical_flow_pyr_lk(h, img.data(), img2.data(), W, H, xy.data(), xy2.data(), st.data(), M, 3, 30, 0.01, 0));
+    OK(esvio_fe_calc_optical_flow_pyr_lk(h, img.data(), img2.data(), W / 2, H / 2, xy.data(), xy2.data(), st.data(), M, 3, 30, 0.01, 0));
+    std::vector<uint8_t> lvl(P);
+    std::vector<int16_t> der(2 * P);
+    OK(esvio_fe_build_pyramid(h, img.data(), W, H, 3, 1, lvl.data(), der.data(), &lw, &lh, &nl));
+    OK(esvio_fe_track_image(h, 1.0, img.data(), img2.data(), 1, &t));
+    OK(esvio_fe_track_image(h, 1.03, img2.data(), img.data(), 1, &t));
+    OK(esvio_fe_reset(h));
+  }
+  Batch b[3];
+  for (int i = 0; i < 3; i++) make_batch(b[i], W, H, i, 9000);
+  uint64_t rej = 0;
+  {  // the time-sliced update: scratch planes, the staging of host-side slice planes
+    const size_t nd = esvio_fe_sae_plane_doubles(h);
+    std::vector<double> last(nd), s_out(nd);
+    OK(esvio_fe_sae_slice_last(h, b[0].L.data(), b[0].L.size(), b[0].R.data(), b[0].R.size(), ESVIO_FE_HOST, last.data(), ESVIO_FE_HOST));
+    OK(esvio_fe_sae_slice_apply(h, b[0].L.data(), b[0].L.size(), b[0].R.data(), b[0].R.size(), ESVIO_FE_HOST, last.data(), 1,
+                                ESVIO_FE_HOST, s_out.data(), ESVIO_FE_HOST));
+    OK(esvio_fe_sae_slice_commit(h, last.data(), s_out.data(), 1, ESVIO_FE_HOST));
+    OK(esvio_fe_reset(h));
+  }
+  OK(esvio_fe_create_sae_stereo(h, b[0].L.data(), b[0].L.size(), b[0].R.data(), b[0].R.size(), ESVIO_FE_HOST, &rej));
+  {
+    std::vector<uint8_t> flags(b[0].L.size());
+    OK(esvio_fe_is_corner(h, b[0].L.data(), b[0].L.size(), ESVIO_FE_HOST, flags.data()));
+    OK(esvio_fe_features_to_track(h, b[0].L.data(), b[0].L.size(), ESVIO_FE_HOST, M, nullptr, xy2.data(), nullptr, &n));
+  }
+  esvio_fe_motion mo;
+  std::memset(&mo, 0, sizeof(mo));
+  mo.t1 = b[0].t; mo.accel[0] = 9.f; mo.fx = mo.fy = 0.9 * W; mo.cx = W / 2.0; mo.cy = H / 2.0;
+  OK(esvio_fe_create_sae_stereo_mc(h, b[0].L.data(), b[0].L.size(), b[0].R.data(), b[0].R.size(), ESVIO_FE_HOST, &mo, &rej));
+  // a plain call, a motion-compensated one, then an announced batch: all from pageable memory
+  OK(esvio_fe_track_event(h, b[0].t, b[0].L.data(), b[0].L.size(), b[0].R.data(), b[0].R.size(), ESVIO_FE_HOST, 1, &t));
+  mo.t1 = b[1].t;
+  OK(esvio_fe_set_next_batch(h, b[2].t, b[2].L.data(), b[2].L.size(), b[2].R.data(), b[2].R.size(), ESVIO_FE_HOST, 1));
+  OK(esvio_fe_track_event_mc(h, b[1].t, b[1].L.data(), b[1].L.size(), b[1].R.data(), b[1].R.size(), ESVIO_FE_HOST, 1, &mo, &t));
+  OK(esvio_fe_track_event(h, b[2].t, b[2].L.data(), b[2].L.size(), b[2].R.data(), b[2].R.size(), ESVIO_FE_HOST, 1, &t));
+  OK(esvio_fe_finish(h, &t));
+  OK(esvio_fe_reserve(h, 1u << 17, 1u << 17, 1));  // (every buffer grows once more)
+#undef OK
+  esvio_fe_destroy(h);
+  return bad;
+}
+
 int main(int argc, char** argv) {
   rs = argc > 1 ? (uint32_t)atoi(argv[1]) : 1u;
   const int frames = argc > 2 ? atoi(argv[2]) : 200;
@@ -62,6 +144,22 @@ int main(int argc, char** argv) {
   t.cur_un_right_pts = f2[4].data(); t.right_pts_velocity = f2[5].data();
   long calls = 0, failed = 0, resets = 0, handles = 0;
   int f = 0;
+  {  // (the injected failures are for the calls of the loop below)
+    hipstub_arm_faults(0);
+    int bad = 0;
+    esvio_fe_config e = c;
+    e.equalize = 1;
+    e.median_blur_kernel_size = 1;
+    bad += first_use_pass(e, W, H, true);
+    setenv("ESVIO_FE_SAE_SORT", "1", 1);       // the radix-sort form of the SAE update ...
+    setenv("ESVIO_FE_STAGE_THREADS", "0", 1);  // ... and host batches without the staging slots (the lanes' own buffers)
+    bad += first_use_pass(c, W, H, false);
+    unsetenv("ESVIO_FE_SAE_SORT");
+    unsetenv("ESVIO_FE_STAGE_THREADS");
+    bad += first_use_pass(c, 1920, 1200, true);  // a sensor whose selection bitmap does not fit LDS: the one in device memory
+    hipstub_arm_faults(1);
+    if (bad) { fprintf(stderr, "first_use_pass: %d calls failed\n", bad); return 5; }
+  }
   while (f < frames) {
     esvio_fe_handle h = nullptr;
     // (both LK modes, and the batches handed over as host or as "device" memory — the stub's device memory is the
@@ -133,5 +231,8 @@ int main(int argc, char** argv) {
   esvio_fe_ransac_tail(tail, 0);
   printf("drive ok: %ld calls on %ld handles, %ld refused/failed, %ld resets, tracks last %d / %d, ransac redone %llu\n", calls,
          handles, failed, resets, t.n_left, t.n_right, (unsigned long long)tail[2]);
+  long live[4];
+  hipstub_live(live);
+  printf("live: device %ld pinned %ld events %ld streams %ld\n", live[0], live[1], live[2], live[3]);
   return 0;
 }

@@ -25,6 +25,9 @@ ihipStream_t* S(hipStream_t s) { return s ? s : &g_null_stream; }
 std::mutex g_mu;
 std::map<const void*, size_t> g_pinned;  // hipHostMalloc / hipHostRegister'ed ranges: base -> bytes
 std::atomic<uint64_t> g_allocs{0};
+// what is alive right now: device blocks, pinned blocks, events, streams (hipstub_live; the driver prints them after its
+// last esvio_fe_destroy, where all four must be 0)
+std::atomic<long> g_live[4];
 // HIPSTUB_FAIL_EVERY=n: every n-th hipEventRecord fails (once each) — a launch that fails in the middle of a call,
 // on whichever thread issues it
 std::atomic<long> g_records{0};
@@ -36,6 +39,9 @@ long fail_every() {
 }  // namespace
 
 extern "C" void hipstub_arm_faults(int on) { g_armed.store(on, std::memory_order_relaxed); }
+extern "C" void hipstub_live(long out[4]) {
+  for (int i = 0; i < 4; i++) out[i] = g_live[i].load(std::memory_order_relaxed);
+}
 
 void hipstub_stream_begin(hipStream_t s) {
   S(s)->mu.lock();
@@ -57,17 +63,24 @@ hipError_t hipMemGetInfo(size_t* f, size_t* t) { *f = (size_t)64 << 30; *t = (si
 hipError_t hipMalloc(void** p, size_t bytes) {
   *p = calloc(bytes ? bytes : 1, 1);
   g_allocs.fetch_add(1, std::memory_order_relaxed);
+  if (*p) g_live[0]++;
   return *p ? hipSuccess : hipErrorOutOfMemory;
 }
-hipError_t hipFree(void* p) { free(p); return hipSuccess; }
+hipError_t hipFree(void* p) {
+  if (p) g_live[0]--;
+  free(p);
+  return hipSuccess;
+}
 hipError_t hipHostMalloc(void** p, size_t bytes, unsigned) {
   *p = calloc(bytes ? bytes : 1, 1);
   if (!*p) return hipErrorOutOfMemory;
+  g_live[1]++;
   std::lock_guard<std::mutex> lk(g_mu);
   g_pinned[*p] = bytes ? bytes : 1;
   return hipSuccess;
 }
 hipError_t hipHostFree(void* p) {
+  if (p) g_live[1]--;
   {
     std::lock_guard<std::mutex> lk(g_mu);
     g_pinned.erase(p);
@@ -120,10 +133,10 @@ hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t st) {
   hipstub_stream_end(st);
   return hipSuccess;
 }
-hipError_t hipStreamCreate(hipStream_t* s) { *s = new ihipStream_t; return hipSuccess; }
+hipError_t hipStreamCreate(hipStream_t* s) { *s = new ihipStream_t; g_live[3]++; return hipSuccess; }
 hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { return hipStreamCreate(s); }
 hipError_t hipStreamCreateWithPriority(hipStream_t* s, unsigned, int) { return hipStreamCreate(s); }
-hipError_t hipStreamDestroy(hipStream_t s) { delete s; return hipSuccess; }
+hipError_t hipStreamDestroy(hipStream_t s) { delete s; g_live[3]--; return hipSuccess; }
 hipError_t hipStreamSynchronize(hipStream_t s) { (void)S(s)->seq.load(std::memory_order_acquire); return hipSuccess; }
 hipError_t hipStreamQuery(hipStream_t s) { (void)S(s)->seq.load(std::memory_order_acquire); return hipSuccess; }
 hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) {
@@ -131,9 +144,9 @@ hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) {
   hipstub_stream_op(s);
   return hipSuccess;
 }
-hipError_t hipEventCreate(hipEvent_t* e) { *e = new ihipEvent_t; return hipSuccess; }
+hipError_t hipEventCreate(hipEvent_t* e) { *e = new ihipEvent_t; g_live[2]++; return hipSuccess; }
 hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return hipEventCreate(e); }
-hipError_t hipEventDestroy(hipEvent_t e) { delete e; return hipSuccess; }
+hipError_t hipEventDestroy(hipEvent_t e) { delete e; g_live[2]--; return hipSuccess; }
 hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) {
   if (fail_every() > 0 && g_armed.load(std::memory_order_relaxed) && (g_records.fetch_add(1, std::memory_order_relaxed) + 1) % fail_every() == 0) return hipErrorInvalidValue;
   hipstub_stream_op(s);

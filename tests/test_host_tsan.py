@@ -45,6 +45,11 @@ def build_driver(tmp_path, tree=ROOT, name="drive_tsan", sanitize="thread"):
     return exe
 
 
+def assert_nothing_alive(stdout):
+    """after the driver's last esvio_fe_destroy the stub's runtime holds no device block, pinned block, event or stream"""
+    assert "live: device 0 pinned 0 events 0 streams 0" in stdout, stdout[-500:]
+
+
 def run_driver(exe, seed, frames, timeout, **extra_env):
     env = dict(os.environ, TSAN_OPTIONS="suppressions=%s halt_on_error=0" % os.path.join(STUB, "tsan.supp"), **extra_env)
     return subprocess.run([exe, str(seed), str(frames)], capture_output=True, text=True, timeout=timeout, env=env)
@@ -60,6 +65,7 @@ def test_every_host_thread_under_thread_sanitizer(tmp_path):
         assert "drive ok:" in p.stdout, out[-2000:]
         calls = int(p.stdout.split("drive ok:")[1].split()[0])
         assert calls >= 300
+        assert_nothing_alive(p.stdout)
     # launches that fail in the middle of a call, on the calling thread or on the launch thread (whose first error
     # is sticky until esvio_fe_reset and travels to the caller's error text): every failed call is followed by a
     # reset in the driver, the stream goes on, nothing hangs, nothing races
@@ -72,6 +78,7 @@ def test_every_host_thread_under_thread_sanitizer(tmp_path):
         # launch thread's own HIP calls count too —: only the densest setting is held to a minimum)
         failed = int(p.stdout.split("handles,")[1].split()[0])
         assert failed >= (3 if every == "97" else 0), p.stdout
+        assert_nothing_alive(p.stdout)
 
 
 def test_host_side_under_address_and_ub_sanitizers(tmp_path):
@@ -85,6 +92,7 @@ def test_host_side_under_address_and_ub_sanitizers(tmp_path):
         out = p.stdout + p.stderr
         assert p.returncode == 0 and "drive ok:" in p.stdout, out[-3000:]
         assert "runtime error" not in out and "AddressSanitizer" not in out and "LeakSanitizer" not in out, out[-6000:]
+        assert_nothing_alive(p.stdout)
     # ... and on the failing exits: every 97th / 701st HIP call fails (calling thread or launch thread), the driver
     # resets and goes on — error paths are where buffers are forgotten or freed twice
     for every in ("97", "701"):
@@ -93,3 +101,4 @@ def test_host_side_under_address_and_ub_sanitizers(tmp_path):
         out = p.stdout + p.stderr
         assert p.returncode == 0 and "drive ok:" in p.stdout, out[-3000:]
         assert "runtime error" not in out and "AddressSanitizer" not in out and "LeakSanitizer" not in out, out[-6000:]
+        assert_nothing_alive(p.stdout)
