@@ -208,28 +208,25 @@ int esvio_fe_create(const esvio_fe_config* cfg, esvio_fe_handle* out) {
         return bail(ESVIO_FE_EHIP);
   }
   const size_t M = cfg->max_cnt;
+  const int Mc = cfg->max_cnt;
   int rc = 0;
   if ((rc = c->L2.alloc(c, (size_t)2 * c->P))) return bail(rc);
   if ((rc = c->S2.alloc(c, (size_t)2 * c->P))) return bail(rc);
   if ((rc = c->d_rejected.alloc(c, 1))) return bail(rc);
+  if ((rc = c->d_res.alloc(c, res_layout(Mc).total))) return bail(rc);
+  c->dres = res_view(c->d_res, Mc, 0);
+  c->dres.mask = nullptr;
   {
-    const ResLayout L = res_layout(M);
-    if ((rc = c->d_res.alloc(c, L.total))) return bail(rc);
-    c->d_ptsB = (float2*)(c->d_res + L.B1[0]);
-    c->d_ptsC = (float2*)(c->d_res + L.C1[0]);
-    c->d_stA = c->d_res + L.SA1[0];
-    c->d_stB = c->d_res + L.SB1[0];
-    c->d_counts = (int*)(c->d_res + L.CNT);
-    c->d_ptsA = (float2*)(c->d_res + L.A[0]);
-  }
-  {
-    const size_t stM = (std::max<size_t>(M, 1) + 63) / 64 * 64;
-    c->spec_bytes = std::max<size_t>(M, 1) * 16 + 2 * stM + 64;  // results + the wait-expired flag
-    c->spec_bytes = (c->spec_bytes + 255) / 256 * 256;
-    // (twice: the speculative launch's block, then the chained launch's)
-    if ((rc = c->h_spec.alloc(c, 2 * c->spec_bytes))) return bail(rc);
-    if (hipHostGetDevicePointer((void**)&c->z_spec, c->h_spec, 0) != hipSuccess) return bail(ESVIO_FE_EHIP);
-    std::memset(c->h_spec, 0, 2 * c->spec_bytes);
+    // (the speculative launch's block, then the chained launch's)
+    uint8_t* z_spec = nullptr;
+    const size_t bytes = kSpecBlocks * spec_layout(Mc).bytes;
+    if ((rc = c->h_spec.alloc(c, bytes))) return bail(rc);
+    if (hipHostGetDevicePointer((void**)&z_spec, c->h_spec, 0) != hipSuccess) return bail(ESVIO_FE_EHIP);
+    std::memset(c->h_spec, 0, bytes);
+    for (int b = 0; b < kSpecBlocks; b++) {
+      c->hspec[b] = spec_view(c->h_spec, Mc, b);
+      c->zspec[b] = spec_view(z_spec, Mc, b);
+    }
   }
   if ((rc = c->d_chain.alloc(c, 2 * std::max<size_t>(M, 1)))) return bail(rc);
   if ((rc = c->d_lane_gate.alloc(c, 16))) return bail(rc);
@@ -281,22 +278,20 @@ int esvio_fe_create(const esvio_fe_config* cfg, esvio_fe_handle* out) {
     if ((rc = c->d_eq_tmp.alloc(c, (size_t)2 * c->P))) return bail(rc);
     if ((rc = c->d_minmax.alloc(c, 4))) return bail(rc);
   }
-  if ((rc = c->h_pin.alloc(c, pin_bytes(*cfg)))) return bail(rc);
-  if (hipHostGetDevicePointer((void**)&c->z_res, c->h_pin, 0) != hipSuccess) return bail(ESVIO_FE_EHIP);
-  std::memset(c->h_pin, 0, c->h_pin.cap);
   {
-    const ResLayout L = res_layout(std::max<size_t>(M, 1));
-    c->z_counts = (int*)(c->z_res + L.CNT);
-    c->z_new = (float2*)(c->z_res + L.NEW);
-    c->z_ptsB2 = (float2*)(c->z_res + L.B2);
-    c->z_ptsC2 = (float2*)(c->z_res + L.C2);
-    c->z_stA2 = c->z_res + L.SA2;
-    c->z_stB2 = c->z_res + L.SB2;
+    uint8_t* z_res = nullptr;
+    if ((rc = c->h_pin.alloc(c, pin_bytes(Mc, cfg->width, cfg->height)))) return bail(rc);
+    if (hipHostGetDevicePointer((void**)&z_res, c->h_pin, 0) != hipSuccess) return bail(ESVIO_FE_EHIP);
+    std::memset(c->h_pin, 0, c->h_pin.cap);
+    for (int s = 0; s < 2; s++) {
+      c->pin[s] = res_view(c->h_pin, Mc, s);
+      c->zpin[s] = res_view(z_res, Mc, s);
+    }
   }
   if (hipMemsetAsync(c->L2, 0, (size_t)2 * c->P * 16, cur_stream(c)) != hipSuccess ||
       hipMemsetAsync(c->S2, 0, (size_t)2 * c->P * 16, cur_stream(c)) != hipSuccess ||
       hipMemsetAsync(c->d_rejected, 0, 8, cur_stream(c)) != hipSuccess ||
-      hipMemsetAsync(c->d_counts, 0, 64, cur_stream(c)) != hipSuccess ||
+      hipMemsetAsync(c->dres.counts, 0, 64, cur_stream(c)) != hipSuccess ||
       hipStreamSynchronize(cur_stream(c)) != hipSuccess)
     return bail(ESVIO_FE_EHIP);
   // One kernel of this library on every stream, now: the runtime loads the code object with the first
@@ -378,9 +373,9 @@ int esvio_fe_reset(esvio_fe_handle c) {
   stager_drain(c);
   c->cur_stage = -1;
   // (a call that failed with ESVIO_FE_EINTERNAL: the expired wait's flag, the sort's scratch words)
-  pin_of(c).counts[3] = 0;
+  c->pin[0].counts[3] = 0;
   if (c->hist) HIPCHK(c, hipMemsetAsync(c->hist, 0, c->hist.cap * 4, cur_stream(c)));
-  std::memset(c->h_spec, 0, 2 * c->spec_bytes);
+  std::memset(c->h_spec, 0, kSpecBlocks * spec_layout(c->cfg.max_cnt).bytes);
   c->spec_valid = false;
   c->chain_valid = false;
   c->chain_map_ok = false;
@@ -408,7 +403,7 @@ int esvio_fe_create_sae_stereo(esvio_fe_handle c, const esvio_fe_event* left, si
   unsigned long long rej = 0;
   HIPCHK(c, hipMemcpyAsync(&rej, c->d_rejected, 8, hipMemcpyDeviceToHost, cur_stream(c)));
   HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
-  if (pin_of(c).counts[3]) return fail(c, ESVIO_FE_EINTERNAL, "radix sort look-back spin expired");
+  if (int rc = lookback_expired(c)) return rc;
   if (n_rejected) *n_rejected = rej;
   if (c->prof_on) resolve_profile(c);
   return 0;
@@ -430,7 +425,7 @@ int esvio_fe_create_sae_stereo_mc(esvio_fe_handle c, const esvio_fe_event* left,
   unsigned long long rej = 0;
   HIPCHK(c, hipMemcpyAsync(&rej, c->d_rejected, 8, hipMemcpyDeviceToHost, cur_stream(c)));
   HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
-  if (pin_of(c).counts[3]) return fail(c, ESVIO_FE_EINTERNAL, "radix sort look-back spin expired");
+  if (int rc = lookback_expired(c)) return rc;
   if (n_rejected) *n_rejected = rej;
   if (c->prof_on) resolve_profile(c);
   return 0;
@@ -462,7 +457,7 @@ int slice_planes_out(esvio_fe_ctx* c, const double2* src, double* out, int space
   HIPCHK(c, hipMemcpyAsync(out, src, bytes, space == ESVIO_FE_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
                            cur_stream(c)));
   HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
-  if (pin_of(c).counts[3]) return fail(c, ESVIO_FE_EINTERNAL, "radix sort look-back spin expired");
+  if (int rc = lookback_expired(c)) return rc;
   return 0;
 }
 }  // namespace
@@ -624,7 +619,7 @@ int esvio_fe_features_to_track(esvio_fe_handle c, const esvio_fe_event* ev, size
   const EventRec *dL, *dR;
   if (int rc = stage_events(c, ev, n, nullptr, 0, space, &dL, &dR)) return rc;
   if (int rc = ensure_arc_capacity(c, n, c->cand_cur)) return rc;
-  Pin pin = pin_of(c);
+  const ResView& pin = c->pin[0];
   host::BitMask bm;
   bm.reset(c->W, c->H);
   if (mask) bm.from_bytes(mask);
@@ -635,7 +630,7 @@ int esvio_fe_features_to_track(esvio_fe_handle c, const esvio_fe_event* ev, size
   run_arc(c, dL, (uint32_t)n, &ts, true, false, true, c->cand_cur);
   run_compact(c, (uint32_t)n, c->cand_cur);
   run_select(c, c->cand_cur, max_corners, c->d_ptsD, 0, c->d_sel_idx);
-  HIPCHK(c, hipMemcpyAsync(pin.counts, c->d_counts, 8, hipMemcpyDeviceToHost, cur_stream(c)));
+  HIPCHK(c, hipMemcpyAsync(pin.counts, c->dres.counts, 8, hipMemcpyDeviceToHost, cur_stream(c)));
   HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
   const int k = pin.counts[0];
   if (k > 0) {
@@ -707,14 +702,15 @@ int esvio_fe_calc_optical_flow_pyr_lk(esvio_fe_handle c, const uint8_t* prev_img
   if (int rc = prep_tmp_pyr(c, 1, next_img, w, hgt, max_level)) return rc;
   PyrDesc two[2] = {c->tmp_pyr[0].d, c->tmp_pyr[1].d};
   pyr_build(c, two, 2);
-  HIPCHK(c, hipMemcpyAsync(c->d_ptsA, prev_pts, (size_t)n * 8, hipMemcpyHostToDevice, cur_stream(c)));
+  float2 *d_prev = (float2*)c->dres.A, *d_next = (float2*)c->dres.s1.fwd;
+  uint8_t* d_st = c->dres.s1.st_fwd;
+  HIPCHK(c, hipMemcpyAsync(d_prev, prev_pts, (size_t)n * 8, hipMemcpyHostToDevice, cur_stream(c)));
   if (flags & ESVIO_FE_LK_USE_INITIAL_FLOW)
-    HIPCHK(c, hipMemcpyAsync(c->d_ptsB, next_pts, (size_t)n * 8, hipMemcpyHostToDevice, cur_stream(c)));
-  LkArgs f = make_lk(two[0], two[1], c->d_ptsA, c->d_ptsB, c->d_ptsB, c->d_stA, nullptr, n, max_level,
-                     max_count, eps, flags);
+    HIPCHK(c, hipMemcpyAsync(d_next, next_pts, (size_t)n * 8, hipMemcpyHostToDevice, cur_stream(c)));
+  LkArgs f = make_lk(two[0], two[1], d_prev, d_next, d_next, d_st, nullptr, n, max_level, max_count, eps, flags);
   run_lk(c, f, nullptr, nullptr, nullptr);
-  HIPCHK(c, hipMemcpyAsync(next_pts, c->d_ptsB, (size_t)n * 8, hipMemcpyDeviceToHost, cur_stream(c)));
-  HIPCHK(c, hipMemcpyAsync(status, c->d_stA, (size_t)n, hipMemcpyDeviceToHost, cur_stream(c)));
+  HIPCHK(c, hipMemcpyAsync(next_pts, d_next, (size_t)n * 8, hipMemcpyDeviceToHost, cur_stream(c)));
+  HIPCHK(c, hipMemcpyAsync(status, d_st, (size_t)n, hipMemcpyDeviceToHost, cur_stream(c)));
   HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
   if (c->prof_on) resolve_profile(c);
   return 0;
@@ -943,7 +939,7 @@ int esvio_fe_good_features_to_track(esvio_fe_handle c, const uint8_t* img, int m
   if (int rc = prep_tmp_pyr(c, 0, img, c->W, c->H, 0)) return rc;
   PyrDesc d = c->tmp_pyr[0].d;
   pyr_build(c, &d, 1);  // materialises the reflect-101 border the Sobel taps read
-  Pin pin = pin_of(c);
+  const ResView& pin = c->pin[0];
   if (mask) {  // nonzero = allowed; the device bitmap holds the BLOCKED pixels
     host::BitMask bm;
     bm.reset(c->W, c->H);
@@ -954,14 +950,14 @@ int esvio_fe_good_features_to_track(esvio_fe_handle c, const uint8_t* img, int m
     HIPCHK(c, hipMemcpyAsync(c->d_mask_bits, pin.mask, bm.bits.size() * 4, hipMemcpyHostToDevice,
                              cur_stream(c)));
   }
-  if (int rc = gftt_run(c, d, max_corners, quality, min_distance, mask != nullptr, c->z_new, 0,
-                        c->z_counts))
+  if (int rc = gftt_run(c, d, max_corners, quality, min_distance, mask != nullptr, (float2*)c->zpin[0].news, 0,
+                        c->zpin[0].counts))
     return rc;
   if (eig_out)
     HIPCHK(c, hipMemcpyAsync(eig_out, c->d_gftt_eig, (size_t)c->W * c->H * 4, hipMemcpyDeviceToHost,
                              cur_stream(c)));
   HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
-  if (pin.counts[3]) return fail(c, ESVIO_FE_EINTERNAL, "radix sort look-back spin expired");
+  if (int rc = lookback_expired(c)) return rc;
   const int k = pin.counts[0];
   std::memcpy(out_xy, pin.news, (size_t)k * 8);
   *n_out = k;
@@ -1021,8 +1017,7 @@ int esvio_fe_pack_track_records(esvio_fe_handle c, float* out, int32_t* n_rows) 
     HIPCHK(c, hipSetDevice(c->dev));
     // (in this order: the previous published frame's new corners — which that frame's call may have left to "the next
     // call" while their stereo LK was running — extend the map this frame's right-camera velocities read)
-    if (int rc = finalize_pending(c)) return rc;
-    if (int rc = finalize_right(c)) return rc;
+    if (int rc = finalize_lazy(c)) return rc;
   }
   const int rows = 2 * std::max(c->cfg.max_cnt, 1);
   int k = 0;
@@ -1176,8 +1171,7 @@ int esvio_fe_exchange_end(esvio_fe_handle c, float* gathered) {
 int esvio_fe_set_lazy_new_stereo(esvio_fe_handle c, int on) {
   if (!c) return ESVIO_FE_EINVAL;
   HIPCHK(c, hipSetDevice(c->dev));
-  if (int rc = finalize_pending(c)) return rc;
-  if (int rc = finalize_right(c)) return rc;
+  if (int rc = finalize_lazy(c)) return rc;
   c->lazy_new = on != 0;
   return 0;
 }
@@ -1193,8 +1187,7 @@ int esvio_fe_set_host_threads(esvio_fe_handle c, int threads) {
 int esvio_fe_finish(esvio_fe_handle c, esvio_fe_tracks* out) {
   if (!c) return ESVIO_FE_EINVAL;
   HIPCHK(c, hipSetDevice(c->dev));
-  if (int rc = finalize_pending(c)) return rc;
-  if (int rc = finalize_right(c)) return rc;
+  if (int rc = finalize_lazy(c)) return rc;
   return fill_tracks(c, out);
 }
 

@@ -7,6 +7,8 @@
 //                  (prefetch stream, speculative / chained temporal LK, lazy right-camera tails)
 //   fe_image.cpp   FeatureTracker::trackImage and goodFeaturesToTrack
 //   fe_api.cpp     the C ABI entry points
+//   fe_layout.h    the layout of the blocks the LK kernels work in (d_res / h_pin, h_spec) and the views of them
+//                  the handle keeps; no HIP, every offset into those blocks is computed there
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -29,6 +31,7 @@
 #include "../../include/esvio_fe_test.h"
 #include "fe_host.h"
 #include "fe_kernels.h"
+#include "fe_layout.h"
 #include "fe_mc.h"
 #include "fe_res.h"
 
@@ -36,10 +39,6 @@ using namespace esvio;
 
 namespace esvio {
 namespace fe {
-
-struct P2f {
-  float x, y;
-};
 
 // std::map<int, cv::Point2f> as ptsVelocity uses it (insert-if-absent, find, empty, clear), kept as a
 // sorted flat vector: same semantics, no node allocations per frame
@@ -137,8 +136,8 @@ using namespace esvio::fe;
 // Every device buffer, pinned block, event and stream below is a member that releases itself (fe_res.h).  The
 // members' destruction order — the reverse of their declaration — carries no dependency: esvio_fe_destroy deletes the
 // handle only after its threads have stopped and every stream is idle, and the one step that has an order (the
-// RCCL communicator before the stream it runs on) is written out there.  Pointers INTO a block (d_ptsA...d_counts
-// into d_res, z_* into h_pin / h_spec) stay raw: only the block is owned.
+// RCCL communicator before the stream it runs on) is written out there.  Pointers INTO a block (the views of
+// d_res, h_pin and h_spec, fe_layout.h) stay raw: only the block is owned.
 struct esvio_fe_ctx {
   esvio_fe_config cfg{};
   int dev = 0;
@@ -253,36 +252,30 @@ struct esvio_fe_ctx {
   DevBuf<uint8_t> d_lut;
   DevBuf<int> d_minmax;
   // device-side point / status buffers of the standalone entry points (LK, featuresToTrack) and the
-  // selection counters; one allocation with the layout of ResLayout
+  // selection counters; one allocation with the layout of ResLayout (dres: its view, no mask area)
   DevBuf<uint8_t> d_res;
+  ResView dres{};
   DevBuf<float2> d_ptsD;
-  float2 *d_ptsA = nullptr, *d_ptsB = nullptr, *d_ptsC = nullptr;
-  uint8_t *d_stA = nullptr, *d_stB = nullptr;
-  int* d_counts = nullptr;  // [0]=n_out (select) [1]=n_total (kept + new: the LK kernels' n_ptr)
   // The per-frame path works on the pinned host block itself (device-visible): the LK kernels read
   // their points from it and write results into it, k_select mirrors its counters into it — no
   // H2D / D2H copy calls on the frame's critical path (each costs more host time than the few
-  // hundred bytes take over PCIe).  z_* = device-side addresses of the h_pin / h_spec regions.
-  uint8_t *z_res = nullptr, *z_spec = nullptr;
-  // (set 1 — temporal LK, then stereo LK of the survivors — exists twice, see pin_of(); its device
-  // addresses come from zdev())
-  float2 *z_new = nullptr, *z_ptsB2 = nullptr, *z_ptsC2 = nullptr;
-  uint8_t *z_stA2 = nullptr, *z_stB2 = nullptr;
-  int* z_counts = nullptr;
+  // hundred bytes take over PCIe).  pin[s] / hspec[b] = the host's views of h_pin (by copy of set 1) and of
+  // h_spec (by block), zpin[s] / zspec[b] = the same regions at their device-side addresses; built once, at create.
+  ResView pin[2] = {}, zpin[2] = {};
+  SpecView hspec[kSpecBlocks] = {}, zspec[kSpecBlocks] = {};
   int res_set = 0;  // which copy of set 1 the current frame works in
   int lks_last = -1;  // copy the latest stereo LK launch (stream4) writes to, -1: none so far
   // ---- speculative temporal LK of the next frame (replay mode): once this frame's kept points
   // and new corners are final, next frame's calcOpticalFlowPyrLK(cur -> next) pair is launched on
   // stream3 against the prefetched pyramids, so it overlaps this frame's stereo LK and host tail
-  PinBuf<uint8_t> h_spec;  // pinned, device-visible: [ptsB | ptsC | stA | stB] of that launch
-  size_t spec_bytes = 0;
+  PinBuf<uint8_t> h_spec;  // pinned, device-visible: [ptsB | ptsC | stA | stB | wait-expired flag] of that launch (SpecLayout)
   bool spec_valid = false;
   int spec_n = 0;             // number of points of that launch (= the next frame's prev_pts.size())
   // ---- chained temporal LK of the frame after next: when the next frame publishes nothing, the
   // frame after it tracks exactly the next frame's forward results, point by point, so its launch
   // (stream4) is made together with the speculative one and each of its waves starts the moment the
   // producer's wave of the same index publishes its forward result (LkArgs::chain_*).  Results:
-  // second half of h_spec, indexed like the producer's points; the intermediate frame's temporal
+  // second block of h_spec, indexed like the producer's points; the intermediate frame's temporal
   // filter gives the map from the final frame's prev_pts to those indices.
   DevBuf<unsigned long long> d_chain;  // [2 * max_cnt] published forward results
   // one word per prefetch lane: the serial number of the last prefetch sequence that has RUN there (LkArgs::gate_*)
@@ -366,7 +359,7 @@ struct esvio_fe_ctx {
   DevBuf<uint32_t> d_fast_cxy, d_fast_cscore, d_fast_tot;
   DevBuf<uint8_t> d_fast_img;  // a caller's host image (linear, width*height)
   bool fast_lds = false;          // (ESVIO_FE_FAST_LDS=1: k_fast_score's LDS-tiled form, for the A/B in KERNELS.md)
-  // pinned host staging (layout: pin_of())
+  // pinned host staging (h_pin's layout: ResLayout)
   PinBuf<uint8_t> h_img;  // copy_level0_in's staging ring: pinned host side ...
   DevBuf<uint8_t> d_img;  // ... and its device side (linear images)
   unsigned img_stage_next = 0;

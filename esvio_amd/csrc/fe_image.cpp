@@ -132,7 +132,7 @@ int gftt_run(esvio_fe_ctx* c, const PyrDesc& d, int max_corners, double quality,
     for (int p = 0; p < 4; p++) {
       launch_radix_pass(cur_stream(c), c->keys[cur], c->vals[cur], n, 8 * p, 8, ghist + ((size_t)p << 8),
                         lookback + (size_t)p * (nb << 8), tickets + p, c->keys[cur ^ 1],
-                        c->vals[cur ^ 1], c->z_counts + 3, c->lim.lookback);
+                        c->vals[cur ^ 1], c->zpin[0].counts + 3, c->lim.lookback);
       cur ^= 1;
     }
     HIPCHK(c, hipMemsetAsync(c->hist, 0, (size_t)head * 4, cur_stream(c)));  // as k_sae_apply leaves it
@@ -151,8 +151,8 @@ int gftt_run(esvio_fe_ctx* c, const PyrDesc& d, int max_corners, double quality,
   sa.out_pts = out_pts;
   sa.out_idx = nullptr;
   sa.out_base = out_base;
-  sa.n_out = c->d_counts;
-  sa.n_total = c->d_counts + 1;
+  sa.n_out = c->dres.counts;
+  sa.n_total = c->dres.counts + 1;
   sa.host_counts = host_counts;
   sa.init_bits = nullptr;
   sa.gbitmap = nullptr;
@@ -206,10 +206,9 @@ int track_image_impl(esvio_fe_ctx* c, double _cur_time, const uint8_t* img_left,
                      const uint8_t* img_right, bool PUB_THIS_FRAME) {
   const esvio_fe_config& cfg = c->cfg;
   const int M = cfg.max_cnt;
-  if (int rc = finalize_pending(c)) return rc;  // (a lazy trackEvent call came before)
-  if (int rc = finalize_right(c)) return rc;
+  if (int rc = finalize_lazy(c)) return rc;  // (a lazy trackEvent call came before)
   if (int rc = cancel_chain(c)) return rc;
-  Pin pin = pin_of(c);
+  const ResView &pin = c->pin[0], &zpin = c->zpin[0];
   c->cur_time = _cur_time;
   const bool first = !c->have_img;
   const bool have_right = img_right != nullptr;
@@ -251,18 +250,14 @@ int track_image_impl(esvio_fe_ctx* c, double _cur_time, const uint8_t* img_left,
   if (c->prev_pts.size() > 0) {  // :180-209: forward, and backward with maxLevel 3 / no initial flow
     const int n = (int)c->prev_pts.size();
     std::memcpy(pin.A, c->prev_pts.data(), (size_t)n * 8);
-    LkArgs f = make_lk(prevL, L, zdev(c, pin.A), nullptr, zdev(c, pin.ptsB), zdev(c, pin.stA), nullptr, n, 3, 30, 0.01, 0);
-    LkArgs b = make_lk(L, prevL, nullptr, nullptr, nullptr, nullptr, nullptr, n, 3, 30, 0.01, 0);
-    run_lk(c, f, cfg.flow_back ? &b : nullptr, zdev(c, pin.ptsC), zdev(c, pin.stB));
+    run_lk_pair(c, lk_pair(prevL, L, zpin.A, nullptr, n, kLkStereo, zpin.s1));
     HIPCHK(c, sync_main(c));
-    std::vector<uint8_t> status(pin.stA, pin.stA + n);
-    c->cur_pts.resize(n);
-    std::memcpy(c->cur_pts.data(), pin.ptsB, (size_t)n * 8);
-    if (cfg.flow_back) {
-      const P2f* reverse_pts = (const P2f*)pin.ptsC;
+    const LkOut& r = pin.s1;
+    std::vector<uint8_t> status(r.st_fwd, r.st_fwd + n);
+    c->cur_pts.assign(r.fwd, r.fwd + n);
+    if (cfg.flow_back)
       for (int i = 0; i < n; i++)
-        status[i] = status[i] && pin.stB[i] && pt_distance(c->prev_pts[i], reverse_pts[i]) <= 0.5;
-    }
+        status[i] = status[i] && r.st_back[i] && pt_distance(c->prev_pts[i], r.back[i]) <= 0.5;
     for (int i = 0; i < n; i++)
       if (status[i] && !in_border_event(c, c->cur_pts[i])) status[i] = 0;
     reduce_vector(c->prev_pts, status);
@@ -280,13 +275,11 @@ int track_image_impl(esvio_fe_ctx* c, double _cur_time, const uint8_t* img_left,
       std::memcpy(pin.mask, c->mask_event.bits.data(), c->mask_event.bits.size() * 4);
       HIPCHK(c, hipMemcpyAsync(c->d_mask_bits, pin.mask, c->mask_event.bits.size() * 4,
                                hipMemcpyHostToDevice, cur_stream(c)));
-      if (int rc = gftt_run(c, L, n_max_cnt, 0.01, (double)cfg.min_dist, true, c->z_new, 0, c->z_counts))
+      if (int rc = gftt_run(c, L, n_max_cnt, 0.01, (double)cfg.min_dist, true, (float2*)zpin.news, 0, zpin.counts))
         return rc;
       HIPCHK(c, sync_main(c));
-      if (pin.counts[3] != 0) return fail(c, ESVIO_FE_EINTERNAL, "radix sort look-back spin expired");
-      const int n_new = pin.counts[0];
-      const P2f* np = (const P2f*)pin.news;
-      for (int i = 0; i < n_new; i++) c->n_pts.push_back(np[i]);
+      if (int rc = lookback_expired(c)) return rc;
+      c->n_pts.assign(pin.news, pin.news + pin.counts[0]);
     }
     for (auto& p : c->n_pts) {
       c->cur_pts.push_back(p);
@@ -308,19 +301,15 @@ int track_image_impl(esvio_fe_ctx* c, double _cur_time, const uint8_t* img_left,
     if (!c->cur_pts.empty()) {
       const int n = (int)c->cur_pts.size();
       std::memcpy(pin.A, c->cur_pts.data(), (size_t)n * 8);
-      LkArgs f = make_lk(L, R, zdev(c, pin.A), nullptr, zdev(c, pin.ptsB), zdev(c, pin.stA), nullptr, n, 3, 30, 0.01, 0);
-      LkArgs b = make_lk(R, L, nullptr, nullptr, nullptr, nullptr, nullptr, n, 3, 30, 0.01, 0);
-      run_lk(c, f, cfg.flow_back ? &b : nullptr, zdev(c, pin.ptsC), zdev(c, pin.stB));
+      run_lk_pair(c, lk_pair(L, R, zpin.A, nullptr, n, kLkStereo, zpin.s1));
       HIPCHK(c, sync_main(c));
-      std::vector<uint8_t> status(pin.stA, pin.stA + n);
-      c->cur_right_pts.resize(n);
-      std::memcpy(c->cur_right_pts.data(), pin.ptsB, (size_t)n * 8);
-      if (cfg.flow_back) {
-        const P2f* reverseLeftPts = (const P2f*)pin.ptsC;
+      const LkOut& r = pin.s1;
+      std::vector<uint8_t> status(r.st_fwd, r.st_fwd + n);
+      c->cur_right_pts.assign(r.fwd, r.fwd + n);
+      if (cfg.flow_back)
         for (int i = 0; i < n; i++)
-          status[i] = status[i] && pin.stB[i] && in_border_event(c, c->cur_right_pts[i]) &&
-                      pt_distance(c->cur_pts[i], reverseLeftPts[i]) <= 0.5;
-      }
+          status[i] = status[i] && r.st_back[i] && in_border_event(c, c->cur_right_pts[i]) &&
+                      pt_distance(c->cur_pts[i], r.back[i]) <= 0.5;
       c->ids_right = c->ids;
       reduce_vector(c->cur_right_pts, status);
       reduce_vector(c->ids_right, status);

@@ -16,28 +16,9 @@ void reduce_vector(std::vector<T>& v, const std::vector<uint8_t>& status) {  // 
 
 inline uint8_t* px00(const PyrDesc& d) { return d.img[0] + (size_t)kPad * d.stride[0] + kPad; }
 
-// device result block (and its pinned mirror): set 1 = temporal LK, then stereo LK of the temporal
-// survivors; set 2 = stereo LK of the newly selected corners
-struct ResLayout {
-  size_t B1[2], C1[2], SA1[2], SB1[2], A[2], CNT, NEW, B2, C2, SA2, SB2, total;
-};
-
-// pinned staging: a mirror of the device result block (D2H) + upload areas (H2D)
-struct Pin {
-  float2 *ptsB, *ptsC;    // set 1 (the copy asked for)
-  uint8_t *stA, *stB;
-  int* counts;            // [16]
-  float2* news;           // [kept points (as uploaded) | newly selected corners]
-  float2 *ptsB2, *ptsC2;  // set 2
-  uint8_t *stA2, *stB2;
-  float2* A;              // LK input points (read by the kernels in place)
-  uint32_t* mask;         // H2D H*wpr words
-};
-
-// device-side address of a location inside the pinned block
-template <typename T>
-T* zdev(esvio_fe_ctx* c, T* host) {
-  return (T*)(c->z_res + ((uint8_t*)host - c->h_pin));
+// the sort passes and the tiled update raise this word of the pinned block when a bounded spin runs out
+inline int lookback_expired(esvio_fe_ctx* c) {
+  return c->pin[0].counts[3] ? fail(c, ESVIO_FE_EINTERNAL, "radix sort look-back spin expired") : 0;
 }
 
 // ---------------------------------------------------------------- fe_stages.cpp
@@ -66,6 +47,18 @@ LkArgs make_lk(const PyrDesc& P, const PyrDesc& N, const float2* prev, const flo
                uint8_t* status, const int* n_ptr, int n_max, int max_level, int max_count, double eps,
                int flags);
 void run_lk(esvio_fe_ctx* c, const LkArgs& f, const LkArgs* b, float2* back_pts, uint8_t* back_status);
+// A forward call P -> N from `src` (null: chained input) and its reverse N -> P, both into `out` (device addresses).
+// Temporal (:410, :416-418): the reverse with maxLevel 1 and USE_INITIAL_FLOW, seeded with the source points;
+// stereo (:490, :495, and both pairs of trackImage): the reverse like the forward call.  The caller sets the
+// poll_* / chain_* / gate_* fields of f; run_lk_pair launches the reverse call with it if cfg.flow_back.
+enum LkPairKind { kLkTemporal, kLkStereo };
+struct LkPair {
+  LkArgs f, b;
+  LkOut out;
+};
+LkPair lk_pair(const PyrDesc& P, const PyrDesc& N, const P2f* src, const int* n_ptr, int n_max, LkPairKind kind,
+               const LkOut& out);
+void run_lk_pair(esvio_fe_ctx* c, const LkPair& p);
 int copy_level0_out(esvio_fe_ctx* c, const PyrDesc& d, uint8_t* out);
 int copy_level0_in(esvio_fe_ctx* c, const PyrDesc& d, const uint8_t* in);
 bool in_border_event(const esvio_fe_ctx* c, const P2f& pt);
@@ -75,9 +68,6 @@ std::vector<P2f> undistorted_pts(const std::vector<P2f>& pts, const esvio_fe_cam
 std::vector<P2f> pts_velocity_fn(std::vector<int>& ids, std::vector<P2f>& pts, IdMap& cur_id_pts,
                                  IdMap& prev_id_pts, double dt, size_t n_left);
 void reject_with_f_event(esvio_fe_ctx* c);
-ResLayout res_layout(size_t M);
-Pin pin_of(esvio_fe_ctx* c, int set = 0);
-size_t pin_bytes(const esvio_fe_config& cfg);
 void clear_tracker_state(esvio_fe_ctx* c);
 SelectArgs make_select_args(esvio_fe_ctx* c, int set, int max_corners, float2* out_pts, int out_base,
                             int32_t* out_idx);
@@ -121,8 +111,7 @@ int launcher_drain(esvio_fe_ctx* c);          // every job handed over has been 
 int launcher_wait_lane(esvio_fe_ctx* c, int lane);  // ... the job that records this lane's events
 void launcher_clear_error(esvio_fe_ctx* c);   // esvio_fe_reset: a failed job.s sticky error is dropped with the batches
 int cancel_chain(esvio_fe_ctx* c);
-int finalize_right(esvio_fe_ctx* c);
-int finalize_pending(esvio_fe_ctx* c);
+int finalize_lazy(esvio_fe_ctx* c);  // what lazy calls left open: the new corners' right entries, then the right-camera tail
 int track_event_impl(esvio_fe_ctx* c, double cur_time, const esvio_fe_event* left, size_t nL,
                      const esvio_fe_event* right, size_t nR, int space, bool PUB_THIS_FRAME,
                      const esvio_fe_motion* motion = nullptr);

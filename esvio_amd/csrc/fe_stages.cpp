@@ -216,7 +216,7 @@ int sae_update_tiled(esvio_fe_ctx* c, const EventRec* evL, uint32_t nL, const Ev
   {
     ScopedKernel k(c, K_TILE_APPLY, (uint64_t)n * 32);
     launch_tile_apply(cur_stream(c), c->d_part, n, c->tgeom, sc, L2, S2, c->cfg.feature_filter_threshold,
-                      arc_touched, c->z_counts + 3, c->lim.ticket);
+                      arc_touched, c->zpin[0].counts + 3, c->lim.ticket);
   }
   return 0;
 }
@@ -256,7 +256,7 @@ int sae_update(esvio_fe_ctx* c, const EventRec* evL, uint32_t nL, const EventRec
     ScopedKernel k(c, K_RADIX_PASS, (uint64_t)n * 16);
     launch_radix_pass(cur_stream(c), c->keys[cur], c->vals[cur], n, p * bits, bits, ghist + ((size_t)p << bits),
                       lookback + (size_t)p * (nblk << bits), tickets + p, c->keys[cur ^ 1],
-                      c->vals[cur ^ 1], c->z_counts + 3, c->lim.lookback);
+                      c->vals[cur ^ 1], c->zpin[0].counts + 3, c->lim.lookback);
     cur ^= 1;
   }
   {
@@ -458,6 +458,19 @@ void run_lk(esvio_fe_ctx* c, const LkArgs& f, const LkArgs* b, float2* back_pts,
   launch_lk(cur_stream(c), fa, b, back_pts, back_status);
 }
 
+LkPair lk_pair(const PyrDesc& P, const PyrDesc& N, const P2f* src, const int* n_ptr, int n_max, LkPairKind kind,
+               const LkOut& out) {
+  const bool t = kind == kLkTemporal;
+  return LkPair{make_lk(P, N, (const float2*)src, nullptr, (float2*)out.fwd, out.st_fwd, n_ptr, n_max, 3, 30, 0.01, 0),
+                make_lk(N, P, nullptr, nullptr, nullptr, nullptr, n_ptr, n_max, t ? 1 : 3, 30, 0.01,
+                        t ? ESVIO_FE_LK_USE_INITIAL_FLOW : 0),
+                out};
+}
+
+void run_lk_pair(esvio_fe_ctx* c, const LkPair& p) {
+  run_lk(c, p.f, c->cfg.flow_back ? &p.b : nullptr, (float2*)p.out.back, p.out.st_back);
+}
+
 // A caller's W x H image <-> level 0 of a padded pyramid.  Not as one 2-D copy between the caller's
 // pageable memory and the pitched device image: the runtime does that row by row (4.5 ms for a
 // stereo pair of 346 x 260 images, more than the rest of trackImage together).  The rows go through
@@ -630,60 +643,6 @@ void reject_with_f_event(esvio_fe_ctx* c) {  // :910-947
   }
 }
 
-// device result block (and its pinned mirror): set 1 = temporal LK, then stereo LK of the temporal
-// survivors; set 2 = stereo LK of the newly selected corners
-
-ResLayout res_layout(size_t M) {
-  const size_t stM = (M + 63) / 64 * 64;
-  ResLayout L;
-  size_t o = 0;
-  for (int s = 0; s < 2; s++) {
-    L.B1[s] = o;  o += M * 8;
-    L.C1[s] = o;  o += M * 8;
-    L.SA1[s] = o; o += stM;
-    L.SB1[s] = o; o += stM;
-    L.A[s] = o;   o += M * 8;
-  }
-  L.CNT = o; o += 64;
-  L.NEW = o; o += M * 8;
-  L.B2 = o;  o += M * 8;
-  L.C2 = o;  o += M * 8;
-  L.SA2 = o; o += stM;
-  L.SB2 = o; o += stM;
-  L.total = o;
-  return L;
-}
-
-
-Pin pin_of(esvio_fe_ctx* c, int set) {
-  const size_t M = std::max(c->cfg.max_cnt, 1);
-  const ResLayout L = res_layout(M);
-  Pin p;
-  uint8_t* b = c->h_pin;
-  p.ptsB = (float2*)(b + L.B1[set]);
-  p.ptsC = (float2*)(b + L.C1[set]);
-  p.stA = b + L.SA1[set];
-  p.stB = b + L.SB1[set];
-  p.counts = (int*)(b + L.CNT);
-  p.news = (float2*)(b + L.NEW);
-  p.A = (float2*)(b + L.A[set]);
-  p.ptsB2 = (float2*)(b + L.B2);
-  p.ptsC2 = (float2*)(b + L.C2);
-  p.stA2 = b + L.SA2;
-  p.stB2 = b + L.SB2;
-  b += (L.total + 255) / 256 * 256;
-  p.mask = (uint32_t*)b;
-  return p;
-}
-
-
-size_t pin_bytes(const esvio_fe_config& cfg) {
-  const size_t M = std::max(cfg.max_cnt, 1);
-  const ResLayout L = res_layout(M);
-  return (L.total + 255) / 256 * 256 +
-         (size_t)cfg.height * ((cfg.width + 31) / 32) * 4 + 256;
-}
-
 void clear_tracker_state(esvio_fe_ctx* c) {
   c->prev_pts.clear();
   c->cur_pts.clear();
@@ -725,8 +684,8 @@ SelectArgs make_select_args(esvio_fe_ctx* c, int set, int max_corners, float2* o
   s.out_pts = out_pts;
   s.out_idx = out_idx;
   s.out_base = out_base;
-  s.n_out = c->d_counts;
-  s.n_total = c->d_counts + 1;
+  s.n_out = c->dres.counts;
+  s.n_total = c->dres.counts + 1;
   s.host_counts = nullptr;
   s.init_bits = nullptr;
   s.gbitmap = nullptr;

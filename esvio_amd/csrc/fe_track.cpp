@@ -323,35 +323,34 @@ int prefetch_next(esvio_fe_ctx* c, bool wait_planes, bool must_take_first) {
   return rc;
 }
 
+static uint32_t next_chain_seq(esvio_fe_ctx* c) {  // 30 bits, never 0 (LkArgs::chain_seq)
+  c->chain_seq = (c->chain_seq + 1) & 0x3fffffffu;
+  if (!c->chain_seq) c->chain_seq = 1;
+  return c->chain_seq;
+}
+
 // Launch the NEXT frame's temporal forward/backward LK (feature_tracker.cpp:410,417 of the next
-// call) now: its inputs are final once this frame's kept points (written to z_new[0..n_kept)) and
-// new corners (written by k_select behind them, total count in d_counts[1]) are known, and the next
+// call) now: its inputs are final once this frame's kept points (written to news[0..n_kept)) and
+// new corners (written by k_select behind them, total count in counts[1]) are known, and the next
 // frame's pyramids are already being built on the prefetch stream.
 int enqueue_spec_temporal(esvio_fe_ctx* c, const Inflight& nxt /* the next frame's batch */,
                           int n_kept, bool with_new) {
-  const size_t M = std::max(c->cfg.max_cnt, 1);
-  const size_t stM = (M + 63) / 64 * 64;
   // (kept points: already in host memory; new corners: published one by one by the k_select that
   // has just been launched — the waves of points >= n_kept wait for their slot)
   if (int rc = launcher_wait_lane(c, nxt.lane)) return rc;
   HIPCHK(c, hipStreamWaitEvent(c->stream3, c->ev_lane_done[nxt.lane], 0));
-  float2* B = (float2*)c->z_spec;  // results land in the pinned block itself
-  float2* Cb = B + M;
-  uint8_t* sA = c->z_spec + M * 16;
-  uint8_t* sB = sA + stM;
   const PyrDesc& P = c->pyr[c->slot_curL].d;
   const PyrDesc& N = c->pyr[nxt.slotL].d;
-  const int n_max = with_new ? (int)M : n_kept;
-  LkArgs f = make_lk(P, N, c->z_new, nullptr, B, sA, nullptr, n_max, 3, 30, 0.01, 0);
-  LkArgs b = make_lk(N, P, nullptr, nullptr, nullptr, nullptr, nullptr, n_max, 1, 30, 0.01,
-                     ESVIO_FE_LK_USE_INITIAL_FLOW);
+  const int n_max = with_new ? (int)layout_points(c->cfg.max_cnt) : n_kept;
+  // (results land in the pinned block itself)
+  LkPair sp = lk_pair(P, N, c->zpin[0].news, nullptr, n_max, kLkTemporal, c->zspec[0].out);
   if (with_new) {
-    f.poll_slots = c->d_pub_slots;
-    f.poll_done = c->d_pub_done;
-    f.poll_seq = c->pub_seq;
-    f.poll_from = n_kept;
-    f.poll_err = (int*)(c->z_spec + M * 16 + 2 * stM);
-    f.poll_ticks = c->lim.poll;
+    sp.f.poll_slots = c->d_pub_slots;
+    sp.f.poll_done = c->d_pub_done;
+    sp.f.poll_seq = c->pub_seq;
+    sp.f.poll_from = n_kept;
+    sp.f.poll_err = c->zspec[0].expired;
+    sp.f.poll_ticks = c->lim.poll;
   }
   // the frame after next, chained to this launch point by point (see esvio_fe_ctx::d_chain)
   const Inflight* nxt2 = nullptr;
@@ -359,14 +358,12 @@ int enqueue_spec_temporal(esvio_fe_ctx* c, const Inflight& nxt /* the next frame
       !c->chain_valid)
     nxt2 = &c->inflight[1];
   if (nxt2) {
-    c->chain_seq = (c->chain_seq + 1) & 0x3fffffffu;
-    if (!c->chain_seq) c->chain_seq = 1;
-    f.chain_out = c->d_chain;
-    f.chain_seq = c->chain_seq;
+    sp.f.chain_out = c->d_chain;
+    sp.f.chain_seq = next_chain_seq(c);
   }
   {
     StreamScope on_spec_stream(c->stream3);
-    run_lk(c, f, c->cfg.flow_back ? &b : nullptr, Cb, sB);
+    run_lk_pair(c, sp);
   }
   HIPCHK(c, hipEventRecord(c->ev_spec_done, c->stream3));
   c->spec_valid = true;
@@ -380,22 +377,19 @@ int enqueue_spec_temporal(esvio_fe_ctx* c, const Inflight& nxt /* the next frame
       if (int rc = launcher_wait_lane(c, nxt2->lane)) return rc;
     HIPCHK(c, hipStreamWaitEvent(c->stream4, c->ev_lane_done[nxt.lane], 0));
     if (!gated) HIPCHK(c, hipStreamWaitEvent(c->stream4, c->ev_lane_done[nxt2->lane], 0));
-    uint8_t* zc = c->z_spec + c->spec_bytes;
     const PyrDesc& N2 = c->pyr[nxt2->slotL].d;
-    LkArgs f2 = make_lk(N, N2, nullptr, nullptr, (float2*)zc, zc + M * 16, nullptr, n_max, 3, 30, 0.01, 0);
-    LkArgs b2 = make_lk(N2, N, nullptr, nullptr, nullptr, nullptr, nullptr, n_max, 1, 30, 0.01,
-                        ESVIO_FE_LK_USE_INITIAL_FLOW);
-    f2.chain_in = c->d_chain;
-    f2.chain_seq = c->chain_seq;
-    f2.chain_ticks = c->lim.chain;
-    f2.poll_err = (int*)(zc + M * 16 + 2 * stM);
+    LkPair ch = lk_pair(N, N2, nullptr, nullptr, n_max, kLkTemporal, c->zspec[1].out);
+    ch.f.chain_in = c->d_chain;
+    ch.f.chain_seq = c->chain_seq;
+    ch.f.chain_ticks = c->lim.chain;
+    ch.f.poll_err = c->zspec[1].expired;
     if (gated) {
-      f2.gate_ptr = c->d_lane_gate + nxt2->lane;
-      f2.gate_val = nxt2->gate;
+      ch.f.gate_ptr = c->d_lane_gate + nxt2->lane;
+      ch.f.gate_val = nxt2->gate;
     }
     {
       StreamScope on_chain_stream(c->stream4);
-      run_lk(c, f2, c->cfg.flow_back ? &b2 : nullptr, (float2*)zc + M, zc + M * 16 + stM);
+      run_lk_pair(c, ch);
     }
     HIPCHK(c, hipEventRecord(c->ev_chain_done, c->stream4));
     c->chain_valid = true;
@@ -420,7 +414,7 @@ int cancel_chain(esvio_fe_ctx* c) {
 // only the kept ones in lazy mode): the stereo LK results of the kept points are in set 1 (by
 // survivor index, src == nullptr: identity), those of the new corners in set 2.  n_left = the
 // frame's left point count (ptsVelocity's sizing quirk).
-void right_tail(esvio_fe_ctx* c, const Pin& pin, const P2f* left, const int* ids, const int* src,
+void right_tail(esvio_fe_ctx* c, const LkOut& kept, const P2f* left, const int* ids, const int* src,
                 int n, int n_kept, double dt, size_t n_left) {
   const esvio_fe_config& cfg = c->cfg;
   c->ids_right.clear();
@@ -434,22 +428,13 @@ void right_tail(esvio_fe_ctx* c, const Pin& pin, const P2f* left, const int* ids
     std::vector<uint8_t> status(n), statusRightLeft(n);
     std::vector<P2f> reverseLeftPts(n);
     c->cur_right_pts.resize(n);
-    const P2f *B1 = (const P2f*)pin.ptsB, *C1 = (const P2f*)pin.ptsC;
-    const P2f *B2 = (const P2f*)pin.ptsB2, *C2 = (const P2f*)pin.ptsC2;
     for (int i = 0; i < n; i++) {
-      if (i < n_kept) {
-        const int j = src ? src[i] : i;
-        c->cur_right_pts[i] = B1[j];
-        status[i] = pin.stA[j];
-        reverseLeftPts[i] = C1[j];
-        statusRightLeft[i] = pin.stB[j];
-      } else {
-        const int j = i - n_kept;
-        c->cur_right_pts[i] = B2[j];
-        status[i] = pin.stA2[j];
-        reverseLeftPts[i] = C2[j];
-        statusRightLeft[i] = pin.stB2[j];
-      }
+      const LkOut& r = i < n_kept ? kept : c->pin[0].s2;
+      const int j = i < n_kept ? (src ? src[i] : i) : i - n_kept;
+      c->cur_right_pts[i] = r.fwd[j];
+      status[i] = r.st_fwd[j];
+      reverseLeftPts[i] = r.back[j];
+      statusRightLeft[i] = r.st_back[j];
     }
     if (cfg.flow_back && !c->cur_right_pts.empty()) {
       for (int i = 0; i < n; i++) {
@@ -476,14 +461,14 @@ void right_tail(esvio_fe_ctx* c, const Pin& pin, const P2f* left, const int* ids
 
 // Lazy mode: the right-camera tail of the previous call's frame, which published nothing and
 // returned with its stereo LK still in flight.
-int finalize_right(esvio_fe_ctx* c) {
+static int finalize_right(esvio_fe_ctx* c) {
   if (!c->pend_right.active) return 0;
   esvio_fe_ctx::PendingRight& pr = c->pend_right;
   pr.active = false;
   const int n = (int)pr.left.size();
   if (n) HIPCHK(c, sync_event(c->ev_lks_done[pr.set]));
-  if (pin_of(c).counts[3] != 0) return fail(c, ESVIO_FE_EINTERNAL, "radix sort look-back spin expired");
-  right_tail(c, pin_of(c, pr.set), pr.left.data(), pr.ids.data(), nullptr, n, n, pr.dt, (size_t)n);
+  if (int rc = lookback_expired(c)) return rc;
+  right_tail(c, c->pin[pr.set].s1, pr.left.data(), pr.ids.data(), nullptr, n, n, pr.dt, (size_t)n);
   return 0;
 }
 
@@ -491,21 +476,20 @@ int finalize_right(esvio_fe_ctx* c) {
 // (their stereo LK has run meanwhile).  Equal to what the eager tail would have produced: the new
 // ids are the largest, come last in every vector, are absent from the previous frame's map (zero
 // velocity, feature_tracker.cpp:1026-1040) and extend the (sorted) map the next frame reads.
-int finalize_pending(esvio_fe_ctx* c) {
+static int finalize_pending(esvio_fe_ctx* c) {
   if (!c->pend.active) return 0;
   c->pend.active = false;
   HIPCHK(c, sync_event(c->ev_lknew_done));
-  Pin pin = pin_of(c);
+  const LkOut& r = c->pin[0].s2;
   const esvio_fe_config& cfg = c->cfg;
-  const P2f *B2 = (const P2f*)pin.ptsB2, *C2 = (const P2f*)pin.ptsC2;
   std::vector<P2f> add;
   std::vector<int> add_ids;
   for (size_t j = 0; j < c->pend.ids.size(); j++) {
-    bool ok = pin.stA2[j] != 0;
+    bool ok = r.st_fwd[j] != 0;
     if (cfg.flow_back)
-      ok = ok && pin.stB2[j] && in_border_event(c, B2[j]) && pt_distance(c->pend.left[j], C2[j]) <= 0.5;
+      ok = ok && r.st_back[j] && in_border_event(c, r.fwd[j]) && pt_distance(c->pend.left[j], r.back[j]) <= 0.5;
     if (ok) {
-      add.push_back(B2[j]);
+      add.push_back(r.fwd[j]);
       add_ids.push_back(c->pend.ids[j]);
     }
   }
@@ -520,6 +504,21 @@ int finalize_pending(esvio_fe_ctx* c) {
     c->prev_un_right_pts_map.v.emplace_back(add_ids[j], un[j]);  // (already swapped: next frame's prev)
   }
   return 0;
+}
+
+// The one order the two may run in: the new corners' map entries are what the tail's velocities read.  (TrackCall
+// below takes them apart, in this order: publish() runs the tail only if its stereo LK is over, tails() may leave both.)
+int finalize_lazy(esvio_fe_ctx* c) {
+  if (int rc = finalize_pending(c)) return rc;
+  return finalize_right(c);
+}
+
+// Has everything recorded before `ev` run?  Anything but "not ready" counts as over: the completing path then waits
+// with sync_event, which reports a real error.
+static bool event_over(hipEvent_t ev) {
+  const bool over = hipEventQuery(ev) != hipErrorNotReady;
+  (void)hipGetLastError();
+  return over;
 }
 
 // ---------------------------------------------------------------- trackEvent
@@ -544,7 +543,7 @@ struct TrackCall {
   const bool PUB_THIS_FRAME;
   const esvio_fe_motion* motion;
   const int M;
-  Pin pin{};
+  ResView pin{}, zpin{};  // the frame's copy of set 1: host view, device-side view
   const EventRec *dL = nullptr, *dR = nullptr;
   bool first = false;
   bool arc_done = false, arc_prefetched = false, arc_marked_main = false;
@@ -564,7 +563,7 @@ struct TrackCall {
   // and the stereo LK is launched WITH the temporal one, chained to it point by point on the device
   bool plain = false, arc_side = false, stereo_chained = false;
   bool split_right = false;  // ... and the right camera's update + image run on the stereo stream beside the left one's
-  Pin pin_st{};               // where the frame's stereo LK results of the kept points land
+  int set_st = 0;             // copy of set 1 where the frame's stereo LK results of the kept points land
   std::vector<int> surv_src;  // chained stereo: survivor i was the temporal launch's point surv_src[i]
   int n_surv = 0, n_kept = 0;
   clk::time_point tp;
@@ -743,7 +742,7 @@ struct TrackCall {
     plain = !c->cur_prefetched && !had_announced && c->inflight.empty() && !c->lazy_new && !c->chain_valid &&
             !c->spec_valid;
     if (plain) c->n_plain_calls++;
-    pin_st = pin;
+    set_st = c->res_set;
     c->cur_pts.clear();
     c->cur_right_pts.clear();
     return 0;
@@ -847,8 +846,7 @@ struct TrackCall {
     const PyrDesc& curL = c->pyr[c->slot_curL].d;
     if (c->prev_pts.size() > 0) {
       const int n = (int)c->prev_pts.size();
-      const uint8_t *t_stA, *t_stB;
-      const P2f *t_ptsB, *t_ptsC;
+      LkOut t{};  // where the temporal pair's results are read from
       bool spec_ok = false;
       if (use_spec) {
         if (!defer_late)
@@ -858,12 +856,8 @@ struct TrackCall {
         if (int rc = exchange_flush(c)) return rc;  // (host time that would be spent waiting)
         HIPCHK(c, sync_event(c->ev_spec_done));
         lap(2);
-        const size_t stM = ((size_t)std::max(M, 1) + 63) / 64 * 64;
-        t_ptsB = (const P2f*)c->h_spec;
-        t_ptsC = (const P2f*)(c->h_spec + (size_t)std::max(M, 1) * 8);
-        t_stA = c->h_spec + (size_t)std::max(M, 1) * 16;
-        t_stB = t_stA + stM;
-        int* wait_expired = (int*)(c->h_spec + (size_t)std::max(M, 1) * 16 + 2 * stM);
+        t = c->hspec[0].out;
+        int* wait_expired = c->hspec[0].expired;
         spec_ok = *wait_expired == 0;  // (a wave gave up waiting for k_select: redo the launch below)
         *wait_expired = 0;
         if (!spec_ok) {
@@ -883,50 +877,40 @@ struct TrackCall {
         if (int rc = exchange_flush(c)) return rc;
         HIPCHK(c, sync_event(c->ev_chain_done));
         lap(2);
-        const size_t Mx = (size_t)std::max(M, 1), stM = (Mx + 63) / 64 * 64;
-        const uint8_t* hc = c->h_spec + c->spec_bytes;
-        int* wait_expired = (int*)(hc + Mx * 16 + 2 * stM);
+        int* wait_expired = c->hspec[1].expired;
         spec_ok = *wait_expired == 0;
         *wait_expired = 0;
         c->tr_chain_used += spec_ok;
         if (!spec_ok) c->n_chain_expired++;
         if (c->trace && spec_ok) trace_chain_intervals();
         if (spec_ok) {  // gather: prev_pts[j] was the producer's point chain_map[j]
-          const P2f *sB = (const P2f*)hc, *sC = (const P2f*)(hc + Mx * 8);
-          const uint8_t *sa = hc + Mx * 16, *sb = sa + stM;
+          const LkOut& r = c->hspec[1].out;
           g_ptsB.resize(n);
           g_ptsC.resize(n);
           g_stA.resize(n);
           g_stB.resize(n);
           for (int j = 0; j < n; j++) {
             const int k = c->chain_map[j];
-            g_ptsB[j] = sB[k];
-            g_ptsC[j] = sC[k];
-            g_stA[j] = sa[k];
-            g_stB[j] = sb[k];
+            g_ptsB[j] = r.fwd[k];
+            g_ptsC[j] = r.back[k];
+            g_stA[j] = r.st_fwd[k];
+            g_stB[j] = r.st_back[k];
           }
-          t_ptsB = g_ptsB.data();
-          t_ptsC = g_ptsC.data();
-          t_stA = g_stA.data();
-          t_stB = g_stB.data();
+          t = LkOut{g_ptsB.data(), g_ptsC.data(), g_stA.data(), g_stB.data()};
         }
       }
       if (!spec_ok) {
         std::memcpy(pin.A, c->prev_pts.data(), (size_t)n * 8);
         // forward: prevL -> curL, maxLevel 3 (:410); reverse: curL -> prevL, maxLevel 1,
         // USE_INITIAL_FLOW seeded with prev_pts (:416-418) — fused into the same launch
-        LkArgs f = make_lk(prevL, curL, zdev(c, pin.A), nullptr, zdev(c, pin.ptsB), zdev(c, pin.stA), nullptr, n, 3, 30, 0.01, 0);
-        LkArgs b = make_lk(curL, prevL, nullptr, nullptr, nullptr, nullptr, nullptr, n, 1, 30, 0.01,
-                           ESVIO_FE_LK_USE_INITIAL_FLOW);
+        LkPair lk = lk_pair(prevL, curL, zpin.A, nullptr, n, kLkTemporal, zpin.s1);
         stereo_chained = plain && c->chain_enabled && c->waits_fit_chain;
         if (stereo_chained) {
           c->n_stereo_chained++;
-          c->chain_seq = (c->chain_seq + 1) & 0x3fffffffu;
-          if (!c->chain_seq) c->chain_seq = 1;
-          f.chain_out = c->d_chain;
-          f.chain_seq = c->chain_seq;
+          lk.f.chain_out = c->d_chain;
+          lk.f.chain_seq = next_chain_seq(c);
         }
-        run_lk(c, f, cfg.flow_back ? &b : nullptr, zdev(c, pin.ptsC), zdev(c, pin.stB));
+        run_lk_pair(c, lk);
         if (stereo_chained) {
           // cv::calcOpticalFlowPyrLK(curL, curR, cur_pts, ...) (:490) and its reverse (:495) start from the
           // temporal FORWARD results, point by point: launched now, on the stereo stream, every wave
@@ -934,18 +918,15 @@ struct TrackCall {
           // points the host's filters drop below are simply not gathered.  Results: the other copy of
           // set 1 (the temporal launch is still writing this one).
           const PyrDesc& curR = c->pyr[c->slot_curR].d;
-          pin_st = pin_of(c, c->res_set ^ 1);
-          const size_t Mx = (size_t)std::max(M, 1), stM = (Mx + 63) / 64 * 64;
-          LkArgs f2 = make_lk(curL, curR, nullptr, nullptr, zdev(c, pin_st.ptsB), zdev(c, pin_st.stA), nullptr, n, 3, 30,
-                              0.01, 0);
-          LkArgs b2 = make_lk(curR, curL, nullptr, nullptr, nullptr, nullptr, nullptr, n, 3, 30, 0.01, 0);
-          f2.chain_in = c->d_chain;
-          f2.chain_seq = c->chain_seq;
-          f2.chain_ticks = c->lim.chain;
-          f2.poll_err = (int*)(c->z_spec + c->spec_bytes + Mx * 16 + 2 * stM);
+          set_st = c->res_set ^ 1;
+          LkPair st = lk_pair(curL, curR, nullptr, nullptr, n, kLkStereo, c->zpin[set_st].s1);
+          st.f.chain_in = c->d_chain;
+          st.f.chain_seq = c->chain_seq;
+          st.f.chain_ticks = c->lim.chain;
+          st.f.poll_err = c->zspec[1].expired;  // (the chained block's flag)
           StreamScope on_stereo_stream(stereo_stream(c));
           HIPCHK(c, hipStreamWaitEvent(stereo_stream(c), c->ev_imgs_ready, 0));
-          run_lk(c, f2, cfg.flow_back ? &b2 : nullptr, zdev(c, pin_st.ptsC), zdev(c, pin_st.stB));
+          run_lk_pair(c, st);
           if (int rc = record_lks_done(c, c->res_set)) return rc;
         }
         if (int rc = early_work()) return rc;
@@ -954,18 +935,15 @@ struct TrackCall {
         lap(1);
         HIPCHK(c, sync_main(c));
         lap(2);
-        t_ptsB = (const P2f*)pin.ptsB;
-        t_ptsC = (const P2f*)pin.ptsC;
-        t_stA = pin.stA;
-        t_stB = pin.stB;
+        t = pin.s1;
       }
-      std::vector<uint8_t> status(t_stA, t_stA + n);
+      std::vector<uint8_t> status(t.st_fwd, t.st_fwd + n);
       c->cur_pts.resize(n);
-      std::memcpy(c->cur_pts.data(), t_ptsB, (size_t)n * 8);
+      std::memcpy(c->cur_pts.data(), t.fwd, (size_t)n * 8);
       if (cfg.flow_back) {
-        const P2f* reverse_pts = t_ptsC;
+        const P2f* reverse_pts = t.back;
         for (int i = 0; i < n; i++) {
-          if (status[i] && t_stB[i] && pt_distance(c->prev_pts[i], reverse_pts[i]) <= 0.5)
+          if (status[i] && t.st_back[i] && pt_distance(c->prev_pts[i], reverse_pts[i]) <= 0.5)
             status[i] = 1;
           else
             status[i] = 0;
@@ -1043,7 +1021,6 @@ struct TrackCall {
   // this is exactly cv::calcOpticalFlowPyrLK(curL, curR, cur_pts, ...) (:490) and its reverse (:495)
   // for the kept points — launched now so that it overlaps the host-side RANSAC + mask.
   int survivors_stereo() {
-    const esvio_fe_config& cfg = c->cfg;
     const PyrDesc& curL = c->pyr[c->slot_curL].d;
     const PyrDesc& curR = c->pyr[c->slot_curR].d;
     n_surv = (int)c->cur_pts.size();
@@ -1063,14 +1040,11 @@ struct TrackCall {
     }
     if (n_surv && !stereo_chained) {
       std::memcpy(pin.A, c->cur_pts.data(), (size_t)n_surv * 8);
-      LkArgs f = make_lk(curL, curR, zdev(c, pin.A), nullptr, zdev(c, pin.ptsB), zdev(c, pin.stA), nullptr, n_surv, 3, 30,
-                         0.01, 0);
-      LkArgs b = make_lk(curR, curL, nullptr, nullptr, nullptr, nullptr, nullptr, n_surv, 3, 30, 0.01, 0);
       {
         // on its own stream.  Its inputs are complete without a device-side wait: the host has just
         // read this frame's temporal LK results, and that launch ran behind the frame's pyramids.
         StreamScope on_stereo_stream(stereo_stream(c));
-        run_lk(c, f, cfg.flow_back ? &b : nullptr, zdev(c, pin.ptsC), zdev(c, pin.stB));
+        run_lk_pair(c, lk_pair(curL, curR, zpin.A, nullptr, n_surv, kLkStereo, zpin.s1));
         if (int rc = record_lks_done(c, c->res_set)) return rc;
       }
     }
@@ -1110,14 +1084,14 @@ struct TrackCall {
         // instead of a 38 KB bitmap copied over); candidates on them are skipped there
         if (!will_spec && n_kept) std::memcpy(pin.news, c->cur_pts.data(), (size_t)n_kept * 8);
         if (arc_prefetched) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_lane_arc[arc_lane], 0));
-        // new corners go behind the kept points: z_new = next frame's prev_pts
+        // new corners go behind the kept points: news = next frame's prev_pts
         c->pub_seq++;
         if (c->trace) {
           HIPCHK(c, hipEventRecord(c->ev_dbg_sel_start, cur_stream(c)));
           c->tr_sel_launch = clk::now();
         }
-        run_select(c, c->cand_cur, n_max_cnt, c->z_new, n_kept, nullptr, nullptr, c->z_counts, will_spec,
-                   c->z_new, n_kept);
+        run_select(c, c->cand_cur, n_max_cnt, (float2*)zpin.news, n_kept, nullptr, nullptr, zpin.counts, will_spec,
+                   (const float2*)zpin.news, n_kept);
         sub(1);
         if (will_spec)
           if (const Inflight* nb = next_batch())
@@ -1131,17 +1105,12 @@ struct TrackCall {
         // that frame's right-camera tail, after this frame's own left-camera bookkeeping: waiting HERE was 37-77 us
         // of every published call once the unpublished frame's call had become short, bench.py --call-phases)
         if (!c->pend_right.active || c->pend_right.left.empty() ||
-            (!c->lazy_late && hipEventQuery(c->ev_lks_done[c->pend_right.set]) != hipErrorNotReady))
+            (!c->lazy_late && event_over(c->ev_lks_done[c->pend_right.set])))
           if (int rc = finalize_right(c)) return rc;
-        (void)hipGetLastError();
         sub(3);
         // stereo LK of the new corners only (count known on the device)
         if (split_right) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_right_ready, 0));  // (the right image)
-        LkArgs f = make_lk(curL, curR, c->z_new + n_kept, nullptr, c->z_ptsB2, c->z_stA2, c->d_counts,
-                           n_max_cnt, 3, 30, 0.01, 0);
-        LkArgs b = make_lk(curR, curL, nullptr, nullptr, nullptr, nullptr, c->d_counts, n_max_cnt, 3, 30,
-                           0.01, 0);
-        run_lk(c, f, cfg.flow_back ? &b : nullptr, c->z_ptsC2, c->z_stB2);
+        run_lk_pair(c, lk_pair(curL, curR, zpin.news + n_kept, c->dres.counts, n_max_cnt, kLkStereo, zpin.s2));
         if (c->lazy_new) HIPCHK(c, hipEventRecord(c->ev_lknew_done, cur_stream(c)));
         sub(4);
       }
@@ -1166,7 +1135,7 @@ struct TrackCall {
         c->tr_cand += (uint64_t)pin.counts[2];
         c->tr_new += (uint64_t)n_new;
         c->tr_detect++;
-        const P2f* np = (const P2f*)pin.news + n_kept;
+        const P2f* np = pin.news + n_kept;
         for (int i = 0; i < n_new; i++) c->n_pts.push_back(np[i]);
       }
       for (auto& p : c->n_pts) {  // :463-468
@@ -1197,13 +1166,11 @@ struct TrackCall {
     // profiles/r06_replay_cycle_floor.md).
     bool pending_later = false;
     if (defer_right && c->pend.active && !c->pend_right.active) {
-      pending_later = c->lazy_late || hipEventQuery(c->ev_lknew_done) == hipErrorNotReady;
-      (void)hipGetLastError();
+      pending_later = c->lazy_late || !event_over(c->ev_lknew_done);
     }
-    if (!pending_later) {
-      if (int rc = finalize_pending(c)) return rc;  // (the previous published frame's new corners,
-      if (int rc = finalize_right(c)) return rc;    //  or the previous unpublished frame's whole tail)
-    }
+    // (the previous published frame's new corners, or the previous unpublished frame's whole tail)
+    if (!pending_later)
+      if (int rc = finalize_lazy(c)) return rc;
     tail_lap(1);
     if (defer_right) {
       // (returns with the stereo LK in flight)
@@ -1211,8 +1178,7 @@ struct TrackCall {
       if (!lazy) HIPCHK(c, sync_main(c));  // stereo LK results of the new corners
       if (n_surv || stereo_chained) HIPCHK(c, sync_event(c->ev_lks_done[c->res_set]));  // ... of the kept points
       if (stereo_chained) {
-        const size_t Mx = (size_t)std::max(M, 1), stM = (Mx + 63) / 64 * 64;
-        int* wait_expired = (int*)(c->h_spec + c->spec_bytes + Mx * 16 + 2 * stM);
+        int* wait_expired = c->hspec[1].expired;
         if (*wait_expired != 0) {
           // a wave of the chained stereo launch gave up waiting for its point: the same launch the plain
           // way, from the temporal forward results (still in this frame's copy of set 1; a point the
@@ -1223,11 +1189,8 @@ struct TrackCall {
           if (n) {
             const PyrDesc& curL = c->pyr[c->slot_curL].d;
             const PyrDesc& curR = c->pyr[c->slot_curR].d;
-            LkArgs f2 = make_lk(curL, curR, zdev(c, pin.ptsB), nullptr, zdev(c, pin_st.ptsB), zdev(c, pin_st.stA), nullptr, n,
-                                3, 30, 0.01, 0);
-            LkArgs b2 = make_lk(curR, curL, nullptr, nullptr, nullptr, nullptr, nullptr, n, 3, 30, 0.01, 0);
             StreamScope on_stereo_stream(stereo_stream(c));
-            run_lk(c, f2, cfg.flow_back ? &b2 : nullptr, zdev(c, pin_st.ptsC), zdev(c, pin_st.stB));
+            run_lk_pair(c, lk_pair(curL, curR, zpin.s1.fwd, nullptr, n, kLkStereo, c->zpin[set_st].s1));
             HIPCHK(c, hipStreamSynchronize(stereo_stream(c)));
           }
         }
@@ -1235,8 +1198,8 @@ struct TrackCall {
     }
     lap(6);
     tt = clk::now();
-    if (!defer_right && (n_surv || detect) && pin.counts[3] != 0)
-      return fail(c, ESVIO_FE_EINTERNAL, "radix sort look-back spin expired");
+    if (!defer_right && (n_surv || detect))
+      if (int rc = lookback_expired(c)) return rc;
 
     if (defer_right) {
       // nothing of this frame is published: its right-camera tail waits for the next call
@@ -1252,7 +1215,7 @@ struct TrackCall {
         c->pend.ids.assign(c->ids.begin() + n_kept, c->ids.end());
         c->pend.left.assign(c->cur_pts.begin() + n_kept, c->cur_pts.end());
       }
-      right_tail(c, pin_st, c->cur_pts.data(), c->ids.data(), c->src_idx.data(),
+      right_tail(c, c->pin[set_st].s1, c->cur_pts.data(), c->ids.data(), c->src_idx.data(),
                  lazy ? n_kept : (int)c->cur_pts.size(), n_kept, c->cur_time - c->prev_time,
                  c->cur_pts.size());
     }
@@ -1366,7 +1329,8 @@ int track_event_impl(esvio_fe_ctx* c, double _cur_time, const esvio_fe_event* le
                                                             : (c->cfg.lk_accum == 2 && c->launcher != nullptr && c->stager == nullptr));
   c->stereo_unpub = !PUB_THIS_FRAME && c->stereo_split;
   c->frame_no++;
-  t.pin = pin_of(c, c->res_set);
+  t.pin = c->pin[c->res_set];
+  t.zpin = c->zpin[c->res_set];
   if (PUB_THIS_FRAME && c->pool) host::ransac_pool_wake(c->pool);
   c->cur_time = _cur_time;
   t.tp = clk::now();

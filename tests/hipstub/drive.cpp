@@ -6,6 +6,8 @@
 // under test is every thread the library starts and every hand-over between them.  Before that, handles of a few
 // configurations pass once through every entry point that allocates on first use (first_use_pass); after the last
 // esvio_fe_destroy the stub's count of live device blocks, pinned blocks, events and streams is printed.
+// The last line is a digest of what every successful track call and esvio_fe_finish returned (n_left, n_right, ids,
+// cur_pts, ids_right, cur_right_pts, both velocity arrays): two builds of the library that compute the same print the same.
 //   drive <seed> <frames>      exit 0: done; the sanitizer reports on stderr
 #include <cstdio>
 #include <cstdlib>
@@ -21,6 +23,22 @@ extern "C" void hipstub_live(long out[4]);
 
 static uint32_t rs;
 static uint32_t rnd() { return rs = rs * 1664525u + 1013904223u; }
+
+static uint64_t digest = 1469598103934665603ull;  // FNV-1a
+static void fold(const void* p, size_t bytes) {
+  for (size_t i = 0; i < bytes; i++) digest = (digest ^ ((const uint8_t*)p)[i]) * 1099511628211ull;
+}
+static void fold_tracks(const esvio_fe_tracks& t) {
+  const size_t nl = (size_t)t.n_left, nr = (size_t)t.n_right;
+  fold(&t.n_left, 4);
+  fold(&t.n_right, 4);
+  fold(t.ids, nl * 4);
+  fold(t.cur_pts, nl * 8);
+  fold(t.ids_right, nr * 4);
+  fold(t.cur_right_pts, nr * 8);
+  fold(t.pts_velocity, nl * 8);
+  fold(t.right_pts_velocity, nr * 8);
+}
 
 struct Batch {
   std::vector<esvio_fe_event> L, R;
@@ -216,10 +234,12 @@ int main(int argc, char** argv) {
         failed++;
         esvio_fe_reset(h);
         announced = i;
+      } else {
+        fold_tracks(t);
       }
-      if (rnd() % 17u == 0) esvio_fe_finish(h, &t);
+      if (rnd() % 17u == 0 && esvio_fe_finish(h, &t) == ESVIO_FE_OK) fold_tracks(t);
     }
-    esvio_fe_finish(h, &t);
+    if (esvio_fe_finish(h, &t) == ESVIO_FE_OK) fold_tracks(t);
     {
       esvio_fe_latency_call lc;
       if (esvio_fe_latency_recent(h, 0, &lc) == ESVIO_FE_OK && lc.ms < 0) { fprintf(stderr, "latency record\n"); return 4; }
@@ -234,5 +254,6 @@ int main(int argc, char** argv) {
   long live[4];
   hipstub_live(live);
   printf("live: device %ld pinned %ld events %ld streams %ld\n", live[0], live[1], live[2], live[3]);
+  printf("digest: %016llx\n", (unsigned long long)digest);
   return 0;
 }
