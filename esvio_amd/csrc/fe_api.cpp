@@ -239,6 +239,7 @@ int esvio_fe_create(const esvio_fe_config* cfg, esvio_fe_handle* out) {
   c->dedup_enabled = getenv("ESVIO_FE_NO_DEDUP") == nullptr && (cfg->max_cnt > 500 || getenv("ESVIO_FE_DEDUP") != nullptr);
   c->fuse_ts_pyr = getenv("ESVIO_FE_NO_FUSE") == nullptr;
   c->fast_lds = getenv("ESVIO_FE_FAST_LDS") != nullptr;
+  if (const char* v = getenv("ESVIO_FE_CONVERT_PINNED_COPY")) c->cvt_pinned_copy = atoi(v) != 0 ? 1 : 0;
   c->select_one_wave = getenv("ESVIO_FE_SELECT_SERIAL") != nullptr;
   if (const char* v = getenv("ESVIO_FE_SAE_EV_MIN")) c->sae_ev_min = (size_t)strtoull(v, nullptr, 10);
   c->tiled = make_tile_geom(c->W, c->H, &c->tgeom) && getenv("ESVIO_FE_SAE_SORT") == nullptr;
@@ -921,6 +922,212 @@ int esvio_fe_track_event_mc(esvio_fe_handle c, double cur_time, const esvio_fe_e
                             esvio_fe_tracks* out) {
   if (!motion) return ESVIO_FE_EINVAL;
   return track_event_entry(c, cur_time, left, nL, right, nR, space, pub_this_frame, motion, out);
+}
+
+// ---- event layouts: caller-layout field arrays -> event records (esvio_fe_convert_events)
+namespace {
+struct FieldView {  // one field of the descriptor: where, how far apart, how wide
+  const uint8_t* p;
+  int32_t stride;
+  int width;
+  const char* name;
+};
+void field_views(const esvio_fe_event_fields& f, FieldView v[4]) {
+  v[0] = {(const uint8_t*)f.x, f.x_stride, 2, "x"};
+  v[1] = {(const uint8_t*)f.y, f.y_stride, 2, "y"};
+  v[2] = {(const uint8_t*)f.t, f.t_stride, f.t_bits / 8, "t"};
+  v[3] = {(const uint8_t*)f.p, f.p_stride, f.p_bits / 8, "p"};
+}
+size_t field_span(const FieldView& v, size_t n) { return (n - 1) * (size_t)v.stride + (size_t)v.width; }
+
+int fields_check(esvio_fe_ctx* c, const esvio_fe_event_fields* f, size_t n, const char* who) {
+  if (!f) return n ? fail(c, ESVIO_FE_EINVAL, "%s: no field descriptor", who) : 0;
+  if (f->t_bits != 32 && f->t_bits != 64) return fail(c, ESVIO_FE_EINVAL, "%s: t_bits must be 32 or 64 (got %d)", who, f->t_bits);
+  if (f->t_unit_ns != 1 && f->t_unit_ns != 1000)
+    return fail(c, ESVIO_FE_EINVAL, "%s: t_unit_ns must be 1 or 1000 (got %d)", who, f->t_unit_ns);
+  if (f->p_bits != 8 && f->p_bits != 16) return fail(c, ESVIO_FE_EINVAL, "%s: p_bits must be 8 or 16 (got %d)", who, f->p_bits);
+  const int64_t lim = (int64_t)1 << 62;
+  if (f->t_offset > lim || f->t_offset < -lim) return fail(c, ESVIO_FE_EINVAL, "%s: |t_offset| must be <= 2^62", who);
+  FieldView v[4];
+  field_views(*f, v);
+  for (const FieldView& k : v) {
+    if (k.stride < k.width)
+      return fail(c, ESVIO_FE_EINVAL, "%s: %s_stride %d is below the field's width %d", who, k.name, k.stride, k.width);
+    if (n && !k.p) return fail(c, ESVIO_FE_EINVAL, "%s: field %s is null", who, k.name);
+  }
+  return 0;
+}
+
+// [p, p + len) is page-locked memory the runtime knows and maps contiguously: its device-side address, else null
+// (first AND last byte, as fe_evstage.cpp's test: a kernel reading beyond a mapping is a fatal queue error)
+const uint8_t* pinned_device_ptr(const uint8_t* p, size_t len) {
+  auto pinned = [](const void* q) {
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, q) != hipSuccess) {
+      (void)hipGetLastError();
+      return false;
+    }
+    return a.type == hipMemoryTypeHost;
+  };
+  if (!len || !pinned(p) || !pinned(p + len - 1)) return nullptr;
+  void *d0 = nullptr, *d1 = nullptr;
+  if (hipHostGetDevicePointer(&d0, const_cast<uint8_t*>(p), 0) != hipSuccess || !d0 ||
+      hipHostGetDevicePointer(&d1, const_cast<uint8_t*>(p) + len - 1, 0) != hipSuccess ||
+      (uint8_t*)d1 != (uint8_t*)d0 + len - 1) {
+    (void)hipGetLastError();
+    return nullptr;
+  }
+  return (const uint8_t*)d0;
+}
+
+// Enqueue the conversion of n events (checked descriptor) into d_dst on the current stream; bad events are added to
+// c->d_cvt_bad.  A host source that is not read in place is copied into c->d_cvt_src first: every byte range the
+// fields span once (the four fields of an AoS source overlap: one range), each at its source's address modulo 16,
+// so that an aligned source stays aligned for the kernel's wide loads.
+int convert_enqueue(esvio_fe_ctx* c, const esvio_fe_event_fields& f, size_t n, int src_space, EventRec* d_dst) {
+  if (!n) return 0;
+  hipStream_t s = cur_stream(c);
+  FieldView v[4];
+  field_views(f, v);
+  const uint8_t* dev[4] = {v[0].p, v[1].p, v[2].p, v[3].p};
+  if (src_space == ESVIO_FE_HOST) {
+    // Page-locked sources, measured both ways (KERNELS.md "Event layouts"): separate arrays are faster read in place
+    // at both batch sizes; records (a stride above the field's width: 16 or 13 bytes per lane and event, a poor
+    // shape for reads over PCIe) are faster in place at 167 k events and faster copied first at 3.3 M — the
+    // crossover itself was not measured, the switch sits at 2^20 events.
+    bool records = false;
+    for (const FieldView& k : v) records = records || k.stride != k.width;
+    bool in_place = c->cvt_pinned_copy < 0 ? !(records && n >= ((size_t)1 << 20)) : c->cvt_pinned_copy == 0;
+    for (int k = 0; k < 4 && in_place; k++) {
+      dev[k] = pinned_device_ptr(v[k].p, field_span(v[k], n));
+      in_place = dev[k] != nullptr;
+    }
+    if (!in_place) {
+      int order[4] = {0, 1, 2, 3};
+      std::sort(order, order + 4, [&](int a, int b) { return v[a].p < v[b].p; });
+      struct Range {
+        const uint8_t *lo, *hi;
+        size_t off;
+      } rg[4];
+      int nr = 0;
+      for (int k : order) {
+        const uint8_t *lo = v[k].p, *hi = lo + field_span(v[k], n);
+        if (nr && lo <= rg[nr - 1].hi)
+          rg[nr - 1].hi = std::max(rg[nr - 1].hi, hi);
+        else
+          rg[nr++] = {lo, hi, 0};
+      }
+      size_t total = 0;
+      for (int r = 0; r < nr; r++) {
+        rg[r].off = ((total + 15) & ~(size_t)15) + ((uintptr_t)rg[r].lo & 15);
+        total = rg[r].off + (size_t)(rg[r].hi - rg[r].lo);
+      }
+      if (int rc = c->d_cvt_src.grow(c, total)) return rc;
+      for (int r = 0; r < nr; r++)
+        HIPCHK(c, hipMemcpyAsync(c->d_cvt_src + rg[r].off, rg[r].lo, (size_t)(rg[r].hi - rg[r].lo), hipMemcpyHostToDevice, s));
+      for (int k = 0; k < 4; k++)
+        for (int r = 0; r < nr; r++)
+          if (v[k].p >= rg[r].lo && v[k].p < rg[r].hi) dev[k] = c->d_cvt_src + rg[r].off + (v[k].p - rg[r].lo);
+    }
+  }
+  FieldsArgs a{};
+  a.x = dev[0], a.y = dev[1], a.t = dev[2], a.p = dev[3];
+  a.x_stride = f.x_stride, a.y_stride = f.y_stride, a.t_stride = f.t_stride, a.p_stride = f.p_stride;
+  a.t_bits = f.t_bits, a.t_unit_ns = f.t_unit_ns, a.p_bits = f.p_bits, a.t_offset = f.t_offset;
+  ScopedKernel k(c, K_EVENTS_FROM_FIELDS, n * (size_t)(2 + 2 + v[2].width + v[3].width + 16));
+  launch_events_from_fields(s, a, n, d_dst, c->d_cvt_bad);
+  return 0;
+}
+int convert_begin(esvio_fe_ctx* c) {  // the bad-event counter, cleared in stream order
+  if (!c->d_cvt_bad)
+    if (int rc = c->d_cvt_bad.alloc(c, 1)) return rc;
+  HIPCHK(c, hipMemsetAsync(c->d_cvt_bad, 0, sizeof(unsigned long long), cur_stream(c)));
+  return 0;
+}
+int convert_end(esvio_fe_ctx* c, unsigned long long* bad) {  // waits for the conversions enqueued since convert_begin
+  HIPCHK(c, hipMemcpyAsync(bad, c->d_cvt_bad, sizeof(unsigned long long), hipMemcpyDeviceToHost, cur_stream(c)));
+  HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  return 0;
+}
+}  // namespace
+
+int esvio_fe_convert_events(esvio_fe_handle c, const esvio_fe_event_fields* src, size_t n, int src_space,
+                            esvio_fe_event* dst, int dst_space, uint64_t* n_bad) {
+  if (!c) return ESVIO_FE_EINVAL;
+  if (n_bad) *n_bad = 0;
+  if ((src_space != ESVIO_FE_HOST && src_space != ESVIO_FE_DEVICE) || (dst_space != ESVIO_FE_HOST && dst_space != ESVIO_FE_DEVICE))
+    return fail(c, ESVIO_FE_EINVAL, "convert_events: bad memory space");
+  if (int rc = fields_check(c, src, n, "convert_events")) return rc;
+  if (!n) return 0;
+  if (!dst) return fail(c, ESVIO_FE_EINVAL, "convert_events: dst is null");
+  if (dst_space == ESVIO_FE_DEVICE && ((uintptr_t)dst & 15) != 0)
+    return fail(c, ESVIO_FE_EINVAL, "convert_events: a device dst must be 16-byte aligned");
+  HIPCHK(c, hipSetDevice(c->dev));
+  EventRec* d_dst = (EventRec*)dst;
+  if (dst_space == ESVIO_FE_HOST) {
+    if (int rc = c->d_cvt_out.grow(c, n)) return rc;
+    d_dst = c->d_cvt_out;
+  }
+  if (int rc = convert_begin(c)) return rc;
+  if (int rc = convert_enqueue(c, *src, n, src_space, d_dst)) return rc;
+  unsigned long long bad = 0;
+  if (int rc = convert_end(c, &bad)) return rc;
+  if (c->prof_on) resolve_profile(c);
+  if (n_bad) *n_bad = bad;
+  if (bad)
+    return fail(c, ESVIO_FE_EINVAL, "convert_events: %llu of %zu events have a stamp outside [0, 2^32 s) (or a 64-bit t outside +-2^62)", bad, n);
+  if (dst_space == ESVIO_FE_HOST) {
+    HIPCHK(c, hipMemcpyAsync(dst, d_dst, n * sizeof(EventRec), hipMemcpyDeviceToHost, cur_stream(c)));
+    HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  }
+  return 0;
+}
+
+int esvio_fe_track_event_fields(esvio_fe_handle c, double cur_time, const esvio_fe_event_fields* left, size_t nL,
+                                const esvio_fe_event_fields* right, size_t nR, int src_space, int pub_this_frame,
+                                esvio_fe_tracks* out) {
+  if (!c) return ESVIO_FE_EINVAL;
+  if (src_space != ESVIO_FE_HOST && src_space != ESVIO_FE_DEVICE) return fail(c, ESVIO_FE_EINVAL, "track_event_fields: bad memory space");
+  if (nL == 0 || !left) return fail(c, ESVIO_FE_EINVAL, "left batch must not be empty (node:150)");
+  if (nL + nR >= (1ull << 31)) return fail(c, ESVIO_FE_EINVAL, "batch too large");
+  if (int rc = fields_check(c, left, nL, "track_event_fields (left)")) return rc;
+  if (int rc = fields_check(c, right, nR, "track_event_fields (right)")) return rc;
+  if (!c->announced.empty() || !c->inflight.empty())
+    return fail(c, ESVIO_FE_EINVAL, "track_event_fields: batches are announced on this handle (convert into memory of your own)");
+  HIPCHK(c, hipSetDevice(c->dev));
+  // both pairs at once: the second call of a size allocates nothing
+  for (int p = 0; p < 2; p++) {
+    if (int rc = c->d_cvt_ev[p][0].grow(c, nL)) return rc;
+    if (int rc = c->d_cvt_ev[p][1].grow(c, nR)) return rc;
+  }
+  const int pair = c->cvt_pair;
+  // the pair's previous batch: two calls back, read by nothing on the main stream that is not in front of us there;
+  // what that call left on the other streams is marked by the events recorded when it returned
+  hipStream_t side[4] = {c->stream2, c->stream3, c->stream4, c->stream6};
+  if (c->cvt_side_rec[pair])
+    for (int k = 0; k < 4; k++)
+      if (side[k]) HIPCHK(c, hipStreamWaitEvent(cur_stream(c), c->ev_cvt_side[pair][k], 0));
+  EventRec *dL = c->d_cvt_ev[pair][0], *dR = nR ? (EventRec*)c->d_cvt_ev[pair][1] : nullptr;
+  if (int rc = convert_begin(c)) return rc;
+  if (int rc = convert_enqueue(c, *left, nL, src_space, dL)) return rc;
+  if (nR)
+    if (int rc = convert_enqueue(c, *right, nR, src_space, dR)) return rc;
+  unsigned long long bad = 0;
+  if (int rc = convert_end(c, &bad)) return rc;
+  if (bad)
+    return fail(c, ESVIO_FE_EINVAL, "track_event_fields: %llu of %zu events have a stamp outside [0, 2^32 s) (or a 64-bit t outside +-2^62)",
+                bad, nL + nR);
+  const int rc = track_event_impl(c, cur_time, (const esvio_fe_event*)dL, nL, (const esvio_fe_event*)dR, nR, ESVIO_FE_DEVICE,
+                                  pub_this_frame != 0, nullptr);
+  for (int k = 0; k < 4; k++)
+    if (side[k]) {
+      if (!c->ev_cvt_side[pair][k]) HIPCHK(c, c->ev_cvt_side[pair][k].create());
+      HIPCHK(c, hipEventRecord(c->ev_cvt_side[pair][k], side[k]));
+    }
+  c->cvt_side_rec[pair] = true;
+  c->cvt_pair ^= 1;
+  if (rc) return rc;
+  return fill_tracks(c, out);
 }
 
 // ---- image front-end

@@ -69,7 +69,7 @@ const char* const kKernelNames[K_COUNT] = {
     "k_tile_hist", "k_tile_scan", "k_tile_scatter", "k_tile_apply", "k_sae_keys", "k_radix_pass", "k_sae_apply",
     "k_time_surface4", "k_time_surface", "k_median", "k_clahe", "k_norm_pyr", "k_pyr3", "k_pyr_down", "k_pyr_pad",
     "k_scharr", "k_pad_scharr", "k_lk_f32", "k_lk", "k_arc_map", "k_arc_ev", "k_dedup", "k_compact", "k_select_mw",
-    "k_select", "k_select_gbm", "k_fast_score", "k_fast_collect"};
+    "k_select", "k_select_gbm", "k_fast_score", "k_fast_collect", "k_events_from_fields"};
 
 struct KStat {
   double ms = 0;
@@ -425,6 +425,20 @@ struct esvio_fe_ctx {
   KStat stats[K_COUNT];
   std::vector<ProfRec> pending;
   std::vector<Event> ev_pool;
+
+  // ---- event layouts (behind everything else: the members above lie where they lay before these existed)
+  // esvio_fe_convert_events, allocated on first use: the field bytes of a host source that is not read in place, the
+  // records behind a host destination, the bad-event count
+  DevBuf<uint8_t> d_cvt_src;
+  DevBuf<EventRec> d_cvt_out;
+  DevBuf<unsigned long long> d_cvt_bad;
+  int cvt_pinned_copy = -1;  // page-locked sources: -1 = the measured choice; ESVIO_FE_CONVERT_PINNED_COPY=1 / 0: always copied first / always read in place (the A/B in KERNELS.md)
+  // esvio_fe_track_event_fields: two pairs of record buffers [pair][camera] that alternate, and per pair the events
+  // that mark what its latest call left on stream2 / stream3 / stream4 / stream6 (include/esvio_fe.h: buffer lifetime)
+  DevBuf<EventRec> d_cvt_ev[2][2];
+  Event ev_cvt_side[2][4];
+  bool cvt_side_rec[2] = {false, false};
+  int cvt_pair = 0;
 };
 
 namespace esvio {

@@ -70,6 +70,7 @@ enum KernelId {
   K_SELECT_GBM,
   K_FAST_SCORE,      // (appended: the ids above keep their meaning)
   K_FAST_COLLECT,
+  K_EVENTS_FROM_FIELDS,
   K_COUNT
 };
 
@@ -436,6 +437,26 @@ struct FastArgs {
 };
 void launch_fast_score(hipStream_t s, const FastArgs& a);
 void launch_fast_collect(hipStream_t s, const FastArgs& a);
+
+// ---- caller-layout event arrays -> event records (esvio_fe_convert_events) -------------------
+// Where the four fields of event i lie: base + i * stride, any alignment (esvio_fe_event_fields with the pointers
+// the DEVICE reads: device memory, or the device-side address of page-locked host memory).  Per event, in integers:
+//   ticks = t + t_offset; bad (counted in *n_bad, record unspecified) if ticks < 0, ticks >= 2^32 * tps or a
+//   64-bit t outside +-2^62;  sec = ticks / tps, nsec = (ticks % tps) * t_unit_ns with tps = 10^9 / t_unit_ns;
+//   polarity = (signed p > 0);  x, y copied;  the record's padding bytes zero.
+// k_events_from_fields: four consecutive events per lane.  A field whose four values lie side by side and aligned
+// is read with one load (8 B of x or y, 16 / 2 x 16 B of t, 4 B of p); four fields that share aligned 16-byte
+// records are read as those records; anything else element by element, byte by byte where the element itself is
+// unaligned.  One 16-byte store per event.
+struct FieldsArgs {
+  const uint8_t *x, *y, *t, *p;
+  int32_t x_stride, y_stride, t_stride, p_stride;
+  int32_t t_bits;     // 32 (unsigned) or 64 (signed)
+  int32_t t_unit_ns;  // 1 or 1000
+  int32_t p_bits;     // 8 or 16 (signed)
+  int64_t t_offset;
+};
+void launch_events_from_fields(hipStream_t s, const FieldsArgs& a, size_t n, EventRec* dst, unsigned long long* n_bad);
 
 struct SelectArgs {
   const uint32_t* comp_xy;   // compacted candidates in stream order

@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <tuple>
+#include <type_traits>
 
 namespace esvio {
 
@@ -3699,6 +3700,169 @@ void launch_fast_collect(hipStream_t s, const FastArgs& a) {
   const uint32_t nblk = ((uint32_t)a.W * a.H + kArcBlock - 1) / kArcBlock;
   launch_k(k_fast_collect, dim3(nblk), dim3(kArcBlock), 0, s, a);
   if (a.n_detected) launch_k(k_fast_sum, dim3(1), dim3(256), 0, s, (const uint32_t*)a.det_cnt, nblk, a.n_detected);
+}
+
+// ============================================================================ event layouts
+// esvio_fe_convert_events: caller-layout field arrays -> the 16-byte records every other kernel reads (the layout
+// support is this project's own: the reference only ever sees dvs_msgs::Event).  Arithmetic and the paths: FieldsArgs,
+// fe_kernels.h.  Streaming: per event 9-16 bytes read, 16 written, nothing reused.
+namespace {
+// an element of T at any address: the element's own load where it is aligned, else byte by byte (little endian)
+template <class T>
+__device__ __forceinline__ T ld_any(const uint8_t* p) {
+  if (((uintptr_t)p & (sizeof(T) - 1)) == 0) return *(const T*)p;
+  uint64_t v = 0;
+#pragma unroll
+  for (int k = 0; k < (int)sizeof(T); k++) v |= (uint64_t)p[k] << (8 * k);
+  return (T)v;
+}
+// 8 bytes at byte offset o (0..15, wave-uniform) of a 16-byte record, zeros behind its end
+__device__ __forceinline__ uint64_t rec_bits(const uint4& r, uint32_t o) {
+  const uint32_t k = o >> 2, sh = (o & 3) * 8;
+  const uint32_t w0 = k == 0 ? r.x : k == 1 ? r.y : k == 2 ? r.z : r.w;
+  const uint32_t w1 = k == 0 ? r.y : k == 1 ? r.z : k == 2 ? r.w : 0u;
+  const uint32_t w2 = k == 0 ? r.z : k == 1 ? r.w : 0u;
+  const uint64_t lo = ((uint64_t)w1 << 32) | w0;
+  return sh ? (lo >> sh) | ((uint64_t)w2 << (64 - sh)) : lo;
+}
+template <int kTBits>
+__device__ __forceinline__ int64_t field_t(uint64_t raw) {  // 32: unsigned, 64: signed
+  return kTBits == 32 ? (int64_t)(uint32_t)raw : (int64_t)raw;
+}
+template <int kPBits>
+__device__ __forceinline__ uint32_t field_pol(uint64_t raw) {  // signed value > 0
+  return kPBits == 8 ? (uint32_t)((int8_t)raw > 0) : (uint32_t)((int16_t)raw > 0);
+}
+// ticks = t + t_offset (both within +-2^62, so the one sum that wraps, 2^63, comes out negative: bad either way);
+// tps is a compile-time constant: the division and the remainder are multiplies
+template <int kUnitNs, int kTBits>
+__device__ __forceinline__ uint4 fields_record(uint32_t x, uint32_t y, int64_t t, int64_t off, uint32_t pol, uint32_t& bad) {
+  constexpr uint64_t tps = 1000000000ull / kUnitNs;
+  constexpr int64_t lim = (int64_t)1 << 62;
+  const int64_t ticks = (int64_t)((uint64_t)t + (uint64_t)off);
+  const bool ok = (kTBits == 32 || (t >= -lim && t <= lim)) && ticks >= 0 && (uint64_t)ticks < (tps << 32);
+  bad += ok ? 0u : 1u;
+  const uint64_t u = ok ? (uint64_t)ticks : 0ull;
+  const uint64_t sec = u / tps;
+  const uint32_t nsec = (uint32_t)(u - sec * tps) * (uint32_t)kUnitNs;
+  return make_uint4((x & 0xffffu) | (y << 16), (uint32_t)sec, nsec, pol);
+}
+}  // namespace
+
+// aos: bit 31 = the four fields of event i lie inside the aligned 16-byte record a.x + 16 * i (a.x then IS the record
+// base); bits 0-3 / 4-7 / 8-11 / 12-15 = byte offsets of x / y / t / p in it
+template <int kUnitNs, int kTBits, int kPBits>
+__global__ __launch_bounds__(256) void k_events_from_fields(FieldsArgs a, size_t n, uint32_t aos, uint4* __restrict__ dst,
+                                                            unsigned long long* __restrict__ n_bad) {
+  using TT = typename std::conditional<kTBits == 32, uint32_t, uint64_t>::type;
+  using PT = typename std::conditional<kPBits == 8, uint8_t, uint16_t>::type;
+  const size_t groups = (n + 3) / 4, step = (size_t)gridDim.x * blockDim.x;
+  uint32_t bad = 0;
+  for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += step) {
+    const size_t i0 = g * 4;
+    const int cnt = n - i0 >= 4 ? 4 : (int)(n - i0);
+    uint32_t xs[4] = {0, 0, 0, 0}, ys[4] = {0, 0, 0, 0}, ps[4] = {0, 0, 0, 0};
+    int64_t ts[4] = {0, 0, 0, 0};
+    if (aos >> 31) {
+      const uint4* rec = (const uint4*)a.x + i0;
+#pragma unroll
+      for (int k = 0; k < 4; k++)
+        if (k < cnt) {
+          const uint4 r = rec[k];
+          xs[k] = (uint32_t)rec_bits(r, aos & 15) & 0xffffu;
+          ys[k] = (uint32_t)rec_bits(r, (aos >> 4) & 15) & 0xffffu;
+          ts[k] = field_t<kTBits>(rec_bits(r, (aos >> 8) & 15));
+          ps[k] = field_pol<kPBits>(rec_bits(r, (aos >> 12) & 15));
+        }
+    } else {
+      const uint8_t* px = a.x + i0 * (size_t)a.x_stride;
+      const uint8_t* py = a.y + i0 * (size_t)a.y_stride;
+      const uint8_t* pt = a.t + i0 * (size_t)a.t_stride;
+      const uint8_t* pp = a.p + i0 * (size_t)a.p_stride;
+      const bool full = cnt == 4;
+      if (full && a.x_stride == 2 && ((uintptr_t)px & 7) == 0) {
+        const uint2 v = *(const uint2*)px;
+        xs[0] = v.x & 0xffffu, xs[1] = v.x >> 16, xs[2] = v.y & 0xffffu, xs[3] = v.y >> 16;
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+          if (k < cnt) xs[k] = ld_any<uint16_t>(px + (size_t)k * a.x_stride);
+      }
+      if (full && a.y_stride == 2 && ((uintptr_t)py & 7) == 0) {
+        const uint2 v = *(const uint2*)py;
+        ys[0] = v.x & 0xffffu, ys[1] = v.x >> 16, ys[2] = v.y & 0xffffu, ys[3] = v.y >> 16;
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+          if (k < cnt) ys[k] = ld_any<uint16_t>(py + (size_t)k * a.y_stride);
+      }
+      if (full && a.t_stride == kTBits / 8 && ((uintptr_t)pt & 15) == 0) {
+        if (kTBits == 32) {
+          const uint4 v = *(const uint4*)pt;
+          ts[0] = v.x, ts[1] = v.y, ts[2] = v.z, ts[3] = v.w;
+        } else {
+          const uint4 v = ((const uint4*)pt)[0], w = ((const uint4*)pt)[1];
+          ts[0] = (int64_t)(((uint64_t)v.y << 32) | v.x), ts[1] = (int64_t)(((uint64_t)v.w << 32) | v.z);
+          ts[2] = (int64_t)(((uint64_t)w.y << 32) | w.x), ts[3] = (int64_t)(((uint64_t)w.w << 32) | w.z);
+        }
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+          if (k < cnt) ts[k] = field_t<kTBits>((uint64_t)ld_any<TT>(pt + (size_t)k * a.t_stride));
+      }
+      if (full && a.p_stride == kPBits / 8 && ((uintptr_t)pp & (kPBits / 2 - 1)) == 0) {
+        if (kPBits == 8) {
+          const uint32_t v = *(const uint32_t*)pp;
+#pragma unroll
+          for (int k = 0; k < 4; k++) ps[k] = field_pol<8>(v >> (8 * k));
+        } else {
+          const uint2 v = *(const uint2*)pp;
+          ps[0] = field_pol<16>(v.x), ps[1] = field_pol<16>(v.x >> 16), ps[2] = field_pol<16>(v.y), ps[3] = field_pol<16>(v.y >> 16);
+        }
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+          if (k < cnt) ps[k] = field_pol<kPBits>((uint64_t)ld_any<PT>(pp + (size_t)k * a.p_stride));
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+      if (k < cnt) dst[i0 + k] = fields_record<kUnitNs, kTBits>(xs[k], ys[k], ts[k], a.t_offset, ps[k], bad);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o);
+  if (lane_id() == 0 && bad) atomicAdd(n_bad, (unsigned long long)bad);
+}
+
+void launch_events_from_fields(hipStream_t s, const FieldsArgs& a, size_t n, EventRec* dst, unsigned long long* n_bad) {
+  if (!n) return;
+  // the four fields inside one aligned 16-byte record per event (a dvs-style AoS with a 64-bit stamp, say)
+  uint32_t aos = 0;
+  FieldsArgs k = a;
+  if (a.x_stride == 16 && a.y_stride == 16 && a.t_stride == 16 && a.p_stride == 16) {
+    const uintptr_t lo = std::min(std::min((uintptr_t)a.x, (uintptr_t)a.y), std::min((uintptr_t)a.t, (uintptr_t)a.p));
+    const uintptr_t base = lo & ~(uintptr_t)15;
+    const uintptr_t ox = (uintptr_t)a.x - base, oy = (uintptr_t)a.y - base, ot = (uintptr_t)a.t - base, op = (uintptr_t)a.p - base;
+    if (ox + 2 <= 16 && oy + 2 <= 16 && ot + (uintptr_t)a.t_bits / 8 <= 16 && op + (uintptr_t)a.p_bits / 8 <= 16) {
+      aos = 0x80000000u | (uint32_t)ox | (uint32_t)oy << 4 | (uint32_t)ot << 8 | (uint32_t)op << 12;
+      k.x = (const uint8_t*)base;
+    }
+  }
+  const size_t groups = (n + 3) / 4;
+  const unsigned grid = (unsigned)std::min<size_t>(2048, (groups + 255) / 256);
+  uint4* d = (uint4*)dst;  // (EventRec: 16-byte aligned)
+#define ESVIO_FIELDS_CASE(U, T, P)                                                                      \
+  if (a.t_unit_ns == U && a.t_bits == T && a.p_bits == P)                                               \
+    return launch_k(k_events_from_fields<U, T, P>, dim3(grid), dim3(256), 0, s, k, n, aos, d, n_bad);
+  ESVIO_FIELDS_CASE(1, 32, 8)
+  ESVIO_FIELDS_CASE(1, 32, 16)
+  ESVIO_FIELDS_CASE(1, 64, 8)
+  ESVIO_FIELDS_CASE(1, 64, 16)
+  ESVIO_FIELDS_CASE(1000, 32, 8)
+  ESVIO_FIELDS_CASE(1000, 32, 16)
+  ESVIO_FIELDS_CASE(1000, 64, 8)
+  ESVIO_FIELDS_CASE(1000, 64, 16)
+#undef ESVIO_FIELDS_CASE
 }
 
 // ============================================================================ greedy selection

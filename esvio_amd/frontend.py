@@ -61,6 +61,22 @@ def make_motion(t1, v, v_pre, accel, omega, fx, fy, cx, cy):
     return m
 
 
+class EventFieldsDesc(C.Structure):
+    """esvio_fe_event_fields"""
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("t", C.c_void_p), ("p", C.c_void_p),
+                ("x_stride", C.c_int32), ("y_stride", C.c_int32), ("t_stride", C.c_int32), ("p_stride", C.c_int32),
+                ("t_bits", C.c_int32), ("t_unit_ns", C.c_int32), ("p_bits", C.c_int32), ("t_offset", C.c_int64)]
+
+
+def fields_desc(f):
+    """events.EventFields -> esvio_fe_event_fields"""
+    d = EventFieldsDesc()
+    d.x, d.y, d.t, d.p = f.ptrs
+    d.x_stride, d.y_stride, d.t_stride, d.p_stride = f.strides
+    d.t_bits, d.t_unit_ns, d.p_bits, d.t_offset = f.t_bits, f.t_unit_ns, f.p_bits, f.t_offset
+    return d
+
+
 class Tracks(C.Structure):
     _fields_ = [
         ("n_left", C.c_int32), ("n_right", C.c_int32),
@@ -75,7 +91,8 @@ class Tracks(C.Structure):
 # the drop-in boundary: every entry point include/esvio_fe.h declares (INTEGRATION.md section 3 maps each to the
 # reference call it replaces)
 ABI_SYMBOLS = [
-    "esvio_fe_calc_optical_flow_pyr_lk", "esvio_fe_comm_init", "esvio_fe_comm_unique_id", "esvio_fe_create",
+    "esvio_fe_calc_optical_flow_pyr_lk", "esvio_fe_comm_init", "esvio_fe_comm_unique_id",
+    "esvio_fe_convert_events", "esvio_fe_create",
     "esvio_fe_create_sae", "esvio_fe_create_sae_stereo", "esvio_fe_create_sae_stereo_mc", "esvio_fe_destroy",
     "esvio_fe_exchange_begin", "esvio_fe_exchange_end", "esvio_fe_exchange_tracks", "esvio_fe_export_image",
     "esvio_fe_fast_corners", "esvio_fe_features_to_track", "esvio_fe_find_fundamental_mat", "esvio_fe_finish", "esvio_fe_get_sae",
@@ -85,7 +102,8 @@ ABI_SYMBOLS = [
     "esvio_fe_sae_plane_doubles", "esvio_fe_sae_slice_apply", "esvio_fe_sae_slice_commit",
     "esvio_fe_sae_slice_last", "esvio_fe_sae_to_time_surface", "esvio_fe_set_auto_exchange",
     "esvio_fe_set_host_threads", "esvio_fe_set_launch_thread", "esvio_fe_set_lazy_new_stereo",
-    "esvio_fe_set_next_batch", "esvio_fe_set_next_batch_mc", "esvio_fe_track_event", "esvio_fe_track_event_mc",
+    "esvio_fe_set_next_batch", "esvio_fe_set_next_batch_mc", "esvio_fe_track_event", "esvio_fe_track_event_fields",
+    "esvio_fe_track_event_mc",
     "esvio_fe_track_image", "esvio_fe_unregister_host_buffer", "esvio_fe_version",
 ]
 # test / measurement taps: include/esvio_fe_test.h (not part of the boundary)
@@ -185,6 +203,9 @@ def load_library(build_if_missing=True):
     L.esvio_fe_import_image.argtypes = [vp, i, vp, i]
     L.esvio_fe_fast_corners.argtypes = [vp, i, vp, i, i, i, i, vp, vp, C.c_int32, C.POINTER(C.c_int32),
                                         C.POINTER(C.c_int32)]
+    L.esvio_fe_convert_events.argtypes = [vp, C.POINTER(EventFieldsDesc), sz, i, vp, i, C.POINTER(C.c_uint64)]
+    L.esvio_fe_track_event_fields.argtypes = [vp, d, C.POINTER(EventFieldsDesc), sz, C.POINTER(EventFieldsDesc), sz, i, i,
+                                              C.POINTER(Tracks)]
     L.esvio_fe_set_profiling.argtypes = [vp, i]
     L.esvio_fe_kernel_name.restype = C.c_char_p
     L.esvio_fe_kernel_name.argtypes = [i]
@@ -402,6 +423,23 @@ class FeatureTracker:
             self._hd.check(self._hd.L.esvio_fe_track_event_mc(
                 self._hd.h, float(cur_time), pl, nl, pr, nr, sl, int(PUB_THIS_FRAME),
                 C.byref(measurements), C.byref(self._tr)))
+        return self._take(copy)
+
+    def convert_events(self, fields, space=DEVICE, src_space=HOST):
+        """events.EventFields -> event records, converted on the device (esvio_fe_convert_events).  Returns a
+        ConvertedEvents with EventBuffer's contract: `.arg` (space DEVICE: what every entry point takes for device
+        events, set_next_batch included) or `.array` (space HOST: a numpy EVENT_DTYPE array), and `.free()`.
+        src_space DEVICE: the fields' pointers are device addresses (EventFields.at_pointers).  A stamp that falls
+        outside [0, 2^32 s) raises FrontendError; `.n_bad` of the exception holds the count."""
+        return ConvertedEvents(self._hd, fields, space, src_space)
+
+    def trackEventFields(self, cur_time, left_fields, right_fields, PUB_THIS_FRAME=True, copy=True, src_space=HOST):
+        """trackEvent for events.EventFields of the two cameras (esvio_fe_track_event_fields): converted into
+        buffers of the handle, then tracked as device events"""
+        dl, dr = fields_desc(left_fields), fields_desc(right_fields)
+        self._hd.check(self._hd.L.esvio_fe_track_event_fields(
+            self._hd.h, float(cur_time), C.byref(dl), left_fields.n, C.byref(dr), right_fields.n, src_space,
+            int(PUB_THIS_FRAME), C.byref(self._tr)))
         return self._take(copy)
 
     _LEFT = frozenset(("ids", "track_cnt", "cur_pts", "cur_un_pts", "pts_velocity"))
@@ -778,6 +816,41 @@ class EventBuffer:
             load_library().esvio_fe_mem_free(self.space, self.ptr)
             self.ptr = None
             self.array = None
+
+
+class ConvertedEvents:
+    """the records esvio_fe_convert_events made of an events.EventFields: in device memory of the library's runtime
+    (`.arg`, the (pointer, n) tuple of ESVIO_FE_DEVICE) or downloaded (`.array`); EventBuffer's contract"""
+
+    def __init__(self, hd, fields, space=DEVICE, src_space=HOST):
+        from .events import EVENT_DTYPE
+        self.space, self.n, self.ptr, self.array = space, fields.n, None, None
+        L = hd.L
+        if space == DEVICE:
+            p = C.c_void_p()
+            rc = L.esvio_fe_mem_alloc(DEVICE, 16 * max(self.n, 1), C.byref(p))
+            if rc:
+                raise FrontendError("esvio_fe_mem_alloc rc=%d" % rc)
+            self.ptr, dst = p, p
+        else:
+            self.array = np.zeros(self.n, EVENT_DTYPE)
+            dst = _p(self.array)
+        bad = C.c_uint64(0)
+        desc = fields_desc(fields)
+        rc = L.esvio_fe_convert_events(hd.h, C.byref(desc), self.n, src_space, dst, space, C.byref(bad))
+        if rc:
+            self.free()
+            e = FrontendError("rc=%d: %s" % (rc, L.esvio_fe_last_error(hd.h).decode()))
+            e.n_bad = int(bad.value)
+            raise e
+        if space == DEVICE:
+            self.arg = (self.ptr.value, self.n)
+
+    def free(self):
+        if self.ptr:
+            load_library().esvio_fe_mem_free(DEVICE, self.ptr)
+            self.ptr = None
+        self.array = None
 
 
 class RegisteredEvents:

@@ -336,6 +336,56 @@ int esvio_fe_fast_corners(esvio_fe_handle h, int cam, const uint8_t* img, int sp
                           int nonmax, int16_t* out_xy, int32_t* out_score, int32_t capacity,
                           int32_t* n_out, int32_t* n_detected);
 
+/* ---- event layouts: caller-layout arrays -> event records, on the device ------------------ */
+/* Recordings (DSEC, MVSEC, VECtor, ECMD) and vendor SDKs deliver events as separate arrays (x[], y[], p[], t[] in
+ * microseconds plus a file-wide offset) or as records with a 64-bit stamp, some of them packed; only a ROS host holds
+ * dvs_msgs::Event records.  The reference has no counterpart: it only ever sees ROS records — this layout support is
+ * the project's own.  esvio_fe_event_fields says where the four fields of event i lie: field + i * stride, at any
+ * alignment.  It expresses separate arrays (strides 2, 2, 4 or 8, 1), an aligned AoS record (one base, four offsets,
+ * stride 16) and a packed AoS record (stride 13, say, where the 8-byte stamp is unaligned). */
+typedef struct esvio_fe_event_fields {
+  const void *x, *y, *t, *p;                      /* field of event 0 */
+  int32_t x_stride, y_stride, t_stride, p_stride; /* bytes from event i to event i+1 (>= the field's width) */
+  int32_t t_bits;     /* 32: unsigned; 64: signed */
+  int32_t t_unit_ns;  /* 1 or 1000 (ns or us ticks) */
+  int32_t p_bits;     /* 8 or 16, read as SIGNED: polarity = (value > 0), so {0,1} and {-1,+1} both work */
+  int64_t t_offset;   /* added to every t, in ticks; |t_offset| <= 2^62 */
+} esvio_fe_event_fields;
+/* n records into dst (ESVIO_FE_DEVICE: device memory, 16-byte aligned — esvio_fe_mem_alloc's is; ESVIO_FE_HOST: the
+ * records are downloaded), exact in integers: x and y (16 bits) are copied as bit patterns (an out-of-sensor value is
+ * the SAE update's business: it skips and counts those); ticks = t + t_offset, tps = 10^9 / t_unit_ns,
+ * sec = ticks / tps, nsec = (ticks % tps) * t_unit_ns; polarity 0 or 1; the padding bytes 0 — byte for byte what
+ * esvio_amd.events.make_events builds on the host.
+ * An event is BAD when ticks < 0, when sec >= 2^32, or when a 64-bit t lies outside +-2^62.  Bad events are counted
+ * on the device, nothing is clamped: if there is one, the call returns ESVIO_FE_EINVAL with *n_bad (optional) exact
+ * and dst unspecified.  n == 0 succeeds and touches nothing.  Descriptor errors (bits or unit outside the lists
+ * above, a stride below the field's width, a null field with n > 0, |t_offset| > 2^62) are ESVIO_FE_EINVAL with a
+ * message and happen before anything else does.
+ * src_space says where the FIELDS lie.  ESVIO_FE_DEVICE: read in place.  ESVIO_FE_HOST: page-locked memory the
+ * library's runtime knows (esvio_fe_mem_alloc, esvio_fe_register_host_buffer) is read in place by the kernel, over
+ * PCIe (records of 2^20 events and more are copied first: measured faster, KERNELS.md "Event layouts"); pageable
+ * memory is copied into scratch of the handle first — the bytes the fields span, not 16 per event
+ * (9 or 13 for separate arrays) — and converted there.  That scratch and the buffer behind a host dst grow on first
+ * use.
+ * The call orders itself on the handle's main stream, waits for its own result and touches nothing of the tracker:
+ * made between two track calls (announced batches or not) it changes no later result.  Records in a device dst can be
+ * handed to every entry point that takes device events, esvio_fe_set_next_batch included. */
+int esvio_fe_convert_events(esvio_fe_handle h, const esvio_fe_event_fields* src, size_t n, int src_space,
+                            esvio_fe_event* dst, int dst_space, uint64_t* n_bad);
+/* esvio_fe_track_event for a host that has fields, not records: both cameras are converted into device buffers of the
+ * handle and the plain esvio_fe_track_event runs on those (ESVIO_FE_DEVICE).  A bad event fails the call
+ * (ESVIO_FE_EINVAL) before anything is tracked; nL must be > 0.  Not to be mixed with esvio_fe_set_next_batch (convert
+ * into memory of your own for that).
+ * Buffer lifetime: a returned track call may still have kernels in flight that read its events — the SAE update of a
+ * frame that had nothing to wait for (a first or an unpublished frame without points), the right camera's update on
+ * the stereo stream, an Arc* pass beside the temporal LK; what lazy returns leave open (new-corner stereo, an
+ * unpublished frame's stereo LK) reads images, not events.  So the handle keeps TWO pairs of buffers that alternate,
+ * and a pair is rewritten, two calls later, behind everything that call had enqueued on any of the handle's streams
+ * (events recorded when it returned; the wait is on the device and long over by then). */
+int esvio_fe_track_event_fields(esvio_fe_handle h, double cur_time, const esvio_fe_event_fields* left, size_t nL,
+                                const esvio_fe_event_fields* right, size_t nR, int src_space,
+                                int pub_this_frame, esvio_fe_tracks* out);
+
 /* ---- camera split across GPUs (BASELINE config C4) ----------------------- */
 /* The left and right cameras have disjoint SAE state (sae_/sae_latest_ vs sae_right/
  * sae_latest_right, event_detector.h:74-79), so a second GPU can own the right camera: it runs
