@@ -352,6 +352,7 @@ int esvio_fe_create(const esvio_fe_config* cfg, esvio_fe_handle* out) {
   // their one-bit-per-pixel map in LDS; above ~1.3 M pixels (the frame cameras of the shipped ESVIO
   // configs go up to 1920x1200) it lives in device memory instead (k_select_gbm)
   c->select_ok = select_lds_bytes(c) <= 160 * 1024;
+  if (!c->select_ok && (rc = c->d_sel_bitmap.alloc(c, (size_t)c->H * ((c->W + 31) / 32) + 4))) return bail(rc);
   *out = c;
   return 0;
 }
@@ -580,7 +581,7 @@ int esvio_fe_import_image(esvio_fe_handle c, int cam, const uint8_t* src, int sp
   HIPCHK(c, hipSetDevice(c->dev));
   if (!c->announced.empty() || !c->inflight.empty())
     return fail(c, ESVIO_FE_EINVAL, "import_image cannot be combined with set_next_batch");
-  c->slot_curR = c->slot_curR == kLeftSlots ? kLeftSlots + 1 : kLeftSlots;  // next trackEvent's curR
+  c->slot_curR = other_right_slot(c);  // next trackEvent's curR (its rotate_slots leaves it)
   const PyrDesc& d = c->pyr[c->slot_curR].d;
   const int stride = d.stride[0];
   if (space == ESVIO_FE_HOST) {  // (staged through pinned memory: src is free again on return)

@@ -120,55 +120,21 @@ int gftt_run(esvio_fe_ctx* c, const PyrDesc& d, int max_corners, double quality,
   const uint32_t* sorted_xy = cs.comp_xy;
   if (n > 1) {  // by response, then address, both descending: 4 x 8-bit stable radix passes
     if (int rc = ensure_sort_capacity(c, n)) return rc;
-    const uint32_t head = ((uint32_t)kRadixMaxPasses << kRadixMaxBits) + 64;
-    const uint32_t nb = radix_blocks(n);
-    uint32_t* ghist = c->hist;
-    uint32_t* tickets = c->hist + ((size_t)kRadixMaxPasses << kRadixMaxBits);
-    uint32_t* lookback = c->hist + head;
-    HIPCHK(c, hipMemsetAsync(c->hist, 0, (size_t)head * 4, cur_stream(c)));
-    launch_gftt_sortprep(cur_stream(c), cs.comp_xy, cs.comp_idx, n, c->keys[0], c->vals[0], ghist, lookback,
-                         4u * (nb << 8));
-    int cur = 0;
-    for (int p = 0; p < 4; p++) {
-      launch_radix_pass(cur_stream(c), c->keys[cur], c->vals[cur], n, 8 * p, 8, ghist + ((size_t)p << 8),
-                        lookback + (size_t)p * (nb << 8), tickets + p, c->keys[cur ^ 1],
-                        c->vals[cur ^ 1], c->zpin[0].counts + 3, c->lim.lookback);
-      cur ^= 1;
-    }
-    HIPCHK(c, hipMemsetAsync(c->hist, 0, (size_t)head * 4, cur_stream(c)));  // as k_sae_apply leaves it
+    const SortScratch sc = sort_scratch(c->hist);
+    HIPCHK(c, hipMemsetAsync(c->hist, 0, (size_t)sc.head_words * 4, cur_stream(c)));
+    launch_gftt_sortprep(cur_stream(c), cs.comp_xy, cs.comp_idx, n, c->keys[0], c->vals[0], sc.ghist, sc.lookback,
+                         4u * (radix_blocks(n) << 8));
+    const int cur = radix_sort_pairs(c, n, 4, 8, false);
+    HIPCHK(c, hipMemsetAsync(c->hist, 0, (size_t)sc.head_words * 4, cur_stream(c)));  // as k_sae_apply leaves it
     sorted_xy = c->vals[cur];
   }
-  SelectArgs sa{};
-  sa.comp_xy = sorted_xy;
-  sa.comp_idx = sorted_xy;
-  sa.total = cs.total;
-  sa.W = c->W;
-  sa.H = c->H;
-  sa.wpr = (c->W + 31) / 32;
-  sa.max_corners = max_corners;
+  // the sorted list (positions only), the open Euclidean disc of min_distance, the counts mirrored to the host
+  SelectArgs sa = make_select_args(c, set, max_corners, out_pts, out_base, nullptr);
+  sa.comp_xy = sa.comp_idx = sorted_xy;
   euclid_halfwidths(min_distance, sa.hw, &sa.radius);
   sa.disc_c = disc_threshold(sa.hw, sa.radius);
-  sa.out_pts = out_pts;
-  sa.out_idx = nullptr;
-  sa.out_base = out_base;
-  sa.n_out = c->dres.counts;
-  sa.n_total = c->dres.counts + 1;
   sa.host_counts = host_counts;
-  sa.init_bits = nullptr;
-  sa.gbitmap = nullptr;
-  sa.pub_slots = nullptr;
-  sa.pub_done = nullptr;
-  sa.pub_seq = 0;
-  sa.one_wave = c->select_one_wave ? 1 : 0;
-  size_t lds = select_lds_bytes(c);
-  if (!c->select_ok) {  // a frame camera's size: the min-distance bitmap goes to device memory
-    if (!c->d_sel_bitmap)
-      if (int rc = c->d_sel_bitmap.alloc(c, (size_t)c->H * sa.wpr + 4)) return rc;
-    sa.gbitmap = c->d_sel_bitmap;
-    lds = select_tables_lds_bytes(c);
-  }
-  ScopedKernel k(c, K_SELECT_MW, 0);
-  k.id = launch_select(cur_stream(c), sa, lds);
+  launch_select_args(c, sa);
   return 0;
 }
 
@@ -212,27 +178,17 @@ int track_image_impl(esvio_fe_ctx* c, double _cur_time, const uint8_t* img_left,
   c->cur_time = _cur_time;
   const bool first = !c->have_img;
   const bool have_right = img_right != nullptr;
-  // slot rotation as in trackEvent's plain path
-  int sl = 0;
-  while (!first && (sl == c->slot_prevL || sl == c->slot_curL)) sl++;
-  c->slot_curL = sl;
-  c->slot_curR = c->slot_curR == kLeftSlots ? kLeftSlots + 1 : kLeftSlots;
+  rotate_slots(c, false);  // as in trackEvent's plain path
   const PyrDesc& L = c->pyr[c->slot_curL].d;
   const PyrDesc& R = c->pyr[c->slot_curR].d;
   if (cfg.equalize) {
-    c->raw_cur = (c->raw_cur + 1) % kRightSlots;
     const PyrDesc& rl = c->raw[c->raw_cur][0].d;
     const PyrDesc& rr = c->raw[c->raw_cur][1].d;
     if (int rc = copy_level0_in(c, rl, img_left)) return rc;
     if (have_right)
       if (int rc = copy_level0_in(c, rr, img_right)) return rc;
-    const int nimg = have_right ? 2 : 1;
-    for (int stage = 0; stage < 2; stage++) {
-      ScopedKernel k(c, K_CLAHE, 0);
-      launch_clahe(cur_stream(c), px00(rl), have_right ? px00(rr) : px00(rl), rl.stride[0], px00(L),
-                   have_right ? px00(R) : px00(L), L.stride[0], c->W, c->H, c->d_lut, c->d_minmax, nimg,
-                   stage);
-    }
+    run_clahe(c, px00(rl), have_right ? px00(rr) : px00(rl), rl.stride[0], px00(L), have_right ? px00(R) : px00(L),
+              L.stride[0], have_right ? 2 : 1, 2, 0);
   } else {
     if (int rc = copy_level0_in(c, L, img_left)) return rc;
     if (have_right)

@@ -28,6 +28,7 @@ int ensure_part_capacity(esvio_fe_ctx* c, size_t n, bool mc);
 int ensure_cand_capacity(esvio_fe_ctx* c, int set, size_t n);
 int ensure_arc_capacity(esvio_fe_ctx* c, size_t n, int set);
 int pyr_alloc(esvio_fe_ctx* c, PyrStore& ps, int w, int h, int max_level);
+uint64_t pyr_pixels(const PyrDesc& d);  // of all its levels
 void pyr_build(esvio_fe_ctx* c, const PyrDesc* p, int nimg);
 McParams make_mc_params(const esvio_fe_motion* m);
 // arc_set >= 0: this batch's Arc* pass will run into candidate set arc_set; *arc_marked tells
@@ -35,13 +36,18 @@ McParams make_mc_params(const esvio_fe_motion* m);
 int sae_update(esvio_fe_ctx* c, const EventRec* evL, uint32_t nL, const EventRec* evR, uint32_t nR,
                const McParams* mc = nullptr, double2* L2 = nullptr, double2* S2 = nullptr, int arc_set = -1,
                bool* arc_marked = nullptr);
+int radix_sort_pairs(esvio_fe_ctx* c, uint32_t n, int passes, int bits, bool booked = true);
 int stage_events(esvio_fe_ctx* c, const esvio_fe_event* left, size_t nL, const esvio_fe_event* right,
                  size_t nR, int space, const EventRec** dL, const EventRec** dR, int lane = -1);
 void render_ts(esvio_fe_ctx* c, double t_sync, uint8_t* dst0, uint8_t* dst1, int ncam, const double2* S2);
+void run_clahe(esvio_fe_ctx* c, const uint8_t* src0, const uint8_t* src1, int src_stride, uint8_t* dst0, uint8_t* dst1,
+               int dst_stride, int nimg, int stages, uint64_t booked_px);
 void render_lk_images(esvio_fe_ctx* c, double t_sync, int cams, int slotL, int slotR, int rawbuf);
-void render_and_build(esvio_fe_ctx* c, double t_sync, int slotL, int slotR, int rawbuf);
-bool render_cam_ok(const esvio_fe_ctx* c);
-void render_and_build_cam(esvio_fe_ctx* c, double t_sync, int cam, int slot);
+bool render_cam_ok(const esvio_fe_ctx* c);  // one camera alone can be built with the fused kernels
+void build_lk_images(esvio_fe_ctx* c, double t_sync, int cams /*1 left, 2 right, 3 both*/, int slotL, int slotR,
+                     int rawbuf, bool right_imported = false);
+inline int other_right_slot(const esvio_fe_ctx* c) { return c->slot_curR == kLeftSlots ? kLeftSlots + 1 : kLeftSlots; }
+void rotate_slots(esvio_fe_ctx* c, bool right_advanced);
 const PyrDesc& raw_ts_desc(const esvio_fe_ctx* c, int cam);
 LkArgs make_lk(const PyrDesc& P, const PyrDesc& N, const float2* prev, const float2* init, float2* next,
                uint8_t* status, const int* n_ptr, int n_max, int max_level, int max_count, double eps,
@@ -72,7 +78,7 @@ void clear_tracker_state(esvio_fe_ctx* c);
 SelectArgs make_select_args(esvio_fe_ctx* c, int set, int max_corners, float2* out_pts, int out_base,
                             int32_t* out_idx);
 size_t select_lds_bytes(const esvio_fe_ctx* c);
-size_t select_tables_lds_bytes(const esvio_fe_ctx* c);
+void launch_select_args(esvio_fe_ctx* c, SelectArgs s);
 void run_compact(esvio_fe_ctx* c, uint32_t n_events, int set);
 void run_select(esvio_fe_ctx* c, int set, int max_corners, float2* out_pts, int out_base, int32_t* out_idx,
                 const uint32_t* mask_bits = nullptr, int* host_counts = nullptr, bool publish = false,

@@ -88,7 +88,23 @@ constexpr int kRadixMaxBits = 8;
 constexpr int kRadixMaxPasses = 4;
 inline uint32_t radix_blocks(uint32_t n) { return (n + kRadixTile - 1) / kRadixTile; }
 // sort scratch layout (uint32 words): [ghist: passes<<bits][tickets: passes] cleared by k_sae_apply,
-// then [lookback: passes * radix_blocks(n) << bits] cleared by k_sae_keys
+// then [lookback: passes * radix_blocks(n) << bits] cleared by k_sae_keys.  The only place that computes an offset
+// into it (host-only arithmetic, inline like make_tile_geom below).
+constexpr uint32_t kSortTickets = (uint32_t)kRadixMaxPasses << kRadixMaxBits;  // behind the largest ghist
+constexpr uint32_t kSortHeadWords = kSortTickets + 64;
+static_assert(kSortTickets == 1024 && kSortHeadWords == 1088, "sort scratch layout moved");
+struct SortScratch {
+  uint32_t* ghist;      // [passes << bits]
+  uint32_t* tickets;    // [passes]
+  uint32_t* lookback;   // [passes][radix_blocks(n) << bits]
+  uint32_t head_words;  // ghist + tickets: what k_sae_apply clears
+};
+inline size_t sort_scratch_words(size_t cap) {  // for sorts of up to cap pairs, whatever (passes, bits)
+  return kSortHeadWords + (size_t)kRadixMaxPasses * ((size_t)radix_blocks((uint32_t)cap) << kRadixMaxBits);
+}
+inline SortScratch sort_scratch(uint32_t* base) {
+  return SortScratch{base, base + kSortTickets, base + kSortHeadWords, kSortHeadWords};
+}
 // keys[i] = cam*P + y*W + x (or invalid_key for out-of-sensor events), vals[i] = i, for the
 // virtual concatenation [left; right]; also fills the per-pass global digit histograms.
 void launch_sae_keys(hipStream_t s, const EventRec* evL, uint32_t nL, const EventRec* evR,
@@ -216,6 +232,33 @@ struct TileScratch {
   uint32_t* T;         // [ngroups][nt_cam + 1] bucket counts per group
   uint32_t* C;         // [ngroups][nt_cam + 1] ... of all earlier groups of the camera (out-of-sensor bin: of all earlier groups)
 };
+// The layout of the scratch (d_tile), in words, for a partition buffer of part_cap events: the only place that
+// computes an offset into it (host-only arithmetic, inline like make_tile_geom).  `meta` sits in the 32 spare words
+// behind tile_order.
+constexpr size_t kTileOffTotals = 0, kTileOffTileOff = kTileMaxBins, kTileOffOrder = 2 * (size_t)kTileMaxBins + 32,
+                 kTileOffMeta = 3 * (size_t)kTileMaxBins + 32, kTileOffRanges = 3 * (size_t)kTileMaxBins + 64,
+                 kTileOffP = kTileOffRanges + 4 * (size_t)kTileMaxGroups;
+static_assert(kTileOffTotals == 0 && kTileOffTileOff == 2048 && kTileOffOrder == 4128 && kTileOffMeta == 6176 &&
+                  kTileOffRanges == 6208 && kTileOffP == 8256,
+              "tile scratch layout moved");
+static_assert(kTileOffMeta + kTileMetaWords <= kTileOffRanges, "meta leaves the spare words behind tile_order");
+// rows of P: 2048 events per scatter block at least; each camera's last block may be short
+inline size_t tile_scratch_blocks(size_t part_cap) { return (part_cap + 2047) / 2048 + 2; }
+inline size_t tile_scratch_words(size_t part_cap) {
+  return kTileOffP + (tile_scratch_blocks(part_cap) + 2 * (size_t)kTileMaxGroups) * kTileMaxBins;
+}
+inline TileScratch tile_scratch(uint32_t* base, size_t part_cap) {
+  TileScratch sc;
+  sc.meta = base + kTileOffMeta;
+  sc.ranges = base + kTileOffRanges;
+  sc.totals = base + kTileOffTotals;
+  sc.tile_off = base + kTileOffTileOff;
+  sc.tile_order = base + kTileOffOrder;
+  sc.P = base + kTileOffP;
+  sc.T = sc.P + tile_scratch_blocks(part_cap) * kTileMaxBins;
+  sc.C = sc.T + (size_t)kTileMaxGroups * kTileMaxBins;
+  return sc;
+}
 // k_tile_hist: P, T and the blocks' ranges; launch_tile_scan: C, totals, the record format; out-of-sensor
 // events added to *n_rejected
 // mc (optional, enabled): the motion-compensated overload — buckets by the warped pixel, which is kept

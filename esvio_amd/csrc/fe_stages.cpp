@@ -3,6 +3,8 @@
 // Every data-parallel stage is a HIP kernel from fe_kernels.hip; there is no CPU fallback.
 #include "fe_internal.h"
 
+#include <optional>
+
 namespace esvio {
 namespace fe {
 
@@ -29,9 +31,7 @@ static int grow_sort_buffers(esvio_fe_ctx* c, size_t cap) {
 int ensure_sort_capacity(esvio_fe_ctx* c, size_t n) {
   if (n > c->sort_cap)
     if (int rc = grow_sort_buffers(c, std::max<size_t>(n + n / 4, 1 << 16))) return rc;
-  // [ghist + tickets | lookback for every pass]
-  const size_t head = ((size_t)kRadixMaxPasses << kRadixMaxBits) + 64;
-  size_t hneed = head + (size_t)kRadixMaxPasses * (radix_blocks((uint32_t)c->sort_cap) << kRadixMaxBits);
+  const size_t hneed = sort_scratch_words(c->sort_cap);
   if (hneed > c->hist.cap) {
     if (int rc = c->hist.alloc(c, hneed)) return rc;
     const hipError_t zeroed = hipMemsetAsync(c->hist, 0, hneed * 4, cur_stream(c));
@@ -116,9 +116,14 @@ int pyr_alloc(esvio_fe_ctx* c, PyrStore& ps, int w, int h, int max_level) {
   return 0;
 }
 
+uint64_t pyr_pixels(const PyrDesc& d) {
+  uint64_t px = 0;
+  for (int l = 0; l <= d.levels; l++) px += (uint64_t)d.w[l] * d.h[l];
+  return px;
+}
+
 // level 0 interior already written -> pyrDown chain, border fill, Scharr
 void pyr_build(esvio_fe_ctx* c, const PyrDesc* p, int nimg) {
-  uint64_t px0 = (uint64_t)p[0].w[0] * p[0].h[0] * nimg;
   for (int l = 0; l < p[0].levels; l++) {
     uint64_t src = (uint64_t)p[0].w[l] * p[0].h[l], dst = (uint64_t)p[0].w[l + 1] * p[0].h[l + 1];
     ScopedKernel k(c, K_PYR_DOWN, (src + dst) * nimg);
@@ -129,17 +134,10 @@ void pyr_build(esvio_fe_ctx* c, const PyrDesc* p, int nimg) {
     launch_pyr_pad(cur_stream(c), p, nimg);
   }
   {
-    uint64_t all = 0;
-    for (int l = 0; l <= p[0].levels; l++) all += (uint64_t)p[0].w[l] * p[0].h[l];
-    ScopedKernel k(c, K_SCHARR, all * 5 * nimg);  // 1 B read + 4 B written per pixel
+    ScopedKernel k(c, K_SCHARR, pyr_pixels(p[0]) * 5 * nimg);  // 1 B read + 4 B written per pixel
     launch_scharr(cur_stream(c), p, nimg);
   }
-  (void)px0;
 }
-
-// both cameras' LK images of a batch + their pyramids: render_lk_images + pyr_build, with the
-// time-surface and pyrDown launches fused into one when nothing sits between them
-void render_and_build(esvio_fe_ctx* c, double t_sync, int slotL, int slotR, int rawbuf);
 
 // ---------------------------------------------------------------- SAE update (both cameras)
 // Motion_correction_value -> kernel parameters (the kernels take t_0, the first left event's time,
@@ -176,9 +174,7 @@ int ensure_part_capacity(esvio_fe_ctx* c, size_t n, bool mc) {
   }
   if (mc && !c->d_warp)  // the motion-compensated overload: 4 B per event for the warped pixels
     if (int rc = c->d_warp.alloc(c, c->d_part.cap)) return rc;
-  const size_t nblk_cap = (c->d_part.cap + 2047) / 2048 + 2;  // (2048 events per scatter block at least; each camera's last block may be short)
-  const size_t head = (size_t)3 * kTileMaxBins + 64 + 4 * (size_t)kTileMaxGroups;
-  const size_t need = head + (nblk_cap + 2 * (size_t)kTileMaxGroups) * kTileMaxBins;
+  const size_t need = tile_scratch_words(c->d_part.cap);
   if (need > c->d_tile.cap)
     if (int rc = c->d_tile.alloc(c, need)) return rc;
   return 0;
@@ -188,30 +184,18 @@ int sae_update_tiled(esvio_fe_ctx* c, const EventRec* evL, uint32_t nL, const Ev
                      double2* L2, double2* S2, uint8_t* arc_touched, const McParams* mc) {
   const uint32_t n = nL + nR;
   if (int rc = ensure_part_capacity(c, n, mc != nullptr)) return rc;
-  const size_t nblk_cap = (c->d_part.cap + 2047) / 2048 + 2;
-  const size_t head = (size_t)3 * kTileMaxBins + 64 + 4 * (size_t)kTileMaxGroups;
-  TileScratch sc;
-  sc.meta = c->d_tile + 3 * kTileMaxBins + 32;  // (the 32 free words behind tile_order)
-  sc.ranges = c->d_tile + 3 * kTileMaxBins + 64;
-  sc.totals = c->d_tile;
-  sc.tile_off = c->d_tile + kTileMaxBins;
-  sc.tile_order = c->d_tile + 2 * kTileMaxBins + 32;
-  sc.P = c->d_tile + head;
-  sc.T = sc.P + nblk_cap * kTileMaxBins;
-  sc.C = sc.T + (size_t)kTileMaxGroups * kTileMaxBins;
+  const TileScratch sc = tile_scratch(c->d_tile, c->d_part.cap);
   {
-    {
-      ScopedKernel k(c, K_TILE_HIST, (uint64_t)n * 16);  // ingest: the raw records, read once
-      launch_tile_hist(cur_stream(c), evL, nL, evR, nR, c->tgeom, sc, c->d_rejected, mc, mc ? c->d_warp.p : nullptr);
-    }
-    {
-      ScopedKernel k(c, K_TILE_SCAN, 0);  // (the count matrices: not in SURVEY's accounting)
-      launch_tile_scan(cur_stream(c), nL, nR, c->tgeom, sc, c->d_rejected);
-    }
-    {
-      ScopedKernel k(c, K_TILE_SCATTER, (uint64_t)n * 24);  // the partition's own traffic: 16 B in, 8 B out (16 for wide records)
-      launch_tile_scatter(cur_stream(c), evL, nL, evR, nR, c->tgeom, sc, c->d_part, mc ? c->d_warp.p : nullptr);
-    }
+    ScopedKernel k(c, K_TILE_HIST, (uint64_t)n * 16);  // ingest: the raw records, read once
+    launch_tile_hist(cur_stream(c), evL, nL, evR, nR, c->tgeom, sc, c->d_rejected, mc, mc ? c->d_warp.p : nullptr);
+  }
+  {
+    ScopedKernel k(c, K_TILE_SCAN, 0);  // (the count matrices: not in SURVEY's accounting)
+    launch_tile_scan(cur_stream(c), nL, nR, c->tgeom, sc, c->d_rejected);
+  }
+  {
+    ScopedKernel k(c, K_TILE_SCATTER, (uint64_t)n * 24);  // the partition's own traffic: 16 B in, 8 B out (16 for wide records)
+    launch_tile_scatter(cur_stream(c), evL, nL, evR, nR, c->tgeom, sc, c->d_part, mc ? c->d_warp.p : nullptr);
   }
   {
     ScopedKernel k(c, K_TILE_APPLY, (uint64_t)n * 32);
@@ -219,6 +203,24 @@ int sae_update_tiled(esvio_fe_ctx* c, const EventRec* evL, uint32_t nL, const Ev
                       arc_touched, c->zpin[0].counts + 3, c->lim.ticket);
   }
   return 0;
+}
+
+// keys[0] / vals[0] (n pairs, their digit histograms in the sort scratch, look-back words cleared) -> sorted by
+// `passes` stable passes of `bits` bits each; returns which of keys[] / vals[] holds the result.  `booked`: the passes
+// are booked as K_RADIX_PASS (goodFeaturesToTrack's stages are not in the kernel statistics).
+int radix_sort_pairs(esvio_fe_ctx* c, uint32_t n, int passes, int bits, bool booked) {
+  const SortScratch sc = sort_scratch(c->hist);
+  const size_t pass_words = (size_t)radix_blocks(n) << bits;
+  int cur = 0;
+  for (int p = 0; p < passes; p++) {
+    std::optional<ScopedKernel> k;
+    if (booked) k.emplace(c, K_RADIX_PASS, (uint64_t)n * 16);
+    launch_radix_pass(cur_stream(c), c->keys[cur], c->vals[cur], n, p * bits, bits, sc.ghist + ((size_t)p << bits),
+                      sc.lookback + p * pass_words, sc.tickets + p, c->keys[cur ^ 1], c->vals[cur ^ 1],
+                      c->zpin[0].counts + 3, c->lim.lookback);
+    cur ^= 1;
+  }
+  return cur;
 }
 
 // arc_set >= 0: this batch's Arc* pass will run into candidate set arc_set; *arc_marked tells
@@ -240,33 +242,21 @@ int sae_update(esvio_fe_ctx* c, const EventRec* evL, uint32_t nL, const EventRec
   if (int rc = ensure_sort_capacity(c, n)) return rc;
   const int passes = (c->key_bits + 6) / 7;
   const int bits = (c->key_bits + passes - 1) / passes;
-  const uint32_t nblk = radix_blocks(n);
-  const uint32_t head = ((uint32_t)kRadixMaxPasses << kRadixMaxBits) + 64;
-  uint32_t* ghist = c->hist;                                        // [passes << bits]
-  uint32_t* tickets = c->hist + ((size_t)kRadixMaxPasses << kRadixMaxBits);  // [passes]
-  uint32_t* lookback = c->hist + head;                              // [passes][nblk << bits]
-  const uint32_t lb_words = (uint32_t)passes * (nblk << bits);
+  const SortScratch sc = sort_scratch(c->hist);
   {
     ScopedKernel k(c, K_SAE_KEYS, (uint64_t)n * 16);
     launch_sae_keys(cur_stream(c), evL, nL, evR, nR, c->W, c->H, c->keys[0], c->vals[0], c->invalid_key,
-                    c->d_rejected, passes, bits, ghist, lookback, lb_words, mc);
+                    c->d_rejected, passes, bits, sc.ghist, sc.lookback, (uint32_t)passes * (radix_blocks(n) << bits), mc);
   }
-  int cur = 0;
-  for (int p = 0; p < passes; p++) {
-    ScopedKernel k(c, K_RADIX_PASS, (uint64_t)n * 16);
-    launch_radix_pass(cur_stream(c), c->keys[cur], c->vals[cur], n, p * bits, bits, ghist + ((size_t)p << bits),
-                      lookback + (size_t)p * (nblk << bits), tickets + p, c->keys[cur ^ 1],
-                      c->vals[cur ^ 1], c->zpin[0].counts + 3, c->lim.lookback);
-    cur ^= 1;
-  }
+  const int cur = radix_sort_pairs(c, n, passes, bits);
   {
     ScopedKernel k(c, K_SAE_APPLY, (uint64_t)n * 32);
     if (n >= c->sae_ev_min)  // many events per pixel: one lane per event
       launch_sae_apply_ev(cur_stream(c), c->keys[cur], c->vals[cur], n, evL, nL, evR, L2, S2,
-                          c->cfg.feature_filter_threshold, c->invalid_key, c->hist, head, c->sae_marks);
+                          c->cfg.feature_filter_threshold, c->invalid_key, c->hist, sc.head_words, c->sae_marks);
     else
       launch_sae_apply(cur_stream(c), c->keys[cur], c->vals[cur], n, evL, nL, evR, L2, S2,
-                       c->cfg.feature_filter_threshold, c->invalid_key, c->hist, head);
+                       c->cfg.feature_filter_threshold, c->invalid_key, c->hist, sc.head_words);
   }
   return 0;
 }
@@ -309,116 +299,78 @@ void render_ts(esvio_fe_ctx* c, double t_sync, uint8_t* dst0, uint8_t* dst1, int
 }
 
 
+// CLAHE of nimg images, stages 0 .. stages-1: per-tile LUTs, LUT blending + min/max, MINMAX normalisation in place.
+// booked_px: the pixels per image the stages are booked with (0: the image front-end's, which are not)
+void run_clahe(esvio_fe_ctx* c, const uint8_t* src0, const uint8_t* src1, int src_stride, uint8_t* dst0, uint8_t* dst1,
+               int dst_stride, int nimg, int stages, uint64_t booked_px) {
+  for (int stage = 0; stage < stages; stage++) {
+    ScopedKernel k(c, K_CLAHE, booked_px * (stage == 0 ? 1 : 2) * nimg);
+    launch_clahe(cur_stream(c), src0, src1, src_stride, dst0, dst1, dst_stride, c->W, c->H, c->d_lut, c->d_minmax, nimg,
+                 stage);
+  }
+}
+
 // the image trackEvent feeds to LK: the raw time surface, or CLAHE + normalize of it when
 // `equalize` (feature_tracker.cpp:375-387).  cams: bit 0 left, bit 1 right.  Raw surfaces stay
 // available for the TS_LK_THRESHOLD test and gettimesurface().
 void render_lk_images(esvio_fe_ctx* c, double t_sync, int cams, int slotL, int slotR, int rawbuf) {
-  const PyrDesc& L = c->pyr[slotL].d;
-  const PyrDesc& R = c->pyr[slotR].d;
-  if (!c->cfg.equalize) {
-    if (cams == 3) render_ts(c, t_sync, L.img[0], R.img[0], 2, c->S2);
-    else if (cams == 1) render_ts(c, t_sync, L.img[0], L.img[0], 1, c->S2);
-    else if (cams == 2) render_ts(c, t_sync, R.img[0], R.img[0], 1, c->S2 + c->P);
-    return;
-  }
-  const PyrDesc& rl = c->raw[rawbuf][0].d;
-  const PyrDesc& rr = c->raw[rawbuf][1].d;
-  int nimg;
-  const uint8_t *s0, *s1;
-  uint8_t *d0, *d1;
-  if (cams == 3) {
-    render_ts(c, t_sync, rl.img[0], rr.img[0], 2, c->S2);
-    nimg = 2; s0 = px00(rl); s1 = px00(rr); d0 = px00(L); d1 = px00(R);
-  } else if (cams == 1) {
-    render_ts(c, t_sync, rl.img[0], rl.img[0], 1, c->S2);
-    nimg = 1; s0 = s1 = px00(rl); d0 = d1 = px00(L);
-  } else {
-    render_ts(c, t_sync, rr.img[0], rr.img[0], 1, c->S2 + c->P);
-    nimg = 1; s0 = s1 = px00(rr); d0 = d1 = px00(R);
-  }
-  for (int stage = 0; stage < 3; stage++) {
-    ScopedKernel k(c, K_CLAHE, stage == 0 ? (uint64_t)c->P * nimg : (uint64_t)c->P * 2 * nimg);
-    launch_clahe(cur_stream(c), s0, s1, rl.stride[0], d0, d1, L.stride[0], c->W, c->H, c->d_lut,
-                 c->d_minmax, nimg, stage);
-  }
+  const bool eq = c->cfg.equalize;
+  // the cameras rendered: cam0, and with both cam1 = the right one (one camera: both name it)
+  const int cam0 = cams == 2 ? 1 : 0, cam1 = cams == 1 ? 0 : 1, nimg = cams == 3 ? 2 : 1;
+  const PyrDesc* lk[2] = {&c->pyr[slotL].d, &c->pyr[slotR].d};
+  const PyrDesc &l0 = *lk[cam0], &l1 = *lk[cam1];
+  const PyrDesc &r0 = eq ? c->raw[rawbuf][cam0].d : l0, &r1 = eq ? c->raw[rawbuf][cam1].d : l1;  // the raw surfaces
+  render_ts(c, t_sync, r0.img[0], r1.img[0], nimg, c->S2 + (size_t)cam0 * c->P);
+  if (eq) run_clahe(c, px00(r0), px00(r1), r0.stride[0], px00(l0), px00(l1), l0.stride[0], nimg, 3, c->P);
 }
 
-void render_and_build(esvio_fe_ctx* c, double t_sync, int slotL, int slotR, int rawbuf) {
-  PyrDesc two[2] = {c->pyr[slotL].d, c->pyr[slotR].d};
-  const bool fused = c->fuse_ts_pyr && !c->cfg.equalize && c->cfg.median_blur_kernel_size <= 0 &&
-                     two[0].levels == 3 && two[1].levels == 3;
-  const bool fused_eq = c->fuse_ts_pyr && c->cfg.equalize && c->cfg.median_blur_kernel_size <= 0 &&
-                        two[0].levels == 3 && two[1].levels == 3;
-  if (fused_eq) {
+// The fused kernels apply — the time surface rendered into level 0 in place, levels 1..3 in one launch, borders and
+// Scharr in one — when nothing sits between the surface and the pyramid (no median) and the pyramid has the three
+// levels they build.  With `equalize` the middle launch is k_norm_pyr (both cameras only) instead of k_pyr3.
+static bool fused_build_ok(const esvio_fe_ctx* c, const PyrDesc& d) {
+  return c->fuse_ts_pyr && c->cfg.median_blur_kernel_size <= 0 && d.levels == 3;
+}
+// ... for one camera alone (a plain call split by camera, fe_track.cpp)
+bool render_cam_ok(const esvio_fe_ctx* c) { return !c->cfg.equalize && fused_build_ok(c, c->pyr[0].d); }
+
+// The LK images of the cameras in `cams` (1 left, 2 right, 3 both) at t_sync and their pyramids.  right_imported
+// (cams == 1): the right image is in slotR already (esvio_fe_import_image) and gets its pyramid here too.
+void build_lk_images(esvio_fe_ctx* c, double t_sync, int cams, int slotL, int slotR, int rawbuf, bool right_imported) {
+  const int cam0 = cams == 2 ? 1 : 0, nimg = cams == 3 ? 2 : 1;
+  const PyrDesc two[2] = {c->pyr[slotL].d, c->pyr[slotR].d};
+  const PyrDesc* p = two + cam0;
+  if (right_imported || !fused_build_ok(c, p[0]) || (c->cfg.equalize && cams != 3)) {
+    render_lk_images(c, t_sync, cams, slotL, slotR, rawbuf);
+    pyr_build(c, p, right_imported ? 2 : nimg);
+    return;
+  }
+  const uint64_t px = pyr_pixels(p[0]);
+  if (c->cfg.equalize) {
     // time surfaces -> raw; CLAHE LUTs; CLAHE output -> a linear scratch pair (no in-place normalise:
-    // the fused kernel's blocks read their neighbours' pixels); normalise + pyramid levels; borders + Scharr
+    // the fused kernel's blocks read their neighbours' pixels); normalise + pyramid levels
     const PyrDesc& rl = c->raw[rawbuf][0].d;
     const PyrDesc& rr = c->raw[rawbuf][1].d;
     render_ts(c, t_sync, rl.img[0], rr.img[0], 2, c->S2);
-    for (int stage = 0; stage < 2; stage++) {
-      ScopedKernel k(c, K_CLAHE, stage == 0 ? (uint64_t)c->P * 2 : (uint64_t)c->P * 4);
-      launch_clahe(cur_stream(c), px00(rl), px00(rr), rl.stride[0], c->d_eq_tmp, c->d_eq_tmp + c->P, c->W, c->W,
-                   c->H, c->d_lut, c->d_minmax, 2, stage);
-    }
-    {
-      uint64_t px = 0;
-      for (int l = 0; l <= 3; l++) px += (uint64_t)two[0].w[l] * two[0].h[l];
-      ScopedKernel k(c, K_NORM_PYR, ((uint64_t)c->P + px) * 2);
-      launch_norm_pyr(cur_stream(c), c->d_eq_tmp, c->d_eq_tmp + c->P, c->W, c->d_minmax, two);
-    }
-    {
-      uint64_t all = 0;
-      for (int l = 0; l <= 3; l++) all += (uint64_t)two[0].w[l] * two[0].h[l];
-      ScopedKernel k(c, K_PAD_SCHARR, all * 5 * 2);
-      launch_pad_scharr(cur_stream(c), two, 2);
-    }
-    return;
+    run_clahe(c, px00(rl), px00(rr), rl.stride[0], c->d_eq_tmp, c->d_eq_tmp + c->P, c->W, 2, 2, c->P);
+    ScopedKernel k(c, K_NORM_PYR, ((uint64_t)c->P + px) * 2);
+    launch_norm_pyr(cur_stream(c), c->d_eq_tmp, c->d_eq_tmp + c->P, c->W, c->d_minmax, two);
+  } else {
+    render_ts(c, t_sync, p[0].img[0], p[nimg - 1].img[0], nimg, c->S2 + (size_t)cam0 * c->P);
+    ScopedKernel k(c, K_PYR3, px * nimg);
+    launch_pyr3(cur_stream(c), p, nimg);
   }
-  if (!fused) {
-    render_lk_images(c, t_sync, 3, slotL, slotR, rawbuf);
-    pyr_build(c, two, 2);
-    return;
-  }
-  {
-    ScopedKernel k(c, K_TIME_SURFACE4, (uint64_t)c->P * 17 * 2);
-    k.id = launch_time_surface(cur_stream(c), c->S2, c->W, c->H, t_sync, c->cfg.decay_ms / 1000.0, c->cfg.ignore_polarity,
-                               two[0].img[0], two[1].img[0], two[0].stride[0], 2);
-  }
-  {
-    uint64_t px = 0;
-    for (int l = 0; l <= 3; l++) px += (uint64_t)two[0].w[l] * two[0].h[l];
-    ScopedKernel k(c, K_PYR3, px * 2);
-    launch_pyr3(cur_stream(c), two, 2);
-  }
-  {
-    uint64_t all = 0;
-    for (int l = 0; l <= 3; l++) all += (uint64_t)two[0].w[l] * two[0].h[l];
-    ScopedKernel k(c, K_PAD_SCHARR, all * 5 * 2);
-    launch_pad_scharr(cur_stream(c), two, 2);
-  }
+  ScopedKernel k(c, K_PAD_SCHARR, px * 5 * nimg);
+  launch_pad_scharr(cur_stream(c), p, nimg);
 }
 
-// one camera's LK image + pyramid (the fused kernels; the caller has checked render_cam_ok)
-bool render_cam_ok(const esvio_fe_ctx* c) {
-  return c->fuse_ts_pyr && !c->cfg.equalize && c->cfg.median_blur_kernel_size <= 0 && c->pyr[0].d.levels == 3;
-}
-void render_and_build_cam(esvio_fe_ctx* c, double t_sync, int cam, int slot) {
-  const PyrDesc one = c->pyr[slot].d;
-  uint64_t px = 0;
-  for (int l = 0; l <= 3; l++) px += (uint64_t)one.w[l] * one.h[l];
-  {
-    ScopedKernel k(c, K_TIME_SURFACE4, (uint64_t)c->P * 17);
-    k.id = launch_time_surface(cur_stream(c), c->S2 + (size_t)cam * c->P, c->W, c->H, t_sync, c->cfg.decay_ms / 1000.0,
-                               c->cfg.ignore_polarity, one.img[0], one.img[0], one.stride[0], 1);
-  }
-  {
-    ScopedKernel k(c, K_PYR3, px);
-    launch_pyr3(cur_stream(c), &one, 1);
-  }
-  {
-    ScopedKernel k(c, K_PAD_SCHARR, px * 5);
-    launch_pad_scharr(cur_stream(c), &one, 1);
-  }
+// the next frame's slots: a left slot that is neither prev nor cur (the first frame: slot 0), the other right slot —
+// unless esvio_fe_import_image has advanced it with the image it brought (right_advanced) — and the next raw pair
+void rotate_slots(esvio_fe_ctx* c, bool right_advanced) {
+  int sl = 0;
+  while (c->have_img && (sl == c->slot_prevL || sl == c->slot_curL)) sl++;
+  c->slot_curL = sl;
+  if (!right_advanced) c->slot_curR = other_right_slot(c);
+  c->raw_cur = (c->raw_cur + 1) % kRightSlots;
 }
 
 const PyrDesc& raw_ts_desc(const esvio_fe_ctx* c, int cam) {
@@ -668,6 +620,8 @@ void clear_tracker_state(esvio_fe_ctx* c) {
   c->cur_time = c->prev_time = 0;
 }
 
+// the selection over candidate set `set` with the handle's disc (cv::circle of min_dist); what a caller's selection
+// differs in — another list, another disc, host_counts, a mask, publication — it sets itself
 SelectArgs make_select_args(esvio_fe_ctx* c, int set, int max_corners, float2* out_pts, int out_base,
                             int32_t* out_idx) {
   SelectArgs s{};
@@ -700,8 +654,16 @@ size_t select_lds_bytes(const esvio_fe_ctx* c) {
   // bitmap + half-width table + the kept points whose discs seed the bitmap
   return ((size_t)c->H * ((c->W + 31) / 32) + 4 + 64 + (size_t)std::max(c->cfg.max_cnt, 1)) * 4;
 }
-size_t select_tables_lds_bytes(const esvio_fe_ctx* c) {  // with the bitmap in global memory
+static size_t select_tables_lds_bytes(const esvio_fe_ctx* c) {  // with the bitmap in global memory
   return (4 + 64 + (size_t)std::max(c->cfg.max_cnt, 1)) * 4;
+}
+
+// the greedy selection `s` describes, its bitmap in LDS or — where that does not fit (select_ok, esvio_fe_create:
+// d_sel_bitmap is there then) — in device memory: slower, same result
+void launch_select_args(esvio_fe_ctx* c, SelectArgs s) {
+  if (!c->select_ok) s.gbitmap = c->d_sel_bitmap;
+  ScopedKernel k(c, K_SELECT_MW, 0);
+  k.id = launch_select(cur_stream(c), s, c->select_ok ? select_lds_bytes(c) : select_tables_lds_bytes(c));
 }
 
 // ordered compaction of candidate set `set` (right behind the k_arc that filled it)
@@ -727,14 +689,7 @@ void run_select(esvio_fe_ctx* c, int set, int max_corners, float2* out_pts, int 
     s.pub_done = c->d_pub_done;
     s.pub_seq = c->pub_seq;
   }
-  size_t lds = select_lds_bytes(c);
-  if (!c->select_ok) {  // the bitmap does not fit LDS: it lives in device memory (slower, same result)
-    if (!c->d_sel_bitmap && c->d_sel_bitmap.alloc(c, (size_t)c->H * s.wpr + 4) != 0) return;
-    s.gbitmap = c->d_sel_bitmap;
-    lds = select_tables_lds_bytes(c);
-  }
-  ScopedKernel k(c, K_SELECT_MW, 0);
-  k.id = launch_select(cur_stream(c), s, lds);
+  launch_select_args(c, s);
 }
 
 // Arc* flags (+ ordered per-block candidate lists into set `set`) for the left events; `ts` is the

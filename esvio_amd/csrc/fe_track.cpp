@@ -53,7 +53,7 @@ static int prefetch_issue(esvio_fe_ctx* c, const PrefetchJob& j) {
   int rc = sae_update(c, dL, (uint32_t)b.nL, dR, (uint32_t)b.nR, b.has_motion ? &mcp : nullptr, nullptr, nullptr,
                       b.pub && b.nL ? b.cand : -1, &arc_marked);
   if (!rc) {
-    render_and_build(c, b.time, b.slotL, b.slotR, b.raw);
+    build_lk_images(c, b.time, 3, b.slotL, b.slotR, b.raw);
     if (hipEventRecord(c->ev_lane_done[b.lane], c->stream2) != hipSuccess)
       rc = fail(c, ESVIO_FE_EHIP, "hipEventRecord failed");
     // (a sequence issued by the launch thread: the word a chained LK launch made before this point waits for)
@@ -673,20 +673,15 @@ struct TrackCall {
       } else if (int rc = stage_events(c, left, nL, right, nR, space, &dL, &dR)) {
         return rc;
       }
-      // SAEtoTimeSurface_left/right(cur_time) (:367-368) -> cur images; slot rotation replaces the
+      // SAEtoTimeSurface_left/right(cur_time) (:367-368) -> cur images; slot rotation (rotate_slots) replaces the
       // cv::Mat header swaps of :390-403,:585.  Left slots 0..2: {prev, cur, free}.
-      int sl = 0;
-      while (!first && (sl == c->slot_prevL || sl == c->slot_curL)) sl++;
-      const int new_curL = sl;
       if (split) {
         if (int rc = sae_update(c, dL, (uint32_t)nL, nullptr, 0, nullptr, nullptr, nullptr,
                                 PUB_THIS_FRAME ? c->cand_cur : -1, &arc_marked_main))
           return rc;
         HIPCHK(c, hipEventRecord(c->ev_sae_left, c->stream));
-        c->slot_curL = new_curL;
-        c->slot_curR = c->slot_curR == kLeftSlots ? kLeftSlots + 1 : kLeftSlots;
-        c->raw_cur = (c->raw_cur + 1) % kRightSlots;
-        render_and_build_cam(c, c->cur_time, 0, c->slot_curL);
+        rotate_slots(c, false);
+        build_lk_images(c, c->cur_time, 1, c->slot_curL, c->slot_curR, c->raw_cur);
         HIPCHK(c, hipEventRecord(c->ev_imgs_ready, c->stream));
         // the right camera, on the stereo stream
         if (staged) {
@@ -699,7 +694,7 @@ struct TrackCall {
           StreamScope on_stereo_stream(stereo_stream(c));
           HIPCHK(c, hipStreamWaitEvent(stereo_stream(c), c->ev_sae_left, 0));  // (the partition scratch is the left chain's until then)
           if (int rc = sae_update(c, nullptr, 0, dR, (uint32_t)nR)) return rc;
-          render_and_build_cam(c, c->cur_time, 1, c->slot_curR);
+          build_lk_images(c, c->cur_time, 2, c->slot_curL, c->slot_curR, c->raw_cur);
           HIPCHK(c, hipEventRecord(c->ev_right_ready, stereo_stream(c)));
         }
         split_right = true;
@@ -718,17 +713,10 @@ struct TrackCall {
                                      PUB_THIS_FRAME ? c->cand_cur : -1, &arc_marked_main)) {
         return rc;
       }
-      c->slot_curL = new_curL;
       // camera split: the right image was imported into slot_curR by esvio_fe_import_image
-      if (!c->ext_right_pending) c->slot_curR = c->slot_curR == kLeftSlots ? kLeftSlots + 1 : kLeftSlots;
-      c->raw_cur = (c->raw_cur + 1) % kRightSlots;
-      if (c->ext_right_pending) {
-        render_lk_images(c, c->cur_time, 1, c->slot_curL, c->slot_curR, c->raw_cur);
-        PyrDesc cur2[2] = {c->pyr[c->slot_curL].d, c->pyr[c->slot_curR].d};
-        pyr_build(c, cur2, 2);
-      } else {
-        render_and_build(c, c->cur_time, c->slot_curL, c->slot_curR, c->raw_cur);
-      }
+      rotate_slots(c, c->ext_right_pending);
+      build_lk_images(c, c->cur_time, c->ext_right_pending ? 1 : 3, c->slot_curL, c->slot_curR, c->raw_cur,
+                      c->ext_right_pending);
       c->ext_right_pending = false;
       HIPCHK(c, hipEventRecord(c->ev_imgs_ready, c->stream));
       }

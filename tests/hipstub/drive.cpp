@@ -9,6 +9,9 @@
 // The last line is a digest of what every successful track call and esvio_fe_finish returned (n_left, n_right, ids,
 // cur_pts, ids_right, cur_right_pts, both velocity arrays): two builds of the library that compute the same print the same.
 //   drive <seed> <frames>      exit 0: done; the sanitizer reports on stderr
+//   drive trace                with HIPSTUB_TRACE=<file>: one thread, a fixed matrix of handles and calls (trace_matrix
+//                              below); the file then holds every launch and stream call in order, with its stream, and
+//                              per handle what the profiling API counted (tests/test_launch_trace.py)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -19,6 +22,9 @@
 #include "esvio_fe_test.h"
 extern "C" void hipstub_arm_faults(int on);  // tests/hipstub/hip_stub.cpp
 extern "C" void hipstub_live(long out[4]);
+extern "C" void hipstub_trace_on(int on);
+extern "C" void hipstub_trace_note(const char* text);
+extern "C" void hipstub_set_compact_total(uint32_t n);
 #endif
 
 static uint32_t rs;
@@ -142,7 +148,152 @@ static int first_use_pass(esvio_fe_config c, int W, int H, bool images) {
   return bad;
 }
 
+// ---- drive trace.  No launch thread, no RANSAC helpers, no staging threads: every HIP call is made by this thread,
+// so the order of the lines is the order of the code.  The handles' creation is left out of the trace (its warm-up
+// alone is 1200 lines); everything from there to the profile counters is in.
+static int trace_bad = 0;
+static void note(const char* fmt, const char* a, int b = 0, int c2 = 0) {
+  char buf[256];
+  snprintf(buf, sizeof(buf), fmt, a, b, c2);
+  hipstub_trace_note(buf);
+}
+#define TR(call)                                                                  \
+  do {                                                                            \
+    note("-- %s", #call);                                                         \
+    if ((call) != ESVIO_FE_OK) {                                                  \
+      trace_bad++;                                                                \
+      fprintf(stderr, "drive trace: %s: %s\n", #call, esvio_fe_last_error(h));    \
+    }                                                                             \
+  } while (0)
+
+static esvio_fe_handle trace_create(const char* label, esvio_fe_config c, int W, int H) {
+  c.width = W; c.height = H;
+  for (int k = 0; k < 2; k++) { c.cam[k].fx = c.cam[k].fy = 0.9 * W; c.cam[k].cx = W / 2.0; c.cam[k].cy = H / 2.0; }
+  note("== %s %d x %d", label, W, H);
+  esvio_fe_handle h = nullptr;
+  hipstub_trace_on(0);
+  const int rc = esvio_fe_create(&c, &h);
+  if (rc == ESVIO_FE_OK) esvio_fe_set_profiling(h, 1);
+  hipstub_trace_on(1);
+  if (rc != ESVIO_FE_OK) { trace_bad++; return nullptr; }
+  rs = 1;
+  return h;
+}
+
+static void trace_destroy(esvio_fe_handle h) {
+  for (int id = 0; id < esvio_fe_kernel_count(); id++) {
+    uint64_t launches = 0, bytes = 0;
+    hipstub_trace_on(0);
+    esvio_fe_get_kernel_stats(h, id, nullptr, &launches, &bytes);
+    hipstub_trace_on(1);
+    char buf[128];
+    snprintf(buf, sizeof(buf), "profile %s launches %llu bytes %llu", esvio_fe_kernel_name(id), (unsigned long long)launches,
+             (unsigned long long)bytes);
+    hipstub_trace_note(buf);
+  }
+  esvio_fe_destroy(h);
+}
+
+struct TraceOut {
+  std::vector<int32_t> ids, cnt, idr;
+  std::vector<float> f2[6];
+  esvio_fe_tracks t;
+  explicit TraceOut(int M) : ids((size_t)M), cnt((size_t)M), idr((size_t)M) {
+    for (auto& v : f2) v.resize(2 * (size_t)M);
+    std::memset(&t, 0, sizeof(t));
+    t.ids = ids.data(); t.track_cnt = cnt.data(); t.cur_pts = f2[0].data(); t.cur_un_pts = f2[1].data();
+    t.pts_velocity = f2[2].data(); t.ids_right = idr.data(); t.cur_right_pts = f2[3].data();
+    t.cur_un_right_pts = f2[4].data(); t.right_pts_velocity = f2[5].data();
+  }
+};
+
+static void trace_event_handle(const char* label, const esvio_fe_config& c, int W, int H) {
+  esvio_fe_handle h = trace_create(label, c, W, H);
+  if (!h) return;
+  const int M = c.max_cnt;
+  TraceOut o(M);
+  esvio_fe_tracks& t = o.t;
+  Batch b[9];
+  for (int i = 0; i < 9; i++) make_batch(b[i], W, H, i, 3000 + 100 * i);
+#define EV(i) b[i].t, b[i].L.data(), b[i].L.size(), b[i].R.data(), b[i].R.size()
+  // plain calls: batches in "device" memory (the stub's device memory is the host's), then in pageable memory
+  TR(esvio_fe_track_event(h, EV(0), ESVIO_FE_DEVICE, 1, &t));
+  TR(esvio_fe_track_event(h, EV(1), ESVIO_FE_DEVICE, 0, &t));
+  TR(esvio_fe_track_event(h, EV(2), ESVIO_FE_DEVICE, 1, &t));
+  TR(esvio_fe_track_event(h, EV(3), ESVIO_FE_HOST, 1, &t));
+  TR(esvio_fe_track_event(h, EV(4), ESVIO_FE_HOST, 0, &t));
+  TR(esvio_fe_track_event(h, EV(5), ESVIO_FE_HOST, 1, &t));
+  // two batches announced ahead
+  TR(esvio_fe_set_next_batch(h, EV(6), ESVIO_FE_HOST, 1));
+  TR(esvio_fe_set_next_batch(h, EV(7), ESVIO_FE_HOST, 0));
+  TR(esvio_fe_track_event(h, EV(6), ESVIO_FE_HOST, 1, &t));
+  TR(esvio_fe_track_event(h, EV(7), ESVIO_FE_HOST, 0, &t));
+  TR(esvio_fe_finish(h, &t));
+  // the right camera's image brought in from outside, then the frame it belongs to
+  std::vector<uint8_t> img((size_t)W * H, 7);
+  TR(esvio_fe_import_image(h, 1, img.data(), ESVIO_FE_HOST));
+  TR(esvio_fe_track_event(h, EV(8), ESVIO_FE_DEVICE, 1, &t));
+  TR(esvio_fe_sae_to_time_surface(h, 0, b[8].t, img.data()));
+  TR(esvio_fe_sae_to_time_surface(h, 1, b[8].t, img.data()));
+  std::vector<float> xy(2 * (size_t)M);
+  int32_t n = 0;
+  TR(esvio_fe_features_to_track(h, b[8].L.data(), b[8].L.size(), ESVIO_FE_HOST, M, nullptr, xy.data(), nullptr, &n));
+#undef EV
+  trace_destroy(h);
+}
+
+static void trace_image_handle(const char* label, const esvio_fe_config& c, int W, int H) {
+  esvio_fe_handle h = trace_create(label, c, W, H);
+  if (!h) return;
+  const int M = c.max_cnt;
+  TraceOut o(M);
+  const size_t P = (size_t)W * H;
+  std::vector<uint8_t> img(P, 7), img2(P, 9);
+  std::vector<float> xy(2 * (size_t)M);
+  int32_t n = 0;
+  TR(esvio_fe_track_image(h, 1.0, img.data(), img2.data(), 1, &o.t));
+  TR(esvio_fe_track_image(h, 1.03, img2.data(), img.data(), 0, &o.t));
+  TR(esvio_fe_track_image(h, 1.06, img.data(), nullptr, 1, &o.t));
+  TR(esvio_fe_good_features_to_track(h, img.data(), M, 0.01, 10.0, nullptr, xy.data(), &n, nullptr));
+  trace_destroy(h);
+}
+
+static int trace_matrix(esvio_fe_config c) {
+  setenv("ESVIO_FE_STAGE_THREADS", "0", 1);
+  hipstub_arm_faults(0);
+  hipstub_set_compact_total(1000);
+  const int W = 346, H = 260;
+  esvio_fe_config eq = c, med = c;
+  eq.equalize = 1;
+  med.median_blur_kernel_size = 1;
+  trace_event_handle("default", c, W, H);
+  trace_event_handle("equalize", eq, W, H);
+  trace_event_handle("median_blur_kernel_size=1", med, W, H);
+  setenv("ESVIO_FE_NO_FUSE", "1", 1);
+  trace_event_handle("ESVIO_FE_NO_FUSE", c, W, H);
+  trace_event_handle("equalize ESVIO_FE_NO_FUSE", eq, W, H);
+  unsetenv("ESVIO_FE_NO_FUSE");
+  setenv("ESVIO_FE_SAE_SORT", "1", 1);
+  trace_event_handle("ESVIO_FE_SAE_SORT", c, W, H);
+  unsetenv("ESVIO_FE_SAE_SORT");
+  setenv("ESVIO_FE_NO_CAMSPLIT", "1", 1);
+  trace_event_handle("ESVIO_FE_NO_CAMSPLIT", c, W, H);
+  unsetenv("ESVIO_FE_NO_CAMSPLIT");
+  trace_event_handle("pyramid of fewer than three levels", c, 160, 120);
+  trace_event_handle("selection bitmap in device memory", c, 1920, 1080);
+  trace_image_handle("images", c, W, H);
+  trace_image_handle("images equalize", eq, W, H);
+  long live[4];
+  hipstub_live(live);
+  char buf[128];
+  snprintf(buf, sizeof(buf), "live: device %ld pinned %ld events %ld streams %ld", live[0], live[1], live[2], live[3]);
+  hipstub_trace_note(buf);
+  if (trace_bad) fprintf(stderr, "drive trace: %d calls failed\n", trace_bad);
+  return trace_bad ? 6 : 0;
+}
+
 int main(int argc, char** argv) {
+  const bool trace_mode = argc > 1 && !strcmp(argv[1], "trace");
   rs = argc > 1 ? (uint32_t)atoi(argv[1]) : 1u;
   const int frames = argc > 2 ? atoi(argv[2]) : 200;
   const int W = 640, H = 480, M = 120;
@@ -152,6 +303,7 @@ int main(int argc, char** argv) {
   c.max_cnt = M; c.min_dist = 10; c.flow_back = 1; c.f_threshold = 1.0; c.f_ransac = 1; c.lk_accum = 1;
   c.focal_length = 460; c.device = -1;
   for (int k = 0; k < 2; k++) { c.cam[k].fx = c.cam[k].fy = 0.9 * W; c.cam[k].cx = W / 2.0; c.cam[k].cy = H / 2.0; }
+  if (trace_mode) return trace_matrix(c);
   std::vector<int32_t> ids(M), cnt(M), idr(M);
   std::vector<float> f2[6];
   for (auto& v : f2) v.resize(2 * M);

@@ -12,6 +12,7 @@ uint32_t lcg(uint32_t& s) { return s = s * 1664525u + 1013904223u; }
 
 // H2D of staged events by a kernel: the pinned buffer the staging threads filled is READ here
 void launch_stage_pull(hipStream_t s, const void* pinned_src, void* dst, size_t bytes) {
+  hipstub_trace("launch_stage_pull", s);
   hipstub_stream_begin(s);
   std::memcpy(dst, pinned_src, bytes);
   hipstub_stream_end(s);
@@ -19,6 +20,7 @@ void launch_stage_pull(hipStream_t s, const void* pinned_src, void* dst, size_t 
 
 // ... of packed chunks (fe_evstage.cpp stage_pack): unpacked here as k_stage_pull_packed does
 void launch_stage_pull_packed(hipStream_t s, const void* pinned_src, void* dst, size_t bytes, const void* desc, uint32_t epc) {
+  hipstub_trace("launch_stage_pull_packed", s);
   hipstub_stream_begin(s);
   const uint32_t* d = (const uint32_t*)desc;
   const uint8_t* src = (const uint8_t*)pinned_src;
@@ -40,15 +42,21 @@ void launch_stage_pull_packed(hipStream_t s, const void* pinned_src, void* dst, 
   hipstub_stream_end(s);
 }
 
+// (drive trace: goodFeaturesToTrack sorts its candidates only if there are at least two)
+static uint32_t g_compact_total = 0;
+extern "C" void hipstub_set_compact_total(uint32_t n) { g_compact_total = n; }
+
 void launch_compact(hipStream_t s, const uint32_t*, const uint32_t*, const uint32_t*, uint32_t, uint32_t*, uint32_t*,
                     uint32_t* total, uint32_t*) {
+  hipstub_trace("launch_compact", s);
   hipstub_stream_begin(s);
-  if (total) *total = 0;
+  if (total) *total = g_compact_total;
   hipstub_stream_end(s);
 }
 
 // Event_FeaturesToTrack: fills the free places with corners on a jittered grid (deterministic)
 KernelId launch_select(hipStream_t s, const SelectArgs& a, size_t) {
+  hipstub_trace("launch_select", s);
   hipstub_stream_begin(s);
   static uint32_t seed = 12345;
   const int want = a.max_corners > 0 ? a.max_corners : 0;
@@ -75,6 +83,7 @@ KernelId launch_select(hipStream_t s, const SelectArgs& a, size_t) {
 // calcOpticalFlowPyrLK forward (+ backward): every point found, moved by a fraction of a pixel that depends on the
 // point (so that the epipolar geometry is not degenerate), the backward pass lands on the start
 void launch_lk(hipStream_t s, const LkArgs& f, const LkArgs* b, float2* back_pts, uint8_t* back_status) {
+  hipstub_trace("launch_lk", s);
   hipstub_stream_begin(s);
   const int n = f.n_ptr ? *f.n_ptr : f.n_max;
   for (int i = 0; i < n && i < f.n_max; i++) {

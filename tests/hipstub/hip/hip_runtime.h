@@ -92,4 +92,10 @@ hipError_t hipGraphExecKernelNodeSetParams(hipGraphExec_t g, hipGraphNode_t n, c
 void hipstub_stream_begin(hipStream_t s);
 void hipstub_stream_end(hipStream_t s);
 static inline void hipstub_stream_op(hipStream_t s) { hipstub_stream_begin(s); hipstub_stream_end(s); }
+// HIPSTUB_TRACE=<file>: one line per launcher / stream call, "<what> <stream ordinal>[ <bytes>]" (streams are numbered
+// in the order they were created, from 1 again once none is left, 0 = the null stream); hipstub_trace_on switches the lines off and on (they start
+// on), hipstub_trace_note writes a line of the caller's own
+void hipstub_trace(const char* what, hipStream_t s, long bytes = -1);
+extern "C" void hipstub_trace_on(int on);
+extern "C" void hipstub_trace_note(const char* text);
 }

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -36,7 +37,33 @@ long fail_every() {
   static const long n = getenv("HIPSTUB_FAIL_EVERY") ? atol(getenv("HIPSTUB_FAIL_EVERY")) : 0;
   return n;
 }
+// HIPSTUB_TRACE (hip/hip_runtime.h)
+FILE* trace_file() {
+  static FILE* f = getenv("HIPSTUB_TRACE") ? fopen(getenv("HIPSTUB_TRACE"), "w") : nullptr;
+  return f;
+}
+std::mutex g_trace_mu;
+std::map<const void*, int> g_stream_no;  // (under g_trace_mu)
+int g_streams_made = 0;
+std::atomic<int> g_trace_on{1};
 }  // namespace
+
+void hipstub_trace(const char* what, hipStream_t s, long bytes) {
+  FILE* f = trace_file();
+  if (!f || !g_trace_on.load(std::memory_order_relaxed)) return;
+  std::lock_guard<std::mutex> lk(g_trace_mu);
+  const int no = s ? g_stream_no[s] : 0;
+  if (bytes >= 0) fprintf(f, "%s %d %ld\n", what, no, bytes);
+  else fprintf(f, "%s %d\n", what, no);
+}
+extern "C" void hipstub_trace_on(int on) { g_trace_on.store(on, std::memory_order_relaxed); }
+extern "C" void hipstub_trace_note(const char* text) {
+  FILE* f = trace_file();
+  if (!f) return;
+  std::lock_guard<std::mutex> lk(g_trace_mu);
+  fprintf(f, "%s\n", text);
+  fflush(f);
+}
 
 extern "C" void hipstub_arm_faults(int on) { g_armed.store(on, std::memory_order_relaxed); }
 extern "C" void hipstub_live(long out[4]) {
@@ -116,30 +143,49 @@ hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) {
   return hipSuccess;
 }
 hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t st) {
+  hipstub_trace("hipMemcpyAsync", st, (long)n);
   hipstub_stream_begin(st);
   if (n) memmove(d, s, n);
   hipstub_stream_end(st);
   return hipSuccess;
 }
 hipError_t hipMemcpy2DAsync(void* d, size_t dp, const void* s, size_t sp, size_t w, size_t h, hipMemcpyKind, hipStream_t st) {
+  hipstub_trace("hipMemcpy2DAsync", st, (long)(w * h));
   hipstub_stream_begin(st);
   for (size_t y = 0; y < h; y++) memmove((char*)d + y * dp, (const char*)s + y * sp, w);
   hipstub_stream_end(st);
   return hipSuccess;
 }
 hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t st) {
+  hipstub_trace("hipMemsetAsync", st, (long)n);
   hipstub_stream_begin(st);
   if (n) memset(d, v, n);
   hipstub_stream_end(st);
   return hipSuccess;
 }
-hipError_t hipStreamCreate(hipStream_t* s) { *s = new ihipStream_t; g_live[3]++; return hipSuccess; }
+hipError_t hipStreamCreate(hipStream_t* s) {
+  *s = new ihipStream_t;
+  g_live[3]++;
+  std::lock_guard<std::mutex> lk(g_trace_mu);
+  if (g_stream_no.empty()) g_streams_made = 0;  // (one handle at a time: every handle's streams count from 1)
+  g_stream_no[*s] = ++g_streams_made;
+  return hipSuccess;
+}
 hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { return hipStreamCreate(s); }
 hipError_t hipStreamCreateWithPriority(hipStream_t* s, unsigned, int) { return hipStreamCreate(s); }
-hipError_t hipStreamDestroy(hipStream_t s) { delete s; g_live[3]--; return hipSuccess; }
+hipError_t hipStreamDestroy(hipStream_t s) {
+  {
+    std::lock_guard<std::mutex> lk(g_trace_mu);
+    g_stream_no.erase(s);
+  }
+  delete s;
+  g_live[3]--;
+  return hipSuccess;
+}
 hipError_t hipStreamSynchronize(hipStream_t s) { (void)S(s)->seq.load(std::memory_order_acquire); return hipSuccess; }
 hipError_t hipStreamQuery(hipStream_t s) { (void)S(s)->seq.load(std::memory_order_acquire); return hipSuccess; }
 hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) {
+  hipstub_trace("hipStreamWaitEvent", s);
   (void)e->seq.load(std::memory_order_acquire);
   hipstub_stream_op(s);
   return hipSuccess;
@@ -149,6 +195,7 @@ hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return hipEventCre
 hipError_t hipEventDestroy(hipEvent_t e) { delete e; g_live[2]--; return hipSuccess; }
 hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) {
   if (fail_every() > 0 && g_armed.load(std::memory_order_relaxed) && (g_records.fetch_add(1, std::memory_order_relaxed) + 1) % fail_every() == 0) return hipErrorInvalidValue;
+  hipstub_trace("hipEventRecord", s);
   hipstub_stream_op(s);
   e->seq.fetch_add(1, std::memory_order_acq_rel);
   return hipSuccess;

@@ -33,7 +33,7 @@ def build_driver(tmp_path, tree=ROOT, name="drive_tsan", sanitize="thread"):
     subprocess.check_call([sys.executable, os.path.join(STUB, "gen_kernel_stubs.py"), os.path.join(csrc, "fe_kernels.h"), gen],
                           stdout=subprocess.DEVNULL)
     exe = str(tmp_path / name)
-    cmd = [cxx, "-O1", "-g", "-std=c++17", "-fsanitize=" + sanitize, "-ffp-contract=off", "-fno-math-errno",
+    cmd = [cxx, "-O1", "-g", "-std=c++17"] + (["-fsanitize=" + sanitize] if sanitize else []) + ["-ffp-contract=off", "-fno-math-errno",
            "-DESVIO_NO_SIMD_CLONES", "-pthread", "-I" + STUB, "-I" + os.path.join(tree, "include"), "-I" + csrc]
     cmd += [os.path.join(csrc, f) for f in HOST_SOURCES]
     cmd += [os.path.join(STUB, "hip_stub.cpp"), os.path.join(STUB, "fake_device.cpp"), gen, os.path.join(STUB, "drive.cpp"),

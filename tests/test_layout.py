@@ -41,3 +41,18 @@ def test_layout_header_stands_alone_and_owns_the_offsets():
         text = open(os.path.join(CSRC, name)).read()
         for expr in (r"\* 16 \+ 2 \*", r"\bstM\b", r"\bspec_bytes\b"):
             assert not re.search(expr, text), "%s computes an offset of its own: %s" % (name, expr)
+
+
+def test_partition_scratch_layouts_live_in_fe_kernels_h():
+    """the word offsets into the tiled partition's scratch (d_tile) and the radix sort's (hist) are computed by
+    tile_scratch / sort_scratch in fe_kernels.h — pinned there by static_asserts — and by no source file"""
+    hdr = open(os.path.join(CSRC, "fe_kernels.h")).read()
+    for pinned in ("kTileOffTileOff == 2048", "kTileOffOrder == 4128", "kTileOffMeta == 6176", "kTileOffRanges == 6208",
+                   "kTileOffP == 8256", "kSortHeadWords == 1088"):
+        assert pinned in hdr, pinned
+    for name in sorted(os.listdir(CSRC)):
+        if not name.endswith(".cpp"):
+            continue
+        text = open(os.path.join(CSRC, name)).read()
+        for expr in (r"kTileMaxBins", r"kTileOff", r"kRadixMaxPasses\s*<<", r"kSortTickets", r"->(hist|d_tile)(\.p)?\s*\+"):
+            assert not re.search(expr, text), "%s computes a scratch offset of its own: %s" % (name, expr)
