@@ -593,6 +593,77 @@ void lk_pair_end() {
   g_lk_pair_iter_sum += sum;
 }
 
+// ---- trace tap (oracle_lk_trace): what every (point, level) visit of lk_level did.  Filled only while g_lk_trace is
+// set; nothing below feeds back into the arithmetic, so oracle_lk's results are the same with and without it.
+enum { kLkExitNone = -1, kLkExitWindowOutAtStart = 0, kLkExitEig, kLkExitConverged, kLkExitOscillation, kLkExitCount,
+       kLkExitOutside };
+struct LkTrace {
+  int n, max_iter;     // points; slots per (point, level) in the per-iteration arrays
+  int32_t* iters;      // [n][4]            iterations that computed a delta
+  int32_t* exit;       // [n][4]            kLkExit*, kLkExitNone for a level the pyramid does not have
+  float* delta;        // [n][4][max_iter][2]  deltaX, deltaY of iteration j < iters
+  int32_t* inext;      // [n][4][max_iter][2]  inextX, inextY of iteration j (j == iters too where the exit is `outside`)
+  double* bmax;        // [n][4][2]         largest |running b1|, |running b2| (exact, row-major) of any iteration
+  float* A;            // [n][4][3]         A11, A12, A22 as the level used them (already scaled)
+  float* sat;          // [n][4][max_iter]  where along its chain (0..1) the first of the float-order mode's chains of
+                       //                   iteration j reached |sum| >= 2^24; 2 where none did; -1 where the chains as
+                       //                   lk_trace_b lays them out do not add up to the level's own float-order b
+};
+LkTrace* g_lk_trace = nullptr;
+constexpr int kLkTraceLevels = 4;
+
+// the b sums of one iteration once more, exactly: the running row-major totals, and the running sums of the chains the
+// x86 SIMD128 order adds in float — per component four vector lanes (pair sums of columns k, k + 4 of each step of 8:
+// 2 terms a row, 42 in all) and the scalar tail (columns 16.., 5 terms a row).  check_b: the level's b1, b2 where it
+// summed in that order (accum 2 / 4), or null; the chains here, added in float, must give the same bits
+void lk_trace_b(const uint8_t* J, int stepJ, int inextX, int inextY, int iw00, int iw01, int iw10, int iw11,
+                const int16_t* IWin, const int16_t* dWin, int win, double* bmax2, float* sat, const float* check_b) {
+  int64_t run[2] = {0, 0}, vec[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, tail[2] = {0, 0};
+  float fvec[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, ftail[2] = {0, 0};
+  const int nvec = (win / 8) * 8, vec_terms = (nvec / 8) * win * 2, tail_terms = (win - nvec) * win;
+  int vec_i = 0, tail_i = 0;
+  float first = 2.f;
+  const int64_t lim = (int64_t)1 << 24;
+  for (int y = 0; y < win; y++) {
+    const uint8_t* Jptr = J + (ptrdiff_t)(y + inextY) * stepJ + inextX;
+    int dv[64];
+    for (int x = 0; x < win; x++)
+      dv[x] = CV_DESCALE(Jptr[x] * iw00 + Jptr[x + 1] * iw01 + Jptr[x + stepJ] * iw10 + Jptr[x + stepJ + 1] * iw11, 9) -
+              IWin[y * win + x];
+    for (int x = 0; x < win; x++)
+      for (int c = 0; c < 2; c++) {
+        run[c] += (int64_t)dv[x] * dWin[(y * win + x) * 2 + c];
+        bmax2[c] = std::max(bmax2[c], (double)std::llabs(run[c]));
+      }
+    for (int x = 0; x + 8 <= nvec; x += 8) {
+      for (int k = 0; k < 4; k++)
+        for (int c = 0; c < 2; c++) {
+          const int64_t pair = (int64_t)dv[x + k] * dWin[(y * win + x + k) * 2 + c] +
+                               (int64_t)dv[x + k + 4] * dWin[(y * win + x + k + 4) * 2 + c];
+          vec[c][k] += pair;
+          fvec[c][k] += (float)pair;
+          if (std::llabs(vec[c][k]) >= lim) first = std::min(first, (float)vec_i / (float)vec_terms);
+        }
+      vec_i++;
+    }
+    for (int x = nvec; x < win; x++) {
+      for (int c = 0; c < 2; c++) {
+        const int64_t term = (int64_t)dv[x] * dWin[(y * win + x) * 2 + c];
+        tail[c] += term;
+        ftail[c] += (float)term;
+        if (std::llabs(tail[c]) >= lim) first = std::min(first, (float)tail_i / (float)tail_terms);
+      }
+      tail_i++;
+    }
+  }
+  if (check_b)
+    for (int c = 0; c < 2; c++) {
+      const float b = (ftail[c] + ((fvec[c][0] + fvec[c][2]) + (fvec[c][1] + fvec[c][3]))) * (1.f / (1 << 20));  // FLT_SCALE
+      if (std::memcmp(&b, &check_b[c], sizeof b) != 0) first = -1.f;
+    }
+  *sat = first;
+}
+
 // LKTrackerInvoker::operator() for all points at one level (video/src/lkpyramid.cpp) [OpenCV]
 // I, J: level images padded by `win` with BORDER_REFLECT_101; dI: Scharr (Ix,Iy) of I padded by
 // `win` with BORDER_CONSTANT 0 — exactly the buffers OpenCV's tracker indexes.  cols/rows are
@@ -610,7 +681,9 @@ void lk_level(const uint8_t* Ipad, const int16_t* dIpad, const uint8_t* Jpad, in
   const uint8_t* J = Jpad + (size_t)win * stepJ + win;
   const int16_t* derivI = dIpad + ((size_t)win * stepI + win) * 2;
 
+  LkTrace* const tr = g_lk_trace;
   for (int ptidx = 0; ptidx < npoints; ptidx++) {
+    const size_t tslot = (size_t)ptidx * kLkTraceLevels + level;  // (trace only)
     float prevX = prevPts[ptidx * 2] * (float)(1. / (1 << level));
     float prevY = prevPts[ptidx * 2 + 1] * (float)(1. / (1 << level));
     float nextX, nextY;
@@ -634,6 +707,7 @@ void lk_level(const uint8_t* Ipad, const int16_t* dIpad, const uint8_t* Jpad, in
     int iprevX = cv_floor_f(prevX), iprevY = cv_floor_f(prevY);
     if (iprevX < -win || iprevX >= cols || iprevY < -win || iprevY >= rows) {
       if (level == 0) status[ptidx] = 0;
+      if (tr) tr->exit[tslot] = kLkExitWindowOutAtStart;
       continue;
     }
     float a = prevX - iprevX;
@@ -738,8 +812,14 @@ void lk_level(const uint8_t* Ipad, const int16_t* dIpad, const uint8_t* Jpad, in
     float D = A11 * A22 - A12 * A12;
     float minEig = (A22 + A11 - std::sqrt((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) /
                    (float)(2 * win * win);
+    if (tr) {
+      tr->A[tslot * 3] = A11;
+      tr->A[tslot * 3 + 1] = A12;
+      tr->A[tslot * 3 + 2] = A22;
+    }
     if (minEig < minEigThreshold || D < FLT_EPSILON) {
       if (level == 0) status[ptidx] = 0;
+      if (tr) tr->exit[tslot] = kLkExitEig;
       continue;
     }
     D = 1.f / D;
@@ -748,13 +828,19 @@ void lk_level(const uint8_t* Ipad, const int16_t* dIpad, const uint8_t* Jpad, in
     nextY -= halfWinY;
     float prevDeltaX = 0, prevDeltaY = 0;
     g_lk_visits++;
+    int tr_exit = kLkExitCount, tr_iters = 0;  // (trace only)
     for (int j = 0; j < maxCount; j++) {
       g_lk_iters++;
       if (g_lk_pair_on && (size_t)ptidx < g_lk_pair.size()) g_lk_pair[ptidx]++;
       if (j == maxCount - 1) g_lk_maxed++;
       int inextX = cv_floor_f(nextX), inextY = cv_floor_f(nextY);
+      if (tr) {
+        tr->inext[(tslot * tr->max_iter + j) * 2] = inextX;
+        tr->inext[(tslot * tr->max_iter + j) * 2 + 1] = inextY;
+      }
       if (inextX < -win || inextX >= cols || inextY < -win || inextY >= rows) {
         if (level == 0) status[ptidx] = 0;
+        tr_exit = kLkExitOutside;
         break;
       }
       a = nextX - inextX;
@@ -883,18 +969,34 @@ void lk_level(const uint8_t* Ipad, const int16_t* dIpad, const uint8_t* Jpad, in
       }
       float deltaX = (float)((A12 * b2 - A22 * b1) * D);
       float deltaY = (float)((A12 * b1 - A11 * b2) * D);
+      if (tr) {
+        const float bb[2] = {b1, b2};
+        tr->delta[(tslot * tr->max_iter + j) * 2] = deltaX;
+        tr->delta[(tslot * tr->max_iter + j) * 2 + 1] = deltaY;
+        lk_trace_b(J, stepJ, inextX, inextY, iw00, iw01, iw10, iw11, IWinBuf.data(), dWinBuf.data(), win,
+                   &tr->bmax[tslot * 2], &tr->sat[tslot * tr->max_iter + j], accum == 2 || accum == 4 ? bb : nullptr);
+        tr_iters = j + 1;
+      }
       nextX += deltaX;
       nextY += deltaY;
       nextPts[ptidx * 2] = nextX + halfWinX;
       nextPts[ptidx * 2 + 1] = nextY + halfWinY;
-      if ((double)deltaX * deltaX + (double)deltaY * deltaY <= epsilon) break;
+      if ((double)deltaX * deltaX + (double)deltaY * deltaY <= epsilon) {
+        tr_exit = kLkExitConverged;
+        break;
+      }
       if (j > 0 && std::abs(deltaX + prevDeltaX) < 0.01 && std::abs(deltaY + prevDeltaY) < 0.01) {
         nextPts[ptidx * 2] -= deltaX * 0.5f;
         nextPts[ptidx * 2 + 1] -= deltaY * 0.5f;
+        tr_exit = kLkExitOscillation;
         break;
       }
       prevDeltaX = deltaX;
       prevDeltaY = deltaY;
+    }
+    if (tr) {
+      tr->exit[tslot] = tr_exit;
+      tr->iters[tslot] = tr_iters;
     }
     // the reference passes an `err` vector and no GET_MIN_EIGENVALS flag, so the err block
     // runs at level 0 and re-validates the final window position
@@ -2262,6 +2364,28 @@ int oracle_features_to_track(void* dv, const oracle_event* ev, size_t n, int max
 void oracle_pyr_down(const uint8_t* src, int sw, int sh, uint8_t* dst) { pyr_down(src, sw, sh, dst); }
 void oracle_scharr(const uint8_t* src, int w, int h, int16_t* dst) { scharr(src, w, h, dst); }
 int oracle_pyr_levels(int w, int h, int win, int max_level) { return pyr_levels(w, h, win, max_level); }
+int oracle_lk_trace(const uint8_t* prev, const uint8_t* next, int w, int h, const float* prev_pts, float* next_pts,
+                    uint8_t* status, int n, int win, int max_level, int max_count, double eps, int flags, int accum,
+                    int trace_iters, int32_t* t_iters, int32_t* t_exit, float* t_delta, int32_t* t_inext,
+                    double* t_bmax, float* t_A, float* t_sat) {
+  if (win > 64 || max_level >= kLkTraceLevels || trace_iters < std::min(std::max(max_count, 0), 100) + 1) {
+    std::fill(status, status + n, (uint8_t)0);  // nothing was tracked
+    return -1;
+  }
+  LkTrace tr{n, trace_iters, t_iters, t_exit, t_delta, t_inext, t_bmax, t_A, t_sat};
+  const size_t slots = (size_t)n * kLkTraceLevels;
+  std::fill(t_iters, t_iters + slots, 0);
+  std::fill(t_exit, t_exit + slots, (int32_t)kLkExitNone);
+  std::fill(t_delta, t_delta + slots * trace_iters * 2, 0.f);
+  std::fill(t_inext, t_inext + slots * trace_iters * 2, 0);
+  std::fill(t_bmax, t_bmax + slots * 2, 0.);
+  std::fill(t_A, t_A + slots * 3, 0.f);
+  std::fill(t_sat, t_sat + slots * trace_iters, 2.f);
+  g_lk_trace = &tr;
+  calc_lk(prev, next, w, h, prev_pts, next_pts, status, n, win, max_level, max_count, eps, flags, accum);
+  g_lk_trace = nullptr;
+  return 0;
+}
 void oracle_lk(const uint8_t* prev, const uint8_t* next, int w, int h, const float* prev_pts,
                float* next_pts, uint8_t* status, int n, int win, int max_level, int max_count,
                double eps, int flags, int accum) {

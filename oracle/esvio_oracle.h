@@ -103,6 +103,23 @@ int oracle_pyr_levels(int w, int h, int win, int max_level);
 void oracle_lk(const uint8_t* prev, const uint8_t* next, int w, int h, const float* prev_pts,
                float* next_pts, uint8_t* status, int n, int win, int max_level, int max_count,
                double eps, int flags, int accum);
+/* oracle_lk with a trace tap: the same arguments, the same next_pts and status, and per (point, level) — level stride 4,
+ * exit -1 for a level the pyramid does not have — what the tracker did there.  trace_iters >= clamp(max_count, 0, 100) + 1
+ * is the per-iteration arrays' slot count.
+ *   t_iters [n][4]      iterations that computed a delta
+ *   t_exit  [n][4]      0 window_out_at_start, 1 eig, 2 converged, 3 oscillation, 4 count, 5 outside
+ *   t_delta [n][4][trace_iters][2]  deltaX, deltaY
+ *   t_inext [n][4][trace_iters][2]  inextX, inextY (of the iteration that found the window outside too)
+ *   t_bmax  [n][4][2]   largest |running b1|, |running b2| over the level's iterations, exact, before FLT_SCALE
+ *   t_A     [n][4][3]   A11, A12, A22 (scaled)
+ *   t_sat   [n][4][trace_iters]  position (0..1) along its chain at which the first float-order chain of the b sums
+ *                       reached 2^24 in magnitude; 2 if none did; -1 if (accum 2 / 4) the chains as the trace lays
+ *                       them out, added in float, do not give the level's own b1, b2
+ * Returns 0; -1 (status all 0, nothing else written) for win > 64, max_level > 3 or too small a trace_iters. */
+int oracle_lk_trace(const uint8_t* prev, const uint8_t* next, int w, int h, const float* prev_pts, float* next_pts,
+                    uint8_t* status, int n, int win, int max_level, int max_count, double eps, int flags, int accum,
+                    int trace_iters, int32_t* t_iters, int32_t* t_exit, float* t_delta, int32_t* t_inext,
+                    double* t_bmax, float* t_A, float* t_sat);
 
 /* cv::createCLAHE()->apply (clip 40, 8x8 tiles) and cv::normalize(.,0,255,NORM_MINMAX) on u8
  * (feature_tracker.cpp:377-381) */

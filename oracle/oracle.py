@@ -102,6 +102,8 @@ def lib():
         L.oracle_pyr_levels.restype = i
         L.oracle_pyr_levels.argtypes = [i, i, i, i]
         L.oracle_lk.argtypes = [vp, vp, i, i, vp, vp, vp, i, i, i, i, d, i, i]
+        L.oracle_lk_trace.restype = i
+        L.oracle_lk_trace.argtypes = [vp, vp, i, i, vp, vp, vp, i, i, i, i, d, i, i, i, vp, vp, vp, vp, vp, vp, vp]
         L.oracle_lift_projective.argtypes = [C.POINTER(Camera), d, d, vp]
         L.oracle_clahe.argtypes = [vp, i, i, vp]
         L.oracle_normalize_minmax.argtypes = [vp, sz]
@@ -289,6 +291,52 @@ def lk(prev, nxt, prev_pts, next_pts=None, win=21, max_level=3, max_count=30, ep
     lib().oracle_lk(_p(prev), _p(nxt), w, h, _p(prev_pts), _p(next_pts), _p(status), n, win,
                     max_level, max_count, eps, flags, accum)
     return next_pts, status
+
+
+LK_EXITS = ("window_out_at_start", "eig", "converged", "oscillation", "count", "outside")
+LK_EXIT = {name: k for k, name in enumerate(LK_EXITS)}
+
+
+class LkTrace:
+    """what oracle.lk did per (point, level): iters / exit [n, 4] (exit -1: no such level; see LK_EXITS), delta
+    [n, 4, slots, 2] float32, inext [n, 4, slots, 2] int32 (the slot after the last delta holds the window that was found
+    outside, where that is the exit), bmax [n, 4, 2] (largest |running b| before the 2^-20 scale), A [n, 4, 3]
+    (A11, A12, A22), sat [n, 4, slots] (how far along its chain a float-order b chain reached 2^24; 2: never; -1: the
+    trace's layout of the chains does not reproduce the float-order b of that iteration)"""
+
+    def exit_name(self, pt, level):
+        e = int(self.exit[pt, level])
+        return "none" if e < 0 else LK_EXITS[e]
+
+
+def lk_trace(prev, nxt, prev_pts, next_pts=None, win=21, max_level=3, max_count=30, eps=0.01, flags=0,
+             accum=1):
+    """lk() with the trace tap -> (next_pts, status, LkTrace); next_pts and status are lk()'s"""
+    prev = np.ascontiguousarray(prev, np.uint8)
+    nxt = np.ascontiguousarray(nxt, np.uint8)
+    h, w = prev.shape
+    prev_pts = np.ascontiguousarray(prev_pts, np.float32).reshape(-1, 2)
+    n = prev_pts.shape[0]
+    if next_pts is None:
+        next_pts = np.zeros((n, 2), np.float32)
+    else:
+        next_pts = np.array(next_pts, np.float32).reshape(-1, 2).copy()
+    status = np.zeros(n, np.uint8)
+    slots = min(max(int(max_count), 0), 100) + 1
+    t = LkTrace()
+    t.iters = np.zeros((n, 4), np.int32)
+    t.exit = np.full((n, 4), -1, np.int32)
+    t.delta = np.zeros((n, 4, slots, 2), np.float32)
+    t.inext = np.zeros((n, 4, slots, 2), np.int32)
+    t.bmax = np.zeros((n, 4, 2), np.float64)
+    t.A = np.zeros((n, 4, 3), np.float32)
+    t.sat = np.full((n, 4, slots), 2, np.float32)
+    rc = lib().oracle_lk_trace(_p(prev), _p(nxt), w, h, _p(prev_pts), _p(next_pts), _p(status), n, win, max_level,
+                               max_count, eps, flags, accum, slots, _p(t.iters), _p(t.exit), _p(t.delta), _p(t.inext),
+                               _p(t.bmax), _p(t.A), _p(t.sat))
+    if rc != 0:
+        raise ValueError("oracle_lk_trace: win %d / max_level %d cannot be traced" % (win, max_level))
+    return next_pts, status, t
 
 
 def median_blur(img, ksize):
