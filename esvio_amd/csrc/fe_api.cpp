@@ -1206,6 +1206,92 @@ int esvio_fe_fast_corners(esvio_fe_handle c, int cam, const uint8_t* img, int sp
   return fast_run(c, src, stride, arc, barrier, nonmax != 0, out_xy, out_score, capacity, n_out, n_detected);
 }
 
+// FAST as trackEvent's detector (include/esvio_fe.h)
+int esvio_fe_set_detector(esvio_fe_handle c, int detector, int fast_barrier) {
+  if (!c) return ESVIO_FE_EINVAL;
+  if (detector != ESVIO_FE_DETECT_ARC && detector != ESVIO_FE_DETECT_FAST)
+    return fail(c, ESVIO_FE_EINVAL, "set_detector: detector must be ESVIO_FE_DETECT_ARC or ESVIO_FE_DETECT_FAST (got %d)", detector);
+  if (detector == ESVIO_FE_DETECT_FAST && (fast_barrier < 0 || fast_barrier > 255))
+    return fail(c, ESVIO_FE_EINVAL, "set_detector: fast_barrier must be in 0..255 (got %d)", fast_barrier);
+  if (!c->inflight.empty() || !c->announced.empty())
+    return fail(c, ESVIO_FE_EINVAL, "esvio_fe_set_detector while batches are announced");
+  HIPCHK(c, hipSetDevice(c->dev));
+  // (the launch thread reads the setting, and growing a candidate set frees it: nothing may be in flight)
+  if (int rc = launcher_drain(c)) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream2));
+  HIPCHK(c, hipStreamSynchronize(c->stream3));
+  HIPCHK(c, hipStreamSynchronize(c->stream4));
+  if (c->stream6) HIPCHK(c, hipStreamSynchronize(c->stream6));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (detector == ESVIO_FE_DETECT_FAST) {
+    if (int rc = ensure_fast_detector(c)) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->fast_barrier = fast_barrier;
+  }
+  c->detector = detector;
+  return 0;
+}
+
+int esvio_fe_features_to_track_fast(esvio_fe_handle c, const uint8_t* img, int space, int barrier, int max_corners,
+                                    const uint8_t* mask, float* out_xy, int32_t* out_score, int32_t* n_out,
+                                    int32_t* n_candidates) {
+  if (!c || !n_out) return ESVIO_FE_EINVAL;
+  *n_out = 0;
+  if (n_candidates) *n_candidates = 0;
+  if (barrier < 0 || barrier > 255)
+    return fail(c, ESVIO_FE_EINVAL, "features_to_track_fast: barrier must be in 0..255 (got %d)", barrier);
+  if (img && space != ESVIO_FE_HOST && space != ESVIO_FE_DEVICE)
+    return fail(c, ESVIO_FE_EINVAL, "features_to_track_fast: bad memory space");
+  if (max_corners > c->cfg.max_cnt) return fail(c, ESVIO_FE_EINVAL, "max_corners > max_cnt");
+  if (max_corners > 0 && !out_xy) return ESVIO_FE_EINVAL;
+  HIPCHK(c, hipSetDevice(c->dev));
+  if (int rc = ensure_fast_tap(c)) return rc;
+  const uint8_t* src = img;
+  int stride = c->W;
+  if (!img) {  // (as esvio_fe_fast_corners: the main stream is behind whatever rendered the plane)
+    const PyrDesc& d = raw_ts_desc(c, 0);
+    src = px00(d);
+    stride = d.stride[0];
+  } else if (space == ESVIO_FE_HOST) {
+    HIPCHK(c, hipMemcpyAsync(c->d_fast_tap_img, img, (size_t)c->W * c->H, hipMemcpyHostToDevice, cur_stream(c)));
+    src = c->d_fast_tap_img;
+  }
+  const esvio_fe_ctx::FastCand& fc = c->fastc[kRightSlots];
+  if (int rc = fast_cand_pass(c, src, stride, barrier, c->fast_tap, fc, n_candidates != nullptr)) return rc;
+  const ResView& pin = c->pin[0];
+  if (max_corners > 0) {
+    host::BitMask bm;
+    bm.reset(c->W, c->H);
+    if (mask) bm.from_bytes(mask);
+    std::memcpy(pin.mask, bm.bits.data(), bm.bits.size() * 4);
+    HIPCHK(c, hipMemcpyAsync(c->d_mask_bits, pin.mask, bm.bits.size() * 4, hipMemcpyHostToDevice, cur_stream(c)));
+    // the selection of esvio_fe_features_to_track over the tap's own set; out_idx: the sort keys, score in bits 8..15
+    SelectArgs sa = make_select_args(c, 0, max_corners, c->d_ptsD, 0, c->d_sel_idx);
+    sa.comp_xy = c->fast_tap.comp_xy;
+    sa.comp_idx = c->fast_tap.comp_idx;
+    sa.total = c->fast_tap.total;
+    sa.init_bits = c->d_mask_bits;
+    launch_select_args(c, sa);
+    HIPCHK(c, hipMemcpyAsync(pin.counts, c->dres.counts, 8, hipMemcpyDeviceToHost, cur_stream(c)));
+  }
+  uint32_t n_cand = 0;
+  if (n_candidates) HIPCHK(c, hipMemcpyAsync(&n_cand, fc.tot, 4, hipMemcpyDeviceToHost, cur_stream(c)));
+  HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  if (int rc = lookback_expired(c)) return rc;
+  const int k = max_corners > 0 ? pin.counts[0] : 0;
+  if (k > 0) {
+    HIPCHK(c, hipMemcpy(out_xy, c->d_ptsD, (size_t)k * 8, hipMemcpyDeviceToHost));
+    if (out_score) {
+      HIPCHK(c, hipMemcpy(out_score, c->d_sel_idx, (size_t)k * 4, hipMemcpyDeviceToHost));
+      for (int i = 0; i < k; i++) out_score[i] = (out_score[i] >> 8) & 255;
+    }
+  }
+  *n_out = k;
+  if (n_candidates) *n_candidates = (int32_t)n_cand;
+  if (c->prof_on) resolve_profile(c);
+  return 0;
+}
+
 int esvio_fe_track_image(esvio_fe_handle c, double cur_time, const uint8_t* img_left,
                          const uint8_t* img_right, int pub_this_frame, esvio_fe_tracks* out) {
   if (!c || !img_left) return ESVIO_FE_EINVAL;

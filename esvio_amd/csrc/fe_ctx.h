@@ -439,6 +439,21 @@ struct esvio_fe_ctx {
   Event ev_cvt_side[2][4];
   bool cvt_side_rec[2] = {false, false};
   int cvt_pair = 0;
+
+  // ---- esvio_fe_set_detector: where trackEvent's new corners come from.  ESVIO_FE_DETECT_FAST: a FAST pass over the
+  // frame's raw left time surface fills the frame's candidate set instead of the Arc* pass over its left events
+  // (run_fast_cand, fe_image.cpp).  A pass works in scratch of its own — the score map, the counts before the
+  // TS_LK_threshold test (+ their sum), the unsorted pairs and the sort's scratch words — one per candidate set, so
+  // that passes of batches in flight on different streams share nothing, none of it with esvio_fe_fast_corners; the
+  // last one, with a candidate set of its own and a device copy of a caller's host image, is the stage tap's
+  // (esvio_fe_features_to_track_fast).  Allocated by esvio_fe_set_detector(FAST) or the tap's first call.
+  int detector = ESVIO_FE_DETECT_ARC, fast_barrier = 0;
+  struct FastCand {
+    DevBuf<uint8_t> m;
+    DevBuf<uint32_t> det, tot, keys, vals, hist;
+  } fastc[kRightSlots + 1];
+  CandSet fast_tap;
+  DevBuf<uint8_t> d_fast_tap_img;
 };
 
 namespace esvio {

@@ -53,6 +53,7 @@ int fast_run(esvio_fe_ctx* c, const uint8_t* img, int stride, int arc, int barri
   a.cand_cnt = c->d_fast_cnt;
   a.det_cnt = c->d_fast_det;
   a.n_detected = (n_detected && nonmax) ? c->d_fast_tot + 1 : nullptr;  // (without non-max it is the total)
+  a.skip_center = -1;
   {
     ScopedKernel k(c, K_FAST_SCORE, 2 * P);  // the image read once, the map written
     launch_fast_score(s, a);
@@ -77,6 +78,91 @@ int fast_run(esvio_fe_ctx* c, const uint8_t* img, int stride, int arc, int barri
   if (n_detected) *n_detected = (int32_t)(nonmax ? tot[1] : tot[0]);
   if (c->prof_on) resolve_profile(c);
   return 0;
+}
+
+// ---- ESVIO_FE_DETECT_FAST: FAST as trackEvent's detector (include/esvio_fe.h: esvio_fe_set_detector)
+// The survivors of a 3x3 non-max with ">=" are never 8-neighbours of each other: one per 2 x 2 pixels at most.
+static uint32_t fast_cand_max(const esvio_fe_ctx* c) { return (uint32_t)((c->W + 1) / 2) * (uint32_t)((c->H + 1) / 2); }
+
+static int fast_scratch_alloc(esvio_fe_ctx* c, esvio_fe_ctx::FastCand& f) {
+  if (f.hist) return 0;  // (the last one: "all of them")
+  const size_t P = (size_t)c->W * c->H;
+  const size_t n_max = fast_cand_max(c);
+  if (int rc = f.m.alloc(c, P)) return rc;
+  if (int rc = f.det.alloc(c, (P + kArcBlock - 1) / kArcBlock)) return rc;
+  if (int rc = f.tot.alloc(c, 1)) return rc;
+  if (int rc = f.keys.alloc(c, n_max)) return rc;
+  if (int rc = f.vals.alloc(c, n_max)) return rc;
+  return f.hist.alloc(c, sort_scratch_words(n_max));
+}
+
+// the stage tap's: its scratch, its candidate set (one entry per pixel), the device copy of a caller's host image
+int ensure_fast_tap(esvio_fe_ctx* c) {
+  if (c->fast_tap.cap) return 0;
+  const size_t P = (size_t)c->W * c->H;
+  if (int rc = fast_scratch_alloc(c, c->fastc[kRightSlots])) return rc;
+  if (int rc = c->d_fast_tap_img.alloc(c, P)) return rc;
+  return cand_set_alloc(c, c->fast_tap, (P + kArcBlock - 1) / kArcBlock * kArcBlock);
+}
+
+// ... and the tracker's: the per-block lists of a pass are its candidate set's own (cand[set].xy / idx / cnt), one
+// entry per pixel.  (Growing a set frees it: the caller has made sure that nothing is in flight.)
+int ensure_fast_detector(esvio_fe_ctx* c) {
+  for (int k = 0; k < kRightSlots; k++) {
+    if (int rc = ensure_cand_capacity(c, k, (size_t)c->W * c->H)) return rc;
+    if (int rc = fast_scratch_alloc(c, c->fastc[k])) return rc;
+  }
+  return ensure_fast_tap(c);
+}
+
+int fast_cand_pass(esvio_fe_ctx* c, const uint8_t* img, int stride, int barrier, const esvio_fe_ctx::CandSet& cs,
+                   const esvio_fe_ctx::FastCand& fc, bool want_count) {
+  const size_t P = (size_t)c->W * c->H;
+  const uint32_t nblk = (uint32_t)((P + kArcBlock - 1) / kArcBlock);
+  const uint32_t n_max = fast_cand_max(c);
+  const double thr = c->cfg.ts_lk_threshold;
+  hipStream_t s = cur_stream(c);
+  FastArgs a{};
+  a.img = img;
+  a.stride = stride;
+  a.W = c->W;
+  a.H = c->H;
+  a.arc = 10;
+  a.barrier = barrier;
+  a.nonmax = 1;
+  a.lds = c->fast_lds ? 1 : 0;
+  a.m = fc.m;
+  a.cand_xy = cs.xy;
+  a.cand_score = cs.idx;
+  a.cand_cnt = cs.cnt;
+  a.det_cnt = fc.det;
+  a.n_detected = want_count ? fc.tot.p : nullptr;
+  a.skip_center = thr >= 0 && thr < 256 ? (int)(uint8_t)thr : 256;  // (a byte that no pixel has: nobody is left out)
+  {
+    ScopedKernel k(c, K_FAST_SCORE, 2 * P);
+    launch_fast_score(s, a);
+  }
+  {
+    ScopedKernel k(c, K_FAST_COLLECT, P);
+    launch_fast_collect(s, a);
+  }
+  {
+    ScopedKernel k(c, K_COMPACT, 0);
+    launch_compact(s, cs.xy, cs.idx, cs.cnt, nblk, cs.comp_xy, cs.comp_idx, cs.total, cs.grp);
+  }
+  // raster order -> by score, descending: keys + one stable 8-bit pass, booked together as one k_radix_pass entry.
+  // The count stays on the device (cs.total): both launches are sized for n_max.  The pass writes the set's own
+  // lists: comp_xy = the positions, comp_idx = the keys (score in bits 8..15), which the selection hands through.
+  const SortScratch sc = sort_scratch(fc.hist);
+  ScopedKernel k(c, K_RADIX_PASS, 0);
+  HIPCHK(c, hipMemsetAsync(fc.hist, 0, (size_t)sc.head_words * 4, s));
+  launch_fast_keys(s, cs.comp_xy, cs.comp_idx, cs.total, n_max, fc.keys, fc.vals, sc.ghist, sc.lookback);
+  radix_sort_pairs(c, SortBufs{{fc.keys, cs.comp_idx}, {fc.vals, cs.comp_xy}, fc.hist, cs.total}, n_max, 1, 8, false);
+  return 0;
+}
+
+int run_fast_cand(esvio_fe_ctx* c, const PyrDesc& ts, int set) {
+  return fast_cand_pass(c, px00(ts), ts.stride[0], c->fast_barrier, c->cand[set], c->fastc[set], false);
 }
 
 // cv::goodFeaturesToTrack on the level-0 image of pyramid `d` (padded, so no border arithmetic);

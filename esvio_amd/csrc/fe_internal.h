@@ -37,6 +37,15 @@ int sae_update(esvio_fe_ctx* c, const EventRec* evL, uint32_t nL, const EventRec
                const McParams* mc = nullptr, double2* L2 = nullptr, double2* S2 = nullptr, int arc_set = -1,
                bool* arc_marked = nullptr);
 int radix_sort_pairs(esvio_fe_ctx* c, uint32_t n, int passes, int bits, bool booked = true);
+// ... of other buffers than the handle's keys[] / vals[] / hist; n_dev (optional): the count is *n_dev, read on the
+// device, and n its upper bound (launch_radix_pass)
+struct SortBufs {
+  uint32_t *keys[2], *vals[2];
+  uint32_t* scratch;  // sort_scratch() layout
+  const uint32_t* n_dev;
+};
+int radix_sort_pairs(esvio_fe_ctx* c, const SortBufs& b, uint32_t n, int passes, int bits, bool booked);
+int cand_set_alloc(esvio_fe_ctx* c, esvio_fe_ctx::CandSet& s, size_t cap);  // the seven arrays of a candidate set
 int stage_events(esvio_fe_ctx* c, const esvio_fe_event* left, size_t nL, const esvio_fe_event* right,
                  size_t nR, int space, const EventRec** dL, const EventRec** dR, int lane = -1);
 void render_ts(esvio_fe_ctx* c, double t_sync, uint8_t* dst0, uint8_t* dst1, int ncam, const double2* S2);
@@ -85,6 +94,11 @@ void run_select(esvio_fe_ctx* c, int set, int max_corners, float2* out_pts, int 
                 const float2* stamp_pts = nullptr, int n_stamp = 0);
 void run_arc(esvio_fe_ctx* c, const EventRec* ev, uint32_t n, const PyrDesc* ts, bool use_mask,
              bool want_flags, bool want_cand, int set, bool marked = false);
+// a frame's candidates into set `set`, by the handle's detector: the Arc* pass over the batch's left events and its
+// ordered compaction, or the FAST pass over `ts`, the frame's raw left time surface
+int run_detect(esvio_fe_ctx* c, const EventRec* ev, uint32_t n, const PyrDesc& ts, int set, bool marked);
+// candidates set `set` must have room for before a frame with n left events is detected in it
+inline size_t detect_cand_need(const esvio_fe_ctx* c, size_t n) { return c->detector == ESVIO_FE_DETECT_FAST ? (size_t)c->P : n; }
 hipError_t sync_main(esvio_fe_ctx* c);
 hipError_t sync_event(hipEvent_t ev);
 
@@ -137,6 +151,16 @@ int gftt_run(esvio_fe_ctx* c, const PyrDesc& d, int max_corners, double quality,
 // the current stream; synchronises it.  Up to `capacity` corners in raster order go to out_xy / out_score (host).
 int fast_run(esvio_fe_ctx* c, const uint8_t* img, int stride, int arc, int barrier, bool nonmax, int16_t* out_xy,
              int32_t* out_score, int32_t capacity, int32_t* n_out, int32_t* n_detected);
+// ESVIO_FE_DETECT_FAST (esvio_fe_ctx::fastc): everything the candidate passes and the stage tap need, allocated once;
+// what the stage tap alone needs
+int ensure_fast_detector(esvio_fe_ctx* c);
+int ensure_fast_tap(esvio_fe_ctx* c);
+// FAST-10 + score_10 + nonmax_3x3 of the image at `img` -> candidate set `cs`, ordered by score (descending, equal
+// scores in raster order), corners whose byte is (uint8_t)ts_lk_threshold left out, in the scratch `fc`, on the current
+// stream; no host synchronisation.  want_count: fc.tot[0] = the survivors of the non-max, those left out included
+int fast_cand_pass(esvio_fe_ctx* c, const uint8_t* img, int stride, int barrier, const esvio_fe_ctx::CandSet& cs,
+                   const esvio_fe_ctx::FastCand& fc, bool want_count);
+int run_fast_cand(esvio_fe_ctx* c, const PyrDesc& ts, int set);  // ... of a frame's raw left time surface -> cand[set]
 int track_image_impl(esvio_fe_ctx* c, double cur_time, const uint8_t* img_left, const uint8_t* img_right,
                      bool PUB_THIS_FRAME);
 

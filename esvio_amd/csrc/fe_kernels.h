@@ -113,10 +113,12 @@ void launch_sae_keys(hipStream_t s, const EventRec* evL, uint32_t nL, const Even
                      uint32_t* ghist, uint32_t* lookback, uint32_t lookback_words,
                      const struct McParams* mc /* NULL: no motion compensation */);
 // one stable LSD pass on digit (key >> shift) & ((1<<bits)-1) with decoupled look-back
+// n_dev (optional): the number of pairs is *n_dev, known on the device only, and n its upper bound — the launch is
+// sized for n, a block whose tile lies behind *n_dev ends at once
 void launch_radix_pass(hipStream_t s, const uint32_t* keys_in, const uint32_t* vals_in, uint32_t n,
                        int shift, int bits, const uint32_t* ghist, uint32_t* lookback,
                        uint32_t* ticket, uint32_t* keys_out, uint32_t* vals_out, int* err,
-                       uint32_t spin_limit = kSpinLookback);
+                       uint32_t spin_limit = kSpinLookback, const uint32_t* n_dev = nullptr);
 // walk every same-pixel segment of the sorted keys in stream order applying the SAE rule
 // (event_detector.cc:149-166). L2/S2: double2 per (cam,pixel): {L[0],L[1]} and {S[0],S[1]}.
 void launch_sae_apply(hipStream_t s, const uint32_t* keys, const uint32_t* vals, uint32_t n,
@@ -477,9 +479,20 @@ struct FastArgs {
   uint32_t* cand_cnt;   // [nblk]
   uint32_t* det_cnt;    // [nblk] corners before non-max
   uint32_t* n_detected; // [1] their sum (k_fast_sum), or NULL: not wanted
+  // >= 0 (the candidate pass of ESVIO_FE_DETECT_FAST, nonmax only): a survivor of the non-max whose centre byte has
+  // this value is left out of the lists (the TS_LK_threshold test of feature_tracker.cpp:26); det_cnt / n_detected
+  // then count the survivors, the left-out ones included, instead of the corners before non-max.  -1: nobody is
+  int skip_center;
 };
 void launch_fast_score(hipStream_t s, const FastArgs& a);
 void launch_fast_collect(hipStream_t s, const FastArgs& a);
+// The FAST candidate pass orders its corners by score, descending, equal scores in raster order: k_compact's raster-
+// ordered list of *total (xy, score) entries -> the pairs of ONE stable 8-bit radix pass.  Scores are 0..254, so
+// keys[i] = (254 - score) | score << 8 (the pass looks at the low byte, the score rides along), vals[i] = xy; the
+// low bytes' histogram is added to ghist[256] (zeroed by the caller) and the look-back words of the tiles that pass
+// will use are cleared.  *total is read on the device: the launch is sized for n_max.
+void launch_fast_keys(hipStream_t s, const uint32_t* comp_xy, const uint32_t* comp_score, const uint32_t* total,
+                      uint32_t n_max, uint32_t* keys, uint32_t* vals, uint32_t* ghist, uint32_t* lookback);
 
 // ---- caller-layout event arrays -> event records (esvio_fe_convert_events) -------------------
 // Where the four fields of event i lie: base + i * stride, any alignment (esvio_fe_event_fields with the pointers

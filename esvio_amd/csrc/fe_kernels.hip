@@ -165,7 +165,8 @@ __global__ __launch_bounds__(256) void k_radix_pass(const uint32_t* __restrict__
                                                     uint32_t* __restrict__ ticket,
                                                     uint32_t* __restrict__ keys_out,
                                                     uint32_t* __restrict__ vals_out,
-                                                    int* __restrict__ err, uint32_t spin_limit) {
+                                                    int* __restrict__ err, uint32_t spin_limit,
+                                                    const uint32_t* __restrict__ n_dev) {
   __shared__ uint32_t wave_cnt_s[4][1 << kRadixMaxBits];
   __shared__ uint32_t bin_base[1 << kRadixMaxBits];
   __shared__ uint32_t s_tile;
@@ -180,6 +181,12 @@ __global__ __launch_bounds__(256) void k_radix_pass(const uint32_t* __restrict__
   if ((int)threadIdx.x < bins) bin_base[threadIdx.x] = ghist[threadIdx.x];
   __syncthreads();
   const uint32_t tile = s_tile;
+  // (a count known on the device only: the launch is sized for its bound; tickets go to the tiles in order, so the
+  // tiles that hold pairs are all taken, and nobody looks back at a later one)
+  if (n_dev) {
+    n = min(n, *n_dev);
+    if ((unsigned long long)tile * kRadixTile >= n) return;
+  }
 
   constexpr int ROUNDS = kRadixTile / 256;  // 8 rounds of 64 consecutive keys per wave
   uint32_t key[ROUNDS], val[ROUNDS], rank[ROUNDS];
@@ -276,9 +283,11 @@ __global__ __launch_bounds__(256) void k_radix_pass(const uint32_t* __restrict__
 
 void launch_radix_pass(hipStream_t s, const uint32_t* keys_in, const uint32_t* vals_in, uint32_t n,
                        int shift, int bits, const uint32_t* ghist, uint32_t* lookback,
-                       uint32_t* ticket, uint32_t* keys_out, uint32_t* vals_out, int* err, uint32_t spin_limit) {
+                       uint32_t* ticket, uint32_t* keys_out, uint32_t* vals_out, int* err, uint32_t spin_limit,
+                       const uint32_t* n_dev) {
+  if (!n) return;
   launch_k(k_radix_pass, dim3(radix_blocks(n)), dim3(256), 0, s, keys_in, vals_in, n, shift,
-                     bits, ghist, lookback, ticket, keys_out, vals_out, err, spin_limit);
+                     bits, ghist, lookback, ticket, keys_out, vals_out, err, spin_limit, n_dev);
 }
 
 // ============================================================================ SAE apply
@@ -3657,16 +3666,21 @@ __global__ __launch_bounds__(kArcBlock) void k_fast_collect(FastArgs a) {
     nmax = max(nmax, max(max((uint32_t)q[-W - 1], (uint32_t)q[-W + 1]), max((uint32_t)q[W - 1], (uint32_t)q[W + 1])));
     take = nmax < v;  // an equal neighbour suppresses, as the library's `scores[j] >= score`
   }
+  const uint32_t y = i / (uint32_t)W, x = i - y * (uint32_t)W;
+  unsigned long long counted = det;
+  if (a.skip_center >= 0) {  // (FastArgs::skip_center: out of the lists, still counted)
+    counted = __ballot(take);
+    if (take) take = (int)a.img[(size_t)y * a.stride + x] != a.skip_center;
+  }
   const unsigned long long mb = __ballot(take);
   if (lane == 0) {
     wave_cnt[wave] = __popcll(mb);
-    wave_det[wave] = __popcll(det);
+    wave_det[wave] = __popcll(counted);
   }
   __syncthreads();
   uint32_t base = 0;
   for (int w = 0; w < wave; w++) base += wave_cnt[w];
   if (take) {
-    const uint32_t y = i / (uint32_t)W, x = i - y * (uint32_t)W;
     const uint32_t pos = base + __popcll(mb & ((1ull << lane) - 1ull));
     a.cand_xy[(size_t)blockIdx.x * kArcBlock + pos] = x | (y << 16);
     a.cand_score[(size_t)blockIdx.x * kArcBlock + pos] = v - 1;
@@ -3700,6 +3714,39 @@ void launch_fast_collect(hipStream_t s, const FastArgs& a) {
   const uint32_t nblk = ((uint32_t)a.W * a.H + kArcBlock - 1) / kArcBlock;
   launch_k(k_fast_collect, dim3(nblk), dim3(kArcBlock), 0, s, a);
   if (a.n_detected) launch_k(k_fast_sum, dim3(1), dim3(256), 0, s, (const uint32_t*)a.det_cnt, nblk, a.n_detected);
+}
+
+// fe_kernels.h: launch_fast_keys.  A streaming pass over a few thousand entries at most (a quarter of the pixels at
+// the very worst): one entry per lane and round, the histogram in LDS, one global atomic per digit and block.
+__global__ __launch_bounds__(256) void k_fast_keys(const uint32_t* __restrict__ comp_xy,
+                                                   const uint32_t* __restrict__ comp_score,
+                                                   const uint32_t* __restrict__ total, uint32_t n_max,
+                                                   uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
+                                                   uint32_t* __restrict__ ghist, uint32_t* __restrict__ lookback) {
+  __shared__ uint32_t h[256];
+  const uint32_t n = min(*total, n_max);
+  const uint32_t first = blockIdx.x * 256u + threadIdx.x, step = gridDim.x * 256u;
+  const uint32_t lookback_words = ((n + kRadixTile - 1) / kRadixTile) << 8;
+  for (uint32_t i = first; i < lookback_words; i += step) lookback[i] = 0;
+  if (blockIdx.x * 256u >= n) return;  // (the whole block: nothing of the list is its)
+  h[threadIdx.x] = 0;
+  __syncthreads();
+  for (uint32_t i = first; i < n; i += step) {
+    const uint32_t score = min(comp_score[i], 254u);
+    const uint32_t key = (254u - score) | (score << 8);
+    keys[i] = key;
+    vals[i] = comp_xy[i];
+    atomicAdd(&h[key & 255u], 1u);
+  }
+  __syncthreads();
+  if (h[threadIdx.x]) atomicAdd(&ghist[threadIdx.x], h[threadIdx.x]);
+}
+
+void launch_fast_keys(hipStream_t s, const uint32_t* comp_xy, const uint32_t* comp_score, const uint32_t* total,
+                      uint32_t n_max, uint32_t* keys, uint32_t* vals, uint32_t* ghist, uint32_t* lookback) {
+  uint32_t grid = (n_max + 1023) / 1024;
+  grid = grid < 1 ? 1 : (grid > 64 ? 64 : grid);
+  launch_k(k_fast_keys, dim3(grid), dim3(256), 0, s, comp_xy, comp_score, total, n_max, keys, vals, ghist, lookback);
 }
 
 // ============================================================================ event layouts

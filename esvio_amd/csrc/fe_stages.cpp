@@ -42,8 +42,7 @@ int ensure_sort_capacity(esvio_fe_ctx* c, size_t n) {
 }
 
 // the seven arrays of a candidate set share one capacity (cap: set once all of them are there)
-static int grow_cand_set(esvio_fe_ctx* c, int set, size_t cap) {
-  esvio_fe_ctx::CandSet& s = c->cand[set];
+int cand_set_alloc(esvio_fe_ctx* c, esvio_fe_ctx::CandSet& s, size_t cap) {
   s = esvio_fe_ctx::CandSet();
   if (int rc = s.xy.alloc(c, cap)) return rc;
   if (int rc = s.idx.alloc(c, cap)) return rc;
@@ -55,6 +54,7 @@ static int grow_cand_set(esvio_fe_ctx* c, int set, size_t cap) {
   s.cap = cap;
   return 0;
 }
+static int grow_cand_set(esvio_fe_ctx* c, int set, size_t cap) { return cand_set_alloc(c, c->cand[set], cap); }
 
 int ensure_cand_capacity(esvio_fe_ctx* c, int set, size_t n) {
   if (n <= c->cand[set].cap) return 0;
@@ -209,15 +209,20 @@ int sae_update_tiled(esvio_fe_ctx* c, const EventRec* evL, uint32_t nL, const Ev
 // `passes` stable passes of `bits` bits each; returns which of keys[] / vals[] holds the result.  `booked`: the passes
 // are booked as K_RADIX_PASS (goodFeaturesToTrack's stages are not in the kernel statistics).
 int radix_sort_pairs(esvio_fe_ctx* c, uint32_t n, int passes, int bits, bool booked) {
-  const SortScratch sc = sort_scratch(c->hist);
+  return radix_sort_pairs(c, SortBufs{{c->keys[0], c->keys[1]}, {c->vals[0], c->vals[1]}, c->hist, nullptr}, n, passes,
+                          bits, booked);
+}
+
+int radix_sort_pairs(esvio_fe_ctx* c, const SortBufs& b, uint32_t n, int passes, int bits, bool booked) {
+  const SortScratch sc = sort_scratch(b.scratch);
   const size_t pass_words = (size_t)radix_blocks(n) << bits;
   int cur = 0;
   for (int p = 0; p < passes; p++) {
     std::optional<ScopedKernel> k;
     if (booked) k.emplace(c, K_RADIX_PASS, (uint64_t)n * 16);
-    launch_radix_pass(cur_stream(c), c->keys[cur], c->vals[cur], n, p * bits, bits, sc.ghist + ((size_t)p << bits),
-                      sc.lookback + p * pass_words, sc.tickets + p, c->keys[cur ^ 1], c->vals[cur ^ 1],
-                      c->zpin[0].counts + 3, c->lim.lookback);
+    launch_radix_pass(cur_stream(c), b.keys[cur], b.vals[cur], n, p * bits, bits, sc.ghist + ((size_t)p << bits),
+                      sc.lookback + p * pass_words, sc.tickets + p, b.keys[cur ^ 1], b.vals[cur ^ 1],
+                      c->zpin[0].counts + 3, c->lim.lookback, b.n_dev);
     cur ^= 1;
   }
   return cur;
@@ -748,6 +753,13 @@ void run_arc(esvio_fe_ctx* c, const EventRec* ev, uint32_t n, const PyrDesc* ts,
     launch_dedup(cur_stream(c), a.cand_xy, a.cand_idx, a.cand_cnt, (n + kArcBlock - 1) / kArcBlock,
                  a.first_map, a.first_key, c->W);
   }
+}
+
+int run_detect(esvio_fe_ctx* c, const EventRec* ev, uint32_t n, const PyrDesc& ts, int set, bool marked) {
+  if (c->detector == ESVIO_FE_DETECT_FAST) return run_fast_cand(c, ts, set);
+  run_arc(c, ev, n, &ts, false, false, true, set, marked);
+  run_compact(c, n, set);
+  return 0;
 }
 
 // wait for the main stream with a short busy poll first: the two per-frame host syncs are on the

@@ -50,8 +50,9 @@ static int prefetch_issue(esvio_fe_ctx* c, const PrefetchJob& j) {
   bool arc_marked = false;
   McParams mcp;
   if (b.has_motion) mcp = make_mc_params(&b.motion);
+  // (the touched flags are Arc*'s: a FAST pass has no use for them)
   int rc = sae_update(c, dL, (uint32_t)b.nL, dR, (uint32_t)b.nR, b.has_motion ? &mcp : nullptr, nullptr, nullptr,
-                      b.pub && b.nL ? b.cand : -1, &arc_marked);
+                      b.pub && b.nL && c->detector == ESVIO_FE_DETECT_ARC ? b.cand : -1, &arc_marked);
   if (!rc) {
     build_lk_images(c, b.time, 3, b.slotL, b.slotR, b.raw);
     if (hipEventRecord(c->ev_lane_done[b.lane], c->stream2) != hipSuccess)
@@ -62,8 +63,7 @@ static int prefetch_issue(esvio_fe_ctx* c, const PrefetchJob& j) {
   if (rc) return rc;
   if (b.arc_done) {  // (decided with the bookkeeping: the PUB hint says the frame will publish)
     const PyrDesc& ts = c->cfg.equalize ? c->raw[b.raw][0].d : c->pyr[b.slotL].d;
-    run_arc(c, dL, (uint32_t)b.nL, &ts, false, false, true, b.cand, arc_marked);
-    run_compact(c, (uint32_t)b.nL, b.cand);
+    if (int rc2 = run_detect(c, dL, (uint32_t)b.nL, ts, b.cand, arc_marked)) return rc2;
     HIPCHK(c, hipEventRecord(c->ev_lane_arc[b.lane], c->stream2));
   }
   // (the last kernels on this stream that read the batch's events)
@@ -293,13 +293,13 @@ int prefetch_next(esvio_fe_ctx* c, bool wait_planes, bool must_take_first) {
     // be about to use them)
     const size_t n = b.nL + b.nR;
     const bool grows = (c->tiled ? n > c->d_part.cap || (b.has_motion && !c->d_warp) : n > c->sort_cap) ||
-                       (b.arc_done && b.nL > c->cand[b.cand].cap);
+                       (b.arc_done && detect_cand_need(c, b.nL) > c->cand[b.cand].cap);
     if ((grows || !async) && c->launcher)
       if ((rc = launcher_drain(c))) break;
     {
       StreamScope on_prefetch_stream(c->stream2);  // (a grown buffer's initialisation precedes its first use there)
       if (c->tiled ? (rc = ensure_part_capacity(c, n, b.has_motion)) : (rc = ensure_sort_capacity(c, n))) break;
-      if (b.arc_done && (rc = ensure_cand_capacity(c, b.cand, b.nL))) break;
+      if (b.arc_done && (rc = ensure_cand_capacity(c, b.cand, detect_cand_need(c, b.nL)))) break;
     }
     if (async) {
       if (!++c->gate_seq) c->gate_seq = 1;
@@ -677,7 +677,7 @@ struct TrackCall {
       // cv::Mat header swaps of :390-403,:585.  Left slots 0..2: {prev, cur, free}.
       if (split) {
         if (int rc = sae_update(c, dL, (uint32_t)nL, nullptr, 0, nullptr, nullptr, nullptr,
-                                PUB_THIS_FRAME ? c->cand_cur : -1, &arc_marked_main))
+                                arc_set_main(), &arc_marked_main))
           return rc;
         HIPCHK(c, hipEventRecord(c->ev_sae_left, c->stream));
         rotate_slots(c, false);
@@ -710,7 +710,7 @@ struct TrackCall {
         const McParams mc = make_mc_params(motion);
         if (int rc = sae_update(c, dL, (uint32_t)nL, dR, (uint32_t)nR, &mc)) return rc;
       } else if (int rc = sae_update(c, dL, (uint32_t)nL, dR, (uint32_t)nR, nullptr, nullptr, nullptr,
-                                     PUB_THIS_FRAME ? c->cand_cur : -1, &arc_marked_main)) {
+                                     arc_set_main(), &arc_marked_main)) {
         return rc;
       }
       // camera split: the right image was imported into slot_curR by esvio_fe_import_image
@@ -736,6 +736,10 @@ struct TrackCall {
     return 0;
   }
 
+  // the candidate set the SAE update marks the touched (pixel, polarity) pairs for: a published frame's, if its
+  // candidates come from Arc*
+  int arc_set_main() const { return PUB_THIS_FRAME && c->detector == ESVIO_FE_DETECT_ARC ? c->cand_cur : -1; }
+
   const Inflight* next_batch() {
     if (!have_next && had_announced) {
       if (!c->inflight.empty()) {
@@ -755,20 +759,19 @@ struct TrackCall {
     if (early_done) return 0;
     early_done = true;
     if (PUB_THIS_FRAME && !arc_done) {
-      if (int rc = ensure_arc_capacity(c, nL, c->cand_cur)) return rc;
+      if (c->detector == ESVIO_FE_DETECT_ARC)  // (a FAST handle's sets have had their size since esvio_fe_set_detector)
+        if (int rc = ensure_arc_capacity(c, nL, c->cand_cur)) return rc;
       const PyrDesc ts = raw_ts_desc(c, 0);
       if (plain) {
         // on the prefetch stream (idle in a plain call), behind the frame's images: it runs beside the
         // temporal LK instead of behind it, and the host's wait for that LK no longer includes it
         StreamScope on_side_stream(c->stream2);
         HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_imgs_ready, 0));
-        run_arc(c, dL, (uint32_t)nL, &ts, false, false, true, c->cand_cur, arc_marked_main);
-        run_compact(c, (uint32_t)nL, c->cand_cur);
+        if (int rc = run_detect(c, dL, (uint32_t)nL, ts, c->cand_cur, arc_marked_main)) return rc;
         HIPCHK(c, hipEventRecord(c->ev_arc_side, c->stream2));
         arc_side = true;
       } else {
-        run_arc(c, dL, (uint32_t)nL, &ts, false, false, true, c->cand_cur, arc_marked_main);
-        run_compact(c, (uint32_t)nL, c->cand_cur);
+        if (int rc = run_detect(c, dL, (uint32_t)nL, ts, c->cand_cur, arc_marked_main)) return rc;
       }
       arc_done = true;
       main_reads_planes = true;

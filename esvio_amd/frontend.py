@@ -95,12 +95,12 @@ ABI_SYMBOLS = [
     "esvio_fe_convert_events", "esvio_fe_create",
     "esvio_fe_create_sae", "esvio_fe_create_sae_stereo", "esvio_fe_create_sae_stereo_mc", "esvio_fe_destroy",
     "esvio_fe_exchange_begin", "esvio_fe_exchange_end", "esvio_fe_exchange_tracks", "esvio_fe_export_image",
-    "esvio_fe_fast_corners", "esvio_fe_features_to_track", "esvio_fe_find_fundamental_mat", "esvio_fe_finish", "esvio_fe_get_sae",
+    "esvio_fe_fast_corners", "esvio_fe_features_to_track", "esvio_fe_features_to_track_fast", "esvio_fe_find_fundamental_mat", "esvio_fe_finish", "esvio_fe_get_sae",
     "esvio_fe_get_time_surface", "esvio_fe_good_features_to_track", "esvio_fe_import_image", "esvio_fe_is_corner",
     "esvio_fe_last_error", "esvio_fe_mem_alloc", "esvio_fe_mem_free", "esvio_fe_mem_upload",
     "esvio_fe_pack_track_records", "esvio_fe_register_host_buffer", "esvio_fe_reserve", "esvio_fe_reset",
     "esvio_fe_sae_plane_doubles", "esvio_fe_sae_slice_apply", "esvio_fe_sae_slice_commit",
-    "esvio_fe_sae_slice_last", "esvio_fe_sae_to_time_surface", "esvio_fe_set_auto_exchange",
+    "esvio_fe_sae_slice_last", "esvio_fe_sae_to_time_surface", "esvio_fe_set_auto_exchange", "esvio_fe_set_detector",
     "esvio_fe_set_host_threads", "esvio_fe_set_launch_thread", "esvio_fe_set_lazy_new_stereo",
     "esvio_fe_set_next_batch", "esvio_fe_set_next_batch_mc", "esvio_fe_track_event", "esvio_fe_track_event_fields",
     "esvio_fe_track_event_mc",
@@ -203,6 +203,8 @@ def load_library(build_if_missing=True):
     L.esvio_fe_import_image.argtypes = [vp, i, vp, i]
     L.esvio_fe_fast_corners.argtypes = [vp, i, vp, i, i, i, i, vp, vp, C.c_int32, C.POINTER(C.c_int32),
                                         C.POINTER(C.c_int32)]
+    L.esvio_fe_set_detector.argtypes = [vp, i, i]
+    L.esvio_fe_features_to_track_fast.argtypes = [vp, vp, i, i, i, vp, vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.esvio_fe_convert_events.argtypes = [vp, C.POINTER(EventFieldsDesc), sz, i, vp, i, C.POINTER(C.c_uint64)]
     L.esvio_fe_track_event_fields.argtypes = [vp, d, C.POINTER(EventFieldsDesc), sz, C.POINTER(EventFieldsDesc), sz, i, i,
                                               C.POINTER(Tracks)]
@@ -279,6 +281,7 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+DETECT_ARC, DETECT_FAST = 0, 1  # esvio_fe_set_detector
 FAULT_TICKET, FAULT_LOOKBACK, FAULT_SPECULATIVE, FAULT_CHAINED, FAULT_LAZY_LATE = 1, 2, 4, 8, 16
 
 
@@ -691,6 +694,37 @@ class FeatureTracker:
         k = min(n.value, cap)
         out = (xy[:k].copy(), sc[:k].copy() if sc is not None else None)
         return out + ((n.value, nd.value),) if want_count else out
+
+    def set_detector(self, detector, barrier=20):
+        """where trackEvent takes a published frame's new corners from: DETECT_ARC (the reference, the default) or
+        DETECT_FAST — FAST-10 + score + non-max on the raw left time surface at `barrier`, ordered by score, then
+        the same greedy min_dist scan (include/esvio_fe.h).  Not while batches are announced; survives reset()."""
+        self._hd.check(self._hd.L.esvio_fe_set_detector(self._hd.h, int(detector), int(barrier)))
+
+    def features_to_track_fast(self, img=None, barrier=20, maxCorners=None, mask=None, want_count=False):
+        """the DETECT_FAST selection for one image (esvio_fe_features_to_track_fast): the current raw left time
+        surface (img None), a numpy (H,W) u8 image or a device image given as int pointer; mask: (H,W) u8,
+        255 = blocked -> (xy float32[n,2], score int32[n]) in the order of acceptance; want_count: also the number of
+        FAST corners after non-max, before any mask or threshold test"""
+        hd = self._hd
+        if img is None:
+            ptr, space, keep = None, HOST, None
+        elif isinstance(img, np.ndarray):
+            keep = np.ascontiguousarray(img, np.uint8)
+            if keep.shape != (self.cfg.height, self.cfg.width):
+                raise ValueError("image must be (height, width) of the handle")
+            ptr, space = _p(keep), HOST
+        else:
+            ptr, space, keep = C.c_void_p(int(img)), DEVICE, None
+        m = self.cfg.max_cnt if maxCorners is None else int(maxCorners)
+        xy = np.zeros((max(m, 1), 2), np.float32)
+        sc = np.zeros(max(m, 1), np.int32)
+        k, nc = C.c_int32(0), C.c_int32(0)
+        mk = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        hd.check(hd.L.esvio_fe_features_to_track_fast(hd.h, ptr, space, int(barrier), m, _p(mk), _p(xy), _p(sc),
+                                                      C.byref(k), C.byref(nc)))
+        out = (xy[:k.value].copy(), sc[:k.value].copy())
+        return out + (nc.value,) if want_count else out
 
     # ---- camera split (right camera on another GPU)
     def export_image(self, cam, dst=None):

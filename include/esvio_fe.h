@@ -336,6 +336,47 @@ int esvio_fe_fast_corners(esvio_fe_handle h, int cam, const uint8_t* img, int sp
                           int nonmax, int16_t* out_xy, int32_t* out_score, int32_t capacity,
                           int32_t* n_out, int32_t* n_detected);
 
+/* ---- FAST as trackEvent's detector --------------------------------------------------------- */
+/* Where esvio_fe_track_event (both overloads, esvio_fe_track_event_fields, announced batches) takes a published
+ * frame's NEW corners from.  The reference has one detector, Arc*, and no counterpart to the other: this text is
+ * its specification. */
+#define ESVIO_FE_DETECT_ARC  0   /* Event_FeaturesToTrack + isCorner: the reference, the default */
+#define ESVIO_FE_DETECT_FAST 1   /* FAST-10 + score_10 + nonmax_3x3 on the left time surface, score-ordered */
+/* ESVIO_FE_DETECT_FAST, for an image, a mask of blocked pixels and a budget max_corners:
+ *  1. C = the corners esvio_fe_fast_corners(arc 10, nonmax 1, barrier) returns for the image, with their
+ *     fast_corner_score_10.
+ *  2. C is ordered by score, descending; corners of equal score stay in raster order (y, then x, ascending).
+ *     (Raster order fed to a greedy scan would fill the budget from the top rows; cv::goodFeaturesToTrack orders by
+ *     response for the same reason.)
+ *  3. The scan of Event_FeaturesToTrack (feature_tracker.cpp:13-38) over that list, from a working copy of the mask:
+ *     a corner whose pixel is blocked in the working mask is skipped; so is one whose image byte equals
+ *     (uint8_t)ts_lk_threshold; any other is accepted as ((float)x, (float)y) and the filled cv::circle of radius
+ *     min_dist around it is blocked — the disc the Arc* selection stamps, not goodFeaturesToTrack's Euclidean
+ *     one; the scan stops at max_corners accepted corners.
+ * In trackEvent the image is the batch's raw left time surface (after median_blur_kernel_size, before CLAHE: the
+ * plane the TS_LK_threshold test reads and esvio_fe_get_time_surface returns), the mask is Event_setMask's and
+ * max_corners = max_cnt - kept points.  Everything else in the call — tracking, filters, ids, the stereo LK, lazy
+ * returns, the exchange — is what it is with Arc*, and so is every schedule: with a non-zero pub_hint an announced
+ * batch's FAST pass is prefetched as its Arc* pass would be.  esvio_fe_track_image ignores the setting.
+ *
+ * detector: one of the two above; fast_barrier: 0..255 (ignored for ESVIO_FE_DETECT_ARC).  ESVIO_FE_EINVAL for
+ * other values, and while batches are announced and not yet tracked (as esvio_fe_reserve).  The call waits for the
+ * handle's streams and, for ESVIO_FE_DETECT_FAST, allocates everything the FAST passes need (about 35 bytes per
+ * pixel, and room for one candidate per pixel in every candidate set): no later track call allocates for them.  The setting survives esvio_fe_reset. */
+int esvio_fe_set_detector(esvio_fe_handle h, int detector, int fast_barrier);
+/* The stage tap beside esvio_fe_features_to_track: steps 1-3 above for one image.
+ * img == NULL: the handle's current raw left time surface, read in place; otherwise width*height bytes of the
+ * handle's size in `space`, as in esvio_fe_fast_corners.  barrier: 0..255.  mask: width*height bytes on host,
+ * 255 = blocked, may be NULL.  max_corners <= max_cnt; <= 0 selects nothing.  Writes the accepted corners' (x,y)
+ * pairs to out_xy, (optionally) their scores to out_score, their number to *n_out and (optionally) the size of C —
+ * the survivors of the non-max before any mask or threshold test, esvio_fe_fast_corners' *n_out — to
+ * *n_candidates.  min_dist and ts_lk_threshold are the handle's.
+ * The call runs on the handle's main stream in scratch of its own, waits for its own result and touches nothing of
+ * the tracker: made between two track calls (announced batches or not) it changes no later result. */
+int esvio_fe_features_to_track_fast(esvio_fe_handle h, const uint8_t* img, int space, int barrier,
+                                    int max_corners, const uint8_t* mask, float* out_xy,
+                                    int32_t* out_score, int32_t* n_out, int32_t* n_candidates);
+
 /* ---- event layouts: caller-layout arrays -> event records, on the device ------------------ */
 /* Recordings (DSEC, MVSEC, VECtor, ECMD) and vendor SDKs deliver events as separate arrays (x[], y[], p[], t[] in
  * microseconds plus a file-wide offset) or as records with a 64-bit stamp, some of them packed; only a ROS host holds
