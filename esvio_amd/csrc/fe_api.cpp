@@ -630,7 +630,7 @@ int esvio_fe_features_to_track(esvio_fe_handle c, const esvio_fe_event* ev, size
                            cur_stream(c)));
   const PyrDesc ts = raw_ts_desc(c, 0);
   run_arc(c, dL, (uint32_t)n, &ts, true, false, true, c->cand_cur);
-  run_compact(c, (uint32_t)n, c->cand_cur);
+  compact_set(c, c->cand[c->cand_cur], ((uint32_t)n + kArcBlock - 1) / kArcBlock, true);
   run_select(c, c->cand_cur, max_corners, c->d_ptsD, 0, c->d_sel_idx);
   HIPCHK(c, hipMemcpyAsync(pin.counts, c->dres.counts, 8, hipMemcpyDeviceToHost, cur_stream(c)));
   HIPCHK(c, hipStreamSynchronize(cur_stream(c)));

@@ -332,7 +332,7 @@ struct esvio_fe_ctx {
   // batch (prefetch stream) never overwrites the set the current frame's selection still reads
   struct CandSet {
     DevBuf<uint32_t> xy, idx, cnt;
-    // ... and their ordered compaction into one stream (k_compact, launched right behind k_arc)
+    // ... and their ordered compaction into one stream (compact_set, right behind the kernel that filled them)
     DevBuf<uint32_t> comp_xy, comp_idx, total, grp;
     size_t cap = 0;  // of the set (grow_cand_set)
   } cand[kRightSlots];
@@ -352,12 +352,7 @@ struct esvio_fe_ctx {
   DevBuf<float> d_gftt_eig;
   DevBuf<uint32_t> d_gftt_max;
   DevBuf<int32_t> d_sel_idx;
-  // esvio_fe_fast_corners scratch, allocated on first use: the score map, the per-block lists, their
-  // counts (+ k_compact's group sums), the compacted list and {total, detected before non-max}
-  DevBuf<uint8_t> d_fast_m;
-  DevBuf<uint32_t> d_fast_xy, d_fast_score, d_fast_cnt, d_fast_det, d_fast_grp;
-  DevBuf<uint32_t> d_fast_cxy, d_fast_cscore, d_fast_tot;
-  DevBuf<uint8_t> d_fast_img;  // a caller's host image (linear, width*height)
+  DevBuf<uint8_t> d_fast_img;  // esvio_fe_fast_corners: a caller's host image (linear, width*height); its lists: fast_own below
   bool fast_lds = false;          // (ESVIO_FE_FAST_LDS=1: k_fast_score's LDS-tiled form, for the A/B in KERNELS.md)
   // pinned host staging (h_pin's layout: ResLayout)
   PinBuf<uint8_t> h_img;  // copy_level0_in's staging ring: pinned host side ...
@@ -454,6 +449,12 @@ struct esvio_fe_ctx {
   } fastc[kRightSlots + 1];
   CandSet fast_tap;
   DevBuf<uint8_t> d_fast_tap_img;
+  // esvio_fe_fast_corners' own (fast_run, fe_image.cpp), allocated by its first call: a candidate set of one entry per
+  // pixel — the per-block lists, the compacted list it returns — and of a FastCand the score map and the counts
+  // before non-max alone: it sorts nothing, so tot / keys / vals / hist stay empty.  The set's `total` has two words
+  // here, {total, detected before non-max}: adjacent, so that one copy brings both to the host.
+  CandSet fast_own;
+  FastCand fast_own_fc;
 };
 
 namespace esvio {

@@ -19,24 +19,12 @@ void euclid_halfwidths(double md, int8_t* hw /*[kMaxDiscR+1]*/, int* radius) {
   }
 }
 
-// fast::fast_corner_detect_9 / _10 (+ fast_corner_score_10, fast_nonmax_3x3) of the reference's vendored FAST
-// (dependences/fast_neon-master/include/fast/fast.h:22-47) on a device image.  Buffers of its own, allocated on
-// the first call: nothing the tracker or a prefetched batch uses is touched.
-int fast_run(esvio_fe_ctx* c, const uint8_t* img, int stride, int arc, int barrier, bool nonmax, int16_t* out_xy,
-             int32_t* out_score, int32_t capacity, int32_t* n_out, int32_t* n_detected) {
+// What every FAST pass starts with, on the current stream: the score map of the W x H image at `img` (in fc.m), the
+// per-block lists of `cs` — positions in xy, scores in idx — with the counts before them in fc.det, and the lists'
+// compaction.  skip_center: FastArgs::skip_center.  n_detected (device, may be null): where the sum of fc.det goes.
+static void fast_lists(esvio_fe_ctx* c, const uint8_t* img, int stride, int arc, int barrier, bool nonmax, int skip_center,
+                       const esvio_fe_ctx::CandSet& cs, const esvio_fe_ctx::FastCand& fc, uint32_t* n_detected) {
   const size_t P = (size_t)c->W * c->H;
-  const uint32_t nblk = (uint32_t)((P + kArcBlock - 1) / kArcBlock);
-  if (!c->d_fast_m) {
-    if (int rc = c->d_fast_xy.alloc(c, (size_t)nblk * kArcBlock)) return rc;
-    if (int rc = c->d_fast_score.alloc(c, (size_t)nblk * kArcBlock)) return rc;
-    if (int rc = c->d_fast_cnt.alloc(c, nblk)) return rc;
-    if (int rc = c->d_fast_det.alloc(c, nblk)) return rc;
-    if (int rc = c->d_fast_grp.alloc(c, nblk / 64 + 1)) return rc;
-    if (int rc = c->d_fast_cxy.alloc(c, P)) return rc;
-    if (int rc = c->d_fast_cscore.alloc(c, P)) return rc;
-    if (int rc = c->d_fast_tot.alloc(c, 2)) return rc;
-    if (int rc = c->d_fast_m.alloc(c, P)) return rc;  // (last: the test above means "all of them")
-  }
   hipStream_t s = cur_stream(c);
   FastArgs a{};
   a.img = img;
@@ -47,13 +35,13 @@ int fast_run(esvio_fe_ctx* c, const uint8_t* img, int stride, int arc, int barri
   a.barrier = barrier;
   a.nonmax = nonmax ? 1 : 0;
   a.lds = c->fast_lds ? 1 : 0;
-  a.m = c->d_fast_m;
-  a.cand_xy = c->d_fast_xy;
-  a.cand_score = c->d_fast_score;
-  a.cand_cnt = c->d_fast_cnt;
-  a.det_cnt = c->d_fast_det;
-  a.n_detected = (n_detected && nonmax) ? c->d_fast_tot + 1 : nullptr;  // (without non-max it is the total)
-  a.skip_center = -1;
+  a.m = fc.m;
+  a.cand_xy = cs.xy;
+  a.cand_score = cs.idx;
+  a.cand_cnt = cs.cnt;
+  a.det_cnt = fc.det;
+  a.n_detected = n_detected;
+  a.skip_center = skip_center;
   {
     ScopedKernel k(c, K_FAST_SCORE, 2 * P);  // the image read once, the map written
     launch_fast_score(s, a);
@@ -62,17 +50,38 @@ int fast_run(esvio_fe_ctx* c, const uint8_t* img, int stride, int arc, int barri
     ScopedKernel k(c, K_FAST_COLLECT, P);
     launch_fast_collect(s, a);
   }
-  {
-    ScopedKernel k(c, K_COMPACT, 0);
-    launch_compact(s, c->d_fast_xy, c->d_fast_score, c->d_fast_cnt, nblk, c->d_fast_cxy, c->d_fast_cscore, c->d_fast_tot,
-                   c->d_fast_grp);
+  compact_set(c, cs, (uint32_t)((P + kArcBlock - 1) / kArcBlock), true);
+}
+
+// the score map and the per-block counts before non-max: what fast_lists needs of a FastCand
+static int fast_map_alloc(esvio_fe_ctx* c, esvio_fe_ctx::FastCand& f) {
+  if (f.det) return 0;  // (the last one: "all of them")
+  const size_t P = (size_t)c->W * c->H;
+  if (int rc = f.m.alloc(c, P)) return rc;
+  return f.det.alloc(c, (P + kArcBlock - 1) / kArcBlock);
+}
+
+// fast::fast_corner_detect_9 / _10 (+ fast_corner_score_10, fast_nonmax_3x3) of the reference's vendored FAST
+// (dependences/fast_neon-master/include/fast/fast.h:22-47) on a device image.  A candidate set and a score map of
+// its own (fast_own, fast_own_fc), allocated on the first call: nothing the tracker, a prefetched batch or the stage
+// tap uses is touched.
+int fast_run(esvio_fe_ctx* c, const uint8_t* img, int stride, int arc, int barrier, bool nonmax, int16_t* out_xy,
+             int32_t* out_score, int32_t capacity, int32_t* n_out, int32_t* n_detected) {
+  esvio_fe_ctx::CandSet& cs = c->fast_own;
+  if (!cs.cap) {
+    if (int rc = fast_map_alloc(c, c->fast_own_fc)) return rc;
+    // total[0]: k_compact's total; total[1]: the count before non-max — side by side, one copy for both
+    if (int rc = cand_set_alloc(c, cs, ((size_t)c->W * c->H + kArcBlock - 1) / kArcBlock * kArcBlock, 2)) return rc;
   }
+  hipStream_t s = cur_stream(c);
+  // (without non-max the count before it is the total)
+  fast_lists(c, img, stride, arc, barrier, nonmax, -1, cs, c->fast_own_fc, (n_detected && nonmax) ? cs.total + 1 : nullptr);
   uint32_t tot[2] = {0, 0};
-  HIPCHK(c, hipMemcpyAsync(tot, c->d_fast_tot, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(tot, cs.total, 8, hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));
   const size_t k = std::min<size_t>(tot[0], capacity > 0 ? (size_t)capacity : 0);
-  if (k && out_xy) HIPCHK(c, hipMemcpyAsync(out_xy, c->d_fast_cxy, k * 4, hipMemcpyDeviceToHost, s));  // x | y<<16 = int16 x, y
-  if (k && out_score) HIPCHK(c, hipMemcpyAsync(out_score, c->d_fast_cscore, k * 4, hipMemcpyDeviceToHost, s));
+  if (k && out_xy) HIPCHK(c, hipMemcpyAsync(out_xy, cs.comp_xy, k * 4, hipMemcpyDeviceToHost, s));  // x | y<<16 = int16 x, y
+  if (k && out_score) HIPCHK(c, hipMemcpyAsync(out_score, cs.comp_idx, k * 4, hipMemcpyDeviceToHost, s));
   if (k) HIPCHK(c, hipStreamSynchronize(s));
   *n_out = (int32_t)tot[0];
   if (n_detected) *n_detected = (int32_t)(nonmax ? tot[1] : tot[0]);
@@ -86,10 +95,8 @@ static uint32_t fast_cand_max(const esvio_fe_ctx* c) { return (uint32_t)((c->W +
 
 static int fast_scratch_alloc(esvio_fe_ctx* c, esvio_fe_ctx::FastCand& f) {
   if (f.hist) return 0;  // (the last one: "all of them")
-  const size_t P = (size_t)c->W * c->H;
   const size_t n_max = fast_cand_max(c);
-  if (int rc = f.m.alloc(c, P)) return rc;
-  if (int rc = f.det.alloc(c, (P + kArcBlock - 1) / kArcBlock)) return rc;
+  if (int rc = fast_map_alloc(c, f)) return rc;
   if (int rc = f.tot.alloc(c, 1)) return rc;
   if (int rc = f.keys.alloc(c, n_max)) return rc;
   if (int rc = f.vals.alloc(c, n_max)) return rc;
@@ -117,39 +124,11 @@ int ensure_fast_detector(esvio_fe_ctx* c) {
 
 int fast_cand_pass(esvio_fe_ctx* c, const uint8_t* img, int stride, int barrier, const esvio_fe_ctx::CandSet& cs,
                    const esvio_fe_ctx::FastCand& fc, bool want_count) {
-  const size_t P = (size_t)c->W * c->H;
-  const uint32_t nblk = (uint32_t)((P + kArcBlock - 1) / kArcBlock);
   const uint32_t n_max = fast_cand_max(c);
   const double thr = c->cfg.ts_lk_threshold;
   hipStream_t s = cur_stream(c);
-  FastArgs a{};
-  a.img = img;
-  a.stride = stride;
-  a.W = c->W;
-  a.H = c->H;
-  a.arc = 10;
-  a.barrier = barrier;
-  a.nonmax = 1;
-  a.lds = c->fast_lds ? 1 : 0;
-  a.m = fc.m;
-  a.cand_xy = cs.xy;
-  a.cand_score = cs.idx;
-  a.cand_cnt = cs.cnt;
-  a.det_cnt = fc.det;
-  a.n_detected = want_count ? fc.tot.p : nullptr;
-  a.skip_center = thr >= 0 && thr < 256 ? (int)(uint8_t)thr : 256;  // (a byte that no pixel has: nobody is left out)
-  {
-    ScopedKernel k(c, K_FAST_SCORE, 2 * P);
-    launch_fast_score(s, a);
-  }
-  {
-    ScopedKernel k(c, K_FAST_COLLECT, P);
-    launch_fast_collect(s, a);
-  }
-  {
-    ScopedKernel k(c, K_COMPACT, 0);
-    launch_compact(s, cs.xy, cs.idx, cs.cnt, nblk, cs.comp_xy, cs.comp_idx, cs.total, cs.grp);
-  }
+  const int skip_center = thr >= 0 && thr < 256 ? (int)(uint8_t)thr : 256;  // (a byte that no pixel has: nobody is left out)
+  fast_lists(c, img, stride, 10, barrier, true, skip_center, cs, fc, want_count ? fc.tot.p : nullptr);
   // raster order -> by score, descending: keys + one stable 8-bit pass, booked together as one k_radix_pass entry.
   // The count stays on the device (cs.total): both launches are sized for n_max.  The pass writes the set's own
   // lists: comp_xy = the positions, comp_idx = the keys (score in bits 8..15), which the selection hands through.
@@ -198,8 +177,7 @@ int gftt_run(esvio_fe_ctx* c, const PyrDesc& d, int max_corners, double quality,
   g.cand_cnt = cs.cnt;
   launch_gftt_response(cur_stream(c), g);
   launch_gftt_collect(cur_stream(c), g);
-  const uint32_t nblk = (uint32_t)((P + kArcBlock - 1) / kArcBlock);
-  launch_compact(cur_stream(c), cs.xy, cs.idx, cs.cnt, nblk, cs.comp_xy, cs.comp_idx, cs.total);
+  compact_set(c, cs, (uint32_t)((P + kArcBlock - 1) / kArcBlock), false);
   uint32_t n = 0;
   HIPCHK(c, hipMemcpyAsync(&n, cs.total, 4, hipMemcpyDeviceToHost, cur_stream(c)));
   HIPCHK(c, hipStreamSynchronize(cur_stream(c)));

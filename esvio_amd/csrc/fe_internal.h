@@ -45,7 +45,8 @@ struct SortBufs {
   const uint32_t* n_dev;
 };
 int radix_sort_pairs(esvio_fe_ctx* c, const SortBufs& b, uint32_t n, int passes, int bits, bool booked);
-int cand_set_alloc(esvio_fe_ctx* c, esvio_fe_ctx::CandSet& s, size_t cap);  // the seven arrays of a candidate set
+// the seven arrays of a candidate set (total_words: of its `total`; fast_run keeps a second count behind it)
+int cand_set_alloc(esvio_fe_ctx* c, esvio_fe_ctx::CandSet& s, size_t cap, size_t total_words = 1);
 int stage_events(esvio_fe_ctx* c, const esvio_fe_event* left, size_t nL, const esvio_fe_event* right,
                  size_t nR, int space, const EventRec** dL, const EventRec** dR, int lane = -1);
 void render_ts(esvio_fe_ctx* c, double t_sync, uint8_t* dst0, uint8_t* dst1, int ncam, const double2* S2);
@@ -88,7 +89,7 @@ SelectArgs make_select_args(esvio_fe_ctx* c, int set, int max_corners, float2* o
                             int32_t* out_idx);
 size_t select_lds_bytes(const esvio_fe_ctx* c);
 void launch_select_args(esvio_fe_ctx* c, SelectArgs s);
-void run_compact(esvio_fe_ctx* c, uint32_t n_events, int set);
+void compact_set(esvio_fe_ctx* c, const esvio_fe_ctx::CandSet& cs, uint32_t nblk, bool booked);
 void run_select(esvio_fe_ctx* c, int set, int max_corners, float2* out_pts, int out_base, int32_t* out_idx,
                 const uint32_t* mask_bits = nullptr, int* host_counts = nullptr, bool publish = false,
                 const float2* stamp_pts = nullptr, int n_stamp = 0);
@@ -151,6 +152,7 @@ int gftt_run(esvio_fe_ctx* c, const PyrDesc& d, int max_corners, double quality,
 // the current stream; synchronises it.  Up to `capacity` corners in raster order go to out_xy / out_score (host).
 int fast_run(esvio_fe_ctx* c, const uint8_t* img, int stride, int arc, int barrier, bool nonmax, int16_t* out_xy,
              int32_t* out_score, int32_t capacity, int32_t* n_out, int32_t* n_detected);
+// (in a candidate set and FAST scratch of its own, esvio_fe_ctx::fast_own / fast_own_fc, allocated by the first call)
 // ESVIO_FE_DETECT_FAST (esvio_fe_ctx::fastc): everything the candidate passes and the stage tap need, allocated once;
 // what the stage tap alone needs
 int ensure_fast_detector(esvio_fe_ctx* c);

@@ -3125,6 +3125,33 @@ __device__ __forceinline__ bool arc_ring_ranks(const double (&v)[N]) {
 //               of the survivors (ballot + popcount) as before.
 constexpr int kArcRegion = 256;  // pixels per k_arc_map block: 512 (pixel, polarity) flag bytes
 
+// The form every detector hands its corners on in (k_arc_ev, k_dedup, k_gftt_collect, k_fast_collect -> k_compact):
+// a block of kArcBlock lanes leaves its takers as a list in lane order, with a count.  Returns the slot of this
+// lane's entry in its block's list (meaningful where `take`) and, in *total, the block's count.  Every thread of the
+// block calls it: it holds the kernel's one __syncthreads().  wave_cnt: kArcBlock / 64 words of LDS.
+// counted / wave_cnt2 / total2: a second count — a ballot the caller has taken — carried through the same barrier.
+__device__ __forceinline__ uint32_t block_list_slot(bool take, uint32_t* wave_cnt, uint32_t* total,
+                                                    unsigned long long counted = 0, uint32_t* wave_cnt2 = nullptr,
+                                                    uint32_t* total2 = nullptr) {
+  const int wave = threadIdx.x >> 6, lane = lane_id();
+  const unsigned long long m = __ballot(take);
+  if (lane == 0) {
+    wave_cnt[wave] = __popcll(m);
+    if (wave_cnt2) wave_cnt2[wave] = __popcll(counted);
+  }
+  __syncthreads();
+  uint32_t base = 0, tot = 0, tot2 = 0;
+#pragma unroll
+  for (int w = 0; w < kArcBlock / 64; w++) {
+    if (w < wave) base += wave_cnt[w];
+    tot += wave_cnt[w];
+    if (wave_cnt2) tot2 += wave_cnt2[w];
+  }
+  *total = tot;
+  if (total2) *total2 = tot2;
+  return base + __popcll(m & ((1ull << lane) - 1ull));
+}
+
 __global__ __launch_bounds__(256) void k_arc_mark(const uint4* __restrict__ ev, uint32_t n, int W, int H,
                                                   uint8_t* __restrict__ touched) {
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
@@ -3208,24 +3235,15 @@ __global__ __launch_bounds__(kArcBlock) void k_arc_ev(ArcArgs a) {
     }
     if (a.flags) a.flags[i] = corner ? 1 : 0;
   }
-  if (a.cand_cnt) {
-    const int wave = threadIdx.x >> 6, lane = lane_id();
-    const unsigned long long m = __ballot(corner);
-    if (lane == 0) wave_cnt[wave] = __popcll(m);
-    __syncthreads();
-    uint32_t base = 0;
-    for (int w = 0; w < wave; w++) base += wave_cnt[w];
+  if (a.cand_cnt) {  // (block-uniform: block_list_slot's barrier)
+    uint32_t total;
+    const size_t pos = (size_t)blockIdx.x * kArcBlock + block_list_slot(corner, wave_cnt, &total);
     if (corner) {
-      const uint32_t pos = blockIdx.x * kArcBlock + base + __popcll(m & ((1ull << lane) - 1ull));
       a.cand_xy[pos] = x | (y << 16);
       a.cand_idx[pos] = i;
       if (a.first_map) atomicMin(&a.first_map[y * (uint32_t)a.W + x], a.first_key | i);
     }
-    if (threadIdx.x == 0) {
-      uint32_t t = 0;
-      for (int w = 0; w < kArcBlock / 64; w++) t += wave_cnt[w];
-      a.cand_cnt[blockIdx.x] = t;
-    }
+    if (threadIdx.x == 0) a.cand_cnt[blockIdx.x] = total;
   }
 }
 
@@ -3308,7 +3326,6 @@ __global__ __launch_bounds__(kArcBlock) void k_dedup(uint32_t* __restrict__ cand
                                                      uint32_t first_key, int W) {
   __shared__ uint32_t wave_cnt[kArcBlock / 64];
   const uint32_t b = blockIdx.x, c = cand_cnt[b];
-  const int wave = threadIdx.x >> 6, lane = lane_id();
   uint32_t xy = 0, idx = 0;
   bool keep = false;
   if (threadIdx.x < c) {
@@ -3316,20 +3333,14 @@ __global__ __launch_bounds__(kArcBlock) void k_dedup(uint32_t* __restrict__ cand
     idx = cand_idx[(size_t)b * kArcBlock + threadIdx.x];
     keep = first_map[(xy >> 16) * (uint32_t)W + (xy & 0xffffu)] == (first_key | idx);
   }
-  const unsigned long long m = __ballot(keep);
-  if (lane == 0) wave_cnt[wave] = __popcll(m);
-  __syncthreads();  // (also: every thread has read its entry before any is overwritten)
-  uint32_t base = 0, tot = 0;
-  for (int w = 0; w < kArcBlock / 64; w++) {
-    if (w < wave) base += wave_cnt[w];
-    tot += wave_cnt[w];
-  }
+  // (its barrier also: every thread has read its entry before any is overwritten)
+  uint32_t total;
+  const size_t pos = (size_t)b * kArcBlock + block_list_slot(keep, wave_cnt, &total);
   if (keep) {
-    const uint32_t pos = base + __popcll(m & ((1ull << lane) - 1ull));
-    cand_xy[(size_t)b * kArcBlock + pos] = xy;
-    cand_idx[(size_t)b * kArcBlock + pos] = idx;
+    cand_xy[pos] = xy;
+    cand_idx[pos] = idx;
   }
-  if (threadIdx.x == 0) cand_cnt[b] = tot;
+  if (threadIdx.x == 0) cand_cnt[b] = total;
 }
 
 void launch_dedup(hipStream_t s, uint32_t* cand_xy, uint32_t* cand_idx, uint32_t* cand_cnt,
@@ -3469,7 +3480,6 @@ void launch_gftt_response(hipStream_t s, const GfttArgs& a) {
 // row-major order and leaves its candidates in that order
 __global__ __launch_bounds__(kArcBlock) void k_gftt_collect(GfttArgs a) {
   __shared__ uint32_t wave_cnt[kArcBlock / 64];
-  const int wave = threadIdx.x >> 6, lane = lane_id();
   const uint32_t i = blockIdx.x * kArcBlock + threadIdx.x;
   const int W = a.W, H = a.H;
   const uint32_t mk = *a.max_key;
@@ -3495,21 +3505,13 @@ __global__ __launch_bounds__(kArcBlock) void k_gftt_collect(GfttArgs a) {
       }
     }
   }
-  const unsigned long long mb = __ballot(take);
-  if (lane == 0) wave_cnt[wave] = __popcll(mb);
-  __syncthreads();
-  uint32_t base = 0;
-  for (int w = 0; w < wave; w++) base += wave_cnt[w];
+  uint32_t total;
+  const size_t pos = (size_t)blockIdx.x * kArcBlock + block_list_slot(take, wave_cnt, &total);
   if (take) {
-    const uint32_t pos = base + __popcll(mb & ((1ull << lane) - 1ull));
-    a.cand_xy[(size_t)blockIdx.x * kArcBlock + pos] = (uint32_t)x | ((uint32_t)y << 16);
-    a.cand_val[(size_t)blockIdx.x * kArcBlock + pos] = __float_as_uint(val);
+    a.cand_xy[pos] = (uint32_t)x | ((uint32_t)y << 16);
+    a.cand_val[pos] = __float_as_uint(val);
   }
-  if (threadIdx.x == 0) {
-    uint32_t t = 0;
-    for (int w = 0; w < kArcBlock / 64; w++) t += wave_cnt[w];
-    a.cand_cnt[blockIdx.x] = t;
-  }
+  if (threadIdx.x == 0) a.cand_cnt[blockIdx.x] = total;
 }
 
 void launch_gftt_collect(hipStream_t s, const GfttArgs& a) {
@@ -3653,7 +3655,6 @@ void launch_fast_score(hipStream_t s, const FastArgs& a) {
 // m > 0 only inside the 3-pixel border, so a corner's eight neighbours are always inside the image
 __global__ __launch_bounds__(kArcBlock) void k_fast_collect(FastArgs a) {
   __shared__ uint32_t wave_cnt[kArcBlock / 64], wave_det[kArcBlock / 64];
-  const int wave = threadIdx.x >> 6, lane = lane_id();
   const uint32_t i = blockIdx.x * kArcBlock + threadIdx.x;
   const int W = a.W;
   uint32_t v = 0;
@@ -3672,27 +3673,15 @@ __global__ __launch_bounds__(kArcBlock) void k_fast_collect(FastArgs a) {
     counted = __ballot(take);
     if (take) take = (int)a.img[(size_t)y * a.stride + x] != a.skip_center;
   }
-  const unsigned long long mb = __ballot(take);
-  if (lane == 0) {
-    wave_cnt[wave] = __popcll(mb);
-    wave_det[wave] = __popcll(counted);
-  }
-  __syncthreads();
-  uint32_t base = 0;
-  for (int w = 0; w < wave; w++) base += wave_cnt[w];
+  uint32_t total, detected;
+  const size_t pos = (size_t)blockIdx.x * kArcBlock + block_list_slot(take, wave_cnt, &total, counted, wave_det, &detected);
   if (take) {
-    const uint32_t pos = base + __popcll(mb & ((1ull << lane) - 1ull));
-    a.cand_xy[(size_t)blockIdx.x * kArcBlock + pos] = x | (y << 16);
-    a.cand_score[(size_t)blockIdx.x * kArcBlock + pos] = v - 1;
+    a.cand_xy[pos] = x | (y << 16);
+    a.cand_score[pos] = v - 1;
   }
   if (threadIdx.x == 0) {
-    uint32_t t = 0, dsum = 0;
-    for (int w = 0; w < kArcBlock / 64; w++) {
-      t += wave_cnt[w];
-      dsum += wave_det[w];
-    }
-    a.cand_cnt[blockIdx.x] = t;
-    a.det_cnt[blockIdx.x] = dsum;
+    a.cand_cnt[blockIdx.x] = total;
+    a.det_cnt[blockIdx.x] = detected;
   }
 }
 

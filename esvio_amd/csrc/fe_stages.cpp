@@ -42,7 +42,7 @@ int ensure_sort_capacity(esvio_fe_ctx* c, size_t n) {
 }
 
 // the seven arrays of a candidate set share one capacity (cap: set once all of them are there)
-int cand_set_alloc(esvio_fe_ctx* c, esvio_fe_ctx::CandSet& s, size_t cap) {
+int cand_set_alloc(esvio_fe_ctx* c, esvio_fe_ctx::CandSet& s, size_t cap, size_t total_words) {
   s = esvio_fe_ctx::CandSet();
   if (int rc = s.xy.alloc(c, cap)) return rc;
   if (int rc = s.idx.alloc(c, cap)) return rc;
@@ -50,7 +50,7 @@ int cand_set_alloc(esvio_fe_ctx* c, esvio_fe_ctx::CandSet& s, size_t cap) {
   if (int rc = s.grp.alloc(c, cap / kArcBlock / 64 + 2)) return rc;
   if (int rc = s.comp_xy.alloc(c, cap)) return rc;
   if (int rc = s.comp_idx.alloc(c, cap)) return rc;
-  if (int rc = s.total.alloc(c, 1)) return rc;
+  if (int rc = s.total.alloc(c, total_words)) return rc;
   s.cap = cap;
   return 0;
 }
@@ -671,12 +671,12 @@ void launch_select_args(esvio_fe_ctx* c, SelectArgs s) {
   k.id = launch_select(cur_stream(c), s, c->select_ok ? select_lds_bytes(c) : select_tables_lds_bytes(c));
 }
 
-// ordered compaction of candidate set `set` (right behind the k_arc that filled it)
-void run_compact(esvio_fe_ctx* c, uint32_t n_events, int set) {
-  const uint32_t nblk = (n_events + kArcBlock - 1) / kArcBlock;
-  const esvio_fe_ctx::CandSet& cs = c->cand[set];
-  ScopedKernel k(c, K_COMPACT, 0);
-  launch_compact(cur_stream(c), cs.xy, cs.idx, cs.cnt, nblk, cs.comp_xy, cs.comp_idx, cs.total, cs.grp);
+// ordered compaction of the first nblk per-block lists of `cs` (right behind the kernel that filled them).  booked: as
+// K_COMPACT in the kernel statistics, and with the set's group sums (goodFeaturesToTrack's stages are neither)
+void compact_set(esvio_fe_ctx* c, const esvio_fe_ctx::CandSet& cs, uint32_t nblk, bool booked) {
+  std::optional<ScopedKernel> k;
+  if (booked) k.emplace(c, K_COMPACT, 0);
+  launch_compact(cur_stream(c), cs.xy, cs.idx, cs.cnt, nblk, cs.comp_xy, cs.comp_idx, cs.total, booked ? cs.grp.p : nullptr);
 }
 
 // the sequential greedy (Event_FeaturesToTrack) over the compacted candidates of set `set`;
@@ -758,7 +758,7 @@ void run_arc(esvio_fe_ctx* c, const EventRec* ev, uint32_t n, const PyrDesc* ts,
 int run_detect(esvio_fe_ctx* c, const EventRec* ev, uint32_t n, const PyrDesc& ts, int set, bool marked) {
   if (c->detector == ESVIO_FE_DETECT_FAST) return run_fast_cand(c, ts, set);
   run_arc(c, ev, n, &ts, false, false, true, set, marked);
-  run_compact(c, n, set);
+  compact_set(c, c->cand[set], (n + kArcBlock - 1) / kArcBlock, true);
   return 0;
 }
 

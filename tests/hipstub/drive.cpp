@@ -12,6 +12,8 @@
 //   drive trace                with HIPSTUB_TRACE=<file>: one thread, a fixed matrix of handles and calls (trace_matrix
 //                              below); the file then holds every launch and stream call in order, with its stream, and
 //                              per handle what the profiling API counted (tests/test_launch_trace.py)
+//   drive trace_cand           the same for the paths that leave per-block candidate lists and the matrix above never
+//                              reaches (trace_cand_matrix below; tests/test_launch_trace_cand.py)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -258,6 +260,16 @@ static void trace_image_handle(const char* label, const esvio_fe_config& c, int 
   trace_destroy(h);
 }
 
+static int trace_finish(const char* mode) {
+  long live[4];
+  hipstub_live(live);
+  char buf[128];
+  snprintf(buf, sizeof(buf), "live: device %ld pinned %ld events %ld streams %ld", live[0], live[1], live[2], live[3]);
+  hipstub_trace_note(buf);
+  if (trace_bad) fprintf(stderr, "drive %s: %d calls failed\n", mode, trace_bad);
+  return trace_bad ? 6 : 0;
+}
+
 static int trace_matrix(esvio_fe_config c) {
   setenv("ESVIO_FE_STAGE_THREADS", "0", 1);
   hipstub_arm_faults(0);
@@ -283,17 +295,104 @@ static int trace_matrix(esvio_fe_config c) {
   trace_event_handle("selection bitmap in device memory", c, 1920, 1080);
   trace_image_handle("images", c, W, H);
   trace_image_handle("images equalize", eq, W, H);
-  long live[4];
-  hipstub_live(live);
-  char buf[128];
-  snprintf(buf, sizeof(buf), "live: device %ld pinned %ld events %ld streams %ld", live[0], live[1], live[2], live[3]);
-  hipstub_trace_note(buf);
-  if (trace_bad) fprintf(stderr, "drive trace: %d calls failed\n", trace_bad);
-  return trace_bad ? 6 : 0;
+  return trace_finish("trace");
+}
+
+// ---- drive trace_cand: every path that fills per-block candidate lists and has them compacted — esvio_fe_fast_corners,
+// FAST as trackEvent's detector and its stage tap, the Arc* pass with k_dedup, goodFeaturesToTrack
+static void trace_fast_corners(const esvio_fe_config& c, int W, int H) {
+  esvio_fe_handle h = trace_create("esvio_fe_fast_corners", c, W, H);
+  if (!h) return;
+  std::vector<uint8_t> img((size_t)W * H, 7);
+  std::vector<int16_t> fxy(2 * 64);
+  std::vector<int32_t> fsc(64);
+  int32_t n = 0, n_det = 0;
+  // the handle's time surface, then a host image (the fake compaction reports 1000 corners: 64 are copied out)
+  TR(esvio_fe_fast_corners(h, 0, nullptr, ESVIO_FE_HOST, 10, 20, 1, fxy.data(), fsc.data(), 64, &n, &n_det));
+  TR(esvio_fe_fast_corners(h, 0, nullptr, ESVIO_FE_HOST, 10, 20, 0, fxy.data(), fsc.data(), 64, &n, &n_det));
+  TR(esvio_fe_fast_corners(h, 1, nullptr, ESVIO_FE_HOST, 9, 20, 0, fxy.data(), nullptr, 64, &n, &n_det));
+  TR(esvio_fe_fast_corners(h, 0, img.data(), ESVIO_FE_HOST, 10, 20, 1, fxy.data(), fsc.data(), 64, &n, &n_det));
+  TR(esvio_fe_fast_corners(h, 0, img.data(), ESVIO_FE_HOST, 10, 20, 0, fxy.data(), nullptr, 64, &n, nullptr));
+  TR(esvio_fe_fast_corners(h, 0, img.data(), ESVIO_FE_HOST, 9, 20, 0, fxy.data(), nullptr, 0, &n, &n_det));
+  trace_destroy(h);
+}
+
+static void trace_fast_detector(const esvio_fe_config& c, int W, int H) {
+  esvio_fe_handle h = trace_create("ESVIO_FE_DETECT_FAST", c, W, H);
+  if (!h) return;
+  const int M = c.max_cnt;
+  TraceOut o(M);
+  esvio_fe_tracks& t = o.t;
+  Batch b[4];
+  for (int i = 0; i < 4; i++) make_batch(b[i], W, H, i, 3000 + 100 * i);
+#define EV(i) b[i].t, b[i].L.data(), b[i].L.size(), b[i].R.data(), b[i].R.size()
+  TR(esvio_fe_set_detector(h, ESVIO_FE_DETECT_FAST, 20));
+  TR(esvio_fe_track_event(h, EV(0), ESVIO_FE_HOST, 1, &t));
+  TR(esvio_fe_set_next_batch(h, EV(1), ESVIO_FE_HOST, 1));
+  TR(esvio_fe_track_event(h, EV(1), ESVIO_FE_HOST, 1, &t));
+  TR(esvio_fe_finish(h, &t));
+  std::vector<uint8_t> img((size_t)W * H, 7), mask((size_t)W * H, 0);
+  std::vector<float> xy(2 * (size_t)M);
+  std::vector<int32_t> sc((size_t)M);
+  int32_t n = 0, n_cand = 0;
+  TR(esvio_fe_features_to_track_fast(h, nullptr, ESVIO_FE_HOST, 20, M, nullptr, xy.data(), sc.data(), &n, &n_cand));
+  TR(esvio_fe_features_to_track_fast(h, img.data(), ESVIO_FE_HOST, 20, M, mask.data(), xy.data(), nullptr, &n, nullptr));
+  TR(esvio_fe_set_next_batch(h, EV(2), ESVIO_FE_HOST, 1));
+  TR(esvio_fe_reset(h));
+  TR(esvio_fe_track_event(h, EV(3), ESVIO_FE_HOST, 1, &t));
+#undef EV
+  trace_destroy(h);
+}
+
+static void trace_dedup_handle(const char* label, const esvio_fe_config& c, int W, int H) {
+  esvio_fe_handle h = trace_create(label, c, W, H);
+  if (!h) return;
+  const int M = c.max_cnt;
+  TraceOut o(M);
+  Batch b[2];
+  for (int i = 0; i < 2; i++) make_batch(b[i], W, H, i, 3000 + 100 * i);
+  TR(esvio_fe_track_event(h, b[0].t, b[0].L.data(), b[0].L.size(), b[0].R.data(), b[0].R.size(), ESVIO_FE_HOST, 1, &o.t));
+  TR(esvio_fe_set_next_batch(h, b[1].t, b[1].L.data(), b[1].L.size(), b[1].R.data(), b[1].R.size(), ESVIO_FE_HOST, 1));
+  TR(esvio_fe_track_event(h, b[1].t, b[1].L.data(), b[1].L.size(), b[1].R.data(), b[1].R.size(), ESVIO_FE_HOST, 1, &o.t));
+  TR(esvio_fe_finish(h, &o.t));
+  std::vector<float> xy(2 * (size_t)M);
+  int32_t n = 0;
+  TR(esvio_fe_features_to_track(h, b[1].L.data(), b[1].L.size(), ESVIO_FE_HOST, M, nullptr, xy.data(), nullptr, &n));
+  trace_destroy(h);
+}
+
+static void trace_gftt_handle(const esvio_fe_config& c, int W, int H) {
+  esvio_fe_handle h = trace_create("esvio_fe_good_features_to_track", c, W, H);
+  if (!h) return;
+  const int M = c.max_cnt;
+  std::vector<uint8_t> img((size_t)W * H, 7), mask((size_t)W * H, 0);
+  std::vector<float> xy(2 * (size_t)M);
+  int32_t n = 0;
+  TR(esvio_fe_good_features_to_track(h, img.data(), M, 0.01, 10.0, nullptr, xy.data(), &n, nullptr));
+  TR(esvio_fe_good_features_to_track(h, img.data(), M, 0.01, 10.0, mask.data(), xy.data(), &n, nullptr));
+  trace_destroy(h);
+}
+
+static int trace_cand_matrix(esvio_fe_config c) {
+  setenv("ESVIO_FE_STAGE_THREADS", "0", 1);
+  hipstub_arm_faults(0);
+  hipstub_set_compact_total(1000);
+  const int W = 346, H = 260;
+  trace_fast_corners(c, W, H);
+  trace_fast_detector(c, W, H);
+  esvio_fe_config big = c;
+  big.max_cnt = 600;
+  trace_dedup_handle("k_dedup: max_cnt 600", big, W, H);
+  setenv("ESVIO_FE_DEDUP", "1", 1);
+  trace_dedup_handle("k_dedup: ESVIO_FE_DEDUP", c, W, H);
+  unsetenv("ESVIO_FE_DEDUP");
+  trace_gftt_handle(c, W, H);
+  return trace_finish("trace_cand");
 }
 
 int main(int argc, char** argv) {
   const bool trace_mode = argc > 1 && !strcmp(argv[1], "trace");
+  const bool trace_cand_mode = argc > 1 && !strcmp(argv[1], "trace_cand");
   rs = argc > 1 ? (uint32_t)atoi(argv[1]) : 1u;
   const int frames = argc > 2 ? atoi(argv[2]) : 200;
   const int W = 640, H = 480, M = 120;
@@ -304,6 +403,7 @@ int main(int argc, char** argv) {
   c.focal_length = 460; c.device = -1;
   for (int k = 0; k < 2; k++) { c.cam[k].fx = c.cam[k].fy = 0.9 * W; c.cam[k].cx = W / 2.0; c.cam[k].cy = H / 2.0; }
   if (trace_mode) return trace_matrix(c);
+  if (trace_cand_mode) return trace_cand_matrix(c);
   std::vector<int32_t> ids(M), cnt(M), idr(M);
   std::vector<float> f2[6];
   for (auto& v : f2) v.resize(2 * M);
