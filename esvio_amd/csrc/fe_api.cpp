@@ -55,25 +55,21 @@ int exchange_buffers(esvio_fe_ctx* c, int world) {
 // the ESVIO_FE_TRACE summary of a handle's life
 static void print_trace_summary(const esvio_fe_ctx* c) {
   if (!c->trace || !c->phase_frames) return;
-  static const char* nm[8] = {"enqueue sae+ts+pyr", "enqueue temporal LK", "sync A", "host filter",
-                              "host ransac", "host mask + enqueue detect/stereo", "sync B", "host tail"};
   for (int pub = 0; pub < 2; pub++) {
     if (!c->phase_count[pub]) continue;
     double tot = 0;
     fprintf(stderr, "[esvio_fe trace] %llu %s frames, ms/frame:", (unsigned long long)c->phase_count[pub],
             pub ? "published" : "unpublished");
-    for (int i = 0; i < 8; i++) {
-      fprintf(stderr, " %s=%.3f", nm[i], c->phase_ms[pub][i] / c->phase_count[pub]);
-      tot += c->phase_ms[pub][i] / c->phase_count[pub];
+    for (int i = PH_ENQ_BATCH; i <= PH_TAIL; i++) {
+      fprintf(stderr, " %s=%.3f", kPhaseNames[i], c->trace_phase_ms[pub][i] / c->phase_count[pub]);
+      tot += c->trace_phase_ms[pub][i] / c->phase_count[pub];
     }
     fprintf(stderr, " | total=%.3f\n", tot);
   }
   if (c->phase_count[1]) {
-    static const char* pn[6] = {"Event_setMask", "points + k_select launch", "speculative + chained LK launches",
-                                "previous frame's right-camera tail", "stereo LK of new corners launch",
-                                "next batch's prefetch launches"};
     fprintf(stderr, "[esvio_fe trace] published frames, parts of 'host mask + enqueue', ms/frame:");
-    for (int i = 0; i < 6; i++) fprintf(stderr, " %s=%.3f", pn[i], c->pub_ms[i] / c->phase_count[1]);
+    for (int i = PH_PUB_SETMASK; i <= PH_PUB_PREFETCH; i++)
+      fprintf(stderr, " %s=%.3f", kPhaseNames[i] + strlen("pub: "), c->trace_phase_ms[1][i] / c->phase_count[1]);
     fprintf(stderr, "\n");
   }
   fprintf(stderr, "[esvio_fe trace]");
@@ -390,10 +386,9 @@ int esvio_fe_reset(esvio_fe_handle c) {
   return 0;
 }
 
-int esvio_fe_create_sae_stereo(esvio_fe_handle c, const esvio_fe_event* left, size_t nL,
-                               const esvio_fe_event* right, size_t nR, int space,
-                               uint64_t* n_rejected) {
-  if (!c || (nL && !left) || (nR && !right)) return ESVIO_FE_EINVAL;
+// esvio_fe_create_sae_stereo and its motion-compensated form (mc != nullptr) behind their argument checks
+static int create_sae_stereo(esvio_fe_ctx* c, const esvio_fe_event* left, size_t nL, const esvio_fe_event* right,
+                             size_t nR, int space, const McParams* mc, uint64_t* n_rejected) {
   if (nL + nR >= (1ull << 31)) return fail(c, ESVIO_FE_EINVAL, "batch too large");
   if (!c->inflight.empty()) return fail(c, ESVIO_FE_EINVAL, "a prefetched batch is pending");
   HIPCHK(c, hipSetDevice(c->dev));
@@ -401,7 +396,7 @@ int esvio_fe_create_sae_stereo(esvio_fe_handle c, const esvio_fe_event* left, si
   const EventRec *dL, *dR;
   if (int rc = stage_events(c, left, nL, right, nR, space, &dL, &dR)) return rc;
   HIPCHK(c, hipMemsetAsync(c->d_rejected, 0, 8, cur_stream(c)));
-  if (int rc = sae_update(c, dL, (uint32_t)nL, dR, (uint32_t)nR)) return rc;
+  if (int rc = sae_update(c, dL, (uint32_t)nL, dR, (uint32_t)nR, mc)) return rc;
   unsigned long long rej = 0;
   HIPCHK(c, hipMemcpyAsync(&rej, c->d_rejected, 8, hipMemcpyDeviceToHost, cur_stream(c)));
   HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
@@ -411,26 +406,19 @@ int esvio_fe_create_sae_stereo(esvio_fe_handle c, const esvio_fe_event* left, si
   return 0;
 }
 
+int esvio_fe_create_sae_stereo(esvio_fe_handle c, const esvio_fe_event* left, size_t nL,
+                               const esvio_fe_event* right, size_t nR, int space,
+                               uint64_t* n_rejected) {
+  if (!c || (nL && !left) || (nR && !right)) return ESVIO_FE_EINVAL;
+  return create_sae_stereo(c, left, nL, right, nR, space, nullptr, n_rejected);
+}
+
 int esvio_fe_create_sae_stereo_mc(esvio_fe_handle c, const esvio_fe_event* left, size_t nL,
                                   const esvio_fe_event* right, size_t nR, int space,
                                   const esvio_fe_motion* motion, uint64_t* n_rejected) {
   if (!c || !motion || !nL || !left || (nR && !right)) return ESVIO_FE_EINVAL;
-  if (nL + nR >= (1ull << 31)) return fail(c, ESVIO_FE_EINVAL, "batch too large");
-  if (!c->inflight.empty()) return fail(c, ESVIO_FE_EINVAL, "a prefetched batch is pending");
-  HIPCHK(c, hipSetDevice(c->dev));
   const McParams mc = make_mc_params(motion);
-  c->ext_sae_pending = false;
-  const EventRec *dL, *dR;
-  if (int rc = stage_events(c, left, nL, right, nR, space, &dL, &dR)) return rc;
-  HIPCHK(c, hipMemsetAsync(c->d_rejected, 0, 8, cur_stream(c)));
-  if (int rc = sae_update(c, dL, (uint32_t)nL, dR, (uint32_t)nR, &mc)) return rc;
-  unsigned long long rej = 0;
-  HIPCHK(c, hipMemcpyAsync(&rej, c->d_rejected, 8, hipMemcpyDeviceToHost, cur_stream(c)));
-  HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
-  if (int rc = lookback_expired(c)) return rc;
-  if (n_rejected) *n_rejected = rej;
-  if (c->prof_on) resolve_profile(c);
-  return 0;
+  return create_sae_stereo(c, left, nL, right, nR, space, &mc, n_rejected);
 }
 
 // ---- one stream time-sliced across GPUs -----------------------------------------
@@ -1645,13 +1633,7 @@ int esvio_fe_reserve(esvio_fe_handle c, size_t max_left, size_t max_right, int h
 }
 
 const char* esvio_fe_latency_phase_name(int i) {
-  static const char* nm[ESVIO_FE_LATENCY_PHASES] = {
-      "enqueue sae+ts+pyr", "enqueue temporal LK", "wait temporal LK", "host filter", "host ransac",
-      "host mask + enqueue detect/stereo", "wait stereo LK", "host tail",
-      "pub: Event_setMask", "pub: points + k_select launch", "pub: speculative + chained LK launches",
-      "pub: previous frame's right tail", "pub: stereo LK of new corners launch", "pub: next batch's prefetch launches",
-      "check + take-up of a late batch", "sae: staging the host batch (part of enqueue sae+ts+pyr)"};
-  return (i >= 0 && i < ESVIO_FE_LATENCY_PHASES) ? nm[i] : "";
+  return (i >= 0 && i < PH_COUNT) ? kPhaseNames[i] : "";
 }
 
 int esvio_fe_latency_recent(esvio_fe_handle c, int back, esvio_fe_latency_call* out) {

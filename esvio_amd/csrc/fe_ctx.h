@@ -71,6 +71,33 @@ const char* const kKernelNames[K_COUNT] = {
     "k_scharr", "k_pad_scharr", "k_lk_f32", "k_lk", "k_arc_map", "k_arc_ev", "k_dedup", "k_compact", "k_select_mw",
     "k_select", "k_select_gbm", "k_fast_score", "k_fast_collect", "k_events_from_fields"};
 
+// The host phases of one trackEvent call, in the order of esvio_fe_latency_call::phase_ms; kPhaseNames is what
+// esvio_fe_latency_phase_name returns and what the ESVIO_FE_TRACE summary prints.  The PH_PUB_* phases are parts of
+// PH_MASK_DETECT on published frames, PH_STAGE_HOST is part of PH_ENQ_BATCH.
+enum Phase {
+  PH_ENQ_BATCH, PH_ENQ_TEMPORAL, PH_WAIT_TEMPORAL, PH_FILTER, PH_RANSAC, PH_MASK_DETECT, PH_WAIT_STEREO, PH_TAIL,
+  PH_PUB_SETMASK, PH_PUB_SELECT, PH_PUB_SPEC, PH_PUB_PREV_RIGHT, PH_PUB_STEREO_NEW, PH_PUB_PREFETCH,
+  PH_CHECK, PH_STAGE_HOST, PH_COUNT
+};
+static_assert(PH_COUNT == ESVIO_FE_LATENCY_PHASES, "one enumerator per public latency phase");
+const char* const kPhaseNames[PH_COUNT] = {
+    "enqueue sae+ts+pyr", "enqueue temporal LK", "wait temporal LK", "host filter", "host ransac",
+    "host mask + enqueue detect/stereo", "wait stereo LK", "host tail",
+    "pub: Event_setMask", "pub: points + k_select launch", "pub: speculative + chained LK launches",
+    "pub: previous frame's right tail", "pub: stereo LK of new corners launch", "pub: next batch's prefetch launches",
+    "check + take-up of a late batch", "sae: staging the host batch (part of enqueue sae+ts+pyr)"};
+
+// the stopwatch behind every phase: lap() = the milliseconds since the last lap (or the construction)
+struct PhaseClock {
+  std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+  double lap() {
+    const auto now = std::chrono::steady_clock::now();
+    const double ms = std::chrono::duration<double, std::milli>(now - t).count();
+    t = now;
+    return ms;
+  }
+};
+
 struct KStat {
   double ms = 0;
   uint64_t launches = 0;
@@ -370,15 +397,13 @@ struct esvio_fe_ctx {
   IdMap cur_un_pts_map, prev_un_pts_map, cur_un_right_pts_map, prev_un_right_pts_map;
   host::BitMask mask_event;
 
-  // ---- host phase trace (ESVIO_FE_TRACE=1): stage, sae+ts enqueue, sync A, host A, enqueue B,
-  // sync B, host B
+  // ---- host phase trace (ESVIO_FE_TRACE=1): the sums of the successful calls' latency records, and what is finer
   DevBuf<uint8_t> d_eq_tmp;  // equalize: the two CLAHE outputs before normalisation (linear W x H each)
   bool select_ok = true;  // the greedy selection's bitmap fits LDS
   bool select_one_wave = false;  // (ESVIO_FE_SELECT_SERIAL=1, test-only: the one-wave selection kernel)
   DevBuf<uint32_t> d_sel_bitmap;  // ... else it lives here (k_select_gbm)
   bool trace = false;
-  double phase_ms[2][8] = {};  // [published?][phase]
-  double pub_ms[6] = {};       // published frames: the parts of "host mask + enqueue detect/stereo"
+  double trace_phase_ms[2][ESVIO_FE_LATENCY_PHASES] = {};  // [published?][Phase]: lat.cur_phase of every successful call
   double tail_ms[2][4] = {};   // [published?]: left bookkeeping, previous frames' right tails, this frame's right tail, the rest
   uint64_t phase_count[2] = {0, 0};
   uint64_t phase_frames = 0, tr_cand = 0, tr_new = 0, tr_detect = 0, tr_surv = 0;

@@ -566,20 +566,15 @@ struct TrackCall {
   int set_st = 0;             // copy of set 1 where the frame's stereo LK results of the kept points land
   std::vector<int> surv_src;  // chained stereo: survivor i was the temporal launch's point surv_src[i]
   int n_surv = 0, n_kept = 0;
-  clk::time_point tp;
+  PhaseClock clock;  // lap()'s; publish()'s parts and tails()'s trace intervals run on clocks of their own
 
   TrackCall(esvio_fe_ctx* ctx, double t, const esvio_fe_event* l, size_t nl, const esvio_fe_event* r, size_t nr,
             int sp, bool pub, const esvio_fe_motion* mo)
       : c(ctx), time(t), left(l), right(r), nL(nl), nR(nr), space(sp), PUB_THIS_FRAME(pub), motion(mo),
         M(ctx->cfg.max_cnt) {}
 
-  void lap(int i) {  // (always on: esvio_fe_latency_stats names the slowest call's phases)
-    const auto now = clk::now();
-    const double ms = std::chrono::duration<double, std::milli>(now - tp).count();
-    c->lat.cur_phase[i] += ms;
-    if (c->trace) c->phase_ms[PUB_THIS_FRAME ? 1 : 0][i] += ms;
-    tp = now;
-  }
+  // (always on: esvio_fe_latency_stats names the slowest call's phases)
+  void lap(Phase p) { c->lat.cur_phase[p] += clock.lap(); }
 
   bool same_motion(const Batch& a) const {  // (field by field: the struct has padding)
     if ((motion != nullptr) != a.has_motion) return false;
@@ -662,14 +657,14 @@ struct TrackCall {
       if (staged) {
         // not announced: the helpers and this thread stage the chunks together, the DMA of group k runs
         // under the memcpy of group k+1
-        const auto ts0 = clk::now();
+        PhaseClock staging;
         if (int rc = stager_begin(c, left, nL, right, nR, 4, &c->cur_stage, split)) return rc;
         if (split) {
           if (int rc = stager_attach_left(c, c->cur_stage, c->stream, &dL)) return rc;
         } else if (int rc = stager_attach(c, c->cur_stage, nL, c->stream, &dL, &dR)) {
           return rc;
         }
-        c->lat.cur_phase[15] = std::chrono::duration<double, std::milli>(clk::now() - ts0).count();  // (part of phase 0)
+        c->lat.cur_phase[PH_STAGE_HOST] = staging.lap();
       } else if (int rc = stage_events(c, left, nL, right, nR, space, &dL, &dR)) {
         return rc;
       }
@@ -685,10 +680,10 @@ struct TrackCall {
         HIPCHK(c, hipEventRecord(c->ev_imgs_ready, c->stream));
         // the right camera, on the stereo stream
         if (staged) {
-          const auto ts1 = clk::now();
+          PhaseClock staging;
           const EventRec* dl2 = nullptr;
           if (int rc = stager_attach(c, c->cur_stage, nL, stereo_stream(c), &dl2, &dR)) return rc;
-          c->lat.cur_phase[15] += std::chrono::duration<double, std::milli>(clk::now() - ts1).count();
+          c->lat.cur_phase[PH_STAGE_HOST] += staging.lap();
         }
         {
           StreamScope on_stereo_stream(stereo_stream(c));
@@ -818,21 +813,40 @@ struct TrackCall {
     return 0;
   }
 
+  // rejectWithF_event lifts prev_pts and cur_pts through the camera model before its RANSAC; prev_pts are known
+  // now, and the host is about to wait for the temporal LK anyway: their half of the lifts is done under that wait
+  // (a published frame's RANSAC sits on the replay cycle's critical chain)
+  void pre_lift() {
+    const esvio_fe_config& cfg = c->cfg;
+    const size_t n = c->prev_pts.size();
+    if (!PUB_THIS_FRAME || !cfg.f_ransac || n < 8 || c->pre_lift_valid) return;
+    c->pre_lx.resize(n);
+    c->pre_ly.resize(n);
+    host::lift_projective_batch(cfg.cam[0], &c->prev_pts[0].x, (int)n, c->pre_lx.data(), c->pre_ly.data());
+    c->pre_lift_valid = true;
+  }
+
+  // did a wave of the launch that works in block `block` of h_spec give up waiting?  (The word is cleared.)
+  bool take_expired(int block) { return std::exchange(*c->hspec[block].expired, 0) != 0; }
+
+  // The wait for a temporal LK an earlier call launched (the speculative one: block 0 of h_spec, the chained one:
+  // block 1), with what the host has to do anyway put under it.  *ok: every wave of it ran to its end.
+  int await_early(hipEvent_t done, int block, bool* ok) {
+    if (!defer_late)
+      if (int rc = early_work()) return rc;
+    pre_lift();
+    lap(PH_ENQ_TEMPORAL);
+    if (int rc = exchange_flush(c)) return rc;  // (host time that would be spent waiting)
+    HIPCHK(c, sync_event(done));
+    lap(PH_WAIT_TEMPORAL);
+    *ok = !take_expired(block);
+    return 0;
+  }
+
   int temporal() {  // :405-440
     if (int rc = plan_temporal()) return rc;
     const esvio_fe_config& cfg = c->cfg;
-    // rejectWithF_event lifts prev_pts and cur_pts through the camera model before its RANSAC; prev_pts are known
-    // now, and the host is about to wait for the temporal LK anyway: their half of the lifts is done under that wait
-    // (a published frame's RANSAC sits on the replay cycle's critical chain)
     c->pre_lift_valid = false;
-    auto pre_lift = [&]() {
-      const size_t n = c->prev_pts.size();
-      if (!PUB_THIS_FRAME || !cfg.f_ransac || n < 8 || c->pre_lift_valid) return;
-      c->pre_lx.resize(n);
-      c->pre_ly.resize(n);
-      host::lift_projective_batch(cfg.cam[0], &c->prev_pts[0].x, (int)n, c->pre_lx.data(), c->pre_ly.data());
-      c->pre_lift_valid = true;
-    };
     const PyrDesc& prevL = c->pyr[c->slot_prevL].d;
     const PyrDesc& curL = c->pyr[c->slot_curL].d;
     if (c->prev_pts.size() > 0) {
@@ -840,18 +854,9 @@ struct TrackCall {
       LkOut t{};  // where the temporal pair's results are read from
       bool spec_ok = false;
       if (use_spec) {
-        if (!defer_late)
-          if (int rc = early_work()) return rc;
-        pre_lift();
-        lap(1);
-        if (int rc = exchange_flush(c)) return rc;  // (host time that would be spent waiting)
-        HIPCHK(c, sync_event(c->ev_spec_done));
-        lap(2);
+        if (int rc = await_early(c->ev_spec_done, 0, &spec_ok)) return rc;
         t = c->hspec[0].out;
-        int* wait_expired = c->hspec[0].expired;
-        spec_ok = *wait_expired == 0;  // (a wave gave up waiting for k_select: redo the launch below)
-        *wait_expired = 0;
-        if (!spec_ok) {
+        if (!spec_ok) {  // (a wave gave up waiting for k_select: redo the launch below)
           c->n_spec_expired++;
           // its waves have ended without results; nothing of it may still be running when the same
           // points go through the plain launch below
@@ -861,16 +866,7 @@ struct TrackCall {
       std::vector<P2f> g_ptsB, g_ptsC;
       std::vector<uint8_t> g_stA, g_stB;
       if (use_chain) {
-        if (!defer_late)
-          if (int rc = early_work()) return rc;
-        pre_lift();
-        lap(1);
-        if (int rc = exchange_flush(c)) return rc;
-        HIPCHK(c, sync_event(c->ev_chain_done));
-        lap(2);
-        int* wait_expired = c->hspec[1].expired;
-        spec_ok = *wait_expired == 0;
-        *wait_expired = 0;
+        if (int rc = await_early(c->ev_chain_done, 1, &spec_ok)) return rc;
         c->tr_chain_used += spec_ok;
         if (!spec_ok) c->n_chain_expired++;
         if (c->trace && spec_ok) trace_chain_intervals();
@@ -923,9 +919,9 @@ struct TrackCall {
         if (int rc = early_work()) return rc;
         if (int rc = exchange_flush(c)) return rc;
         pre_lift();
-        lap(1);
+        lap(PH_ENQ_TEMPORAL);
         HIPCHK(c, sync_main(c));
-        lap(2);
+        lap(PH_WAIT_TEMPORAL);
         t = pin.s1;
       }
       std::vector<uint8_t> status(t.st_fwd, t.st_fwd + n);
@@ -1017,7 +1013,7 @@ struct TrackCall {
     n_surv = (int)c->cur_pts.size();
     c->src_idx.resize(n_surv);
     for (int i = 0; i < n_surv; i++) c->src_idx[i] = stereo_chained ? surv_src[i] : i;
-    lap(3);
+    lap(PH_FILTER);
     n_kept = n_surv;
     // the next batch's pyramids are in flight on the prefetch stream: next frame's temporal LK can be
     // launched as soon as this frame's points are final
@@ -1048,17 +1044,11 @@ struct TrackCall {
     const PyrDesc& curR = c->pyr[c->slot_curR].d;
     if (PUB_THIS_FRAME) {
       if (cfg.f_ransac) reject_with_f_event(c);
-      lap(4);
-      auto tq = clk::now();
-      auto sub = [&](int i) {
-        const auto now = clk::now();
-        const double ms = std::chrono::duration<double, std::milli>(now - tq).count();
-        c->lat.cur_phase[8 + i] += ms;
-        if (c->trace) c->pub_ms[i] += ms;
-        tq = now;
-      };
+      lap(PH_RANSAC);
+      PhaseClock parts;  // (of PH_MASK_DETECT)
+      auto sub = [&](Phase p) { c->lat.cur_phase[p] += parts.lap(); };
       event_set_mask(c);
-      sub(0);
+      sub(PH_PUB_SETMASK);
       // (a plain call's Arc* pass ran on the prefetch stream: the selection, and whatever the next call
       // puts on the main stream, follow it)
       if (arc_side) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_arc_side, 0));
@@ -1083,11 +1073,11 @@ struct TrackCall {
         }
         run_select(c, c->cand_cur, n_max_cnt, (float2*)zpin.news, n_kept, nullptr, nullptr, zpin.counts, will_spec,
                    (const float2*)zpin.news, n_kept);
-        sub(1);
+        sub(PH_PUB_SELECT);
         if (will_spec)
           if (const Inflight* nb = next_batch())
             if (int rc = enqueue_spec_temporal(c, *nb, n_kept, true)) return rc;
-        sub(2);
+        sub(PH_PUB_SPEC);
         // the selection result is in host memory once k_select is done: an event right behind it lets
         // the left-camera bookkeeping below run under the stereo LK of the new corners
         HIPCHK(c, hipEventRecord(c->ev_sel_host, cur_stream(c)));
@@ -1098,20 +1088,20 @@ struct TrackCall {
         if (!c->pend_right.active || c->pend_right.left.empty() ||
             (!c->lazy_late && event_over(c->ev_lks_done[c->pend_right.set])))
           if (int rc = finalize_right(c)) return rc;
-        sub(3);
+        sub(PH_PUB_PREV_RIGHT);
         // stereo LK of the new corners only (count known on the device)
         if (split_right) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_right_ready, 0));  // (the right image)
         run_lk_pair(c, lk_pair(curL, curR, zpin.news + n_kept, c->dres.counts, n_max_cnt, kLkStereo, zpin.s2));
         if (c->lazy_new) HIPCHK(c, hipEventRecord(c->ev_lknew_done, cur_stream(c)));
-        sub(4);
+        sub(PH_PUB_STEREO_NEW);
       }
       if (defer_late)
         if (int rc = early_work()) return rc;
-      sub(5);
+      sub(PH_PUB_PREFETCH);
     } else if (defer_late) {
       if (int rc = early_work()) return rc;
     }
-    lap(5);
+    lap(PH_MASK_DETECT);
     if (detect) HIPCHK(c, sync_event(c->ev_sel_host));
     return 0;
   }
@@ -1135,17 +1125,13 @@ struct TrackCall {
         c->track_cnt.push_back(1);
       }
     }
-    auto tt = clk::now();
-    auto tail_lap = [&](int i) {
-      if (!c->trace) return;
-      const auto now = clk::now();
-      c->tail_ms[PUB_THIS_FRAME ? 1 : 0][i] += std::chrono::duration<double, std::milli>(now - tt).count();
-      tt = now;
-    };
+    const int pub = PUB_THIS_FRAME ? 1 : 0;
+    PhaseClock tt;
+    auto tail_lap = [&](int i) { if (c->trace) c->tail_ms[pub][i] += tt.lap(); };
     c->cur_un_pts = undistorted_pts(c->cur_pts, cfg.cam[0]);  // :470-473
     c->pts_velocity = pts_velocity_fn(c->ids, c->cur_un_pts, c->cur_un_pts_map, c->prev_un_pts_map,
                                       c->cur_time - c->prev_time, c->cur_pts.size());
-    lap(7);
+    lap(PH_TAIL);
     tail_lap(0);
     const bool lazy = c->lazy_new && detect;      // leave this frame's new corners to the next call
     const bool defer_right = c->lazy_new && !PUB_THIS_FRAME;  // ... or its whole right-camera tail
@@ -1169,12 +1155,10 @@ struct TrackCall {
       if (!lazy) HIPCHK(c, sync_main(c));  // stereo LK results of the new corners
       if (n_surv || stereo_chained) HIPCHK(c, sync_event(c->ev_lks_done[c->res_set]));  // ... of the kept points
       if (stereo_chained) {
-        int* wait_expired = c->hspec[1].expired;
-        if (*wait_expired != 0) {
+        if (take_expired(1)) {
           // a wave of the chained stereo launch gave up waiting for its point: the same launch the plain
           // way, from the temporal forward results (still in this frame's copy of set 1; a point the
           // filters dropped is tracked for nothing, as in the chained launch)
-          *wait_expired = 0;
           c->n_chain_expired++;
           const int n = (int)surv_src.size() ? surv_src.back() + 1 : 0;
           if (n) {
@@ -1187,8 +1171,8 @@ struct TrackCall {
         }
       }
     }
-    lap(6);
-    tt = clk::now();
+    lap(PH_WAIT_STEREO);
+    tt = PhaseClock();
     if (!defer_right && (n_surv || detect))
       if (int rc = lookback_expired(c)) return rc;
 
@@ -1216,7 +1200,7 @@ struct TrackCall {
     c->prev_un_pts_map.swap(c->cur_un_pts_map);
     c->prev_time = c->cur_time;
     c->spec_n = (int)c->prev_pts.size();
-    lap(7);
+    lap(PH_TAIL);
     if (c->cur_stage >= 0) {  // the staging slot of this batch's host events is free for another batch
       if (main_reads_events)
         if (int rc = stager_mark_read(c, c->cur_stage, c->stream, true)) return rc;
@@ -1231,7 +1215,9 @@ struct TrackCall {
     // scratch — follows the right camera's chain
     if (split_right) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_right_ready, 0));
     c->phase_frames++;
-    c->phase_count[PUB_THIS_FRAME ? 1 : 0]++;
+    c->phase_count[pub]++;
+    if (c->trace)
+      for (int i = 0; i < PH_COUNT; i++) c->trace_phase_ms[pub][i] += c->lat.cur_phase[i];
     c->tr_surv += (uint64_t)n_surv;
     if (c->prof_on) resolve_profile(c);
     // esvio_fe_set_auto_exchange: what an earlier published frame left to enqueue goes out now at the
@@ -1303,7 +1289,7 @@ int track_event_impl(esvio_fe_ctx* c, double _cur_time, const esvio_fe_event* le
                      const esvio_fe_event* right, size_t nR, int space, bool PUB_THIS_FRAME,
                      const esvio_fe_motion* motion) {
   TrackCall t(c, _cur_time, left, nL, right, nR, space, PUB_THIS_FRAME, motion);
-  const auto t0 = clk::now();
+  const auto t0 = t.clock.t = clk::now();
   const int cpu0 = sched_getcpu();
   const long sw0 = thread_invol_switches();
   const uint64_t allocs0 = c->n_allocs;
@@ -1324,11 +1310,10 @@ int track_event_impl(esvio_fe_ctx* c, double _cur_time, const esvio_fe_event* le
   t.zpin = c->zpin[c->res_set];
   if (PUB_THIS_FRAME && c->pool) host::ransac_pool_wake(c->pool);
   c->cur_time = _cur_time;
-  t.tp = clk::now();
-  c->lat.cur_phase[14] = std::chrono::duration<double, std::milli>(t.tp - t0).count();
+  c->lat.cur_phase[PH_CHECK] = t.clock.lap();
   int rc = t.take_batch();
   if (!rc) {
-    t.lap(0);
+    t.lap(PH_ENQ_BATCH);
     rc = t.temporal();
   }
   if (!rc) rc = t.survivors_stereo();

@@ -123,7 +123,7 @@ LATENCY_PHASES = 16
 
 class LatencyCall(C.Structure):  # esvio_fe_latency_call
     _fields_ = [("call", C.c_uint64), ("published", C.c_int32), ("reserved", C.c_int32), ("begin_ms", C.c_double),
-                ("ms", C.c_double), ("phase_ms", C.c_double * 16)]
+                ("ms", C.c_double), ("phase_ms", C.c_double * LATENCY_PHASES)]
 
 
 class Latency(C.Structure):  # esvio_fe_latency

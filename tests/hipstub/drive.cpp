@@ -52,6 +52,32 @@ struct Batch {
   std::vector<esvio_fe_event> L, R;
   double t;
 };
+
+// The latest call's latency record: identities of the bookkeeping, whatever the clock read (1e-6 ms: the rounding of
+// summed clock differences).  Phases 8..13 are parts of phase 5 and of published calls only, 15 is part of 0, and
+// 0..7 with 14 lie end to end inside the call.
+static bool latency_record_ok(esvio_fe_handle h, int pub) {
+  esvio_fe_latency_call r;
+  if (esvio_fe_latency_recent(h, 0, &r) != ESVIO_FE_OK) return false;
+  double main_sum = r.phase_ms[14], pub_sum = 0;
+  bool ok = r.published == (pub != 0);
+  for (int i = 0; i < ESVIO_FE_LATENCY_PHASES; i++) {
+    ok = ok && r.phase_ms[i] >= 0;
+    if (i < 8) main_sum += r.phase_ms[i];
+    else if (i < 14) pub_sum += r.phase_ms[i];
+    const char* name = esvio_fe_latency_phase_name(i);
+    ok = ok && name[0] != 0;
+    for (int k = 0; k < i; k++) ok = ok && strcmp(name, esvio_fe_latency_phase_name(k)) != 0;
+  }
+  ok = ok && (pub ? pub_sum <= r.phase_ms[5] + 1e-6 : pub_sum == 0) && r.phase_ms[15] <= r.phase_ms[0] + 1e-6 &&
+       main_sum <= r.ms + 1e-6;
+  if (!ok) {
+    fprintf(stderr, "latency record of call %llu (%s, %.6f ms):", (unsigned long long)r.call, pub ? "published" : "unpublished", r.ms);
+    for (int i = 0; i < ESVIO_FE_LATENCY_PHASES; i++) fprintf(stderr, " %d=%.6f", i, r.phase_ms[i]);
+    fprintf(stderr, "\n");
+  }
+  return ok;
+}
 static void make_batch(Batch& b, int W, int H, int frame, int n) {
   b.L.resize((size_t)n);
   b.R.resize((size_t)n * 3 / 4);
@@ -488,6 +514,7 @@ int main(int argc, char** argv) {
         announced = i;
       } else {
         fold_tracks(t);
+        if (!latency_record_ok(h, pub[(size_t)i])) return 4;
       }
       if (rnd() % 17u == 0 && esvio_fe_finish(h, &t) == ESVIO_FE_OK) fold_tracks(t);
     }
