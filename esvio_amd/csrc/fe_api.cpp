@@ -562,6 +562,27 @@ int esvio_fe_export_image(esvio_fe_handle c, int cam, uint8_t* dst, int space) {
   return 0;
 }
 
+int esvio_fe_export_level(esvio_fe_handle c, int cam, int level, uint8_t* img, int16_t* deriv, int32_t* w,
+                          int32_t* hgt, int32_t* levels) {
+  if (!c || (cam != 0 && cam != 1)) return ESVIO_FE_EINVAL;
+  HIPCHK(c, hipSetDevice(c->dev));
+  if (!c->announced.empty() || !c->inflight.empty()) return fail(c, ESVIO_FE_EINVAL, "a prefetched batch is pending");
+  if (int rc = finalize_lazy(c)) return rc;
+  const PyrDesc& d = cam ? c->pyr[c->slot_curR].d : c->pyr[c->slot_curL].d;
+  if (level < 0 || level > d.levels) return fail(c, ESVIO_FE_EINVAL, "level %d of a pyramid of %d", level, d.levels + 1);
+  if (w) *w = d.w[level];
+  if (hgt) *hgt = d.h[level];
+  if (levels) *levels = d.levels;
+  // (the padded planes from their origin, without the bytes between the padded width and the row stride)
+  const size_t pw = (size_t)d.w[level] + 2 * kPad, ph = (size_t)d.h[level] + 2 * kPad, stride = d.stride[level];
+  if (img) HIPCHK(c, hipMemcpy2DAsync(img, pw, d.img[level], stride, pw, ph, hipMemcpyDeviceToHost, cur_stream(c)));
+  if (deriv)
+    HIPCHK(c, hipMemcpy2DAsync(deriv, pw * 4, d.deriv[level], stride * 4, pw * 4, ph, hipMemcpyDeviceToHost,
+                               cur_stream(c)));
+  HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  return 0;
+}
+
 int esvio_fe_import_image(esvio_fe_handle c, int cam, const uint8_t* src, int space) {
   if (!c || !src) return ESVIO_FE_EINVAL;
   if (cam != 1) return fail(c, ESVIO_FE_EINVAL, "only the right camera's image can be imported");

@@ -50,6 +50,11 @@ __device__ __forceinline__ int reflect101(int p, int len) {
   return p >= len ? 2 * len - 2 - p : p;
 }
 
+// The source of a pixel of a level's kPad-wide border ring, p in [-kPad, len + kPad): BORDER_REFLECT_101 folded twice.
+// One fold leaves p > 2 len - 2 negative, which happens where len <= kPad (a top level may be 22 to 24 wide or high: a
+// level is kept while both sides exceed kLkWin); two folds are total for len >= 13.
+__device__ __forceinline__ int reflect101_ring(int p, int len) { return reflect101(reflect101(p, len), len); }
+
 // trackEvent's per-event gate (feature_tracker.cpp:627-641) + createSAE_* with
 // Motion_correction_value (event_detector.cc:102-147): the pixel an in-sensor event is written at.
 // t0 = left.events[0].ts.toSec() (:621) is read from the batch itself, dt = header stamp - t0 (:623).
@@ -1532,6 +1537,7 @@ __global__ __launch_bounds__(256) void k_clahe_lut(ClaheArgs a) {
   const uint8_t* src = a.raw[img];
   for (int p = tid; p < area; p += 256) {
     const int py = p / tw, px = p - py * tw;
+    // (at most 8 past the image: EW - W <= 8 <= W - 2, inside reflect101's range)
     const int y = reflect101(ty * th + py, H), x = reflect101(tx * tw + px, W);
     atomicAdd(&hist[src[(size_t)y * a.raw_stride + x]], 1);
   }
@@ -1688,11 +1694,11 @@ __global__ __launch_bounds__(256) void k_pyr_down(PyrPack pk, int src_level) {
   const int wk[5] = {1, 4, 6, 4, 1};
   int xs[5];
 #pragma unroll
-  for (int k = 0; k < 5; k++) xs[k] = reflect101(2 * x + k - 2, sw);
+  for (int k = 0; k < 5; k++) xs[k] = reflect101(2 * x + k - 2, sw);  // (-2 .. sw + 2: inside its range, sw >= 22)
   int acc = 0;
 #pragma unroll
   for (int ky = 0; ky < 5; ky++) {
-    const uint8_t* row = src + (size_t)reflect101(2 * y + ky - 2, sh) * sstride;
+    const uint8_t* row = src + (size_t)reflect101(2 * y + ky - 2, sh) * sstride;  // (-2 .. sh + 2: as for x)
     int r = 0;
 #pragma unroll
     for (int kx = 0; kx < 5; kx++) r += wk[kx] * (int)row[xs[kx]];
@@ -1728,12 +1734,12 @@ __device__ __forceinline__ void fused_down(const uint8_t* __restrict__ src_l, ui
     if (x < 0 || y < 0 || x >= dw || y >= dh) continue;
     int xs[5];
 #pragma unroll
-    for (int k = 0; k < 5; k++) xs[k] = reflect101(2 * x + k - 2, sw) - sox;
+    for (int k = 0; k < 5; k++) xs[k] = reflect101(2 * x + k - 2, sw) - sox;  // (-2 .. sw + 2: inside its range)
     const int wk[5] = {1, 4, 6, 4, 1};
     int acc = 0;
 #pragma unroll
     for (int ky = 0; ky < 5; ky++) {
-      const uint8_t* row = src_l + (reflect101(2 * y + ky - 2, sh) - soy) * SS;
+      const uint8_t* row = src_l + (reflect101(2 * y + ky - 2, sh) - soy) * SS;  // (-2 .. sh + 2: inside its range)
       int r = 0;
 #pragma unroll
       for (int kx = 0; kx < 5; kx++) r += wk[kx] * (int)row[xs[kx]];
@@ -1872,7 +1878,7 @@ __global__ __launch_bounds__(256) void k_pyr_pad(PyrPack pk) {
       y += kPad;
       x += kPad + w;
     }
-    const int sx = reflect101(x - kPad, w), sy = reflect101(y - kPad, h);
+    const int sx = reflect101_ring(x - kPad, w), sy = reflect101_ring(y - kPad, h);
     uint8_t* img = p.img[level];
     img[(size_t)y * stride + x] = img[(size_t)(sy + kPad) * stride + sx + kPad];
   }
@@ -1918,8 +1924,8 @@ __global__ __launch_bounds__(256) void k_pad_scharr(PyrPack pk, int n_scharr) {
     const int total = w * h;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += n_scharr * 256) {
       const int y = i / w, x = i - y * w;
-      const int xm = reflect101(x - 1, w), xp = reflect101(x + 1, w);
-      const uint8_t* r0 = img + (size_t)reflect101(y - 1, h) * stride;
+      const int xm = reflect101(x - 1, w), xp = reflect101(x + 1, w);  // (-1 .. w: inside its range)
+      const uint8_t* r0 = img + (size_t)reflect101(y - 1, h) * stride;  // (-1 .. h: inside its range)
       const uint8_t* r1 = img + (size_t)y * stride;
       const uint8_t* r2 = img + (size_t)reflect101(y + 1, h) * stride;
       const int a0 = r0[xm], a1 = r0[x], a2 = r0[xp];
@@ -1956,7 +1962,7 @@ __global__ __launch_bounds__(256) void k_pad_scharr(PyrPack pk, int n_scharr) {
       y += kPad;
       x += kPad + w;
     }
-    const int sx = reflect101(x - kPad, w), sy = reflect101(y - kPad, h);
+    const int sx = reflect101_ring(x - kPad, w), sy = reflect101_ring(y - kPad, h);
     uint8_t* img = p.img[level];
     img[(size_t)y * stride + x] = img[(size_t)(sy + kPad) * stride + sx + kPad];
   }
@@ -3424,6 +3430,7 @@ __global__ __launch_bounds__(256) void k_gftt_rowsum(GfttArgs a) {
   const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (x >= a.W || y >= a.H) return;
   const float4* r = a.cov + (size_t)y * a.W;
+  // (-1 .. W: inside reflect101's range)
   const float4 l = r[reflect101(x - 1, a.W)], c = r[x], rr = r[reflect101(x + 1, a.W)];
   a.rowsum[(size_t)y * a.W + x] =
       make_float4(__fadd_rn(__fadd_rn(l.x, c.x), rr.x), __fadd_rn(__fadd_rn(l.y, c.y), rr.y),
@@ -3435,7 +3442,7 @@ __global__ __launch_bounds__(64) void k_gftt_eig(GfttArgs a) {
   const int x = blockIdx.x * 64 + threadIdx.x;
   if (x >= a.W) return;
   const int W = a.W, H = a.H;
-  auto row = [&](int y) { return a.rowsum[(size_t)reflect101(y, H) * W + x]; };
+  auto row = [&](int y) { return a.rowsum[(size_t)reflect101(y, H) * W + x]; };  // (called with -1 .. H: inside its range)
   float4 prev = row(-1), cur = row(0);
   float s0 = __fadd_rn(__fadd_rn(0.f, prev.x), cur.x), s1 = __fadd_rn(__fadd_rn(0.f, prev.y), cur.y),
         s2 = __fadd_rn(__fadd_rn(0.f, prev.z), cur.z);

@@ -109,6 +109,7 @@ ABI_SYMBOLS = [
 # test / measurement taps: include/esvio_fe_test.h (not part of the boundary)
 TEST_SYMBOLS = [
     "esvio_fe_build_pyramid", "esvio_fe_debug_counters", "esvio_fe_debug_inject", "esvio_fe_device_memory",
+    "esvio_fe_export_level",
     "esvio_fe_find_fundamental_mat_held", "esvio_fe_find_fundamental_mat_idle", "esvio_fe_find_fundamental_mat_mt",
     "esvio_fe_get_kernel_stats", "esvio_fe_host_hypot", "esvio_fe_host_nullspace", "esvio_fe_host_stage_copy",
     "esvio_fe_host_stage_pack", "esvio_fe_staging_counters",
@@ -201,6 +202,7 @@ def load_library(build_if_missing=True):
     L.esvio_fe_get_time_surface.argtypes = [vp, i, vp]
     L.esvio_fe_export_image.argtypes = [vp, i, vp, i]
     L.esvio_fe_import_image.argtypes = [vp, i, vp, i]
+    L.esvio_fe_export_level.argtypes = [vp, i, i, vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.esvio_fe_fast_corners.argtypes = [vp, i, vp, i, i, i, i, vp, vp, C.c_int32, C.POINTER(C.c_int32),
                                         C.POINTER(C.c_int32)]
     L.esvio_fe_set_detector.argtypes = [vp, i, i]
@@ -281,6 +283,7 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+PAD = 24  # kPad (fe_kernels.h): the border kept around every pyramid level
 DETECT_ARC, DETECT_FAST = 0, 1  # esvio_fe_set_detector
 FAULT_TICKET, FAULT_LOOKBACK, FAULT_SPECULATIVE, FAULT_CHAINED, FAULT_LAZY_LATE = 1, 2, 4, 8, 16
 
@@ -735,6 +738,18 @@ class FeatureTracker:
             return out
         self._hd.check(self._hd.L.esvio_fe_export_image(self._hd.h, cam, C.c_void_p(int(dst)), DEVICE))
         return None
+
+    def export_level(self, cam, level):
+        """level `level` of the pyramid in the current slot of `cam`, with its border (esvio_fe_export_level) ->
+        (image (h + 2 PAD, w + 2 PAD) u8, derivatives (h + 2 PAD, w + 2 PAD, 2) int16, the handle's top level)"""
+        w, h, top = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        self._hd.check(self._hd.L.esvio_fe_export_level(self._hd.h, cam, level, None, None, C.byref(w), C.byref(h),
+                                                        C.byref(top)))
+        im = np.empty((h.value + 2 * PAD, w.value + 2 * PAD), np.uint8)
+        dv = np.empty((h.value + 2 * PAD, w.value + 2 * PAD, 2), np.int16)
+        self._hd.check(self._hd.L.esvio_fe_export_level(self._hd.h, cam, level, _p(im), _p(dv), C.byref(w), C.byref(h),
+                                                        C.byref(top)))
+        return im, dv, top.value
 
     def import_image(self, cam, src):
         """numpy (H,W) u8 or device pointer (int): right image for the next trackEvent"""

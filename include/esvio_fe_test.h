@@ -102,6 +102,13 @@ int esvio_fe_set_sae(esvio_fe_handle h, int cam, const double* L0, const double*
 int esvio_fe_build_pyramid(esvio_fe_handle h, const uint8_t* img, int w, int hgt, int max_level,
                            int level, uint8_t* out_img, int16_t* out_deriv, int32_t* lw,
                            int32_t* lh, int32_t* n_levels);
+/* test tap: one level of the pyramid the last track call (or esvio_fe_sae_to_time_surface: level 0 only) left in the
+ * current slot of `cam` (0 left, 1 right: the slots esvio_fe_export_image reads), WITH its border: (h_l + 48) rows of
+ * (w_l + 48) image bytes into img, as many interleaved (Ix, Iy) int16 pairs into deriv (either may be NULL); *w, *hgt =
+ * w_l, h_l, *levels = the handle's top level.  Copies and a wait for the stream only, no launch.  ESVIO_FE_EINVAL for
+ * a bad cam or level and while batches are announced or in flight; what a lazy call left open is completed first. */
+int esvio_fe_export_level(esvio_fe_handle h, int cam, int level, uint8_t* img, int16_t* deriv, int32_t* w,
+                          int32_t* hgt, int32_t* levels);
 /* camodocal PinholeCamera::liftProjective (PinholeCamera.cc:450-510); host-side. */
 int esvio_fe_lift_projective(const esvio_fe_camera* cam, double u, double v, double* out3);
 
