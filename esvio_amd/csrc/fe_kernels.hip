@@ -55,6 +55,11 @@ __device__ __forceinline__ int reflect101(int p, int len) {
 // level is kept while both sides exceed kLkWin); two folds are total for len >= 13.
 __device__ __forceinline__ int reflect101_ring(int p, int len) { return reflect101(reflect101(p, len), len); }
 
+// cv::saturate_cast<uchar>(int)
+__device__ __forceinline__ uint8_t sat_u8(int v) {
+  return (uint8_t)((unsigned)v <= 255u ? v : v > 0 ? 255 : 0);
+}
+
 // trackEvent's per-event gate (feature_tracker.cpp:627-641) + createSAE_* with
 // Motion_correction_value (event_detector.cc:102-147): the pixel an in-sensor event is written at.
 // t0 = left.events[0].ts.toSec() (:621) is read from the batch itself, dt = header stamp - t0 (:623).
@@ -1445,7 +1450,7 @@ __device__ __forceinline__ uint8_t ts_pixel(double2 s, double t_sync, double dec
     const double r = rint(sc);
     iv = (r > 2147483647.0 || r < -2147483648.0) ? INT_MIN : (int)r;
   }
-  return (uint8_t)((unsigned)iv <= 255u ? iv : iv > 0 ? 255 : 0);
+  return sat_u8(iv);
 }
 
 __global__ __launch_bounds__(256) void k_time_surface(const double2* __restrict__ S2, int W,
@@ -1505,6 +1510,7 @@ KernelId launch_time_surface(hipStream_t s, const double2* S2, int W, int H, dou
 // core/norm.cpp].  One block per tile builds the clipped-histogram LUT; one thread per pixel blends
 // the four neighbouring LUTs and tracks the image min/max; a third pass rescales to 0..255.
 constexpr int kClaheTiles = 8;
+constexpr int kClaheLut = kClaheTiles * kClaheTiles * 256;  // one image's LUTs: [tile][256]
 
 struct ClaheArgs {
   const uint8_t* raw[2];  // pixel (0,0) of the raw time surfaces
@@ -1512,21 +1518,32 @@ struct ClaheArgs {
   uint8_t* dst[2];        // pixel (0,0) of the LK level-0 images
   int dst_stride;
   int W, H;
-  uint8_t* lut;           // [nimg][64][256]
+  uint8_t* lut;           // [nimg][kClaheLut]
   int* minmax;            // [nimg][2]
 };
+
+// The tile size.  An image that is not a multiple of the tile count on BOTH sides is extended on
+// both sides (by reflect-101, to the right and below), a side that already divides by a full
+// kClaheTiles.
+struct ClaheGeom {
+  int tw, th;
+};
+__device__ __forceinline__ ClaheGeom clahe_geom(int W, int H) {
+  int EW = W, EH = H;
+  if (!(W % kClaheTiles == 0 && H % kClaheTiles == 0)) {
+    EW = W + (kClaheTiles - (W % kClaheTiles));
+    EH = H + (kClaheTiles - (H % kClaheTiles));
+  }
+  return {EW / kClaheTiles, EH / kClaheTiles};
+}
 
 __global__ __launch_bounds__(256) void k_clahe_lut(ClaheArgs a) {
   __shared__ int hist[256];
   __shared__ int part[4];
   const int img = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
   const int W = a.W, H = a.H;
-  int EW = W, EH = H;
-  if (!(W % kClaheTiles == 0 && H % kClaheTiles == 0)) {
-    EW = W + (kClaheTiles - (W % kClaheTiles));
-    EH = H + (kClaheTiles - (H % kClaheTiles));
-  }
-  const int tw = EW / kClaheTiles, th = EH / kClaheTiles, area = tw * th;
+  const auto [tw, th] = clahe_geom(W, H);
+  const int area = tw * th;
   const int ty = tile / kClaheTiles, tx = tile - ty * kClaheTiles;
   hist[tid] = 0;
   if (tile == 0 && tid == 0) {
@@ -1573,20 +1590,15 @@ __global__ __launch_bounds__(256) void k_clahe_lut(ClaheArgs a) {
   for (int w = 0; w < (tid >> 6); w++) sum += part[w];
   const float lutScale = (float)255 / (float)area;
   const int r = __float2int_rn((float)sum * lutScale);
-  a.lut[((size_t)img * 64 + tile) * 256 + tid] = (uint8_t)((unsigned)r <= 255u ? r : r > 0 ? 255 : 0);
+  a.lut[(size_t)img * kClaheLut + tile * 256 + tid] = sat_u8(r);
 }
 
 __global__ __launch_bounds__(256) void k_clahe_interp(ClaheArgs a) {
   const int img = blockIdx.y;
   const int W = a.W, H = a.H;
-  int EW = W, EH = H;
-  if (!(W % kClaheTiles == 0 && H % kClaheTiles == 0)) {
-    EW = W + (kClaheTiles - (W % kClaheTiles));
-    EH = H + (kClaheTiles - (H % kClaheTiles));
-  }
-  const int tw = EW / kClaheTiles, th = EH / kClaheTiles;
+  const auto [tw, th] = clahe_geom(W, H);
   const float inv_tw = 1.0f / tw, inv_th = 1.0f / th;
-  const uint8_t* lut = a.lut + (size_t)img * 64 * 256;
+  const uint8_t* lut = a.lut + (size_t)img * kClaheLut;
   int mn = 255, mx = 0;
   // (a bounded grid walks the image: the launch ends with one atomic pair per block on the image's
   // two extreme words, and a few hundred of those are cheap where thousands serialise at L2)
@@ -1605,11 +1617,11 @@ __global__ __launch_bounds__(256) void k_clahe_interp(ClaheArgs a) {
     tx1 = max(tx1, 0);
     tx2 = min(tx2, kClaheTiles - 1);
     const int v = a.raw[img][(size_t)y * a.raw_stride + x];
-    const float l11 = lut[(ty1 * 8 + tx1) * 256 + v], l12 = lut[(ty1 * 8 + tx2) * 256 + v];
-    const float l21 = lut[(ty2 * 8 + tx1) * 256 + v], l22 = lut[(ty2 * 8 + tx2) * 256 + v];
+    const int t1 = ty1 * kClaheTiles, t2 = ty2 * kClaheTiles;
+    const float l11 = lut[(t1 + tx1) * 256 + v], l12 = lut[(t1 + tx2) * 256 + v];
+    const float l21 = lut[(t2 + tx1) * 256 + v], l22 = lut[(t2 + tx2) * 256 + v];
     const float res = (l11 * xa1 + l12 * xa) * ya1 + (l21 * xa1 + l22 * xa) * ya;
-    const int r = __float2int_rn(res);
-    const int res8 = (unsigned)r <= 255u ? r : r > 0 ? 255 : 0;
+    const int res8 = sat_u8(__float2int_rn(res));
     a.dst[img][(size_t)y * a.dst_stride + x] = (uint8_t)res8;
     mn = min(mn, res8);
     mx = max(mx, res8);
@@ -1638,18 +1650,32 @@ __global__ __launch_bounds__(256) void k_clahe_interp(ClaheArgs a) {
   }
 }
 
+// cv::normalize(., 0, 255, NORM_MINMAX) of a u8 image whose extremes are in
+// minmax[2 img .. 2 img + 1] [OpenCV core/norm.cpp, convertTo]: scale and shift are computed in
+// double and each rounded to float once.  (The shift taken in float from the rounded scale,
+// -(float)smin * a, is another float for most (smin, smax) and moves bytes next to a rounding
+// tie: 1830 pairs, KERNELS.md.)
+struct NormCoef {
+  float a, b;
+};
+__device__ __forceinline__ NormCoef norm_coef(const int* minmax, int img) {
+  const double smin = minmax[2 * img], smax = minmax[2 * img + 1];
+  const double scale = 255.0 * (__dsub_rn(smax, smin) > 2.2204460492503131e-16 ? 1. / __dsub_rn(smax, smin) : 0);
+  const double shift = __dsub_rn(0.0, __dmul_rn(smin, scale));
+  return {(float)scale, (float)shift};
+}
+__device__ __forceinline__ uint8_t norm_px(uint8_t v, const NormCoef& c) {
+  return sat_u8(__float2int_rn(__fadd_rn(__fmul_rn((float)v, c.a), c.b)));
+}
+
 __global__ __launch_bounds__(256) void k_normalize(ClaheArgs a) {
   const int img = blockIdx.y;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= a.W * a.H) return;
-  const double smin = a.minmax[2 * img], smax = a.minmax[2 * img + 1];
-  const double scale = 255.0 * (__dsub_rn(smax, smin) > 2.2204460492503131e-16 ? 1. / __dsub_rn(smax, smin) : 0);
-  const double shift = __dsub_rn(0.0, __dmul_rn(smin, scale));
-  const float fa = (float)scale, fb = (float)shift;
+  const NormCoef nc = norm_coef(a.minmax, img);
   const int y = i / a.W, x = i - y * a.W;
   uint8_t* p = a.dst[img] + (size_t)y * a.dst_stride + x;
-  const int r = __float2int_rn(__fadd_rn(__fmul_rn((float)*p, fa), fb));
-  *p = (uint8_t)((unsigned)r <= 255u ? r : r > 0 ? 255 : 0);
+  *p = norm_px(*p, nc);
 }
 
 void launch_clahe(hipStream_t s, const uint8_t* raw0, const uint8_t* raw1, int raw_stride,
@@ -1668,7 +1694,7 @@ void launch_clahe(hipStream_t s, const uint8_t* raw0, const uint8_t* raw1, int r
   a.minmax = minmax;
   const int nb = (W * H + 255) / 256;
   if (stage == 0)
-    launch_k(k_clahe_lut, dim3(64, nimg), dim3(256), 0, s, a);
+    launch_k(k_clahe_lut, dim3(kClaheTiles * kClaheTiles, nimg), dim3(256), 0, s, a);
   else if (stage == 1)
     launch_k(k_clahe_interp, dim3(nb < 256 ? nb : 256, nimg), dim3(256), 0, s, a);
   else
@@ -1682,6 +1708,28 @@ struct PyrPack {
 
 // cv::pyrDown u8 [OpenCV imgproc/pyramids.cpp]: [1 4 6 4 1]x[1 4 6 4 1], (sum+128)>>8,
 // BORDER_REFLECT_101, dst size ((w+1)/2,(h+1)/2). Reads the source interior only.
+// Pixel (x, y) of the destination, from an sw x sh source whose pixel (sox, soy) is at src: the
+// whole level in HBM with (0, 0), or a tile of it in LDS with the tile's origin — the reflection
+// is taken at the level's own size.  (Offsets are ints: a level's sh * stride is far below 2^31,
+// as is the W * H every kernel here counts pixels with.)
+__device__ __forceinline__ uint8_t pyr_down_px(const uint8_t* __restrict__ src, int stride, int sox,
+                                               int soy, int sw, int sh, int x, int y) {
+  const int wk[5] = {1, 4, 6, 4, 1};
+  int xs[5];  // (-2 .. sw + 2: inside reflect101's range, sw >= 22)
+#pragma unroll
+  for (int k = 0; k < 5; k++) xs[k] = reflect101(2 * x + k - 2, sw) - sox;
+  int acc = 0;
+#pragma unroll
+  for (int ky = 0; ky < 5; ky++) {
+    const uint8_t* row = src + (reflect101(2 * y + ky - 2, sh) - soy) * stride;  // (as for x)
+    int r = 0;
+#pragma unroll
+    for (int kx = 0; kx < 5; kx++) r += wk[kx] * (int)row[xs[kx]];
+    acc += wk[ky] * r;
+  }
+  return (uint8_t)((acc + 128) >> 8);
+}
+
 __global__ __launch_bounds__(256) void k_pyr_down(PyrPack pk, int src_level) {
   const PyrDesc& p = pk.p[blockIdx.z];
   const int sw = p.w[src_level], sh = p.h[src_level];
@@ -1691,20 +1739,8 @@ __global__ __launch_bounds__(256) void k_pyr_down(PyrPack pk, int src_level) {
   if (x >= dw || y >= dh) return;
   const int sstride = p.stride[src_level], dstride = p.stride[src_level + 1];
   const uint8_t* src = p.img[src_level] + (size_t)kPad * sstride + kPad;
-  const int wk[5] = {1, 4, 6, 4, 1};
-  int xs[5];
-#pragma unroll
-  for (int k = 0; k < 5; k++) xs[k] = reflect101(2 * x + k - 2, sw);  // (-2 .. sw + 2: inside its range, sw >= 22)
-  int acc = 0;
-#pragma unroll
-  for (int ky = 0; ky < 5; ky++) {
-    const uint8_t* row = src + (size_t)reflect101(2 * y + ky - 2, sh) * sstride;  // (-2 .. sh + 2: as for x)
-    int r = 0;
-#pragma unroll
-    for (int kx = 0; kx < 5; kx++) r += wk[kx] * (int)row[xs[kx]];
-    acc += wk[ky] * r;
-  }
-  p.img[src_level + 1][(size_t)(y + kPad) * dstride + x + kPad] = (uint8_t)((acc + 128) >> 8);
+  p.img[src_level + 1][(size_t)(y + kPad) * dstride + x + kPad] =
+      pyr_down_px(src, sstride, 0, 0, sw, sh, x, y);
 }
 
 static PyrPack make_pack(const PyrDesc* p, int nimg);
@@ -1714,7 +1750,7 @@ static PyrPack make_pack(const PyrDesc* p, int nimg);
 // prefetch stream's dependent chain).  A block owns an 8x4 tile of level 3 = 16x8 of level 2 =
 // 32x16 of level 1 = 64x32 of level 0 and recomputes the halo the 5x5 kernels need (85x53 level-0
 // pixels rendered per block, x2.2 the owned ones — fp64 exp is cheap next to three launches), level
-// by level through LDS.  Per pixel the arithmetic is ts_pixel resp. k_pyr_down's, reflect-101 taken at
+// by level through LDS.  Per pixel the arithmetic is ts_pixel resp. pyr_down_px, reflect-101 taken at
 // each level's own size, so every byte equals the unfused kernels' output.
 constexpr int kFt3x = 8, kFt3y = 4;
 constexpr int kFt2x = 2 * kFt3x + 3, kFt2y = 2 * kFt3y + 3;  // 19 x 11
@@ -1723,7 +1759,7 @@ constexpr int kFt0x = 2 * kFt1x + 3, kFt0y = 2 * kFt1y + 3;  // 85 x 53
 constexpr int kFs0 = 88, kFs1 = 44, kFs2 = 20;               // LDS row strides
 constexpr int kFtThreads = 1024;  // 16 waves per block: the fp64 exp chains need the latency hiding
 
-template <int SRX, int SS, int DRX, int DRY, int DS>
+template <int SS, int DRX, int DRY, int DS>
 __device__ __forceinline__ void fused_down(const uint8_t* __restrict__ src_l, uint8_t* __restrict__ dst_l,
                                            int sox, int soy, int sw, int sh, int dox, int doy, int dw,
                                            int dh, uint8_t* __restrict__ dst_img, int dstride, int ownx0,
@@ -1732,20 +1768,7 @@ __device__ __forceinline__ void fused_down(const uint8_t* __restrict__ src_l, ui
     const int ry = i / DRX, rx = i - ry * DRX;
     const int x = dox + rx, y = doy + ry;
     if (x < 0 || y < 0 || x >= dw || y >= dh) continue;
-    int xs[5];
-#pragma unroll
-    for (int k = 0; k < 5; k++) xs[k] = reflect101(2 * x + k - 2, sw) - sox;  // (-2 .. sw + 2: inside its range)
-    const int wk[5] = {1, 4, 6, 4, 1};
-    int acc = 0;
-#pragma unroll
-    for (int ky = 0; ky < 5; ky++) {
-      const uint8_t* row = src_l + (reflect101(2 * y + ky - 2, sh) - soy) * SS;  // (-2 .. sh + 2: inside its range)
-      int r = 0;
-#pragma unroll
-      for (int kx = 0; kx < 5; kx++) r += wk[kx] * (int)row[xs[kx]];
-      acc += wk[ky] * r;
-    }
-    const uint8_t v = (uint8_t)((acc + 128) >> 8);
+    const uint8_t v = pyr_down_px(src_l, SS, sox, soy, sw, sh, x, y);
     if (dst_l) dst_l[ry * DS + rx] = v;
     if (x >= ownx0 && x < ownx0 + ownw && y >= owny0 && y < owny0 + ownh)
       dst_img[(size_t)(y + kPad) * dstride + x + kPad] = v;
@@ -1754,7 +1777,7 @@ __device__ __forceinline__ void fused_down(const uint8_t* __restrict__ src_l, ui
 
 // FROM_IMG: level 0 is not rendered from the SAE but is cv::normalize(., 0, 255, NORM_MINMAX) of an
 // existing u8 image (the CLAHE output of the `equalize: 1` branch, k_clahe_interp) whose extremes are
-// in minmax[2 cam .. 2 cam + 1] — k_normalize's arithmetic per pixel — so that branch, too, goes from
+// in minmax[2 cam .. 2 cam + 1] — norm_px per pixel, as k_normalize — so that branch, too, goes from
 // its level-0 source to the four pyramid levels in one launch.
 struct EqSrc {
   const uint8_t* img[2];  // pixel (0,0) of the two un-normalised images
@@ -1778,43 +1801,36 @@ __device__ __forceinline__ void pyr3_body(const EqSrc& eq, const PyrPack& pk) {
   const int o2x = 2 * o3x - 2, o2y = 2 * o3y - 2;
   const int o1x = 2 * o2x - 2, o1y = 2 * o2y - 2;
   const int o0x = 2 * o1x - 2, o0y = 2 * o1y - 2;
-  constexpr int kN0 = kFt0x * kFt0y;
   constexpr bool FROM_IMG = MODE == 1;
-  if (MODE == 2) {
-    const uint8_t* src = p.img[0] + (size_t)kPad * p.stride[0] + kPad;
-    for (int i = threadIdx.x; i < kN0; i += kFtThreads) {
-      const int ry = i / kFt0x, rx = i - ry * kFt0x;
-      const int x = o0x + rx, y = o0y + ry;
-      if (x < 0 || y < 0 || x >= W || y >= H) continue;
-      l0[ry * kFs0 + rx] = src[(size_t)y * p.stride[0] + x];
-    }
-  }
-  if (FROM_IMG) {
-    const double smin = eq.minmax[2 * cam], smax = eq.minmax[2 * cam + 1];
-    const double scale = 255.0 * (__dsub_rn(smax, smin) > 2.2204460492503131e-16 ? 1. / __dsub_rn(smax, smin) : 0);
-    const float fa = (float)scale, fb = (float)__dsub_rn(0.0, __dmul_rn(smin, scale));
-    const uint8_t* src = eq.img[cam];
-    for (int i = threadIdx.x; i < kN0; i += kFtThreads) {
-      const int ry = i / kFt0x, rx = i - ry * kFt0x;
-      const int x = o0x + rx, y = o0y + ry;
-      if (x < 0 || y < 0 || x >= W || y >= H) continue;
-      const int r = __float2int_rn(__fadd_rn(__fmul_rn((float)src[(size_t)y * eq.stride + x], fa), fb));
-      const uint8_t v = (uint8_t)((unsigned)r <= 255u ? r : r > 0 ? 255 : 0);
-      l0[ry * kFs0 + rx] = v;
+  // this block's level-0 tile: copied from the level in place, or normalised from eq's image and,
+  // where the block owns the pixel, stored to the level as well
+  uint8_t* lvl0 = p.img[0] + (size_t)kPad * p.stride[0] + kPad;
+  const uint8_t* src = FROM_IMG ? eq.img[cam] : lvl0;
+  const int sstride = FROM_IMG ? eq.stride : p.stride[0];
+  NormCoef nc{};
+  if (FROM_IMG) nc = norm_coef(eq.minmax, cam);
+  for (int i = threadIdx.x; i < kFt0x * kFt0y; i += kFtThreads) {
+    const int ry = i / kFt0x, rx = i - ry * kFt0x;
+    const int x = o0x + rx, y = o0y + ry;
+    if (x < 0 || y < 0 || x >= W || y >= H) continue;
+    uint8_t v = src[(size_t)y * sstride + x];
+    if (FROM_IMG) {
+      v = norm_px(v, nc);
       if (x >= 8 * o3x && x < 8 * o3x + 8 * kFt3x && y >= 8 * o3y && y < 8 * o3y + 8 * kFt3y)
-        p.img[0][(size_t)(y + kPad) * p.stride[0] + x + kPad] = v;
+        lvl0[(size_t)y * p.stride[0] + x] = v;
     }
+    l0[ry * kFs0 + rx] = v;
   }
   __syncthreads();
-  fused_down<kFt0x, kFs0, kFt1x, kFt1y, kFs1>(l0, l1, o0x, o0y, W, H, o1x, o1y, p.w[1], p.h[1], p.img[1],
-                                               p.stride[1], 4 * o3x, 4 * o3y, 4 * kFt3x, 4 * kFt3y);
+  fused_down<kFs0, kFt1x, kFt1y, kFs1>(l0, l1, o0x, o0y, W, H, o1x, o1y, p.w[1], p.h[1], p.img[1],
+                                       p.stride[1], 4 * o3x, 4 * o3y, 4 * kFt3x, 4 * kFt3y);
   __syncthreads();
-  fused_down<kFt1x, kFs1, kFt2x, kFt2y, kFs2>(l1, l2, o1x, o1y, p.w[1], p.h[1], o2x, o2y, p.w[2], p.h[2],
-                                               p.img[2], p.stride[2], 2 * o3x, 2 * o3y, 2 * kFt3x,
-                                               2 * kFt3y);
+  fused_down<kFs1, kFt2x, kFt2y, kFs2>(l1, l2, o1x, o1y, p.w[1], p.h[1], o2x, o2y, p.w[2], p.h[2],
+                                       p.img[2], p.stride[2], 2 * o3x, 2 * o3y, 2 * kFt3x,
+                                       2 * kFt3y);
   __syncthreads();
-  fused_down<kFt2x, kFs2, kFt3x, kFt3y, kFt3x>(l2, nullptr, o2x, o2y, p.w[2], p.h[2], o3x, o3y, p.w[3],
-                                                p.h[3], p.img[3], p.stride[3], o3x, o3y, kFt3x, kFt3y);
+  fused_down<kFs2, kFt3x, kFt3y, kFt3x>(l2, nullptr, o2x, o2y, p.w[2], p.h[2], o3x, o3y, p.w[3],
+                                        p.h[3], p.img[3], p.stride[3], o3x, o3y, kFt3x, kFt3y);
 }
 
 __global__ __launch_bounds__(kFtThreads) void k_norm_pyr(EqSrc eq, PyrPack pk) {
@@ -1845,127 +1861,99 @@ void launch_norm_pyr(hipStream_t s, const uint8_t* src0, const uint8_t* src1, in
            make_pack(p, 2));
 }
 
-// copyMakeBorder(level, BORDER_REFLECT_101) for every level [OpenCV buildOpticalFlowPyramid]
+// copyMakeBorder(level, BORDER_REFLECT_101) for every level [OpenCV buildOpticalFlowPyramid].
+// Only the border ring is enumerated: the top and the bottom band (pw * kPad each), then the left
+// and the right one (kPad * h each).
+struct RingGeom {
+  int pw, band, side;
+  __host__ __device__ int total() const { return 2 * band + 2 * side; }
+};
+__host__ __device__ inline RingGeom ring_geom(int w, int h) {
+  const int pw = w + 2 * kPad;
+  return {pw, pw * kPad, kPad * h};
+}
+
+// ring elements first, first + step, ... of a level
+__device__ __forceinline__ void ring_fill(const PyrDesc& p, int level, int first, int step) {
+  const int w = p.w[level], h = p.h[level], stride = p.stride[level];
+  const RingGeom g = ring_geom(w, h);
+  uint8_t* img = p.img[level];
+  for (int i = first; i < g.total(); i += step) {
+    int x, y;
+    if (i < g.band) {
+      y = i / g.pw;
+      x = i - y * g.pw;
+    } else if (i < 2 * g.band) {
+      const int j = i - g.band;
+      y = j / g.pw;
+      x = j - y * g.pw;
+      y += kPad + h;
+    } else if (i < 2 * g.band + g.side) {
+      const int j = i - 2 * g.band;
+      y = j / kPad;
+      x = j - y * kPad;
+      y += kPad;
+    } else {
+      const int j = i - 2 * g.band - g.side;
+      y = j / kPad;
+      x = j - y * kPad;
+      y += kPad;
+      x += kPad + w;
+    }
+    const int sx = reflect101_ring(x - kPad, w), sy = reflect101_ring(y - kPad, h);
+    img[(size_t)y * stride + x] = img[(size_t)(sy + kPad) * stride + sx + kPad];
+  }
+}
+
 __global__ __launch_bounds__(256) void k_pyr_pad(PyrPack pk) {
   const PyrDesc& p = pk.p[blockIdx.z];
   const int level = blockIdx.y;
   if (level > p.levels) return;
-  const int w = p.w[level], h = p.h[level];
-  const int pw = w + 2 * kPad, ph = h + 2 * kPad, stride = p.stride[level];
-  // enumerate only the border ring: top+bottom bands (pw*kPad each), then left+right bands
-  const int band = pw * kPad;
-  const int side = kPad * h;
-  const int total = 2 * band + 2 * side;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-    int x, y;
-    if (i < band) {
-      y = i / pw;
-      x = i - y * pw;
-    } else if (i < 2 * band) {
-      const int j = i - band;
-      y = j / pw;
-      x = j - y * pw;
-      y += kPad + h;
-    } else if (i < 2 * band + side) {
-      const int j = i - 2 * band;
-      y = j / kPad;
-      x = j - y * kPad;
-      y += kPad;
-    } else {
-      const int j = i - 2 * band - side;
-      y = j / kPad;
-      x = j - y * kPad;
-      y += kPad;
-      x += kPad + w;
-    }
-    const int sx = reflect101_ring(x - kPad, w), sy = reflect101_ring(y - kPad, h);
-    uint8_t* img = p.img[level];
-    img[(size_t)y * stride + x] = img[(size_t)(sy + kPad) * stride + sx + kPad];
-  }
-  (void)ph;
+  ring_fill(p, level, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
 }
 
 // calcSharrDeriv [OpenCV video/lkpyramid.cpp]: Ix = [3 10 3]^T (x) [-1 0 1],
-// Iy = [-1 0 1]^T (x) [3 10 3], REFLECT_101 (read from the padded image), int16 interleaved.
+// Iy = [-1 0 1]^T (x) [3 10 3], REFLECT_101, int16 interleaved; pixels first, first + step, ...
+// of a level.  An edge pixel takes its neighbours by reflect-101 from the interior (= the values
+// the border ring holds or is about to receive), so the ring need not have been filled.
+__device__ __forceinline__ void scharr_fill(const PyrDesc& p, int level, int first, int step) {
+  const int w = p.w[level], h = p.h[level], stride = p.stride[level];
+  const uint8_t* img = p.img[level] + (size_t)kPad * stride + kPad;
+  int* deriv = (int*)(p.deriv[level]) + (size_t)kPad * stride + kPad;
+  for (int i = first; i < w * h; i += step) {
+    const int y = i / w, x = i - y * w;
+    const int xm = reflect101(x - 1, w), xp = reflect101(x + 1, w);  // (-1 .. w: inside its range)
+    const int o = y * stride;  // (an int, as the w * h above)
+    const uint8_t* r0 = img + reflect101(y - 1, h) * stride;  // (-1 .. h: inside its range)
+    const uint8_t* r1 = img + o;
+    const uint8_t* r2 = img + reflect101(y + 1, h) * stride;
+    const int a0 = r0[xm], a1 = r0[x], a2 = r0[xp];
+    const int b0 = r1[xm], b2 = r1[xp];
+    const int c0 = r2[xm], c1 = r2[x], c2 = r2[xp];
+    const int ix = ((a2 + c2) * 3 + b2 * 10) - ((a0 + c0) * 3 + b0 * 10);
+    const int iy = ((c2 - a2) + (c0 - a0)) * 3 + (c1 - a1) * 10;
+    deriv[o + x] = (int)(((unsigned)(uint16_t)(int16_t)iy << 16) | (uint16_t)(int16_t)ix);
+  }
+}
+
 __global__ __launch_bounds__(256) void k_scharr(PyrPack pk) {
   const PyrDesc& p = pk.p[blockIdx.z];
   const int level = blockIdx.y;
   if (level > p.levels) return;
-  const int w = p.w[level], h = p.h[level];
-  const int stride = p.stride[level];
-  const uint8_t* img = p.img[level] + (size_t)kPad * stride + kPad;
-  int* deriv = (int*)(p.deriv[level]) + (size_t)kPad * stride + kPad;
-  const int total = w * h;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-    const int y = i / w, x = i - y * w;
-    const uint8_t* r0 = img + (ptrdiff_t)(y - 1) * stride + x;
-    const uint8_t* r1 = r0 + stride;
-    const uint8_t* r2 = r1 + stride;
-    const int a0 = r0[-1], a1 = r0[0], a2 = r0[1];
-    const int b0 = r1[-1], b2 = r1[1];
-    const int c0 = r2[-1], c1 = r2[0], c2 = r2[1];
-    const int ix = ((a2 + c2) * 3 + b2 * 10) - ((a0 + c0) * 3 + b0 * 10);
-    const int iy = ((c2 - a2) + (c0 - a0)) * 3 + (c1 - a1) * 10;
-    deriv[(size_t)y * stride + x] = (int)(((unsigned)(uint16_t)(int16_t)iy << 16) | (uint16_t)(int16_t)ix);
-  }
+  scharr_fill(p, level, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
 }
 
-// k_pyr_pad and k_scharr in one launch: the derivative of an edge pixel takes its neighbours by
-// reflect-101 from the interior (= the values the border ring is about to receive), so the two
-// parts do not depend on each other; blocks [0, n_scharr) differentiate, the rest fill the ring.
+// k_pyr_pad and k_scharr in one launch: the two parts do not depend on each other (see
+// scharr_fill); blocks [0, n_scharr) differentiate, the rest fill the ring.
 __global__ __launch_bounds__(256) void k_pad_scharr(PyrPack pk, int n_scharr) {
   const PyrDesc& p = pk.p[blockIdx.z];
   const int level = blockIdx.y;
   if (level > p.levels) return;
-  const int w = p.w[level], h = p.h[level], stride = p.stride[level];
-  if ((int)blockIdx.x < n_scharr) {
-    const uint8_t* img = p.img[level] + (size_t)kPad * stride + kPad;
-    int* deriv = (int*)(p.deriv[level]) + (size_t)kPad * stride + kPad;
-    const int total = w * h;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += n_scharr * 256) {
-      const int y = i / w, x = i - y * w;
-      const int xm = reflect101(x - 1, w), xp = reflect101(x + 1, w);  // (-1 .. w: inside its range)
-      const uint8_t* r0 = img + (size_t)reflect101(y - 1, h) * stride;  // (-1 .. h: inside its range)
-      const uint8_t* r1 = img + (size_t)y * stride;
-      const uint8_t* r2 = img + (size_t)reflect101(y + 1, h) * stride;
-      const int a0 = r0[xm], a1 = r0[x], a2 = r0[xp];
-      const int b0 = r1[xm], b2 = r1[xp];
-      const int c0 = r2[xm], c1 = r2[x], c2 = r2[xp];
-      const int ix = ((a2 + c2) * 3 + b2 * 10) - ((a0 + c0) * 3 + b0 * 10);
-      const int iy = ((c2 - a2) + (c0 - a0)) * 3 + (c1 - a1) * 10;
-      deriv[(size_t)y * stride + x] = (int)(((unsigned)(uint16_t)(int16_t)iy << 16) | (uint16_t)(int16_t)ix);
-    }
-    return;
-  }
-  const int n_pad = gridDim.x - n_scharr;
-  const int pw = w + 2 * kPad;
-  const int band = pw * kPad, side = kPad * h, total = 2 * band + 2 * side;
-  for (int i = ((int)blockIdx.x - n_scharr) * 256 + threadIdx.x; i < total; i += n_pad * 256) {
-    int x, y;
-    if (i < band) {
-      y = i / pw;
-      x = i - y * pw;
-    } else if (i < 2 * band) {
-      const int j = i - band;
-      y = j / pw;
-      x = j - y * pw;
-      y += kPad + h;
-    } else if (i < 2 * band + side) {
-      const int j = i - 2 * band;
-      y = j / kPad;
-      x = j - y * kPad;
-      y += kPad;
-    } else {
-      const int j = i - 2 * band - side;
-      y = j / kPad;
-      x = j - y * kPad;
-      y += kPad;
-      x += kPad + w;
-    }
-    const int sx = reflect101_ring(x - kPad, w), sy = reflect101_ring(y - kPad, h);
-    uint8_t* img = p.img[level];
-    img[(size_t)y * stride + x] = img[(size_t)(sy + kPad) * stride + sx + kPad];
-  }
+  if ((int)blockIdx.x < n_scharr)
+    scharr_fill(p, level, blockIdx.x * 256 + threadIdx.x, n_scharr * 256);
+  else
+    ring_fill(p, level, ((int)blockIdx.x - n_scharr) * 256 + threadIdx.x,
+              ((int)gridDim.x - n_scharr) * 256);
 }
 
 static PyrPack make_pack(const PyrDesc* p, int nimg) {
@@ -1981,15 +1969,13 @@ void launch_pyr_down(hipStream_t s, const PyrDesc* p, int nimg, int src_level) {
                      make_pack(p, nimg), src_level);
 }
 void launch_pyr_pad(hipStream_t s, const PyrDesc* p, int nimg) {
-  const int pw = p[0].w[0] + 2 * kPad;
-  const int total = 2 * pw * kPad + 2 * kPad * p[0].h[0];
+  const int total = ring_geom(p[0].w[0], p[0].h[0]).total();
   launch_k(k_pyr_pad, dim3((total + 255) / 256, p[0].levels + 1, nimg), dim3(256), 0, s,
                      make_pack(p, nimg));
 }
 void launch_pad_scharr(hipStream_t s, const PyrDesc* p, int nimg) {
   const int n_scharr = (p[0].w[0] * p[0].h[0] + 255) / 256;
-  const int pw = p[0].w[0] + 2 * kPad;
-  const int n_pad = (2 * pw * kPad + 2 * kPad * p[0].h[0] + 255) / 256;
+  const int n_pad = (ring_geom(p[0].w[0], p[0].h[0]).total() + 255) / 256;
   launch_k(k_pad_scharr, dim3(n_scharr + n_pad, p[0].levels + 1, nimg), dim3(256), 0, s,
            make_pack(p, nimg), n_scharr);
 }
