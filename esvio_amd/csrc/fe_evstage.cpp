@@ -59,26 +59,53 @@ inline void stage_copy(uint8_t* dst, const uint8_t* src, size_t len) {
   std::memcpy(dst, src, len);
 }
 
+// nanoseconds since t0, as the stager's counters keep them; NsScope adds a scope's to one (cf. PhaseClock, fe_ctx.h)
+using Clock = std::chrono::steady_clock;
+inline uint64_t ns_since(Clock::time_point t0) { return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(Clock::now() - t0).count(); }
+struct NsScope {
+  uint64_t& sum;
+  Clock::time_point t0 = Clock::now();
+  ~NsScope() { sum += ns_since(t0); }
+};
+
 // The same chunk as 8 bytes per event, when its events allow it: x | y << 16 as they are, nsec (30 bits) | polarity
 // (!= 0, as every kernel reads it) << 30 | (sec - base) << 31 with base = the chunk's first event's second — so a
 // chunk may cross ONE second boundary forwards; anything else (stamps going backwards across a second, nsec >= 2^30)
-// and the caller copies the chunk raw instead.  Returns whether the packed form was written (dst: the first len / 2
-// bytes of the chunk's place in the pinned buffer); *base_sec: the second the offsets count from.
+// and the caller copies the chunk raw instead.
+// Whether the n events at src allow it.  Reads only: the OR over the records of their 32-bit lanes — x | y << 16,
+// sec - base, nsec, polarity byte | padding — says it all
+inline bool stage_packable(const uint8_t* src, size_t n, uint32_t base) {
+  uint32_t acc[4] = {0, 0, 0, 0};
+#ifdef ESVIO_STAGE_NT
+  const __m128i b = _mm_set_epi32(0, 0, (int)base, 0);
+  __m128i v = _mm_setzero_si128();
+  for (size_t i = 0; i < n; i++) v = _mm_or_si128(v, _mm_sub_epi32(_mm_loadu_si128((const __m128i*)(src + 16 * i)), b));
+  _mm_storeu_si128((__m128i*)acc, v);
+#else
+  for (size_t i = 0; i < n; i++) {
+    uint32_t r[4];
+    std::memcpy(r, src + 16 * i, 16);
+    acc[1] |= r[1] - base;
+    acc[2] |= r[2];
+  }
+#endif
+  return ((acc[1] >> 1) | (acc[2] >> 30)) == 0;
+}
+// Decides first, writes afterwards: returns whether the packed form was written (dst: the first len / 2 bytes of the
+// chunk's place in the pinned buffer) — a refused chunk leaves dst as it was.  *base_sec: the second the offsets count from.
 inline bool stage_pack(uint8_t* dst, const uint8_t* src, size_t len, uint32_t* base_sec) {
   const size_t n = len / 16;
   if (!n || (len & 15u) || ((uintptr_t)dst & 15u)) return false;
-  uint64_t a0;
-  std::memcpy(&a0, src, 8);
-  const uint32_t base = (uint32_t)(a0 >> 32);
-  uint64_t bad = 0;
+  uint32_t base;
+  std::memcpy(&base, src + 4, 4);
+  *base_sec = base;
+  if (!stage_packable(src, n, base)) return false;
   size_t i = 0;
   auto pack1 = [&](const uint8_t* p) -> uint64_t {
     uint64_t a, b;  // a = x | y << 16 | sec << 32;  b = nsec | polarity byte << 32 | padding
     std::memcpy(&a, p, 8);
     std::memcpy(&b, p + 8, 8);
-    const uint32_t nsec = (uint32_t)b, off = (uint32_t)(a >> 32) - base;
-    bad |= (uint64_t)(nsec >> 30) | (uint64_t)(off >> 1);
-    const uint32_t hi = nsec | (((b >> 32) & 0xffu) ? 1u << 30 : 0u) | (off << 31);
+    const uint32_t hi = (uint32_t)b | (((b >> 32) & 0xffu) ? 1u << 30 : 0u) | (((uint32_t)(a >> 32) - base) << 31);
     return (a & 0xffffffffull) | ((uint64_t)hi << 32);
   };
 #ifdef ESVIO_STAGE_NT
@@ -86,19 +113,18 @@ inline bool stage_pack(uint8_t* dst, const uint8_t* src, size_t len, uint32_t* b
     const uint64_t lo = pack1(src + 16 * i), hi = pack1(src + 16 * i + 16);
     _mm_stream_si128((__m128i*)(dst + 8 * i), _mm_set_epi64x((long long)hi, (long long)lo));
   }
+  _mm_sfence();
 #endif
   for (; i < n; i++) {
     const uint64_t v = pack1(src + 16 * i);
     std::memcpy(dst + 8 * i, &v, 8);
   }
-#ifdef ESVIO_STAGE_NT
-  _mm_sfence();
-#endif
-  *base_sec = base;
-  return bad == 0;
+  return true;
 }
 constexpr size_t kChunkBytes = 256 * 1024;
 constexpr int kMaxGroups = 8;
+// (by camera the calling thread waits for the left array: smaller pieces, more threads on it at once)
+inline size_t chunk_bytes(bool by_camera) { return by_camera ? kChunkBytes / 4 : kChunkBytes; }
 
 struct Group {
   size_t off = 0, len = 0;  // byte range of the slot's buffers that one DMA moves
@@ -107,15 +133,17 @@ struct Group {
   std::atomic<bool> dma_enq{false};  // the group's DMA has been enqueued (at least once)
 };
 
-// one memcpy into a slot's pinned buffer.  st: 0 not taken, 1 taken, 2 done — whoever moves it from 1 to 2
-// accounts for the chunk (a helper, or the calling thread redoing the copy of a helper that went away)
+// one memcpy into a slot's pinned buffer.  Whoever moves it from TAKEN to DONE accounts for the chunk (a helper, or
+// the calling thread redoing the copy of a helper that went away)
+enum ChunkState : uint8_t { CH_FREE, CH_TAKEN, CH_DONE };
 struct Chunk {
   int group = 0;
   const uint8_t* src = nullptr;
   size_t off = 0, len = 0;  // byte offset inside the slot's buffers
-  std::atomic<uint8_t> st{0};
+  std::atomic<uint8_t> st{CH_FREE};
 };
 
+enum SlotState : int { SL_FAILED = -1, SL_IDLE, SL_STAGING, SL_SENT };  // SENT: every DMA enqueued and `copied` recorded
 struct Slot {
   std::unique_ptr<Chunk[]> chunk;
   size_t chunk_cap = 0;
@@ -139,21 +167,25 @@ struct Slot {
   bool pack = false;
   uint32_t pack_epc = 0;             // events per chunk
   PinBuf<uint32_t> desc;             // {base second, packed?} per chunk
-  std::chrono::steady_clock::time_point t_begin;  // (trace) when stager_begin opened the batch for taking
+  Clock::time_point t_begin;  // (trace) when stager_begin opened the batch for taking
   bool in_use = false;
-  std::atomic<int> state{0};  // 0 idle, 1 staging, 2 every DMA enqueued and `copied` recorded, -1 failed
+  std::atomic<int> state{SL_IDLE};
   Group grp[kMaxGroups];
   std::atomic<uint32_t> groups_left{0};
   std::atomic<int> busy{0};  // threads inside this slot's chunks (or about to take one)
+  bool staging() const { return state.load(std::memory_order_acquire) == SL_STAGING; }
 };
 }  // namespace
 
-// Work is handed out without a lock (a thread that loses its CPU while holding one would stop every
-// other thread for a scheduler quantum: profiles/r04_stall_forensics.md): a slot's chunks are numbered,
-// `next` is an atomic counter.  Everything a thread does for a chunk may be done twice — the copy writes
-// the same bytes, a group's DMA moves the same bytes, `copied` recorded again only moves the event
-// later — so the calling thread, when it waits for a batch (stager_attach), finishes whatever a helper
-// has started and not finished instead of waiting for that helper.
+// Work is handed out without a lock (a thread that loses its CPU while holding one would stop every other thread for a
+// scheduler quantum: profiles/r04_stall_forensics.md): a slot's chunks are numbered, `next` is an atomic counter.
+// Everything a thread does for a chunk may be done twice, so the calling thread, when it waits for a batch (wait_for),
+// finishes whatever a helper has started and not finished instead of waiting for that helper.  What makes twice
+// harmless: a chunk's bytes in the pinned buffer and its descriptor are functions of the caller's events alone, and
+// packed or raw is settled from the source BEFORE a byte is written (stage_pack) — so every thread that writes a place
+// writes the bytes that are published, and a transfer that reads it meanwhile reads those bytes whoever stored them; a
+// group's DMA moves the same bytes again; `copied` recorded again only moves the event later.  The counters are NOT
+// idempotent: they belong to the one thread that moves a chunk from TAKEN to DONE.
 // (the members release themselves, fe_res.h; stager_destroy deletes the stager once its threads have stopped and its
 // stream is idle, so their order carries no dependency)
 struct EventStager {
@@ -195,12 +227,12 @@ struct EventStager {
   bool dma(void* dst, const void* src, size_t len) {
     const uint32_t t = gate_n.fetch_add(1, std::memory_order_acq_rel);
     if (t >= 2) {
-      const auto tg0 = std::chrono::steady_clock::now();
+      const auto tg0 = Clock::now();
       const uint32_t w = (t - 2) & 3u;
       for (unsigned spin = 0;; spin++) {
         if (gate_rec[w].load(std::memory_order_acquire) == t - 1 && hipEventQuery(gate_ev[w]) == hipSuccess) break;
         (void)hipGetLastError();  // (hipErrorNotReady)
-        if ((spin & 15) == 15 && std::chrono::steady_clock::now() - tg0 > std::chrono::microseconds(400)) {
+        if ((spin & 15) == 15 && Clock::now() - tg0 > std::chrono::microseconds(400)) {
           gate_expired.fetch_add(1, std::memory_order_relaxed);
           break;
         }
@@ -223,11 +255,11 @@ struct EventStager {
         launch_stage_pull_packed(stream, s.pin + g.off, (uint8_t*)s.dev + g.off, g.len, s.desc + 2 * (size_t)g.first_chunk, s.pack_epc);
       else
         launch_stage_pull(stream, s.pin + g.off, (uint8_t*)s.dev + g.off, g.len);
-      if (hipGetLastError() != hipSuccess) s.state.store(-1, std::memory_order_release);
+      if (hipGetLastError() != hipSuccess) s.state.store(SL_FAILED, std::memory_order_release);
     } else {
       // an announced batch, staged whole frames ahead: one DMA (a 5 MB pull kernel on the copy stream costs the
       // compute streams 0.025 ms/step in replay mode, the copy engine nothing)
-      if (!dma((uint8_t*)s.dev + g.off, s.pin + g.off, g.len)) s.state.store(-1, std::memory_order_release);
+      if (!dma((uint8_t*)s.dev + g.off, s.pin + g.off, g.len)) s.state.store(SL_FAILED, std::memory_order_release);
     }
     g.dma_enq.store(true, std::memory_order_release);
     if ((int)(&g - s.grp) < s.n_left_groups) {
@@ -236,20 +268,19 @@ struct EventStager {
       bool all = true;
       for (int i = 0; i < s.n_left_groups; i++) all = all && s.grp[i].dma_enq.load(std::memory_order_acquire);
       if (all) {
-        if (c->trace) left_sent_ns.fetch_add((uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - s.t_begin).count());
-        if (hipEventRecord(s.copiedL, stream) != hipSuccess) s.state.store(-1, std::memory_order_release);
+        if (c->trace) left_sent_ns.fetch_add(ns_since(s.t_begin));
+        if (hipEventRecord(s.copiedL, stream) != hipSuccess) s.state.store(SL_FAILED, std::memory_order_release);
         s.left_enq.store(true, std::memory_order_release);
       }
     }
   }
   void finish_batch(Slot& s) {  // every group's DMA is enqueued: the event the compute streams wait for
-    if (c->trace) all_sent_ns.fetch_add((uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - s.t_begin).count());
-    const bool ok = hipEventRecord(s.copied, stream) == hipSuccess;
-    int expect = 1;
-    if (!ok)
-      s.state.store(-1, std::memory_order_release);
+    if (c->trace) all_sent_ns.fetch_add(ns_since(s.t_begin));
+    int expect = SL_STAGING;
+    if (hipEventRecord(s.copied, stream) != hipSuccess)
+      s.state.store(SL_FAILED, std::memory_order_release);
     else
-      (void)s.state.compare_exchange_strong(expect, 2, std::memory_order_acq_rel);  // (2 already: a redone batch)
+      (void)s.state.compare_exchange_strong(expect, SL_SENT, std::memory_order_acq_rel);  // (SENT already: a redone batch)
   }
 
   // the chunk is in the pinned buffer: its group's DMA if it was the group's last, the batch's event if
@@ -261,50 +292,53 @@ struct EventStager {
     if (s.groups_left.fetch_sub(1, std::memory_order_acq_rel) == 1) finish_batch(s);
   }
 
-  void run_chunk(Slot& s, uint32_t idx) {
-    Chunk& ch = s.chunk[idx];
-    uint8_t q = 0;
-    if (!ch.st.compare_exchange_strong(q, 1, std::memory_order_acq_rel)) return;  // (somebody else's already)
-    if (c->trace) {
-      const auto t0 = std::chrono::steady_clock::now();
-      if (idx == 0) first_take_ns.fetch_add((uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(t0 - s.t_begin).count());
-      stage_chunk(s, idx);
-      chunk_ns.fetch_add((uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count());
-      chunk_cnt.fetch_add(1);
-    } else {
-      stage_chunk(s, idx);
-    }
-    uint8_t taken = 1;
-    if (ch.st.compare_exchange_strong(taken, 2, std::memory_order_acq_rel)) chunk_done(s, ch);
-  }
-
-  // (idempotent like everything a chunk goes through: a chunk done twice writes the same bytes and the same descriptor)
-  void stage_chunk(Slot& s, uint32_t idx) {
-    Chunk& ch = s.chunk[idx];
+  // the chunk's bytes and descriptor into their pinned places — the same ones whoever does it and however often; returns whether packed
+  bool stage_chunk(Slot& s, uint32_t idx) {
+    const Chunk& ch = s.chunk[idx];
+    uint32_t base = 0;
+    const bool packed = s.pack && stage_pack(s.pin + ch.off, ch.src, ch.len, &base);
+    if (!packed) stage_copy(s.pin + ch.off, ch.src, ch.len);
     if (s.pack) {
-      uint32_t base = 0;
-      const bool packed = stage_pack(s.pin + ch.off, ch.src, ch.len, &base);
-      if (!packed) stage_copy(s.pin + ch.off, ch.src, ch.len);
       s.desc[2 * idx] = base;
       s.desc[2 * idx + 1] = packed ? 1u : 0u;
-      (packed ? chunks_packed : chunks_raw).fetch_add(1, std::memory_order_relaxed);
-      return;
     }
-    stage_copy(s.pin + ch.off, ch.src, ch.len);
+    return packed;
   }
 
-  // the calling thread while it waits for the LEFT array of slot k (by_camera): only that array's chunks — a
-  // right-array chunk taken now would keep it busy past the moment the left DMA is on its way
-  bool try_one_left(int k) {
-    Slot& s = slot[k];
-    if (s.state.load(std::memory_order_acquire) != 1 || s.next.load(std::memory_order_relaxed) >= s.n_left_chunks) return false;
+  // A TAKEN chunk (this thread's own, or a straggler's being redone) to DONE.  Returns whether this thread is the one
+  // that got it there: it counts the chunk and does what follows from its being in (chunk_done)
+  bool finish_chunk(Slot& s, uint32_t idx) {
+    const auto t0 = c->trace ? Clock::now() : Clock::time_point();
+    const bool packed = stage_chunk(s, idx);
+    if (c->trace) chunk_ns.fetch_add(ns_since(t0)), chunk_cnt.fetch_add(1);
+    Chunk& ch = s.chunk[idx];
+    uint8_t taken = CH_TAKEN;
+    if (!ch.st.compare_exchange_strong(taken, CH_DONE, std::memory_order_acq_rel)) return false;
+    if (s.pack) (packed ? chunks_packed : chunks_raw).fetch_add(1, std::memory_order_relaxed);
+    chunk_done(s, ch);
+    return true;
+  }
+
+  // Take and finish the slot's next chunk if its number is below `upper` (n_chunks: any chunk; n_left_chunks: the
+  // calling thread while it waits for the LEFT array — a right-array chunk taken then would keep it busy past the
+  // moment the left DMA is on its way).  `busy` goes up BEFORE the claim — stager_abandon / stager_release wait for
+  // it — and the slot may have been closed, or reopened for another batch, until it has: state and next are looked at again
+  bool take(Slot& s, uint32_t upper) {
+    auto open = [&] {
+      return s.staging() && s.next.load(std::memory_order_relaxed) < std::min(upper, s.n_chunks.load(std::memory_order_acquire));
+    };
+    if (!open()) return false;
     s.busy.fetch_add(1, std::memory_order_acq_rel);
     bool did = false;
-    if (s.state.load(std::memory_order_acquire) == 1 && s.next.load(std::memory_order_relaxed) < s.n_left_chunks) {
-      const uint32_t idx = s.next.fetch_add(1, std::memory_order_acq_rel);  // (may be a right chunk after all: run it)
+    if (open()) {
+      const uint32_t idx = s.next.fetch_add(1, std::memory_order_acq_rel);  // (may be >= upper after all, a right chunk: run it)
+      uint8_t q = CH_FREE;
       if (idx < s.n_chunks.load(std::memory_order_acquire)) {
         pending->fetch_sub(1, std::memory_order_acq_rel);
-        run_chunk(s, idx);
+        if (s.chunk[idx].st.compare_exchange_strong(q, CH_TAKEN, std::memory_order_acq_rel)) {  // (else: somebody else's already)
+          if (c->trace && idx == 0) first_take_ns.fetch_add(ns_since(s.t_begin));
+          finish_chunk(s, idx);
+        }
         did = true;
       }
     }
@@ -315,54 +349,51 @@ struct EventStager {
   // any thread: take one chunk of any batch being staged, if there is one
   bool try_one() {
     if (pending->load(std::memory_order_acquire) <= 0) return false;
-    for (Slot& s : slot) {
-      if (s.state.load(std::memory_order_acquire) != 1) continue;
-      s.busy.fetch_add(1, std::memory_order_acq_rel);  // (before the claim: stager_abandon / release wait for it)
-      bool did = false;
-      if (s.state.load(std::memory_order_acquire) == 1 &&
-          s.next.load(std::memory_order_relaxed) < s.n_chunks.load(std::memory_order_acquire)) {
-        const uint32_t idx = s.next.fetch_add(1, std::memory_order_acq_rel);
-        if (idx < s.n_chunks.load(std::memory_order_acquire)) {
-          pending->fetch_sub(1, std::memory_order_acq_rel);
-          run_chunk(s, idx);
-          did = true;
-        }
-      }
-      s.busy.fetch_sub(1, std::memory_order_acq_rel);
-      if (did) return true;
-    }
+    for (Slot& s : slot)
+      if (take(s, s.n_chunks.load(std::memory_order_acquire))) return true;
     return false;
   }
 
   // The calling thread, waiting for slot k with nothing left to take: whatever some helper has started
   // and not finished is done again here — a chunk taken and not copied, a complete group whose DMA is
-  // not enqueued, a complete batch whose event is not recorded.  Returns whether the batch is complete.
+  // not enqueued, a complete batch whose event is not recorded.
   void finish_for(int k) {
     Slot& s = slot[k];
     const uint32_t n = s.n_chunks.load(std::memory_order_acquire);
-    for (uint32_t i = 0; i < n; i++) {
-      Chunk& ch = s.chunk[i];
-      if (ch.st.load(std::memory_order_acquire) != 1) continue;
-      stage_chunk(s, i);
-      uint8_t taken = 1;
-      if (ch.st.compare_exchange_strong(taken, 2, std::memory_order_acq_rel)) {
-        chunk_done(s, ch);
-        redone++;
-      }
-    }
+    for (uint32_t i = 0; i < n; i++)
+      if (s.chunk[i].st.load(std::memory_order_acquire) == CH_TAKEN && finish_chunk(s, i)) redone++;
     bool all = true;
     for (int g = 0; g < s.n_groups; g++) {
       Group& gr = s.grp[g];
       if (gr.chunks_left.load(std::memory_order_acquire) != 0) {
         all = false;
-        continue;
-      }
-      if (!gr.dma_enq.load(std::memory_order_acquire)) {  // (its last chunk's thread has not got to it)
+      } else if (!gr.dma_enq.load(std::memory_order_acquire)) {  // (its last chunk's thread has not got to it)
         enqueue_dma(s, gr);
         redone++;
       }
     }
-    if (all && s.state.load(std::memory_order_acquire) == 1) finish_batch(s);
+    if (all && s.staging()) finish_batch(s);
+  }
+
+  // The calling thread until done() says so: it takes chunks itself (take_one) and, after ~25 us with nothing to
+  // take — some helper has started something and is not finishing it — redoes what is stuck in slot k instead of
+  // waiting for that helper.  Returns the chunks it took.
+  template <class Done, class Take>
+  uint64_t wait_for(int k, Done done, Take take_one) {
+    uint64_t took = 0;
+    unsigned idle = 0;
+    while (!done()) {
+      if (take_one()) {
+        took++;
+        idle = 0;
+      } else if (++idle > 1000) {
+        finish_for(k);
+        idle = 0;
+      } else {
+        cpu_relax();
+      }
+    }
+    return took;
   }
 
   void worker() {
@@ -468,8 +499,9 @@ static int slot_capacity(esvio_fe_ctx* c, Slot& s, size_t n) {
   return 0;
 }
 
-// the slot's chunk table (and, beside it, the pinned descriptor pairs of a packed batch) for `chunks` chunks
-static int slot_chunks(esvio_fe_ctx* c, Slot& s, size_t chunks) {
+// the slot's chunk table (and, beside it, the pinned descriptor pairs of a packed batch) for `bytes` in chunks of cb
+static int slot_chunks(esvio_fe_ctx* c, Slot& s, size_t bytes, size_t cb) {
+  const size_t chunks = (bytes + cb - 1) / cb;
   if (chunks + 4 > s.chunk_cap) {  // (+: a chunk never straddles the two source arrays)
     s.chunk_cap = chunks + 4 + chunks / 4;
     s.chunk.reset(new Chunk[s.chunk_cap]);
@@ -487,9 +519,134 @@ int stager_reserve(esvio_fe_ctx* c, size_t n_events) {
   for (Slot& s : st->slot)
     if (!s.in_use) {
       if (int rc = slot_capacity(c, s, n_events)) return rc;
-      const size_t chunks = (n_events * 16 + kChunkBytes / 4 - 1) / (kChunkBytes / 4);  // (the by-camera chunk size)
-      if (int rc = slot_chunks(c, s, chunks)) return rc;
+      if (int rc = slot_chunks(c, s, n_events * 16, chunk_bytes(true))) return rc;
     }
+  return 0;
+}
+
+struct BatchSrc {  // ---- stager_begin, step by step.  What the caller hands over:
+  const uint8_t *left, *right;
+  size_t bL, bR;     // bytes of the two arrays: the left one's place in the slot's buffers is [0, bL), the right one's [bL, bL + bR)
+  bool pinL, pinR;   // the array is page-locked memory the runtime knows: [lo, hi) is the pageable part's place
+  size_t lo() const { return pinL ? bL : 0; }
+  size_t hi() const { return pinR ? bL : bL + bR; }
+};
+
+// A free slot, big enough, its copy stream ordered behind the kernels that read the slot's previous batch (the
+// transfers overwrite its device buffer), its by-batch flags cleared
+static int slot_acquire(esvio_fe_ctx* c, EventStager* st, size_t n_events, int* k_out) {
+  int k = 0;
+  // (a slot a straggling helper is still inside — its chunk was redone by the calling thread — is passed over)
+  while (k < kStageSlots && (st->slot[k].in_use || st->slot[k].busy.load(std::memory_order_acquire) != 0)) k++;
+  if (k == kStageSlots) return fail(c, ESVIO_FE_EINTERNAL, "no free event staging slot");
+  Slot& s = st->slot[k];
+  if (int rc = slot_capacity(c, s, n_events)) return rc;
+  if (s.pf_rec) HIPCHK(c, hipStreamWaitEvent(st->stream, s.pf_done, 0));
+  if (s.main_rec) HIPCHK(c, hipStreamWaitEvent(st->stream, s.main_done, 0));
+  if (s.aux_rec) HIPCHK(c, hipStreamWaitEvent(st->stream, s.aux_done, 0));
+  s.pf_rec = s.main_rec = s.aux_rec = false;
+  s.n_left_chunks = s.n_left_groups = 0;
+  s.left_enq.store(false, std::memory_order_release);
+  s.n_chunks.store(0, std::memory_order_release);
+  s.next.store(0, std::memory_order_release);
+  *k_out = k;
+  return 0;
+}
+
+// A pinned array: one transfer straight from it, now.
+// (a batch the calling thread waits for: pulled by a kernel, as its pageable groups are — hipMemcpyAsync out of
+// hipHostRegister'ed memory ran at 10 GB/s on this stack: the plain call took 0.77 ms against 0.40 with the pull
+// kernel and 0.45 from pageable memory; an announced batch: the copy engine, which costs the compute streams nothing)
+static bool send_pinned(EventStager* st, Slot& s, void* dst, const void* src, size_t len) {
+  if (!s.pull) return st->dma(dst, src, len);
+  // (hipHostMalloc memory is mapped at its host address; hipHostRegister'ed memory need not be: ask)
+  // The kernel reads uint4s: a source that is not 16-byte aligned (an EventArray inside a deserialisation buffer is
+  // only 8-byte aligned in general), or whose first and last byte are mapped by two different registrations that do
+  // not continue each other on the device side, goes through the copy engine instead.
+  void *dp = nullptr, *dp_last = nullptr;
+  if (hipHostGetDevicePointer(&dp, const_cast<void*>(src), 0) != hipSuccess || !dp || ((uintptr_t)dp & 15) != 0 ||
+      ((uintptr_t)dst & 15) != 0 ||
+      hipHostGetDevicePointer(&dp_last, (uint8_t*)const_cast<void*>(src) + len - 1, 0) != hipSuccess ||
+      (uint8_t*)dp_last != (uint8_t*)dp + len - 1) {
+    (void)hipGetLastError();
+    return st->dma(dst, src, len);
+  }
+  (void)hipGetLastError();
+  launch_stage_pull(st->stream, dp, dst, len);
+  return hipGetLastError() == hipSuccess;
+}
+
+// ... both arrays' pinned parts, and copiedL where that settles the left array: it is on its way already, or there is none
+static int send_pinned_parts(esvio_fe_ctx* c, EventStager* st, Slot& s, const BatchSrc& b, bool by_camera) {
+  bool ok = !b.pinL || send_pinned(st, s, s.dev, b.left, b.bL);
+  if (ok && by_camera && (b.pinL || !b.bL)) {
+    HIPCHK(c, hipEventRecord(s.copiedL, st->stream));
+    s.left_enq.store(true, std::memory_order_release);
+  }
+  ok = ok && (!b.pinR || send_pinned(st, s, (uint8_t*)s.dev + b.bL, b.right, b.bR));
+  return ok ? 0 : fail(c, ESVIO_FE_EHIP, "event staging from pinned memory failed");
+}
+
+// The pageable part into groups (one transfer each) of whole chunks of cb bytes, a chunk never straddling the two
+// source arrays: the slot's group and chunk tables and their counts, nothing else — no HIP call.  Returns the chunks.
+// by_camera: the left and the right array are two groups each (group k's transfer runs under the memcpy of group
+// k + 1; the left array's can be waited for on their own); otherwise <= dma_groups groups over the whole range
+static uint32_t cut_batch(Slot& s, const BatchSrc& b, size_t cb, int dma_groups, bool by_camera) {
+  int ng = 0;
+  uint32_t nch = 0;
+  auto split = [&](size_t a0, size_t b0, int want) {  // [a0, b0) into <= want groups of whole chunks
+    const size_t nc = (b0 - a0 + cb - 1) / cb;
+    const int k = (int)std::min<size_t>((size_t)std::max(1, want), nc);
+    const size_t per = (nc + k - 1) / k;
+    for (size_t o = a0; o < b0 && ng < kMaxGroups; o += per * cb) {
+      s.grp[ng].off = o;
+      s.grp[ng].len = (ng == kMaxGroups - 1 ? b0 : std::min(b0, o + per * cb)) - o;
+      ng++;
+    }
+  };
+  if (by_camera) {
+    if (!b.pinL && b.bL) {
+      split(0, b.bL, 2);
+      s.n_left_groups = ng;
+    }
+    if (!b.pinR && b.bR) split(b.bL, b.bL + b.bR, 2);
+  } else if (b.hi() > b.lo()) {
+    split(b.lo(), b.hi(), std::min(dma_groups, kMaxGroups));
+  }
+  for (int g = 0; g < ng; g++) {
+    Group& gr = s.grp[g];
+    gr.first_chunk = nch;
+    gr.dma_enq.store(false, std::memory_order_relaxed);
+    for (size_t o = gr.off, end; o < gr.off + gr.len; o = end) {
+      const bool in_left = o < b.bL;
+      end = std::min(std::min(o + cb, gr.off + gr.len), in_left ? b.bL : gr.off + gr.len);
+      Chunk& ch = s.chunk[nch++];
+      ch.group = g;
+      ch.src = in_left ? b.left + o : b.right + (o - b.bL);
+      ch.off = o;
+      ch.len = end - o;
+      ch.st.store(CH_FREE, std::memory_order_relaxed);
+    }
+    gr.chunks_left.store(nch - gr.first_chunk, std::memory_order_relaxed);
+    if (g < s.n_left_groups) s.n_left_chunks = nch;
+  }
+  s.n_groups = ng;
+  s.groups_left.store((uint32_t)ng, std::memory_order_relaxed);
+  return nch;
+}
+
+// The slot is the batch's from here on: open for taking, the helpers woken — or, with nothing pageable in it, complete
+static int slot_open(esvio_fe_ctx* c, EventStager* st, Slot& s, uint32_t nch) {
+  if (!nch && hipEventRecord(s.copied, st->stream) != hipSuccess) return fail(c, ESVIO_FE_EHIP, "hipEventRecord (event staging) failed");
+  s.in_use = true;
+  s.n_chunks.store(nch, std::memory_order_release);
+  s.t_begin = Clock::now();
+  s.state.store(nch ? SL_STAGING : SL_SENT, std::memory_order_release);
+  if (nch) {
+    st->pending->fetch_add((int)nch, std::memory_order_acq_rel);
+    { std::lock_guard<std::mutex> g(st->mu); }  // (a helper between its predicate and its sleep sees the count)
+    st->cv.notify_all();
+  }
   return 0;
 }
 
@@ -498,163 +655,36 @@ int stager_reserve(esvio_fe_ctx* c, size_t n_events) {
 // DMA; more: a plain call's batch, piece k goes to the device — by k_stage_pull — under the memcpy of piece k+1)
 // by_camera: the left array and the right array are two pieces each (dma_groups is ignored), and the left
 // one's arrival can be waited for on its own (stager_attach_left)
-static int stager_begin_impl(esvio_fe_ctx* c, const esvio_fe_event* left, size_t nL, const esvio_fe_event* right, size_t nR,
-                             int dma_groups, int* slot_out, bool by_camera);
 int stager_begin(esvio_fe_ctx* c, const esvio_fe_event* left, size_t nL, const esvio_fe_event* right, size_t nR,
                  int dma_groups, int* slot_out, bool by_camera) {
-  if (!c->trace) return stager_begin_impl(c, left, nL, right, nR, dma_groups, slot_out, by_camera);
-  {  // (the stager's one-time set-up — stream, events, threads: ~9 ms — is not part of a batch's figure)
-    EventStager* st = nullptr;
-    if (int rc = stager_get(c, &st)) return rc;
-  }
-  const auto t0 = std::chrono::steady_clock::now();
-  const int rc = stager_begin_impl(c, left, nL, right, nR, dma_groups, slot_out, by_camera);
-  if (c->stager)
-    c->stager->begin_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-  return rc;
-}
-static int stager_begin_impl(esvio_fe_ctx* c, const esvio_fe_event* left, size_t nL, const esvio_fe_event* right, size_t nR,
-                             int dma_groups, int* slot_out, bool by_camera) {
   EventStager* st = nullptr;
   if (int rc = stager_get(c, &st)) return rc;
+  NsScope lap{st->begin_ns};  // (the stager's one-time set-up above — stream, events, threads: ~9 ms — is not part of a batch's figure)
+  const auto tp0 = Clock::now();
+  const BatchSrc b{(const uint8_t*)left, (const uint8_t*)right, nL * 16, nR * 16, host_range_is_pinned(left, nL * 16),
+                   host_range_is_pinned(right, nR * 16)};
+  st->pin_ns += ns_since(tp0);
   int k = 0;
-  // (a slot a straggling helper is still inside — its chunk was redone by the calling thread — is passed over)
-  while (k < kStageSlots && (st->slot[k].in_use || st->slot[k].busy.load(std::memory_order_acquire) != 0)) k++;
-  if (k == kStageSlots) return fail(c, ESVIO_FE_EINTERNAL, "no free event staging slot");
+  if (int rc = slot_acquire(c, st, nL + nR, &k)) return rc;
   Slot& s = st->slot[k];
-  const size_t n = nL + nR;
-  const auto tp0 = std::chrono::steady_clock::now();
-  const bool pinL = host_range_is_pinned(left, nL * 16), pinR = host_range_is_pinned(right, nR * 16);
-  if (c->trace) st->pin_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - tp0).count();
-  if (int rc = slot_capacity(c, s, n)) return rc;
-  // the DMA overwrites the slot's device buffer: behind the kernels that read its previous batch
-  if (s.pf_rec) HIPCHK(c, hipStreamWaitEvent(st->stream, s.pf_done, 0));
-  if (s.main_rec) HIPCHK(c, hipStreamWaitEvent(st->stream, s.main_done, 0));
-  if (s.aux_rec) HIPCHK(c, hipStreamWaitEvent(st->stream, s.aux_done, 0));
-  s.pf_rec = s.main_rec = s.aux_rec = false;
-  s.n_left_groups = 0;
-  s.n_left_chunks = 0;
   s.pull = by_camera || dma_groups > 1;  // (a batch the calling thread waits for)
-  s.pack = false;
-  s.left_enq.store(false, std::memory_order_release);
-  st->bytes_staged += n * 16;
+  // by-camera staging of a batch the call waits for: chunks of one size, every group whole chunks of one array —
+  // what the packed form needs (k_stage_pull_packed finds an event's chunk by division)
+  const size_t cb = chunk_bytes(by_camera);
+  s.pack = st->pack_enabled && by_camera;
+  s.pack_epc = (uint32_t)(cb / 16);
+  st->bytes_staged += b.bL + b.bR;
   st->batches++;
-  // a pinned source: one DMA straight from it, now (the slot is taken only once nothing below can fail
-  // before its state is set)
-  // (a batch the calling thread waits for: pulled by a kernel, as its pageable groups are — hipMemcpyAsync out of
-  // hipHostRegister'ed memory ran at 10 GB/s on this stack: the plain call took 0.77 ms against 0.40 with the pull
-  // kernel and 0.45 from pageable memory; an announced batch: the copy engine, which costs the compute streams nothing)
-  auto from_pinned = [&](void* dst, const void* src, size_t len) {
-    if (!s.pull) return st->dma(dst, src, len);
-    // (hipHostMalloc memory is mapped at its host address; hipHostRegister'ed memory need not be: ask)
-    // The kernel reads uint4s: a source that is not 16-byte aligned (an EventArray inside a deserialisation buffer is
-    // only 8-byte aligned in general), or whose first and last byte are mapped by two different registrations that do
-    // not continue each other on the device side, goes through the copy engine instead.
-    void *dp = nullptr, *dp_last = nullptr;
-    if (hipHostGetDevicePointer(&dp, const_cast<void*>(src), 0) != hipSuccess || !dp || ((uintptr_t)dp & 15) != 0 ||
-        ((uintptr_t)dst & 15) != 0 ||
-        hipHostGetDevicePointer(&dp_last, (uint8_t*)const_cast<void*>(src) + len - 1, 0) != hipSuccess ||
-        (uint8_t*)dp_last != (uint8_t*)dp + len - 1) {
-      (void)hipGetLastError();
-      return st->dma(dst, src, len);
-    }
-    (void)hipGetLastError();
-    launch_stage_pull(st->stream, dp, dst, len);
-    return hipGetLastError() == hipSuccess;
-  };
-  if (pinL && !from_pinned(s.dev, left, nL * 16)) return fail(c, ESVIO_FE_EHIP, "event staging from pinned memory failed");
-  if (by_camera && (pinL || !nL)) {  // (the left array is on its way already, or there is none)
-    HIPCHK(c, hipEventRecord(s.copiedL, st->stream));
-    s.left_enq.store(true, std::memory_order_release);
-  }
-  if (pinR && !from_pinned(s.dev + nL, right, nR * 16)) return fail(c, ESVIO_FE_EHIP, "event staging from pinned memory failed");
-  s.in_use = true;
-  // the pageable part: destination byte range [lo, hi) of the slot's buffers
-  const size_t lo = pinL ? nL * 16 : 0, hi = pinR ? nL * 16 : n * 16;
-  int ng = 0;
-  uint32_t nch = 0;
-  s.n_chunks.store(0, std::memory_order_release);
-  s.next.store(0, std::memory_order_release);
-  if (hi > lo) {
-    // (by camera: the calling thread waits for the left array: smaller pieces, more threads on it at once)
-    const size_t cb = by_camera ? kChunkBytes / 4 : kChunkBytes;
-    const size_t chunks = (hi - lo + cb - 1) / cb;
-    // the groups (one DMA each): destination byte ranges [a, b)
-    size_t ga[kMaxGroups], gb[kMaxGroups];
-    auto split = [&](size_t a0, size_t b0, int want) {  // [a0, b0) into <= want groups of whole chunks
-      const size_t nc = (b0 - a0 + cb - 1) / cb;
-      const int k = (int)std::min<size_t>((size_t)std::max(1, want), nc);
-      const size_t per = (nc + k - 1) / k;
-      for (size_t o = a0; o < b0 && ng < kMaxGroups; o += per * cb) {
-        ga[ng] = o;
-        gb[ng] = ng == kMaxGroups - 1 ? b0 : std::min(b0, o + per * cb);
-        ng++;
-      }
-    };
-    if (by_camera) {
-      // the left array's DMAs can be waited for on their own; group k's DMA runs under the memcpy of group k+1
-      if (!pinL && nL) {
-        split(0, nL * 16, 2);
-        s.n_left_groups = ng;
-      }
-      if (!pinR && nR) split(nL * 16, n * 16, 2);
-    } else {
-      split(lo, hi, std::min(dma_groups, kMaxGroups));
-    }
-    if (int rc = slot_chunks(c, s, chunks)) {
-      s.in_use = false;
-      return rc;
-    }
-    // by-camera staging of a batch the call waits for: chunks of one size, every group whole chunks of one array —
-    // what the packed form needs (k_stage_pull_packed finds an event's chunk by division)
-    s.pack = st->pack_enabled && by_camera && s.pull;
-    s.pack_epc = (uint32_t)(cb / 16);
-    for (int g = 0; g < ng; g++) {
-      const size_t a = ga[g], b = gb[g];
-      s.grp[g].off = a;
-      s.grp[g].len = b - a;
-      s.grp[g].first_chunk = nch;
-      s.grp[g].dma_enq.store(false, std::memory_order_relaxed);
-      uint32_t cnt = 0;
-      for (size_t o = a; o < b;) {
-        // a chunk never straddles the boundary between the two source arrays
-        const bool in_left = o < nL * 16;
-        const size_t end = std::min(std::min(o + cb, b), in_left ? nL * 16 : b);
-        const uint8_t* src = in_left ? (const uint8_t*)left + o : (const uint8_t*)right + (o - nL * 16);
-        Chunk& ch = s.chunk[nch];
-        ch.group = g;
-        ch.src = src;
-        ch.off = o;
-        ch.len = end - o;
-        ch.st.store(0, std::memory_order_relaxed);
-        nch++;
-        cnt++;
-        if (g < s.n_left_groups) s.n_left_chunks = nch;
-        o = end;
-      }
-      s.grp[g].chunks_left.store(cnt, std::memory_order_relaxed);
-    }
-  }
-  s.n_groups = ng;
-  s.groups_left.store((uint32_t)ng, std::memory_order_relaxed);
-  if (!nch && hipEventRecord(s.copied, st->stream) != hipSuccess) {
-    s.in_use = false;
-    return fail(c, ESVIO_FE_EHIP, "hipEventRecord (event staging) failed");
-  }
-  s.n_chunks.store(nch, std::memory_order_release);
-  s.t_begin = std::chrono::steady_clock::now();
-  s.state.store(nch ? 1 : 2, std::memory_order_release);  // (open for taking)
-  if (nch) {
-    st->pending->fetch_add((int)nch, std::memory_order_acq_rel);
-    { std::lock_guard<std::mutex> g(st->mu); }  // (a helper between its predicate and its sleep sees the count)
-    st->cv.notify_all();
-  }
+  if (int rc = send_pinned_parts(c, st, s, b, by_camera)) return rc;
+  if (b.hi() > b.lo())
+    if (int rc = slot_chunks(c, s, b.hi() - b.lo(), cb)) return rc;
+  if (int rc = slot_open(c, st, s, cut_batch(s, b, cb, dma_groups, by_camera))) return rc;
   *slot_out = k;
   return 0;
 }
 
 bool stager_ready(esvio_fe_ctx* c, int slot) {
-  const bool r = c->stager->slot[slot].state.load(std::memory_order_acquire) != 1;
+  const bool r = !c->stager->slot[slot].staging();
   if (!r) c->stager->skipped++;
   return r;
 }
@@ -664,63 +694,37 @@ bool stager_ready(esvio_fe_ctx* c, int slot) {
 int stager_attach(esvio_fe_ctx* c, int slot, size_t nL, hipStream_t s, const EventRec** dL, const EventRec** dR) {
   EventStager* st = c->stager;
   Slot& sl = st->slot[slot];
-  if (sl.state.load(std::memory_order_acquire) == 1) {
-    const auto t0 = std::chrono::steady_clock::now();
-    unsigned idle = 0;
-    while (sl.state.load(std::memory_order_acquire) == 1) {
-      if (st->try_one()) {
-        st->caller_chunks++;
-        idle = 0;
-      } else if (++idle > 1000) {  // (~25 us with nothing to take: some helper has started something and is not finishing it)
-        st->finish_for(slot);
-        idle = 0;
-      } else {
-        cpu_relax();
-      }
-    }
-    st->wait_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+  if (sl.staging()) {
+    NsScope w{st->wait_ns};
+    st->caller_chunks += st->wait_for(slot, [&] { return !sl.staging(); }, [&] { return st->try_one(); });
   }
-  if (sl.state.load(std::memory_order_acquire) != 2) {
+  if (sl.state.load(std::memory_order_acquire) != SL_SENT) {
     // a DMA could not be enqueued: chunks of this slot may still be queued or being copied from the
     // caller's memory, which is the caller's again once this call has returned — finish them first
     stager_abandon(c, slot);
     return fail(c, ESVIO_FE_EHIP, "staging the event batch failed");
   }
   HIPCHK(c, hipStreamWaitEvent(s, sl.copied, 0));
-  *dL = sl.dev;
-  *dR = sl.dev + nL;
+  stager_ptrs(c, slot, nL, dL, dR);
   return 0;
 }
 
-// by_camera staging: wait (taking chunks meanwhile) until the LEFT array's DMA is enqueued and make stream
-// `s` wait for it; the right array may still be on its way (stager_attach follows for it)
+// by_camera staging: wait (taking the left array's chunks meanwhile) until the LEFT array's DMA is enqueued and make
+// stream `s` wait for it; the right array may still be on its way (stager_attach follows for it)
 int stager_attach_left(esvio_fe_ctx* c, int slot, hipStream_t s, const EventRec** dL) {
   EventStager* st = c->stager;
   Slot& sl = st->slot[slot];
-  unsigned idle = 0;
-  const auto tl0 = std::chrono::steady_clock::now();
-  struct Lap {
-    EventStager* st; std::chrono::steady_clock::time_point t0;
-    ~Lap() { st->left_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count(); st->left_calls++; }
-  } lap{st, tl0};
-  while (!sl.left_enq.load(std::memory_order_acquire) && sl.state.load(std::memory_order_acquire) == 1) {
-    if (st->try_one_left(slot)) {
-      st->caller_chunks++;
-      idle = 0;
-    } else if (++idle > 1000) {
-      st->finish_for(slot);
-      idle = 0;
-    } else {
-      cpu_relax();
-    }
-  }
+  NsScope lap{st->left_ns};
+  st->left_calls++;
+  st->caller_chunks += st->wait_for(
+      slot, [&] { return sl.left_enq.load(std::memory_order_acquire) || !sl.staging(); }, [&] { return st->take(sl, sl.n_left_chunks); });
   const int stt = sl.state.load(std::memory_order_acquire);
   const bool left = sl.left_enq.load(std::memory_order_acquire);
-  if (stt < 0 || (!left && stt != 2)) {
+  if (stt == SL_FAILED || (!left && stt != SL_SENT)) {
     stager_abandon(c, slot);
     return fail(c, ESVIO_FE_EHIP, "staging the event batch failed (left array)");
   }
-  // (the whole batch can be complete — finish_for above closed it — while the thread that sent the last left
+  // (the whole batch can be complete — finish_for closed it — while the thread that sent the last left
   // group has not got to recording copiedL yet: the batch's own event covers the left array as well)
   HIPCHK(c, hipStreamWaitEvent(s, left ? sl.copiedL : sl.copied, 0));
   *dL = sl.dev;
@@ -737,13 +741,13 @@ void stager_abandon(esvio_fe_ctx* c, int slot) {
     const uint32_t n = sl.n_chunks.load(std::memory_order_acquire);
     const uint32_t nx = sl.next.exchange(n, std::memory_order_acq_rel);
     if (nx < n) st->pending->fetch_sub((int)(n - nx), std::memory_order_acq_rel);
-    sl.state.store(-1, std::memory_order_release);  // (closed for taking)
+    sl.state.store(SL_FAILED, std::memory_order_release);  // (closed for taking)
   }
   while (sl.busy.load(std::memory_order_acquire) != 0) cpu_relax();  // chunks a thread holds: waited for
   (void)hipStreamSynchronize(st->stream);  // (DMAs straight from a pinned source, groups already enqueued)
   for (int g2 = 0; g2 < kMaxGroups; g2++) sl.grp[g2].chunks_left.store(0, std::memory_order_relaxed);
   sl.groups_left.store(0, std::memory_order_relaxed);
-  sl.state.store(0, std::memory_order_release);
+  sl.state.store(SL_IDLE, std::memory_order_release);
   sl.in_use = false;
 }
 
@@ -775,7 +779,7 @@ int stager_release(esvio_fe_ctx* c, int slot) {
   if (slot < 0 || !c->stager) return 0;
   Slot& sl = c->stager->slot[slot];
   sl.in_use = false;
-  if (sl.state.load(std::memory_order_acquire) == 2) HIPCHK(c, hipEventSynchronize(sl.copied));
+  if (sl.state.load(std::memory_order_acquire) == SL_SENT) HIPCHK(c, hipEventSynchronize(sl.copied));
   // (a helper whose chunk was redone may still be inside its own copy of it: it reads the caller's memory)
   while (sl.busy.load(std::memory_order_acquire) != 0) cpu_relax();
   return 0;
@@ -787,17 +791,7 @@ void stager_drain(esvio_fe_ctx* c) {
   if (!st) return;
   for (int k = 0; k < kStageSlots; k++) {
     Slot& s = st->slot[k];
-    unsigned idle = 0;
-    while (s.state.load(std::memory_order_acquire) == 1) {
-      if (st->try_one()) {
-        idle = 0;
-      } else if (++idle > 1000) {
-        st->finish_for(k);
-        idle = 0;
-      } else {
-        cpu_relax();
-      }
-    }
+    (void)st->wait_for(k, [&] { return !s.staging(); }, [&] { return st->try_one(); });
     while (s.busy.load(std::memory_order_acquire) != 0) cpu_relax();
     s.in_use = false;
   }

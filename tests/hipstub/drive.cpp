@@ -439,6 +439,7 @@ int main(int argc, char** argv) {
   t.pts_velocity = f2[2].data(); t.ids_right = idr.data(); t.cur_right_pts = f2[3].data();
   t.cur_un_right_pts = f2[4].data(); t.right_pts_velocity = f2[5].data();
   long calls = 0, failed = 0, resets = 0, handles = 0;
+  uint64_t staged[4] = {0, 0, 0, 0};  // esvio_fe_staging_counters, summed over the handles
   int f = 0;
   {  // (the injected failures are for the calls of the loop below)
     hipstub_arm_faults(0);
@@ -474,7 +475,14 @@ int main(int argc, char** argv) {
     esvio_fe_reserve(h, 1u << 16, 1u << 16, 1);
     const int stretch = 20 + (int)(rnd() % 40u);  // frames on this handle
     std::vector<Batch> bs((size_t)stretch);
-    for (int i = 0; i < stretch; i++) make_batch(bs[(size_t)i], W, H, f + i, 9000 + (int)(rnd() % 6000u));
+    for (int i = 0; i < stretch; i++) {
+      Batch& b = bs[(size_t)i];
+      make_batch(b, W, H, f + i, 9000 + (int)(rnd() % 6000u));
+      // about one batch in four: the second half of the left array one second earlier — a plain call's staging then meets
+      // a chunk whose stamps step back over a second, which it must send raw and never write packed (fe_evstage.cpp)
+      if (rnd() % 4u == 0)
+        for (size_t j = b.L.size() / 2; j < b.L.size(); j++) b.L[j].sec -= 1;
+    }
     std::vector<int> pub((size_t)stretch);
     for (int i = 0; i < stretch; i++) pub[(size_t)i] = (rnd() % 3u) != 0;
     int announced = 0;                                 // batches [i + 1, announced] are announced
@@ -522,6 +530,9 @@ int main(int argc, char** argv) {
     {
       esvio_fe_latency_call lc;
       if (esvio_fe_latency_recent(h, 0, &lc) == ESVIO_FE_OK && lc.ms < 0) { fprintf(stderr, "latency record\n"); return 4; }
+      uint64_t sc[4];
+      if (esvio_fe_staging_counters(h, sc) == ESVIO_FE_OK)
+        for (int k = 0; k < 4; k++) staged[k] += sc[k];
     }
     esvio_fe_destroy(h);
     f += stretch;
@@ -530,6 +541,8 @@ int main(int argc, char** argv) {
   esvio_fe_ransac_tail(tail, 0);
   printf("drive ok: %ld calls on %ld handles, %ld refused/failed, %ld resets, tracks last %d / %d, ransac redone %llu\n", calls,
          handles, failed, resets, t.n_left, t.n_right, (unsigned long long)tail[2]);
+  printf("staging: %llu batches, %llu chunks packed, %llu raw\n", (unsigned long long)staged[0], (unsigned long long)staged[2],
+         (unsigned long long)staged[3]);
   long live[4];
   hipstub_live(live);
   printf("live: device %ld pinned %ld events %ld streams %ld\n", live[0], live[1], live[2], live[3]);

@@ -248,7 +248,10 @@ def test_stage_pack_round_trip_and_refusals():
     k_stage_pull_packed): x | y << 16, nsec | (polarity != 0) << 30 | (sec - base) << 31.  Every field a kernel reads
     comes back (polarity as != 0, the record's padding bytes as zero: no kernel reads them — and a ROS message leaves
     them uninitialised); a chunk whose stamps step back over a second, jump two, or carry an nsec no ros::Time has is
-    refused (it then travels raw)."""
+    refused (it then travels raw) — and refused BEFORE anything is written: the chunk's place in the pinned buffer may be
+    written by two threads at once (fe_evstage.cpp), which is harmless only if it never holds anything but the form that
+    is published.  So the destination, the whole len bytes of the chunk's place between two guards, starts as 0xA5:
+    a refusal leaves every byte of it, an acceptance every byte beyond len / 2."""
     from esvio_amd.events import EVENT_DTYPE
     L = FE.load_library()
     L.esvio_fe_host_stage_pack.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
@@ -256,10 +259,14 @@ def test_stage_pack_round_trip_and_refusals():
 
     def pack(ev):
         raw = np.ascontiguousarray(ev).view(np.uint8).reshape(-1)
-        buf = np.zeros(len(raw) // 2 + 64, np.uint8)
-        off = (-buf.ctypes.data) % 16
+        guard = 64
+        buf = np.full(guard + 16 + len(raw) + guard, 0xA5, np.uint8)
+        off = guard + (-(buf.ctypes.data + guard)) % 16
         base = C.c_uint32(0)
         rc = L.esvio_fe_host_stage_pack(C.c_void_p(buf.ctypes.data + off), C.c_void_p(raw.ctypes.data), len(raw), C.byref(base))
+        written = len(raw) // 2 if rc == 1 else 0
+        assert rc in (0, 1) and (buf[:off] == 0xA5).all() and (buf[off + written:] == 0xA5).all(), \
+            (rc, len(ev), np.flatnonzero(np.concatenate([buf[:off], buf[off + written:]]) != 0xA5)[:4])
         return rc, base.value, buf[off:off + len(raw) // 2].view(np.uint32).reshape(-1, 2)
 
     for n in (1, 2, 3, 4095, 4096, 4097):
@@ -291,6 +298,24 @@ def test_stage_pack_round_trip_and_refusals():
             else:
                 e2["nsec"][k2] = (1 << 31) | 5
             assert pack(e2)[0] == 0, (bad, k)
+    # ... and at a real chunk's size (4096 events = 64 KiB): the offender second, in the middle, last
+    big = np.zeros(4096, EVENT_DTYPE)
+    big["x"], big["y"] = rng.integers(0, 65536, 4096), rng.integers(0, 65536, 4096)
+    big["sec"], big["nsec"], big["polarity"] = 100, np.arange(4096) * 1000, 1
+    assert pack(big)[0] == 1
+    for k in (1, 2048, 4095):
+        for bad in ("back", "jump", "nsec", "nsec_top"):
+            e2 = big.copy()
+            if bad == "back":
+                e2["sec"][k] = 99
+            elif bad == "jump":
+                e2["sec"][k:] = 102
+            else:
+                e2["nsec"][k] = 1 << 30 if bad == "nsec" else (1 << 31) | 5
+            assert pack(e2)[0] == 0, (bad, k)
+    e2 = big.copy()
+    e2["nsec"][0] = 1 << 30
+    assert pack(e2)[0] == 0
     # one step forwards over a second is fine wherever it falls
     for k in range(1, 64):
         e2 = ev.copy()

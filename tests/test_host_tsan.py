@@ -7,7 +7,8 @@ with 1..4 batches announced, the launch thread switched on and off mid-stream, 0
 calls, refused calls, esvio_fe_reset with batches in flight, handles created and destroyed).
 
 No report may appear (tests/hipstub/tsan.supp suppresses the one designed race: the idempotent re-do of a staging
-chunk a straggling helper holds) and the driver must finish — a hang is a failure too: on the commit before round
+chunk a straggling helper holds; about one driver batch in four holds a chunk the packer refuses, and every un-failed
+seed must have staged chunks of both forms) and the driver must finish — a hang is a failure too: on the commit before round
 4's launcher fix (e4c4950^: job numbers not reset when the launch thread is restarted) this driver hangs for every
 seed; profiles/r05_tsan_history.txt has that run, and the run on the commit before round 4's staging fix (f0d8679^),
 whose window — a DMA still in flight when the batch is closed — a device that completes at once does not open."""
@@ -50,6 +51,14 @@ def assert_nothing_alive(stdout):
     assert "live: device 0 pinned 0 events 0 streams 0" in stdout, stdout[-500:]
 
 
+def assert_both_staging_forms(stdout):
+    """coverage, not a measurement: the run staged chunks packed AND chunks the packer refused (the driver's batches
+    that step back over a second) — the path where a chunk's place must never see the packed form"""
+    words = stdout.split("staging:")[1].split()
+    packed, raw = int(words[words.index("packed,") - 2]), int(words[words.index("raw") - 1])
+    assert packed > 0 and raw > 0, stdout[-500:]
+
+
 def run_driver(exe, seed, frames, timeout, **extra_env):
     env = dict(os.environ, TSAN_OPTIONS="suppressions=%s halt_on_error=0" % os.path.join(STUB, "tsan.supp"), **extra_env)
     return subprocess.run([exe, str(seed), str(frames)], capture_output=True, text=True, timeout=timeout, env=env)
@@ -66,6 +75,7 @@ def test_every_host_thread_under_thread_sanitizer(tmp_path):
         calls = int(p.stdout.split("drive ok:")[1].split()[0])
         assert calls >= 300
         assert_nothing_alive(p.stdout)
+        assert_both_staging_forms(p.stdout)
     # launches that fail in the middle of a call, on the calling thread or on the launch thread (whose first error
     # is sticky until esvio_fe_reset and travels to the caller's error text): every failed call is followed by a
     # reset in the driver, the stream goes on, nothing hangs, nothing races
@@ -93,6 +103,7 @@ def test_host_side_under_address_and_ub_sanitizers(tmp_path):
         assert p.returncode == 0 and "drive ok:" in p.stdout, out[-3000:]
         assert "runtime error" not in out and "AddressSanitizer" not in out and "LeakSanitizer" not in out, out[-6000:]
         assert_nothing_alive(p.stdout)
+        assert_both_staging_forms(p.stdout)
     # ... and on the failing exits: every 97th / 701st HIP call fails (calling thread or launch thread), the driver
     # resets and goes on — error paths are where buffers are forgotten or freed twice
     for every in ("97", "701"):
