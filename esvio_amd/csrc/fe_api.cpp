@@ -353,6 +353,11 @@ int esvio_fe_create(const esvio_fe_config* cfg, esvio_fe_handle* out) {
   return 0;
 }
 
+namespace {
+int baf_clear(esvio_fe_ctx* c);  // the background-activity filter's planes back to `none` (below, with the stage)
+int baf_ensure(esvio_fe_ctx* c, size_t n, bool host_src, bool host_dst);
+}  // namespace
+
 int esvio_fe_reset(esvio_fe_handle c) {
   if (!c) return ESVIO_FE_EINVAL;
   HIPCHK(c, hipSetDevice(c->dev));
@@ -381,6 +386,7 @@ int esvio_fe_reset(esvio_fe_handle c) {
   c->pend_right.active = false;
   HIPCHK(c, hipMemsetAsync(c->L2, 0, (size_t)2 * c->P * 16, cur_stream(c)));
   HIPCHK(c, hipMemsetAsync(c->S2, 0, (size_t)2 * c->P * 16, cur_stream(c)));
+  if (int rc = baf_clear(c)) return rc;  // the background-activity filter's planes: none everywhere
   HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
   clear_tracker_state(c);
   return 0;
@@ -1093,6 +1099,45 @@ int esvio_fe_convert_events(esvio_fe_handle c, const esvio_fe_event_fields* src,
   return 0;
 }
 
+// The handle's two alternating pairs of record buffers [pair][camera] (include/esvio_fe.h: buffer lifetime), shared by
+// the entry points that make the records they track.  cvt_pair_begin: room for (nL, nR) records in both pairs — the
+// second call of a size allocates nothing — and the current pair's buffers, behind everything the pair's previous use
+// (two calls back) left on the side streams: what it left on the main stream is in front of us there anyway.
+// cvt_pair_track: the plain track call on the pair's records; marks what it leaves on the side streams and hands
+// the next call the other pair.
+namespace {
+int cvt_pair_begin(esvio_fe_ctx* c, size_t nL, size_t nR, EventRec** dL, EventRec** dR) {
+  for (int p = 0; p < 2; p++) {
+    if (int rc = c->d_cvt_ev[p][0].grow(c, nL)) return rc;
+    if (int rc = c->d_cvt_ev[p][1].grow(c, nR)) return rc;
+  }
+  const int pair = c->cvt_pair;
+  hipStream_t side[4] = {c->stream2, c->stream3, c->stream4, c->stream6};
+  if (c->cvt_side_rec[pair])
+    for (int k = 0; k < 4; k++)
+      if (side[k]) HIPCHK(c, hipStreamWaitEvent(cur_stream(c), c->ev_cvt_side[pair][k], 0));
+  *dL = c->d_cvt_ev[pair][0];
+  *dR = c->d_cvt_ev[pair][1];
+  return 0;
+}
+int cvt_pair_track(esvio_fe_ctx* c, double cur_time, const EventRec* dL, size_t nL, const EventRec* dR, size_t nR,
+                   int pub_this_frame, esvio_fe_tracks* out) {
+  const int pair = c->cvt_pair;
+  hipStream_t side[4] = {c->stream2, c->stream3, c->stream4, c->stream6};
+  const int rc = track_event_impl(c, cur_time, (const esvio_fe_event*)dL, nL, (const esvio_fe_event*)(nR ? dR : nullptr), nR,
+                                  ESVIO_FE_DEVICE, pub_this_frame != 0, nullptr);
+  for (int k = 0; k < 4; k++)
+    if (side[k]) {
+      if (!c->ev_cvt_side[pair][k]) HIPCHK(c, c->ev_cvt_side[pair][k].create());
+      HIPCHK(c, hipEventRecord(c->ev_cvt_side[pair][k], side[k]));
+    }
+  c->cvt_side_rec[pair] = true;
+  c->cvt_pair ^= 1;
+  if (rc) return rc;
+  return fill_tracks(c, out);
+}
+}  // namespace
+
 int esvio_fe_track_event_fields(esvio_fe_handle c, double cur_time, const esvio_fe_event_fields* left, size_t nL,
                                 const esvio_fe_event_fields* right, size_t nR, int src_space, int pub_this_frame,
                                 esvio_fe_tracks* out) {
@@ -1105,19 +1150,8 @@ int esvio_fe_track_event_fields(esvio_fe_handle c, double cur_time, const esvio_
   if (!c->announced.empty() || !c->inflight.empty())
     return fail(c, ESVIO_FE_EINVAL, "track_event_fields: batches are announced on this handle (convert into memory of your own)");
   HIPCHK(c, hipSetDevice(c->dev));
-  // both pairs at once: the second call of a size allocates nothing
-  for (int p = 0; p < 2; p++) {
-    if (int rc = c->d_cvt_ev[p][0].grow(c, nL)) return rc;
-    if (int rc = c->d_cvt_ev[p][1].grow(c, nR)) return rc;
-  }
-  const int pair = c->cvt_pair;
-  // the pair's previous batch: two calls back, read by nothing on the main stream that is not in front of us there;
-  // what that call left on the other streams is marked by the events recorded when it returned
-  hipStream_t side[4] = {c->stream2, c->stream3, c->stream4, c->stream6};
-  if (c->cvt_side_rec[pair])
-    for (int k = 0; k < 4; k++)
-      if (side[k]) HIPCHK(c, hipStreamWaitEvent(cur_stream(c), c->ev_cvt_side[pair][k], 0));
-  EventRec *dL = c->d_cvt_ev[pair][0], *dR = nR ? (EventRec*)c->d_cvt_ev[pair][1] : nullptr;
+  EventRec *dL = nullptr, *dR = nullptr;
+  if (int rc = cvt_pair_begin(c, nL, nR, &dL, &dR)) return rc;
   if (int rc = convert_begin(c)) return rc;
   if (int rc = convert_enqueue(c, *left, nL, src_space, dL)) return rc;
   if (nR)
@@ -1127,17 +1161,208 @@ int esvio_fe_track_event_fields(esvio_fe_handle c, double cur_time, const esvio_
   if (bad)
     return fail(c, ESVIO_FE_EINVAL, "track_event_fields: %llu of %zu events have a stamp outside [0, 2^32 s) (or a 64-bit t outside +-2^62)",
                 bad, nL + nR);
-  const int rc = track_event_impl(c, cur_time, (const esvio_fe_event*)dL, nL, (const esvio_fe_event*)dR, nR, ESVIO_FE_DEVICE,
-                                  pub_this_frame != 0, nullptr);
-  for (int k = 0; k < 4; k++)
-    if (side[k]) {
-      if (!c->ev_cvt_side[pair][k]) HIPCHK(c, c->ev_cvt_side[pair][k].create());
-      HIPCHK(c, hipEventRecord(c->ev_cvt_side[pair][k], side[k]));
+  return cvt_pair_track(c, cur_time, dL, nL, dR, nR, pub_this_frame, out);
+}
+
+// ---- background-activity filter of an event batch (esvio_fe_filter_events; the rule: include/esvio_fe.h)
+namespace {
+constexpr int64_t kBafMaxWindow = (int64_t)1 << 62;
+
+int baf_params_check(esvio_fe_ctx* c, int64_t window_ns, int min_support, const char* who) {
+  if (window_ns < 1 || window_ns > kBafMaxWindow) return fail(c, ESVIO_FE_EINVAL, "%s: window_ns must be in 1..2^62 (got %lld)", who, (long long)window_ns);
+  if (min_support < 1 || min_support > 8) return fail(c, ESVIO_FE_EINVAL, "%s: min_support must be in 1..8 (got %d)", who, min_support);
+  return 0;
+}
+
+int baf_clear(esvio_fe_ctx* c) {  // every plane back to `none`, the sort's scratch words as a finished sort leaves them
+  esvio_fe_ctx::Baf& f = c->baf;
+  if (f.B) HIPCHK(c, hipMemsetAsync(f.B, 0xff, (size_t)2 * c->P * sizeof(long long), cur_stream(c)));
+  if (f.sort) HIPCHK(c, hipMemsetAsync(f.sort, 0, (size_t)kSortHeadWords * 4, cur_stream(c)));
+  return 0;
+}
+
+// the planes (first call) and the per-event scratch for calls of up to n events; host_src / host_dst: the record
+// buffers of a host source / destination as well
+int baf_ensure(esvio_fe_ctx* c, size_t n, bool host_src, bool host_dst) {
+  esvio_fe_ctx::Baf& f = c->baf;
+  if (!f.B) {
+    if (int rc = f.head.alloc(c, c->P)) return rc;
+    if (int rc = f.res.alloc(c, 1)) return rc;
+    if (int rc = f.B.alloc(c, (size_t)2 * c->P)) return rc;
+    // (f.B says "the stage's state exists": a plane or a head table that could not be cleared is not there)
+    hipError_t e = hipMemsetAsync(f.head, 0, (size_t)c->P * 4, cur_stream(c));
+    if (e == hipSuccess) e = hipMemsetAsync(f.B, 0xff, (size_t)2 * c->P * sizeof(long long), cur_stream(c));
+    if (e != hipSuccess) {
+      f.B.release();
+      HIPCHK(c, e);
     }
-  c->cvt_side_rec[pair] = true;
-  c->cvt_pair ^= 1;
-  if (rc) return rc;
-  return fill_tracks(c, out);
+  }
+  if (n > f.cap) {
+    const size_t cap = std::max<size_t>(n + n / 4, 1 << 16);
+    f.cap = 0;
+    for (int k = 0; k < 2; k++) {
+      if (int rc = f.keys[k].alloc(c, cap)) return rc;
+      if (int rc = f.vals[k].alloc(c, cap)) return rc;
+    }
+    if (int rc = f.tsort.alloc(c, cap)) return rc;
+    if (int rc = f.flags.alloc(c, cap + 4)) return rc;
+    if (int rc = f.blk_cnt.alloc(c, (size_t)baf_blocks((uint32_t)cap) + 1)) return rc;
+    const size_t words = sort_scratch_words(cap);
+    if (int rc = f.sort.alloc(c, words)) return rc;
+    HIPCHK(c, hipMemsetAsync(f.sort, 0, words * 4, cur_stream(c)));
+    f.cap = cap;
+  }
+  if (host_src)
+    if (int rc = f.src.grow(c, n)) return rc;
+  if (host_dst)
+    if (int rc = f.out.grow(c, n)) return rc;
+  return 0;
+}
+
+// Filter the n events at `ev` (n > 0; a host source is copied into the stage's scratch first, as it is) into the device
+// buffer d_dst, advancing camera cam's plane; waits for the result block *r and, if asked for, the flags.
+int baf_run(esvio_fe_ctx* c, int cam, const esvio_fe_event* ev, size_t n, int space, int64_t window_ns, int min_support,
+            EventRec* d_dst, BafResult* r, uint8_t* flags, const char* who) {
+  esvio_fe_ctx::Baf& f = c->baf;
+  hipStream_t s = cur_stream(c);
+  const EventRec* d_ev = (const EventRec*)ev;
+  if (space == ESVIO_FE_HOST) {
+    HIPCHK(c, hipMemcpyAsync(f.src, ev, n * sizeof(EventRec), hipMemcpyHostToDevice, s));
+    d_ev = f.src;
+  }
+  HIPCHK(c, hipMemsetAsync(f.res, 0, sizeof(BafResult), s));
+  int key_bits = 1;
+  while (((uint64_t)1 << key_bits) <= c->P) key_bits++;  // keys 0..P, P = out of the sensor
+  const int passes = (key_bits + 6) / 7, bits = (key_bits + passes - 1) / passes;
+  if (passes > kRadixMaxPasses) return fail(c, ESVIO_FE_ENOTIMPL, "%s: the sensor has more pixels than the sort's %d digits hold", who, kRadixMaxPasses);
+  const uint32_t n32 = (uint32_t)n;
+  const SortScratch sc = sort_scratch(f.sort);
+  const size_t pass_words = (size_t)radix_blocks(n32) << bits;
+  uint8_t* res_bytes = (uint8_t*)f.res.p;
+  {
+    ScopedKernel k(c, K_SAE_KEYS, (uint64_t)n * 24);
+    launch_sae_keys(s, d_ev, n32, nullptr, 0, c->W, c->H, f.keys[0], f.vals[0], c->P,
+                    (unsigned long long*)(res_bytes + offsetof(BafResult, n_rejected)), passes, bits, sc.ghist, sc.lookback,
+                    (uint32_t)(passes * pass_words), nullptr);
+  }
+  int cur = 0;
+  for (int p = 0; p < passes; p++) {
+    ScopedKernel k(c, K_RADIX_PASS, (uint64_t)n * 16);
+    launch_radix_pass(s, f.keys[cur], f.vals[cur], n32, p * bits, bits, sc.ghist + ((size_t)p << bits),
+                      sc.lookback + p * pass_words, sc.tickets + p, f.keys[cur ^ 1], f.vals[cur ^ 1],
+                      (int*)(res_bytes + offsetof(BafResult, err)), c->lim.lookback);
+    cur ^= 1;
+  }
+  BafArgs a{};
+  a.ev = d_ev, a.n = n32, a.P = c->P, a.W = c->W, a.H = c->H;
+  a.keys = f.keys[cur], a.vals = f.vals[cur], a.head = f.head, a.tsort = f.tsort;
+  a.B = f.B + (size_t)cam * c->P;
+  a.window_ns = window_ns, a.min_support = min_support;
+  a.flags = f.flags, a.blk_cnt = f.blk_cnt, a.dst = d_dst, a.res = f.res;
+  a.sort_scratch = f.sort, a.sort_head_words = sc.head_words;
+  // booked: what each launch has to move at least (keys, indices and stamps once; per neighbour a head and a stamp);
+  // the emit's share for the kept records is booked as if all were kept
+  {
+    ScopedKernel k(c, K_BAF_HEADS, (uint64_t)n * 32);
+    launch_baf_heads(s, a);
+  }
+  {
+    ScopedKernel k(c, K_BAF_FILTER, (uint64_t)n * (16 + 8 * 12 + 1));
+    launch_baf_filter(s, a);
+  }
+  {
+    ScopedKernel k(c, K_BAF_COUNT, (uint64_t)n * (1 + 4 + 8));
+    launch_baf_count(s, a);
+  }
+  {
+    ScopedKernel k(c, K_BAF_SCAN, (uint64_t)baf_blocks(n32) * 8);
+    launch_baf_scan(s, a);
+  }
+  {
+    ScopedKernel k(c, K_BAF_EMIT, (uint64_t)n * 33);
+    launch_baf_emit(s, a);
+  }
+  HIPCHK(c, hipMemcpyAsync(r, f.res, sizeof(BafResult), hipMemcpyDeviceToHost, s));
+  if (flags) HIPCHK(c, hipMemcpyAsync(flags, f.flags, n, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  if (c->prof_on) resolve_profile(c);
+  if (r->err) {  // (the sort did not finish: its scratch words are cleared again; the plane is what the chain made of it)
+    HIPCHK(c, hipMemsetAsync(f.sort, 0, f.sort.cap * 4, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    return fail(c, ESVIO_FE_EINTERNAL, "%s: radix sort look-back spin expired (esvio_fe_filter_reset before the next call)", who);
+  }
+  return 0;
+}
+}  // namespace
+
+int esvio_fe_filter_events(esvio_fe_handle c, int cam, const esvio_fe_event* ev, size_t n, int space, int64_t window_ns,
+                           int min_support, esvio_fe_event* dst, int dst_space, uint64_t* n_kept, uint8_t* flags,
+                           esvio_fe_event* last_kept, uint64_t* n_rejected) {
+  if (!c) return ESVIO_FE_EINVAL;
+  if (n_kept) *n_kept = 0;
+  if (n_rejected) *n_rejected = 0;
+  if (int rc = baf_params_check(c, window_ns, min_support, "filter_events")) return rc;
+  if (cam != 0 && cam != 1) return fail(c, ESVIO_FE_EINVAL, "filter_events: cam must be 0 or 1 (got %d)", cam);
+  if ((space != ESVIO_FE_HOST && space != ESVIO_FE_DEVICE) || (dst_space != ESVIO_FE_HOST && dst_space != ESVIO_FE_DEVICE))
+    return fail(c, ESVIO_FE_EINVAL, "filter_events: bad memory space");
+  if (!n) return 0;
+  if (n >= (1ull << 31)) return fail(c, ESVIO_FE_EINVAL, "filter_events: batch too large");
+  if (!ev) return fail(c, ESVIO_FE_EINVAL, "filter_events: ev is null");
+  if (!dst) return fail(c, ESVIO_FE_EINVAL, "filter_events: dst is null");
+  if (dst_space == ESVIO_FE_DEVICE && ((uintptr_t)dst & 15) != 0)
+    return fail(c, ESVIO_FE_EINVAL, "filter_events: a device dst must be 16-byte aligned");
+  {  // (one address space: a range of one is the same memory under the other name)
+    const uintptr_t a0 = (uintptr_t)ev, b0 = (uintptr_t)dst, len = n * sizeof(EventRec);
+    if (a0 < b0 + len && b0 < a0 + len) return fail(c, ESVIO_FE_EINVAL, "filter_events: dst overlaps ev");
+  }
+  HIPCHK(c, hipSetDevice(c->dev));
+  if (int rc = baf_ensure(c, n, space == ESVIO_FE_HOST, dst_space == ESVIO_FE_HOST)) return rc;
+  EventRec* d_dst = dst_space == ESVIO_FE_HOST ? c->baf.out.p : (EventRec*)dst;
+  BafResult r{};
+  if (int rc = baf_run(c, cam, ev, n, space, window_ns, min_support, d_dst, &r, flags, "filter_events")) return rc;
+  if (dst_space == ESVIO_FE_HOST && r.n_kept) {
+    HIPCHK(c, hipMemcpyAsync(dst, d_dst, (size_t)r.n_kept * sizeof(EventRec), hipMemcpyDeviceToHost, cur_stream(c)));
+    HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  }
+  if (n_kept) *n_kept = r.n_kept;
+  if (n_rejected) *n_rejected = r.n_rejected;
+  if (last_kept && r.n_kept) std::memcpy(last_kept, &r.last, sizeof(EventRec));
+  return 0;
+}
+
+int esvio_fe_filter_reset(esvio_fe_handle c) {
+  if (!c) return ESVIO_FE_EINVAL;
+  HIPCHK(c, hipSetDevice(c->dev));
+  if (int rc = baf_clear(c)) return rc;
+  HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  return 0;
+}
+
+int esvio_fe_track_event_filtered(esvio_fe_handle c, const esvio_fe_event* left, size_t nL, const esvio_fe_event* right,
+                                  size_t nR, int space, int64_t window_ns, int min_support, int pub_this_frame,
+                                  esvio_fe_tracks* out, uint64_t kept[2], double* cur_time_out) {
+  if (!c) return ESVIO_FE_EINVAL;
+  if (kept) kept[0] = kept[1] = 0;
+  if (space != ESVIO_FE_HOST && space != ESVIO_FE_DEVICE) return fail(c, ESVIO_FE_EINVAL, "track_event_filtered: bad memory space");
+  if (int rc = baf_params_check(c, window_ns, min_support, "track_event_filtered")) return rc;
+  if ((nL && !left) || (nR && !right)) return fail(c, ESVIO_FE_EINVAL, "track_event_filtered: a batch with events and no pointer");
+  if (nL + nR >= (1ull << 31)) return fail(c, ESVIO_FE_EINVAL, "batch too large");
+  if (!c->announced.empty() || !c->inflight.empty())
+    return fail(c, ESVIO_FE_EINVAL, "track_event_filtered: batches are announced on this handle (filter into memory of your own)");
+  HIPCHK(c, hipSetDevice(c->dev));
+  EventRec *dL = nullptr, *dR = nullptr;
+  if (int rc = cvt_pair_begin(c, nL, nR, &dL, &dR)) return rc;
+  if (int rc = baf_ensure(c, std::max(nL, nR), space == ESVIO_FE_HOST, false)) return rc;
+  BafResult rL{}, rR{};
+  if (nL)
+    if (int rc = baf_run(c, 0, left, nL, space, window_ns, min_support, dL, &rL, nullptr, "track_event_filtered (left)")) return rc;
+  if (nR)
+    if (int rc = baf_run(c, 1, right, nR, space, window_ns, min_support, dR, &rR, nullptr, "track_event_filtered (right)")) return rc;
+  if (kept) kept[0] = rL.n_kept, kept[1] = rR.n_kept;
+  if (!rL.n_kept) return 0;  // node:150: an empty left message is not tracked (the pair stays this call's: nothing reads it)
+  const double cur_time = (double)rL.last.sec + 1e-9 * (double)rL.last.nsec;
+  if (cur_time_out) *cur_time_out = cur_time;
+  return cvt_pair_track(c, cur_time, dL, rL.n_kept, dR, rR.n_kept, pub_this_frame, out);
 }
 
 // ---- image front-end
@@ -1639,6 +1864,10 @@ int esvio_fe_reserve(esvio_fe_handle c, size_t max_left, size_t max_right, int h
   }
   for (int k = 0; k < kRightSlots; k++)
     if (int rc = ensure_arc_capacity(c, max_left, k)) return rc;
+  // a handle that filters (esvio_fe_filter_events): the stage's scratch for one camera's batch and, for host batches,
+  // the copy of a host source — not the records behind a host dst, which grow on the first call that has one
+  if (c->baf.B)
+    if (int rc = baf_ensure(c, std::max(max_left, max_right), host_batches != 0, false)) return rc;
   if (host_batches) {
     if (int rc = ensure_event_capacity(c, n)) return rc;
     if (stager_enabled(c)) {
@@ -1720,7 +1949,8 @@ int esvio_fe_device_memory(esvio_fe_handle c, size_t* free_bytes, size_t* total_
   return 0;
 }
 
-int esvio_fe_kernel_count(void) { return K_COUNT; }
+int esvio_fe_kernel_count(void) { return kTrackKernels; }
+int esvio_fe_stage_kernel_count(void) { return K_COUNT; }
 const char* esvio_fe_kernel_name(int id) { return (id >= 0 && id < K_COUNT) ? kKernelNames[id] : ""; }
 int esvio_fe_get_kernel_stats(esvio_fe_handle c, int id, double* total_ms, uint64_t* launches,
                               uint64_t* alg_bytes) {

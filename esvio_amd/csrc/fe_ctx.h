@@ -69,7 +69,8 @@ const char* const kKernelNames[K_COUNT] = {
     "k_tile_hist", "k_tile_scan", "k_tile_scatter", "k_tile_apply", "k_sae_keys", "k_radix_pass", "k_sae_apply",
     "k_time_surface4", "k_time_surface", "k_median", "k_clahe", "k_norm_pyr", "k_pyr3", "k_pyr_down", "k_pyr_pad",
     "k_scharr", "k_pad_scharr", "k_lk_f32", "k_lk", "k_arc_map", "k_arc_ev", "k_dedup", "k_compact", "k_select_mw",
-    "k_select", "k_select_gbm", "k_fast_score", "k_fast_collect", "k_events_from_fields"};
+    "k_select", "k_select_gbm", "k_fast_score", "k_fast_collect", "k_events_from_fields", "k_baf_heads", "k_baf_filter",
+    "k_baf_count", "k_baf_scan", "k_baf_emit"};
 
 // The host phases of one trackEvent call, in the order of esvio_fe_latency_call::phase_ms; kPhaseNames is what
 // esvio_fe_latency_phase_name returns and what the ESVIO_FE_TRACE summary prints.  The PH_PUB_* phases are parts of
@@ -480,6 +481,22 @@ struct esvio_fe_ctx {
   // here, {total, detected before non-max}: adjacent, so that one copy brings both to the host.
   CandSet fast_own;
   FastCand fast_own_fc;
+
+  // ---- esvio_fe_filter_events: the background-activity filter of an event batch (include/esvio_fe.h has the rule,
+  // fe_kernels.h the chain).  Everything is allocated by the first filtering call — a handle that never filters
+  // holds none of it — and is the stage's own: the main stream is the only one that touches it.  B: the stamp plane
+  // of each camera, [2][P] nanoseconds, -1 = none.  head: [P], the chain's per-pixel segment heads (never cleared).
+  // Per event, for calls of up to `cap` events: the (key, index) pairs of the sort and its scratch words, the stamps in
+  // sorted order, the flags, the per-block counts.  src / out: a host source's records and the records behind a host
+  // dst, on first use of either.  (esvio_fe_track_event_filtered filters into esvio_fe_track_event_fields' two pairs.)
+  struct Baf {
+    DevBuf<long long> B, tsort;
+    DevBuf<uint32_t> head, keys[2], vals[2], sort, blk_cnt;
+    DevBuf<uint8_t> flags;
+    DevBuf<BafResult> res;
+    DevBuf<EventRec> src, out;
+    size_t cap = 0;
+  } baf;
 };
 
 namespace esvio {

@@ -71,8 +71,20 @@ enum KernelId {
   K_FAST_SCORE,      // (appended: the ids above keep their meaning)
   K_FAST_COLLECT,
   K_EVENTS_FROM_FIELDS,
+  // ---- from here on: kernels of stages that no track call launches (kTrackKernels below).  A kernel of a track path
+  // is appended ABOVE this line — the ids below move up by one; nothing outside the library holds them as numbers
+  K_BAF_HEADS,       // esvio_fe_filter_events (its key and sort launches are booked as K_SAE_KEYS / K_RADIX_PASS)
+  K_BAF_FILTER,
+  K_BAF_COUNT,
+  K_BAF_SCAN,
+  K_BAF_EMIT,
   K_COUNT
 };
+// esvio_fe_kernel_count(): the kernels of the tracker's entry points, the table bench.py and the recorded launch traces
+// list.  The ids from here on belong to stages off every track path and are listed by esvio_fe_stage_kernel_count().
+constexpr int kTrackKernels = K_BAF_HEADS;
+static_assert(K_EVENTS_FROM_FIELDS + 1 == kTrackKernels && K_BAF_EMIT + 1 == K_COUNT,
+              "a track-path kernel goes in front of K_BAF_HEADS (and into this assertion), a stage's kernel behind it");
 
 // ---- SAE update -------------------------------------------------------------------------
 // Bounds of the device-side waits (every one gives up instead of hanging the GPU; the host then fails
@@ -513,6 +525,44 @@ struct FieldsArgs {
   int64_t t_offset;
 };
 void launch_events_from_fields(hipStream_t s, const FieldsArgs& a, size_t n, EventRec* dst, unsigned long long* n_bad);
+
+// ---- background-activity filter of an event batch (esvio_fe_filter_events) -------------------
+// include/esvio_fe.h holds the rule.  The chain: launch_sae_keys (keys = y*W + x, out-of-sensor events = P: they sort
+// last; values = event index) -> launch_radix_pass x passes -> heads -> filter -> count -> scan -> emit, all on one
+// stream, each launch reading what the launches before it wrote; no launch of these five waits on the device.
+struct BafResult {  // zeroed by the host in front of the chain
+  unsigned long long n_rejected;  // k_sae_keys
+  uint32_t n_kept;                // k_baf_scan
+  int err;                        // k_radix_pass: a look-back wait expired
+  EventRec last;                  // k_baf_emit: the last kept record (untouched if none)
+};
+static_assert(sizeof(BafResult) == 32, "BafResult layout");
+constexpr uint32_t kBafBlock = 1024;  // events per block of the ordered compaction (four flags per lane)
+inline uint32_t baf_blocks(uint32_t n) { return (n + kBafBlock - 1) / kBafBlock; }
+struct BafArgs {
+  const EventRec* ev;    // [n] the call's events, device memory
+  uint32_t n;
+  uint32_t P;            // W * H, also the key of an out-of-sensor event
+  int W, H;
+  const uint32_t* keys;  // [n] sorted ...
+  const uint32_t* vals;  // ... with their event indices (ascending inside a key: the sort is stable)
+  uint32_t* head;        // [P] position of a pixel's first pair; stale entries are recognised, never cleared
+  long long* tsort;      // [n] stamps (ns) in sorted order
+  long long* B;          // [P] the camera's plane: -1 = none, else the stamp in ns
+  long long window_ns;
+  int min_support;
+  uint8_t* flags;        // [n rounded up to 4] keep_i, by event index
+  uint32_t* blk_cnt;     // [baf_blocks(n) + 1] kept per block, then their exclusive offsets and the total
+  EventRec* dst;         // [n] the kept records in stream order; must not overlap ev
+  BafResult* res;
+  uint32_t* sort_scratch;  // the sort's ghist + tickets, cleared by launch_baf_filter (sort_head_words words)
+  uint32_t sort_head_words;
+};
+void launch_baf_heads(hipStream_t s, const BafArgs& a);
+void launch_baf_filter(hipStream_t s, const BafArgs& a);
+void launch_baf_count(hipStream_t s, const BafArgs& a);   // + the plane update
+void launch_baf_scan(hipStream_t s, const BafArgs& a);
+void launch_baf_emit(hipStream_t s, const BafArgs& a);
 
 struct SelectArgs {
   const uint32_t* comp_xy;   // compacted candidates in stream order

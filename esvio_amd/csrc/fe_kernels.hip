@@ -3894,6 +3894,187 @@ void launch_events_from_fields(hipStream_t s, const FieldsArgs& a, size_t n, Eve
 #undef ESVIO_FIELDS_CASE
 }
 
+// ============================================================================ background-activity filter
+// esvio_fe_filter_events (include/esvio_fe.h is the specification): an event is kept iff at least min_support of its
+// 8 neighbour pixels hold a stamp less than window_ns older than its own — "hold" as of just before the event, in
+// stream order.  The stamp pixel q holds just before event i is the stamp of the last event j < i of this call at q,
+// else the carried-in plane B[q]: a predecessor query in q's events kept in stream order.  The stable sort of
+// (pixel key, event index) pairs (k_sae_keys + k_radix_pass) lays every pixel's events out as one segment with
+// ascending indices, so "the last j < i at q" is the end of a monotone predicate over the positions from the segment's
+// head on: keys[pos] == q && vals[pos] < i.  Nothing here depends on the stamps being ordered.
+//   k_baf_heads   per sorted position: the event's stamp in sorted order (tsort), and head[pixel] = position for a
+//                 segment's first pair.  head[] is never cleared: an entry is believed only if it points at a pair of
+//                 that pixel whose predecessor is not (that is the pixel's head, whoever wrote it and when).
+//   k_baf_filter  per sorted position (neighbouring lanes = the same or adjacent pixels, so their look-ups share
+//                 lines): 8 x {head, gallop + bisect for the predecessor, else B}; flags[event index] = keep.
+//                 Also clears the sort's digit histograms and tickets for the next call, as k_sae_apply does.
+//   k_baf_count   per block of kBafBlock events in stream order: how many are kept; and, per sorted position, the
+//                 plane update B[pixel] = stamp of the segment's last pair (every look-up of the call is done)
+//   k_baf_scan    one block: exclusive offsets of the blocks, the total
+//   k_baf_emit    per block: the kept records to dst[offset + rank], whole 16 bytes, and the last kept one
+// No kernel waits for another block: the only device-side wait of the chain is k_radix_pass's bounded look-back.
+constexpr long long kBafNone = -1;  // (stamps are sec * 10^9 + nsec >= 0: a stamp 0 is a stamp)
+
+__device__ __forceinline__ bool baf_is_head(const uint32_t* __restrict__ keys, uint32_t n, uint32_t s, uint32_t q) {
+  return s < n && keys[s] == q && (s == 0 || keys[s - 1] != q);
+}
+
+__global__ __launch_bounds__(256) void k_baf_heads(BafArgs a) {
+  const uint32_t p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= a.n) return;
+  const uint32_t k = a.keys[p];
+  // (an index is below n by construction; the min() holds where a sort pass gave up, BafResult::err, and left the
+  // buffers as they were)
+  const uint4 e = ((const uint4*)a.ev)[min(a.vals[p], a.n - 1)];
+  a.tsort[p] = (long long)e.y * 1000000000ll + (long long)e.z;
+  if (k < a.P && (p == 0 || a.keys[p - 1] != k)) a.head[k] = p;
+}
+
+__global__ __launch_bounds__(256) void k_baf_filter(BafArgs a) {
+  const uint32_t gid = blockIdx.x * 256 + threadIdx.x;
+  for (uint32_t j = gid; j < a.sort_head_words; j += gridDim.x * 256) a.sort_scratch[j] = 0;
+  const uint32_t p = gid;
+  if (p >= a.n) return;
+  const uint32_t k = a.keys[p], i = a.vals[p];
+  if (i >= a.n) return;  // (only behind a sort pass that gave up)
+  if (k >= a.P) {  // out of the sensor: rejected (counted by k_sae_keys), supports nothing, no look-up
+    a.flags[i] = 0;
+    return;
+  }
+  const long long t = a.tsort[p];
+  const int x = (int)(k % (uint32_t)a.W), y = (int)(k / (uint32_t)a.W);
+  int support = 0;
+#pragma unroll
+  for (int d = 0; d < 9; d++) {
+    if (d == 4) continue;
+    const int nx = x + d % 3 - 1, ny = y + d / 3 - 1;
+    if ((unsigned)nx >= (unsigned)a.W || (unsigned)ny >= (unsigned)a.H) continue;
+    const uint32_t q = (uint32_t)ny * (uint32_t)a.W + (uint32_t)nx;
+    long long tb = kBafNone;
+    bool found = false;
+    const uint32_t s = a.head[q];
+    if (baf_is_head(a.keys, a.n, s, q) && a.vals[s] < i) {
+      // ok(pos) = keys[pos] == q && vals[pos] < i holds at s and is monotone from there: gallop, then bisect
+      uint32_t lo = s, step = 1;
+      for (;;) {
+        const uint32_t hi = lo + step;
+        if (hi < lo || hi >= a.n || a.keys[hi] != q || a.vals[hi] >= i) break;
+        lo = hi;
+        step <<= 1;
+      }
+      uint32_t hi = lo + step;
+      if (hi < lo || hi > a.n) hi = a.n;
+      while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (a.keys[mid] == q && a.vals[mid] < i) lo = mid;
+        else hi = mid;
+      }
+      tb = a.tsort[lo];
+      found = true;
+    } else {
+      tb = a.B[q];
+      found = tb != kBafNone;
+    }
+    support += (found && t - tb < a.window_ns) ? 1 : 0;
+  }
+  a.flags[i] = support >= a.min_support ? 1 : 0;
+}
+
+// flags[4w .. 4w+3] as one word (one lane's share of the compaction), the bytes of events behind the n-th cleared
+__device__ __forceinline__ uint32_t baf_flag_word(const BafArgs& a, uint32_t w) {
+  const uint32_t i0 = w * 4;
+  if (i0 >= a.n) return 0;
+  uint32_t f = ((const uint32_t*)a.flags)[w] & 0x01010101u;
+  if (a.n - i0 < 4) f &= (1u << (8 * (a.n - i0))) - 1u;
+  return f;
+}
+
+__global__ __launch_bounds__(256) void k_baf_count(BafArgs a) {
+  __shared__ uint32_t part[4];
+  uint32_t c = __popc(baf_flag_word(a, blockIdx.x * 256 + threadIdx.x));
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+  if (lane_id() == 0) part[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) a.blk_cnt[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+  // the plane after the call: every touched pixel's last event of the call
+  for (uint32_t p = blockIdx.x * 256 + threadIdx.x; p < a.n; p += gridDim.x * 256) {
+    const uint32_t k = a.keys[p];
+    if (k < a.P && (p + 1 == a.n || a.keys[p + 1] != k)) a.B[k] = a.tsort[p];
+  }
+}
+
+constexpr int kBafScanThreads = 1024;
+__global__ __launch_bounds__(kBafScanThreads) void k_baf_scan(BafArgs a, uint32_t nblk) {
+  __shared__ uint32_t wsum[kBafScanThreads / 64];
+  const uint32_t per = (nblk + kBafScanThreads - 1) / kBafScanThreads;
+  const uint32_t lo = min(threadIdx.x * per, nblk), hi = min(lo + per, nblk);
+  uint32_t sum = 0;
+  for (uint32_t j = lo; j < hi; j++) sum += a.blk_cnt[j];
+  uint32_t incl = sum;  // inclusive scan over the wave, then over the 16 waves
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t v = __shfl_up(incl, o);
+    if (lane_id() >= o) incl += v;
+  }
+  if (lane_id() == 63) wsum[threadIdx.x >> 6] = incl;
+  __syncthreads();
+  uint32_t run = incl - sum;
+  for (int w = 0; w < (int)(threadIdx.x >> 6); w++) run += wsum[w];
+  for (uint32_t j = lo; j < hi; j++) {
+    const uint32_t c = a.blk_cnt[j];
+    a.blk_cnt[j] = run;
+    run += c;
+  }
+  if (threadIdx.x == kBafScanThreads - 1) {
+    a.blk_cnt[nblk] = run;
+    a.res->n_kept = run;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_baf_emit(BafArgs a, uint32_t nblk) {
+  __shared__ uint32_t part[4];
+  const uint32_t w = blockIdx.x * 256 + threadIdx.x;
+  const uint32_t f = baf_flag_word(a, w);
+  const uint32_t c = __popc(f);
+  uint32_t incl = c;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t v = __shfl_up(incl, o);
+    if (lane_id() >= o) incl += v;
+  }
+  if (lane_id() == 63) part[threadIdx.x >> 6] = incl;
+  __syncthreads();
+  uint32_t pos = a.blk_cnt[blockIdx.x] + incl - c;
+  for (int wv = 0; wv < (int)(threadIdx.x >> 6); wv++) pos += part[wv];
+  const uint32_t total = a.blk_cnt[nblk];
+  const uint4* src = (const uint4*)a.ev;
+  uint4* dst = (uint4*)a.dst;
+#pragma unroll
+  for (int j = 0; j < 4; j++)
+    if (f & (1u << (8 * j))) {
+      const uint4 e = src[(size_t)w * 4 + j];
+      dst[pos++] = e;
+      if (pos == total) *(uint4*)&a.res->last = e;
+    }
+}
+
+void launch_baf_heads(hipStream_t s, const BafArgs& a) {
+  if (a.n) launch_k(k_baf_heads, dim3((a.n + 255) / 256), dim3(256), 0, s, a);
+}
+void launch_baf_filter(hipStream_t s, const BafArgs& a) {
+  if (a.n) launch_k(k_baf_filter, dim3((a.n + 255) / 256), dim3(256), 0, s, a);
+}
+void launch_baf_count(hipStream_t s, const BafArgs& a) {
+  if (a.n) launch_k(k_baf_count, dim3(baf_blocks(a.n)), dim3(256), 0, s, a);
+}
+void launch_baf_scan(hipStream_t s, const BafArgs& a) {
+  if (a.n) launch_k(k_baf_scan, dim3(1), dim3(kBafScanThreads), 0, s, a, baf_blocks(a.n));
+}
+void launch_baf_emit(hipStream_t s, const BafArgs& a) {
+  if (a.n) launch_k(k_baf_emit, dim3(baf_blocks(a.n)), dim3(256), 0, s, a, baf_blocks(a.n));
+}
+
 // ============================================================================ greedy selection
 // Event_FeaturesToTrack (feature_tracker.cpp:13-38): candidates in stream order; accept iff the
 // pixel is not blocked; stamp cv::circle(r = MIN_DIST, filled) [OpenCV midpoint disc]; stop at

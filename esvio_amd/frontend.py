@@ -95,7 +95,7 @@ ABI_SYMBOLS = [
     "esvio_fe_convert_events", "esvio_fe_create",
     "esvio_fe_create_sae", "esvio_fe_create_sae_stereo", "esvio_fe_create_sae_stereo_mc", "esvio_fe_destroy",
     "esvio_fe_exchange_begin", "esvio_fe_exchange_end", "esvio_fe_exchange_tracks", "esvio_fe_export_image",
-    "esvio_fe_fast_corners", "esvio_fe_features_to_track", "esvio_fe_features_to_track_fast", "esvio_fe_find_fundamental_mat", "esvio_fe_finish", "esvio_fe_get_sae",
+    "esvio_fe_fast_corners", "esvio_fe_filter_events", "esvio_fe_filter_reset", "esvio_fe_features_to_track", "esvio_fe_features_to_track_fast", "esvio_fe_find_fundamental_mat", "esvio_fe_finish", "esvio_fe_get_sae",
     "esvio_fe_get_time_surface", "esvio_fe_good_features_to_track", "esvio_fe_import_image", "esvio_fe_is_corner",
     "esvio_fe_last_error", "esvio_fe_mem_alloc", "esvio_fe_mem_free", "esvio_fe_mem_upload",
     "esvio_fe_pack_track_records", "esvio_fe_register_host_buffer", "esvio_fe_reserve", "esvio_fe_reset",
@@ -103,7 +103,7 @@ ABI_SYMBOLS = [
     "esvio_fe_sae_slice_last", "esvio_fe_sae_to_time_surface", "esvio_fe_set_auto_exchange", "esvio_fe_set_detector",
     "esvio_fe_set_host_threads", "esvio_fe_set_launch_thread", "esvio_fe_set_lazy_new_stereo",
     "esvio_fe_set_next_batch", "esvio_fe_set_next_batch_mc", "esvio_fe_track_event", "esvio_fe_track_event_fields",
-    "esvio_fe_track_event_mc",
+    "esvio_fe_track_event_filtered", "esvio_fe_track_event_mc",
     "esvio_fe_track_image", "esvio_fe_unregister_host_buffer", "esvio_fe_version",
 ]
 # test / measurement taps: include/esvio_fe_test.h (not part of the boundary)
@@ -116,7 +116,7 @@ TEST_SYMBOLS = [
     "esvio_fe_kernel_count", "esvio_fe_kernel_name", "esvio_fe_latency_phase_name", "esvio_fe_latency_recent",
     "esvio_fe_latency_stats", "esvio_fe_lift_projective", "esvio_fe_plain_call_counters", "esvio_fe_ransac_stats",
     "esvio_fe_ransac_tail", "esvio_fe_reset_kernel_stats", "esvio_fe_set_profiling", "esvio_fe_set_sae",
-    "esvio_fe_stream",
+    "esvio_fe_stage_kernel_count", "esvio_fe_stream",
 ]
 
 LATENCY_PHASES = 16
@@ -210,6 +210,11 @@ def load_library(build_if_missing=True):
     L.esvio_fe_convert_events.argtypes = [vp, C.POINTER(EventFieldsDesc), sz, i, vp, i, C.POINTER(C.c_uint64)]
     L.esvio_fe_track_event_fields.argtypes = [vp, d, C.POINTER(EventFieldsDesc), sz, C.POINTER(EventFieldsDesc), sz, i, i,
                                               C.POINTER(Tracks)]
+    L.esvio_fe_filter_events.argtypes = [vp, i, vp, sz, i, C.c_int64, i, vp, i, C.POINTER(C.c_uint64), vp, vp,
+                                         C.POINTER(C.c_uint64)]
+    L.esvio_fe_filter_reset.argtypes = [vp]
+    L.esvio_fe_track_event_filtered.argtypes = [vp, vp, sz, vp, sz, i, C.c_int64, i, i, C.POINTER(Tracks),
+                                                C.POINTER(C.c_uint64 * 2), C.POINTER(d)]
     L.esvio_fe_set_profiling.argtypes = [vp, i]
     L.esvio_fe_kernel_name.restype = C.c_char_p
     L.esvio_fe_kernel_name.argtypes = [i]
@@ -447,6 +452,56 @@ class FeatureTracker:
             self._hd.h, float(cur_time), C.byref(dl), left_fields.n, C.byref(dr), right_fields.n, src_space,
             int(PUB_THIS_FRAME), C.byref(self._tr)))
         return self._take(copy)
+
+    def filter_events(self, cam, ev, window_ns, min_support=1, device=False):
+        """the background-activity filter stage (esvio_fe_filter_events; include/esvio_fe.h has the rule): advances
+        camera `cam`'s stamp plane by the events `ev` (a numpy EVENT_DTYPE array, or a (device_ptr, n) tuple) and
+        returns (kept, flags, n_rejected).  kept: the kept records in stream order — a numpy array, or with
+        device=True a FilteredEvents in device memory (`.arg`: what every entry point takes for device events,
+        set_next_batch included; `.n`, `.last`: the last kept record or None; `.free()`).  flags: keep_i per event."""
+        from .events import EVENT_DTYPE
+        ptr, n, space, keep = _events_arg(ev)
+        flags = np.zeros(n, np.uint8)
+        nk, rej = C.c_uint64(0), C.c_uint64(0)
+        last = np.zeros(1, EVENT_DTYPE)
+        L = self._hd.L
+        if device:
+            dst = C.c_void_p()
+            rc = L.esvio_fe_mem_alloc(DEVICE, 16 * max(n, 1), C.byref(dst))
+            if rc:
+                raise FrontendError("esvio_fe_mem_alloc rc=%d" % rc)
+            out = None
+        else:
+            out = np.zeros(n, EVENT_DTYPE)
+            dst = _p(out)
+        rc = L.esvio_fe_filter_events(self._hd.h, int(cam), ptr, n, space, int(window_ns), int(min_support), dst,
+                                      DEVICE if device else HOST, C.byref(nk), _p(flags), _p(last), C.byref(rej))
+        if rc and device:
+            L.esvio_fe_mem_free(DEVICE, dst)
+        self._hd.check(rc)
+        k = int(nk.value)
+        kept = FilteredEvents(dst, k, last[0] if k else None) if device else out[:k]
+        return kept, flags, int(rej.value)
+
+    def filter_reset(self):
+        """every stamp plane of the background-activity filter back to `none` (esvio_fe_filter_reset)"""
+        self._hd.check(self._hd.L.esvio_fe_filter_reset(self._hd.h))
+
+    def trackEventFiltered(self, left, right, window_ns, min_support=1, pub=True, copy=True):
+        """filter both cameras' batches, then trackEvent on the kept records at the stamp of the last kept left
+        event (esvio_fe_track_event_filtered).  Returns (kept, cur_time): kept = (left, right) counts; with
+        kept[0] == 0 nothing was tracked, cur_time is None and the result members are the previous call's."""
+        pl, nl, sl, k1 = _events_arg(left)
+        pr, nr, sr, k2 = _events_arg(right)
+        assert sl == sr
+        kept = (C.c_uint64 * 2)()
+        t = C.c_double(0.0)
+        self._hd.check(self._hd.L.esvio_fe_track_event_filtered(
+            self._hd.h, pl, nl, pr, nr, sl, int(window_ns), int(min_support), int(pub), C.byref(self._tr),
+            C.byref(kept), C.byref(t)))
+        if kept[0]:
+            self._take(copy)
+        return (int(kept[0]), int(kept[1])), (t.value if kept[0] else None)
 
     _LEFT = frozenset(("ids", "track_cnt", "cur_pts", "cur_un_pts", "pts_velocity"))
     _RIGHT = frozenset(("ids_right", "cur_right_pts", "cur_un_right_pts", "right_pts_velocity"))
@@ -811,10 +866,11 @@ class FeatureTracker:
     def reset_kernel_stats(self):
         self._hd.check(self._hd.L.esvio_fe_reset_kernel_stats(self._hd.h))
 
-    def kernel_stats(self):
+    def kernel_stats(self, stages=False):
+        """per kernel of the track paths (stages=True: and of the stages off them, esvio_fe_filter_events' k_baf_*)"""
         L = self._hd.L
         out = {}
-        for k in range(L.esvio_fe_kernel_count()):
+        for k in range(L.esvio_fe_stage_kernel_count() if stages else L.esvio_fe_kernel_count()):
             ms, n, b = C.c_double(0), C.c_uint64(0), C.c_uint64(0)
             self._hd.check(L.esvio_fe_get_kernel_stats(self._hd.h, k, C.byref(ms), C.byref(n),
                                                        C.byref(b)))
@@ -900,6 +956,20 @@ class ConvertedEvents:
             load_library().esvio_fe_mem_free(DEVICE, self.ptr)
             self.ptr = None
         self.array = None
+
+
+class FilteredEvents:
+    """the records esvio_fe_filter_events kept, in device memory of the library's runtime: `.arg` is the (pointer, n)
+    tuple of ESVIO_FE_DEVICE, `.last` the last kept record (None if there is none)"""
+
+    def __init__(self, ptr, n, last):
+        self.space, self.ptr, self.n, self.last = DEVICE, ptr, n, last
+        self.arg = (ptr.value, n)
+
+    def free(self):
+        if self.ptr:
+            load_library().esvio_fe_mem_free(DEVICE, self.ptr)
+            self.ptr = None
 
 
 class RegisteredEvents:

@@ -427,6 +427,66 @@ int esvio_fe_track_event_fields(esvio_fe_handle h, double cur_time, const esvio_
                                 const esvio_fe_event_fields* right, size_t nR, int src_space,
                                 int pub_this_frame, esvio_fe_tracks* out);
 
+/* ---- background-activity noise filter of an event batch, on the device -------------------- */
+/* The reference's live path never sees raw sensor noise: its DAVIS driver switches the camera's hardware
+ * background-activity filter on by default (dependences/rpg_dvs_ros/davis_ros_driver/cfg/DAVIS_ROS_Driver.cfg:28-29:
+ * enabled, 80 x 250 us = 20 ms; src/driver.cpp:461-464), so every batch trackEvent gets over ROS has passed it.
+ * Recordings, vendor SDKs and simulators hand over unfiltered streams.  That filter is FPGA logic: there is nothing
+ * of the reference to be equal to, so — as for ESVIO_FE_DETECT_FAST and the event layouts — THIS TEXT IS THE
+ * SPECIFICATION, and the kernels equal its sequential reading (tests/ba_filter_ref.py) exactly.
+ *
+ * Per handle and camera a plane B[x + y*width] holds, per pixel, either `none` or a stamp in integer nanoseconds.  A
+ * fresh handle holds `none` everywhere.  (8 bytes per pixel and camera, allocated by the first filtering call: a
+ * handle that never filters allocates nothing for it.)  For the events of one call, in stream order, i = 0 .. n-1:
+ *  1. x >= width or y >= height: the event is REJECTED — counted in *n_rejected, flag 0, not emitted; it neither
+ *     reads nor writes B.
+ *  2. t = sec * 10^9 + nsec, exact in 64-bit integers; nsec is taken as it is, also when it is >= 10^9.
+ *  3. support = the number of the 8 neighbour pixels (x+dx, y+dy), dx, dy in {-1,0,1}, not both 0, for which all of
+ *     these hold: the pixel lies inside the sensor; B there is not `none`; t - B < window_ns as a SIGNED 64-bit
+ *     difference (a neighbour stamped later than t has a negative difference and counts).  The event's own pixel
+ *     never counts.  Polarity is ignored.
+ *  4. keep_i = (support >= min_support).
+ *  5. B[x + y*width] = t — always, kept or not.
+ * The kept events are emitted in stream order, all 16 bytes of each record copied as they are.  B carries over from
+ * call to call (the first events of a batch find the support the previous batch left).  An event stamped 0 supports
+ * like any other: `none` is not stamp 0.  Nothing is assumed about the order of the stamps: non-monotonic stamps,
+ * equal stamps and stamps stepping back a second give what the loop above gives.
+ * Limits: 1 <= window_ns <= 2^62, 1 <= min_support <= 8.  With min_support 1 (and the strict <) this is the classic
+ * software form of the filter (jAER's BackgroundActivityFilter; libcaer's dvsnoise with supportMin), restated from
+ * recall: it is unpinned, and not claimed to be bit-equal to the DAVIS FPGA.  The sensor's refractory filter (off by
+ * default in the reference's driver) is not part of it.
+ *
+ * the filter stage: advances camera `cam`'s plane B by the n events of `ev` (space: ESVIO_FE_HOST — copied to the
+ * device as they are, one copy — or ESVIO_FE_DEVICE, read in place) and writes the kept records, in order, to dst
+ * (room for n records; ESVIO_FE_DEVICE: 16-byte aligned device memory, may be handed to every entry point that takes
+ * device events, esvio_fe_set_next_batch included; ESVIO_FE_HOST: downloaded).  flags (optional, host, n bytes): keep_i.
+ * *last_kept (optional): the last kept record (untouched if none).  n == 0 succeeds and touches nothing.
+ * Orders itself on the main stream, waits for its own result, touches nothing of the tracker: made between two track
+ * calls (announced batches or not) it changes no later tracking result.  Its scratch grows on first use (and with
+ * esvio_fe_reserve, for a handle that has filtered before: the per-event scratch for max(max_left, max_right) events
+ * and, with host_batches, the copy of a host source; the records behind a host dst grow on the first call that has
+ * one): the second call of a size allocates nothing.
+ * ESVIO_FE_EINVAL with a message, before any device work: window_ns or min_support outside the limits, cam outside
+ * 0..1, a bad space, a null ev or dst with n > 0, a misaligned device dst, dst overlapping ev. */
+int esvio_fe_filter_events(esvio_fe_handle h, int cam, const esvio_fe_event* ev, size_t n, int space,
+                           int64_t window_ns, int min_support, esvio_fe_event* dst, int dst_space,
+                           uint64_t* n_kept, uint8_t* flags, esvio_fe_event* last_kept, uint64_t* n_rejected);
+/* all planes B back to `none` (esvio_fe_reset does the same as part of "as a freshly created handle") */
+int esvio_fe_filter_reset(esvio_fe_handle h);
+/* filter both cameras into buffers of the handle, then esvio_fe_track_event on the kept records with
+ * cur_time = (double)sec + 1e-9 * (double)nsec of the last KEPT left event (what node:190 reads from a message the
+ * sensor had already filtered); *cur_time_out (optional) returns it.  kept[0] == 0: nothing is tracked and nothing
+ * of the tracker changes (node:150 returns early on an empty left message) — the call returns ESVIO_FE_OK, `out`
+ * is untouched, both planes B have advanced.  Buffer lifetime and "not with announced batches" exactly as
+ * esvio_fe_track_event_fields (two alternating pairs — the same two).
+ * A caller whose publish decision reads the batch's last stamp (node:190-200 decides PUB_THIS_FRAME from the message's
+ * last event) cannot know that stamp before the filter has run: it uses the two-step form — esvio_fe_filter_events
+ * per camera into device memory with last_kept, decide, then esvio_fe_track_event on the device records. */
+int esvio_fe_track_event_filtered(esvio_fe_handle h, const esvio_fe_event* left, size_t nL,
+                                  const esvio_fe_event* right, size_t nR, int space, int64_t window_ns,
+                                  int min_support, int pub_this_frame, esvio_fe_tracks* out,
+                                  uint64_t kept[2], double* cur_time_out);
+
 /* ---- camera split across GPUs (BASELINE config C4) ----------------------- */
 /* The left and right cameras have disjoint SAE state (sae_/sae_latest_ vs sae_right/
  * sae_latest_right, event_detector.h:74-79), so a second GPU can own the right camera: it runs

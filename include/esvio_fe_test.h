@@ -156,6 +156,10 @@ int esvio_fe_latency_recent(esvio_fe_handle h, int back, esvio_fe_latency_call* 
  * bracketed by hipEventRecord and resolved lazily). */
 int esvio_fe_set_profiling(esvio_fe_handle h, int on);
 int esvio_fe_kernel_count(void);
+/* ids 0 .. esvio_fe_kernel_count()-1: the kernels of the tracker's entry points; ids up to
+ * esvio_fe_stage_kernel_count()-1: those and the kernels of stages no track call launches (esvio_fe_filter_events).
+ * esvio_fe_kernel_name and esvio_fe_get_kernel_stats take every id below esvio_fe_stage_kernel_count(). */
+int esvio_fe_stage_kernel_count(void);
 const char* esvio_fe_kernel_name(int kernel_id);
 /* total_ms / launches / algorithmic bytes accumulated since the last reset_kernel_stats */
 int esvio_fe_get_kernel_stats(esvio_fe_handle h, int kernel_id, double* total_ms,

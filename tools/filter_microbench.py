@@ -1,0 +1,117 @@
+"""esvio_fe_filter_events micro-benchmark: per-launch times of the filter's chain (esvio_fe_get_kernel_stats: k_sae_keys,
+k_radix_pass x passes, k_baf_heads, k_baf_filter, k_baf_count, k_baf_scan, k_baf_emit) and the whole call's wall time,
+at C3's batch (640 x 480, ~167 k events) and C5's (1280 x 720, ~3.3 M), on the scene stream and on the uniform stream,
+from device memory into device memory, with the bytes each launch is booked with.  Beside it, measured in the same
+run on the same events: the SAE update chain (k_tile_hist, k_tile_scan, k_tile_scatter, k_tile_apply) of
+esvio_fe_create_sae, the existing event-proportional pass of a batch.  The filter runs with the reference driver's
+20 ms window and support 1, every call on fresh planes (esvio_fe_filter_reset between the calls, not timed).  Per
+figure: the median of BLOCKS blocks of REPS calls after a warm-up block, and the blocks' min - max.  One process, one
+pass, no retries; run it under a time limit:
+
+    timeout -k 10 600 python tools/filter_microbench.py [--json out.json]
+"""
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np  # noqa: E402
+
+from esvio_amd import frontend as FE  # noqa: E402
+from esvio_amd.synth import SceneStream, uniform_batch  # noqa: E402
+
+BLOCKS, REPS = 5, 10
+WINDOW_NS, MIN_SUPPORT = 20_000_000, 1
+SIZES = (("C3", 640, 480, 167_000), ("C5", 1280, 720, 3_300_000))
+FILTER_CHAIN = ("k_sae_keys", "k_radix_pass", "k_baf_heads", "k_baf_filter", "k_baf_count", "k_baf_scan", "k_baf_emit")
+SAE_CHAIN = ("k_tile_hist", "k_tile_scan", "k_tile_scatter", "k_tile_apply")
+
+
+def med(v):
+    return float(np.median(v)), float(np.min(v)), float(np.max(v))
+
+
+def streams(w, h, n):
+    """~n left events of one 1/30 s batch: the bench scene (7 % uniform noise) and uniform noise alone"""
+    scene = SceneStream(W=w, H=h, rate=n * 30.0, seed=11).next_batch()[0]
+    uni = uniform_batch(w, h, n, 1_000_000_000, 33_333, np.random.default_rng(12))
+    return (("scene", scene), ("uniform", uni))
+
+
+def measure(tr, call, chain, between=None):
+    """-> {kernel: (us per call: median, min, max), launches per call, booked bytes per call}, call wall us"""
+    for _ in range(REPS):
+        if between:
+            between()
+        call()
+    per, wall = {k: [] for k in chain}, []
+    info = {}
+    for _ in range(BLOCKS):
+        tr.set_profiling(True)
+        tr.reset_kernel_stats()
+        t = 0.0
+        for _ in range(REPS):
+            if between:
+                between()
+            t0 = time.perf_counter()
+            call()
+            t += time.perf_counter() - t0
+        wall.append(t / REPS * 1e6)
+        st = tr.kernel_stats(stages=True)
+        tr.set_profiling(False)
+        for k in chain:
+            per[k].append(st[k]["ms"] / REPS * 1e3)
+            info[k] = (st[k]["launches"] / REPS, st[k]["alg_bytes"] / REPS)
+    return {k: (med(per[k]),) + info[k] for k in chain}, med(wall), [sum(per[k][b] for k in chain) for b in range(BLOCKS)]
+
+
+def main():
+    L = FE.load_library()
+    rows = []
+    for tag, w, h, n_target in SIZES:
+        tr = FE.FeatureTracker(FE.make_config(w, h))
+        for name, ev in streams(w, h, n_target):
+            n = len(ev)
+            src = FE.EventBuffer(ev, FE.DEVICE)
+            dst = C.c_void_p()
+            assert L.esvio_fe_mem_alloc(FE.DEVICE, 16 * n, C.byref(dst)) == 0
+            nk, rej = C.c_uint64(0), C.c_uint64(0)
+
+            def filt():
+                assert L.esvio_fe_filter_events(tr._hd.h, 0, C.c_void_p(src.arg[0]), n, FE.DEVICE, WINDOW_NS, MIN_SUPPORT, dst,
+                                                FE.DEVICE, C.byref(nk), None, None, C.byref(rej)) == 0
+
+            def sae():
+                tr.detector.createSAE_left(src.arg)
+
+            fk, fwall, fsum = measure(tr, filt, FILTER_CHAIN, between=tr.filter_reset)
+            sk, swall, ssum = measure(tr, sae, SAE_CHAIN)
+            print("%s %dx%d %-8s n %8d, kept %.3f, rejected %d" % (tag, w, h, name, n, nk.value / n, rej.value))
+            for title, ks, wall, tot in (("filter", fk, fwall, fsum), ("SAE update", sk, swall, ssum)):
+                for k, (us, launches, nbytes) in ks.items():
+                    print("    %-16s %9.1f us (%.1f - %.1f)  %4.1f launches  %7.1f B/event booked = %6.0f GB/s"
+                          % (k, us[0], us[1], us[2], launches, nbytes / n, nbytes / max(us[0], 1e-9) / 1e3))
+                t = med(tot)
+                print("  %-10s chain %9.1f us (%.1f - %.1f) = %7.1f Mev/s | call %9.1f us (%.1f - %.1f) = %7.1f Mev/s"
+                      % (title, t[0], t[1], t[2], n / t[0], wall[0], wall[1], wall[2], n / wall[0]))
+            f, s = med(fsum)[0], med(ssum)[0]
+            print("  filter chain / SAE chain = %.2f" % (f / s))
+            rows.append(dict(batch=tag, width=w, height=h, stream=name, n=n, kept=int(nk.value), rejected=int(rej.value),
+                             window_ns=WINDOW_NS, min_support=MIN_SUPPORT,
+                             filter={k: dict(us=v[0], launches=v[1], booked_bytes=v[2]) for k, v in fk.items()},
+                             sae={k: dict(us=v[0], launches=v[1], booked_bytes=v[2]) for k, v in sk.items()},
+                             filter_chain_us=med(fsum), sae_chain_us=med(ssum), filter_call_us=fwall, sae_call_us=swall,
+                             ratio=f / s))
+            src.free()
+            L.esvio_fe_mem_free(FE.DEVICE, dst)
+        tr.close()
+    if "--json" in sys.argv:
+        with open(sys.argv[sys.argv.index("--json") + 1], "w") as fo:
+            json.dump(rows, fo, indent=1)
+
+
+if __name__ == "__main__":
+    main()
