@@ -355,7 +355,7 @@ int esvio_fe_create(const esvio_fe_config* cfg, esvio_fe_handle* out) {
 
 namespace {
 int baf_clear(esvio_fe_ctx* c);  // the background-activity filter's planes back to `none` (below, with the stage)
-int baf_ensure(esvio_fe_ctx* c, size_t n, bool host_src, bool host_dst);
+int baf_ensure(esvio_fe_ctx* c, size_t n, bool host_src, bool host_dst, bool fields_form);
 }  // namespace
 
 int esvio_fe_reset(esvio_fe_handle c) {
@@ -996,12 +996,13 @@ const uint8_t* pinned_device_ptr(const uint8_t* p, size_t len) {
   return (const uint8_t*)d0;
 }
 
-// Enqueue the conversion of n events (checked descriptor) into d_dst on the current stream; bad events are added to
-// c->d_cvt_bad.  A host source that is not read in place is copied into c->d_cvt_src first: every byte range the
+// Make the fields of n events (n > 0, checked descriptor) readable on the device, on the current stream: *a = what a
+// kernel reads them with.  Device memory is read where it lies, page-locked host memory through its device-side
+// address; a host source that is not read in place is copied into c->d_cvt_src first: every byte range the
 // fields span once (the four fields of an AoS source overlap: one range), each at its source's address modulo 16,
-// so that an aligned source stays aligned for the kernel's wide loads.
-int convert_enqueue(esvio_fe_ctx* c, const esvio_fe_event_fields& f, size_t n, int src_space, EventRec* d_dst) {
-  if (!n) return 0;
+// so that an aligned source stays aligned for the kernels' wide loads.  Shared by the conversion and the filter's
+// fields form; c->d_cvt_src is reused in stream order.
+int fields_on_device(esvio_fe_ctx* c, const esvio_fe_event_fields& f, size_t n, int src_space, FieldsArgs* a) {
   hipStream_t s = cur_stream(c);
   FieldView v[4];
   field_views(f, v);
@@ -1046,18 +1047,28 @@ int convert_enqueue(esvio_fe_ctx* c, const esvio_fe_event_fields& f, size_t n, i
           if (v[k].p >= rg[r].lo && v[k].p < rg[r].hi) dev[k] = c->d_cvt_src + rg[r].off + (v[k].p - rg[r].lo);
     }
   }
-  FieldsArgs a{};
-  a.x = dev[0], a.y = dev[1], a.t = dev[2], a.p = dev[3];
-  a.x_stride = f.x_stride, a.y_stride = f.y_stride, a.t_stride = f.t_stride, a.p_stride = f.p_stride;
-  a.t_bits = f.t_bits, a.t_unit_ns = f.t_unit_ns, a.p_bits = f.p_bits, a.t_offset = f.t_offset;
-  ScopedKernel k(c, K_EVENTS_FROM_FIELDS, n * (size_t)(2 + 2 + v[2].width + v[3].width + 16));
-  launch_events_from_fields(s, a, n, d_dst, c->d_cvt_bad);
+  *a = FieldsArgs{};
+  a->x = dev[0], a->y = dev[1], a->t = dev[2], a->p = dev[3];
+  a->x_stride = f.x_stride, a->y_stride = f.y_stride, a->t_stride = f.t_stride, a->p_stride = f.p_stride;
+  a->t_bits = f.t_bits, a->t_unit_ns = f.t_unit_ns, a->p_bits = f.p_bits, a->t_offset = f.t_offset;
   return 0;
 }
-int convert_begin(esvio_fe_ctx* c) {  // the bad-event counter, cleared in stream order
+size_t fields_bytes_per_event(const esvio_fe_event_fields& f) { return (size_t)(2 + 2 + f.t_bits / 8 + f.p_bits / 8); }
+
+// Enqueue the conversion of n events (checked descriptor) into d_dst on the current stream; bad events are added to
+// c->d_cvt_bad[slot] (one count per camera).
+int convert_enqueue(esvio_fe_ctx* c, const esvio_fe_event_fields& f, size_t n, int src_space, EventRec* d_dst, int slot = 0) {
+  if (!n) return 0;
+  FieldsArgs a;
+  if (int rc = fields_on_device(c, f, n, src_space, &a)) return rc;
+  ScopedKernel k(c, K_EVENTS_FROM_FIELDS, n * (fields_bytes_per_event(f) + 16));
+  launch_events_from_fields(cur_stream(c), a, n, d_dst, c->d_cvt_bad + slot);
+  return 0;
+}
+int convert_begin(esvio_fe_ctx* c) {  // the bad-event counters, cleared in stream order
   if (!c->d_cvt_bad)
-    if (int rc = c->d_cvt_bad.alloc(c, 1)) return rc;
-  HIPCHK(c, hipMemsetAsync(c->d_cvt_bad, 0, sizeof(unsigned long long), cur_stream(c)));
+    if (int rc = c->d_cvt_bad.alloc(c, 2)) return rc;
+  HIPCHK(c, hipMemsetAsync(c->d_cvt_bad, 0, 2 * sizeof(unsigned long long), cur_stream(c)));
   return 0;
 }
 int convert_end(esvio_fe_ctx* c, unsigned long long* bad) {  // waits for the conversions enqueued since convert_begin
@@ -1103,8 +1114,8 @@ int esvio_fe_convert_events(esvio_fe_handle c, const esvio_fe_event_fields* src,
 // the entry points that make the records they track.  cvt_pair_begin: room for (nL, nR) records in both pairs — the
 // second call of a size allocates nothing — and the current pair's buffers, behind everything the pair's previous use
 // (two calls back) left on the side streams: what it left on the main stream is in front of us there anyway.
-// cvt_pair_track: the plain track call on the pair's records; marks what it leaves on the side streams and hands
-// the next call the other pair.
+// cvt_pair_track: the track call (plain, or motion-compensated with `motion`) on the pair's records; marks what it
+// leaves on the side streams and hands the next call the other pair.
 namespace {
 int cvt_pair_begin(esvio_fe_ctx* c, size_t nL, size_t nR, EventRec** dL, EventRec** dR) {
   for (int p = 0; p < 2; p++) {
@@ -1121,11 +1132,11 @@ int cvt_pair_begin(esvio_fe_ctx* c, size_t nL, size_t nR, EventRec** dL, EventRe
   return 0;
 }
 int cvt_pair_track(esvio_fe_ctx* c, double cur_time, const EventRec* dL, size_t nL, const EventRec* dR, size_t nR,
-                   int pub_this_frame, esvio_fe_tracks* out) {
+                   int pub_this_frame, const esvio_fe_motion* motion, esvio_fe_tracks* out) {
   const int pair = c->cvt_pair;
   hipStream_t side[4] = {c->stream2, c->stream3, c->stream4, c->stream6};
   const int rc = track_event_impl(c, cur_time, (const esvio_fe_event*)dL, nL, (const esvio_fe_event*)(nR ? dR : nullptr), nR,
-                                  ESVIO_FE_DEVICE, pub_this_frame != 0, nullptr);
+                                  ESVIO_FE_DEVICE, pub_this_frame != 0, motion);
   for (int k = 0; k < 4; k++)
     if (side[k]) {
       if (!c->ev_cvt_side[pair][k]) HIPCHK(c, c->ev_cvt_side[pair][k].create());
@@ -1138,39 +1149,25 @@ int cvt_pair_track(esvio_fe_ctx* c, double cur_time, const EventRec* dL, size_t 
 }
 }  // namespace
 
-int esvio_fe_track_event_fields(esvio_fe_handle c, double cur_time, const esvio_fe_event_fields* left, size_t nL,
-                                const esvio_fe_event_fields* right, size_t nR, int src_space, int pub_this_frame,
-                                esvio_fe_tracks* out) {
-  if (!c) return ESVIO_FE_EINVAL;
-  if (src_space != ESVIO_FE_HOST && src_space != ESVIO_FE_DEVICE) return fail(c, ESVIO_FE_EINVAL, "track_event_fields: bad memory space");
-  if (nL == 0 || !left) return fail(c, ESVIO_FE_EINVAL, "left batch must not be empty (node:150)");
-  if (nL + nR >= (1ull << 31)) return fail(c, ESVIO_FE_EINVAL, "batch too large");
-  if (int rc = fields_check(c, left, nL, "track_event_fields (left)")) return rc;
-  if (int rc = fields_check(c, right, nR, "track_event_fields (right)")) return rc;
-  if (!c->announced.empty() || !c->inflight.empty())
-    return fail(c, ESVIO_FE_EINVAL, "track_event_fields: batches are announced on this handle (convert into memory of your own)");
-  HIPCHK(c, hipSetDevice(c->dev));
-  EventRec *dL = nullptr, *dR = nullptr;
-  if (int rc = cvt_pair_begin(c, nL, nR, &dL, &dR)) return rc;
-  if (int rc = convert_begin(c)) return rc;
-  if (int rc = convert_enqueue(c, *left, nL, src_space, dL)) return rc;
-  if (nR)
-    if (int rc = convert_enqueue(c, *right, nR, src_space, dR)) return rc;
-  unsigned long long bad = 0;
-  if (int rc = convert_end(c, &bad)) return rc;
-  if (bad)
-    return fail(c, ESVIO_FE_EINVAL, "track_event_fields: %llu of %zu events have a stamp outside [0, 2^32 s) (or a 64-bit t outside +-2^62)",
-                bad, nL + nR);
-  return cvt_pair_track(c, cur_time, dL, nL, dR, nR, pub_this_frame, out);
-}
-
-// ---- background-activity filter of an event batch (esvio_fe_filter_events; the rule: include/esvio_fe.h)
+// ---- background-activity + refractory filter of an event batch (the rule: include/esvio_fe.h)
 namespace {
 constexpr int64_t kBafMaxWindow = (int64_t)1 << 62;
 
+// esvio_fe_filter_events' limits (min_support 1..8), its messages
 int baf_params_check(esvio_fe_ctx* c, int64_t window_ns, int min_support, const char* who) {
   if (window_ns < 1 || window_ns > kBafMaxWindow) return fail(c, ESVIO_FE_EINVAL, "%s: window_ns must be in 1..2^62 (got %lld)", who, (long long)window_ns);
   if (min_support < 1 || min_support > 8) return fail(c, ESVIO_FE_EINVAL, "%s: min_support must be in 1..8 (got %d)", who, min_support);
+  return 0;
+}
+// esvio_fe_filter_params' limits
+int baf_prm_check(esvio_fe_ctx* c, const esvio_fe_filter_params* p, const char* who) {
+  if (!p) return fail(c, ESVIO_FE_EINVAL, "%s: no filter parameters", who);
+  if (p->reserved != 0) return fail(c, ESVIO_FE_EINVAL, "%s: esvio_fe_filter_params.reserved must be 0", who);
+  if (p->min_support < 0 || p->min_support > 8) return fail(c, ESVIO_FE_EINVAL, "%s: min_support must be in 0..8 (got %d)", who, p->min_support);
+  if (p->min_support > 0 && (p->window_ns < 1 || p->window_ns > kBafMaxWindow))
+    return fail(c, ESVIO_FE_EINVAL, "%s: window_ns must be in 1..2^62 (got %lld)", who, (long long)p->window_ns);
+  if (p->refractory_ns < 0 || p->refractory_ns > kBafMaxWindow)
+    return fail(c, ESVIO_FE_EINVAL, "%s: refractory_ns must be in 0..2^62 (got %lld)", who, (long long)p->refractory_ns);
   return 0;
 }
 
@@ -1182,12 +1179,13 @@ int baf_clear(esvio_fe_ctx* c) {  // every plane back to `none`, the sort's scra
 }
 
 // the planes (first call) and the per-event scratch for calls of up to n events; host_src / host_dst: the record
-// buffers of a host source / destination as well
-int baf_ensure(esvio_fe_ctx* c, size_t n, bool host_src, bool host_dst) {
+// buffers of a host source / destination as well; fields_form: the stream-order stamps of the fields form (on its
+// first use, as src and out: a handle that only filters records holds none; kept at the scratch's size from then on)
+int baf_ensure(esvio_fe_ctx* c, size_t n, bool host_src, bool host_dst, bool fields_form) {
   esvio_fe_ctx::Baf& f = c->baf;
   if (!f.B) {
     if (int rc = f.head.alloc(c, c->P)) return rc;
-    if (int rc = f.res.alloc(c, 1)) return rc;
+    if (int rc = f.res.alloc(c, 2)) return rc;
     if (int rc = f.B.alloc(c, (size_t)2 * c->P)) return rc;
     // (f.B says "the stage's state exists": a plane or a head table that could not be cleared is not there)
     hipError_t e = hipMemsetAsync(f.head, 0, (size_t)c->P * 4, cur_stream(c));
@@ -1212,6 +1210,8 @@ int baf_ensure(esvio_fe_ctx* c, size_t n, bool host_src, bool host_dst) {
     HIPCHK(c, hipMemsetAsync(f.sort, 0, words * 4, cur_stream(c)));
     f.cap = cap;
   }
+  if (fields_form || f.tstream)
+    if (int rc = f.tstream.grow(c, f.cap + 4)) return rc;
   if (host_src)
     if (int rc = f.src.grow(c, n)) return rc;
   if (host_dst)
@@ -1219,27 +1219,41 @@ int baf_ensure(esvio_fe_ctx* c, size_t n, bool host_src, bool host_dst) {
   return 0;
 }
 
-// Filter the n events at `ev` (n > 0; a host source is copied into the stage's scratch first, as it is) into the device
-// buffer d_dst, advancing camera cam's plane; waits for the result block *r and, if asked for, the flags.
-int baf_run(esvio_fe_ctx* c, int cam, const esvio_fe_event* ev, size_t n, int space, int64_t window_ns, int min_support,
-            EventRec* d_dst, BafResult* r, uint8_t* flags, const char* who) {
+// Enqueue camera cam's chain for n > 0 events — records at `ev` (a host source is copied into the stage's scratch
+// first, as it is) or `fields` where they lie (fields_on_device) — into the device buffer d_dst, advancing the
+// camera's plane.  Nothing is waited for: the chain's result block is c->baf.res[cam] (baf_fetch), and the per-event
+// scratch is free for the next chain on the stream behind this one.
+int baf_enqueue(esvio_fe_ctx* c, int cam, const esvio_fe_event* ev, const esvio_fe_event_fields* fields, size_t n, int space,
+                const esvio_fe_filter_params& prm, EventRec* d_dst, const char* who) {
   esvio_fe_ctx::Baf& f = c->baf;
   hipStream_t s = cur_stream(c);
-  const EventRec* d_ev = (const EventRec*)ev;
-  if (space == ESVIO_FE_HOST) {
-    HIPCHK(c, hipMemcpyAsync(f.src, ev, n * sizeof(EventRec), hipMemcpyHostToDevice, s));
-    d_ev = f.src;
-  }
-  HIPCHK(c, hipMemsetAsync(f.res, 0, sizeof(BafResult), s));
   int key_bits = 1;
   while (((uint64_t)1 << key_bits) <= c->P) key_bits++;  // keys 0..P, P = out of the sensor
   const int passes = (key_bits + 6) / 7, bits = (key_bits + passes - 1) / passes;
   if (passes > kRadixMaxPasses) return fail(c, ESVIO_FE_ENOTIMPL, "%s: the sensor has more pixels than the sort's %d digits hold", who, kRadixMaxPasses);
+  const EventRec* d_ev = (const EventRec*)ev;
+  FieldsArgs fa{};
+  if (fields) {
+    d_ev = nullptr;
+    if (int rc = fields_on_device(c, *fields, n, space, &fa)) return rc;
+  } else if (space == ESVIO_FE_HOST) {
+    HIPCHK(c, hipMemcpyAsync(f.src, ev, n * sizeof(EventRec), hipMemcpyHostToDevice, s));
+    d_ev = f.src;
+  }
+  BafResult* res = f.res + cam;
+  HIPCHK(c, hipMemsetAsync(res, 0, sizeof(BafResult), s));
   const uint32_t n32 = (uint32_t)n;
   const SortScratch sc = sort_scratch(f.sort);
   const size_t pass_words = (size_t)radix_blocks(n32) << bits;
-  uint8_t* res_bytes = (uint8_t*)f.res.p;
-  {
+  uint8_t* res_bytes = (uint8_t*)res;
+  const uint64_t fb = fields ? fields_bytes_per_event(*fields) : 0;
+  // booked: what each launch has to move at least (keys, indices and stamps once; per neighbour a head and a stamp);
+  // the emits' share for the kept records is booked as if all were kept
+  if (fields) {
+    ScopedKernel k(c, K_BAF_KEYS_FIELDS, (uint64_t)n * (fb + 4 + 4 + 8));
+    launch_baf_keys_fields(s, fa, n32, c->W, c->H, f.keys[0], f.vals[0], f.tstream, res, passes, bits, sc.ghist, sc.lookback,
+                           (uint32_t)(passes * pass_words));
+  } else {
     ScopedKernel k(c, K_SAE_KEYS, (uint64_t)n * 24);
     launch_sae_keys(s, d_ev, n32, nullptr, 0, c->W, c->H, f.keys[0], f.vals[0], c->P,
                     (unsigned long long*)(res_bytes + offsetof(BafResult, n_rejected)), passes, bits, sc.ghist, sc.lookback,
@@ -1254,20 +1268,18 @@ int baf_run(esvio_fe_ctx* c, int cam, const esvio_fe_event* ev, size_t n, int sp
     cur ^= 1;
   }
   BafArgs a{};
-  a.ev = d_ev, a.n = n32, a.P = c->P, a.W = c->W, a.H = c->H;
+  a.ev = d_ev, a.tstream = fields ? f.tstream.p : nullptr, a.n = n32, a.P = c->P, a.W = c->W, a.H = c->H;
   a.keys = f.keys[cur], a.vals = f.vals[cur], a.head = f.head, a.tsort = f.tsort;
   a.B = f.B + (size_t)cam * c->P;
-  a.window_ns = window_ns, a.min_support = min_support;
-  a.flags = f.flags, a.blk_cnt = f.blk_cnt, a.dst = d_dst, a.res = f.res;
+  a.window_ns = prm.window_ns, a.min_support = prm.min_support, a.refractory_ns = prm.refractory_ns;
+  a.flags = f.flags, a.blk_cnt = f.blk_cnt, a.dst = d_dst, a.res = res;
   a.sort_scratch = f.sort, a.sort_head_words = sc.head_words;
-  // booked: what each launch has to move at least (keys, indices and stamps once; per neighbour a head and a stamp);
-  // the emit's share for the kept records is booked as if all were kept
   {
-    ScopedKernel k(c, K_BAF_HEADS, (uint64_t)n * 32);
+    ScopedKernel k(c, K_BAF_HEADS, (uint64_t)n * (fields ? 24 : 32));
     launch_baf_heads(s, a);
   }
   {
-    ScopedKernel k(c, K_BAF_FILTER, (uint64_t)n * (16 + 8 * 12 + 1));
+    ScopedKernel k(c, K_BAF_FILTER, (uint64_t)n * (16 + (prm.min_support ? 8 * 12 : 0) + (prm.refractory_ns ? 12 : 0) + 1));
     launch_baf_filter(s, a);
   }
   {
@@ -1278,19 +1290,85 @@ int baf_run(esvio_fe_ctx* c, int cam, const esvio_fe_event* ev, size_t n, int sp
     ScopedKernel k(c, K_BAF_SCAN, (uint64_t)baf_blocks(n32) * 8);
     launch_baf_scan(s, a);
   }
-  {
+  if (fields) {
+    ScopedKernel k(c, K_BAF_EMIT_FIELDS, (uint64_t)n * (1 + fb + 16));
+    launch_baf_emit_fields(s, a, fa);
+  } else {
     ScopedKernel k(c, K_BAF_EMIT, (uint64_t)n * 33);
     launch_baf_emit(s, a);
   }
-  HIPCHK(c, hipMemcpyAsync(r, f.res, sizeof(BafResult), hipMemcpyDeviceToHost, s));
-  if (flags) HIPCHK(c, hipMemcpyAsync(flags, f.flags, n, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  if (c->prof_on) resolve_profile(c);
-  if (r->err) {  // (the sort did not finish: its scratch words are cleared again; the plane is what the chain made of it)
-    HIPCHK(c, hipMemsetAsync(f.sort, 0, f.sort.cap * 4, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    return fail(c, ESVIO_FE_EINTERNAL, "%s: radix sort look-back spin expired (esvio_fe_filter_reset before the next call)", who);
+  return 0;
+}
+// the copies that bring camera cam's result block (and, if asked for, the n flags) to the host, behind its chain
+int baf_fetch(esvio_fe_ctx* c, int cam, BafResult* r, uint8_t* flags, size_t n) {
+  HIPCHK(c, hipMemcpyAsync(r, c->baf.res + cam, sizeof(BafResult), hipMemcpyDeviceToHost, cur_stream(c)));
+  if (flags) HIPCHK(c, hipMemcpyAsync(flags, c->baf.flags, n, hipMemcpyDeviceToHost, cur_stream(c)));
+  return 0;
+}
+// a waited-for result block: the sort's bounded wait
+int baf_result_check(esvio_fe_ctx* c, const BafResult& r, const char* who) {
+  if (!r.err) return 0;
+  // (the sort did not finish: its scratch words are cleared again; the plane is what the chain made of it)
+  HIPCHK(c, hipMemsetAsync(c->baf.sort, 0, c->baf.sort.cap * 4, cur_stream(c)));
+  HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  return fail(c, ESVIO_FE_EINTERNAL, "%s: radix sort look-back spin expired (esvio_fe_filter_reset before the next call)", who);
+}
+const char* const kBadStampText = "have a stamp outside [0, 2^32 s) (or a 64-bit t outside +-2^62)";
+
+// The filter stage behind esvio_fe_filter_events and esvio_fe_filter_batch: the arguments checked before any device
+// work, camera cam's chain, one wait, the results.
+int baf_stage(esvio_fe_ctx* c, const char* who, bool takes_fields, int cam, const esvio_fe_event* ev, const esvio_fe_event_fields* fields, size_t n,
+              int space, const esvio_fe_filter_params* prm, esvio_fe_event* dst, int dst_space, uint64_t* n_kept, uint8_t* flags,
+              esvio_fe_event* last_kept, uint64_t* n_rejected, uint64_t* n_bad) {
+  if (n_kept) *n_kept = 0;
+  if (n_rejected) *n_rejected = 0;
+  if (n_bad) *n_bad = 0;
+  if (fields)
+    if (int rc = fields_check(c, fields, n, who)) return rc;
+  if (int rc = baf_prm_check(c, prm, who)) return rc;
+  if (cam != 0 && cam != 1) return fail(c, ESVIO_FE_EINVAL, "%s: cam must be 0 or 1 (got %d)", who, cam);
+  if ((space != ESVIO_FE_HOST && space != ESVIO_FE_DEVICE) || (dst_space != ESVIO_FE_HOST && dst_space != ESVIO_FE_DEVICE))
+    return fail(c, ESVIO_FE_EINVAL, "%s: bad memory space", who);
+  if (!n) return 0;
+  if (n >= (1ull << 31)) return fail(c, ESVIO_FE_EINVAL, "%s: batch too large", who);
+  if (!ev && !fields) return fail(c, ESVIO_FE_EINVAL, takes_fields ? "%s: neither ev nor fields is given" : "%s: ev is null", who);
+  if (ev && fields) return fail(c, ESVIO_FE_EINVAL, "%s: both ev and fields are given", who);
+  if (!dst) return fail(c, ESVIO_FE_EINVAL, "%s: dst is null", who);
+  if (dst_space == ESVIO_FE_DEVICE && ((uintptr_t)dst & 15) != 0)
+    return fail(c, ESVIO_FE_EINVAL, "%s: a device dst must be 16-byte aligned", who);
+  {  // (one address space: a range of one is the same memory under the other name)
+    const uintptr_t b0 = (uintptr_t)dst, len = n * sizeof(EventRec);
+    if (ev) {
+      const uintptr_t a0 = (uintptr_t)ev;
+      if (a0 < b0 + len && b0 < a0 + len) return fail(c, ESVIO_FE_EINVAL, "%s: dst overlaps ev", who);
+    } else {
+      FieldView v[4];
+      field_views(*fields, v);
+      for (const FieldView& k : v) {
+        const uintptr_t a0 = (uintptr_t)k.p, alen = field_span(k, n);
+        if (a0 < b0 + len && b0 < a0 + alen) return fail(c, ESVIO_FE_EINVAL, "%s: dst overlaps field %s", who, k.name);
+      }
+    }
   }
+  HIPCHK(c, hipSetDevice(c->dev));
+  if (int rc = baf_ensure(c, n, ev && space == ESVIO_FE_HOST, dst_space == ESVIO_FE_HOST, fields != nullptr)) return rc;
+  EventRec* d_dst = dst_space == ESVIO_FE_HOST ? c->baf.out.p : (EventRec*)dst;
+  BafResult r{};
+  if (int rc = baf_enqueue(c, cam, ev, fields, n, space, *prm, d_dst, who)) return rc;
+  if (int rc = baf_fetch(c, cam, &r, flags, n)) return rc;
+  HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  if (c->prof_on) resolve_profile(c);
+  if (int rc = baf_result_check(c, r, who)) return rc;
+  if (n_bad) *n_bad = r.n_bad;
+  if (r.n_bad)
+    return fail(c, ESVIO_FE_EINVAL, "%s: %llu of %zu events %s; the camera's plane is as it was", who, r.n_bad, n, kBadStampText);
+  if (dst_space == ESVIO_FE_HOST && r.n_kept) {
+    HIPCHK(c, hipMemcpyAsync(dst, d_dst, (size_t)r.n_kept * sizeof(EventRec), hipMemcpyDeviceToHost, cur_stream(c)));
+    HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  }
+  if (n_kept) *n_kept = r.n_kept;
+  if (n_rejected) *n_rejected = r.n_rejected;
+  if (last_kept && r.n_kept) std::memcpy(last_kept, &r.last, sizeof(EventRec));
   return 0;
 }
 }  // namespace
@@ -1302,32 +1380,15 @@ int esvio_fe_filter_events(esvio_fe_handle c, int cam, const esvio_fe_event* ev,
   if (n_kept) *n_kept = 0;
   if (n_rejected) *n_rejected = 0;
   if (int rc = baf_params_check(c, window_ns, min_support, "filter_events")) return rc;
-  if (cam != 0 && cam != 1) return fail(c, ESVIO_FE_EINVAL, "filter_events: cam must be 0 or 1 (got %d)", cam);
-  if ((space != ESVIO_FE_HOST && space != ESVIO_FE_DEVICE) || (dst_space != ESVIO_FE_HOST && dst_space != ESVIO_FE_DEVICE))
-    return fail(c, ESVIO_FE_EINVAL, "filter_events: bad memory space");
-  if (!n) return 0;
-  if (n >= (1ull << 31)) return fail(c, ESVIO_FE_EINVAL, "filter_events: batch too large");
-  if (!ev) return fail(c, ESVIO_FE_EINVAL, "filter_events: ev is null");
-  if (!dst) return fail(c, ESVIO_FE_EINVAL, "filter_events: dst is null");
-  if (dst_space == ESVIO_FE_DEVICE && ((uintptr_t)dst & 15) != 0)
-    return fail(c, ESVIO_FE_EINVAL, "filter_events: a device dst must be 16-byte aligned");
-  {  // (one address space: a range of one is the same memory under the other name)
-    const uintptr_t a0 = (uintptr_t)ev, b0 = (uintptr_t)dst, len = n * sizeof(EventRec);
-    if (a0 < b0 + len && b0 < a0 + len) return fail(c, ESVIO_FE_EINVAL, "filter_events: dst overlaps ev");
-  }
-  HIPCHK(c, hipSetDevice(c->dev));
-  if (int rc = baf_ensure(c, n, space == ESVIO_FE_HOST, dst_space == ESVIO_FE_HOST)) return rc;
-  EventRec* d_dst = dst_space == ESVIO_FE_HOST ? c->baf.out.p : (EventRec*)dst;
-  BafResult r{};
-  if (int rc = baf_run(c, cam, ev, n, space, window_ns, min_support, d_dst, &r, flags, "filter_events")) return rc;
-  if (dst_space == ESVIO_FE_HOST && r.n_kept) {
-    HIPCHK(c, hipMemcpyAsync(dst, d_dst, (size_t)r.n_kept * sizeof(EventRec), hipMemcpyDeviceToHost, cur_stream(c)));
-    HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
-  }
-  if (n_kept) *n_kept = r.n_kept;
-  if (n_rejected) *n_rejected = r.n_rejected;
-  if (last_kept && r.n_kept) std::memcpy(last_kept, &r.last, sizeof(EventRec));
-  return 0;
+  const esvio_fe_filter_params prm{window_ns, min_support, 0, 0};
+  return baf_stage(c, "filter_events", false, cam, ev, nullptr, n, space, &prm, dst, dst_space, n_kept, flags, last_kept, n_rejected, nullptr);
+}
+
+int esvio_fe_filter_batch(esvio_fe_handle c, int cam, const esvio_fe_event* ev, const esvio_fe_event_fields* fields, size_t n,
+                          int space, const esvio_fe_filter_params* prm, esvio_fe_event* dst, int dst_space, uint64_t* n_kept,
+                          uint8_t* flags, esvio_fe_event* last_kept, uint64_t* n_rejected, uint64_t* n_bad) {
+  if (!c) return ESVIO_FE_EINVAL;
+  return baf_stage(c, "filter_batch", true, cam, ev, fields, n, space, prm, dst, dst_space, n_kept, flags, last_kept, n_rejected, n_bad);
 }
 
 int esvio_fe_filter_reset(esvio_fe_handle c) {
@@ -1338,6 +1399,137 @@ int esvio_fe_filter_reset(esvio_fe_handle c) {
   return 0;
 }
 
+// ---- the batch call: records or fields per camera, filtered or not, plain or motion-compensated
+namespace {
+// own_memory: what the message tells a caller to do instead while batches are announced
+int track_batch_body(esvio_fe_ctx* c, const char* who, const char* own_memory, const esvio_fe_batch& b, esvio_fe_tracks* out,
+                     esvio_fe_batch_info* info_out) {
+  esvio_fe_batch_info info{};
+  if (info_out) *info_out = info;
+  const size_t n[2] = {b.nL, b.nR};
+  const esvio_fe_event* ev[2] = {b.left, b.right};
+  const esvio_fe_event_fields* fl[2] = {b.left_fields, b.right_fields};
+  if (b.space != ESVIO_FE_HOST && b.space != ESVIO_FE_DEVICE) return fail(c, ESVIO_FE_EINVAL, "%s: bad memory space", who);
+  if (b.reserved != 0) return fail(c, ESVIO_FE_EINVAL, "%s: esvio_fe_batch.reserved must be 0", who);
+  for (int cam = 0; cam < 2; cam++) {
+    const char* side = cam ? "right" : "left";
+    if (n[cam] && !ev[cam] && !fl[cam]) return fail(c, ESVIO_FE_EINVAL, "%s: the %s batch has events and neither records nor fields", who, side);
+    if (n[cam] && ev[cam] && fl[cam]) return fail(c, ESVIO_FE_EINVAL, "%s: the %s batch has both records and fields", who, side);
+    if (fl[cam]) {
+      char w[96];
+      snprintf(w, sizeof w, "%s (%s)", who, side);
+      if (int rc = fields_check(c, fl[cam], n[cam], w)) return rc;
+    }
+    if (!n[cam]) ev[cam] = nullptr, fl[cam] = nullptr;
+  }
+  if (b.filter)
+    if (int rc = baf_prm_check(c, b.filter, who)) return rc;
+  if (n[0] + n[1] >= (1ull << 31)) return fail(c, ESVIO_FE_EINVAL, "batch too large");
+  hipStream_t s = cur_stream(c);
+  EventRec last{};
+  if (!fl[0] && !fl[1] && !b.filter) {  // records as they are: the track call itself, announced batches included
+    if (n[0] == 0 || !ev[0]) return fail(c, ESVIO_FE_EINVAL, "left batch must not be empty (node:150)");
+    double cur_time = b.cur_time;
+    if (b.cur_time_from_batch) {
+      if (b.space == ESVIO_FE_HOST) {
+        std::memcpy(&last, ev[0] + (n[0] - 1), sizeof(EventRec));
+      } else {
+        HIPCHK(c, hipSetDevice(c->dev));
+        HIPCHK(c, hipMemcpyAsync(&last, ev[0] + (n[0] - 1), sizeof(EventRec), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+      }
+      cur_time = (double)last.sec + 1e-9 * (double)last.nsec;
+    }
+    info.kept[0] = n[0], info.kept[1] = n[1], info.cur_time = cur_time;
+    const int rc = track_event_entry(c, cur_time, ev[0], n[0], ev[1], n[1], b.space, b.pub_this_frame, b.motion, out);
+    info.tracked = rc == 0;
+    if (info_out) *info_out = info;
+    return rc;
+  }
+  if (!b.filter && n[0] == 0) return fail(c, ESVIO_FE_EINVAL, "left batch must not be empty (node:150)");
+  if (!c->announced.empty() || !c->inflight.empty())
+    return fail(c, ESVIO_FE_EINVAL, "%s: batches are announced on this handle (%s into memory of your own)", who, own_memory);
+  HIPCHK(c, hipSetDevice(c->dev));
+  EventRec* d[2] = {nullptr, nullptr};
+  if (int rc = cvt_pair_begin(c, n[0], n[1], &d[0], &d[1])) return rc;
+  if (b.filter) {
+    const bool host_records = b.space == ESVIO_FE_HOST && (ev[0] || ev[1]);
+    if (int rc = baf_ensure(c, std::max(n[0], n[1]), host_records, false, fl[0] || fl[1])) return rc;
+  } else if (int rc = convert_begin(c)) {
+    return rc;
+  }
+  // both cameras' conversion / filter chains, one behind the other on the stream; then ONE wait for everything the
+  // host reads before it tracks: the result blocks or the bad counts, and the last left record where it is the stamp
+  for (int cam = 0; cam < 2; cam++) {
+    if (!n[cam]) continue;
+    if (b.filter) {
+      char w[96];
+      snprintf(w, sizeof w, "%s (%s)", who, cam ? "right" : "left");
+      if (int rc = baf_enqueue(c, cam, ev[cam], fl[cam], n[cam], b.space, *b.filter, d[cam], w)) return rc;
+    } else if (fl[cam]) {
+      if (int rc = convert_enqueue(c, *fl[cam], n[cam], b.space, d[cam], cam)) return rc;
+    } else {  // records beside the other camera's fields: into the pair as they are
+      HIPCHK(c, hipMemcpyAsync(d[cam], ev[cam], n[cam] * sizeof(EventRec),
+                               b.space == ESVIO_FE_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
+    }
+  }
+  BafResult r[2] = {};
+  unsigned long long bad[2] = {0, 0};
+  if (b.filter) {
+    for (int cam = 0; cam < 2; cam++)
+      if (n[cam])
+        if (int rc = baf_fetch(c, cam, &r[cam], nullptr, 0)) return rc;
+  } else {
+    HIPCHK(c, hipMemcpyAsync(bad, c->d_cvt_bad, sizeof bad, hipMemcpyDeviceToHost, s));
+    if (b.cur_time_from_batch) HIPCHK(c, hipMemcpyAsync(&last, d[0] + (n[0] - 1), sizeof(EventRec), hipMemcpyDeviceToHost, s));
+  }
+  HIPCHK(c, hipStreamSynchronize(s));
+  if (c->prof_on) resolve_profile(c);
+  for (int cam = 0; cam < 2; cam++) {
+    if (b.filter) {
+      if (int rc = baf_result_check(c, r[cam], who)) return rc;
+      bad[cam] = r[cam].n_bad;
+      info.rejected[cam] = r[cam].n_rejected;
+    }
+    info.bad[cam] = bad[cam];
+    info.kept[cam] = b.filter ? r[cam].n_kept : n[cam];
+  }
+  if (bad[0] || bad[1]) {
+    info.kept[0] = info.kept[1] = 0;
+    if (info_out) *info_out = info;
+    return fail(c, ESVIO_FE_EINVAL, "%s: %llu of %zu events %s%s", who, bad[0] + bad[1], n[0] + n[1], kBadStampText,
+                b.filter ? "; the plane of a camera with such an event is as it was, whether the other camera's has advanced is unspecified" : "");
+  }
+  if (info_out) *info_out = info;
+  if (!info.kept[0]) return 0;  // node:150: an empty left message is not tracked (the pair stays this call's: nothing reads it)
+  if (b.filter) last = r[0].last;
+  info.cur_time = b.cur_time_from_batch ? (double)last.sec + 1e-9 * (double)last.nsec : b.cur_time;
+  const int rc = cvt_pair_track(c, info.cur_time, d[0], info.kept[0], d[1], info.kept[1], b.pub_this_frame, b.motion, out);
+  info.tracked = rc == 0;
+  if (info_out) *info_out = info;
+  return rc;
+}
+}  // namespace
+
+int esvio_fe_track_batch(esvio_fe_handle c, const esvio_fe_batch* b, esvio_fe_tracks* out, esvio_fe_batch_info* info) {
+  if (!c) return ESVIO_FE_EINVAL;
+  if (!b) return fail(c, ESVIO_FE_EINVAL, "track_batch: no batch");
+  return track_batch_body(c, "track_batch", "convert and filter", *b, out, info);
+}
+
+int esvio_fe_track_event_fields(esvio_fe_handle c, double cur_time, const esvio_fe_event_fields* left, size_t nL,
+                                const esvio_fe_event_fields* right, size_t nR, int src_space, int pub_this_frame,
+                                esvio_fe_tracks* out) {
+  if (!c) return ESVIO_FE_EINVAL;
+  if (src_space != ESVIO_FE_HOST && src_space != ESVIO_FE_DEVICE) return fail(c, ESVIO_FE_EINVAL, "track_event_fields: bad memory space");
+  if (nL == 0 || !left) return fail(c, ESVIO_FE_EINVAL, "left batch must not be empty (node:150)");
+  if (nL + nR >= (1ull << 31)) return fail(c, ESVIO_FE_EINVAL, "batch too large");
+  esvio_fe_batch b{};
+  b.left_fields = left, b.right_fields = right, b.nL = nL, b.nR = nR, b.space = src_space, b.pub_this_frame = pub_this_frame;
+  b.cur_time = cur_time;
+  return track_batch_body(c, "track_event_fields", "convert", b, out, nullptr);
+}
+
 int esvio_fe_track_event_filtered(esvio_fe_handle c, const esvio_fe_event* left, size_t nL, const esvio_fe_event* right,
                                   size_t nR, int space, int64_t window_ns, int min_support, int pub_this_frame,
                                   esvio_fe_tracks* out, uint64_t kept[2], double* cur_time_out) {
@@ -1346,23 +1538,15 @@ int esvio_fe_track_event_filtered(esvio_fe_handle c, const esvio_fe_event* left,
   if (space != ESVIO_FE_HOST && space != ESVIO_FE_DEVICE) return fail(c, ESVIO_FE_EINVAL, "track_event_filtered: bad memory space");
   if (int rc = baf_params_check(c, window_ns, min_support, "track_event_filtered")) return rc;
   if ((nL && !left) || (nR && !right)) return fail(c, ESVIO_FE_EINVAL, "track_event_filtered: a batch with events and no pointer");
-  if (nL + nR >= (1ull << 31)) return fail(c, ESVIO_FE_EINVAL, "batch too large");
-  if (!c->announced.empty() || !c->inflight.empty())
-    return fail(c, ESVIO_FE_EINVAL, "track_event_filtered: batches are announced on this handle (filter into memory of your own)");
-  HIPCHK(c, hipSetDevice(c->dev));
-  EventRec *dL = nullptr, *dR = nullptr;
-  if (int rc = cvt_pair_begin(c, nL, nR, &dL, &dR)) return rc;
-  if (int rc = baf_ensure(c, std::max(nL, nR), space == ESVIO_FE_HOST, false)) return rc;
-  BafResult rL{}, rR{};
-  if (nL)
-    if (int rc = baf_run(c, 0, left, nL, space, window_ns, min_support, dL, &rL, nullptr, "track_event_filtered (left)")) return rc;
-  if (nR)
-    if (int rc = baf_run(c, 1, right, nR, space, window_ns, min_support, dR, &rR, nullptr, "track_event_filtered (right)")) return rc;
-  if (kept) kept[0] = rL.n_kept, kept[1] = rR.n_kept;
-  if (!rL.n_kept) return 0;  // node:150: an empty left message is not tracked (the pair stays this call's: nothing reads it)
-  const double cur_time = (double)rL.last.sec + 1e-9 * (double)rL.last.nsec;
-  if (cur_time_out) *cur_time_out = cur_time;
-  return cvt_pair_track(c, cur_time, dL, rL.n_kept, dR, rR.n_kept, pub_this_frame, out);
+  const esvio_fe_filter_params prm{window_ns, min_support, 0, 0};
+  esvio_fe_batch b{};
+  b.left = left, b.right = right, b.nL = nL, b.nR = nR, b.space = space, b.pub_this_frame = pub_this_frame;
+  b.filter = &prm, b.cur_time_from_batch = 1;
+  esvio_fe_batch_info info{};
+  const int rc = track_batch_body(c, "track_event_filtered", "filter", b, out, &info);
+  if (kept) kept[0] = info.kept[0], kept[1] = info.kept[1];
+  if (info.tracked && cur_time_out) *cur_time_out = info.cur_time;
+  return rc;
 }
 
 // ---- image front-end
@@ -1867,7 +2051,7 @@ int esvio_fe_reserve(esvio_fe_handle c, size_t max_left, size_t max_right, int h
   // a handle that filters (esvio_fe_filter_events): the stage's scratch for one camera's batch and, for host batches,
   // the copy of a host source — not the records behind a host dst, which grow on the first call that has one
   if (c->baf.B)
-    if (int rc = baf_ensure(c, std::max(max_left, max_right), host_batches != 0, false)) return rc;
+    if (int rc = baf_ensure(c, std::max(max_left, max_right), host_batches != 0, false, false)) return rc;
   if (host_batches) {
     if (int rc = ensure_event_capacity(c, n)) return rc;
     if (stager_enabled(c)) {

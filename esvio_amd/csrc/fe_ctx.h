@@ -70,7 +70,7 @@ const char* const kKernelNames[K_COUNT] = {
     "k_time_surface4", "k_time_surface", "k_median", "k_clahe", "k_norm_pyr", "k_pyr3", "k_pyr_down", "k_pyr_pad",
     "k_scharr", "k_pad_scharr", "k_lk_f32", "k_lk", "k_arc_map", "k_arc_ev", "k_dedup", "k_compact", "k_select_mw",
     "k_select", "k_select_gbm", "k_fast_score", "k_fast_collect", "k_events_from_fields", "k_baf_heads", "k_baf_filter",
-    "k_baf_count", "k_baf_scan", "k_baf_emit"};
+    "k_baf_count", "k_baf_scan", "k_baf_emit", "k_baf_keys_fields", "k_baf_emit_fields"};
 
 // The host phases of one trackEvent call, in the order of esvio_fe_latency_call::phase_ms; kPhaseNames is what
 // esvio_fe_latency_phase_name returns and what the ESVIO_FE_TRACE summary prints.  The PH_PUB_* phases are parts of
@@ -487,13 +487,14 @@ struct esvio_fe_ctx {
   // holds none of it — and is the stage's own: the main stream is the only one that touches it.  B: the stamp plane
   // of each camera, [2][P] nanoseconds, -1 = none.  head: [P], the chain's per-pixel segment heads (never cleared).
   // Per event, for calls of up to `cap` events: the (key, index) pairs of the sort and its scratch words, the stamps in
-  // sorted order, the flags, the per-block counts.  src / out: a host source's records and the records behind a host
+  // sorted order (and in stream order: the fields form's, allocated by its first use), the flags, the per-block counts; shared by the two
+  // cameras' chains in stream order, while each camera has a result block of its own.  src / out: a host source's records and the records behind a host
   // dst, on first use of either.  (esvio_fe_track_event_filtered filters into esvio_fe_track_event_fields' two pairs.)
   struct Baf {
-    DevBuf<long long> B, tsort;
+    DevBuf<long long> B, tsort, tstream;
     DevBuf<uint32_t> head, keys[2], vals[2], sort, blk_cnt;
     DevBuf<uint8_t> flags;
-    DevBuf<BafResult> res;
+    DevBuf<BafResult> res;  // [2]: one per camera, so that both cameras' chains are waited for once
     DevBuf<EventRec> src, out;
     size_t cap = 0;
   } baf;

@@ -78,12 +78,14 @@ enum KernelId {
   K_BAF_COUNT,
   K_BAF_SCAN,
   K_BAF_EMIT,
+  K_BAF_KEYS_FIELDS, // esvio_fe_filter_batch on field arrays (its heads launch is booked as K_BAF_HEADS)
+  K_BAF_EMIT_FIELDS,
   K_COUNT
 };
 // esvio_fe_kernel_count(): the kernels of the tracker's entry points, the table bench.py and the recorded launch traces
 // list.  The ids from here on belong to stages off every track path and are listed by esvio_fe_stage_kernel_count().
 constexpr int kTrackKernels = K_BAF_HEADS;
-static_assert(K_EVENTS_FROM_FIELDS + 1 == kTrackKernels && K_BAF_EMIT + 1 == K_COUNT,
+static_assert(K_EVENTS_FROM_FIELDS + 1 == kTrackKernels && K_BAF_EMIT_FIELDS + 1 == K_COUNT,
               "a track-path kernel goes in front of K_BAF_HEADS (and into this assertion), a stage's kernel behind it");
 
 // ---- SAE update -------------------------------------------------------------------------
@@ -526,21 +528,26 @@ struct FieldsArgs {
 };
 void launch_events_from_fields(hipStream_t s, const FieldsArgs& a, size_t n, EventRec* dst, unsigned long long* n_bad);
 
-// ---- background-activity filter of an event batch (esvio_fe_filter_events) -------------------
+// ---- background-activity + refractory filter of an event batch (esvio_fe_filter_events, esvio_fe_filter_batch) ----
 // include/esvio_fe.h holds the rule.  The chain: launch_sae_keys (keys = y*W + x, out-of-sensor events = P: they sort
 // last; values = event index) -> launch_radix_pass x passes -> heads -> filter -> count -> scan -> emit, all on one
 // stream, each launch reading what the launches before it wrote; no launch of these five waits on the device.
-struct BafResult {  // zeroed by the host in front of the chain
-  unsigned long long n_rejected;  // k_sae_keys
+// On field arrays (esvio_fe_filter_batch with esvio_fe_event_fields) three launches differ: launch_baf_keys_fields
+// in launch_sae_keys' place, the heads launch with BafArgs::tstream set, launch_baf_emit_fields in launch_baf_emit's.
+struct BafResult {  // zeroed by the host in front of the chain; one per camera
+  unsigned long long n_rejected;  // k_sae_keys / k_baf_keys_fields
   uint32_t n_kept;                // k_baf_scan
   int err;                        // k_radix_pass: a look-back wait expired
-  EventRec last;                  // k_baf_emit: the last kept record (untouched if none)
+  EventRec last;                  // k_baf_emit(_fields): the last kept record (untouched if none)
+  unsigned long long n_bad;       // k_baf_keys_fields: BAD events by conversion's test; != 0: k_baf_count leaves B alone
+  unsigned long long reserved;
 };
-static_assert(sizeof(BafResult) == 32, "BafResult layout");
+static_assert(sizeof(BafResult) == 48 && offsetof(BafResult, last) == 16, "BafResult layout");
 constexpr uint32_t kBafBlock = 1024;  // events per block of the ordered compaction (four flags per lane)
 inline uint32_t baf_blocks(uint32_t n) { return (n + kBafBlock - 1) / kBafBlock; }
 struct BafArgs {
-  const EventRec* ev;    // [n] the call's events, device memory
+  const EventRec* ev;    // [n] the call's events, device memory (the fields form: not read)
+  const long long* tstream;  // the fields form: [n] stamps (ns) in stream order; NULL: the stamps are read from ev
   uint32_t n;
   uint32_t P;            // W * H, also the key of an out-of-sensor event
   int W, H;
@@ -550,7 +557,8 @@ struct BafArgs {
   long long* tsort;      // [n] stamps (ns) in sorted order
   long long* B;          // [P] the camera's plane: -1 = none, else the stamp in ns
   long long window_ns;
-  int min_support;
+  int min_support;       // 0: no support test
+  long long refractory_ns;  // 0: no refractory test
   uint8_t* flags;        // [n rounded up to 4] keep_i, by event index
   uint32_t* blk_cnt;     // [baf_blocks(n) + 1] kept per block, then their exclusive offsets and the total
   EventRec* dst;         // [n] the kept records in stream order; must not overlap ev
@@ -563,6 +571,13 @@ void launch_baf_filter(hipStream_t s, const BafArgs& a);
 void launch_baf_count(hipStream_t s, const BafArgs& a);   // + the plane update
 void launch_baf_scan(hipStream_t s, const BafArgs& a);
 void launch_baf_emit(hipStream_t s, const BafArgs& a);
+// the fields form: per event of `fields` (FieldsArgs, above: pointers the device reads) the key, the index, the
+// stream-order stamp, the digit histograms and the cleared look-back words as launch_sae_keys; res->n_rejected and
+// res->n_bad are added to
+void launch_baf_keys_fields(hipStream_t s, const FieldsArgs& fields, uint32_t n, int W, int H, uint32_t* keys, uint32_t* vals,
+                            long long* tstream, BafResult* res, int passes, int bits, uint32_t* ghist, uint32_t* lookback,
+                            uint32_t lookback_words);
+void launch_baf_emit_fields(hipStream_t s, const BafArgs& a, const FieldsArgs& fields);
 
 struct SelectArgs {
   const uint32_t* comp_xy;   // compacted candidates in stream order

@@ -3779,81 +3779,111 @@ __device__ __forceinline__ uint4 fields_record(uint32_t x, uint32_t y, int64_t t
 }  // namespace
 
 // aos: bit 31 = the four fields of event i lie inside the aligned 16-byte record a.x + 16 * i (a.x then IS the record
-// base); bits 0-3 / 4-7 / 8-11 / 12-15 = byte offsets of x / y / t / p in it
+// base); bits 0-3 / 4-7 / 8-11 / 12-15 = byte offsets of x / y / t / p in it (fields_aos below makes the word)
+//
+// The loading rules of the field arrays, stated once: the cnt (1..4) events from i0 on, i0 a multiple of 4 — one
+// lane's share in every kernel that reads fields.  Aligned AoS records as whole 16-byte loads; else per field one wide
+// load where its four values lie side by side and aligned, else element by element (ld_any).
+namespace {
+template <int kTBits, int kPBits>
+__device__ __forceinline__ void fields_load4(const FieldsArgs& a, uint32_t aos, size_t i0, int cnt, uint32_t xs[4],
+                                             uint32_t ys[4], int64_t ts[4], uint32_t ps[4]) {
+  using TT = typename std::conditional<kTBits == 32, uint32_t, uint64_t>::type;
+  using PT = typename std::conditional<kPBits == 8, uint8_t, uint16_t>::type;
+#pragma unroll
+  for (int k = 0; k < 4; k++) xs[k] = ys[k] = ps[k] = 0, ts[k] = 0;
+  if (aos >> 31) {
+    const uint4* rec = (const uint4*)a.x + i0;
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+      if (k < cnt) {
+        const uint4 r = rec[k];
+        xs[k] = (uint32_t)rec_bits(r, aos & 15) & 0xffffu;
+        ys[k] = (uint32_t)rec_bits(r, (aos >> 4) & 15) & 0xffffu;
+        ts[k] = field_t<kTBits>(rec_bits(r, (aos >> 8) & 15));
+        ps[k] = field_pol<kPBits>(rec_bits(r, (aos >> 12) & 15));
+      }
+    return;
+  }
+  const uint8_t* px = a.x + i0 * (size_t)a.x_stride;
+  const uint8_t* py = a.y + i0 * (size_t)a.y_stride;
+  const uint8_t* pt = a.t + i0 * (size_t)a.t_stride;
+  const uint8_t* pp = a.p + i0 * (size_t)a.p_stride;
+  const bool full = cnt == 4;
+  if (full && a.x_stride == 2 && ((uintptr_t)px & 7) == 0) {
+    const uint2 v = *(const uint2*)px;
+    xs[0] = v.x & 0xffffu, xs[1] = v.x >> 16, xs[2] = v.y & 0xffffu, xs[3] = v.y >> 16;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+      if (k < cnt) xs[k] = ld_any<uint16_t>(px + (size_t)k * a.x_stride);
+  }
+  if (full && a.y_stride == 2 && ((uintptr_t)py & 7) == 0) {
+    const uint2 v = *(const uint2*)py;
+    ys[0] = v.x & 0xffffu, ys[1] = v.x >> 16, ys[2] = v.y & 0xffffu, ys[3] = v.y >> 16;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+      if (k < cnt) ys[k] = ld_any<uint16_t>(py + (size_t)k * a.y_stride);
+  }
+  if (full && a.t_stride == kTBits / 8 && ((uintptr_t)pt & 15) == 0) {
+    if (kTBits == 32) {
+      const uint4 v = *(const uint4*)pt;
+      ts[0] = v.x, ts[1] = v.y, ts[2] = v.z, ts[3] = v.w;
+    } else {
+      const uint4 v = ((const uint4*)pt)[0], w = ((const uint4*)pt)[1];
+      ts[0] = (int64_t)(((uint64_t)v.y << 32) | v.x), ts[1] = (int64_t)(((uint64_t)v.w << 32) | v.z);
+      ts[2] = (int64_t)(((uint64_t)w.y << 32) | w.x), ts[3] = (int64_t)(((uint64_t)w.w << 32) | w.z);
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+      if (k < cnt) ts[k] = field_t<kTBits>((uint64_t)ld_any<TT>(pt + (size_t)k * a.t_stride));
+  }
+  if (full && a.p_stride == kPBits / 8 && ((uintptr_t)pp & (kPBits / 2 - 1)) == 0) {
+    if (kPBits == 8) {
+      const uint32_t v = *(const uint32_t*)pp;
+#pragma unroll
+      for (int k = 0; k < 4; k++) ps[k] = field_pol<8>(v >> (8 * k));
+    } else {
+      const uint2 v = *(const uint2*)pp;
+      ps[0] = field_pol<16>(v.x), ps[1] = field_pol<16>(v.x >> 16), ps[2] = field_pol<16>(v.y), ps[3] = field_pol<16>(v.y >> 16);
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+      if (k < cnt) ps[k] = field_pol<kPBits>((uint64_t)ld_any<PT>(pp + (size_t)k * a.p_stride));
+  }
+}
+
+// the four fields inside one aligned 16-byte record per event (a dvs-style AoS with a 64-bit stamp, say): the aos
+// word, and k = the arguments the kernel reads (k.x = the record base); 0: the fields are read field by field
+uint32_t fields_aos(const FieldsArgs& a, FieldsArgs* k) {
+  *k = a;
+  if (a.x_stride == 16 && a.y_stride == 16 && a.t_stride == 16 && a.p_stride == 16) {
+    const uintptr_t lo = std::min(std::min((uintptr_t)a.x, (uintptr_t)a.y), std::min((uintptr_t)a.t, (uintptr_t)a.p));
+    const uintptr_t base = lo & ~(uintptr_t)15;
+    const uintptr_t ox = (uintptr_t)a.x - base, oy = (uintptr_t)a.y - base, ot = (uintptr_t)a.t - base, op = (uintptr_t)a.p - base;
+    if (ox + 2 <= 16 && oy + 2 <= 16 && ot + (uintptr_t)a.t_bits / 8 <= 16 && op + (uintptr_t)a.p_bits / 8 <= 16) {
+      k->x = (const uint8_t*)base;
+      return 0x80000000u | (uint32_t)ox | (uint32_t)oy << 4 | (uint32_t)ot << 8 | (uint32_t)op << 12;
+    }
+  }
+  return 0;
+}
+}  // namespace
+
 template <int kUnitNs, int kTBits, int kPBits>
 __global__ __launch_bounds__(256) void k_events_from_fields(FieldsArgs a, size_t n, uint32_t aos, uint4* __restrict__ dst,
                                                             unsigned long long* __restrict__ n_bad) {
-  using TT = typename std::conditional<kTBits == 32, uint32_t, uint64_t>::type;
-  using PT = typename std::conditional<kPBits == 8, uint8_t, uint16_t>::type;
   const size_t groups = (n + 3) / 4, step = (size_t)gridDim.x * blockDim.x;
   uint32_t bad = 0;
   for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += step) {
     const size_t i0 = g * 4;
     const int cnt = n - i0 >= 4 ? 4 : (int)(n - i0);
-    uint32_t xs[4] = {0, 0, 0, 0}, ys[4] = {0, 0, 0, 0}, ps[4] = {0, 0, 0, 0};
-    int64_t ts[4] = {0, 0, 0, 0};
-    if (aos >> 31) {
-      const uint4* rec = (const uint4*)a.x + i0;
-#pragma unroll
-      for (int k = 0; k < 4; k++)
-        if (k < cnt) {
-          const uint4 r = rec[k];
-          xs[k] = (uint32_t)rec_bits(r, aos & 15) & 0xffffu;
-          ys[k] = (uint32_t)rec_bits(r, (aos >> 4) & 15) & 0xffffu;
-          ts[k] = field_t<kTBits>(rec_bits(r, (aos >> 8) & 15));
-          ps[k] = field_pol<kPBits>(rec_bits(r, (aos >> 12) & 15));
-        }
-    } else {
-      const uint8_t* px = a.x + i0 * (size_t)a.x_stride;
-      const uint8_t* py = a.y + i0 * (size_t)a.y_stride;
-      const uint8_t* pt = a.t + i0 * (size_t)a.t_stride;
-      const uint8_t* pp = a.p + i0 * (size_t)a.p_stride;
-      const bool full = cnt == 4;
-      if (full && a.x_stride == 2 && ((uintptr_t)px & 7) == 0) {
-        const uint2 v = *(const uint2*)px;
-        xs[0] = v.x & 0xffffu, xs[1] = v.x >> 16, xs[2] = v.y & 0xffffu, xs[3] = v.y >> 16;
-      } else {
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-          if (k < cnt) xs[k] = ld_any<uint16_t>(px + (size_t)k * a.x_stride);
-      }
-      if (full && a.y_stride == 2 && ((uintptr_t)py & 7) == 0) {
-        const uint2 v = *(const uint2*)py;
-        ys[0] = v.x & 0xffffu, ys[1] = v.x >> 16, ys[2] = v.y & 0xffffu, ys[3] = v.y >> 16;
-      } else {
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-          if (k < cnt) ys[k] = ld_any<uint16_t>(py + (size_t)k * a.y_stride);
-      }
-      if (full && a.t_stride == kTBits / 8 && ((uintptr_t)pt & 15) == 0) {
-        if (kTBits == 32) {
-          const uint4 v = *(const uint4*)pt;
-          ts[0] = v.x, ts[1] = v.y, ts[2] = v.z, ts[3] = v.w;
-        } else {
-          const uint4 v = ((const uint4*)pt)[0], w = ((const uint4*)pt)[1];
-          ts[0] = (int64_t)(((uint64_t)v.y << 32) | v.x), ts[1] = (int64_t)(((uint64_t)v.w << 32) | v.z);
-          ts[2] = (int64_t)(((uint64_t)w.y << 32) | w.x), ts[3] = (int64_t)(((uint64_t)w.w << 32) | w.z);
-        }
-      } else {
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-          if (k < cnt) ts[k] = field_t<kTBits>((uint64_t)ld_any<TT>(pt + (size_t)k * a.t_stride));
-      }
-      if (full && a.p_stride == kPBits / 8 && ((uintptr_t)pp & (kPBits / 2 - 1)) == 0) {
-        if (kPBits == 8) {
-          const uint32_t v = *(const uint32_t*)pp;
-#pragma unroll
-          for (int k = 0; k < 4; k++) ps[k] = field_pol<8>(v >> (8 * k));
-        } else {
-          const uint2 v = *(const uint2*)pp;
-          ps[0] = field_pol<16>(v.x), ps[1] = field_pol<16>(v.x >> 16), ps[2] = field_pol<16>(v.y), ps[3] = field_pol<16>(v.y >> 16);
-        }
-      } else {
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-          if (k < cnt) ps[k] = field_pol<kPBits>((uint64_t)ld_any<PT>(pp + (size_t)k * a.p_stride));
-      }
-    }
+    uint32_t xs[4], ys[4], ps[4];
+    int64_t ts[4];
+    fields_load4<kTBits, kPBits>(a, aos, i0, cnt, xs, ys, ts, ps);
 #pragma unroll
     for (int k = 0; k < 4; k++)
       if (k < cnt) dst[i0 + k] = fields_record<kUnitNs, kTBits>(xs[k], ys[k], ts[k], a.t_offset, ps[k], bad);
@@ -3863,35 +3893,25 @@ __global__ __launch_bounds__(256) void k_events_from_fields(FieldsArgs a, size_t
   if (lane_id() == 0 && bad) atomicAdd(n_bad, (unsigned long long)bad);
 }
 
+// one instantiation per (unit, stamp width, polarity width) of a descriptor.  Every CASE returns from the launcher;
+// fields_check (fe_api.cpp) admits no other combination, so a launcher that falls through its cases was handed an
+// unchecked descriptor: it aborts — a launch that silently does not happen is not an outcome
+#define ESVIO_FIELDS_DISPATCH(CASE) \
+  CASE(1, 32, 8) CASE(1, 32, 16) CASE(1, 64, 8) CASE(1, 64, 16) CASE(1000, 32, 8) CASE(1000, 32, 16) CASE(1000, 64, 8) CASE(1000, 64, 16)
+
 void launch_events_from_fields(hipStream_t s, const FieldsArgs& a, size_t n, EventRec* dst, unsigned long long* n_bad) {
   if (!n) return;
-  // the four fields inside one aligned 16-byte record per event (a dvs-style AoS with a 64-bit stamp, say)
-  uint32_t aos = 0;
-  FieldsArgs k = a;
-  if (a.x_stride == 16 && a.y_stride == 16 && a.t_stride == 16 && a.p_stride == 16) {
-    const uintptr_t lo = std::min(std::min((uintptr_t)a.x, (uintptr_t)a.y), std::min((uintptr_t)a.t, (uintptr_t)a.p));
-    const uintptr_t base = lo & ~(uintptr_t)15;
-    const uintptr_t ox = (uintptr_t)a.x - base, oy = (uintptr_t)a.y - base, ot = (uintptr_t)a.t - base, op = (uintptr_t)a.p - base;
-    if (ox + 2 <= 16 && oy + 2 <= 16 && ot + (uintptr_t)a.t_bits / 8 <= 16 && op + (uintptr_t)a.p_bits / 8 <= 16) {
-      aos = 0x80000000u | (uint32_t)ox | (uint32_t)oy << 4 | (uint32_t)ot << 8 | (uint32_t)op << 12;
-      k.x = (const uint8_t*)base;
-    }
-  }
+  FieldsArgs k;
+  const uint32_t aos = fields_aos(a, &k);
   const size_t groups = (n + 3) / 4;
   const unsigned grid = (unsigned)std::min<size_t>(2048, (groups + 255) / 256);
   uint4* d = (uint4*)dst;  // (EventRec: 16-byte aligned)
 #define ESVIO_FIELDS_CASE(U, T, P)                                                                      \
   if (a.t_unit_ns == U && a.t_bits == T && a.p_bits == P)                                               \
     return launch_k(k_events_from_fields<U, T, P>, dim3(grid), dim3(256), 0, s, k, n, aos, d, n_bad);
-  ESVIO_FIELDS_CASE(1, 32, 8)
-  ESVIO_FIELDS_CASE(1, 32, 16)
-  ESVIO_FIELDS_CASE(1, 64, 8)
-  ESVIO_FIELDS_CASE(1, 64, 16)
-  ESVIO_FIELDS_CASE(1000, 32, 8)
-  ESVIO_FIELDS_CASE(1000, 32, 16)
-  ESVIO_FIELDS_CASE(1000, 64, 8)
-  ESVIO_FIELDS_CASE(1000, 64, 16)
+  ESVIO_FIELDS_DISPATCH(ESVIO_FIELDS_CASE)
 #undef ESVIO_FIELDS_CASE
+  abort();
 }
 
 // ============================================================================ background-activity filter
@@ -3902,16 +3922,25 @@ void launch_events_from_fields(hipStream_t s, const FieldsArgs& a, size_t n, Eve
 // (pixel key, event index) pairs (k_sae_keys + k_radix_pass) lays every pixel's events out as one segment with
 // ascending indices, so "the last j < i at q" is the end of a monotone predicate over the positions from the segment's
 // head on: keys[pos] == q && vals[pos] < i.  Nothing here depends on the stamps being ordered.
-//   k_baf_heads   per sorted position: the event's stamp in sorted order (tsort), and head[pixel] = position for a
-//                 segment's first pair.  head[] is never cleared: an entry is believed only if it points at a pair of
+//   k_baf_heads   per sorted position: the event's stamp in sorted order (tsort) — gathered from the records, or, in
+//                 the fields form, from the stream-order stamps k_baf_keys_fields wrote (8 bytes instead of 16) —
+//                 and head[pixel] = position for a segment's first pair.  head[] is never cleared: an entry is believed only if it points at a pair of
 //                 that pixel whose predecessor is not (that is the pixel's head, whoever wrote it and when).
 //   k_baf_filter  per sorted position (neighbouring lanes = the same or adjacent pixels, so their look-ups share
-//                 lines): 8 x {head, gallop + bisect for the predecessor, else B}; flags[event index] = keep.
+//                 lines): 8 x {head, gallop + bisect for the predecessor, else B} unless min_support is 0; the
+//                 refractory test on the pixel's own previous stamp — the pair one position to the left if it is
+//                 the same pixel's (the sort is stable: that is the pixel's previous event of this call), else B —
+//                 one more dependent load beside the eight chains; flags[event index] = keep.
 //                 Also clears the sort's digit histograms and tickets for the next call, as k_sae_apply does.
 //   k_baf_count   per block of kBafBlock events in stream order: how many are kept; and, per sorted position, the
-//                 plane update B[pixel] = stamp of the segment's last pair (every look-up of the call is done)
+//                 plane update B[pixel] = stamp of the segment's last pair (every look-up of the call is done);
+//                 not made when the fields form counted a BAD event (BafResult::n_bad, read on the device)
 //   k_baf_scan    one block: exclusive offsets of the blocks, the total
 //   k_baf_emit    per block: the kept records to dst[offset + rank], whole 16 bytes, and the last kept one
+// The fields form (esvio_fe_filter_batch with field arrays) never makes the record of an event it does not keep:
+//   k_baf_keys_fields  k_sae_keys' work from the fields where they lie (fields_load4), plus the stream-order stamps
+//                      and the count of BAD events by conversion's test (fields_record)
+//   k_baf_emit_fields  k_baf_emit's ordered compaction; a kept record is built from its fields by fields_record
 // No kernel waits for another block: the only device-side wait of the chain is k_radix_pass's bounded look-back.
 constexpr long long kBafNone = -1;  // (stamps are sec * 10^9 + nsec >= 0: a stamp 0 is a stamp)
 
@@ -3919,14 +3948,20 @@ __device__ __forceinline__ bool baf_is_head(const uint32_t* __restrict__ keys, u
   return s < n && keys[s] == q && (s == 0 || keys[s - 1] != q);
 }
 
+template <bool kStreamStamps>
 __global__ __launch_bounds__(256) void k_baf_heads(BafArgs a) {
   const uint32_t p = blockIdx.x * 256 + threadIdx.x;
   if (p >= a.n) return;
   const uint32_t k = a.keys[p];
   // (an index is below n by construction; the min() holds where a sort pass gave up, BafResult::err, and left the
   // buffers as they were)
-  const uint4 e = ((const uint4*)a.ev)[min(a.vals[p], a.n - 1)];
-  a.tsort[p] = (long long)e.y * 1000000000ll + (long long)e.z;
+  const uint32_t i = min(a.vals[p], a.n - 1);
+  if (kStreamStamps) {
+    a.tsort[p] = a.tstream[i];
+  } else {
+    const uint4 e = ((const uint4*)a.ev)[i];
+    a.tsort[p] = (long long)e.y * 1000000000ll + (long long)e.z;
+  }
   if (k < a.P && (p == 0 || a.keys[p - 1] != k)) a.head[k] = p;
 }
 
@@ -3943,41 +3978,49 @@ __global__ __launch_bounds__(256) void k_baf_filter(BafArgs a) {
   }
   const long long t = a.tsort[p];
   const int x = (int)(k % (uint32_t)a.W), y = (int)(k / (uint32_t)a.W);
-  int support = 0;
-#pragma unroll
-  for (int d = 0; d < 9; d++) {
-    if (d == 4) continue;
-    const int nx = x + d % 3 - 1, ny = y + d / 3 - 1;
-    if ((unsigned)nx >= (unsigned)a.W || (unsigned)ny >= (unsigned)a.H) continue;
-    const uint32_t q = (uint32_t)ny * (uint32_t)a.W + (uint32_t)nx;
-    long long tb = kBafNone;
-    bool found = false;
-    const uint32_t s = a.head[q];
-    if (baf_is_head(a.keys, a.n, s, q) && a.vals[s] < i) {
-      // ok(pos) = keys[pos] == q && vals[pos] < i holds at s and is monotone from there: gallop, then bisect
-      uint32_t lo = s, step = 1;
-      for (;;) {
-        const uint32_t hi = lo + step;
-        if (hi < lo || hi >= a.n || a.keys[hi] != q || a.vals[hi] >= i) break;
-        lo = hi;
-        step <<= 1;
-      }
-      uint32_t hi = lo + step;
-      if (hi < lo || hi > a.n) hi = a.n;
-      while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (a.keys[mid] == q && a.vals[mid] < i) lo = mid;
-        else hi = mid;
-      }
-      tb = a.tsort[lo];
-      found = true;
-    } else {
-      tb = a.B[q];
-      found = tb != kBafNone;
-    }
-    support += (found && t - tb < a.window_ns) ? 1 : 0;
+  // the refractory test: what the pixel itself held just before the event
+  bool refractory = false;
+  if (a.refractory_ns > 0) {
+    const long long own = (p > 0 && a.keys[p - 1] == k) ? a.tsort[p - 1] : a.B[k];
+    refractory = own != kBafNone && t - own < a.refractory_ns;
   }
-  a.flags[i] = support >= a.min_support ? 1 : 0;
+  int support = 0;
+  if (a.min_support > 0) {
+#pragma unroll
+    for (int d = 0; d < 9; d++) {
+      if (d == 4) continue;
+      const int nx = x + d % 3 - 1, ny = y + d / 3 - 1;
+      if ((unsigned)nx >= (unsigned)a.W || (unsigned)ny >= (unsigned)a.H) continue;
+      const uint32_t q = (uint32_t)ny * (uint32_t)a.W + (uint32_t)nx;
+      long long tb = kBafNone;
+      bool found = false;
+      const uint32_t s = a.head[q];
+      if (baf_is_head(a.keys, a.n, s, q) && a.vals[s] < i) {
+        // ok(pos) = keys[pos] == q && vals[pos] < i holds at s and is monotone from there: gallop, then bisect
+        uint32_t lo = s, step = 1;
+        for (;;) {
+          const uint32_t hi = lo + step;
+          if (hi < lo || hi >= a.n || a.keys[hi] != q || a.vals[hi] >= i) break;
+          lo = hi;
+          step <<= 1;
+        }
+        uint32_t hi = lo + step;
+        if (hi < lo || hi > a.n) hi = a.n;
+        while (hi - lo > 1) {
+          const uint32_t mid = lo + (hi - lo) / 2;
+          if (a.keys[mid] == q && a.vals[mid] < i) lo = mid;
+          else hi = mid;
+        }
+        tb = a.tsort[lo];
+        found = true;
+      } else {
+        tb = a.B[q];
+        found = tb != kBafNone;
+      }
+      support += (found && t - tb < a.window_ns) ? 1 : 0;
+    }
+  }
+  a.flags[i] = (support >= a.min_support && !refractory) ? 1 : 0;
 }
 
 // flags[4w .. 4w+3] as one word (one lane's share of the compaction), the bytes of events behind the n-th cleared
@@ -3997,7 +4040,9 @@ __global__ __launch_bounds__(256) void k_baf_count(BafArgs a) {
   if (lane_id() == 0) part[threadIdx.x >> 6] = c;
   __syncthreads();
   if (threadIdx.x == 0) a.blk_cnt[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
-  // the plane after the call: every touched pixel's last event of the call
+  // the plane after the call: every touched pixel's last event of the call (a call that fails for a BAD event
+  // leaves the plane as it was)
+  if (a.res->n_bad) return;
   for (uint32_t p = blockIdx.x * 256 + threadIdx.x; p < a.n; p += gridDim.x * 256) {
     const uint32_t k = a.keys[p];
     if (k < a.P && (p + 1 == a.n || a.keys[p + 1] != k)) a.B[k] = a.tsort[p];
@@ -4032,10 +4077,10 @@ __global__ __launch_bounds__(kBafScanThreads) void k_baf_scan(BafArgs a, uint32_
   }
 }
 
-__global__ __launch_bounds__(256) void k_baf_emit(BafArgs a, uint32_t nblk) {
+// the ordered compaction of the emit kernels (all 256 threads of the block call it): a lane's flag word -> where its
+// first kept record goes
+__device__ __forceinline__ uint32_t baf_emit_pos(const BafArgs& a, uint32_t f) {
   __shared__ uint32_t part[4];
-  const uint32_t w = blockIdx.x * 256 + threadIdx.x;
-  const uint32_t f = baf_flag_word(a, w);
   const uint32_t c = __popc(f);
   uint32_t incl = c;
 #pragma unroll
@@ -4047,6 +4092,13 @@ __global__ __launch_bounds__(256) void k_baf_emit(BafArgs a, uint32_t nblk) {
   __syncthreads();
   uint32_t pos = a.blk_cnt[blockIdx.x] + incl - c;
   for (int wv = 0; wv < (int)(threadIdx.x >> 6); wv++) pos += part[wv];
+  return pos;
+}
+
+__global__ __launch_bounds__(256) void k_baf_emit(BafArgs a, uint32_t nblk) {
+  const uint32_t w = blockIdx.x * 256 + threadIdx.x;
+  const uint32_t f = baf_flag_word(a, w);
+  uint32_t pos = baf_emit_pos(a, f);
   const uint32_t total = a.blk_cnt[nblk];
   const uint4* src = (const uint4*)a.ev;
   uint4* dst = (uint4*)a.dst;
@@ -4059,8 +4111,87 @@ __global__ __launch_bounds__(256) void k_baf_emit(BafArgs a, uint32_t nblk) {
     }
 }
 
+// ---- the fields form
+template <int kUnitNs, int kTBits, int kPBits>
+__global__ __launch_bounds__(256) void k_baf_keys_fields(FieldsArgs fa, uint32_t n, uint32_t aos, int W, int H,
+                                                         uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
+                                                         long long* __restrict__ tstream, BafResult* res, int passes,
+                                                         int bits, uint32_t* __restrict__ ghist,
+                                                         uint32_t* __restrict__ lookback, uint32_t lookback_words) {
+  __shared__ uint32_t h[kRadixMaxPasses << kRadixMaxBits];
+  const int bins = 1 << bits;
+  for (int i = threadIdx.x; i < passes * bins; i += 256) h[i] = 0;
+  __syncthreads();
+  const uint32_t P = (uint32_t)W * (uint32_t)H;
+  const uint32_t groups = (n + 3) / 4, step = gridDim.x * 256u;
+  uint32_t bad = 0, rejected = 0;
+  for (uint32_t g = blockIdx.x * 256u + threadIdx.x; g < groups; g += step) {
+    const uint32_t i0 = g * 4;
+    const int cnt = n - i0 >= 4 ? 4 : (int)(n - i0);
+    uint32_t xs[4], ys[4], ps[4];
+    int64_t ts[4];
+    fields_load4<kTBits, kPBits>(fa, aos, i0, cnt, xs, ys, ts, ps);
+    uint32_t key[4] = {0, 0, 0, 0};
+    long long stamp[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+      if (k < cnt) {
+        const uint4 r = fields_record<kUnitNs, kTBits>(xs[k], ys[k], ts[k], fa.t_offset, ps[k], bad);
+        const uint32_t x = r.x & 0xffffu, y = r.x >> 16;
+        const bool ok = x < (uint32_t)W && y < (uint32_t)H;
+        key[k] = ok ? y * (uint32_t)W + x : P;
+        stamp[k] = (long long)r.y * 1000000000ll + (long long)r.z;
+        rejected += ok ? 0u : 1u;
+        for (int p = 0; p < passes; p++) atomicAdd(&h[p * bins + ((key[k] >> (p * bits)) & (bins - 1))], 1u);
+      }
+    if (cnt == 4) {  // (i0 is a multiple of 4: the three arrays' groups are 16- and 32-byte aligned)
+      *(uint4*)(keys + i0) = make_uint4(key[0], key[1], key[2], key[3]);
+      *(uint4*)(vals + i0) = make_uint4(i0, i0 + 1, i0 + 2, i0 + 3);
+      *(longlong2*)(tstream + i0) = make_longlong2(stamp[0], stamp[1]);
+      *(longlong2*)(tstream + i0 + 2) = make_longlong2(stamp[2], stamp[3]);
+    } else {
+      for (int k = 0; k < cnt; k++) keys[i0 + k] = key[k], vals[i0 + k] = i0 + k, tstream[i0 + k] = stamp[k];
+    }
+  }
+  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < lookback_words; i += step) lookback[i] = 0;
+  __syncthreads();
+  for (int i = threadIdx.x; i < passes * bins; i += 256)
+    if (h[i]) atomicAdd(&ghist[i], h[i]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o), rejected += __shfl_xor(rejected, o);
+  if (lane_id() == 0 && bad) atomicAdd(&res->n_bad, (unsigned long long)bad);
+  if (lane_id() == 0 && rejected) atomicAdd(&res->n_rejected, (unsigned long long)rejected);
+}
+
+template <int kUnitNs, int kTBits, int kPBits>
+__global__ __launch_bounds__(256) void k_baf_emit_fields(BafArgs a, FieldsArgs fa, uint32_t aos, uint32_t nblk) {
+  const uint32_t w = blockIdx.x * 256 + threadIdx.x;
+  const uint32_t f = baf_flag_word(a, w);
+  uint32_t pos = baf_emit_pos(a, f);
+  const uint32_t total = a.blk_cnt[nblk];
+  if (!f) return;  // (no kept event in the lane's four: their fields are not read a second time)
+  const uint32_t i0 = w * 4;
+  const int cnt = a.n - i0 >= 4 ? 4 : (int)(a.n - i0);
+  uint32_t xs[4], ys[4], ps[4];
+  int64_t ts[4];
+  fields_load4<kTBits, kPBits>(fa, aos, i0, cnt, xs, ys, ts, ps);
+  uint4* dst = (uint4*)a.dst;
+  uint32_t bad = 0;  // (counted by k_baf_keys_fields)
+#pragma unroll
+  for (int j = 0; j < 4; j++)
+    if (f & (1u << (8 * j))) {
+      const uint4 e = fields_record<kUnitNs, kTBits>(xs[j], ys[j], ts[j], fa.t_offset, ps[j], bad);
+      dst[pos++] = e;
+      if (pos == total) *(uint4*)&a.res->last = e;
+    }
+}
+
 void launch_baf_heads(hipStream_t s, const BafArgs& a) {
-  if (a.n) launch_k(k_baf_heads, dim3((a.n + 255) / 256), dim3(256), 0, s, a);
+  if (!a.n) return;
+  if (a.tstream)
+    launch_k(k_baf_heads<true>, dim3((a.n + 255) / 256), dim3(256), 0, s, a);
+  else
+    launch_k(k_baf_heads<false>, dim3((a.n + 255) / 256), dim3(256), 0, s, a);
 }
 void launch_baf_filter(hipStream_t s, const BafArgs& a) {
   if (a.n) launch_k(k_baf_filter, dim3((a.n + 255) / 256), dim3(256), 0, s, a);
@@ -4073,6 +4204,33 @@ void launch_baf_scan(hipStream_t s, const BafArgs& a) {
 }
 void launch_baf_emit(hipStream_t s, const BafArgs& a) {
   if (a.n) launch_k(k_baf_emit, dim3(baf_blocks(a.n)), dim3(256), 0, s, a, baf_blocks(a.n));
+}
+void launch_baf_keys_fields(hipStream_t s, const FieldsArgs& fields, uint32_t n, int W, int H, uint32_t* keys, uint32_t* vals,
+                            long long* tstream, BafResult* res, int passes, int bits, uint32_t* ghist, uint32_t* lookback,
+                            uint32_t lookback_words) {
+  if (!n) return;
+  FieldsArgs k;
+  const uint32_t aos = fields_aos(fields, &k);
+  uint32_t grid = ((n + 3) / 4 + 255) / 256;  // four events per lane and round, as k_sae_keys' grid has
+  if (grid > 1024) grid = 1024;
+#define ESVIO_FIELDS_CASE(U, T, P)                                                                                     \
+  if (fields.t_unit_ns == U && fields.t_bits == T && fields.p_bits == P)                                              \
+    return launch_k(k_baf_keys_fields<U, T, P>, dim3(grid), dim3(256), 0, s, k, n, aos, W, H, keys, vals, tstream, res, \
+                    passes, bits, ghist, lookback, lookback_words);
+  ESVIO_FIELDS_DISPATCH(ESVIO_FIELDS_CASE)
+#undef ESVIO_FIELDS_CASE
+  abort();
+}
+void launch_baf_emit_fields(hipStream_t s, const BafArgs& a, const FieldsArgs& fields) {
+  if (!a.n) return;
+  FieldsArgs k;
+  const uint32_t aos = fields_aos(fields, &k);
+#define ESVIO_FIELDS_CASE(U, T, P)                                                                        \
+  if (fields.t_unit_ns == U && fields.t_bits == T && fields.p_bits == P)                                 \
+    return launch_k(k_baf_emit_fields<U, T, P>, dim3(baf_blocks(a.n)), dim3(256), 0, s, a, k, aos, baf_blocks(a.n));
+  ESVIO_FIELDS_DISPATCH(ESVIO_FIELDS_CASE)
+#undef ESVIO_FIELDS_CASE
+  abort();
 }
 
 // ============================================================================ greedy selection

@@ -77,6 +77,29 @@ def fields_desc(f):
     return d
 
 
+class FilterParams(C.Structure):
+    """esvio_fe_filter_params (include/esvio_fe.h has the rule): min_support 0 skips the support test, refractory_ns 0
+    the refractory test"""
+    _fields_ = [("window_ns", C.c_int64), ("min_support", C.c_int32), ("reserved", C.c_int32), ("refractory_ns", C.c_int64)]
+
+    def __init__(self, window_ns=0, min_support=1, refractory_ns=0):
+        super().__init__(int(window_ns), int(min_support), 0, int(refractory_ns))
+
+
+class Batch(C.Structure):
+    """esvio_fe_batch"""
+    _fields_ = [("left", C.c_void_p), ("right", C.c_void_p), ("left_fields", C.POINTER(EventFieldsDesc)),
+                ("right_fields", C.POINTER(EventFieldsDesc)), ("nL", C.c_size_t), ("nR", C.c_size_t), ("space", C.c_int32),
+                ("pub_this_frame", C.c_int32), ("filter", C.POINTER(FilterParams)), ("motion", C.POINTER(Motion)),
+                ("cur_time", C.c_double), ("cur_time_from_batch", C.c_int32), ("reserved", C.c_int32)]
+
+
+class BatchInfo(C.Structure):
+    """esvio_fe_batch_info"""
+    _fields_ = [("kept", C.c_uint64 * 2), ("rejected", C.c_uint64 * 2), ("bad", C.c_uint64 * 2), ("cur_time", C.c_double),
+                ("tracked", C.c_int32), ("reserved", C.c_int32)]
+
+
 class Tracks(C.Structure):
     _fields_ = [
         ("n_left", C.c_int32), ("n_right", C.c_int32),
@@ -95,14 +118,14 @@ ABI_SYMBOLS = [
     "esvio_fe_convert_events", "esvio_fe_create",
     "esvio_fe_create_sae", "esvio_fe_create_sae_stereo", "esvio_fe_create_sae_stereo_mc", "esvio_fe_destroy",
     "esvio_fe_exchange_begin", "esvio_fe_exchange_end", "esvio_fe_exchange_tracks", "esvio_fe_export_image",
-    "esvio_fe_fast_corners", "esvio_fe_filter_events", "esvio_fe_filter_reset", "esvio_fe_features_to_track", "esvio_fe_features_to_track_fast", "esvio_fe_find_fundamental_mat", "esvio_fe_finish", "esvio_fe_get_sae",
+    "esvio_fe_fast_corners", "esvio_fe_filter_batch", "esvio_fe_filter_events", "esvio_fe_filter_reset", "esvio_fe_features_to_track", "esvio_fe_features_to_track_fast", "esvio_fe_find_fundamental_mat", "esvio_fe_finish", "esvio_fe_get_sae",
     "esvio_fe_get_time_surface", "esvio_fe_good_features_to_track", "esvio_fe_import_image", "esvio_fe_is_corner",
     "esvio_fe_last_error", "esvio_fe_mem_alloc", "esvio_fe_mem_free", "esvio_fe_mem_upload",
     "esvio_fe_pack_track_records", "esvio_fe_register_host_buffer", "esvio_fe_reserve", "esvio_fe_reset",
     "esvio_fe_sae_plane_doubles", "esvio_fe_sae_slice_apply", "esvio_fe_sae_slice_commit",
     "esvio_fe_sae_slice_last", "esvio_fe_sae_to_time_surface", "esvio_fe_set_auto_exchange", "esvio_fe_set_detector",
     "esvio_fe_set_host_threads", "esvio_fe_set_launch_thread", "esvio_fe_set_lazy_new_stereo",
-    "esvio_fe_set_next_batch", "esvio_fe_set_next_batch_mc", "esvio_fe_track_event", "esvio_fe_track_event_fields",
+    "esvio_fe_set_next_batch", "esvio_fe_set_next_batch_mc", "esvio_fe_track_batch", "esvio_fe_track_event", "esvio_fe_track_event_fields",
     "esvio_fe_track_event_filtered", "esvio_fe_track_event_mc",
     "esvio_fe_track_image", "esvio_fe_unregister_host_buffer", "esvio_fe_version",
 ]
@@ -213,6 +236,9 @@ def load_library(build_if_missing=True):
     L.esvio_fe_filter_events.argtypes = [vp, i, vp, sz, i, C.c_int64, i, vp, i, C.POINTER(C.c_uint64), vp, vp,
                                          C.POINTER(C.c_uint64)]
     L.esvio_fe_filter_reset.argtypes = [vp]
+    L.esvio_fe_filter_batch.argtypes = [vp, i, vp, C.POINTER(EventFieldsDesc), sz, i, C.POINTER(FilterParams), vp, i,
+                                        C.POINTER(C.c_uint64), vp, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.esvio_fe_track_batch.argtypes = [vp, C.POINTER(Batch), C.POINTER(Tracks), C.POINTER(BatchInfo)]
     L.esvio_fe_track_event_filtered.argtypes = [vp, vp, sz, vp, sz, i, C.c_int64, i, i, C.POINTER(Tracks),
                                                 C.POINTER(C.c_uint64 * 2), C.POINTER(d)]
     L.esvio_fe_set_profiling.argtypes = [vp, i]
@@ -482,6 +508,84 @@ class FeatureTracker:
         k = int(nk.value)
         kept = FilteredEvents(dst, k, last[0] if k else None) if device else out[:k]
         return kept, flags, int(rej.value)
+
+    def filter_batch(self, cam, ev, params, device=False, src_space=HOST):
+        """the filter stage with FilterParams (esvio_fe_filter_batch): `ev` is a numpy EVENT_DTYPE array, a
+        (device_ptr, n) tuple or an events.EventFields (read where they lie: `src_space` says where; no record of an
+        event that is not kept is made).  Returns (kept, flags, n_rejected) as filter_events does.  A BAD event in the
+        fields raises FrontendError with `.n_bad`; the camera's plane is then as it was."""
+        from .events import EVENT_DTYPE, EventFields
+        L = self._hd.L
+        if isinstance(ev, EventFields):
+            desc = fields_desc(ev)
+            ptr, fptr, n, space = None, C.byref(desc), ev.n, src_space
+        else:
+            ptr, n, space, keep = _events_arg(ev)
+            fptr = None
+        flags = np.zeros(n, np.uint8)
+        nk, rej, bad = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        last = np.zeros(1, EVENT_DTYPE)
+        if device:
+            dst = C.c_void_p()
+            rc = L.esvio_fe_mem_alloc(DEVICE, 16 * max(n, 1), C.byref(dst))
+            if rc:
+                raise FrontendError("esvio_fe_mem_alloc rc=%d" % rc)
+            out = None
+        else:
+            out = np.zeros(n, EVENT_DTYPE)
+            dst = _p(out)
+        rc = L.esvio_fe_filter_batch(self._hd.h, int(cam), ptr, fptr, n, space, C.byref(params), dst,
+                                     DEVICE if device else HOST, C.byref(nk), _p(flags), _p(last), C.byref(rej), C.byref(bad))
+        if rc and device:
+            L.esvio_fe_mem_free(DEVICE, dst)
+        if rc:
+            e = FrontendError("rc=%d: %s" % (rc, L.esvio_fe_last_error(self._hd.h).decode()))
+            e.n_bad = int(bad.value)
+            raise e
+        k = int(nk.value)
+        kept = FilteredEvents(dst, k, last[0] if k else None) if device else out[:k]
+        return kept, flags, int(rej.value)
+
+    def track_batch(self, left, right, cur_time=None, pub=True, params=None, measurements=None, copy=True, src_space=HOST):
+        """one batch through esvio_fe_track_batch: left / right are numpy EVENT_DTYPE arrays, (device_ptr, n) tuples or
+        events.EventFields (per camera one kind; `src_space` says where fields lie); params: a FilterParams or None;
+        measurements: an esvio_fe_motion or None; cur_time None: the stamp of the last left record the tracker is
+        given.  Returns the BatchInfo: .kept, .rejected, .bad, .cur_time, .tracked (0: no left record was kept, the
+        result members are the previous call's)."""
+        from .events import EventFields
+        b, keep, spaces = Batch(), [], []
+        for side, ev in (("left", left), ("right", right)):
+            if isinstance(ev, EventFields):
+                d = fields_desc(ev)
+                keep.append(d)
+                setattr(b, side + "_fields", C.pointer(d))
+                n = ev.n
+                spaces.append(src_space)
+            else:
+                ptr, n, sp, k = _events_arg(ev)
+                keep.append(k)
+                setattr(b, side, ptr)
+                if n:
+                    spaces.append(sp)
+            setattr(b, "nL" if side == "left" else "nR", n)
+        assert len(set(spaces)) <= 1, "both cameras' batches lie in one memory space"
+        b.space = spaces[0] if spaces else HOST
+        b.pub_this_frame = int(pub)
+        if params is not None:
+            b.filter = C.pointer(params)
+        if measurements is not None:
+            b.motion = C.pointer(measurements)
+        b.cur_time_from_batch = int(cur_time is None)
+        b.cur_time = 0.0 if cur_time is None else float(cur_time)
+        info = BatchInfo()
+        rc = self._hd.L.esvio_fe_track_batch(self._hd.h, C.byref(b), C.byref(self._tr), C.byref(info))
+        if rc:
+            e = FrontendError("rc=%d: %s" % (rc, self._hd.L.esvio_fe_last_error(self._hd.h).decode()))
+            e.info = info
+            raise e
+        if info.tracked:
+            self._take(copy)
+        return info
 
     def filter_reset(self):
         """every stamp plane of the background-activity filter back to `none` (esvio_fe_filter_reset)"""

@@ -445,7 +445,13 @@ int esvio_fe_track_event_fields(esvio_fe_handle h, double cur_time, const esvio_
  *     these hold: the pixel lies inside the sensor; B there is not `none`; t - B < window_ns as a SIGNED 64-bit
  *     difference (a neighbour stamped later than t has a negative difference and counts).  The event's own pixel
  *     never counts.  Polarity is ignored.
- *  4. keep_i = (support >= min_support).
+ *  3b. (esvio_fe_filter_batch, esvio_fe_track_batch: esvio_fe_filter_params.refractory_ns) own = B[x + y*width] as it
+ *     is just before this event.  The event is REFRACTORY when all three hold: refractory_ns > 0; own is not `none`;
+ *     t - own < refractory_ns as a SIGNED 64-bit difference (a pixel stamped later than t has a negative difference and
+ *     counts, exactly as for neighbours).  A stamp of 0 is a stamp.
+ *  4. keep_i = (support >= min_support).  With esvio_fe_filter_params:
+ *     keep_i = (min_support == 0 || support >= min_support) && !refractory — min_support 0 skips steps 3 and 4's
+ *     support test: every in-sensor event passes it.
  *  5. B[x + y*width] = t — always, kept or not.
  * The kept events are emitted in stream order, all 16 bytes of each record copied as they are.  B carries over from
  * call to call (the first events of a batch find the support the previous batch left).  An event stamped 0 supports
@@ -455,6 +461,11 @@ int esvio_fe_track_event_fields(esvio_fe_handle h, double cur_time, const esvio_
  * software form of the filter (jAER's BackgroundActivityFilter; libcaer's dvsnoise with supportMin), restated from
  * recall: it is unpinned, and not claimed to be bit-equal to the DAVIS FPGA.  The sensor's refractory filter (off by
  * default in the reference's driver) is not part of it.
+ * Steps 3b and 4's second form are that refractory filter in its software form, beside the background-activity filter
+ * as in the reference's driver (DAVIS_ROS_Driver.cfg, off by default) and in every software noise filter (libcaer's
+ * dvsnoise, jAER).  B is written by every in-sensor event — kept or not, refractory or not (step 5): ONE timestamp
+ * map serves both tests, as libcaer's does, restated from recall like the rest: it is unpinned as well.  The
+ * restatement is tests/ba_filter2_ref.py.  Old and new entry points on one handle advance the same planes.
  *
  * the filter stage: advances camera `cam`'s plane B by the n events of `ev` (space: ESVIO_FE_HOST — copied to the
  * device as they are, one copy — or ESVIO_FE_DEVICE, read in place) and writes the kept records, in order, to dst
@@ -471,6 +482,32 @@ int esvio_fe_track_event_fields(esvio_fe_handle h, double cur_time, const esvio_
 int esvio_fe_filter_events(esvio_fe_handle h, int cam, const esvio_fe_event* ev, size_t n, int space,
                            int64_t window_ns, int min_support, esvio_fe_event* dst, int dst_space,
                            uint64_t* n_kept, uint8_t* flags, esvio_fe_event* last_kept, uint64_t* n_rejected);
+/* The parameters of the rule above.  Limits: 0 <= min_support <= 8; 1 <= window_ns <= 2^62 unless min_support is 0
+ * (then it is not read); 0 <= refractory_ns <= 2^62; reserved 0.  {window_ns, min_support, 0, 0} with min_support >= 1 is
+ * esvio_fe_filter_events' rule, bit for bit. */
+typedef struct esvio_fe_filter_params {
+  int64_t window_ns;      /* 1..2^62; not read when min_support == 0 */
+  int32_t min_support;    /* 0..8; 0: the support test (steps 3-4) is skipped, every in-sensor event passes it */
+  int32_t reserved;       /* must be 0 */
+  int64_t refractory_ns;  /* 0..2^62; 0: no refractory test */
+} esvio_fe_filter_params;
+/* the filter stage with esvio_fe_filter_params, on records (`ev`) or on caller-layout field arrays (`fields`): exactly
+ * one of the two is non-null when n > 0, else ESVIO_FE_EINVAL.  Everything esvio_fe_filter_events states about dst,
+ * flags, last_kept, n == 0, the ordering on the main stream, the scratch's growth, esvio_fe_reserve and argument errors
+ * raised before any device work holds here unchanged (reserved != 0, a null prm and the limits above are such errors).
+ * With ev: the kept records are copied whole, all 16 bytes, padding included.
+ * With fields: `space` says where the FIELDS lie, with esvio_fe_convert_events' three source paths — device memory,
+ * read in place; page-locked memory, read in place except records at or above 2^20 events; pageable memory, copied
+ * once into the handle's scratch, only the bytes the fields span.  The 16-byte record of an event that is not kept is
+ * never made: keys and stamps are computed from the fields, the kept records are built exactly as
+ * esvio_fe_convert_events builds them, byte for byte, padding 0.  dst must not overlap a field.  An event that
+ * conversion calls BAD fails the call with ESVIO_FE_EINVAL: *n_bad (optional) is exact, dst, flags and last_kept are
+ * unspecified, CAMERA cam's PLANE IS AS IT WAS BEFORE THE CALL, and the next call works normally.  Descriptor errors
+ * are esvio_fe_convert_events', raised before anything else.  (With ev, *n_bad is 0.) */
+int esvio_fe_filter_batch(esvio_fe_handle h, int cam, const esvio_fe_event* ev, const esvio_fe_event_fields* fields,
+                          size_t n, int space, const esvio_fe_filter_params* prm, esvio_fe_event* dst, int dst_space,
+                          uint64_t* n_kept, uint8_t* flags, esvio_fe_event* last_kept, uint64_t* n_rejected,
+                          uint64_t* n_bad);
 /* all planes B back to `none` (esvio_fe_reset does the same as part of "as a freshly created handle") */
 int esvio_fe_filter_reset(esvio_fe_handle h);
 /* filter both cameras into buffers of the handle, then esvio_fe_track_event on the kept records with
@@ -486,6 +523,45 @@ int esvio_fe_track_event_filtered(esvio_fe_handle h, const esvio_fe_event* left,
                                   const esvio_fe_event* right, size_t nR, int space, int64_t window_ns,
                                   int min_support, int pub_this_frame, esvio_fe_tracks* out,
                                   uint64_t kept[2], double* cur_time_out);
+
+/* ---- one batch call: records or fields, filtered or not, plain or motion-compensated ------ */
+/* Every combination of {records, fields} per camera x {no filter, filter} x {plain, motion-compensated} through one
+ * call; esvio_fe_track_event_fields and esvio_fe_track_event_filtered are this call with their arguments. */
+typedef struct esvio_fe_batch {
+  const esvio_fe_event *left, *right;                      /* records, or                                   */
+  const esvio_fe_event_fields *left_fields, *right_fields; /* fields: per camera exactly one kind when n>0 */
+  size_t nL, nR;
+  int32_t space;                        /* where records / fields lie */
+  int32_t pub_this_frame;
+  const esvio_fe_filter_params* filter; /* NULL: no filter */
+  const esvio_fe_motion* motion;        /* NULL: the plain overload; else the motion-compensated one */
+  double cur_time;                      /* read when cur_time_from_batch == 0 */
+  int32_t cur_time_from_batch;          /* != 0: (double)sec + 1e-9*(double)nsec of the last LEFT record the tracker is given */
+  int32_t reserved;                     /* must be 0 */
+} esvio_fe_batch;
+typedef struct esvio_fe_batch_info {
+  uint64_t kept[2], rejected[2], bad[2]; /* kept = records handed to the tracker; rejected: filled when a filter ran */
+  double cur_time;                       /* the one used */
+  int32_t tracked, reserved;             /* tracked 0: no left record was kept, nothing of the tracker changed */
+} esvio_fe_batch_info;
+/* No fields and no filter: the call IS esvio_fe_track_event (motion NULL) or esvio_fe_track_event_mc on the same
+ * arguments, announced batches included (with cur_time_from_batch the last left record is read first: from host
+ * memory directly, from device memory with a wait).
+ * Any other combination: ESVIO_FE_EINVAL while batches are announced.  The records the tracker reads live in the
+ * handle's two alternating buffer pairs — buffer lifetime exactly as esvio_fe_track_event_fields states it.  The
+ * conversion and / or the filter chains of BOTH cameras are enqueued first, and the host waits ONCE before tracking
+ * starts: in that wait it reads both cameras' result blocks (and, with cur_time_from_batch and no filter, the last left
+ * record) — not once per camera, not once per stage.  A camera given as records beside the other's fields is copied
+ * into the pair as it is.  Without a filter nL must be > 0.
+ * A BAD event (esvio_fe_convert_events) in either camera: ESVIO_FE_EINVAL, info->bad exact, nothing tracked; with a
+ * filter the plane of the camera that held the bad event is unchanged, and whether the other camera's plane has
+ * advanced is unspecified (the error message says so).
+ * Filter set and kept[0] == 0: ESVIO_FE_OK, tracked = 0, `out` untouched, both planes advanced (node:150 returns early
+ * on an empty left message).
+ * With motion, t_0 is read on the device from the first left record the tracker is given: after a filter that is the
+ * first KEPT one.  info is optional.  Argument errors (a bad space, reserved != 0, a camera with both kinds or none
+ * and n > 0, descriptor errors, the filter's limits) are ESVIO_FE_EINVAL before any device work. */
+int esvio_fe_track_batch(esvio_fe_handle h, const esvio_fe_batch* b, esvio_fe_tracks* out, esvio_fe_batch_info* info);
 
 /* ---- camera split across GPUs (BASELINE config C4) ----------------------- */
 /* The left and right cameras have disjoint SAE state (sae_/sae_latest_ vs sae_right/

@@ -9,6 +9,15 @@ figure: the median of BLOCKS blocks of REPS calls after a warm-up block, and the
 pass, no retries; run it under a time limit:
 
     timeout -k 10 600 python tools/filter_microbench.py [--json out.json]
+
+--fields runs another pass instead: the same events as separate arrays in device memory (x[], y[] uint16, t[] uint32
+microseconds behind an offset, p[] uint8: event_fields_ref's soa_u32_us) through esvio_fe_filter_batch on the fields,
+against the two-call form it replaces — esvio_fe_convert_events into device memory, then esvio_fe_filter_events —
+block after block in turn, in one process, the library's kernel timers off: call wall times, the median of BLOCKS
+blocks of REPS calls after a warm-up block, min - max.  Behind the timed blocks, with the timers on, the per-launch
+times of the fields form's chain.
+
+    timeout -k 10 600 python tools/filter_microbench.py --fields [--json out.json]
 """
 import ctypes as C
 import json
@@ -28,6 +37,8 @@ WINDOW_NS, MIN_SUPPORT = 20_000_000, 1
 SIZES = (("C3", 640, 480, 167_000), ("C5", 1280, 720, 3_300_000))
 FILTER_CHAIN = ("k_sae_keys", "k_radix_pass", "k_baf_heads", "k_baf_filter", "k_baf_count", "k_baf_scan", "k_baf_emit")
 SAE_CHAIN = ("k_tile_hist", "k_tile_scan", "k_tile_scatter", "k_tile_apply")
+FIELDS_CHAIN = ("k_baf_keys_fields", "k_radix_pass", "k_baf_heads", "k_baf_filter", "k_baf_count", "k_baf_scan", "k_baf_emit_fields")
+TWO_CALL_CHAIN = ("k_events_from_fields",) + FILTER_CHAIN
 
 
 def med(v):
@@ -66,6 +77,92 @@ def measure(tr, call, chain, between=None):
             per[k].append(st[k]["ms"] / REPS * 1e3)
             info[k] = (st[k]["launches"] / REPS, st[k]["alg_bytes"] / REPS)
     return {k: (med(per[k]),) + info[k] for k in chain}, med(wall), [sum(per[k][b] for k in chain) for b in range(BLOCKS)]
+
+
+def device_fields(L, ev):
+    """the events as separate arrays in one block of device memory -> (EventFields of device pointers, the block)"""
+    from esvio_amd.events import EventFields
+    t_us = ev["sec"].astype(np.int64) * 1_000_000 + ev["nsec"].astype(np.int64) // 1000
+    base = int(t_us.min())
+    arrs = (ev["x"].astype(np.uint16), ev["y"].astype(np.uint16), (t_us - base).astype(np.uint32), ev["polarity"].astype(np.uint8))
+    offs, o = [], 0
+    for a in arrs:
+        offs.append(o)
+        o = (o + a.nbytes + 15) & ~15
+    raw = np.zeros(o, np.uint8)
+    for a, off in zip(arrs, offs):
+        raw[off:off + a.nbytes] = a.view(np.uint8)
+    blk = C.c_void_p()
+    assert L.esvio_fe_mem_alloc(FE.DEVICE, o, C.byref(blk)) == 0
+    assert L.esvio_fe_mem_upload(blk, C.c_void_p(raw.ctypes.data), o) == 0
+    f = EventFields.at_pointers([blk.value + off for off in offs], (2, 2, 4, 1), len(ev), 32, 8, 1000, base)
+    return f, blk
+
+
+def timed_blocks(calls, between):
+    """calls: {name: callable}, run block after block in turn -> {name: wall us per call (median, min, max)}"""
+    wall = {k: [] for k in calls}
+    for b in range(BLOCKS + 1):  # (block 0: the warm-up)
+        for k, call in calls.items():
+            t = 0.0
+            for _ in range(REPS):
+                between()
+                t0 = time.perf_counter()
+                call()
+                t += time.perf_counter() - t0
+            if b:
+                wall[k].append(t / REPS * 1e6)
+    return {k: med(v) for k, v in wall.items()}
+
+
+def main_fields():
+    L = FE.load_library()
+    rows = []
+    for tag, w, h, n_target in SIZES:
+        tr = FE.FeatureTracker(FE.make_config(w, h))
+        for name, ev in streams(w, h, n_target):
+            n = len(ev)
+            fields, blk = device_fields(L, ev)
+            desc = FE.fields_desc(fields)
+            prm = FE.FilterParams(WINDOW_NS, MIN_SUPPORT, 0)
+            rec, dst = C.c_void_p(), C.c_void_p()
+            assert L.esvio_fe_mem_alloc(FE.DEVICE, 16 * n, C.byref(rec)) == 0 and L.esvio_fe_mem_alloc(FE.DEVICE, 16 * n, C.byref(dst)) == 0
+            nk, rej, bad, nk2 = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+
+            def one_call():
+                assert L.esvio_fe_filter_batch(tr._hd.h, 0, None, C.byref(desc), n, FE.DEVICE, C.byref(prm), dst, FE.DEVICE,
+                                               C.byref(nk), None, None, C.byref(rej), C.byref(bad)) == 0
+
+            def two_calls():
+                assert L.esvio_fe_convert_events(tr._hd.h, C.byref(desc), n, FE.DEVICE, rec, FE.DEVICE, C.byref(bad)) == 0
+                assert L.esvio_fe_filter_events(tr._hd.h, 0, rec, n, FE.DEVICE, WINDOW_NS, MIN_SUPPORT, dst, FE.DEVICE,
+                                                C.byref(nk2), None, None, C.byref(rej)) == 0
+
+            wall = timed_blocks({"fields": one_call, "two-call": two_calls}, tr.filter_reset)
+            assert nk.value == nk2.value
+            fk, _, fsum = measure(tr, one_call, FIELDS_CHAIN, between=tr.filter_reset)
+            tk, _, tsum = measure(tr, two_calls, TWO_CALL_CHAIN, between=tr.filter_reset)
+            print("%s %dx%d %-8s n %8d, kept %.3f, rejected %d" % (tag, w, h, name, n, nk.value / n, rej.value))
+            for k in ("fields", "two-call"):
+                print("  %-9s call %9.1f us (%.1f - %.1f) = %7.1f Mev/s" % ((k,) + wall[k] + (n / wall[k][0],)))
+            print("  fields / two-call = %.3f; the two-call form's own spread: %.1f us" %
+                  (wall["fields"][0] / wall["two-call"][0], wall["two-call"][2] - wall["two-call"][1]))
+            for title, ks, tot in (("fields form", fk, fsum), ("two-call form", tk, tsum)):
+                for k, (us, launches, nbytes) in ks.items():
+                    print("    %-20s %9.1f us (%.1f - %.1f)  %4.1f launches  %7.1f B/event booked" % (k, us[0], us[1], us[2], launches, nbytes / n))
+                t = med(tot)
+                print("  %-13s launches %9.1f us (%.1f - %.1f), timers on" % (title, t[0], t[1], t[2]))
+            rows.append(dict(batch=tag, width=w, height=h, stream=name, n=n, kept=int(nk.value), rejected=int(rej.value),
+                             window_ns=WINDOW_NS, min_support=MIN_SUPPORT, fields_call_us=wall["fields"], two_call_us=wall["two-call"],
+                             fields={k: dict(us=v[0], launches=v[1], booked_bytes=v[2]) for k, v in fk.items()},
+                             two_call={k: dict(us=v[0], launches=v[1], booked_bytes=v[2]) for k, v in tk.items()},
+                             fields_launches_us=med(fsum), two_call_launches_us=med(tsum)))
+            for p in (blk, rec, dst):
+                L.esvio_fe_mem_free(FE.DEVICE, p)
+        tr.close()
+    if "--json" in sys.argv:
+        with open(sys.argv[sys.argv.index("--json") + 1], "w") as fo:
+            json.dump(rows, fo, indent=1)
 
 
 def main():
@@ -114,4 +211,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    main_fields() if "--fields" in sys.argv else main()
