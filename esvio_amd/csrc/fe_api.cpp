@@ -236,6 +236,7 @@ int esvio_fe_create(const esvio_fe_config* cfg, esvio_fe_handle* out) {
   c->fuse_ts_pyr = getenv("ESVIO_FE_NO_FUSE") == nullptr;
   c->fast_lds = getenv("ESVIO_FE_FAST_LDS") != nullptr;
   if (const char* v = getenv("ESVIO_FE_CONVERT_PINNED_COPY")) c->cvt_pinned_copy = atoi(v) != 0 ? 1 : 0;
+  if (const char* v = getenv("ESVIO_FE_RAW_PINNED_COPY")) c->rawdec.pinned_copy = atoi(v) != 0 ? 1 : 0;
   c->select_one_wave = getenv("ESVIO_FE_SELECT_SERIAL") != nullptr;
   if (const char* v = getenv("ESVIO_FE_SAE_EV_MIN")) c->sae_ev_min = (size_t)strtoull(v, nullptr, 10);
   c->tiled = make_tile_geom(c->W, c->H, &c->tgeom) && getenv("ESVIO_FE_SAE_SORT") == nullptr;
@@ -356,6 +357,7 @@ int esvio_fe_create(const esvio_fe_config* cfg, esvio_fe_handle* out) {
 namespace {
 int baf_clear(esvio_fe_ctx* c);  // the background-activity filter's planes back to `none` (below, with the stage)
 int baf_ensure(esvio_fe_ctx* c, size_t n, bool host_src, bool host_dst, bool fields_form);
+int raw_ensure(esvio_fe_ctx* c, int cam, size_t n_bytes, bool copied_src, size_t dec_records);  // (below, with the stage)
 }  // namespace
 
 int esvio_fe_reset(esvio_fe_handle c) {
@@ -387,6 +389,7 @@ int esvio_fe_reset(esvio_fe_handle c) {
   HIPCHK(c, hipMemsetAsync(c->L2, 0, (size_t)2 * c->P * 16, cur_stream(c)));
   HIPCHK(c, hipMemsetAsync(c->S2, 0, (size_t)2 * c->P * 16, cur_stream(c)));
   if (int rc = baf_clear(c)) return rc;  // the background-activity filter's planes: none everywhere
+  c->rawdec.st[0] = c->rawdec.st[1] = esvio_fe_ctx::Raw::State();  // the raw-stream decoder: the fresh state
   HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
   clear_tracker_state(c);
   return 0;
@@ -1549,6 +1552,284 @@ int esvio_fe_track_event_filtered(esvio_fe_handle c, const esvio_fe_event* left,
   return rc;
 }
 
+// ---- raw sensor streams: EVT3 / EVT2 words -> event records (the rule: include/esvio_fe.h; the chain: fe_kernels.h)
+namespace {
+constexpr size_t kRawMaxBytes = (size_t)1 << 28;
+// Page-locked sources, measured both ways on prefixes of one stream (KERNELS.md "Raw streams"): the chain reads every
+// word twice, so read in place they cross PCIe twice.  In place is faster at 4 .. 256 KiB (by 1.5 - 7 us of a 35 - 58 us
+// call), copied first at 512 KiB and beyond (by 5 us there, 220 us at 11.8 MB): the switch sits behind the last size at
+// which in place won.
+constexpr size_t kRawPinnedInPlaceBytes = (size_t)256 << 10;
+struct RawJob {  // one camera's part of a call
+  const void* words = nullptr;
+  size_t n_bytes = 0;
+  EventRec* d_dst = nullptr;
+  size_t cap = 0;
+};
+
+int raw_args_check(esvio_fe_ctx* c, const char* who, int format, const void* words, size_t n_bytes, int space, int64_t t_offset_us) {
+  if (format != ESVIO_FE_RAW_EVT2 && format != ESVIO_FE_RAW_EVT3)
+    return fail(c, ESVIO_FE_EINVAL, "%s: format must be ESVIO_FE_RAW_EVT2 or ESVIO_FE_RAW_EVT3 (got %d)", who, format);
+  if (space != ESVIO_FE_HOST && space != ESVIO_FE_DEVICE) return fail(c, ESVIO_FE_EINVAL, "%s: bad memory space", who);
+  const int64_t lim = (int64_t)1 << 62;
+  if (t_offset_us > lim || t_offset_us < -lim) return fail(c, ESVIO_FE_EINVAL, "%s: |t_offset_us| must be <= 2^62", who);
+  const size_t wb = format == ESVIO_FE_RAW_EVT3 ? 2 : 4;
+  if (n_bytes % wb) return fail(c, ESVIO_FE_EINVAL, "%s: %zu bytes are no whole number of %zu-byte words", who, n_bytes, wb);
+  if (n_bytes > kRawMaxBytes) return fail(c, ESVIO_FE_EINVAL, "%s: a chunk holds at most 2^28 bytes", who);
+  if (n_bytes && !words) return fail(c, ESVIO_FE_EINVAL, "%s: words is null", who);
+  return 0;
+}
+size_t raw_bound(int format, size_t n_bytes) {  // the records n_bytes of words can stand for at most
+  return format == ESVIO_FE_RAW_EVT3 ? n_bytes / 2 * 12 : n_bytes / 4;
+}
+uint32_t raw_tiles(size_t n_bytes) { return (uint32_t)((n_bytes + kRawTileBytes - 1) / kRawTileBytes); }
+
+int raw_ensure(esvio_fe_ctx* c, int cam, size_t n_bytes, bool copied_src, size_t dec_records) {
+  esvio_fe_ctx::Raw& r = c->rawdec;
+  r.used = true;
+  if (!r.res)
+    if (int rc = r.res.alloc(c, 2)) return rc;
+  if (int rc = r.sums[cam].grow(c, raw_tiles(n_bytes))) return rc;
+  if (copied_src)
+    if (int rc = r.src[cam].grow(c, n_bytes)) return rc;
+  if (dec_records)
+    if (int rc = r.dec[cam].grow(c, dec_records)) return rc;
+  return 0;
+}
+
+// Enqueue the decode chain of one camera (job[1].n_bytes == 0) or of both on the current stream, and the copies that
+// bring the result blocks to the host; nothing is waited for.  *args: what the emit launch can be repeated with.
+int raw_enqueue(esvio_fe_ctx* c, int format, int space, int64_t t_offset_us, const RawJob job[2], const int cam_of[2], RawArgs* args,
+                RawResult res[2]) {
+  esvio_fe_ctx::Raw& r = c->rawdec;
+  hipStream_t s = cur_stream(c);
+  RawArgs a{};
+  a.format = format;
+  uint64_t bytes = 0, cap_bytes = 0;
+  for (int k = 0; k < 2; k++) {
+    if (!job[k].n_bytes) continue;
+    const int cam = cam_of[k];
+    const uint8_t* d_words = (const uint8_t*)job[k].words;
+    if (space == ESVIO_FE_HOST) {
+      const bool in_place = r.pinned_copy < 0 ? job[k].n_bytes <= kRawPinnedInPlaceBytes : r.pinned_copy == 0;
+      d_words = in_place ? pinned_device_ptr((const uint8_t*)job[k].words, job[k].n_bytes) : nullptr;
+      if (!d_words) {
+        if (int rc = raw_ensure(c, cam, job[k].n_bytes, true, 0)) return rc;
+        HIPCHK(c, hipMemcpyAsync(r.src[cam], job[k].words, job[k].n_bytes, hipMemcpyHostToDevice, s));
+        d_words = r.src[cam];
+      }
+    }
+    if (int rc = raw_ensure(c, cam, job[k].n_bytes, false, 0)) return rc;
+    const esvio_fe_ctx::Raw::State& st = r.st[cam];
+    RawCam& rc = a.cam[k];
+    rc.words = d_words, rc.n_bytes = (uint32_t)job[k].n_bytes, rc.tiles = raw_tiles(job[k].n_bytes);
+    rc.seed = RawXf{st.th, st.th, 0, (st.seen ? kRawHasTh : 0u) | kRawHasTl | kRawHasY | kRawHasBx | (st.bp ? kRawBp : 0u) |
+                                        st.tl << kRawTlShift | st.y << kRawYShift,
+                    st.bx, 0, 0, 0};
+    rc.wraps_base = st.wraps, rc.t_offset = t_offset_us;
+    rc.sums = r.sums[cam], rc.dst = job[k].d_dst, rc.dst_cap = (uint32_t)std::min<size_t>(job[k].cap, 0xffffffffu);
+    rc.res = r.res + cam;
+    bytes += job[k].n_bytes, cap_bytes += std::min(job[k].cap, raw_bound(format, job[k].n_bytes)) * 16;
+  }
+  {
+    ScopedKernel k(c, K_RAW_REDUCE, bytes + (uint64_t)(a.cam[0].tiles + a.cam[1].tiles) * sizeof(RawXf));
+    launch_raw_reduce(s, a);
+  }
+  {
+    ScopedKernel k(c, K_RAW_SCAN, (uint64_t)(a.cam[0].tiles + a.cam[1].tiles) * 2 * sizeof(RawXf));
+    launch_raw_scan(s, a);
+  }
+  {  // (booked as if every record the buffers have room for were written: the count is not known here)
+    ScopedKernel k(c, K_RAW_EMIT, bytes + cap_bytes);
+    launch_raw_emit(s, a);
+  }
+  for (int k = 0; k < 2; k++)
+    if (job[k].n_bytes) HIPCHK(c, hipMemcpyAsync(&res[k], a.cam[k].res, sizeof(RawResult), hipMemcpyDeviceToHost, s));
+  *args = a;
+  return 0;
+}
+// the emit launch again, into buffers that have room now (the tiles' prefixes are still where the scan left them)
+int raw_emit_again(esvio_fe_ctx* c, RawArgs* a, const RawJob job[2], RawResult res[2]) {
+  hipStream_t s = cur_stream(c);
+  for (int k = 0; k < 2; k++) {
+    if (!job[k].n_bytes) continue;
+    a->cam[k].dst = job[k].d_dst, a->cam[k].dst_cap = (uint32_t)std::min<size_t>(job[k].cap, 0xffffffffu);
+    HIPCHK(c, hipMemsetAsync((uint8_t*)a->cam[k].res + offsetof(RawResult, bad), 0, sizeof(unsigned long long), s));
+  }
+  {
+    ScopedKernel k(c, K_RAW_EMIT, (uint64_t)(res[0].events + res[1].events) * 16);
+    launch_raw_emit(s, *a);
+  }
+  for (int k = 0; k < 2; k++)
+    if (job[k].n_bytes) HIPCHK(c, hipMemcpyAsync(&res[k], a->cam[k].res, sizeof(RawResult), hipMemcpyDeviceToHost, s));
+  return 0;
+}
+void raw_info_fill(esvio_fe_raw_info* info, const RawResult& r, uint64_t wraps) {
+  if (!info) return;
+  info->events = r.events, info->untimed = r.untimed, info->other = r.other, info->bad = r.bad, info->wraps = wraps;
+  if (r.events) info->first_t_us = r.first_t, info->last_t_us = r.last_t;
+}
+void raw_info_clear(esvio_fe_raw_info* info, uint64_t wraps) {
+  if (!info) return;
+  info->events = info->untimed = info->other = info->bad = 0;
+  info->wraps = wraps;
+}
+// a call that succeeded: the camera's state is what the scan composed
+void raw_commit(esvio_fe_ctx* c, int cam, const RawResult& r) {
+  esvio_fe_ctx::Raw::State& st = c->rawdec.st[cam];
+  const RawXf& x = r.state;
+  st.seen = x.flags & kRawHasTh ? 1 : 0, st.th = x.th_last, st.wraps += x.wraps;
+  st.tl = (x.flags >> kRawTlShift) & 0xfffu, st.y = (x.flags >> kRawYShift) & 0x7ffu;
+  st.bx = x.bx, st.bp = x.flags & kRawBp ? 1 : 0;
+}
+}  // namespace
+
+int esvio_fe_raw_tile_bytes(void) { return (int)kRawTileBytes; }
+
+int esvio_fe_decode_raw(esvio_fe_handle c, int cam, int format, const void* words, size_t n_bytes, int space,
+                        int64_t t_offset_us, esvio_fe_event* dst, size_t dst_cap, int dst_space, esvio_fe_raw_info* info) {
+  if (!c) return ESVIO_FE_EINVAL;
+  if (cam != 0 && cam != 1) return fail(c, ESVIO_FE_EINVAL, "decode_raw: cam must be 0 or 1 (got %d)", cam);
+  raw_info_clear(info, c->rawdec.st[cam].wraps);
+  if (int rc = raw_args_check(c, "decode_raw", format, words, n_bytes, space, t_offset_us)) return rc;
+  if (dst_space != ESVIO_FE_HOST && dst_space != ESVIO_FE_DEVICE) return fail(c, ESVIO_FE_EINVAL, "decode_raw: bad memory space");
+  if (dst_cap && !dst) return fail(c, ESVIO_FE_EINVAL, "decode_raw: dst is null");
+  if (dst_space == ESVIO_FE_DEVICE && ((uintptr_t)dst & 15) != 0)
+    return fail(c, ESVIO_FE_EINVAL, "decode_raw: a device dst must be 16-byte aligned");
+  if (!n_bytes) return 0;
+  HIPCHK(c, hipSetDevice(c->dev));
+  const size_t bound = raw_bound(format, n_bytes);
+  RawJob job[2];
+  job[0].words = words, job[0].n_bytes = n_bytes;
+  job[0].d_dst = (EventRec*)dst, job[0].cap = std::min(dst_cap, bound);
+  if (dst_space == ESVIO_FE_HOST) {  // the records behind a host dst: one per word to begin with, never more than dst has room for
+    const size_t want = std::min(job[0].cap, std::max<size_t>(c->rawdec.dec[cam].cap, n_bytes / (format == ESVIO_FE_RAW_EVT3 ? 2 : 4)));
+    if (int rc = raw_ensure(c, cam, n_bytes, false, want)) return rc;
+    job[0].d_dst = c->rawdec.dec[cam], job[0].cap = std::min(job[0].cap, c->rawdec.dec[cam].cap);
+  }
+  const int cam_of[2] = {cam, cam};
+  RawArgs a;
+  RawResult r[2] = {};
+  if (int rc = raw_enqueue(c, format, space, t_offset_us, job, cam_of, &a, r)) return rc;
+  HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  if (dst_space == ESVIO_FE_HOST && !r[0].bad && r[0].events > job[0].cap && r[0].events <= dst_cap) {
+    if (int rc = raw_ensure(c, cam, n_bytes, false, r[0].events)) return rc;
+    job[0].d_dst = c->rawdec.dec[cam], job[0].cap = c->rawdec.dec[cam].cap;
+    if (int rc = raw_emit_again(c, &a, job, r)) return rc;
+    HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  }
+  if (c->prof_on) resolve_profile(c);
+  raw_info_fill(info, r[0], c->rawdec.st[cam].wraps);
+  if (r[0].bad)
+    return fail(c, ESVIO_FE_EINVAL, "decode_raw: %llu of %u events have a stamp outside [0, 2^32 s); the camera's decoder state is as it was",
+                r[0].bad, r[0].events);
+  if (r[0].events > dst_cap)
+    return fail(c, ESVIO_FE_EINVAL, "decode_raw: the chunk holds %u events, dst has room for %zu; the camera's decoder state is as it was",
+                r[0].events, dst_cap);
+  if (dst_space == ESVIO_FE_HOST && r[0].events) {
+    HIPCHK(c, hipMemcpyAsync(dst, job[0].d_dst, (size_t)r[0].events * sizeof(EventRec), hipMemcpyDeviceToHost, cur_stream(c)));
+    HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  }
+  raw_commit(c, cam, r[0]);
+  if (info) info->wraps = c->rawdec.st[cam].wraps;
+  return 0;
+}
+
+int esvio_fe_decode_reset(esvio_fe_handle c) {
+  if (!c) return ESVIO_FE_EINVAL;
+  c->rawdec.st[0] = c->rawdec.st[1] = esvio_fe_ctx::Raw::State();
+  return 0;
+}
+
+int esvio_fe_track_raw(esvio_fe_handle c, int format, const void* left, size_t left_bytes, const void* right,
+                       size_t right_bytes, int space, int64_t t_offset_us, int pub_this_frame,
+                       const esvio_fe_filter_params* filter, const esvio_fe_motion* motion, esvio_fe_tracks* out,
+                       esvio_fe_batch_info* info_out, esvio_fe_raw_info raw[2]) {
+  if (!c) return ESVIO_FE_EINVAL;
+  esvio_fe_batch_info info{};
+  if (info_out) *info_out = info;
+  const void* words[2] = {left, right};
+  const size_t nb[2] = {left_bytes, right_bytes};
+  for (int cam = 0; cam < 2; cam++) {
+    if (raw) raw_info_clear(&raw[cam], c->rawdec.st[cam].wraps);
+    if (int rc = raw_args_check(c, cam ? "track_raw (right)" : "track_raw (left)", format, words[cam], nb[cam], space, t_offset_us)) return rc;
+  }
+  if (filter)
+    if (int rc = baf_prm_check(c, filter, "track_raw")) return rc;
+  if (!c->announced.empty() || !c->inflight.empty())
+    return fail(c, ESVIO_FE_EINVAL, "track_raw: batches are announced on this handle (decode into memory of your own)");
+  if (!nb[0] && !nb[1]) return 0;  // nothing to decode: no left event, nothing tracked
+  HIPCHK(c, hipSetDevice(c->dev));
+  // where the records go: the current pair, or, in front of a filter, the stage's own buffers
+  const size_t wb = format == ESVIO_FE_RAW_EVT3 ? 2 : 4;
+  RawJob job[2];
+  auto place = [&](const size_t want[2]) -> int {
+    EventRec* d[2] = {nullptr, nullptr};
+    if (filter) {
+      for (int cam = 0; cam < 2; cam++) {
+        if (int rc = raw_ensure(c, cam, nb[cam], false, std::max<size_t>(want[cam], 1))) return rc;
+        d[cam] = c->rawdec.dec[cam];
+        job[cam].cap = c->rawdec.dec[cam].cap;
+      }
+    } else {
+      const int pair = c->cvt_pair;
+      const size_t nL = std::max(want[0], c->d_cvt_ev[pair][0].cap), nR = std::max(want[1], c->d_cvt_ev[pair][1].cap);
+      if (int rc = cvt_pair_begin(c, nL, nR, &d[0], &d[1])) return rc;
+      job[0].cap = c->d_cvt_ev[pair][0].cap, job[1].cap = c->d_cvt_ev[pair][1].cap;
+    }
+    for (int cam = 0; cam < 2; cam++) job[cam].words = words[cam], job[cam].n_bytes = nb[cam], job[cam].d_dst = d[cam];
+    return 0;
+  };
+  const size_t first[2] = {nb[0] / wb, nb[1] / wb};
+  if (int rc = place(first)) return rc;
+  const int cam_of[2] = {0, 1};
+  RawArgs a;
+  RawResult r[2] = {};
+  if (int rc = raw_enqueue(c, format, space, t_offset_us, job, cam_of, &a, r)) return rc;
+  HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  if (!r[0].bad && !r[1].bad && (r[0].events > job[0].cap || r[1].events > job[1].cap)) {
+    const size_t need[2] = {r[0].events, r[1].events};
+    if (int rc = place(need)) return rc;
+    if (int rc = raw_emit_again(c, &a, job, r)) return rc;
+    HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  }
+  if (c->prof_on) resolve_profile(c);
+  for (int cam = 0; cam < 2; cam++) {
+    if (raw && nb[cam]) raw_info_fill(&raw[cam], r[cam], c->rawdec.st[cam].wraps);
+    info.bad[cam] = r[cam].bad;
+  }
+  if (r[0].bad || r[1].bad) {
+    if (info_out) *info_out = info;
+    return fail(c, ESVIO_FE_EINVAL, "track_raw: %llu of %u events have a stamp outside [0, 2^32 s); both cameras' decoder states are as they were",
+                r[0].bad + r[1].bad, r[0].events + r[1].events);
+  }
+  // the decoder states move only when the whole call succeeds: a filter or track body that fails leaves them as they were
+  auto done = [&](int rc) {
+    for (int cam = 0; cam < 2 && rc == 0; cam++)
+      if (nb[cam]) {
+        raw_commit(c, cam, r[cam]);
+        if (raw) raw[cam].wraps = c->rawdec.st[cam].wraps;
+      }
+    return rc;
+  };
+  if (filter) {  // the body esvio_fe_track_batch has for device records with a filter: into the pair, stamped by the last kept left record
+    esvio_fe_batch b{};
+    b.left = (const esvio_fe_event*)job[0].d_dst, b.right = (const esvio_fe_event*)job[1].d_dst;
+    b.nL = r[0].events, b.nR = r[1].events, b.space = ESVIO_FE_DEVICE, b.pub_this_frame = pub_this_frame;
+    b.filter = filter, b.motion = motion, b.cur_time_from_batch = 1;
+    return done(track_batch_body(c, "track_raw", "decode and filter", b, out, info_out));
+  }
+  info.kept[0] = r[0].events, info.kept[1] = r[1].events;
+  if (info_out) *info_out = info;
+  if (!r[0].events) return done(0);  // node:150: an empty left message is not tracked
+  const uint64_t ticks = (uint64_t)r[0].last_t;
+  info.cur_time = (double)(uint32_t)(ticks / 1000000u) + 1e-9 * (double)(uint32_t)(ticks % 1000000u * 1000u);
+  const int rc = cvt_pair_track(c, info.cur_time, job[0].d_dst, r[0].events, job[1].d_dst, r[1].events, pub_this_frame, motion, out);
+  info.tracked = rc == 0;
+  if (info_out) *info_out = info;
+  return done(rc);
+}
+
 // ---- image front-end
 int esvio_fe_good_features_to_track(esvio_fe_handle c, const uint8_t* img, int max_corners,
                                     double quality, double min_distance, const uint8_t* mask,
@@ -2052,6 +2333,12 @@ int esvio_fe_reserve(esvio_fe_handle c, size_t max_left, size_t max_right, int h
   // the copy of a host source — not the records behind a host dst, which grow on the first call that has one
   if (c->baf.B)
     if (int rc = baf_ensure(c, std::max(max_left, max_right), host_batches != 0, false, false)) return rc;
+  // a handle that decodes raw streams: per camera the scratch of a stream of up to 8 bytes per event (include/esvio_fe.h)
+  if (c->rawdec.used) {
+    const size_t ev[2] = {max_left, max_right};
+    for (int cam = 0; cam < 2; cam++)
+      if (int rc = raw_ensure(c, cam, ev[cam] * 8, host_batches != 0, 0)) return rc;
+  }
   if (host_batches) {
     if (int rc = ensure_event_capacity(c, n)) return rc;
     if (stager_enabled(c)) {

@@ -70,7 +70,8 @@ const char* const kKernelNames[K_COUNT] = {
     "k_time_surface4", "k_time_surface", "k_median", "k_clahe", "k_norm_pyr", "k_pyr3", "k_pyr_down", "k_pyr_pad",
     "k_scharr", "k_pad_scharr", "k_lk_f32", "k_lk", "k_arc_map", "k_arc_ev", "k_dedup", "k_compact", "k_select_mw",
     "k_select", "k_select_gbm", "k_fast_score", "k_fast_collect", "k_events_from_fields", "k_baf_heads", "k_baf_filter",
-    "k_baf_count", "k_baf_scan", "k_baf_emit", "k_baf_keys_fields", "k_baf_emit_fields"};
+    "k_baf_count", "k_baf_scan", "k_baf_emit", "k_baf_keys_fields", "k_baf_emit_fields", "k_raw_reduce", "k_raw_scan",
+    "k_raw_emit"};
 
 // The host phases of one trackEvent call, in the order of esvio_fe_latency_call::phase_ms; kPhaseNames is what
 // esvio_fe_latency_phase_name returns and what the ESVIO_FE_TRACE summary prints.  The PH_PUB_* phases are parts of
@@ -498,6 +499,26 @@ struct esvio_fe_ctx {
     DevBuf<EventRec> src, out;
     size_t cap = 0;
   } baf;
+
+  // ---- esvio_fe_decode_raw / esvio_fe_track_raw: raw sensor streams (include/esvio_fe.h has the rule, fe_kernels.h
+  // the chain).  st: each camera's decoder state, kept on the HOST — it travels to the scan launch as an argument and
+  // comes back in the camera's result block, which is the pending slot: the host takes it over only once the call is
+  // known to succeed.  Everything else is allocated on first use and is the stage's own (main stream only), one per
+  // camera so that both cameras' chains are in flight together: src, the copy of a host source that is not read in
+  // place; sums, the tiles' transformers; dec, the records behind a host dst and, in esvio_fe_track_raw with a filter,
+  // the decoded records the filter reads; res, the two result blocks.
+  struct Raw {
+    struct State {
+      uint32_t seen = 0, th = 0, tl = 0, y = 0, bx = 0, bp = 0;
+      uint64_t wraps = 0;
+    } st[2];
+    DevBuf<uint8_t> src[2];
+    DevBuf<RawXf> sums[2];
+    DevBuf<EventRec> dec[2];
+    DevBuf<RawResult> res;
+    bool used = false;     // esvio_fe_reserve grows the scratch of a handle that has decoded before
+    int pinned_copy = -1;  // page-locked sources: -1 = in place up to kRawPinnedInPlaceBytes (fe_api.cpp); ESVIO_FE_RAW_PINNED_COPY=1 / 0: always copied first / always in place
+  } rawdec;
 };
 
 namespace esvio {

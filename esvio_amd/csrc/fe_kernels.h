@@ -80,12 +80,15 @@ enum KernelId {
   K_BAF_EMIT,
   K_BAF_KEYS_FIELDS, // esvio_fe_filter_batch on field arrays (its heads launch is booked as K_BAF_HEADS)
   K_BAF_EMIT_FIELDS,
+  K_RAW_REDUCE,      // esvio_fe_decode_raw / esvio_fe_track_raw: the decode chain runs in front of the track call
+  K_RAW_SCAN,
+  K_RAW_EMIT,
   K_COUNT
 };
 // esvio_fe_kernel_count(): the kernels of the tracker's entry points, the table bench.py and the recorded launch traces
 // list.  The ids from here on belong to stages off every track path and are listed by esvio_fe_stage_kernel_count().
 constexpr int kTrackKernels = K_BAF_HEADS;
-static_assert(K_EVENTS_FROM_FIELDS + 1 == kTrackKernels && K_BAF_EMIT_FIELDS + 1 == K_COUNT,
+static_assert(K_EVENTS_FROM_FIELDS + 1 == kTrackKernels && K_RAW_EMIT + 1 == K_COUNT,
               "a track-path kernel goes in front of K_BAF_HEADS (and into this assertion), a stage's kernel behind it");
 
 // ---- SAE update -------------------------------------------------------------------------
@@ -578,6 +581,56 @@ void launch_baf_keys_fields(hipStream_t s, const FieldsArgs& fields, uint32_t n,
                             long long* tstream, BafResult* res, int passes, int bits, uint32_t* ghist, uint32_t* lookback,
                             uint32_t lookback_words);
 void launch_baf_emit_fields(hipStream_t s, const BafArgs& a, const FieldsArgs& fields);
+
+// ---- raw sensor streams: Prophesee EVT3 / EVT2 words -> event records (esvio_fe_decode_raw, esvio_fe_track_raw) ----
+// include/esvio_fe.h holds the rule.  Everything a word needs from the words before it is a "last writer before me"
+// or a prefix sum, so a run of words is summarised by a TRANSFORMER of the decoder state (RawXf) and transformers
+// compose associatively (raw_combine: earlier, later).  The chain: reduce (one transformer per tile of kRawTileBytes
+// bytes) -> scan (one workgroup per camera: the tiles' exclusive prefixes, seeded with the camera's carried state; the
+// totals and the state after the call) -> emit (re-reads the tile, scans inside it from the tile's carry-in, builds the
+// records at offset + rank).  Three launches for one camera or for both: both cameras' tiles share each grid.  No
+// launch waits on the device for another workgroup.  EVT2 is the same chain with a smaller classifier.
+constexpr uint32_t kRawTileBytes = 4096;  // 256 lanes x 16 bytes: 2048 EVT3 words, 1024 EVT2 words
+constexpr int kRawEvt2 = 2, kRawEvt3 = 3;
+constexpr uint32_t kRawHasTh = 1u, kRawHasTl = 2u, kRawHasY = 4u, kRawHasBx = 8u, kRawBp = 16u;
+constexpr int kRawTlShift = 8, kRawYShift = 20;  // flags: tl in bits 8..19, y in bits 20..30
+struct RawXf {
+  uint32_t th_first, th_last;  // kRawHasTh: the first and the last TIME_HIGH value of the run ...
+  uint32_t wraps;              // ... and the wraps between its TIME_HIGH words
+  uint32_t flags;              // which fields the run sets (kRawHas*), and bp, tl, y as it leaves them
+  uint32_t bx;                 // kRawHasBx: bx as the run leaves it; else the sum of its increments (mod 2^16)
+  uint32_t before;             // events in front of the run's first TIME_HIGH (all of them if it has none): emitted if
+                               // the state in front of the run has seen a TIME_HIGH, else untimed
+  uint32_t after;              // events behind it: emitted
+  uint32_t other;
+};
+static_assert(sizeof(RawXf) == 32, "RawXf layout");
+struct RawResult {  // written by k_raw_scan (bad: cleared there, added to by k_raw_emit); one per camera
+  uint32_t events, untimed, other, wraps;  // wraps: inside this call
+  RawXf state;                             // the carried state composed with the whole call: the state after it
+  unsigned long long bad;
+  long long first_t, last_t;               // ticks of the first / last emitted event (k_raw_emit; untouched if none)
+};
+static_assert(sizeof(RawResult) == 72, "RawResult layout");
+struct RawCam {
+  const uint8_t* words;   // the device reads them here, at any alignment (16-byte aligned: one load per lane)
+  uint32_t n_bytes;       // a multiple of the word size
+  uint32_t tiles;         // ceil(n_bytes / kRawTileBytes); 0: the camera takes no part
+  RawXf seed;             // the carried state as a transformer (wraps 0, counts 0)
+  unsigned long long wraps_base;  // the carried wrap count
+  long long t_offset;     // microseconds
+  RawXf* sums;            // [tiles] reduce: the tiles' transformers; scan: their exclusive prefixes, seed included
+  EventRec* dst;          // [dst_cap]; nothing is stored when the call's events exceed dst_cap
+  uint32_t dst_cap;
+  RawResult* res;
+};
+struct RawArgs {
+  int format;     // kRawEvt2 / kRawEvt3
+  RawCam cam[2];  // the grid's blocks: cam[0].tiles, then cam[1].tiles
+};
+void launch_raw_reduce(hipStream_t s, const RawArgs& a);
+void launch_raw_scan(hipStream_t s, const RawArgs& a);
+void launch_raw_emit(hipStream_t s, const RawArgs& a);
 
 struct SelectArgs {
   const uint32_t* comp_xy;   // compacted candidates in stream order

@@ -4233,6 +4233,290 @@ void launch_baf_emit_fields(hipStream_t s, const BafArgs& a, const FieldsArgs& f
   abort();
 }
 
+// ============================================================================ raw sensor streams
+// EVT3 / EVT2 words -> event records (fe_kernels.h has the chain, include/esvio_fe.h the rule).
+//   raw_push      one word applied to a running transformer: raw_combine(run, the word's own transformer), written out
+//   raw_combine   (earlier, later) -> both; associative, not commutative
+//   k_raw_reduce  per tile: each lane its 16 bytes, the wave by cross-lane moves, the four waves through LDS
+//   k_raw_scan    per camera one workgroup: exclusive prefixes of the tiles' transformers behind the carried state
+//   k_raw_emit    per tile: the same scan inside the tile from its carry-in; every word emits from the state in front
+//                 of it, a VECT word's events ranked by the set bits of its mask; records stored from the word's lane
+__device__ __forceinline__ RawXf raw_identity() { return RawXf{0, 0, 0, 0, 0, 0, 0, 0}; }
+__device__ __forceinline__ uint32_t raw_wrap_step(uint32_t prev, uint32_t v, uint32_t half) {
+  return (v < prev && prev - v >= half) ? 1u : 0u;
+}
+__device__ __forceinline__ RawXf raw_combine(const RawXf& a, const RawXf& b, uint32_t half) {
+  RawXf r;
+  const bool ath = a.flags & kRawHasTh, bth = b.flags & kRawHasTh;
+  r.th_first = ath ? a.th_first : b.th_first;
+  r.th_last = bth ? b.th_last : a.th_last;
+  r.wraps = a.wraps + b.wraps + (ath && bth ? raw_wrap_step(a.th_last, b.th_first, half) : 0u);
+  const uint32_t tl_mask = kRawHasTl | (0xfffu << kRawTlShift), y_mask = kRawHasY | (0x7ffu << kRawYShift);
+  const uint32_t bx_mask = kRawHasBx | kRawBp;
+  r.flags = ((a.flags | b.flags) & kRawHasTh) | ((b.flags & kRawHasTl ? b.flags : a.flags) & tl_mask) |
+            ((b.flags & kRawHasY ? b.flags : a.flags) & y_mask) | ((b.flags & kRawHasBx ? b.flags : a.flags) & bx_mask);
+  r.bx = b.flags & kRawHasBx ? b.bx : ((a.bx + b.bx) & 0xffffu);
+  r.before = a.before + (ath ? 0u : b.before);
+  r.after = a.after + b.after + (ath ? b.before : 0u);
+  r.other = a.other + b.other;
+  return r;
+}
+__device__ __forceinline__ void raw_count(RawXf& r, uint32_t n) {
+  if (r.flags & kRawHasTh)
+    r.after += n;
+  else
+    r.before += n;
+}
+__device__ __forceinline__ void raw_time_high(RawXf& r, uint32_t v, uint32_t half) {
+  if (r.flags & kRawHasTh)
+    r.wraps += raw_wrap_step(r.th_last, v, half);
+  else
+    r.th_first = v;
+  r.th_last = v;
+  r.flags |= kRawHasTh;
+}
+template <int kFormat>
+__device__ __forceinline__ uint32_t raw_word_events(uint32_t w) {  // how many events the word stands for
+  if (kFormat == kRawEvt2) return (w >> 28) <= 1u ? 1u : 0u;
+  const uint32_t t = w >> 12;
+  return t == 2u ? 1u : t == 4u ? (uint32_t)__popc(w & 0xfffu) : t == 5u ? (uint32_t)__popc(w & 0xffu) : 0u;
+}
+template <int kFormat>
+__device__ __forceinline__ void raw_push(RawXf& r, uint32_t w) {
+  if (kFormat == kRawEvt2) {
+    const uint32_t t = w >> 28;
+    if (t <= 1u)
+      raw_count(r, 1u);
+    else if (t == 8u)
+      raw_time_high(r, w & 0x0fffffffu, 1u << 27);
+    else
+      r.other++;
+    return;
+  }
+  switch (w >> 12) {
+    case 0x0: r.flags = (r.flags & ~(0x7ffu << kRawYShift)) | kRawHasY | ((w & 0x7ffu) << kRawYShift); break;
+    case 0x2: raw_count(r, 1u); break;
+    case 0x3:
+      r.bx = w & 0x7ffu;
+      r.flags = (r.flags & ~kRawBp) | kRawHasBx | ((w >> 11) & 1u ? kRawBp : 0u);
+      break;
+    case 0x4:
+      raw_count(r, (uint32_t)__popc(w & 0xfffu));
+      r.bx = (r.bx + 12u) & 0xffffu;
+      break;
+    case 0x5:
+      raw_count(r, (uint32_t)__popc(w & 0xffu));
+      r.bx = (r.bx + 8u) & 0xffffu;
+      break;
+    case 0x6: r.flags = (r.flags & ~(0xfffu << kRawTlShift)) | kRawHasTl | ((w & 0xfffu) << kRawTlShift); break;
+    case 0x8: raw_time_high(r, w & 0xfffu, 2048u); break;
+    default: r.other++; break;
+  }
+}
+__device__ __forceinline__ RawXf raw_shfl_up(const RawXf& v, int o) {
+  RawXf r;
+  r.th_first = __shfl_up(v.th_first, o), r.th_last = __shfl_up(v.th_last, o), r.wraps = __shfl_up(v.wraps, o);
+  r.flags = __shfl_up(v.flags, o), r.bx = __shfl_up(v.bx, o), r.before = __shfl_up(v.before, o);
+  r.after = __shfl_up(v.after, o), r.other = __shfl_up(v.other, o);
+  return r;
+}
+// inclusive scan over the wave, lane 0 first (every lane of the wave calls it)
+__device__ __forceinline__ RawXf raw_wave_scan(RawXf incl, uint32_t half) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const RawXf v = raw_shfl_up(incl, o);
+    if (lane_id() >= o) incl = raw_combine(v, incl, half);
+  }
+  return incl;
+}
+// The lane's words of the tile: 16 bytes = kW words, the first nv of them inside the stream.  One 16-byte load where
+// the stream is 16-byte aligned and the lane's bytes all lie inside it; else byte by byte, never beyond n_bytes.
+template <int kFormat>
+__device__ __forceinline__ int raw_load(const RawCam& c, uint32_t tile, uint32_t w[8]) {
+  constexpr int kW = kFormat == kRawEvt3 ? 8 : 4, kB = 16 / kW;
+  const uint32_t off = tile * kRawTileBytes + threadIdx.x * 16u;
+  if (off >= c.n_bytes) return 0;
+  const uint32_t left = c.n_bytes - off;
+  if (left >= 16u && ((uintptr_t)c.words & 15) == 0) {
+    const uint4 q = *(const uint4*)(c.words + off);
+    if (kFormat == kRawEvt3) {
+      w[0] = q.x & 0xffffu, w[1] = q.x >> 16, w[2] = q.y & 0xffffu, w[3] = q.y >> 16;
+      w[4] = q.z & 0xffffu, w[5] = q.z >> 16, w[6] = q.w & 0xffffu, w[7] = q.w >> 16;
+    } else {
+      w[0] = q.x, w[1] = q.y, w[2] = q.z, w[3] = q.w;
+    }
+    return kW;
+  }
+  const int nv = left >= 16u ? kW : (int)(left / kB);
+#pragma unroll
+  for (int k = 0; k < kW; k++) {
+    w[k] = 0;
+    if (k < nv) {
+      const uint8_t* p = c.words + off + k * kB;
+      w[k] = kFormat == kRawEvt3 ? (uint32_t)p[0] | (uint32_t)p[1] << 8
+                                 : (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
+    }
+  }
+  return nv;
+}
+__device__ __forceinline__ const RawCam& raw_block_cam(const RawArgs& a, uint32_t* tile) {
+  const uint32_t b = blockIdx.x;
+  *tile = b < a.cam[0].tiles ? b : b - a.cam[0].tiles;
+  return b < a.cam[0].tiles ? a.cam[0] : a.cam[1];
+}
+
+template <int kFormat>
+__global__ __launch_bounds__(256) void k_raw_reduce(RawArgs a) {
+  constexpr int kW = kFormat == kRawEvt3 ? 8 : 4;
+  constexpr uint32_t kHalf = kFormat == kRawEvt3 ? 2048u : 1u << 27;
+  __shared__ RawXf part[4];
+  uint32_t tile;
+  const RawCam& c = raw_block_cam(a, &tile);
+  uint32_t w[8];
+  const int nv = raw_load<kFormat>(c, tile, w);
+  RawXf x = raw_identity();
+#pragma unroll
+  for (int k = 0; k < kW; k++)
+    if (k < nv) raw_push<kFormat>(x, w[k]);
+  x = raw_wave_scan(x, kHalf);
+  if (lane_id() == 63) part[threadIdx.x >> 6] = x;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    c.sums[tile] = raw_combine(raw_combine(part[0], part[1], kHalf), raw_combine(part[2], part[3], kHalf), kHalf);
+}
+
+__global__ __launch_bounds__(256) void k_raw_scan(RawArgs a) {
+  __shared__ RawXf part[4];
+  const RawCam& c = a.cam[blockIdx.x];
+  if (!c.tiles) return;
+  const uint32_t half = a.format == kRawEvt3 ? 2048u : 1u << 27;
+  const uint32_t per = (c.tiles + 255u) / 256u;
+  const uint32_t lo = min(threadIdx.x * per, c.tiles), hi = min(lo + per, c.tiles);
+  RawXf sum = raw_identity();
+  for (uint32_t j = lo; j < hi; j++) sum = raw_combine(sum, c.sums[j], half);
+  const RawXf incl = raw_wave_scan(sum, half);
+  if (lane_id() == 63) part[threadIdx.x >> 6] = incl;
+  __syncthreads();
+  RawXf run = c.seed;
+  for (int wv = 0; wv < (int)(threadIdx.x >> 6); wv++) run = raw_combine(run, part[wv], half);
+  const RawXf up = raw_shfl_up(incl, 1);
+  if (lane_id() > 0) run = raw_combine(run, up, half);
+  for (uint32_t j = lo; j < hi; j++) {
+    const RawXf s = c.sums[j];
+    c.sums[j] = run;
+    run = raw_combine(run, s, half);
+  }
+  if (threadIdx.x == 255) {  // (the chunks behind the last tile are empty: this lane's run is the whole call)
+    RawResult* r = c.res;
+    r->events = run.after, r->untimed = run.before, r->other = run.other, r->wraps = run.wraps;
+    r->state = run;
+    r->bad = 0;
+  }
+}
+
+// ticks -> the record's stamp words; bad: ticks < 0 or sec >= 2^32
+__device__ __forceinline__ bool raw_stamp(long long ticks, uint32_t* sec, uint32_t* nsec) {
+  if (ticks < 0 || ticks >= 4294967296ll * 1000000ll) {
+    *sec = *nsec = 0;
+    return false;
+  }
+  const unsigned long long s = (unsigned long long)ticks / 1000000ull;
+  *sec = (uint32_t)s;
+  *nsec = (uint32_t)((unsigned long long)ticks - s * 1000000ull) * 1000u;
+  return true;
+}
+
+template <int kFormat>
+__global__ __launch_bounds__(256) void k_raw_emit(RawArgs a) {
+  constexpr int kW = kFormat == kRawEvt3 ? 8 : 4;
+  constexpr uint32_t kHalf = kFormat == kRawEvt3 ? 2048u : 1u << 27;
+  __shared__ RawXf part[4];
+  uint32_t tile;
+  const RawCam& c = raw_block_cam(a, &tile);
+  uint32_t w[8];
+  const int nv = raw_load<kFormat>(c, tile, w);
+  RawXf x = raw_identity();
+  uint32_t mine = 0;
+#pragma unroll
+  for (int k = 0; k < kW; k++)
+    if (k < nv) raw_push<kFormat>(x, w[k]), mine += raw_word_events<kFormat>(w[k]);
+  const RawXf incl = raw_wave_scan(x, kHalf);
+  if (lane_id() == 63) part[threadIdx.x >> 6] = incl;
+  const RawXf up = raw_shfl_up(incl, 1);  // (while every lane is still here: the lane in front may have no event)
+  __syncthreads();
+  if (!mine) return;  // (behind the barrier and the cross-lane move: a lane without an event word has nothing to emit)
+  RawXf run = c.sums[tile];  // the tile's carry-in: the carried state and every tile in front of this one
+  for (int wv = 0; wv < (int)(threadIdx.x >> 6); wv++) run = raw_combine(run, part[wv], kHalf);
+  if (lane_id() > 0) run = raw_combine(run, up, kHalf);
+  const uint32_t total = c.res->events;
+  const bool store = total <= c.dst_cap;
+  uint4* dst = (uint4*)c.dst;
+  uint32_t bad = 0;
+#pragma unroll
+  for (int k = 0; k < kW; k++) {
+    if (k >= nv) break;
+    const uint32_t n = raw_word_events<kFormat>(w[k]);
+    if (n && (run.flags & kRawHasTh)) {
+      // (128 bits: the carried wrap count is 64 bits wide and the rule's integers have no bound; a stamp that leaves
+      // 64 bits is BAD like any other stamp behind 2^32 s, it never wraps around)
+      const __int128 wr = (__int128)(c.wraps_base + run.wraps);
+      __int128 t;
+      uint32_t xy, pol, mask = 1u;
+      if (kFormat == kRawEvt2) {
+        t = (wr << 34) + ((unsigned long long)run.th_last << 6) + ((w[k] >> 22) & 0x3fu);
+        xy = ((w[k] >> 11) & 0x7ffu) | (w[k] & 0x7ffu) << 16;
+        pol = w[k] >> 28;
+      } else {
+        t = (wr << 24) + ((unsigned long long)run.th_last << 12) + ((run.flags >> kRawTlShift) & 0xfffu);
+        const uint32_t y = (run.flags >> kRawYShift) & 0x7ffu;
+        if ((w[k] >> 12) == 2u) {
+          xy = (w[k] & 0x7ffu) | y << 16;
+          pol = (w[k] >> 11) & 1u;
+        } else {
+          xy = run.bx | y << 16;
+          pol = run.flags & kRawBp ? 1u : 0u;
+          mask = w[k] & ((w[k] >> 12) == 4u ? 0xfffu : 0xffu);
+        }
+      }
+      const __int128 wide = t + c.t_offset;
+      const long long ticks = wide < -0x7fffffffffffffffll ? -0x7fffffffffffffffll : wide > 0x7fffffffffffffffll ? 0x7fffffffffffffffll : (long long)wide;
+      uint32_t sec, nsec;
+      if (!raw_stamp(ticks, &sec, &nsec)) bad += n;
+      uint32_t pos = run.after;
+      if (pos == 0) c.res->first_t = ticks;
+      if (pos + n == total) c.res->last_t = ticks;
+      if (store)
+        while (mask) {  // ascending i: the lowest set bit first
+          const uint32_t i = (uint32_t)__ffs((int)mask) - 1u;
+          mask &= mask - 1u;
+          const uint32_t xi = ((xy & 0xffffu) + i) & 0xffffu;
+          dst[pos++] = make_uint4(xi | (xy & 0xffff0000u), sec, nsec, pol);
+        }
+    }
+    raw_push<kFormat>(run, w[k]);
+  }
+  if (bad) atomicAdd(&c.res->bad, (unsigned long long)bad);
+}
+
+static uint32_t raw_grid(const RawArgs& a) { return a.cam[0].tiles + a.cam[1].tiles; }
+void launch_raw_reduce(hipStream_t s, const RawArgs& a) {
+  if (!raw_grid(a)) return;
+  if (a.format == kRawEvt3)
+    launch_k(k_raw_reduce<kRawEvt3>, dim3(raw_grid(a)), dim3(256), 0, s, a);
+  else
+    launch_k(k_raw_reduce<kRawEvt2>, dim3(raw_grid(a)), dim3(256), 0, s, a);
+}
+void launch_raw_scan(hipStream_t s, const RawArgs& a) {
+  if (raw_grid(a)) launch_k(k_raw_scan, dim3(2), dim3(256), 0, s, a);
+}
+void launch_raw_emit(hipStream_t s, const RawArgs& a) {
+  if (!raw_grid(a)) return;
+  if (a.format == kRawEvt3)
+    launch_k(k_raw_emit<kRawEvt3>, dim3(raw_grid(a)), dim3(256), 0, s, a);
+  else
+    launch_k(k_raw_emit<kRawEvt2>, dim3(raw_grid(a)), dim3(256), 0, s, a);
+}
+
 // ============================================================================ greedy selection
 // Event_FeaturesToTrack (feature_tracker.cpp:13-38): candidates in stream order; accept iff the
 // pixel is not blocked; stamp cv::circle(r = MIN_DIST, filled) [OpenCV midpoint disc]; stop at

@@ -100,6 +100,15 @@ class BatchInfo(C.Structure):
                 ("tracked", C.c_int32), ("reserved", C.c_int32)]
 
 
+class RawInfo(C.Structure):
+    """esvio_fe_raw_info"""
+    _fields_ = [("events", C.c_uint64), ("untimed", C.c_uint64), ("other", C.c_uint64), ("bad", C.c_uint64),
+                ("wraps", C.c_uint64), ("first_t_us", C.c_int64), ("last_t_us", C.c_int64)]
+
+
+RAW_EVT2, RAW_EVT3 = 2, 3  # esvio_fe_decode_raw's formats
+
+
 class Tracks(C.Structure):
     _fields_ = [
         ("n_left", C.c_int32), ("n_right", C.c_int32),
@@ -115,7 +124,7 @@ class Tracks(C.Structure):
 # reference call it replaces)
 ABI_SYMBOLS = [
     "esvio_fe_calc_optical_flow_pyr_lk", "esvio_fe_comm_init", "esvio_fe_comm_unique_id",
-    "esvio_fe_convert_events", "esvio_fe_create",
+    "esvio_fe_convert_events", "esvio_fe_create", "esvio_fe_decode_raw", "esvio_fe_decode_reset",
     "esvio_fe_create_sae", "esvio_fe_create_sae_stereo", "esvio_fe_create_sae_stereo_mc", "esvio_fe_destroy",
     "esvio_fe_exchange_begin", "esvio_fe_exchange_end", "esvio_fe_exchange_tracks", "esvio_fe_export_image",
     "esvio_fe_fast_corners", "esvio_fe_filter_batch", "esvio_fe_filter_events", "esvio_fe_filter_reset", "esvio_fe_features_to_track", "esvio_fe_features_to_track_fast", "esvio_fe_find_fundamental_mat", "esvio_fe_finish", "esvio_fe_get_sae",
@@ -126,7 +135,7 @@ ABI_SYMBOLS = [
     "esvio_fe_sae_slice_last", "esvio_fe_sae_to_time_surface", "esvio_fe_set_auto_exchange", "esvio_fe_set_detector",
     "esvio_fe_set_host_threads", "esvio_fe_set_launch_thread", "esvio_fe_set_lazy_new_stereo",
     "esvio_fe_set_next_batch", "esvio_fe_set_next_batch_mc", "esvio_fe_track_batch", "esvio_fe_track_event", "esvio_fe_track_event_fields",
-    "esvio_fe_track_event_filtered", "esvio_fe_track_event_mc",
+    "esvio_fe_track_event_filtered", "esvio_fe_track_event_mc", "esvio_fe_track_raw",
     "esvio_fe_track_image", "esvio_fe_unregister_host_buffer", "esvio_fe_version",
 ]
 # test / measurement taps: include/esvio_fe_test.h (not part of the boundary)
@@ -138,7 +147,7 @@ TEST_SYMBOLS = [
     "esvio_fe_host_stage_pack", "esvio_fe_staging_counters",
     "esvio_fe_kernel_count", "esvio_fe_kernel_name", "esvio_fe_latency_phase_name", "esvio_fe_latency_recent",
     "esvio_fe_latency_stats", "esvio_fe_lift_projective", "esvio_fe_plain_call_counters", "esvio_fe_ransac_stats",
-    "esvio_fe_ransac_tail", "esvio_fe_reset_kernel_stats", "esvio_fe_set_profiling", "esvio_fe_set_sae",
+    "esvio_fe_ransac_tail", "esvio_fe_raw_tile_bytes", "esvio_fe_reset_kernel_stats", "esvio_fe_set_profiling", "esvio_fe_set_sae",
     "esvio_fe_stage_kernel_count", "esvio_fe_stream",
 ]
 
@@ -241,6 +250,10 @@ def load_library(build_if_missing=True):
     L.esvio_fe_track_batch.argtypes = [vp, C.POINTER(Batch), C.POINTER(Tracks), C.POINTER(BatchInfo)]
     L.esvio_fe_track_event_filtered.argtypes = [vp, vp, sz, vp, sz, i, C.c_int64, i, i, C.POINTER(Tracks),
                                                 C.POINTER(C.c_uint64 * 2), C.POINTER(d)]
+    L.esvio_fe_decode_raw.argtypes = [vp, i, i, vp, sz, i, C.c_int64, vp, sz, i, C.POINTER(RawInfo)]
+    L.esvio_fe_decode_reset.argtypes = [vp]
+    L.esvio_fe_track_raw.argtypes = [vp, i, vp, sz, vp, sz, i, C.c_int64, i, C.POINTER(FilterParams), C.POINTER(Motion),
+                                     C.POINTER(Tracks), C.POINTER(BatchInfo), C.POINTER(RawInfo * 2)]
     L.esvio_fe_set_profiling.argtypes = [vp, i]
     L.esvio_fe_kernel_name.restype = C.c_char_p
     L.esvio_fe_kernel_name.argtypes = [i]
@@ -586,6 +599,76 @@ class FeatureTracker:
         if info.tracked:
             self._take(copy)
         return info
+
+    def decode_raw(self, cam, fmt, words, t_offset_us=0, dst_cap=None, device=False):
+        """the raw-stream decode stage (esvio_fe_decode_raw; include/esvio_fe.h has the rule): camera `cam`'s decoder
+        state advanced by `words` — a contiguous numpy array of raw words (any dtype: its bytes are the stream) or a
+        (device_ptr, n_bytes) tuple — of format RAW_EVT2 / RAW_EVT3.  Returns (records, RawInfo): records a numpy
+        EVENT_DTYPE array, or with device=True a FilteredEvents in device memory (`.arg`, `.n`, `.free()`).  dst_cap
+        None: room for every record the words can stand for.  A failed call raises FrontendError with `.info`."""
+        from .events import EVENT_DTYPE
+        L = self._hd.L
+        if isinstance(words, tuple):
+            ptr, nbytes, space = C.c_void_p(words[0]), int(words[1]), DEVICE
+        else:
+            words = np.ascontiguousarray(words)
+            ptr, nbytes, space = _p(words), words.nbytes, HOST
+        if dst_cap is None:
+            dst_cap = nbytes // 2 * 12 if fmt == RAW_EVT3 else nbytes // 4
+        info = RawInfo()
+        if device:
+            dst = C.c_void_p()
+            rc = L.esvio_fe_mem_alloc(DEVICE, 16 * max(dst_cap, 1), C.byref(dst))
+            if rc:
+                raise FrontendError("esvio_fe_mem_alloc rc=%d" % rc)
+            out = None
+        else:
+            out = np.zeros(dst_cap, EVENT_DTYPE)
+            dst = _p(out)
+        rc = L.esvio_fe_decode_raw(self._hd.h, int(cam), int(fmt), ptr, nbytes, space, int(t_offset_us), dst, int(dst_cap),
+                                   DEVICE if device else HOST, C.byref(info))
+        if rc:
+            if device:
+                L.esvio_fe_mem_free(DEVICE, dst)
+            e = FrontendError("rc=%d: %s" % (rc, L.esvio_fe_last_error(self._hd.h).decode()))
+            e.info = info
+            raise e
+        k = int(info.events)
+        return (FilteredEvents(dst, k, None) if device else out[:k]), info
+
+    def decode_reset(self):
+        """both cameras' raw-stream decoder states back to the fresh state (esvio_fe_decode_reset)"""
+        self._hd.check(self._hd.L.esvio_fe_decode_reset(self._hd.h))
+
+    def track_raw(self, fmt, left, right, t_offset_us=0, pub=True, params=None, measurements=None, copy=True):
+        """one batch of raw words per camera through esvio_fe_track_raw: left / right are contiguous numpy arrays of raw
+        words or (device_ptr, n_bytes) tuples (both in one memory space); params: a FilterParams or None; measurements:
+        an esvio_fe_motion or None.  Returns (BatchInfo, (RawInfo, RawInfo)); a failed call raises FrontendError with
+        `.info` and `.raw`."""
+        args, spaces, keep = [], [], []
+        for w in (left, right):
+            if isinstance(w, tuple):
+                args += [C.c_void_p(w[0]), int(w[1])]
+                spaces.append(DEVICE)
+            else:
+                w = np.ascontiguousarray(w)
+                keep.append(w)
+                args += [_p(w), w.nbytes]
+                if w.nbytes:
+                    spaces.append(HOST)
+        assert len(set(spaces)) <= 1, "both cameras' words lie in one memory space"
+        info, raw = BatchInfo(), (RawInfo * 2)()
+        rc = self._hd.L.esvio_fe_track_raw(self._hd.h, int(fmt), *args, spaces[0] if spaces else HOST, int(t_offset_us), int(pub),
+                                           C.byref(params) if params is not None else None,
+                                           C.byref(measurements) if measurements is not None else None,
+                                           C.byref(self._tr), C.byref(info), C.byref(raw))
+        if rc:
+            e = FrontendError("rc=%d: %s" % (rc, self._hd.L.esvio_fe_last_error(self._hd.h).decode()))
+            e.info, e.raw = info, raw
+            raise e
+        if info.tracked:
+            self._take(copy)
+        return info, (raw[0], raw[1])
 
     def filter_reset(self):
         """every stamp plane of the background-activity filter back to `none` (esvio_fe_filter_reset)"""

@@ -563,6 +563,99 @@ typedef struct esvio_fe_batch_info {
  * and n > 0, descriptor errors, the filter's limits) are ESVIO_FE_EINVAL before any device work. */
 int esvio_fe_track_batch(esvio_fe_handle h, const esvio_fe_batch* b, esvio_fe_tracks* out, esvio_fe_batch_info* info);
 
+/* ---- raw sensor streams: Prophesee EVT3 / EVT2 words -> event records, on the device ------- */
+/* Prophesee sensors (the Gen3 VGA of the esio_DSEC and esvio_VECtor parameter sets: EVT2; the Gen4 HD, 1280x720: EVT3)
+ * emit a bit-packed, stateful word stream — a .raw recording behind its ASCII header, and what the sensor's USB
+ * transfers hold.  An event's row, time base and vector base live in EARLIER words, so no esvio_fe_event_fields can
+ * express it.  The reference has no counterpart, and neither a specification nor a vendor decoder was at hand: the rule
+ * below is RESTATED FROM RECALL of the published format descriptions, it is UNPINNED — not claimed to be bit-equal to
+ * the vendor's decoder — and THIS TEXT IS THE SPECIFICATION; the kernels equal its sequential reading
+ * (tests/evt_ref.py) exactly.
+ *
+ * Per handle and camera there is a decoder state.  It survives from call to call, so a chunk may end anywhere, in the
+ * middle of a vector run too.  It is cleared by esvio_fe_decode_reset, and by esvio_fe_reset as part of "as a freshly
+ * created handle".
+ *
+ * EVT3.  State: seen=0, th=0, wraps=0, tl=0, y=0, bx=0, bp=0.  Words are 16-bit little-endian, processed in order;
+ * type = w >> 12:
+ *   0x0 ADDR_Y       y = w & 0x7FF (bit 11 ignored)
+ *   0x2 ADDR_X       one event (x = w & 0x7FF, y, p = (w>>11)&1, t)
+ *   0x3 VECT_BASE_X  bx = w & 0x7FF; bp = (w>>11)&1
+ *   0x4 VECT_12      for i = 0..11 ascending, if bit i of w is set: one event (x = (bx+i) & 0xFFFF, y, bp, t);
+ *                    then bx = (bx+12) & 0xFFFF
+ *   0x5 VECT_8       the same with 8 bits and +8
+ *   0x6 TIME_LOW     tl = w & 0xFFF
+ *   0x8 TIME_HIGH    v = w & 0xFFF; if seen && v < th && th - v >= 2048: wraps += 1 (a smaller back-step is a
+ *                    back-step: time goes back, no wrap); then th = v, seen = 1; tl is kept
+ *   every other type: ignored, counted in `other` (EXT_TRIGGER, OTHERS, CONTINUED_*: counted, not decoded)
+ * t is in microseconds: t = wraps * 2^24 + th * 4096 + tl, taken at the word that emits.  An event emitted while
+ * seen == 0 is not emitted: it is counted in `untimed`.
+ *
+ * EVT2.  State: seen=0, th=0, wraps=0.  Words are 32-bit little-endian; type = w >> 28:
+ *   0x0 CD_OFF (p=0), 0x1 CD_ON (p=1): one event x = (w>>11)&0x7FF, y = w&0x7FF,
+ *                    t = wraps * 2^34 + th * 64 + ((w>>22)&0x3F)
+ *   0x8 TIME_HIGH    v = w & 0x0FFFFFFF, the same wrap rule with half range 2^27
+ *   everything else: counted in `other`; `untimed` as for EVT3.
+ *
+ * Records.  ticks = t + t_offset_us (signed, |t_offset_us| <= 2^62); sec = ticks / 10^6, nsec = (ticks % 10^6) * 1000;
+ * x and y are copied as 16-bit patterns (an out-of-sensor pixel is the SAE update's business, as in the conversion);
+ * polarity 0 or 1, the padding bytes 0 — byte for byte what esvio_amd.events.make_events builds.  Events are emitted in
+ * word order, and inside a VECT word in ascending i.  An event is BAD when ticks < 0 or sec >= 2^32 (in exact integers,
+ * whatever the carried wrap count: a stamp that leaves 64 bits is BAD, it never wraps around): any BAD event fails
+ * the call with ESVIO_FE_EINVAL, info->bad is exact and dst is unspecified.  More events than dst_cap also fail the call
+ * with ESVIO_FE_EINVAL: info->events holds the exact number needed, dst is unspecified.  In both failures THE CAMERA'S
+ * DECODER STATE IS AS IT WAS BEFORE THE CALL, and the next call works normally.  A trailing odd byte (EVT3) or a length
+ * that is not a multiple of 4 (EVT2) is an argument error, raised before any device work.
+ *
+ * Out of scope: cutting a stream into time-based batches (the caller chooses the chunks; first_t_us / last_t_us tell it
+ * what it got), EVT2.1, EVT4, AEDAT, the .raw file's ASCII header. */
+#define ESVIO_FE_RAW_EVT2 2
+#define ESVIO_FE_RAW_EVT3 3
+typedef struct esvio_fe_raw_info {
+  uint64_t events, untimed, other, bad, wraps; /* wraps: the camera's count after the call (before it, if it failed) */
+  int64_t first_t_us, last_t_us;               /* ticks of the first / last emitted event; untouched if none */
+} esvio_fe_raw_info;
+/* the decode stage: camera `cam`'s state advanced by the n_bytes of `words`, the records written to dst.
+ * space says where the words lie, with esvio_fe_convert_events' three source paths: ESVIO_FE_DEVICE is read in place
+ * (at any alignment; 16-byte aligned words are read 16 bytes per lane); ESVIO_FE_HOST: page-locked memory the library's
+ * runtime knows is read in place by the kernels, over PCIe, up to 256 KiB and copied first beyond that (every word is
+ * read twice: KERNELS.md "Raw streams"); pageable memory is copied once into the handle's scratch, the 2 or 4 bytes
+ * per word and nothing else.  dst: room for dst_cap records (ESVIO_FE_DEVICE: 16-byte aligned device memory, may be
+ * handed to every entry point that takes device events, esvio_fe_set_next_batch included; ESVIO_FE_HOST: downloaded);
+ * 12 * (n_bytes / 2) records (EVT3) or n_bytes / 4 (EVT2) always suffice.  info is optional.  n_bytes == 0 succeeds and
+ * touches nothing; n_bytes <= 2^28.
+ * Orders itself on the main stream, waits for its own result and touches nothing of the tracker: made between two
+ * track calls (announced batches or not) it changes no later tracking result.  Its scratch — 32 bytes per 4096 bytes
+ * of words, the copy of a pageable source, the records behind a host dst — grows on first use, and with
+ * esvio_fe_reserve for a handle that has decoded before (there for streams of up to 8 bytes per event): a second call
+ * of a given size allocates nothing.
+ * ESVIO_FE_EINVAL with a message, before any device work: an unknown format, cam outside 0..1, a bad space, null words
+ * with n_bytes > 0, a null dst with dst_cap > 0, a misaligned device dst, |t_offset_us| > 2^62, a bad length. */
+int esvio_fe_decode_raw(esvio_fe_handle h, int cam, int format, const void* words, size_t n_bytes, int space,
+                        int64_t t_offset_us, esvio_fe_event* dst, size_t dst_cap, int dst_space,
+                        esvio_fe_raw_info* info);
+/* both cameras' decoder states back to the fresh state */
+int esvio_fe_decode_reset(esvio_fe_handle h);
+/* esvio_fe_track_batch for a host that has raw words: both cameras' chunks are decoded into the handle's two alternating
+ * buffer pairs (buffer lifetime exactly as esvio_fe_track_event_fields states it) and tracked from there with
+ * cur_time = (double)sec + 1e-9 * (double)nsec of the last LEFT record the tracker is given; `filter` (optional) and
+ * `motion` (optional) as in esvio_fe_batch; with a filter the decoded records are filtered into the pair.  Both
+ * cameras' decode chains are enqueued first — three launches for the two of them — and the host waits once before
+ * filtering or tracking starts.
+ * Capacity is the handle's business: a camera's buffer holds one record per word to begin with (always enough for EVT2
+ * and for EVT3 without dense vectors); when the reduce pass reports more, the buffers grow to the reported count and the
+ * emit launch alone is repeated — after that a stream of the same density allocates nothing.
+ * info->kept = the events decoded (after a filter: kept), info->bad the BAD events; raw[cam] (optional) as
+ * esvio_fe_decode_raw's info.  A BAD event in either camera: ESVIO_FE_EINVAL, nothing tracked, BOTH cameras' decoder
+ * states as they were — as after every other failure of this call, the filter's or the tracker's included: the states
+ * move only when the call returns ESVIO_FE_OK.  No left event (or, with a filter, none kept): ESVIO_FE_OK, tracked = 0, `out` untouched, the
+ * decoder states (and the filter's planes) advanced.  Refused while batches are announced (decode into memory of your
+ * own for that).  Argument errors as esvio_fe_decode_raw's and the filter's limits, before any device work. */
+int esvio_fe_track_raw(esvio_fe_handle h, int format, const void* left, size_t left_bytes,
+                       const void* right, size_t right_bytes, int space, int64_t t_offset_us,
+                       int pub_this_frame, const esvio_fe_filter_params* filter, const esvio_fe_motion* motion,
+                       esvio_fe_tracks* out, esvio_fe_batch_info* info, esvio_fe_raw_info raw[2]);
+
 /* ---- camera split across GPUs (BASELINE config C4) ----------------------- */
 /* The left and right cameras have disjoint SAE state (sae_/sae_latest_ vs sae_right/
  * sae_latest_right, event_detector.h:74-79), so a second GPU can own the right camera: it runs

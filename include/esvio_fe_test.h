@@ -165,6 +165,8 @@ const char* esvio_fe_kernel_name(int kernel_id);
 int esvio_fe_get_kernel_stats(esvio_fe_handle h, int kernel_id, double* total_ms,
                               uint64_t* launches, uint64_t* alg_bytes);
 int esvio_fe_reset_kernel_stats(esvio_fe_handle h);
+/* the bytes of raw words one workgroup of the decode chain takes (esvio_fe_decode_raw): where its tile edges lie */
+int esvio_fe_raw_tile_bytes(void);
 /* the hipStream_t the handle launches on (as void*) */
 void* esvio_fe_stream(esvio_fe_handle h);
 /* hipMemGetInfo on the handle's device, through the HIP runtime the library itself is linked to */
