@@ -358,6 +358,7 @@ namespace {
 int baf_clear(esvio_fe_ctx* c);  // the background-activity filter's planes back to `none` (below, with the stage)
 int baf_ensure(esvio_fe_ctx* c, size_t n, bool host_src, bool host_dst, bool fields_form);
 int raw_ensure(esvio_fe_ctx* c, int cam, size_t n_bytes, bool copied_src, size_t dec_records);  // (below, with the stage)
+void feed_empty(esvio_fe_ctx* c, bool streams_idle);  // the feed: no records, no windows (below, with the feed)
 }  // namespace
 
 int esvio_fe_reset(esvio_fe_handle c) {
@@ -390,7 +391,9 @@ int esvio_fe_reset(esvio_fe_handle c) {
   HIPCHK(c, hipMemsetAsync(c->S2, 0, (size_t)2 * c->P * 16, cur_stream(c)));
   if (int rc = baf_clear(c)) return rc;  // the background-activity filter's planes: none everywhere
   c->rawdec.st[0] = c->rawdec.st[1] = esvio_fe_ctx::Raw::State();  // the raw-stream decoder: the fresh state
+  c->slice.st[0] = c->slice.st[1] = esvio_fe_ctx::Slice::State();  // the stream slicer: no event seen, no window closed
   HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  feed_empty(c, true);  // an open feed: no records, no windows (it stays open); every stream is idle here
   clear_tracker_state(c);
   return 0;
 }
@@ -1830,6 +1833,540 @@ int esvio_fe_track_raw(esvio_fe_handle c, int format, const void* left, size_t l
   return done(rc);
 }
 
+// ---- stream slicing: a record stream cut into fixed-rate windows (the rule: include/esvio_fe.h; the chain: fe_kernels.h)
+namespace {
+using SliceState = esvio_fe_ctx::Slice::State;
+using SliceBound = esvio_fe_ctx::Slice::Bound;
+constexpr size_t kSliceMaxEvents = (size_t)1 << 30;
+constexpr size_t kSliceTable = 4 * (kSliceMaxWindows + 1);  // boundaries the table holds: a call needs kSliceMaxWindows + 1 of them
+constexpr uint32_t kSliceInlineCuts = 60;                   // cut entries that arrive with the result block (one 256-byte copy)
+
+inline double slice_to_sec(uint64_t sec, uint32_t nsec) { return (double)sec + 1e-9 * (double)nsec; }
+// ros::Time::fromSec, restated (include/esvio_fe.h)
+inline SliceBound slice_time(double d) {
+  const double fl = std::floor(d);
+  uint64_t sec = (uint64_t)fl;
+  uint64_t nsec = (uint64_t)std::round((d - fl) * 1e9);
+  if (nsec >= 1000000000ull) sec += 1, nsec -= 1000000000ull;
+  return SliceBound{sec, (uint32_t)nsec};
+}
+inline bool slice_same_chain(const SliceState& a, const SliceState& b) {
+  return a.seen && b.seen && a.frequency == b.frequency && a.o_sec == b.o_sec && a.o_nsec == b.o_nsec;
+}
+
+// The camera's table covers E_m .. E_{m + kSliceMaxWindows} of st's chain (or ends in front of that with a boundary that
+// leaves 32 bits); *n_bounds: the entries from E_m on a call may search.  Recomputed — from E_0 for a new chain, else
+// from the entry for m, which the table always holds — and sent to the device when it does not.
+int slice_table(esvio_fe_ctx* c, int cam, const SliceState& st, uint32_t* n_bounds, hipStream_t s) {
+  esvio_fe_ctx::Slice& sl = c->slice;
+  std::vector<SliceBound>& E = sl.E[cam];
+  const double period = 1.0 / st.frequency;
+  const bool same = slice_same_chain(sl.tab_for[cam], st) && st.m >= sl.tb[cam] && st.m - sl.tb[cam] < E.size();
+  auto covers = [&] {
+    const size_t at = (size_t)(st.m - sl.tb[cam]);
+    return E.size() - at > kSliceMaxWindows || (E.back().sec >> 32) != 0;
+  };
+  if (!same || !covers()) {
+    SliceBound e;
+    if (same) {
+      e = E[(size_t)(st.m - sl.tb[cam])];
+    } else {  // (a fresh chain has closed nothing: m == 0)
+      if (st.m != 0) return fail(c, ESVIO_FE_EINTERNAL, "slice: the boundary table does not belong to the camera's state");
+      e = slice_time(slice_to_sec(st.o_sec, st.o_nsec) + period);
+    }
+    E.clear();
+    E.push_back(e);
+    while (E.size() < kSliceTable && (E.back().sec >> 32) == 0) E.push_back(slice_time(slice_to_sec(E.back().sec, E.back().nsec) + period));
+    sl.tb[cam] = st.m;
+    sl.tab_for[cam] = st;
+    if (!sl.bounds[cam])
+      if (int rc = sl.bounds[cam].alloc(c, kSliceTable)) return rc;
+    if (!sl.h_bounds[cam])
+      if (int rc = sl.h_bounds[cam].alloc(c, kSliceTable)) return rc;
+    for (size_t k = 0; k < E.size(); k++) sl.h_bounds[cam][k] = slice_to_sec(E[k].sec, E[k].nsec);
+    HIPCHK(c, hipMemcpyAsync(sl.bounds[cam], sl.h_bounds[cam], E.size() * sizeof(double), hipMemcpyHostToDevice, s));
+  }
+  *n_bounds = (uint32_t)std::min<size_t>(E.size() - (size_t)(st.m - sl.tb[cam]), kSliceMaxWindows + 1);
+  return 0;
+}
+SliceBound slice_bound(const esvio_fe_ctx* c, int cam, uint64_t k) { return c->slice.E[cam][(size_t)(k - c->slice.tb[cam])]; }
+
+void slice_info_state(esvio_fe_slice_info* info, const SliceState& st) {
+  if (!info) return;
+  info->closed = 0, info->first_window = info->count = st.m, info->open_events = st.open;
+}
+int slice_cam_check(esvio_fe_ctx* c, const char* who, int cam) {
+  return cam == 0 || cam == 1 ? 0 : fail(c, ESVIO_FE_EINVAL, "%s: cam must be 0 or 1 (got %d)", who, cam);
+}
+}  // namespace
+
+int esvio_fe_slice_tile_events(void) { return (int)kSliceTile; }
+
+namespace {
+int slice_feed_check(esvio_fe_ctx* c, const char* who) {  // an open feed keeps its windows in the cameras' slicer states
+  return c->feed.open ? fail(c, ESVIO_FE_EINVAL, "%s: a feed is open on this handle and owns the slicer (esvio_fe_feed_close first)", who) : 0;
+}
+int slice_events_impl(esvio_fe_ctx* c, int cam, const esvio_fe_event* ev, size_t n, int space, const esvio_fe_slice_params* prm,
+                      uint64_t* cuts, size_t cuts_cap, esvio_fe_slice_info* info);
+}  // namespace
+
+int esvio_fe_slice_events(esvio_fe_handle c, int cam, const esvio_fe_event* ev, size_t n, int space,
+                          const esvio_fe_slice_params* prm, uint64_t* cuts, size_t cuts_cap, esvio_fe_slice_info* info) {
+  if (!c) return ESVIO_FE_EINVAL;
+  if (int rc = slice_feed_check(c, "slice_events")) return rc;
+  return slice_events_impl(c, cam, ev, n, space, prm, cuts, cuts_cap, info);
+}
+
+namespace {
+int slice_events_impl(esvio_fe_ctx* c, int cam, const esvio_fe_event* ev, size_t n, int space, const esvio_fe_slice_params* prm,
+                      uint64_t* cuts, size_t cuts_cap, esvio_fe_slice_info* info) {
+  if (int rc = slice_cam_check(c, "slice_events", cam)) return rc;
+  esvio_fe_ctx::Slice& sl = c->slice;
+  const SliceState& cur = sl.st[cam];
+  slice_info_state(info, cur);
+  if (space != ESVIO_FE_HOST && space != ESVIO_FE_DEVICE) return fail(c, ESVIO_FE_EINVAL, "slice_events: bad memory space");
+  if (!prm) return fail(c, ESVIO_FE_EINVAL, "slice_events: prm is null");
+  if (prm->reserved != 0) return fail(c, ESVIO_FE_EINVAL, "slice_events: reserved must be 0");
+  if (!(prm->frequency >= 1e-3 && prm->frequency <= 1e6))
+    return fail(c, ESVIO_FE_EINVAL, "slice_events: frequency must be in [1e-3, 1e6] (got %g)", prm->frequency);
+  if (n && !ev) return fail(c, ESVIO_FE_EINVAL, "slice_events: ev is null");
+  if (n > kSliceMaxEvents) return fail(c, ESVIO_FE_EINVAL, "slice_events: a call takes at most 2^30 events");
+  if (space == ESVIO_FE_DEVICE && ((uintptr_t)ev & 15) != 0)
+    return fail(c, ESVIO_FE_EINVAL, "slice_events: device events must be 16-byte aligned");
+  if (cuts_cap && !cuts) return fail(c, ESVIO_FE_EINVAL, "slice_events: cuts is null");
+  if (!n) return 0;
+  HIPCHK(c, hipSetDevice(c->dev));
+  hipStream_t s = cur_stream(c);
+  // the state this call works from: the camera's, or — for its first events — the one they and prm define
+  SliceState st = cur;
+  if (cur.seen) {
+    const bool same = prm->frequency == cur.frequency && (prm->has_origin != 0) == (cur.has_origin != 0) &&
+                      (!prm->has_origin || (prm->origin.sec == cur.o_sec && prm->origin.nsec == cur.o_nsec));
+    if (!same)
+      return fail(c, ESVIO_FE_EINVAL, "slice_events: frequency and origin are fixed by the camera's first call (esvio_fe_slice_reset first)");
+  } else {
+    esvio_fe_event first = prm->origin;
+    if (!prm->has_origin) {
+      if (space == ESVIO_FE_HOST) {
+        first = ev[0];
+      } else {
+        HIPCHK(c, hipMemcpyAsync(&first, ev, sizeof(first), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+      }
+    }
+    st.seen = true, st.has_origin = prm->has_origin != 0, st.frequency = prm->frequency;
+    st.o_sec = first.sec, st.o_nsec = first.nsec;
+  }
+  uint32_t n_bounds = 0;
+  if (int rc = slice_table(c, cam, st, &n_bounds, s)) return rc;
+  const uint32_t tiles = (uint32_t)((n + kSliceTile - 1) / kSliceTile);
+  if (!sl.res)
+    if (int rc = sl.res.alloc(c, 2 * kSliceResWords)) return rc;
+  if (!sl.h_res)
+    if (int rc = sl.h_res.alloc(c, 2 * kSliceResWords)) return rc;
+  if (int rc = sl.tmax[cam].grow(c, tiles)) return rc;
+  const EventRec* d_ev = (const EventRec*)ev;
+  if (space == ESVIO_FE_HOST) {
+    if (int rc = sl.src[cam].grow(c, n)) return rc;
+    HIPCHK(c, hipMemcpyAsync(sl.src[cam], ev, n * sizeof(EventRec), hipMemcpyHostToDevice, s));
+    d_ev = sl.src[cam];
+  }
+  uint32_t* d_res = sl.res + (size_t)cam * kSliceResWords;
+  uint32_t* h_res = sl.h_res + (size_t)cam * kSliceResWords;
+  SliceArgs a{};
+  SliceCam& sc = a.cam[0];
+  sc.ev = d_ev, sc.n = (uint32_t)n, sc.tiles = tiles;
+  sc.bounds = sl.bounds[cam] + (size_t)(st.m - sl.tb[cam]), sc.n_bounds = n_bounds;
+  sc.tmax = sl.tmax[cam], sc.res = (SliceResult*)d_res, sc.cuts = d_res + sizeof(SliceResult) / 4;
+  {
+    ScopedKernel k(c, K_SLICE_REDUCE, (uint64_t)n * sizeof(EventRec) + (uint64_t)tiles * 4);
+    launch_slice_reduce(s, a);
+  }
+  {
+    ScopedKernel k(c, K_SLICE_SCAN, (uint64_t)tiles * 8);
+    launch_slice_scan(s, a);
+  }
+  {
+    ScopedKernel k(c, K_SLICE_CUTS, (uint64_t)n * sizeof(EventRec) + (uint64_t)tiles * 4);
+    launch_slice_cuts(s, a);
+  }
+  HIPCHK(c, hipMemcpyAsync(h_res, d_res, sizeof(SliceResult) + kSliceInlineCuts * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  if (c->prof_on) resolve_profile(c);
+  const SliceResult r = *(const SliceResult*)h_res;
+  if (r.overflow) {
+    const SliceBound last = slice_bound(c, cam, st.m + n_bounds - 1);
+    if (last.sec >> 32)
+      return fail(c, ESVIO_FE_EINVAL, "slice_events: an event lies at or beyond a boundary whose seconds leave 32 bits; the camera's state is as it was");
+    return fail(c, ESVIO_FE_EINVAL, "slice_events: an event lies at or beyond E_%llu: a call closes at most %u windows; the camera's state is as it was",
+                (unsigned long long)(st.m + n_bounds - 1), kSliceMaxWindows);
+  }
+  if (r.closed > cuts_cap) {
+    if (info) info->closed = r.closed;
+    return fail(c, ESVIO_FE_EINVAL, "slice_events: the call closes %u windows, cuts has room for %zu; the camera's state is as it was", r.closed, cuts_cap);
+  }
+  if (r.closed > kSliceInlineCuts) {
+    HIPCHK(c, hipMemcpyAsync(h_res + sizeof(SliceResult) / 4 + kSliceInlineCuts, d_res + sizeof(SliceResult) / 4 + kSliceInlineCuts,
+                             (size_t)(r.closed - kSliceInlineCuts) * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+  }
+  for (uint32_t j = 0; j < r.closed; j++) cuts[j] = h_res[sizeof(SliceResult) / 4 + j];
+  // the call succeeded: the camera's state is what it computed
+  st.open = r.closed ? n - r.first_of_last : cur.open + n;
+  st.m += r.closed;
+  if (info) {
+    info->closed = r.closed, info->first_window = cur.m, info->count = st.m, info->open_events = st.open;
+    if (r.closed) {
+      const SliceBound f = slice_bound(c, cam, cur.m), l = slice_bound(c, cam, st.m - 1);
+      info->first_sec = (uint32_t)f.sec, info->first_nsec = f.nsec, info->last_sec = (uint32_t)l.sec, info->last_nsec = l.nsec;
+    }
+  }
+  sl.st[cam] = st;
+  return 0;
+}
+}  // namespace
+
+int esvio_fe_slice_flush(esvio_fe_handle c, int cam, esvio_fe_slice_info* info) {
+  if (!c) return ESVIO_FE_EINVAL;
+  if (int rc = slice_cam_check(c, "slice_flush", cam)) return rc;
+  if (int rc = slice_feed_check(c, "slice_flush")) return rc;
+  SliceState& st = c->slice.st[cam];
+  slice_info_state(info, st);
+  if (!st.seen) return 0;
+  HIPCHK(c, hipSetDevice(c->dev));
+  uint32_t n_bounds = 0;
+  if (int rc = slice_table(c, cam, st, &n_bounds, cur_stream(c))) return rc;
+  HIPCHK(c, hipStreamSynchronize(cur_stream(c)));  // (a refilled table leaves its pinned copy before the next call can rewrite it)
+  const SliceBound e = slice_bound(c, cam, st.m);
+  if (e.sec >> 32) return fail(c, ESVIO_FE_EINVAL, "slice_flush: the open window's boundary leaves 32 bits of seconds");
+  st.m += 1, st.open = 0;
+  if (info) {
+    info->closed = 1, info->count = st.m, info->open_events = 0;
+    info->first_sec = info->last_sec = (uint32_t)e.sec, info->first_nsec = info->last_nsec = e.nsec;
+  }
+  return 0;
+}
+
+int esvio_fe_slice_reset(esvio_fe_handle c) {
+  if (!c) return ESVIO_FE_EINVAL;
+  if (int rc = slice_feed_check(c, "slice_reset")) return rc;
+  c->slice.st[0] = c->slice.st[1] = SliceState();
+  return 0;
+}
+
+// ---- the feed: chunks in, time-aligned windows tracked where they lie (include/esvio_fe.h)
+namespace {
+using FeedCam = esvio_fe_ctx::Feed::Cam;
+constexpr size_t kFeedMinRecords = 4096;  // a camera's first buffer
+
+// No records, no windows; the buffers stay.  The append position falls back to the front of the current buffer, where a
+// returned track call may still be reading a window (include/esvio_fe.h: buffer lifetime): unless every stream is known
+// to be idle, the next append waits for what that call left on the side streams first (feed_room).
+void feed_empty(esvio_fe_ctx* c, bool streams_idle) {
+  esvio_fe_ctx::Feed& f = c->feed;
+  for (esvio_fe_ctx::Feed::Cam& fc : f.cam) {
+    fc.pos0 = fc.len = fc.open_begin = 0;
+    fc.win.clear();
+    if (streams_idle) fc.read_rec[0] = fc.read_rec[1] = false;
+    fc.rewound = fc.read_rec[fc.cur];
+  }
+  f.origin_known = f.prm.has_origin != 0;
+}
+int feed_gate(esvio_fe_ctx* c, const char* who) {
+  if (!c->feed.open) return fail(c, ESVIO_FE_EINVAL, "%s: no feed is open on this handle (esvio_fe_feed_open)", who);
+  if (!c->announced.empty() || !c->inflight.empty())
+    return fail(c, ESVIO_FE_EINVAL, "%s: batches are announced on this handle", who);
+  return 0;
+}
+// Room for `need` more records behind the camera's records, *dst = the append position.  When they do not fit, the
+// untracked tail moves to the front of the other buffer (grown first if it is too small: that frees it, which waits
+// for the device) on the main stream, behind whatever the last track call that read that buffer left on the side streams.
+// the main stream behind whatever the last track call that read camera buffer b left on the side streams
+int feed_wait_readers(esvio_fe_ctx* c, FeedCam& fc, int b) {
+  if (fc.read_rec[b]) {
+    hipStream_t side[4] = {c->stream2, c->stream3, c->stream4, c->stream6};
+    for (int k = 0; k < 4; k++)
+      if (side[k]) HIPCHK(c, hipStreamWaitEvent(cur_stream(c), fc.read_ev[b][k], 0));
+  }
+  fc.read_rec[b] = false;
+  return 0;
+}
+int feed_room(esvio_fe_ctx* c, int cam, size_t need, EventRec** dst) {
+  FeedCam& fc = c->feed.cam[cam];
+  if (!fc.buf[fc.cur])
+    if (int rc = fc.buf[fc.cur].alloc(c, std::max(need + need / 4, kFeedMinRecords))) return rc;
+  if (fc.len + need > fc.buf[fc.cur].cap) {
+    const uint64_t keep_from = fc.win.empty() ? fc.open_begin : fc.win.front().begin;
+    const size_t tail = (size_t)(fc.pos0 + fc.len - keep_from), want = tail + need;
+    const int to = fc.cur ^ 1;
+    hipStream_t s = cur_stream(c);
+    if (want > fc.buf[to].cap) {
+      if (int rc = fc.buf[to].alloc(c, std::max(want + want / 4, kFeedMinRecords))) return rc;
+      fc.read_rec[to] = false;
+    } else if (int rc = feed_wait_readers(c, fc, to)) {
+      return rc;
+    }
+    fc.rewound = false;  // (the buffer left behind keeps its read_rec: coming back to it waits)
+    if (tail)
+      HIPCHK(c, hipMemcpyAsync(fc.buf[to], fc.buf[fc.cur] + (size_t)(keep_from - fc.pos0), tail * sizeof(EventRec), hipMemcpyDeviceToDevice, s));
+    fc.cur = to, fc.pos0 = keep_from, fc.len = tail;
+  }
+  if (fc.rewound) {  // the first append behind a close / open: the front of this buffer may still be read
+    if (int rc = feed_wait_readers(c, fc, fc.cur)) return rc;
+    fc.rewound = false;
+  }
+  *dst = fc.buf[fc.cur] + (size_t)fc.len;
+  return 0;
+}
+void feed_info_fill(esvio_fe_feed_info* info, const FeedCam& fc, uint64_t appended, uint64_t rejected, uint64_t bad, uint64_t closed) {
+  if (!info) return;
+  info->appended = appended, info->rejected = rejected, info->bad = bad, info->closed = closed, info->queued = fc.win.size();
+}
+
+enum FeedKind { FEED_EVENTS, FEED_FIELDS, FEED_RAW };
+struct FeedSrc {
+  FeedKind kind;
+  const esvio_fe_event* ev = nullptr;
+  const esvio_fe_event_fields* fields = nullptr;
+  size_t n = 0;  // events or fields
+  int format = 0;
+  const void* words = nullptr;
+  size_t n_bytes = 0;
+  int64_t t_offset_us = 0;
+  int space = 0;
+};
+
+int feed_push(esvio_fe_ctx* c, const char* who, int cam, const FeedSrc& src, esvio_fe_feed_info* info) {
+  if (info) *info = esvio_fe_feed_info{};
+  if (int rc = slice_cam_check(c, who, cam)) return rc;
+  if (int rc = feed_gate(c, who)) return rc;
+  esvio_fe_ctx::Feed& f = c->feed;
+  FeedCam& fc = f.cam[cam];
+  feed_info_fill(info, fc, 0, 0, 0, 0);
+  if (src.space != ESVIO_FE_HOST && src.space != ESVIO_FE_DEVICE) return fail(c, ESVIO_FE_EINVAL, "%s: bad memory space", who);
+  if (src.kind == FEED_EVENTS) {
+    if (src.n && !src.ev) return fail(c, ESVIO_FE_EINVAL, "%s: ev is null", who);
+    if (src.space == ESVIO_FE_DEVICE && ((uintptr_t)src.ev & 15) != 0) return fail(c, ESVIO_FE_EINVAL, "%s: device events must be 16-byte aligned", who);
+  } else if (src.kind == FEED_FIELDS) {
+    if (int rc = fields_check(c, src.fields, src.n, who)) return rc;
+  } else if (int rc = raw_args_check(c, who, src.format, src.words, src.n_bytes, src.space, src.t_offset_us)) {
+    return rc;
+  }
+  if (src.kind != FEED_RAW && src.n >= (1ull << 30)) return fail(c, ESVIO_FE_EINVAL, "%s: chunk too large", who);
+  if (src.kind == FEED_RAW ? !src.n_bytes : !src.n) return 0;
+  if (cam == 1 && !f.origin_known)
+    return fail(c, ESVIO_FE_EINVAL, "%s: the origin is the first left record, and no left record has been appended yet", who);
+  HIPCHK(c, hipSetDevice(c->dev));
+  hipStream_t s = cur_stream(c);
+  const esvio_fe_filter_params* flt = f.has_filter ? &f.filter : nullptr;
+  EventRec* dst = nullptr;
+  uint64_t n_new = 0, rejected = 0, bad = 0;
+  // what the filter reads, when the records have to be made first (raw words)
+  const esvio_fe_event* flt_ev = src.ev;
+  const esvio_fe_event_fields* flt_fields = src.fields;
+  size_t flt_n = src.n;
+  int flt_space = src.space;
+  RawResult raw_res[2] = {};
+  if (src.kind == FEED_RAW) {
+    const size_t wb = src.format == ESVIO_FE_RAW_EVT3 ? 2 : 4;
+    RawJob job[2];
+    job[0].words = src.words, job[0].n_bytes = src.n_bytes;
+    // one record per word to begin with; when the reduce pass reports more, room is made and the emit launch repeated
+    auto place = [&](size_t want) -> int {
+      if (flt) {
+        if (int rc = raw_ensure(c, cam, src.n_bytes, false, std::max<size_t>(want, 1))) return rc;
+        job[0].d_dst = c->rawdec.dec[cam], job[0].cap = c->rawdec.dec[cam].cap;
+      } else {
+        if (int rc = feed_room(c, cam, want, &dst)) return rc;
+        job[0].d_dst = dst, job[0].cap = fc.buf[fc.cur].cap - (size_t)fc.len;
+      }
+      return 0;
+    };
+    if (int rc = place(src.n_bytes / wb)) return rc;
+    const int cam_of[2] = {cam, cam};
+    RawArgs a;
+    if (int rc = raw_enqueue(c, src.format, src.space, src.t_offset_us, job, cam_of, &a, raw_res)) return rc;
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (!raw_res[0].bad && raw_res[0].events > job[0].cap) {
+      if (int rc = place(raw_res[0].events)) return rc;
+      if (int rc = raw_emit_again(c, &a, job, raw_res)) return rc;
+      HIPCHK(c, hipStreamSynchronize(s));
+    }
+    if (c->prof_on) resolve_profile(c);
+    if (raw_res[0].bad) {
+      feed_info_fill(info, fc, 0, 0, raw_res[0].bad, 0);
+      return fail(c, ESVIO_FE_EINVAL, "%s: %llu of %u events have a stamp outside [0, 2^32 s); nothing was appended, the camera's decoder state is as it was",
+                  who, raw_res[0].bad, raw_res[0].events);
+    }
+    n_new = raw_res[0].events;
+    flt_ev = (const esvio_fe_event*)job[0].d_dst, flt_fields = nullptr, flt_n = raw_res[0].events, flt_space = ESVIO_FE_DEVICE;
+  }
+  if (flt) {
+    n_new = 0;
+    if (flt_n) {
+      if (int rc = feed_room(c, cam, flt_n, &dst)) return rc;
+      if (int rc = baf_ensure(c, flt_n, flt_ev && flt_space == ESVIO_FE_HOST, false, flt_fields != nullptr)) return rc;
+      BafResult r{};
+      if (int rc = baf_enqueue(c, cam, flt_ev, flt_fields, flt_n, flt_space, *flt, dst, who)) return rc;
+      if (int rc = baf_fetch(c, cam, &r, nullptr, 0)) return rc;
+      HIPCHK(c, hipStreamSynchronize(s));
+      if (c->prof_on) resolve_profile(c);
+      if (int rc = baf_result_check(c, r, who)) return rc;
+      if (r.n_bad) {
+        feed_info_fill(info, fc, 0, 0, r.n_bad, 0);
+        return fail(c, ESVIO_FE_EINVAL, "%s: %llu of %zu events %s; nothing was appended, the camera's plane is as it was", who, r.n_bad, flt_n, kBadStampText);
+      }
+      n_new = r.n_kept, rejected = r.n_rejected;
+    }
+  } else if (src.kind == FEED_EVENTS) {
+    if (int rc = feed_room(c, cam, src.n, &dst)) return rc;
+    HIPCHK(c, hipMemcpyAsync(dst, src.ev, src.n * sizeof(EventRec), src.space == ESVIO_FE_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
+    n_new = src.n;
+  } else if (src.kind == FEED_FIELDS) {
+    if (int rc = feed_room(c, cam, src.n, &dst)) return rc;
+    if (int rc = convert_begin(c)) return rc;
+    if (int rc = convert_enqueue(c, *src.fields, src.n, src.space, dst, 0)) return rc;
+    unsigned long long nb = 0;
+    if (int rc = convert_end(c, &nb)) return rc;
+    if (c->prof_on) resolve_profile(c);
+    if (nb) {
+      feed_info_fill(info, fc, 0, 0, nb, 0);
+      return fail(c, ESVIO_FE_EINVAL, "%s: %llu of %zu events %s; nothing was appended", who, nb, src.n, kBadStampText);
+    }
+    n_new = src.n;
+  }
+  // the slicer over the appended records; the windows it closes are queued
+  esvio_fe_slice_info si{};
+  uint64_t first_window = c->slice.st[cam].m;
+  if (n_new) {
+    esvio_fe_slice_params prm = f.prm;
+    if (cam == 1 && !prm.has_origin) {  // the first left record's stamp, as the left camera's slicer took it
+      prm.has_origin = 1;
+      prm.origin = esvio_fe_event{};
+      prm.origin.sec = c->slice.st[0].o_sec, prm.origin.nsec = c->slice.st[0].o_nsec;
+    }
+    f.cuts.resize(kSliceMaxWindows);
+    if (int rc = slice_events_impl(c, cam, (const esvio_fe_event*)dst, (size_t)n_new, ESVIO_FE_DEVICE, &prm, f.cuts.data(), f.cuts.size(), &si))
+      return rc;  // (nothing was appended: len has not moved; the decoder's state is not taken over)
+    first_window = si.first_window;
+  }
+  if (src.kind == FEED_RAW) raw_commit(c, cam, raw_res[0]);
+  const uint64_t at = fc.pos0 + fc.len;
+  for (uint64_t j = 0; j < si.closed; j++) {
+    const SliceBound e = slice_bound(c, cam, first_window + j);
+    fc.win.push_back(esvio_fe_ctx::Feed::Window{first_window + j, fc.open_begin, at + f.cuts[(size_t)j], (uint32_t)e.sec, e.nsec});
+    fc.open_begin = at + f.cuts[(size_t)j];
+  }
+  fc.len += n_new;
+  if (cam == 0 && n_new) f.origin_known = true;
+  feed_info_fill(info, fc, n_new, rejected, bad, si.closed);
+  return 0;
+}
+}  // namespace
+
+int esvio_fe_feed_open(esvio_fe_handle c, const esvio_fe_slice_params* prm, const esvio_fe_filter_params* filter) {
+  if (!c) return ESVIO_FE_EINVAL;
+  if (c->feed.open) return fail(c, ESVIO_FE_EINVAL, "feed_open: a feed is open on this handle (esvio_fe_feed_close first)");
+  if (!prm) return fail(c, ESVIO_FE_EINVAL, "feed_open: prm is null");
+  if (prm->reserved != 0) return fail(c, ESVIO_FE_EINVAL, "feed_open: reserved must be 0");
+  if (!(prm->frequency >= 1e-3 && prm->frequency <= 1e6))
+    return fail(c, ESVIO_FE_EINVAL, "feed_open: frequency must be in [1e-3, 1e6] (got %g)", prm->frequency);
+  if (filter)
+    if (int rc = baf_prm_check(c, filter, "feed_open")) return rc;
+  if (!c->announced.empty() || !c->inflight.empty()) return fail(c, ESVIO_FE_EINVAL, "feed_open: batches are announced on this handle");
+  esvio_fe_ctx::Feed& f = c->feed;
+  f.prm = *prm;
+  f.prm.has_origin = prm->has_origin != 0;
+  f.has_filter = filter != nullptr;
+  if (filter) f.filter = *filter;
+  c->slice.st[0] = c->slice.st[1] = SliceState();
+  feed_empty(c, false);
+  f.open = true;
+  return 0;
+}
+
+int esvio_fe_feed_close(esvio_fe_handle c) {
+  if (!c) return ESVIO_FE_EINVAL;
+  if (!c->feed.open) return fail(c, ESVIO_FE_EINVAL, "feed_close: no feed is open on this handle");
+  c->feed.open = false;
+  feed_empty(c, false);
+  return 0;
+}
+
+int esvio_fe_feed_push_events(esvio_fe_handle c, int cam, const esvio_fe_event* ev, size_t n, int space, esvio_fe_feed_info* info) {
+  if (!c) return ESVIO_FE_EINVAL;
+  FeedSrc src{FEED_EVENTS};
+  src.ev = ev, src.n = n, src.space = space;
+  return feed_push(c, "feed_push_events", cam, src, info);
+}
+int esvio_fe_feed_push_fields(esvio_fe_handle c, int cam, const esvio_fe_event_fields* fields, size_t n, int space,
+                              esvio_fe_feed_info* info) {
+  if (!c) return ESVIO_FE_EINVAL;
+  FeedSrc src{FEED_FIELDS};
+  src.fields = fields, src.n = n, src.space = space;
+  return feed_push(c, "feed_push_fields", cam, src, info);
+}
+int esvio_fe_feed_push_raw(esvio_fe_handle c, int cam, int format, const void* words, size_t n_bytes, int space,
+                           int64_t t_offset_us, esvio_fe_feed_info* info) {
+  if (!c) return ESVIO_FE_EINVAL;
+  FeedSrc src{FEED_RAW};
+  src.format = format, src.words = words, src.n_bytes = n_bytes, src.t_offset_us = t_offset_us, src.space = space;
+  return feed_push(c, "feed_push_raw", cam, src, info);
+}
+
+int esvio_fe_feed_peek(esvio_fe_handle c, esvio_fe_feed_window* out) {
+  if (!c || !out) return ESVIO_FE_EINVAL;
+  *out = esvio_fe_feed_window{};
+  if (int rc = feed_gate(c, "feed_peek")) return rc;
+  const FeedCam &l = c->feed.cam[0], &r = c->feed.cam[1];
+  if (l.win.empty() || r.win.empty()) return 0;
+  const esvio_fe_ctx::Feed::Window &wl = l.win.front(), &wr = r.win.front();
+  out->ready = 1, out->index = wl.index, out->end_sec = wl.sec, out->end_nsec = wl.nsec;
+  out->count[0] = wl.end - wl.begin, out->count[1] = wr.end - wr.begin;
+  return 0;
+}
+
+int esvio_fe_feed_track(esvio_fe_handle c, int pub_this_frame, const esvio_fe_motion* motion, esvio_fe_tracks* out,
+                        esvio_fe_batch_info* info_out) {
+  if (!c) return ESVIO_FE_EINVAL;
+  esvio_fe_batch_info info{};
+  if (info_out) *info_out = info;
+  if (int rc = feed_gate(c, "feed_track")) return rc;
+  FeedCam* fc[2] = {&c->feed.cam[0], &c->feed.cam[1]};
+  if (fc[0]->win.empty() || fc[1]->win.empty()) return fail(c, ESVIO_FE_EINVAL, "feed_track: no window is closed in both cameras (esvio_fe_feed_peek)");
+  const esvio_fe_ctx::Feed::Window w[2] = {fc[0]->win.front(), fc[1]->win.front()};
+  if (w[0].index != w[1].index) return fail(c, ESVIO_FE_EINTERNAL, "feed_track: the cameras' windows do not pair");
+  const size_t n[2] = {(size_t)(w[0].end - w[0].begin), (size_t)(w[1].end - w[1].begin)};
+  if (n[0] + n[1] >= (1ull << 31)) return fail(c, ESVIO_FE_EINVAL, "feed_track: window too large");
+  fc[0]->win.pop_front(), fc[1]->win.pop_front();
+  info.kept[0] = n[0], info.kept[1] = n[1];
+  if (info_out) *info_out = info;
+  if (!n[0]) return 0;  // node:150: an empty left message is not tracked
+  HIPCHK(c, hipSetDevice(c->dev));
+  const EventRec* d[2];
+  for (int cam = 0; cam < 2; cam++) d[cam] = fc[cam]->buf[fc[cam]->cur] + (size_t)(w[cam].begin - fc[cam]->pos0);
+  EventRec last{};
+  HIPCHK(c, hipMemcpyAsync(&last, d[0] + (n[0] - 1), sizeof(EventRec), hipMemcpyDeviceToHost, cur_stream(c)));
+  HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  info.cur_time = (double)last.sec + 1e-9 * (double)last.nsec;
+  const int rc = track_event_impl(c, info.cur_time, (const esvio_fe_event*)d[0], n[0], (const esvio_fe_event*)(n[1] ? d[1] : nullptr), n[1],
+                                  ESVIO_FE_DEVICE, pub_this_frame != 0, motion);
+  // what this call left on the side streams reads the buffers the windows lie in
+  hipStream_t side[4] = {c->stream2, c->stream3, c->stream4, c->stream6};
+  for (int cam = 0; cam < 2; cam++)
+    for (int k = 0; k < 4; k++)
+      if (side[k]) {
+        Event& e = fc[cam]->read_ev[fc[cam]->cur][k];
+        if (!e) HIPCHK(c, e.create());
+        HIPCHK(c, hipEventRecord(e, side[k]));
+      }
+  fc[0]->read_rec[fc[0]->cur] = fc[1]->read_rec[fc[1]->cur] = true;
+  info.tracked = rc == 0;
+  if (info_out) *info_out = info;
+  if (rc) return rc;
+  return fill_tracks(c, out);
+}
+
 // ---- image front-end
 int esvio_fe_good_features_to_track(esvio_fe_handle c, const uint8_t* img, int max_corners,
                                     double quality, double min_distance, const uint8_t* mask,
@@ -2338,6 +2875,18 @@ int esvio_fe_reserve(esvio_fe_handle c, size_t max_left, size_t max_right, int h
     const size_t ev[2] = {max_left, max_right};
     for (int cam = 0; cam < 2; cam++)
       if (int rc = raw_ensure(c, cam, ev[cam] * 8, host_batches != 0, 0)) return rc;
+  }
+  // a handle with an open feed: per camera both buffers for 2 * max_events records (the one that holds records is left alone)
+  if (c->feed.open) {
+    const size_t ev[2] = {max_left, max_right};
+    for (int cam = 0; cam < 2; cam++) {
+      esvio_fe_ctx::Feed::Cam& fc = c->feed.cam[cam];
+      for (int b = 0; b < 2; b++)
+        if ((b != fc.cur || fc.len == 0) && fc.buf[b].cap < 2 * ev[cam]) {
+          if (int rc = fc.buf[b].alloc(c, 2 * ev[cam])) return rc;
+          fc.read_rec[b] = false;
+        }
+    }
   }
   if (host_batches) {
     if (int rc = ensure_event_capacity(c, n)) return rc;

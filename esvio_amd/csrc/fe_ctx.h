@@ -71,7 +71,7 @@ const char* const kKernelNames[K_COUNT] = {
     "k_scharr", "k_pad_scharr", "k_lk_f32", "k_lk", "k_arc_map", "k_arc_ev", "k_dedup", "k_compact", "k_select_mw",
     "k_select", "k_select_gbm", "k_fast_score", "k_fast_collect", "k_events_from_fields", "k_baf_heads", "k_baf_filter",
     "k_baf_count", "k_baf_scan", "k_baf_emit", "k_baf_keys_fields", "k_baf_emit_fields", "k_raw_reduce", "k_raw_scan",
-    "k_raw_emit"};
+    "k_raw_emit", "k_slice_reduce", "k_slice_scan", "k_slice_cuts"};
 
 // The host phases of one trackEvent call, in the order of esvio_fe_latency_call::phase_ms; kPhaseNames is what
 // esvio_fe_latency_phase_name returns and what the ESVIO_FE_TRACE summary prints.  The PH_PUB_* phases are parts of
@@ -519,6 +519,60 @@ struct esvio_fe_ctx {
     bool used = false;     // esvio_fe_reserve grows the scratch of a handle that has decoded before
     int pinned_copy = -1;  // page-locked sources: -1 = in place up to kRawPinnedInPlaceBytes (fe_api.cpp); ESVIO_FE_RAW_PINNED_COPY=1 / 0: always copied first / always in place
   } rawdec;
+
+  // ---- esvio_fe_slice_events: a record stream cut into fixed-rate windows (include/esvio_fe.h has the rule,
+  // fe_kernels.h the chain).  st: each camera's state, kept on the HOST like the decoder's: the device works on counts
+  // relative to it and the host takes a call's result over only once the call is known to succeed.  E: the boundaries
+  // E_{tb} .. of the camera's chain as the host computed them (a cache: tagged with the frequency and origin it was made
+  // for), bounds their toSec() on the device.  Everything is allocated on first use and is the stage's own (main stream
+  // only): src, the copy of a host source; tmax, the tiles' maxima; res, per camera the result block with the cut
+  // entries behind it; h_res, where they arrive.
+  struct Slice {
+    struct State {
+      bool seen = false;
+      int32_t has_origin = 0;
+      double frequency = 0;
+      uint32_t o_sec = 0, o_nsec = 0;  // the origin record's stamp
+      uint64_t m = 0, open = 0;        // windows closed so far; events in the open one
+    } st[2];
+    struct Bound {
+      uint64_t sec;  // (may leave 32 bits: such an entry ends the table)
+      uint32_t nsec;
+    };
+    std::vector<Bound> E[2];
+    uint64_t tb[2] = {0, 0};
+    State tab_for[2];  // frequency / origin the table was computed for (seen == false: none)
+    DevBuf<double> bounds[2];
+    PinBuf<double> h_bounds[2];
+    DevBuf<EventRec> src[2];
+    DevBuf<uint32_t> tmax[2];
+    DevBuf<uint32_t> res;   // [2][kSliceResWords]
+    PinBuf<uint32_t> h_res; // [2][kSliceResWords]
+  } slice;
+
+  // ---- esvio_fe_feed_*: chunks in, windows tracked where they lie (include/esvio_fe.h).  Per camera two buffers;
+  // `cur` holds records [pos0, pos0 + len) of the camera's stream (positions count the records appended since the feed
+  // was opened or emptied), of which everything from the oldest untracked window's start on is still needed.  read_ev:
+  // per buffer the events recorded on the side streams when the last track call that read it returned.
+  struct Feed {
+    bool open = false, has_filter = false, origin_known = false;
+    esvio_fe_slice_params prm{};
+    esvio_fe_filter_params filter{};
+    struct Window {
+      uint64_t index, begin, end;  // [begin, end): positions in the camera's stream
+      uint32_t sec, nsec;          // E_index
+    };
+    struct Cam {
+      DevBuf<EventRec> buf[2];
+      Event read_ev[2][4];
+      bool read_rec[2] = {false, false};
+      bool rewound = false;  // emptied without idle streams: the next append waits for read_ev[cur] first
+      int cur = 0;
+      uint64_t pos0 = 0, len = 0, open_begin = 0;
+      std::deque<Window> win;
+    } cam[2];
+    std::vector<uint64_t> cuts;
+  } feed;
 };
 
 namespace esvio {

@@ -83,12 +83,15 @@ enum KernelId {
   K_RAW_REDUCE,      // esvio_fe_decode_raw / esvio_fe_track_raw: the decode chain runs in front of the track call
   K_RAW_SCAN,
   K_RAW_EMIT,
+  K_SLICE_REDUCE,    // esvio_fe_slice_events: cutting a record stream into fixed-rate windows
+  K_SLICE_SCAN,
+  K_SLICE_CUTS,
   K_COUNT
 };
 // esvio_fe_kernel_count(): the kernels of the tracker's entry points, the table bench.py and the recorded launch traces
 // list.  The ids from here on belong to stages off every track path and are listed by esvio_fe_stage_kernel_count().
 constexpr int kTrackKernels = K_BAF_HEADS;
-static_assert(K_EVENTS_FROM_FIELDS + 1 == kTrackKernels && K_RAW_EMIT + 1 == K_COUNT,
+static_assert(K_EVENTS_FROM_FIELDS + 1 == kTrackKernels && K_SLICE_CUTS + 1 == K_COUNT,
               "a track-path kernel goes in front of K_BAF_HEADS (and into this assertion), a stage's kernel behind it");
 
 // ---- SAE update -------------------------------------------------------------------------
@@ -631,6 +634,41 @@ struct RawArgs {
 void launch_raw_reduce(hipStream_t s, const RawArgs& a);
 void launch_raw_scan(hipStream_t s, const RawArgs& a);
 void launch_raw_emit(hipStream_t s, const RawArgs& a);
+
+// ---- stream slicing: a record stream cut into fixed-rate windows (esvio_fe_slice_events) ----
+// include/esvio_fe.h holds the rule.  An event's window is m_i = max(m_{i-1}, c_i), c_i = the boundaries at or below its
+// stamp: a prefix MAXIMUM, associative and commutative, so a tile of events is summarised by one number and the chain
+// is the raw chain's: reduce (the tile's maximum of c) -> scan (one workgroup per camera: the tiles' exclusive prefix
+// maxima behind the carried count, the totals and the state after the call) -> cuts (re-reads the tile, scans inside it
+// from the tile's prefix; the lane where m rises writes the cut entries it owns).  The kernels take two cameras' tiles
+// in one grid, as the raw chain's do; the entry points there are so far run ONE camera per chain (a slice call and a
+// feed push are per camera): cam[1].tiles is 0 and the scan is one workgroup.  No launch waits on the device for another workgroup.  Every count is RELATIVE to the windows closed before the call.
+constexpr uint32_t kSliceTile = 1024;        // events per workgroup: 256 lanes x 4 consecutive records
+constexpr uint32_t kSliceMaxWindows = 4096;  // ESVIO_FE_SLICE_MAX_WINDOWS
+struct SliceResult {  // written by k_slice_scan (first_of_last: k_slice_cuts); one per camera, the cuts behind it
+  uint32_t closed;         // windows the call closes (the maximum of c over its events)
+  uint32_t overflow;       // an event lies at or beyond the last boundary of the call's range: nothing else is valid
+  uint32_t first_of_last;  // index of the first event of the window left open (untouched when closed == 0)
+  uint32_t reserved;
+};
+static_assert(sizeof(SliceResult) == 16, "SliceResult layout");
+constexpr uint32_t kSliceResWords = sizeof(SliceResult) / 4 + kSliceMaxWindows;  // a camera's result block and its cuts
+struct SliceCam {
+  const EventRec* ev;   // [n] device memory
+  uint32_t n;
+  uint32_t tiles;       // ceil(n / kSliceTile); 0: the camera takes no part
+  const double* bounds; // [n_bounds] toSec(E_k) of the windows open or ahead at the call's start, ascending
+  uint32_t n_bounds;    // <= kSliceMaxWindows + 1; c == n_bounds is the overflow
+  uint32_t* tmax;       // [tiles] reduce: the tiles' maxima; scan: their exclusive prefix maxima
+  SliceResult* res;
+  uint32_t* cuts;       // [kSliceMaxWindows] entry j: the first event that does not belong to the j-th window closed
+};
+struct SliceArgs {
+  SliceCam cam[2];  // the grid's blocks: cam[0].tiles, then cam[1].tiles
+};
+void launch_slice_reduce(hipStream_t s, const SliceArgs& a);
+void launch_slice_scan(hipStream_t s, const SliceArgs& a);
+void launch_slice_cuts(hipStream_t s, const SliceArgs& a);
 
 struct SelectArgs {
   const uint32_t* comp_xy;   // compacted candidates in stream order

@@ -4517,6 +4517,130 @@ void launch_raw_emit(hipStream_t s, const RawArgs& a) {
     launch_k(k_raw_emit<kRawEvt2>, dim3(raw_grid(a)), dim3(256), 0, s, a);
 }
 
+// ============================================================================ stream slicing
+// A record stream cut into fixed-rate windows (fe_kernels.h has the chain, include/esvio_fe.h the rule).
+//   slice_count     the boundaries at or below a stamp: the upper bound in the ascending table, by bisection
+//   slice_lane      the lane's four consecutive records' counts (0 behind the stream's end) and their maximum
+//   k_slice_reduce  per tile: the maximum of the counts
+//   k_slice_scan    per camera one workgroup: the tiles' exclusive prefix maxima, the totals
+//   k_slice_cuts    per tile: the prefix maximum inside the tile from the tile's prefix; where it rises, the cut entries
+__device__ __forceinline__ uint32_t slice_count(const double* __restrict__ b, uint32_t nb, double ts) {
+  uint32_t lo = 0, hi = nb;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (b[mid] <= ts)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  return lo;
+}
+__device__ __forceinline__ const SliceCam& slice_block_cam(const SliceArgs& a, uint32_t* tile) {
+  const uint32_t b = blockIdx.x;
+  *tile = b < a.cam[0].tiles ? b : b - a.cam[0].tiles;
+  return b < a.cam[0].tiles ? a.cam[0] : a.cam[1];
+}
+__device__ __forceinline__ uint32_t slice_lane(const SliceCam& c, uint32_t tile, uint32_t cnt[4]) {
+  const uint32_t first = tile * kSliceTile + threadIdx.x * 4u;
+  const uint4* ev = (const uint4*)c.ev;
+  uint32_t mx = 0;
+  // (most of a tile lies in one window: the neighbours of the last answer are looked at before the table is bisected)
+  uint32_t guess = 0;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    cnt[k] = 0;
+    if (first + k < c.n) {
+      const uint4 e = ev[first + k];
+      const double ts = ev_time(e.y, e.z);
+      const bool lo_ok = guess == 0 || c.bounds[guess - 1] <= ts, hi_ok = guess == c.n_bounds || !(c.bounds[guess] <= ts);
+      cnt[k] = lo_ok && hi_ok ? guess : slice_count(c.bounds, c.n_bounds, ts);
+      guess = cnt[k];
+      mx = max(mx, cnt[k]);
+    }
+  }
+  return mx;
+}
+// inclusive prefix maximum over the wave, lane 0 first (every lane of the wave calls it)
+__device__ __forceinline__ uint32_t slice_wave_scan(uint32_t v) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t u = __shfl_up(v, o);
+    if (lane_id() >= o) v = max(v, u);
+  }
+  return v;
+}
+
+__global__ __launch_bounds__(256) void k_slice_reduce(SliceArgs a) {
+  __shared__ uint32_t part[4];
+  uint32_t tile, cnt[4];
+  const SliceCam& c = slice_block_cam(a, &tile);
+  const uint32_t incl = slice_wave_scan(slice_lane(c, tile, cnt));
+  if (lane_id() == 63) part[threadIdx.x >> 6] = incl;
+  __syncthreads();
+  if (threadIdx.x == 0) c.tmax[tile] = max(max(part[0], part[1]), max(part[2], part[3]));
+}
+
+__global__ __launch_bounds__(256) void k_slice_scan(SliceArgs a) {
+  __shared__ uint32_t part[4];
+  const SliceCam& c = a.cam[blockIdx.x];
+  if (!c.tiles) return;
+  const uint32_t per = (c.tiles + 255u) / 256u;
+  const uint32_t lo = min(threadIdx.x * per, c.tiles), hi = min(lo + per, c.tiles);
+  uint32_t mine = 0;
+  for (uint32_t j = lo; j < hi; j++) mine = max(mine, c.tmax[j]);
+  const uint32_t incl = slice_wave_scan(mine);
+  if (lane_id() == 63) part[threadIdx.x >> 6] = incl;
+  __syncthreads();
+  uint32_t run = 0;  // (relative to the carried count: nothing closed yet)
+  for (int wv = 0; wv < (int)(threadIdx.x >> 6); wv++) run = max(run, part[wv]);
+  const uint32_t up = __shfl_up(incl, 1);
+  if (lane_id() > 0) run = max(run, up);
+  for (uint32_t j = lo; j < hi; j++) {
+    const uint32_t t = c.tmax[j];
+    c.tmax[j] = run;
+    run = max(run, t);
+  }
+  if (threadIdx.x == 255) {  // (the chunks behind the last tile are empty: this lane's run is the whole call)
+    c.res->closed = run;
+    c.res->overflow = run >= c.n_bounds ? 1u : 0u;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_slice_cuts(SliceArgs a) {
+  __shared__ uint32_t part[4];
+  uint32_t tile, cnt[4];
+  const SliceCam& c = slice_block_cam(a, &tile);
+  const uint32_t incl = slice_wave_scan(slice_lane(c, tile, cnt));
+  if (lane_id() == 63) part[threadIdx.x >> 6] = incl;
+  const uint32_t up = __shfl_up(incl, 1);
+  __syncthreads();
+  if (c.res->overflow) return;  // (the whole camera: the call fails, its cuts are never read)
+  uint32_t run = c.tmax[tile];  // the tile's prefix: every tile in front of this one
+  for (int wv = 0; wv < (int)(threadIdx.x >> 6); wv++) run = max(run, part[wv]);
+  if (lane_id() > 0) run = max(run, up);
+  const uint32_t total = c.res->closed, first = tile * kSliceTile + threadIdx.x * 4u;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    if (first + k >= c.n || cnt[k] <= run) continue;
+    // m rises here: this event is the first that belongs to none of the windows run .. cnt[k] - 1
+    const uint32_t to = min(cnt[k], kSliceMaxWindows);
+    for (uint32_t j = run; j < to; j++) c.cuts[j] = first + k;
+    run = cnt[k];
+    if (run == total) c.res->first_of_last = first + k;
+  }
+}
+
+static uint32_t slice_grid(const SliceArgs& a) { return a.cam[0].tiles + a.cam[1].tiles; }
+void launch_slice_reduce(hipStream_t s, const SliceArgs& a) {
+  if (slice_grid(a)) launch_k(k_slice_reduce, dim3(slice_grid(a)), dim3(256), 0, s, a);
+}
+void launch_slice_scan(hipStream_t s, const SliceArgs& a) {
+  if (slice_grid(a)) launch_k(k_slice_scan, dim3(a.cam[1].tiles ? 2 : 1), dim3(256), 0, s, a);  // (cam[0] alone: one workgroup)
+}
+void launch_slice_cuts(hipStream_t s, const SliceArgs& a) {
+  if (slice_grid(a)) launch_k(k_slice_cuts, dim3(slice_grid(a)), dim3(256), 0, s, a);
+}
+
 // ============================================================================ greedy selection
 // Event_FeaturesToTrack (feature_tracker.cpp:13-38): candidates in stream order; accept iff the
 // pixel is not blocked; stamp cv::circle(r = MIN_DIST, filled) [OpenCV midpoint disc]; stop at

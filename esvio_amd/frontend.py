@@ -109,6 +109,43 @@ class RawInfo(C.Structure):
 RAW_EVT2, RAW_EVT3 = 2, 3  # esvio_fe_decode_raw's formats
 
 
+class EventRecord(C.Structure):
+    """esvio_fe_event"""
+    _fields_ = [("x", C.c_uint16), ("y", C.c_uint16), ("sec", C.c_uint32), ("nsec", C.c_uint32), ("polarity", C.c_uint8),
+                ("_pad", C.c_uint8 * 3)]
+
+
+class SliceParams(C.Structure):
+    """esvio_fe_slice_params (include/esvio_fe.h has the rule): origin None: the camera's first event; else (sec, nsec)"""
+    _fields_ = [("frequency", C.c_double), ("origin", EventRecord), ("has_origin", C.c_int32), ("reserved", C.c_int32)]
+
+    def __init__(self, frequency=30.0, origin=None):
+        super().__init__(float(frequency))
+        if origin is not None:
+            self.origin.sec, self.origin.nsec, self.has_origin = int(origin[0]), int(origin[1]), 1
+
+
+class SliceInfo(C.Structure):
+    """esvio_fe_slice_info"""
+    _fields_ = [("closed", C.c_uint64), ("first_window", C.c_uint64), ("count", C.c_uint64), ("open_events", C.c_uint64),
+                ("first_sec", C.c_uint32), ("first_nsec", C.c_uint32), ("last_sec", C.c_uint32), ("last_nsec", C.c_uint32)]
+
+
+SLICE_MAX_WINDOWS = 4096  # ESVIO_FE_SLICE_MAX_WINDOWS
+
+
+class FeedInfo(C.Structure):
+    """esvio_fe_feed_info"""
+    _fields_ = [("appended", C.c_uint64), ("rejected", C.c_uint64), ("bad", C.c_uint64), ("closed", C.c_uint64),
+                ("queued", C.c_uint64)]
+
+
+class FeedWindow(C.Structure):
+    """esvio_fe_feed_window"""
+    _fields_ = [("ready", C.c_int32), ("reserved", C.c_int32), ("index", C.c_uint64), ("end_sec", C.c_uint32),
+                ("end_nsec", C.c_uint32), ("count", C.c_uint64 * 2)]
+
+
 class Tracks(C.Structure):
     _fields_ = [
         ("n_left", C.c_int32), ("n_right", C.c_int32),
@@ -127,6 +164,8 @@ ABI_SYMBOLS = [
     "esvio_fe_convert_events", "esvio_fe_create", "esvio_fe_decode_raw", "esvio_fe_decode_reset",
     "esvio_fe_create_sae", "esvio_fe_create_sae_stereo", "esvio_fe_create_sae_stereo_mc", "esvio_fe_destroy",
     "esvio_fe_exchange_begin", "esvio_fe_exchange_end", "esvio_fe_exchange_tracks", "esvio_fe_export_image",
+    "esvio_fe_feed_close", "esvio_fe_feed_open", "esvio_fe_feed_peek", "esvio_fe_feed_push_events", "esvio_fe_feed_push_fields",
+    "esvio_fe_feed_push_raw", "esvio_fe_feed_track",
     "esvio_fe_fast_corners", "esvio_fe_filter_batch", "esvio_fe_filter_events", "esvio_fe_filter_reset", "esvio_fe_features_to_track", "esvio_fe_features_to_track_fast", "esvio_fe_find_fundamental_mat", "esvio_fe_finish", "esvio_fe_get_sae",
     "esvio_fe_get_time_surface", "esvio_fe_good_features_to_track", "esvio_fe_import_image", "esvio_fe_is_corner",
     "esvio_fe_last_error", "esvio_fe_mem_alloc", "esvio_fe_mem_free", "esvio_fe_mem_upload",
@@ -134,7 +173,8 @@ ABI_SYMBOLS = [
     "esvio_fe_sae_plane_doubles", "esvio_fe_sae_slice_apply", "esvio_fe_sae_slice_commit",
     "esvio_fe_sae_slice_last", "esvio_fe_sae_to_time_surface", "esvio_fe_set_auto_exchange", "esvio_fe_set_detector",
     "esvio_fe_set_host_threads", "esvio_fe_set_launch_thread", "esvio_fe_set_lazy_new_stereo",
-    "esvio_fe_set_next_batch", "esvio_fe_set_next_batch_mc", "esvio_fe_track_batch", "esvio_fe_track_event", "esvio_fe_track_event_fields",
+    "esvio_fe_set_next_batch", "esvio_fe_set_next_batch_mc", "esvio_fe_slice_events", "esvio_fe_slice_flush",
+    "esvio_fe_slice_reset", "esvio_fe_track_batch", "esvio_fe_track_event", "esvio_fe_track_event_fields",
     "esvio_fe_track_event_filtered", "esvio_fe_track_event_mc", "esvio_fe_track_raw",
     "esvio_fe_track_image", "esvio_fe_unregister_host_buffer", "esvio_fe_version",
 ]
@@ -148,7 +188,7 @@ TEST_SYMBOLS = [
     "esvio_fe_kernel_count", "esvio_fe_kernel_name", "esvio_fe_latency_phase_name", "esvio_fe_latency_recent",
     "esvio_fe_latency_stats", "esvio_fe_lift_projective", "esvio_fe_plain_call_counters", "esvio_fe_ransac_stats",
     "esvio_fe_ransac_tail", "esvio_fe_raw_tile_bytes", "esvio_fe_reset_kernel_stats", "esvio_fe_set_profiling", "esvio_fe_set_sae",
-    "esvio_fe_stage_kernel_count", "esvio_fe_stream",
+    "esvio_fe_slice_tile_events", "esvio_fe_stage_kernel_count", "esvio_fe_stream",
 ]
 
 LATENCY_PHASES = 16
@@ -254,6 +294,16 @@ def load_library(build_if_missing=True):
     L.esvio_fe_decode_reset.argtypes = [vp]
     L.esvio_fe_track_raw.argtypes = [vp, i, vp, sz, vp, sz, i, C.c_int64, i, C.POINTER(FilterParams), C.POINTER(Motion),
                                      C.POINTER(Tracks), C.POINTER(BatchInfo), C.POINTER(RawInfo * 2)]
+    L.esvio_fe_slice_events.argtypes = [vp, i, vp, sz, i, C.POINTER(SliceParams), vp, sz, C.POINTER(SliceInfo)]
+    L.esvio_fe_slice_flush.argtypes = [vp, i, C.POINTER(SliceInfo)]
+    L.esvio_fe_slice_reset.argtypes = [vp]
+    L.esvio_fe_feed_open.argtypes = [vp, C.POINTER(SliceParams), C.POINTER(FilterParams)]
+    L.esvio_fe_feed_push_events.argtypes = [vp, i, vp, sz, i, C.POINTER(FeedInfo)]
+    L.esvio_fe_feed_push_fields.argtypes = [vp, i, C.POINTER(EventFieldsDesc), sz, i, C.POINTER(FeedInfo)]
+    L.esvio_fe_feed_push_raw.argtypes = [vp, i, i, vp, sz, i, C.c_int64, C.POINTER(FeedInfo)]
+    L.esvio_fe_feed_peek.argtypes = [vp, C.POINTER(FeedWindow)]
+    L.esvio_fe_feed_track.argtypes = [vp, i, C.POINTER(Motion), C.POINTER(Tracks), C.POINTER(BatchInfo)]
+    L.esvio_fe_feed_close.argtypes = [vp]
     L.esvio_fe_set_profiling.argtypes = [vp, i]
     L.esvio_fe_kernel_name.restype = C.c_char_p
     L.esvio_fe_kernel_name.argtypes = [i]
@@ -669,6 +719,91 @@ class FeatureTracker:
         if info.tracked:
             self._take(copy)
         return info, (raw[0], raw[1])
+
+    def slice_events(self, cam, ev, frequency=30.0, origin=None, cuts_cap=SLICE_MAX_WINDOWS):
+        """the stream-slicing stage (esvio_fe_slice_events; include/esvio_fe.h has the rule): camera `cam`'s slicer
+        advanced by `ev` — a numpy EVENT_DTYPE array or a (device_ptr, n) tuple.  origin None: the windows count from the
+        camera's first event; else (sec, nsec).  Returns (cuts, SliceInfo): cuts[j] = the index in `ev` of the first event
+        behind the j-th window this call closed (numpy uint64, info.closed entries).  A failed call raises FrontendError
+        with `.info`; the camera's state is then as it was."""
+        ptr, n, space, keep = _events_arg(ev)
+        prm, info = SliceParams(frequency, origin), SliceInfo()
+        cuts = np.zeros(max(int(cuts_cap), 1), np.uint64)
+        rc = self._hd.L.esvio_fe_slice_events(self._hd.h, int(cam), ptr, n, space, C.byref(prm), _p(cuts), int(cuts_cap), C.byref(info))
+        if rc:
+            e = FrontendError("rc=%d: %s" % (rc, self._hd.L.esvio_fe_last_error(self._hd.h).decode()))
+            e.info = info
+            raise e
+        return cuts[:int(info.closed)], info
+
+    def slice_flush(self, cam):
+        """close camera `cam`'s open window, the end of a stream (esvio_fe_slice_flush).  Returns the SliceInfo."""
+        info = SliceInfo()
+        self._hd.check(self._hd.L.esvio_fe_slice_flush(self._hd.h, int(cam), C.byref(info)))
+        return info
+
+    def slice_reset(self):
+        """both cameras' slicer states back to the fresh state (esvio_fe_slice_reset)"""
+        self._hd.check(self._hd.L.esvio_fe_slice_reset(self._hd.h))
+
+    def feed_open(self, frequency=30.0, origin=None, params=None):
+        """open the handle's feed (esvio_fe_feed_open; include/esvio_fe.h): chunks pushed per camera are cut into windows
+        of 1 / frequency seconds counted from `origin` ((sec, nsec); None: the first left record), through the filter
+        `params` (a FilterParams) if given"""
+        prm = SliceParams(frequency, origin)
+        self._hd.check(self._hd.L.esvio_fe_feed_open(self._hd.h, C.byref(prm), C.byref(params) if params is not None else None))
+
+    def _feed_pushed(self, rc, info):
+        if rc:
+            e = FrontendError("rc=%d: %s" % (rc, self._hd.L.esvio_fe_last_error(self._hd.h).decode()))
+            e.info = info
+            raise e
+        return info
+
+    def feed_push_events(self, cam, ev):
+        """append a chunk of records — a numpy EVENT_DTYPE array or a (device_ptr, n) tuple — to camera `cam`'s stream.
+        Returns the FeedInfo; a failed push raises FrontendError with `.info`."""
+        ptr, n, space, keep = _events_arg(ev)
+        info = FeedInfo()
+        return self._feed_pushed(self._hd.L.esvio_fe_feed_push_events(self._hd.h, int(cam), ptr, n, space, C.byref(info)), info)
+
+    def feed_push_fields(self, cam, fields, src_space=HOST):
+        """append a chunk given as events.EventFields (`src_space` says where the fields lie)"""
+        d, info = fields_desc(fields), FeedInfo()
+        return self._feed_pushed(self._hd.L.esvio_fe_feed_push_fields(self._hd.h, int(cam), C.byref(d), fields.n, src_space, C.byref(info)), info)
+
+    def feed_push_raw(self, cam, fmt, words, t_offset_us=0):
+        """append a chunk of raw words (a contiguous numpy array — its bytes are the stream — or a (device_ptr, n_bytes)
+        tuple) of format RAW_EVT2 / RAW_EVT3; the chunk may end anywhere"""
+        if isinstance(words, tuple):
+            ptr, nbytes, space = C.c_void_p(words[0]), int(words[1]), DEVICE
+        else:
+            words = np.ascontiguousarray(words)
+            ptr, nbytes, space = _p(words), words.nbytes, HOST
+        info = FeedInfo()
+        return self._feed_pushed(self._hd.L.esvio_fe_feed_push_raw(self._hd.h, int(cam), int(fmt), ptr, nbytes, space, int(t_offset_us),
+                                                                   C.byref(info)), info)
+
+    def feed_peek(self):
+        """the oldest window closed in both cameras and not yet tracked, as a FeedWindow (.index, .end_sec / .end_nsec =
+        E_k, .count), or None"""
+        w = FeedWindow()
+        self._hd.check(self._hd.L.esvio_fe_feed_peek(self._hd.h, C.byref(w)))
+        return w if w.ready else None
+
+    def feed_track(self, pub=True, measurements=None, copy=True):
+        """track the window feed_peek shows (esvio_fe_feed_track).  Returns the BatchInfo: .kept, .cur_time, .tracked (0:
+        the left window was empty, the result members are the previous call's)."""
+        info = BatchInfo()
+        self._hd.check(self._hd.L.esvio_fe_feed_track(self._hd.h, int(pub), C.byref(measurements) if measurements is not None else None,
+                                                      C.byref(self._tr), C.byref(info)))
+        if info.tracked:
+            self._take(copy)
+        return info
+
+    def feed_close(self):
+        """close the handle's feed (esvio_fe_feed_close): what it still holds is dropped"""
+        self._hd.check(self._hd.L.esvio_fe_feed_close(self._hd.h))
 
     def filter_reset(self):
         """every stamp plane of the background-activity filter back to `none` (esvio_fe_filter_reset)"""

@@ -607,8 +607,8 @@ int esvio_fe_track_batch(esvio_fe_handle h, const esvio_fe_batch* b, esvio_fe_tr
  * DECODER STATE IS AS IT WAS BEFORE THE CALL, and the next call works normally.  A trailing odd byte (EVT3) or a length
  * that is not a multiple of 4 (EVT2) is an argument error, raised before any device work.
  *
- * Out of scope: cutting a stream into time-based batches (the caller chooses the chunks; first_t_us / last_t_us tell it
- * what it got), EVT2.1, EVT4, AEDAT, the .raw file's ASCII header. */
+ * Cutting the decoded stream into time-based batches is the next stage's business (esvio_fe_slice_events below).
+ * Out of scope: EVT2.1, EVT4, AEDAT, the .raw file's ASCII header. */
 #define ESVIO_FE_RAW_EVT2 2
 #define ESVIO_FE_RAW_EVT3 3
 typedef struct esvio_fe_raw_info {
@@ -655,6 +655,156 @@ int esvio_fe_track_raw(esvio_fe_handle h, int format, const void* left, size_t l
                        const void* right, size_t right_bytes, int space, int64_t t_offset_us,
                        int pub_this_frame, const esvio_fe_filter_params* filter, const esvio_fe_motion* motion,
                        esvio_fe_tracks* out, esvio_fe_batch_info* info, esvio_fe_raw_info raw[2]);
+
+/* ---- stream slicing: a record stream cut into fixed-rate windows, on the device ------------ */
+/* trackEvent takes one batch per camera and call; a recording or a sensor transfer is a long stream whose batch edges
+ * are points in time.  The reference cuts its streams off line, dependences/events_repacking_helper/src/
+ * EventMessageEditor.cpp: every event topic is re-chunked at 30 Hz, the message's header.stamp is the window's END (:25),
+ * the node pairs left and right by it (stereo_event_tracker_node.cpp:382-403) and its publish decision reads it
+ * (:155-188).  This stage does that cut on the device, per camera, with state that survives from call to call, so a chunk
+ * may end anywhere.  The rule below is the specification; its sequential reading is tests/slice_ref.py
+ * (slice_windows), the reference's own loop as it is written is repack() beside it.
+ *
+ * Times.  The stamp of an event is ts = (double)sec + 1e-9 * (double)nsec — ros::Time::toSec(): two roundings, no FMA.
+ * Time(d) of a double is roscpp's ros::Time::fromSec: sec = floor(d), nsec = round((d - sec) * 1e9) (halves away from
+ * zero), and nsec == 10^9 carries into sec.  toSec(Time) is the expression above.  Time() is RESTATED FROM RECALL of
+ * roscpp: the CONTROL FLOW of the reference's loop is pinned by recordings of its compiled code
+ * (tests/golden/repack_ref_*.npz), this rounding is not — the recordings were made against a stand-in ros::Time that
+ * restates it the same way.  period = 1.0 / frequency in double; 1e-3 <= frequency <= 1e6.
+ *
+ * Boundaries.  Per camera E_0 = Time(ts_origin + period), E_{k+1} = Time(toSec(E_k) + period).  ts_origin is the stamp
+ * of the first event the camera's slicer ever sees (the reference's bFirstMessage_ rule) or, with has_origin, the stamp
+ * of esvio_fe_slice_params.origin — the project's own option, so that two cameras share their windows.  The chain
+ * depends on no event after the first: the host computes it.  E_k whose sec leaves 32 bits is no boundary: an event at
+ * or beyond it fails the call (ESVIO_FE_EINVAL).
+ *
+ * Windows.  The carried state is the origin, m — the number of windows closed so far — and whether a first event was
+ * seen.  For the events of a call in stream order, with m_start the count before the call and m_{-1} = m_start:
+ *   c_i = m_start + #{k >= m_start : toSec(E_k) <= ts_i};   m_i = max(m_{i-1}, c_i);   event i belongs to window m_i.
+ * So an event at or after the boundary closes the window (the reference's >=); an event that steps back in time stays
+ * in the open window (where the reference's push_back puts it); equal and non-monotonic stamps need no special case;
+ * an event before an explicit origin belongs to window 0; a jump over whole windows closes each of them, the skipped
+ * ones empty.  The window open at the end of a call is NOT closed — the reference never writes its tail either, and a
+ * stream's end is the caller's business: esvio_fe_slice_flush closes it.  m_i is a prefix maximum, which is associative:
+ * slice(whole) = slice(part 1) then slice(part 2) at every cut.
+ *
+ * Against the reference.  EventMessageEditor::insertEvent advances by at most ONE window per event:
+ * b_i = b_{i-1} + [c_i > b_{i-1}].  Both rules give the same windows and the same header stamps E_k on every stream in
+ * which no event jumps a whole window (c_i <= m_{i-1} + 1 for all i).  After a longer gap the reference's windows lag
+ * behind their own header stamps — a message stamped E_k then holds events from behind E_k — until enough events have
+ * come; there the rule above is THE PROJECT'S OWN, chosen so that the end stamp of a window stays true (the node's
+ * publish decision and its left / right pairing read nothing else).
+ *
+ * Per call at most ESVIO_FE_SLICE_MAX_WINDOWS windows are closed: the call's range is the boundaries E_{m_start} ..
+ * E_{m_start + 4096}, and an event at or beyond the last of them fails the call with ESVIO_FE_EINVAL.  After that
+ * failure, and after every other one, THE CAMERA'S STATE IS AS IT WAS BEFORE THE CALL (the same events in smaller calls
+ * work): the state lives on the host, the device works on counts relative to it, and the host takes the result over
+ * only once the call is known to succeed. */
+#define ESVIO_FE_SLICE_MAX_WINDOWS 4096
+typedef struct esvio_fe_slice_params {
+  double frequency;       /* windows per second, 1e-3 .. 1e6 */
+  esvio_fe_event origin;  /* has_origin != 0: ts_origin is this record's stamp (x, y, polarity are not read) */
+  int32_t has_origin;     /* 0: ts_origin is the stamp of the camera's first event */
+  int32_t reserved;       /* must be 0 */
+} esvio_fe_slice_params;
+typedef struct esvio_fe_slice_info {
+  uint64_t closed;        /* windows this call closed (a failed call: 0, or with too small a cuts_cap the number needed) */
+  uint64_t first_window;  /* index of the first of them = the camera's count before the call */
+  uint64_t count;         /* the camera's count after the call (a failed call: before it) */
+  uint64_t open_events;   /* events in the window left open, earlier calls' included */
+  uint32_t first_sec, first_nsec; /* E of the first closed window (untouched when closed == 0) */
+  uint32_t last_sec, last_nsec;   /* E of the last closed window  (untouched when closed == 0) */
+} esvio_fe_slice_info;
+/* the slicer stage: camera `cam`'s state advanced by the n records of `ev` (space: ESVIO_FE_HOST — copied to the device
+ * as they are, one copy — or ESVIO_FE_DEVICE, 16-byte aligned, read in place; n <= 2^30).  cuts (host, room for cuts_cap
+ * entries): cuts[j] is the index in `ev` of the first event that does not belong to the j-th window this call closed —
+ * window first_window + j is [cuts[j-1], cuts[j]) of this call's events, behind whatever earlier calls left open of it;
+ * entries are non-decreasing, skipped windows repeat an index; entries behind `closed` are not touched.  More closed
+ * windows than cuts_cap: ESVIO_FE_EINVAL, info->closed holds the number needed, the state is as it was.
+ * A camera's frequency and origin are fixed by its first call with n > 0; a later call with other parameters is
+ * ESVIO_FE_EINVAL (esvio_fe_slice_reset first).  n == 0 succeeds, touches nothing and reports the state.
+ * Orders itself on the main stream, waits for its own result (for a device source the very first call without has_origin
+ * also reads ev[0] first) and touches nothing of the tracker: made between two track calls (announced batches or not)
+ * it changes no later tracking result.  ESVIO_FE_EINVAL while a feed is open on the handle (below).  Three launches, none of which waits on the device for another workgroup
+ * (KERNELS.md "Stream slicing").  Its scratch — 4 bytes per 1024 events, the copy of a host source, the boundary table
+ * (128 KiB per camera, refilled every ~12000 windows) — grows on first use: a second call of a size allocates nothing.
+ * ESVIO_FE_EINVAL with a message, before any device work: cam outside 0..1, a bad space, a null prm, reserved != 0, a
+ * frequency outside the limits, null ev with n > 0, a misaligned device ev, null cuts with cuts_cap > 0. */
+int esvio_fe_slice_events(esvio_fe_handle h, int cam, const esvio_fe_event* ev, size_t n, int space,
+                          const esvio_fe_slice_params* prm, uint64_t* cuts, size_t cuts_cap, esvio_fe_slice_info* info);
+/* closes camera `cam`'s open window, empty or not (the end of a stream): closed = 1, first_window = its index,
+ * first / last = its E, open_events = 0.  A camera that has seen no event has no boundaries yet: closed = 0. */
+int esvio_fe_slice_flush(esvio_fe_handle h, int cam, esvio_fe_slice_info* info);
+/* both cameras' slicer states back to the fresh state (esvio_fe_reset does the same as part of "as a freshly created
+ * handle") */
+int esvio_fe_slice_reset(esvio_fe_handle h);
+
+/* ---- the feed: chunks of a stereo stream in, time-aligned windows tracked where they lie ---- */
+/* A small layer over the stages above for a caller that holds a recording or a sensor transfer, not batches: chunks of
+ * records, fields or raw words go in per camera, at any chunk size (a raw chunk may end inside a vector run), optionally
+ * through the noise filter; esvio_fe_track_event calls on fixed-rate windows come out.  The records never leave the
+ * device.  The reference's counterpart is the off-line re-chunking above plus the node's pairing of left and right
+ * messages by header.stamp (stereo_event_tracker_node.cpp:382-403); with a shared origin the window INDEX pairs the
+ * cameras here, the node's 0.2 s tolerance has nothing to do.
+ *
+ * esvio_fe_feed_open: prm as esvio_fe_slice_params — both cameras share the origin: the explicit one, else the stamp of
+ * the first LEFT record the feed appends (a right push before that is ESVIO_FE_EINVAL).  filter: NULL, or the
+ * parameters every pushed chunk is filtered with (copied).  Opening resets both cameras' slicer states; one feed per
+ * handle (a second open is ESVIO_FE_EINVAL; esvio_fe_feed_close first).  esvio_fe_reset empties an open feed — no
+ * records, no windows, the origin as esvio_fe_feed_open left it — and keeps it open.  An open feed owns both cameras'
+ * slicer states — its window queue counts in them: esvio_fe_slice_events, esvio_fe_slice_flush and esvio_fe_slice_reset
+ * are ESVIO_FE_EINVAL while it is open.
+ *
+ * A push appends what it produces to camera cam's accumulation buffer, on the device: the existing convert, filter and
+ * decode chains write at the append position (records without a filter are copied there); then the slicer runs over the
+ * appended records and the windows it closes are queued.  info (optional): the records appended, the filter's rejected
+ * count, the BAD events, the windows this push closed, the camera's closed and untracked windows.
+ * A push waits for the result blocks of the chains it ran — the decode's, the conversion's or the filter's, the
+ * slicer's — and for nothing else.
+ * Failures: argument errors are raised before any device work.  A BAD event (esvio_fe_convert_events,
+ * esvio_fe_decode_raw), a slicer failure or a HIP error appends nothing, queues nothing and leaves the camera's decoder
+ * and slicer states as they were; so is the filter's plane after a BAD event.  Only a slicer failure BEHIND a filter
+ * (a chunk that jumps ESVIO_FE_SLICE_MAX_WINDOWS windows) finds the camera's plane advanced by the chunk:
+ * esvio_fe_filter_reset is then the caller's business.
+ *
+ * esvio_fe_feed_peek: whether a window is closed in BOTH cameras and not yet tracked, and for the oldest such window its
+ * index, its end stamp E_k — the reference's header.stamp, the msg_timestamp the node's publish decision reads
+ * (node:155-188): the caller decides pub_this_frame before it tracks — and both cameras' counts.
+ * esvio_fe_feed_track tracks that window from the accumulation buffers where they lie (ESVIO_FE_DEVICE; with `motion`
+ * the motion-compensated overload), with cur_time = (double)sec + 1e-9 * (double)nsec of the window's last LEFT record
+ * (node:190), read from the device first.  An empty left window is consumed with tracked = 0 and `out` untouched
+ * (node:150); no window ready is ESVIO_FE_EINVAL.  info as esvio_fe_track_batch's: kept = the counts, cur_time, tracked.
+ * Buffer lifetime: each camera has TWO buffers.  The records a track call reads stay untouched until everything that
+ * call enqueued on any of the handle's streams has finished: appends write behind every record a track call was ever
+ * given; when a chunk does not fit behind them, the untracked tail moves to the front of the camera's OTHER buffer
+ * (grown first if it is too small) on the main stream, behind the events recorded on the side streams when the last
+ * track call that read that buffer returned — the mechanism of esvio_fe_track_event_fields' alternating pairs.  Closing
+ * a feed and opening one again rewinds the append position to the front of the current buffers: the first append
+ * behind it waits, on the device, for those same events.  A buffer
+ * grows to 5/4 of what it has to hold: a second stream of the same density allocates nothing; esvio_fe_reserve, for a
+ * handle with an open feed, makes the buffers large enough for 2 * max_events records per camera.
+ * Every feed entry point is refused while batches are announced. */
+typedef struct esvio_fe_feed_info {
+  uint64_t appended, rejected, bad; /* records appended; rejected: filled when a filter ran; BAD events */
+  uint64_t closed, queued;          /* windows this push closed; the camera's closed and untracked windows after it */
+} esvio_fe_feed_info;
+typedef struct esvio_fe_feed_window {
+  int32_t ready, reserved;     /* ready 0: nothing else is filled */
+  uint64_t index;              /* k */
+  uint32_t end_sec, end_nsec;  /* E_k */
+  uint64_t count[2];           /* left, right */
+} esvio_fe_feed_window;
+int esvio_fe_feed_open(esvio_fe_handle h, const esvio_fe_slice_params* prm, const esvio_fe_filter_params* filter);
+int esvio_fe_feed_push_events(esvio_fe_handle h, int cam, const esvio_fe_event* ev, size_t n, int space,
+                              esvio_fe_feed_info* info);
+int esvio_fe_feed_push_fields(esvio_fe_handle h, int cam, const esvio_fe_event_fields* fields, size_t n, int space,
+                              esvio_fe_feed_info* info);
+int esvio_fe_feed_push_raw(esvio_fe_handle h, int cam, int format, const void* words, size_t n_bytes, int space,
+                           int64_t t_offset_us, esvio_fe_feed_info* info);
+int esvio_fe_feed_peek(esvio_fe_handle h, esvio_fe_feed_window* out);
+int esvio_fe_feed_track(esvio_fe_handle h, int pub_this_frame, const esvio_fe_motion* motion, esvio_fe_tracks* out,
+                        esvio_fe_batch_info* info);
+int esvio_fe_feed_close(esvio_fe_handle h);
 
 /* ---- camera split across GPUs (BASELINE config C4) ----------------------- */
 /* The left and right cameras have disjoint SAE state (sae_/sae_latest_ vs sae_right/

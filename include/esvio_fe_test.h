@@ -167,6 +167,8 @@ int esvio_fe_get_kernel_stats(esvio_fe_handle h, int kernel_id, double* total_ms
 int esvio_fe_reset_kernel_stats(esvio_fe_handle h);
 /* the bytes of raw words one workgroup of the decode chain takes (esvio_fe_decode_raw): where its tile edges lie */
 int esvio_fe_raw_tile_bytes(void);
+/* the events one workgroup of the slicing chain takes (esvio_fe_slice_events): where its tile edges lie */
+int esvio_fe_slice_tile_events(void);
 /* the hipStream_t the handle launches on (as void*) */
 void* esvio_fe_stream(esvio_fe_handle h);
 /* hipMemGetInfo on the handle's device, through the HIP runtime the library itself is linked to */
