@@ -356,6 +356,7 @@ int esvio_fe_create(const esvio_fe_config* cfg, esvio_fe_handle* out) {
 
 namespace {
 int baf_clear(esvio_fe_ctx* c);  // the background-activity filter's planes back to `none` (below, with the stage)
+int hot_clear(esvio_fe_ctx* c);  // hot-pixel learning: nothing counted (below, with the stage)
 int baf_ensure(esvio_fe_ctx* c, size_t n, bool host_src, bool host_dst, bool fields_form);
 int raw_ensure(esvio_fe_ctx* c, int cam, size_t n_bytes, bool copied_src, size_t dec_records);  // (below, with the stage)
 void feed_empty(esvio_fe_ctx* c, bool streams_idle);  // the feed: no records, no windows (below, with the feed)
@@ -390,6 +391,7 @@ int esvio_fe_reset(esvio_fe_handle c) {
   HIPCHK(c, hipMemsetAsync(c->L2, 0, (size_t)2 * c->P * 16, cur_stream(c)));
   HIPCHK(c, hipMemsetAsync(c->S2, 0, (size_t)2 * c->P * 16, cur_stream(c)));
   if (int rc = baf_clear(c)) return rc;  // the background-activity filter's planes: none everywhere
+  if (int rc = hot_clear(c)) return rc;  // hot-pixel learning: nothing counted (the address filter and the mask are settings: kept)
   c->rawdec.st[0] = c->rawdec.st[1] = esvio_fe_ctx::Raw::State();  // the raw-stream decoder: the fresh state
   c->slice.st[0] = c->slice.st[1] = esvio_fe_ctx::Slice::State();  // the stream slicer: no event seen, no window closed
   HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
@@ -1177,6 +1179,17 @@ int baf_prm_check(esvio_fe_ctx* c, const esvio_fe_filter_params* p, const char* 
   return 0;
 }
 
+// what the chain's keys kernels take of camera cam's address stage (on == 0: none set)
+AddrArgs addr_args(const esvio_fe_ctx* c, int cam) {
+  AddrArgs a{};
+  if (!c->addr.on[cam]) return a;
+  const esvio_fe_address_filter& f = c->addr.f[cam];
+  a.x0 = f.roi_x0, a.y0 = f.roi_y0, a.x1 = f.roi_x1, a.y1 = f.roi_y1;
+  a.polarity = f.polarity, a.on = 1;
+  a.mask = f.use_mask ? c->addr.mask[cam].p : nullptr;  // (no mask set: use_mask rejects nothing)
+  return a;
+}
+
 int baf_clear(esvio_fe_ctx* c) {  // every plane back to `none`, the sort's scratch words as a finished sort leaves them
   esvio_fe_ctx::Baf& f = c->baf;
   if (f.B) HIPCHK(c, hipMemsetAsync(f.B, 0xff, (size_t)2 * c->P * sizeof(long long), cur_stream(c)));
@@ -1253,12 +1266,17 @@ int baf_enqueue(esvio_fe_ctx* c, int cam, const esvio_fe_event* ev, const esvio_
   const size_t pass_words = (size_t)radix_blocks(n32) << bits;
   uint8_t* res_bytes = (uint8_t*)res;
   const uint64_t fb = fields ? fields_bytes_per_event(*fields) : 0;
+  const AddrArgs ad = addr_args(c, cam);
   // booked: what each launch has to move at least (keys, indices and stamps once; per neighbour a head and a stamp);
   // the emits' share for the kept records is booked as if all were kept
   if (fields) {
     ScopedKernel k(c, K_BAF_KEYS_FIELDS, (uint64_t)n * (fb + 4 + 4 + 8));
     launch_baf_keys_fields(s, fa, n32, c->W, c->H, f.keys[0], f.vals[0], f.tstream, res, passes, bits, sc.ghist, sc.lookback,
-                           (uint32_t)(passes * pass_words));
+                           (uint32_t)(passes * pass_words), ad);
+  } else if (ad.on) {  // step 1a: the stage's keys kernel in k_sae_keys' place (one mask word more per event)
+    ScopedKernel k(c, K_BAF_KEYS_ADDR, (uint64_t)n * 28);
+    launch_baf_keys_addr(s, d_ev, n32, c->W, c->H, f.keys[0], f.vals[0], res, passes, bits, sc.ghist, sc.lookback,
+                         (uint32_t)(passes * pass_words), ad);
   } else {
     ScopedKernel k(c, K_SAE_KEYS, (uint64_t)n * 24);
     launch_sae_keys(s, d_ev, n32, nullptr, 0, c->W, c->H, f.keys[0], f.vals[0], c->P,
@@ -1280,6 +1298,7 @@ int baf_enqueue(esvio_fe_ctx* c, int cam, const esvio_fe_event* ev, const esvio_
   a.window_ns = prm.window_ns, a.min_support = prm.min_support, a.refractory_ns = prm.refractory_ns;
   a.flags = f.flags, a.blk_cnt = f.blk_cnt, a.dst = d_dst, a.res = res;
   a.sort_scratch = f.sort, a.sort_head_words = sc.head_words;
+  a.flatten = ad.on ? c->addr.f[cam].flatten : 0;
   {
     ScopedKernel k(c, K_BAF_HEADS, (uint64_t)n * (fields ? 24 : 32));
     launch_baf_heads(s, a);
@@ -1401,6 +1420,240 @@ int esvio_fe_filter_reset(esvio_fe_handle c) {
   if (!c) return ESVIO_FE_EINVAL;
   HIPCHK(c, hipSetDevice(c->dev));
   if (int rc = baf_clear(c)) return rc;
+  HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  return 0;
+}
+
+// ---- the address stage's settings and hot-pixel learning (the rule: include/esvio_fe.h)
+namespace {
+size_t mask_words(const esvio_fe_ctx* c) { return ((size_t)c->P + 31) / 32; }
+
+int hot_clear(esvio_fe_ctx* c) {
+  esvio_fe_ctx::Hot& h = c->hot;
+  h.h_st[0] = h.h_st[1] = HotState{};
+  if (h.C) {
+    HIPCHK(c, hipMemsetAsync(h.C, 0, (size_t)2 * c->P * 4, cur_stream(c)));
+    HIPCHK(c, hipMemsetAsync(h.st, 0, 2 * sizeof(HotState), cur_stream(c)));
+  }
+  return 0;
+}
+int hot_ensure(esvio_fe_ctx* c) {  // the count planes and the cameras' states, on first use: nothing counted
+  esvio_fe_ctx::Hot& h = c->hot;
+  if (h.C) return 0;
+  if (int rc = h.st.alloc(c, 2)) return rc;
+  if (int rc = h.C.alloc(c, (size_t)2 * c->P)) return rc;
+  hipError_t e = hipMemsetAsync(h.st, 0, 2 * sizeof(HotState), cur_stream(c));
+  if (e == hipSuccess) e = hipMemsetAsync(h.C, 0, (size_t)2 * c->P * 4, cur_stream(c));
+  if (e != hipSuccess) {
+    h.C.release();
+    HIPCHK(c, e);
+  }
+  return 0;
+}
+int mask_ensure(esvio_fe_ctx* c, int cam) {  // camera cam's mask words, on first use: no pixel set
+  DevBuf<uint32_t>& m = c->addr.mask[cam];
+  if (m) return 0;
+  if (int rc = m.alloc(c, mask_words(c))) return rc;
+  const hipError_t e = hipMemsetAsync(m, 0, mask_words(c) * 4, cur_stream(c));
+  if (e != hipSuccess) {
+    m.release();
+    HIPCHK(c, e);
+  }
+  return 0;
+}
+}  // namespace
+
+int esvio_fe_set_address_filter(esvio_fe_handle c, int cam, const esvio_fe_address_filter* a) {
+  if (!c) return ESVIO_FE_EINVAL;
+  const char* who = "set_address_filter";
+  if (cam != 0 && cam != 1) return fail(c, ESVIO_FE_EINVAL, "%s: cam must be 0 or 1 (got %d)", who, cam);
+  if (a) {
+    if (a->roi_x0 > a->roi_x1 || a->roi_y0 > a->roi_y1 || (int)a->roi_x1 >= c->W || (int)a->roi_y1 >= c->H)
+      return fail(c, ESVIO_FE_EINVAL, "%s: the ROI (%u,%u)-(%u,%u) is inverted or leaves the %d x %d sensor", who, a->roi_x0, a->roi_y0,
+                  a->roi_x1, a->roi_y1, c->W, c->H);
+    if (a->polarity < 0 || a->polarity > 2) return fail(c, ESVIO_FE_EINVAL, "%s: polarity must be in 0..2 (got %d)", who, a->polarity);
+    if (a->flatten < 0 || a->flatten > 2) return fail(c, ESVIO_FE_EINVAL, "%s: flatten must be in 0..2 (got %d)", who, a->flatten);
+    if (a->use_mask < 0 || a->use_mask > 1) return fail(c, ESVIO_FE_EINVAL, "%s: use_mask must be 0 or 1 (got %d)", who, a->use_mask);
+    if (a->reserved != 0) return fail(c, ESVIO_FE_EINVAL, "%s: esvio_fe_address_filter.reserved must be 0", who);
+    c->addr.f[cam] = *a;
+  }
+  c->addr.on[cam] = a != nullptr;
+  return 0;
+}
+
+int esvio_fe_set_pixel_mask(esvio_fe_handle c, int cam, const uint16_t* xy, size_t n) {
+  if (!c) return ESVIO_FE_EINVAL;
+  const char* who = "set_pixel_mask";
+  if (cam != 0 && cam != 1) return fail(c, ESVIO_FE_EINVAL, "%s: cam must be 0 or 1 (got %d)", who, cam);
+  if (n && !xy) return fail(c, ESVIO_FE_EINVAL, "%s: xy is null", who);
+  for (size_t k = 0; k < n; k++)
+    if ((int)xy[2 * k] >= c->W || (int)xy[2 * k + 1] >= c->H)
+      return fail(c, ESVIO_FE_EINVAL, "%s: pair %zu (%u,%u) lies outside the %d x %d sensor", who, k, xy[2 * k], xy[2 * k + 1], c->W, c->H);
+  HIPCHK(c, hipSetDevice(c->dev));
+  if (int rc = mask_ensure(c, cam)) return rc;
+  std::vector<uint32_t> words(mask_words(c), 0u);
+  for (size_t k = 0; k < n; k++) {
+    const uint32_t pix = (uint32_t)xy[2 * k + 1] * (uint32_t)c->W + xy[2 * k];
+    words[pix >> 5] |= 1u << (pix & 31u);
+  }
+  // (behind every chain that reads the old words; the copy has left `words` when the wait returns)
+  HIPCHK(c, hipMemcpyAsync(c->addr.mask[cam], words.data(), words.size() * 4, hipMemcpyHostToDevice, cur_stream(c)));
+  HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  return 0;
+}
+
+int esvio_fe_get_pixel_mask(esvio_fe_handle c, int cam, uint16_t* xy, size_t cap, size_t* n) {
+  if (!c) return ESVIO_FE_EINVAL;
+  const char* who = "get_pixel_mask";
+  if (n) *n = 0;
+  if (cam != 0 && cam != 1) return fail(c, ESVIO_FE_EINVAL, "%s: cam must be 0 or 1 (got %d)", who, cam);
+  if (cap && !xy) return fail(c, ESVIO_FE_EINVAL, "%s: xy is null", who);
+  if (!c->addr.mask[cam]) return 0;  // no mask set
+  HIPCHK(c, hipSetDevice(c->dev));
+  std::vector<uint32_t> words(mask_words(c), 0u);
+  HIPCHK(c, hipMemcpyAsync(words.data(), c->addr.mask[cam], words.size() * 4, hipMemcpyDeviceToHost, cur_stream(c)));
+  HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  size_t set = 0;
+  for (uint32_t pix = 0; pix < c->P; pix++)
+    if ((words[pix >> 5] >> (pix & 31u)) & 1u) {
+      if (set < cap) xy[2 * set] = (uint16_t)(pix % (uint32_t)c->W), xy[2 * set + 1] = (uint16_t)(pix / (uint32_t)c->W);
+      set++;
+    }
+  if (n) *n = set;
+  if (set > cap) return fail(c, ESVIO_FE_EINVAL, "%s: the mask holds %zu pixels, xy has room for %zu", who, set, cap);
+  return 0;
+}
+
+int esvio_fe_hot_learn(esvio_fe_handle c, int cam, const esvio_fe_event* ev, const esvio_fe_event_fields* fields, size_t n,
+                       int space, uint64_t* n_bad) {
+  if (!c) return ESVIO_FE_EINVAL;
+  const char* who = "hot_learn";
+  if (n_bad) *n_bad = 0;
+  if (fields)
+    if (int rc = fields_check(c, fields, n, who)) return rc;
+  if (cam != 0 && cam != 1) return fail(c, ESVIO_FE_EINVAL, "%s: cam must be 0 or 1 (got %d)", who, cam);
+  if (space != ESVIO_FE_HOST && space != ESVIO_FE_DEVICE) return fail(c, ESVIO_FE_EINVAL, "%s: bad memory space", who);
+  if (!n) return 0;
+  if (n >= (1ull << 31)) return fail(c, ESVIO_FE_EINVAL, "%s: batch too large", who);
+  if (!ev && !fields) return fail(c, ESVIO_FE_EINVAL, "%s: neither ev nor fields is given", who);
+  if (ev && fields) return fail(c, ESVIO_FE_EINVAL, "%s: both ev and fields are given", who);
+  esvio_fe_ctx::Hot& h = c->hot;
+  if (h.h_st[cam].n + n >= (1ull << 32))
+    return fail(c, ESVIO_FE_EINVAL, "%s: %llu events are counted, %zu more would reach 2^32 (esvio_fe_hot_reset)", who, h.h_st[cam].n, n);
+  HIPCHK(c, hipSetDevice(c->dev));
+  if (int rc = hot_ensure(c)) return rc;
+  hipStream_t s = cur_stream(c);
+  HotState* st = h.st + cam;
+  uint32_t* plane = h.C + (size_t)cam * c->P;
+  HIPCHK(c, hipMemsetAsync((uint8_t*)st + offsetof(HotState, n_bad), 0, 8, s));
+  if (fields) {
+    FieldsArgs fa{};
+    if (int rc = fields_on_device(c, *fields, n, space, &fa)) return rc;
+    ScopedKernel k(c, K_HOT_COUNT, (uint64_t)n * (fields_bytes_per_event(*fields) + 4));
+    launch_hot_count_fields(s, fa, (uint32_t)n, c->W, c->H, plane, st);
+  } else {
+    const EventRec* d_ev = (const EventRec*)ev;
+    if (space == ESVIO_FE_HOST) {
+      if (int rc = h.src.grow(c, n)) return rc;
+      HIPCHK(c, hipMemcpyAsync(h.src, ev, n * sizeof(EventRec), hipMemcpyHostToDevice, s));
+      d_ev = h.src;
+    }
+    ScopedKernel k(c, K_HOT_COUNT, (uint64_t)n * 20);
+    launch_hot_count(s, d_ev, (uint32_t)n, c->W, c->H, plane, st);
+  }
+  HotState got{};
+  HIPCHK(c, hipMemcpyAsync(&got, st, sizeof(HotState), hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  if (c->prof_on) resolve_profile(c);
+  h.h_st[cam] = got;
+  if (n_bad) *n_bad = got.n_bad;
+  if (got.n_bad)
+    return fail(c, ESVIO_FE_EINVAL, "%s: %llu of %zu events %s; they are not counted, the others are", who, got.n_bad, n, kBadStampText);
+  return 0;
+}
+
+int esvio_fe_hot_select(esvio_fe_handle c, int cam, const esvio_fe_hot_params* prm, uint16_t* xy, uint32_t* counts, size_t cap,
+                        esvio_fe_hot_info* info) {
+  if (!c) return ESVIO_FE_EINVAL;
+  const char* who = "hot_select";
+  if (info) *info = esvio_fe_hot_info{};
+  if (cam != 0 && cam != 1) return fail(c, ESVIO_FE_EINVAL, "%s: cam must be 0 or 1 (got %d)", who, cam);
+  if (!prm) return fail(c, ESVIO_FE_EINVAL, "%s: no parameters", who);
+  if (prm->reserved != 0) return fail(c, ESVIO_FE_EINVAL, "%s: esvio_fe_hot_params.reserved must be 0", who);
+  if (prm->max_pixels < 1 || prm->max_pixels > kHotMaxPixels)
+    return fail(c, ESVIO_FE_EINVAL, "%s: max_pixels must be in 1..%u (got %u)", who, kHotMaxPixels, prm->max_pixels);
+  if (prm->min_count < 1) return fail(c, ESVIO_FE_EINVAL, "%s: min_count must be at least 1", who);
+  if (prm->min_rate_hz > (1u << 20) || prm->mean_factor > (1u << 20))
+    return fail(c, ESVIO_FE_EINVAL, "%s: min_rate_hz and mean_factor must not exceed 2^20", who);
+  esvio_fe_ctx::Hot& h = c->hot;
+  const HotState& st = h.h_st[cam];
+  const uint64_t N = st.n, span = N ? st.tmax - ~st.not_tmin : 0;
+  if (prm->min_rate_hz && span > ((uint64_t)1 << 42))
+    return fail(c, ESVIO_FE_EINVAL, "%s: the counted events span %llu ns, above the 2^42 a rate threshold takes", who, (unsigned long long)span);
+  uint64_t T = prm->min_count;  // (2^20 * 2^42 and 2^20 * 2^32 stay inside 64 bits)
+  if (prm->min_rate_hz) T = std::max<uint64_t>(T, ((uint64_t)prm->min_rate_hz * span + 999999999ull) / 1000000000ull);
+  if (prm->mean_factor) T = std::max<uint64_t>(T, ((uint64_t)prm->mean_factor * N + c->P - 1) / c->P);
+  HIPCHK(c, hipSetDevice(c->dev));
+  if (int rc = hot_ensure(c)) return rc;
+  const uint32_t P = c->P;
+  if (!h.sort) {  // the selection's scratch, on first use
+    for (int k = 0; k < 2; k++) {
+      if (int rc = h.keys[k].alloc(c, P)) return rc;
+      if (int rc = h.vals[k].alloc(c, P)) return rc;
+    }
+    if (int rc = h.xy.alloc(c, 2 * kHotMaxPixels)) return rc;
+    if (int rc = h.counts.alloc(c, kHotMaxPixels)) return rc;
+    if (int rc = h.res.alloc(c, 1)) return rc;
+    if (int rc = h.sort.alloc(c, sort_scratch_words(P))) return rc;
+  }
+  if (prm->install)
+    if (int rc = mask_ensure(c, cam)) return rc;
+  hipStream_t s = cur_stream(c);
+  HIPCHK(c, hipMemsetAsync(h.res, 0, sizeof(HotResult), s));
+  HIPCHK(c, hipMemsetAsync(h.sort, 0, h.sort.cap * 4, s));  // digit histograms, tickets and look-back words
+  const SortScratch sc = sort_scratch(h.sort);
+  const size_t pass_words = (size_t)radix_blocks(P) << kRadixMaxBits;
+  HotResult* res = h.res;
+  {
+    ScopedKernel k(c, K_HOT_KEYS, (uint64_t)P * 12);
+    // (a threshold above every possible count: no pixel reaches it)
+    launch_hot_keys(s, h.C + (size_t)cam * P, P, (uint32_t)std::min<uint64_t>(T, 0xffffffffull), h.keys[0], h.vals[0], sc.ghist, res);
+  }
+  int cur = 0;
+  for (int p = 0; p < kRadixMaxPasses; p++) {
+    ScopedKernel k(c, K_RADIX_PASS, (uint64_t)P * 16);
+    launch_radix_pass(s, h.keys[cur], h.vals[cur], P, p * kRadixMaxBits, kRadixMaxBits, sc.ghist + ((size_t)p << kRadixMaxBits),
+                      sc.lookback + p * pass_words, sc.tickets + p, h.keys[cur ^ 1], h.vals[cur ^ 1],
+                      (int*)((uint8_t*)res + offsetof(HotResult, err)), c->lim.lookback);
+    cur ^= 1;
+  }
+  const bool wants_list = xy || counts;
+  {
+    ScopedKernel k(c, K_HOT_PICK, (uint64_t)prm->max_pixels * 16);
+    launch_hot_pick(s, h.keys[cur], h.vals[cur], c->W, P, prm->max_pixels,
+                    wants_list ? (uint32_t)std::min<size_t>(cap, kHotMaxPixels) : kHotMaxPixels, h.xy, h.counts,
+                    prm->install ? c->addr.mask[cam].p : nullptr, (uint32_t)mask_words(c), res);
+  }
+  HotResult r{};
+  HIPCHK(c, hipMemcpyAsync(&r, res, sizeof(HotResult), hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  if (c->prof_on) resolve_profile(c);
+  if (r.err) return fail(c, ESVIO_FE_EINTERNAL, "%s: radix sort look-back spin expired; nothing selected or installed", who);
+  if (info) info->events = N, info->span_ns = span, info->threshold = T, info->above = r.above, info->selected = r.selected;
+  if (wants_list && r.selected > cap)
+    return fail(c, ESVIO_FE_EINVAL, "%s: %u pixels are selected, the lists have room for %zu; nothing installed", who, r.selected, cap);
+  if (r.selected) {
+    if (xy) HIPCHK(c, hipMemcpyAsync(xy, h.xy, (size_t)r.selected * 4, hipMemcpyDeviceToHost, s));
+    if (counts) HIPCHK(c, hipMemcpyAsync(counts, h.counts, (size_t)r.selected * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+  }
+  return 0;
+}
+
+int esvio_fe_hot_reset(esvio_fe_handle c) {
+  if (!c) return ESVIO_FE_EINVAL;
+  HIPCHK(c, hipSetDevice(c->dev));
+  if (int rc = hot_clear(c)) return rc;
   HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
   return 0;
 }

@@ -71,7 +71,8 @@ const char* const kKernelNames[K_COUNT] = {
     "k_scharr", "k_pad_scharr", "k_lk_f32", "k_lk", "k_arc_map", "k_arc_ev", "k_dedup", "k_compact", "k_select_mw",
     "k_select", "k_select_gbm", "k_fast_score", "k_fast_collect", "k_events_from_fields", "k_baf_heads", "k_baf_filter",
     "k_baf_count", "k_baf_scan", "k_baf_emit", "k_baf_keys_fields", "k_baf_emit_fields", "k_raw_reduce", "k_raw_scan",
-    "k_raw_emit", "k_slice_reduce", "k_slice_scan", "k_slice_cuts"};
+    "k_raw_emit", "k_slice_reduce", "k_slice_scan", "k_slice_cuts", "k_baf_keys_addr", "k_hot_count", "k_hot_keys",
+    "k_hot_pick"};
 
 // The host phases of one trackEvent call, in the order of esvio_fe_latency_call::phase_ms; kPhaseNames is what
 // esvio_fe_latency_phase_name returns and what the ESVIO_FE_TRACE summary prints.  The PH_PUB_* phases are parts of
@@ -499,6 +500,24 @@ struct esvio_fe_ctx {
     DevBuf<EventRec> src, out;
     size_t cap = 0;
   } baf;
+
+  // ---- the address stage of the filter rule and hot-pixel learning (include/esvio_fe.h).  The address filter and the
+  // pixel mask are SETTINGS (they survive esvio_fe_reset); the mask's words are allocated by the first call that sets
+  // one.  hot: the count planes [2][P] and the per-camera state, allocated by the first learn / select, the host's
+  // copy of each camera's state (taken over when a learn call returns), the selection's own scratch (main stream only).
+  struct Addr {
+    bool on[2] = {false, false};
+    esvio_fe_address_filter f[2] = {};
+    DevBuf<uint32_t> mask[2];
+  } addr;
+  struct Hot {
+    DevBuf<uint32_t> C, keys[2], vals[2], sort, counts;
+    DevBuf<uint16_t> xy;
+    DevBuf<HotState> st;   // [2]
+    DevBuf<HotResult> res;
+    DevBuf<EventRec> src;  // the copy of a host source of records
+    HotState h_st[2] = {};
+  } hot;
 
   // ---- esvio_fe_decode_raw / esvio_fe_track_raw: raw sensor streams (include/esvio_fe.h has the rule, fe_kernels.h
   // the chain).  st: each camera's decoder state, kept on the HOST — it travels to the scan launch as an argument and

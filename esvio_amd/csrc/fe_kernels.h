@@ -86,12 +86,16 @@ enum KernelId {
   K_SLICE_REDUCE,    // esvio_fe_slice_events: cutting a record stream into fixed-rate windows
   K_SLICE_SCAN,
   K_SLICE_CUTS,
+  K_BAF_KEYS_ADDR,   // the filter's record form with an address stage set (in k_sae_keys' place)
+  K_HOT_COUNT,       // esvio_fe_hot_learn (records and fields)
+  K_HOT_KEYS,        // esvio_fe_hot_select: keys of the count plane (its sort is booked as K_RADIX_PASS), then the pick
+  K_HOT_PICK,
   K_COUNT
 };
 // esvio_fe_kernel_count(): the kernels of the tracker's entry points, the table bench.py and the recorded launch traces
 // list.  The ids from here on belong to stages off every track path and are listed by esvio_fe_stage_kernel_count().
 constexpr int kTrackKernels = K_BAF_HEADS;
-static_assert(K_EVENTS_FROM_FIELDS + 1 == kTrackKernels && K_SLICE_CUTS + 1 == K_COUNT,
+static_assert(K_EVENTS_FROM_FIELDS + 1 == kTrackKernels && K_HOT_PICK + 1 == K_COUNT,
               "a track-path kernel goes in front of K_BAF_HEADS (and into this assertion), a stage's kernel behind it");
 
 // ---- SAE update -------------------------------------------------------------------------
@@ -540,8 +544,18 @@ void launch_events_from_fields(hipStream_t s, const FieldsArgs& a, size_t n, Eve
 // stream, each launch reading what the launches before it wrote; no launch of these five waits on the device.
 // On field arrays (esvio_fe_filter_batch with esvio_fe_event_fields) three launches differ: launch_baf_keys_fields
 // in launch_sae_keys' place, the heads launch with BafArgs::tstream set, launch_baf_emit_fields in launch_baf_emit's.
+// With an address stage set (esvio_fe_set_address_filter: step 1a of the rule) the record form launches
+// launch_baf_keys_addr in launch_sae_keys' place and the fields form's keys kernel takes the stage too: an event the
+// stage rejects gets key P, as an out-of-sensor one — it sorts last and nothing behind the keys looks at it.  The emits
+// take the flatten value.  on == 0: no stage; the chain is then the launches it was without one.
+struct AddrArgs {
+  uint32_t x0, y0, x1, y1;  // the ROI, inclusive
+  int32_t polarity;         // 0 both; 1 ON only; 2 OFF only
+  int32_t on;               // != 0: a stage is set
+  const uint32_t* mask;     // [(P + 31) / 32] bit (pixel & 31) of word (pixel >> 5): the pixel is silenced; NULL: no mask
+};
 struct BafResult {  // zeroed by the host in front of the chain; one per camera
-  unsigned long long n_rejected;  // k_sae_keys / k_baf_keys_fields
+  unsigned long long n_rejected;  // k_sae_keys / k_baf_keys_addr / k_baf_keys_fields
   uint32_t n_kept;                // k_baf_scan
   int err;                        // k_radix_pass: a look-back wait expired
   EventRec last;                  // k_baf_emit(_fields): the last kept record (untouched if none)
@@ -571,6 +585,7 @@ struct BafArgs {
   BafResult* res;
   uint32_t* sort_scratch;  // the sort's ghist + tickets, cleared by launch_baf_filter (sort_head_words words)
   uint32_t sort_head_words;
+  int flatten;           // the address stage's: 0 no; 1 / 2: a kept record's polarity byte becomes 1 / 0
 };
 void launch_baf_heads(hipStream_t s, const BafArgs& a);
 void launch_baf_filter(hipStream_t s, const BafArgs& a);
@@ -582,8 +597,43 @@ void launch_baf_emit(hipStream_t s, const BafArgs& a);
 // res->n_bad are added to
 void launch_baf_keys_fields(hipStream_t s, const FieldsArgs& fields, uint32_t n, int W, int H, uint32_t* keys, uint32_t* vals,
                             long long* tstream, BafResult* res, int passes, int bits, uint32_t* ghist, uint32_t* lookback,
-                            uint32_t lookback_words);
+                            uint32_t lookback_words, const AddrArgs& addr);
 void launch_baf_emit_fields(hipStream_t s, const BafArgs& a, const FieldsArgs& fields);
+// the record form with an address stage: launch_sae_keys' keys, indices, digit histograms and look-back clearing for
+// one camera's n records; key P for an out-of-sensor or address-rejected event, both counted in res->n_rejected
+void launch_baf_keys_addr(hipStream_t s, const EventRec* ev, uint32_t n, int W, int H, uint32_t* keys, uint32_t* vals,
+                          BafResult* res, int passes, int bits, uint32_t* ghist, uint32_t* lookback, uint32_t lookback_words,
+                          const AddrArgs& addr);
+
+// ---- hot-pixel learning (esvio_fe_hot_learn, esvio_fe_hot_select) ----------------------------------------------------
+// include/esvio_fe.h holds the rule.  Learn: one launch; C[pixel] += 1 per in-sensor event, equal pixels combined
+// inside a wave (one add of the group's size per distinct pixel), per wave one add to n and one 64-bit max each to
+// tmax and to ~tmin.  Select: keys of the count plane (0xFFFFFFFF - C for C >= T, else 0xFFFFFFFF; value = pixel) ->
+// launch_radix_pass x 4 over 8 bits (stable: equal counts stay in pixel order) -> pick (one workgroup: the list, the
+// counts, the result block and, installing, the mask words).  No launch of these waits on the device for another
+// workgroup but the radix pass's bounded look-back.
+struct HotState {  // per camera; all zero = nothing learned
+  unsigned long long n;         // events counted
+  unsigned long long not_tmin;  // ~t_min (so that the empty state is zero and the update is a max)
+  unsigned long long tmax;
+  unsigned long long n_bad;     // the running call's BAD events (zeroed by the host in front of the launch)
+};
+struct HotResult {  // zeroed by the host in front of a selection
+  uint32_t above, selected;
+  int err;          // k_radix_pass: a look-back wait expired
+  int installed;
+};
+constexpr uint32_t kHotMaxPixels = 4096;
+void launch_hot_count(hipStream_t s, const EventRec* ev, uint32_t n, int W, int H, uint32_t* C, HotState* st);
+void launch_hot_count_fields(hipStream_t s, const FieldsArgs& fields, uint32_t n, int W, int H, uint32_t* C, HotState* st);
+// keys / values of the P pixels, their four digit histograms added to ghist[4 << 8] (zeroed by the caller, as the
+// look-back words are), res->above
+void launch_hot_keys(hipStream_t s, const uint32_t* C, uint32_t P, uint32_t threshold, uint32_t* keys, uint32_t* vals,
+                     uint32_t* ghist, HotResult* res);
+// the first min(res->above, max_pixels) sorted pairs -> xy[2j], xy[2j+1], counts[j]; res->selected; with mask != NULL
+// and selected <= cap: the mask_words words cleared and the selection's bits set (res->installed = 1)
+void launch_hot_pick(hipStream_t s, const uint32_t* keys, const uint32_t* vals, int W, uint32_t P, uint32_t max_pixels,
+                     uint32_t cap, uint16_t* xy, uint32_t* counts, uint32_t* mask, uint32_t mask_words, HotResult* res);
 
 // ---- raw sensor streams: Prophesee EVT3 / EVT2 words -> event records (esvio_fe_decode_raw, esvio_fe_track_raw) ----
 // include/esvio_fe.h holds the rule.  Everything a word needs from the words before it is a "last writer before me"

@@ -4105,19 +4105,61 @@ __global__ __launch_bounds__(256) void k_baf_emit(BafArgs a, uint32_t nblk) {
 #pragma unroll
   for (int j = 0; j < 4; j++)
     if (f & (1u << (8 * j))) {
-      const uint4 e = src[(size_t)w * 4 + j];
+      const uint4 r = src[(size_t)w * 4 + j];
+      // (a new value, not r.w rewritten in place: a record whose member is stored to is kept in memory, not registers)
+      const uint4 e = a.flatten ? make_uint4(r.x, r.y, r.z, (r.w & ~0xffu) | (a.flatten == 1 ? 1u : 0u)) : r;
       dst[pos++] = e;
       if (pos == total) *(uint4*)&a.res->last = e;
     }
 }
 
-// ---- the fields form
-template <int kUnitNs, int kTBits, int kPBits>
+// ---- the address stage (step 1a of the rule): an in-sensor event (pix < P) outside the ROI, of a suppressed polarity
+// or of a masked pixel is rejected as an out-of-sensor one is.  The mask is read with a plain load: 115 KB at 1280 x 720.
+__device__ __forceinline__ bool addr_rejects(const AddrArgs& a, uint32_t x, uint32_t y, uint32_t pix, bool on) {
+  bool rej = x < a.x0 || x > a.x1 || y < a.y0 || y > a.y1 || (a.polarity == 1 && !on) || (a.polarity == 2 && on);
+  if (!rej && a.mask) rej = (a.mask[pix >> 5] >> (pix & 31u)) & 1u;
+  return rej;
+}
+
+// the record form with a stage: k_sae_keys' work for one camera's records (k_sae_keys is shared with the SAE sort form
+// and stays as it is), n_rejected as one atomic per wave
+__global__ __launch_bounds__(256) void k_baf_keys_addr(const uint4* __restrict__ ev, uint32_t n, int W, int H,
+                                                       uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
+                                                       BafResult* res, int passes, int bits, uint32_t* __restrict__ ghist,
+                                                       uint32_t* __restrict__ lookback, uint32_t lookback_words, AddrArgs ad) {
+  __shared__ uint32_t h[kRadixMaxPasses << kRadixMaxBits];
+  const int bins = 1 << bits;
+  for (int i = threadIdx.x; i < passes * bins; i += 256) h[i] = 0;
+  __syncthreads();
+  const uint32_t P = (uint32_t)W * (uint32_t)H;
+  uint32_t rejected = 0;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const uint4 e = ev[i];
+    const uint32_t x = e.x & 0xffffu, y = e.x >> 16;
+    bool ok = x < (uint32_t)W && y < (uint32_t)H;
+    if (ok) ok = !addr_rejects(ad, x, y, y * (uint32_t)W + x, (e.w & 0xffu) != 0);
+    const uint32_t key = ok ? y * (uint32_t)W + x : P;
+    keys[i] = key;
+    vals[i] = i;
+    rejected += ok ? 0u : 1u;
+    for (int p = 0; p < passes; p++) atomicAdd(&h[p * bins + ((key >> (p * bits)) & (bins - 1))], 1u);
+  }
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < lookback_words; i += gridDim.x * blockDim.x) lookback[i] = 0;
+  __syncthreads();
+  for (int i = threadIdx.x; i < passes * bins; i += 256)
+    if (h[i]) atomicAdd(&ghist[i], h[i]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) rejected += __shfl_xor(rejected, o);
+  if (lane_id() == 0 && rejected) atomicAdd(&res->n_rejected, (unsigned long long)rejected);
+}
+
+// ---- the fields form (kAddr: with an address stage; without one the kernel is what it was)
+template <int kUnitNs, int kTBits, int kPBits, bool kAddr>
 __global__ __launch_bounds__(256) void k_baf_keys_fields(FieldsArgs fa, uint32_t n, uint32_t aos, int W, int H,
                                                          uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
                                                          long long* __restrict__ tstream, BafResult* res, int passes,
                                                          int bits, uint32_t* __restrict__ ghist,
-                                                         uint32_t* __restrict__ lookback, uint32_t lookback_words) {
+                                                         uint32_t* __restrict__ lookback, uint32_t lookback_words, AddrArgs ad) {
   __shared__ uint32_t h[kRadixMaxPasses << kRadixMaxBits];
   const int bins = 1 << bits;
   for (int i = threadIdx.x; i < passes * bins; i += 256) h[i] = 0;
@@ -4138,7 +4180,8 @@ __global__ __launch_bounds__(256) void k_baf_keys_fields(FieldsArgs fa, uint32_t
       if (k < cnt) {
         const uint4 r = fields_record<kUnitNs, kTBits>(xs[k], ys[k], ts[k], fa.t_offset, ps[k], bad);
         const uint32_t x = r.x & 0xffffu, y = r.x >> 16;
-        const bool ok = x < (uint32_t)W && y < (uint32_t)H;
+        bool ok = x < (uint32_t)W && y < (uint32_t)H;
+        if (kAddr && ok) ok = !addr_rejects(ad, x, y, y * (uint32_t)W + x, r.w != 0);
         key[k] = ok ? y * (uint32_t)W + x : P;
         stamp[k] = (long long)r.y * 1000000000ll + (long long)r.z;
         rejected += ok ? 0u : 1u;
@@ -4180,7 +4223,8 @@ __global__ __launch_bounds__(256) void k_baf_emit_fields(BafArgs a, FieldsArgs f
 #pragma unroll
   for (int j = 0; j < 4; j++)
     if (f & (1u << (8 * j))) {
-      const uint4 e = fields_record<kUnitNs, kTBits>(xs[j], ys[j], ts[j], fa.t_offset, ps[j], bad);
+      const uint4 r = fields_record<kUnitNs, kTBits>(xs[j], ys[j], ts[j], fa.t_offset, ps[j], bad);
+      const uint4 e = a.flatten ? make_uint4(r.x, r.y, r.z, a.flatten == 1 ? 1u : 0u) : r;
       dst[pos++] = e;
       if (pos == total) *(uint4*)&a.res->last = e;
     }
@@ -4207,16 +4251,20 @@ void launch_baf_emit(hipStream_t s, const BafArgs& a) {
 }
 void launch_baf_keys_fields(hipStream_t s, const FieldsArgs& fields, uint32_t n, int W, int H, uint32_t* keys, uint32_t* vals,
                             long long* tstream, BafResult* res, int passes, int bits, uint32_t* ghist, uint32_t* lookback,
-                            uint32_t lookback_words) {
+                            uint32_t lookback_words, const AddrArgs& addr) {
   if (!n) return;
   FieldsArgs k;
   const uint32_t aos = fields_aos(fields, &k);
   uint32_t grid = ((n + 3) / 4 + 255) / 256;  // four events per lane and round, as k_sae_keys' grid has
   if (grid > 1024) grid = 1024;
 #define ESVIO_FIELDS_CASE(U, T, P)                                                                                     \
-  if (fields.t_unit_ns == U && fields.t_bits == T && fields.p_bits == P)                                              \
-    return launch_k(k_baf_keys_fields<U, T, P>, dim3(grid), dim3(256), 0, s, k, n, aos, W, H, keys, vals, tstream, res, \
-                    passes, bits, ghist, lookback, lookback_words);
+  if (fields.t_unit_ns == U && fields.t_bits == T && fields.p_bits == P) {                                            \
+    if (addr.on)                                                                                                       \
+      return launch_k(k_baf_keys_fields<U, T, P, true>, dim3(grid), dim3(256), 0, s, k, n, aos, W, H, keys, vals,      \
+                      tstream, res, passes, bits, ghist, lookback, lookback_words, addr);                              \
+    return launch_k(k_baf_keys_fields<U, T, P, false>, dim3(grid), dim3(256), 0, s, k, n, aos, W, H, keys, vals,       \
+                    tstream, res, passes, bits, ghist, lookback, lookback_words, addr);                                \
+  }
   ESVIO_FIELDS_DISPATCH(ESVIO_FIELDS_CASE)
 #undef ESVIO_FIELDS_CASE
   abort();
@@ -4231,6 +4279,190 @@ void launch_baf_emit_fields(hipStream_t s, const BafArgs& a, const FieldsArgs& f
   ESVIO_FIELDS_DISPATCH(ESVIO_FIELDS_CASE)
 #undef ESVIO_FIELDS_CASE
   abort();
+}
+
+void launch_baf_keys_addr(hipStream_t s, const EventRec* ev, uint32_t n, int W, int H, uint32_t* keys, uint32_t* vals,
+                          BafResult* res, int passes, int bits, uint32_t* ghist, uint32_t* lookback, uint32_t lookback_words,
+                          const AddrArgs& addr) {
+  if (!n) return;
+  uint32_t grid = (n + 1023) / 1024;  // launch_sae_keys' grid
+  if (grid > 1024) grid = 1024;
+  launch_k(k_baf_keys_addr, dim3(grid), dim3(256), 0, s, (const uint4*)ev, n, W, H, keys, vals, res, passes, bits, ghist,
+           lookback, lookback_words, addr);
+}
+
+// ============================================================================ hot-pixel learning
+// esvio_fe_hot_learn / esvio_fe_hot_select (include/esvio_fe.h is the specification, fe_kernels.h has the chain).
+// A hot pixel is a pile of adders on one word, so equal pixels are combined inside the wave first — match-any by
+// ballots over the pixel's bits, as k_radix_pass ranks its digits — and the lowest lane of each group adds the group's
+// size.  Integer sums, minima and maxima do not depend on the order: the state is exact whatever the schedule.
+// Every lane of the wave calls this (the loops around it have wave-uniform trip counts).
+__device__ __forceinline__ void hot_add(uint32_t* __restrict__ C, bool ok, uint32_t pix, int key_bits) {
+  unsigned long long m = __ballot(ok);
+  for (int b = 0; b < key_bits; b++) {
+    const unsigned long long bal = __ballot((pix >> b) & 1u);
+    m &= ((pix >> b) & 1u) ? bal : ~bal;
+  }
+  if (ok && (m & ((1ull << lane_id()) - 1ull)) == 0) atomicAdd(&C[pix], (uint32_t)__popcll(m));
+}
+// a lane's share of the state -> the wave's -> one add and two 64-bit maxima
+__device__ __forceinline__ void hot_state_add(HotState* st, uint32_t cnt, unsigned long long tmax, unsigned long long not_tmin,
+                                              uint32_t bad) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    cnt += __shfl_xor(cnt, o);
+    bad += __shfl_xor(bad, o);
+    const unsigned long long a = __shfl_xor(tmax, o), b = __shfl_xor(not_tmin, o);
+    tmax = a > tmax ? a : tmax;
+    not_tmin = b > not_tmin ? b : not_tmin;
+  }
+  if (lane_id() != 0) return;
+  if (cnt) {
+    atomicAdd(&st->n, (unsigned long long)cnt);
+    atomicMax(&st->tmax, tmax);
+    atomicMax(&st->not_tmin, not_tmin);
+  }
+  if (bad) atomicAdd(&st->n_bad, (unsigned long long)bad);
+}
+
+__global__ __launch_bounds__(256) void k_hot_count(const uint4* __restrict__ ev, uint32_t n, int W, int H, int key_bits,
+                                                   uint32_t* __restrict__ C, HotState* st) {
+  const uint32_t step = gridDim.x * 256u;
+  uint32_t cnt = 0;
+  unsigned long long tmax = 0, not_tmin = 0;
+  for (uint32_t base = blockIdx.x * 256u + (threadIdx.x & ~63u); base < n; base += step) {  // (the wave's first event)
+    const uint32_t i = base + lane_id();
+    const uint4 e = i < n ? ev[i] : make_uint4(0xffffffffu, 0, 0, 0);
+    const uint32_t x = e.x & 0xffffu, y = e.x >> 16;
+    const bool ok = i < n && x < (uint32_t)W && y < (uint32_t)H;
+    hot_add(C, ok, ok ? y * (uint32_t)W + x : 0u, key_bits);
+    if (ok) {
+      const unsigned long long t = (unsigned long long)e.y * 1000000000ull + e.z;
+      cnt++;
+      tmax = t > tmax ? t : tmax;
+      not_tmin = ~t > not_tmin ? ~t : not_tmin;
+    }
+  }
+  hot_state_add(st, cnt, tmax, not_tmin, 0);
+}
+
+template <int kUnitNs, int kTBits, int kPBits>
+__global__ __launch_bounds__(256) void k_hot_count_fields(FieldsArgs fa, uint32_t n, uint32_t aos, int W, int H, int key_bits,
+                                                          uint32_t* __restrict__ C, HotState* st) {
+  const uint32_t groups = (n + 3) / 4, step = gridDim.x * 256u;
+  uint32_t cnt = 0, bad = 0;
+  unsigned long long tmax = 0, not_tmin = 0;
+  for (uint32_t gb = blockIdx.x * 256u + (threadIdx.x & ~63u); gb < groups; gb += step) {
+    const uint32_t g = gb + lane_id();
+    const uint32_t i0 = g * 4;
+    const int have = g < groups ? (n - i0 >= 4 ? 4 : (int)(n - i0)) : 0;
+    uint32_t xs[4] = {0, 0, 0, 0}, ys[4] = {0, 0, 0, 0}, ps[4] = {0, 0, 0, 0};
+    int64_t ts[4] = {0, 0, 0, 0};
+    if (have) fields_load4<kTBits, kPBits>(fa, aos, i0, have, xs, ys, ts, ps);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      uint32_t b = 0;
+      const uint4 r = fields_record<kUnitNs, kTBits>(xs[k], ys[k], ts[k], fa.t_offset, ps[k], b);
+      const uint32_t x = r.x & 0xffffu, y = r.x >> 16;
+      const bool valid = k < have;
+      const bool ok = valid && !b && x < (uint32_t)W && y < (uint32_t)H;
+      bad += valid ? b : 0u;
+      hot_add(C, ok, ok ? y * (uint32_t)W + x : 0u, key_bits);
+      if (ok) {
+        const unsigned long long t = (unsigned long long)r.y * 1000000000ull + r.z;
+        cnt++;
+        tmax = t > tmax ? t : tmax;
+        not_tmin = ~t > not_tmin ? ~t : not_tmin;
+      }
+    }
+  }
+  hot_state_add(st, cnt, tmax, not_tmin, bad);
+}
+
+__global__ __launch_bounds__(256) void k_hot_keys(const uint32_t* __restrict__ C, uint32_t P, uint32_t threshold,
+                                                  uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
+                                                  uint32_t* __restrict__ ghist, HotResult* res) {
+  __shared__ uint32_t h[4 << 8];
+  for (int i = threadIdx.x; i < (4 << 8); i += 256) h[i] = 0;
+  __syncthreads();
+  uint32_t above = 0, cold = 0;
+  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < P; i += gridDim.x * 256u) {
+    const uint32_t c = C[i];
+    const bool hot = c >= threshold;
+    const uint32_t key = hot ? 0xffffffffu - c : 0xffffffffu;
+    keys[i] = key;
+    vals[i] = i;
+    if (hot) {
+      above++;
+#pragma unroll
+      for (int p = 0; p < 4; p++) atomicAdd(&h[(p << 8) + ((key >> (8 * p)) & 255u)], 1u);
+    } else {
+      cold++;  // (nearly every pixel: digit 255 in all four passes, added once per wave)
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) above += __shfl_xor(above, o), cold += __shfl_xor(cold, o);
+  if (lane_id() == 0 && cold)
+    for (int p = 0; p < 4; p++) atomicAdd(&h[(p << 8) + 255], cold);
+  if (lane_id() == 0 && above) atomicAdd(&res->above, above);
+  __syncthreads();
+  for (int i = threadIdx.x; i < (4 << 8); i += 256)
+    if (h[i]) atomicAdd(&ghist[i], h[i]);
+}
+
+constexpr int kHotPickThreads = 1024;
+__global__ __launch_bounds__(kHotPickThreads) void k_hot_pick(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
+                                                              int W, uint32_t P, uint32_t max_pixels, uint32_t cap,
+                                                              uint16_t* __restrict__ xy, uint32_t* __restrict__ counts,
+                                                              uint32_t* __restrict__ mask, uint32_t mask_words, HotResult* res) {
+  if (res->err) return;  // (a sort pass gave up: the pairs are not sorted, nothing is picked or installed)
+  const uint32_t sel = min(res->above, max_pixels);
+  const bool install = mask != nullptr && sel <= cap;
+  if (install)
+    for (uint32_t j = threadIdx.x; j < mask_words; j += kHotPickThreads) mask[j] = 0;
+  __syncthreads();
+  for (uint32_t j = threadIdx.x; j < sel; j += kHotPickThreads) {
+    const uint32_t pix = min(vals[j], P - 1);  // (a pixel index by construction)
+    xy[2 * j] = (uint16_t)(pix % (uint32_t)W);
+    xy[2 * j + 1] = (uint16_t)(pix / (uint32_t)W);
+    counts[j] = 0xffffffffu - keys[j];
+    if (install) atomicOr(&mask[pix >> 5], 1u << (pix & 31u));
+  }
+  if (threadIdx.x == 0) res->selected = sel, res->installed = install ? 1 : 0;
+}
+
+void launch_hot_count(hipStream_t s, const EventRec* ev, uint32_t n, int W, int H, uint32_t* C, HotState* st) {
+  if (!n) return;
+  int key_bits = 1;
+  while ((1ull << key_bits) < (unsigned long long)W * H) key_bits++;
+  uint32_t grid = (n + 1023) / 1024;
+  if (grid > 1024) grid = 1024;
+  launch_k(k_hot_count, dim3(grid), dim3(256), 0, s, (const uint4*)ev, n, W, H, key_bits, C, st);
+}
+void launch_hot_count_fields(hipStream_t s, const FieldsArgs& fields, uint32_t n, int W, int H, uint32_t* C, HotState* st) {
+  if (!n) return;
+  int key_bits = 1;
+  while ((1ull << key_bits) < (unsigned long long)W * H) key_bits++;
+  FieldsArgs k;
+  const uint32_t aos = fields_aos(fields, &k);
+  uint32_t grid = ((n + 3) / 4 + 255) / 256;
+  if (grid > 1024) grid = 1024;
+#define ESVIO_FIELDS_CASE(U, T, P)                                        \
+  if (fields.t_unit_ns == U && fields.t_bits == T && fields.p_bits == P) \
+    return launch_k(k_hot_count_fields<U, T, P>, dim3(grid), dim3(256), 0, s, k, n, aos, W, H, key_bits, C, st);
+  ESVIO_FIELDS_DISPATCH(ESVIO_FIELDS_CASE)
+#undef ESVIO_FIELDS_CASE
+  abort();
+}
+void launch_hot_keys(hipStream_t s, const uint32_t* C, uint32_t P, uint32_t threshold, uint32_t* keys, uint32_t* vals,
+                     uint32_t* ghist, HotResult* res) {
+  uint32_t grid = (P + 1023) / 1024;
+  if (grid > 1024) grid = 1024;
+  launch_k(k_hot_keys, dim3(grid), dim3(256), 0, s, C, P, threshold, keys, vals, ghist, res);
+}
+void launch_hot_pick(hipStream_t s, const uint32_t* keys, const uint32_t* vals, int W, uint32_t P, uint32_t max_pixels,
+                     uint32_t cap, uint16_t* xy, uint32_t* counts, uint32_t* mask, uint32_t mask_words, HotResult* res) {
+  launch_k(k_hot_pick, dim3(1), dim3(kHotPickThreads), 0, s, keys, vals, W, P, max_pixels, cap, xy, counts, mask, mask_words, res);
 }
 
 // ============================================================================ raw sensor streams

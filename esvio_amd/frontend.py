@@ -86,6 +86,31 @@ class FilterParams(C.Structure):
         super().__init__(int(window_ns), int(min_support), 0, int(refractory_ns))
 
 
+class AddressFilter(C.Structure):
+    """esvio_fe_address_filter (include/esvio_fe.h: step 1a of the filter rule): roi = (x0, y0, x1, y1), inclusive;
+    polarity 0 both / 1 ON only / 2 OFF only; flatten 0 / 1 / 2; use_mask: reject the camera's masked pixels"""
+    _fields_ = [("roi_x0", C.c_uint16), ("roi_y0", C.c_uint16), ("roi_x1", C.c_uint16), ("roi_y1", C.c_uint16),
+                ("polarity", C.c_int32), ("flatten", C.c_int32), ("use_mask", C.c_int32), ("reserved", C.c_int32)]
+
+    def __init__(self, roi=(0, 0, 0, 0), polarity=0, flatten=0, use_mask=0):
+        super().__init__(int(roi[0]), int(roi[1]), int(roi[2]), int(roi[3]), int(polarity), int(flatten), int(use_mask), 0)
+
+
+class HotParams(C.Structure):
+    """esvio_fe_hot_params"""
+    _fields_ = [("max_pixels", C.c_uint32), ("min_count", C.c_uint32), ("min_rate_hz", C.c_uint32), ("mean_factor", C.c_uint32),
+                ("install", C.c_int32), ("reserved", C.c_int32)]
+
+    def __init__(self, max_pixels=8, min_count=1, min_rate_hz=0, mean_factor=0, install=False):
+        super().__init__(int(max_pixels), int(min_count), int(min_rate_hz), int(mean_factor), int(bool(install)), 0)
+
+
+class HotInfo(C.Structure):
+    """esvio_fe_hot_info"""
+    _fields_ = [("events", C.c_uint64), ("span_ns", C.c_uint64), ("threshold", C.c_uint64), ("above", C.c_uint32),
+                ("selected", C.c_uint32)]
+
+
 class Batch(C.Structure):
     """esvio_fe_batch"""
     _fields_ = [("left", C.c_void_p), ("right", C.c_void_p), ("left_fields", C.POINTER(EventFieldsDesc)),
@@ -167,11 +192,13 @@ ABI_SYMBOLS = [
     "esvio_fe_feed_close", "esvio_fe_feed_open", "esvio_fe_feed_peek", "esvio_fe_feed_push_events", "esvio_fe_feed_push_fields",
     "esvio_fe_feed_push_raw", "esvio_fe_feed_track",
     "esvio_fe_fast_corners", "esvio_fe_filter_batch", "esvio_fe_filter_events", "esvio_fe_filter_reset", "esvio_fe_features_to_track", "esvio_fe_features_to_track_fast", "esvio_fe_find_fundamental_mat", "esvio_fe_finish", "esvio_fe_get_sae",
-    "esvio_fe_get_time_surface", "esvio_fe_good_features_to_track", "esvio_fe_import_image", "esvio_fe_is_corner",
+    "esvio_fe_get_pixel_mask", "esvio_fe_get_time_surface", "esvio_fe_good_features_to_track", "esvio_fe_hot_learn",
+    "esvio_fe_hot_reset", "esvio_fe_hot_select", "esvio_fe_import_image", "esvio_fe_is_corner",
     "esvio_fe_last_error", "esvio_fe_mem_alloc", "esvio_fe_mem_free", "esvio_fe_mem_upload",
     "esvio_fe_pack_track_records", "esvio_fe_register_host_buffer", "esvio_fe_reserve", "esvio_fe_reset",
     "esvio_fe_sae_plane_doubles", "esvio_fe_sae_slice_apply", "esvio_fe_sae_slice_commit",
-    "esvio_fe_sae_slice_last", "esvio_fe_sae_to_time_surface", "esvio_fe_set_auto_exchange", "esvio_fe_set_detector",
+    "esvio_fe_sae_slice_last", "esvio_fe_sae_to_time_surface", "esvio_fe_set_address_filter", "esvio_fe_set_auto_exchange",
+    "esvio_fe_set_detector", "esvio_fe_set_pixel_mask",
     "esvio_fe_set_host_threads", "esvio_fe_set_launch_thread", "esvio_fe_set_lazy_new_stereo",
     "esvio_fe_set_next_batch", "esvio_fe_set_next_batch_mc", "esvio_fe_slice_events", "esvio_fe_slice_flush",
     "esvio_fe_slice_reset", "esvio_fe_track_batch", "esvio_fe_track_event", "esvio_fe_track_event_fields",
@@ -287,6 +314,12 @@ def load_library(build_if_missing=True):
     L.esvio_fe_filter_reset.argtypes = [vp]
     L.esvio_fe_filter_batch.argtypes = [vp, i, vp, C.POINTER(EventFieldsDesc), sz, i, C.POINTER(FilterParams), vp, i,
                                         C.POINTER(C.c_uint64), vp, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.esvio_fe_set_address_filter.argtypes = [vp, i, C.POINTER(AddressFilter)]
+    L.esvio_fe_set_pixel_mask.argtypes = [vp, i, vp, sz]
+    L.esvio_fe_get_pixel_mask.argtypes = [vp, i, vp, sz, C.POINTER(sz)]
+    L.esvio_fe_hot_learn.argtypes = [vp, i, vp, C.POINTER(EventFieldsDesc), sz, i, C.POINTER(C.c_uint64)]
+    L.esvio_fe_hot_select.argtypes = [vp, i, C.POINTER(HotParams), vp, vp, sz, C.POINTER(HotInfo)]
+    L.esvio_fe_hot_reset.argtypes = [vp]
     L.esvio_fe_track_batch.argtypes = [vp, C.POINTER(Batch), C.POINTER(Tracks), C.POINTER(BatchInfo)]
     L.esvio_fe_track_event_filtered.argtypes = [vp, vp, sz, vp, sz, i, C.c_int64, i, i, C.POINTER(Tracks),
                                                 C.POINTER(C.c_uint64 * 2), C.POINTER(d)]
@@ -608,6 +641,58 @@ class FeatureTracker:
         k = int(nk.value)
         kept = FilteredEvents(dst, k, last[0] if k else None) if device else out[:k]
         return kept, flags, int(rej.value)
+
+    def set_address_filter(self, cam, address_filter):
+        """camera `cam`'s address stage (esvio_fe_set_address_filter): an AddressFilter, or None for none.  A setting:
+        it survives reset() and filter_reset() and runs wherever FilterParams run"""
+        self._hd.check(self._hd.L.esvio_fe_set_address_filter(
+            self._hd.h, int(cam), C.byref(address_filter) if address_filter is not None else None))
+
+    def set_pixel_mask(self, cam, xy):
+        """camera `cam`'s pixel mask: `xy` an (n, 2) array of (x, y) pairs; empty clears it"""
+        a = np.ascontiguousarray(np.asarray(xy, np.uint16).reshape(-1, 2))
+        self._hd.check(self._hd.L.esvio_fe_set_pixel_mask(self._hd.h, int(cam), _p(a) if len(a) else None, len(a)))
+
+    def pixel_mask(self, cam):
+        """camera `cam`'s masked pixels as an (n, 2) uint16 array of (x, y), in raster order"""
+        L, n = self._hd.L, C.c_size_t(0)
+        L.esvio_fe_get_pixel_mask(self._hd.h, int(cam), None, 0, C.byref(n))  # (the count; EINVAL when it is not 0)
+        out = np.zeros((n.value, 2), np.uint16)
+        if n.value:
+            self._hd.check(L.esvio_fe_get_pixel_mask(self._hd.h, int(cam), _p(out), n.value, C.byref(n)))
+        return out[:n.value]
+
+    def hot_learn(self, cam, ev, src_space=HOST):
+        """counts camera `cam`'s events per pixel (esvio_fe_hot_learn): `ev` as filter_batch takes it.  A BAD event in
+        the fields raises FrontendError with `.n_bad`; the other events of the call are counted"""
+        from .events import EventFields
+        L, bad = self._hd.L, C.c_uint64(0)
+        if isinstance(ev, EventFields):
+            desc = fields_desc(ev)
+            rc = L.esvio_fe_hot_learn(self._hd.h, int(cam), None, C.byref(desc), ev.n, src_space, C.byref(bad))
+        else:
+            ptr, n, space, keep = _events_arg(ev)
+            rc = L.esvio_fe_hot_learn(self._hd.h, int(cam), ptr, None, n, space, C.byref(bad))
+        if rc:
+            e = FrontendError("rc=%d: %s" % (rc, L.esvio_fe_last_error(self._hd.h).decode()))
+            e.n_bad = int(bad.value)
+            raise e
+
+    def hot_select(self, cam, params, cap=None):
+        """the hottest pixels of what camera `cam` has learned (esvio_fe_hot_select; params: a HotParams) ->
+        (xy (n, 2) uint16, counts uint32[n], HotInfo): count descending, then pixel index ascending"""
+        cap = int(params.max_pixels if cap is None else cap)
+        xy, counts, info = np.zeros((max(cap, 1), 2), np.uint16), np.zeros(max(cap, 1), np.uint32), HotInfo()
+        rc = self._hd.L.esvio_fe_hot_select(self._hd.h, int(cam), C.byref(params), _p(xy), _p(counts), cap, C.byref(info))
+        if rc:
+            e = FrontendError("rc=%d: %s" % (rc, self._hd.L.esvio_fe_last_error(self._hd.h).decode()))
+            e.info = info
+            raise e
+        return xy[:info.selected].copy(), counts[:info.selected].copy(), info
+
+    def hot_reset(self):
+        """hot-pixel learning: nothing counted, both cameras"""
+        self._hd.check(self._hd.L.esvio_fe_hot_reset(self._hd.h))
 
     def track_batch(self, left, right, cur_time=None, pub=True, params=None, measurements=None, copy=True, src_space=HOST):
         """one batch through esvio_fe_track_batch: left / right are numpy EVENT_DTYPE arrays, (device_ptr, n) tuples or

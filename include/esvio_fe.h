@@ -524,6 +524,79 @@ int esvio_fe_track_event_filtered(esvio_fe_handle h, const esvio_fe_event* left,
                                   int min_support, int pub_this_frame, esvio_fe_tracks* out,
                                   uint64_t kept[2], double* cur_time_out);
 
+/* ---- the sensors' address filters and hot-pixel learning, on the device -------------------- */
+/* The filter block the reference's drivers program into the camera has more members than the two above
+ * (dependences/rpg_dvs_ros/davis_ros_driver/cfg/DAVIS_ROS_Driver.cfg:26-64, src/driver.cpp:403-488;
+ * dvxplorer_ros_driver/cfg/DVXplorer_ROS_Driver.cfg:34-46): a pixel filter (eight silenced addresses, with
+ * pixel_auto_train, "automatic filtering of 8 most active pixels"), a region of interest, polarity suppress / flatten.
+ * Like the filter itself they are FPGA / sensor logic: there is nothing of the reference to be equal to, THIS TEXT IS
+ * THE SPECIFICATION, the kernels equal its sequential reading (tests/addr_filter_ref.py) exactly.  Integers only.
+ *
+ * THE ADDRESS STAGE — step 1a of the filter rule above, between its steps 1 and 2.  An in-sensor event of camera cam
+ * is REJECTED exactly as in step 1 (counted in *n_rejected, flag 0, not emitted, it NEITHER READS NOR WRITES B) when
+ * the camera has an address filter and any of these holds: it lies outside the ROI; use_mask is set and its pixel is
+ * in the camera's pixel mask; its polarity is suppressed.  A masked hot pixel therefore supports no neighbour and
+ * stamps nothing — the difference from filtering first and dropping afterwards.  Steps 2-5 are unchanged.  A kept
+ * record is copied whole as before, except that with flatten != 0 its byte 12 (the polarity) is 1 or 0; last_kept
+ * shows the flattened record; in the fields form the record is built as esvio_fe_convert_events builds it, then its
+ * polarity is replaced.
+ * The stage runs wherever esvio_fe_filter_params run: esvio_fe_filter_events, esvio_fe_filter_batch (records and
+ * fields), esvio_fe_track_event_filtered, esvio_fe_track_batch, esvio_fe_track_raw with a filter, the feed with a
+ * filter.  {0, 0, 0, 0} filter parameters (no support test, no refractory test) give the address stage alone; with
+ * filter == NULL nothing runs.
+ * The filter and the mask are SETTINGS, like esvio_fe_set_detector's: they survive esvio_fe_reset and
+ * esvio_fe_filter_reset.  A fresh handle has neither and allocates nothing for them; the mask is width*height bits per
+ * camera, allocated by the first esvio_fe_set_pixel_mask call (or the first installing esvio_fe_hot_select).  use_mask
+ * with no mask set rejects nothing.
+ * ESVIO_FE_EINVAL with a message, before any device work, nothing changed: a ROI outside the sensor or inverted,
+ * polarity or flatten outside 0..2, use_mask outside 0..1, reserved != 0, cam outside 0..1, a mask pair outside the
+ * sensor, a null xy with n > 0. */
+typedef struct esvio_fe_address_filter {
+  uint16_t roi_x0, roi_y0, roi_x1, roi_y1; /* INCLUSIVE, as the drivers' start/end; x0<=x1<width, y0<=y1<height */
+  int32_t polarity;  /* 0 both; 1 ON only; 2 OFF only.  ON = polarity byte != 0 */
+  int32_t flatten;   /* 0 no; 1: kept records get polarity 1; 2: polarity 0.  Applied after suppression */
+  int32_t use_mask;  /* 0 / 1: reject events of pixels in the camera's pixel mask */
+  int32_t reserved;  /* 0 */
+} esvio_fe_address_filter;                       /* 24 bytes */
+int esvio_fe_set_address_filter(esvio_fe_handle h, int cam, const esvio_fe_address_filter* a); /* NULL: none */
+int esvio_fe_set_pixel_mask(esvio_fe_handle h, int cam, const uint16_t* xy, size_t n);          /* host, n (x,y) pairs; n == 0 clears */
+int esvio_fe_get_pixel_mask(esvio_fe_handle h, int cam, uint16_t* xy, size_t cap, size_t* n);   /* raster order; *n = pixels set, also when > cap (then EINVAL) */
+
+/* HOT-PIXEL LEARNING.  Per camera: a count plane C[width*height] (uint32), N = the number of events counted, t_min
+ * and t_max in integer ns (step 2's t) over the counted events.  Allocated by the first call.
+ * esvio_fe_hot_learn: every in-sensor event does C[pixel] += 1; out-of-sensor events are ignored; the address stage
+ * is NOT applied: learning sees the stream as it arrives.  Sources are esvio_fe_filter_batch's: records in host or
+ * device memory, or fields in their three spaces (exactly one of ev / fields when n > 0).  A BAD event (the fields
+ * form, by conversion's test) is not counted, every other event of the call is, and the call returns ESVIO_FE_EINVAL
+ * with *n_bad (optional) exact.  A call that would take N to 2^32 or beyond is refused before any device work.  The
+ * state is stream state: esvio_fe_hot_reset and esvio_fe_reset clear it, esvio_fe_filter_reset does not.
+ * esvio_fe_hot_select, all in integers: span = t_max - t_min (0 while N == 0);
+ *   T = max(min_count, min_rate_hz ? ceil(min_rate_hz * span / 10^9) : 0, mean_factor ? ceil(mean_factor * N / P) : 0),
+ * P = width*height.  The hot pixels are those with C >= T, ordered by COUNT DESCENDING, THEN PIXEL INDEX y*width + x
+ * ASCENDING; the first max_pixels are selected.  xy (host, optional, cap (x,y) pairs) and counts (host, optional, cap
+ * values) receive them in that order; info (optional): events = N, span_ns, threshold = T, above = pixels with
+ * C >= T, selected.  With install the selection becomes the camera's pixel mask, replacing it.  min_rate_hz > 0 with
+ * span > 2^42 is ESVIO_FE_EINVAL; selected > cap with a non-null xy or counts is ESVIO_FE_EINVAL, nothing is
+ * installed, info is filled.  N == 0 succeeds with nothing selected (with install: the empty mask).  The state is not
+ * consumed: learning may go on and select may be called again.  The selection sorts on the device (the stage's own
+ * scratch, allocated on first use, main stream only); the sort's bounded wait gives ESVIO_FE_EINTERNAL.
+ * Both calls order themselves on the main stream and wait for their own result; they touch nothing of the tracker and
+ * nothing of the filter's planes. */
+int esvio_fe_hot_learn(esvio_fe_handle h, int cam, const esvio_fe_event* ev, const esvio_fe_event_fields* fields,
+                       size_t n, int space, uint64_t* n_bad);
+typedef struct esvio_fe_hot_params {
+  uint32_t max_pixels;  /* 1..4096 */
+  uint32_t min_count;   /* >= 1 */
+  uint32_t min_rate_hz; /* 0: unused; <= 2^20 */
+  uint32_t mean_factor; /* 0: unused; <= 2^20: a pixel must hold at least mean_factor times the mean count per pixel */
+  int32_t install;      /* != 0: the selection becomes the camera's pixel mask (replacing it) */
+  int32_t reserved;     /* 0 */
+} esvio_fe_hot_params;
+typedef struct esvio_fe_hot_info { uint64_t events, span_ns, threshold; uint32_t above, selected; } esvio_fe_hot_info;
+int esvio_fe_hot_select(esvio_fe_handle h, int cam, const esvio_fe_hot_params* prm, uint16_t* xy, uint32_t* counts,
+                        size_t cap, esvio_fe_hot_info* info);
+int esvio_fe_hot_reset(esvio_fe_handle h);
+
 /* ---- one batch call: records or fields, filtered or not, plain or motion-compensated ------ */
 /* Every combination of {records, fields} per camera x {no filter, filter} x {plain, motion-compensated} through one
  * call; esvio_fe_track_event_fields and esvio_fe_track_event_filtered are this call with their arguments. */

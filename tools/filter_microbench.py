@@ -18,6 +18,21 @@ blocks of REPS calls after a warm-up block, min - max.  Behind the timed blocks,
 times of the fields form's chain.
 
     timeout -k 10 600 python tools/filter_microbench.py --fields [--json out.json]
+
+--address: the address stage (esvio_fe_set_address_filter).  esvio_fe_filter_batch on records and on the separate
+arrays above, device memory into device memory, call wall times, block after block in turn in one process: without a
+stage, with a stage that rejects nothing (the whole sensor as ROI, use_mask with an empty mask) and with the stream's
+eight most active pixels learned, installed and masked — and, with --other LIB, the same calls without a stage through
+another build of the library (the parent commit's, say) in the same turn.  Behind the timed blocks, with the timers on,
+the per-launch times of the chain with the stage that rejects nothing.
+
+--hot: esvio_fe_hot_learn's k_hot_count per launch beside k_sae_keys (the filter's keys kernel, which reads the same 16
+bytes per event) on the same events: the scene stream, the uniform stream, and the uniform stream with 1 % of its
+events on eight pixels (and one with every other event on one pixel); records and fields.  With --other LIB the same launch of another build beside it (a build
+without the in-wave combining, say).
+
+    timeout -k 10 600 python tools/filter_microbench.py --address [--other LIB] [--only C3] [--json out.json]
+    timeout -k 10 600 python tools/filter_microbench.py --hot [--other LIB] [--only C3] [--json out.json]
 """
 import ctypes as C
 import json
@@ -210,5 +225,159 @@ def main():
             json.dump(rows, fo, indent=1)
 
 
+def other_tracker(path, cfg):
+    """a handle of another build of the library in this process (its entry points called with this build's
+    argument types; what it lacks is not called)"""
+    cur = FE.load_library()
+    other = C.CDLL(path)
+    for name in FE.ABI_SYMBOLS + FE.TEST_SYMBOLS:
+        fn = getattr(other, name, None)
+        if fn is not None:
+            fn.argtypes, fn.restype = getattr(cur, name).argtypes, getattr(cur, name).restype
+    FE._lib = other
+    try:
+        return FE.FeatureTracker(cfg)
+    finally:
+        FE._lib = cur
+
+
+def sizes():
+    only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else None
+    return [s for s in SIZES if only in (None, s[0])]
+
+
+def turns(calls):
+    """calls: {name: (callable, what runs untimed in front of every call)}, block after block in turn ->
+    {name: wall us per call (median, min, max)}"""
+    wall = {k: [] for k in calls}
+    for b in range(BLOCKS + 1):  # (block 0: the warm-up)
+        for k, (call, between) in calls.items():
+            t = 0.0
+            for _ in range(REPS):
+                between()
+                t0 = time.perf_counter()
+                call()
+                t += time.perf_counter() - t0
+            if b:
+                wall[k].append(t / REPS * 1e6)
+    return {k: med(v) for k, v in wall.items()}
+
+
+def batch_caller(tr, n, dst, prm, ev=None, desc=None):
+    L, nk, rej, bad = tr._hd.L, C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+
+    def call():
+        assert L.esvio_fe_filter_batch(tr._hd.h, 0, ev, C.byref(desc) if desc is not None else None, n, FE.DEVICE, C.byref(prm), dst,
+                                       FE.DEVICE, C.byref(nk), None, None, C.byref(rej), C.byref(bad)) == 0
+    return call, nk, rej
+
+
+def main_address():
+    L = FE.load_library()
+    other_path = sys.argv[sys.argv.index("--other") + 1] if "--other" in sys.argv else None
+    rows = []
+    for tag, w, h, n_target in sizes():
+        cfg = FE.make_config(w, h)
+        tr = {"no stage": FE.FeatureTracker(cfg), "stage, rejects nothing": FE.FeatureTracker(cfg), "stage, 8 pixels masked": FE.FeatureTracker(cfg)}
+        if other_path:
+            tr = dict([("other build, no stage", other_tracker(other_path, cfg))] + list(tr.items()))
+        full = FE.AddressFilter((0, 0, w - 1, h - 1), use_mask=1)
+        tr["stage, rejects nothing"].set_pixel_mask(0, [])
+        tr["stage, rejects nothing"].set_address_filter(0, full)
+        tr["stage, 8 pixels masked"].set_address_filter(0, full)
+        for name, ev in streams(w, h, n_target):
+            n = len(ev)
+            src = FE.EventBuffer(ev, FE.DEVICE)
+            fields, blk = device_fields(L, ev)
+            desc = FE.fields_desc(fields)
+            dst = C.c_void_p()
+            assert L.esvio_fe_mem_alloc(FE.DEVICE, 16 * n, C.byref(dst)) == 0
+            prm = FE.FilterParams(WINDOW_NS, MIN_SUPPORT, 0)
+            hot = tr["stage, 8 pixels masked"]
+            hot.hot_reset()
+            hot.hot_learn(0, src.arg)
+            xy, cnt, info = hot.hot_select(0, FE.HotParams(max_pixels=8, min_count=1, install=True))
+            print("%s %dx%d %-8s n %8d; the 8 most active pixels hold %s" % (tag, w, h, name, n, cnt.tolist()))
+            row = dict(batch=tag, width=w, height=h, stream=name, n=n, masked_counts=cnt.tolist())
+            for form, kw in (("records", dict(ev=C.c_void_p(src.arg[0]))), ("fields", dict(desc=desc))):
+                calls, outs = {}, {}
+                for k, t in tr.items():
+                    call, nk, rej = batch_caller(t, n, dst, prm, **kw)
+                    calls[k], outs[k] = (call, t.filter_reset), (nk, rej)
+                wall = turns(calls)
+                base = wall.get("other build, no stage", wall["no stage"])
+                for k in calls:
+                    print("  %-7s %-24s call %9.1f us (%.1f - %.1f)  %.3f of the first row, whose own spread is %.1f us; kept %d, rejected %d"
+                          % ((form, k) + wall[k] + (wall[k][0] / base[0], base[2] - base[1], outs[k][0].value, outs[k][1].value)))
+                assert outs["no stage"][0].value == outs["stage, rejects nothing"][0].value
+                chain = ("k_baf_keys_addr",) + FILTER_CHAIN[1:] if form == "records" else FIELDS_CHAIN
+                per, _, tot = measure(tr["stage, rejects nothing"], calls["stage, rejects nothing"][0], chain, between=tr["stage, rejects nothing"].filter_reset)
+                ref_chain = FILTER_CHAIN if form == "records" else FIELDS_CHAIN
+                per0, _, tot0 = measure(tr["no stage"], calls["no stage"][0], ref_chain, between=tr["no stage"].filter_reset)
+                for (k, (us, launches, nbytes)), (k0, (us0, _, _)) in zip(per.items(), per0.items()):
+                    print("    %-18s %9.1f us (%.1f - %.1f) | no stage: %-18s %9.1f us (%.1f - %.1f)" % ((k,) + us + (k0,) + us0))
+                row[form] = dict(call_us=wall, stage_launch_us={k: v[0] for k, v in per.items()}, no_stage_launch_us={k: v[0] for k, v in per0.items()})
+            rows.append(row)
+            src.free()
+            for p in (blk, dst):
+                L.esvio_fe_mem_free(FE.DEVICE, p)
+        for t in tr.values():
+            t.close()
+    if "--json" in sys.argv:
+        with open(sys.argv[sys.argv.index("--json") + 1], "w") as fo:
+            json.dump(rows, fo, indent=1)
+
+
+def main_hot():
+    L = FE.load_library()
+    other_path = sys.argv[sys.argv.index("--other") + 1] if "--other" in sys.argv else None
+    rows = []
+    for tag, w, h, n_target in sizes():
+        cfg = FE.make_config(w, h)
+        tr = {"this build": FE.FeatureTracker(cfg)}
+        if other_path:
+            tr["other build"] = other_tracker(other_path, cfg)
+        sts = list(streams(w, h, n_target))
+        piled = sts[1][1].copy()
+        rng = np.random.default_rng(13)
+        idx = rng.choice(len(piled), len(piled) // 100, replace=False)
+        piled["x"][idx] = 17 + 40 * rng.integers(0, 8, len(idx))
+        piled["y"][idx] = 23
+        sts.append(("1% on 8", piled))
+        pile = sts[1][1].copy()  # (beyond the three streams above: every other event on ONE pixel, a pile the combining is for)
+        pile["x"][::2], pile["y"][::2] = 20, 20
+        sts.append(("50% on 1", pile))
+        for name, ev in sts:
+            n = len(ev)
+            src = FE.EventBuffer(ev, FE.DEVICE)
+            fields, blk = device_fields(L, ev)
+            dst = C.c_void_p()
+            assert L.esvio_fe_mem_alloc(FE.DEVICE, 16 * n, C.byref(dst)) == 0
+            print("%s %dx%d %-8s n %8d" % (tag, w, h, name, n))
+            row = dict(batch=tag, width=w, height=h, stream=name, n=n)
+            for k, t in tr.items():
+                call, nk, rej = batch_caller(t, n, dst, FE.FilterParams(WINDOW_NS, MIN_SUPPORT, 0), ev=C.c_void_p(src.arg[0]))
+                keys = measure(t, call, ("k_sae_keys",), between=t.filter_reset)[0]["k_sae_keys"][0]
+                rec = measure(t, lambda: t.hot_learn(0, src.arg), ("k_hot_count",), between=t.hot_reset)[0]["k_hot_count"][0]
+                fld = measure(t, lambda: t.hot_learn(0, fields, src_space=FE.DEVICE), ("k_hot_count",), between=t.hot_reset)[0]["k_hot_count"][0]
+                print("  %-11s k_sae_keys %8.1f us (%.1f - %.1f) | k_hot_count records %8.1f us (%.1f - %.1f) = %6.0f Mev/s | fields %8.1f us (%.1f - %.1f)"
+                      % ((k,) + keys + rec + (n / rec[0],) + fld))
+                row[k] = dict(k_sae_keys_us=keys, k_hot_count_records_us=rec, k_hot_count_fields_us=fld)
+            rows.append(row)
+            src.free()
+            for p in (blk, dst):
+                L.esvio_fe_mem_free(FE.DEVICE, p)
+        for t in tr.values():
+            t.close()
+    if "--json" in sys.argv:
+        with open(sys.argv[sys.argv.index("--json") + 1], "w") as fo:
+            json.dump(rows, fo, indent=1)
+
+
 if __name__ == "__main__":
-    main_fields() if "--fields" in sys.argv else main()
+    if "--address" in sys.argv:
+        main_address()
+    elif "--hot" in sys.argv:
+        main_hot()
+    else:
+        main_fields() if "--fields" in sys.argv else main()
