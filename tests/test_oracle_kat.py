@@ -6,6 +6,8 @@ import pytest
 
 from esvio_amd.events import event_times, make_events
 
+from arc_cases import arc_python as _arc_python  # the independent transcription of the ring loops
+
 
 def _ev(x, y, t_us, p):
     return make_events(np.atleast_1d(x), np.atleast_1d(y), np.atleast_1d(t_us), np.atleast_1d(p))
@@ -96,50 +98,6 @@ def test_time_surface_known_values(oracle):
 
 
 # ------------------------------------------------------------------ Arc* (event_detector.cc:308-544)
-def _arc_python(S, x, y):
-    """independent transcription of the reference loop, used only to cross-check the oracle"""
-    small = [(0, 3), (1, 3), (2, 2), (3, 1), (3, 0), (3, -1), (2, -2), (1, -3), (0, -3), (-1, -3),
-             (-2, -2), (-3, -1), (-3, 0), (-3, 1), (-2, 2), (-1, 3)]
-    large = [(0, 4), (1, 4), (2, 3), (3, 2), (4, 1), (4, 0), (4, -1), (3, -2), (2, -3), (1, -4),
-             (0, -4), (-1, -4), (-2, -3), (-3, -2), (-4, -1), (-4, 0), (-4, 1), (-3, 2), (-2, 3),
-             (-1, 4)]
-
-    def ring(c, kmin, kmax):
-        N = len(c)
-        v = [S[y + dy, x + dx] for dx, dy in c]
-        seg = v[0]
-        ri = 0
-        for i in range(1, N):
-            if v[i] > seg:
-                seg, ri = v[i], i
-        li = (ri - 1 + N) % N
-        ri = (ri + 1) % N
-        lv, rv = v[li], v[ri]
-        lmin, rmin = lv, rv
-        size = kmin
-        for it in range(1, N):
-            if rv > lv:
-                if it < kmin:
-                    seg = min(seg, rmin)
-                elif rv >= seg:
-                    size = it + 1
-                    seg = min(seg, rmin)
-                ri = (ri + 1) % N
-                rv = v[ri]
-                rmin = min(rmin, rv)
-            else:
-                if it < kmin:
-                    seg = min(seg, lmin)
-                elif lv >= seg:
-                    size = it + 1
-                    seg = min(seg, lmin)
-                li = (li - 1 + N) % N
-                lv = v[li]
-                lmin = min(lmin, lv)
-        return size <= kmax or (N - kmax <= size <= N - kmin)
-    return ring(small, 4, 6) and ring(large, 5, 8)
-
-
 def test_arc_star_hand_patterns(oracle):
     W, H = 64, 48
     Z = np.zeros((H, W))
