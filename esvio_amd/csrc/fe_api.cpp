@@ -2781,6 +2781,91 @@ int esvio_fe_features_to_track_fast(esvio_fe_handle c, const uint8_t* img, int s
   return 0;
 }
 
+// Test tap (include/esvio_fe_test.h): the handle's selection launch over a caller's candidate list.  Nothing of the
+// kernels is doubled here: the list goes into the current candidate set, the arguments through make_select_args /
+// launch_select_args like every other selection's.
+int esvio_fe_select_candidates(esvio_fe_handle c, const uint32_t* xy, const int32_t* payload, int n, double disc,
+                               int flags, const uint8_t* mask, const float* stamp_xy, int n_stamp, int max_corners,
+                               int out_base, int variant, float* out_xy, int32_t* out_idx, int32_t counts[3],
+                               int32_t* kernel_id) {
+  if (!c || !out_xy || !out_idx || !counts || n < 0 || n_stamp < 0 || (n && (!xy || !payload)) || (n_stamp && !stamp_xy))
+    return ESVIO_FE_EINVAL;
+  const int M = c->cfg.max_cnt;
+  if (flags & ~(ESVIO_FE_SELECT_EUCLID | ESVIO_FE_SELECT_TABLE))
+    return fail(c, ESVIO_FE_EINVAL, "select_candidates: unknown flag bits %d", flags);
+  if (variant < 0 || variant > 2) return fail(c, ESVIO_FE_EINVAL, "select_candidates: variant must be 0, 1 or 2 (got %d)", variant);
+  if (max_corners < 0 || out_base < 0 || max_corners > M || out_base > M - max_corners)
+    return fail(c, ESVIO_FE_EINVAL, "select_candidates: max_corners and out_base + max_corners must be in 0..max_cnt");
+  if (n_stamp > M) return fail(c, ESVIO_FE_EINVAL, "select_candidates: n_stamp > max_cnt");
+  const bool euclid = (flags & ESVIO_FE_SELECT_EUCLID) != 0;
+  if (!(disc >= 1) || disc > kMaxDiscR || (!euclid && disc != (double)(int)disc))
+    return fail(c, ESVIO_FE_EINVAL, "select_candidates: the disc must be an integer radius or a min_distance in [1, %d]", kMaxDiscR);
+  // (the kernels index the bitmap with a candidate's position, and the short stamp with a point's, unchecked)
+  for (int i = 0; i < n; i++)
+    if ((int)(xy[i] & 0xffffu) >= c->W || (int)(xy[i] >> 16) >= c->H)
+      return fail(c, ESVIO_FE_EINVAL, "select_candidates: candidate %d lies outside the sensor", i);
+  for (int i = 0; i < n_stamp; i++) {
+    const float px = stamp_xy[2 * i], py = stamp_xy[2 * i + 1];
+    if (!(px >= -0.5f && px < (float)c->W && py >= -0.5f && py < (float)c->H) || std::lrintf(px) >= c->W || std::lrintf(py) >= c->H)
+      return fail(c, ESVIO_FE_EINVAL, "select_candidates: stamp point %d does not round to a pixel of the sensor", i);
+  }
+  HIPCHK(c, hipSetDevice(c->dev));
+  if (!c->announced.empty() || !c->inflight.empty())
+    return fail(c, ESVIO_FE_EINVAL, "select_candidates while batches are announced");
+  if (c->pend_right.active)
+    if (int rc = finalize_lazy(c)) return rc;
+  if (variant == 2 && c->select_ok && !c->d_sel_bitmap)
+    if (int rc = c->d_sel_bitmap.alloc(c, (size_t)c->H * ((c->W + 31) / 32) + 4)) return rc;
+  const int set = c->cand_cur;
+  if (int rc = ensure_cand_capacity(c, set, (size_t)std::max(n, 1))) return rc;
+  const esvio_fe_ctx::CandSet& cs = c->cand[set];
+  hipStream_t s = cur_stream(c);
+  const uint32_t total = (uint32_t)n;
+  if (n) {
+    HIPCHK(c, hipMemcpyAsync(cs.comp_xy, xy, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(cs.comp_idx, payload, (size_t)n * 4, hipMemcpyHostToDevice, s));
+  }
+  HIPCHK(c, hipMemcpyAsync(cs.total, &total, 4, hipMemcpyHostToDevice, s));
+  // (the whole output goes up first and comes back whole: what the kernel leaves alone is the caller's own bytes)
+  HIPCHK(c, hipMemcpyAsync(c->d_ptsD, out_xy, (size_t)M * 8, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->d_sel_idx, out_idx, (size_t)M * 4, hipMemcpyHostToDevice, s));
+  const ResView &pin = c->pin[0], &zpin = c->zpin[0];
+  SelectArgs sa = make_select_args(c, set, max_corners, c->d_ptsD, out_base, c->d_sel_idx);
+  if (euclid) {
+    euclid_halfwidths(disc, sa.hw, &sa.radius);
+  } else {
+    const std::vector<int> hw = host::disc_halfwidths((int)disc);
+    sa.radius = (int)disc;
+    for (int i = 0; i <= kMaxDiscR; i++) sa.hw[i] = i < (int)hw.size() ? (int8_t)hw[i] : -1;
+  }
+  sa.disc_c = (flags & ESVIO_FE_SELECT_TABLE) ? -1 : disc_threshold(sa.hw, sa.radius);
+  if (mask) {
+    host::BitMask bm;
+    bm.reset(c->W, c->H);
+    bm.from_bytes(mask);
+    std::memcpy(pin.mask, bm.bits.data(), bm.bits.size() * 4);
+    HIPCHK(c, hipMemcpyAsync(c->d_mask_bits, pin.mask, bm.bits.size() * 4, hipMemcpyHostToDevice, s));
+    sa.init_bits = c->d_mask_bits;
+  }
+  if (n_stamp) {
+    std::memcpy(pin.news, stamp_xy, (size_t)n_stamp * 8);
+    sa.stamp_pts = (const float2*)zpin.news;
+    sa.n_stamp = n_stamp;
+  }
+  pin.counts[0] = pin.counts[1] = pin.counts[2] = -1;
+  sa.host_counts = zpin.counts;
+  if (variant == 1) sa.one_wave = 1;
+  if (variant == 2) sa.gbitmap = c->d_sel_bitmap;
+  const KernelId id = launch_select_args(c, sa);
+  HIPCHK(c, hipMemcpyAsync(out_xy, c->d_ptsD, (size_t)M * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(out_idx, c->d_sel_idx, (size_t)M * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  for (int i = 0; i < 3; i++) counts[i] = pin.counts[i];
+  if (kernel_id) *kernel_id = (int32_t)id;
+  if (c->prof_on) resolve_profile(c);
+  return 0;
+}
+
 int esvio_fe_track_image(esvio_fe_handle c, double cur_time, const uint8_t* img_left,
                          const uint8_t* img_right, int pub_this_frame, esvio_fe_tracks* out) {
   if (!c || !img_left) return ESVIO_FE_EINVAL;

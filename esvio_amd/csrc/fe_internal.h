@@ -88,7 +88,7 @@ void clear_tracker_state(esvio_fe_ctx* c);
 SelectArgs make_select_args(esvio_fe_ctx* c, int set, int max_corners, float2* out_pts, int out_base,
                             int32_t* out_idx);
 size_t select_lds_bytes(const esvio_fe_ctx* c);
-void launch_select_args(esvio_fe_ctx* c, SelectArgs s);
+KernelId launch_select_args(esvio_fe_ctx* c, SelectArgs s);  // (returns the form it launched)
 void compact_set(esvio_fe_ctx* c, const esvio_fe_ctx::CandSet& cs, uint32_t nblk, bool booked);
 void run_select(esvio_fe_ctx* c, int set, int max_corners, float2* out_pts, int out_base, int32_t* out_idx,
                 const uint32_t* mask_bits = nullptr, int* host_counts = nullptr, bool publish = false,

@@ -664,11 +664,14 @@ static size_t select_tables_lds_bytes(const esvio_fe_ctx* c) {  // with the bitm
 }
 
 // the greedy selection `s` describes, its bitmap in LDS or — where that does not fit (select_ok, esvio_fe_create:
-// d_sel_bitmap is there then) — in device memory: slower, same result
-void launch_select_args(esvio_fe_ctx* c, SelectArgs s) {
+// d_sel_bitmap is there then) — in device memory: slower, same result.  (A caller that has set s.gbitmap itself gets the
+// device-memory form on any handle: esvio_fe_select_candidates, test tap)
+KernelId launch_select_args(esvio_fe_ctx* c, SelectArgs s) {
   if (!c->select_ok) s.gbitmap = c->d_sel_bitmap;
   ScopedKernel k(c, K_SELECT_MW, 0);
-  k.id = launch_select(cur_stream(c), s, c->select_ok ? select_lds_bytes(c) : select_tables_lds_bytes(c));
+  const KernelId id = launch_select(cur_stream(c), s, s.gbitmap ? select_tables_lds_bytes(c) : select_lds_bytes(c));
+  k.id = id;
+  return id;
 }
 
 // ordered compaction of the first nblk per-block lists of `cs` (right behind the kernel that filled them).  booked: as

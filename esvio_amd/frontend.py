@@ -214,11 +214,13 @@ TEST_SYMBOLS = [
     "esvio_fe_host_stage_pack", "esvio_fe_staging_counters",
     "esvio_fe_kernel_count", "esvio_fe_kernel_name", "esvio_fe_latency_phase_name", "esvio_fe_latency_recent",
     "esvio_fe_latency_stats", "esvio_fe_lift_projective", "esvio_fe_plain_call_counters", "esvio_fe_ransac_stats",
-    "esvio_fe_ransac_tail", "esvio_fe_raw_tile_bytes", "esvio_fe_reset_kernel_stats", "esvio_fe_set_profiling", "esvio_fe_set_sae",
+    "esvio_fe_ransac_tail", "esvio_fe_raw_tile_bytes", "esvio_fe_reset_kernel_stats", "esvio_fe_select_candidates",
+    "esvio_fe_set_profiling", "esvio_fe_set_sae",
     "esvio_fe_slice_tile_events", "esvio_fe_stage_kernel_count", "esvio_fe_stream",
 ]
 
 LATENCY_PHASES = 16
+SELECT_EUCLID, SELECT_TABLE = 1, 2  # esvio_fe_select_candidates' flags (include/esvio_fe_test.h)
 
 
 class LatencyCall(C.Structure):  # esvio_fe_latency_call
@@ -306,6 +308,7 @@ def load_library(build_if_missing=True):
                                         C.POINTER(C.c_int32)]
     L.esvio_fe_set_detector.argtypes = [vp, i, i]
     L.esvio_fe_features_to_track_fast.argtypes = [vp, vp, i, i, i, vp, vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.esvio_fe_select_candidates.argtypes = [vp, vp, vp, i, d, i, vp, vp, i, i, i, i, vp, vp, vp, C.POINTER(C.c_int32)]
     L.esvio_fe_convert_events.argtypes = [vp, C.POINTER(EventFieldsDesc), sz, i, vp, i, C.POINTER(C.c_uint64)]
     L.esvio_fe_track_event_fields.argtypes = [vp, d, C.POINTER(EventFieldsDesc), sz, C.POINTER(EventFieldsDesc), sz, i, i,
                                               C.POINTER(Tracks)]
@@ -1231,6 +1234,38 @@ class FeatureTracker:
         self._hd.check(self._hd.L.esvio_fe_features_to_track(
             self._hd.h, ptr, n, space, int(maxCorners), _p(mask), _p(xy), _p(idx), C.byref(k)))
         return xy[:k.value].copy(), idx[:k.value].copy()
+
+    def select_candidates(self, xy, payload, disc, euclid=False, table=False, mask=None, stamp_pts=None, max_corners=None,
+                          out_base=0, variant=0, poison=None):
+        """test tap (esvio_fe_select_candidates, include/esvio_fe_test.h): the greedy min-distance selection over the
+        candidates xy (uint32 x | y << 16) with their int32 payloads.  disc: cv::circle's radius, or with euclid the
+        min_distance of the open Euclidean disc; table: membership by the half-width table; mask: (H, W) u8, 255 =
+        blocked; stamp_pts: float32 (k, 2) points whose discs are blocked; variant 0 / 1 / 2: the handle's kernel / the
+        one-wave kernel / the bitmap in device memory.  poison = (float, int): what the output arrays hold before the
+        call -> (out_xy float32 (max_cnt, 2), out_idx int32 (max_cnt), counts int32 (3), kernel name), the arrays WHOLE:
+        the accepted points are out_xy[out_base : out_base + counts[0]], their payloads out_idx[: counts[0]]"""
+        hd = self._hd
+        M = self.cfg.max_cnt
+        xy = np.ascontiguousarray(xy, np.uint32).reshape(-1)
+        payload = np.ascontiguousarray(payload, np.int32).reshape(-1)
+        if xy.size != payload.size:
+            raise ValueError("one payload per candidate")
+        st = None if stamp_pts is None else np.ascontiguousarray(stamp_pts, np.float32).reshape(-1, 2)
+        mk = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        if mk is not None and mk.shape != (self.cfg.height, self.cfg.width):
+            raise ValueError("mask must be (height, width) of the handle")
+        pf, pi = (0.0, 0) if poison is None else poison
+        out_xy = np.full((M, 2), pf, np.float32)
+        out_idx = np.full(M, pi, np.int32)
+        counts = np.zeros(3, np.int32)
+        kid = C.c_int32(-1)
+        flags = (SELECT_EUCLID if euclid else 0) | (SELECT_TABLE if table else 0)
+        hd.check(hd.L.esvio_fe_select_candidates(
+            hd.h, _p(xy) if xy.size else None, _p(payload) if xy.size else None, int(xy.size), float(disc), flags, _p(mk),
+            _p(st) if st is not None and len(st) else None, 0 if st is None else len(st),
+            M if max_corners is None else int(max_corners), int(out_base), int(variant), _p(out_xy), _p(out_idx), _p(counts),
+            C.byref(kid)))
+        return out_xy, out_idx, counts, hd.L.esvio_fe_kernel_name(kid.value).decode()
 
     def calcOpticalFlowPyrLK(self, prev_img, next_img, prev_pts, next_pts=None, maxLevel=3,
                              max_count=30, eps=0.01, flags=0):

@@ -3,7 +3,7 @@
  * NOT part of the drop-in boundary (include/esvio_fe.h): nothing here replaces a
  * call of the reference.  These entry points exist so that tests/ and bench.py can reach pieces of the host
  * side in isolation (the RANSAC pool under adverse scheduling, the staging copy, the 7-point solver's
- * null-space basis), inject faults into the bounded device-side waits, and read counters.  A caller of the
+ * null-space basis), run the min-distance selection over a list of their own, inject faults into the bounded device-side waits, and read counters.  A caller of the
  * front-end never needs them.
  */
 #ifndef ESVIO_FE_TEST_H
@@ -109,6 +109,33 @@ int esvio_fe_build_pyramid(esvio_fe_handle h, const uint8_t* img, int w, int hgt
  * a bad cam or level and while batches are announced or in flight; what a lazy call left open is completed first. */
 int esvio_fe_export_level(esvio_fe_handle h, int cam, int level, uint8_t* img, int16_t* deriv, int32_t* w,
                           int32_t* hgt, int32_t* levels);
+/* test tap: the greedy min-distance selection every detector ends in (Event_FeaturesToTrack, the FAST selection,
+ * goodFeaturesToTrack's distance pass, trackEvent / trackImage behind Event_setMask), over a caller's candidate list.
+ * The rule: seed a map of blocked pixels from `mask` (width*height bytes, 255 = blocked; may be NULL) and from the
+ * filled discs round the n_stamp points of stamp_xy (x, y float pairs, rounded like cvRound: to nearest, ties to even;
+ * may be NULL when n_stamp = 0); walk the n candidates in order; skip one whose pixel is blocked, else accept it and
+ * block the disc round it, clipped to the sensor; stop after max_corners.
+ *   xy[i] = x | y << 16, payload[i] comes back in out_idx for an accepted candidate.  n = 0 is valid.  Every candidate
+ *   must lie inside the sensor and every stamp point must round to a pixel of it, else ESVIO_FE_EINVAL: the kernels
+ *   index the map with them unchecked.
+ *   disc: cv::circle's filled disc of the integer radius `disc` in 1..63, or with ESVIO_FE_SELECT_EUCLID the open
+ *   Euclidean disc dx*dx + dy*dy < disc*disc of a min_distance in [1, 63] — per call, the handle's min_dist plays no
+ *   part.  ESVIO_FE_SELECT_TABLE: the kernels test membership with the half-width table where they would use the
+ *   equivalent threshold on dx*dx + dy*dy (which every disc of either kind has: no other caller takes the table path).
+ *   n_stamp <= max_cnt, 0 <= max_corners, 0 <= out_base, out_base + max_corners <= max_cnt.
+ *   variant 0: the kernel the handle launches for its own selections; 1: the one-wave kernel (as ESVIO_FE_SELECT_SERIAL);
+ *   2: the map in device memory even where it fits LDS (allocated on the first such call).
+ *   out_xy (max_cnt x, y pairs) and out_idx (max_cnt) are read AND written: they travel to the device whole, the
+ *   accepted points land at out_xy[out_base + k], their payloads at out_idx[k], and both travel back whole, so that a
+ *   caller sees what the kernel wrote outside these.  counts = {accepted, out_base + accepted, n}.  *kernel_id (may be
+ *   NULL): the kernel that ran, for esvio_fe_kernel_name.  Not while batches are announced; what a lazy call left open
+ *   is completed first.  Publication to a waiting LK launch (replay mode) is not part of the tap. */
+#define ESVIO_FE_SELECT_EUCLID 1
+#define ESVIO_FE_SELECT_TABLE 2
+int esvio_fe_select_candidates(esvio_fe_handle h, const uint32_t* xy, const int32_t* payload, int n, double disc,
+                               int flags, const uint8_t* mask, const float* stamp_xy, int n_stamp, int max_corners,
+                               int out_base, int variant, float* out_xy, int32_t* out_idx, int32_t counts[3],
+                               int32_t* kernel_id);
 /* camodocal PinholeCamera::liftProjective (PinholeCamera.cc:450-510); host-side. */
 int esvio_fe_lift_projective(const esvio_fe_camera* cam, double u, double v, double* out3);
 

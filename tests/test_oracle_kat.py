@@ -193,21 +193,9 @@ def test_disc_is_opencv_midpoint_circle(oracle):
 
 
 def test_midpoint_disc_r10_table(oracle):
-    """independent re-implementation of the midpoint recurrence, r = 10, 20, 30 (shipped min_dist)"""
-    def ref(r):
-        hw = [-1] * (r + 1)
-        err, dx, dy, plus, minus = 0, r, 0, 1, 2 * r - 1
-        while dx >= dy:
-            hw[dy] = max(hw[dy], dx)
-            hw[dx] = max(hw[dx], dy)
-            dy += 1
-            err += plus
-            plus += 2
-            if err > 0:
-                err -= minus
-                dx -= 1
-                minus -= 2
-        return hw
+    """independent re-implementation of the midpoint recurrence (tests/select_ref.py), r = 10, 20, 30 (shipped
+    min_dist)"""
+    from select_ref import midpoint_halfwidths as ref
     for r in (3, 10, 20, 30):
         assert list(oracle.disc_halfwidths(r)) == ref(r)
     # r=10: (dx,dy) visited = (10,0)(9,1)(9,2)(9,3)(9,4)(8,5)(8,6)(7,7); rows 8..10 get their width
