@@ -393,6 +393,7 @@ int esvio_fe_reset(esvio_fe_handle c) {
   if (int rc = baf_clear(c)) return rc;  // the background-activity filter's planes: none everywhere
   if (int rc = hot_clear(c)) return rc;  // hot-pixel learning: nothing counted (the address filter and the mask are settings: kept)
   c->rawdec.st[0] = c->rawdec.st[1] = esvio_fe_ctx::Raw::State();  // the raw-stream decoder: the fresh state
+  c->rawdec.trig_st[0] = c->rawdec.trig_st[1] = esvio_fe_ctx::Raw::State();  // ... and the trigger decoder's
   c->slice.st[0] = c->slice.st[1] = esvio_fe_ctx::Slice::State();  // the stream slicer: no event seen, no window closed
   HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
   feed_empty(c, true);  // an open feed: no records, no windows (it stays open); every stream is idle here
@@ -1823,20 +1824,21 @@ struct RawJob {  // one camera's part of a call
   size_t cap = 0;
 };
 
+size_t raw_word_bytes(int format) { return format == ESVIO_FE_RAW_EVT3 ? 2 : format == ESVIO_FE_RAW_EVT21 ? 8 : 4; }
 int raw_args_check(esvio_fe_ctx* c, const char* who, int format, const void* words, size_t n_bytes, int space, int64_t t_offset_us) {
-  if (format != ESVIO_FE_RAW_EVT2 && format != ESVIO_FE_RAW_EVT3)
-    return fail(c, ESVIO_FE_EINVAL, "%s: format must be ESVIO_FE_RAW_EVT2 or ESVIO_FE_RAW_EVT3 (got %d)", who, format);
+  if (format != ESVIO_FE_RAW_EVT2 && format != ESVIO_FE_RAW_EVT3 && format != ESVIO_FE_RAW_EVT21)
+    return fail(c, ESVIO_FE_EINVAL, "%s: format must be ESVIO_FE_RAW_EVT2, ESVIO_FE_RAW_EVT3 or ESVIO_FE_RAW_EVT21 (got %d)", who, format);
   if (space != ESVIO_FE_HOST && space != ESVIO_FE_DEVICE) return fail(c, ESVIO_FE_EINVAL, "%s: bad memory space", who);
   const int64_t lim = (int64_t)1 << 62;
   if (t_offset_us > lim || t_offset_us < -lim) return fail(c, ESVIO_FE_EINVAL, "%s: |t_offset_us| must be <= 2^62", who);
-  const size_t wb = format == ESVIO_FE_RAW_EVT3 ? 2 : 4;
+  const size_t wb = raw_word_bytes(format);
   if (n_bytes % wb) return fail(c, ESVIO_FE_EINVAL, "%s: %zu bytes are no whole number of %zu-byte words", who, n_bytes, wb);
   if (n_bytes > kRawMaxBytes) return fail(c, ESVIO_FE_EINVAL, "%s: a chunk holds at most 2^28 bytes", who);
   if (n_bytes && !words) return fail(c, ESVIO_FE_EINVAL, "%s: words is null", who);
   return 0;
 }
 size_t raw_bound(int format, size_t n_bytes) {  // the records n_bytes of words can stand for at most
-  return format == ESVIO_FE_RAW_EVT3 ? n_bytes / 2 * 12 : n_bytes / 4;
+  return format == ESVIO_FE_RAW_EVT3 ? n_bytes / 2 * 12 : format == ESVIO_FE_RAW_EVT21 ? n_bytes * 4 : n_bytes / 4;
 }
 uint32_t raw_tiles(size_t n_bytes) { return (uint32_t)((n_bytes + kRawTileBytes - 1) / kRawTileBytes); }
 
@@ -1855,8 +1857,9 @@ int raw_ensure(esvio_fe_ctx* c, int cam, size_t n_bytes, bool copied_src, size_t
 
 // Enqueue the decode chain of one camera (job[1].n_bytes == 0) or of both on the current stream, and the copies that
 // bring the result blocks to the host; nothing is waited for.  *args: what the emit launch can be repeated with.
+// trig: the trigger chain — the cameras' trigger-decoder states, its own reduce and emit launches around the same scan.
 int raw_enqueue(esvio_fe_ctx* c, int format, int space, int64_t t_offset_us, const RawJob job[2], const int cam_of[2], RawArgs* args,
-                RawResult res[2]) {
+                RawResult res[2], bool trig = false) {
   esvio_fe_ctx::Raw& r = c->rawdec;
   hipStream_t s = cur_stream(c);
   RawArgs a{};
@@ -1876,7 +1879,7 @@ int raw_enqueue(esvio_fe_ctx* c, int format, int space, int64_t t_offset_us, con
       }
     }
     if (int rc = raw_ensure(c, cam, job[k].n_bytes, false, 0)) return rc;
-    const esvio_fe_ctx::Raw::State& st = r.st[cam];
+    const esvio_fe_ctx::Raw::State& st = trig ? r.trig_st[cam] : r.st[cam];
     RawCam& rc = a.cam[k];
     rc.words = d_words, rc.n_bytes = (uint32_t)job[k].n_bytes, rc.tiles = raw_tiles(job[k].n_bytes);
     rc.seed = RawXf{st.th, st.th, 0, (st.seen ? kRawHasTh : 0u) | kRawHasTl | kRawHasY | kRawHasBx | (st.bp ? kRawBp : 0u) |
@@ -1885,19 +1888,26 @@ int raw_enqueue(esvio_fe_ctx* c, int format, int space, int64_t t_offset_us, con
     rc.wraps_base = st.wraps, rc.t_offset = t_offset_us;
     rc.sums = r.sums[cam], rc.dst = job[k].d_dst, rc.dst_cap = (uint32_t)std::min<size_t>(job[k].cap, 0xffffffffu);
     rc.res = r.res + cam;
-    bytes += job[k].n_bytes, cap_bytes += std::min(job[k].cap, raw_bound(format, job[k].n_bytes)) * 16;
+    bytes += job[k].n_bytes;
+    cap_bytes += std::min(job[k].cap, trig ? job[k].n_bytes / raw_word_bytes(format) : raw_bound(format, job[k].n_bytes)) * 16;
   }
   {
-    ScopedKernel k(c, K_RAW_REDUCE, bytes + (uint64_t)(a.cam[0].tiles + a.cam[1].tiles) * sizeof(RawXf));
-    launch_raw_reduce(s, a);
+    ScopedKernel k(c, trig ? K_TRIG_REDUCE : K_RAW_REDUCE, bytes + (uint64_t)(a.cam[0].tiles + a.cam[1].tiles) * sizeof(RawXf));
+    if (trig)
+      launch_trig_reduce(s, a);
+    else
+      launch_raw_reduce(s, a);
   }
   {
     ScopedKernel k(c, K_RAW_SCAN, (uint64_t)(a.cam[0].tiles + a.cam[1].tiles) * 2 * sizeof(RawXf));
     launch_raw_scan(s, a);
   }
   {  // (booked as if every record the buffers have room for were written: the count is not known here)
-    ScopedKernel k(c, K_RAW_EMIT, bytes + cap_bytes);
-    launch_raw_emit(s, a);
+    ScopedKernel k(c, trig ? K_TRIG_EMIT : K_RAW_EMIT, bytes + cap_bytes);
+    if (trig)
+      launch_trig_emit(s, a);
+    else
+      launch_raw_emit(s, a);
   }
   for (int k = 0; k < 2; k++)
     if (job[k].n_bytes) HIPCHK(c, hipMemcpyAsync(&res[k], a.cam[k].res, sizeof(RawResult), hipMemcpyDeviceToHost, s));
@@ -1905,7 +1915,7 @@ int raw_enqueue(esvio_fe_ctx* c, int format, int space, int64_t t_offset_us, con
   return 0;
 }
 // the emit launch again, into buffers that have room now (the tiles' prefixes are still where the scan left them)
-int raw_emit_again(esvio_fe_ctx* c, RawArgs* a, const RawJob job[2], RawResult res[2]) {
+int raw_emit_again(esvio_fe_ctx* c, RawArgs* a, const RawJob job[2], RawResult res[2], bool trig = false) {
   hipStream_t s = cur_stream(c);
   for (int k = 0; k < 2; k++) {
     if (!job[k].n_bytes) continue;
@@ -1913,8 +1923,11 @@ int raw_emit_again(esvio_fe_ctx* c, RawArgs* a, const RawJob job[2], RawResult r
     HIPCHK(c, hipMemsetAsync((uint8_t*)a->cam[k].res + offsetof(RawResult, bad), 0, sizeof(unsigned long long), s));
   }
   {
-    ScopedKernel k(c, K_RAW_EMIT, (uint64_t)(res[0].events + res[1].events) * 16);
-    launch_raw_emit(s, *a);
+    ScopedKernel k(c, trig ? K_TRIG_EMIT : K_RAW_EMIT, (uint64_t)(res[0].events + res[1].events) * 16);
+    if (trig)
+      launch_trig_emit(s, *a);
+    else
+      launch_raw_emit(s, *a);
   }
   for (int k = 0; k < 2; k++)
     if (job[k].n_bytes) HIPCHK(c, hipMemcpyAsync(&res[k], a->cam[k].res, sizeof(RawResult), hipMemcpyDeviceToHost, s));
@@ -1959,7 +1972,7 @@ int esvio_fe_decode_raw(esvio_fe_handle c, int cam, int format, const void* word
   job[0].words = words, job[0].n_bytes = n_bytes;
   job[0].d_dst = (EventRec*)dst, job[0].cap = std::min(dst_cap, bound);
   if (dst_space == ESVIO_FE_HOST) {  // the records behind a host dst: one per word to begin with, never more than dst has room for
-    const size_t want = std::min(job[0].cap, std::max<size_t>(c->rawdec.dec[cam].cap, n_bytes / (format == ESVIO_FE_RAW_EVT3 ? 2 : 4)));
+    const size_t want = std::min(job[0].cap, std::max<size_t>(c->rawdec.dec[cam].cap, n_bytes / raw_word_bytes(format)));
     if (int rc = raw_ensure(c, cam, n_bytes, false, want)) return rc;
     job[0].d_dst = c->rawdec.dec[cam], job[0].cap = std::min(job[0].cap, c->rawdec.dec[cam].cap);
   }
@@ -1994,6 +2007,136 @@ int esvio_fe_decode_raw(esvio_fe_handle c, int cam, int format, const void* word
 int esvio_fe_decode_reset(esvio_fe_handle c) {
   if (!c) return ESVIO_FE_EINVAL;
   c->rawdec.st[0] = c->rawdec.st[1] = esvio_fe_ctx::Raw::State();
+  c->rawdec.trig_st[0] = c->rawdec.trig_st[1] = esvio_fe_ctx::Raw::State();
+  return 0;
+}
+
+// ---- external triggers: the decode chain with the trigger classifier, the camera's trigger-decoder state (include/esvio_fe.h)
+static_assert(sizeof(esvio_fe_trigger) == sizeof(EventRec), "trigger records travel through the decode chain's 16-byte slots");
+int esvio_fe_decode_triggers(esvio_fe_handle c, int cam, int format, const void* words, size_t n_bytes, int space,
+                             int64_t t_offset_us, esvio_fe_trigger* dst, size_t dst_cap, esvio_fe_trigger_info* info) {
+  if (!c) return ESVIO_FE_EINVAL;
+  if (cam != 0 && cam != 1) return fail(c, ESVIO_FE_EINVAL, "decode_triggers: cam must be 0 or 1 (got %d)", cam);
+  esvio_fe_ctx::Raw::State& st = c->rawdec.trig_st[cam];
+  if (info) info->triggers = info->untimed = info->bad = 0, info->wraps = st.wraps;
+  if (int rc = raw_args_check(c, "decode_triggers", format, words, n_bytes, space, t_offset_us)) return rc;
+  if (dst_cap && !dst) return fail(c, ESVIO_FE_EINVAL, "decode_triggers: dst is null");
+  if (!n_bytes) return 0;
+  HIPCHK(c, hipSetDevice(c->dev));
+  const size_t bound = n_bytes / raw_word_bytes(format);  // one trigger per word at the most
+  // the records on the device: the stage's scratch, as large as it is to begin with (triggers are few), never more than dst has room for
+  if (int rc = raw_ensure(c, cam, n_bytes, false, std::max<size_t>(std::min(dst_cap, std::min<size_t>(bound, 4096)), 1))) return rc;
+  RawJob job[2];
+  job[0].words = words, job[0].n_bytes = n_bytes;
+  job[0].d_dst = c->rawdec.dec[cam], job[0].cap = std::min(std::min(dst_cap, bound), c->rawdec.dec[cam].cap);
+  const int cam_of[2] = {cam, cam};
+  RawArgs a;
+  RawResult r[2] = {};
+  if (int rc = raw_enqueue(c, format, space, t_offset_us, job, cam_of, &a, r, true)) return rc;
+  HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  if (!r[0].bad && r[0].events > job[0].cap && r[0].events <= dst_cap) {
+    if (int rc = raw_ensure(c, cam, n_bytes, false, r[0].events)) return rc;
+    job[0].d_dst = c->rawdec.dec[cam], job[0].cap = c->rawdec.dec[cam].cap;
+    if (int rc = raw_emit_again(c, &a, job, r, true)) return rc;
+    HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  }
+  if (c->prof_on) resolve_profile(c);
+  if (info) {
+    info->triggers = r[0].events, info->untimed = r[0].untimed, info->bad = r[0].bad;
+    if (r[0].events) info->first_t_us = r[0].first_t, info->last_t_us = r[0].last_t;
+  }
+  if (r[0].bad)
+    return fail(c, ESVIO_FE_EINVAL, "decode_triggers: %llu of %u triggers have a stamp outside [0, 2^32 s); the camera's trigger-decoder state is as it was",
+                r[0].bad, r[0].events);
+  if (r[0].events > dst_cap)
+    return fail(c, ESVIO_FE_EINVAL, "decode_triggers: the chunk holds %u triggers, dst has room for %zu; the camera's trigger-decoder state is as it was",
+                r[0].events, dst_cap);
+  if (r[0].events) {
+    HIPCHK(c, hipMemcpyAsync(dst, job[0].d_dst, (size_t)r[0].events * sizeof(esvio_fe_trigger), hipMemcpyDeviceToHost, cur_stream(c)));
+    HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  }
+  const RawXf& x = r[0].state;  // the call succeeded: the state is what the scan composed
+  st.seen = x.flags & kRawHasTh ? 1 : 0, st.th = x.th_last, st.wraps += x.wraps, st.tl = (x.flags >> kRawTlShift) & 0xfffu;
+  if (info) info->wraps = st.wraps;
+  return 0;
+}
+
+// ---- the .raw file's ASCII header (include/esvio_fe.h has the rule): host only
+namespace {
+// the text of a header line behind '%' and blanks, in front of "\n" / "\r\n"
+bool hdr_key(const char*& p, const char* end, const char* key) {
+  const size_t k = strlen(key);
+  if ((size_t)(end - p) < k || memcmp(p, key, k) != 0) return false;
+  if ((size_t)(end - p) > k && p[k] != ' ' && p[k] != '\t') return false;
+  p += k;
+  while (p < end && (*p == ' ' || *p == '\t')) p++;
+  return true;
+}
+int hdr_format(const char* p, const char* end) {  // "EVT2" / "EVT21" / "EVT3", "2.0" / "2.1" / "3.0": the whole token
+  const std::string t(p, end);
+  if (t == "EVT2" || t == "2.0") return ESVIO_FE_RAW_EVT2;
+  if (t == "EVT21" || t == "2.1") return ESVIO_FE_RAW_EVT21;
+  if (t == "EVT3" || t == "3.0") return ESVIO_FE_RAW_EVT3;
+  return 0;
+}
+bool hdr_int(const char* p, const char* end, int32_t* out) {  // decimal digits only, 1 .. 2^30
+  if (p == end) return false;
+  int64_t v = 0;
+  for (; p < end; p++) {
+    if (*p < '0' || *p > '9') return false;
+    v = v * 10 + (*p - '0');
+    if (v > (1 << 30)) return false;
+  }
+  *out = (int32_t)v;
+  return v > 0;
+}
+}  // namespace
+
+int esvio_fe_raw_header(const void* bytes, size_t n, esvio_fe_raw_header_info* out) {
+  if (!out || (n && !bytes)) return ESVIO_FE_EINVAL;
+  *out = esvio_fe_raw_header_info{};
+  const char* b = (const char*)bytes;
+  int evt_format = 0, fmt_format = 0;
+  size_t pos = 0;
+  bool ended = false;
+  while (!ended) {
+    if (pos == n) break;                   // behind a whole line that is not "% end" (or no byte at all): not known yet
+    if (b[pos] != '%') { ended = true; break; }
+    const char* nl = (const char*)memchr(b + pos, '\n', n - pos);
+    if (!nl) break;                        // inside a header line
+    const char* p = b + pos + 1;
+    const char* end = nl;
+    if (end > p && end[-1] == '\r') end--;
+    while (p < end && (*p == ' ' || *p == '\t')) p++;
+    while (end > p && (end[-1] == ' ' || end[-1] == '\t')) end--;
+    pos = (size_t)(nl - b) + 1;
+    if (end - p == 3 && memcmp(p, "end", 3) == 0) {
+      ended = true;
+    } else if (hdr_key(p, end, "evt")) {
+      if (int f = hdr_format(p, end)) evt_format = f;
+    } else if (hdr_key(p, end, "format")) {
+      const char* semi = (const char*)memchr(p, ';', (size_t)(end - p));
+      if (int f = hdr_format(p, semi ? semi : end)) fmt_format = f;
+      while (semi) {  // ;key=value
+        const char* k = semi + 1;
+        semi = (const char*)memchr(k, ';', (size_t)(end - k));
+        const char* ke = semi ? semi : end;
+        const char* eq = (const char*)memchr(k, '=', (size_t)(ke - k));
+        if (!eq) continue;
+        const std::string key(k, eq);
+        int32_t v;
+        if (key == "width" && hdr_int(eq + 1, ke, &v)) out->width = v;
+        if (key == "height" && hdr_int(eq + 1, ke, &v)) out->height = v;
+      }
+    } else if (hdr_key(p, end, "geometry")) {
+      const char* x = (const char*)memchr(p, 'x', (size_t)(end - p));
+      int32_t w, h;
+      if (x && hdr_int(p, x, &w) && hdr_int(x + 1, end, &h)) out->width = w, out->height = h;
+    }
+  }
+  out->payload_offset = pos;
+  out->format = fmt_format ? fmt_format : evt_format;
+  out->complete = ended ? 1 : 0;
   return 0;
 }
 
@@ -2017,7 +2160,7 @@ int esvio_fe_track_raw(esvio_fe_handle c, int format, const void* left, size_t l
   if (!nb[0] && !nb[1]) return 0;  // nothing to decode: no left event, nothing tracked
   HIPCHK(c, hipSetDevice(c->dev));
   // where the records go: the current pair, or, in front of a filter, the stage's own buffers
-  const size_t wb = format == ESVIO_FE_RAW_EVT3 ? 2 : 4;
+  const size_t wb = raw_word_bytes(format);
   RawJob job[2];
   auto place = [&](const size_t want[2]) -> int {
     EventRec* d[2] = {nullptr, nullptr};
@@ -2161,6 +2304,8 @@ int slice_feed_check(esvio_fe_ctx* c, const char* who) {  // an open feed keeps 
 }
 int slice_events_impl(esvio_fe_ctx* c, int cam, const esvio_fe_event* ev, size_t n, int space, const esvio_fe_slice_params* prm,
                       uint64_t* cuts, size_t cuts_cap, esvio_fe_slice_info* info);
+int slice_events_at_impl(esvio_fe_ctx* c, int cam, const esvio_fe_event* ev, size_t n, int space, const esvio_fe_event* bounds,
+                         size_t n_bounds, uint64_t* cuts, size_t cuts_cap, esvio_fe_slice_info* info);
 }  // namespace
 
 int esvio_fe_slice_events(esvio_fe_handle c, int cam, const esvio_fe_event* ev, size_t n, int space,
@@ -2170,7 +2315,114 @@ int esvio_fe_slice_events(esvio_fe_handle c, int cam, const esvio_fe_event* ev, 
   return slice_events_impl(c, cam, ev, n, space, prm, cuts, cuts_cap, info);
 }
 
+int esvio_fe_slice_events_at(esvio_fe_handle c, int cam, const esvio_fe_event* ev, size_t n, int space,
+                             const esvio_fe_event* bounds, size_t n_bounds, uint64_t* cuts, size_t cuts_cap,
+                             esvio_fe_slice_info* info) {
+  if (!c) return ESVIO_FE_EINVAL;
+  if (int rc = slice_feed_check(c, "slice_events_at")) return rc;
+  return slice_events_at_impl(c, cam, ev, n, space, bounds, n_bounds, cuts, cuts_cap, info);
+}
+
 namespace {
+// Windows at given stamps (include/esvio_fe.h): the fixed-rate call's three launches over a table of the caller's
+// stamps.  The kernels read c == n_bounds as "at or beyond the range's last boundary" and fail the call; here an event
+// behind the last given boundary is no failure, so the table ends in one more entry that no stamp reaches (+inf: a
+// record's stamp is finite) and a count never gets there.
+int slice_events_at_impl(esvio_fe_ctx* c, int cam, const esvio_fe_event* ev, size_t n, int space, const esvio_fe_event* bounds,
+                         size_t n_bounds, uint64_t* cuts, size_t cuts_cap, esvio_fe_slice_info* info) {
+  if (int rc = slice_cam_check(c, "slice_events_at", cam)) return rc;
+  esvio_fe_ctx::Slice& sl = c->slice;
+  const SliceState& cur = sl.st[cam];
+  slice_info_state(info, cur);
+  if (space != ESVIO_FE_HOST && space != ESVIO_FE_DEVICE) return fail(c, ESVIO_FE_EINVAL, "slice_events_at: bad memory space");
+  if (n_bounds > kSliceMaxWindows)
+    return fail(c, ESVIO_FE_EINVAL, "slice_events_at: a call takes at most %u boundaries (got %zu)", kSliceMaxWindows, n_bounds);
+  if (n_bounds && !bounds) return fail(c, ESVIO_FE_EINVAL, "slice_events_at: bounds is null");
+  for (size_t k = 1; k < n_bounds; k++)
+    if (slice_to_sec(bounds[k].sec, bounds[k].nsec) < slice_to_sec(bounds[k - 1].sec, bounds[k - 1].nsec))
+      return fail(c, ESVIO_FE_EINVAL, "slice_events_at: boundary %zu lies in front of boundary %zu: the stamps must not decrease", k, k - 1);
+  if (n && !ev) return fail(c, ESVIO_FE_EINVAL, "slice_events_at: ev is null");
+  if (n > kSliceMaxEvents) return fail(c, ESVIO_FE_EINVAL, "slice_events_at: a call takes at most 2^30 events");
+  if (space == ESVIO_FE_DEVICE && ((uintptr_t)ev & 15) != 0)
+    return fail(c, ESVIO_FE_EINVAL, "slice_events_at: device events must be 16-byte aligned");
+  if (cuts_cap && !cuts) return fail(c, ESVIO_FE_EINVAL, "slice_events_at: cuts is null");
+  if (!n) return 0;
+  if (cur.seen && !cur.at)
+    return fail(c, ESVIO_FE_EINVAL, "slice_events_at: the camera's first call fixed fixed-rate windows (esvio_fe_slice_reset first)");
+  HIPCHK(c, hipSetDevice(c->dev));
+  hipStream_t s = cur_stream(c);
+  SliceState st = cur;
+  st.seen = true, st.at = true;
+  // the table: the camera's own, which then belongs to no fixed-rate chain any more
+  sl.tab_for[cam] = SliceState();
+  sl.E[cam].clear();
+  if (!sl.bounds[cam])
+    if (int rc = sl.bounds[cam].alloc(c, kSliceTable)) return rc;
+  if (!sl.h_bounds[cam])
+    if (int rc = sl.h_bounds[cam].alloc(c, kSliceTable)) return rc;
+  for (size_t k = 0; k < n_bounds; k++) sl.h_bounds[cam][k] = slice_to_sec(bounds[k].sec, bounds[k].nsec);
+  sl.h_bounds[cam][n_bounds] = std::numeric_limits<double>::infinity();
+  HIPCHK(c, hipMemcpyAsync(sl.bounds[cam], sl.h_bounds[cam], (n_bounds + 1) * sizeof(double), hipMemcpyHostToDevice, s));
+  const uint32_t tiles = (uint32_t)((n + kSliceTile - 1) / kSliceTile);
+  if (!sl.res)
+    if (int rc = sl.res.alloc(c, 2 * kSliceResWords)) return rc;
+  if (!sl.h_res)
+    if (int rc = sl.h_res.alloc(c, 2 * kSliceResWords)) return rc;
+  if (int rc = sl.tmax[cam].grow(c, tiles)) return rc;
+  const EventRec* d_ev = (const EventRec*)ev;
+  if (space == ESVIO_FE_HOST) {
+    if (int rc = sl.src[cam].grow(c, n)) return rc;
+    HIPCHK(c, hipMemcpyAsync(sl.src[cam], ev, n * sizeof(EventRec), hipMemcpyHostToDevice, s));
+    d_ev = sl.src[cam];
+  }
+  uint32_t* d_res = sl.res + (size_t)cam * kSliceResWords;
+  uint32_t* h_res = sl.h_res + (size_t)cam * kSliceResWords;
+  SliceArgs a{};
+  SliceCam& sc = a.cam[0];
+  sc.ev = d_ev, sc.n = (uint32_t)n, sc.tiles = tiles;
+  sc.bounds = sl.bounds[cam], sc.n_bounds = (uint32_t)n_bounds + 1;
+  sc.tmax = sl.tmax[cam], sc.res = (SliceResult*)d_res, sc.cuts = d_res + sizeof(SliceResult) / 4;
+  {
+    ScopedKernel k(c, K_SLICE_REDUCE, (uint64_t)n * sizeof(EventRec) + (uint64_t)tiles * 4);
+    launch_slice_reduce(s, a);
+  }
+  {
+    ScopedKernel k(c, K_SLICE_SCAN, (uint64_t)tiles * 8);
+    launch_slice_scan(s, a);
+  }
+  {
+    ScopedKernel k(c, K_SLICE_CUTS, (uint64_t)n * sizeof(EventRec) + (uint64_t)tiles * 4);
+    launch_slice_cuts(s, a);
+  }
+  HIPCHK(c, hipMemcpyAsync(h_res, d_res, sizeof(SliceResult) + kSliceInlineCuts * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  if (c->prof_on) resolve_profile(c);
+  const SliceResult r = *(const SliceResult*)h_res;
+  if (r.overflow || r.closed > n_bounds)
+    return fail(c, ESVIO_FE_EINTERNAL, "slice_events_at: a count reached the table's closing entry");
+  if (r.closed > cuts_cap) {
+    if (info) info->closed = r.closed;
+    return fail(c, ESVIO_FE_EINVAL, "slice_events_at: the call closes %u windows, cuts has room for %zu; the camera's state is as it was", r.closed, cuts_cap);
+  }
+  if (r.closed > kSliceInlineCuts) {
+    HIPCHK(c, hipMemcpyAsync(h_res + sizeof(SliceResult) / 4 + kSliceInlineCuts, d_res + sizeof(SliceResult) / 4 + kSliceInlineCuts,
+                             (size_t)(r.closed - kSliceInlineCuts) * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+  }
+  for (uint32_t j = 0; j < r.closed; j++) cuts[j] = h_res[sizeof(SliceResult) / 4 + j];
+  st.open = r.closed ? n - r.first_of_last : cur.open + n;
+  st.m += r.closed;
+  if (info) {
+    info->closed = r.closed, info->first_window = cur.m, info->count = st.m, info->open_events = st.open;
+    if (r.closed) {
+      info->first_sec = bounds[0].sec, info->first_nsec = bounds[0].nsec;
+      info->last_sec = bounds[r.closed - 1].sec, info->last_nsec = bounds[r.closed - 1].nsec;
+    }
+  }
+  sl.st[cam] = st;
+  return 0;
+}
+
 int slice_events_impl(esvio_fe_ctx* c, int cam, const esvio_fe_event* ev, size_t n, int space, const esvio_fe_slice_params* prm,
                       uint64_t* cuts, size_t cuts_cap, esvio_fe_slice_info* info) {
   if (int rc = slice_cam_check(c, "slice_events", cam)) return rc;
@@ -2188,6 +2440,8 @@ int slice_events_impl(esvio_fe_ctx* c, int cam, const esvio_fe_event* ev, size_t
     return fail(c, ESVIO_FE_EINVAL, "slice_events: device events must be 16-byte aligned");
   if (cuts_cap && !cuts) return fail(c, ESVIO_FE_EINVAL, "slice_events: cuts is null");
   if (!n) return 0;
+  if (cur.seen && cur.at)
+    return fail(c, ESVIO_FE_EINVAL, "slice_events: the camera's first call fixed windows at given stamps (esvio_fe_slice_reset first)");
   HIPCHK(c, hipSetDevice(c->dev));
   hipStream_t s = cur_stream(c);
   // the state this call works from: the camera's, or — for its first events — the one they and prm define
@@ -2286,6 +2540,11 @@ int esvio_fe_slice_flush(esvio_fe_handle c, int cam, esvio_fe_slice_info* info) 
   SliceState& st = c->slice.st[cam];
   slice_info_state(info, st);
   if (!st.seen) return 0;
+  if (st.at) {  // windows at given stamps: the open window has no boundary, the stamp fields stay as they are
+    st.m += 1, st.open = 0;
+    if (info) info->closed = 1, info->count = st.m, info->open_events = 0;
+    return 0;
+  }
   HIPCHK(c, hipSetDevice(c->dev));
   uint32_t n_bounds = 0;
   if (int rc = slice_table(c, cam, st, &n_bounds, cur_stream(c))) return rc;
@@ -2421,7 +2680,7 @@ int feed_push(esvio_fe_ctx* c, const char* who, int cam, const FeedSrc& src, esv
   int flt_space = src.space;
   RawResult raw_res[2] = {};
   if (src.kind == FEED_RAW) {
-    const size_t wb = src.format == ESVIO_FE_RAW_EVT3 ? 2 : 4;
+    const size_t wb = raw_word_bytes(src.format);
     RawJob job[2];
     job[0].words = src.words, job[0].n_bytes = src.n_bytes;
     // one record per word to begin with; when the reduce pass reports more, room is made and the emit launch repeated

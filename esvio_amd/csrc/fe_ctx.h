@@ -72,7 +72,7 @@ const char* const kKernelNames[K_COUNT] = {
     "k_select", "k_select_gbm", "k_fast_score", "k_fast_collect", "k_events_from_fields", "k_baf_heads", "k_baf_filter",
     "k_baf_count", "k_baf_scan", "k_baf_emit", "k_baf_keys_fields", "k_baf_emit_fields", "k_raw_reduce", "k_raw_scan",
     "k_raw_emit", "k_slice_reduce", "k_slice_scan", "k_slice_cuts", "k_baf_keys_addr", "k_hot_count", "k_hot_keys",
-    "k_hot_pick"};
+    "k_hot_pick", "k_trig_reduce", "k_trig_emit"};
 
 // The host phases of one trackEvent call, in the order of esvio_fe_latency_call::phase_ms; kPhaseNames is what
 // esvio_fe_latency_phase_name returns and what the ESVIO_FE_TRACE summary prints.  The PH_PUB_* phases are parts of
@@ -524,13 +524,15 @@ struct esvio_fe_ctx {
   // comes back in the camera's result block, which is the pending slot: the host takes it over only once the call is
   // known to succeed.  Everything else is allocated on first use and is the stage's own (main stream only), one per
   // camera so that both cameras' chains are in flight together: src, the copy of a host source that is not read in
-  // place; sums, the tiles' transformers; dec, the records behind a host dst and, in esvio_fe_track_raw with a filter,
+  // place; sums, the tiles' transformers; dec, the records behind a host dst (esvio_fe_decode_triggers' 16-byte trigger
+  // records too: every call has taken its records out before it returns) and, in esvio_fe_track_raw with a filter,
   // the decoded records the filter reads; res, the two result blocks.
   struct Raw {
     struct State {
       uint32_t seen = 0, th = 0, tl = 0, y = 0, bx = 0, bp = 0;
       uint64_t wraps = 0;
     } st[2];
+    State trig_st[2];  // esvio_fe_decode_triggers' own decoder states (seen, th, wraps, tl; the rest stays 0)
     DevBuf<uint8_t> src[2];
     DevBuf<RawXf> sums[2];
     DevBuf<EventRec> dec[2];
@@ -549,6 +551,7 @@ struct esvio_fe_ctx {
   struct Slice {
     struct State {
       bool seen = false;
+      bool at = false;  // seen: the camera's windows end at stamps the caller gives (esvio_fe_slice_events_at), not at fixed rate
       int32_t has_origin = 0;
       double frequency = 0;
       uint32_t o_sec = 0, o_nsec = 0;  // the origin record's stamp

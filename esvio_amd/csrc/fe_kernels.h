@@ -90,12 +90,14 @@ enum KernelId {
   K_HOT_COUNT,       // esvio_fe_hot_learn (records and fields)
   K_HOT_KEYS,        // esvio_fe_hot_select: keys of the count plane (its sort is booked as K_RADIX_PASS), then the pick
   K_HOT_PICK,
+  K_TRIG_REDUCE,     // esvio_fe_decode_triggers (its scan launch is k_raw_scan, booked as K_RAW_SCAN)
+  K_TRIG_EMIT,
   K_COUNT
 };
 // esvio_fe_kernel_count(): the kernels of the tracker's entry points, the table bench.py and the recorded launch traces
 // list.  The ids from here on belong to stages off every track path and are listed by esvio_fe_stage_kernel_count().
 constexpr int kTrackKernels = K_BAF_HEADS;
-static_assert(K_EVENTS_FROM_FIELDS + 1 == kTrackKernels && K_HOT_PICK + 1 == K_COUNT,
+static_assert(K_EVENTS_FROM_FIELDS + 1 == kTrackKernels && K_TRIG_EMIT + 1 == K_COUNT,
               "a track-path kernel goes in front of K_BAF_HEADS (and into this assertion), a stage's kernel behind it");
 
 // ---- SAE update -------------------------------------------------------------------------
@@ -642,9 +644,14 @@ void launch_hot_pick(hipStream_t s, const uint32_t* keys, const uint32_t* vals, 
 // bytes) -> scan (one workgroup per camera: the tiles' exclusive prefixes, seeded with the camera's carried state; the
 // totals and the state after the call) -> emit (re-reads the tile, scans inside it from the tile's carry-in, builds the
 // records at offset + rank).  Three launches for one camera or for both: both cameras' tiles share each grid.  No
-// launch waits on the device for another workgroup.  EVT2 is the same chain with a smaller classifier.
-constexpr uint32_t kRawTileBytes = 4096;  // 256 lanes x 16 bytes: 2048 EVT3 words, 1024 EVT2 words
-constexpr int kRawEvt2 = 2, kRawEvt3 = 3;
+// launch waits on the device for another workgroup.  EVT2 is the same chain with a smaller classifier; EVT2.1 is EVT2's
+// with 64-bit words — two per lane — whose event count is the popcount of the word's 32-bit mask (a lane can stand for
+// 64 records, a tile for 16 384).
+// Triggers (esvio_fe_decode_triggers): the same chain with a classifier of its own — k_trig_reduce, k_raw_scan as it is,
+// k_trig_emit — over the same RawXf: only the time base and the counts are used, a trigger word counts as one "event",
+// and the records stored are esvio_fe_trigger's 16 bytes.
+constexpr uint32_t kRawTileBytes = 4096;  // 256 lanes x 16 bytes: 2048 EVT3 words, 1024 EVT2 words, 512 EVT2.1 words
+constexpr int kRawEvt2 = 2, kRawEvt3 = 3, kRawEvt21 = 21;
 constexpr uint32_t kRawHasTh = 1u, kRawHasTl = 2u, kRawHasY = 4u, kRawHasBx = 8u, kRawBp = 16u;
 constexpr int kRawTlShift = 8, kRawYShift = 20;  // flags: tl in bits 8..19, y in bits 20..30
 struct RawXf {
@@ -678,12 +685,16 @@ struct RawCam {
   RawResult* res;
 };
 struct RawArgs {
-  int format;     // kRawEvt2 / kRawEvt3
+  int format;     // kRawEvt2 / kRawEvt3 / kRawEvt21
   RawCam cam[2];  // the grid's blocks: cam[0].tiles, then cam[1].tiles
 };
 void launch_raw_reduce(hipStream_t s, const RawArgs& a);
 void launch_raw_scan(hipStream_t s, const RawArgs& a);
 void launch_raw_emit(hipStream_t s, const RawArgs& a);
+// the trigger chain's own two launches (RawCam::dst: [dst_cap] 16-byte esvio_fe_trigger records; RawResult::events,
+// untimed, bad, first_t, last_t count triggers; `other` stays 0)
+void launch_trig_reduce(hipStream_t s, const RawArgs& a);
+void launch_trig_emit(hipStream_t s, const RawArgs& a);
 
 // ---- stream slicing: a record stream cut into fixed-rate windows (esvio_fe_slice_events) ----
 // include/esvio_fe.h holds the rule.  An event's window is m_i = max(m_{i-1}, c_i), c_i = the boundaries at or below its
@@ -707,7 +718,8 @@ struct SliceCam {
   const EventRec* ev;   // [n] device memory
   uint32_t n;
   uint32_t tiles;       // ceil(n / kSliceTile); 0: the camera takes no part
-  const double* bounds; // [n_bounds] toSec(E_k) of the windows open or ahead at the call's start, ascending
+  const double* bounds; // [n_bounds] toSec(E_k) of the windows open or ahead at the call's start, ascending (windows at
+                        // given stamps: the caller's, non-decreasing, and one closing +inf that no stamp reaches)
   uint32_t n_bounds;    // <= kSliceMaxWindows + 1; c == n_bounds is the overflow
   uint32_t* tmax;       // [tiles] reduce: the tiles' maxima; scan: their exclusive prefix maxima
   SliceResult* res;

@@ -4466,7 +4466,8 @@ void launch_hot_pick(hipStream_t s, const uint32_t* keys, const uint32_t* vals, 
 }
 
 // ============================================================================ raw sensor streams
-// EVT3 / EVT2 words -> event records (fe_kernels.h has the chain, include/esvio_fe.h the rule).
+// EVT3 / EVT2 / EVT2.1 words -> event records, and their EXT_TRIGGER words -> trigger records (fe_kernels.h has the
+// chain, include/esvio_fe.h the rule).
 //   raw_push      one word applied to a running transformer: raw_combine(run, the word's own transformer), written out
 //   raw_combine   (earlier, later) -> both; associative, not commutative
 //   k_raw_reduce  per tile: each lane its 16 bytes, the wave by cross-lane moves, the four waves through LDS
@@ -4507,14 +4508,26 @@ __device__ __forceinline__ void raw_time_high(RawXf& r, uint32_t v, uint32_t hal
   r.th_last = v;
   r.flags |= kRawHasTh;
 }
+// (EVT2.1: w is the 64-bit word's low half — the mask —, hi its high half: type, tlow, bx, y where EVT2 has them)
 template <int kFormat>
-__device__ __forceinline__ uint32_t raw_word_events(uint32_t w) {  // how many events the word stands for
+__device__ __forceinline__ uint32_t raw_word_events(uint32_t w, uint32_t hi = 0) {  // how many events the word stands for
+  if (kFormat == kRawEvt21) return (hi >> 28) <= 1u ? (uint32_t)__popc(w) : 0u;
   if (kFormat == kRawEvt2) return (w >> 28) <= 1u ? 1u : 0u;
   const uint32_t t = w >> 12;
   return t == 2u ? 1u : t == 4u ? (uint32_t)__popc(w & 0xfffu) : t == 5u ? (uint32_t)__popc(w & 0xffu) : 0u;
 }
 template <int kFormat>
-__device__ __forceinline__ void raw_push(RawXf& r, uint32_t w) {
+__device__ __forceinline__ void raw_push(RawXf& r, uint32_t w, uint32_t hi = 0) {
+  if (kFormat == kRawEvt21) {
+    const uint32_t t = hi >> 28;
+    if (t <= 1u)
+      raw_count(r, (uint32_t)__popc(w));  // (a zero mask: nothing, counted nowhere)
+    else if (t == 8u)
+      raw_time_high(r, hi & 0x0fffffffu, 1u << 27);
+    else
+      r.other++;
+    return;
+  }
   if (kFormat == kRawEvt2) {
     const uint32_t t = w >> 28;
     if (t <= 1u)
@@ -4563,6 +4576,7 @@ __device__ __forceinline__ RawXf raw_wave_scan(RawXf incl, uint32_t half) {
 }
 // The lane's words of the tile: 16 bytes = kW words, the first nv of them inside the stream.  One 16-byte load where
 // the stream is 16-byte aligned and the lane's bytes all lie inside it; else byte by byte, never beyond n_bytes.
+// (EVT2.1 loads as EVT2 does — four 32-bit halves, nv counts halves and is even — and raw_items pairs them.)
 template <int kFormat>
 __device__ __forceinline__ int raw_load(const RawCam& c, uint32_t tile, uint32_t w[8]) {
   constexpr int kW = kFormat == kRawEvt3 ? 8 : 4, kB = 16 / kW;
@@ -4597,9 +4611,18 @@ __device__ __forceinline__ const RawCam& raw_block_cam(const RawArgs& a, uint32_
   return b < a.cam[0].tiles ? a.cam[0] : a.cam[1];
 }
 
+// the lane's words as the classifiers take them: raw_load's units one by one, for EVT2.1 in pairs (low half, high half)
+template <int kFormat>
+struct RawItems {
+  static constexpr int kStep = kFormat == kRawEvt21 ? 2 : 1;
+  static constexpr int kItems = kFormat == kRawEvt3 ? 8 : kFormat == kRawEvt21 ? 2 : 4;
+  static __device__ __forceinline__ uint32_t lo(const uint32_t w[8], int k) { return w[k * kStep]; }
+  static __device__ __forceinline__ uint32_t hi(const uint32_t w[8], int k) { return kStep == 2 ? w[k * kStep + 1] : 0u; }
+};
+
 template <int kFormat>
 __global__ __launch_bounds__(256) void k_raw_reduce(RawArgs a) {
-  constexpr int kW = kFormat == kRawEvt3 ? 8 : 4;
+  using It = RawItems<kFormat>;
   constexpr uint32_t kHalf = kFormat == kRawEvt3 ? 2048u : 1u << 27;
   __shared__ RawXf part[4];
   uint32_t tile;
@@ -4608,8 +4631,8 @@ __global__ __launch_bounds__(256) void k_raw_reduce(RawArgs a) {
   const int nv = raw_load<kFormat>(c, tile, w);
   RawXf x = raw_identity();
 #pragma unroll
-  for (int k = 0; k < kW; k++)
-    if (k < nv) raw_push<kFormat>(x, w[k]);
+  for (int k = 0; k < It::kItems; k++)
+    if (k * It::kStep < nv) raw_push<kFormat>(x, It::lo(w, k), It::hi(w, k));
   x = raw_wave_scan(x, kHalf);
   if (lane_id() == 63) part[threadIdx.x >> 6] = x;
   __syncthreads();
@@ -4660,7 +4683,7 @@ __device__ __forceinline__ bool raw_stamp(long long ticks, uint32_t* sec, uint32
 
 template <int kFormat>
 __global__ __launch_bounds__(256) void k_raw_emit(RawArgs a) {
-  constexpr int kW = kFormat == kRawEvt3 ? 8 : 4;
+  using It = RawItems<kFormat>;
   constexpr uint32_t kHalf = kFormat == kRawEvt3 ? 2048u : 1u << 27;
   __shared__ RawXf part[4];
   uint32_t tile;
@@ -4670,8 +4693,8 @@ __global__ __launch_bounds__(256) void k_raw_emit(RawArgs a) {
   RawXf x = raw_identity();
   uint32_t mine = 0;
 #pragma unroll
-  for (int k = 0; k < kW; k++)
-    if (k < nv) raw_push<kFormat>(x, w[k]), mine += raw_word_events<kFormat>(w[k]);
+  for (int k = 0; k < It::kItems; k++)
+    if (k * It::kStep < nv) raw_push<kFormat>(x, It::lo(w, k), It::hi(w, k)), mine += raw_word_events<kFormat>(It::lo(w, k), It::hi(w, k));
   const RawXf incl = raw_wave_scan(x, kHalf);
   if (lane_id() == 63) part[threadIdx.x >> 6] = incl;
   const RawXf up = raw_shfl_up(incl, 1);  // (while every lane is still here: the lane in front may have no event)
@@ -4685,29 +4708,35 @@ __global__ __launch_bounds__(256) void k_raw_emit(RawArgs a) {
   uint4* dst = (uint4*)c.dst;
   uint32_t bad = 0;
 #pragma unroll
-  for (int k = 0; k < kW; k++) {
-    if (k >= nv) break;
-    const uint32_t n = raw_word_events<kFormat>(w[k]);
+  for (int k = 0; k < It::kItems; k++) {
+    if (k * It::kStep >= nv) break;
+    const uint32_t wk = It::lo(w, k), hk = It::hi(w, k);
+    const uint32_t n = raw_word_events<kFormat>(wk, hk);
     if (n && (run.flags & kRawHasTh)) {
       // (128 bits: the carried wrap count is 64 bits wide and the rule's integers have no bound; a stamp that leaves
       // 64 bits is BAD like any other stamp behind 2^32 s, it never wraps around)
       const __int128 wr = (__int128)(c.wraps_base + run.wraps);
       __int128 t;
       uint32_t xy, pol, mask = 1u;
-      if (kFormat == kRawEvt2) {
-        t = (wr << 34) + ((unsigned long long)run.th_last << 6) + ((w[k] >> 22) & 0x3fu);
-        xy = ((w[k] >> 11) & 0x7ffu) | (w[k] & 0x7ffu) << 16;
-        pol = w[k] >> 28;
+      if (kFormat == kRawEvt21) {  // (the high half has EVT2's fields where EVT2 has them; x = bx + i stays below 2^16)
+        t = (wr << 34) + ((unsigned long long)run.th_last << 6) + ((hk >> 22) & 0x3fu);
+        xy = ((hk >> 11) & 0x7ffu) | (hk & 0x7ffu) << 16;
+        pol = hk >> 28;
+        mask = wk;
+      } else if (kFormat == kRawEvt2) {
+        t = (wr << 34) + ((unsigned long long)run.th_last << 6) + ((wk >> 22) & 0x3fu);
+        xy = ((wk >> 11) & 0x7ffu) | (wk & 0x7ffu) << 16;
+        pol = wk >> 28;
       } else {
         t = (wr << 24) + ((unsigned long long)run.th_last << 12) + ((run.flags >> kRawTlShift) & 0xfffu);
         const uint32_t y = (run.flags >> kRawYShift) & 0x7ffu;
-        if ((w[k] >> 12) == 2u) {
-          xy = (w[k] & 0x7ffu) | y << 16;
-          pol = (w[k] >> 11) & 1u;
+        if ((wk >> 12) == 2u) {
+          xy = (wk & 0x7ffu) | y << 16;
+          pol = (wk >> 11) & 1u;
         } else {
           xy = run.bx | y << 16;
           pol = run.flags & kRawBp ? 1u : 0u;
-          mask = w[k] & ((w[k] >> 12) == 4u ? 0xfffu : 0xffu);
+          mask = wk & ((wk >> 12) == 4u ? 0xfffu : 0xffu);
         }
       }
       const __int128 wide = t + c.t_offset;
@@ -4725,7 +4754,111 @@ __global__ __launch_bounds__(256) void k_raw_emit(RawArgs a) {
           dst[pos++] = make_uint4(xi | (xy & 0xffff0000u), sec, nsec, pol);
         }
     }
-    raw_push<kFormat>(run, w[k]);
+    raw_push<kFormat>(run, wk, hk);
+  }
+  if (bad) atomicAdd(&c.res->bad, (unsigned long long)bad);
+}
+
+// ---- triggers: the same chain with a classifier of its own (fe_kernels.h); k_raw_scan runs between the two as it is
+//   trig_push     one word applied to a running transformer: the time words as raw_push has them, an EXT_TRIGGER word
+//                 (type 0xA) counts as one; every other word leaves the transformer alone
+template <int kFormat>
+__device__ __forceinline__ uint32_t trig_word(uint32_t w, uint32_t hi) {  // 1: a trigger word
+  return (kFormat == kRawEvt3 ? w >> 12 : kFormat == kRawEvt2 ? w >> 28 : hi >> 28) == 0xAu ? 1u : 0u;
+}
+template <int kFormat>
+__device__ __forceinline__ void trig_push(RawXf& r, uint32_t w, uint32_t hi) {
+  if (kFormat == kRawEvt3) {
+    const uint32_t t = w >> 12;
+    if (t == 0x6u)
+      r.flags = (r.flags & ~(0xfffu << kRawTlShift)) | kRawHasTl | ((w & 0xfffu) << kRawTlShift);
+    else if (t == 0x8u)
+      raw_time_high(r, w & 0xfffu, 2048u);
+    else if (t == 0xAu)
+      raw_count(r, 1u);
+    return;
+  }
+  const uint32_t v = kFormat == kRawEvt2 ? w : hi, t = v >> 28;
+  if (t == 0x8u)
+    raw_time_high(r, v & 0x0fffffffu, 1u << 27);
+  else if (t == 0xAu)
+    raw_count(r, 1u);
+}
+
+template <int kFormat>
+__global__ __launch_bounds__(256) void k_trig_reduce(RawArgs a) {
+  using It = RawItems<kFormat>;
+  constexpr uint32_t kHalf = kFormat == kRawEvt3 ? 2048u : 1u << 27;
+  __shared__ RawXf part[4];
+  uint32_t tile;
+  const RawCam& c = raw_block_cam(a, &tile);
+  uint32_t w[8];
+  const int nv = raw_load<kFormat>(c, tile, w);
+  RawXf x = raw_identity();
+#pragma unroll
+  for (int k = 0; k < It::kItems; k++)
+    if (k * It::kStep < nv) trig_push<kFormat>(x, It::lo(w, k), It::hi(w, k));
+  x = raw_wave_scan(x, kHalf);
+  if (lane_id() == 63) part[threadIdx.x >> 6] = x;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    c.sums[tile] = raw_combine(raw_combine(part[0], part[1], kHalf), raw_combine(part[2], part[3], kHalf), kHalf);
+}
+
+template <int kFormat>
+__global__ __launch_bounds__(256) void k_trig_emit(RawArgs a) {
+  using It = RawItems<kFormat>;
+  constexpr uint32_t kHalf = kFormat == kRawEvt3 ? 2048u : 1u << 27;
+  __shared__ RawXf part[4];
+  uint32_t tile;
+  const RawCam& c = raw_block_cam(a, &tile);
+  uint32_t w[8];
+  const int nv = raw_load<kFormat>(c, tile, w);
+  RawXf x = raw_identity();
+  uint32_t mine = 0;
+#pragma unroll
+  for (int k = 0; k < It::kItems; k++)
+    if (k * It::kStep < nv) trig_push<kFormat>(x, It::lo(w, k), It::hi(w, k)), mine += trig_word<kFormat>(It::lo(w, k), It::hi(w, k));
+  const RawXf incl = raw_wave_scan(x, kHalf);
+  if (lane_id() == 63) part[threadIdx.x >> 6] = incl;
+  const RawXf up = raw_shfl_up(incl, 1);
+  __syncthreads();
+  if (!mine) return;  // (behind the barrier and the cross-lane move, as in k_raw_emit)
+  RawXf run = c.sums[tile];
+  for (int wv = 0; wv < (int)(threadIdx.x >> 6); wv++) run = raw_combine(run, part[wv], kHalf);
+  if (lane_id() > 0) run = raw_combine(run, up, kHalf);
+  const uint32_t total = c.res->events;
+  const bool store = total <= c.dst_cap;
+  uint4* dst = (uint4*)c.dst;
+  uint32_t bad = 0;
+#pragma unroll
+  for (int k = 0; k < It::kItems; k++) {
+    if (k * It::kStep >= nv) break;
+    const uint32_t wk = It::lo(w, k), hk = It::hi(w, k);
+    if (trig_word<kFormat>(wk, hk) && (run.flags & kRawHasTh)) {
+      const __int128 wr = (__int128)(c.wraps_base + run.wraps);
+      __int128 t;
+      uint32_t idv;  // id | value << 8
+      if (kFormat == kRawEvt3) {
+        t = (wr << 24) + ((unsigned long long)run.th_last << 12) + ((run.flags >> kRawTlShift) & 0xfffu);
+        idv = ((wk >> 8) & 0xfu) | (wk & 1u) << 8;
+      } else if (kFormat == kRawEvt2) {
+        t = (wr << 34) + ((unsigned long long)run.th_last << 6) + ((wk >> 22) & 0x3fu);
+        idv = ((wk >> 8) & 0x1fu) | (wk & 1u) << 8;
+      } else {
+        t = (wr << 34) + ((unsigned long long)run.th_last << 6) + ((hk >> 22) & 0x3fu);
+        idv = ((hk >> 8) & 0x1fu) | (hk & 1u) << 8;
+      }
+      const __int128 wide = t + c.t_offset;
+      const long long ticks = wide < -0x7fffffffffffffffll ? -0x7fffffffffffffffll : wide > 0x7fffffffffffffffll ? 0x7fffffffffffffffll : (long long)wide;
+      uint32_t sec, nsec;
+      if (!raw_stamp(ticks, &sec, &nsec)) bad++;
+      const uint32_t pos = run.after;
+      if (pos == 0) c.res->first_t = ticks;
+      if (pos + 1u == total) c.res->last_t = ticks;
+      if (store) dst[pos] = make_uint4(sec, nsec, idv, 0u);
+    }
+    trig_push<kFormat>(run, wk, hk);
   }
   if (bad) atomicAdd(&c.res->bad, (unsigned long long)bad);
 }
@@ -4735,6 +4868,8 @@ void launch_raw_reduce(hipStream_t s, const RawArgs& a) {
   if (!raw_grid(a)) return;
   if (a.format == kRawEvt3)
     launch_k(k_raw_reduce<kRawEvt3>, dim3(raw_grid(a)), dim3(256), 0, s, a);
+  else if (a.format == kRawEvt21)
+    launch_k(k_raw_reduce<kRawEvt21>, dim3(raw_grid(a)), dim3(256), 0, s, a);
   else
     launch_k(k_raw_reduce<kRawEvt2>, dim3(raw_grid(a)), dim3(256), 0, s, a);
 }
@@ -4745,8 +4880,28 @@ void launch_raw_emit(hipStream_t s, const RawArgs& a) {
   if (!raw_grid(a)) return;
   if (a.format == kRawEvt3)
     launch_k(k_raw_emit<kRawEvt3>, dim3(raw_grid(a)), dim3(256), 0, s, a);
+  else if (a.format == kRawEvt21)
+    launch_k(k_raw_emit<kRawEvt21>, dim3(raw_grid(a)), dim3(256), 0, s, a);
   else
     launch_k(k_raw_emit<kRawEvt2>, dim3(raw_grid(a)), dim3(256), 0, s, a);
+}
+void launch_trig_reduce(hipStream_t s, const RawArgs& a) {
+  if (!raw_grid(a)) return;
+  if (a.format == kRawEvt3)
+    launch_k(k_trig_reduce<kRawEvt3>, dim3(raw_grid(a)), dim3(256), 0, s, a);
+  else if (a.format == kRawEvt21)
+    launch_k(k_trig_reduce<kRawEvt21>, dim3(raw_grid(a)), dim3(256), 0, s, a);
+  else
+    launch_k(k_trig_reduce<kRawEvt2>, dim3(raw_grid(a)), dim3(256), 0, s, a);
+}
+void launch_trig_emit(hipStream_t s, const RawArgs& a) {
+  if (!raw_grid(a)) return;
+  if (a.format == kRawEvt3)
+    launch_k(k_trig_emit<kRawEvt3>, dim3(raw_grid(a)), dim3(256), 0, s, a);
+  else if (a.format == kRawEvt21)
+    launch_k(k_trig_emit<kRawEvt21>, dim3(raw_grid(a)), dim3(256), 0, s, a);
+  else
+    launch_k(k_trig_emit<kRawEvt2>, dim3(raw_grid(a)), dim3(256), 0, s, a);
 }
 
 // ============================================================================ stream slicing

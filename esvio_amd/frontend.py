@@ -131,7 +131,33 @@ class RawInfo(C.Structure):
                 ("wraps", C.c_uint64), ("first_t_us", C.c_int64), ("last_t_us", C.c_int64)]
 
 
-RAW_EVT2, RAW_EVT3 = 2, 3  # esvio_fe_decode_raw's formats
+RAW_EVT2, RAW_EVT3, RAW_EVT21 = 2, 3, 21  # esvio_fe_decode_raw's formats
+RAW_WORD_BYTES = {RAW_EVT2: 4, RAW_EVT3: 2, RAW_EVT21: 8}
+
+
+def raw_bound(fmt, nbytes):
+    """the records nbytes of words of format fmt can stand for at most (include/esvio_fe.h)"""
+    return nbytes // 2 * 12 if fmt == RAW_EVT3 else nbytes * 4 if fmt == RAW_EVT21 else nbytes // 4
+
+
+class Trigger(C.Structure):
+    """esvio_fe_trigger"""
+    _fields_ = [("sec", C.c_uint32), ("nsec", C.c_uint32), ("id", C.c_uint8), ("value", C.c_uint8), ("_pad", C.c_uint8 * 6)]
+
+
+TRIGGER_DTYPE = np.dtype([("sec", "<u4"), ("nsec", "<u4"), ("id", "u1"), ("value", "u1"), ("_pad", "u1", (6,))])
+
+
+class TriggerInfo(C.Structure):
+    """esvio_fe_trigger_info"""
+    _fields_ = [("triggers", C.c_uint64), ("untimed", C.c_uint64), ("bad", C.c_uint64), ("wraps", C.c_uint64),
+                ("first_t_us", C.c_int64), ("last_t_us", C.c_int64)]
+
+
+class RawHeaderInfo(C.Structure):
+    """esvio_fe_raw_header_info"""
+    _fields_ = [("payload_offset", C.c_uint64), ("format", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("complete", C.c_int32)]
 
 
 class EventRecord(C.Structure):
@@ -187,6 +213,7 @@ class Tracks(C.Structure):
 ABI_SYMBOLS = [
     "esvio_fe_calc_optical_flow_pyr_lk", "esvio_fe_comm_init", "esvio_fe_comm_unique_id",
     "esvio_fe_convert_events", "esvio_fe_create", "esvio_fe_decode_raw", "esvio_fe_decode_reset",
+    "esvio_fe_decode_triggers", "esvio_fe_raw_header", "esvio_fe_slice_events_at",
     "esvio_fe_create_sae", "esvio_fe_create_sae_stereo", "esvio_fe_create_sae_stereo_mc", "esvio_fe_destroy",
     "esvio_fe_exchange_begin", "esvio_fe_exchange_end", "esvio_fe_exchange_tracks", "esvio_fe_export_image",
     "esvio_fe_feed_close", "esvio_fe_feed_open", "esvio_fe_feed_peek", "esvio_fe_feed_push_events", "esvio_fe_feed_push_fields",
@@ -331,6 +358,9 @@ def load_library(build_if_missing=True):
     L.esvio_fe_track_raw.argtypes = [vp, i, vp, sz, vp, sz, i, C.c_int64, i, C.POINTER(FilterParams), C.POINTER(Motion),
                                      C.POINTER(Tracks), C.POINTER(BatchInfo), C.POINTER(RawInfo * 2)]
     L.esvio_fe_slice_events.argtypes = [vp, i, vp, sz, i, C.POINTER(SliceParams), vp, sz, C.POINTER(SliceInfo)]
+    L.esvio_fe_decode_triggers.argtypes = [vp, i, i, vp, sz, i, C.c_int64, vp, sz, C.POINTER(TriggerInfo)]
+    L.esvio_fe_raw_header.argtypes = [vp, sz, C.POINTER(RawHeaderInfo)]
+    L.esvio_fe_slice_events_at.argtypes = [vp, i, vp, sz, i, vp, sz, vp, sz, C.POINTER(SliceInfo)]
     L.esvio_fe_slice_flush.argtypes = [vp, i, C.POINTER(SliceInfo)]
     L.esvio_fe_slice_reset.argtypes = [vp]
     L.esvio_fe_feed_open.argtypes = [vp, C.POINTER(SliceParams), C.POINTER(FilterParams)]
@@ -741,7 +771,7 @@ class FeatureTracker:
     def decode_raw(self, cam, fmt, words, t_offset_us=0, dst_cap=None, device=False):
         """the raw-stream decode stage (esvio_fe_decode_raw; include/esvio_fe.h has the rule): camera `cam`'s decoder
         state advanced by `words` — a contiguous numpy array of raw words (any dtype: its bytes are the stream) or a
-        (device_ptr, n_bytes) tuple — of format RAW_EVT2 / RAW_EVT3.  Returns (records, RawInfo): records a numpy
+        (device_ptr, n_bytes) tuple — of format RAW_EVT2 / RAW_EVT3 / RAW_EVT21.  Returns (records, RawInfo): records a numpy
         EVENT_DTYPE array, or with device=True a FilteredEvents in device memory (`.arg`, `.n`, `.free()`).  dst_cap
         None: room for every record the words can stand for.  A failed call raises FrontendError with `.info`."""
         from .events import EVENT_DTYPE
@@ -752,7 +782,7 @@ class FeatureTracker:
             words = np.ascontiguousarray(words)
             ptr, nbytes, space = _p(words), words.nbytes, HOST
         if dst_cap is None:
-            dst_cap = nbytes // 2 * 12 if fmt == RAW_EVT3 else nbytes // 4
+            dst_cap = raw_bound(fmt, nbytes)
         info = RawInfo()
         if device:
             dst = C.c_void_p()
@@ -775,8 +805,32 @@ class FeatureTracker:
         return (FilteredEvents(dst, k, None) if device else out[:k]), info
 
     def decode_reset(self):
-        """both cameras' raw-stream decoder states back to the fresh state (esvio_fe_decode_reset)"""
+        """both cameras' raw-stream decoder states — the event decoder's and the trigger decoder's — back to the fresh
+        state (esvio_fe_decode_reset)"""
         self._hd.check(self._hd.L.esvio_fe_decode_reset(self._hd.h))
+
+    def decode_triggers(self, cam, fmt, words, t_offset_us=0, dst_cap=None):
+        """the EXT_TRIGGER words of a chunk as trigger records (esvio_fe_decode_triggers; include/esvio_fe.h has the
+        rule): camera `cam`'s trigger-decoder state advanced by `words`, given as decode_raw takes them.  Returns
+        (triggers, TriggerInfo): triggers a numpy TRIGGER_DTYPE array.  dst_cap None: one record per word.  A failed call
+        raises FrontendError with `.info`."""
+        L = self._hd.L
+        if isinstance(words, tuple):
+            ptr, nbytes, space = C.c_void_p(words[0]), int(words[1]), DEVICE
+        else:
+            words = np.ascontiguousarray(words)
+            ptr, nbytes, space = _p(words), words.nbytes, HOST
+        if dst_cap is None:
+            dst_cap = nbytes // RAW_WORD_BYTES.get(fmt, 2)
+        info = TriggerInfo()
+        out = np.zeros(max(int(dst_cap), 1), TRIGGER_DTYPE)
+        rc = L.esvio_fe_decode_triggers(self._hd.h, int(cam), int(fmt), ptr, nbytes, space, int(t_offset_us), _p(out), int(dst_cap),
+                                        C.byref(info))
+        if rc:
+            e = FrontendError("rc=%d: %s" % (rc, L.esvio_fe_last_error(self._hd.h).decode()))
+            e.info = info
+            raise e
+        return out[:int(info.triggers)], info
 
     def track_raw(self, fmt, left, right, t_offset_us=0, pub=True, params=None, measurements=None, copy=True):
         """one batch of raw words per camera through esvio_fe_track_raw: left / right are contiguous numpy arrays of raw
@@ -818,6 +872,30 @@ class FeatureTracker:
         prm, info = SliceParams(frequency, origin), SliceInfo()
         cuts = np.zeros(max(int(cuts_cap), 1), np.uint64)
         rc = self._hd.L.esvio_fe_slice_events(self._hd.h, int(cam), ptr, n, space, C.byref(prm), _p(cuts), int(cuts_cap), C.byref(info))
+        if rc:
+            e = FrontendError("rc=%d: %s" % (rc, self._hd.L.esvio_fe_last_error(self._hd.h).decode()))
+            e.info = info
+            raise e
+        return cuts[:int(info.closed)], info
+
+    def slice_events_at(self, cam, ev, bounds, cuts_cap=SLICE_MAX_WINDOWS):
+        """windows that end at given stamps (esvio_fe_slice_events_at; include/esvio_fe.h has the rule): `bounds` a numpy
+        array with `sec` / `nsec` fields (EVENT_DTYPE or TRIGGER_DTYPE records, what decode_triggers returns) or a
+        sequence of (sec, nsec) pairs — the ends of the windows from the camera's closed count on, non-decreasing.
+        Returns (cuts, SliceInfo) as slice_events does; pass bounds[info.closed:] and newer ones next time."""
+        from .events import EVENT_DTYPE
+        ptr, n, space, keep = _events_arg(ev)
+        if isinstance(bounds, np.ndarray) and bounds.dtype.names and "sec" in bounds.dtype.names:
+            sec, nsec = bounds["sec"], bounds["nsec"]
+        else:
+            pairs = np.asarray(bounds, np.int64).reshape(-1, 2)
+            sec, nsec = pairs[:, 0], pairs[:, 1]
+        b = np.zeros(len(sec), EVENT_DTYPE)
+        b["sec"], b["nsec"] = sec, nsec
+        info = SliceInfo()
+        cuts = np.zeros(max(int(cuts_cap), 1), np.uint64)
+        rc = self._hd.L.esvio_fe_slice_events_at(self._hd.h, int(cam), ptr, n, space, _p(b) if len(b) else None, len(b), _p(cuts),
+                                                 int(cuts_cap), C.byref(info))
         if rc:
             e = FrontendError("rc=%d: %s" % (rc, self._hd.L.esvio_fe_last_error(self._hd.h).decode()))
             e.info = info
@@ -1516,6 +1594,18 @@ def find_fundamental_mat_idle(p1, p2, thr=1.0, conf=0.99, threads=4, repeats=4, 
     if rc:
         raise FrontendError("find_fundamental_mat_idle rc=%d" % rc)
     return k.value, status, dict(idle_calls=int(out[0]), idle_done=int(out[1]), idle_left=int(out[2]))
+
+
+def raw_header(data):
+    """a .raw file's ASCII header (esvio_fe_raw_header; host only, no handle): `data` the file's first bytes.  Returns
+    the RawHeaderInfo: .payload_offset, .format (RAW_EVT2 / RAW_EVT21 / RAW_EVT3, 0: unknown), .width / .height
+    (0: unknown), .complete (0: the header's end is not inside `data` — read more and call again)"""
+    buf = bytes(data)
+    info = RawHeaderInfo()
+    rc = load_library().esvio_fe_raw_header(buf if buf else None, len(buf), C.byref(info))
+    if rc:
+        raise FrontendError("esvio_fe_raw_header rc=%d" % rc)
+    return info
 
 
 def lift_projective(cam, u, v):

@@ -670,6 +670,17 @@ int esvio_fe_track_batch(esvio_fe_handle h, const esvio_fe_batch* b, esvio_fe_tr
  *   0x8 TIME_HIGH    v = w & 0x0FFFFFFF, the same wrap rule with half range 2^27
  *   everything else: counted in `other`; `untimed` as for EVT3.
  *
+ * EVT2.1 (the vectorised 64-bit format the Gen4.1 / IMX636 HD sensors offer beside EVT3; like the two above RESTATED
+ * FROM RECALL and UNPINNED, this text being the specification and tests/evt21_ref.py its sequential reading).  State:
+ * EVT2's (seen, th, wraps).  Words are 64-bit little-endian; type = w >> 60:
+ *   0x0 EVT_NEG (p=0), 0x1 EVT_POS (p=1): bx = (w>>43)&0x7FF, y = (w>>32)&0x7FF, tlow = (w>>54)&0x3F,
+ *                    mask = w & 0xFFFFFFFF; for i = 0..31 ascending, if bit i of mask is set: one event
+ *                    (x = bx + i, y, p, t = wraps * 2^34 + th * 64 + tlow).  bx need not be 32-aligned (x reaches
+ *                    2047 + 31).  A zero mask emits nothing and is counted nowhere.
+ *   0x8 TIME_HIGH    v = (w>>32) & 0x0FFFFFFF, EVT2's wrap rule with half range 2^27
+ *   everything else: counted in `other`; `untimed` counts one per set bit while seen == 0.
+ * The half-swapped layout some files store these words in (two 32-bit words, high half first) is out of scope.
+ *
  * Records.  ticks = t + t_offset_us (signed, |t_offset_us| <= 2^62); sec = ticks / 10^6, nsec = (ticks % 10^6) * 1000;
  * x and y are copied as 16-bit patterns (an out-of-sensor pixel is the SAE update's business, as in the conversion);
  * polarity 0 or 1, the padding bytes 0 — byte for byte what esvio_amd.events.make_events builds.  Events are emitted in
@@ -678,12 +689,15 @@ int esvio_fe_track_batch(esvio_fe_handle h, const esvio_fe_batch* b, esvio_fe_tr
  * the call with ESVIO_FE_EINVAL, info->bad is exact and dst is unspecified.  More events than dst_cap also fail the call
  * with ESVIO_FE_EINVAL: info->events holds the exact number needed, dst is unspecified.  In both failures THE CAMERA'S
  * DECODER STATE IS AS IT WAS BEFORE THE CALL, and the next call works normally.  A trailing odd byte (EVT3) or a length
- * that is not a multiple of 4 (EVT2) is an argument error, raised before any device work.
+ * that is not a multiple of 4 (EVT2) or of 8 (EVT2.1) is an argument error, raised before any device work.
  *
- * Cutting the decoded stream into time-based batches is the next stage's business (esvio_fe_slice_events below).
- * Out of scope: EVT2.1, EVT4, AEDAT, the .raw file's ASCII header. */
+ * Cutting the decoded stream into time-based batches is the next stage's business (esvio_fe_slice_events below); the
+ * EXT_TRIGGER words of all three formats are decoded by esvio_fe_decode_triggers, a .raw file's ASCII header is read by
+ * esvio_fe_raw_header (both below).  Out of scope: EVT4, AEDAT, the half-swapped EVT2.1 layout, the payloads of OTHERS /
+ * CONTINUED words. */
 #define ESVIO_FE_RAW_EVT2 2
 #define ESVIO_FE_RAW_EVT3 3
+#define ESVIO_FE_RAW_EVT21 21
 typedef struct esvio_fe_raw_info {
   uint64_t events, untimed, other, bad, wraps; /* wraps: the camera's count after the call (before it, if it failed) */
   int64_t first_t_us, last_t_us;               /* ticks of the first / last emitted event; untouched if none */
@@ -695,7 +709,7 @@ typedef struct esvio_fe_raw_info {
  * read twice: KERNELS.md "Raw streams"); pageable memory is copied once into the handle's scratch, the 2 or 4 bytes
  * per word and nothing else.  dst: room for dst_cap records (ESVIO_FE_DEVICE: 16-byte aligned device memory, may be
  * handed to every entry point that takes device events, esvio_fe_set_next_batch included; ESVIO_FE_HOST: downloaded);
- * 12 * (n_bytes / 2) records (EVT3) or n_bytes / 4 (EVT2) always suffice.  info is optional.  n_bytes == 0 succeeds and
+ * 12 * (n_bytes / 2) records (EVT3), n_bytes / 4 (EVT2) or 4 * n_bytes (EVT2.1) always suffice.  info is optional.  n_bytes == 0 succeeds and
  * touches nothing; n_bytes <= 2^28.
  * Orders itself on the main stream, waits for its own result and touches nothing of the tracker: made between two
  * track calls (announced batches or not) it changes no later tracking result.  Its scratch — 32 bytes per 4096 bytes
@@ -728,6 +742,67 @@ int esvio_fe_track_raw(esvio_fe_handle h, int format, const void* left, size_t l
                        const void* right, size_t right_bytes, int space, int64_t t_offset_us,
                        int pub_this_frame, const esvio_fe_filter_params* filter, const esvio_fe_motion* motion,
                        esvio_fe_tracks* out, esvio_fe_batch_info* info, esvio_fe_raw_info raw[2]);
+
+/* ---- external triggers: the EXT_TRIGGER words of a raw stream -> trigger records, on the device ---- */
+/* In a stereo rig with frame cameras (DSEC, VECtor) the frame cameras' exposure signals are wired to the event sensors'
+ * trigger inputs, and the sensor writes one EXT_TRIGGER word per edge into its event stream: the frames' stamps on the
+ * events' own clock.  esvio_fe_decode_raw counts these words in `other`; this stage decodes them.  Like the formats
+ * above the layouts are RESTATED FROM RECALL of the published descriptions and UNPINNED; this text is the specification,
+ * tests/evt21_ref.py (decode_triggers) its sequential reading.
+ *
+ * A trigger word has type 0xA in its format's own type field:
+ *   EVT3    id = (w>>8)&0xF,   value = w&1;       t = wraps * 2^24 + th * 4096 + tl, taken at the word
+ *   EVT2    id = (w>>8)&0x1F,  value = w&1;       t = wraps * 2^34 + th * 64 + ((w>>22)&0x3F)
+ *   EVT2.1  id = (w>>40)&0x1F, value = (w>>32)&1; t = wraps * 2^34 + th * 64 + ((w>>54)&0x3F)
+ * TIME_HIGH (and EVT3's TIME_LOW) words act exactly as in the event decoder; every other word is skipped.  ticks, the
+ * sec / nsec conversion and the BAD rule are the event records'.  A trigger met while seen == 0 is not written: it is
+ * counted in `untimed`.  Triggers are written in word order; the record's padding bytes are 0.
+ *
+ * State: per handle and camera a decoder state OF ITS OWN (seen, th, wraps, tl), carried from call to call, cleared by
+ * esvio_fe_decode_reset and esvio_fe_reset, and left as it was by every failed call.  Running the same chunks through
+ * esvio_fe_decode_raw and through this call, in either order, therefore puts events and triggers on one time base.
+ *
+ * words / n_bytes / space / t_offset_us and their argument errors: as esvio_fe_decode_raw's, the three source paths
+ * included.  dst: a HOST array with room for dst_cap records.  More triggers than dst_cap: ESVIO_FE_EINVAL,
+ * info->triggers holds the number needed, the state is as it was; a BAD trigger: ESVIO_FE_EINVAL, info->bad exact, the
+ * state as it was.  info is optional; first_t_us / last_t_us are untouched when no trigger was written.  Three launches
+ * in the decode chain's shape (KERNELS.md "EVT2.1, triggers, windows at given stamps"); waits for its own result and
+ * touches nothing of the tracker. */
+typedef struct esvio_fe_trigger {
+  uint32_t sec, nsec;
+  uint8_t id, value;
+  uint8_t _pad[6];
+} esvio_fe_trigger;
+typedef struct esvio_fe_trigger_info {
+  uint64_t triggers, untimed, bad, wraps; /* wraps: the camera's trigger-decoder count after the call (before it, if it failed) */
+  int64_t first_t_us, last_t_us;
+} esvio_fe_trigger_info;
+int esvio_fe_decode_triggers(esvio_fe_handle h, int cam, int format, const void* words, size_t n_bytes, int space,
+                             int64_t t_offset_us, esvio_fe_trigger* dst, size_t dst_cap, esvio_fe_trigger_info* info);
+
+/* ---- the .raw file's ASCII header (host only, no handle) ----------------------------------- */
+/* A Prophesee .raw recording begins with text lines and goes on with the words.  The rule, RESTATED FROM RECALL and
+ * UNPINNED like the formats: the header is the maximal run of lines from byte 0 each of which begins with '%' and ends
+ * with '\n'; it ends in front of the first line that does not begin with '%', or behind a line "% end" (so payload
+ * bytes that happen to begin with '%' behind it are payload).  Inside it, with any blanks between '%' and the key and a
+ * trailing '\r' ignored:
+ *   "% evt 2.0" / "% evt 2.1" / "% evt 3.0"        the format: ESVIO_FE_RAW_EVT2 / _EVT21 / _EVT3
+ *   "% format EVT2|EVT21|EVT3[;key=value...]"       the format and, with width= / height= among the keys, the geometry;
+ *                                                   it wins over "% evt" wherever the two lines stand
+ *   "% geometry WxH"                                the geometry
+ * out: payload_offset = the index of the first payload byte, format and width / height (0: not stated), complete.
+ * complete == 0: the header's end does not lie inside the n bytes — they end inside a header line, or directly behind
+ * one that is not "% end" (the next line may be another; n == 0 is this case).  Nothing behind the last whole line was
+ * read, payload_offset is where the next line starts or started, format and geometry are those of the whole lines; read
+ * more and call again (a caller at the end of its file has a header-only file).  ESVIO_FE_EINVAL: null bytes with
+ * n > 0, null out. */
+typedef struct esvio_fe_raw_header_info {
+  uint64_t payload_offset;
+  int32_t format;        /* 0: unknown */
+  int32_t width, height; /* 0: unknown */
+  int32_t complete;
+} esvio_fe_raw_header_info;
+int esvio_fe_raw_header(const void* bytes, size_t n, esvio_fe_raw_header_info* out);
 
 /* ---- stream slicing: a record stream cut into fixed-rate windows, on the device ------------ */
 /* trackEvent takes one batch per camera and call; a recording or a sensor transfer is a long stream whose batch edges
@@ -811,6 +886,32 @@ int esvio_fe_slice_flush(esvio_fe_handle h, int cam, esvio_fe_slice_info* info);
 /* both cameras' slicer states back to the fresh state (esvio_fe_reset does the same as part of "as a freshly created
  * handle") */
 int esvio_fe_slice_reset(esvio_fe_handle h);
+/* Windows that end at GIVEN stamps — the frames' — instead of at first event + k / frequency.  In ESVIO mode the
+ * reference's estimator pops the front image-feature message and the front event-feature message as a pair, with no
+ * stamp check between them, integrates the IMU up to the image's stamp and treats the event features as observed then
+ * (esvio_estimator/src/stereo_estimator_node.cpp:143-167): a caller that has the frame stamps — from
+ * esvio_fe_decode_triggers, or from a dataset's timestamp file — wants its event windows to end there.
+ *
+ * bounds: a HOST array of n_bounds <= ESVIO_FE_SLICE_MAX_WINDOWS records of which only sec / nsec are read:
+ * b_k = (double)sec + 1e-9 * (double)nsec.  They must be non-decreasing (else ESVIO_FE_EINVAL before any device work)
+ * and are the ends of windows m_start, m_start + 1, ..., m_start being the camera's closed count at the call.  With
+ * m_{-1} = m_start:
+ *   c_i = m_start + #{k : b_k <= ts_i};   m_i = max(m_{i-1}, c_i);   event i belongs to window m_i.
+ * So an event at a boundary closes the window, equal boundaries give empty windows, an event that steps back stays in
+ * the open window, and events at or beyond the last given boundary belong to the open window m_start + n_bounds — that
+ * is no failure: the caller passes bounds + closed, and newer boundaries behind them, next time.  Associative like its
+ * sibling: slice_at(whole, B) = slice_at(part 1, B) then slice_at(part 2, B + closed_1) at every cut.  The sequential
+ * reading is tests/slice_at_ref.py.
+ * ev / n / space, cuts / cuts_cap and info exactly as esvio_fe_slice_events'; first_ / last_sec / nsec are the closing
+ * boundaries' own words, copied.  n_bounds == 0 is allowed (bounds may then be null): nothing closes.
+ * Mode: a camera's first call with n > 0 of either entry point fixes fixed-rate or explicit mode; the other entry point
+ * is ESVIO_FE_EINVAL until esvio_fe_slice_reset.  ESVIO_FE_EINVAL while a feed is open, like its sibling (the feed
+ * itself cuts at fixed rate only).  esvio_fe_slice_flush in explicit mode closes the open window — closed = 1,
+ * first_window = its index, open_events = 0 — and leaves the four stamp fields untouched: the window has no boundary.
+ * The three launches are esvio_fe_slice_events' own, over a table of the caller's stamps. */
+int esvio_fe_slice_events_at(esvio_fe_handle h, int cam, const esvio_fe_event* ev, size_t n, int space,
+                             const esvio_fe_event* bounds, size_t n_bounds, uint64_t* cuts, size_t cuts_cap,
+                             esvio_fe_slice_info* info);
 
 /* ---- the feed: chunks of a stereo stream in, time-aligned windows tracked where they lie ---- */
 /* A small layer over the stages above for a caller that holds a recording or a sensor transfer, not batches: chunks of

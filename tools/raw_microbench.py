@@ -9,11 +9,13 @@ pageable memory, into device memory; for page-locked words also the first 4 .. 5
 reading in place stops paying).  Beside it the sequential decoder the call replaces (tools/raw_seq_decode.cpp on
 one core, + esvio_fe_mem_upload of its records), and esvio_fe_track_raw from pageable words against esvio_fe_track_event
 from pageable records on the same events: plain calls, two handles of one configuration, A/B in one process, ROUNDS
-alternations.  Per figure: the median of BLOCKS blocks after a warm-up block, and the blocks' min - max.  One process,
+alternations.  Per figure: the median of BLOCKS blocks after a warm-up block, and the blocks' min - max.  Also EVT2.1
+(the greedy encoder of tests/evt21_ref.py, and n / 32 words with full masks: 32 records per word), and per encoding
+esvio_fe_decode_triggers on the same words in device memory with a frame's two edges appended.  One process,
 one pass, no retries; run it under a time limit:
 
     g++ -O2 -std=c++17 tools/raw_seq_decode.cpp -o tools/_bin/raw_seq_decode
-    timeout -k 10 900 python tools/raw_microbench.py [--json out.json] [--only C3]
+    timeout -k 10 900 python tools/raw_microbench.py [--json out.json] [--only C3] [--formats evt21,evt2] [--device-only]
 """
 import ctypes as C
 import json
@@ -28,6 +30,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np  # noqa: E402
 
+import evt21_ref as E21  # noqa: E402
 import evt_ref as R  # noqa: E402
 from esvio_amd import frontend as FE  # noqa: E402
 from esvio_amd.events import event_times, make_events  # noqa: E402
@@ -76,6 +79,38 @@ def encode_evt3_novect_np(x, y, p, t):
     return out.astype("<u2")
 
 
+def encode_evt21_np(x, y, p, t):
+    """evt21_ref.encode_evt21 with the loop only inside runs of equal (t, y, p) and increasing x (rare in the scene stream)"""
+    n = len(t)
+    brk = changed(t) | changed(y) | changed(p)
+    brk[1:] |= x[1:] <= x[:-1]
+    starts = np.flatnonzero(brk)
+    ends = np.append(starts[1:], n)
+    word_start = brk.copy()
+    for s in np.flatnonzero(ends - starts > 1):
+        i = int(starts[s])
+        for j in range(i + 1, int(ends[s])):
+            if x[j] - x[i] >= 32:
+                word_start[j] = True
+                i = j
+    ws = np.flatnonzero(word_start)
+    wid = np.cumsum(word_start) - 1
+    mask = np.zeros(len(ws), np.uint64)
+    np.bitwise_or.at(mask, wid, np.uint64(1) << (x - x[ws][wid]).astype(np.uint64))
+    u = [a[ws].astype(np.uint64) for a in (p, t & 0x3F, x, y)]
+    ev = (u[0] << np.uint64(60)) | (u[1] << np.uint64(54)) | (u[2] << np.uint64(43)) | (u[3] << np.uint64(32)) | mask
+    h = changed(t[ws] >> 6)
+    pos = np.cumsum(h + 1) - 1
+    out = np.zeros(int(pos[-1]) + 1, np.uint64)
+    out[pos] = ev
+    out[pos[h] - 1] = (np.uint64(8) << np.uint64(60)) | ((t[ws][h] >> 6).astype(np.uint64) << np.uint64(32))
+    return out.astype("<u8")
+
+
+FORMATS = None  # --formats evt21,evt2: only these encodings are built and measured (the EVT3 loop encoder takes minutes at C5)
+DEVICE_ONLY = False  # --device-only: the per-launch figures from device memory and the trigger call; no host sources, no track A/B
+
+
 def encodings(ev, base):
     x, y, p, t = fields_of(ev)
     o = R.readout_order(x, y, p, t)
@@ -83,10 +118,65 @@ def encodings(ev, base):
     k = min(len(x), 20000)
     assert np.array_equal(encode_evt2_np(xr[:k], yr[:k], pr[:k], tr[:k]), R.encode_evt2(xr[:k], yr[:k], pr[:k], tr[:k]))
     assert np.array_equal(encode_evt3_novect_np(xr[:k], yr[:k], pr[:k], tr[:k]), R.encode_evt3(xr[:k], yr[:k], pr[:k], tr[:k], vect=False))
+    assert np.array_equal(encode_evt21_np(xr[:k], yr[:k], pr[:k], tr[:k]), E21.encode_evt21(xr[:k], yr[:k], pr[:k], tr[:k]))
     rec = make_events(xr, yr, tr + base, pr)
-    return rec, (("EVT3, read-out order, vectors", R.EVT3, R.encode_evt3(xr, yr, pr, tr)),
-                 ("EVT3, no vectors", R.EVT3, encode_evt3_novect_np(xr, yr, pr, tr)),
-                 ("EVT2", R.EVT2, encode_evt2_np(xr, yr, pr, tr)))
+    makers = (("EVT3, read-out order, vectors", "evt3", R.EVT3, lambda: R.encode_evt3(xr, yr, pr, tr)),
+              ("EVT3, no vectors", "evt3nv", R.EVT3, lambda: encode_evt3_novect_np(xr, yr, pr, tr)),
+              ("EVT2", "evt2", R.EVT2, lambda: encode_evt2_np(xr, yr, pr, tr)),
+              ("EVT2.1", "evt21", FE.RAW_EVT21, lambda: encode_evt21_np(xr, yr, pr, tr)))
+    return rec, tuple((name, fmt, make()) for name, key, fmt, make in makers if FORMATS is None or key in FORMATS)
+
+
+def dense_evt21(n, W, base):
+    """n // 32 EVT2.1 words with full masks behind one TIME_HIGH — 32 records per word, the format's densest — and the
+    records they stand for: what the emit launch does when its stores, not its walk, are the work"""
+    k = np.arange(n // 32, dtype=np.int64)
+    per_row = W // 32
+    bx, y = (k % per_row) * 32, (k // per_row) % 2048
+    words = np.empty(len(k) + 1, np.uint64)
+    words[0] = (np.uint64(8) << np.uint64(60)) | (np.uint64(20) << np.uint64(32))
+    words[1:] = (np.uint64(1) << np.uint64(60)) | (np.uint64(5) << np.uint64(54)) | (bx.astype(np.uint64) << np.uint64(43)) | \
+        (y.astype(np.uint64) << np.uint64(32)) | np.uint64(0xFFFFFFFF)
+    x = (bx[:, None] + np.arange(32)[None, :]).reshape(-1)
+    rec = make_events(x, np.repeat(y, 32), np.full(len(x), 20 * 64 + 5 + base, np.int64), np.ones(len(x), np.int64))
+    return rec, words.astype("<u8")
+
+
+def trigger_bench(L, ft, tag, name, fmt, words, base, arena, rows):
+    """esvio_fe_decode_triggers on the same words in device memory, with a frame's two edges appended: the call's wall
+    time and its launches (the scan is k_raw_scan)"""
+    wd = words.dtype
+    edge = {R.EVT3: [0xA001, 0xA000], R.EVT2: [0xA0000001, 0xA0000000], FE.RAW_EVT21: [(0xA << 60) | (1 << 32), 0xA << 60]}[fmt]
+    w = np.concatenate([words, np.array(edge, np.uint64).astype(wd)])
+    nb = w.nbytes
+    _, _, dsrc, _ = arena
+    assert L.esvio_fe_mem_upload(dsrc, C.c_void_p(w.ctypes.data), nb) == 0
+    out, info = (FE.Trigger * 8)(), FE.TriggerInfo()
+
+    def call():
+        ft.decode_reset()
+        assert L.esvio_fe_decode_triggers(ft._hd.h, 0, fmt, dsrc, nb, FE.DEVICE, base, C.byref(out), 8, C.byref(info)) == 0
+    for _ in range(REPS):
+        call()
+    assert info.triggers == 2 and (out[0].value, out[1].value) == (1, 0)
+    ks, call_us = {k: [] for k in ("k_trig_reduce", "k_raw_scan", "k_trig_emit")}, []
+    for _ in range(BLOCKS):
+        ft.set_profiling(True)
+        ft.reset_kernel_stats()
+        t0 = time.perf_counter()
+        for _ in range(REPS):
+            call()
+        call_us.append((time.perf_counter() - t0) / REPS * 1e6)
+        st = ft.kernel_stats(stages=True)
+        ft.set_profiling(False)
+        for k in ks:
+            assert st[k]["launches"] == REPS
+            ks[k].append(st[k]["ms"] / REPS * 1e3)
+    c = med(call_us)
+    k = {name_: med(v) for name_, v in ks.items()}
+    print("    %-18s trig reduce %7.1f us | scan %6.1f us | trig emit %7.1f us | call %8.1f us (%.1f - %.1f), 2 triggers"
+          % ("triggers, device", k["k_trig_reduce"][0], k["k_raw_scan"][0], k["k_trig_emit"][0], c[0], c[1], c[2]))
+    rows.append(dict(batch=tag, encoding=name, source="device", stage="triggers", word_bytes=nb, kernels_us=k, call_us=c))
 
 
 def stage_bench(L, ft, ft_copy, tag, rec, name, fmt, words, base, arena, rows):
@@ -98,6 +188,9 @@ def stage_bench(L, ft, ft_copy, tag, rec, name, fmt, words, base, arena, rows):
     info = FE.RawInfo()
     for src, tr, ptr, space in (("device", ft, dsrc, FE.DEVICE), ("pinned, in place", ft, pin, FE.HOST),
                                 ("pinned, copy first", ft_copy, pin, FE.HOST), ("pageable", ft, C.c_void_p(words.ctypes.data), FE.HOST)):
+        if DEVICE_ONLY and src != "device":
+            continue
+
         def call():
             tr.decode_reset()
             assert L.esvio_fe_decode_raw(tr._hd.h, 0, fmt, ptr, nb, space, base, ddst, n, FE.DEVICE, C.byref(info)) == 0
@@ -133,7 +226,8 @@ def stage_bench(L, ft, ft_copy, tag, rec, name, fmt, words, base, arena, rows):
                  nb + 32 * tiles, 16 * n, emit_gbs, 100 * emit_gbs / HBM_GBS, c[0], c[1], c[2], n / c[0]))
         rows.append(dict(batch=tag, encoding=name, n=n, word_bytes=nb, bytes_per_event=nb / n, source=src, kernels_us=k, call_us=c,
                          emit_store_gbs=emit_gbs, emit_hbm_frac=emit_gbs / HBM_GBS, mev_s_call=n / c[0]))
-    if os.path.exists(SEQ):  # the path without the call: one core decodes, then the records are uploaded
+    trigger_bench(L, ft, tag, name, fmt, words, base, arena, rows)
+    if os.path.exists(SEQ) and fmt != FE.RAW_EVT21 and not DEVICE_ONLY:  # the path without the call: one core decodes, then the records are uploaded
         with tempfile.NamedTemporaryFile(suffix=".words") as f:
             f.write(words.tobytes())
             f.flush()
@@ -218,7 +312,11 @@ def track_ab(tag, W, H, frames, base, rows):
 
 def main():
     L = FE.load_library()
+    global FORMATS, DEVICE_ONLY
     only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else None
+    if "--formats" in sys.argv:
+        FORMATS = set(sys.argv[sys.argv.index("--formats") + 1].split(","))
+    DEVICE_ONLY = "--device-only" in sys.argv
     rows = []
     for tag, W, H, rate, n_frames in SHAPES:
         if only and tag != only:
@@ -226,7 +324,7 @@ def main():
         st = SceneStream(W=W, H=H, rate=rate, seed=3)
         base = st.t_us - 1000
         frames = []
-        for _ in range(n_frames):
+        for _ in range(1 if DEVICE_ONLY else n_frames):
             left, right, _ = st.next_batch()
             fr = dict(rec=[], words={})
             encs = []
@@ -251,14 +349,18 @@ def main():
         pinned = np.ctypeslib.as_array(C.cast(pin, C.POINTER(C.c_uint8)), shape=(cap,))
         for name, (fmt, wl, _) in frames[0]["words"].items():
             stage_bench(L, ft, ft_copy, tag, rec, name, fmt, wl, base, (pin, pinned, dsrc, ddst), rows)
-            if tag == "C3" and name != "EVT3, no vectors":
+            if fmt == FE.RAW_EVT21:
+                drec, dwords = dense_evt21(len(rec), W, base)
+                stage_bench(L, ft, ft_copy, tag, drec, "EVT2.1, full masks", fmt, dwords, base, (pin, pinned, dsrc, ddst), rows)
+            if tag == "C3" and name != "EVT3, no vectors" and not DEVICE_ONLY:
                 pinned_sweep(L, ft, ft_copy, tag, name, fmt, wl, len(rec), base, (pin, pinned, dsrc, ddst), rows)
         L.esvio_fe_mem_free(FE.HOST, pin)
         L.esvio_fe_mem_free(FE.DEVICE, dsrc)
         L.esvio_fe_mem_free(FE.DEVICE, ddst)
         ft.close()
         ft_copy.close()
-        track_ab(tag, W, H, frames, base, rows)
+        if not DEVICE_ONLY:
+            track_ab(tag, W, H, frames, base, rows)
     if "--json" in sys.argv:
         with open(sys.argv[sys.argv.index("--json") + 1], "w") as fo:
             json.dump(rows, fo, indent=1)
