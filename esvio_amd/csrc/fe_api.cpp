@@ -237,6 +237,7 @@ int esvio_fe_create(const esvio_fe_config* cfg, esvio_fe_handle* out) {
   c->fast_lds = getenv("ESVIO_FE_FAST_LDS") != nullptr;
   if (const char* v = getenv("ESVIO_FE_CONVERT_PINNED_COPY")) c->cvt_pinned_copy = atoi(v) != 0 ? 1 : 0;
   if (const char* v = getenv("ESVIO_FE_RAW_PINNED_COPY")) c->rawdec.pinned_copy = atoi(v) != 0 ? 1 : 0;
+  if (const char* v = getenv("ESVIO_FE_AEDAT_WAVE_LOOKUP")) c->aedat.wave_lookup = atoi(v) != 0 ? 1 : 0;
   c->select_one_wave = getenv("ESVIO_FE_SELECT_SERIAL") != nullptr;
   if (const char* v = getenv("ESVIO_FE_SAE_EV_MIN")) c->sae_ev_min = (size_t)strtoull(v, nullptr, 10);
   c->tiled = make_tile_geom(c->W, c->H, &c->tgeom) && getenv("ESVIO_FE_SAE_SORT") == nullptr;
@@ -394,6 +395,7 @@ int esvio_fe_reset(esvio_fe_handle c) {
   if (int rc = hot_clear(c)) return rc;  // hot-pixel learning: nothing counted (the address filter and the mask are settings: kept)
   c->rawdec.st[0] = c->rawdec.st[1] = esvio_fe_ctx::Raw::State();  // the raw-stream decoder: the fresh state
   c->rawdec.trig_st[0] = c->rawdec.trig_st[1] = esvio_fe_ctx::Raw::State();  // ... and the trigger decoder's
+  for (int cam = 0; cam < 2; cam++) c->aedat.ev_st[cam] = c->aedat.side_st[cam] = esvio::aedat::Walk{};  // ... and the AEDAT walkers'
   c->slice.st[0] = c->slice.st[1] = esvio_fe_ctx::Slice::State();  // the stream slicer: no event seen, no window closed
   HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
   feed_empty(c, true);  // an open feed: no records, no windows (it stays open); every stream is idle here
@@ -2008,6 +2010,7 @@ int esvio_fe_decode_reset(esvio_fe_handle c) {
   if (!c) return ESVIO_FE_EINVAL;
   c->rawdec.st[0] = c->rawdec.st[1] = esvio_fe_ctx::Raw::State();
   c->rawdec.trig_st[0] = c->rawdec.trig_st[1] = esvio_fe_ctx::Raw::State();
+  for (int cam = 0; cam < 2; cam++) c->aedat.ev_st[cam] = c->aedat.side_st[cam] = esvio::aedat::Walk{};
   return 0;
 }
 
@@ -2228,6 +2231,285 @@ int esvio_fe_track_raw(esvio_fe_handle c, int format, const void* left, size_t l
   if (info_out) *info_out = info;
   return done(rc);
 }
+
+// ---- libcaer / AEDAT 3.1 packet streams (the rule: include/esvio_fe.h; the host walk: fe_aedat.h; the chain: fe_kernels.h)
+namespace {
+namespace ae = esvio::aedat;
+static_assert(sizeof(ae::Run) == sizeof(AedatRun), "the walk's run table is the kernels'");
+struct AedatJob {  // one camera's part of a call
+  const void* bytes = nullptr;
+  size_t n_bytes = 0;
+  EventRec* d_dst = nullptr;
+  size_t cap = 0;
+  ae::Walk st{};   // the camera's state behind the chunk: taken over when the call succeeds
+  ae::Out cnt;     // what the counting walk found: n_events, n_runs, the packets
+};
+
+int aedat_args_check(esvio_fe_ctx* c, const char* who, const void* bytes, size_t n_bytes, int64_t t_offset_ns, uint32_t flags) {
+  if (flags & ~(uint32_t)ESVIO_FE_AEDAT_KEEP_INVALID) return fail(c, ESVIO_FE_EINVAL, "%s: unknown bits in flags (0x%x)", who, flags);
+  const int64_t lim = (int64_t)1 << 62;
+  if (t_offset_ns > lim || t_offset_ns < -lim) return fail(c, ESVIO_FE_EINVAL, "%s: |t_offset_ns| must be <= 2^62", who);
+  if (n_bytes > kRawMaxBytes) return fail(c, ESVIO_FE_EINVAL, "%s: a chunk holds at most 2^28 bytes", who);
+  if (n_bytes && !bytes) return fail(c, ESVIO_FE_EINVAL, "%s: bytes is null", who);
+  return 0;
+}
+// the counting walk: every header of the chunk checked, the records and runs counted, nothing stored, no state moved
+int aedat_count_walk(esvio_fe_ctx* c, const char* who, int cam, AedatJob* j) {
+  ae::Walk probe = c->aedat.ev_st[cam];
+  j->cnt = ae::Out();
+  if (!ae::walk(&probe, ae::kEvents, (const uint8_t*)j->bytes, j->n_bytes, 0, 0, &j->cnt))
+    return fail(c, ESVIO_FE_EINVAL, "%s: malformed packet header (%s); the camera's state is as it was", who, j->cnt.why);
+  return 0;
+}
+void aedat_info_packets(esvio_fe_aedat_info* info, const ae::Out& o) {
+  if (info) info->polarity_packets = o.polarity_packets, info->other_packets = o.other_packets;
+}
+uint32_t aedat_tiles(size_t n) { return (uint32_t)((n + kAedatTile - 1) / kAedatTile); }
+size_t aedat_runs_offset(size_t n_events) { return (n_events * 8 + 15) & ~(size_t)15; }
+int aedat_ensure(esvio_fe_ctx* c, int cam, size_t n_events, size_t n_runs) {
+  esvio_fe_ctx::Aedat& A = c->aedat;
+  A.used = true;
+  if (!A.res)
+    if (int rc = A.res.alloc(c, 2)) return rc;
+  const size_t bytes = aedat_runs_offset(n_events) + n_runs * sizeof(AedatRun);
+  if (int rc = A.sums[cam].grow(c, aedat_tiles(n_events))) return rc;
+  if (int rc = A.h_pack[cam].grow(c, bytes)) return rc;
+  return A.d_pack[cam].grow(c, bytes);
+}
+// The gathering walk and the chain of one camera (job[1].n_bytes == 0) or of both on the current stream, and the copies
+// that bring the result blocks to the host; nothing is waited for.  A camera whose chunk completes no polarity record
+// takes no part on the device.
+int aedat_enqueue(esvio_fe_ctx* c, int64_t t_offset_ns, uint32_t flags, AedatJob job[2], const int cam_of[2], AedatResult res[2]) {
+  esvio_fe_ctx::Aedat& A = c->aedat;
+  hipStream_t s = cur_stream(c);
+  const bool keep = (flags & ESVIO_FE_AEDAT_KEEP_INVALID) != 0;
+  AedatArgs a{};
+  uint64_t n_all = 0, cap_all = 0;
+  for (int k = 0; k < 2; k++) {
+    if (!job[k].n_bytes) continue;
+    const int cam = cam_of[k];
+    const size_t n = (size_t)job[k].cnt.n_events, n_runs = (size_t)job[k].cnt.n_runs, roff = aedat_runs_offset(n);
+    job[k].st = A.ev_st[cam];
+    ae::Out o;
+    if (n) {
+      if (int rc = aedat_ensure(c, cam, n, n_runs)) return rc;
+      o.payload = A.h_pack[cam], o.events_cap = n;
+      o.runs = (ae::Run*)(A.h_pack[cam] + roff), o.runs_cap = n_runs;
+    }
+    ae::walk(&job[k].st, ae::kEvents, (const uint8_t*)job[k].bytes, job[k].n_bytes, 0, 0, &o);  // (checked by the counting walk)
+    if (!n) continue;
+    HIPCHK(c, hipMemcpyAsync(A.d_pack[cam], A.h_pack[cam], roff + n_runs * sizeof(AedatRun), hipMemcpyHostToDevice, s));
+    AedatCam& ac = a.cam[k];
+    ac.rec = (const uint2*)A.d_pack[cam].p, ac.n = (uint32_t)n, ac.tiles = aedat_tiles(n);
+    ac.runs = (const AedatRun*)(A.d_pack[cam].p + roff), ac.n_runs = (uint32_t)n_runs;
+    ac.keep_invalid = keep, ac.wave_lookup = (uint32_t)A.wave_lookup, ac.t_offset = t_offset_ns, ac.sums = A.sums[cam];
+    ac.dst = job[k].d_dst, ac.dst_cap = (uint32_t)std::min<size_t>(job[k].cap, 0xffffffffu);
+    ac.res = A.res + cam;
+    n_all += n, cap_all += std::min(job[k].cap, n);
+    if (keep) HIPCHK(c, hipMemsetAsync(ac.res, 0, sizeof(AedatResult), s));  // (events = n: the host's own knowledge)
+  }
+  if (!n_all) return 0;
+  const uint64_t tiles = a.cam[0].tiles + a.cam[1].tiles;
+  if (!keep) {
+    {
+      ScopedKernel k(c, K_AEDAT_COUNT, n_all * 8 + tiles * 4);
+      launch_aedat_count(s, a);
+    }
+    {
+      ScopedKernel k(c, K_AEDAT_SCAN, tiles * 8);
+      launch_aedat_scan(s, a);
+    }
+  }
+  {  // (booked as if every record the buffers have room for were written: the count is not known here)
+    ScopedKernel k(c, K_AEDAT_EMIT, n_all * 8 + cap_all * 16);
+    launch_aedat_emit(s, a);
+  }
+  for (int k = 0; k < 2; k++)
+    if (a.cam[k].tiles) HIPCHK(c, hipMemcpyAsync(&res[k], a.cam[k].res, sizeof(AedatResult), hipMemcpyDeviceToHost, s));
+  return 0;
+}
+// behind the wait: what the host knows itself
+void aedat_result_fix(const AedatJob& j, uint32_t flags, AedatResult* r) {
+  if ((flags & ESVIO_FE_AEDAT_KEEP_INVALID) && j.cnt.n_events) r->events = (uint32_t)j.cnt.n_events, r->invalid = 0;
+}
+void aedat_info_fill(esvio_fe_aedat_info* info, const AedatResult& r) {
+  if (!info) return;
+  info->events = r.events, info->invalid = r.invalid, info->bad = r.bad;
+  if (r.events && !r.bad) info->first_t_us = (int64_t)(r.first_t / 1000u), info->last_t_us = (int64_t)(r.last_t / 1000u);
+}
+void aedat_info_clear(esvio_fe_aedat_info* info) {
+  if (info) info->events = info->invalid = info->bad = info->polarity_packets = info->other_packets = 0;
+}
+}  // namespace
+
+int esvio_fe_aedat_tile_events(void) { return (int)kAedatTile; }
+
+int esvio_fe_aedat_header(const void* bytes, size_t n, esvio_fe_aedat_header_info* out) { return ae::file_header(bytes, n, out); }
+
+int esvio_fe_decode_aedat(esvio_fe_handle c, int cam, const void* bytes, size_t n_bytes, int64_t t_offset_ns, uint32_t flags,
+                          esvio_fe_event* dst, size_t dst_cap, int dst_space, esvio_fe_aedat_info* info) {
+  if (!c) return ESVIO_FE_EINVAL;
+  aedat_info_clear(info);
+  if (cam != 0 && cam != 1) return fail(c, ESVIO_FE_EINVAL, "decode_aedat: cam must be 0 or 1 (got %d)", cam);
+  if (int rc = aedat_args_check(c, "decode_aedat", bytes, n_bytes, t_offset_ns, flags)) return rc;
+  if (dst_space != ESVIO_FE_HOST && dst_space != ESVIO_FE_DEVICE) return fail(c, ESVIO_FE_EINVAL, "decode_aedat: bad memory space");
+  if (dst_cap && !dst) return fail(c, ESVIO_FE_EINVAL, "decode_aedat: dst is null");
+  if (dst_space == ESVIO_FE_DEVICE && ((uintptr_t)dst & 15) != 0)
+    return fail(c, ESVIO_FE_EINVAL, "decode_aedat: a device dst must be 16-byte aligned");
+  if (!n_bytes) return 0;
+  AedatJob job[2];
+  job[0].bytes = bytes, job[0].n_bytes = n_bytes;
+  if (int rc = aedat_count_walk(c, "decode_aedat", cam, &job[0])) return rc;
+  aedat_info_packets(info, job[0].cnt);
+  HIPCHK(c, hipSetDevice(c->dev));
+  const size_t bound = (size_t)job[0].cnt.n_events;
+  job[0].d_dst = (EventRec*)dst, job[0].cap = std::min(dst_cap, bound);
+  if (dst_space == ESVIO_FE_HOST && job[0].cap) {  // the records behind a host dst
+    if (int rc = c->rawdec.dec[cam].grow(c, job[0].cap)) return rc;
+    job[0].d_dst = c->rawdec.dec[cam];
+  }
+  const int cam_of[2] = {cam, cam};
+  AedatResult r[2] = {};
+  if (int rc = aedat_enqueue(c, t_offset_ns, flags, job, cam_of, r)) return rc;
+  HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  if (c->prof_on) resolve_profile(c);
+  aedat_result_fix(job[0], flags, &r[0]);
+  aedat_info_fill(info, r[0]);
+  if (r[0].bad)
+    return fail(c, ESVIO_FE_EINVAL, "decode_aedat: %llu of %u events have a stamp outside [0, 2^32 s); the camera's state is as it was",
+                r[0].bad, r[0].events);
+  if (r[0].events > dst_cap)
+    return fail(c, ESVIO_FE_EINVAL, "decode_aedat: the chunk holds %u events, dst has room for %zu; the camera's state is as it was",
+                r[0].events, dst_cap);
+  if (dst_space == ESVIO_FE_HOST && r[0].events) {
+    HIPCHK(c, hipMemcpyAsync(dst, job[0].d_dst, (size_t)r[0].events * sizeof(EventRec), hipMemcpyDeviceToHost, cur_stream(c)));
+    HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  }
+  c->aedat.ev_st[cam] = job[0].st;
+  return 0;
+}
+
+int esvio_fe_aedat_side(esvio_fe_handle c, int cam, const void* bytes, size_t n_bytes, int64_t t_offset_ns, uint32_t flags,
+                        esvio_fe_imu_sample* imu, size_t imu_cap, esvio_fe_trigger* trig, size_t trig_cap,
+                        esvio_fe_aedat_side_info* info) {
+  if (!c) return ESVIO_FE_EINVAL;
+  if (info) *info = esvio_fe_aedat_side_info{};
+  if (cam != 0 && cam != 1) return fail(c, ESVIO_FE_EINVAL, "aedat_side: cam must be 0 or 1 (got %d)", cam);
+  if (int rc = aedat_args_check(c, "aedat_side", bytes, n_bytes, t_offset_ns, flags)) return rc;
+  if (imu_cap && !imu) return fail(c, ESVIO_FE_EINVAL, "aedat_side: imu is null");
+  if (trig_cap && !trig) return fail(c, ESVIO_FE_EINVAL, "aedat_side: trig is null");
+  if (!n_bytes) return 0;
+  ae::Walk st = c->aedat.side_st[cam];
+  ae::Out o;
+  o.imu = imu, o.imu_cap = imu_cap, o.trig = trig, o.trig_cap = trig_cap;
+  if (!ae::walk(&st, ae::kSide, (const uint8_t*)bytes, n_bytes, t_offset_ns, flags, &o))
+    return fail(c, ESVIO_FE_EINVAL, "aedat_side: malformed packet header (%s); the camera's state is as it was", o.why);
+  if (info) {
+    info->imu = o.n_imu, info->triggers = o.n_trig, info->resets = o.resets, info->other_specials = o.other_specials;
+    info->invalid = o.invalid, info->bad = o.bad;
+    info->special_packets = o.special_packets, info->imu_packets = o.imu_packets, info->other_packets = o.other_packets;
+  }
+  if (o.bad)
+    return fail(c, ESVIO_FE_EINVAL, "aedat_side: %llu samples or triggers have a stamp outside [0, 2^32 s); the camera's state is as it was",
+                (unsigned long long)o.bad);
+  if (o.n_imu > imu_cap || o.n_trig > trig_cap)
+    return fail(c, ESVIO_FE_EINVAL, "aedat_side: the chunk holds %llu samples and %llu triggers, there is room for %zu and %zu; the camera's state is as it was",
+                (unsigned long long)o.n_imu, (unsigned long long)o.n_trig, imu_cap, trig_cap);
+  c->aedat.side_st[cam] = st;
+  return 0;
+}
+
+int esvio_fe_track_aedat(esvio_fe_handle c, const void* left, size_t left_bytes, const void* right, size_t right_bytes,
+                         int64_t t_offset_ns, uint32_t flags, int pub_this_frame, const esvio_fe_filter_params* filter,
+                         const esvio_fe_motion* motion, esvio_fe_tracks* out, esvio_fe_batch_info* info_out,
+                         esvio_fe_aedat_info aedat[2]) {
+  if (!c) return ESVIO_FE_EINVAL;
+  esvio_fe_batch_info info{};
+  if (info_out) *info_out = info;
+  AedatJob job[2];
+  job[0].bytes = left, job[0].n_bytes = left_bytes, job[1].bytes = right, job[1].n_bytes = right_bytes;
+  for (int cam = 0; cam < 2; cam++) {
+    if (aedat) aedat_info_clear(&aedat[cam]);
+    if (int rc = aedat_args_check(c, cam ? "track_aedat (right)" : "track_aedat (left)", job[cam].bytes, job[cam].n_bytes, t_offset_ns, flags))
+      return rc;
+  }
+  if (filter)
+    if (int rc = baf_prm_check(c, filter, "track_aedat")) return rc;
+  if (!c->announced.empty() || !c->inflight.empty())
+    return fail(c, ESVIO_FE_EINVAL, "track_aedat: batches are announced on this handle (decode into memory of your own)");
+  if (!left_bytes && !right_bytes) return 0;  // nothing to decode: no left event, nothing tracked
+  for (int cam = 0; cam < 2; cam++) {
+    if (int rc = aedat_count_walk(c, cam ? "track_aedat (right)" : "track_aedat (left)", cam, &job[cam])) return rc;
+    if (aedat) aedat_info_packets(&aedat[cam], job[cam].cnt);
+  }
+  HIPCHK(c, hipSetDevice(c->dev));
+  // where the records go: the current pair, or, in front of a filter, the decode stage's own buffers; the capacity is the
+  // host-known count of the chunk's records
+  const size_t want[2] = {(size_t)job[0].cnt.n_events, (size_t)job[1].cnt.n_events};
+  if (filter) {
+    for (int cam = 0; cam < 2; cam++) {
+      if (int rc = c->rawdec.dec[cam].grow(c, std::max<size_t>(want[cam], 1))) return rc;
+      job[cam].d_dst = c->rawdec.dec[cam], job[cam].cap = c->rawdec.dec[cam].cap;
+    }
+  } else {
+    const int pair = c->cvt_pair;
+    if (int rc = cvt_pair_begin(c, want[0], want[1], &job[0].d_dst, &job[1].d_dst)) return rc;
+    job[0].cap = c->d_cvt_ev[pair][0].cap, job[1].cap = c->d_cvt_ev[pair][1].cap;
+  }
+  const int cam_of[2] = {0, 1};
+  AedatResult r[2] = {};
+  if (int rc = aedat_enqueue(c, t_offset_ns, flags, job, cam_of, r)) return rc;
+  HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  if (c->prof_on) resolve_profile(c);
+  for (int cam = 0; cam < 2; cam++) {
+    aedat_result_fix(job[cam], flags, &r[cam]);
+    if (aedat && job[cam].n_bytes) aedat_info_fill(&aedat[cam], r[cam]);
+    info.bad[cam] = r[cam].bad;
+  }
+  if (r[0].bad || r[1].bad) {
+    if (info_out) *info_out = info;
+    return fail(c, ESVIO_FE_EINVAL, "track_aedat: %llu of %u events have a stamp outside [0, 2^32 s); both cameras' states are as they were",
+                r[0].bad + r[1].bad, r[0].events + r[1].events);
+  }
+  // the walker states move only when the whole call succeeds: a filter or track body that fails leaves them as they were
+  auto done = [&](int rc) {
+    for (int cam = 0; cam < 2 && rc == 0; cam++)
+      if (job[cam].n_bytes) c->aedat.ev_st[cam] = job[cam].st;
+    return rc;
+  };
+  if (filter) {
+    esvio_fe_batch b{};
+    b.left = (const esvio_fe_event*)job[0].d_dst, b.right = (const esvio_fe_event*)job[1].d_dst;
+    b.nL = r[0].events, b.nR = r[1].events, b.space = ESVIO_FE_DEVICE, b.pub_this_frame = pub_this_frame;
+    b.filter = filter, b.motion = motion, b.cur_time_from_batch = 1;
+    return done(track_batch_body(c, "track_aedat", "decode and filter", b, out, info_out));
+  }
+  info.kept[0] = r[0].events, info.kept[1] = r[1].events;
+  if (info_out) *info_out = info;
+  if (!r[0].events) return done(0);  // node:150: an empty left message is not tracked
+  const uint64_t ticks = r[0].last_t;
+  info.cur_time = (double)(uint32_t)(ticks / 1000000000u) + 1e-9 * (double)(uint32_t)(ticks % 1000000000u);
+  const int rc = cvt_pair_track(c, info.cur_time, job[0].d_dst, r[0].events, job[1].d_dst, r[1].events, pub_this_frame, motion, out);
+  info.tracked = rc == 0;
+  if (info_out) *info_out = info;
+  return done(rc);
+}
+
+// the walk tap (include/esvio_fe_test.h): the host walk alone, no handle, no device
+int esvio_fe_aedat_walk_tap(void* state, size_t state_bytes, const void* bytes, size_t n_bytes, uint32_t* runs, size_t runs_cap,
+                            uint8_t* payload, size_t events_cap, uint64_t counts[4]) {
+  if (!state || state_bytes != sizeof(ae::Walk) || (n_bytes && !bytes) || !counts) return ESVIO_FE_EINVAL;
+  ae::Walk st;
+  memcpy(&st, state, sizeof st);
+  ae::Out o;
+  o.runs = (ae::Run*)runs, o.runs_cap = runs ? runs_cap : 0, o.payload = payload, o.events_cap = payload ? events_cap : 0;
+  const bool ok = ae::walk(&st, ae::kEvents, (const uint8_t*)bytes, n_bytes, 0, 0, &o);
+  counts[0] = o.n_events, counts[1] = o.n_runs, counts[2] = o.polarity_packets, counts[3] = o.other_packets;
+  if (!ok) return ESVIO_FE_EINVAL;  // (the caller's state is as it was)
+  memcpy(state, &st, sizeof st);
+  return 0;
+}
+int esvio_fe_aedat_walk_state_bytes(void) { return (int)sizeof(ae::Walk); }
 
 // ---- stream slicing: a record stream cut into fixed-rate windows (the rule: include/esvio_fe.h; the chain: fe_kernels.h)
 namespace {
@@ -2635,7 +2917,7 @@ void feed_info_fill(esvio_fe_feed_info* info, const FeedCam& fc, uint64_t append
   info->appended = appended, info->rejected = rejected, info->bad = bad, info->closed = closed, info->queued = fc.win.size();
 }
 
-enum FeedKind { FEED_EVENTS, FEED_FIELDS, FEED_RAW };
+enum FeedKind { FEED_EVENTS, FEED_FIELDS, FEED_RAW, FEED_AEDAT };
 struct FeedSrc {
   FeedKind kind;
   const esvio_fe_event* ev = nullptr;
@@ -2644,7 +2926,8 @@ struct FeedSrc {
   int format = 0;
   const void* words = nullptr;
   size_t n_bytes = 0;
-  int64_t t_offset_us = 0;
+  int64_t t_offset_us = 0;  // FEED_AEDAT: nanoseconds
+  uint32_t flags = 0;       // FEED_AEDAT
   int space = 0;
 };
 
@@ -2661,11 +2944,19 @@ int feed_push(esvio_fe_ctx* c, const char* who, int cam, const FeedSrc& src, esv
     if (src.space == ESVIO_FE_DEVICE && ((uintptr_t)src.ev & 15) != 0) return fail(c, ESVIO_FE_EINVAL, "%s: device events must be 16-byte aligned", who);
   } else if (src.kind == FEED_FIELDS) {
     if (int rc = fields_check(c, src.fields, src.n, who)) return rc;
+  } else if (src.kind == FEED_AEDAT) {
+    if (int rc = aedat_args_check(c, who, src.words, src.n_bytes, src.t_offset_us, src.flags)) return rc;
   } else if (int rc = raw_args_check(c, who, src.format, src.words, src.n_bytes, src.space, src.t_offset_us)) {
     return rc;
   }
-  if (src.kind != FEED_RAW && src.n >= (1ull << 30)) return fail(c, ESVIO_FE_EINVAL, "%s: chunk too large", who);
-  if (src.kind == FEED_RAW ? !src.n_bytes : !src.n) return 0;
+  const bool byte_src = src.kind == FEED_RAW || src.kind == FEED_AEDAT;
+  if (!byte_src && src.n >= (1ull << 30)) return fail(c, ESVIO_FE_EINVAL, "%s: chunk too large", who);
+  if (byte_src ? !src.n_bytes : !src.n) return 0;
+  AedatJob ajob[2];
+  if (src.kind == FEED_AEDAT) {  // (every header checked before any device work)
+    ajob[0].bytes = src.words, ajob[0].n_bytes = src.n_bytes;
+    if (int rc = aedat_count_walk(c, who, cam, &ajob[0])) return rc;
+  }
   if (cam == 1 && !f.origin_known)
     return fail(c, ESVIO_FE_EINVAL, "%s: the origin is the first left record, and no left record has been appended yet", who);
   HIPCHK(c, hipSetDevice(c->dev));
@@ -2712,6 +3003,29 @@ int feed_push(esvio_fe_ctx* c, const char* who, int cam, const FeedSrc& src, esv
     }
     n_new = raw_res[0].events;
     flt_ev = (const esvio_fe_event*)job[0].d_dst, flt_fields = nullptr, flt_n = raw_res[0].events, flt_space = ESVIO_FE_DEVICE;
+  }
+  if (src.kind == FEED_AEDAT) {  // the capacity is the host-known count of the chunk's records: nothing is repeated
+    const size_t want = (size_t)ajob[0].cnt.n_events;
+    if (flt) {
+      if (int rc = c->rawdec.dec[cam].grow(c, std::max<size_t>(want, 1))) return rc;
+      ajob[0].d_dst = c->rawdec.dec[cam], ajob[0].cap = c->rawdec.dec[cam].cap;
+    } else {
+      if (int rc = feed_room(c, cam, want, &dst)) return rc;
+      ajob[0].d_dst = dst, ajob[0].cap = fc.buf[fc.cur].cap - (size_t)fc.len;
+    }
+    const int cam_of[2] = {cam, cam};
+    AedatResult ar[2] = {};
+    if (int rc = aedat_enqueue(c, src.t_offset_us, src.flags, ajob, cam_of, ar)) return rc;
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (c->prof_on) resolve_profile(c);
+    aedat_result_fix(ajob[0], src.flags, &ar[0]);
+    if (ar[0].bad) {
+      feed_info_fill(info, fc, 0, 0, ar[0].bad, 0);
+      return fail(c, ESVIO_FE_EINVAL, "%s: %llu of %u events have a stamp outside [0, 2^32 s); nothing was appended, the camera's state is as it was",
+                  who, ar[0].bad, ar[0].events);
+    }
+    n_new = ar[0].events;
+    flt_ev = (const esvio_fe_event*)ajob[0].d_dst, flt_fields = nullptr, flt_n = ar[0].events, flt_space = ESVIO_FE_DEVICE;
   }
   if (flt) {
     n_new = 0;
@@ -2763,6 +3077,7 @@ int feed_push(esvio_fe_ctx* c, const char* who, int cam, const FeedSrc& src, esv
     first_window = si.first_window;
   }
   if (src.kind == FEED_RAW) raw_commit(c, cam, raw_res[0]);
+  if (src.kind == FEED_AEDAT) c->aedat.ev_st[cam] = ajob[0].st;
   const uint64_t at = fc.pos0 + fc.len;
   for (uint64_t j = 0; j < si.closed; j++) {
     const SliceBound e = slice_bound(c, cam, first_window + j);
@@ -2824,6 +3139,14 @@ int esvio_fe_feed_push_raw(esvio_fe_handle c, int cam, int format, const void* w
   FeedSrc src{FEED_RAW};
   src.format = format, src.words = words, src.n_bytes = n_bytes, src.t_offset_us = t_offset_us, src.space = space;
   return feed_push(c, "feed_push_raw", cam, src, info);
+}
+
+int esvio_fe_feed_push_aedat(esvio_fe_handle c, int cam, const void* bytes, size_t n_bytes, int64_t t_offset_ns, uint32_t flags,
+                             esvio_fe_feed_info* info) {
+  if (!c) return ESVIO_FE_EINVAL;
+  FeedSrc src{FEED_AEDAT};
+  src.words = bytes, src.n_bytes = n_bytes, src.t_offset_us = t_offset_ns, src.flags = flags, src.space = ESVIO_FE_HOST;
+  return feed_push(c, "feed_push_aedat", cam, src, info);
 }
 
 int esvio_fe_feed_peek(esvio_fe_handle c, esvio_fe_feed_window* out) {
@@ -3473,6 +3796,12 @@ int esvio_fe_reserve(esvio_fe_handle c, size_t max_left, size_t max_right, int h
     for (int cam = 0; cam < 2; cam++)
       if (int rc = raw_ensure(c, cam, ev[cam] * 8, host_batches != 0, 0)) return rc;
   }
+  // a handle that decodes AEDAT streams: per camera the scratch of a chunk of max_events polarity records, each a run
+  if (c->aedat.used) {
+    const size_t ev[2] = {max_left, max_right};
+    for (int cam = 0; cam < 2; cam++)
+      if (int rc = aedat_ensure(c, cam, ev[cam], ev[cam])) return rc;
+  }
   // a handle with an open feed: per camera both buffers for 2 * max_events records (the one that holds records is left alone)
   if (c->feed.open) {
     const size_t ev[2] = {max_left, max_right};
@@ -3568,10 +3897,13 @@ int esvio_fe_device_memory(esvio_fe_handle c, size_t* free_bytes, size_t* total_
 
 int esvio_fe_kernel_count(void) { return kTrackKernels; }
 int esvio_fe_stage_kernel_count(void) { return K_COUNT; }
-const char* esvio_fe_kernel_name(int id) { return (id >= 0 && id < K_COUNT) ? kKernelNames[id] : ""; }
+int esvio_fe_ingest_kernel_count(void) { return K_INGEST_COUNT; }
+const char* esvio_fe_kernel_name(int id) {
+  return (id >= 0 && id < K_COUNT) ? kKernelNames[id] : (id >= K_COUNT && id < K_INGEST_COUNT) ? kIngestKernelNames[id - K_COUNT] : "";
+}
 int esvio_fe_get_kernel_stats(esvio_fe_handle c, int id, double* total_ms, uint64_t* launches,
                               uint64_t* alg_bytes) {
-  if (!c || id < 0 || id >= K_COUNT) return ESVIO_FE_EINVAL;
+  if (!c || id < 0 || id >= K_INGEST_COUNT) return ESVIO_FE_EINVAL;
   HIPCHK(c, hipSetDevice(c->dev));
   if (int rc = launcher_drain(c)) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream2));

@@ -29,6 +29,7 @@
 
 #include "../../include/esvio_fe.h"
 #include "../../include/esvio_fe_test.h"
+#include "fe_aedat.h"
 #include "fe_host.h"
 #include "fe_kernels.h"
 #include "fe_layout.h"
@@ -73,6 +74,8 @@ const char* const kKernelNames[K_COUNT] = {
     "k_baf_count", "k_baf_scan", "k_baf_emit", "k_baf_keys_fields", "k_baf_emit_fields", "k_raw_reduce", "k_raw_scan",
     "k_raw_emit", "k_slice_reduce", "k_slice_scan", "k_slice_cuts", "k_baf_keys_addr", "k_hot_count", "k_hot_keys",
     "k_hot_pick", "k_trig_reduce", "k_trig_emit"};
+// the ingest range behind the stage table (IngestKernelId, fe_kernels.h): esvio_fe_ingest_kernel_count()
+const char* const kIngestKernelNames[K_INGEST_COUNT - K_COUNT] = {"k_aedat_count", "k_aedat_scan", "k_aedat_emit"};
 
 // The host phases of one trackEvent call, in the order of esvio_fe_latency_call::phase_ms; kPhaseNames is what
 // esvio_fe_latency_phase_name returns and what the ESVIO_FE_TRACE summary prints.  The PH_PUB_* phases are parts of
@@ -445,7 +448,7 @@ struct esvio_fe_ctx {
 
   // ---- profiling
   bool prof_on = false;
-  KStat stats[K_COUNT];
+  KStat stats[K_INGEST_COUNT];
   std::vector<ProfRec> pending;
   std::vector<Event> ev_pool;
 
@@ -540,6 +543,22 @@ struct esvio_fe_ctx {
     bool used = false;     // esvio_fe_reserve grows the scratch of a handle that has decoded before
     int pinned_copy = -1;  // page-locked sources: -1 = in place up to kRawPinnedInPlaceBytes (fe_api.cpp); ESVIO_FE_RAW_PINNED_COPY=1 / 0: always copied first / always in place
   } rawdec;
+
+  // ---- esvio_fe_decode_aedat / esvio_fe_aedat_side / esvio_fe_track_aedat: libcaer packet streams (include/esvio_fe.h
+  // has the rule, fe_aedat.h the host walk, fe_kernels.h the chain).  ev_st / side_st: each camera's two walker states,
+  // on the HOST: a call walks a copy and takes it over only once it is known to succeed.  Per camera, allocated on first
+  // use and the stage's own (main stream only): h_pack, the pinned scratch the walk gathers into — the packed polarity
+  // records, the run table behind them at a 16-byte boundary —, d_pack its device copy (one transfer), sums the tiles'
+  // counts; res, the two result blocks.  The records behind a host dst, and in front of a filter, are rawdec.dec's.
+  struct Aedat {
+    esvio::aedat::Walk ev_st[2] = {}, side_st[2] = {};
+    PinBuf<uint8_t> h_pack[2];
+    DevBuf<uint8_t> d_pack[2];
+    DevBuf<uint32_t> sums[2];
+    DevBuf<AedatResult> res;
+    bool used = false;  // esvio_fe_reserve grows the scratch of a handle that has decoded AEDAT before
+    int wave_lookup = 0;  // ESVIO_FE_AEDAT_WAVE_LOOKUP=1: k_aedat_emit's run look-up once per wave with a forward step (the A/B in KERNELS.md)
+  } aedat;
 
   // ---- esvio_fe_slice_events: a record stream cut into fixed-rate windows (include/esvio_fe.h has the rule,
   // fe_kernels.h the chain).  st: each camera's state, kept on the HOST like the decoder's: the device works on counts

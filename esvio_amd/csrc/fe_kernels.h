@@ -696,6 +696,50 @@ void launch_raw_emit(hipStream_t s, const RawArgs& a);
 void launch_trig_reduce(hipStream_t s, const RawArgs& a);
 void launch_trig_emit(hipStream_t s, const RawArgs& a);
 
+// ---- libcaer / AEDAT 3.1 polarity records -> event records (esvio_fe_decode_aedat, esvio_fe_track_aedat) ----
+// include/esvio_fe.h holds the rule.  The host has walked the packet chain (fe_aedat.h): what arrives here is the chunk's
+// polarity records packed into one array and the table of its runs of equal eventTSOverflow.  A record needs nothing
+// from the records before it but its rank among the kept ones, so the chain is count (kept records per tile of
+// kAedatTile) -> scan (one workgroup per camera: the tiles' exclusive prefixes, the totals) -> emit (one record per
+// lane: its run by a binary search of the table — KERNELS.md "AEDAT 3.1" has the measurement against one search per
+// wave —, the stamp, one 16-byte store at dst[rank]).  With keep_invalid the
+// rank is the index: the host writes the result block's counts itself and launches the emit alone.  Both cameras'
+// tiles share each grid, as in the raw chain; no launch waits on the device for another workgroup.
+// The timer slots of these kernels are a range of their own behind K_COUNT (esvio_fe_ingest_kernel_count()): the stage
+// table, whose end a test pins, stays as it is.
+enum IngestKernelId { K_AEDAT_COUNT = K_COUNT, K_AEDAT_SCAN, K_AEDAT_EMIT, K_INGEST_COUNT };
+constexpr uint32_t kAedatTile = 1024;  // records per workgroup: 1024 lanes, one record each
+struct AedatRun {                      // (fe_aedat.h: esvio::aedat::Run)
+  uint32_t first;
+  int32_t overflow;
+};
+struct AedatResult {  // events, invalid: k_aedat_scan (keep_invalid: the host); bad, first_t, last_t: k_aedat_emit
+  uint32_t events, invalid;
+  unsigned long long bad;
+  unsigned long long first_t, last_t;  // ticks_ns of the first / last emitted event (untouched if none)
+};
+static_assert(sizeof(AedatResult) == 32, "AedatResult layout");
+struct AedatCam {
+  const uint2* rec;      // [n] the packed polarity records, device memory
+  uint32_t n;
+  uint32_t tiles;        // ceil(n / kAedatTile); 0: the camera takes no part
+  const AedatRun* runs;  // [n_runs] ascending in `first`, runs[0].first == 0
+  uint32_t n_runs;
+  uint32_t keep_invalid;
+  uint32_t wave_lookup;   // 0: every lane searches the table for its own record (the measured choice); 1: one search per wave, then a forward step
+  long long t_offset;    // nanoseconds
+  uint32_t* sums;        // [tiles] count: the tiles' kept records; scan: their exclusive prefixes
+  EventRec* dst;         // [dst_cap]; nothing is stored when the kept records exceed dst_cap
+  uint32_t dst_cap;
+  AedatResult* res;
+};
+struct AedatArgs {
+  AedatCam cam[2];  // the grid's blocks: cam[0].tiles, then cam[1].tiles
+};
+void launch_aedat_count(hipStream_t s, const AedatArgs& a);
+void launch_aedat_scan(hipStream_t s, const AedatArgs& a);
+void launch_aedat_emit(hipStream_t s, const AedatArgs& a);
+
 // ---- stream slicing: a record stream cut into fixed-rate windows (esvio_fe_slice_events) ----
 // include/esvio_fe.h holds the rule.  An event's window is m_i = max(m_{i-1}, c_i), c_i = the boundaries at or below its
 // stamp: a prefix MAXIMUM, associative and commutative, so a tile of events is summarised by one number and the chain

@@ -4904,6 +4904,126 @@ void launch_trig_emit(hipStream_t s, const RawArgs& a) {
     launch_k(k_trig_emit<kRawEvt2>, dim3(raw_grid(a)), dim3(256), 0, s, a);
 }
 
+// ============================================================================ AEDAT 3.1 polarity records
+// The packed polarity records of a libcaer packet stream -> event records (fe_kernels.h has the chain, include/esvio_fe.h
+// the rule; the packet walk is the host's, fe_aedat.h).  One record per lane everywhere: 8 bytes in, 16 bytes out.
+//   k_aedat_count  per tile: the records whose valid bit is set
+//   k_aedat_scan   per camera one workgroup: the tiles' exclusive prefixes, the totals
+//   k_aedat_emit   per record: its rank among the kept ones, its run's eventTSOverflow by a binary search of the run
+//                  table (every lane its own: KERNELS.md "AEDAT 3.1" has the reason), the stamp, one 16-byte store
+__device__ __forceinline__ const AedatCam& aedat_block_cam(const AedatArgs& a, uint32_t* tile) {
+  const uint32_t b = blockIdx.x;
+  *tile = b < a.cam[0].tiles ? b : b - a.cam[0].tiles;
+  return b < a.cam[0].tiles ? a.cam[0] : a.cam[1];
+}
+
+__global__ __launch_bounds__(kAedatTile) void k_aedat_count(AedatArgs a) {
+  __shared__ uint32_t part[kAedatTile / 64];
+  uint32_t tile;
+  const AedatCam& c = aedat_block_cam(a, &tile);
+  const uint32_t i = tile * kAedatTile + threadIdx.x;
+  const bool keep = i < c.n && (c.rec[i].x & 1u);
+  const uint32_t cnt = (uint32_t)__popcll(bal(keep));
+  if (lane_id() == 0) part[threadIdx.x >> 6] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t s = 0;
+#pragma unroll
+    for (int w = 0; w < (int)(kAedatTile / 64); w++) s += part[w];
+    c.sums[tile] = s;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_aedat_scan(AedatArgs a) {
+  __shared__ uint32_t part[4];
+  const AedatCam& c = a.cam[blockIdx.x];
+  if (!c.tiles) return;
+  const uint32_t per = (c.tiles + 255u) / 256u;
+  const uint32_t lo = min(threadIdx.x * per, c.tiles), hi = min(lo + per, c.tiles);
+  uint32_t sum = 0;
+  for (uint32_t j = lo; j < hi; j++) sum += c.sums[j];
+  uint32_t incl = sum;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t v = __shfl_up(incl, o);
+    if (lane_id() >= o) incl += v;
+  }
+  if (lane_id() == 63) part[threadIdx.x >> 6] = incl;
+  __syncthreads();
+  uint32_t run = incl - sum;
+  for (int wv = 0; wv < (int)(threadIdx.x >> 6); wv++) run += part[wv];
+  for (uint32_t j = lo; j < hi; j++) {
+    const uint32_t s = c.sums[j];
+    c.sums[j] = run;
+    run += s;
+  }
+  if (threadIdx.x == 255) {  // (the chunks behind the last tile are empty: this lane's run is the whole call)
+    AedatResult* r = c.res;
+    r->events = run, r->invalid = c.n - run;
+    r->bad = 0;
+  }
+}
+
+__global__ __launch_bounds__(kAedatTile) void k_aedat_emit(AedatArgs a) {
+  __shared__ uint32_t part[kAedatTile / 64];
+  uint32_t tile;
+  const AedatCam& c = aedat_block_cam(a, &tile);
+  const uint32_t i = tile * kAedatTile + threadIdx.x;
+  const bool active = i < c.n;
+  const uint2 w = active ? c.rec[i] : make_uint2(0u, 0u);
+  const bool keep = active && (c.keep_invalid || (w.x & 1u));
+  const lanemask_t m = bal(keep);
+  if (lane_id() == 0) part[threadIdx.x >> 6] = (uint32_t)__popcll(m);
+  __syncthreads();
+  if (!keep) return;  // (behind the barrier)
+  uint32_t rank = i, total = c.n;
+  if (!c.keep_invalid) {
+    rank = c.sums[tile] + (uint32_t)__popcll(m & (((lanemask_t)1 << lane_id()) - 1));
+    for (int wv = 0; wv < (int)(threadIdx.x >> 6); wv++) rank += part[wv];
+    total = c.res->events;
+  }
+  // the run: the last table entry whose first record is at or in front of this one (runs[0].first == 0)
+  // (wave_lookup, the measured alternative: one search per wave for its first record, then every lane steps forward)
+  const uint32_t key = c.wave_lookup ? (i & ~63u) : i;
+  uint32_t lo = 0, hi = c.n_runs;
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (c.runs[mid].first <= key)
+      lo = mid;
+    else
+      hi = mid;
+  }
+  if (c.wave_lookup)
+    while (lo + 1 < c.n_runs && c.runs[lo + 1].first <= i) lo++;
+  const int32_t overflow = c.runs[lo].overflow, ts = (int32_t)w.y;
+  // BAD first for ts64 >= 2^53; below it ts64 * 1000 + t_offset, modulo 2^64, is the exact sum when that is not negative
+  // and lies at or above 2^63 when it is (|t_offset| <= 2^62): one unsigned comparison decides (fe_aedat.h: stamp)
+  const unsigned long long ts64 = (unsigned long long)(uint32_t)overflow << 31 | (uint32_t)ts;
+  const unsigned long long u = ts64 * 1000ull + (unsigned long long)c.t_offset;
+  const bool bad = ts < 0 || overflow < 0 || ts64 >= (1ull << 53) || u >= 4294967296ull * 1000000000ull;
+  uint32_t sec = 0, nsec = 0;
+  if (!bad) {
+    const unsigned long long s = u / 1000000000ull;
+    sec = (uint32_t)s, nsec = (uint32_t)(u - s * 1000000000ull);
+  }
+  if (bad) atomicAdd(&c.res->bad, 1ull);
+  if (rank == 0) c.res->first_t = u;
+  if (rank + 1 == total) c.res->last_t = u;
+  if (total <= c.dst_cap)
+    ((uint4*)c.dst)[rank] = make_uint4(((w.x >> 17) & 0x7fffu) | ((w.x >> 2) & 0x7fffu) << 16, sec, nsec, (w.x >> 1) & 1u);
+}
+
+static uint32_t aedat_grid(const AedatArgs& a) { return a.cam[0].tiles + a.cam[1].tiles; }
+void launch_aedat_count(hipStream_t s, const AedatArgs& a) {
+  if (aedat_grid(a)) launch_k(k_aedat_count, dim3(aedat_grid(a)), dim3(kAedatTile), 0, s, a);
+}
+void launch_aedat_scan(hipStream_t s, const AedatArgs& a) {
+  if (aedat_grid(a)) launch_k(k_aedat_scan, dim3(2), dim3(256), 0, s, a);
+}
+void launch_aedat_emit(hipStream_t s, const AedatArgs& a) {
+  if (aedat_grid(a)) launch_k(k_aedat_emit, dim3(aedat_grid(a)), dim3(kAedatTile), 0, s, a);
+}
+
 // ============================================================================ stream slicing
 // A record stream cut into fixed-rate windows (fe_kernels.h has the chain, include/esvio_fe.h the rule).
 //   slice_count     the boundaries at or below a stamp: the upper bound in the ascending table, by bisection

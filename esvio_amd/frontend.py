@@ -160,6 +160,35 @@ class RawHeaderInfo(C.Structure):
                 ("complete", C.c_int32)]
 
 
+AEDAT_KEEP_INVALID = 1  # ESVIO_FE_AEDAT_KEEP_INVALID
+
+
+class AedatInfo(C.Structure):
+    """esvio_fe_aedat_info"""
+    _fields_ = [("events", C.c_uint64), ("invalid", C.c_uint64), ("bad", C.c_uint64), ("polarity_packets", C.c_uint64),
+                ("other_packets", C.c_uint64), ("first_t_us", C.c_int64), ("last_t_us", C.c_int64)]
+
+
+class ImuSample(C.Structure):
+    """esvio_fe_imu_sample"""
+    _fields_ = [("sec", C.c_uint32), ("nsec", C.c_uint32), ("acc", C.c_double * 3), ("gyr", C.c_double * 3)]
+
+
+IMU_DTYPE = np.dtype([("sec", "<u4"), ("nsec", "<u4"), ("acc", "<f8", (3,)), ("gyr", "<f8", (3,))])
+
+
+class AedatSideInfo(C.Structure):
+    """esvio_fe_aedat_side_info"""
+    _fields_ = [("imu", C.c_uint64), ("triggers", C.c_uint64), ("resets", C.c_uint64), ("other_specials", C.c_uint64),
+                ("invalid", C.c_uint64), ("bad", C.c_uint64), ("special_packets", C.c_uint64), ("imu_packets", C.c_uint64),
+                ("other_packets", C.c_uint64)]
+
+
+class AedatHeaderInfo(C.Structure):
+    """esvio_fe_aedat_header_info"""
+    _fields_ = [("payload_offset", C.c_uint64), ("version", C.c_int32), ("complete", C.c_int32)]
+
+
 class EventRecord(C.Structure):
     """esvio_fe_event"""
     _fields_ = [("x", C.c_uint16), ("y", C.c_uint16), ("sec", C.c_uint32), ("nsec", C.c_uint32), ("polarity", C.c_uint8),
@@ -214,6 +243,7 @@ ABI_SYMBOLS = [
     "esvio_fe_calc_optical_flow_pyr_lk", "esvio_fe_comm_init", "esvio_fe_comm_unique_id",
     "esvio_fe_convert_events", "esvio_fe_create", "esvio_fe_decode_raw", "esvio_fe_decode_reset",
     "esvio_fe_decode_triggers", "esvio_fe_raw_header", "esvio_fe_slice_events_at",
+    "esvio_fe_aedat_header", "esvio_fe_decode_aedat", "esvio_fe_aedat_side", "esvio_fe_track_aedat", "esvio_fe_feed_push_aedat",
     "esvio_fe_create_sae", "esvio_fe_create_sae_stereo", "esvio_fe_create_sae_stereo_mc", "esvio_fe_destroy",
     "esvio_fe_exchange_begin", "esvio_fe_exchange_end", "esvio_fe_exchange_tracks", "esvio_fe_export_image",
     "esvio_fe_feed_close", "esvio_fe_feed_open", "esvio_fe_feed_peek", "esvio_fe_feed_push_events", "esvio_fe_feed_push_fields",
@@ -244,6 +274,7 @@ TEST_SYMBOLS = [
     "esvio_fe_ransac_tail", "esvio_fe_raw_tile_bytes", "esvio_fe_reset_kernel_stats", "esvio_fe_select_candidates",
     "esvio_fe_set_profiling", "esvio_fe_set_sae",
     "esvio_fe_slice_tile_events", "esvio_fe_stage_kernel_count", "esvio_fe_stream",
+    "esvio_fe_aedat_tile_events", "esvio_fe_ingest_kernel_count", "esvio_fe_aedat_walk_tap", "esvio_fe_aedat_walk_state_bytes",
 ]
 
 LATENCY_PHASES = 16
@@ -368,6 +399,14 @@ def load_library(build_if_missing=True):
     L.esvio_fe_feed_push_fields.argtypes = [vp, i, C.POINTER(EventFieldsDesc), sz, i, C.POINTER(FeedInfo)]
     L.esvio_fe_feed_push_raw.argtypes = [vp, i, i, vp, sz, i, C.c_int64, C.POINTER(FeedInfo)]
     L.esvio_fe_feed_peek.argtypes = [vp, C.POINTER(FeedWindow)]
+    u32 = C.c_uint32
+    L.esvio_fe_aedat_header.argtypes = [vp, sz, C.POINTER(AedatHeaderInfo)]
+    L.esvio_fe_decode_aedat.argtypes = [vp, i, vp, sz, C.c_int64, u32, vp, sz, i, C.POINTER(AedatInfo)]
+    L.esvio_fe_aedat_side.argtypes = [vp, i, vp, sz, C.c_int64, u32, vp, sz, vp, sz, C.POINTER(AedatSideInfo)]
+    L.esvio_fe_track_aedat.argtypes = [vp, vp, sz, vp, sz, C.c_int64, u32, i, C.POINTER(FilterParams), C.POINTER(Motion),
+                                       C.POINTER(Tracks), C.POINTER(BatchInfo), C.POINTER(AedatInfo * 2)]
+    L.esvio_fe_feed_push_aedat.argtypes = [vp, i, vp, sz, C.c_int64, u32, C.POINTER(FeedInfo)]
+    L.esvio_fe_aedat_walk_tap.argtypes = [vp, sz, vp, sz, vp, sz, vp, sz, vp]
     L.esvio_fe_feed_track.argtypes = [vp, i, C.POINTER(Motion), C.POINTER(Tracks), C.POINTER(BatchInfo)]
     L.esvio_fe_feed_close.argtypes = [vp]
     L.esvio_fe_set_profiling.argtypes = [vp, i]
@@ -861,6 +900,82 @@ class FeatureTracker:
         if info.tracked:
             self._take(copy)
         return info, (raw[0], raw[1])
+
+    def decode_aedat(self, cam, data, t_offset_ns=0, flags=0, dst_cap=None, device=False):
+        """the AEDAT 3.1 decode stage (esvio_fe_decode_aedat; include/esvio_fe.h has the rule): camera `cam`'s event
+        walker advanced by `data` — bytes or a contiguous numpy array, host memory; the chunk may end anywhere.  Returns
+        (records, AedatInfo) as decode_raw does.  dst_cap None: one record per 8 bytes of the chunk, and one for a record
+        the last chunk cut.  A failed call raises FrontendError with `.info`."""
+        from .events import EVENT_DTYPE
+        L = self._hd.L
+        buf = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data)
+        if dst_cap is None:
+            dst_cap = buf.nbytes // 8 + 1
+        info = AedatInfo()
+        if device:
+            dst = C.c_void_p()
+            rc = L.esvio_fe_mem_alloc(DEVICE, 16 * max(dst_cap, 1), C.byref(dst))
+            if rc:
+                raise FrontendError("esvio_fe_mem_alloc rc=%d" % rc)
+            out = None
+        else:
+            out = np.zeros(max(int(dst_cap), 1), EVENT_DTYPE)
+            dst = _p(out)
+        rc = L.esvio_fe_decode_aedat(self._hd.h, int(cam), _p(buf) if buf.nbytes else None, buf.nbytes, int(t_offset_ns), int(flags),
+                                     dst, int(dst_cap), DEVICE if device else HOST, C.byref(info))
+        if rc:
+            if device:
+                L.esvio_fe_mem_free(DEVICE, dst)
+            e = FrontendError("rc=%d: %s" % (rc, L.esvio_fe_last_error(self._hd.h).decode()))
+            e.info = info
+            raise e
+        k = int(info.events)
+        return (FilteredEvents(dst, k, None) if device else out[:k]), info
+
+    def aedat_side(self, cam, data, t_offset_ns=0, flags=0, imu_cap=None, trig_cap=None):
+        """the IMU6 samples and external-input specials of an AEDAT 3.1 chunk (esvio_fe_aedat_side): camera `cam`'s side
+        walker advanced by `data`.  Returns (imu, triggers, AedatSideInfo): numpy IMU_DTYPE and TRIGGER_DTYPE arrays.
+        Capacities None: what the chunk can hold at the most.  A failed call raises FrontendError with `.info`."""
+        L = self._hd.L
+        buf = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data)
+        imu_cap = buf.nbytes // 36 + 1 if imu_cap is None else int(imu_cap)
+        trig_cap = buf.nbytes // 8 + 1 if trig_cap is None else int(trig_cap)
+        imu, trig, info = np.zeros(max(imu_cap, 1), IMU_DTYPE), np.zeros(max(trig_cap, 1), TRIGGER_DTYPE), AedatSideInfo()
+        rc = L.esvio_fe_aedat_side(self._hd.h, int(cam), _p(buf) if buf.nbytes else None, buf.nbytes, int(t_offset_ns), int(flags),
+                                   _p(imu), imu_cap, _p(trig), trig_cap, C.byref(info))
+        if rc:
+            e = FrontendError("rc=%d: %s" % (rc, L.esvio_fe_last_error(self._hd.h).decode()))
+            e.info = info
+            raise e
+        return imu[:int(info.imu)], trig[:int(info.triggers)], info
+
+    def track_aedat(self, left, right, t_offset_ns=0, flags=0, pub=True, params=None, measurements=None, copy=True):
+        """one chunk of AEDAT 3.1 bytes per camera through esvio_fe_track_aedat (host memory).  Returns
+        (BatchInfo, (AedatInfo, AedatInfo)); a failed call raises FrontendError with `.info` and `.aedat`."""
+        args, keep = [], []
+        for w in (left, right):
+            w = np.frombuffer(w, np.uint8) if isinstance(w, (bytes, bytearray, memoryview)) else np.ascontiguousarray(w)
+            keep.append(w)
+            args += [_p(w) if w.nbytes else None, w.nbytes]
+        info, ae = BatchInfo(), (AedatInfo * 2)()
+        rc = self._hd.L.esvio_fe_track_aedat(self._hd.h, *args, int(t_offset_ns), int(flags), int(pub),
+                                             C.byref(params) if params is not None else None,
+                                             C.byref(measurements) if measurements is not None else None,
+                                             C.byref(self._tr), C.byref(info), C.byref(ae))
+        if rc:
+            e = FrontendError("rc=%d: %s" % (rc, self._hd.L.esvio_fe_last_error(self._hd.h).decode()))
+            e.info, e.aedat = info, ae
+            raise e
+        if info.tracked:
+            self._take(copy)
+        return info, (ae[0], ae[1])
+
+    def feed_push_aedat(self, cam, data, t_offset_ns=0, flags=0):
+        """append the polarity events of a chunk of AEDAT 3.1 bytes (host memory; the chunk may end anywhere)"""
+        buf = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data)
+        info = FeedInfo()
+        return self._feed_pushed(self._hd.L.esvio_fe_feed_push_aedat(self._hd.h, int(cam), _p(buf) if buf.nbytes else None, buf.nbytes,
+                                                                     int(t_offset_ns), int(flags), C.byref(info)), info)
 
     def slice_events(self, cam, ev, frequency=30.0, origin=None, cuts_cap=SLICE_MAX_WINDOWS):
         """the stream-slicing stage (esvio_fe_slice_events; include/esvio_fe.h has the rule): camera `cam`'s slicer
@@ -1616,3 +1731,34 @@ def lift_projective(cam, u, v):
     if rc:
         raise FrontendError("lift_projective rc=%d" % rc)
     return out
+
+
+def aedat_header(data):
+    """an AEDAT recording's text header (esvio_fe_aedat_header; host only, no handle): `data` the file's first bytes.
+    Returns the AedatHeaderInfo: .payload_offset, .version (31: AEDAT 3.1; 0: not stated), .complete."""
+    buf = bytes(data)
+    info = AedatHeaderInfo()
+    rc = load_library().esvio_fe_aedat_header(buf if buf else None, len(buf), C.byref(info))
+    if rc:
+        raise FrontendError("esvio_fe_aedat_header rc=%d" % rc)
+    return info
+
+
+def aedat_walk_tap(state, data, runs_cap=None, events_cap=None):
+    """the AEDAT host walk alone (esvio_fe_aedat_walk_tap; include/esvio_fe_test.h): `state` a bytes object (None: the
+    fresh state).  Returns (state, runs, payload, counts): runs an (n, 2) int64 array of (first record, overflow),
+    payload the packed 8-byte records as bytes, counts = (records, runs, polarity packets, other packets).  A malformed
+    header raises FrontendError."""
+    L = load_library()
+    nst = L.esvio_fe_aedat_walk_state_bytes()
+    st = np.zeros(nst, np.uint8) if state is None else np.frombuffer(bytes(state), np.uint8).copy()
+    buf = np.frombuffer(bytes(data), np.uint8)
+    events_cap = buf.nbytes // 8 + 1 if events_cap is None else events_cap
+    runs_cap = events_cap if runs_cap is None else runs_cap
+    runs, pay, counts = np.zeros((max(runs_cap, 1), 2), np.uint32), np.zeros(max(events_cap, 1) * 8, np.uint8), np.zeros(4, np.uint64)
+    rc = L.esvio_fe_aedat_walk_tap(_p(st), nst, _p(buf) if buf.nbytes else None, buf.nbytes, _p(runs), runs_cap, _p(pay), events_cap, _p(counts))
+    if rc:
+        raise FrontendError("esvio_fe_aedat_walk_tap rc=%d" % rc)
+    n, nr = int(counts[0]), int(counts[1])
+    r = np.stack([runs[:nr, 0].astype(np.int64), runs[:nr, 1].view(np.int32).astype(np.int64)], axis=1) if nr else np.zeros((0, 2), np.int64)
+    return st.tobytes(), r, pay[:8 * n].tobytes(), tuple(int(v) for v in counts)

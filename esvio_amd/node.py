@@ -133,6 +133,12 @@ class MotionCorrection:
         self.last_imu_t = stamp
         self.imu_buf.append((float(stamp), tuple(map(float, angular_velocity)), tuple(map(float, linear_acceleration))))
 
+    def imu_samples(self, samples):
+        """decoded IMU6 samples (frontend.IMU_DTYPE records, what aedat_side returns) through imu_callback, in order:
+        the stamp is header.stamp.toSec() of the driver's sensor_msgs::Imu"""
+        for s in samples:
+            self.imu_callback(float(s["sec"]) + 1e-9 * float(s["nsec"]), s["gyr"], s["acc"])
+
     def state_callback(self, stamp, linear_velocity):
         self.odom_buffer_.append((float(stamp), tuple(map(float, linear_velocity))))
 

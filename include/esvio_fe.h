@@ -693,7 +693,7 @@ int esvio_fe_track_batch(esvio_fe_handle h, const esvio_fe_batch* b, esvio_fe_tr
  *
  * Cutting the decoded stream into time-based batches is the next stage's business (esvio_fe_slice_events below); the
  * EXT_TRIGGER words of all three formats are decoded by esvio_fe_decode_triggers, a .raw file's ASCII header is read by
- * esvio_fe_raw_header (both below).  Out of scope: EVT4, AEDAT, the half-swapped EVT2.1 layout, the payloads of OTHERS /
+ * esvio_fe_raw_header (both below); libcaer / AEDAT 3.1 packet streams have a section of their own further down.  Out of scope: EVT4, the half-swapped EVT2.1 layout, the payloads of OTHERS /
  * CONTINUED words. */
 #define ESVIO_FE_RAW_EVT2 2
 #define ESVIO_FE_RAW_EVT3 3
@@ -721,7 +721,7 @@ typedef struct esvio_fe_raw_info {
 int esvio_fe_decode_raw(esvio_fe_handle h, int cam, int format, const void* words, size_t n_bytes, int space,
                         int64_t t_offset_us, esvio_fe_event* dst, size_t dst_cap, int dst_space,
                         esvio_fe_raw_info* info);
-/* both cameras' decoder states back to the fresh state */
+/* both cameras' decoder states back to the fresh state (the AEDAT walkers' too) */
 int esvio_fe_decode_reset(esvio_fe_handle h);
 /* esvio_fe_track_batch for a host that has raw words: both cameras' chunks are decoded into the handle's two alternating
  * buffer pairs (buffer lifetime exactly as esvio_fe_track_event_fields states it) and tracked from there with
@@ -803,6 +803,133 @@ typedef struct esvio_fe_raw_header_info {
   int32_t complete;
 } esvio_fe_raw_header_info;
 int esvio_fe_raw_header(const void* bytes, size_t n, esvio_fe_raw_header_info* out);
+
+/* ---- libcaer / AEDAT 3.1 packet streams: polarity events, IMU6 samples, special events ---- */
+/* The DAVIS and DVXplorer sensors of the esvio, esio, esvio_ecmd and esvio_mvsec_flying parameter sets speak libcaer:
+ * the three drivers the reference vendors (dependences/rpg_dvs_ros: davis_ros_driver, dvxplorer_ros_driver,
+ * dvs_ros_driver) receive event PACKETS, and an AEDAT 3.1 recording is those packets written one behind the other, behind
+ * a text header.  The PER-EVENT ARITHMETIC below is the reference driver's, cited by line: the polarity loop is
+ * davis_ros_driver/src/driver.cpp:664-694 (the same lines at dvxplorer_ros_driver/src/driver.cpp:319-323), the IMU6 loop
+ * is davis_ros_driver/src/driver.cpp:722-775.  libcaer's bit accessors are not in the reference's tree: THE PACKET AND
+ * EVENT LAYOUTS ARE RESTATED FROM RECALL of libcaer / AEDAT 3.1 and UNPINNED — not claimed to be bit-equal to libcaer —
+ * and THIS TEXT IS THE SPECIFICATION; tests/aedat_ref.py is its sequential reading, and the library equals it exactly.
+ *
+ * Packet stream.  All fields are little-endian.  A packet is a 28-byte header
+ *   int16 eventType, int16 eventSource, int32 eventSize, int32 eventTSOffset, int32 eventTSOverflow,
+ *   int32 eventCapacity, int32 eventNumber, int32 eventValid
+ * and behind it eventCapacity * eventSize payload bytes (a 64-bit product).  The first eventNumber records of the payload
+ * are events, the rest is padding and is skipped.  eventValid is not trusted: validity is bit 0 of each event's first
+ * word.  Types:
+ *   0 SPECIAL   eventSize 8,  eventTSOffset 4   decoded by esvio_fe_aedat_side
+ *   1 POLARITY  eventSize 8,  eventTSOffset 4   decoded by esvio_fe_decode_aedat
+ *   3 IMU6      eventSize 36, eventTSOffset 4   decoded by esvio_fe_aedat_side
+ *   every other type (frames among them): skipped whole, counted in other_packets
+ * A header is MALFORMED when eventSize <= 0, eventCapacity < 0, eventNumber < 0, eventNumber > eventCapacity, or a type
+ * 0 / 1 / 3 packet's eventSize or eventTSOffset differs from the table.  A malformed header fails the call with
+ * ESVIO_FE_EINVAL before any device work, and the state is as it was.  A packet is counted (polarity_packets,
+ * other_packets) by the call in which its header's last byte arrives.
+ *
+ * Polarity event: uint32 data; int32 ts.  valid = data & 1, p = (data>>1) & 1, y = (data>>2) & 0x7FFF,
+ * x = (data>>17) & 0x7FFF.  ts64 = ((int64)eventTSOverflow << 31) | (uint32)ts, in microseconds
+ * (caerPolarityEventGetTimestamp64).  Record: ticks_ns = ts64 * 1000 + t_offset_ns, where t_offset_ns is the driver's
+ * reset_time_ in NANOSECONDS, |t_offset_ns| <= 2^62 — nanoseconds, unlike the EVT calls' microseconds, because
+ * reset_time_ is ros::Time::now() and the record must equal reset_time_ + Duration().fromNSec(ts64 * 1000)
+ * (driver.cpp:685-686).  sec = ticks_ns / 10^9, nsec = ticks_ns % 10^9; x and y are copied as 16-bit patterns; polarity
+ * is 0 or 1, the padding bytes 0 — byte for byte what esvio_amd.events.make_events builds.  Events go out in stream order.
+ * BAD: an emitted event is BAD when ts < 0, eventTSOverflow < 0, ticks_ns < 0 or sec >= 2^32, decided in exact integers.
+ * (ts64 >= 2^53 is always BAD under the offset limit, so an implementation may test that first and then stay inside 64
+ * bits.)  A BAD event fails the call: info->bad is exact, dst is unspecified, the state is as it was.
+ * Validity: by default an event with valid == 0 is dropped and counted in `invalid` — the format's rule; a dropped event
+ * is not examined further and is never BAD.  With ESVIO_FE_AEDAT_KEEP_INVALID in `flags` every one of the eventNumber
+ * events is emitted and `invalid` stays 0 — exactly what the reference's drivers do, which never look at the bit.
+ *
+ * Special event: uint32 data; int32 ts.  valid = data & 1 (dropped / kept as above), type = (data>>1) & 0x7F.  Type 1,
+ * TIMESTAMP_RESET, is counted in `resets`.  Types 2 / 3 / 4 — external input rising / falling / pulse — become
+ * esvio_fe_trigger records with the events' stamp rule (BAD included), id = type, value = (type != 3).  Every other type
+ * is counted in `other_specials`.  Only a special that becomes a record has its stamp examined.
+ *
+ * IMU6 event: uint32 info; int32 ts; float ax, ay, az, gx, gy, gz, temp (36 bytes).  valid = info & 1.  The output is an
+ * esvio_fe_imu_sample: the stamp as for events (BAD included), acc = (-ax, ay, -az) * 9.81 and
+ * gyr = (-gx, gy, -gz) / 180.0 * M_PI, evaluated as driver.cpp:735-741 writes them: the float is negated first, then
+ * widened to double, then the operations run left to right in double.  No bias is applied: bias is the driver's
+ * calibration state (driver.cpp:766-771).
+ *
+ * State.  Per handle and camera there are TWO walker states, one for esvio_fe_decode_aedat (and the track / feed entry
+ * points), one for esvio_fe_aedat_side.  Each holds the header bytes collected so far (0..27), the open packet's type,
+ * event size and overflow, its events and payload bytes still to come, and the bytes of a record cut by the chunk's end
+ * (up to 35).  A chunk may end anywhere: inside a header, inside a record, inside padding; a cut record is emitted by the
+ * call that brings its last byte.  esvio_fe_decode_reset and esvio_fe_reset clear both states; every failed call leaves
+ * them as they were.  The same chunks through both calls, in either order, give events, IMU samples and triggers on one
+ * time base — the esvio_fe_decode_triggers arrangement.
+ *
+ * Source.  `bytes` is memory the HOST can read, pageable or pinned.  There is no `space` argument and no device source:
+ * the packet chain is a linked list that only a sequential walk can follow, so the host walks it (one cache line per
+ * packet), gathers the polarity records — and nothing else: a DAVIS346 frame packet of 180 KB never crosses PCIe — into
+ * pinned scratch with a table of the runs of equal eventTSOverflow, and the device decodes that array one record per
+ * lane (KERNELS.md "AEDAT 3.1").  A stream that lies in device memory would have to come back first.
+ *
+ * Out of scope: AEDAT 2.0 and AEDAT 4, frame packets' pixels, IMU samples or triggers inside the feed (the side call
+ * beside it is the way). */
+#define ESVIO_FE_AEDAT_KEEP_INVALID 1u
+typedef struct esvio_fe_aedat_info {
+  uint64_t events, invalid, bad;             /* emitted (a too small dst_cap: the number needed); dropped; BAD */
+  uint64_t polarity_packets, other_packets;  /* headers completed by this call: type 1; neither 0, 1 nor 3 */
+  int64_t first_t_us, last_t_us;             /* ticks_ns / 1000 of the first / last emitted event; untouched if none */
+} esvio_fe_aedat_info;
+typedef struct esvio_fe_imu_sample {
+  uint32_t sec, nsec;
+  double acc[3]; /* m/s^2 */
+  double gyr[3]; /* rad/s */
+} esvio_fe_imu_sample;
+typedef struct esvio_fe_aedat_side_info {
+  uint64_t imu, triggers;            /* samples / trigger records written (a too small capacity: the numbers needed) */
+  uint64_t resets, other_specials;   /* TIMESTAMP_RESET specials; specials of every other type */
+  uint64_t invalid, bad;             /* dropped specials and samples; BAD triggers and samples */
+  uint64_t special_packets, imu_packets, other_packets; /* headers completed by this call: type 0; 3; neither 0, 1 nor 3 */
+} esvio_fe_aedat_side_info;
+/* The file header (host only, no handle): the maximal run of lines from byte 0 each of which begins with '#' and ends
+ * with '\n'.  It ends behind the line "#!END-HEADER" (a trailing '\r' ignored), or in front of the first line that does
+ * not begin with '#'.  A FIRST line "#!AER-DAT<a>.<b>" (a: decimal digits, b: one digit, a trailing '\r' ignored) gives
+ * version = 10 a + b — "#!AER-DAT3.1": 31 —, anything else 0.  out->payload_offset, complete as in
+ * esvio_fe_raw_header_info: complete == 0 when the n bytes end inside a line or behind one that is not the end line
+ * (n == 0 is that case); nothing behind the last whole line is read.  Only version 31 is decoded below; the caller
+ * checks.  ESVIO_FE_EINVAL: null bytes with n > 0, null out. */
+typedef struct esvio_fe_aedat_header_info {
+  uint64_t payload_offset;
+  int32_t version;  /* 0: not stated */
+  int32_t complete;
+} esvio_fe_aedat_header_info;
+int esvio_fe_aedat_header(const void* bytes, size_t n, esvio_fe_aedat_header_info* out);
+/* the decode stage: camera `cam`'s event walker advanced by the n_bytes at `bytes`, the records written to dst (room for
+ * dst_cap records; dst_space as esvio_fe_decode_raw's: ESVIO_FE_DEVICE, 16-byte aligned, or ESVIO_FE_HOST).  More
+ * emitted events than dst_cap: ESVIO_FE_EINVAL, info->events holds the exact count needed, the state is as it was; the
+ * sum of the chunk's eventNumber (plus one for a record the last chunk cut) always suffices.  n_bytes == 0 succeeds and
+ * touches nothing; n_bytes <= 2^28.  info is optional.  Orders itself on the main stream, waits for its own result and
+ * touches nothing of the tracker: made between two track calls it changes no later tracking result.  Its scratch — 8
+ * pinned and 8 device bytes per polarity record, the run table, 4 bytes per tile, the records behind a host dst — grows
+ * on first use and with esvio_fe_reserve for a handle that has decoded AEDAT before: a second call of a given size
+ * allocates nothing.  ESVIO_FE_EINVAL with a message, before any device work: cam outside 0..1, flags with unknown bits,
+ * null bytes with n_bytes > 0, a null dst with dst_cap > 0, a bad dst_space, a misaligned device dst,
+ * |t_offset_ns| > 2^62, n_bytes > 2^28, a malformed header. */
+int esvio_fe_decode_aedat(esvio_fe_handle h, int cam, const void* bytes, size_t n_bytes, int64_t t_offset_ns, uint32_t flags,
+                          esvio_fe_event* dst, size_t dst_cap, int dst_space, esvio_fe_aedat_info* info);
+/* the side call: camera `cam`'s side walker advanced by the same kind of chunk; IMU6 samples to imu (HOST, room for
+ * imu_cap), external-input specials to trig (HOST, room for trig_cap), both in stream order.  More of either than its
+ * capacity: ESVIO_FE_EINVAL, info->imu / info->triggers hold the numbers needed, the state is as it was.  A BAD sample or
+ * trigger: ESVIO_FE_EINVAL, info->bad exact, the state as it was.  Runs on the host alone; argument errors as above. */
+int esvio_fe_aedat_side(esvio_fe_handle h, int cam, const void* bytes, size_t n_bytes, int64_t t_offset_ns, uint32_t flags,
+                        esvio_fe_imu_sample* imu, size_t imu_cap, esvio_fe_trigger* trig, size_t trig_cap,
+                        esvio_fe_aedat_side_info* info);
+/* esvio_fe_track_raw with the decode chain exchanged: both cameras' chunks are walked, both chains enqueued, the host
+ * waits once, and the records are tracked from the handle's two alternating buffer pairs with cur_time = the stamp of the
+ * last LEFT record the tracker is given; `filter` and `motion` as there.  Capacity is the host-known sum of eventNumber,
+ * so no launch is ever repeated.  aedat[cam] (optional) as esvio_fe_decode_aedat's info.  A BAD event or a malformed
+ * header in either camera: ESVIO_FE_EINVAL, nothing tracked, BOTH cameras' walker states as they were — the states move
+ * only when the call returns ESVIO_FE_OK.  Refused while batches are announced. */
+int esvio_fe_track_aedat(esvio_fe_handle h, const void* left, size_t left_bytes, const void* right, size_t right_bytes,
+                         int64_t t_offset_ns, uint32_t flags, int pub_this_frame, const esvio_fe_filter_params* filter,
+                         const esvio_fe_motion* motion, esvio_fe_tracks* out, esvio_fe_batch_info* info,
+                         esvio_fe_aedat_info aedat[2]);
 
 /* ---- stream slicing: a record stream cut into fixed-rate windows, on the device ------------ */
 /* trackEvent takes one batch per camera and call; a recording or a sensor transfer is a long stream whose batch edges
@@ -975,6 +1102,10 @@ int esvio_fe_feed_push_fields(esvio_fe_handle h, int cam, const esvio_fe_event_f
                               esvio_fe_feed_info* info);
 int esvio_fe_feed_push_raw(esvio_fe_handle h, int cam, int format, const void* words, size_t n_bytes, int space,
                            int64_t t_offset_us, esvio_fe_feed_info* info);
+/* esvio_fe_feed_push_raw for an AEDAT 3.1 chunk (host memory; it may end anywhere): the polarity events are appended,
+ * everything else is skipped; failures as esvio_fe_decode_aedat's, with nothing appended and the walker as it was */
+int esvio_fe_feed_push_aedat(esvio_fe_handle h, int cam, const void* bytes, size_t n_bytes, int64_t t_offset_ns, uint32_t flags,
+                             esvio_fe_feed_info* info);
 int esvio_fe_feed_peek(esvio_fe_handle h, esvio_fe_feed_window* out);
 int esvio_fe_feed_track(esvio_fe_handle h, int pub_this_frame, const esvio_fe_motion* motion, esvio_fe_tracks* out,
                         esvio_fe_batch_info* info);

@@ -185,7 +185,8 @@ int esvio_fe_set_profiling(esvio_fe_handle h, int on);
 int esvio_fe_kernel_count(void);
 /* ids 0 .. esvio_fe_kernel_count()-1: the kernels of the tracker's entry points; ids up to
  * esvio_fe_stage_kernel_count()-1: those and the kernels of stages no track call launches (esvio_fe_filter_events).
- * esvio_fe_kernel_name and esvio_fe_get_kernel_stats take every id below esvio_fe_stage_kernel_count(). */
+ * esvio_fe_kernel_name and esvio_fe_get_kernel_stats take every id below esvio_fe_stage_kernel_count() — and the ingest
+ * range behind it, esvio_fe_ingest_kernel_count() below. */
 int esvio_fe_stage_kernel_count(void);
 const char* esvio_fe_kernel_name(int kernel_id);
 /* total_ms / launches / algorithmic bytes accumulated since the last reset_kernel_stats */
@@ -194,6 +195,20 @@ int esvio_fe_get_kernel_stats(esvio_fe_handle h, int kernel_id, double* total_ms
 int esvio_fe_reset_kernel_stats(esvio_fe_handle h);
 /* the bytes of raw words one workgroup of the decode chain takes (esvio_fe_decode_raw): where its tile edges lie */
 int esvio_fe_raw_tile_bytes(void);
+/* the AEDAT chain: events per tile of k_aedat_count / k_aedat_emit; the timer ids of its kernels are a range of their
+ * own BEHIND the stage table — esvio_fe_stage_kernel_count() <= id < esvio_fe_ingest_kernel_count() —, which
+ * esvio_fe_kernel_name and esvio_fe_get_kernel_stats take as well; the stage table itself stays as it is */
+int esvio_fe_aedat_tile_events(void);
+int esvio_fe_ingest_kernel_count(void);
+/* The AEDAT host walk alone (esvio_amd/csrc/fe_aedat.h), no handle and no device: an event walker's state in and out
+ * (state_bytes == esvio_fe_aedat_walk_state_bytes(); all zero is the fresh state), the n_bytes of a chunk in; out come
+ * the run table — runs[2k] = index of the run's first record in the packed payload, runs[2k+1] = its eventTSOverflow as
+ * a bit pattern; at most runs_cap entries are written —, the packed 8-byte polarity records (at most events_cap of them)
+ * and counts = {records, runs, polarity packets, other packets} of the chunk, counted whether stored or not.  runs and
+ * payload may be null.  A malformed header: ESVIO_FE_EINVAL, the state as it was. */
+int esvio_fe_aedat_walk_tap(void* state, size_t state_bytes, const void* bytes, size_t n_bytes, uint32_t* runs, size_t runs_cap,
+                            uint8_t* payload, size_t events_cap, uint64_t counts[4]);
+int esvio_fe_aedat_walk_state_bytes(void);
 /* the events one workgroup of the slicing chain takes (esvio_fe_slice_events): where its tile edges lie */
 int esvio_fe_slice_tile_events(void);
 /* the hipStream_t the handle launches on (as void*) */
