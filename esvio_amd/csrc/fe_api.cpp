@@ -238,6 +238,7 @@ int esvio_fe_create(const esvio_fe_config* cfg, esvio_fe_handle* out) {
   if (const char* v = getenv("ESVIO_FE_CONVERT_PINNED_COPY")) c->cvt_pinned_copy = atoi(v) != 0 ? 1 : 0;
   if (const char* v = getenv("ESVIO_FE_RAW_PINNED_COPY")) c->rawdec.pinned_copy = atoi(v) != 0 ? 1 : 0;
   if (const char* v = getenv("ESVIO_FE_AEDAT_WAVE_LOOKUP")) c->aedat.wave_lookup = atoi(v) != 0 ? 1 : 0;
+  if (const char* v = getenv("ESVIO_FE_BAG_WAVE_LOADS")) c->bag.wave_loads = atoi(v) != 0 ? 1 : 0;
   c->select_one_wave = getenv("ESVIO_FE_SELECT_SERIAL") != nullptr;
   if (const char* v = getenv("ESVIO_FE_SAE_EV_MIN")) c->sae_ev_min = (size_t)strtoull(v, nullptr, 10);
   c->tiled = make_tile_geom(c->W, c->H, &c->tgeom) && getenv("ESVIO_FE_SAE_SORT") == nullptr;
@@ -396,6 +397,7 @@ int esvio_fe_reset(esvio_fe_handle c) {
   c->rawdec.st[0] = c->rawdec.st[1] = esvio_fe_ctx::Raw::State();  // the raw-stream decoder: the fresh state
   c->rawdec.trig_st[0] = c->rawdec.trig_st[1] = esvio_fe_ctx::Raw::State();  // ... and the trigger decoder's
   for (int cam = 0; cam < 2; cam++) c->aedat.ev_st[cam] = c->aedat.side_st[cam] = esvio::aedat::Walk{};  // ... and the AEDAT walkers'
+  c->bag.ev_st = c->bag.side_st = esvio::bag::Walk{};  // ... and the bag walkers' (the topics are settings: kept)
   c->slice.st[0] = c->slice.st[1] = esvio_fe_ctx::Slice::State();  // the stream slicer: no event seen, no window closed
   HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
   feed_empty(c, true);  // an open feed: no records, no windows (it stays open); every stream is idle here
@@ -2011,6 +2013,7 @@ int esvio_fe_decode_reset(esvio_fe_handle c) {
   c->rawdec.st[0] = c->rawdec.st[1] = esvio_fe_ctx::Raw::State();
   c->rawdec.trig_st[0] = c->rawdec.trig_st[1] = esvio_fe_ctx::Raw::State();
   for (int cam = 0; cam < 2; cam++) c->aedat.ev_st[cam] = c->aedat.side_st[cam] = esvio::aedat::Walk{};
+  c->bag.ev_st = c->bag.side_st = esvio::bag::Walk{};
   return 0;
 }
 
@@ -2510,6 +2513,210 @@ int esvio_fe_aedat_walk_tap(void* state, size_t state_bytes, const void* bytes, 
   return 0;
 }
 int esvio_fe_aedat_walk_state_bytes(void) { return (int)sizeof(ae::Walk); }
+
+// ---- rosbag v2.0 recordings (the rule: include/esvio_fe.h; the host walk: fe_bag.h; the kernel: fe_kernels.h)
+namespace {
+namespace bg = esvio::bag;
+static_assert(bg::kEventBytes == kBagEventBytes, "the walk's wire event is the kernel's");
+struct BagCall {  // one call's walk and device work
+  bg::Walk st{};   // the state behind the chunk: taken over when the call succeeds
+  bg::Out cnt;     // what the counting walk found
+  EventRec* d_dst[2] = {nullptr, nullptr};
+  size_t cap[2] = {0, 0};
+  BagResult r[2] = {};
+};
+
+int bag_args_check(esvio_fe_ctx* c, const char* who, const void* bytes, size_t n_bytes, uint32_t flags) {
+  if (flags) return fail(c, ESVIO_FE_EINVAL, "%s: unknown bits in flags (0x%x)", who, flags);
+  if (n_bytes > kRawMaxBytes) return fail(c, ESVIO_FE_EINVAL, "%s: a chunk holds at most 2^28 bytes", who);
+  if (n_bytes && !bytes) return fail(c, ESVIO_FE_EINVAL, "%s: bytes is null", who);
+  return 0;
+}
+// the counting walk: everything in the chunk checked, the events and messages counted, nothing stored, no state moved
+int bag_count_walk(esvio_fe_ctx* c, const char* who, const void* bytes, size_t n_bytes, BagCall* b) {
+  bg::Walk probe = c->bag.ev_st;
+  if (!bg::walk(&probe, c->bag.topics, bg::kEvents, (const uint8_t*)bytes, n_bytes, &b->cnt))
+    return fail(c, ESVIO_FE_EINVAL, "%s: malformed bag (%s); the walker's state is as it was", who, b->cnt.why);
+  return 0;
+}
+size_t bag_right_offset(size_t n_left) { return (n_left * kBagEventBytes + 15) & ~(size_t)15; }
+uint32_t bag_tiles(size_t n) { return (uint32_t)((n + kBagTile - 1) / kBagTile); }
+int bag_ensure(esvio_fe_ctx* c, size_t n_left, size_t n_right) {
+  esvio_fe_ctx::Bag& B = c->bag;
+  B.used = true;
+  if (!B.res)
+    if (int rc = B.res.alloc(c, 2)) return rc;
+  const size_t bytes = bag_right_offset(n_left) + bag_right_offset(n_right);  // (each camera's part readable up to a multiple of 16)
+  if (int rc = B.h_pack.grow(c, bytes)) return rc;
+  return B.d_pack.grow(c, bytes);
+}
+// The gathering walk, the copy, the launch and the copies that bring the result blocks to the host, on the current
+// stream; nothing is waited for.  A camera without an event in the chunk takes no part on the device.
+int bag_enqueue(esvio_fe_ctx* c, const void* bytes, size_t n_bytes, BagCall* b, esvio_fe_bag_message* msgs, size_t msgs_cap) {
+  esvio_fe_ctx::Bag& B = c->bag;
+  hipStream_t s = cur_stream(c);
+  const size_t n[2] = {(size_t)b->cnt.n_events[0], (size_t)b->cnt.n_events[1]}, off1 = bag_right_offset(n[0]);
+  if (n[0] + n[1])
+    if (int rc = bag_ensure(c, n[0], n[1])) return rc;
+  bg::Out o;
+  if (n[0] + n[1]) o.payload[0] = B.h_pack, o.payload[1] = B.h_pack + off1, o.events_cap[0] = n[0], o.events_cap[1] = n[1];
+  o.msgs = msgs, o.msgs_cap = msgs ? msgs_cap : 0;
+  b->st = B.ev_st;
+  bg::walk(&b->st, B.topics, bg::kEvents, (const uint8_t*)bytes, n_bytes, &o);  // (checked by the counting walk)
+  if (!(n[0] + n[1])) return 0;
+  HIPCHK(c, hipMemcpyAsync(B.d_pack, B.h_pack, off1 + n[1] * kBagEventBytes, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemsetAsync(B.res, 0, 2 * sizeof(BagResult), s));
+  BagArgs a{};
+  a.wave_loads = (uint32_t)B.wave_loads;
+  uint64_t stored = 0;
+  for (int cam = 0; cam < 2; cam++) {
+    BagCam& bc = a.cam[cam];
+    bc.src = B.d_pack.p + (cam ? off1 : 0), bc.n = (uint32_t)n[cam], bc.tiles = bag_tiles(n[cam]);
+    bc.dst = b->d_dst[cam], bc.dst_cap = (uint32_t)std::min<size_t>(b->cap[cam], 0xffffffffu), bc.res = B.res + cam;
+    if (n[cam] <= b->cap[cam]) stored += n[cam];
+  }
+  {
+    ScopedKernel k(c, K_BAG_EMIT, (n[0] + n[1]) * kBagEventBytes + stored * 16);
+    launch_bag_emit(s, a);
+  }
+  for (int cam = 0; cam < 2; cam++)
+    if (n[cam]) HIPCHK(c, hipMemcpyAsync(&b->r[cam], B.res + cam, sizeof(BagResult), hipMemcpyDeviceToHost, s));
+  return 0;
+}
+void bag_info_clear(esvio_fe_bag_info* info) {
+  if (!info) return;
+  for (int cam = 0; cam < 2; cam++) info->cam[cam].events = info->cam[cam].bad = info->cam[cam].messages = 0;
+  info->other_messages = info->other_records = info->chunks = info->connections = 0;
+}
+void bag_info_host(esvio_fe_bag_info* info, const bg::Out& o) {
+  if (!info) return;
+  for (int cam = 0; cam < 2; cam++) info->cam[cam].events = o.n_events[cam], info->cam[cam].messages = o.n_cam_msgs[cam];
+  info->other_messages = o.other_messages, info->other_records = o.other_records, info->chunks = o.chunks, info->connections = o.connections;
+}
+void bag_info_device(esvio_fe_bag_info* info, const BagCall& b) {
+  if (!info) return;
+  for (int cam = 0; cam < 2; cam++) {
+    const BagResult& r = b.r[cam];
+    info->cam[cam].bad = r.bad;
+    if (b.cnt.n_events[cam] && !r.bad)
+      info->cam[cam].first_sec = r.first_sec, info->cam[cam].first_nsec = r.first_nsec, info->cam[cam].last_sec = r.last_sec, info->cam[cam].last_nsec = r.last_nsec;
+  }
+}
+}  // namespace
+
+int esvio_fe_bag_tile_events(void) { return (int)kBagTile; }
+
+int esvio_fe_bag_header(const void* bytes, size_t n, esvio_fe_bag_header_info* out) { return bg::file_header(bytes, n, out); }
+
+int esvio_fe_bag_set_topics(esvio_fe_handle c, const esvio_fe_bag_topics* topics) {
+  if (!c) return ESVIO_FE_EINVAL;
+  const char* why = nullptr;
+  if (!bg::set_topics(topics, &c->bag.topics, &why)) return fail(c, ESVIO_FE_EINVAL, "bag_set_topics: %s", why);
+  c->bag.ev_st = c->bag.side_st = bg::Walk{};
+  return 0;
+}
+
+int esvio_fe_decode_bag(esvio_fe_handle c, const void* bytes, size_t n_bytes, uint32_t flags, esvio_fe_event* const dst[2],
+                        const size_t dst_cap[2], int dst_space, esvio_fe_bag_message* msgs, size_t msgs_cap, esvio_fe_bag_info* info) {
+  if (!c) return ESVIO_FE_EINVAL;
+  bag_info_clear(info);
+  if (int rc = bag_args_check(c, "decode_bag", bytes, n_bytes, flags)) return rc;
+  if (dst_space != ESVIO_FE_HOST && dst_space != ESVIO_FE_DEVICE) return fail(c, ESVIO_FE_EINVAL, "decode_bag: bad memory space");
+  const size_t room[2] = {dst && dst_cap ? dst_cap[0] : 0, dst && dst_cap ? dst_cap[1] : 0};
+  for (int cam = 0; cam < 2; cam++) {
+    if (room[cam] && !dst[cam]) return fail(c, ESVIO_FE_EINVAL, "decode_bag: dst[%d] is null", cam);
+    if (room[cam] && dst_space == ESVIO_FE_DEVICE && ((uintptr_t)dst[cam] & 15) != 0)
+      return fail(c, ESVIO_FE_EINVAL, "decode_bag: a device dst must be 16-byte aligned");
+  }
+  if (msgs_cap && !msgs) return fail(c, ESVIO_FE_EINVAL, "decode_bag: msgs is null");
+  if (!n_bytes) return 0;
+  BagCall b;
+  if (int rc = bag_count_walk(c, "decode_bag", bytes, n_bytes, &b)) return rc;
+  bag_info_host(info, b.cnt);
+  HIPCHK(c, hipSetDevice(c->dev));
+  const size_t n[2] = {(size_t)b.cnt.n_events[0], (size_t)b.cnt.n_events[1]};
+  for (int cam = 0; cam < 2; cam++) {
+    b.cap[cam] = std::min(room[cam], n[cam]);
+    b.d_dst[cam] = room[cam] ? (EventRec*)dst[cam] : nullptr;
+    if (dst_space == ESVIO_FE_HOST && b.cap[cam]) {  // the records behind a host dst
+      if (int rc = c->rawdec.dec[cam].grow(c, b.cap[cam])) return rc;
+      b.d_dst[cam] = c->rawdec.dec[cam];
+    }
+  }
+  if (int rc = bag_enqueue(c, bytes, n_bytes, &b, msgs, msgs_cap)) return rc;
+  HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  if (c->prof_on) resolve_profile(c);
+  bag_info_device(info, b);
+  if (b.r[0].bad || b.r[1].bad)
+    return fail(c, ESVIO_FE_EINVAL, "decode_bag: %llu of %zu events have nsec >= 10^9; the walker's state is as it was", b.r[0].bad + b.r[1].bad,
+                n[0] + n[1]);
+  if (n[0] > room[0] || n[1] > room[1])
+    return fail(c, ESVIO_FE_EINVAL, "decode_bag: the chunk holds %zu left and %zu right events, dst has room for %zu and %zu; the walker's state is as it was",
+                n[0], n[1], room[0], room[1]);
+  if (b.cnt.n_msgs > msgs_cap)
+    return fail(c, ESVIO_FE_EINVAL, "decode_bag: the chunk completes %llu event messages, msgs has room for %zu; the walker's state is as it was",
+                (unsigned long long)b.cnt.n_msgs, msgs_cap);
+  if (dst_space == ESVIO_FE_HOST && n[0] + n[1]) {
+    for (int cam = 0; cam < 2; cam++)
+      if (n[cam]) HIPCHK(c, hipMemcpyAsync(dst[cam], b.d_dst[cam], n[cam] * sizeof(EventRec), hipMemcpyDeviceToHost, cur_stream(c)));
+    HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  }
+  c->bag.ev_st = b.st;
+  return 0;
+}
+
+int esvio_fe_bag_side(esvio_fe_handle c, const void* bytes, size_t n_bytes, uint32_t flags, esvio_fe_imu_sample* imu, size_t imu_cap,
+                      esvio_fe_bag_side_info* info) {
+  if (!c) return ESVIO_FE_EINVAL;
+  if (info) *info = esvio_fe_bag_side_info{};
+  if (int rc = bag_args_check(c, "bag_side", bytes, n_bytes, flags)) return rc;
+  if (imu_cap && !imu) return fail(c, ESVIO_FE_EINVAL, "bag_side: imu is null");
+  if (!n_bytes) return 0;
+  bg::Walk st = c->bag.side_st;
+  bg::Out o;
+  o.imu = imu, o.imu_cap = imu_cap;
+  if (!bg::walk(&st, c->bag.topics, bg::kSide, (const uint8_t*)bytes, n_bytes, &o))
+    return fail(c, ESVIO_FE_EINVAL, "bag_side: malformed bag (%s); the walker's state is as it was", o.why);
+  if (info) {
+    info->imu = o.n_imu, info->bad = o.bad;
+    info->other_messages = o.other_messages, info->other_records = o.other_records, info->chunks = o.chunks, info->connections = o.connections;
+  }
+  if (o.bad)
+    return fail(c, ESVIO_FE_EINVAL, "bag_side: %llu samples have a stamp with nsec >= 10^9; the walker's state is as it was", (unsigned long long)o.bad);
+  if (o.n_imu > imu_cap)
+    return fail(c, ESVIO_FE_EINVAL, "bag_side: the chunk holds %llu samples, there is room for %zu; the walker's state is as it was",
+                (unsigned long long)o.n_imu, imu_cap);
+  c->bag.side_st = st;
+  return 0;
+}
+
+// the walk tap (include/esvio_fe_test.h): the host walk alone, no handle, no device
+int esvio_fe_bag_walk_tap(void* state, size_t state_bytes, const esvio_fe_bag_topics* topics, int side, const void* bytes, size_t n_bytes,
+                          uint8_t* const payload[2], const size_t events_cap[2], esvio_fe_bag_message* msgs, size_t msgs_cap,
+                          esvio_fe_imu_sample* imu, size_t imu_cap, uint64_t counts[12], char* why, size_t why_cap) {
+  if (why && why_cap) why[0] = 0;
+  if (!state || state_bytes != sizeof(bg::Walk) || (n_bytes && !bytes) || !counts) return ESVIO_FE_EINVAL;
+  bg::Topics t;
+  const char* bad_topics = nullptr;
+  if (!bg::set_topics(topics, &t, &bad_topics)) return ESVIO_FE_EINVAL;
+  bg::Walk st;
+  memcpy(&st, state, sizeof st);
+  bg::Out o;
+  if (payload && events_cap)
+    for (int cam = 0; cam < 2; cam++) o.payload[cam] = payload[cam], o.events_cap[cam] = payload[cam] ? events_cap[cam] : 0;
+  o.msgs = msgs, o.msgs_cap = msgs ? msgs_cap : 0, o.imu = imu, o.imu_cap = imu ? imu_cap : 0;
+  const bool ok = bg::walk(&st, t, side ? bg::kSide : bg::kEvents, (const uint8_t*)bytes, n_bytes, &o);
+  const uint64_t v[12] = {o.n_events[0], o.n_events[1], o.n_cam_msgs[0], o.n_cam_msgs[1], o.n_msgs, o.n_imu,
+                          o.bad, o.other_messages, o.other_records, o.chunks, o.connections, 0};
+  memcpy(counts, v, sizeof v);
+  if (!ok) {  // (the caller's state is as it was)
+    if (why && why_cap) snprintf(why, why_cap, "%s", o.why);
+    return ESVIO_FE_EINVAL;
+  }
+  memcpy(state, &st, sizeof st);
+  return 0;
+}
+int esvio_fe_bag_walk_state_bytes(void) { return (int)sizeof(bg::Walk); }
 
 // ---- stream slicing: a record stream cut into fixed-rate windows (the rule: include/esvio_fe.h; the chain: fe_kernels.h)
 namespace {
@@ -3147,6 +3354,61 @@ int esvio_fe_feed_push_aedat(esvio_fe_handle c, int cam, const void* bytes, size
   FeedSrc src{FEED_AEDAT};
   src.words = bytes, src.n_bytes = n_bytes, src.t_offset_us = t_offset_ns, src.flags = flags, src.space = ESVIO_FE_HOST;
   return feed_push(c, "feed_push_aedat", cam, src, info);
+}
+
+// Both cameras' events of a bag chunk into the feed: decoded into the decode stage's buffers, then appended left before
+// right as device records.  The left camera's append is undone when the right camera's fails: nothing is appended to
+// either, and the walker moves only when both are.
+int esvio_fe_feed_push_bag(esvio_fe_handle c, const void* bytes, size_t n_bytes, uint32_t flags, esvio_fe_feed_info info[2]) {
+  if (!c) return ESVIO_FE_EINVAL;
+  const char* who = "feed_push_bag";
+  if (info) info[0] = info[1] = esvio_fe_feed_info{};
+  if (int rc = feed_gate(c, who)) return rc;
+  esvio_fe_ctx::Feed& f = c->feed;
+  for (int cam = 0; cam < 2 && info; cam++) feed_info_fill(&info[cam], f.cam[cam], 0, 0, 0, 0);
+  if (int rc = bag_args_check(c, who, bytes, n_bytes, flags)) return rc;
+  if (!n_bytes) return 0;
+  BagCall b;
+  if (int rc = bag_count_walk(c, who, bytes, n_bytes, &b)) return rc;
+  const size_t n[2] = {(size_t)b.cnt.n_events[0], (size_t)b.cnt.n_events[1]};
+  if (n[1] && !n[0] && !f.origin_known)
+    return fail(c, ESVIO_FE_EINVAL, "%s: the origin is the first left record; this chunk brings right events and no left one, and none has been appended yet "
+                "(push a longer chunk, or open the feed with an origin); the walker's state is as it was", who);
+  HIPCHK(c, hipSetDevice(c->dev));
+  for (int cam = 0; cam < 2; cam++) {
+    if (!n[cam]) continue;
+    if (int rc = c->rawdec.dec[cam].grow(c, n[cam])) return rc;
+    b.d_dst[cam] = c->rawdec.dec[cam], b.cap[cam] = n[cam];
+  }
+  if (int rc = bag_enqueue(c, bytes, n_bytes, &b, nullptr, 0)) return rc;
+  HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  if (c->prof_on) resolve_profile(c);
+  if (b.r[0].bad || b.r[1].bad) {
+    for (int cam = 0; cam < 2 && info; cam++) feed_info_fill(&info[cam], f.cam[cam], 0, 0, b.r[cam].bad, 0);
+    return fail(c, ESVIO_FE_EINVAL, "%s: %llu of %zu events have nsec >= 10^9; nothing was appended, the walker's state is as it was", who,
+                b.r[0].bad + b.r[1].bad, n[0] + n[1]);
+  }
+  // what the left camera's append moves, for the case that the right camera's fails
+  FeedCam& fl = f.cam[0];
+  const uint64_t end0 = fl.pos0 + fl.len, open0 = fl.open_begin;
+  const size_t win0 = fl.win.size();
+  const SliceState slice0 = c->slice.st[0];
+  const bool origin0 = f.origin_known;
+  for (int cam = 0; cam < 2; cam++) {
+    FeedSrc src{FEED_EVENTS};
+    src.ev = (const esvio_fe_event*)b.d_dst[cam], src.n = n[cam], src.space = ESVIO_FE_DEVICE;
+    const int rc = feed_push(c, who, cam, src, info ? &info[cam] : nullptr);
+    if (rc == 0) continue;
+    if (cam == 1) {
+      fl.len = end0 - fl.pos0, fl.open_begin = open0;
+      while (fl.win.size() > win0) fl.win.pop_back();
+      c->slice.st[0] = slice0, f.origin_known = origin0;
+      if (info) feed_info_fill(&info[0], fl, 0, 0, 0, 0);
+    }
+    return rc;
+  }
+  c->bag.ev_st = b.st;
+  return 0;
 }
 
 int esvio_fe_feed_peek(esvio_fe_handle c, esvio_fe_feed_window* out) {
@@ -3802,6 +4064,9 @@ int esvio_fe_reserve(esvio_fe_handle c, size_t max_left, size_t max_right, int h
     for (int cam = 0; cam < 2; cam++)
       if (int rc = aedat_ensure(c, cam, ev[cam], ev[cam])) return rc;
   }
+  // a handle that decodes bags: the scratch of a chunk of max_left and max_right events
+  if (c->bag.used)
+    if (int rc = bag_ensure(c, max_left, max_right)) return rc;
   // a handle with an open feed: per camera both buffers for 2 * max_events records (the one that holds records is left alone)
   if (c->feed.open) {
     const size_t ev[2] = {max_left, max_right};

@@ -30,6 +30,7 @@
 #include "../../include/esvio_fe.h"
 #include "../../include/esvio_fe_test.h"
 #include "fe_aedat.h"
+#include "fe_bag.h"
 #include "fe_host.h"
 #include "fe_kernels.h"
 #include "fe_layout.h"
@@ -75,7 +76,7 @@ const char* const kKernelNames[K_COUNT] = {
     "k_raw_emit", "k_slice_reduce", "k_slice_scan", "k_slice_cuts", "k_baf_keys_addr", "k_hot_count", "k_hot_keys",
     "k_hot_pick", "k_trig_reduce", "k_trig_emit"};
 // the ingest range behind the stage table (IngestKernelId, fe_kernels.h): esvio_fe_ingest_kernel_count()
-const char* const kIngestKernelNames[K_INGEST_COUNT - K_COUNT] = {"k_aedat_count", "k_aedat_scan", "k_aedat_emit"};
+const char* const kIngestKernelNames[K_INGEST_COUNT - K_COUNT] = {"k_aedat_count", "k_aedat_scan", "k_aedat_emit", "k_bag_emit"};
 
 // The host phases of one trackEvent call, in the order of esvio_fe_latency_call::phase_ms; kPhaseNames is what
 // esvio_fe_latency_phase_name returns and what the ESVIO_FE_TRACE summary prints.  The PH_PUB_* phases are parts of
@@ -559,6 +560,23 @@ struct esvio_fe_ctx {
     bool used = false;  // esvio_fe_reserve grows the scratch of a handle that has decoded AEDAT before
     int wave_lookup = 0;  // ESVIO_FE_AEDAT_WAVE_LOOKUP=1: k_aedat_emit's run look-up once per wave with a forward step (the A/B in KERNELS.md)
   } aedat;
+
+  // ---- esvio_fe_decode_bag / esvio_fe_bag_side / esvio_fe_feed_push_bag: rosbag v2.0 recordings (include/esvio_fe.h has
+  // the rule, fe_bag.h the host walk, fe_kernels.h the kernel).  topics: esvio_fe_bag_set_topics' copies.  ev_st /
+  // side_st: the handle's two walker states, on the HOST: a call walks a copy and takes it over only once it is known
+  // to succeed.  Allocated on first use and the stage's own (main stream only): h_pack, the pinned scratch the walk
+  // gathers into — the left camera's wire events, the right camera's behind them at a 16-byte boundary —, d_pack its
+  // device copy (one transfer); res, the two result blocks.  The records behind a host dst,
+  // and on their way into the feed, are rawdec.dec's.
+  struct Bag {
+    esvio::bag::Topics topics;
+    esvio::bag::Walk ev_st = {}, side_st = {};
+    PinBuf<uint8_t> h_pack;
+    DevBuf<uint8_t> d_pack;
+    DevBuf<BagResult> res;
+    bool used = false;   // esvio_fe_reserve grows the scratch of a handle that has decoded a bag before
+    int wave_loads = 0;  // ESVIO_FE_BAG_WAVE_LOADS=1 / 0: k_bag_emit's wave-cooperative dwordx4 loads through LDS / per-lane loads (the A/B in KERNELS.md)
+  } bag;
 
   // ---- esvio_fe_slice_events: a record stream cut into fixed-rate windows (include/esvio_fe.h has the rule,
   // fe_kernels.h the chain).  st: each camera's state, kept on the HOST like the decoder's: the device works on counts

@@ -707,7 +707,7 @@ void launch_trig_emit(hipStream_t s, const RawArgs& a);
 // tiles share each grid, as in the raw chain; no launch waits on the device for another workgroup.
 // The timer slots of these kernels are a range of their own behind K_COUNT (esvio_fe_ingest_kernel_count()): the stage
 // table, whose end a test pins, stays as it is.
-enum IngestKernelId { K_AEDAT_COUNT = K_COUNT, K_AEDAT_SCAN, K_AEDAT_EMIT, K_INGEST_COUNT };
+enum IngestKernelId { K_AEDAT_COUNT = K_COUNT, K_AEDAT_SCAN, K_AEDAT_EMIT, K_BAG_EMIT, K_INGEST_COUNT };
 constexpr uint32_t kAedatTile = 1024;  // records per workgroup: 1024 lanes, one record each
 struct AedatRun {                      // (fe_aedat.h: esvio::aedat::Run)
   uint32_t first;
@@ -739,6 +739,37 @@ struct AedatArgs {
 void launch_aedat_count(hipStream_t s, const AedatArgs& a);
 void launch_aedat_scan(hipStream_t s, const AedatArgs& a);
 void launch_aedat_emit(hipStream_t s, const AedatArgs& a);
+
+// ---- rosbag v2.0: dvs_msgs/EventArray wire events -> event records (esvio_fe_decode_bag, esvio_fe_feed_push_bag) ----
+// include/esvio_fe.h holds the rule.  The host has walked the records (fe_bag.h): what arrives here is each camera's wire
+// events of the chunk, 13 packed bytes each (u16 x, u16 y, u32 sec, u32 nsec, u8 polarity), from a 16-byte aligned base.
+// Every wire event is emitted and the host knows the count, so one launch does it all: k_bag_emit, both cameras' tiles in
+// one grid, one event per lane, 13 bytes in and one 16-byte store out; no workgroup waits for another.  A wave's 64
+// events are 832 bytes = 52 dwordx4, so every wave's span is 64-byte aligned.  Two forms of the load (KERNELS.md "ROS
+// bags" has the measurement): per lane, the byte assembly of k_events_from_fields' element path; or per wave, 52
+// dwordx4 loads of the span staged through LDS, from which each lane cuts its 13 bytes with four dword reads.
+// K_BAG_EMIT is appended to the ingest range (IngestKernelId above).
+constexpr uint32_t kBagTile = 1024;      // events per workgroup: 1024 lanes, one event each
+constexpr uint32_t kBagEventBytes = 13;
+struct BagResult {  // zeroed in front of the launch; k_bag_emit: the BAD events, the first / last event's stamp
+  unsigned long long bad;
+  uint32_t first_sec, first_nsec, last_sec, last_nsec;
+  uint32_t pad[2];
+};
+static_assert(sizeof(BagResult) == 32, "BagResult layout");
+struct BagCam {
+  const uint8_t* src;  // [13 n] the packed wire events, device memory, 16-byte aligned; readable up to the next multiple of 16
+  uint32_t n;
+  uint32_t tiles;      // ceil(n / kBagTile); 0: the camera takes no part
+  EventRec* dst;       // [dst_cap]; nothing is stored when n exceeds dst_cap
+  uint32_t dst_cap;
+  BagResult* res;
+};
+struct BagArgs {
+  BagCam cam[2];       // the grid's blocks: cam[0].tiles, then cam[1].tiles
+  uint32_t wave_loads; // 0: per-lane loads; 1: wave-cooperative dwordx4 loads through LDS
+};
+void launch_bag_emit(hipStream_t s, const BagArgs& a);
 
 // ---- stream slicing: a record stream cut into fixed-rate windows (esvio_fe_slice_events) ----
 // include/esvio_fe.h holds the rule.  An event's window is m_i = max(m_{i-1}, c_i), c_i = the boundaries at or below its

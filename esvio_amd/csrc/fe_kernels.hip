@@ -5024,6 +5024,53 @@ void launch_aedat_emit(hipStream_t s, const AedatArgs& a) {
   if (aedat_grid(a)) launch_k(k_aedat_emit, dim3(aedat_grid(a)), dim3(kAedatTile), 0, s, a);
 }
 
+// ============================================================================ rosbag v2.0 wire events
+// dvs_msgs/EventArray wire events, 13 packed bytes each -> event records (fe_kernels.h has the two forms of the load,
+// include/esvio_fe.h the rule; the record walk is the host's, fe_bag.h).  One event per lane: 13 bytes in, 16 bytes out.
+__global__ __launch_bounds__(kBagTile) void k_bag_emit(BagArgs a) {
+  __shared__ uint4 stage[kBagTile * kBagEventBytes / 16];  // per wave 52 dwordx4 = its 64 events
+  const uint32_t b = blockIdx.x;
+  const uint32_t tile = b < a.cam[0].tiles ? b : b - a.cam[0].tiles;
+  const BagCam& c = b < a.cam[0].tiles ? a.cam[0] : a.cam[1];
+  const uint32_t i = tile * kBagTile + threadIdx.x;
+  const bool active = i < c.n;
+  uint32_t xy = 0, sec = 0, nsec = 0, pol = 0;
+  if (a.wave_loads) {
+    const uint32_t wave = threadIdx.x >> 6, lane = lane_id();
+    const uint32_t w_first = tile * kBagTile + wave * 64u;  // the wave's first event: its span begins 64-byte aligned
+    const uint32_t w_cnt = w_first < c.n ? min(64u, c.n - w_first) : 0u;
+    const uint32_t w_vec = (w_cnt * kBagEventBytes + 15u) / 16u;  // (the last one may reach into the base's padding)
+    if (lane < w_vec) stage[wave * 52u + lane] = ((const uint4*)(c.src + (size_t)w_first * kBagEventBytes))[lane];
+    __syncthreads();
+    if (active) {
+      // the lane's 13 bytes begin at byte 13 * lane of the wave's 832: four dwords from the aligned one below hold them
+      const uint32_t* lw = (const uint32_t*)stage + wave * 208u;
+      const uint32_t o = kBagEventBytes * lane, k = o >> 2, sh = (o & 3u) * 8u;
+      const uint32_t w0 = lw[k], w1 = lw[k + 1], w2 = lw[k + 2], w3 = lw[k + 3];  // (k + 3 <= 207)
+      xy = (uint32_t)((((uint64_t)w1 << 32) | w0) >> sh);
+      sec = (uint32_t)((((uint64_t)w2 << 32) | w1) >> sh);
+      nsec = (uint32_t)((((uint64_t)w3 << 32) | w2) >> sh);
+      pol = (w3 >> sh) & 0xffu;
+    }
+  } else if (active) {
+    const uint8_t* p = c.src + (size_t)i * kBagEventBytes;
+    xy = (uint32_t)ld_any<uint16_t>(p) | (uint32_t)ld_any<uint16_t>(p + 2) << 16;
+    sec = ld_any<uint32_t>(p + 4), nsec = ld_any<uint32_t>(p + 8), pol = p[12];
+  }
+  const bool bad = active && nsec >= 1000000000u;
+  const uint32_t n_bad = (uint32_t)__popcll(bal(bad));
+  if (n_bad && lane_id() == 0) atomicAdd(&c.res->bad, (unsigned long long)n_bad);
+  if (!active) return;
+  if (i == 0) c.res->first_sec = sec, c.res->first_nsec = nsec;
+  if (i + 1 == c.n) c.res->last_sec = sec, c.res->last_nsec = nsec;
+  if (c.n <= c.dst_cap) ((uint4*)c.dst)[i] = make_uint4(xy, sec, nsec, pol != 0u);
+}
+
+void launch_bag_emit(hipStream_t s, const BagArgs& a) {
+  const uint32_t grid = a.cam[0].tiles + a.cam[1].tiles;
+  if (grid) launch_k(k_bag_emit, dim3(grid), dim3(kBagTile), 0, s, a);
+}
+
 // ============================================================================ stream slicing
 // A record stream cut into fixed-rate windows (fe_kernels.h has the chain, include/esvio_fe.h the rule).
 //   slice_count     the boundaries at or below a stamp: the upper bound in the ascending table, by bisection

@@ -189,6 +189,45 @@ class AedatHeaderInfo(C.Structure):
     _fields_ = [("payload_offset", C.c_uint64), ("version", C.c_int32), ("complete", C.c_int32)]
 
 
+class BagTopics(C.Structure):
+    """esvio_fe_bag_topics"""
+    _fields_ = [("left", C.c_char_p), ("right", C.c_char_p), ("imu", C.c_char_p)]
+
+
+class BagHeaderInfo(C.Structure):
+    """esvio_fe_bag_header_info"""
+    _fields_ = [("payload_offset", C.c_uint64), ("index_pos", C.c_uint64), ("conn_count", C.c_uint32), ("chunk_count", C.c_uint32),
+                ("version", C.c_int32), ("complete", C.c_int32)]
+
+
+class BagMessage(C.Structure):
+    """esvio_fe_bag_message"""
+    _fields_ = [("cam", C.c_int32), ("seq", C.c_uint32), ("stamp_sec", C.c_uint32), ("stamp_nsec", C.c_uint32), ("time_sec", C.c_uint32),
+                ("time_nsec", C.c_uint32), ("height", C.c_uint32), ("width", C.c_uint32), ("first", C.c_uint64), ("count", C.c_uint64)]
+
+
+BAG_MESSAGE_DTYPE = np.dtype([("cam", "<i4"), ("seq", "<u4"), ("stamp_sec", "<u4"), ("stamp_nsec", "<u4"), ("time_sec", "<u4"),
+                              ("time_nsec", "<u4"), ("height", "<u4"), ("width", "<u4"), ("first", "<u8"), ("count", "<u8")])
+
+
+class BagCamInfo(C.Structure):
+    """esvio_fe_bag_cam_info"""
+    _fields_ = [("events", C.c_uint64), ("bad", C.c_uint64), ("messages", C.c_uint64), ("first_sec", C.c_uint32), ("first_nsec", C.c_uint32),
+                ("last_sec", C.c_uint32), ("last_nsec", C.c_uint32)]
+
+
+class BagInfo(C.Structure):
+    """esvio_fe_bag_info"""
+    _fields_ = [("cam", BagCamInfo * 2), ("other_messages", C.c_uint64), ("other_records", C.c_uint64), ("chunks", C.c_uint64),
+                ("connections", C.c_uint64)]
+
+
+class BagSideInfo(C.Structure):
+    """esvio_fe_bag_side_info"""
+    _fields_ = [("imu", C.c_uint64), ("bad", C.c_uint64), ("other_messages", C.c_uint64), ("other_records", C.c_uint64),
+                ("chunks", C.c_uint64), ("connections", C.c_uint64)]
+
+
 class EventRecord(C.Structure):
     """esvio_fe_event"""
     _fields_ = [("x", C.c_uint16), ("y", C.c_uint16), ("sec", C.c_uint32), ("nsec", C.c_uint32), ("polarity", C.c_uint8),
@@ -244,6 +283,7 @@ ABI_SYMBOLS = [
     "esvio_fe_convert_events", "esvio_fe_create", "esvio_fe_decode_raw", "esvio_fe_decode_reset",
     "esvio_fe_decode_triggers", "esvio_fe_raw_header", "esvio_fe_slice_events_at",
     "esvio_fe_aedat_header", "esvio_fe_decode_aedat", "esvio_fe_aedat_side", "esvio_fe_track_aedat", "esvio_fe_feed_push_aedat",
+    "esvio_fe_bag_header", "esvio_fe_bag_set_topics", "esvio_fe_decode_bag", "esvio_fe_bag_side", "esvio_fe_feed_push_bag",
     "esvio_fe_create_sae", "esvio_fe_create_sae_stereo", "esvio_fe_create_sae_stereo_mc", "esvio_fe_destroy",
     "esvio_fe_exchange_begin", "esvio_fe_exchange_end", "esvio_fe_exchange_tracks", "esvio_fe_export_image",
     "esvio_fe_feed_close", "esvio_fe_feed_open", "esvio_fe_feed_peek", "esvio_fe_feed_push_events", "esvio_fe_feed_push_fields",
@@ -275,6 +315,7 @@ TEST_SYMBOLS = [
     "esvio_fe_set_profiling", "esvio_fe_set_sae",
     "esvio_fe_slice_tile_events", "esvio_fe_stage_kernel_count", "esvio_fe_stream",
     "esvio_fe_aedat_tile_events", "esvio_fe_ingest_kernel_count", "esvio_fe_aedat_walk_tap", "esvio_fe_aedat_walk_state_bytes",
+    "esvio_fe_bag_tile_events", "esvio_fe_bag_walk_tap", "esvio_fe_bag_walk_state_bytes",
 ]
 
 LATENCY_PHASES = 16
@@ -407,6 +448,12 @@ def load_library(build_if_missing=True):
                                        C.POINTER(Tracks), C.POINTER(BatchInfo), C.POINTER(AedatInfo * 2)]
     L.esvio_fe_feed_push_aedat.argtypes = [vp, i, vp, sz, C.c_int64, u32, C.POINTER(FeedInfo)]
     L.esvio_fe_aedat_walk_tap.argtypes = [vp, sz, vp, sz, vp, sz, vp, sz, vp]
+    L.esvio_fe_bag_header.argtypes = [vp, sz, C.POINTER(BagHeaderInfo)]
+    L.esvio_fe_bag_set_topics.argtypes = [vp, C.POINTER(BagTopics)]
+    L.esvio_fe_decode_bag.argtypes = [vp, vp, sz, u32, C.POINTER(vp * 2), C.POINTER(sz * 2), i, vp, sz, C.POINTER(BagInfo)]
+    L.esvio_fe_bag_side.argtypes = [vp, vp, sz, u32, vp, sz, C.POINTER(BagSideInfo)]
+    L.esvio_fe_feed_push_bag.argtypes = [vp, vp, sz, u32, C.POINTER(FeedInfo * 2)]
+    L.esvio_fe_bag_walk_tap.argtypes = [vp, sz, C.POINTER(BagTopics), i, vp, sz, C.POINTER(vp * 2), C.POINTER(sz * 2), vp, sz, vp, sz, vp, vp, sz]
     L.esvio_fe_feed_track.argtypes = [vp, i, C.POINTER(Motion), C.POINTER(Tracks), C.POINTER(BatchInfo)]
     L.esvio_fe_feed_close.argtypes = [vp]
     L.esvio_fe_set_profiling.argtypes = [vp, i]
@@ -976,6 +1023,74 @@ class FeatureTracker:
         info = FeedInfo()
         return self._feed_pushed(self._hd.L.esvio_fe_feed_push_aedat(self._hd.h, int(cam), _p(buf) if buf.nbytes else None, buf.nbytes,
                                                                      int(t_offset_ns), int(flags), C.byref(info)), info)
+
+    def bag_set_topics(self, left=None, right=None, imu=None):
+        """which topics of a rosbag hold the left and right dvs_msgs/EventArray messages and the sensor_msgs/Imu messages
+        (esvio_fe_bag_set_topics; None: none).  Clears both bag walker states."""
+        self._hd.check(self._hd.L.esvio_fe_bag_set_topics(self._hd.h, C.byref(_bag_topics(left, right, imu))))
+
+    def decode_bag(self, data, dst_cap=None, msgs_cap=None, device=False, flags=0):
+        """the rosbag decode stage (esvio_fe_decode_bag; include/esvio_fe.h has the rule): the event walker advanced by
+        `data` — bytes or a contiguous numpy array, host memory, from the bag's payload_offset on; the chunk may end
+        anywhere.  Returns ((left, right), messages, BagInfo): per camera a numpy EVENT_DTYPE array, or with device=True a
+        FilteredEvents (the caller frees it); messages a numpy BAG_MESSAGE_DTYPE array.  dst_cap None: one record per 13
+        bytes of the chunk, and one for an event the last chunk cut; a number or a pair.  A failed call raises
+        FrontendError with `.info`."""
+        from .events import EVENT_DTYPE
+        L = self._hd.L
+        buf = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data)
+        if dst_cap is None:
+            dst_cap = buf.nbytes // 13 + 1
+        caps = [int(dst_cap)] * 2 if np.isscalar(dst_cap) else [int(dst_cap[0]), int(dst_cap[1])]
+        msgs_cap = buf.nbytes // 28 + 1 if msgs_cap is None else int(msgs_cap)
+        msgs, info = np.zeros(max(msgs_cap, 1), BAG_MESSAGE_DTYPE), BagInfo()
+        ptrs, outs = (C.c_void_p * 2)(), []
+        for cam in range(2):
+            if device:
+                d = C.c_void_p()
+                rc = L.esvio_fe_mem_alloc(DEVICE, 16 * max(caps[cam], 1), C.byref(d))
+                if rc:
+                    raise FrontendError("esvio_fe_mem_alloc rc=%d" % rc)
+                outs.append(d)
+                ptrs[cam] = d.value
+            else:
+                outs.append(np.zeros(max(caps[cam], 1), EVENT_DTYPE))
+                ptrs[cam] = outs[cam].ctypes.data
+        rc = L.esvio_fe_decode_bag(self._hd.h, _p(buf) if buf.nbytes else None, buf.nbytes, int(flags), C.byref(ptrs),
+                                   C.byref((C.c_size_t * 2)(*caps)), DEVICE if device else HOST, _p(msgs), msgs_cap, C.byref(info))
+        if rc:
+            if device:
+                for d in outs:
+                    L.esvio_fe_mem_free(DEVICE, d)
+            e = FrontendError("rc=%d: %s" % (rc, L.esvio_fe_last_error(self._hd.h).decode()))
+            e.info = info
+            raise e
+        k = [int(info.cam[0].events), int(info.cam[1].events)]
+        ev = tuple(FilteredEvents(outs[cam], k[cam], None) if device else outs[cam][:k[cam]] for cam in range(2))
+        return ev, msgs[:int(info.cam[0].messages + info.cam[1].messages)], info
+
+    def bag_side(self, data, imu_cap=None, flags=0):
+        """the sensor_msgs/Imu samples of a chunk of rosbag bytes (esvio_fe_bag_side): the side walker advanced by `data`.
+        Returns (imu, BagSideInfo): a numpy IMU_DTYPE array, what MotionCorrection.imu_samples takes.  imu_cap None: what
+        the chunk can hold at the most.  A failed call raises FrontendError with `.info`."""
+        L = self._hd.L
+        buf = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data)
+        imu_cap = buf.nbytes // 296 + 1 if imu_cap is None else int(imu_cap)
+        imu, info = np.zeros(max(imu_cap, 1), IMU_DTYPE), BagSideInfo()
+        rc = L.esvio_fe_bag_side(self._hd.h, _p(buf) if buf.nbytes else None, buf.nbytes, int(flags), _p(imu), imu_cap, C.byref(info))
+        if rc:
+            e = FrontendError("rc=%d: %s" % (rc, L.esvio_fe_last_error(self._hd.h).decode()))
+            e.info = info
+            raise e
+        return imu[:int(info.imu)], info
+
+    def feed_push_bag(self, data, flags=0):
+        """append both cameras' events of a chunk of rosbag bytes, left before right (esvio_fe_feed_push_bag; host memory;
+        the chunk may end anywhere).  Returns (FeedInfo, FeedInfo); a failed push raises FrontendError with `.info`."""
+        buf = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data)
+        info = (FeedInfo * 2)()
+        self._feed_pushed(self._hd.L.esvio_fe_feed_push_bag(self._hd.h, _p(buf) if buf.nbytes else None, buf.nbytes, int(flags), C.byref(info)), info)
+        return info[0], info[1]
 
     def slice_events(self, cam, ev, frequency=30.0, origin=None, cuts_cap=SLICE_MAX_WINDOWS):
         """the stream-slicing stage (esvio_fe_slice_events; include/esvio_fe.h has the rule): camera `cam`'s slicer
@@ -1762,3 +1877,47 @@ def aedat_walk_tap(state, data, runs_cap=None, events_cap=None):
     n, nr = int(counts[0]), int(counts[1])
     r = np.stack([runs[:nr, 0].astype(np.int64), runs[:nr, 1].view(np.int32).astype(np.int64)], axis=1) if nr else np.zeros((0, 2), np.int64)
     return st.tobytes(), r, pay[:8 * n].tobytes(), tuple(int(v) for v in counts)
+
+
+def _bag_topics(left, right, imu):
+    enc = lambda t: None if t is None else (t if isinstance(t, bytes) else str(t).encode())
+    return BagTopics(enc(left), enc(right), enc(imu))
+
+
+def bag_header(data):
+    """a rosbag's magic and bag header record (esvio_fe_bag_header; host only, no handle): `data` the file's first bytes.
+    Returns the BagHeaderInfo: .payload_offset (13: where the walkers start), .index_pos, .conn_count, .chunk_count,
+    .version (20), .complete.  Bytes that are no bag raise FrontendError."""
+    buf = bytes(data)
+    info = BagHeaderInfo()
+    rc = load_library().esvio_fe_bag_header(buf if buf else None, len(buf), C.byref(info))
+    if rc:
+        raise FrontendError("esvio_fe_bag_header rc=%d" % rc)
+    return info
+
+
+def bag_walk_tap(state, data, topics=(None, None, None), side=False, events_cap=None, msgs_cap=None, imu_cap=None):
+    """the rosbag host walk alone (esvio_fe_bag_walk_tap; include/esvio_fe_test.h): `state` a bytes object (None: the
+    fresh state), topics = (left, right, imu).  Returns (state, (left, right), messages, imu, counts): each camera's
+    gathered 13-byte wire events as bytes, numpy BAG_MESSAGE_DTYPE and IMU_DTYPE arrays (what there was room for), the
+    twelve counts.  A malformed
+    stream raises FrontendError whose text is the broken rule."""
+    L = load_library()
+    nst = L.esvio_fe_bag_walk_state_bytes()
+    st = np.zeros(nst, np.uint8) if state is None else np.frombuffer(bytes(state), np.uint8).copy()
+    buf = np.frombuffer(bytes(data), np.uint8)
+    events_cap = buf.nbytes // 13 + 1 if events_cap is None else events_cap
+    msgs_cap = buf.nbytes // 28 + 1 if msgs_cap is None else msgs_cap
+    imu_cap = buf.nbytes // 296 + 1 if imu_cap is None else imu_cap
+    pay = [np.zeros(max(events_cap, 1) * 13, np.uint8) for _ in range(2)]
+    msgs, imu, counts = np.zeros(max(msgs_cap, 1), BAG_MESSAGE_DTYPE), np.zeros(max(imu_cap, 1), IMU_DTYPE), np.zeros(12, np.uint64)
+    why = C.create_string_buffer(512)
+    ptrs = (C.c_void_p * 2)(pay[0].ctypes.data, pay[1].ctypes.data)
+    rc = L.esvio_fe_bag_walk_tap(_p(st), nst, C.byref(_bag_topics(*topics)), int(bool(side)), _p(buf) if buf.nbytes else None, buf.nbytes,
+                                 C.byref(ptrs), C.byref((C.c_size_t * 2)(events_cap, events_cap)), _p(msgs), msgs_cap, _p(imu), imu_cap,
+                                 _p(counts), why, len(why))
+    if rc:
+        raise FrontendError("esvio_fe_bag_walk_tap rc=%d: %s" % (rc, why.value.decode()))
+    c = tuple(int(v) for v in counts)
+    return (st.tobytes(), tuple(pay[k][:13 * min(c[k], events_cap)].tobytes() for k in range(2)), msgs[:min(c[4], msgs_cap)].copy(),
+            imu[:min(c[5], imu_cap)].copy(), c)

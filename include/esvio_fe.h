@@ -721,7 +721,7 @@ typedef struct esvio_fe_raw_info {
 int esvio_fe_decode_raw(esvio_fe_handle h, int cam, int format, const void* words, size_t n_bytes, int space,
                         int64_t t_offset_us, esvio_fe_event* dst, size_t dst_cap, int dst_space,
                         esvio_fe_raw_info* info);
-/* both cameras' decoder states back to the fresh state (the AEDAT walkers' too) */
+/* both cameras' decoder states back to the fresh state (the AEDAT and bag walkers' too) */
 int esvio_fe_decode_reset(esvio_fe_handle h);
 /* esvio_fe_track_batch for a host that has raw words: both cameras' chunks are decoded into the handle's two alternating
  * buffer pairs (buffer lifetime exactly as esvio_fe_track_event_fields states it) and tracked from there with
@@ -931,6 +931,147 @@ int esvio_fe_track_aedat(esvio_fe_handle h, const void* left, size_t left_bytes,
                          const esvio_fe_motion* motion, esvio_fe_tracks* out, esvio_fe_batch_info* info,
                          esvio_fe_aedat_info aedat[2]);
 
+/* ---- rosbag v2.0 recordings: dvs_msgs/EventArray events of both cameras, sensor_msgs/Imu samples ---- */
+/* The reference is run on ROS bags and nothing else: its README ("3. Run on Dataset") says `rosbag play`, and the HKU
+ * dataset and the DSEC / MVSEC / VECtor conversions its config/ sets are written for are bags that hold
+ * dvs_msgs/EventArray messages on two topics and sensor_msgs/Imu on a third.  WHAT IS CITED: the event's wire order is
+ * feature_tracker/src/dvs_msgs/Event.h:190-193 (x, y, ts, polarity), the message's is EventArray.h:222-225 (header,
+ * height, width, events), the type name and MD5 are EventArray.h:145,158 ("dvs_msgs/EventArray",
+ * "5e8beee5a6c107e504c2e78903c224b8"), the polarity rule is event_detector.cc:133 (ep ? 1 : 0).  WHAT IS RECALLED: the bag
+ * container, std_msgs/Header and sensor_msgs/Imu serialization are ROS's and are not in the reference's tree: THE
+ * CONTAINER AND THESE TWO LAYOUTS ARE RESTATED FROM RECALL of the rosbag 2.0 format and UNPINNED — not claimed to be
+ * bit-equal to rosbag — and THIS TEXT IS THE SPECIFICATION; tests/bag_ref.py is its sequential reading, and the library
+ * equals it exactly.
+ *
+ * Container.  All integers are little-endian.  The file starts with the 13 bytes "#ROSBAG V2.0\n"; the walkers below
+ * start BEHIND them (esvio_fe_bag_header's payload_offset).  Behind them come RECORDS: uint32 header_len, the header,
+ * uint32 data_len, the data.  A header is a sequence of FIELDS, each uint32 field_len followed by field_len bytes
+ * "name=value": the name ends at the first '=', the value is binary.  Every header has a 1-byte field `op`:
+ *   0x03 bag header    index_pos u64, conn_count u32, chunk_count u32         data: padding, skipped
+ *   0x05 chunk         compression (a string), size u32                       data: with "none" a sequence of op 0x02 /
+ *                                                                             0x07 records that ends exactly at data_len;
+ *                                                                             size == data_len
+ *   0x07 connection    conn u32, topic                                        data: a connection header in the same field
+ *                                                                             encoding: type, md5sum (message_definition,
+ *                                                                             callerid, latching, topic are passed over)
+ *   0x02 message data  conn u32, time (u32 sec, u32 nsec)                     data: the serialized message
+ *   0x04 index data, 0x06 chunk info                                          skipped by length, fields not examined
+ *   every other op                                                            skipped by length, counted in other_records
+ * Fields a record does not need are ignored; of a repeated field the last one counts.  Inside a chunk only op 0x02 and
+ * 0x07 may appear.  Connection records also appear outside chunks (at index_pos); a message record outside a chunk is
+ * read like one inside.  `chunks`, `other_records` and `other_messages` count a record in the call that brings the last
+ * byte of its data_len; `connections` counts every connection record in the call that brings its last data byte.
+ *
+ * Roles.  esvio_fe_bag_set_topics names up to three topics: left events, right events, IMU (NULL: none; the strings are
+ * copied; each at most 255 bytes, not empty, no two equal, else ESVIO_FE_EINVAL).  The call clears both walker states.
+ * Without it no topic has a role.  A connection's role is decided by the `topic` field of its record HEADER.  A
+ * connection with a role enters the handle's connection table (conn id -> role) when its record's last data byte
+ * arrives; its data must then hold `type` == "dvs_msgs/EventArray" and `md5sum` == the MD5 above for an event topic, and
+ * `type` == "sensor_msgs/Imu" for the IMU topic (no MD5 is checked there: none can be cited), else the stream is
+ * MALFORMED and the message names the topic.  A connection record whose conn id is in the table must give the same role
+ * (the same topic), else malformed; one without a role whose id is not in the table is passed over.  A message whose
+ * conn is not in the table is skipped and counted in other_messages.
+ *
+ * EventArray message data:  u32 seq, u32 stamp.sec, u32 stamp.nsec, u32 L, L bytes frame_id, u32 height, u32 width, u32 n,
+ * then n * 13 bytes: uint16 x, uint16 y, uint32 sec, uint32 nsec, uint8 polarity.  data_len == 28 + L + 13 n must hold
+ * exactly.  Record: x and y copied as 16-bit patterns, sec and nsec copied, polarity = (wire byte != 0), the padding
+ * bytes 0 — byte for byte what esvio_amd.events.make_events builds.  Every wire event is emitted, in each camera's stream
+ * order.  An event is BAD when nsec >= 10^9; a BAD event fails the call: the info's bad is exact, dst is unspecified.
+ *
+ * Imu message data: the same header (seq, stamp, L, frame_id), then 37 float64: orientation 4, its covariance 9,
+ * angular_velocity 3, covariance 9, linear_acceleration 3, covariance 9.  data_len == 16 + L + 296 exactly.  Output: an
+ * esvio_fe_imu_sample with the header stamp, gyr = angular_velocity, acc = linear_acceleration, the doubles copied bit
+ * for bit.  A sample is BAD when stamp.nsec >= 10^9.
+ *
+ * MALFORMED, besides the length rules above: header_len > 4096; a field that overruns its header (or, in connection
+ * data, its data); a field without '='; a header without `op` or with an `op` not 1 byte long; a missing required field
+ * or one of the wrong length; a `topic` longer than 255 bytes; `type` or `md5sum` of a connection with a role missing or
+ * different; more than 64 connections with a role; an op other than 0x02 / 0x07 inside a chunk, or a record there that
+ * overruns the chunk; a chunk whose `compression` is not "none" — that message tells the user to run `rosbag decompress`:
+ * silently skipping data is worse than refusing.  A malformed stream fails the call with ESVIO_FE_EINVAL before any
+ * device work, whatever else the chunk holds, in the call that brings the last byte of the offending item (a length
+ * word, a header, a connection field's first 264 bytes or its end, a connection's data, a message's fixed part).
+ *
+ * State.  Each handle has TWO walker states, one for esvio_fe_decode_bag and esvio_fe_feed_push_bag, one for
+ * esvio_fe_bag_side; a state is per handle, not per camera: a bag interleaves both.  Each holds the record phase and the
+ * partial header (at most 4 KB), the connection table, the open chunk's and the open message's bytes still to come, the
+ * <= 12 bytes of an event cut by the call's end, and per camera the number of events emitted since the last reset.  A
+ * call's bytes may end anywhere.  Events are emitted as their last byte arrives; a message is listed, and an IMU sample
+ * written, by the call that brings its last byte.  Every failed call leaves the states as they were — malformed input, a
+ * BAD event or sample, too small a destination or table (the exact counts needed come back in the info).
+ * esvio_fe_decode_reset and esvio_fe_reset clear both states (the topics stay).  The same bytes through both calls, in
+ * either order, give events and samples on one time base: the stamps are the recording's own.
+ *
+ * Source.  `bytes` is memory the HOST can read.  The records of a bag are a chain that only a sequential walk can follow,
+ * so the host walks it (esvio_amd/csrc/fe_bag.h): a counting walk over a copy of the state checks everything and sizes
+ * the outputs, a gathering walk copies the event arrays — and nothing else: images, IMU, index and connection data never
+ * cross PCIe — densely per camera into pinned scratch, one copy brings them to the device, and one kernel turns both
+ * cameras' 13-byte wire events into records, one per lane (KERNELS.md "ROS bags").
+ *
+ * Out of scope: bz2 / lz4 chunks, bag format 1.2, seeking by the index (the walk is sequential), sensor_msgs/Image
+ * payloads, prophesee_event_msgs and other event message types, the odometry topic, IMU inside the feed (the side call
+ * beside it is the way), announced batches, writing bags. */
+typedef struct esvio_fe_bag_topics {
+  const char* left;   /* dvs_msgs/EventArray, camera 0 */
+  const char* right;  /* dvs_msgs/EventArray, camera 1 */
+  const char* imu;    /* sensor_msgs/Imu */
+} esvio_fe_bag_topics;
+int esvio_fe_bag_set_topics(esvio_fe_handle h, const esvio_fe_bag_topics* topics);
+/* The magic and the bag header record (host only, no handle).  payload_offset = 13 once the magic is there (the walkers
+ * start at it and pass over the op 0x03 record themselves), version = 20; index_pos, conn_count, chunk_count from the
+ * record; complete == 1 once the n bytes hold the record's header and data_len, else the other fields past what was
+ * read are 0.  ESVIO_FE_EINVAL: null bytes with n > 0, null out, bytes that are no prefix of the magic, a first record
+ * that is malformed or not op 0x03. */
+typedef struct esvio_fe_bag_header_info {
+  uint64_t payload_offset, index_pos;
+  uint32_t conn_count, chunk_count;
+  int32_t version;  /* 20 once the magic is complete, else 0 */
+  int32_t complete;
+} esvio_fe_bag_header_info;
+int esvio_fe_bag_header(const void* bytes, size_t n, esvio_fe_bag_header_info* out);
+typedef struct esvio_fe_bag_message { /* one completed EventArray message */
+  int32_t cam;                   /* 0 left, 1 right */
+  uint32_t seq;                  /* header.seq */
+  uint32_t stamp_sec, stamp_nsec; /* header.stamp: what the node pairs left and right by */
+  uint32_t time_sec, time_nsec;  /* the record's `time` */
+  uint32_t height, width;
+  uint64_t first;                /* index of its first event in the camera's emitted stream since the last reset */
+  uint64_t count;                /* n */
+} esvio_fe_bag_message;
+typedef struct esvio_fe_bag_cam_info {
+  uint64_t events, bad, messages; /* emitted (too small a dst_cap: the number needed); BAD; messages completed */
+  uint32_t first_sec, first_nsec, last_sec, last_nsec; /* the first / last emitted event's stamp; untouched if none */
+} esvio_fe_bag_cam_info;
+typedef struct esvio_fe_bag_info {
+  esvio_fe_bag_cam_info cam[2];
+  uint64_t other_messages, other_records, chunks, connections;
+} esvio_fe_bag_info;
+typedef struct esvio_fe_bag_side_info {
+  uint64_t imu, bad; /* samples written (too small an imu_cap: the number needed); BAD samples */
+  uint64_t other_messages, other_records, chunks, connections;
+} esvio_fe_bag_side_info;
+/* the decode stage: the event walker advanced by the n_bytes at `bytes`; camera cam's records go to dst[cam] (room for
+ * dst_cap[cam]; dst_space for both: ESVIO_FE_DEVICE, 16-byte aligned, or ESVIO_FE_HOST), an esvio_fe_bag_message per
+ * completed event message, in stream order, to the HOST array msgs (room for msgs_cap).  More events than a dst_cap or
+ * more messages than msgs_cap: ESVIO_FE_EINVAL, info->cam[].events / .messages hold the exact numbers needed, nothing is
+ * stored in a dst that is too small, the state is as it was.  flags must be 0.  n_bytes == 0 succeeds and touches
+ * nothing; n_bytes <= 2^28.  info is optional.  Orders itself on the main stream, waits for its own result and touches
+ * nothing of the tracker, as esvio_fe_decode_aedat.  Its scratch — 13 pinned and 13 device bytes per event, the records
+ * behind a host dst — grows on first use and with esvio_fe_reserve for a handle that has decoded a bag before: a second
+ * call of a given size allocates nothing.  ESVIO_FE_EINVAL with a message, before any device work: unknown bits in
+ * flags, null bytes with n_bytes > 0, a null dst[cam] with dst_cap[cam] > 0, null msgs with msgs_cap > 0, a bad
+ * dst_space, a misaligned device dst, n_bytes > 2^28, a malformed stream.
+ * Tracking message pairs: pair left and right messages by header stamp and hand the slices dst[cam] + first .. + count
+ * to esvio_fe_track_event(..., ESVIO_FE_DEVICE, ...) with cur_time = the last left event's stamp, as the node does. */
+int esvio_fe_decode_bag(esvio_fe_handle h, const void* bytes, size_t n_bytes, uint32_t flags, esvio_fe_event* const dst[2],
+                        const size_t dst_cap[2], int dst_space, esvio_fe_bag_message* msgs, size_t msgs_cap,
+                        esvio_fe_bag_info* info);
+/* the side call: the side walker advanced by the same kind of chunk; the IMU samples, in stream order, to imu (HOST, room
+ * for imu_cap).  More than imu_cap, or a BAD sample: ESVIO_FE_EINVAL, info->imu / info->bad exact, the state as it was.
+ * Runs on the host alone; argument errors as above. */
+int esvio_fe_bag_side(esvio_fe_handle h, const void* bytes, size_t n_bytes, uint32_t flags, esvio_fe_imu_sample* imu,
+                      size_t imu_cap, esvio_fe_bag_side_info* info);
+
 /* ---- stream slicing: a record stream cut into fixed-rate windows, on the device ------------ */
 /* trackEvent takes one batch per camera and call; a recording or a sensor transfer is a long stream whose batch edges
  * are points in time.  The reference cuts its streams off line, dependences/events_repacking_helper/src/
@@ -1106,6 +1247,13 @@ int esvio_fe_feed_push_raw(esvio_fe_handle h, int cam, int format, const void* w
  * everything else is skipped; failures as esvio_fe_decode_aedat's, with nothing appended and the walker as it was */
 int esvio_fe_feed_push_aedat(esvio_fe_handle h, int cam, const void* bytes, size_t n_bytes, int64_t t_offset_ns, uint32_t flags,
                              esvio_fe_feed_info* info);
+/* a chunk of rosbag v2.0 bytes (host memory; it may end anywhere; the rule: "rosbag v2.0 recordings" above): the chunk's
+ * LEFT events are appended before its RIGHT events, whatever their order in the bytes, then each camera's slicer runs;
+ * info[cam] as the other push calls'.  The origin rule holds: a chunk that brings right events while no origin exists
+ * and no left event with them is ESVIO_FE_EINVAL, nothing appended, the walker as it was — push a longer chunk, or open
+ * the feed with an explicit origin.  Failures as esvio_fe_feed_push_aedat's, for both cameras together: nothing is
+ * appended to either, the walker is as it was.  Refused while batches are announced. */
+int esvio_fe_feed_push_bag(esvio_fe_handle h, const void* bytes, size_t n_bytes, uint32_t flags, esvio_fe_feed_info info[2]);
 int esvio_fe_feed_peek(esvio_fe_handle h, esvio_fe_feed_window* out);
 int esvio_fe_feed_track(esvio_fe_handle h, int pub_this_frame, const esvio_fe_motion* motion, esvio_fe_tracks* out,
                         esvio_fe_batch_info* info);

@@ -209,6 +209,20 @@ int esvio_fe_ingest_kernel_count(void);
 int esvio_fe_aedat_walk_tap(void* state, size_t state_bytes, const void* bytes, size_t n_bytes, uint32_t* runs, size_t runs_cap,
                             uint8_t* payload, size_t events_cap, uint64_t counts[4]);
 int esvio_fe_aedat_walk_state_bytes(void);
+/* the bag stage: events per tile of k_bag_emit, whose timer id is appended to the ingest range above */
+int esvio_fe_bag_tile_events(void);
+/* The bag host walk alone (esvio_amd/csrc/fe_bag.h), no handle and no device: a walker's state in and out (state_bytes ==
+ * esvio_fe_bag_walk_state_bytes(); all zero is the fresh state), the topics as esvio_fe_bag_set_topics takes them, side
+ * != 0 for the side walk, the n_bytes of a chunk in; out come each camera's gathered 13-byte wire events (at most
+ * events_cap[cam]), the message table (at most msgs_cap), the IMU samples (at most imu_cap) and counts = {left events,
+ * right events, left messages, right messages, messages, samples, BAD samples, other_messages, other_records, chunks,
+ * connections, 0}, counted whether stored or not.  Every output pointer may be null.  A malformed stream:
+ * ESVIO_FE_EINVAL, the state as it was, the broken rule as text in `why` (room for why_cap bytes; optional). */
+int esvio_fe_bag_walk_tap(void* state, size_t state_bytes, const esvio_fe_bag_topics* topics, int side, const void* bytes,
+                          size_t n_bytes, uint8_t* const payload[2], const size_t events_cap[2], esvio_fe_bag_message* msgs,
+                          size_t msgs_cap, esvio_fe_imu_sample* imu, size_t imu_cap, uint64_t counts[12], char* why,
+                          size_t why_cap);
+int esvio_fe_bag_walk_state_bytes(void);
 /* the events one workgroup of the slicing chain takes (esvio_fe_slice_events): where its tile edges lie */
 int esvio_fe_slice_tile_events(void);
 /* the hipStream_t the handle launches on (as void*) */
