@@ -239,6 +239,7 @@ int esvio_fe_create(const esvio_fe_config* cfg, esvio_fe_handle* out) {
   if (const char* v = getenv("ESVIO_FE_RAW_PINNED_COPY")) c->rawdec.pinned_copy = atoi(v) != 0 ? 1 : 0;
   if (const char* v = getenv("ESVIO_FE_AEDAT_WAVE_LOOKUP")) c->aedat.wave_lookup = atoi(v) != 0 ? 1 : 0;
   if (const char* v = getenv("ESVIO_FE_BAG_WAVE_LOADS")) c->bag.wave_loads = atoi(v) != 0 ? 1 : 0;
+  if (const char* v = getenv("ESVIO_FE_IMAGE_WAVE_LOADS")) c->bag.img_wave_loads = atoi(v) != 0 ? 1 : 0;
   c->select_one_wave = getenv("ESVIO_FE_SELECT_SERIAL") != nullptr;
   if (const char* v = getenv("ESVIO_FE_SAE_EV_MIN")) c->sae_ev_min = (size_t)strtoull(v, nullptr, 10);
   c->tiled = make_tile_geom(c->W, c->H, &c->tgeom) && getenv("ESVIO_FE_SAE_SORT") == nullptr;
@@ -397,7 +398,7 @@ int esvio_fe_reset(esvio_fe_handle c) {
   c->rawdec.st[0] = c->rawdec.st[1] = esvio_fe_ctx::Raw::State();  // the raw-stream decoder: the fresh state
   c->rawdec.trig_st[0] = c->rawdec.trig_st[1] = esvio_fe_ctx::Raw::State();  // ... and the trigger decoder's
   for (int cam = 0; cam < 2; cam++) c->aedat.ev_st[cam] = c->aedat.side_st[cam] = esvio::aedat::Walk{};  // ... and the AEDAT walkers'
-  c->bag.ev_st = c->bag.side_st = esvio::bag::Walk{};  // ... and the bag walkers' (the topics are settings: kept)
+  c->bag.ev_st = c->bag.side_st = c->bag.img_st = esvio::bag::Walk{};  // ... and the bag walkers' (the topics are settings: kept)
   c->slice.st[0] = c->slice.st[1] = esvio_fe_ctx::Slice::State();  // the stream slicer: no event seen, no window closed
   HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
   feed_empty(c, true);  // an open feed: no records, no windows (it stays open); every stream is idle here
@@ -2013,7 +2014,7 @@ int esvio_fe_decode_reset(esvio_fe_handle c) {
   c->rawdec.st[0] = c->rawdec.st[1] = esvio_fe_ctx::Raw::State();
   c->rawdec.trig_st[0] = c->rawdec.trig_st[1] = esvio_fe_ctx::Raw::State();
   for (int cam = 0; cam < 2; cam++) c->aedat.ev_st[cam] = c->aedat.side_st[cam] = esvio::aedat::Walk{};
-  c->bag.ev_st = c->bag.side_st = esvio::bag::Walk{};
+  c->bag.ev_st = c->bag.side_st = c->bag.img_st = esvio::bag::Walk{};
   return 0;
 }
 
@@ -2717,6 +2718,12 @@ int esvio_fe_bag_walk_tap(void* state, size_t state_bytes, const esvio_fe_bag_to
   return 0;
 }
 int esvio_fe_bag_walk_state_bytes(void) { return (int)sizeof(bg::Walk); }
+
+// (the rosbag image stage stands at the end of the file; esvio_fe_reserve sizes its scratch)
+namespace {
+size_t bag_image_slot(size_t payload_bytes);
+int bag_image_ensure(esvio_fe_ctx* c, size_t pix_bytes, size_t n_images, size_t gray_bytes);
+}  // namespace
 
 // ---- stream slicing: a record stream cut into fixed-rate windows (the rule: include/esvio_fe.h; the chain: fe_kernels.h)
 namespace {
@@ -3710,14 +3717,20 @@ int esvio_fe_select_candidates(esvio_fe_handle c, const uint32_t* xy, const int3
   return 0;
 }
 
-int esvio_fe_track_image(esvio_fe_handle c, double cur_time, const uint8_t* img_left,
-                         const uint8_t* img_right, int pub_this_frame, esvio_fe_tracks* out) {
+int esvio_fe_track_image_space(esvio_fe_handle c, double cur_time, const uint8_t* img_left, const uint8_t* img_right, int space,
+                               int pub_this_frame, esvio_fe_tracks* out) {
   if (!c || !img_left) return ESVIO_FE_EINVAL;
+  if (space != ESVIO_FE_HOST && space != ESVIO_FE_DEVICE) return fail(c, ESVIO_FE_EINVAL, "track_image_space: bad memory space");
   HIPCHK(c, hipSetDevice(c->dev));
   if (!c->announced.empty() || !c->inflight.empty())
     return fail(c, ESVIO_FE_EINVAL, "event batches are announced on this handle");
-  if (int rc = track_image_impl(c, cur_time, img_left, img_right, pub_this_frame != 0)) return rc;
+  if (int rc = track_image_impl(c, cur_time, img_left, img_right, pub_this_frame != 0, space)) return rc;
   return fill_tracks(c, out);
+}
+
+int esvio_fe_track_image(esvio_fe_handle c, double cur_time, const uint8_t* img_left,
+                         const uint8_t* img_right, int pub_this_frame, esvio_fe_tracks* out) {
+  return esvio_fe_track_image_space(c, cur_time, img_left, img_right, ESVIO_FE_HOST, pub_this_frame, out);
 }
 
 // The node's sensor_msgs/PointCloud packing (stereo_event_tracker_node.cpp:273-329) of the current
@@ -4067,6 +4080,9 @@ int esvio_fe_reserve(esvio_fe_handle c, size_t max_left, size_t max_right, int h
   // a handle that decodes bags: the scratch of a chunk of max_left and max_right events
   if (c->bag.used)
     if (int rc = bag_ensure(c, max_left, max_right)) return rc;
+  // a handle that decodes bag images: the scratch of one stereo pair of rgb8 frames of its size
+  if (c->bag.img_used)
+    if (int rc = bag_image_ensure(c, 2 * bag_image_slot((size_t)c->W * c->H * 3), 2, 2 * (size_t)c->W * c->H)) return rc;
   // a handle with an open feed: per camera both buffers for 2 * max_events records (the one that holds records is left alone)
   if (c->feed.open) {
     const size_t ev[2] = {max_left, max_right};
@@ -4187,5 +4203,180 @@ int esvio_fe_reset_kernel_stats(esvio_fe_handle c) {
   return 0;
 }
 void* esvio_fe_stream(esvio_fe_handle c) { return c ? (void*)cur_stream(c) : nullptr; }
+
+// ---- rosbag images (the rule: include/esvio_fe.h "rosbag images"; the host walk: fe_bag.h; the kernel: fe_kernels.h)
+namespace {
+size_t bag_image_slot(size_t payload_bytes) { return (payload_bytes + 15) & ~(size_t)15; }
+// the scratch of pix_bytes gathered payload bytes (padding included) and n_images descriptors, and gray_bytes behind a host dst
+int bag_image_ensure(esvio_fe_ctx* c, size_t pix_bytes, size_t n_images, size_t gray_bytes) {
+  esvio_fe_ctx::Bag& B = c->bag;
+  B.img_used = true;
+  const size_t bytes = bag_image_slot(pix_bytes) + 16 + n_images * sizeof(ImageDesc);  // (16: convert_image keeps its source's offset from a 16-byte boundary)
+  if (int rc = B.h_img.grow(c, bytes)) return rc;
+  if (int rc = B.d_img.grow(c, bytes)) return rc;
+  return gray_bytes ? B.d_gray.grow(c, gray_bytes) : 0;
+}
+// the copy of the gathered bytes and the table, and the launch, on the current stream; nothing is waited for
+int bag_image_enqueue(esvio_fe_ctx* c, size_t table_at, uint32_t n_images, uint32_t width, uint32_t height, uint64_t alg_bytes) {
+  esvio_fe_ctx::Bag& B = c->bag;
+  hipStream_t s = cur_stream(c);
+  HIPCHK(c, hipMemcpyAsync(B.d_img, B.h_img, table_at + n_images * sizeof(ImageDesc), hipMemcpyHostToDevice, s));
+  ImageArgs a{};
+  a.desc = (const ImageDesc*)(B.d_img.p + table_at), a.n_images = n_images, a.width = width, a.height = height;
+  a.wave_loads = (uint32_t)B.img_wave_loads;
+  ScopedKernel k(c, K_IMAGE_EMIT, alg_bytes);
+  launch_image_emit(s, a);
+  return 0;
+}
+}  // namespace
+
+int esvio_fe_image_tile_pixels(void) { return (int)kImageTile; }
+
+int esvio_fe_bag_set_image_topics(esvio_fe_handle c, const char* left, const char* right) {
+  if (!c) return ESVIO_FE_EINVAL;
+  const char* why = nullptr;
+  if (!bg::set_image_topics(left, right, &c->bag.topics, &why)) return fail(c, ESVIO_FE_EINVAL, "bag_set_image_topics: %s", why);
+  c->bag.img_st = bg::Walk{};
+  return 0;
+}
+
+int esvio_fe_decode_bag_images(esvio_fe_handle c, const void* bytes, size_t n_bytes, uint32_t flags, uint8_t* const dst[2],
+                               const size_t dst_cap[2], int dst_space, esvio_fe_bag_image* msgs, size_t msgs_cap,
+                               esvio_fe_bag_image_info* info) {
+  if (!c) return ESVIO_FE_EINVAL;
+  if (info) *info = esvio_fe_bag_image_info{};
+  const char* who = "decode_bag_images";
+  if (int rc = bag_args_check(c, who, bytes, n_bytes, flags)) return rc;
+  if (dst_space != ESVIO_FE_HOST && dst_space != ESVIO_FE_DEVICE) return fail(c, ESVIO_FE_EINVAL, "%s: bad memory space", who);
+  const size_t room[2] = {dst && dst_cap ? dst_cap[0] : 0, dst && dst_cap ? dst_cap[1] : 0};
+  for (int cam = 0; cam < 2; cam++)
+    if (room[cam] && !dst[cam]) return fail(c, ESVIO_FE_EINVAL, "%s: dst[%d] is null", who, cam);
+  if (msgs_cap && !msgs) return fail(c, ESVIO_FE_EINVAL, "%s: msgs is null", who);
+  if (!n_bytes) return 0;
+  esvio_fe_ctx::Bag& B = c->bag;
+  const uint32_t W = (uint32_t)c->W, H = (uint32_t)c->H;
+  const size_t wh = (size_t)W * H;
+  // the counting walk: everything in the chunk checked, the messages and their bytes counted, nothing stored or moved
+  bg::Out cnt;
+  cnt.want_w = W, cnt.want_h = H;
+  {
+    bg::Walk probe = B.img_st;
+    if (!bg::walk(&probe, B.topics, bg::kImages, (const uint8_t*)bytes, n_bytes, &cnt))
+      return fail(c, ESVIO_FE_EINVAL, "%s: malformed bag or refused message (%s); the walker's state is as it was", who, cnt.why);
+  }
+  const size_t n[2] = {(size_t)cnt.n_cam_imgs[0], (size_t)cnt.n_cam_imgs[1]};
+  if (info) {
+    for (int cam = 0; cam < 2; cam++) {
+      esvio_fe_bag_image_cam_info& ci = info->cam[cam];
+      ci.images = n[cam];
+      ci.first_sec = cnt.first_stamp[cam][0], ci.first_nsec = cnt.first_stamp[cam][1], ci.last_sec = cnt.last_stamp[cam][0], ci.last_nsec = cnt.last_stamp[cam][1];
+    }
+    info->other_messages = cnt.other_messages, info->other_records = cnt.other_records, info->chunks = cnt.chunks, info->connections = cnt.connections;
+  }
+  if (n[0] > room[0] || n[1] > room[1])
+    return fail(c, ESVIO_FE_EINVAL, "%s: the chunk completes %zu left and %zu right images, dst has room for %zu and %zu; the walker's state is as it was", who,
+                n[0], n[1], room[0], room[1]);
+  if (cnt.n_imgs > msgs_cap)
+    return fail(c, ESVIO_FE_EINVAL, "%s: the chunk completes %llu image messages, msgs has room for %zu; the walker's state is as it was", who,
+                (unsigned long long)cnt.n_imgs, msgs_cap);
+  const size_t n_all = (size_t)cnt.n_imgs, table_at = (size_t)cnt.n_pix_bytes;
+  if (n_all) {
+    HIPCHK(c, hipSetDevice(c->dev));
+    if (int rc = bag_image_ensure(c, table_at, n_all, dst_space == ESVIO_FE_HOST ? n_all * wh : 0)) return rc;
+  }
+  // the gathering walk (checked by the counting walk): the completed payloads into the pinned scratch, what the call's end
+  // cuts into the carry; the state it leaves is taken over at the end
+  bg::Out o;
+  o.want_w = W, o.want_h = H, o.carry = &B.carry;
+  o.pix = n_all ? B.h_img.p : nullptr, o.pix_cap = table_at, o.imgs = msgs, o.imgs_cap = msgs_cap;
+  bg::Walk st = B.img_st;
+  bg::walk(&st, B.topics, bg::kImages, (const uint8_t*)bytes, n_bytes, &o);
+  if (n_all) {
+    ImageDesc* desc = (ImageDesc*)(B.h_img.p + table_at);
+    size_t at = 0;
+    uint64_t alg = 0;
+    for (size_t k = 0; k < n_all; k++) {
+      const esvio_fe_bag_image& m = msgs[k];
+      uint8_t* base = dst_space == ESVIO_FE_HOST ? B.d_gray.p + (m.cam ? n[0] * wh : 0) : dst[m.cam];
+      desc[k] = ImageDesc{B.d_img.p + at, base + (size_t)m.index * wh, m.step, (uint32_t)m.encoding};
+      at += bag_image_slot((size_t)m.step * m.height);
+      alg += (uint64_t)wh * (bg::encoding_bpp(m.encoding) + 1);
+    }
+    if (int rc = bag_image_enqueue(c, table_at, (uint32_t)n_all, W, H, alg)) return rc;
+    if (dst_space == ESVIO_FE_HOST)
+      for (int cam = 0; cam < 2; cam++)
+        if (n[cam]) HIPCHK(c, hipMemcpyAsync(dst[cam], B.d_gray.p + (cam ? n[0] * wh : 0), n[cam] * wh, hipMemcpyDeviceToHost, cur_stream(c)));
+    HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+    if (c->prof_on) resolve_profile(c);
+  }
+  B.img_st = st;
+  return 0;
+}
+
+int esvio_fe_convert_image(esvio_fe_handle c, const void* src, int src_space, uint32_t height, uint32_t width, uint32_t step,
+                           int32_t encoding, uint8_t* dst, int dst_space) {
+  if (!c) return ESVIO_FE_EINVAL;
+  const char* who = "convert_image";
+  if (!src || !dst) return fail(c, ESVIO_FE_EINVAL, "%s: src or dst is null", who);
+  if ((src_space != ESVIO_FE_HOST && src_space != ESVIO_FE_DEVICE) || (dst_space != ESVIO_FE_HOST && dst_space != ESVIO_FE_DEVICE))
+    return fail(c, ESVIO_FE_EINVAL, "%s: bad memory space", who);
+  if (height < 1 || height > kImageMaxSide || width < 1 || width > kImageMaxSide)
+    return fail(c, ESVIO_FE_EINVAL, "%s: height and width must be 1 .. %u", who, kImageMaxSide);
+  if (encoding < bg::kEncMono || encoding > bg::kEncRgb) return fail(c, ESVIO_FE_EINVAL, "%s: encoding must be 1 (mono8, 8UC1), 2 (bgr8, 8UC3) or 3 (rgb8)", who);
+  const size_t row = (size_t)width * bg::encoding_bpp(encoding), wh = (size_t)width * height;
+  if (step < row) return fail(c, ESVIO_FE_EINVAL, "%s: step is below width * bytes per pixel", who);
+  const size_t need = (size_t)step * (height - 1) + row;  // the bytes up to the last row's last pixel
+  if (need > kRawMaxBytes) return fail(c, ESVIO_FE_EINVAL, "%s: a source holds at most 2^28 bytes", who);
+  esvio_fe_ctx::Bag& B = c->bag;
+  HIPCHK(c, hipSetDevice(c->dev));
+  const size_t lead = src_space == ESVIO_FE_HOST ? (size_t)((uintptr_t)src & 15) : 0;  // the copy lies as the source does
+  const size_t table_at = bag_image_slot(src_space == ESVIO_FE_HOST ? lead + need : 0);
+  if (int rc = bag_image_ensure(c, table_at, 1, dst_space == ESVIO_FE_HOST ? wh : 0)) return rc;
+  if (src_space == ESVIO_FE_HOST) memcpy(B.h_img.p + lead, src, need);
+  ImageDesc* desc = (ImageDesc*)(B.h_img.p + table_at);
+  desc[0] = ImageDesc{src_space == ESVIO_FE_HOST ? B.d_img.p + lead : (const uint8_t*)src, dst_space == ESVIO_FE_HOST ? B.d_gray.p : dst, step, (uint32_t)encoding};
+  if (int rc = bag_image_enqueue(c, table_at, 1, width, height, (uint64_t)wh * (bg::encoding_bpp(encoding) + 1))) return rc;
+  if (dst_space == ESVIO_FE_HOST) HIPCHK(c, hipMemcpyAsync(dst, B.d_gray.p, wh, hipMemcpyDeviceToHost, cur_stream(c)));
+  HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  if (c->prof_on) resolve_profile(c);
+  return 0;
+}
+
+// the image walk tap (include/esvio_fe_test.h): the host walk alone, no handle, no device
+int esvio_fe_bag_image_walk_tap(void* state, size_t state_bytes, const char* left, const char* right, uint32_t width, uint32_t height,
+                                const void* bytes, size_t n_bytes, uint8_t* carry, size_t carry_cap, uint8_t* pix, size_t pix_cap,
+                                esvio_fe_bag_image* imgs, size_t imgs_cap, uint64_t counts[12], char* why, size_t why_cap) {
+  if (why && why_cap) why[0] = 0;
+  if (!state || state_bytes != sizeof(bg::Walk) || (n_bytes && !bytes) || !counts) return ESVIO_FE_EINVAL;
+  bg::Topics t;
+  const char* bad_topics = nullptr;
+  if (!bg::set_image_topics(left, right, &t, &bad_topics)) return ESVIO_FE_EINVAL;
+  bg::Walk st;
+  memcpy(&st, state, sizeof st);
+  if (st.carry_len > carry_cap || (st.carry_len && !carry)) return ESVIO_FE_EINVAL;
+  bg::Carry cy;
+  if (st.carry_len) cy.buf[st.carry_buf & 1u].assign(carry, carry + st.carry_len);
+  bg::Out cnt, o;
+  cnt.want_w = o.want_w = width, cnt.want_h = o.want_h = height;
+  bg::Walk probe = st;
+  bool ok = bg::walk(&probe, t, bg::kImages, (const uint8_t*)bytes, n_bytes, &cnt);  // the counting walk, as the library's call does
+  if (ok) {
+    o.carry = &cy;
+    if (pix && cnt.n_pix_bytes <= pix_cap) o.pix = pix, o.pix_cap = pix_cap;
+    o.imgs = imgs, o.imgs_cap = imgs ? imgs_cap : 0;
+    bg::walk(&st, t, bg::kImages, (const uint8_t*)bytes, n_bytes, &o);
+    ok = st.carry_len <= carry_cap && (!st.carry_len || carry);
+  }
+  const uint64_t v[12] = {cnt.n_imgs, cnt.n_cam_imgs[0], cnt.n_cam_imgs[1], cnt.n_pix_bytes, cnt.other_messages, cnt.other_records,
+                          cnt.chunks, cnt.connections, ok ? st.carry_len : 0, 0, 0, 0};
+  memcpy(counts, v, sizeof v);
+  if (!ok) {  // (the caller's state and carry are as they were)
+    if (why && why_cap) snprintf(why, why_cap, "%s", cnt.why ? cnt.why : "carry_cap is too small for the bytes that wait");
+    return ESVIO_FE_EINVAL;
+  }
+  if (st.carry_len) memcpy(carry, cy.buf[st.carry_buf & 1u].data(), (size_t)st.carry_len);
+  memcpy(state, &st, sizeof st);
+  return 0;
+}
 
 }  // extern "C"

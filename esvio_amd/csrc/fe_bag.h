@@ -5,12 +5,16 @@
 // A bag is a chain of records, each of which says how long it is, so it is walked on the host.  The event walk gathers
 // the 13-byte wire events of the chunk's EventArray messages, and nothing else, densely per camera and lists the
 // messages it completes; the side walk decodes the Imu messages where they lie: they are few.  Whatever is cut by the
-// call's end — a length word, a header, a message's fixed part, an event — waits in the state.
+// call's end — a length word, a header, a message's fixed part, an event — waits in the state.  The image walk gathers the
+// pixel payloads of the sensor_msgs/Image messages of its two topics, each at a 16-byte boundary, and lists them; the
+// bytes of a payload that the call's end cuts wait in a carry buffer beside the state (Carry), which may be megabytes.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+
+#include <vector>
 
 #include "../../include/esvio_fe.h"
 
@@ -21,16 +25,35 @@ constexpr uint32_t kMagicBytes = 13, kMaxHeader = 4096, kMaxValue = 255, kMaxCon
 constexpr uint32_t kFieldKeep = 9 + kMaxValue;  // the bytes of a connection field that are looked at: "md5sum=" + a value, with room
 constexpr char kMagic[] = "#ROSBAG V2.0\n";
 constexpr char kEventType[] = "dvs_msgs/EventArray", kEventMd5[] = "5e8beee5a6c107e504c2e78903c224b8", kImuType[] = "sensor_msgs/Imu";
-enum Role { kNone = 0, kLeft = 1, kRight = 2, kImu = 3 };
+constexpr char kImageType[] = "sensor_msgs/Image";
+constexpr uint32_t kMaxEncoding = 32;  // bytes of an Image message's encoding string
+constexpr uint32_t kImageFixed = 37;   // an Image message without frame_id, encoding and data: 16 + 12 + 1 + 4 + 4
+enum Role { kNone = 0, kLeft = 1, kRight = 2, kImu = 3, kImgLeft = 4, kImgRight = 5 };
+enum EncodingClass { kEncNone = 0, kEncMono = 1, kEncBgr = 2, kEncRgb = 3 };  // esvio_fe_bag_image::encoding
+inline bool is_image_role(uint32_t role) { return role == kImgLeft || role == kImgRight; }
+inline uint32_t encoding_bpp(int cls) { return cls == kEncMono ? 1u : 3u; }
+// getImageFromMsg's accepted encodings (stereo_image_tracker_node.cpp:261-307) -> the class, kEncNone: every other string
+inline int encoding_class(const uint8_t* s, uint32_t n) {
+  const struct {
+    const char* name;
+    int cls;
+  } known[] = {{"mono8", kEncMono}, {"8UC1", kEncMono}, {"bgr8", kEncBgr}, {"8UC3", kEncBgr}, {"rgb8", kEncRgb}};
+  for (const auto& k : known)
+    if (n == strlen(k.name) && memcmp(s, k.name, n) == 0) return k.cls;
+  return kEncNone;
+}
 
-struct Topics {  // esvio_fe_bag_set_topics: role - 1 -> the topic (len 0: none)
-  uint32_t len[3] = {0, 0, 0};
-  char name[3][kMaxValue + 1] = {};
+// role - 1 -> the topic (len 0: none).  0..2: esvio_fe_bag_set_topics', read by the event and the side walk; 3..4:
+// esvio_fe_bag_set_image_topics', read by the image walk.
+struct Topics {
+  uint32_t len[5] = {0, 0, 0, 0, 0};
+  char name[5][kMaxValue + 1] = {};
 };
 
 // esvio_fe_bag_set_topics' check and copy; false: *why says which rule `in` breaks (null `in`: no topic has a role)
 inline bool set_topics(const esvio_fe_bag_topics* in, Topics* out, const char** why) {
   Topics t;
+  for (int r = 3; r < 5; r++) t.len[r] = out->len[r], memcpy(t.name[r], out->name[r], sizeof t.name[r]);  // (the image topics stay)
   const char* src[3] = {in ? in->left : nullptr, in ? in->right : nullptr, in ? in->imu : nullptr};
   for (int r = 0; r < 3; r++) {
     if (!src[r]) continue;
@@ -40,6 +63,26 @@ inline bool set_topics(const esvio_fe_bag_topics* in, Topics* out, const char** 
       if (t.len[q] == n && memcmp(t.name[q], src[r], n) == 0) return *why = "two roles name the same topic", false;
     t.len[r] = (uint32_t)n;
     memcpy(t.name[r], src[r], n);
+  }
+  *out = t;
+  return true;
+}
+// esvio_fe_bag_set_image_topics' check and copy: the same string rules, and no image topic may be one that has a role
+// from set_topics
+inline bool set_image_topics(const char* left, const char* right, Topics* out, const char** why) {
+  Topics t = *out;
+  const char* src[2] = {left, right};
+  for (int r = 0; r < 2; r++) {
+    t.len[3 + r] = 0;
+    memset(t.name[3 + r], 0, sizeof t.name[3 + r]);
+    if (!src[r]) continue;
+    const size_t n = strlen(src[r]);
+    if (n == 0 || n > kMaxValue) return *why = "a topic must hold 1 to 255 bytes", false;
+    for (int q = 0; q < 3 + r; q++)
+      if (t.len[q] == n && memcmp(t.name[q], src[r], n) == 0)
+        return *why = q < 3 ? "an image topic that has a role from esvio_fe_bag_set_topics" : "two roles name the same topic", false;
+    t.len[3 + r] = (uint32_t)n;
+    memcpy(t.name[3 + r], src[r], n);
   }
   *out = t;
   return true;
@@ -60,13 +103,17 @@ enum Phase {
   P_MEVENTS,   //       whole events where they lie
   P_MCARRY,    // C 13  an event the call's end cut
   P_MIMU,      // C 296 the Imu body
+  P_MIMHEAD,   // C 12  an Image message's height, width, Le
+  P_MIMENC,    // C     its encoding, is_bigendian, step, D: Le + 9 bytes
+  P_MIMDATA,   //       its pixel payload where it lies
 };
 
 struct Conn {
   uint32_t id, role;
 };
 
-// One walker's state (a handle has two: the event call's and the side call's).  All zero is the fresh state.
+// One walker's state (a handle has three: the event call's, the side call's and the image call's).  All zero is the
+// fresh state.
 struct Walk {
   uint32_t phase, need, have;
   uint64_t left;        // S phases: bytes still to pass over
@@ -79,6 +126,9 @@ struct Walk {
   uint32_t seq, st_sec, st_nsec, height, width;  // the open message
   uint64_t data_len, frame_len, ev_left, msg_first, msg_count;
   uint64_t emitted[2];  // events emitted per camera since the last reset
+  uint32_t step, enc, bigendian;  // the open Image message (its payload bytes still to come: ev_left)
+  uint32_t carry_buf;             // ... which of the Carry's two buffers holds its bytes so far
+  uint64_t carry_len;             // ... and how many they are
   uint32_t n_conn;
   Conn conns[kMaxConns];
   uint8_t buf[kMaxHeader];
@@ -87,7 +137,15 @@ struct Walk {
 inline uint32_t rd_u32(const uint8_t* p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
 inline uint64_t rd_u64(const uint8_t* p) { return (uint64_t)rd_u32(p) | (uint64_t)rd_u32(p + 4) << 32; }
 
-enum Mode { kEvents = 0, kSide = 1 };
+enum Mode { kEvents = 0, kSide = 1, kImages = 2 };
+
+// The bytes of an Image payload that a call's end cut, beside the image walker's state (Walk::carry_buf, carry_len say
+// which buffer and how much of it counts).  Two buffers: a call whose first message was waiting in one puts what it
+// leaves waiting into the other, so a call that fails after its gathering walk has overwritten nothing of the state it
+// goes back to.  A payload still open at the call's end grows in place, behind the bytes that count.
+struct Carry {
+  std::vector<uint8_t> buf[2];
+};
 
 // What one walk call produces.  Pointers may be null: the walk then counts only.
 struct Out {
@@ -101,7 +159,16 @@ struct Out {
   esvio_fe_imu_sample* imu = nullptr;
   size_t imu_cap = 0;
   uint64_t n_imu = 0, bad = 0;
-  // both
+  // the image walk: want_w x want_h the only size taken (0: any); pix null: counted only; carry null: nothing waits
+  uint32_t want_w = 0, want_h = 0;
+  Carry* carry = nullptr;
+  uint8_t* pix = nullptr;  // room for pix_cap bytes: the completed messages' payloads, each from a 16-byte boundary
+  size_t pix_cap = 0;
+  esvio_fe_bag_image* imgs = nullptr;
+  size_t imgs_cap = 0;
+  uint64_t n_pix_bytes = 0, n_imgs = 0, n_cam_imgs[2] = {0, 0};  // counted whether stored or not
+  uint32_t first_stamp[2][2] = {}, last_stamp[2][2] = {};        // per camera (sec, nsec) of its first / last completed message
+  // all
   uint64_t other_messages = 0, other_records = 0, chunks = 0, connections = 0;
   const char* why = nullptr;  // a malformed stream: which rule it breaks
   char why_buf[400];
@@ -174,8 +241,8 @@ inline bool bag_header_fields(const Header& h, const char** why) {
   return true;
 }
 
-inline uint32_t topic_role(const Topics& t, const uint8_t* topic, uint32_t n) {
-  for (uint32_t r = 0; r < 3; r++)
+inline uint32_t topic_role(const Topics& t, Mode mode, const uint8_t* topic, uint32_t n) {
+  for (uint32_t r = mode == kImages ? 3 : 0; r < (mode == kImages ? 5u : 3u); r++)
     if (t.len[r] && t.len[r] == n && memcmp(t.name[r], topic, n) == 0) return r + 1;
   return kNone;
 }
@@ -231,6 +298,8 @@ inline bool open_record(Walk* w, const Topics& topics, Mode mode, Out* out) {
         skip(w, P_SKIP, dl);
         return true;
       }
+      if (is_image_role(w->role) && dl < kImageFixed + 1)
+        return malformed_topic(out, "an Image message whose data_len is not 37 + L + Le + D", topics, w->role);
       if (dl < (w->role == kImu ? 16 + kImuBody : 28))
         return malformed_topic(out, w->role == kImu ? "an Imu message whose data_len is not 16 + L + 296" : "an EventArray message whose data_len is not 28 + L + 13 n", topics, w->role);
       collect(w, P_MHEAD, 16);
@@ -257,8 +326,9 @@ inline bool close_conn(Walk* w, const Topics& topics, Out* out) {
   const int k = find_conn(*w, w->conn);
   if (k >= 0 && w->conns[k].role != w->role) return malformed(out, "a repeated conn id with another topic");
   if (w->role != kNone) {
-    if (!w->c_type) return malformed_topic(out, w->role == kImu ? "a connection whose type is not sensor_msgs/Imu" : "a connection whose type is not dvs_msgs/EventArray", topics, w->role);
-    if (w->role != kImu && !w->c_md5) return malformed_topic(out, "a connection whose md5sum is not dvs_msgs/EventArray's (5e8beee5a6c107e504c2e78903c224b8)", topics, w->role);
+    if (!w->c_type)
+      return malformed_topic(out, is_image_role(w->role) ? "a connection whose type is not sensor_msgs/Image" : w->role == kImu ? "a connection whose type is not sensor_msgs/Imu" : "a connection whose type is not dvs_msgs/EventArray", topics, w->role);
+    if ((w->role == kLeft || w->role == kRight) && !w->c_md5) return malformed_topic(out, "a connection whose md5sum is not dvs_msgs/EventArray's (5e8beee5a6c107e504c2e78903c224b8)", topics, w->role);
     if (k < 0) {
       if (w->n_conn == kMaxConns) return malformed(out, "more than 64 connections with a role");
       w->conns[w->n_conn++] = Conn{w->conn, w->role};
@@ -279,6 +349,41 @@ inline void close_message(Walk* w, Mode mode, Out* out) {
     }
     out->n_msgs++, out->n_cam_msgs[cam]++;
   }
+}
+
+// `take` bytes of the open Image message's payload at p.  The message's last ones: the payload, the waiting bytes in
+// front, goes to out->pix at the next 16-byte boundary and the message is listed.  Else the call ends inside it: they wait.
+inline void take_pixels(Walk* w, const uint8_t* p, uint64_t take, uint32_t start_buf, Out* out) {
+  if (take < w->ev_left) {
+    if (w->carry_len == 0) w->carry_buf = start_buf ^ 1u;  // (never the buffer the call's first message waited in)
+    if (out->carry) {
+      std::vector<uint8_t>& b = out->carry->buf[w->carry_buf];
+      if (b.size() < w->carry_len + take) b.resize((size_t)(w->carry_len + take));
+      memcpy(b.data() + w->carry_len, p, (size_t)take);
+    }
+    w->carry_len += take, w->ev_left -= take;
+    return;
+  }
+  const int cam = (int)w->role - (int)kImgLeft;
+  const uint64_t total = w->carry_len + take;
+  if (out->pix && out->carry && out->n_pix_bytes + total <= out->pix_cap) {
+    if (w->carry_len) memcpy(out->pix + out->n_pix_bytes, out->carry->buf[w->carry_buf].data(), (size_t)w->carry_len);
+    memcpy(out->pix + out->n_pix_bytes + w->carry_len, p, (size_t)take);
+  }
+  out->n_pix_bytes += (total + 15) & ~(uint64_t)15;
+  if (out->imgs && out->n_imgs < out->imgs_cap) {
+    // the row as its 14 words, so that the padding word in front of `index` is 0 too: a row is compared byte for byte
+    static_assert(sizeof(esvio_fe_bag_image) == 56 && offsetof(esvio_fe_bag_image, is_bigendian) == 40 && offsetof(esvio_fe_bag_image, index) == 48,
+                  "esvio_fe_bag_image layout");
+    const uint64_t index = out->n_cam_imgs[cam];
+    const uint32_t row[14] = {(uint32_t)cam, w->seq, w->st_sec, w->st_nsec, w->t_sec, w->t_nsec, w->height, w->width, w->step, w->enc, w->bigendian, 0u,
+                              (uint32_t)index, (uint32_t)(index >> 32)};
+    memcpy(&out->imgs[out->n_imgs], row, sizeof row);
+  }
+  if (out->n_cam_imgs[cam] == 0) out->first_stamp[cam][0] = w->st_sec, out->first_stamp[cam][1] = w->st_nsec;
+  out->last_stamp[cam][0] = w->st_sec, out->last_stamp[cam][1] = w->st_nsec;
+  out->n_imgs++, out->n_cam_imgs[cam]++;
+  w->carry_len = 0, w->ev_left = 0;
 }
 
 // `count` whole wire events of the open message at p
@@ -318,7 +423,7 @@ inline bool collected(Walk* w, const Topics& topics, Mode mode, Out* out) {
       if (h.op == 7) {
         if (!h.has_conn || !h.has_topic) return malformed(out, "a connection record without conn (4 bytes) or topic");
         if (h.topic_len > kMaxValue) return malformed(out, "a topic longer than 255 bytes");
-        w->role = topic_role(topics, h.topic, h.topic_len);
+        w->role = topic_role(topics, mode, h.topic, h.topic_len);
       }
       if (h.op == 2 && (!h.has_conn || !h.has_time)) return malformed(out, "a message record without conn (4 bytes) or time (8 bytes)");
       collect(w, P_DLEN, 4);
@@ -341,9 +446,9 @@ inline bool collected(Walk* w, const Topics& topics, Mode mode, Out* out) {
       const uint8_t* v;
       uint32_t vn;
       if (w->role != kNone && field_is(b, w->need, "type", &v, &vn)) {
-        const char* want = w->role == kImu ? kImuType : kEventType;
+        const char* want = is_image_role(w->role) ? kImageType : w->role == kImu ? kImuType : kEventType;
         w->c_type = w->cf_rest == 0 && vn == strlen(want) && memcmp(v, want, vn) == 0;
-      } else if (w->role != kNone && field_is(b, w->need, "md5sum", &v, &vn)) {
+      } else if ((w->role == kLeft || w->role == kRight) && field_is(b, w->need, "md5sum", &v, &vn)) {
         w->c_md5 = w->cf_rest == 0 && vn == strlen(kEventMd5) && memcmp(v, kEventMd5, vn) == 0;
       }
       skip(w, P_CFSKIP, w->cf_rest);
@@ -351,7 +456,9 @@ inline bool collected(Walk* w, const Topics& topics, Mode mode, Out* out) {
     }
     case P_MHEAD: {
       w->seq = rd_u32(b), w->st_sec = rd_u32(b + 4), w->st_nsec = rd_u32(b + 8), w->frame_len = rd_u32(b + 12);
-      if (w->role == kImu) {
+      if (is_image_role(w->role)) {
+        if (w->frame_len > w->data_len - (kImageFixed + 1)) return malformed_topic(out, "an Image message whose data_len is not 37 + L + Le + D", topics, w->role);
+      } else if (w->role == kImu) {
         if (w->data_len != 16 + w->frame_len + kImuBody) return malformed_topic(out, "an Imu message whose data_len is not 16 + L + 296", topics, w->role);
       } else if (w->frame_len > w->data_len - 28) {
         return malformed_topic(out, "an EventArray message whose data_len is not 28 + L + 13 n", topics, w->role);
@@ -365,6 +472,40 @@ inline bool collected(Walk* w, const Topics& topics, Mode mode, Out* out) {
       if (w->data_len != 28 + w->frame_len + kEventBytes * n) return malformed_topic(out, "an EventArray message whose data_len is not 28 + L + 13 n", topics, w->role);
       w->ev_left = w->msg_count = n, w->msg_first = w->emitted[w->role - 1];
       w->phase = P_MEVENTS;
+      return true;
+    }
+    case P_MIMHEAD: {
+      w->height = rd_u32(b), w->width = rd_u32(b + 4);
+      const uint32_t le = rd_u32(b + 8);
+      if (le > kMaxEncoding) return malformed_topic(out, "an Image message whose encoding is longer than 32 bytes", topics, w->role);
+      if (le > w->data_len - (kImageFixed + 1) - w->frame_len) return malformed_topic(out, "an Image message whose data_len is not 37 + L + Le + D", topics, w->role);
+      if (w->height == 0 || w->width == 0) return malformed_topic(out, "an Image message with height or width 0", topics, w->role);
+      collect(w, P_MIMENC, le + 9);
+      return true;
+    }
+    case P_MIMENC: {
+      const uint32_t le = w->need - 9;
+      w->bigendian = b[le], w->step = rd_u32(b + le + 1);
+      const uint64_t d = rd_u32(b + le + 5);
+      if (d != (uint64_t)w->step * w->height) return malformed_topic(out, "an Image message whose data length is not step * height", topics, w->role);
+      if (w->data_len != kImageFixed + w->frame_len + le + d) return malformed_topic(out, "an Image message whose data_len is not 37 + L + Le + D", topics, w->role);
+      w->enc = (uint32_t)encoding_class(b, le);
+      if (w->enc == kEncNone) {
+        char name[kMaxEncoding + 1];
+        for (uint32_t k = 0; k < le; k++) name[k] = b[k] >= 0x20 && b[k] < 0x7f ? (char)b[k] : '?';
+        name[le] = 0;
+        snprintf(out->why_buf, sizeof out->why_buf, "an Image message with encoding \"%s\" on topic %s: mono8, 8UC1, bgr8, 8UC3 and rgb8 are taken", name,
+                 topics.name[w->role - 1]);
+        return out->why = out->why_buf, false;
+      }
+      if (w->step < (uint64_t)w->width * encoding_bpp((int)w->enc)) return malformed_topic(out, "an Image message whose step is below width * bytes per pixel", topics, w->role);
+      if (out->want_w && (w->width != out->want_w || w->height != out->want_h)) {
+        snprintf(out->why_buf, sizeof out->why_buf, "an Image message of %u x %u on topic %s, the handle's size is %u x %u: cv::resize is out of scope",
+                 w->width, w->height, topics.name[w->role - 1], out->want_w, out->want_h);
+        return out->why = out->why_buf, false;
+      }
+      w->ev_left = d, w->carry_len = 0;
+      w->phase = P_MIMDATA;
       return true;
     }
     case P_MCARRY:
@@ -404,7 +545,9 @@ inline bool skipped(Walk* w, const Topics& topics, Mode mode, Out* out) {
       collect(w, P_CFLEN, 4);
       return true;
     case P_MFRAME:
-      if (w->role == kImu) {
+      if (is_image_role(w->role)) {
+        collect(w, P_MIMHEAD, 12);
+      } else if (w->role == kImu) {
         if (mode == kSide)
           collect(w, P_MIMU, kImuBody);
         else
@@ -426,6 +569,7 @@ inline void consumed(Walk* w, uint64_t n) {
 // works on a copy of the state and takes it over when the whole call succeeds.  Reads bytes[0 .. n) and nothing else.
 inline bool walk(Walk* w, const Topics& topics, Mode mode, const uint8_t* bytes, size_t n, Out* out) {
   size_t pos = 0;
+  const uint32_t start_buf = w->carry_len ? w->carry_buf : w->carry_buf ^ 1u;  // the Carry buffer whose bytes count at the call's start
   if (w->phase == P_HLEN && w->need == 0) w->need = 4;  // the fresh state
   for (;;) {
     switch (w->phase) {
@@ -457,6 +601,16 @@ inline bool walk(Walk* w, const Topics& topics, Mode mode, const uint8_t* bytes,
         } else {
           collect(w, P_MCARRY, kEventBytes);  // fewer bytes than an event: they wait
         }
+        break;
+      }
+      case P_MIMDATA: {
+        if (pos == n) return true;
+        const uint64_t take = w->ev_left < n - pos ? w->ev_left : n - pos;
+        take_pixels(w, bytes + pos, take, start_buf, out);
+        pos += (size_t)take;
+        consumed(w, take);
+        if (w->ev_left) return true;
+        if (!next_record(w, out)) return false;
         break;
       }
       default: {  // the collect phases

@@ -76,7 +76,7 @@ const char* const kKernelNames[K_COUNT] = {
     "k_raw_emit", "k_slice_reduce", "k_slice_scan", "k_slice_cuts", "k_baf_keys_addr", "k_hot_count", "k_hot_keys",
     "k_hot_pick", "k_trig_reduce", "k_trig_emit"};
 // the ingest range behind the stage table (IngestKernelId, fe_kernels.h): esvio_fe_ingest_kernel_count()
-const char* const kIngestKernelNames[K_INGEST_COUNT - K_COUNT] = {"k_aedat_count", "k_aedat_scan", "k_aedat_emit", "k_bag_emit"};
+const char* const kIngestKernelNames[K_INGEST_COUNT - K_COUNT] = {"k_aedat_count", "k_aedat_scan", "k_aedat_emit", "k_bag_emit", "k_image_emit"};
 
 // The host phases of one trackEvent call, in the order of esvio_fe_latency_call::phase_ms; kPhaseNames is what
 // esvio_fe_latency_phase_name returns and what the ESVIO_FE_TRACE summary prints.  The PH_PUB_* phases are parts of
@@ -576,6 +576,17 @@ struct esvio_fe_ctx {
     DevBuf<BagResult> res;
     bool used = false;   // esvio_fe_reserve grows the scratch of a handle that has decoded a bag before
     int wave_loads = 0;  // ESVIO_FE_BAG_WAVE_LOADS=1 / 0: k_bag_emit's wave-cooperative dwordx4 loads through LDS / per-lane loads (the A/B in KERNELS.md)
+    // esvio_fe_decode_bag_images / esvio_fe_convert_image.  img_st: the third walker state, carry the bytes of the payload
+    // a call's end cut (fe_bag.h: Carry), both on the HOST and taken over as the others are.  The stage's own, main
+    // stream only, allocated on first use: h_img, the pinned scratch the walk gathers the payloads into, each from a
+    // 16-byte boundary, the descriptor table behind them; d_img its device copy (one transfer); d_gray the images behind
+    // a host dst.
+    esvio::bag::Walk img_st = {};
+    esvio::bag::Carry carry;
+    PinBuf<uint8_t> h_img;
+    DevBuf<uint8_t> d_img, d_gray;
+    bool img_used = false;    // esvio_fe_reserve grows the scratch of a handle that has decoded images before
+    int img_wave_loads = 0;   // ESVIO_FE_IMAGE_WAVE_LOADS=1 / 0: k_image_emit's wave-cooperative dwordx4 loads through LDS / per-lane loads (the A/B in KERNELS.md)
   } bag;
 
   // ---- esvio_fe_slice_events: a record stream cut into fixed-rate windows (include/esvio_fe.h has the rule,

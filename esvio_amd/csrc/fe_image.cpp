@@ -233,7 +233,7 @@ void image_set_mask(esvio_fe_ctx* c) {
 // node's CLAHE (stereo_image_tracker_node.cpp:92-96, no normalisation) to both images first.
 // No pipelining here: one frame at a time on the main stream.
 int track_image_impl(esvio_fe_ctx* c, double _cur_time, const uint8_t* img_left,
-                     const uint8_t* img_right, bool PUB_THIS_FRAME) {
+                     const uint8_t* img_right, bool PUB_THIS_FRAME, int space) {
   const esvio_fe_config& cfg = c->cfg;
   const int M = cfg.max_cnt;
   if (int rc = finalize_lazy(c)) return rc;  // (a lazy trackEvent call came before)
@@ -248,15 +248,15 @@ int track_image_impl(esvio_fe_ctx* c, double _cur_time, const uint8_t* img_left,
   if (cfg.equalize) {
     const PyrDesc& rl = c->raw[c->raw_cur][0].d;
     const PyrDesc& rr = c->raw[c->raw_cur][1].d;
-    if (int rc = copy_level0_in(c, rl, img_left)) return rc;
+    if (int rc = copy_level0_in(c, rl, img_left, space)) return rc;
     if (have_right)
-      if (int rc = copy_level0_in(c, rr, img_right)) return rc;
+      if (int rc = copy_level0_in(c, rr, img_right, space)) return rc;
     run_clahe(c, px00(rl), have_right ? px00(rr) : px00(rl), rl.stride[0], px00(L), have_right ? px00(R) : px00(L),
               L.stride[0], have_right ? 2 : 1, 2, 0);
   } else {
-    if (int rc = copy_level0_in(c, L, img_left)) return rc;
+    if (int rc = copy_level0_in(c, L, img_left, space)) return rc;
     if (have_right)
-      if (int rc = copy_level0_in(c, R, img_right)) return rc;
+      if (int rc = copy_level0_in(c, R, img_right, space)) return rc;
   }
   {
     PyrDesc two[2] = {L, R};

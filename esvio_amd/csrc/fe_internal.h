@@ -76,7 +76,7 @@ LkPair lk_pair(const PyrDesc& P, const PyrDesc& N, const P2f* src, const int* n_
                const LkOut& out);
 void run_lk_pair(esvio_fe_ctx* c, const LkPair& p);
 int copy_level0_out(esvio_fe_ctx* c, const PyrDesc& d, uint8_t* out);
-int copy_level0_in(esvio_fe_ctx* c, const PyrDesc& d, const uint8_t* in);
+int copy_level0_in(esvio_fe_ctx* c, const PyrDesc& d, const uint8_t* in, int space = ESVIO_FE_HOST);  // (where `in` lies)
 bool in_border_event(const esvio_fe_ctx* c, const P2f& pt);
 double pt_distance(const P2f& a, const P2f& b);
 void event_set_mask(esvio_fe_ctx* c);
@@ -164,7 +164,7 @@ int fast_cand_pass(esvio_fe_ctx* c, const uint8_t* img, int stride, int barrier,
                    const esvio_fe_ctx::FastCand& fc, bool want_count);
 int run_fast_cand(esvio_fe_ctx* c, const PyrDesc& ts, int set);  // ... of a frame's raw left time surface -> cand[set]
 int track_image_impl(esvio_fe_ctx* c, double cur_time, const uint8_t* img_left, const uint8_t* img_right,
-                     bool PUB_THIS_FRAME);
+                     bool PUB_THIS_FRAME, int space = ESVIO_FE_HOST);  // (where both images lie)
 
 }  // namespace fe
 }  // namespace esvio

@@ -707,7 +707,7 @@ void launch_trig_emit(hipStream_t s, const RawArgs& a);
 // tiles share each grid, as in the raw chain; no launch waits on the device for another workgroup.
 // The timer slots of these kernels are a range of their own behind K_COUNT (esvio_fe_ingest_kernel_count()): the stage
 // table, whose end a test pins, stays as it is.
-enum IngestKernelId { K_AEDAT_COUNT = K_COUNT, K_AEDAT_SCAN, K_AEDAT_EMIT, K_BAG_EMIT, K_INGEST_COUNT };
+enum IngestKernelId { K_AEDAT_COUNT = K_COUNT, K_AEDAT_SCAN, K_AEDAT_EMIT, K_BAG_EMIT, K_IMAGE_EMIT, K_INGEST_COUNT };
 constexpr uint32_t kAedatTile = 1024;  // records per workgroup: 1024 lanes, one record each
 struct AedatRun {                      // (fe_aedat.h: esvio::aedat::Run)
   uint32_t first;
@@ -770,6 +770,35 @@ struct BagArgs {
   uint32_t wave_loads; // 0: per-lane loads; 1: wave-cooperative dwordx4 loads through LDS
 };
 void launch_bag_emit(hipStream_t s, const BagArgs& a);
+
+// ---- rosbag images: sensor_msgs/Image payloads -> dense 8-bit gray (esvio_fe_decode_bag_images, esvio_fe_convert_image) ----
+// include/esvio_fe.h holds the rule.  The host has walked the records (fe_bag.h): what arrives here is a table of image
+// descriptors — where the payload's first row lies, its row stride, its encoding class, where the dense width x height
+// gray image goes — and one launch, k_image_emit, writes all of them: grid.y is the image, a lane writes ONE ALIGNED DWORD
+// of the destination, four consecutive pixels of the dense image counted from the dword boundary at or below dst (dst may
+// lie at any byte: 346 x 260 images side by side do not keep 16-byte boundaries, 5 x 1 ones not even dword boundaries);
+// the dwords the image's ends share with its neighbours, and groups that span two rows, go pixel by pixel.  The source
+// bytes of a group are 4 or 12 consecutive bytes at ANY alignment (step may be odd).  Two forms of the load (KERNELS.md
+// "ROS bag images" has the measurement): per lane, the byte assembly of ld_any; or per wave, whose 256 pixels — where
+// they lie in one row — are 256 or 768 consecutive bytes, loaded as the <= 50 aligned dwordx4 that overlap them (each
+// holds at least one byte of the row, so none leaves the pages the payload lies in) into LDS, from which a lane cuts its
+// bytes with two or four dword reads and a funnel shift.  K_IMAGE_EMIT is appended to the ingest range.
+constexpr uint32_t kImageTile = 1024;  // pixels per workgroup: 256 lanes, one destination dword each
+constexpr uint32_t kImageMaxSide = 8192;
+struct ImageDesc {
+  const uint8_t* src;  // the payload's first byte, device memory, any alignment
+  uint8_t* dst;        // [width * height], device memory, any alignment
+  uint32_t step;       // bytes between rows, >= width * bpp
+  uint32_t cls;        // 1: the byte; 2: (B, G, R) -> gray; 3: (R, G, B) -> gray
+};
+static_assert(sizeof(ImageDesc) == 24, "ImageDesc layout");
+struct ImageArgs {
+  const ImageDesc* desc;  // [n_images] device memory
+  uint32_t n_images;
+  uint32_t width, height;  // of every image of the launch; width * height <= 2^26
+  uint32_t wave_loads;     // 0: per-lane loads; 1: wave-cooperative dwordx4 loads through LDS where a wave's pixels lie in one row
+};
+void launch_image_emit(hipStream_t s, const ImageArgs& a);
 
 // ---- stream slicing: a record stream cut into fixed-rate windows (esvio_fe_slice_events) ----
 // include/esvio_fe.h holds the rule.  An event's window is m_i = max(m_{i-1}, c_i), c_i = the boundaries at or below its

@@ -5823,4 +5823,90 @@ KernelId launch_select(hipStream_t s, const SelectArgs& a, size_t lds_bytes) {
   return K_SELECT;
 }
 
+// ============================================================================ rosbag images
+// sensor_msgs/Image payloads -> dense gray images (fe_kernels.h has the lay-out of the work and the two forms of the
+// load, include/esvio_fe.h the rule).
+__device__ __forceinline__ uint32_t image_gray(uint32_t r, uint32_t g, uint32_t b) {
+  return (r * 9798u + g * 19235u + b * 3735u + (1u << 14)) >> 15;
+}
+// the gray of the pixel whose three bytes are the low 24 bits of v
+__device__ __forceinline__ uint32_t image_gray3(uint32_t v, uint32_t cls) {
+  const uint32_t b0 = v & 0xffu, b1 = (v >> 8) & 0xffu, b2 = (v >> 16) & 0xffu;
+  return cls == 2u ? image_gray(b2, b1, b0) : image_gray(b0, b1, b2);
+}
+// four pixels' gray bytes from their 12 source bytes q0 q1 q2
+__device__ __forceinline__ uint32_t image_gray4(uint32_t q0, uint32_t q1, uint32_t q2, uint32_t cls) {
+  return image_gray3(q0, cls) | image_gray3(q0 >> 24 | q1 << 8, cls) << 8 | image_gray3(q1 >> 16 | q2 << 16, cls) << 16 |
+         image_gray3(q2 >> 8, cls) << 24;
+}
+__device__ __forceinline__ uint32_t image_funnel(uint32_t lo, uint32_t hi, uint32_t sh) {
+  return (uint32_t)((((uint64_t)hi << 32) | lo) >> sh);
+}
+
+__global__ __launch_bounds__(256) void k_image_emit(ImageArgs a, uint32_t first_image) {
+  __shared__ uint4 stage[4 * 64];  // per wave 64 dwordx4, of which its span fills 50 at the most
+  const ImageDesc d = a.desc[first_image + blockIdx.y];
+  const int W = (int)a.width, N = (int)(a.width * a.height);
+  const uint32_t bpp = d.cls == 1u ? 1u : 3u;
+  const int shift = (int)((uintptr_t)d.dst & 3u);
+  const uint32_t wave = threadIdx.x >> 6, lane = lane_id();
+  const int p0 = (int)((blockIdx.x * 256u + threadIdx.x) * 4u) - shift;  // the lane's first pixel in the dense image (< 0: in front of it)
+  bool staged = false;
+  uint32_t off = 0;
+  if (a.wave_loads) {
+    const int w0 = (int)((blockIdx.x * 256u + wave * 64u) * 4u) - shift, w1 = w0 + 255;  // the wave's first and last pixel
+    if (w0 >= 0 && w1 < N) {
+      const int row = w0 / W;
+      if (w1 / W == row) {
+        const uint8_t* s0 = d.src + (size_t)row * d.step + (size_t)(w0 - row * W) * bpp;
+        off = (uint32_t)((uintptr_t)s0 & 15u);
+        const uint32_t n_vec = (off + 256u * bpp + 15u) >> 4;  // the dwordx4 that overlap the span
+        if (lane < n_vec) stage[wave * 64u + lane] = ((const uint4*)(s0 - off))[lane];
+        staged = true;
+      }
+    }
+    __syncthreads();
+  }
+  if (p0 >= N) return;
+  if (staged) {
+    const uint32_t* lw = (const uint32_t*)stage + wave * 256u;
+    const uint32_t o = off + lane * 4u * bpp, k = o >> 2, sh = (o & 3u) * 8u;
+    uint32_t v;
+    if (bpp == 1u) {
+      v = image_funnel(lw[k], lw[k + 1], sh);  // (k + 1 <= 67)
+    } else {
+      const uint32_t x0 = lw[k], x1 = lw[k + 1], x2 = lw[k + 2], x3 = lw[k + 3];  // (k + 3 <= 195)
+      v = image_gray4(image_funnel(x0, x1, sh), image_funnel(x1, x2, sh), image_funnel(x2, x3, sh), d.cls);
+    }
+    *(uint32_t*)(d.dst + p0) = v;
+    return;
+  }
+  const int row = p0 >= 0 ? p0 / W : 0;
+  if (p0 >= 0 && p0 + 3 < N && (p0 + 3) / W == row) {  // a whole dword of one row
+    const uint8_t* sp = d.src + (size_t)row * d.step + (size_t)(p0 - row * W) * bpp;
+    uint32_t v;
+    if (bpp == 1u)
+      v = ld_any<uint32_t>(sp);
+    else
+      v = image_gray4(ld_any<uint32_t>(sp), ld_any<uint32_t>(sp + 4), ld_any<uint32_t>(sp + 8), d.cls);
+    *(uint32_t*)(d.dst + p0) = v;
+    return;
+  }
+  for (int j = 0; j < 4; j++) {  // the image's ends, and a group that spans two rows: pixel by pixel
+    const int p = p0 + j;
+    if (p < 0 || p >= N) continue;
+    const int r = p / W;
+    const uint8_t* sp = d.src + (size_t)r * d.step + (size_t)(p - r * W) * bpp;
+    d.dst[p] = (uint8_t)(bpp == 1u ? (uint32_t)sp[0] : image_gray3((uint32_t)sp[0] | (uint32_t)sp[1] << 8 | (uint32_t)sp[2] << 16, d.cls));
+  }
+}
+
+void launch_image_emit(hipStream_t s, const ImageArgs& a) {
+  const uint32_t groups = (a.width * a.height + 3u + 3u) / 4u;  // destination dwords an image touches at the most
+  for (uint32_t first = 0; first < a.n_images; first += 65535u)
+    launch_k(k_image_emit, dim3((groups + 255u) / 256u, std::min(a.n_images - first, 65535u)), dim3(256), 0, s, a, first);
+}
+// (Behind every other kernel of the file on purpose: appended here, the image stage moves no track-path kernel's place in
+// the code object.)
+
 }  // namespace esvio

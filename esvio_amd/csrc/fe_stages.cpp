@@ -447,9 +447,14 @@ static int image_stage_slot(esvio_fe_ctx* c, size_t bytes, size_t* off) {
   return 0;
 }
 
-int copy_level0_in(esvio_fe_ctx* c, const PyrDesc& d, const uint8_t* in) {
+int copy_level0_in(esvio_fe_ctx* c, const PyrDesc& d, const uint8_t* in, int space) {
   const int stride = d.stride[0];
   const size_t bytes = (size_t)d.w[0] * d.h[0];
+  if (space == ESVIO_FE_DEVICE) {  // a dense image that lies on the device already: the re-pitching alone
+    HIPCHK(c, hipMemcpy2DAsync(d.img[0] + (size_t)kPad * stride + kPad, stride, in, d.w[0], d.w[0], d.h[0], hipMemcpyDeviceToDevice,
+                               cur_stream(c)));
+    return 0;
+  }
   size_t off = 0;
   if (int rc = image_stage_slot(c, bytes, &off)) return rc;
   std::memcpy(c->h_img + off, in, bytes);

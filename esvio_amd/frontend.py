@@ -228,6 +228,31 @@ class BagSideInfo(C.Structure):
                 ("chunks", C.c_uint64), ("connections", C.c_uint64)]
 
 
+class BagImage(C.Structure):
+    """esvio_fe_bag_image"""
+    _fields_ = [("cam", C.c_int32), ("seq", C.c_uint32), ("stamp_sec", C.c_uint32), ("stamp_nsec", C.c_uint32), ("time_sec", C.c_uint32),
+                ("time_nsec", C.c_uint32), ("height", C.c_uint32), ("width", C.c_uint32), ("step", C.c_uint32), ("encoding", C.c_int32),
+                ("is_bigendian", C.c_int32), ("index", C.c_uint64)]
+
+
+BAG_IMAGE_DTYPE = np.dtype({"names": ["cam", "seq", "stamp_sec", "stamp_nsec", "time_sec", "time_nsec", "height", "width", "step", "encoding",
+                                      "is_bigendian", "index"],
+                            "formats": ["<i4", "<u4", "<u4", "<u4", "<u4", "<u4", "<u4", "<u4", "<u4", "<i4", "<i4", "<u8"],
+                            "offsets": [0, 4, 8, 12, 16, 20, 24, 28, 32, 36, 40, 48], "itemsize": 56})
+ENC_MONO, ENC_BGR, ENC_RGB = 1, 2, 3  # esvio_fe_bag_image.encoding: mono8 | 8UC1, bgr8 | 8UC3, rgb8
+
+
+class BagImageCamInfo(C.Structure):
+    """esvio_fe_bag_image_cam_info"""
+    _fields_ = [("images", C.c_uint64), ("first_sec", C.c_uint32), ("first_nsec", C.c_uint32), ("last_sec", C.c_uint32), ("last_nsec", C.c_uint32)]
+
+
+class BagImageInfo(C.Structure):
+    """esvio_fe_bag_image_info"""
+    _fields_ = [("cam", BagImageCamInfo * 2), ("other_messages", C.c_uint64), ("other_records", C.c_uint64), ("chunks", C.c_uint64),
+                ("connections", C.c_uint64)]
+
+
 class EventRecord(C.Structure):
     """esvio_fe_event"""
     _fields_ = [("x", C.c_uint16), ("y", C.c_uint16), ("sec", C.c_uint32), ("nsec", C.c_uint32), ("polarity", C.c_uint8),
@@ -284,6 +309,7 @@ ABI_SYMBOLS = [
     "esvio_fe_decode_triggers", "esvio_fe_raw_header", "esvio_fe_slice_events_at",
     "esvio_fe_aedat_header", "esvio_fe_decode_aedat", "esvio_fe_aedat_side", "esvio_fe_track_aedat", "esvio_fe_feed_push_aedat",
     "esvio_fe_bag_header", "esvio_fe_bag_set_topics", "esvio_fe_decode_bag", "esvio_fe_bag_side", "esvio_fe_feed_push_bag",
+    "esvio_fe_bag_set_image_topics", "esvio_fe_decode_bag_images", "esvio_fe_convert_image", "esvio_fe_track_image_space",
     "esvio_fe_create_sae", "esvio_fe_create_sae_stereo", "esvio_fe_create_sae_stereo_mc", "esvio_fe_destroy",
     "esvio_fe_exchange_begin", "esvio_fe_exchange_end", "esvio_fe_exchange_tracks", "esvio_fe_export_image",
     "esvio_fe_feed_close", "esvio_fe_feed_open", "esvio_fe_feed_peek", "esvio_fe_feed_push_events", "esvio_fe_feed_push_fields",
@@ -316,6 +342,7 @@ TEST_SYMBOLS = [
     "esvio_fe_slice_tile_events", "esvio_fe_stage_kernel_count", "esvio_fe_stream",
     "esvio_fe_aedat_tile_events", "esvio_fe_ingest_kernel_count", "esvio_fe_aedat_walk_tap", "esvio_fe_aedat_walk_state_bytes",
     "esvio_fe_bag_tile_events", "esvio_fe_bag_walk_tap", "esvio_fe_bag_walk_state_bytes",
+    "esvio_fe_bag_image_walk_tap", "esvio_fe_image_tile_pixels",
 ]
 
 LATENCY_PHASES = 16
@@ -453,6 +480,11 @@ def load_library(build_if_missing=True):
     L.esvio_fe_decode_bag.argtypes = [vp, vp, sz, u32, C.POINTER(vp * 2), C.POINTER(sz * 2), i, vp, sz, C.POINTER(BagInfo)]
     L.esvio_fe_bag_side.argtypes = [vp, vp, sz, u32, vp, sz, C.POINTER(BagSideInfo)]
     L.esvio_fe_feed_push_bag.argtypes = [vp, vp, sz, u32, C.POINTER(FeedInfo * 2)]
+    L.esvio_fe_bag_set_image_topics.argtypes = [vp, C.c_char_p, C.c_char_p]
+    L.esvio_fe_decode_bag_images.argtypes = [vp, vp, sz, u32, C.POINTER(vp * 2), C.POINTER(sz * 2), i, vp, sz, C.POINTER(BagImageInfo)]
+    L.esvio_fe_convert_image.argtypes = [vp, vp, i, u32, u32, u32, C.c_int32, vp, i]
+    L.esvio_fe_track_image_space.argtypes = [vp, d, vp, vp, i, i, vp]
+    L.esvio_fe_bag_image_walk_tap.argtypes = [vp, sz, C.c_char_p, C.c_char_p, u32, u32, vp, sz, vp, sz, vp, sz, vp, sz, vp, vp, sz]
     L.esvio_fe_bag_walk_tap.argtypes = [vp, sz, C.POINTER(BagTopics), i, vp, sz, C.POINTER(vp * 2), C.POINTER(sz * 2), vp, sz, vp, sz, vp, vp, sz]
     L.esvio_fe_feed_track.argtypes = [vp, i, C.POINTER(Motion), C.POINTER(Tracks), C.POINTER(BatchInfo)]
     L.esvio_fe_feed_close.argtypes = [vp]
@@ -1084,6 +1116,75 @@ class FeatureTracker:
             raise e
         return imu[:int(info.imu)], info
 
+    def bag_set_image_topics(self, left=None, right=None):
+        """which topics of a rosbag hold the left and right sensor_msgs/Image messages (esvio_fe_bag_set_image_topics;
+        None: none).  Clears the image walker's state only."""
+        enc = lambda t: None if t is None else (t if isinstance(t, bytes) else str(t).encode())
+        self._hd.check(self._hd.L.esvio_fe_bag_set_image_topics(self._hd.h, enc(left), enc(right)))
+
+    def decode_bag_images(self, data, dst_cap=None, msgs_cap=None, device=False, flags=0):
+        """the rosbag image call (esvio_fe_decode_bag_images; include/esvio_fe.h "rosbag images" has the rule): the image
+        walker advanced by `data`, host memory, which may end anywhere.  Returns ((left, right), table, BagImageInfo): per
+        camera a numpy uint8 array [n, height, width] of gray images, or with device=True a DeviceImages (the caller
+        frees it; `.image(k)` is the pointer trackImage(..., device=True) takes); table a numpy BAG_IMAGE_DTYPE array.
+        dst_cap None: what the chunk and the bytes that wait can complete at the most; a number or a pair.  A failed
+        call raises FrontendError with `.info`."""
+        L = self._hd.L
+        W, H = self.cfg.width, self.cfg.height
+        buf = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data)
+        most = buf.nbytes // (38 + H) + 1  # (a message is 37 bytes and `height` rows of a byte at the least; one may have waited)
+        if dst_cap is None:
+            dst_cap = most
+        caps = [int(dst_cap)] * 2 if np.isscalar(dst_cap) else [int(dst_cap[0]), int(dst_cap[1])]
+        msgs_cap = most if msgs_cap is None else int(msgs_cap)
+        msgs, info = np.zeros(max(msgs_cap, 1), BAG_IMAGE_DTYPE), BagImageInfo()
+        ptrs, outs = (C.c_void_p * 2)(), []
+        for cam in range(2):
+            if device:
+                d = C.c_void_p()
+                rc = L.esvio_fe_mem_alloc(DEVICE, W * H * max(caps[cam], 1), C.byref(d))
+                if rc:
+                    raise FrontendError("esvio_fe_mem_alloc rc=%d" % rc)
+                outs.append(d)
+                ptrs[cam] = d.value
+            else:
+                outs.append(np.zeros((max(caps[cam], 1), H, W), np.uint8))
+                ptrs[cam] = outs[cam].ctypes.data
+        rc = L.esvio_fe_decode_bag_images(self._hd.h, _p(buf) if buf.nbytes else None, buf.nbytes, int(flags), C.byref(ptrs),
+                                          C.byref((C.c_size_t * 2)(*caps)), DEVICE if device else HOST, _p(msgs), msgs_cap, C.byref(info))
+        if rc:
+            if device:
+                for d in outs:
+                    L.esvio_fe_mem_free(DEVICE, d)
+            e = FrontendError("rc=%d: %s" % (rc, L.esvio_fe_last_error(self._hd.h).decode()))
+            e.info = info
+            raise e
+        k = [int(info.cam[0].images), int(info.cam[1].images)]
+        img = tuple(DeviceImages(outs[cam], k[cam], W, H) if device else outs[cam][:k[cam]] for cam in range(2))
+        return img, msgs[:k[0] + k[1]], info
+
+    def convert_image(self, src, height, width, step, encoding, src_space=HOST, device=False):
+        """getImageFromMsg's conversion alone (esvio_fe_convert_image): `src` a numpy uint8 array (host) or a device
+        pointer (src_space=DEVICE) whose rows lie `step` bytes apart, encoding ENC_MONO / ENC_BGR / ENC_RGB.  Returns the
+        gray image [height, width], or with device=True a DeviceImages of one image (the caller frees it)."""
+        L = self._hd.L
+        sp = _p(src) if isinstance(src, np.ndarray) else C.c_void_p(int(src))
+        if device:
+            d = C.c_void_p()
+            rc = L.esvio_fe_mem_alloc(DEVICE, max(int(height) * int(width), 1), C.byref(d))
+            if rc:
+                raise FrontendError("esvio_fe_mem_alloc rc=%d" % rc)
+            out, dp = DeviceImages(d, 1, int(width), int(height)), d
+        else:
+            out = np.zeros((int(height), int(width)), np.uint8)
+            dp = _p(out)
+        rc = L.esvio_fe_convert_image(self._hd.h, sp, int(src_space), int(height), int(width), int(step), int(encoding), dp, DEVICE if device else HOST)
+        if rc:
+            if device:
+                out.free()
+            raise FrontendError("rc=%d: %s" % (rc, L.esvio_fe_last_error(self._hd.h).decode()))
+        return out
+
     def feed_push_bag(self, data, flags=0):
         """append both cameras' events of a chunk of rosbag bytes, left before right (esvio_fe_feed_push_bag; host memory;
         the chunk may end anywhere).  Returns (FeedInfo, FeedInfo); a failed push raises FrontendError with `.info`."""
@@ -1247,9 +1348,15 @@ class FeatureTracker:
         self.__dict__[name] = v
         return v
 
-    def trackImage(self, cur_time, img_left, img_right, PUB_THIS_FRAME=True, copy=True):
+    def trackImage(self, cur_time, img_left, img_right, PUB_THIS_FRAME=True, copy=True, device=False):
         """FeatureTracker::trackImage (feature_tracker.cpp:164-338); the handle's width/height/
-        max_cnt/min_dist are the image camera's COL/ROW/MAX_CNT_IMG/MIN_DIST_IMG"""
+        max_cnt/min_dist are the image camera's COL/ROW/MAX_CNT_IMG/MIN_DIST_IMG.  device=True: img_left and img_right
+        are pointers to dense gray images in device memory (esvio_fe_track_image_space; DeviceImages.image(k))"""
+        if device:
+            self._hd.check(self._hd.L.esvio_fe_track_image_space(
+                self._hd.h, float(cur_time), C.c_void_p(int(img_left)), None if img_right is None else C.c_void_p(int(img_right)), DEVICE,
+                int(PUB_THIS_FRAME), C.byref(self._tr)))
+            return self._take(copy)
         il = np.ascontiguousarray(img_left, np.uint8)
         assert il.shape == (self.cfg.height, self.cfg.width)
         ir = None
@@ -1722,6 +1829,34 @@ class FilteredEvents:
             self.ptr = None
 
 
+class DeviceImages:
+    """n dense width x height gray images side by side in device memory of the library's runtime (what
+    esvio_fe_decode_bag_images and esvio_fe_convert_image write): `.image(k)` is the k-th one's address, which
+    trackImage(..., device=True) takes; `.download()` brings them to the host"""
+
+    def __init__(self, ptr, n, width, height):
+        self.space, self.ptr, self.n, self.width, self.height = DEVICE, ptr, n, width, height
+
+    def image(self, k):
+        assert 0 <= k < self.n
+        return self.ptr.value + int(k) * self.width * self.height
+
+    def download(self):
+        out = np.zeros((self.n, self.height, self.width), np.uint8)
+        if out.nbytes:
+            hip = C.CDLL("libamdhip64.so")
+            hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+            rc = hip.hipMemcpy(_p(out), self.ptr, out.nbytes, 2)
+            if rc:
+                raise FrontendError("hipMemcpy rc=%d" % rc)
+        return out
+
+    def free(self):
+        if self.ptr:
+            load_library().esvio_fe_mem_free(DEVICE, self.ptr)
+            self.ptr = None
+
+
 class RegisteredEvents:
     """a caller-owned numpy event array page-locked where it lies (esvio_fe_register_host_buffer): batches handed
     over from it cross PCIe without the staging copy; `.array` is the array itself"""
@@ -1921,3 +2056,29 @@ def bag_walk_tap(state, data, topics=(None, None, None), side=False, events_cap=
     c = tuple(int(v) for v in counts)
     return (st.tobytes(), tuple(pay[k][:13 * min(c[k], events_cap)].tobytes() for k in range(2)), msgs[:min(c[4], msgs_cap)].copy(),
             imu[:min(c[5], imu_cap)].copy(), c)
+
+
+def bag_image_walk_tap(state, data, topics=(None, None), size=(0, 0), pix_cap=None, imgs_cap=None):
+    """the rosbag host walk in its image mode alone (esvio_fe_bag_image_walk_tap; include/esvio_fe_test.h): `state` a
+    (walker bytes, waiting payload bytes) pair (None: the fresh state), topics = (left, right), size = (width, height)
+    the only size taken ((0, 0): any).  Returns (state, pix, table, counts): the gathered payloads, each from a 16-byte
+    boundary, as bytes, a numpy BAG_IMAGE_DTYPE array (what there was room for), the twelve counts.  A malformed stream
+    or a refused message raises FrontendError whose text is the broken rule."""
+    L = load_library()
+    nst = L.esvio_fe_bag_walk_state_bytes()
+    st = np.zeros(nst, np.uint8) if state is None else np.frombuffer(bytes(state[0]), np.uint8).copy()
+    waiting = b"" if state is None else bytes(state[1])
+    buf = np.frombuffer(bytes(data), np.uint8)
+    carry = np.zeros(len(waiting) + buf.nbytes + 1, np.uint8)
+    carry[:len(waiting)] = np.frombuffer(waiting, np.uint8)
+    pix_cap = len(waiting) + buf.nbytes + 16 * (buf.nbytes // 38 + 2) if pix_cap is None else int(pix_cap)
+    imgs_cap = buf.nbytes // 38 + 1 if imgs_cap is None else int(imgs_cap)
+    pix, imgs, counts = np.zeros(max(pix_cap, 1), np.uint8), np.zeros(max(imgs_cap, 1), BAG_IMAGE_DTYPE), np.zeros(12, np.uint64)
+    why = C.create_string_buffer(512)
+    enc = lambda t: None if t is None else (t if isinstance(t, bytes) else str(t).encode())
+    rc = L.esvio_fe_bag_image_walk_tap(_p(st), nst, enc(topics[0]), enc(topics[1]), int(size[0]), int(size[1]), _p(buf) if buf.nbytes else None,
+                                       buf.nbytes, _p(carry), len(carry), _p(pix), pix_cap, _p(imgs), imgs_cap, _p(counts), why, len(why))
+    if rc:
+        raise FrontendError("esvio_fe_bag_image_walk_tap rc=%d: %s" % (rc, why.value.decode()))
+    c = tuple(int(v) for v in counts)
+    return ((st.tobytes(), carry[:c[8]].tobytes()), pix[:c[3]].tobytes() if c[3] <= pix_cap else b"", imgs[:min(c[0], imgs_cap)], c)  # (a view: a copy would drop the row's padding word)

@@ -253,7 +253,30 @@ class StereoImageTrackerNode:
         self.restart_flag = False
         self.FREQ = freq if freq != 0 else 100
 
-    def handle(self, img_left, img_right, msg_timestamp):
+    @staticmethod
+    def pair_images(table):
+        """sync_process's pairing (stereo_image_tracker_node.cpp:219-246) applied off line to an image table
+        (frontend.BAG_IMAGE_DTYPE rows in stream order, what decode_bag_images returns): the two cameras' entries are
+        two queues; while both hold one, the fronts' header stamps decide — a left image at least 1 s older than the
+        right one is dropped (:226-230), a left image more than 1 s newer drops the right one (:231-235), else the two
+        are a pair and msg_timestamp is the left stamp (:238).  Returns [(left row, right row, msg_timestamp)]; rows left
+        over in one queue stay unpaired, as they would wait in the node's buffer."""
+        to_sec = lambda m: float(m["stamp_sec"]) + 1e-9 * float(m["stamp_nsec"])  # ros::Time::toSec
+        left = [m for m in table if m["cam"] == 0]
+        right = [m for m in table if m["cam"] == 1]
+        pairs, i, j = [], 0, 0
+        while i < len(left) and j < len(right):
+            time_left, time_right = to_sec(left[i]), to_sec(right[j])
+            if time_left <= time_right - 1:
+                i += 1
+            elif time_left > time_right + 1:
+                j += 1
+            else:
+                pairs.append((left[i], right[j], time_left))
+                i, j = i + 1, j + 1
+        return pairs
+
+    def handle(self, img_left, img_right, msg_timestamp, device=False):
         self.restart_flag = False
         if self.first_image_flag:  # :58-64
             self.first_image_flag = False
@@ -276,7 +299,10 @@ class StereoImageTrackerNode:
                 self.pub_count = 0
         else:
             pub = False
-        self.trackerData.trackImage(msg_timestamp, img_left, img_right, pub)  # :100
+        if device:  # (img_left / img_right: addresses of dense gray images in device memory)
+            self.trackerData.trackImage(msg_timestamp, img_left, img_right, pub, device=True)
+        else:
+            self.trackerData.trackImage(msg_timestamp, img_left, img_right, pub)  # :100
         if not pub:
             return None
         self.pub_count += 1  # :113-115

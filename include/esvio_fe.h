@@ -1008,9 +1008,10 @@ int esvio_fe_track_aedat(esvio_fe_handle h, const void* left, size_t left_bytes,
  * cross PCIe — densely per camera into pinned scratch, one copy brings them to the device, and one kernel turns both
  * cameras' 13-byte wire events into records, one per lane (KERNELS.md "ROS bags").
  *
- * Out of scope: bz2 / lz4 chunks, bag format 1.2, seeking by the index (the walk is sequential), sensor_msgs/Image
- * payloads, prophesee_event_msgs and other event message types, the odometry topic, IMU inside the feed (the side call
- * beside it is the way), announced batches, writing bags. */
+ * Out of scope: bz2 / lz4 chunks, bag format 1.2, seeking by the index (the walk is sequential), compressed image topics
+ * (sensor_msgs/CompressedImage) and every sensor_msgs/Image encoding or size that "rosbag images" below refuses,
+ * prophesee_event_msgs and other event message types, the odometry topic, IMU and images inside the feed (the side call
+ * and the image call beside it are the way), announced batches, writing bags. */
 typedef struct esvio_fe_bag_topics {
   const char* left;   /* dvs_msgs/EventArray, camera 0 */
   const char* right;  /* dvs_msgs/EventArray, camera 1 */
@@ -1071,6 +1072,98 @@ int esvio_fe_decode_bag(esvio_fe_handle h, const void* bytes, size_t n_bytes, ui
  * Runs on the host alone; argument errors as above. */
 int esvio_fe_bag_side(esvio_fe_handle h, const void* bytes, size_t n_bytes, uint32_t flags, esvio_fe_imu_sample* imu,
                       size_t imu_cap, esvio_fe_bag_side_info* info);
+
+/* ---- rosbag images: sensor_msgs/Image messages of two topics -> trackImage's 8-bit gray, on the device ---- */
+/* The ESVIO-mode parameter sets name image_left_topic / image_right_topic beside the event and IMU topics, and their bags
+ * hold all five.  WHAT IS CITED: which encodings the node takes and what it does with each is getImageFromMsg,
+ * feature_tracker/src/stereo_image_tracker_node.cpp:257-318 — "8UC1" is relabelled mono8 and copied (:261-275), "8UC3" is
+ * relabelled bgr8 and goes through cv::COLOR_BGR2GRAY (:276-290), "mono8" is copied (:291-295), "rgb8" goes through
+ * cv::COLOR_RGB2GRAY (:296-301), "bgr8" through cv::COLOR_BGR2GRAY (:302-307); the size check is :314-316; left and right
+ * are paired by header.stamp within +-1 s and msg_timestamp is the left stamp (:219-246).  WHAT IS RECALLED AND UNPINNED,
+ * as the container above: the sensor_msgs/Image wire layout, what cv_bridge::toCvCopy does for an unchanged encoding, and
+ * cv::cvtColor's 8-bit gray.  THIS TEXT IS THE SPECIFICATION; tests/bag_image_ref.py is its sequential reading.
+ *
+ * Image message data: the std_msgs/Header as above (u32 seq, u32 stamp.sec, u32 stamp.nsec, u32 L, L bytes frame_id),
+ * u32 height, u32 width, u32 Le, Le bytes encoding, u8 is_bigendian, u32 step, u32 D, D bytes data.  Well-formed:
+ * data_len == 37 + L + Le + D exactly, D == step * height exactly, height >= 1 and width >= 1, Le <= 32,
+ * step >= width * bpp (bpp 1 for the mono class, 3 for the colour classes); else the stream is MALFORMED and the message
+ * names the topic.  The connection's `type` must be "sensor_msgs/Image"; no MD5 is checked, as for the IMU: none can be
+ * cited.  is_bigendian is recorded and otherwise ignored: every accepted encoding has 8 bits per channel.
+ *
+ * Pixels.  toCvCopy with an unchanged encoding: row r is the width * bpp bytes at data + r * step, the rows packed
+ * densely; bytes behind them in a row are never read.  Classes: 1 = "mono8" | "8UC1": the byte; 2 = "bgr8" | "8UC3":
+ * (B, G, R) = the pixel's three bytes; 3 = "rgb8": (R, G, B).  Gray, as recalled for OpenCV 4.2's RGB2Gray<uchar>:
+ *     gray = (R * 9798 + G * 19235 + B * 3735 + (1 << 14)) >> 15
+ * THIS RULE IS THE 15-BIT FORM.  OpenCV 3's constants (4899 / 9617 / 1868, + (1 << 13), >> 14) give another byte on some
+ * pixels — (R, G, B) = (0, 0, 250) is 28 here and 29 there; tests/test_image_msg_vs_cv2.py compares with the cv2 at hand.
+ *
+ * REFUSED BY NAME, with ESVIO_FE_EINVAL, before any device work, the state as it was, in the call that brings the last
+ * byte of the message's fixed part: every other encoding (the reference's else branch hands those to cv_bridge's
+ * converters, which are not in its tree; the message names the encoding and the topic), and a message whose width x
+ * height is not the handle's (the reference calls cv::resize there, :314-316; no shipped parameter set triggers it, its
+ * 8-bit INTER_LINEAR can only be recalled, and a silently different resize is worse than a refusal).
+ *
+ * Roles and state.  esvio_fe_bag_set_image_topics names the left and the right image topic (NULL: none; the string rules of
+ * esvio_fe_bag_set_topics; no image topic may equal a topic that has a role from esvio_fe_bag_set_topics, else
+ * ESVIO_FE_EINVAL).  It clears the image walker's state only.  The handle has a THIRD walker state for
+ * esvio_fe_decode_bag_images, so the same bytes may go through the event call, the side call and the image call in any
+ * order; the image walk sees only the image topics (event and IMU messages are other_messages to it) and the other two
+ * walks see only theirs.  In ESVIO mode the image call is made on the image tracker's handle — width and height are the
+ * frame camera's — where no event topic need be set.  The bytes of a payload that a call's end cuts wait in a carry
+ * buffer the handle owns; a failed call leaves state and carry as they were.  esvio_fe_decode_reset and esvio_fe_reset
+ * clear the image state too; the topics stay.
+ *
+ * Source.  The counting walk checks everything; the gathering walk copies each completed message's D payload bytes, and
+ * nothing else, into pinned scratch, each from a 16-byte boundary; one copy brings them and the descriptor table to the
+ * device and ONE launch of k_image_emit (KERNELS.md "ROS bag images") writes all images of both cameras. */
+typedef struct esvio_fe_bag_image { /* one completed Image message */
+  int32_t cam;                     /* 0 left, 1 right */
+  uint32_t seq;                    /* header.seq */
+  uint32_t stamp_sec, stamp_nsec;  /* header.stamp: what the node pairs left and right by */
+  uint32_t time_sec, time_nsec;    /* the record's `time` */
+  uint32_t height, width, step;
+  int32_t encoding;                /* 1 mono8 | 8UC1, 2 bgr8 | 8UC3, 3 rgb8 */
+  int32_t is_bigendian;
+  uint64_t index;                  /* its image in dst[cam], counted per call */
+} esvio_fe_bag_image;
+typedef struct esvio_fe_bag_image_cam_info {
+  uint64_t images; /* messages completed (too small a dst_cap: the number needed) */
+  uint32_t first_sec, first_nsec, last_sec, last_nsec; /* the first / last completed message's header stamp; 0 if none */
+} esvio_fe_bag_image_cam_info;
+typedef struct esvio_fe_bag_image_info {
+  esvio_fe_bag_image_cam_info cam[2];
+  uint64_t other_messages, other_records, chunks, connections;
+} esvio_fe_bag_image_info;
+int esvio_fe_bag_set_image_topics(esvio_fe_handle h, const char* left, const char* right);
+/* the image call: the image walker advanced by the n_bytes at `bytes`; camera cam's k-th completed message of the call
+ * becomes the dense width * height gray image at dst[cam] + k * width * height (room for dst_cap[cam] IMAGES; dst_space
+ * for both: ESVIO_FE_DEVICE, any alignment, or ESVIO_FE_HOST), an esvio_fe_bag_image per completed message, in stream
+ * order, to the HOST array msgs (room for msgs_cap).  More images than a dst_cap or more messages than msgs_cap:
+ * ESVIO_FE_EINVAL, info->cam[].images hold the exact numbers needed, nothing is stored, the state is as it was.  flags
+ * must be 0.  n_bytes == 0 succeeds and touches nothing; n_bytes <= 2^28.  info is optional.  Orders itself on the main
+ * stream, waits for its own result and touches nothing of the tracker.  Its scratch — the payload bytes pinned and on the
+ * device, the images behind a host dst — grows on first use and with esvio_fe_reserve (one stereo pair of rgb8 frames of
+ * the handle's size) for a handle that has decoded images before: a second call of a given size allocates nothing.
+ * ESVIO_FE_EINVAL with a message, before any device work: unknown bits in flags, null bytes with n_bytes > 0, a null
+ * dst[cam] with dst_cap[cam] > 0, null msgs with msgs_cap > 0, a bad dst_space, n_bytes > 2^28, a malformed stream, a
+ * refused encoding or size.
+ * Tracking frame pairs: pair left and right entries as the node does (esvio_amd.node.StereoImageTrackerNode.pair_images)
+ * and hand dst[cam] + index * width * height to esvio_fe_track_image_space(..., ESVIO_FE_DEVICE, ...). */
+int esvio_fe_decode_bag_images(esvio_fe_handle h, const void* bytes, size_t n_bytes, uint32_t flags, uint8_t* const dst[2],
+                               const size_t dst_cap[2], int dst_space, esvio_fe_bag_image* msgs, size_t msgs_cap,
+                               esvio_fe_bag_image_info* info);
+/* the conversion alone: one image of height x width pixels (each 1 .. 8192, whatever the handle's size) of class
+ * `encoding` (1, 2, 3 as above), its rows `step` bytes apart at src (src_space ESVIO_FE_HOST: copied to the device first;
+ * ESVIO_FE_DEVICE: read in place, at any alignment), to the dense gray image dst (dst_space likewise; any alignment).
+ * step >= width * bpp, and the source's bytes up to the last row's last pixel, (height - 1) * step + width * bpp, are at
+ * most 2^28.  Argument errors are ESVIO_FE_EINVAL before any device work. */
+int esvio_fe_convert_image(esvio_fe_handle h, const void* src, int src_space, uint32_t height, uint32_t width, uint32_t step,
+                           int32_t encoding, uint8_t* dst, int dst_space);
+/* esvio_fe_track_image whose dense width * height images lie in `space`: ESVIO_FE_HOST is esvio_fe_track_image itself;
+ * ESVIO_FE_DEVICE: device memory, any alignment, re-pitched into level 0 (with equalize: into the raw slot in front of
+ * CLAHE) on the device — the pixels never come to the host.  The results are bit-identical for the same bytes. */
+int esvio_fe_track_image_space(esvio_fe_handle h, double cur_time, const uint8_t* img_left, const uint8_t* img_right,
+                               int space, int pub_this_frame, esvio_fe_tracks* out);
 
 /* ---- stream slicing: a record stream cut into fixed-rate windows, on the device ------------ */
 /* trackEvent takes one batch per camera and call; a recording or a sensor transfer is a long stream whose batch edges

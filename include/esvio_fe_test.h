@@ -223,6 +223,21 @@ int esvio_fe_bag_walk_tap(void* state, size_t state_bytes, const esvio_fe_bag_to
                           size_t msgs_cap, esvio_fe_imu_sample* imu, size_t imu_cap, uint64_t counts[12], char* why,
                           size_t why_cap);
 int esvio_fe_bag_walk_state_bytes(void);
+/* The bag host walk in its image mode alone, no handle and no device: the image walker's state in and out (as above), the
+ * topics as esvio_fe_bag_set_image_topics takes them, the only size taken (width 0: any), the n_bytes of a chunk in.
+ * `carry` holds the bytes of the open payload that earlier calls left waiting (the state says how many) and takes, on
+ * success, those that wait behind this call (room for carry_cap; it needs the waiting bytes + n_bytes at the most).  Out
+ * come the completed messages' payloads, each from a 16-byte boundary of pix (nothing is stored unless all fit pix_cap
+ * bytes), the image table (at most imgs_cap) and counts = {messages, left messages, right messages, payload bytes with
+ * their padding, other_messages, other_records, chunks, connections, bytes waiting behind the call, 0, 0, 0}.  pix and
+ * imgs may be null.  A malformed stream or a refused message: ESVIO_FE_EINVAL, state and carry as they were, the broken
+ * rule as text in `why`. */
+int esvio_fe_bag_image_walk_tap(void* state, size_t state_bytes, const char* left, const char* right, uint32_t width,
+                                uint32_t height, const void* bytes, size_t n_bytes, uint8_t* carry, size_t carry_cap,
+                                uint8_t* pix, size_t pix_cap, esvio_fe_bag_image* imgs, size_t imgs_cap, uint64_t counts[12],
+                                char* why, size_t why_cap);
+/* pixels per workgroup of k_image_emit, whose timer id is appended to the ingest range above */
+int esvio_fe_image_tile_pixels(void);
 /* the events one workgroup of the slicing chain takes (esvio_fe_slice_events): where its tile edges lie */
 int esvio_fe_slice_tile_events(void);
 /* the hipStream_t the handle launches on (as void*) */
