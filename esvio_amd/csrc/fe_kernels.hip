@@ -3524,7 +3524,8 @@ __global__ __launch_bounds__(256) void k_gftt_sortprep(const uint32_t* __restric
   __syncthreads();
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
     const uint32_t src = n - 1u - i;
-    const uint32_t key = ~comp_val[src];  // positive floats: larger value -> smaller key
+    // larger value -> smaller key, below zero too (a masked maximum below zero with a quality above 1)
+    const uint32_t key = ~f32_order_key(__uint_as_float(comp_val[src]));
     keys[i] = key;
     vals[i] = comp_xy[src];
     for (int p = 0; p < 4; p++) atomicAdd(&h[(p << 8) + ((key >> (8 * p)) & 255u)], 1u);
