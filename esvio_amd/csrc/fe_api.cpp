@@ -361,7 +361,7 @@ namespace {
 int baf_clear(esvio_fe_ctx* c);  // the background-activity filter's planes back to `none` (below, with the stage)
 int hot_clear(esvio_fe_ctx* c);  // hot-pixel learning: nothing counted (below, with the stage)
 int baf_ensure(esvio_fe_ctx* c, size_t n, bool host_src, bool host_dst, bool fields_form);
-int raw_ensure(esvio_fe_ctx* c, int cam, size_t n_bytes, bool copied_src, size_t dec_records);  // (below, with the stage)
+void decode_state_reset(esvio_fe_ctx* c);  // every ingest stage's decoder / walker state: fresh (below, behind the stages)
 void feed_empty(esvio_fe_ctx* c, bool streams_idle);  // the feed: no records, no windows (below, with the feed)
 }  // namespace
 
@@ -395,10 +395,7 @@ int esvio_fe_reset(esvio_fe_handle c) {
   HIPCHK(c, hipMemsetAsync(c->S2, 0, (size_t)2 * c->P * 16, cur_stream(c)));
   if (int rc = baf_clear(c)) return rc;  // the background-activity filter's planes: none everywhere
   if (int rc = hot_clear(c)) return rc;  // hot-pixel learning: nothing counted (the address filter and the mask are settings: kept)
-  c->rawdec.st[0] = c->rawdec.st[1] = esvio_fe_ctx::Raw::State();  // the raw-stream decoder: the fresh state
-  c->rawdec.trig_st[0] = c->rawdec.trig_st[1] = esvio_fe_ctx::Raw::State();  // ... and the trigger decoder's
-  for (int cam = 0; cam < 2; cam++) c->aedat.ev_st[cam] = c->aedat.side_st[cam] = esvio::aedat::Walk{};  // ... and the AEDAT walkers'
-  c->bag.ev_st = c->bag.side_st = c->bag.img_st = esvio::bag::Walk{};  // ... and the bag walkers' (the topics are settings: kept)
+  decode_state_reset(c);  // the raw-stream and trigger decoders, the AEDAT and bag walkers (the topics are settings: kept)
   c->slice.st[0] = c->slice.st[1] = esvio_fe_ctx::Slice::State();  // the stream slicer: no event seen, no window closed
   HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
   feed_empty(c, true);  // an open feed: no records, no windows (it stays open); every stream is idle here
@@ -1814,6 +1811,91 @@ int esvio_fe_track_event_filtered(esvio_fe_handle c, const esvio_fe_event* left,
   return rc;
 }
 
+// ---- ingest: what the stream formats' stages share.  A stage decodes a chunk in one "run" (raw_run, aedat_run, bag_run:
+// the chain enqueued, waited for and booked, the host's own corrections).  The run asks a placement where each camera's
+// records go (DecodedCam::d, cap: the caller's device dst, the decode scratch, the convert pair, the feed's room), fills
+// in the rest and leaves the state behind the chunk in the job.  The consumer refuses (BAD stamps first, then lack of
+// room) or takes the records, and takes the state over itself when the whole call has succeeded.
+namespace {
+struct DecodedCam {  // one camera's decoded records behind the wait
+  EventRec* d = nullptr;  // where they lie ...
+  size_t cap = 0;         // ... and the room there
+  size_t events = 0;      // (more than cap: nothing was stored)
+  unsigned long long bad = 0;
+  uint32_t sec = 0, nsec = 0;  // the last record's stamp (events > 0, bad == 0)
+};
+// an event dst: its memory space, null with room, the alignment of a device dst
+int dst_check(esvio_fe_ctx* c, const char* who, const char* name, const void* dst, size_t room, int space) {
+  if (space != ESVIO_FE_HOST && space != ESVIO_FE_DEVICE) return fail(c, ESVIO_FE_EINVAL, "%s: bad memory space", who);
+  if (room && !dst) return fail(c, ESVIO_FE_EINVAL, "%s: %s is null", who, name);
+  if (space == ESVIO_FE_DEVICE && ((uintptr_t)dst & 15) != 0) return fail(c, ESVIO_FE_EINVAL, "%s: a device dst must be 16-byte aligned", who);
+  return 0;
+}
+// placement: the decode scratch — behind a host dst, in front of a filter, for the feed's bag push
+int dec_scratch(esvio_fe_ctx* c, int cam, size_t records, DecodedCam* dc) {
+  if (int rc = c->rawdec.dec[cam].grow(c, records)) return rc;
+  dc->d = c->rawdec.dec[cam], dc->cap = c->rawdec.dec[cam].cap;
+  return 0;
+}
+// placement for "decode and track": the current convert pair, or, in front of a filter, the decode scratch
+int track_place(esvio_fe_ctx* c, bool filtered, const size_t want[2], DecodedCam dc[2]) {
+  if (filtered) {
+    for (int cam = 0; cam < 2; cam++)
+      if (int rc = dec_scratch(c, cam, std::max<size_t>(want[cam], 1), &dc[cam])) return rc;
+    return 0;
+  }
+  const int pair = c->cvt_pair;
+  if (int rc = cvt_pair_begin(c, want[0], want[1], &dc[0].d, &dc[1].d)) return rc;
+  dc[0].cap = c->d_cvt_ev[pair][0].cap, dc[1].cap = c->d_cvt_ev[pair][1].cap;
+  return 0;
+}
+// the records of n cameras to their host dst: the copies, one wait
+int deliver_host(esvio_fe_ctx* c, int n, void* const dst[], const DecodedCam dc[]) {
+  bool any = false;
+  for (int k = 0; k < n; k++) {
+    if (!dc[k].events) continue;
+    HIPCHK(c, hipMemcpyAsync(dst[k], dc[k].d, dc[k].events * sizeof(EventRec), hipMemcpyDeviceToHost, cur_stream(c)));
+    any = true;
+  }
+  if (any) HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  return 0;
+}
+// "Decode and track" from the BAD-stamp refusal on: dc[0], dc[1] are the cameras' records — in the decode scratch when
+// there is a filter, which then writes the kept ones into the convert pair, else in the pair —, states: how the refusal
+// names what stays.  commit() takes the decoders' states over; they move only when the whole call succeeds: a filter or
+// track body that fails leaves them as they were.
+extern "C++" template <class Commit>  // (this file is one extern "C" block)
+int track_decoded(esvio_fe_ctx* c, const char* who, const char* states, const DecodedCam dc[2], const esvio_fe_filter_params* filter,
+                  const esvio_fe_motion* motion, int pub_this_frame, esvio_fe_tracks* out, esvio_fe_batch_info* info_out, Commit commit) {
+  esvio_fe_batch_info info{};
+  info.bad[0] = dc[0].bad, info.bad[1] = dc[1].bad;
+  if (dc[0].bad || dc[1].bad) {
+    if (info_out) *info_out = info;
+    return fail(c, ESVIO_FE_EINVAL, "%s: %llu of %zu events have a stamp outside [0, 2^32 s); both cameras' %s are as they were", who,
+                dc[0].bad + dc[1].bad, dc[0].events + dc[1].events, states);
+  }
+  auto done = [&](int rc) {
+    if (rc == 0) commit();
+    return rc;
+  };
+  if (filter) {  // the body esvio_fe_track_batch has for device records with a filter: into the pair, stamped by the last kept left record
+    esvio_fe_batch b{};
+    b.left = (const esvio_fe_event*)dc[0].d, b.right = (const esvio_fe_event*)dc[1].d;
+    b.nL = dc[0].events, b.nR = dc[1].events, b.space = ESVIO_FE_DEVICE, b.pub_this_frame = pub_this_frame;
+    b.filter = filter, b.motion = motion, b.cur_time_from_batch = 1;
+    return done(track_batch_body(c, who, "decode and filter", b, out, info_out));
+  }
+  info.kept[0] = dc[0].events, info.kept[1] = dc[1].events;
+  if (info_out) *info_out = info;
+  if (!dc[0].events) return done(0);  // node:150: an empty left message is not tracked
+  info.cur_time = (double)dc[0].sec + 1e-9 * (double)dc[0].nsec;
+  const int rc = cvt_pair_track(c, info.cur_time, dc[0].d, dc[0].events, dc[1].d, dc[1].events, pub_this_frame, motion, out);
+  info.tracked = rc == 0;
+  if (info_out) *info_out = info;
+  return done(rc);
+}
+}  // namespace
+
 // ---- raw sensor streams: EVT3 / EVT2 words -> event records (the rule: include/esvio_fe.h; the chain: fe_kernels.h)
 namespace {
 constexpr size_t kRawMaxBytes = (size_t)1 << 28;
@@ -1825,8 +1907,6 @@ constexpr size_t kRawPinnedInPlaceBytes = (size_t)256 << 10;
 struct RawJob {  // one camera's part of a call
   const void* words = nullptr;
   size_t n_bytes = 0;
-  EventRec* d_dst = nullptr;
-  size_t cap = 0;
 };
 
 size_t raw_word_bytes(int format) { return format == ESVIO_FE_RAW_EVT3 ? 2 : format == ESVIO_FE_RAW_EVT21 ? 8 : 4; }
@@ -1847,24 +1927,30 @@ size_t raw_bound(int format, size_t n_bytes) {  // the records n_bytes of words 
 }
 uint32_t raw_tiles(size_t n_bytes) { return (uint32_t)((n_bytes + kRawTileBytes - 1) / kRawTileBytes); }
 
-int raw_ensure(esvio_fe_ctx* c, int cam, size_t n_bytes, bool copied_src, size_t dec_records) {
+int raw_ensure(esvio_fe_ctx* c, int cam, size_t n_bytes, bool copied_src) {
   esvio_fe_ctx::Raw& r = c->rawdec;
   r.used = true;
   if (!r.res)
     if (int rc = r.res.alloc(c, 2)) return rc;
   if (int rc = r.sums[cam].grow(c, raw_tiles(n_bytes))) return rc;
-  if (copied_src)
-    if (int rc = r.src[cam].grow(c, n_bytes)) return rc;
-  if (dec_records)
-    if (int rc = r.dec[cam].grow(c, dec_records)) return rc;
+  return copied_src ? r.src[cam].grow(c, n_bytes) : 0;
+}
+// esvio_fe_reserve for a handle that decodes raw streams: per camera the scratch of a stream of up to 8 bytes per event (include/esvio_fe.h)
+int raw_reserve(esvio_fe_ctx* c, const size_t events[2], bool host_batches) {
+  for (int cam = 0; cam < 2 && c->rawdec.used; cam++)
+    if (int rc = raw_ensure(c, cam, events[cam] * 8, host_batches)) return rc;
   return 0;
+}
+void raw_state_reset(esvio_fe_ctx* c) {  // the event decoder's and the trigger decoder's
+  c->rawdec.st[0] = c->rawdec.st[1] = c->rawdec.trig_st[0] = c->rawdec.trig_st[1] = esvio_fe_ctx::Raw::State();
 }
 
 // Enqueue the decode chain of one camera (job[1].n_bytes == 0) or of both on the current stream, and the copies that
-// bring the result blocks to the host; nothing is waited for.  *args: what the emit launch can be repeated with.
+// bring the result blocks to the host; nothing is waited for.  dc[k].d, cap: where job[k]'s records go.  *args: what the
+// emit launch can be repeated with.
 // trig: the trigger chain — the cameras' trigger-decoder states, its own reduce and emit launches around the same scan.
-int raw_enqueue(esvio_fe_ctx* c, int format, int space, int64_t t_offset_us, const RawJob job[2], const int cam_of[2], RawArgs* args,
-                RawResult res[2], bool trig = false) {
+int raw_enqueue(esvio_fe_ctx* c, int format, int space, int64_t t_offset_us, const RawJob job[2], const DecodedCam dc[2], const int cam_of[2],
+                RawArgs* args, RawResult res[2], bool trig) {
   esvio_fe_ctx::Raw& r = c->rawdec;
   hipStream_t s = cur_stream(c);
   RawArgs a{};
@@ -1878,12 +1964,12 @@ int raw_enqueue(esvio_fe_ctx* c, int format, int space, int64_t t_offset_us, con
       const bool in_place = r.pinned_copy < 0 ? job[k].n_bytes <= kRawPinnedInPlaceBytes : r.pinned_copy == 0;
       d_words = in_place ? pinned_device_ptr((const uint8_t*)job[k].words, job[k].n_bytes) : nullptr;
       if (!d_words) {
-        if (int rc = raw_ensure(c, cam, job[k].n_bytes, true, 0)) return rc;
+        if (int rc = raw_ensure(c, cam, job[k].n_bytes, true)) return rc;
         HIPCHK(c, hipMemcpyAsync(r.src[cam], job[k].words, job[k].n_bytes, hipMemcpyHostToDevice, s));
         d_words = r.src[cam];
       }
     }
-    if (int rc = raw_ensure(c, cam, job[k].n_bytes, false, 0)) return rc;
+    if (int rc = raw_ensure(c, cam, job[k].n_bytes, false)) return rc;
     const esvio_fe_ctx::Raw::State& st = trig ? r.trig_st[cam] : r.st[cam];
     RawCam& rc = a.cam[k];
     rc.words = d_words, rc.n_bytes = (uint32_t)job[k].n_bytes, rc.tiles = raw_tiles(job[k].n_bytes);
@@ -1891,10 +1977,10 @@ int raw_enqueue(esvio_fe_ctx* c, int format, int space, int64_t t_offset_us, con
                                         st.tl << kRawTlShift | st.y << kRawYShift,
                     st.bx, 0, 0, 0};
     rc.wraps_base = st.wraps, rc.t_offset = t_offset_us;
-    rc.sums = r.sums[cam], rc.dst = job[k].d_dst, rc.dst_cap = (uint32_t)std::min<size_t>(job[k].cap, 0xffffffffu);
+    rc.sums = r.sums[cam], rc.dst = dc[k].d, rc.dst_cap = (uint32_t)std::min<size_t>(dc[k].cap, 0xffffffffu);
     rc.res = r.res + cam;
     bytes += job[k].n_bytes;
-    cap_bytes += std::min(job[k].cap, trig ? job[k].n_bytes / raw_word_bytes(format) : raw_bound(format, job[k].n_bytes)) * 16;
+    cap_bytes += std::min(dc[k].cap, trig ? job[k].n_bytes / raw_word_bytes(format) : raw_bound(format, job[k].n_bytes)) * 16;
   }
   {
     ScopedKernel k(c, trig ? K_TRIG_REDUCE : K_RAW_REDUCE, bytes + (uint64_t)(a.cam[0].tiles + a.cam[1].tiles) * sizeof(RawXf));
@@ -1920,11 +2006,11 @@ int raw_enqueue(esvio_fe_ctx* c, int format, int space, int64_t t_offset_us, con
   return 0;
 }
 // the emit launch again, into buffers that have room now (the tiles' prefixes are still where the scan left them)
-int raw_emit_again(esvio_fe_ctx* c, RawArgs* a, const RawJob job[2], RawResult res[2], bool trig = false) {
+int raw_emit_again(esvio_fe_ctx* c, RawArgs* a, const RawJob job[2], const DecodedCam dc[2], RawResult res[2], bool trig) {
   hipStream_t s = cur_stream(c);
   for (int k = 0; k < 2; k++) {
     if (!job[k].n_bytes) continue;
-    a->cam[k].dst = job[k].d_dst, a->cam[k].dst_cap = (uint32_t)std::min<size_t>(job[k].cap, 0xffffffffu);
+    a->cam[k].dst = dc[k].d, a->cam[k].dst_cap = (uint32_t)std::min<size_t>(dc[k].cap, 0xffffffffu);
     HIPCHK(c, hipMemsetAsync((uint8_t*)a->cam[k].res + offsetof(RawResult, bad), 0, sizeof(unsigned long long), s));
   }
   {
@@ -1948,13 +2034,97 @@ void raw_info_clear(esvio_fe_raw_info* info, uint64_t wraps) {
   info->events = info->untimed = info->other = info->bad = 0;
   info->wraps = wraps;
 }
-// a call that succeeded: the camera's state is what the scan composed
-void raw_commit(esvio_fe_ctx* c, int cam, const RawResult& r) {
-  esvio_fe_ctx::Raw::State& st = c->rawdec.st[cam];
+// a call that succeeded: the camera's state is what the scan composed (the trigger decoder's: the time base alone)
+void raw_commit(esvio_fe_ctx* c, int cam, const RawResult& r, bool trig = false) {
+  esvio_fe_ctx::Raw::State& st = trig ? c->rawdec.trig_st[cam] : c->rawdec.st[cam];
   const RawXf& x = r.state;
   st.seen = x.flags & kRawHasTh ? 1 : 0, st.th = x.th_last, st.wraps += x.wraps;
-  st.tl = (x.flags >> kRawTlShift) & 0xfffu, st.y = (x.flags >> kRawYShift) & 0x7ffu;
+  st.tl = (x.flags >> kRawTlShift) & 0xfffu;
+  if (trig) return;
+  st.y = (x.flags >> kRawYShift) & 0x7ffu;
   st.bx = x.bx, st.bp = x.flags & kRawBp ? 1 : 0;
+}
+// The decode step of one camera (job[1].n_bytes == 0) or of both.  place(want, repeat, dc) says where job[k]'s records go
+// and how many fit there: one per word to begin with.  The chain runs and is waited for; when the reduce pass reports
+// more records than a buffer holds, no stamp is BAD and every count stays within repeat_up_to (kRawNoRepeat: the records
+// lie where they cannot be given more room; SIZE_MAX: whatever comes), place(counts, true, dc) makes room and the emit
+// launch is repeated.  r[k], dc[k]: the
+// result block and the records of job[k]; the cameras' states are as they were (raw_commit).
+constexpr size_t kRawNoRepeat = 0;
+extern "C++" template <class Place>
+int raw_run(esvio_fe_ctx* c, int format, int space, int64_t t_offset_us, const RawJob job[2], const int cam_of[2], bool trig,
+            size_t repeat_up_to, Place place, RawResult r[2], DecodedCam dc[2]) {
+  const size_t wb = raw_word_bytes(format);
+  const size_t first[2] = {job[0].n_bytes / wb, job[1].n_bytes / wb};
+  if (int rc = place(first, false, dc)) return rc;
+  RawArgs a;
+  if (int rc = raw_enqueue(c, format, space, t_offset_us, job, dc, cam_of, &a, r, trig)) return rc;
+  HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  if (!r[0].bad && !r[1].bad && (r[0].events > dc[0].cap || r[1].events > dc[1].cap) && r[0].events <= repeat_up_to &&
+      r[1].events <= repeat_up_to) {
+    const size_t need[2] = {r[0].events, r[1].events};
+    if (int rc = place(need, true, dc)) return rc;
+    if (int rc = raw_emit_again(c, &a, job, dc, r, trig)) return rc;
+    HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  }
+  if (c->prof_on) resolve_profile(c);
+  for (int k = 0; k < 2; k++) {
+    const uint64_t ticks = r[k].events ? (uint64_t)r[k].last_t : 0;  // microseconds
+    dc[k].events = r[k].events, dc[k].bad = r[k].bad;
+    dc[k].sec = (uint32_t)(ticks / 1000000u), dc[k].nsec = (uint32_t)(ticks % 1000000u * 1000u);
+  }
+  return 0;
+}
+
+// esvio_fe_decode_raw, and esvio_fe_decode_triggers (trig: the trigger chain, the camera's trigger-decoder state, one
+// record per word at the most, a dst that is always the host's) behind the null-handle check
+int raw_decode(esvio_fe_ctx* c, bool trig, int cam, int format, const void* words, size_t n_bytes, int space, int64_t t_offset_us,
+               void* dst, size_t dst_cap, int dst_space, esvio_fe_raw_info* info) {
+  const char* who = trig ? "decode_triggers" : "decode_raw";
+  const char* noun = trig ? "triggers" : "events";
+  const char* state = trig ? "trigger-decoder state" : "decoder state";
+  if (cam != 0 && cam != 1) return fail(c, ESVIO_FE_EINVAL, "%s: cam must be 0 or 1 (got %d)", who, cam);
+  const esvio_fe_ctx::Raw::State& st = trig ? c->rawdec.trig_st[cam] : c->rawdec.st[cam];
+  raw_info_clear(info, st.wraps);
+  if (int rc = raw_args_check(c, who, format, words, n_bytes, space, t_offset_us)) return rc;
+  if (int rc = dst_check(c, who, "dst", dst, dst_cap, dst_space)) return rc;
+  if (!n_bytes) return 0;
+  HIPCHK(c, hipSetDevice(c->dev));
+  const size_t per_word = n_bytes / raw_word_bytes(format), bound = trig ? per_word : raw_bound(format, n_bytes);
+  const size_t room = std::min(dst_cap, bound);
+  RawJob job[2];
+  job[0].words = words, job[0].n_bytes = n_bytes;
+  // The records behind a host dst lie in the decode scratch, never more than dst has room for.  Events: as many as the
+  // scratch holds, one per word at least; triggers (they are few): 4096 at the most to begin with
+  auto place = [&](const size_t want[2], bool repeat, DecodedCam dc[2]) -> int {
+    if (dst_space == ESVIO_FE_DEVICE) {  // the caller's own buffer, as it is
+      dc[0].d = (EventRec*)dst, dc[0].cap = room;
+      return 0;
+    }
+    size_t n = want[0];
+    if (!repeat) n = trig ? std::max<size_t>(std::min<size_t>(room, 4096), 1) : std::min(room, std::max(c->rawdec.dec[cam].cap, per_word));
+    if (int rc = dec_scratch(c, cam, n, &dc[0])) return rc;
+    if (!repeat) dc[0].cap = std::min(dc[0].cap, room);
+    return 0;
+  };
+  const int cam_of[2] = {cam, cam};
+  RawResult r[2] = {};
+  DecodedCam dc[2];
+  // (a repeat is for the scratch alone, and only for counts dst has room for: more are refused below, unrepeated)
+  const size_t repeat_up_to = dst_space == ESVIO_FE_HOST ? dst_cap : kRawNoRepeat;
+  if (int rc = raw_run(c, format, space, t_offset_us, job, cam_of, trig, repeat_up_to, place, r, dc)) return rc;
+  raw_info_fill(info, r[0], st.wraps);
+  if (dc[0].bad)
+    return fail(c, ESVIO_FE_EINVAL, "%s: %llu of %zu %s have a stamp outside [0, 2^32 s); the camera's %s is as it was", who, dc[0].bad,
+                dc[0].events, noun, state);
+  if (dc[0].events > dst_cap)
+    return fail(c, ESVIO_FE_EINVAL, "%s: the chunk holds %zu %s, dst has room for %zu; the camera's %s is as it was", who, dc[0].events, noun,
+                dst_cap, state);
+  if (dst_space == ESVIO_FE_HOST)
+    if (int rc = deliver_host(c, 1, &dst, dc)) return rc;
+  raw_commit(c, cam, r[0], trig);
+  if (info) info->wraps = st.wraps;
+  return 0;
 }
 }  // namespace
 
@@ -1963,59 +2133,7 @@ int esvio_fe_raw_tile_bytes(void) { return (int)kRawTileBytes; }
 int esvio_fe_decode_raw(esvio_fe_handle c, int cam, int format, const void* words, size_t n_bytes, int space,
                         int64_t t_offset_us, esvio_fe_event* dst, size_t dst_cap, int dst_space, esvio_fe_raw_info* info) {
   if (!c) return ESVIO_FE_EINVAL;
-  if (cam != 0 && cam != 1) return fail(c, ESVIO_FE_EINVAL, "decode_raw: cam must be 0 or 1 (got %d)", cam);
-  raw_info_clear(info, c->rawdec.st[cam].wraps);
-  if (int rc = raw_args_check(c, "decode_raw", format, words, n_bytes, space, t_offset_us)) return rc;
-  if (dst_space != ESVIO_FE_HOST && dst_space != ESVIO_FE_DEVICE) return fail(c, ESVIO_FE_EINVAL, "decode_raw: bad memory space");
-  if (dst_cap && !dst) return fail(c, ESVIO_FE_EINVAL, "decode_raw: dst is null");
-  if (dst_space == ESVIO_FE_DEVICE && ((uintptr_t)dst & 15) != 0)
-    return fail(c, ESVIO_FE_EINVAL, "decode_raw: a device dst must be 16-byte aligned");
-  if (!n_bytes) return 0;
-  HIPCHK(c, hipSetDevice(c->dev));
-  const size_t bound = raw_bound(format, n_bytes);
-  RawJob job[2];
-  job[0].words = words, job[0].n_bytes = n_bytes;
-  job[0].d_dst = (EventRec*)dst, job[0].cap = std::min(dst_cap, bound);
-  if (dst_space == ESVIO_FE_HOST) {  // the records behind a host dst: one per word to begin with, never more than dst has room for
-    const size_t want = std::min(job[0].cap, std::max<size_t>(c->rawdec.dec[cam].cap, n_bytes / raw_word_bytes(format)));
-    if (int rc = raw_ensure(c, cam, n_bytes, false, want)) return rc;
-    job[0].d_dst = c->rawdec.dec[cam], job[0].cap = std::min(job[0].cap, c->rawdec.dec[cam].cap);
-  }
-  const int cam_of[2] = {cam, cam};
-  RawArgs a;
-  RawResult r[2] = {};
-  if (int rc = raw_enqueue(c, format, space, t_offset_us, job, cam_of, &a, r)) return rc;
-  HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
-  if (dst_space == ESVIO_FE_HOST && !r[0].bad && r[0].events > job[0].cap && r[0].events <= dst_cap) {
-    if (int rc = raw_ensure(c, cam, n_bytes, false, r[0].events)) return rc;
-    job[0].d_dst = c->rawdec.dec[cam], job[0].cap = c->rawdec.dec[cam].cap;
-    if (int rc = raw_emit_again(c, &a, job, r)) return rc;
-    HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
-  }
-  if (c->prof_on) resolve_profile(c);
-  raw_info_fill(info, r[0], c->rawdec.st[cam].wraps);
-  if (r[0].bad)
-    return fail(c, ESVIO_FE_EINVAL, "decode_raw: %llu of %u events have a stamp outside [0, 2^32 s); the camera's decoder state is as it was",
-                r[0].bad, r[0].events);
-  if (r[0].events > dst_cap)
-    return fail(c, ESVIO_FE_EINVAL, "decode_raw: the chunk holds %u events, dst has room for %zu; the camera's decoder state is as it was",
-                r[0].events, dst_cap);
-  if (dst_space == ESVIO_FE_HOST && r[0].events) {
-    HIPCHK(c, hipMemcpyAsync(dst, job[0].d_dst, (size_t)r[0].events * sizeof(EventRec), hipMemcpyDeviceToHost, cur_stream(c)));
-    HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
-  }
-  raw_commit(c, cam, r[0]);
-  if (info) info->wraps = c->rawdec.st[cam].wraps;
-  return 0;
-}
-
-int esvio_fe_decode_reset(esvio_fe_handle c) {
-  if (!c) return ESVIO_FE_EINVAL;
-  c->rawdec.st[0] = c->rawdec.st[1] = esvio_fe_ctx::Raw::State();
-  c->rawdec.trig_st[0] = c->rawdec.trig_st[1] = esvio_fe_ctx::Raw::State();
-  for (int cam = 0; cam < 2; cam++) c->aedat.ev_st[cam] = c->aedat.side_st[cam] = esvio::aedat::Walk{};
-  c->bag.ev_st = c->bag.side_st = c->bag.img_st = esvio::bag::Walk{};
-  return 0;
+  return raw_decode(c, false, cam, format, words, n_bytes, space, t_offset_us, dst, dst_cap, dst_space, info);
 }
 
 // ---- external triggers: the decode chain with the trigger classifier, the camera's trigger-decoder state (include/esvio_fe.h)
@@ -2023,49 +2141,13 @@ static_assert(sizeof(esvio_fe_trigger) == sizeof(EventRec), "trigger records tra
 int esvio_fe_decode_triggers(esvio_fe_handle c, int cam, int format, const void* words, size_t n_bytes, int space,
                              int64_t t_offset_us, esvio_fe_trigger* dst, size_t dst_cap, esvio_fe_trigger_info* info) {
   if (!c) return ESVIO_FE_EINVAL;
-  if (cam != 0 && cam != 1) return fail(c, ESVIO_FE_EINVAL, "decode_triggers: cam must be 0 or 1 (got %d)", cam);
-  esvio_fe_ctx::Raw::State& st = c->rawdec.trig_st[cam];
-  if (info) info->triggers = info->untimed = info->bad = 0, info->wraps = st.wraps;
-  if (int rc = raw_args_check(c, "decode_triggers", format, words, n_bytes, space, t_offset_us)) return rc;
-  if (dst_cap && !dst) return fail(c, ESVIO_FE_EINVAL, "decode_triggers: dst is null");
-  if (!n_bytes) return 0;
-  HIPCHK(c, hipSetDevice(c->dev));
-  const size_t bound = n_bytes / raw_word_bytes(format);  // one trigger per word at the most
-  // the records on the device: the stage's scratch, as large as it is to begin with (triggers are few), never more than dst has room for
-  if (int rc = raw_ensure(c, cam, n_bytes, false, std::max<size_t>(std::min(dst_cap, std::min<size_t>(bound, 4096)), 1))) return rc;
-  RawJob job[2];
-  job[0].words = words, job[0].n_bytes = n_bytes;
-  job[0].d_dst = c->rawdec.dec[cam], job[0].cap = std::min(std::min(dst_cap, bound), c->rawdec.dec[cam].cap);
-  const int cam_of[2] = {cam, cam};
-  RawArgs a;
-  RawResult r[2] = {};
-  if (int rc = raw_enqueue(c, format, space, t_offset_us, job, cam_of, &a, r, true)) return rc;
-  HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
-  if (!r[0].bad && r[0].events > job[0].cap && r[0].events <= dst_cap) {
-    if (int rc = raw_ensure(c, cam, n_bytes, false, r[0].events)) return rc;
-    job[0].d_dst = c->rawdec.dec[cam], job[0].cap = c->rawdec.dec[cam].cap;
-    if (int rc = raw_emit_again(c, &a, job, r, true)) return rc;
-    HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  esvio_fe_raw_info ri{};  // (a trigger word counts as one "event" of the chain)
+  const int rc = raw_decode(c, true, cam, format, words, n_bytes, space, t_offset_us, dst, dst_cap, ESVIO_FE_HOST, info ? &ri : nullptr);
+  if (info && (cam == 0 || cam == 1)) {
+    info->triggers = ri.events, info->untimed = ri.untimed, info->bad = ri.bad, info->wraps = ri.wraps;
+    if (ri.events) info->first_t_us = ri.first_t_us, info->last_t_us = ri.last_t_us;
   }
-  if (c->prof_on) resolve_profile(c);
-  if (info) {
-    info->triggers = r[0].events, info->untimed = r[0].untimed, info->bad = r[0].bad;
-    if (r[0].events) info->first_t_us = r[0].first_t, info->last_t_us = r[0].last_t;
-  }
-  if (r[0].bad)
-    return fail(c, ESVIO_FE_EINVAL, "decode_triggers: %llu of %u triggers have a stamp outside [0, 2^32 s); the camera's trigger-decoder state is as it was",
-                r[0].bad, r[0].events);
-  if (r[0].events > dst_cap)
-    return fail(c, ESVIO_FE_EINVAL, "decode_triggers: the chunk holds %u triggers, dst has room for %zu; the camera's trigger-decoder state is as it was",
-                r[0].events, dst_cap);
-  if (r[0].events) {
-    HIPCHK(c, hipMemcpyAsync(dst, job[0].d_dst, (size_t)r[0].events * sizeof(esvio_fe_trigger), hipMemcpyDeviceToHost, cur_stream(c)));
-    HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
-  }
-  const RawXf& x = r[0].state;  // the call succeeded: the state is what the scan composed
-  st.seen = x.flags & kRawHasTh ? 1 : 0, st.th = x.th_last, st.wraps += x.wraps, st.tl = (x.flags >> kRawTlShift) & 0xfffu;
-  if (info) info->wraps = st.wraps;
-  return 0;
+  return rc;
 }
 
 // ---- the .raw file's ASCII header (include/esvio_fe.h has the rule): host only
@@ -2152,8 +2234,7 @@ int esvio_fe_track_raw(esvio_fe_handle c, int format, const void* left, size_t l
                        const esvio_fe_filter_params* filter, const esvio_fe_motion* motion, esvio_fe_tracks* out,
                        esvio_fe_batch_info* info_out, esvio_fe_raw_info raw[2]) {
   if (!c) return ESVIO_FE_EINVAL;
-  esvio_fe_batch_info info{};
-  if (info_out) *info_out = info;
+  if (info_out) *info_out = esvio_fe_batch_info{};
   const void* words[2] = {left, right};
   const size_t nb[2] = {left_bytes, right_bytes};
   for (int cam = 0; cam < 2; cam++) {
@@ -2166,74 +2247,22 @@ int esvio_fe_track_raw(esvio_fe_handle c, int format, const void* left, size_t l
     return fail(c, ESVIO_FE_EINVAL, "track_raw: batches are announced on this handle (decode into memory of your own)");
   if (!nb[0] && !nb[1]) return 0;  // nothing to decode: no left event, nothing tracked
   HIPCHK(c, hipSetDevice(c->dev));
-  // where the records go: the current pair, or, in front of a filter, the stage's own buffers
-  const size_t wb = raw_word_bytes(format);
   RawJob job[2];
-  auto place = [&](const size_t want[2]) -> int {
-    EventRec* d[2] = {nullptr, nullptr};
-    if (filter) {
-      for (int cam = 0; cam < 2; cam++) {
-        if (int rc = raw_ensure(c, cam, nb[cam], false, std::max<size_t>(want[cam], 1))) return rc;
-        d[cam] = c->rawdec.dec[cam];
-        job[cam].cap = c->rawdec.dec[cam].cap;
-      }
-    } else {
-      const int pair = c->cvt_pair;
-      const size_t nL = std::max(want[0], c->d_cvt_ev[pair][0].cap), nR = std::max(want[1], c->d_cvt_ev[pair][1].cap);
-      if (int rc = cvt_pair_begin(c, nL, nR, &d[0], &d[1])) return rc;
-      job[0].cap = c->d_cvt_ev[pair][0].cap, job[1].cap = c->d_cvt_ev[pair][1].cap;
-    }
-    for (int cam = 0; cam < 2; cam++) job[cam].words = words[cam], job[cam].n_bytes = nb[cam], job[cam].d_dst = d[cam];
-    return 0;
-  };
-  const size_t first[2] = {nb[0] / wb, nb[1] / wb};
-  if (int rc = place(first)) return rc;
+  for (int cam = 0; cam < 2; cam++) job[cam].words = words[cam], job[cam].n_bytes = nb[cam];
+  auto place = [&](const size_t want[2], bool, DecodedCam dc[2]) { return track_place(c, filter != nullptr, want, dc); };
   const int cam_of[2] = {0, 1};
-  RawArgs a;
   RawResult r[2] = {};
-  if (int rc = raw_enqueue(c, format, space, t_offset_us, job, cam_of, &a, r)) return rc;
-  HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
-  if (!r[0].bad && !r[1].bad && (r[0].events > job[0].cap || r[1].events > job[1].cap)) {
-    const size_t need[2] = {r[0].events, r[1].events};
-    if (int rc = place(need)) return rc;
-    if (int rc = raw_emit_again(c, &a, job, r)) return rc;
-    HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
-  }
-  if (c->prof_on) resolve_profile(c);
-  for (int cam = 0; cam < 2; cam++) {
+  DecodedCam dc[2];
+  if (int rc = raw_run(c, format, space, t_offset_us, job, cam_of, false, SIZE_MAX, place, r, dc)) return rc;
+  for (int cam = 0; cam < 2; cam++)
     if (raw && nb[cam]) raw_info_fill(&raw[cam], r[cam], c->rawdec.st[cam].wraps);
-    info.bad[cam] = r[cam].bad;
-  }
-  if (r[0].bad || r[1].bad) {
-    if (info_out) *info_out = info;
-    return fail(c, ESVIO_FE_EINVAL, "track_raw: %llu of %u events have a stamp outside [0, 2^32 s); both cameras' decoder states are as they were",
-                r[0].bad + r[1].bad, r[0].events + r[1].events);
-  }
-  // the decoder states move only when the whole call succeeds: a filter or track body that fails leaves them as they were
-  auto done = [&](int rc) {
-    for (int cam = 0; cam < 2 && rc == 0; cam++)
+  return track_decoded(c, "track_raw", "decoder states", dc, filter, motion, pub_this_frame, out, info_out, [&] {
+    for (int cam = 0; cam < 2; cam++)
       if (nb[cam]) {
         raw_commit(c, cam, r[cam]);
         if (raw) raw[cam].wraps = c->rawdec.st[cam].wraps;
       }
-    return rc;
-  };
-  if (filter) {  // the body esvio_fe_track_batch has for device records with a filter: into the pair, stamped by the last kept left record
-    esvio_fe_batch b{};
-    b.left = (const esvio_fe_event*)job[0].d_dst, b.right = (const esvio_fe_event*)job[1].d_dst;
-    b.nL = r[0].events, b.nR = r[1].events, b.space = ESVIO_FE_DEVICE, b.pub_this_frame = pub_this_frame;
-    b.filter = filter, b.motion = motion, b.cur_time_from_batch = 1;
-    return done(track_batch_body(c, "track_raw", "decode and filter", b, out, info_out));
-  }
-  info.kept[0] = r[0].events, info.kept[1] = r[1].events;
-  if (info_out) *info_out = info;
-  if (!r[0].events) return done(0);  // node:150: an empty left message is not tracked
-  const uint64_t ticks = (uint64_t)r[0].last_t;
-  info.cur_time = (double)(uint32_t)(ticks / 1000000u) + 1e-9 * (double)(uint32_t)(ticks % 1000000u * 1000u);
-  const int rc = cvt_pair_track(c, info.cur_time, job[0].d_dst, r[0].events, job[1].d_dst, r[1].events, pub_this_frame, motion, out);
-  info.tracked = rc == 0;
-  if (info_out) *info_out = info;
-  return done(rc);
+  });
 }
 
 // ---- libcaer / AEDAT 3.1 packet streams (the rule: include/esvio_fe.h; the host walk: fe_aedat.h; the chain: fe_kernels.h)
@@ -2243,8 +2272,6 @@ static_assert(sizeof(ae::Run) == sizeof(AedatRun), "the walk's run table is the 
 struct AedatJob {  // one camera's part of a call
   const void* bytes = nullptr;
   size_t n_bytes = 0;
-  EventRec* d_dst = nullptr;
-  size_t cap = 0;
   ae::Walk st{};   // the camera's state behind the chunk: taken over when the call succeeds
   ae::Out cnt;     // what the counting walk found: n_events, n_runs, the packets
 };
@@ -2280,10 +2307,20 @@ int aedat_ensure(esvio_fe_ctx* c, int cam, size_t n_events, size_t n_runs) {
   if (int rc = A.h_pack[cam].grow(c, bytes)) return rc;
   return A.d_pack[cam].grow(c, bytes);
 }
+// esvio_fe_reserve for a handle that decodes AEDAT streams: per camera the scratch of a chunk of max_events polarity records, each a run
+int aedat_reserve(esvio_fe_ctx* c, const size_t events[2]) {
+  for (int cam = 0; cam < 2 && c->aedat.used; cam++)
+    if (int rc = aedat_ensure(c, cam, events[cam], events[cam])) return rc;
+  return 0;
+}
+void aedat_state_reset(esvio_fe_ctx* c) {
+  for (int cam = 0; cam < 2; cam++) c->aedat.ev_st[cam] = c->aedat.side_st[cam] = ae::Walk{};
+}
 // The gathering walk and the chain of one camera (job[1].n_bytes == 0) or of both on the current stream, and the copies
-// that bring the result blocks to the host; nothing is waited for.  A camera whose chunk completes no polarity record
-// takes no part on the device.
-int aedat_enqueue(esvio_fe_ctx* c, int64_t t_offset_ns, uint32_t flags, AedatJob job[2], const int cam_of[2], AedatResult res[2]) {
+// that bring the result blocks to the host; nothing is waited for.  dc[k].d, cap: where job[k]'s records go.  A camera
+// whose chunk completes no polarity record takes no part on the device.
+int aedat_enqueue(esvio_fe_ctx* c, int64_t t_offset_ns, uint32_t flags, AedatJob job[2], const DecodedCam dc[2], const int cam_of[2],
+                  AedatResult res[2]) {
   esvio_fe_ctx::Aedat& A = c->aedat;
   hipStream_t s = cur_stream(c);
   const bool keep = (flags & ESVIO_FE_AEDAT_KEEP_INVALID) != 0;
@@ -2307,9 +2344,9 @@ int aedat_enqueue(esvio_fe_ctx* c, int64_t t_offset_ns, uint32_t flags, AedatJob
     ac.rec = (const uint2*)A.d_pack[cam].p, ac.n = (uint32_t)n, ac.tiles = aedat_tiles(n);
     ac.runs = (const AedatRun*)(A.d_pack[cam].p + roff), ac.n_runs = (uint32_t)n_runs;
     ac.keep_invalid = keep, ac.wave_lookup = (uint32_t)A.wave_lookup, ac.t_offset = t_offset_ns, ac.sums = A.sums[cam];
-    ac.dst = job[k].d_dst, ac.dst_cap = (uint32_t)std::min<size_t>(job[k].cap, 0xffffffffu);
+    ac.dst = dc[k].d, ac.dst_cap = (uint32_t)std::min<size_t>(dc[k].cap, 0xffffffffu);
     ac.res = A.res + cam;
-    n_all += n, cap_all += std::min(job[k].cap, n);
+    n_all += n, cap_all += std::min(dc[k].cap, n);
     if (keep) HIPCHK(c, hipMemsetAsync(ac.res, 0, sizeof(AedatResult), s));  // (events = n: the host's own knowledge)
   }
   if (!n_all) return 0;
@@ -2344,6 +2381,26 @@ void aedat_info_fill(esvio_fe_aedat_info* info, const AedatResult& r) {
 void aedat_info_clear(esvio_fe_aedat_info* info) {
   if (info) info->events = info->invalid = info->bad = info->polarity_packets = info->other_packets = 0;
 }
+// The decode step of one camera (job[1].n_bytes == 0) or of both, behind their counting walks.  place(want, dc) says
+// where job[k]'s records go: want[k] is the host-known count of the chunk's records, so nothing is repeated.  The
+// gathering walk and the chain run and are waited for, and the host adds what it knows itself.  r[k], dc[k]: the result
+// block and the records of job[k]; job[k].st: the walker behind the chunk, which the consumer takes over.
+extern "C++" template <class Place>
+int aedat_run(esvio_fe_ctx* c, int64_t t_offset_ns, uint32_t flags, AedatJob job[2], const int cam_of[2], Place place, AedatResult r[2],
+              DecodedCam dc[2]) {
+  const size_t want[2] = {(size_t)job[0].cnt.n_events, (size_t)job[1].cnt.n_events};
+  if (int rc = place(want, dc)) return rc;
+  if (int rc = aedat_enqueue(c, t_offset_ns, flags, job, dc, cam_of, r)) return rc;
+  HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  if (c->prof_on) resolve_profile(c);
+  for (int k = 0; k < 2; k++) {
+    aedat_result_fix(job[k], flags, &r[k]);
+    const uint64_t ticks = r[k].events ? r[k].last_t : 0;  // nanoseconds
+    dc[k].events = r[k].events, dc[k].bad = r[k].bad;
+    dc[k].sec = (uint32_t)(ticks / 1000000000u), dc[k].nsec = (uint32_t)(ticks % 1000000000u);
+  }
+  return 0;
+}
 }  // namespace
 
 int esvio_fe_aedat_tile_events(void) { return (int)kAedatTile; }
@@ -2356,39 +2413,35 @@ int esvio_fe_decode_aedat(esvio_fe_handle c, int cam, const void* bytes, size_t 
   aedat_info_clear(info);
   if (cam != 0 && cam != 1) return fail(c, ESVIO_FE_EINVAL, "decode_aedat: cam must be 0 or 1 (got %d)", cam);
   if (int rc = aedat_args_check(c, "decode_aedat", bytes, n_bytes, t_offset_ns, flags)) return rc;
-  if (dst_space != ESVIO_FE_HOST && dst_space != ESVIO_FE_DEVICE) return fail(c, ESVIO_FE_EINVAL, "decode_aedat: bad memory space");
-  if (dst_cap && !dst) return fail(c, ESVIO_FE_EINVAL, "decode_aedat: dst is null");
-  if (dst_space == ESVIO_FE_DEVICE && ((uintptr_t)dst & 15) != 0)
-    return fail(c, ESVIO_FE_EINVAL, "decode_aedat: a device dst must be 16-byte aligned");
+  if (int rc = dst_check(c, "decode_aedat", "dst", dst, dst_cap, dst_space)) return rc;
   if (!n_bytes) return 0;
   AedatJob job[2];
   job[0].bytes = bytes, job[0].n_bytes = n_bytes;
   if (int rc = aedat_count_walk(c, "decode_aedat", cam, &job[0])) return rc;
   aedat_info_packets(info, job[0].cnt);
   HIPCHK(c, hipSetDevice(c->dev));
-  const size_t bound = (size_t)job[0].cnt.n_events;
-  job[0].d_dst = (EventRec*)dst, job[0].cap = std::min(dst_cap, bound);
-  if (dst_space == ESVIO_FE_HOST && job[0].cap) {  // the records behind a host dst
-    if (int rc = c->rawdec.dec[cam].grow(c, job[0].cap)) return rc;
-    job[0].d_dst = c->rawdec.dec[cam];
-  }
+  auto place = [&](const size_t want[2], DecodedCam dc[2]) -> int {
+    const size_t room = std::min(dst_cap, want[0]);
+    dc[0].d = (EventRec*)dst;
+    if (dst_space == ESVIO_FE_HOST && room)  // the records behind a host dst: as many as it has room for
+      if (int rc = dec_scratch(c, cam, room, &dc[0])) return rc;
+    dc[0].cap = room;
+    return 0;
+  };
   const int cam_of[2] = {cam, cam};
   AedatResult r[2] = {};
-  if (int rc = aedat_enqueue(c, t_offset_ns, flags, job, cam_of, r)) return rc;
-  HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
-  if (c->prof_on) resolve_profile(c);
-  aedat_result_fix(job[0], flags, &r[0]);
+  DecodedCam dc[2];
+  if (int rc = aedat_run(c, t_offset_ns, flags, job, cam_of, place, r, dc)) return rc;
   aedat_info_fill(info, r[0]);
-  if (r[0].bad)
-    return fail(c, ESVIO_FE_EINVAL, "decode_aedat: %llu of %u events have a stamp outside [0, 2^32 s); the camera's state is as it was",
-                r[0].bad, r[0].events);
-  if (r[0].events > dst_cap)
-    return fail(c, ESVIO_FE_EINVAL, "decode_aedat: the chunk holds %u events, dst has room for %zu; the camera's state is as it was",
-                r[0].events, dst_cap);
-  if (dst_space == ESVIO_FE_HOST && r[0].events) {
-    HIPCHK(c, hipMemcpyAsync(dst, job[0].d_dst, (size_t)r[0].events * sizeof(EventRec), hipMemcpyDeviceToHost, cur_stream(c)));
-    HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
-  }
+  if (dc[0].bad)
+    return fail(c, ESVIO_FE_EINVAL, "decode_aedat: %llu of %zu events have a stamp outside [0, 2^32 s); the camera's state is as it was",
+                dc[0].bad, dc[0].events);
+  if (dc[0].events > dst_cap)
+    return fail(c, ESVIO_FE_EINVAL, "decode_aedat: the chunk holds %zu events, dst has room for %zu; the camera's state is as it was",
+                dc[0].events, dst_cap);
+  void* const host_dst = dst;
+  if (dst_space == ESVIO_FE_HOST)
+    if (int rc = deliver_host(c, 1, &host_dst, dc)) return rc;
   c->aedat.ev_st[cam] = job[0].st;
   return 0;
 }
@@ -2428,8 +2481,7 @@ int esvio_fe_track_aedat(esvio_fe_handle c, const void* left, size_t left_bytes,
                          const esvio_fe_motion* motion, esvio_fe_tracks* out, esvio_fe_batch_info* info_out,
                          esvio_fe_aedat_info aedat[2]) {
   if (!c) return ESVIO_FE_EINVAL;
-  esvio_fe_batch_info info{};
-  if (info_out) *info_out = info;
+  if (info_out) *info_out = esvio_fe_batch_info{};
   AedatJob job[2];
   job[0].bytes = left, job[0].n_bytes = left_bytes, job[1].bytes = right, job[1].n_bytes = right_bytes;
   for (int cam = 0; cam < 2; cam++) {
@@ -2447,56 +2499,17 @@ int esvio_fe_track_aedat(esvio_fe_handle c, const void* left, size_t left_bytes,
     if (aedat) aedat_info_packets(&aedat[cam], job[cam].cnt);
   }
   HIPCHK(c, hipSetDevice(c->dev));
-  // where the records go: the current pair, or, in front of a filter, the decode stage's own buffers; the capacity is the
-  // host-known count of the chunk's records
-  const size_t want[2] = {(size_t)job[0].cnt.n_events, (size_t)job[1].cnt.n_events};
-  if (filter) {
-    for (int cam = 0; cam < 2; cam++) {
-      if (int rc = c->rawdec.dec[cam].grow(c, std::max<size_t>(want[cam], 1))) return rc;
-      job[cam].d_dst = c->rawdec.dec[cam], job[cam].cap = c->rawdec.dec[cam].cap;
-    }
-  } else {
-    const int pair = c->cvt_pair;
-    if (int rc = cvt_pair_begin(c, want[0], want[1], &job[0].d_dst, &job[1].d_dst)) return rc;
-    job[0].cap = c->d_cvt_ev[pair][0].cap, job[1].cap = c->d_cvt_ev[pair][1].cap;
-  }
+  auto place = [&](const size_t want[2], DecodedCam dc[2]) { return track_place(c, filter != nullptr, want, dc); };
   const int cam_of[2] = {0, 1};
   AedatResult r[2] = {};
-  if (int rc = aedat_enqueue(c, t_offset_ns, flags, job, cam_of, r)) return rc;
-  HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
-  if (c->prof_on) resolve_profile(c);
-  for (int cam = 0; cam < 2; cam++) {
-    aedat_result_fix(job[cam], flags, &r[cam]);
+  DecodedCam dc[2];
+  if (int rc = aedat_run(c, t_offset_ns, flags, job, cam_of, place, r, dc)) return rc;
+  for (int cam = 0; cam < 2; cam++)
     if (aedat && job[cam].n_bytes) aedat_info_fill(&aedat[cam], r[cam]);
-    info.bad[cam] = r[cam].bad;
-  }
-  if (r[0].bad || r[1].bad) {
-    if (info_out) *info_out = info;
-    return fail(c, ESVIO_FE_EINVAL, "track_aedat: %llu of %u events have a stamp outside [0, 2^32 s); both cameras' states are as they were",
-                r[0].bad + r[1].bad, r[0].events + r[1].events);
-  }
-  // the walker states move only when the whole call succeeds: a filter or track body that fails leaves them as they were
-  auto done = [&](int rc) {
-    for (int cam = 0; cam < 2 && rc == 0; cam++)
+  return track_decoded(c, "track_aedat", "states", dc, filter, motion, pub_this_frame, out, info_out, [&] {
+    for (int cam = 0; cam < 2; cam++)
       if (job[cam].n_bytes) c->aedat.ev_st[cam] = job[cam].st;
-    return rc;
-  };
-  if (filter) {
-    esvio_fe_batch b{};
-    b.left = (const esvio_fe_event*)job[0].d_dst, b.right = (const esvio_fe_event*)job[1].d_dst;
-    b.nL = r[0].events, b.nR = r[1].events, b.space = ESVIO_FE_DEVICE, b.pub_this_frame = pub_this_frame;
-    b.filter = filter, b.motion = motion, b.cur_time_from_batch = 1;
-    return done(track_batch_body(c, "track_aedat", "decode and filter", b, out, info_out));
-  }
-  info.kept[0] = r[0].events, info.kept[1] = r[1].events;
-  if (info_out) *info_out = info;
-  if (!r[0].events) return done(0);  // node:150: an empty left message is not tracked
-  const uint64_t ticks = r[0].last_t;
-  info.cur_time = (double)(uint32_t)(ticks / 1000000000u) + 1e-9 * (double)(uint32_t)(ticks % 1000000000u);
-  const int rc = cvt_pair_track(c, info.cur_time, job[0].d_dst, r[0].events, job[1].d_dst, r[1].events, pub_this_frame, motion, out);
-  info.tracked = rc == 0;
-  if (info_out) *info_out = info;
-  return done(rc);
+  });
 }
 
 // the walk tap (include/esvio_fe_test.h): the host walk alone, no handle, no device
@@ -2522,8 +2535,6 @@ static_assert(bg::kEventBytes == kBagEventBytes, "the walk's wire event is the k
 struct BagCall {  // one call's walk and device work
   bg::Walk st{};   // the state behind the chunk: taken over when the call succeeds
   bg::Out cnt;     // what the counting walk found
-  EventRec* d_dst[2] = {nullptr, nullptr};
-  size_t cap[2] = {0, 0};
   BagResult r[2] = {};
 };
 
@@ -2551,9 +2562,13 @@ int bag_ensure(esvio_fe_ctx* c, size_t n_left, size_t n_right) {
   if (int rc = B.h_pack.grow(c, bytes)) return rc;
   return B.d_pack.grow(c, bytes);
 }
+// esvio_fe_reserve for a handle that decodes bags: the scratch of a chunk of max_left and max_right events
+int bag_reserve(esvio_fe_ctx* c, const size_t events[2]) { return c->bag.used ? bag_ensure(c, events[0], events[1]) : 0; }
+void bag_state_reset(esvio_fe_ctx* c) { c->bag.ev_st = c->bag.side_st = bg::Walk{}; }  // the event and the side walker
 // The gathering walk, the copy, the launch and the copies that bring the result blocks to the host, on the current
-// stream; nothing is waited for.  A camera without an event in the chunk takes no part on the device.
-int bag_enqueue(esvio_fe_ctx* c, const void* bytes, size_t n_bytes, BagCall* b, esvio_fe_bag_message* msgs, size_t msgs_cap) {
+// stream; nothing is waited for.  dc[cam].d, cap: where the camera's records go.  A camera without an event in the chunk
+// takes no part on the device.
+int bag_enqueue(esvio_fe_ctx* c, const void* bytes, size_t n_bytes, BagCall* b, const DecodedCam dc[2], esvio_fe_bag_message* msgs, size_t msgs_cap) {
   esvio_fe_ctx::Bag& B = c->bag;
   hipStream_t s = cur_stream(c);
   const size_t n[2] = {(size_t)b->cnt.n_events[0], (size_t)b->cnt.n_events[1]}, off1 = bag_right_offset(n[0]);
@@ -2573,8 +2588,8 @@ int bag_enqueue(esvio_fe_ctx* c, const void* bytes, size_t n_bytes, BagCall* b, 
   for (int cam = 0; cam < 2; cam++) {
     BagCam& bc = a.cam[cam];
     bc.src = B.d_pack.p + (cam ? off1 : 0), bc.n = (uint32_t)n[cam], bc.tiles = bag_tiles(n[cam]);
-    bc.dst = b->d_dst[cam], bc.dst_cap = (uint32_t)std::min<size_t>(b->cap[cam], 0xffffffffu), bc.res = B.res + cam;
-    if (n[cam] <= b->cap[cam]) stored += n[cam];
+    bc.dst = dc[cam].d, bc.dst_cap = (uint32_t)std::min<size_t>(dc[cam].cap, 0xffffffffu), bc.res = B.res + cam;
+    if (n[cam] <= dc[cam].cap) stored += n[cam];
   }
   {
     ScopedKernel k(c, K_BAG_EMIT, (n[0] + n[1]) * kBagEventBytes + stored * 16);
@@ -2582,6 +2597,21 @@ int bag_enqueue(esvio_fe_ctx* c, const void* bytes, size_t n_bytes, BagCall* b, 
   }
   for (int cam = 0; cam < 2; cam++)
     if (n[cam]) HIPCHK(c, hipMemcpyAsync(&b->r[cam], B.res + cam, sizeof(BagResult), hipMemcpyDeviceToHost, s));
+  return 0;
+}
+// The decode step of a chunk behind its counting walk: place(n, dc) says where each camera's n[cam] records go, the
+// gathering walk and the launch run and are waited for.  b->r[cam], dc[cam]: the result block and the records; b->st:
+// the walker behind the chunk, which the consumer takes over.
+extern "C++" template <class Place>
+int bag_run(esvio_fe_ctx* c, const void* bytes, size_t n_bytes, BagCall* b, esvio_fe_bag_message* msgs, size_t msgs_cap, Place place,
+            DecodedCam dc[2]) {
+  const size_t n[2] = {(size_t)b->cnt.n_events[0], (size_t)b->cnt.n_events[1]};
+  if (int rc = place(n, dc)) return rc;
+  if (int rc = bag_enqueue(c, bytes, n_bytes, b, dc, msgs, msgs_cap)) return rc;
+  HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  if (c->prof_on) resolve_profile(c);
+  for (int cam = 0; cam < 2; cam++)
+    dc[cam].events = n[cam], dc[cam].bad = b->r[cam].bad, dc[cam].sec = b->r[cam].last_sec, dc[cam].nsec = b->r[cam].last_nsec;
   return 0;
 }
 void bag_info_clear(esvio_fe_bag_info* info) {
@@ -2613,7 +2643,7 @@ int esvio_fe_bag_set_topics(esvio_fe_handle c, const esvio_fe_bag_topics* topics
   if (!c) return ESVIO_FE_EINVAL;
   const char* why = nullptr;
   if (!bg::set_topics(topics, &c->bag.topics, &why)) return fail(c, ESVIO_FE_EINVAL, "bag_set_topics: %s", why);
-  c->bag.ev_st = c->bag.side_st = bg::Walk{};
+  bag_state_reset(c);
   return 0;
 }
 
@@ -2622,46 +2652,40 @@ int esvio_fe_decode_bag(esvio_fe_handle c, const void* bytes, size_t n_bytes, ui
   if (!c) return ESVIO_FE_EINVAL;
   bag_info_clear(info);
   if (int rc = bag_args_check(c, "decode_bag", bytes, n_bytes, flags)) return rc;
-  if (dst_space != ESVIO_FE_HOST && dst_space != ESVIO_FE_DEVICE) return fail(c, ESVIO_FE_EINVAL, "decode_bag: bad memory space");
   const size_t room[2] = {dst && dst_cap ? dst_cap[0] : 0, dst && dst_cap ? dst_cap[1] : 0};
-  for (int cam = 0; cam < 2; cam++) {
-    if (room[cam] && !dst[cam]) return fail(c, ESVIO_FE_EINVAL, "decode_bag: dst[%d] is null", cam);
-    if (room[cam] && dst_space == ESVIO_FE_DEVICE && ((uintptr_t)dst[cam] & 15) != 0)
-      return fail(c, ESVIO_FE_EINVAL, "decode_bag: a device dst must be 16-byte aligned");
-  }
+  void* d[2] = {room[0] ? dst[0] : nullptr, room[1] ? dst[1] : nullptr};  // (a dst without room is not looked at)
+  for (int cam = 0; cam < 2; cam++)
+    if (int rc = dst_check(c, "decode_bag", cam ? "dst[1]" : "dst[0]", d[cam], room[cam], dst_space)) return rc;
   if (msgs_cap && !msgs) return fail(c, ESVIO_FE_EINVAL, "decode_bag: msgs is null");
   if (!n_bytes) return 0;
   BagCall b;
   if (int rc = bag_count_walk(c, "decode_bag", bytes, n_bytes, &b)) return rc;
   bag_info_host(info, b.cnt);
   HIPCHK(c, hipSetDevice(c->dev));
-  const size_t n[2] = {(size_t)b.cnt.n_events[0], (size_t)b.cnt.n_events[1]};
-  for (int cam = 0; cam < 2; cam++) {
-    b.cap[cam] = std::min(room[cam], n[cam]);
-    b.d_dst[cam] = room[cam] ? (EventRec*)dst[cam] : nullptr;
-    if (dst_space == ESVIO_FE_HOST && b.cap[cam]) {  // the records behind a host dst
-      if (int rc = c->rawdec.dec[cam].grow(c, b.cap[cam])) return rc;
-      b.d_dst[cam] = c->rawdec.dec[cam];
+  auto place = [&](const size_t n[2], DecodedCam dc[2]) -> int {
+    for (int cam = 0; cam < 2; cam++) {
+      const size_t fit = std::min(room[cam], n[cam]);
+      dc[cam].d = (EventRec*)d[cam];
+      if (dst_space == ESVIO_FE_HOST && fit)  // the records behind a host dst: as many as it has room for
+        if (int rc = dec_scratch(c, cam, fit, &dc[cam])) return rc;
+      dc[cam].cap = fit;
     }
-  }
-  if (int rc = bag_enqueue(c, bytes, n_bytes, &b, msgs, msgs_cap)) return rc;
-  HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
-  if (c->prof_on) resolve_profile(c);
+    return 0;
+  };
+  DecodedCam dc[2];
+  if (int rc = bag_run(c, bytes, n_bytes, &b, msgs, msgs_cap, place, dc)) return rc;
   bag_info_device(info, b);
-  if (b.r[0].bad || b.r[1].bad)
-    return fail(c, ESVIO_FE_EINVAL, "decode_bag: %llu of %zu events have nsec >= 10^9; the walker's state is as it was", b.r[0].bad + b.r[1].bad,
-                n[0] + n[1]);
-  if (n[0] > room[0] || n[1] > room[1])
+  if (dc[0].bad || dc[1].bad)
+    return fail(c, ESVIO_FE_EINVAL, "decode_bag: %llu of %zu events have nsec >= 10^9; the walker's state is as it was", dc[0].bad + dc[1].bad,
+                dc[0].events + dc[1].events);
+  if (dc[0].events > room[0] || dc[1].events > room[1])
     return fail(c, ESVIO_FE_EINVAL, "decode_bag: the chunk holds %zu left and %zu right events, dst has room for %zu and %zu; the walker's state is as it was",
-                n[0], n[1], room[0], room[1]);
+                dc[0].events, dc[1].events, room[0], room[1]);
   if (b.cnt.n_msgs > msgs_cap)
     return fail(c, ESVIO_FE_EINVAL, "decode_bag: the chunk completes %llu event messages, msgs has room for %zu; the walker's state is as it was",
                 (unsigned long long)b.cnt.n_msgs, msgs_cap);
-  if (dst_space == ESVIO_FE_HOST && n[0] + n[1]) {
-    for (int cam = 0; cam < 2; cam++)
-      if (n[cam]) HIPCHK(c, hipMemcpyAsync(dst[cam], b.d_dst[cam], n[cam] * sizeof(EventRec), hipMemcpyDeviceToHost, cur_stream(c)));
-    HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
-  }
+  if (dst_space == ESVIO_FE_HOST)
+    if (int rc = deliver_host(c, 2, d, dc)) return rc;
   c->bag.ev_st = b.st;
   return 0;
 }
@@ -2719,11 +2743,18 @@ int esvio_fe_bag_walk_tap(void* state, size_t state_bytes, const esvio_fe_bag_to
 }
 int esvio_fe_bag_walk_state_bytes(void) { return (int)sizeof(bg::Walk); }
 
-// (the rosbag image stage stands at the end of the file; esvio_fe_reserve sizes its scratch)
+// (the rosbag image stage stands at the end of the file)
 namespace {
-size_t bag_image_slot(size_t payload_bytes);
-int bag_image_ensure(esvio_fe_ctx* c, size_t pix_bytes, size_t n_images, size_t gray_bytes);
+int bag_image_reserve(esvio_fe_ctx* c);
+void bag_image_state_reset(esvio_fe_ctx* c);
+void decode_state_reset(esvio_fe_ctx* c) { raw_state_reset(c), aedat_state_reset(c), bag_state_reset(c), bag_image_state_reset(c); }
 }  // namespace
+
+int esvio_fe_decode_reset(esvio_fe_handle c) {
+  if (!c) return ESVIO_FE_EINVAL;
+  decode_state_reset(c);
+  return 0;
+}
 
 // ---- stream slicing: a record stream cut into fixed-rate windows (the rule: include/esvio_fe.h; the chain: fe_kernels.h)
 namespace {
@@ -3178,68 +3209,40 @@ int feed_push(esvio_fe_ctx* c, const char* who, int cam, const FeedSrc& src, esv
   const esvio_fe_filter_params* flt = f.has_filter ? &f.filter : nullptr;
   EventRec* dst = nullptr;
   uint64_t n_new = 0, rejected = 0, bad = 0;
-  // what the filter reads, when the records have to be made first (raw words)
+  // what the filter reads, when the records have to be made first (a byte source)
   const esvio_fe_event* flt_ev = src.ev;
   const esvio_fe_event_fields* flt_fields = src.fields;
   size_t flt_n = src.n;
   int flt_space = src.space;
+  // a byte source: decoded into the feed's room, or, in front of the filter, into the decode scratch
   RawResult raw_res[2] = {};
+  DecodedCam dc[2];
+  auto put = [&](size_t want, DecodedCam* to) -> int {
+    if (flt) return dec_scratch(c, cam, std::max<size_t>(want, 1), to);
+    if (int rc = feed_room(c, cam, want, &dst)) return rc;
+    to->d = dst, to->cap = fc.buf[fc.cur].cap - (size_t)fc.len;
+    return 0;
+  };
+  const int cam_of[2] = {cam, cam};
   if (src.kind == FEED_RAW) {
-    const size_t wb = raw_word_bytes(src.format);
     RawJob job[2];
     job[0].words = src.words, job[0].n_bytes = src.n_bytes;
-    // one record per word to begin with; when the reduce pass reports more, room is made and the emit launch repeated
-    auto place = [&](size_t want) -> int {
-      if (flt) {
-        if (int rc = raw_ensure(c, cam, src.n_bytes, false, std::max<size_t>(want, 1))) return rc;
-        job[0].d_dst = c->rawdec.dec[cam], job[0].cap = c->rawdec.dec[cam].cap;
-      } else {
-        if (int rc = feed_room(c, cam, want, &dst)) return rc;
-        job[0].d_dst = dst, job[0].cap = fc.buf[fc.cur].cap - (size_t)fc.len;
-      }
-      return 0;
-    };
-    if (int rc = place(src.n_bytes / wb)) return rc;
-    const int cam_of[2] = {cam, cam};
-    RawArgs a;
-    if (int rc = raw_enqueue(c, src.format, src.space, src.t_offset_us, job, cam_of, &a, raw_res)) return rc;
-    HIPCHK(c, hipStreamSynchronize(s));
-    if (!raw_res[0].bad && raw_res[0].events > job[0].cap) {
-      if (int rc = place(raw_res[0].events)) return rc;
-      if (int rc = raw_emit_again(c, &a, job, raw_res)) return rc;
-      HIPCHK(c, hipStreamSynchronize(s));
-    }
-    if (c->prof_on) resolve_profile(c);
-    if (raw_res[0].bad) {
-      feed_info_fill(info, fc, 0, 0, raw_res[0].bad, 0);
-      return fail(c, ESVIO_FE_EINVAL, "%s: %llu of %u events have a stamp outside [0, 2^32 s); nothing was appended, the camera's decoder state is as it was",
-                  who, raw_res[0].bad, raw_res[0].events);
-    }
-    n_new = raw_res[0].events;
-    flt_ev = (const esvio_fe_event*)job[0].d_dst, flt_fields = nullptr, flt_n = raw_res[0].events, flt_space = ESVIO_FE_DEVICE;
+    auto place = [&](const size_t want[2], bool, DecodedCam to[2]) { return put(want[0], &to[0]); };
+    if (int rc = raw_run(c, src.format, src.space, src.t_offset_us, job, cam_of, false, SIZE_MAX, place, raw_res, dc)) return rc;
   }
-  if (src.kind == FEED_AEDAT) {  // the capacity is the host-known count of the chunk's records: nothing is repeated
-    const size_t want = (size_t)ajob[0].cnt.n_events;
-    if (flt) {
-      if (int rc = c->rawdec.dec[cam].grow(c, std::max<size_t>(want, 1))) return rc;
-      ajob[0].d_dst = c->rawdec.dec[cam], ajob[0].cap = c->rawdec.dec[cam].cap;
-    } else {
-      if (int rc = feed_room(c, cam, want, &dst)) return rc;
-      ajob[0].d_dst = dst, ajob[0].cap = fc.buf[fc.cur].cap - (size_t)fc.len;
-    }
-    const int cam_of[2] = {cam, cam};
+  if (src.kind == FEED_AEDAT) {
+    auto place = [&](const size_t want[2], DecodedCam to[2]) { return put(want[0], &to[0]); };
     AedatResult ar[2] = {};
-    if (int rc = aedat_enqueue(c, src.t_offset_us, src.flags, ajob, cam_of, ar)) return rc;
-    HIPCHK(c, hipStreamSynchronize(s));
-    if (c->prof_on) resolve_profile(c);
-    aedat_result_fix(ajob[0], src.flags, &ar[0]);
-    if (ar[0].bad) {
-      feed_info_fill(info, fc, 0, 0, ar[0].bad, 0);
-      return fail(c, ESVIO_FE_EINVAL, "%s: %llu of %u events have a stamp outside [0, 2^32 s); nothing was appended, the camera's state is as it was",
-                  who, ar[0].bad, ar[0].events);
+    if (int rc = aedat_run(c, src.t_offset_us, src.flags, ajob, cam_of, place, ar, dc)) return rc;
+  }
+  if (byte_src) {
+    if (dc[0].bad) {
+      feed_info_fill(info, fc, 0, 0, dc[0].bad, 0);
+      return fail(c, ESVIO_FE_EINVAL, "%s: %llu of %zu events have a stamp outside [0, 2^32 s); nothing was appended, the camera's %s is as it was",
+                  who, dc[0].bad, dc[0].events, src.kind == FEED_RAW ? "decoder state" : "state");
     }
-    n_new = ar[0].events;
-    flt_ev = (const esvio_fe_event*)ajob[0].d_dst, flt_fields = nullptr, flt_n = ar[0].events, flt_space = ESVIO_FE_DEVICE;
+    n_new = dc[0].events;
+    flt_ev = (const esvio_fe_event*)dc[0].d, flt_fields = nullptr, flt_n = dc[0].events, flt_space = ESVIO_FE_DEVICE;
   }
   if (flt) {
     n_new = 0;
@@ -3382,18 +3385,20 @@ int esvio_fe_feed_push_bag(esvio_fe_handle c, const void* bytes, size_t n_bytes,
     return fail(c, ESVIO_FE_EINVAL, "%s: the origin is the first left record; this chunk brings right events and no left one, and none has been appended yet "
                 "(push a longer chunk, or open the feed with an origin); the walker's state is as it was", who);
   HIPCHK(c, hipSetDevice(c->dev));
-  for (int cam = 0; cam < 2; cam++) {
-    if (!n[cam]) continue;
-    if (int rc = c->rawdec.dec[cam].grow(c, n[cam])) return rc;
-    b.d_dst[cam] = c->rawdec.dec[cam], b.cap[cam] = n[cam];
-  }
-  if (int rc = bag_enqueue(c, bytes, n_bytes, &b, nullptr, 0)) return rc;
-  HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
-  if (c->prof_on) resolve_profile(c);
-  if (b.r[0].bad || b.r[1].bad) {
-    for (int cam = 0; cam < 2 && info; cam++) feed_info_fill(&info[cam], f.cam[cam], 0, 0, b.r[cam].bad, 0);
+  auto place = [&](const size_t want[2], DecodedCam dc[2]) -> int {  // the decode scratch: exactly the chunk's records
+    for (int cam = 0; cam < 2; cam++) {
+      if (!want[cam]) continue;
+      if (int rc = dec_scratch(c, cam, want[cam], &dc[cam])) return rc;
+      dc[cam].cap = want[cam];
+    }
+    return 0;
+  };
+  DecodedCam dc[2];
+  if (int rc = bag_run(c, bytes, n_bytes, &b, nullptr, 0, place, dc)) return rc;
+  if (dc[0].bad || dc[1].bad) {
+    for (int cam = 0; cam < 2 && info; cam++) feed_info_fill(&info[cam], f.cam[cam], 0, 0, dc[cam].bad, 0);
     return fail(c, ESVIO_FE_EINVAL, "%s: %llu of %zu events have nsec >= 10^9; nothing was appended, the walker's state is as it was", who,
-                b.r[0].bad + b.r[1].bad, n[0] + n[1]);
+                dc[0].bad + dc[1].bad, n[0] + n[1]);
   }
   // what the left camera's append moves, for the case that the right camera's fails
   FeedCam& fl = f.cam[0];
@@ -3403,7 +3408,7 @@ int esvio_fe_feed_push_bag(esvio_fe_handle c, const void* bytes, size_t n_bytes,
   const bool origin0 = f.origin_known;
   for (int cam = 0; cam < 2; cam++) {
     FeedSrc src{FEED_EVENTS};
-    src.ev = (const esvio_fe_event*)b.d_dst[cam], src.n = n[cam], src.space = ESVIO_FE_DEVICE;
+    src.ev = (const esvio_fe_event*)dc[cam].d, src.n = n[cam], src.space = ESVIO_FE_DEVICE;
     const int rc = feed_push(c, who, cam, src, info ? &info[cam] : nullptr);
     if (rc == 0) continue;
     if (cam == 1) {
@@ -4065,24 +4070,12 @@ int esvio_fe_reserve(esvio_fe_handle c, size_t max_left, size_t max_right, int h
   // the copy of a host source — not the records behind a host dst, which grow on the first call that has one
   if (c->baf.B)
     if (int rc = baf_ensure(c, std::max(max_left, max_right), host_batches != 0, false, false)) return rc;
-  // a handle that decodes raw streams: per camera the scratch of a stream of up to 8 bytes per event (include/esvio_fe.h)
-  if (c->rawdec.used) {
-    const size_t ev[2] = {max_left, max_right};
-    for (int cam = 0; cam < 2; cam++)
-      if (int rc = raw_ensure(c, cam, ev[cam] * 8, host_batches != 0, 0)) return rc;
-  }
-  // a handle that decodes AEDAT streams: per camera the scratch of a chunk of max_events polarity records, each a run
-  if (c->aedat.used) {
-    const size_t ev[2] = {max_left, max_right};
-    for (int cam = 0; cam < 2; cam++)
-      if (int rc = aedat_ensure(c, cam, ev[cam], ev[cam])) return rc;
-  }
-  // a handle that decodes bags: the scratch of a chunk of max_left and max_right events
-  if (c->bag.used)
-    if (int rc = bag_ensure(c, max_left, max_right)) return rc;
-  // a handle that decodes bag images: the scratch of one stereo pair of rgb8 frames of its size
-  if (c->bag.img_used)
-    if (int rc = bag_image_ensure(c, 2 * bag_image_slot((size_t)c->W * c->H * 3), 2, 2 * (size_t)c->W * c->H)) return rc;
+  // a handle that has used an ingest stage: the stage's scratch for chunks of max_left and max_right events
+  const size_t events[2] = {max_left, max_right};
+  if (int rc = raw_reserve(c, events, host_batches != 0)) return rc;
+  if (int rc = aedat_reserve(c, events)) return rc;
+  if (int rc = bag_reserve(c, events)) return rc;
+  if (int rc = bag_image_reserve(c)) return rc;
   // a handle with an open feed: per camera both buffers for 2 * max_events records (the one that holds records is left alone)
   if (c->feed.open) {
     const size_t ev[2] = {max_left, max_right};
@@ -4216,6 +4209,11 @@ int bag_image_ensure(esvio_fe_ctx* c, size_t pix_bytes, size_t n_images, size_t 
   if (int rc = B.d_img.grow(c, bytes)) return rc;
   return gray_bytes ? B.d_gray.grow(c, gray_bytes) : 0;
 }
+// esvio_fe_reserve for a handle that decodes bag images: the scratch of one stereo pair of rgb8 frames of its size
+int bag_image_reserve(esvio_fe_ctx* c) {
+  return c->bag.img_used ? bag_image_ensure(c, 2 * bag_image_slot((size_t)c->W * c->H * 3), 2, 2 * (size_t)c->W * c->H) : 0;
+}
+void bag_image_state_reset(esvio_fe_ctx* c) { c->bag.img_st = bg::Walk{}; }
 // the copy of the gathered bytes and the table, and the launch, on the current stream; nothing is waited for
 int bag_image_enqueue(esvio_fe_ctx* c, size_t table_at, uint32_t n_images, uint32_t width, uint32_t height, uint64_t alg_bytes) {
   esvio_fe_ctx::Bag& B = c->bag;
@@ -4236,7 +4234,7 @@ int esvio_fe_bag_set_image_topics(esvio_fe_handle c, const char* left, const cha
   if (!c) return ESVIO_FE_EINVAL;
   const char* why = nullptr;
   if (!bg::set_image_topics(left, right, &c->bag.topics, &why)) return fail(c, ESVIO_FE_EINVAL, "bag_set_image_topics: %s", why);
-  c->bag.img_st = bg::Walk{};
+  bag_image_state_reset(c);
   return 0;
 }
 

@@ -1,6 +1,8 @@
 // The few "kernels" of the ThreadSanitizer build that do something (tests/hipstub): enough for the host side to have
 // real work — corners appear, LK moves them a little, so tracks live on and rejectWithF_event runs its RANSAC on
 // the helper pool every published frame — and the staged events are really read where the device would read them.
+#include <cstdarg>
+#include <cstdio>
 #include <cstring>
 
 #include "fe_kernels.h"
@@ -113,6 +115,119 @@ void launch_lk(hipStream_t s, const LkArgs& f, const LkArgs* b, float2* back_pts
       back_status[i] = 1;
     }
   }
+  hipstub_stream_end(s);
+}
+
+// ---- drive trace_ingest: the decode chains' result blocks.  The stub launchers leave a result block as the host zeroed
+// it, so no refusal and no repeated emit would ever be walked: the driver sets, per job slot k of a call (0: the call's
+// only or left camera, 1: its right one), what the next emit launches report (hipstub_set_ingest), and every launcher
+// here writes what it was handed into the trace — the carried decoder state as the seed, the chunk, the room — so that a
+// state that moved when it should not have, or did not when it should have, shows in the next call's lines.
+namespace {
+struct IngestPreset {
+  uint32_t events, untimed;
+  unsigned long long bad;
+  long long first_t, last_t;
+  uint32_t st_th, st_flags, st_bx, st_wraps;  // the raw chain's state behind the call
+};
+IngestPreset g_ingest[2];
+struct BafPreset {
+  int on, err;
+  uint32_t kept;
+  int err_at;  // > 0: the err_at-th launch from now reports err, whatever `on` says (the ones in front of it are as they were)
+} g_baf;
+void note(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
+void note(const char* fmt, ...) {
+  char buf[320];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  hipstub_trace_note(buf);
+}
+void raw_note(const char* what, const RawArgs& a) {
+  for (int k = 0; k < 2; k++) {
+    const RawCam& c = a.cam[k];
+    if (!c.tiles) continue;
+    note("  %s[%d] format %d n_bytes %u tiles %u seed th %u flags 0x%x bx %u wraps_base %llu t_offset %lld dst %s dst_cap %u res %s", what, k,
+         a.format, c.n_bytes, c.tiles, c.seed.th_last, c.seed.flags, c.seed.bx, c.wraps_base, c.t_offset, c.dst ? "set" : "null", c.dst_cap,
+         c.res == a.cam[0].res ? "0" : "+");
+  }
+}
+void raw_emit(const char* what, hipStream_t s, const RawArgs& a) {
+  hipstub_trace(what, s);
+  hipstub_stream_begin(s);
+  raw_note(what, a);
+  for (int k = 0; k < 2; k++) {
+    if (!a.cam[k].tiles) continue;
+    const IngestPreset& p = g_ingest[k];
+    RawResult r{};
+    r.events = p.events, r.untimed = p.untimed, r.wraps = p.st_wraps, r.bad = p.bad, r.first_t = p.first_t, r.last_t = p.last_t;
+    r.state = RawXf{p.st_th, p.st_th, p.st_wraps, p.st_flags, p.st_bx, 0, 0, 0};
+    *a.cam[k].res = r;
+  }
+  hipstub_stream_end(s);
+}
+}  // namespace
+extern "C" void hipstub_set_ingest(int k, uint32_t events, uint32_t untimed, unsigned long long bad, long long first_t, long long last_t,
+                                   uint32_t st_th, uint32_t st_flags, uint32_t st_bx, uint32_t st_wraps) {
+  g_ingest[k & 1] = IngestPreset{events, untimed, bad, first_t, last_t, st_th, st_flags, st_bx, st_wraps};
+}
+// the filter's last launch: on = 0 keeps every record (what the launch does until the driver says otherwise)
+extern "C" void hipstub_set_baf(int on, uint32_t kept, int err) { g_baf = BafPreset{on, err, kept, 0}; }
+// ... or only its nth launch from now: one camera's chain of a call that runs both
+extern "C" void hipstub_set_baf_err_at(int nth) { g_baf.err_at = nth; }
+
+void launch_raw_reduce(hipStream_t s, const RawArgs& a) {
+  hipstub_trace("launch_raw_reduce", s);
+  hipstub_stream_begin(s);
+  raw_note("launch_raw_reduce", a);
+  hipstub_stream_end(s);
+}
+void launch_raw_emit(hipStream_t s, const RawArgs& a) { raw_emit("launch_raw_emit", s, a); }
+void launch_trig_emit(hipStream_t s, const RawArgs& a) { raw_emit("launch_trig_emit", s, a); }
+
+void launch_aedat_emit(hipStream_t s, const AedatArgs& a) {
+  hipstub_trace("launch_aedat_emit", s);
+  hipstub_stream_begin(s);
+  for (int k = 0; k < 2; k++) {
+    const AedatCam& c = a.cam[k];
+    if (!c.tiles) continue;
+    note("  launch_aedat_emit[%d] n %u tiles %u n_runs %u keep_invalid %u t_offset %lld dst %s dst_cap %u", k, c.n, c.tiles, c.n_runs,
+         c.keep_invalid, c.t_offset, c.dst ? "set" : "null", c.dst_cap);
+    const IngestPreset& p = g_ingest[k];
+    AedatResult r{};
+    r.events = p.events, r.invalid = p.untimed, r.bad = p.bad, r.first_t = (unsigned long long)p.first_t, r.last_t = (unsigned long long)p.last_t;
+    *c.res = r;
+  }
+  hipstub_stream_end(s);
+}
+
+void launch_bag_emit(hipStream_t s, const BagArgs& a) {
+  hipstub_trace("launch_bag_emit", s);
+  hipstub_stream_begin(s);
+  for (int k = 0; k < 2; k++) {
+    const BagCam& c = a.cam[k];
+    if (!c.tiles) continue;
+    note("  launch_bag_emit[%d] n %u tiles %u dst %s dst_cap %u", k, c.n, c.tiles, c.dst ? "set" : "null", c.dst_cap);
+    const IngestPreset& p = g_ingest[k];
+    BagResult r{};
+    r.bad = p.bad;
+    r.first_sec = (uint32_t)(p.first_t / 1000000000), r.first_nsec = (uint32_t)(p.first_t % 1000000000);
+    r.last_sec = (uint32_t)(p.last_t / 1000000000), r.last_nsec = (uint32_t)(p.last_t % 1000000000);
+    *c.res = r;
+  }
+  hipstub_stream_end(s);
+}
+
+void launch_baf_emit(hipStream_t s, const BafArgs& a) {
+  hipstub_trace("launch_baf_emit", s);
+  hipstub_stream_begin(s);
+  const bool hit = g_baf.err_at > 0 && --g_baf.err_at == 0;
+  a.res->n_kept = hit ? 0 : g_baf.on ? g_baf.kept : a.n;
+  a.res->err = hit ? 1 : g_baf.on ? g_baf.err : 0;
+  a.res->last = EventRec{};
+  a.res->last.sec = 1700000000u, a.res->last.nsec = 5000u;
   hipstub_stream_end(s);
 }
 
