@@ -393,6 +393,8 @@ int esvio_fe_reset(esvio_fe_handle c) {
   c->pend_right.active = false;
   HIPCHK(c, hipMemsetAsync(c->L2, 0, (size_t)2 * c->P * 16, cur_stream(c)));
   HIPCHK(c, hipMemsetAsync(c->S2, 0, (size_t)2 * c->P * 16, cur_stream(c)));
+  if (c->evimg.on)  // the event images: zero (the setting is kept)
+    if (int rc = evimg_zero(c, true)) return rc;
   if (int rc = baf_clear(c)) return rc;  // the background-activity filter's planes: none everywhere
   if (int rc = hot_clear(c)) return rc;  // hot-pixel learning: nothing counted (the address filter and the mask are settings: kept)
   decode_state_reset(c);  // the raw-stream and trigger decoders, the AEDAT and bag walkers (the topics are settings: kept)
@@ -413,6 +415,7 @@ static int create_sae_stereo(esvio_fe_ctx* c, const esvio_fe_event* left, size_t
   const EventRec *dL, *dR;
   if (int rc = stage_events(c, left, nL, right, nR, space, &dL, &dR)) return rc;
   HIPCHK(c, hipMemsetAsync(c->d_rejected, 0, 8, cur_stream(c)));
+  c->evimg.fresh_cams = 0;  // (a stage call accumulates into the event images)
   if (int rc = sae_update(c, dL, (uint32_t)nL, dR, (uint32_t)nR, mc)) return rc;
   unsigned long long rej = 0;
   HIPCHK(c, hipMemcpyAsync(&rej, c->d_rejected, 8, hipMemcpyDeviceToHost, cur_stream(c)));
@@ -3577,6 +3580,101 @@ int esvio_fe_set_detector(esvio_fe_handle c, int detector, int fast_barrier) {
   return 0;
 }
 
+// ---- event images (the rule: include/esvio_fe.h "event images"; the kernels: fe_kernels.h; the update: evimg_update)
+int esvio_fe_set_event_images(esvio_fe_handle c, int on) {
+  if (!c) return ESVIO_FE_EINVAL;
+  if (!c->inflight.empty() || !c->announced.empty())
+    return fail(c, ESVIO_FE_EINVAL, "esvio_fe_set_event_images while batches are announced");
+  HIPCHK(c, hipSetDevice(c->dev));
+  if (int rc = launcher_drain(c)) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream2));
+  HIPCHK(c, hipStreamSynchronize(c->stream3));
+  HIPCHK(c, hipStreamSynchronize(c->stream4));
+  if (c->stream6) HIPCHK(c, hipStreamSynchronize(c->stream6));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  esvio_fe_ctx::Evimg& E = c->evimg;
+  E.on = false;
+  E.fresh_cams = 0;
+  E.wstream[0] = E.wstream[1] = nullptr;
+  if (!on) {
+    for (int cam = 0; cam < 2; cam++) {
+      E.marks[cam].release();
+      E.img[cam].release();
+      E.written[cam] = Event();
+    }
+    E.canvas.release();
+    return 0;
+  }
+  // everything the feature needs, pixel-proportional: 2 x (4 + 3) bytes per pixel and the getter's canvas, 6 more
+  E.groups = (c->P + 3u) / 4u;
+  for (int cam = 0; cam < 2; cam++) {
+    if (int rc = E.marks[cam].alloc(c, (size_t)E.groups * 4)) return rc;
+    if (int rc = E.img[cam].alloc(c, (size_t)E.groups * 3)) return rc;
+    if (!E.written[cam]) HIPCHK(c, E.written[cam].create());
+    HIPCHK(c, hipMemsetAsync(E.marks[cam], 0, (size_t)E.groups * 16, c->stream));
+    HIPCHK(c, hipMemsetAsync(E.img[cam], 0, (size_t)E.groups * 12, c->stream));
+  }
+  if (int rc = E.canvas.alloc(c, (size_t)c->P * 6)) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  E.on = true;
+  return 0;
+}
+
+int esvio_fe_clear_event_images(esvio_fe_handle c) {
+  if (!c) return ESVIO_FE_EINVAL;
+  if (!c->evimg.on) return fail(c, ESVIO_FE_EINVAL, "clear_event_images: esvio_fe_set_event_images is off");
+  HIPCHK(c, hipSetDevice(c->dev));
+  return evimg_zero(c);
+}
+
+// a getter's argument checks, then the wait for the last write to the cameras' images on whichever stream made it
+static int evimg_get_ready(esvio_fe_ctx* c, const char* who, int cam0, int cam1, const uint8_t* dst, int space) {
+  if (!c->evimg.on) return fail(c, ESVIO_FE_EINVAL, "%s: esvio_fe_set_event_images is off", who);
+  if (cam0 < 0 || cam1 > 1) return fail(c, ESVIO_FE_EINVAL, "%s: cam must be 0 or 1", who);
+  if (!dst) return fail(c, ESVIO_FE_EINVAL, "%s: dst is null", who);
+  if (space != ESVIO_FE_HOST && space != ESVIO_FE_DEVICE) return fail(c, ESVIO_FE_EINVAL, "%s: bad memory space %d", who, space);
+  HIPCHK(c, hipSetDevice(c->dev));
+  for (int cam = cam0; cam <= cam1; cam++)
+    if (c->evimg.wstream[cam]) HIPCHK(c, hipEventSynchronize(c->evimg.written[cam]));
+  return 0;
+}
+
+int esvio_fe_get_event_image(esvio_fe_handle c, int cam, uint8_t* dst, int space) {
+  if (!c) return ESVIO_FE_EINVAL;
+  if (int rc = evimg_get_ready(c, "get_event_image", cam, cam, dst, space)) return rc;
+  // one dense copy on the null stream (none of the handle's: they are non-blocking streams), waited for
+  HIPCHK(c, hipMemcpyAsync(dst, c->evimg.img[cam], (size_t)c->P * 3, space == ESVIO_FE_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, nullptr));
+  HIPCHK(c, hipStreamSynchronize(nullptr));
+  return 0;
+}
+
+int esvio_fe_get_event_canvas(esvio_fe_handle c, uint8_t* dst, int space) {
+  if (!c) return ESVIO_FE_EINVAL;
+  if (int rc = evimg_get_ready(c, "get_event_canvas", 0, 1, dst, space)) return rc;
+  esvio_fe_ctx::Evimg& E = c->evimg;
+  // composed at getter time: device memory takes it directly, host memory one dense copy of the scratch
+  uint8_t* canvas = space == ESVIO_FE_DEVICE ? dst : E.canvas.p;
+  launch_evimg_canvas(nullptr, (const uint8_t*)E.img[0].p, (const uint8_t*)E.img[1].p, c->W, c->H, canvas);
+  if (space == ESVIO_FE_HOST) HIPCHK(c, hipMemcpyAsync(dst, canvas, (size_t)c->P * 6, hipMemcpyDeviceToHost, nullptr));
+  HIPCHK(c, hipStreamSynchronize(nullptr));
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+int esvio_fe_event_image_kernel_stats(esvio_fe_handle c, int which, double* total_ms, uint64_t* launches, uint64_t* alg_bytes) {
+  if (!c || which < 0 || which > 1) return ESVIO_FE_EINVAL;
+  HIPCHK(c, hipSetDevice(c->dev));
+  HIPCHK(c, hipStreamSynchronize(c->stream4));
+  if (c->stream6) HIPCHK(c, hipStreamSynchronize(c->stream6));
+  HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  resolve_profile(c);
+  const KStat& s = c->stats[K_EVIMG_MARK + which];
+  if (total_ms) *total_ms = s.ms;
+  if (launches) *launches = s.launches;
+  if (alg_bytes) *alg_bytes = s.bytes;
+  return 0;
+}
+
 int esvio_fe_features_to_track_fast(esvio_fe_handle c, const uint8_t* img, int space, int barrier, int max_corners,
                                     const uint8_t* mask, float* out_xy, int32_t* out_score, int32_t* n_out,
                                     int32_t* n_candidates) {
@@ -3928,6 +4026,7 @@ static int set_next_batch_impl(esvio_fe_handle c, double next_cur_time, const es
   if (nL == 0 || !left || (nR && !right)) return fail(c, ESVIO_FE_EINVAL, "bad next batch");
   if (space != ESVIO_FE_HOST && space != ESVIO_FE_DEVICE) return ESVIO_FE_EINVAL;
   if (c->ext_right_pending) return fail(c, ESVIO_FE_EINVAL, "not with an imported right image");
+  if (c->evimg.on) return fail(c, ESVIO_FE_EINVAL, "not while esvio_fe_set_event_images is on: the event images do not follow announced batches");
   if ((int)(c->announced.size() + c->inflight.size()) >= 2 * kPrefetchDepth)
     return fail(c, ESVIO_FE_EINVAL, "at most %d batches can be announced and not yet tracked", 2 * kPrefetchDepth);
   Batch b;

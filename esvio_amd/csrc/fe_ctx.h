@@ -105,6 +105,10 @@ struct PhaseClock {
   }
 };
 
+// the event images' two timer slots behind the ingest range: esvio_fe_event_image_kernel_stats reads them, the stage
+// and ingest tables (whose ends tests pin) stay as they are
+enum { K_EVIMG_MARK = K_INGEST_COUNT, K_EVIMG_EMIT, K_ALL_COUNT };
+
 struct KStat {
   double ms = 0;
   uint64_t launches = 0;
@@ -449,7 +453,7 @@ struct esvio_fe_ctx {
 
   // ---- profiling
   bool prof_on = false;
-  KStat stats[K_INGEST_COUNT];
+  KStat stats[K_ALL_COUNT];
   std::vector<ProfRec> pending;
   std::vector<Event> ev_pool;
 
@@ -643,6 +647,23 @@ struct esvio_fe_ctx {
     } cam[2];
     std::vector<uint64_t> cuts;
   } feed;
+
+  // ---- esvio_fe_set_event_images: detector.cur_event_mat_left/right (include/esvio_fe.h has the rule, fe_kernels.h the
+  // chain).  A SETTING (it survives esvio_fe_reset).  Everything is pixel-proportional and allocated by set(1), released
+  // by set(0): per camera the mark plane (one word per pixel) and the image (3 bytes per pixel), both padded to `groups`
+  // groups of four pixels, and the canvas scratch of the getter.  fresh_cams: the cameras whose image the running TRACK
+  // call rewrites (set by take_batch, cleared as the camera's emit is enqueued); 0 in a stage call: accumulate.
+  // written[cam]: recorded behind every write to the camera's image on wstream[cam], whichever stream made it; the
+  // getters wait for it and copy on none of the handle's streams.
+  struct Evimg {
+    bool on = false;
+    uint32_t groups = 0;
+    DevBuf<uint32_t> marks[2], img[2];
+    DevBuf<uint8_t> canvas;
+    Event written[2];
+    hipStream_t wstream[2] = {nullptr, nullptr};
+    int fresh_cams = 0;
+  } evimg;
 };
 
 namespace esvio {

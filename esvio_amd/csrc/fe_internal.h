@@ -36,6 +36,12 @@ McParams make_mc_params(const esvio_fe_motion* m);
 int sae_update(esvio_fe_ctx* c, const EventRec* evL, uint32_t nL, const EventRec* evR, uint32_t nR,
                const McParams* mc = nullptr, double2* L2 = nullptr, double2* S2 = nullptr, int arc_set = -1,
                bool* arc_marked = nullptr);
+// esvio_fe_set_event_images is on: sae_update of the handle's own planes ends in evimg_update — the batch into the
+// event images, the cameras of evimg.fresh_cams rewritten, the others accumulated; with no events it still rewrites
+// the fresh ones (a track call whose update is skipped).  evimg_zero: both images zero, on the current stream
+// (marks_too: esvio_fe_reset's, behind a call that may have failed half way)
+int evimg_update(esvio_fe_ctx* c, const EventRec* evL, uint32_t nL, const EventRec* evR, uint32_t nR, const McParams* mc);
+int evimg_zero(esvio_fe_ctx* c, bool marks_too = false);
 int radix_sort_pairs(esvio_fe_ctx* c, uint32_t n, int passes, int bits, bool booked = true);
 // ... of other buffers than the handle's keys[] / vals[] / hist; n_dev (optional): the count is *n_dev, read on the
 // device, and n its upper bound (launch_radix_pass)

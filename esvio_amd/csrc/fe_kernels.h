@@ -800,6 +800,34 @@ struct ImageArgs {
 };
 void launch_image_emit(hipStream_t s, const ImageArgs& a);
 
+// ---- event images: detector.cur_event_mat_left/right (esvio_fe_set_event_images) ----
+// include/esvio_fe.h holds the rule: per camera the LAST event of the call at every pixel decides its colour.  Two
+// launches behind the SAE update of the handle's own planes, on its stream:
+//   k_evimg_mark  one lane per event, both cameras in one grid: atomicMax(marks[cam][pixel], ((k + 1) << 1) | polarity),
+//                 k the event's index in its camera's array (< 2^31 - 1: every entry point refuses larger batches).  The
+//                 maximum does not depend on the order in which the lanes arrive, so the word ends as the pixel's last
+//                 event in stream order, exactly.  For a batch of more than one event per pixel the lanes walk the stream from its end and read the word first: an
+//                 event that finds a later one's key there skips its atomic (each atomic is a 64-byte request at the
+//                 memory side, whose rate bounds the kernel; KERNELS.md "Event images").  The pixel: the event's own (kEvimgPixOwn), or the one the
+//                 motion-compensated update writes it at — k_mc_warp's warp_xy[i] where the tiled update has filled it
+//                 (kEvimgPixWarp), mc_pixel as k_sae_keys<true> computes it in the sort form (kEvimgPixMc).  An
+//                 out-of-sensor event is skipped as the update skips it; the warp drops none (mc_warp keeps the event's
+//                 own pixel where the warped one leaves the sensor).
+//   k_evimg_emit  one lane per FOUR pixels: four marks in, three dwords of (B, G, R) bytes out, the marks it found set
+//                 back to zero — so the planes are zero between calls and no call clears them.  FRESH (track calls):
+//                 every pixel is written, colour or zero.  Otherwise (stage calls): only marked pixels are merged into
+//                 the bytes that are there.  marks and images are padded to a multiple of four pixels (`groups` of
+//                 them); the caller sees the first width*height*3 bytes, dense.
+//   k_evimg_canvas  hconcat(left, right) into a scratch of the getter's (esvio_fe_get_event_canvas), one lane per pixel.
+// They are booked in two timer slots of their own (esvio_fe_ctx::evimg.stats), outside the stage and the ingest tables.
+enum { kEvimgPixOwn = 0, kEvimgPixWarp = 1, kEvimgPixMc = 2 };
+void launch_evimg_mark(hipStream_t s, const EventRec* evL, uint32_t nL, const EventRec* evR, uint32_t nR, int W, int H,
+                       uint32_t* marksL, uint32_t* marksR, int pix, const uint32_t* warp_xy, const McParams* mc);
+// marks1 == nullptr: one camera (marks0 / img0)
+void launch_evimg_emit(hipStream_t s, uint32_t* marks0, uint32_t* img0, uint32_t* marks1, uint32_t* img1, uint32_t groups,
+                       bool fresh);
+void launch_evimg_canvas(hipStream_t s, const uint8_t* left, const uint8_t* right, int W, int H, uint8_t* canvas);
+
 // ---- stream slicing: a record stream cut into fixed-rate windows (esvio_fe_slice_events) ----
 // include/esvio_fe.h holds the rule.  An event's window is m_i = max(m_{i-1}, c_i), c_i = the boundaries at or below its
 // stamp: a prefix MAXIMUM, associative and commutative, so a tile of events is summarised by one number and the chain

@@ -5910,4 +5910,126 @@ void launch_image_emit(hipStream_t s, const ImageArgs& a) {
 // (Behind every other kernel of the file on purpose: appended here, the image stage moves no track-path kernel's place in
 // the code object.)
 
+// ============================================================================ event images
+// detector.cur_event_mat_left/right (event_detector.cc:145-146, :164-165, :208-209, :226-227): include/esvio_fe.h
+// "event images" holds the rule, fe_kernels.h the chain.  (Behind the image stage for the same reason.)
+template <int PIX, bool SKIP>
+__global__ __launch_bounds__(256) void k_evimg_mark(const uint4* __restrict__ evL, uint32_t nL,
+                                                    const uint4* __restrict__ evR, uint32_t nR, int W, int H,
+                                                    uint32_t* __restrict__ marksL, uint32_t* __restrict__ marksR,
+                                                    const uint32_t* __restrict__ warp_xy, McParams mc) {
+  // Every global atomic leaves L2 as a 64-byte request of its own, and the memory side's atomic rate bounds the kernel
+  // (~20 G atomics/s: 330 us for the 6.7 M events of a C5 batch).  SKIP, for batches of more than one event per pixel: the
+  // stream is walked from its END — workgroups start roughly in grid order, so the late events, the ones that decide, are
+  // marked first — and an earlier event that finds a larger key already there (a relaxed agent-scope load: the words only
+  // grow during the launch, so a stale value costs an atomic that changes nothing, never a wrong result) skips its
+  // atomic: 180 us at C5.  Sparser batches skip little and pay the dependent load (+ 1.5-3 us at C1 and C3): stream order, no load.
+  const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+  if (j >= nL + nR) return;
+  const uint32_t i = SKIP ? nL + nR - 1u - j : j;
+  const bool right = i >= nL;
+  const uint32_t k = right ? i - nL : i;  // the event's index in its own array
+  const uint4 e = right ? evR[k] : evL[i];
+  uint32_t xy = e.x;
+  if ((xy & 0xffffu) >= (uint32_t)W || (xy >> 16) >= (uint32_t)H) return;  // the SAE update skips it
+  if (PIX == kEvimgPixWarp) xy = warp_xy[i];                               // (k_mc_warp's, of an in-sensor event: in the sensor)
+  if (PIX == kEvimgPixMc) xy = mc_pixel(mc, mc_batch(mc, evL), W, H, e);   // (what k_sae_keys<true> computes)
+  const uint32_t x = xy & 0xffffu, y = xy >> 16;
+  if (x >= (uint32_t)W || y >= (uint32_t)H) return;
+  uint32_t* const word = (right ? marksR : marksL) + (y * (uint32_t)W + x);
+  const uint32_t key = ((k + 1u) << 1) | ((e.w & 0xffu) ? 1u : 0u);
+  if (!SKIP || __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < key) atomicMax(word, key);
+}
+
+namespace {
+template <int PIX>
+void launch_evimg_mark_pix(hipStream_t s, const EventRec* evL, uint32_t nL, const EventRec* evR, uint32_t nR, int W, int H,
+                           uint32_t* marksL, uint32_t* marksR, const uint32_t* warp_xy, const McParams& m) {
+  const uint32_t n = nL + nR;
+  const dim3 grid((n + 255u) / 256u), block(256);
+  // more than one event per pixel of the cameras that have events: the form that skips (measured: the comment above)
+  const bool skip = n > (uint32_t)W * (uint32_t)H * ((nL ? 1u : 0u) + (nR ? 1u : 0u));
+  if (skip)
+    launch_k(k_evimg_mark<PIX, true>, grid, block, 0, s, (const uint4*)evL, nL, (const uint4*)evR, nR, W, H, marksL, marksR,
+             warp_xy, m);
+  else
+    launch_k(k_evimg_mark<PIX, false>, grid, block, 0, s, (const uint4*)evL, nL, (const uint4*)evR, nR, W, H, marksL, marksR,
+             warp_xy, m);
+}
+}  // namespace
+
+void launch_evimg_mark(hipStream_t s, const EventRec* evL, uint32_t nL, const EventRec* evR, uint32_t nR, int W, int H,
+                       uint32_t* marksL, uint32_t* marksR, int pix, const uint32_t* warp_xy, const McParams* mc) {
+  if (!(nL + nR)) return;
+  McParams m = McParams();
+  if (mc) m = *mc;
+  if (pix == kEvimgPixWarp)
+    launch_evimg_mark_pix<kEvimgPixWarp>(s, evL, nL, evR, nR, W, H, marksL, marksR, warp_xy, m);
+  else if (pix == kEvimgPixMc)
+    launch_evimg_mark_pix<kEvimgPixMc>(s, evL, nL, evR, nR, W, H, marksL, marksR, warp_xy, m);
+  else
+    launch_evimg_mark_pix<kEvimgPixOwn>(s, evL, nL, evR, nR, W, H, marksL, marksR, warp_xy, m);
+}
+
+// Four pixels per lane: four marks in (one dwordx4), twelve image bytes out (three dwords), the marks back to zero where
+// one was set.  A pixel's three bytes in the 96 bits of its group: pixel j at bits [24 j, 24 j + 24), B lowest.
+template <bool FRESH>
+__global__ __launch_bounds__(256) void k_evimg_emit(uint32_t* __restrict__ marks0, uint32_t* __restrict__ marks1,
+                                                    uint32_t* __restrict__ img0, uint32_t* __restrict__ img1,
+                                                    uint32_t groups) {
+  const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+  if (g >= groups) return;
+  uint32_t* const marks = blockIdx.y ? marks1 : marks0;
+  uint32_t* const img = (blockIdx.y ? img1 : img0) + (size_t)g * 3;
+  const uint4 m = ((const uint4*)marks)[g];
+  const bool any = (m.x | m.y | m.z | m.w) != 0;
+  if (!FRESH && !any) return;
+  // (255, 0, 0) for ON, (0, 0, 255) for OFF, as 24-bit little-endian values; `set`: all ones where the pixel is marked
+  const uint32_t mk[4] = {m.x, m.y, m.z, m.w};
+  uint32_t v[4], set[4];
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    set[j] = mk[j] ? 0xffffffu : 0u;
+    v[j] = mk[j] ? ((mk[j] & 1u) ? 0x0000ffu : 0xff0000u) : 0u;
+  }
+  uint32_t w0 = v[0] | v[1] << 24, w1 = v[1] >> 8 | v[2] << 16, w2 = v[2] >> 16 | v[3] << 8;
+  if (!FRESH) {
+    const uint32_t s0 = set[0] | set[1] << 24, s1 = set[1] >> 8 | set[2] << 16, s2 = set[2] >> 16 | set[3] << 8;
+    w0 |= img[0] & ~s0;
+    w1 |= img[1] & ~s1;
+    w2 |= img[2] & ~s2;
+  }
+  img[0] = w0;
+  img[1] = w1;
+  img[2] = w2;
+  if (any) ((uint4*)marks)[g] = make_uint4(0, 0, 0, 0);
+}
+
+void launch_evimg_emit(hipStream_t s, uint32_t* marks0, uint32_t* img0, uint32_t* marks1, uint32_t* img1, uint32_t groups,
+                       bool fresh) {
+  const int ncam = marks1 ? 2 : 1;
+  const dim3 grid((groups + 255u) / 256u, ncam), block(256);
+  if (fresh)
+    launch_k(k_evimg_emit<true>, grid, block, 0, s, marks0, marks1, img0, img1, groups);
+  else
+    launch_k(k_evimg_emit<false>, grid, block, 0, s, marks0, marks1, img0, img1, groups);
+}
+
+// hconcat(left, right) (feature_tracker.cpp:1107): one lane per canvas pixel
+__global__ __launch_bounds__(256) void k_evimg_canvas(const uint8_t* __restrict__ left, const uint8_t* __restrict__ right,
+                                                      int W, int H, uint8_t* __restrict__ canvas) {
+  const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+  if (p >= 2u * (uint32_t)W * (uint32_t)H) return;
+  const uint32_t y = p / (2u * (uint32_t)W), x = p - y * 2u * (uint32_t)W;
+  const uint8_t* src = (x < (uint32_t)W ? left + ((size_t)y * W + x) * 3 : right + ((size_t)y * W + (x - W)) * 3);
+  uint8_t* dst = canvas + (size_t)p * 3;
+  dst[0] = src[0];
+  dst[1] = src[1];
+  dst[2] = src[2];
+}
+
+void launch_evimg_canvas(hipStream_t s, const uint8_t* left, const uint8_t* right, int W, int H, uint8_t* canvas) {
+  launch_k(k_evimg_canvas, dim3((2u * (uint32_t)W * (uint32_t)H + 255u) / 256u), dim3(256), 0, s, left, right, W, H, canvas);
+}
+
 }  // namespace esvio

@@ -228,10 +228,80 @@ int radix_sort_pairs(esvio_fe_ctx* c, const SortBufs& b, uint32_t n, int passes,
   return cur;
 }
 
+// ---------------------------------------------------------------- event images (esvio_fe_set_event_images)
+// a camera's image (and its mark plane) is about to be written on stream s: behind its last writer, if that was
+// another stream (a plain call's right camera runs on the stereo stream)
+static int evimg_order(esvio_fe_ctx* c, int cams, hipStream_t s) {
+  esvio_fe_ctx::Evimg& E = c->evimg;
+  for (int cam = 0; cam < 2; cam++)
+    if ((cams >> cam & 1) && E.wstream[cam] && E.wstream[cam] != s) HIPCHK(c, hipStreamWaitEvent(s, E.written[cam], 0));
+  return 0;
+}
+static int evimg_written(esvio_fe_ctx* c, int cams, hipStream_t s) {
+  esvio_fe_ctx::Evimg& E = c->evimg;
+  for (int cam = 0; cam < 2; cam++)
+    if (cams >> cam & 1) {
+      HIPCHK(c, hipEventRecord(E.written[cam], s));
+      E.wstream[cam] = s;
+    }
+  return 0;
+}
+
+int evimg_zero(esvio_fe_ctx* c, bool marks_too) {
+  esvio_fe_ctx::Evimg& E = c->evimg;
+  hipStream_t s = cur_stream(c);
+  if (int rc = evimg_order(c, 3, s)) return rc;
+  for (int cam = 0; cam < 2; cam++) {
+    HIPCHK(c, hipMemsetAsync(E.img[cam], 0, (size_t)E.groups * 12, s));
+    // (the emit leaves the mark planes zero; a call that failed between its mark and its emit may not have)
+    if (marks_too) HIPCHK(c, hipMemsetAsync(E.marks[cam], 0, (size_t)E.groups * 16, s));
+  }
+  E.fresh_cams = 0;
+  return evimg_written(c, 3, s);
+}
+
+// The batch a call's SAE update consumes -> the event images, on the update's stream, behind it (the tiled update has
+// filled d_warp by then).  The cameras of E.fresh_cams are rewritten (a track call's: zero, then the rule), the others
+// that have events accumulate (a stage call's).  Reads the event arrays on the stream the update reads them on, so
+// whatever keeps them alive for the update keeps them alive for this.
+int evimg_update(esvio_fe_ctx* c, const EventRec* evL, uint32_t nL, const EventRec* evR, uint32_t nR, const McParams* mc) {
+  esvio_fe_ctx::Evimg& E = c->evimg;
+  const uint32_t n = nL + nR;
+  const int fresh = E.fresh_cams, acc = ((nL ? 1 : 0) | (nR ? 2 : 0)) & ~fresh;
+  E.fresh_cams = 0;
+  if (!(fresh | acc)) return 0;
+  hipStream_t s = cur_stream(c);
+  if (int rc = evimg_order(c, fresh | acc, s)) return rc;
+  if (n) {
+    const bool warped = mc && mc->enabled;
+    ScopedKernel k(c, K_EVIMG_MARK, (uint64_t)n * (warped && c->tiled ? 24 : 20));  // the record (+ its warped pixel) in, one atomic word out
+    launch_evimg_mark(s, evL, nL, evR, nR, c->W, c->H, E.marks[0], E.marks[1],
+                      !warped ? kEvimgPixOwn : c->tiled ? kEvimgPixWarp : kEvimgPixMc, c->d_warp, mc);
+  }
+  for (int form = 0; form < 2; form++) {
+    const int cams = form ? acc : fresh;
+    if (!cams) continue;
+    const int c0 = cams & 1 ? 0 : 1, ncam = cams == 3 ? 2 : 1;
+    ScopedKernel k(c, K_EVIMG_EMIT, (uint64_t)E.groups * 4 * (4 + 3) * ncam);  // the marks in, the bytes out (marks set: + 4 B back)
+    launch_evimg_emit(s, E.marks[c0], E.img[c0], ncam == 2 ? E.marks[1].p : nullptr, ncam == 2 ? E.img[1].p : nullptr,
+                      E.groups, form == 0);
+  }
+  return evimg_written(c, fresh | acc, s);
+}
+
 // arc_set >= 0: this batch's Arc* pass will run into candidate set arc_set; *arc_marked tells
 // whether the update has set that set's touched flags on its way (else run_arc does it)
+static int sae_update_planes(esvio_fe_ctx* c, const EventRec* evL, uint32_t nL, const EventRec* evR, uint32_t nR,
+                             const McParams* mc, double2* L2, double2* S2, int arc_set, bool* arc_marked);
 int sae_update(esvio_fe_ctx* c, const EventRec* evL, uint32_t nL, const EventRec* evR,
                uint32_t nR, const McParams* mc, double2* L2, double2* S2, int arc_set, bool* arc_marked) {
+  if (int rc = sae_update_planes(c, evL, nL, evR, nR, mc, L2, S2, arc_set, arc_marked)) return rc;
+  // the handle's own planes: the event images follow (the time-slice entry points' scratch pair writes none)
+  return c->evimg.on && !L2 && !S2 ? evimg_update(c, evL, nL, evR, nR, mc) : 0;
+}
+
+static int sae_update_planes(esvio_fe_ctx* c, const EventRec* evL, uint32_t nL, const EventRec* evR, uint32_t nR,
+                             const McParams* mc, double2* L2, double2* S2, int arc_set, bool* arc_marked) {
   const uint32_t n = nL + nR;
   if (!n) return 0;
   if (!L2) L2 = c->L2;  // (other planes: the scratch pair of the time-slice entry points)

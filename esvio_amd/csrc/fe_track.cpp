@@ -654,6 +654,8 @@ struct TrackCall {
       const bool split = c->cam_split_enabled && c->tiled && render_cam_ok(c) && !motion && !c->ext_sae_pending && !c->ext_right_pending &&
                          nL && nR && c->announced.empty() && c->inflight.empty() && !c->lazy_new && !c->chain_valid && !c->spec_valid &&
                          (staged || space == ESVIO_FE_DEVICE);
+      // the event images (esvio_fe_set_event_images): this call rewrites both, each behind its camera's update
+      if (c->evimg.on) c->evimg.fresh_cams = split ? 1 : 3;
       if (staged) {
         // not announced: the helpers and this thread stage the chunks together, the DMA of group k runs
         // under the memcpy of group k+1
@@ -688,6 +690,7 @@ struct TrackCall {
         {
           StreamScope on_stereo_stream(stereo_stream(c));
           HIPCHK(c, hipStreamWaitEvent(stereo_stream(c), c->ev_sae_left, 0));  // (the partition scratch is the left chain's until then)
+          if (c->evimg.on) c->evimg.fresh_cams = 2;
           if (int rc = sae_update(c, nullptr, 0, dR, (uint32_t)nR)) return rc;
           build_lk_images(c, c->cur_time, 2, c->slot_curL, c->slot_curR, c->raw_cur);
           HIPCHK(c, hipEventRecord(c->ev_right_ready, stereo_stream(c)));
@@ -701,6 +704,8 @@ struct TrackCall {
         // time-sliced over several GPUs); the events are still needed below for Arc*
         if (motion) return fail(c, ESVIO_FE_EINVAL, "time-sliced SAE update has no motion-compensated form");
         c->ext_sae_pending = false;
+        if (c->evimg.on)  // (both cameras' updates are skipped: both images zero)
+          if (int rc = evimg_update(c, nullptr, 0, nullptr, 0, nullptr)) return rc;
       } else if (motion) {
         const McParams mc = make_mc_params(motion);
         if (int rc = sae_update(c, dL, (uint32_t)nL, dR, (uint32_t)nR, &mc)) return rc;

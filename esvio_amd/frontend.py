@@ -322,6 +322,7 @@ ABI_SYMBOLS = [
     "esvio_fe_sae_plane_doubles", "esvio_fe_sae_slice_apply", "esvio_fe_sae_slice_commit",
     "esvio_fe_sae_slice_last", "esvio_fe_sae_to_time_surface", "esvio_fe_set_address_filter", "esvio_fe_set_auto_exchange",
     "esvio_fe_set_detector", "esvio_fe_set_pixel_mask",
+    "esvio_fe_set_event_images", "esvio_fe_clear_event_images", "esvio_fe_get_event_image", "esvio_fe_get_event_canvas",
     "esvio_fe_set_host_threads", "esvio_fe_set_launch_thread", "esvio_fe_set_lazy_new_stereo",
     "esvio_fe_set_next_batch", "esvio_fe_set_next_batch_mc", "esvio_fe_slice_events", "esvio_fe_slice_flush",
     "esvio_fe_slice_reset", "esvio_fe_track_batch", "esvio_fe_track_event", "esvio_fe_track_event_fields",
@@ -342,7 +343,7 @@ TEST_SYMBOLS = [
     "esvio_fe_slice_tile_events", "esvio_fe_stage_kernel_count", "esvio_fe_stream",
     "esvio_fe_aedat_tile_events", "esvio_fe_ingest_kernel_count", "esvio_fe_aedat_walk_tap", "esvio_fe_aedat_walk_state_bytes",
     "esvio_fe_bag_tile_events", "esvio_fe_bag_walk_tap", "esvio_fe_bag_walk_state_bytes",
-    "esvio_fe_bag_image_walk_tap", "esvio_fe_image_tile_pixels",
+    "esvio_fe_bag_image_walk_tap", "esvio_fe_image_tile_pixels", "esvio_fe_event_image_kernel_stats",
 ]
 
 LATENCY_PHASES = 16
@@ -433,6 +434,11 @@ def load_library(build_if_missing=True):
     L.esvio_fe_fast_corners.argtypes = [vp, i, vp, i, i, i, i, vp, vp, C.c_int32, C.POINTER(C.c_int32),
                                         C.POINTER(C.c_int32)]
     L.esvio_fe_set_detector.argtypes = [vp, i, i]
+    L.esvio_fe_set_event_images.argtypes = [vp, i]
+    L.esvio_fe_clear_event_images.argtypes = [vp]
+    L.esvio_fe_get_event_image.argtypes = [vp, i, vp, i]
+    L.esvio_fe_get_event_canvas.argtypes = [vp, vp, i]
+    L.esvio_fe_event_image_kernel_stats.argtypes = [vp, i, C.POINTER(d), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.esvio_fe_features_to_track_fast.argtypes = [vp, vp, i, i, i, vp, vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.esvio_fe_select_candidates.argtypes = [vp, vp, vp, i, d, i, vp, vp, i, i, i, i, vp, vp, vp, C.POINTER(C.c_int32)]
     L.esvio_fe_convert_events.argtypes = [vp, C.POINTER(EventFieldsDesc), sz, i, vp, i, C.POINTER(C.c_uint64)]
@@ -660,6 +666,21 @@ class EventDetector:
         self._hd.check(self._hd.L.esvio_fe_is_corner(self._hd.h, ptr, n, space, _p(flags)))
         return flags
 
+    def event_image(self, cam):
+        """detector.cur_event_mat_left / _right (event_detector.cc:145-146, :208-209) as (H, W, 3) uint8, B G R
+        (esvio_fe_get_event_image; esvio_fe_set_event_images must be on)"""
+        out = np.empty((self.H, self.W, 3), np.uint8)
+        self._hd.check(self._hd.L.esvio_fe_get_event_image(self._hd.h, int(cam), _p(out), HOST))
+        return out
+
+    @property
+    def cur_event_mat_left(self):
+        return self.event_image(0)
+
+    @property
+    def cur_event_mat_right(self):
+        return self.event_image(1)
+
     def get_sae(self, cam):
         planes = [np.empty((self.H, self.W), np.float64) for _ in range(4)]
         self._hd.check(self._hd.L.esvio_fe_get_sae(self._hd.h, cam, *[_p(a) for a in planes]))
@@ -708,6 +729,26 @@ class FeatureTracker:
                 self._hd.h, float(cur_time), pl, nl, pr, nr, sl, int(PUB_THIS_FRAME),
                 C.byref(measurements), C.byref(self._tr)))
         return self._take(copy)
+
+    def set_event_images(self, on):
+        """show_track's event images (esvio_fe_set_event_images): every track and stage call from now on keeps
+        detector.cur_event_mat_left/right on the device; allocates (on) or releases (off) their memory"""
+        self._hd.check(self._hd.L.esvio_fe_set_event_images(self._hd.h, int(bool(on))))
+
+    def clear_event_images(self):
+        """the Mat::zeros of feature_tracker.cpp:352-353 (esvio_fe_clear_event_images)"""
+        self._hd.check(self._hd.L.esvio_fe_clear_event_images(self._hd.h))
+
+    def event_image(self, cam):
+        """(H, W, 3) uint8, B G R: the camera's event image after the latest call"""
+        return self.detector.event_image(cam)
+
+    def event_canvas(self):
+        """hconcat(cur_event_mat_left, cur_event_mat_right) (feature_tracker.cpp:1107), the base of feature_img, as
+        (H, 2 W, 3) uint8 (esvio_fe_get_event_canvas)"""
+        out = np.empty((self.cfg.height, 2 * self.cfg.width, 3), np.uint8)
+        self._hd.check(self._hd.L.esvio_fe_get_event_canvas(self._hd.h, _p(out), HOST))
+        return out
 
     def convert_events(self, fields, space=DEVICE, src_space=HOST):
         """events.EventFields -> event records, converted on the device (esvio_fe_convert_events).  Returns a

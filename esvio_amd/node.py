@@ -168,10 +168,21 @@ class StereoEventTrackerNode:
     """handle_stereo_event (node:145-344).  ``handle(left, right, msg_timestamp)`` returns the
     published PointCloud rows or None (first frame, reset, non-published frame, swallowed first
     publish).  With ``motion`` (a MotionCorrection and the module whose ``make_motion`` builds the
-    tracker's argument) the batch takes the motion-compensated trackEvent (node:194-254)."""
+    tracker's argument) the batch takes the motion-compensated trackEvent (node:194-254).
 
-    def __init__(self, tracker, freq, reset_tracker_on_restart=False, motion=None, make_motion=None):
+    ``show_track`` (SHOW_TRACK, node:257-265, which precedes the PUB_THIS_FRAME branch of :268): the tracker's event
+    images are turned on and ``handle`` returns, for EVERY tracked frame, published or not, a dict: ``points`` (what it
+    returns otherwise: the PointCloud rows or None), ``feature_img_base`` (hconcat of the two event images,
+    feature_tracker.cpp:1107: feature_img before the host's markers), ``time_surface`` (gettimesurface(), :894) and, for
+    a frame tracked through the motion-compensated overload only, ``event_loop`` (the left event image, :863, :1161:
+    the plain overload leaves imTrack_loop empty and node:94 publishes nothing).  Frames that are not tracked (first
+    frame, restart, empty left batch) return None as before."""
+
+    def __init__(self, tracker, freq, reset_tracker_on_restart=False, motion=None, make_motion=None, show_track=False):
         self.trackerData = tracker
+        self.show_track = bool(show_track)
+        if self.show_track:
+            tracker.set_event_images(True)
         self.motion = motion
         self.make_motion = make_motion
         self.freq = freq
@@ -225,6 +236,18 @@ class StereoEventTrackerNode:
             t_left_1 = msg_timestamp if header_stamp is None else header_stamp
             mv = self.make_motion(**self.motion.value(event_times(event_left[:1])[0], t_left_1))
             self.trackerData.trackEvent(msg_timestamp_left, event_left, event_right, pub, measurements=mv)
+        shown = None
+        if self.show_track:  # node:257-265
+            shown = dict(feature_img_base=self.trackerData.event_canvas(), time_surface=self.trackerData.gettimesurface(0))
+            if self.motion is not None:
+                shown["event_loop"] = self.trackerData.event_image(0)
+        pc = self._published(pub)
+        if shown is None:
+            return pc
+        shown["points"] = pc
+        return shown
+
+    def _published(self, pub):
         if not pub:
             return None
         self.pub_count += 1

@@ -1352,6 +1352,62 @@ int esvio_fe_feed_track(esvio_fe_handle h, int pub_this_frame, const esvio_fe_mo
                         esvio_fe_batch_info* info);
 int esvio_fe_feed_close(esvio_fe_handle h);
 
+/* ---- event images: detector.cur_event_mat_left/right on the device ------------------------ */
+/* Every parameter set the reference ships has show_track: 1.  With it trackEvent keeps two CV_8UC3 images,
+ * detector.cur_event_mat_left/right: zeroed at feature_tracker.cpp:352-353 (:624-625 in the motion-compensated
+ * overload), one pixel written by every createSAE_* call (event_detector.cc:145-146, :164-165, :208-209, :226-227);
+ * feature_img is hconcat(left, right) with markers on it (feature_tracker.cpp:1107), the left image unchanged is
+ * event_loop in the motion-compensated overload (:863, :1161), and the node publishes them
+ * (stereo_event_tracker_node.cpp:64-99, :257-265).  This is the event-proportional part of show_track — one write per
+ * event, in stream order — and the part this library takes; the rule below is those lines, in integers.
+ *
+ * Per handle and camera there is an image E_cam: `height` rows of `width` pixels of 3 bytes (B, G, R), dense and
+ * row-major.  It exists only while the setting is on.  For the events of a call, in stream order:
+ *   Pixel.   The pixel of event i is the pixel at which that call's SAE update writes event i: for the plain overload
+ *            the event's own pixel; for the motion-compensated overload the warped pixel (event_detector.cc:128-129
+ *            feeds both :135 and :145), for both cameras.  An event the SAE update skips (x >= width or y >= height;
+ *            the warp itself drops none: where the warped pixel leaves the sensor the event keeps its own) writes
+ *            nothing.
+ *   Colour.  E[pixel] = (255, 0, 0) if the event's polarity byte is non-zero, else (0, 0, 255).
+ *   Order.   Later events overwrite earlier ones.  Stamps are never looked at: equal, decreasing or stepping-back
+ *            stamps change nothing.  ignore_polarity and feature_filter_threshold play no part.
+ * What each call does to the images:
+ *   Stage calls (esvio_fe_create_sae, _stereo, _stereo_mc) ACCUMULATE: they apply the rule to the images as they are
+ *     and clear nothing — what the reference's createSAE_* do to whatever Mat is there.
+ *   Plain track calls — esvio_fe_track_event, esvio_fe_track_event_mc and everything that ends in them: _fields,
+ *     _filtered, esvio_fe_track_batch, esvio_fe_track_raw, esvio_fe_track_aedat, esvio_fe_feed_track — set both images
+ *     to zero, then apply the rule to the arrays their SAE update consumes (filtered calls: the kept records).
+ *   A call that skips a camera's SAE update leaves that camera's image zero: nR = 0, the one-shot right image of
+ *     esvio_fe_import_image, a batch committed by esvio_fe_sae_slice_commit (both cameras).
+ *   esvio_fe_reset zeroes both images; the setting survives, like esvio_fe_set_detector's.  esvio_fe_track_image
+ *     ignores the setting.  The time-slice entry points that run on scratch planes (esvio_fe_sae_slice_last, _apply)
+ *     write nothing.
+ *
+ * esvio_fe_set_event_images(on) waits for the handle's streams and, for on != 0, allocates everything the feature
+ * needs — 14 bytes per pixel for the two cameras and 6 for the canvas: pixel-proportional only, so no later call
+ * allocates for it — and leaves both images zero; on == 0 releases the memory.  A handle that never turns the setting
+ * on allocates nothing and launches nothing for it.  esvio_fe_clear_event_images is the Mat::zeros of
+ * feature_tracker.cpp:352-353 for a host that drives the stage calls itself.
+ * The getters: dst is host memory of any kind, or device memory (`space`); esvio_fe_get_event_image writes
+ * width*height*3 bytes, esvio_fe_get_event_canvas hconcat(left, right) (:1107): height rows of 2*width*3 bytes.  A
+ * getter orders itself behind every write to the image on whichever stream made it (in a plain track call the right
+ * camera's update runs on the stereo stream), waits for its own result and touches nothing of the tracker.  After a
+ * lazily returned call (esvio_fe_set_lazy_new_stereo) the getters already give that batch's images: they read
+ * events, not LK results.
+ * ESVIO_FE_EINVAL with a message, before any device work: a getter or esvio_fe_clear_event_images while the setting is
+ * off; cam outside 0..1; a null dst; a bad space; esvio_fe_set_event_images while batches are announced;
+ * esvio_fe_set_next_batch and _mc while the setting is on.  (The kernel's per-pixel key holds the event's index in its
+ * camera's array in 31 bits; every entry point above already refuses batches of 2^31 events and more.)
+ * Out of scope: announced batches (refused as above: their update runs ahead of the call on the prefetch stream); the
+ * markers, arrows and the two gray canvases (feature_img_two, pointfeature_img_two), which the host composes from
+ * esvio_fe_get_time_surface / esvio_fe_export_image with the cv::circle and cv::arrowedLine calls it already has — at
+ * most 300 of them a frame; the time-sliced and camera splits beyond "skipped camera = zero image";
+ * prev_event_mat_left (written and never read in the reference); sensor_msgs serialisation. */
+int esvio_fe_set_event_images(esvio_fe_handle h, int on);
+int esvio_fe_clear_event_images(esvio_fe_handle h);
+int esvio_fe_get_event_image(esvio_fe_handle h, int cam, uint8_t* dst, int space);
+int esvio_fe_get_event_canvas(esvio_fe_handle h, uint8_t* dst, int space);
+
 /* ---- camera split across GPUs (BASELINE config C4) ----------------------- */
 /* The left and right cameras have disjoint SAE state (sae_/sae_latest_ vs sae_right/
  * sae_latest_right, event_detector.h:74-79), so a second GPU can own the right camera: it runs

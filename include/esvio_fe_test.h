@@ -238,6 +238,10 @@ int esvio_fe_bag_image_walk_tap(void* state, size_t state_bytes, const char* lef
                                 char* why, size_t why_cap);
 /* pixels per workgroup of k_image_emit, whose timer id is appended to the ingest range above */
 int esvio_fe_image_tile_pixels(void);
+/* the event images' two kernels (esvio_fe_set_event_images), booked in timer slots of their own outside the stage and
+ * ingest tables: which = 0, k_evimg_mark; 1, k_evimg_emit (both forms); as esvio_fe_get_kernel_stats otherwise */
+int esvio_fe_event_image_kernel_stats(esvio_fe_handle h, int which, double* total_ms, uint64_t* launches,
+                                      uint64_t* alg_bytes);
 /* the events one workgroup of the slicing chain takes (esvio_fe_slice_events): where its tile edges lie */
 int esvio_fe_slice_tile_events(void);
 /* the hipStream_t the handle launches on (as void*) */

@@ -13,6 +13,8 @@
 //       ahead (0: one batch in flight like the reference; 1..3: esvio_fe_set_next_batch replay mode)
 //       lazy threads  (throughput options, results identical)   rccl (1: also all-gather every
 //       published frame's records over a one-rank RCCL communicator, esvio_fe_exchange_tracks)
+//       show (1: show_track — esvio_fe_set_event_images is turned on and after every tracked frame, published or not
+//       (node:257-265), the canvas hconcat(cur_event_mat_left, cur_event_mat_right) is fetched; ahead = 0)
 //
 // Log format (little endian): "ESVB" u32 version (1 or 2) u32 width u32 height u32 n_messages, then
 // per message: u8 kind u8 pad[3] u32 n f64 header_stamp and
@@ -27,7 +29,9 @@
 // Messages are delivered to the callbacks in log order; a left/right pair is handled as soon as its
 // second message has arrived (the reference's spinner and sync_process threads interleave freely).
 // Dump format: "ESVD" u32 n_frames, per frame: f64 stamp u8 restart_flag u8 published u8 pad[2]
-// u32 n_rows, n_rows x 8 f32 (x_un, y_un, 1, id*2+cam, u, v, vx, vy).
+// u32 n_rows, n_rows x 8 f32 (x_un, y_un, 1, id*2+cam, u, v, vx, vy).  With show=1 text lines follow the last frame,
+// one per tracked frame: "show <frame index> <FNV-1a 64 of the canvas bytes, 16 hex digits>\n"; without it the dump is
+// what it was, byte for byte.
 //
 // Build: g++ -O2 -std=c++17 tools/replay_node.cpp -Iinclude -Lesvio_amd -lesvio_fe
 //        -Wl,-rpath,$PWD/esvio_amd -Wl,-rpath-link,/opt/rocm/lib -ldl -o tools/replay_node
@@ -64,7 +68,15 @@ struct Frame {
   double stamp;
   uint8_t restart, published;
   std::vector<float> rows;  // n x 8
+  bool shown = false;       // show=1: the frame was tracked, canvas_hash is its canvas's
+  uint64_t canvas_hash = 0;
 };
+
+uint64_t fnv1a64(const uint8_t* p, size_t n) {
+  uint64_t h = 14695981039346656037ull;
+  for (size_t i = 0; i < n; i++) h = (h ^ p[i]) * 1099511628211ull;
+  return h;
+}
 
 double to_sec(const esvio_fe_event& e) { return (double)e.sec + 1e-9 * (double)e.nsec; }  // ros::Time::toSec
 
@@ -95,6 +107,8 @@ struct Node {
   void* comm = nullptr;  // ncclComm_t (rccl=1)
   std::vector<float> gathered;
   int exchanges = 0;
+  bool show = false;  // SHOW_TRACK
+  std::vector<uint8_t> canvas;
 
   void alloc() {
     const size_t M = (size_t)cfg.max_cnt;
@@ -268,6 +282,12 @@ struct Node {
     }
     if (rc) return rc;
     if (announced_ahead > 0) announced_ahead--;
+    if (show) {  // node:257-265: before the PUB_THIS_FRAME branch, so for every tracked frame
+      canvas.resize((size_t)cfg.width * cfg.height * 6);
+      if ((rc = esvio_fe_get_event_canvas(h, canvas.data(), ESVIO_FE_HOST))) return rc;
+      f.shown = true;
+      f.canvas_hash = fnv1a64(canvas.data(), canvas.size());
+    }
     if (PUB_THIS_FRAME) {
       pub_count++;  // node:268
       pack_rows(f);
@@ -367,6 +387,8 @@ int write_dump(const char* path, Node& node, size_t n_pairs, size_t thrown) {
     n_pub += f.published;
     n_rows += n;
   }
+  for (size_t k = 0; k < node.out.size(); k++)
+    if (node.out[k].shown) fprintf(fo, "show %zu %016llx\n", k, (unsigned long long)node.out[k].canvas_hash);
   fclose(fo);
   printf("replay_node: %zu message pairs (%zu thrown), %u frames tracked or restarted, %zu published, %zu rows, "
          "%d RCCL exchanges\n", n_pairs, thrown, nf, n_pub, n_rows, node.exchanges);
@@ -384,7 +406,7 @@ int main(int argc, char** argv) {
   std::map<std::string, double> kv = {{"max_cnt", 300}, {"min_dist", 10},   {"freq", 15},     {"equalize", 0},
                                       {"flow_back", 1}, {"f_threshold", 1}, {"f_ransac", 1},  {"decay_ms", 20},
                                       {"filter_thr", 0.01}, {"ahead", 0},   {"lazy", 0},      {"threads", 1},
-                                      {"rccl", 0},          {"mc", 0},      {"lk_accum", 2}};
+                                      {"rccl", 0},          {"mc", 0},      {"lk_accum", 2},  {"show", 0}};
   for (int i = 3; i < argc; i++) {
     const char* eq = std::strchr(argv[i], '=');
     if (!eq) continue;
@@ -418,6 +440,11 @@ int main(int argc, char** argv) {
     fprintf(stderr, "mc=1 needs ahead=0: the Motion_correction_value of a batch is assembled when it is handled\n");
     return 2;
   }
+  node.show = kv["show"] != 0;
+  if (node.show && node.ahead > 0) {
+    fprintf(stderr, "show=1 needs ahead=0: the event images do not follow announced batches\n");
+    return 2;
+  }
   node.K[0] = kv.count("fx") ? kv["fx"] : c.cam[0].fx;
   node.K[1] = kv.count("fy") ? kv["fy"] : c.cam[0].fy;
   node.K[2] = kv.count("cx") ? kv["cx"] : c.cam[0].cx;
@@ -429,6 +456,10 @@ int main(int argc, char** argv) {
   }
   node.alloc();
   if (node.lazy) esvio_fe_set_lazy_new_stereo(node.h, 1);
+  if (node.show && (rc = esvio_fe_set_event_images(node.h, 1))) {
+    fprintf(stderr, "esvio_fe_set_event_images failed: %d %s\n", rc, esvio_fe_last_error(node.h));
+    return 1;
+  }
   if (kv["threads"] > 1) esvio_fe_set_host_threads(node.h, (int)kv["threads"]);
   if (kv["rccl"] != 0) {
     // a communicator of one rank (this box has one GPU); on a multi-GPU node every rank passes its own
