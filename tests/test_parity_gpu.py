@@ -660,13 +660,14 @@ def _motion(mod, L, accel=(4.0, 5.0, 3.0), omega=(0.9, -1.4, 2.1), W=640, H=480,
                            fx=0.9 * W, fy=0.9 * W, cx=W / 2.0 + 3.5, cy=H / 2.0 - 2.25)
 
 
-@pytest.mark.parametrize("path", ["tiled", "sort_walk"])
+@pytest.mark.parametrize("path", list(SAE_PATHS))
 def test_motion_compensated_sae(oracle, path, monkeypatch):
     """createSAE_left/right with Motion_correction_value (event_detector.cc:102-147,168-210) under
     trackEvent's per-event gate (feature_tracker.cpp:627-641): planes bit-exact, incl. |a| <= 5
     (no warp), large rotations (Pade-5 / Pade-7 branches of Matrix3f::exp) and border pixels.  Through
     the tiled update (the warp inside k_tile_hist, the warped pixel written into the partitioned
-    record by k_tile_scatter) and through the radix-sort form (k_sae_keys<true>)."""
+    record by k_tile_scatter) and through both radix-sort forms (k_sae_keys<true>).  The inputs aimed at the gates,
+    the band and the branch thresholds, and the float64 comparison, are tests/test_mc_edges_gpu.py's."""
     for k, v in SAE_PATHS[path].items():
         monkeypatch.setenv(k, v)
     W, H = 640, 480
