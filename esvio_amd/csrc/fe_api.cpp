@@ -3583,6 +3583,8 @@ int esvio_fe_set_detector(esvio_fe_handle c, int detector, int fast_barrier) {
 // ---- event images (the rule: include/esvio_fe.h "event images"; the kernels: fe_kernels.h; the update: evimg_update)
 int esvio_fe_set_event_images(esvio_fe_handle c, int on) {
   if (!c) return ESVIO_FE_EINVAL;
+  if (on != 0 && on != 1 && on != ESVIO_FE_EVENT_IMAGES_AHEAD)
+    return fail(c, ESVIO_FE_EINVAL, "esvio_fe_set_event_images: the value must be 0, 1 or ESVIO_FE_EVENT_IMAGES_AHEAD (got %d)", on);
   if (!c->inflight.empty() || !c->announced.empty())
     return fail(c, ESVIO_FE_EINVAL, "esvio_fe_set_event_images while batches are announced");
   HIPCHK(c, hipSetDevice(c->dev));
@@ -3594,28 +3596,37 @@ int esvio_fe_set_event_images(esvio_fe_handle c, int on) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
   esvio_fe_ctx::Evimg& E = c->evimg;
   E.on = false;
+  E.mode = 0;
+  E.nsets = 0;
+  E.cur = 0;
   E.fresh_cams = 0;
-  E.wstream[0] = E.wstream[1] = nullptr;
-  if (!on) {
+  for (esvio_fe_ctx::Evimg::Set& S : E.set) {
+    S.wstream[0] = S.wstream[1] = nullptr;
     for (int cam = 0; cam < 2; cam++) {
-      E.marks[cam].release();
-      E.img[cam].release();
-      E.written[cam] = Event();
+      S.marks[cam].release();
+      S.img[cam].release();
+      S.written[cam] = Event();
     }
-    E.canvas.release();
-    return 0;
   }
-  // everything the feature needs, pixel-proportional: 2 x (4 + 3) bytes per pixel and the getter's canvas, 6 more
+  E.canvas.release();
+  if (!on) return 0;
+  // everything the feature needs, pixel-proportional: per set 2 x (4 + 3) bytes per pixel — one set, or one for the
+  // frame being tracked and one per prefetch lane — and the getter's canvas, 6 more
   E.groups = (c->P + 3u) / 4u;
-  for (int cam = 0; cam < 2; cam++) {
-    if (int rc = E.marks[cam].alloc(c, (size_t)E.groups * 4)) return rc;
-    if (int rc = E.img[cam].alloc(c, (size_t)E.groups * 3)) return rc;
-    if (!E.written[cam]) HIPCHK(c, E.written[cam].create());
-    HIPCHK(c, hipMemsetAsync(E.marks[cam], 0, (size_t)E.groups * 16, c->stream));
-    HIPCHK(c, hipMemsetAsync(E.img[cam], 0, (size_t)E.groups * 12, c->stream));
-  }
+  const int nsets = on == ESVIO_FE_EVENT_IMAGES_AHEAD ? esvio_fe_ctx::Evimg::kSets : 1;
+  for (int k = 0; k < nsets; k++)
+    for (int cam = 0; cam < 2; cam++) {
+      esvio_fe_ctx::Evimg::Set& S = E.set[k];
+      if (int rc = S.marks[cam].alloc(c, (size_t)E.groups * 4)) return rc;
+      if (int rc = S.img[cam].alloc(c, (size_t)E.groups * 3)) return rc;
+      HIPCHK(c, S.written[cam].create());
+      HIPCHK(c, hipMemsetAsync(S.marks[cam], 0, (size_t)E.groups * 16, c->stream));
+      HIPCHK(c, hipMemsetAsync(S.img[cam], 0, (size_t)E.groups * 12, c->stream));
+    }
   if (int rc = E.canvas.alloc(c, (size_t)c->P * 6)) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  E.nsets = nsets;
+  E.mode = on;
   E.on = true;
   return 0;
 }
@@ -3634,8 +3645,10 @@ static int evimg_get_ready(esvio_fe_ctx* c, const char* who, int cam0, int cam1,
   if (!dst) return fail(c, ESVIO_FE_EINVAL, "%s: dst is null", who);
   if (space != ESVIO_FE_HOST && space != ESVIO_FE_DEVICE) return fail(c, ESVIO_FE_EINVAL, "%s: bad memory space %d", who, space);
   HIPCHK(c, hipSetDevice(c->dev));
+  // (the current set's writes alone: a batch prefetched since writes a set of its own)
+  const esvio_fe_ctx::Evimg::Set& S = c->evimg.set[c->evimg.cur];
   for (int cam = cam0; cam <= cam1; cam++)
-    if (c->evimg.wstream[cam]) HIPCHK(c, hipEventSynchronize(c->evimg.written[cam]));
+    if (S.wstream[cam]) HIPCHK(c, hipEventSynchronize(S.written[cam]));
   return 0;
 }
 
@@ -3643,7 +3656,7 @@ int esvio_fe_get_event_image(esvio_fe_handle c, int cam, uint8_t* dst, int space
   if (!c) return ESVIO_FE_EINVAL;
   if (int rc = evimg_get_ready(c, "get_event_image", cam, cam, dst, space)) return rc;
   // one dense copy on the null stream (none of the handle's: they are non-blocking streams), waited for
-  HIPCHK(c, hipMemcpyAsync(dst, c->evimg.img[cam], (size_t)c->P * 3, space == ESVIO_FE_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, nullptr));
+  HIPCHK(c, hipMemcpyAsync(dst, c->evimg.set[c->evimg.cur].img[cam], (size_t)c->P * 3, space == ESVIO_FE_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, nullptr));
   HIPCHK(c, hipStreamSynchronize(nullptr));
   return 0;
 }
@@ -3654,7 +3667,8 @@ int esvio_fe_get_event_canvas(esvio_fe_handle c, uint8_t* dst, int space) {
   esvio_fe_ctx::Evimg& E = c->evimg;
   // composed at getter time: device memory takes it directly, host memory one dense copy of the scratch
   uint8_t* canvas = space == ESVIO_FE_DEVICE ? dst : E.canvas.p;
-  launch_evimg_canvas(nullptr, (const uint8_t*)E.img[0].p, (const uint8_t*)E.img[1].p, c->W, c->H, canvas);
+  const esvio_fe_ctx::Evimg::Set& S = E.set[E.cur];
+  launch_evimg_canvas(nullptr, (const uint8_t*)S.img[0].p, (const uint8_t*)S.img[1].p, c->W, c->H, canvas);
   if (space == ESVIO_FE_HOST) HIPCHK(c, hipMemcpyAsync(dst, canvas, (size_t)c->P * 6, hipMemcpyDeviceToHost, nullptr));
   HIPCHK(c, hipStreamSynchronize(nullptr));
   HIPCHK(c, hipGetLastError());
@@ -4026,7 +4040,8 @@ static int set_next_batch_impl(esvio_fe_handle c, double next_cur_time, const es
   if (nL == 0 || !left || (nR && !right)) return fail(c, ESVIO_FE_EINVAL, "bad next batch");
   if (space != ESVIO_FE_HOST && space != ESVIO_FE_DEVICE) return ESVIO_FE_EINVAL;
   if (c->ext_right_pending) return fail(c, ESVIO_FE_EINVAL, "not with an imported right image");
-  if (c->evimg.on) return fail(c, ESVIO_FE_EINVAL, "not while esvio_fe_set_event_images is on: the event images do not follow announced batches");
+  if (c->evimg.mode == 1)
+    return fail(c, ESVIO_FE_EINVAL, "not while esvio_fe_set_event_images is 1: the event images do not follow announced batches (ESVIO_FE_EVENT_IMAGES_AHEAD does)");
   if ((int)(c->announced.size() + c->inflight.size()) >= 2 * kPrefetchDepth)
     return fail(c, ESVIO_FE_EINVAL, "at most %d batches can be announced and not yet tracked", 2 * kPrefetchDepth);
   Batch b;

@@ -151,6 +151,10 @@ struct Inflight : Batch {
   const EventRec *dL = nullptr, *dR = nullptr;
   bool arc_done = false;
   uint32_t gate = 0;  // != 0: the value the batch's prefetch sequence leaves in d_lane_gate[lane] (issued by the launch thread)
+  // event images that follow announced batches: the set the batch's prefetch sequence rewrites (-1: none), and the
+  // cameras of that set whose last write was made on another stream than the prefetch stream (their `written` events
+  // are waited for first)
+  int evset = -1, ev_wait = 0;
 };
 constexpr int kPrefetchDepth = 3;
 // host-event staging slots: one per batch the handle can know about at a time (2 * kPrefetchDepth
@@ -655,13 +659,30 @@ struct esvio_fe_ctx {
   // call rewrites (set by take_batch, cleared as the camera's emit is enqueued); 0 in a stage call: accumulate.
   // written[cam]: recorded behind every write to the camera's image on wstream[cam], whichever stream made it; the
   // getters wait for it and copy on none of the handle's streams.
+  // ESVIO_FE_EVENT_IMAGES_AHEAD (mode 2): kSets image sets instead of one — the frame being tracked's (`cur`) and one per
+  // prefetch lane — all allocated by set(2).  A set is what ONE batch writes: an announced batch is given a set that is
+  // neither `cur` nor another prefetched batch's with its other resources (prefetch_next; Inflight::evset), its
+  // prefetch sequence rewrites both cameras of that set on the prefetch stream, and take_batch makes the set `cur`.
+  // The mark planes are kept PER SET, not shared: a set's marks and bytes are then touched by its batch's launches
+  // alone, and the one order to keep is between a set's successive owners (written[] / wstream[]) — shared planes
+  // would have to be ordered between the prefetch stream and a plain call's main and stereo streams as well.  Mode 2
+  // therefore holds kSets x 2 x (4 + 3) + 6 = 62 bytes per pixel, mode 1 its 20.
+  // fresh_cams, and the wstream[] of every set, are the CALLING thread's: the launch thread is told what to do by its
+  // job (Inflight::evset, ::ev_wait) and touches only the set's device memory and its two events.
   struct Evimg {
+    static constexpr int kSets = kPrefetchDepth + 1;
+    struct Set {
+      DevBuf<uint32_t> marks[2], img[2];
+      Event written[2];
+      hipStream_t wstream[2] = {nullptr, nullptr};
+    };
     bool on = false;
+    int mode = 0;   // 0, 1, ESVIO_FE_EVENT_IMAGES_AHEAD
+    int nsets = 0;  // 1 in mode 1, kSets in mode 2
+    int cur = 0;    // the set the getters read and plain / stage calls write
     uint32_t groups = 0;
-    DevBuf<uint32_t> marks[2], img[2];
+    Set set[kSets];
     DevBuf<uint8_t> canvas;
-    Event written[2];
-    hipStream_t wstream[2] = {nullptr, nullptr};
     int fresh_cams = 0;
   } evimg;
 };
@@ -681,6 +702,14 @@ struct StreamScope {
   hipStream_t saved;
   explicit StreamScope(hipStream_t s) : saved(t_stream_override) { t_stream_override = s; }
   ~StreamScope() { t_stream_override = saved; }
+};
+
+// The announced batch whose prefetch sequence the thread is issuing (prefetch_issue), else null: the sequence's SAE
+// update writes the event images of the batch's own set (evimg_update), and nothing handle-global.
+inline thread_local const Inflight* t_prefetch_batch = nullptr;
+struct PrefetchBatchScope {
+  explicit PrefetchBatchScope(const Inflight* b) { t_prefetch_batch = b; }
+  ~PrefetchBatchScope() { t_prefetch_batch = nullptr; }
 };
 
 // (a thread of the handle that is not the calling thread — the launch thread — gives its error texts a place of its

@@ -38,10 +38,12 @@ int sae_update(esvio_fe_ctx* c, const EventRec* evL, uint32_t nL, const EventRec
                bool* arc_marked = nullptr);
 // esvio_fe_set_event_images is on: sae_update of the handle's own planes ends in evimg_update — the batch into the
 // event images, the cameras of evimg.fresh_cams rewritten, the others accumulated; with no events it still rewrites
-// the fresh ones (a track call whose update is skipped).  evimg_zero: both images zero, on the current stream
-// (marks_too: esvio_fe_reset's, behind a call that may have failed half way)
+// the fresh ones (a track call whose update is skipped); inside an announced batch's prefetch sequence
+// (t_prefetch_batch) it rewrites both cameras of the batch's own set.  evimg_zero: both images of the current set
+// zero, on the current stream (every_set: esvio_fe_reset's, behind a call that may have failed half way — every set
+// and its mark planes)
 int evimg_update(esvio_fe_ctx* c, const EventRec* evL, uint32_t nL, const EventRec* evR, uint32_t nR, const McParams* mc);
-int evimg_zero(esvio_fe_ctx* c, bool marks_too = false);
+int evimg_zero(esvio_fe_ctx* c, bool every_set = false);
 int radix_sort_pairs(esvio_fe_ctx* c, uint32_t n, int passes, int bits, bool booked = true);
 // ... of other buffers than the handle's keys[] / vals[] / hist; n_dev (optional): the count is *n_dev, read on the
 // device, and n its upper bound (launch_radix_pass)

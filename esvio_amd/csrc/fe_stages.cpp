@@ -229,53 +229,69 @@ int radix_sort_pairs(esvio_fe_ctx* c, const SortBufs& b, uint32_t n, int passes,
 }
 
 // ---------------------------------------------------------------- event images (esvio_fe_set_event_images)
-// a camera's image (and its mark plane) is about to be written on stream s: behind its last writer, if that was
-// another stream (a plain call's right camera runs on the stereo stream)
-static int evimg_order(esvio_fe_ctx* c, int cams, hipStream_t s) {
-  esvio_fe_ctx::Evimg& E = c->evimg;
+using EvimgSet = esvio_fe_ctx::Evimg::Set;
+// a camera's image (and its mark plane) of set S is about to be written on stream s: behind its last writer, if that
+// was another stream (a plain call's right camera runs on the stereo stream, an announced batch's on the prefetch stream)
+static int evimg_order(esvio_fe_ctx* c, EvimgSet& S, int cams, hipStream_t s) {
   for (int cam = 0; cam < 2; cam++)
-    if ((cams >> cam & 1) && E.wstream[cam] && E.wstream[cam] != s) HIPCHK(c, hipStreamWaitEvent(s, E.written[cam], 0));
+    if ((cams >> cam & 1) && S.wstream[cam] && S.wstream[cam] != s) HIPCHK(c, hipStreamWaitEvent(s, S.written[cam], 0));
   return 0;
 }
-static int evimg_written(esvio_fe_ctx* c, int cams, hipStream_t s) {
-  esvio_fe_ctx::Evimg& E = c->evimg;
+static int evimg_written(esvio_fe_ctx* c, EvimgSet& S, int cams, hipStream_t s) {
   for (int cam = 0; cam < 2; cam++)
     if (cams >> cam & 1) {
-      HIPCHK(c, hipEventRecord(E.written[cam], s));
-      E.wstream[cam] = s;
+      HIPCHK(c, hipEventRecord(S.written[cam], s));
+      S.wstream[cam] = s;
     }
   return 0;
 }
 
-int evimg_zero(esvio_fe_ctx* c, bool marks_too) {
+// the current set's images zero; every_set (esvio_fe_reset, no batch announced any more): every set's, their mark
+// planes too, and set 0 is the current one again
+int evimg_zero(esvio_fe_ctx* c, bool every_set) {
   esvio_fe_ctx::Evimg& E = c->evimg;
   hipStream_t s = cur_stream(c);
-  if (int rc = evimg_order(c, 3, s)) return rc;
-  for (int cam = 0; cam < 2; cam++) {
-    HIPCHK(c, hipMemsetAsync(E.img[cam], 0, (size_t)E.groups * 12, s));
-    // (the emit leaves the mark planes zero; a call that failed between its mark and its emit may not have)
-    if (marks_too) HIPCHK(c, hipMemsetAsync(E.marks[cam], 0, (size_t)E.groups * 16, s));
+  if (every_set) E.cur = 0;
+  for (int k = every_set ? 0 : E.cur; k < (every_set ? E.nsets : E.cur + 1); k++) {
+    EvimgSet& S = E.set[k];
+    if (int rc = evimg_order(c, S, 3, s)) return rc;
+    for (int cam = 0; cam < 2; cam++) {
+      HIPCHK(c, hipMemsetAsync(S.img[cam], 0, (size_t)E.groups * 12, s));
+      // (the emit leaves the mark planes zero; a call that failed between its mark and its emit may not have)
+      if (every_set) HIPCHK(c, hipMemsetAsync(S.marks[cam], 0, (size_t)E.groups * 16, s));
+    }
+    if (int rc = evimg_written(c, S, 3, s)) return rc;
   }
   E.fresh_cams = 0;
-  return evimg_written(c, 3, s);
+  return 0;
 }
 
 // The batch a call's SAE update consumes -> the event images, on the update's stream, behind it (the tiled update has
 // filled d_warp by then).  The cameras of E.fresh_cams are rewritten (a track call's: zero, then the rule), the others
 // that have events accumulate (a stage call's).  Reads the event arrays on the stream the update reads them on, so
 // whatever keeps them alive for the update keeps them alive for this.
+// Inside an announced batch's prefetch sequence (t_prefetch_batch; possibly on the launch thread): both cameras of the
+// BATCH's set are rewritten, what to wait for comes with the batch, and no word of the handle's own state is touched.
 int evimg_update(esvio_fe_ctx* c, const EventRec* evL, uint32_t nL, const EventRec* evR, uint32_t nR, const McParams* mc) {
   esvio_fe_ctx::Evimg& E = c->evimg;
+  const Inflight* job = t_prefetch_batch;
+  if (job && job->evset < 0) return 0;
   const uint32_t n = nL + nR;
-  const int fresh = E.fresh_cams, acc = ((nL ? 1 : 0) | (nR ? 2 : 0)) & ~fresh;
-  E.fresh_cams = 0;
+  EvimgSet& S = E.set[job ? job->evset : E.cur];
+  const int fresh = job ? 3 : E.fresh_cams, acc = ((nL ? 1 : 0) | (nR ? 2 : 0)) & ~fresh;
+  if (!job) E.fresh_cams = 0;
   if (!(fresh | acc)) return 0;
   hipStream_t s = cur_stream(c);
-  if (int rc = evimg_order(c, fresh | acc, s)) return rc;
+  if (job) {
+    for (int cam = 0; cam < 2; cam++)
+      if (job->ev_wait >> cam & 1) HIPCHK(c, hipStreamWaitEvent(s, S.written[cam], 0));
+  } else if (int rc = evimg_order(c, S, fresh | acc, s)) {
+    return rc;
+  }
   if (n) {
     const bool warped = mc && mc->enabled;
     ScopedKernel k(c, K_EVIMG_MARK, (uint64_t)n * (warped && c->tiled ? 24 : 20));  // the record (+ its warped pixel) in, one atomic word out
-    launch_evimg_mark(s, evL, nL, evR, nR, c->W, c->H, E.marks[0], E.marks[1],
+    launch_evimg_mark(s, evL, nL, evR, nR, c->W, c->H, S.marks[0], S.marks[1],
                       !warped ? kEvimgPixOwn : c->tiled ? kEvimgPixWarp : kEvimgPixMc, c->d_warp, mc);
   }
   for (int form = 0; form < 2; form++) {
@@ -283,10 +299,14 @@ int evimg_update(esvio_fe_ctx* c, const EventRec* evL, uint32_t nL, const EventR
     if (!cams) continue;
     const int c0 = cams & 1 ? 0 : 1, ncam = cams == 3 ? 2 : 1;
     ScopedKernel k(c, K_EVIMG_EMIT, (uint64_t)E.groups * 4 * (4 + 3) * ncam);  // the marks in, the bytes out (marks set: + 4 B back)
-    launch_evimg_emit(s, E.marks[c0], E.img[c0], ncam == 2 ? E.marks[1].p : nullptr, ncam == 2 ? E.img[1].p : nullptr,
+    launch_evimg_emit(s, S.marks[c0], S.img[c0], ncam == 2 ? S.marks[1].p : nullptr, ncam == 2 ? S.img[1].p : nullptr,
                       E.groups, form == 0);
   }
-  return evimg_written(c, fresh | acc, s);
+  if (job) {  // (wstream[] was set with the batch's bookkeeping, prefetch_next)
+    for (int cam = 0; cam < 2; cam++) HIPCHK(c, hipEventRecord(S.written[cam], s));
+    return 0;
+  }
+  return evimg_written(c, S, fresh | acc, s);
 }
 
 // arc_set >= 0: this batch's Arc* pass will run into candidate set arc_set; *arc_marked tells

@@ -37,6 +37,7 @@ struct PrefetchJob {
 static int prefetch_issue(esvio_fe_ctx* c, const PrefetchJob& j) {
   const Inflight& b = j.b;
   StreamScope on_prefetch_stream(c->stream2);
+  PrefetchBatchScope its_event_images(&b);  // (sae_update -> evimg_update: into the batch's own set)
   if (j.wait_planes) HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_planes_free, 0));
   // the right-camera pyramid slot this batch gets may be the one an earlier frame's stereo LK
   // (stream4) still reads — in lazy mode nobody has waited for that launch yet
@@ -274,6 +275,19 @@ int prefetch_next(esvio_fe_ctx* c, bool wait_planes, bool must_take_first) {
     while (b.raw == c->raw_cur || taken(&Inflight::raw, b.raw)) b.raw++;
     b.cand = 0;
     while (b.cand == c->cand_cur || taken(&Inflight::cand, b.cand)) b.cand++;
+    if (c->evimg.mode == ESVIO_FE_EVENT_IMAGES_AHEAD) {
+      // the image set the batch rewrites: not the one the getters read, not another prefetched batch's.  Its last
+      // owner's writes may have been a plain call's (main / stereo stream): the sequence waits for those first
+      esvio_fe_ctx::Evimg& E = c->evimg;
+      b.evset = 0;
+      while (b.evset == E.cur || taken(&Inflight::evset, b.evset)) b.evset++;
+      esvio_fe_ctx::Evimg::Set& S = E.set[b.evset];
+      b.ev_wait = 0;
+      for (int cam = 0; cam < 2; cam++) {
+        if (S.wstream[cam] && S.wstream[cam] != c->stream2) b.ev_wait |= 1 << cam;
+        S.wstream[cam] = c->stream2;
+      }
+    }
     b.arc_done = b.pub && b.nL;
     job.wait_planes = wait_planes;
     wait_planes = false;  // later batches simply follow on the same stream
@@ -636,6 +650,7 @@ struct TrackCall {
       c->slot_curL = b.slotL;
       c->slot_curR = b.slotR;
       c->raw_cur = b.raw;
+      if (b.evset >= 0) c->evimg.cur = b.evset;  // the getters read this batch's images from now on
       c->cur_prefetched = true;
       if (b.arc_done) {  // candidates of this batch are in its own set
         c->cand_cur = b.cand;

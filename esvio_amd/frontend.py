@@ -15,6 +15,7 @@ from . import build as _build
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HOST, DEVICE = 0, 1
+EVENT_IMAGES_AHEAD = 2  # ESVIO_FE_EVENT_IMAGES_AHEAD
 LK_USE_INITIAL_FLOW = 4
 
 
@@ -732,8 +733,9 @@ class FeatureTracker:
 
     def set_event_images(self, on):
         """show_track's event images (esvio_fe_set_event_images): every track and stage call from now on keeps
-        detector.cur_event_mat_left/right on the device; allocates (on) or releases (off) their memory"""
-        self._hd.check(self._hd.L.esvio_fe_set_event_images(self._hd.h, int(bool(on))))
+        detector.cur_event_mat_left/right on the device; allocates (on) or releases (off) their memory.  on = 2
+        (EVENT_IMAGES_AHEAD): the images follow announced batches (set_next_batch is accepted), at 62 bytes per pixel"""
+        self._hd.check(self._hd.L.esvio_fe_set_event_images(self._hd.h, EVENT_IMAGES_AHEAD if on == EVENT_IMAGES_AHEAD else int(bool(on))))
 
     def clear_event_images(self):
         """the Mat::zeros of feature_tracker.cpp:352-353 (esvio_fe_clear_event_images)"""

@@ -1384,10 +1384,25 @@ int esvio_fe_feed_close(esvio_fe_handle h);
  *     write nothing.
  *
  * esvio_fe_set_event_images(on) waits for the handle's streams and, for on != 0, allocates everything the feature
- * needs — 14 bytes per pixel for the two cameras and 6 for the canvas: pixel-proportional only, so no later call
- * allocates for it — and leaves both images zero; on == 0 releases the memory.  A handle that never turns the setting
- * on allocates nothing and launches nothing for it.  esvio_fe_clear_event_images is the Mat::zeros of
- * feature_tracker.cpp:352-353 for a host that drives the stage calls itself.
+ * needs — on == 1: 14 bytes per pixel for the two cameras and 6 for the canvas; pixel-proportional only, so no later
+ * call allocates for it — and leaves both images zero; on == 0 releases the memory.  A handle that never turns the
+ * setting on allocates nothing and launches nothing for it.
+ * on == ESVIO_FE_EVENT_IMAGES_AHEAD (2): the images follow announced batches.  esvio_fe_set_next_batch and _mc are
+ *   accepted, and an announced batch's prefetch sequence — which runs whole frames ahead of the batch's track call, on
+ *   the prefetch stream — applies "zero, then the rule" (the warped pixels for _mc, in both forms of the update; a zero
+ *   right image for nR = 0) to an image set of the BATCH's.  There is one set (both cameras, 14 bytes per pixel, its
+ *   mark planes included) for the frame being tracked and one per batch that can be prefetched, three: 4 x 14 + 6 =
+ *   62 bytes per pixel, all allocated by this call — which is why it is a mode of its own: mode 1 keeps its 20.  After
+ *   ANY track call returns — a plain one, one that takes up an announced batch, a lazily returned one — the getters
+ *   give the images of the batch that call tracked: never those of a batch announced or prefetched later, although
+ *   its update has run, and byte for byte what mode 1 gives for the same batches tracked by plain calls.  A getter
+ *   waits for the writes to that one set and not for later batches' prefetch work.  A set is rewritten whole by the
+ *   batch that gets it next, so frames whose images nobody fetches leave nothing behind.  esvio_fe_reset zeroes every
+ *   set.  Stage calls and esvio_fe_clear_event_images work on the set the getters read.  Everything else is mode 1's.
+ *   No stream is added: a stream takes a hardware queue from the process's pool.  What the mode costs the replay
+ *   schedule is measured in KERNELS.md "Event images".
+ * esvio_fe_clear_event_images is the Mat::zeros of feature_tracker.cpp:352-353 for a host that drives the stage calls
+ * itself.
  * The getters: dst is host memory of any kind, or device memory (`space`); esvio_fe_get_event_image writes
  * width*height*3 bytes, esvio_fe_get_event_canvas hconcat(left, right) (:1107): height rows of 2*width*3 bytes.  A
  * getter orders itself behind every write to the image on whichever stream made it (in a plain track call the right
@@ -1395,15 +1410,17 @@ int esvio_fe_feed_close(esvio_fe_handle h);
  * lazily returned call (esvio_fe_set_lazy_new_stereo) the getters already give that batch's images: they read
  * events, not LK results.
  * ESVIO_FE_EINVAL with a message, before any device work: a getter or esvio_fe_clear_event_images while the setting is
- * off; cam outside 0..1; a null dst; a bad space; esvio_fe_set_event_images while batches are announced;
- * esvio_fe_set_next_batch and _mc while the setting is on.  (The kernel's per-pixel key holds the event's index in its
- * camera's array in 31 bits; every entry point above already refuses batches of 2^31 events and more.)
- * Out of scope: announced batches (refused as above: their update runs ahead of the call on the prefetch stream); the
- * markers, arrows and the two gray canvases (feature_img_two, pointfeature_img_two), which the host composes from
+ * off; cam outside 0..1; a null dst; a bad space; esvio_fe_set_event_images with a value other than 0, 1, 2, or
+ * with any value while batches are announced; esvio_fe_set_next_batch and _mc while the setting is 1.  (The kernel's
+ * per-pixel key holds the event's index in its camera's array in 31 bits; every entry point above already refuses
+ * batches of 2^31 events and more.)
+ * Out of scope: the time-surface and esvio_fe_get_sae taps of the tracked frame under announced batches (they keep
+ * their "latest prefetched batch" meaning); the markers, arrows and the two gray canvases (feature_img_two, pointfeature_img_two), which the host composes from
  * esvio_fe_get_time_surface / esvio_fe_export_image with the cv::circle and cv::arrowedLine calls it already has — at
  * most 300 of them a frame; the time-sliced and camera splits beyond "skipped camera = zero image";
  * prev_event_mat_left (written and never read in the reference); sensor_msgs serialisation. */
-int esvio_fe_set_event_images(esvio_fe_handle h, int on);
+#define ESVIO_FE_EVENT_IMAGES_AHEAD 2
+int esvio_fe_set_event_images(esvio_fe_handle h, int on); /* 0, 1 as above; 2: the images follow announced batches */
 int esvio_fe_clear_event_images(esvio_fe_handle h);
 int esvio_fe_get_event_image(esvio_fe_handle h, int cam, uint8_t* dst, int space);
 int esvio_fe_get_event_canvas(esvio_fe_handle h, uint8_t* dst, int space);

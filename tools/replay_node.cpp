@@ -14,7 +14,8 @@
 //       lazy threads  (throughput options, results identical)   rccl (1: also all-gather every
 //       published frame's records over a one-rank RCCL communicator, esvio_fe_exchange_tracks)
 //       show (1: show_track — esvio_fe_set_event_images is turned on and after every tracked frame, published or not
-//       (node:257-265), the canvas hconcat(cur_event_mat_left, cur_event_mat_right) is fetched; ahead = 0)
+//       (node:257-265), the canvas hconcat(cur_event_mat_left, cur_event_mat_right) is fetched; with ahead = 1..3 the
+//       setting is ESVIO_FE_EVENT_IMAGES_AHEAD: the images follow the announced batches)
 //
 // Log format (little endian): "ESVB" u32 version (1 or 2) u32 width u32 height u32 n_messages, then
 // per message: u8 kind u8 pad[3] u32 n f64 header_stamp and
@@ -441,10 +442,6 @@ int main(int argc, char** argv) {
     return 2;
   }
   node.show = kv["show"] != 0;
-  if (node.show && node.ahead > 0) {
-    fprintf(stderr, "show=1 needs ahead=0: the event images do not follow announced batches\n");
-    return 2;
-  }
   node.K[0] = kv.count("fx") ? kv["fx"] : c.cam[0].fx;
   node.K[1] = kv.count("fy") ? kv["fy"] : c.cam[0].fy;
   node.K[2] = kv.count("cx") ? kv["cx"] : c.cam[0].cx;
@@ -456,7 +453,7 @@ int main(int argc, char** argv) {
   }
   node.alloc();
   if (node.lazy) esvio_fe_set_lazy_new_stereo(node.h, 1);
-  if (node.show && (rc = esvio_fe_set_event_images(node.h, 1))) {
+  if (node.show && (rc = esvio_fe_set_event_images(node.h, node.ahead > 0 ? ESVIO_FE_EVENT_IMAGES_AHEAD : 1))) {
     fprintf(stderr, "esvio_fe_set_event_images failed: %d %s\n", rc, esvio_fe_last_error(node.h));
     return 1;
   }
