@@ -4492,3 +4492,6 @@ int esvio_fe_bag_image_walk_tap(void* state, size_t state_bytes, const char* lef
 }
 
 }  // extern "C"
+
+// ---- loop-closure keyframes (the rules: include/esvio_fe.h "keyframes"; the kernels: fe_kernels.h)
+#include "fe_kf.h"

@@ -107,7 +107,10 @@ struct PhaseClock {
 
 // the event images' two timer slots behind the ingest range: esvio_fe_event_image_kernel_stats reads them, the stage
 // and ingest tables (whose ends tests pin) stay as they are
-enum { K_EVIMG_MARK = K_INGEST_COUNT, K_EVIMG_EMIT, K_ALL_COUNT };
+// ... and behind them the keyframe stage's three (esvio_fe_kf_kernel_count / _name / _stats, include/esvio_fe_test.h)
+enum { K_EVIMG_MARK = K_INGEST_COUNT, K_EVIMG_EMIT, K_KF_BLUR, K_KF_BRIEF, K_KF_MATCH, K_ALL_COUNT };
+constexpr int kKfKernels = K_ALL_COUNT - K_KF_BLUR;
+const char* const kKfKernelNames[kKfKernels] = {"k_kf_blur", "k_kf_brief", "k_kf_match"};
 
 struct KStat {
   double ms = 0;
@@ -685,6 +688,27 @@ struct esvio_fe_ctx {
     DevBuf<uint8_t> canvas;
     int fresh_cams = 0;
   } evimg;
+
+  // ---- esvio_fe_kf_*: loop-closure keyframes (include/esvio_fe.h "keyframes" has the rules, fe_kernels.h the kernels,
+  // fe_kf.h the host side).  The pattern is a SETTING (it survives esvio_fe_reset): pat, the host's copy, x1 | y1 | x2 |
+  // y2; d_pat its device copy, made by esvio_fe_kf_set_pattern.  Everything else is the stage's own scratch (main stream
+  // only), allocated on first use: img, the device copy of a host image; blur, the blurred plane (and what stands
+  // behind a host dst); pts / desc, the points of a descriptor call and their descriptors; q / t, the device copies of
+  // host descriptors of a match call; res, its results (idx | dist | status).  F works in esvio_fe_fast_corners' own
+  // candidate set and score map (fast_own, fast_own_fc): both are the main stream's between calls.  h_xy / h_score:
+  // where F's list arrives on the host.
+  struct Kf {
+    bool has_pattern = false;
+    int8_t pat[4 * kKfPatternTests] = {};
+    DevBuf<int8_t> d_pat;
+    DevBuf<uint8_t> img, blur;
+    DevBuf<float2> pts;
+    DevBuf<uint32_t> desc, q, t;
+    DevBuf<int32_t> res;
+    std::vector<uint32_t> h_xy, h_score;
+    std::vector<float> h_pts;
+    std::vector<double> lift_x, lift_y;
+  } kf;
 };
 
 namespace esvio {

@@ -61,6 +61,14 @@ static int fast_map_alloc(esvio_fe_ctx* c, esvio_fe_ctx::FastCand& f) {
   return f.det.alloc(c, (P + kArcBlock - 1) / kArcBlock);
 }
 
+// esvio_fe_fast_corners' candidate set and score map (esvio_fe_ctx::fast_own, fast_own_fc), on the first call
+static int fast_own_alloc(esvio_fe_ctx* c) {
+  if (c->fast_own.cap) return 0;
+  if (int rc = fast_map_alloc(c, c->fast_own_fc)) return rc;
+  // total[0]: k_compact's total; total[1]: the count before non-max — side by side, one copy for both
+  return cand_set_alloc(c, c->fast_own, ((size_t)c->W * c->H + kArcBlock - 1) / kArcBlock * kArcBlock, 2);
+}
+
 // fast::fast_corner_detect_9 / _10 (+ fast_corner_score_10, fast_nonmax_3x3) of the reference's vendored FAST
 // (dependences/fast_neon-master/include/fast/fast.h:22-47) on a device image.  A candidate set and a score map of
 // its own (fast_own, fast_own_fc), allocated on the first call: nothing the tracker, a prefetched batch or the stage
@@ -68,11 +76,7 @@ static int fast_map_alloc(esvio_fe_ctx* c, esvio_fe_ctx::FastCand& f) {
 int fast_run(esvio_fe_ctx* c, const uint8_t* img, int stride, int arc, int barrier, bool nonmax, int16_t* out_xy,
              int32_t* out_score, int32_t capacity, int32_t* n_out, int32_t* n_detected) {
   esvio_fe_ctx::CandSet& cs = c->fast_own;
-  if (!cs.cap) {
-    if (int rc = fast_map_alloc(c, c->fast_own_fc)) return rc;
-    // total[0]: k_compact's total; total[1]: the count before non-max — side by side, one copy for both
-    if (int rc = cand_set_alloc(c, cs, ((size_t)c->W * c->H + kArcBlock - 1) / kArcBlock * kArcBlock, 2)) return rc;
-  }
+  if (int rc = fast_own_alloc(c)) return rc;
   hipStream_t s = cur_stream(c);
   // (without non-max the count before it is the total)
   fast_lists(c, img, stride, arc, barrier, nonmax, -1, cs, c->fast_own_fc, (n_detected && nonmax) ? cs.total + 1 : nullptr);
@@ -85,6 +89,40 @@ int fast_run(esvio_fe_ctx* c, const uint8_t* img, int stride, int arc, int barri
   if (k) HIPCHK(c, hipStreamSynchronize(s));
   *n_out = (int32_t)tot[0];
   if (n_detected) *n_detected = (int32_t)(nonmax ? tot[1] : tot[0]);
+  if (c->prof_on) resolve_profile(c);
+  return 0;
+}
+
+// cv::FAST(image, keypoints, threshold, true) as include/esvio_fe.h "keyframes" states it (rule F), for
+// esvio_fe_kf_fast / esvio_fe_kf_describe: arc 9, the score, the strict 3x3 non-max, on the kernels and in the scratch
+// of fast_run above.  The whole list comes to the host (xy[i] = x | y << 16 in raster order, score[i]): a corner of
+// score 0 — possible at threshold 0 only — is not greater than the 0 of a pixel that is no corner and is dropped here,
+// which k_fast_collect's map of score + 1 cannot say.  Synchronises the stream.
+int fast_keyframe_run(esvio_fe_ctx* c, const uint8_t* img, int stride, int threshold, std::vector<uint32_t>& xy,
+                      std::vector<uint32_t>& score, int32_t* n_detected) {
+  esvio_fe_ctx::CandSet& cs = c->fast_own;
+  if (int rc = fast_own_alloc(c)) return rc;
+  hipStream_t s = cur_stream(c);
+  fast_lists(c, img, stride, 9, threshold, true, -1, cs, c->fast_own_fc, cs.total + 1);
+  uint32_t tot[2] = {0, 0};
+  HIPCHK(c, hipMemcpyAsync(tot, cs.total, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  if (tot[0] > cs.cap) return fail(c, ESVIO_FE_EINTERNAL, "kf_fast: %u corners in a set of %zu", tot[0], cs.cap);
+  xy.resize(tot[0]);
+  score.resize(tot[0]);
+  if (tot[0]) {
+    HIPCHK(c, hipMemcpyAsync(xy.data(), cs.comp_xy, (size_t)tot[0] * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(score.data(), cs.comp_idx, (size_t)tot[0] * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+  }
+  if (threshold == 0) {
+    size_t k = 0;
+    for (size_t i = 0; i < xy.size(); i++)
+      if (score[i]) xy[k] = xy[i], score[k++] = score[i];
+    xy.resize(k);
+    score.resize(k);
+  }
+  if (n_detected) *n_detected = (int32_t)tot[1];
   if (c->prof_on) resolve_profile(c);
   return 0;
 }

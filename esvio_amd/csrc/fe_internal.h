@@ -161,6 +161,10 @@ int gftt_run(esvio_fe_ctx* c, const PyrDesc& d, int max_corners, double quality,
 int fast_run(esvio_fe_ctx* c, const uint8_t* img, int stride, int arc, int barrier, bool nonmax, int16_t* out_xy,
              int32_t* out_score, int32_t capacity, int32_t* n_out, int32_t* n_detected);
 // (in a candidate set and FAST scratch of its own, esvio_fe_ctx::fast_own / fast_own_fc, allocated by the first call)
+// rule F of include/esvio_fe.h "keyframes" (cv::FAST, TYPE_9_16, non-max) in the same set and scratch: the whole list
+// on the host, raster order, xy[i] = x | y << 16; *n_detected (optional): the corners before non-max
+int fast_keyframe_run(esvio_fe_ctx* c, const uint8_t* img, int stride, int threshold, std::vector<uint32_t>& xy,
+                      std::vector<uint32_t>& score, int32_t* n_detected);
 // ESVIO_FE_DETECT_FAST (esvio_fe_ctx::fastc): everything the candidate passes and the stage tap need, allocated once;
 // what the stage tap alone needs
 int ensure_fast_detector(esvio_fe_ctx* c);

@@ -916,5 +916,35 @@ inline int disc_threshold(const int8_t* hw, int radius) {
   return inside >= 0 && inside < outside ? (int)inside : -1;
 }
 
+// ---- loop-closure keyframes: blur, BRIEF, matching (esvio_fe_kf_*) ----
+// include/esvio_fe.h "keyframes" holds the rules (B, F, D, M); all of it is integer arithmetic except D's one float
+// addition.  F runs on k_fast_score<9> / k_fast_collect / k_compact above as they are.  Three kernels of their own,
+// booked in timer slots of their own behind the event images' (esvio_fe_kf_kernel_*), outside the stage and ingest
+// tables.  No kernel waits on another workgroup; every loop is bounded by its arguments.
+//   k_kf_blur   cv::GaussianBlur(9 x 9, sigma 2) of an 8-bit image: a kKfBlurTileW x kKfBlurTileH tile per workgroup;
+//               the tile and its 4-pixel halo go into LDS once, the reflect-101 indices resolved at the load; the row
+//               pass leaves 16-bit sums in LDS (exact: at most 255 * 256), the column pass reads them, rounds once
+//               ((sum + 2^15) >> 16) and stores 4 pixels per lane — as one word where the four lie in the row and their
+//               address is a word's, byte by byte elsewhere (a width that is no multiple of 4).
+//   k_kf_brief  one wave per point, 4 tests per lane; the pattern (4 x 256 int8: x1 | y1 | x2 | y2) is copied into LDS
+//               by the workgroup; the gathers go to the blurred plane (dense, width bytes per row); a lane's 4 bits
+//               are OR-ed over its group of 8 lanes by shuffles into one of the point's 8 words, which lanes 0 and 32
+//               store as two 16-byte stores.
+//   k_kf_match  one workgroup per query: its 8 words in registers, the lanes stride over the train set (8 x xor +
+//               popcount); the reduction runs on the key dist << 20 | index, wave then block, so that the minimum key
+//               is the FIRST index of the minimal distance whatever order the lanes finish in.  nt <= 2^20.
+constexpr int kKfBlurTileW = 64, kKfBlurTileH = 16;
+constexpr int kKfPatternTests = 256;
+constexpr uint32_t kKfMatchMaxTrain = 1u << 20;
+constexpr int kKfBestInit = 128, kKfMatchDist = 80;  // ESVIO_FE_KF_BEST_INIT, ESVIO_FE_KF_MATCH_DIST
+// src: pixel (0,0), rows src_stride bytes apart; dst: dense width x height
+void launch_kf_blur(hipStream_t s, const uint8_t* src, int src_stride, int W, int H, uint8_t* dst);
+// pattern: [4][256] int8 (device); pts: [n] (x, y); desc: [n][8] words, 16-byte aligned
+void launch_kf_brief(hipStream_t s, const uint8_t* blurred, int W, int H, const int8_t* pattern, const float2* pts,
+                     uint32_t n, uint32_t* desc);
+// query [nq][8], train [nt][8] words, both 16-byte aligned; idx / dist [nq] int32, status [nq] bytes.  nq >= 1
+void launch_kf_match(hipStream_t s, const uint32_t* query, uint32_t nq, const uint32_t* train, uint32_t nt, int32_t* idx,
+                     int32_t* dist, uint8_t* status);
+
 
 }  // namespace esvio

@@ -6032,4 +6032,141 @@ void launch_evimg_canvas(hipStream_t s, const uint8_t* left, const uint8_t* righ
   launch_k(k_evimg_canvas, dim3((2u * (uint32_t)W * (uint32_t)H + 255u) / 256u), dim3(256), 0, s, left, right, W, H, canvas);
 }
 
+// ============================================================================ loop-closure keyframes
+// KeyFrame::KeyFrame's image passes (pose_graph/src/keyframe.cpp:34-63): include/esvio_fe.h "keyframes" holds the
+// rules, fe_kernels.h the chain.  (Behind the event images for the same reason as they.)
+constexpr int kKfHalo = 4, kKfSrcW = kKfBlurTileW + 2 * kKfHalo, kKfSrcH = kKfBlurTileH + 2 * kKfHalo;
+static_assert(kKfBlurTileW == 64 && kKfBlurTileH * (kKfBlurTileW / 4) == 256, "k_kf_blur: one lane per 4 pixels of the tile");
+
+// [OpenCV] getGaussianKernel(9, 2.0) in the 8-bit path's fixed point, sum 256
+__device__ __forceinline__ uint32_t kf_taps9(const uint32_t v0, const uint32_t v1, const uint32_t v2, const uint32_t v3,
+                                             const uint32_t v4, const uint32_t v5, const uint32_t v6, const uint32_t v7,
+                                             const uint32_t v8) {
+  return 7u * (v0 + v8) + 17u * (v1 + v7) + 32u * (v2 + v6) + 46u * (v3 + v5) + 52u * v4;
+}
+
+__global__ __launch_bounds__(256) void k_kf_blur(const uint8_t* __restrict__ src, int src_stride, int W, int H,
+                                                 uint8_t* __restrict__ dst) {
+  __shared__ uint8_t tile[kKfSrcH * kKfSrcW];
+  __shared__ uint16_t rows[kKfSrcH * kKfBlurTileW];
+  const int x0 = blockIdx.x * kKfBlurTileW, y0 = blockIdx.y * kKfBlurTileH;
+  // positions behind the image's own 4-pixel border (a tile that hangs over the right or lower edge) are clamped to
+  // it: nothing that is stored reads them, and one fold of reflect101 covers [-4, len + 3] for len >= 5
+  for (int i = threadIdx.x; i < kKfSrcH * kKfSrcW; i += 256) {
+    const int r = i / kKfSrcW, col = i - r * kKfSrcW;
+    const int gx = reflect101(min(x0 - kKfHalo + col, W + kKfHalo - 1), W);
+    const int gy = reflect101(min(y0 - kKfHalo + r, H + kKfHalo - 1), H);
+    tile[i] = src[(size_t)gy * src_stride + gx];
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < kKfSrcH * kKfBlurTileW; i += 256) {
+    const uint8_t* t = tile + (i >> 6) * kKfSrcW + (i & 63);
+    rows[i] = (uint16_t)kf_taps9(t[0], t[1], t[2], t[3], t[4], t[5], t[6], t[7], t[8]);  // <= 255 * 256
+  }
+  __syncthreads();
+  const int ty = threadIdx.x >> 4, tx = (threadIdx.x & 15) * 4;
+  const int x = x0 + tx, y = y0 + ty;
+  if (x >= W || y >= H) return;
+  uint32_t v[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const uint16_t* r = rows + ty * kKfBlurTileW + tx + k;
+    const uint32_t s = kf_taps9(r[0], r[kKfBlurTileW], r[2 * kKfBlurTileW], r[3 * kKfBlurTileW], r[4 * kKfBlurTileW],
+                                r[5 * kKfBlurTileW], r[6 * kKfBlurTileW], r[7 * kKfBlurTileW], r[8 * kKfBlurTileW]);
+    v[k] = (s + 32768u) >> 16;  // <= 255
+  }
+  uint8_t* out = dst + (size_t)y * W + x;
+  if (x + 4 <= W && ((uintptr_t)out & 3u) == 0) {
+    *(uint32_t*)out = v[0] | v[1] << 8 | v[2] << 16 | v[3] << 24;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+      if (x + k < W) out[k] = (uint8_t)v[k];
+  }
+}
+
+void launch_kf_blur(hipStream_t s, const uint8_t* src, int src_stride, int W, int H, uint8_t* dst) {
+  const dim3 grid((W + kKfBlurTileW - 1) / kKfBlurTileW, (H + kKfBlurTileH - 1) / kKfBlurTileH);
+  launch_k(k_kf_blur, grid, dim3(256), 0, s, src, src_stride, W, H, dst);
+}
+
+// DVision::BRIEF::compute's loop (pose_graph/src/ThirdParty/DVision/BRIEF.cpp:84-106) for 4 tests: (int)(p + (float)d)
+// is one float addition rounded to nearest, then truncated toward zero
+__global__ __launch_bounds__(256) void k_kf_brief(const uint8_t* __restrict__ img, int W, int H,
+                                                  const int8_t* __restrict__ pattern, const float2* __restrict__ pts,
+                                                  uint32_t n, uint32_t* __restrict__ desc) {
+  __shared__ int8_t pat[4 * kKfPatternTests];
+  ((uint32_t*)pat)[threadIdx.x] = ((const uint32_t*)pattern)[threadIdx.x];
+  __syncthreads();
+  const uint32_t p = blockIdx.x * 4u + (threadIdx.x >> 6);
+  if (p >= n) return;  // (the whole wave, behind the workgroup's only barrier)
+  const int lane = lane_id();
+  const float2 pt = pts[p];
+  uint32_t bits = 0;
+  if (fabsf(pt.x) < 32768.f && fabsf(pt.y) < 32768.f) {  // (false for a NaN or an infinity: the all-zero descriptor)
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const int i = lane * 4 + k;
+      const int X1 = (int)__fadd_rn(pt.x, (float)pat[i]), Y1 = (int)__fadd_rn(pt.y, (float)pat[kKfPatternTests + i]);
+      const int X2 = (int)__fadd_rn(pt.x, (float)pat[2 * kKfPatternTests + i]);
+      const int Y2 = (int)__fadd_rn(pt.y, (float)pat[3 * kKfPatternTests + i]);
+      if ((unsigned)X1 < (unsigned)W && (unsigned)Y1 < (unsigned)H && (unsigned)X2 < (unsigned)W && (unsigned)Y2 < (unsigned)H)
+        bits |= (uint32_t)(img[(size_t)Y1 * W + X1] < img[(size_t)Y2 * W + X2]) << k;
+    }
+  }
+  // bit i of the descriptor = word i >> 5, bit i & 31: lane l holds bits 4 l .. 4 l + 3, the 8 lanes of a group one word
+  uint32_t v = bits << ((lane & 7) * 4);
+  v |= __shfl_xor(v, 1);
+  v |= __shfl_xor(v, 2);
+  v |= __shfl_xor(v, 4);
+  const int base = lane & 32;
+  uint4 w;
+  w.x = __shfl(v, base);
+  w.y = __shfl(v, base + 8);
+  w.z = __shfl(v, base + 16);
+  w.w = __shfl(v, base + 24);
+  if ((lane & 31) == 0) ((uint4*)desc)[(size_t)p * 2 + (lane >> 5)] = w;
+}
+
+void launch_kf_brief(hipStream_t s, const uint8_t* blurred, int W, int H, const int8_t* pattern, const float2* pts,
+                     uint32_t n, uint32_t* desc) {
+  if (!n) return;
+  launch_k(k_kf_brief, dim3((n + 3u) / 4u), dim3(256), 0, s, blurred, W, H, pattern, pts, n, desc);
+}
+
+// KeyFrame::searchInAera (pose_graph/src/keyframe.cpp:183-212) for one query per workgroup
+__global__ __launch_bounds__(256) void k_kf_match(const uint4* __restrict__ query, const uint4* __restrict__ train,
+                                                  uint32_t nt, int32_t* __restrict__ idx, int32_t* __restrict__ dist,
+                                                  uint8_t* __restrict__ status) {
+  __shared__ uint32_t part[4];
+  const uint32_t q = blockIdx.x;
+  const uint4 a = query[(size_t)q * 2], b = query[(size_t)q * 2 + 1];
+  constexpr uint32_t none = (uint32_t)kKfBestInit << 20;  // `dis < bestDist` from bestDist = 128: a key at or above it never wins
+  uint32_t best = none;
+  for (uint32_t i = threadIdx.x; i < nt; i += 256u) {
+    const uint4 t0 = train[(size_t)i * 2], t1 = train[(size_t)i * 2 + 1];
+    const uint32_t d = __popc(a.x ^ t0.x) + __popc(a.y ^ t0.y) + __popc(a.z ^ t0.z) + __popc(a.w ^ t0.w) +
+                       __popc(b.x ^ t1.x) + __popc(b.y ^ t1.y) + __popc(b.z ^ t1.z) + __popc(b.w ^ t1.w);
+    best = min(best, d << 20 | i);  // (i < 2^20, d <= 256)
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) best = min(best, (uint32_t)__shfl_xor(best, o));
+  if (lane_id() == 0) part[threadIdx.x >> 6] = best;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    best = min(min(part[0], part[1]), min(part[2], part[3]));
+    const bool hit = best < none;
+    const int32_t d = hit ? (int32_t)(best >> 20) : kKfBestInit;
+    idx[q] = hit ? (int32_t)(best & (kKfMatchMaxTrain - 1u)) : -1;
+    dist[q] = d;
+    status[q] = (uint8_t)(hit && d < kKfMatchDist);
+  }
+}
+
+void launch_kf_match(hipStream_t s, const uint32_t* query, uint32_t nq, const uint32_t* train, uint32_t nt, int32_t* idx,
+                     int32_t* dist, uint8_t* status) {
+  if (!nq) return;
+  launch_k(k_kf_match, dim3(nq), dim3(256), 0, s, (const uint4*)query, (const uint4*)train, nt, idx, dist, status);
+}
+
 }  // namespace esvio

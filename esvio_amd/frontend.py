@@ -329,6 +329,8 @@ ABI_SYMBOLS = [
     "esvio_fe_slice_reset", "esvio_fe_track_batch", "esvio_fe_track_event", "esvio_fe_track_event_fields",
     "esvio_fe_track_event_filtered", "esvio_fe_track_event_mc", "esvio_fe_track_raw",
     "esvio_fe_track_image", "esvio_fe_unregister_host_buffer", "esvio_fe_version",
+    "esvio_fe_kf_set_pattern", "esvio_fe_kf_blur", "esvio_fe_kf_fast", "esvio_fe_kf_brief", "esvio_fe_kf_match",
+    "esvio_fe_kf_describe",
 ]
 # test / measurement taps: include/esvio_fe_test.h (not part of the boundary)
 TEST_SYMBOLS = [
@@ -345,6 +347,7 @@ TEST_SYMBOLS = [
     "esvio_fe_aedat_tile_events", "esvio_fe_ingest_kernel_count", "esvio_fe_aedat_walk_tap", "esvio_fe_aedat_walk_state_bytes",
     "esvio_fe_bag_tile_events", "esvio_fe_bag_walk_tap", "esvio_fe_bag_walk_state_bytes",
     "esvio_fe_bag_image_walk_tap", "esvio_fe_image_tile_pixels", "esvio_fe_event_image_kernel_stats",
+    "esvio_fe_kf_kernel_count", "esvio_fe_kf_kernel_name", "esvio_fe_kf_kernel_stats", "esvio_fe_kf_blur_tile",
 ]
 
 LATENCY_PHASES = 16
@@ -354,6 +357,54 @@ SELECT_EUCLID, SELECT_TABLE = 1, 2  # esvio_fe_select_candidates' flags (include
 class LatencyCall(C.Structure):  # esvio_fe_latency_call
     _fields_ = [("call", C.c_uint64), ("published", C.c_int32), ("reserved", C.c_int32), ("begin_ms", C.c_double),
                 ("ms", C.c_double), ("phase_ms", C.c_double * LATENCY_PHASES)]
+
+
+class KfOut(C.Structure):  # esvio_fe_kf_out
+    _fields_ = [("window_desc", C.c_void_p), ("kp_xy", C.c_void_p), ("kp_score", C.c_void_p), ("kp_norm", C.c_void_p),
+                ("kp_desc", C.c_void_p), ("kp_capacity", C.c_int32), ("n_kp", C.c_int32), ("n_detected", C.c_int32),
+                ("desc_space", C.c_int32)]
+
+
+KF_BEST_INIT, KF_MATCH_DIST = 128, 80  # ESVIO_FE_KF_BEST_INIT, ESVIO_FE_KF_MATCH_DIST
+
+
+def parse_brief_pattern(text):
+    """brief_pattern.yml as BriefExtractor reads it (keyframe.cpp:623-640): the four top-level lists x1, y1, x2, y2 of
+    the file's list-of-integers YAML (`key:` lines, `- value` items, or one flow list `key: [a, b, ...]`) ->
+    (x1, y1, x2, y2) int32 arrays.  Nothing else of YAML is understood; anything else raises ValueError."""
+    lists, cur = {}, None
+    for ln, raw in enumerate(text.splitlines(), 1):
+        line = raw.split("#", 1)[0].strip() if not raw.startswith("%") else ""
+        if not line or line == "---":
+            continue
+        if line.startswith("-"):
+            if cur is None:
+                raise ValueError("brief pattern, line %d: an item outside a list" % ln)
+            lists[cur].append(int(line[1:].strip()))
+        elif ":" in line:
+            key, rest = line.split(":", 1)
+            cur = key.strip()
+            lists[cur] = []
+            rest = rest.strip()
+            if rest:
+                if not (rest.startswith("[") and rest.endswith("]")):
+                    raise ValueError("brief pattern, line %d: not a list of integers" % ln)
+                lists[cur] = [int(v) for v in rest[1:-1].split(",") if v.strip()]
+                cur = None
+        else:
+            raise ValueError("brief pattern, line %d: %r" % (ln, raw))
+    try:
+        out = tuple(np.array(lists[k], np.int32) for k in ("x1", "y1", "x2", "y2"))
+    except KeyError as e:
+        raise ValueError("brief pattern: list %s is missing" % e)
+    if len({len(a) for a in out}) != 1:
+        raise ValueError("brief pattern: the four lists differ in length")
+    return out
+
+
+def load_brief_pattern(path):
+    with open(path) as f:
+        return parse_brief_pattern(f.read())
 
 
 class Latency(C.Structure):  # esvio_fe_latency
@@ -524,6 +575,17 @@ def load_library(build_if_missing=True):
     L.esvio_fe_ransac_tail.argtypes = [vp, i]
     L.esvio_fe_find_fundamental_mat_held.argtypes = [vp, vp, i, d, d, i, i, vp, C.POINTER(C.c_int32)]
     L.esvio_fe_find_fundamental_mat_idle.argtypes = [vp, vp, i, d, d, i, i, i, vp, C.POINTER(C.c_int32), vp]
+    i32p = C.POINTER(C.c_int32)
+    L.esvio_fe_kf_set_pattern.argtypes = [vp, vp, vp, vp, vp, i]
+    L.esvio_fe_kf_blur.argtypes = [vp, vp, i, vp, i]
+    L.esvio_fe_kf_fast.argtypes = [vp, vp, i, i, vp, vp, C.c_int32, i32p, i32p]
+    L.esvio_fe_kf_brief.argtypes = [vp, vp, i, vp, i, vp, i]
+    L.esvio_fe_kf_match.argtypes = [vp, vp, i, vp, i, i, vp, vp, vp]
+    L.esvio_fe_kf_describe.argtypes = [vp, i, vp, i, vp, i, i, C.POINTER(KfOut)]
+    L.esvio_fe_kf_kernel_name.restype = C.c_char_p
+    L.esvio_fe_kf_kernel_name.argtypes = [i]
+    L.esvio_fe_kf_kernel_stats.argtypes = [vp, i, C.POINTER(d), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.esvio_fe_kf_blur_tile.argtypes = [i32p, i32p]
     _lib = L
     return L
 
@@ -1651,6 +1713,122 @@ class FeatureTracker:
                                                       C.byref(k), C.byref(nc)))
         out = (xy[:k.value].copy(), sc[:k.value].copy())
         return out + (nc.value,) if want_count else out
+
+    # ---- loop-closure keyframes (esvio_fe_kf_*; include/esvio_fe.h "keyframes" has the rules)
+    def _kf_image(self, img):
+        """None (the handle's plane), a numpy (H,W) u8 image or a device image given as int pointer -> (ptr, space, keep)"""
+        if img is None:
+            return None, HOST, None
+        if isinstance(img, np.ndarray):
+            keep = np.ascontiguousarray(img, np.uint8)
+            if keep.shape != (self.cfg.height, self.cfg.width):
+                raise ValueError("image must be (height, width) of the handle")
+            return _p(keep), HOST, keep
+        return C.c_void_p(int(img)), DEVICE, None
+
+    def kf_set_pattern(self, x1, y1, x2, y2):
+        """the BRIEF pattern (esvio_fe_kf_set_pattern): four lists of 256 integers, as parse_brief_pattern returns
+        them; survives reset()"""
+        a = [np.ascontiguousarray(v, np.int32) for v in (x1, y1, x2, y2)]
+        n = len(a[0])
+        if any(len(v) != n for v in a):
+            raise ValueError("the four pattern lists differ in length")
+        self._hd.check(self._hd.L.esvio_fe_kf_set_pattern(self._hd.h, _p(a[0]), _p(a[1]), _p(a[2]), _p(a[3]), n))
+
+    def kf_blur(self, img=None, dst=None):
+        """cv::GaussianBlur(9x9, sigma 2) of the image (esvio_fe_kf_blur) -> numpy (H,W) u8, or into the device buffer
+        given as int pointer `dst`"""
+        ptr, space, keep = self._kf_image(img)
+        if dst is None:
+            out = np.empty((self.cfg.height, self.cfg.width), np.uint8)
+            self._hd.check(self._hd.L.esvio_fe_kf_blur(self._hd.h, ptr, space, _p(out), HOST))
+            return out
+        self._hd.check(self._hd.L.esvio_fe_kf_blur(self._hd.h, ptr, space, C.c_void_p(int(dst)), DEVICE))
+        return None
+
+    def kf_fast(self, img=None, threshold=20, capacity=None, want_count=False):
+        """cv::FAST(img, kps, threshold, true) (esvio_fe_kf_fast) -> (xy float32[n,2] in raster order, score int32[n]);
+        capacity: room for that many corners only (the first ones); want_count: also (n_out, n_detected)"""
+        hd = self._hd
+        ptr, space, keep = self._kf_image(img)
+        cap = 4096 if capacity is None else int(capacity)
+        n, nd = C.c_int32(0), C.c_int32(0)
+        while True:
+            xy = np.empty((max(cap, 1), 2), np.float32)
+            sc = np.empty(max(cap, 1), np.int32)
+            hd.check(hd.L.esvio_fe_kf_fast(hd.h, ptr, space, int(threshold), _p(xy), _p(sc), cap, C.byref(n), C.byref(nd)))
+            if capacity is not None or n.value <= cap:
+                break
+            cap = n.value
+        k = min(n.value, cap)
+        out = (xy[:k].copy(), sc[:k].copy())
+        return out + ((n.value, nd.value),) if want_count else out
+
+    def kf_brief(self, blurred, pts, desc=None):
+        """BRIEF::compute(treat_image = false) at the (x, y) float pairs `pts` on the blurred image (numpy or device
+        pointer; esvio_fe_kf_brief) -> uint32[n,8], or into the device buffer given as int pointer `desc`"""
+        ptr, space, keep = self._kf_image(blurred)
+        p = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
+        n = len(p)
+        if desc is None:
+            out = np.zeros((n, 8), np.uint32)
+            self._hd.check(self._hd.L.esvio_fe_kf_brief(self._hd.h, ptr, space, _p(p) if n else None, n, _p(out) if n else None, HOST))
+            return out
+        self._hd.check(self._hd.L.esvio_fe_kf_brief(self._hd.h, ptr, space, _p(p) if n else None, n, C.c_void_p(int(desc)), DEVICE))
+        return None
+
+    def kf_match(self, query, train, nq=None, nt=None):
+        """searchInAera for every query (esvio_fe_kf_match): numpy uint32[n,8] arrays, or device pointers (int) with
+        nq / nt -> (idx int32[nq], dist int32[nq], status uint8[nq])"""
+        if isinstance(query, np.ndarray):
+            q = np.ascontiguousarray(query, np.uint32).reshape(-1, 8)
+            t = np.ascontiguousarray(train, np.uint32).reshape(-1, 8)
+            nq, nt, space = len(q), len(t), HOST
+            qp, tp = (_p(q) if nq else None), (_p(t) if nt else None)
+        else:
+            space, qp, tp = DEVICE, C.c_void_p(int(query)), C.c_void_p(int(train))
+        idx, dist, st = np.zeros(max(nq, 1), np.int32), np.zeros(max(nq, 1), np.int32), np.zeros(max(nq, 1), np.uint8)
+        self._hd.check(self._hd.L.esvio_fe_kf_match(self._hd.h, qp, int(nq), tp, int(nt), space, _p(idx), _p(dist), _p(st)))
+        return idx[:nq], dist[:nq], st[:nq]
+
+    def keyframe_describe(self, img=None, window_pts=(), cam=0, fast_threshold=20, kp_capacity=None, device_desc=None):
+        """KeyFrame::KeyFrame's computeWindowBRIEFPoint + computeBRIEFPoint (esvio_fe_kf_describe) -> dict(window_desc,
+        kp_xy, kp_score, kp_norm, kp_desc, n_kp, n_detected).  device_desc: (window_desc_ptr, kp_desc_ptr) device
+        buffers (int) that take the descriptors instead of the returned arrays (then None in the dict)."""
+        hd = self._hd
+        ptr, space, keep = self._kf_image(img)
+        w = np.ascontiguousarray(window_pts, np.float32).reshape(-1, 2)
+        nw = len(w)
+        cap = 4096 if kp_capacity is None else int(kp_capacity)
+        while True:
+            m = max(cap, 1)
+            o = KfOut()
+            wd = np.zeros((max(nw, 1), 8), np.uint32)
+            kxy, ksc, knorm = np.zeros((m, 2), np.float32), np.zeros(m, np.int32), np.zeros((m, 2), np.float32)
+            kd = np.zeros((m, 8), np.uint32)
+            if device_desc is None:
+                o.window_desc, o.kp_desc, o.desc_space = wd.ctypes.data, kd.ctypes.data, HOST
+            else:
+                o.window_desc, o.kp_desc, o.desc_space = int(device_desc[0]), int(device_desc[1]), DEVICE
+            o.kp_xy, o.kp_score, o.kp_norm, o.kp_capacity = kxy.ctypes.data, ksc.ctypes.data, knorm.ctypes.data, cap
+            hd.check(hd.L.esvio_fe_kf_describe(hd.h, int(cam), ptr, space, _p(w) if nw else None, nw, int(fast_threshold), C.byref(o)))
+            if kp_capacity is not None or o.n_kp <= cap:
+                break
+            cap = o.n_kp
+        k = min(o.n_kp, cap)
+        host = device_desc is None
+        return dict(window_desc=wd[:nw] if host else None, kp_xy=kxy[:k], kp_score=ksc[:k], kp_norm=knorm[:k],
+                    kp_desc=kd[:k] if host else None, n_kp=int(o.n_kp), n_detected=int(o.n_detected))
+
+    def kf_kernel_stats(self):
+        """the keyframe stage's own kernel table (esvio_fe_kf_kernel_*): name -> dict(ms, launches, alg_bytes)"""
+        L = self._hd.L
+        out = {}
+        for k in range(L.esvio_fe_kf_kernel_count()):
+            ms, n, b = C.c_double(0), C.c_uint64(0), C.c_uint64(0)
+            self._hd.check(L.esvio_fe_kf_kernel_stats(self._hd.h, k, C.byref(ms), C.byref(n), C.byref(b)))
+            out[L.esvio_fe_kf_kernel_name(k).decode()] = dict(ms=ms.value, launches=n.value, alg_bytes=b.value)
+        return out
 
     # ---- camera split (right camera on another GPU)
     def export_image(self, cam, dst=None):

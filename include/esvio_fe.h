@@ -1425,6 +1425,102 @@ int esvio_fe_clear_event_images(esvio_fe_handle h);
 int esvio_fe_get_event_image(esvio_fe_handle h, int cam, uint8_t* dst, int space);
 int esvio_fe_get_event_canvas(esvio_fe_handle h, uint8_t* dst, int space);
 
+/* ---- keyframes: the image passes of the loop-closure keyframe (pose_graph) -------------------- */
+/* Every shipped parameter set has loop_closure: 1, and the image behind it is the left frame-camera topic
+ * (loop_closure_topic, config/.../esvio.yaml), which this library already holds as dense gray on the device
+ * (esvio_fe_decode_bag_images, esvio_fe_convert_image, esvio_fe_track_image_space).  For every keyframe
+ * KeyFrame::KeyFrame (pose_graph/src/keyframe.cpp:34-63) runs, on one CPU core: cv::GaussianBlur(9x9, sigma 2) of the
+ * frame — twice, with the same result, inside DVision::BRIEF::compute (ThirdParty/DVision/BRIEF.cpp:46-62; from
+ * computeWindowBRIEFPoint, keyframe.cpp:116-127, and computeBRIEFPoint, :133-161) —, cv::FAST(image, keypoints, 20,
+ * true) (:138), 256 BRIEF tests per window point and keypoint (BRIEF.cpp:84-106), liftProjective of every keypoint
+ * (:153-160), and for every loop candidate the brute-force Hamming search searchByBRIEFDes / searchInAera (:183-232).
+ * These calls are those passes.  DBoW2, PnP, the 4-DoF optimisation, the cv::resize of pose_graph_node.cpp:418-420 and
+ * the 80 x 60 thumbnail stay with the host.  This text is the specification; all of it is integer arithmetic except
+ * one float addition.
+ *
+ * B(I), the blur — cv::GaussianBlur(I, Size(9,9), 2, 2) for CV_8UC1, BORDER_REFLECT_101:
+ *   taps c = {7, 17, 32, 46, 52, 46, 32, 17, 7}, sum 256: getGaussianKernel(9, 2.0) x 256, rounded (plain rounding and
+ *   error-diffused rounding give the same nine values);
+ *   B[y][x] = (sum_j sum_i c_j c_i I[r(y+j-4)][r(x+i-4)] + 32768) >> 16, r the reflect-101 index (-1 -> 1, n -> n-2);
+ *   no rounding between the two passes: the row pass is exact in 16 bits.
+ *   This is OpenCV 4.2's fixed-point 8-bit path RESTATED FROM RECALL: it is UNPINNED — no vector of a compiled OpenCV
+ *   backs it here (tests/test_kf_vs_cv2.py is the kit that pins it where cv2 is at hand).
+ * F(I, t), the corners — cv::FAST(I, kps, t, true), TYPE_9_16:
+ *   for 3 <= x < W-3, 3 <= y < H-3 a pixel is a corner at barrier b when 9 contiguous of the 16 pixels of the radius-3
+ *   ring (circular; the ring of esvio_fe_fast_corners) are all > I + b or all < I - b;
+ *   score = the largest b at which it still is one: max over the 16 arcs of the arc's min |difference|, minus 1; the
+ *   score of every pixel that is no corner at barrier t is 0;
+ *   kept: the corners at barrier t whose score is strictly greater than all 8 neighbours' scores — so a corner of
+ *   score 0 (possible at t = 0 only) is never kept; order: raster (y, then x);
+ *   a kept corner is cv::KeyPoint(x, y, 7.f, -1, score): the calls return (float)x, (float)y and the score.
+ *   RESTATED FROM RECALL and UNPINNED like B (the same kit); stated this way it is a definition a test can brute-force.
+ * D(Bimg, p), the descriptor — BRIEF::compute(..., treat_image = false), BRIEF.cpp:84-106, with the pattern of
+ *   brief_pattern.yml as BriefExtractor loads it (keyframe.cpp:623-640): 256 tests (x1, y1, x2, y2)_i;
+ *   X1 = (int)(p.x + (float)x1_i): ONE float addition rounded to nearest, then truncation toward zero, and so for the
+ *   other three — p.x + x1 = -0.5 gives 0 and is inside, -1.0 is outside, 0.99999994f + 24 is 25;
+ *   bit i = 1 exactly when all four coordinates lie inside the image and Bimg[Y1][X1] < Bimg[Y2][X2];
+ *   output: 8 little-endian uint32 per point, bit i in word i >> 5 at bit i & 31 — boost::dynamic_bitset's bit i, so
+ *   DBoW2 takes the words unchanged;
+ *   the reference converts a non-finite coordinate with undefined behaviour; here a point with a non-finite
+ *   coordinate, or with |coordinate| >= 32768, gets the all-zero descriptor.
+ * M(Q, T), the match — searchInAera, keyframe.cpp:183-212: for a query q, dist = min_i popcount(q xor T_i), idx the
+ *   FIRST i that reaches it; only distances below ESVIO_FE_KF_BEST_INIT qualify, otherwise idx = -1, dist = 128;
+ *   status = (idx >= 0 && dist < ESVIO_FE_KF_MATCH_DIST).
+ *
+ * Images are width*height bytes of the handle's size, dense; every other size has to be brought to it by the host.
+ * ESVIO_FE_HOST images are copied to the device first, ESVIO_FE_DEVICE images are read in place.  img == NULL: the
+ * plane esvio_fe_export_image(h, cam, ...) returns (cam 0 except in esvio_fe_kf_describe), read in place and ordered
+ * after the work that renders it; refused when cfg.equalize != 0 — the pose graph sees the raw frame, not the CLAHE
+ * image.  Every call orders itself on the main stream, waits for its own result and touches nothing of the tracker:
+ * made between two track calls, announced batches or not, it changes no later result.  Scratch (the blurred plane, the
+ * FAST map and lists — esvio_fe_fast_corners' own —, point and descriptor buffers) is allocated on first use; the
+ * second call of a size allocates nothing.  Descriptors in ESVIO_FE_DEVICE memory are 16-byte aligned (esvio_fe_mem_alloc's
+ * are).  ESVIO_FE_EINVAL with a message, before any device work: a bad space; a threshold outside 0..255; a negative
+ * count or capacity, n or nq above 2^20, nt above 2^20; a null buffer with a non-zero count; dst overlapping img; a
+ * device descriptor pointer that is not 16-byte aligned; a descriptor call before esvio_fe_kf_set_pattern; cam outside
+ * 0..1.  A null handle: ESVIO_FE_EINVAL.
+ *
+ * esvio_fe_kf_set_pattern: the four arrays of the pattern file (host int32, n must be 256, every |value| <= 127; the
+ *   host parses the YAML).  A setting like esvio_fe_set_detector's: it survives esvio_fe_reset.
+ * esvio_fe_kf_blur: dst = B(img), width*height bytes in dst_space.
+ * esvio_fe_kf_fast: F(img, threshold).  *n_out is always the full count; at most `capacity` entries, the first ones,
+ *   are written to out_xy (x, y float pairs) and out_score (may be NULL).  *n_detected (may be NULL): the corners at the
+ *   barrier before the non-max.
+ * esvio_fe_kf_brief: D(blurred, p) at the n (x, y) float pairs of pts (host) -> n x 8 words in desc_space.
+ * esvio_fe_kf_match: M for nq queries against nt train descriptors, both in `space`; idx, dist (int32) and status
+ *   (bytes) on the host.  nq == 0 and nt == 0 succeed; with nt == 0 every result is -1 / 128 / 0.
+ * esvio_fe_kf_describe: the two compute*BRIEFPoint calls of the constructor — ONE blur; F on the UNBLURRED image;
+ *   D at the window points and at the kept corners on the blurred image; kp_norm[i] = (float)(x/z), (float)(y/z) of
+ *   liftProjective(kp_xy[i]) in double with cfg.cam[cam] (keyframe.cpp:156-158).  out: caller-owned buffers;
+ *   window_desc (n_window x 8 words) and kp_desc in desc_space — device memory, so that a later esvio_fe_kf_match reads
+ *   them in place, or host —, kp_xy / kp_score / kp_norm on the host; kp_capacity and n_kp as capacity and *n_out of
+ *   esvio_fe_kf_fast (every kp_* buffer holds the first min(n_kp, kp_capacity) corners; a NULL kp_* buffer is not
+ *   written).  The binding in keyframe.cpp: INTEGRATION.md. */
+#define ESVIO_FE_KF_BEST_INIT 128
+#define ESVIO_FE_KF_MATCH_DIST 80
+typedef struct esvio_fe_kf_out {
+  uint32_t* window_desc; /* [n_window][8], desc_space */
+  float* kp_xy;          /* [kp_capacity][2], host */
+  int32_t* kp_score;     /* [kp_capacity], host */
+  float* kp_norm;        /* [kp_capacity][2], host */
+  uint32_t* kp_desc;     /* [kp_capacity][8], desc_space */
+  int32_t kp_capacity;
+  int32_t n_kp;          /* out: the full count */
+  int32_t n_detected;    /* out: corners before the non-max */
+  int32_t desc_space;    /* ESVIO_FE_HOST / ESVIO_FE_DEVICE */
+} esvio_fe_kf_out;
+int esvio_fe_kf_set_pattern(esvio_fe_handle h, const int32_t* x1, const int32_t* y1, const int32_t* x2, const int32_t* y2,
+                            int n);
+int esvio_fe_kf_blur(esvio_fe_handle h, const uint8_t* img, int space, uint8_t* dst, int dst_space);
+int esvio_fe_kf_fast(esvio_fe_handle h, const uint8_t* img, int space, int threshold, float* out_xy, int32_t* out_score,
+                     int32_t capacity, int32_t* n_out, int32_t* n_detected);
+int esvio_fe_kf_brief(esvio_fe_handle h, const uint8_t* blurred, int space, const float* pts, int n, uint32_t* desc,
+                      int desc_space);
+int esvio_fe_kf_match(esvio_fe_handle h, const uint32_t* query, int nq, const uint32_t* train, int nt, int space,
+                      int32_t* idx, int32_t* dist, uint8_t* status);
+int esvio_fe_kf_describe(esvio_fe_handle h, int cam, const uint8_t* img, int space, const float* window_pts, int n_window,
+                         int fast_threshold, esvio_fe_kf_out* out);
+
 /* ---- camera split across GPUs (BASELINE config C4) ----------------------- */
 /* The left and right cameras have disjoint SAE state (sae_/sae_latest_ vs sae_right/
  * sae_latest_right, event_detector.h:74-79), so a second GPU can own the right camera: it runs

@@ -162,7 +162,7 @@ typedef struct esvio_fe_latency {
   int64_t max_invol_switches;
   int64_t max_allocs;
   double max_phase_ms[ESVIO_FE_LATENCY_PHASES];
-  uint64_t allocs;          /* allocations inside track / announce calls since the reset */
+  uint64_t allocs;          /* allocations inside track / announce / keyframe (esvio_fe_kf_*) calls since the reset */
   uint64_t invol_switches;  /* involuntary context switches inside track calls since the reset */
 } esvio_fe_latency;
 int esvio_fe_latency_stats(esvio_fe_handle h, esvio_fe_latency* out, int reset);
@@ -242,6 +242,15 @@ int esvio_fe_image_tile_pixels(void);
  * ingest tables: which = 0, k_evimg_mark; 1, k_evimg_emit (both forms); as esvio_fe_get_kernel_stats otherwise */
 int esvio_fe_event_image_kernel_stats(esvio_fe_handle h, int which, double* total_ms, uint64_t* launches,
                                       uint64_t* alg_bytes);
+/* the keyframe stage's kernels (esvio_fe_kf_*), a table of their own in timer slots outside the stage and ingest tables,
+ * which stay as they are: esvio_fe_kf_kernel_count() names, k_kf_blur, k_kf_brief, k_kf_match (the corners run on
+ * k_fast_score / k_fast_collect / k_compact of the stage table); esvio_fe_kf_kernel_name: "" for any other id;
+ * esvio_fe_kf_kernel_stats as esvio_fe_get_kernel_stats.  esvio_fe_kf_blur_tile: the pixels one workgroup of k_kf_blur
+ * writes — where its tile seams lie. */
+int esvio_fe_kf_kernel_count(void);
+const char* esvio_fe_kf_kernel_name(int which);
+int esvio_fe_kf_kernel_stats(esvio_fe_handle h, int which, double* total_ms, uint64_t* launches, uint64_t* alg_bytes);
+int esvio_fe_kf_blur_tile(int32_t* tile_w, int32_t* tile_h);
 /* the events one workgroup of the slicing chain takes (esvio_fe_slice_events): where its tile edges lie */
 int esvio_fe_slice_tile_events(void);
 /* the hipStream_t the handle launches on (as void*) */
