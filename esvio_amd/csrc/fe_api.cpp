@@ -4495,3 +4495,6 @@ int esvio_fe_bag_image_walk_tap(void* state, size_t state_bytes, const char* lef
 
 // ---- loop-closure keyframes (the rules: include/esvio_fe.h "keyframes"; the kernels: fe_kernels.h)
 #include "fe_kf.h"
+
+// ---- loop detection: DBoW2 words, database, L1 query (the rules: include/esvio_fe.h "loop detection")
+#include "fe_bow.h"

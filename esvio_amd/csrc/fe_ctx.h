@@ -108,9 +108,13 @@ struct PhaseClock {
 // the event images' two timer slots behind the ingest range: esvio_fe_event_image_kernel_stats reads them, the stage
 // and ingest tables (whose ends tests pin) stay as they are
 // ... and behind them the keyframe stage's three (esvio_fe_kf_kernel_count / _name / _stats, include/esvio_fe_test.h)
-enum { K_EVIMG_MARK = K_INGEST_COUNT, K_EVIMG_EMIT, K_KF_BLUR, K_KF_BRIEF, K_KF_MATCH, K_ALL_COUNT };
-constexpr int kKfKernels = K_ALL_COUNT - K_KF_BLUR;
+// ... and behind those loop detection's four (esvio_fe_bow_kernel_count / _name / _stats)
+enum { K_EVIMG_MARK = K_INGEST_COUNT, K_EVIMG_EMIT, K_KF_BLUR, K_KF_BRIEF, K_KF_MATCH, K_BOW_WALK, K_BOW_VECTOR, K_BOW_SCORE,
+       K_BOW_SELECT, K_ALL_COUNT };
+constexpr int kKfKernels = K_BOW_WALK - K_KF_BLUR;
 const char* const kKfKernelNames[kKfKernels] = {"k_kf_blur", "k_kf_brief", "k_kf_match"};
+constexpr int kBowKernels = K_ALL_COUNT - K_BOW_WALK;
+const char* const kBowKernelNames[kBowKernels] = {"k_bow_walk", "k_bow_vector", "k_bow_score", "k_bow_select"};
 
 struct KStat {
   double ms = 0;
@@ -709,6 +713,36 @@ struct esvio_fe_ctx {
     std::vector<float> h_pts;
     std::vector<double> lift_x, lift_y;
   } kf;
+
+  // ---- esvio_fe_bow_*: loop detection (include/esvio_fe.h "loop detection" has the rules, fe_kernels.h the kernels and
+  // the tree's device layout, fe_bow.h the host side).  The vocabulary is a SETTING and the database is pose-graph
+  // state: esvio_fe_reset touches neither.  Vocabulary: info as esvio_fe_bow_vocabulary_header fills it; the node arrays
+  // in the layout's order; word_weight[word id], the weight of the word's leaf; passes, the 8-bit sort passes that cover
+  // the keys 0..n_words.  Scratch of a transform (main stream only, grown on first use): desc, a host array's copy; word /
+  // weight per descriptor; keys / vals / sort, the radix sort's; heads; q_word / q_val, the vector; cnt, k_bow_vector's
+  // two counts and k_bow_select's one; err, the sort's look-back flag.  Database: db_word / db_val, the entries' vectors end
+  // to end; off (host) / db_off (device), entries + 1 offsets into them; score / present per entry and res_* per result
+  // of a query.
+  struct Bow {
+    bool has_voc = false;
+    esvio_fe_bow_vocabulary_info info = {};
+    int passes = 0;
+    DevBuf<uint4> node_desc;
+    DevBuf<uint2> kids;
+    DevBuf<int32_t> node_word;
+    DevBuf<double> node_weight, word_weight;
+    DevBuf<uint32_t> desc, keys[2], vals[2], sort, heads, q_word, cnt;
+    DevBuf<int32_t> word, err;
+    DevBuf<double> weight, q_val;
+    uint32_t q_n = 0;  // words in q_word / q_val
+    DevBuf<uint32_t> db_word;
+    DevBuf<double> db_val;
+    DevBuf<uint64_t> db_off;
+    std::vector<uint64_t> off = std::vector<uint64_t>(1, 0);
+    DevBuf<double> score, res_score, res_raw;
+    DevBuf<uint8_t> present;
+    DevBuf<int32_t> res_id;
+  } bow;
 };
 
 namespace esvio {

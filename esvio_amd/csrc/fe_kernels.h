@@ -946,5 +946,46 @@ void launch_kf_brief(hipStream_t s, const uint8_t* blurred, int W, int H, const 
 void launch_kf_match(hipStream_t s, const uint32_t* query, uint32_t nq, const uint32_t* train, uint32_t nt, int32_t* idx,
                      int32_t* dist, uint8_t* status);
 
+// ---- loop detection: DBoW2 words, vectors, the database's L1 scores (esvio_fe_bow_*) ----
+// include/esvio_fe.h "loop detection" holds the rules (V, W, T, A, Q, L): Hamming distances, integer sorting and IEEE
+// double additions, subtractions and one division in a stated order; no product anywhere.  Four kernels of their own in
+// timer slots behind the keyframes' (esvio_fe_bow_kernel_*); the sort between the first two is k_radix_pass as it is.
+// No kernel of the four waits on another workgroup; every loop is bounded by its arguments and by the tree, which the
+// host has checked (fe_bow.h: every child index lies inside the node arrays, every walk ends at a leaf).
+// The tree on the device: node 0 is the root, every node's children are contiguous and in child order —
+// kids[node] = {first child, child count}, count 0 at a leaf; node_desc[node] 8 words; node_word / node_weight at leaves.
+//   k_bow_walk    W: kBowGroup lanes per descriptor, 4 descriptors per wave.  A lane takes one child per round (32 bytes
+//                 as two 16-byte loads) and keeps its least distance with the lowest rank; the group reduces the distance,
+//                 then the rank among the lanes that hold that distance: the first child of the least distance, whatever
+//                 lane held it.  More children than lanes: more rounds.  Leaves word and weight per descriptor, and the
+//                 sort's input: key = word (or invalid_key, above every word, where the weight is not > 0), value =
+//                 index, the digit histograms of `passes` 8-bit passes.
+//   k_bow_vector  T behind the sort, ONE workgroup: the heads of the runs of equal keys compacted in order (ballot
+//                 ranks), run lengths as counts, per word the weight added count times one after another (repeat != 0)
+//                 or the weight itself, then the norm — lane 0 adds 1024 staged values at a time in ascending word order,
+//                 the chain the rule prescribes — and the division.  out[0] = words in the vector.
+//   k_bow_score   Q's sums: one wave per database entry (grid-stride), the entry's words in chunks of 64, each lane
+//                 looks its word up in the query's sorted words (binary search; in LDS up to kBowLdsWords words, in memory
+//                 beyond), the matching lanes' terms are added in lane (= word) order.  score[e], present[e].
+//   k_bow_select  one workgroup: max_results times the least (order-preserving bits of score, id) above the last one taken.
+constexpr int kBowGroup = 16;
+constexpr int kBowLdsWords = 4096;
+constexpr int kBowMaxResults = 64;
+constexpr int kBowVectorBlock = 1024;
+// desc [n][8] words, 16-byte aligned; word / weight / keys / vals [n]; ghist: the sort scratch's, cleared.  n >= 1
+void launch_bow_walk(hipStream_t s, const uint32_t* desc, uint32_t n, const uint4* node_desc, const uint2* kids,
+                     const int32_t* node_word, const double* node_weight, uint32_t invalid_key, int passes, int32_t* word,
+                     double* weight, uint32_t* keys, uint32_t* vals, uint32_t* ghist);
+// keys [n] sorted; heads [n] scratch; vec_word / vec_val [n]; out [2]: words in the vector, keys below invalid_key.  n >= 1
+void launch_bow_vector(hipStream_t s, const uint32_t* keys, uint32_t n, uint32_t invalid_key, const double* word_weight,
+                       int repeat, uint32_t* heads, uint32_t* vec_word, double* vec_val, uint32_t* out);
+// the query's m words; the database's pools and offsets [n_entries + 1]; score / present [n_entries].  n_entries >= 1
+void launch_bow_score(hipStream_t s, const uint32_t* q_word, const double* q_val, uint32_t m, const uint32_t* db_word,
+                      const double* db_val, const uint64_t* db_off, uint32_t n_entries, int max_id, double* score,
+                      uint8_t* present);
+// out_id / out_score / out_raw [max_results], *out_n: how many; out_score = -raw / 2.  n_entries >= 1
+void launch_bow_select(hipStream_t s, const double* score, const uint8_t* present, uint32_t n_entries, int max_results,
+                       int32_t* out_id, double* out_score, double* out_raw, uint32_t* out_n);
+
 
 }  // namespace esvio

@@ -6169,4 +6169,259 @@ void launch_kf_match(hipStream_t s, const uint32_t* query, uint32_t nq, const ui
   launch_k(k_kf_match, dim3(nq), dim3(256), 0, s, (const uint4*)query, (const uint4*)train, nt, idx, dist, status);
 }
 
+// ============================================================================ loop detection (esvio_fe_bow_*)
+// TemplatedVocabulary::transform(feature, id, weight) (pose_graph/src/ThirdParty/DBoW/TemplatedVocabulary.h:1217-1258)
+// with FBrief::distance (FBrief.cpp:53-57) for kBowGroup lanes per descriptor; fe_kernels.h has the layout of the tree.
+__global__ __launch_bounds__(256) void k_bow_walk(const uint4* __restrict__ desc, uint32_t n,
+                                                  const uint4* __restrict__ node_desc, const uint2* __restrict__ kids,
+                                                  const int32_t* __restrict__ node_word,
+                                                  const double* __restrict__ node_weight, uint32_t invalid_key, int passes,
+                                                  int32_t* __restrict__ word, double* __restrict__ weight,
+                                                  uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
+                                                  uint32_t* __restrict__ ghist) {
+  __shared__ uint32_t h[kRadixMaxPasses << kRadixMaxBits];
+  for (int i = threadIdx.x; i < (kRadixMaxPasses << kRadixMaxBits); i += 256) h[i] = 0;
+  __syncthreads();
+  const uint32_t g = (blockIdx.x * 256u + threadIdx.x) / kBowGroup, r0 = threadIdx.x % kBowGroup;
+  if (g < n) {  // (a whole group or none of it)
+    const uint4 a = desc[(size_t)g * 2], b = desc[(size_t)g * 2 + 1];
+    uint32_t node = 0;
+    uint2 kc = kids[0];
+    while (kc.y) {  // the same trip count for the lanes of a group: they hold the same node
+      uint32_t bd = 0xffffffffu, br = 0xffffffffu;
+      for (uint32_t r = r0; r < kc.y; r += kBowGroup) {  // ascending ranks and a strict <: a lane's first of its least
+        const uint4* c = node_desc + ((size_t)kc.x + r) * 2;
+        const uint4 t0 = c[0], t1 = c[1];
+        const uint32_t d = __popc(a.x ^ t0.x) + __popc(a.y ^ t0.y) + __popc(a.z ^ t0.z) + __popc(a.w ^ t0.w) +
+                           __popc(b.x ^ t1.x) + __popc(b.y ^ t1.y) + __popc(b.z ^ t1.z) + __popc(b.w ^ t1.w);
+        if (d < bd) bd = d, br = r;
+      }
+      uint32_t md = bd;
+#pragma unroll
+      for (int o = kBowGroup / 2; o > 0; o >>= 1) md = min(md, (uint32_t)__shfl_xor(md, o, kBowGroup));
+      uint32_t mr = bd == md ? br : 0xffffffffu;
+#pragma unroll
+      for (int o = kBowGroup / 2; o > 0; o >>= 1) mr = min(mr, (uint32_t)__shfl_xor(mr, o, kBowGroup));
+      node = kc.x + mr;  // (mr < kc.y: the lane that held md has a rank)
+      kc = kids[node];
+    }
+    if (r0 == 0) {
+      const int32_t w = node_word[node];
+      const double wt = node_weight[node];
+      const uint32_t key = wt > 0 ? (uint32_t)w : invalid_key;  // `if(w > 0)`: a NaN is stopped too
+      word[g] = w;
+      weight[g] = wt;
+      keys[g] = key;
+      vals[g] = g;
+      for (int p = 0; p < passes; p++) atomicAdd(&h[(p << kRadixMaxBits) + ((key >> (p * kRadixMaxBits)) & 255u)], 1u);
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < (passes << kRadixMaxBits); i += 256)
+    if (h[i]) atomicAdd(&ghist[i], h[i]);
+}
+
+void launch_bow_walk(hipStream_t s, const uint32_t* desc, uint32_t n, const uint4* node_desc, const uint2* kids,
+                     const int32_t* node_word, const double* node_weight, uint32_t invalid_key, int passes, int32_t* word,
+                     double* weight, uint32_t* keys, uint32_t* vals, uint32_t* ghist) {
+  if (!n) return;
+  constexpr uint32_t per_block = 256 / kBowGroup;
+  launch_k(k_bow_walk, dim3((n + per_block - 1) / per_block), dim3(256), 0, s, (const uint4*)desc, n, node_desc, kids,
+           node_word, node_weight, invalid_key, passes, word, weight, keys, vals, ghist);
+}
+
+// TemplatedVocabulary::transform(features, v) behind the walk and the sort (TemplatedVocabulary.h:1065-1121,
+// BowVector.cpp:34-84): addWeight's `+=` per hit, normalize(L1)'s `norm += fabs(value)` in map order, `value /= norm`.
+__global__ __launch_bounds__(kBowVectorBlock) void k_bow_vector(const uint32_t* __restrict__ keys, uint32_t n,
+                                                                uint32_t invalid_key,
+                                                                const double* __restrict__ word_weight, int repeat,
+                                                                uint32_t* __restrict__ heads, uint32_t* __restrict__ vec_word,
+                                                                double* __restrict__ vec_val, uint32_t* __restrict__ out) {
+  constexpr int kWaves = kBowVectorBlock / 64;
+  __shared__ uint32_t wave_heads[kWaves], wave_valid[kWaves];
+  __shared__ uint32_t s_heads, s_valid;
+  __shared__ double s_chunk[kBowVectorBlock];
+  __shared__ double s_norm;
+  const uint32_t tid = threadIdx.x, wave = tid >> 6;
+  const int lane = lane_id();
+  if (tid == 0) s_heads = 0, s_valid = 0, s_norm = 0.0;
+  __syncthreads();
+  // the heads of the runs, in order; the invalid keys are the sorted list's tail
+  for (uint32_t base = 0; base < n; base += kBowVectorBlock) {
+    const uint32_t i = base + tid;
+    const uint32_t k = i < n ? keys[i] : invalid_key;
+    const bool valid = k != invalid_key;
+    const bool head = valid && (i == 0 || keys[i - 1] != k);
+    const unsigned long long bh = __ballot(head), bv = __ballot(valid);
+    if (lane == 0) wave_heads[wave] = __popcll(bh), wave_valid[wave] = __popcll(bv);
+    __syncthreads();
+    uint32_t before = s_heads;
+    for (uint32_t w = 0; w < wave; w++) before += wave_heads[w];
+    if (head) heads[before + __popcll(bh & ((1ull << lane) - 1ull))] = i;
+    __syncthreads();
+    if (tid == 0)
+      for (int w = 0; w < kWaves; w++) s_heads += wave_heads[w], s_valid += wave_valid[w];
+    __syncthreads();
+  }
+  const uint32_t m = s_heads, nvalid = s_valid;
+  for (uint32_t j = tid; j < m; j += kBowVectorBlock) {
+    const uint32_t start = heads[j], end = j + 1 < m ? heads[j + 1] : nvalid;
+    const uint32_t wd = keys[start];
+    const double w = word_weight[wd];
+    double v = w;
+    if (repeat)
+      for (uint32_t t = start + 1; t < end; t++) v = __dadd_rn(v, w);  // ((w + w) + w) + ..., not count * w
+    vec_word[j] = wd;
+    vec_val[j] = v;
+  }
+  __syncthreads();
+  // the norm: one lane, ascending word id, from 0.0
+  for (uint32_t base = 0; base < m; base += kBowVectorBlock) {
+    const uint32_t j = base + tid;
+    s_chunk[tid] = j < m ? fabs(vec_val[j]) : 0.0;
+    __syncthreads();
+    if (tid == 0) {
+      double norm = s_norm;
+      const uint32_t cnt = min(m - base, (uint32_t)kBowVectorBlock);
+      for (uint32_t t = 0; t < cnt; t++) norm = __dadd_rn(norm, s_chunk[t]);
+      s_norm = norm;
+    }
+    __syncthreads();
+  }
+  const double norm = s_norm;
+  if (norm > 0.0)
+    for (uint32_t j = tid; j < m; j += kBowVectorBlock) vec_val[j] = __ddiv_rn(vec_val[j], norm);
+  if (tid == 0) out[0] = m, out[1] = nvalid;
+}
+
+void launch_bow_vector(hipStream_t s, const uint32_t* keys, uint32_t n, uint32_t invalid_key, const double* word_weight,
+                       int repeat, uint32_t* heads, uint32_t* vec_word, double* vec_val, uint32_t* out) {
+  if (!n) return;
+  launch_k(k_bow_vector, dim3(1), dim3(kBowVectorBlock), 0, s, keys, n, invalid_key, word_weight, repeat, heads, vec_word,
+           vec_val, out);
+}
+
+// TemplatedDatabase::queryL1's sums (TemplatedDatabase.h:656-696) entry by entry: the inverted file visits an entry's
+// shared words in ascending word id, and so do the lanes here
+template <bool kLds>
+__global__ __launch_bounds__(256) void k_bow_score(const uint32_t* __restrict__ q_word, const double* __restrict__ q_val,
+                                                   uint32_t m, const uint32_t* __restrict__ db_word,
+                                                   const double* __restrict__ db_val,
+                                                   const uint64_t* __restrict__ db_off, uint32_t n_entries, int max_id,
+                                                   double* __restrict__ score, uint8_t* __restrict__ present) {
+  __shared__ uint32_t sq[kLds ? kBowLdsWords : 1];
+  if (kLds) {
+    for (uint32_t i = threadIdx.x; i < m; i += 256) sq[i] = q_word[i];
+    __syncthreads();
+  }
+  const int lane = lane_id();
+  for (uint32_t e = blockIdx.x * 4u + (threadIdx.x >> 6); e < n_entries; e += gridDim.x * 4u) {  // wave-uniform
+    const bool takes_part = (int)e < max_id || max_id == -1 || e == n_entries - 1;
+    double s = 0.0;
+    bool any = false;
+    if (takes_part && m) {
+      const uint64_t end = db_off[e + 1];
+      for (uint64_t base = db_off[e]; base < end; base += 64) {
+        const uint64_t i = base + lane;
+        const bool ok = i < end;
+        const uint32_t w = ok ? db_word[i] : 0u;
+        uint32_t lo = 0, hi = m;  // lower bound of w in the query's words
+        while (lo < hi) {
+          const uint32_t mid = (lo + hi) >> 1;
+          const uint32_t qw = kLds ? sq[mid] : q_word[mid];
+          if (qw < w) lo = mid + 1; else hi = mid;
+        }
+        bool hit = false;
+        if (ok && lo < m) hit = (kLds ? sq[lo] : q_word[lo]) == w;
+        double term = 0.0;
+        if (hit) {
+          const double qv = q_val[lo], dv = db_val[i];
+          term = __dsub_rn(__dsub_rn(fabs(__dsub_rn(qv, dv)), fabs(qv)), fabs(dv));
+        }
+        unsigned long long hits = __ballot(hit);
+        while (hits) {  // in lane order = ascending word id; every lane keeps the same sum
+          const int l = __ffsll((long long)hits) - 1;
+          hits &= hits - 1;
+          const double t = __shfl(term, l);
+          s = any ? __dadd_rn(s, t) : t;
+          any = true;
+        }
+      }
+    }
+    if (lane == 0) score[e] = s, present[e] = (uint8_t)any;
+  }
+}
+
+void launch_bow_score(hipStream_t s, const uint32_t* q_word, const double* q_val, uint32_t m, const uint32_t* db_word,
+                      const double* db_val, const uint64_t* db_off, uint32_t n_entries, int max_id, double* score,
+                      uint8_t* present) {
+  if (!n_entries) return;
+  const uint32_t grid = std::min<uint32_t>((n_entries + 3u) / 4u, 1024u);
+  if (m <= (uint32_t)kBowLdsWords)
+    launch_k(k_bow_score<true>, dim3(grid), dim3(256), 0, s, q_word, q_val, m, db_word, db_val, db_off, n_entries, max_id,
+             score, present);
+  else
+    launch_k(k_bow_score<false>, dim3(grid), dim3(256), 0, s, q_word, q_val, m, db_word, db_val, db_off, n_entries, max_id,
+             score, present);
+}
+
+// a double's bits as an unsigned number of the same order (-0.0 taken as 0.0: equal scores are ordered by id)
+__device__ __forceinline__ unsigned long long bow_order_bits(double v) {
+  if (v == 0.0) v = 0.0;
+  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+  return (b >> 63) ? ~b : b | (1ull << 63);
+}
+
+// std::sort + resize + `Score = -Score / 2.0` of queryL1 (TemplatedDatabase.h:698-722), equal scores by ascending id
+__global__ __launch_bounds__(256) void k_bow_select(const double* __restrict__ score, const uint8_t* __restrict__ present,
+                                                    uint32_t n_entries, int max_results, int32_t* __restrict__ out_id,
+                                                    double* __restrict__ out_score, double* __restrict__ out_raw,
+                                                    uint32_t* __restrict__ out_n) {
+  __shared__ unsigned long long part_k[4];
+  __shared__ uint32_t part_i[4];
+  constexpr uint32_t none = 0xffffffffu;
+  unsigned long long last_k = 0;
+  uint32_t last_i = none;  // none: nothing taken yet
+  int r = 0;
+  for (; r < max_results; r++) {
+    // (~0ull is also the key of one NaN, 0x7fffffffffffffff; such an entry is still taken, by the id tie-break
+    // against `none`, which no entry has)
+    unsigned long long bk = ~0ull;
+    uint32_t bi = none;
+    for (uint32_t e = threadIdx.x; e < n_entries; e += 256u) {
+      if (!present[e]) continue;
+      const unsigned long long k = bow_order_bits(score[e]);
+      const bool above = last_i == none || k > last_k || (k == last_k && e > last_i);
+      if (above && (k < bk || (k == bk && e < bi))) bk = k, bi = e;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const unsigned long long ok = __shfl_xor(bk, o);
+      const uint32_t oi = __shfl_xor(bi, o);
+      if (ok < bk || (ok == bk && oi < bi)) bk = ok, bi = oi;
+    }
+    if (lane_id() == 0) part_k[threadIdx.x >> 6] = bk, part_i[threadIdx.x >> 6] = bi;
+    __syncthreads();
+    bk = part_k[0], bi = part_i[0];
+    for (int w = 1; w < 4; w++)
+      if (part_k[w] < bk || (part_k[w] == bk && part_i[w] < bi)) bk = part_k[w], bi = part_i[w];
+    __syncthreads();
+    if (bi == none) break;  // (the whole workgroup: everybody read the same four pairs)
+    if (threadIdx.x == 0) {
+      const double s = score[bi];
+      out_id[r] = (int32_t)bi;
+      out_raw[r] = s;
+      out_score[r] = __ddiv_rn(-s, 2.0);
+    }
+    last_k = bk, last_i = bi;
+  }
+  if (threadIdx.x == 0) *out_n = (uint32_t)r;
+}
+
+void launch_bow_select(hipStream_t s, const double* score, const uint8_t* present, uint32_t n_entries, int max_results,
+                       int32_t* out_id, double* out_score, double* out_raw, uint32_t* out_n) {
+  if (!n_entries) return;
+  launch_k(k_bow_select, dim3(1), dim3(256), 0, s, score, present, n_entries, max_results, out_id, out_score, out_raw, out_n);
+}
+
 }  // namespace esvio

@@ -331,6 +331,8 @@ ABI_SYMBOLS = [
     "esvio_fe_track_image", "esvio_fe_unregister_host_buffer", "esvio_fe_version",
     "esvio_fe_kf_set_pattern", "esvio_fe_kf_blur", "esvio_fe_kf_fast", "esvio_fe_kf_brief", "esvio_fe_kf_match",
     "esvio_fe_kf_describe",
+    "esvio_fe_bow_vocabulary_header", "esvio_fe_bow_set_vocabulary", "esvio_fe_bow_transform", "esvio_fe_bow_add",
+    "esvio_fe_bow_query", "esvio_fe_bow_detect_loop", "esvio_fe_bow_clear", "esvio_fe_bow_entries", "esvio_fe_bow_reserve",
 ]
 # test / measurement taps: include/esvio_fe_test.h (not part of the boundary)
 TEST_SYMBOLS = [
@@ -348,6 +350,7 @@ TEST_SYMBOLS = [
     "esvio_fe_bag_tile_events", "esvio_fe_bag_walk_tap", "esvio_fe_bag_walk_state_bytes",
     "esvio_fe_bag_image_walk_tap", "esvio_fe_image_tile_pixels", "esvio_fe_event_image_kernel_stats",
     "esvio_fe_kf_kernel_count", "esvio_fe_kf_kernel_name", "esvio_fe_kf_kernel_stats", "esvio_fe_kf_blur_tile",
+    "esvio_fe_bow_kernel_count", "esvio_fe_bow_kernel_name", "esvio_fe_bow_kernel_stats", "esvio_fe_bow_limits", "esvio_fe_bow_scores",
 ]
 
 LATENCY_PHASES = 16
@@ -366,6 +369,42 @@ class KfOut(C.Structure):  # esvio_fe_kf_out
 
 
 KF_BEST_INIT, KF_MATCH_DIST = 128, 80  # ESVIO_FE_KF_BEST_INIT, ESVIO_FE_KF_MATCH_DIST
+
+
+class BowVocabularyInfo(C.Structure):  # esvio_fe_bow_vocabulary_info
+    _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("scoring", C.c_int32), ("weighting", C.c_int32), ("nodes", C.c_int32),
+                ("words", C.c_int32), ("leaves", C.c_int32), ("max_children", C.c_int32), ("depth", C.c_int32),
+                ("message", C.c_char * 188)]
+
+
+class BowResult(C.Structure):  # esvio_fe_bow_result
+    _fields_ = [("id", C.c_int32), ("score", C.c_double)]
+
+
+class BowLimits(C.Structure):  # esvio_fe_bow_limits_info
+    _fields_ = [("group_lanes", C.c_int32), ("lds_words", C.c_int32), ("vector_block", C.c_int32), ("max_results", C.c_int32)]
+
+
+# ESVIO_FE_BOW_MAX_RESULTS, _LOOP_RESULTS, _LOOP_GAP, _LOOP_MIN_FIRST, _LOOP_MIN_OTHER
+BOW_MAX_RESULTS, BOW_LOOP_RESULTS, BOW_LOOP_GAP, BOW_LOOP_MIN_FIRST, BOW_LOOP_MIN_OTHER = 64, 4, 50, 0.05, 0.015
+
+
+def bow_vocabulary_header(data):
+    """esvio_fe_bow_vocabulary_header on a vocabulary file's bytes (no handle, no device) -> (return code, dict of the
+    info struct's fields, message as str)"""
+    buf = bytes(data)
+    info = BowVocabularyInfo()
+    rc = load_library().esvio_fe_bow_vocabulary_header(buf, len(buf), C.byref(info))
+    d = {n: getattr(info, n) for n, _ in BowVocabularyInfo._fields_ if n != "message"}
+    d["message"] = info.message.decode()
+    return rc, d
+
+
+def bow_limits():
+    """esvio_fe_bow_limits -> dict"""
+    o = BowLimits()
+    assert load_library().esvio_fe_bow_limits(C.byref(o)) == 0
+    return {n: getattr(o, n) for n, _ in BowLimits._fields_}
 
 
 def parse_brief_pattern(text):
@@ -586,6 +625,20 @@ def load_library(build_if_missing=True):
     L.esvio_fe_kf_kernel_name.argtypes = [i]
     L.esvio_fe_kf_kernel_stats.argtypes = [vp, i, C.POINTER(d), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.esvio_fe_kf_blur_tile.argtypes = [i32p, i32p]
+    L.esvio_fe_bow_vocabulary_header.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(BowVocabularyInfo)]
+    L.esvio_fe_bow_set_vocabulary.argtypes = [vp, C.c_char_p, C.c_size_t]
+    L.esvio_fe_bow_transform.argtypes = [vp, vp, i, i, vp, vp, vp, vp, C.c_int32, i32p]
+    L.esvio_fe_bow_add.argtypes = [vp, vp, i, i, i32p]
+    L.esvio_fe_bow_query.argtypes = [vp, vp, i, i, i, i, C.POINTER(BowResult), i32p]
+    L.esvio_fe_bow_detect_loop.argtypes = [vp, vp, i, i, i, i32p, C.POINTER(BowResult), i32p]
+    L.esvio_fe_bow_clear.argtypes = [vp]
+    L.esvio_fe_bow_entries.argtypes = [vp]
+    L.esvio_fe_bow_reserve.argtypes = [vp, C.c_int64, C.c_int64]
+    L.esvio_fe_bow_kernel_name.restype = C.c_char_p
+    L.esvio_fe_bow_kernel_name.argtypes = [i]
+    L.esvio_fe_bow_kernel_stats.argtypes = [vp, i, C.POINTER(d), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.esvio_fe_bow_limits.argtypes = [C.POINTER(BowLimits)]
+    L.esvio_fe_bow_scores.argtypes = [vp, vp, i, i, i, vp, vp]
     _lib = L
     return L
 
@@ -1828,6 +1881,78 @@ class FeatureTracker:
             ms, n, b = C.c_double(0), C.c_uint64(0), C.c_uint64(0)
             self._hd.check(L.esvio_fe_kf_kernel_stats(self._hd.h, k, C.byref(ms), C.byref(n), C.byref(b)))
             out[L.esvio_fe_kf_kernel_name(k).decode()] = dict(ms=ms.value, launches=n.value, alg_bytes=b.value)
+        return out
+
+    # ---- loop detection (esvio_fe_bow_*; include/esvio_fe.h "loop detection" has the rules)
+    def _bow_desc(self, desc, n):
+        """numpy uint32[n,8] descriptors, or a device pointer (int) with n -> (ptr, n, space, keep)"""
+        if isinstance(desc, np.ndarray):
+            keep = np.ascontiguousarray(desc, np.uint32).reshape(-1, 8)
+            return (_p(keep) if len(keep) else None), len(keep), HOST, keep
+        return C.c_void_p(int(desc)), int(n), DEVICE, None
+
+    def bow_set_vocabulary(self, data):
+        """the vocabulary file's bytes (esvio_fe_bow_set_vocabulary); survives reset()"""
+        buf = bytes(data)
+        self._hd.check(self._hd.L.esvio_fe_bow_set_vocabulary(self._hd.h, buf, len(buf)))
+
+    def bow_transform(self, desc, n=None, bow_cap=None):
+        """W and T (esvio_fe_bow_transform) -> dict(word int32[n], weight float64[n], bow_word uint32[m], bow_value
+        float64[m], n_bow); bow_cap: room for that many pairs only (n_bow is the full count)"""
+        ptr, n, space, keep = self._bow_desc(desc, n)
+        cap = n if bow_cap is None else int(bow_cap)
+        word, weight = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.float64)
+        bw, bv, m = np.zeros(max(cap, 1), np.uint32), np.zeros(max(cap, 1), np.float64), C.c_int32(0)
+        self._hd.check(self._hd.L.esvio_fe_bow_transform(self._hd.h, ptr, n, space, _p(word), _p(weight), _p(bw), _p(bv), cap, C.byref(m)))
+        k = min(m.value, cap)
+        return dict(word=word[:n], weight=weight[:n], bow_word=bw[:k], bow_value=bv[:k], n_bow=m.value)
+
+    def bow_add(self, desc, n=None):
+        """db.add(desc) (esvio_fe_bow_add) -> the new entry's id"""
+        ptr, n, space, keep = self._bow_desc(desc, n)
+        e = C.c_int32(-1)
+        self._hd.check(self._hd.L.esvio_fe_bow_add(self._hd.h, ptr, n, space, C.byref(e)))
+        return e.value
+
+    def bow_query(self, desc, max_results=BOW_LOOP_RESULTS, max_id=-1, n=None):
+        """db.query(desc, ret, max_results, max_id) (esvio_fe_bow_query) -> [(id, score), ...]"""
+        ptr, n, space, keep = self._bow_desc(desc, n)
+        res, k = (BowResult * BOW_MAX_RESULTS)(), C.c_int32(0)
+        self._hd.check(self._hd.L.esvio_fe_bow_query(self._hd.h, ptr, n, space, int(max_results), int(max_id), res, C.byref(k)))
+        return [(res[j].id, res[j].score) for j in range(k.value)]
+
+    def detect_loop(self, desc, frame_index, n=None):
+        """PoseGraph::detectLoop's query, add and decision (esvio_fe_bow_detect_loop) -> (loop index or -1, [(id, score), ...])"""
+        ptr, n, space, keep = self._bow_desc(desc, n)
+        res, k, m = (BowResult * BOW_LOOP_RESULTS)(), C.c_int32(0), C.c_int32(-1)
+        self._hd.check(self._hd.L.esvio_fe_bow_detect_loop(self._hd.h, ptr, n, space, int(frame_index), C.byref(m), res, C.byref(k)))
+        return m.value, [(res[j].id, res[j].score) for j in range(k.value)]
+
+    def bow_scores(self, desc, max_id=-1, n=None):
+        """the raw sums of a query (esvio_fe_bow_scores, a test tap) -> (score float64[entries], present bool[entries])"""
+        ptr, n, space, keep = self._bow_desc(desc, n)
+        N = self.bow_entries()
+        sc, pr = np.zeros(max(N, 1), np.float64), np.zeros(max(N, 1), np.uint8)
+        self._hd.check(self._hd.L.esvio_fe_bow_scores(self._hd.h, ptr, n, space, int(max_id), _p(sc), _p(pr)))
+        return sc[:N], pr[:N].astype(bool)
+
+    def bow_entries(self):
+        return self._hd.L.esvio_fe_bow_entries(self._hd.h)
+
+    def bow_clear(self):
+        self._hd.check(self._hd.L.esvio_fe_bow_clear(self._hd.h))
+
+    def bow_reserve(self, entries, words):
+        self._hd.check(self._hd.L.esvio_fe_bow_reserve(self._hd.h, int(entries), int(words)))
+
+    def bow_kernel_stats(self):
+        """loop detection's own kernel table (esvio_fe_bow_kernel_*): name -> dict(ms, launches, alg_bytes)"""
+        L = self._hd.L
+        out = {}
+        for k in range(L.esvio_fe_bow_kernel_count()):
+            ms, n, b = C.c_double(0), C.c_uint64(0), C.c_uint64(0)
+            self._hd.check(L.esvio_fe_bow_kernel_stats(self._hd.h, k, C.byref(ms), C.byref(n), C.byref(b)))
+            out[L.esvio_fe_bow_kernel_name(k).decode()] = dict(ms=ms.value, launches=n.value, alg_bytes=b.value)
         return out
 
     # ---- camera split (right camera on another GPU)

@@ -1434,8 +1434,8 @@ int esvio_fe_get_event_canvas(esvio_fe_handle h, uint8_t* dst, int space);
  * computeWindowBRIEFPoint, keyframe.cpp:116-127, and computeBRIEFPoint, :133-161) —, cv::FAST(image, keypoints, 20,
  * true) (:138), 256 BRIEF tests per window point and keypoint (BRIEF.cpp:84-106), liftProjective of every keypoint
  * (:153-160), and for every loop candidate the brute-force Hamming search searchByBRIEFDes / searchInAera (:183-232).
- * These calls are those passes.  DBoW2, PnP, the 4-DoF optimisation, the cv::resize of pose_graph_node.cpp:418-420 and
- * the 80 x 60 thumbnail stay with the host.  This text is the specification; all of it is integer arithmetic except
+ * These calls are those passes.  DBoW2's words, database and query are the next group ("loop detection" below); PnP, the
+ * 4-DoF optimisation, the cv::resize of pose_graph_node.cpp:418-420 and the 80 x 60 thumbnail stay with the host.  This text is the specification; all of it is integer arithmetic except
  * one float addition.
  *
  * B(I), the blur — cv::GaussianBlur(I, Size(9,9), 2, 2) for CV_8UC1, BORDER_REFLECT_101:
@@ -1520,6 +1520,116 @@ int esvio_fe_kf_match(esvio_fe_handle h, const uint32_t* query, int nq, const ui
                       int32_t* idx, int32_t* dist, uint8_t* status);
 int esvio_fe_kf_describe(esvio_fe_handle h, int cam, const uint8_t* img, int space, const float* window_pts, int n_window,
                          int fast_threshold, esvio_fe_kf_out* out);
+
+/* ---- loop detection: DBoW2 words, database and L1 query (pose_graph) --------------------------- */
+/* What the keyframe's descriptors are computed for: PoseGraph::detectLoop (pose_graph/src/pose_graph.cpp:331-406) hands
+ * keyframe->brief_descriptors to DBoW2 — db.query(desc, ret, 4, frame_index - 50), db.add(desc), and a rule on the
+ * scores that names the loop candidate or -1.  These calls are that step, so that a keyframe's way from the frame
+ * (esvio_fe_kf_describe, descriptors left in device memory) to the candidate (esvio_fe_kf_match) stays on the device.
+ * PnP, the 4-DoF optimisation and the DEBUG_IMAGE canvases stay with the host; so do the direct index / FeatureVector
+ * (use_di is false, pose_graph.cpp:49), scorings other than L1, vocabulary creation, delete_entry and the text
+ * vocabulary format.  This text is the specification.  Everything is integer arithmetic plus IEEE double additions,
+ * subtractions and one division in a stated order; no rule has a product.
+ * WHAT IS PINNED: BowVector's addWeight / addIfNotExist / normalize(L1) (ThirdParty/DBoW/BowVector.cpp:34-84) are held
+ * to outputs of that file compiled unchanged (tests/golden/bow_vector_ref.npz).  The rest of DBoW2 includes OpenCV and
+ * boost; its rules are CITED BY LINE AND RESTATED here, unpinned.  Every vocabulary in the tests and measurements is
+ * synthetic: the shipped brief_k10L6.bin is not at hand.
+ *
+ * V, the vocabulary file — ThirdParty/VocabularyBinary.hpp:12-45, VocabularyBinary.cpp:29-37, TemplatedVocabulary.h:
+ *   1509-1561 (loadBin): 24 bytes {k, L, scoringType, weightingType, nNodes, nWords}, little-endian int32; nNodes records
+ *   of 48 bytes {int32 nodeId, int32 parentId, double weight, uint64 descriptor[4]}; nWords records of 8 bytes {int32
+ *   nodeId, int32 wordId}.  Node 0 is the root and is not in the file.  A node's children are in the order in which their
+ *   records appear (children.push_back), whatever their ids.  Descriptor bit i is bit i & 63 of descriptor[i >> 6] — the
+ *   bit esvio_fe_kf_brief's eight uint32 hold it at, so the words go in unchanged.  weightingType 0..3 = TF_IDF, TF, IDF,
+ *   BINARY; scoringType 0 = L1_NORM (BowVector.h:36-53).  A word record sets its node's word id; of two records that
+ *   name one node the later stands (`m_nodes[nid].word_id = wid`).
+ *   The reference trusts the file.  Here a file that would make it read out of bounds is refused by name
+ *   (ESVIO_FE_EINVAL, before any device work): a byte count other than the header implies; nNodes < 1; a nodeId outside
+ *   1..nNodes or duplicated; a parentId outside 0..nNodes or equal to its node; a node not reachable from the root; a
+ *   root without children; a wordId outside 0..nWords-1 or duplicated; a word on a node that has children (or on a node
+ *   outside 1..nNodes); a leaf without a word; a weighting outside 0..3.  Scoring other than L1_NORM: ESVIO_FE_ENOTIMPL.
+ * W, the word of a descriptor — TemplatedVocabulary.h:1217-1258, FBrief.cpp:53-57: from the root, go to the child with
+ *   the least popcount(d xor child); of equal distances the first in child order (`d < best_d` is strict); stop at a
+ *   leaf: its word_id and weight.  The walk follows the tree, not L: leaves at any depth, any child count >= 1.
+ * T, the BoW vector — TemplatedVocabulary.h:1065-1121, BowVector.cpp:34-84, ScoringObject.h:73 (L1 scoring normalises
+ *   with L1): descriptors whose weight is not > 0 are skipped.  TF_IDF, TF: the value of a word hit c times is w added c
+ *   times one after another, ((w + w) + w) + ..., not c * w.  IDF, BINARY: w.  norm = the sum of fabs(value) in ascending
+ *   word id, one addition after another from 0.0; if norm > 0.0 every value is divided by it (IEEE division).  The vector
+ *   is the list of (word, value) in ascending word id.
+ * A, add — TemplatedDatabase.h:408-475: entry id = entries so far; its vector is T(desc); empty vectors make entries too.
+ * Q, query — TemplatedDatabase.h:607-723: q = T(desc), N = entries now.  Entry e takes part iff e < max_id ||
+ *   max_id == -1 || e == N - 1 (the last entry always does; max_id == -1 admits all; any other max_id <= 0 the last
+ *   alone).  For an entry that takes part and shares a word with q, s_e = the sum over the shared words in ascending
+ *   word id of fabs(qv - dv) - fabs(qv) - fabs(dv), each term left to right in double, the first term starting the sum;
+ *   entries that share no word are absent.  Results by ascending s_e, cut at max_results, then Score = -s_e / 2.0.
+ *   The reference orders with std::sort on the score alone, so the order of equal scores is its library's; HERE EQUAL
+ *   SCORES ARE ORDERED BY ASCENDING ENTRY ID — this project's own rule (-0.0 and 0.0 are equal; a NaN, which only a
+ *   file with non-finite weights produces, is ordered by its bits — the NaN 0x7fffffffffffffff has the largest key
+ *   there is and comes last).  max_results is 1..ESVIO_FE_BOW_MAX_RESULTS; the
+ *   reference's "all results" form (<= 0) has no caller in ESVIO: ESVIO_FE_EINVAL.
+ * L, the loop decision — pose_graph.cpp:347-404: R = Q(desc, ESVIO_FE_BOW_LOOP_RESULTS, frame_index -
+ *   ESVIO_FE_BOW_LOOP_GAP), then A(desc).  find = |R| >= 1 && R[0].Score > ESVIO_FE_BOW_LOOP_MIN_FIRST && (exists i >= 1:
+ *   R[i].Score > ESVIO_FE_BOW_LOOP_MIN_OTHER).  If find && frame_index > ESVIO_FE_BOW_LOOP_GAP: m = -1; for i = 0..: if
+ *   m == -1 || (R[i].Id < m && R[i].Score > ESVIO_FE_BOW_LOOP_MIN_OTHER) then m = R[i].Id; the answer is m.  Otherwise -1.
+ *   So R[0] is taken whatever its score is to 0.015, and at frame_index 49 max_id is -1: everything takes part.
+ *
+ * Conventions: the keyframe group's.  desc: n x 8 words in `space` (ESVIO_FE_HOST: copied first; ESVIO_FE_DEVICE: read
+ * in place, 16-byte aligned), 0 <= n <= 2^20.  Every argument error is ESVIO_FE_EINVAL with a message, before any device
+ * work; a null handle: ESVIO_FE_EINVAL.  Every call orders itself on the main stream, waits for its own result and
+ * touches nothing of the tracker: made between two track calls, batches announced or not, it changes no later result.
+ * No track path launches anything of this group; the group's own sort passes are k_radix_pass launches and are counted
+ * in that slot of the track path's kernel statistics (esvio_fe_get_kernel_stats) when profiling is on.
+ * Every call but esvio_fe_bow_vocabulary_header, _set_vocabulary and _entries is ESVIO_FE_EINVAL before a vocabulary is
+ * set.  The vocabulary is a setting and survives esvio_fe_reset; the database is pose-graph state: esvio_fe_reset does
+ * not touch it, esvio_fe_bow_clear empties it.
+ *
+ * esvio_fe_bow_vocabulary_header: checks V on a file image in host memory and fills info; takes no handle and uses no
+ *   device.  On a refusal info->message names the item.  max_children: the largest child count; depth: the deepest
+ *   leaf's (the root's children are at depth 1); leaves: nodes without children.
+ * esvio_fe_bow_set_vocabulary: checks V, lays the tree out for the device (every node's children contiguous in child
+ *   order, descriptors apart from weights) and uploads it.  Refused while the database holds entries.
+ * esvio_fe_bow_transform: W and T.  word / weight (host, n entries each, either may be NULL): W per descriptor.  bow_word /
+ *   bow_value (host): the first min(*n_bow, bow_cap) pairs of T; *n_bow (may be NULL with bow_cap 0) is the full count.
+ * esvio_fe_bow_add: A; *entry_id (may be NULL) is the new entry's id.
+ * esvio_fe_bow_query: Q; results (host, room for max_results), *n_results how many.
+ * esvio_fe_bow_detect_loop: L — the descriptors are transformed once for the query and the add; *loop_index the answer;
+ *   results / n_results (both may be NULL): R, room for ESVIO_FE_BOW_LOOP_RESULTS.
+ * esvio_fe_bow_entries: the entries now (0 before a vocabulary).  esvio_fe_bow_reserve(h, entries, words): room for that
+ *   many entries and that many (word, value) pairs in all; adds and queries inside it allocate nothing beyond the scratch
+ *   the first call of a descriptor count allocates.  Without a reserve the pools grow like the other buffers, a quarter
+ *   to spare, earlier entries kept.  The binding in pose_graph.cpp: INTEGRATION.md. */
+#define ESVIO_FE_BOW_MAX_RESULTS 64
+#define ESVIO_FE_BOW_LOOP_RESULTS 4
+#define ESVIO_FE_BOW_LOOP_GAP 50
+#define ESVIO_FE_BOW_LOOP_MIN_FIRST 0.05
+#define ESVIO_FE_BOW_LOOP_MIN_OTHER 0.015
+typedef struct esvio_fe_bow_vocabulary_info {
+  int32_t k, L;      /* as the header has them; the walk does not use them */
+  int32_t scoring;   /* 0: L1_NORM */
+  int32_t weighting; /* 0..3: TF_IDF, TF, IDF, BINARY */
+  int32_t nodes;     /* nNodes: without the root */
+  int32_t words;     /* nWords */
+  int32_t leaves;
+  int32_t max_children;
+  int32_t depth;
+  char message[188]; /* "" or what the file is refused for */
+} esvio_fe_bow_vocabulary_info;
+typedef struct esvio_fe_bow_result {
+  int32_t id;
+  double score;
+} esvio_fe_bow_result;
+int esvio_fe_bow_vocabulary_header(const void* bytes, size_t n_bytes, esvio_fe_bow_vocabulary_info* info);
+int esvio_fe_bow_set_vocabulary(esvio_fe_handle h, const void* bytes, size_t n_bytes);
+int esvio_fe_bow_transform(esvio_fe_handle h, const uint32_t* desc, int n, int space, int32_t* word, double* weight,
+                           uint32_t* bow_word, double* bow_value, int32_t bow_cap, int32_t* n_bow);
+int esvio_fe_bow_add(esvio_fe_handle h, const uint32_t* desc, int n, int space, int32_t* entry_id);
+int esvio_fe_bow_query(esvio_fe_handle h, const uint32_t* desc, int n, int space, int max_results, int max_id,
+                       esvio_fe_bow_result* results, int32_t* n_results);
+int esvio_fe_bow_detect_loop(esvio_fe_handle h, const uint32_t* desc, int n, int space, int frame_index,
+                             int32_t* loop_index, esvio_fe_bow_result* results, int32_t* n_results);
+int esvio_fe_bow_clear(esvio_fe_handle h);
+int esvio_fe_bow_entries(esvio_fe_handle h);
+int esvio_fe_bow_reserve(esvio_fe_handle h, int64_t entries, int64_t words);
 
 /* ---- camera split across GPUs (BASELINE config C4) ----------------------- */
 /* The left and right cameras have disjoint SAE state (sae_/sae_latest_ vs sae_right/

@@ -251,6 +251,27 @@ int esvio_fe_kf_kernel_count(void);
 const char* esvio_fe_kf_kernel_name(int which);
 int esvio_fe_kf_kernel_stats(esvio_fe_handle h, int which, double* total_ms, uint64_t* launches, uint64_t* alg_bytes);
 int esvio_fe_kf_blur_tile(int32_t* tile_w, int32_t* tile_h);
+/* loop detection's kernels (esvio_fe_bow_*), a table of their own in timer slots behind the keyframes'; every other
+ * table stays as it is: esvio_fe_bow_kernel_count() names, k_bow_walk, k_bow_vector, k_bow_score, k_bow_select (the sort
+ * between the first two is booked as k_radix_pass of the TRACK table, esvio_fe_kernel_count's, as esvio_fe_hot_select's
+ * passes are: a host that profiles the track path sees a bow call's sort launches and bytes in that slot); esvio_fe_bow_kernel_name: "" for any other id;
+ * esvio_fe_bow_kernel_stats as esvio_fe_get_kernel_stats.
+ * esvio_fe_bow_limits: the sizes at which the kernels change path — group_lanes: k_bow_walk's lanes per descriptor (a node
+ * with more children takes more rounds); lds_words: the query words k_bow_score keeps in LDS (a longer vector is looked
+ * up in memory); vector_block: the values k_bow_vector's norm chain stages at a time.
+ * esvio_fe_bow_scores: for the query Q(desc, max_id) the raw sum s_e (score[e], 0.0 where absent) and whether the entry is
+ * present (present[e], 0 or 1) for every entry — room for esvio_fe_bow_entries() each, host memory; nothing is added. */
+typedef struct esvio_fe_bow_limits_info {
+  int32_t group_lanes;
+  int32_t lds_words;
+  int32_t vector_block;
+  int32_t max_results;
+} esvio_fe_bow_limits_info;
+int esvio_fe_bow_kernel_count(void);
+const char* esvio_fe_bow_kernel_name(int which);
+int esvio_fe_bow_kernel_stats(esvio_fe_handle h, int which, double* total_ms, uint64_t* launches, uint64_t* alg_bytes);
+int esvio_fe_bow_limits(esvio_fe_bow_limits_info* out);
+int esvio_fe_bow_scores(esvio_fe_handle h, const uint32_t* desc, int n, int space, int max_id, double* score, uint8_t* present);
 /* the events one workgroup of the slicing chain takes (esvio_fe_slice_events): where its tile edges lie */
 int esvio_fe_slice_tile_events(void);
 /* the hipStream_t the handle launches on (as void*) */
