@@ -234,12 +234,8 @@ int esvio_fe_create(const esvio_fe_config* cfg, esvio_fe_handle* out) {
   // (the per-pixel dedup of the Arc* candidates pays only where the selection digs deep into its list: fe_stages.cpp run_arc)
   c->dedup_enabled = getenv("ESVIO_FE_NO_DEDUP") == nullptr && (cfg->max_cnt > 500 || getenv("ESVIO_FE_DEDUP") != nullptr);
   c->fuse_ts_pyr = getenv("ESVIO_FE_NO_FUSE") == nullptr;
-  c->fast_lds = getenv("ESVIO_FE_FAST_LDS") != nullptr;
   if (const char* v = getenv("ESVIO_FE_CONVERT_PINNED_COPY")) c->cvt_pinned_copy = atoi(v) != 0 ? 1 : 0;
   if (const char* v = getenv("ESVIO_FE_RAW_PINNED_COPY")) c->rawdec.pinned_copy = atoi(v) != 0 ? 1 : 0;
-  if (const char* v = getenv("ESVIO_FE_AEDAT_WAVE_LOOKUP")) c->aedat.wave_lookup = atoi(v) != 0 ? 1 : 0;
-  if (const char* v = getenv("ESVIO_FE_BAG_WAVE_LOADS")) c->bag.wave_loads = atoi(v) != 0 ? 1 : 0;
-  if (const char* v = getenv("ESVIO_FE_IMAGE_WAVE_LOADS")) c->bag.img_wave_loads = atoi(v) != 0 ? 1 : 0;
   c->select_one_wave = getenv("ESVIO_FE_SELECT_SERIAL") != nullptr;
   if (const char* v = getenv("ESVIO_FE_SAE_EV_MIN")) c->sae_ev_min = (size_t)strtoull(v, nullptr, 10);
   c->tiled = make_tile_geom(c->W, c->H, &c->tgeom) && getenv("ESVIO_FE_SAE_SORT") == nullptr;
@@ -2346,7 +2342,7 @@ int aedat_enqueue(esvio_fe_ctx* c, int64_t t_offset_ns, uint32_t flags, AedatJob
     AedatCam& ac = a.cam[k];
     ac.rec = (const uint2*)A.d_pack[cam].p, ac.n = (uint32_t)n, ac.tiles = aedat_tiles(n);
     ac.runs = (const AedatRun*)(A.d_pack[cam].p + roff), ac.n_runs = (uint32_t)n_runs;
-    ac.keep_invalid = keep, ac.wave_lookup = (uint32_t)A.wave_lookup, ac.t_offset = t_offset_ns, ac.sums = A.sums[cam];
+    ac.keep_invalid = keep, ac.t_offset = t_offset_ns, ac.sums = A.sums[cam];
     ac.dst = dc[k].d, ac.dst_cap = (uint32_t)std::min<size_t>(dc[k].cap, 0xffffffffu);
     ac.res = A.res + cam;
     n_all += n, cap_all += std::min(dc[k].cap, n);
@@ -2586,7 +2582,6 @@ int bag_enqueue(esvio_fe_ctx* c, const void* bytes, size_t n_bytes, BagCall* b, 
   HIPCHK(c, hipMemcpyAsync(B.d_pack, B.h_pack, off1 + n[1] * kBagEventBytes, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipMemsetAsync(B.res, 0, 2 * sizeof(BagResult), s));
   BagArgs a{};
-  a.wave_loads = (uint32_t)B.wave_loads;
   uint64_t stored = 0;
   for (int cam = 0; cam < 2; cam++) {
     BagCam& bc = a.cam[cam];
@@ -4335,7 +4330,6 @@ int bag_image_enqueue(esvio_fe_ctx* c, size_t table_at, uint32_t n_images, uint3
   HIPCHK(c, hipMemcpyAsync(B.d_img, B.h_img, table_at + n_images * sizeof(ImageDesc), hipMemcpyHostToDevice, s));
   ImageArgs a{};
   a.desc = (const ImageDesc*)(B.d_img.p + table_at), a.n_images = n_images, a.width = width, a.height = height;
-  a.wave_loads = (uint32_t)B.img_wave_loads;
   ScopedKernel k(c, K_IMAGE_EMIT, alg_bytes);
   launch_image_emit(s, a);
   return 0;

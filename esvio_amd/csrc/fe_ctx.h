@@ -402,7 +402,6 @@ struct esvio_fe_ctx {
   DevBuf<uint32_t> d_gftt_max;
   DevBuf<int32_t> d_sel_idx;
   DevBuf<uint8_t> d_fast_img;  // esvio_fe_fast_corners: a caller's host image (linear, width*height); its lists: fast_own below
-  bool fast_lds = false;          // (ESVIO_FE_FAST_LDS=1: k_fast_score's LDS-tiled form, for the A/B in KERNELS.md)
   // pinned host staging (h_pin's layout: ResLayout)
   PinBuf<uint8_t> h_img;  // copy_level0_in's staging ring: pinned host side ...
   DevBuf<uint8_t> d_img;  // ... and its device side (linear images)
@@ -573,7 +572,6 @@ struct esvio_fe_ctx {
     DevBuf<uint32_t> sums[2];
     DevBuf<AedatResult> res;
     bool used = false;  // esvio_fe_reserve grows the scratch of a handle that has decoded AEDAT before
-    int wave_lookup = 0;  // ESVIO_FE_AEDAT_WAVE_LOOKUP=1: k_aedat_emit's run look-up once per wave with a forward step (the A/B in KERNELS.md)
   } aedat;
 
   // ---- esvio_fe_decode_bag / esvio_fe_bag_side / esvio_fe_feed_push_bag: rosbag v2.0 recordings (include/esvio_fe.h has
@@ -590,7 +588,6 @@ struct esvio_fe_ctx {
     DevBuf<uint8_t> d_pack;
     DevBuf<BagResult> res;
     bool used = false;   // esvio_fe_reserve grows the scratch of a handle that has decoded a bag before
-    int wave_loads = 0;  // ESVIO_FE_BAG_WAVE_LOADS=1 / 0: k_bag_emit's wave-cooperative dwordx4 loads through LDS / per-lane loads (the A/B in KERNELS.md)
     // esvio_fe_decode_bag_images / esvio_fe_convert_image.  img_st: the third walker state, carry the bytes of the payload
     // a call's end cut (fe_bag.h: Carry), both on the HOST and taken over as the others are.  The stage's own, main
     // stream only, allocated on first use: h_img, the pinned scratch the walk gathers the payloads into, each from a
@@ -601,7 +598,6 @@ struct esvio_fe_ctx {
     PinBuf<uint8_t> h_img;
     DevBuf<uint8_t> d_img, d_gray;
     bool img_used = false;    // esvio_fe_reserve grows the scratch of a handle that has decoded images before
-    int img_wave_loads = 0;   // ESVIO_FE_IMAGE_WAVE_LOADS=1 / 0: k_image_emit's wave-cooperative dwordx4 loads through LDS / per-lane loads (the A/B in KERNELS.md)
   } bag;
 
   // ---- esvio_fe_slice_events: a record stream cut into fixed-rate windows (include/esvio_fe.h has the rule,

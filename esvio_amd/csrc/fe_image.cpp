@@ -34,7 +34,6 @@ static void fast_lists(esvio_fe_ctx* c, const uint8_t* img, int stride, int arc,
   a.arc = arc;
   a.barrier = barrier;
   a.nonmax = nonmax ? 1 : 0;
-  a.lds = c->fast_lds ? 1 : 0;
   a.m = fc.m;
   a.cand_xy = cs.xy;
   a.cand_score = cs.idx;

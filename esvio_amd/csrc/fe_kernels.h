@@ -498,7 +498,6 @@ struct FastArgs {
   int arc;              // 9 or 10
   int barrier;          // 0..255
   int nonmax;
-  int lds;              // != 0: k_fast_score reads its tile + 3-pixel halo through LDS (see KERNELS.md)
   uint8_t* m;           // [W*H]
   uint32_t* cand_xy;    // [nblk*kArcBlock]
   uint32_t* cand_score; // [nblk*kArcBlock]
@@ -701,8 +700,7 @@ void launch_trig_emit(hipStream_t s, const RawArgs& a);
 // polarity records packed into one array and the table of its runs of equal eventTSOverflow.  A record needs nothing
 // from the records before it but its rank among the kept ones, so the chain is count (kept records per tile of
 // kAedatTile) -> scan (one workgroup per camera: the tiles' exclusive prefixes, the totals) -> emit (one record per
-// lane: its run by a binary search of the table — KERNELS.md "AEDAT 3.1" has the measurement against one search per
-// wave —, the stamp, one 16-byte store at dst[rank]).  With keep_invalid the
+// lane: its run by a binary search of the table, the stamp, one 16-byte store at dst[rank]).  With keep_invalid the
 // rank is the index: the host writes the result block's counts itself and launches the emit alone.  Both cameras'
 // tiles share each grid, as in the raw chain; no launch waits on the device for another workgroup.
 // The timer slots of these kernels are a range of their own behind K_COUNT (esvio_fe_ingest_kernel_count()): the stage
@@ -726,7 +724,6 @@ struct AedatCam {
   const AedatRun* runs;  // [n_runs] ascending in `first`, runs[0].first == 0
   uint32_t n_runs;
   uint32_t keep_invalid;
-  uint32_t wave_lookup;   // 0: every lane searches the table for its own record (the measured choice); 1: one search per wave, then a forward step
   long long t_offset;    // nanoseconds
   uint32_t* sums;        // [tiles] count: the tiles' kept records; scan: their exclusive prefixes
   EventRec* dst;         // [dst_cap]; nothing is stored when the kept records exceed dst_cap
@@ -745,9 +742,8 @@ void launch_aedat_emit(hipStream_t s, const AedatArgs& a);
 // events of the chunk, 13 packed bytes each (u16 x, u16 y, u32 sec, u32 nsec, u8 polarity), from a 16-byte aligned base.
 // Every wire event is emitted and the host knows the count, so one launch does it all: k_bag_emit, both cameras' tiles in
 // one grid, one event per lane, 13 bytes in and one 16-byte store out; no workgroup waits for another.  A wave's 64
-// events are 832 bytes = 52 dwordx4, so every wave's span is 64-byte aligned.  Two forms of the load (KERNELS.md "ROS
-// bags" has the measurement): per lane, the byte assembly of k_events_from_fields' element path; or per wave, 52
-// dwordx4 loads of the span staged through LDS, from which each lane cuts its 13 bytes with four dword reads.
+// events are 832 bytes = 52 dwordx4, so every wave's span is 64-byte aligned.  Each lane assembles its own 13 bytes,
+// the byte assembly of k_events_from_fields' element path (KERNELS.md "ROS bags" has the measurement behind it).
 // K_BAG_EMIT is appended to the ingest range (IngestKernelId above).
 constexpr uint32_t kBagTile = 1024;      // events per workgroup: 1024 lanes, one event each
 constexpr uint32_t kBagEventBytes = 13;
@@ -767,7 +763,6 @@ struct BagCam {
 };
 struct BagArgs {
   BagCam cam[2];       // the grid's blocks: cam[0].tiles, then cam[1].tiles
-  uint32_t wave_loads; // 0: per-lane loads; 1: wave-cooperative dwordx4 loads through LDS
 };
 void launch_bag_emit(hipStream_t s, const BagArgs& a);
 
@@ -778,11 +773,8 @@ void launch_bag_emit(hipStream_t s, const BagArgs& a);
 // of the destination, four consecutive pixels of the dense image counted from the dword boundary at or below dst (dst may
 // lie at any byte: 346 x 260 images side by side do not keep 16-byte boundaries, 5 x 1 ones not even dword boundaries);
 // the dwords the image's ends share with its neighbours, and groups that span two rows, go pixel by pixel.  The source
-// bytes of a group are 4 or 12 consecutive bytes at ANY alignment (step may be odd).  Two forms of the load (KERNELS.md
-// "ROS bag images" has the measurement): per lane, the byte assembly of ld_any; or per wave, whose 256 pixels — where
-// they lie in one row — are 256 or 768 consecutive bytes, loaded as the <= 50 aligned dwordx4 that overlap them (each
-// holds at least one byte of the row, so none leaves the pages the payload lies in) into LDS, from which a lane cuts its
-// bytes with two or four dword reads and a funnel shift.  K_IMAGE_EMIT is appended to the ingest range.
+// bytes of a group are 4 or 12 consecutive bytes at ANY alignment (step may be odd): each lane assembles its own with
+// ld_any (KERNELS.md "ROS bag images" has the measurement behind it).  K_IMAGE_EMIT is appended to the ingest range.
 constexpr uint32_t kImageTile = 1024;  // pixels per workgroup: 256 lanes, one destination dword each
 constexpr uint32_t kImageMaxSide = 8192;
 struct ImageDesc {
@@ -796,7 +788,6 @@ struct ImageArgs {
   const ImageDesc* desc;  // [n_images] device memory
   uint32_t n_images;
   uint32_t width, height;  // of every image of the launch; width * height <= 2^26
-  uint32_t wave_loads;     // 0: per-lane loads; 1: wave-cooperative dwordx4 loads through LDS where a wave's pixels lie in one row
 };
 void launch_image_emit(hipStream_t s, const ImageArgs& a);
 

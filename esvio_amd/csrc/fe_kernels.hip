@@ -691,13 +691,9 @@ __global__ __launch_bounds__(kTileHistThreads) void k_tile_hist(const uint4* __r
       }
     }
     if (k + 1 < group) request(k + 1);
-#ifndef ESVIO_ABL_HIST_NOCOUNT  // (measurement build: the kernel as a pure read of the records)
 #pragma unroll
     for (int j = 0; j < UE; j++)
       if (bins[j] != 0xffffffffu) atomicAdd(&hme[bins[j]], 1u);
-#else
-    if (bins[0] == 0xfffffff0u) hme[0] = bins[UE - 1];
-#endif
     lds_barrier();
     if (live)
       for (int i = threadIdx.x; i < nbc; i += kTileHistThreads) {
@@ -1010,7 +1006,6 @@ __global__ __launch_bounds__(kTileScatterThreads) void k_tile_scatter(
       const bool ok = i < ncam;
       const uint32_t d = tile_bin(g, rec[r].x);
       uint32_t rank = 0;
-#ifndef ESVIO_ABL_NORANK  // (measurement builds, tools/build_variant.sh + tools/scatter_ablation.sh: what the kernel costs without its parts)
 #pragma unroll
       for (int half = 0; half < 2; half++) {
         if (ok && (lane >> 5) == half) {
@@ -1025,7 +1020,6 @@ __global__ __launch_bounds__(kTileScatterThreads) void k_tile_scatter(
         // order; nothing has to wait for them)
         __asm__ volatile("" ::: "memory");
       }
-#endif
       dr[r] = d | (rank << 16);
     }
     lds_barrier();  // every wave's counts are final — and every wave's stores of the previous scatter block have read bin_base
@@ -1054,14 +1048,7 @@ __global__ __launch_bounds__(kTileScatterThreads) void k_tile_scatter(
         if (i < ncam) {
           const uint32_t d = dr[r] & 0xffffu;
           const uint32_t pos = bin_base[d] + (mc_s[wave * nbcp + d].y >> 16) + (dr[r] >> 16);
-#if defined(ESVIO_ABL_NOWRITE)
-          if (pos == 0xffffffffu)  // (never: the address is still computed)
-#endif
-#if defined(ESVIO_ABL_COALESCED)
-          part2[ioff + i + (pos >> 31)] = tile_rec_pack(rec[r], g.tw, g.th, twsh, sec_base);
-#else
           part2[pos] = tile_rec_pack(rec[r], g.tw, g.th, twsh, sec_base);
-#endif
         }
       }
     } else {
@@ -1149,11 +1136,7 @@ __device__ __forceinline__ void tile_apply_body(
   }
   for (int p = threadIdx.x; p < npx; p += kTileApplyThreads) {
     const int gx = x0 + (p & (g.tw - 1)), gy = y0 + (p >> twsh);
-#ifdef ESVIO_ABL_APPLY_NOLOAD
-    Ls[p] = make_double2((double)gx, (double)gy);
-#else
     Ls[p] = (gx < g.W && gy < g.H) ? L2[cam * P + (size_t)gy * g.W + gx] : make_double2(0, 0);
-#endif
     Sidx[2 * p] = 0;
     Sidx[2 * p + 1] = 0;
   }
@@ -1183,10 +1166,6 @@ __device__ __forceinline__ void tile_apply_body(
       const bool pol = Rec::pol(cur[k]);
       const double t = Rec::time(cur[k], sec_base);
       unsigned long long m = __ballot(valid);
-#ifdef ESVIO_ABL_APPLY_NOMATCH  // (measurement builds, WRONG results)
-      m &= self;
-      if (false)
-#endif
 #pragma unroll
       for (int b = 0; b < kPixBits; b++) {
         const int sx = ((int)(pix << (31 - b))) >> 31;  // -1 where the bit is set, else 0
@@ -1223,9 +1202,6 @@ __device__ __forceinline__ void tile_apply_body(
       __asm__ volatile("" : "+s"(rm[k]), "+s"(wm[k]), "+v"(ra[k]), "+v"(wa[k]));
     }
     bool gave_up = false;
-#ifdef ESVIO_ABL_APPLY_NOTICKET  // (measurement build, WRONG results: the turns' LDS sections in no particular order)
-    if (false)
-#endif
     for (uint32_t spins = 0;;) {
       const uint32_t d =
           __builtin_amdgcn_readfirstlane(__hip_atomic_load(&s_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
@@ -1290,11 +1266,7 @@ __device__ __forceinline__ void tile_apply_body(
       // one LDS atomic per event that matters: the chunk's last event of a (pixel, polarity) marks the pair as
       // touched (1), a passing event leaves 2 + its position; the maximum keeps the last passing one
       const uint32_t pos = (turn * kTileTurn + k) * 64u + (uint32_t)lane;
-#ifdef ESVIO_ABL_APPLY_NOPOST
-      if ((pass || (flg[k] & 16u)) && pos == 0xffffffffu)
-#else
       if (pass || (flg[k] & 16u))
-#endif
         atomicMax(&Sidx[2 * pixk[k] + (pol ? 1 : 0)], pass ? pos + 2u : 1u);
     }
   }
@@ -1320,11 +1292,7 @@ __device__ __forceinline__ void tile_apply_body(
   for (int q = 0; q < kPer; q++) {
     const int p = threadIdx.x + q * kTileApplyThreads;
     const uint32_t tb = sb[q] & 3u;
-#ifdef ESVIO_ABL_APPLY_NOWB
-    if (p >= npx || !tb || tb != 7u) continue;
-#else
     if (p >= npx || !tb) continue;
-#endif
     const int gx = x0 + (p & (g.tw - 1)), gy = y0 + (p >> twsh);
     const size_t k = cam * P + (size_t)gy * g.W + gx;
     L2[k] = Ls[p];
@@ -1430,13 +1398,7 @@ __device__ __forceinline__ uint8_t ts_pixel(double2 s, double t_sync, double dec
   double v = 0.0;
   if (m > 0) {
     const double dt = __dsub_rn(t_sync, m);
-#if defined(ESVIO_ABL_TS_NOEXP)  // (measurement build: the render without its exp and its division)
-    v = dt * decay_sec;
-#elif defined(ESVIO_ABL_TS_NODIV)  // (... with a multiplication by 1 / decay instead of the division: NOT the reference's rounding)
-    v = exp(-dt * (1.0 / decay_sec));
-#else
     v = exp(-dt / decay_sec);
-#endif
     if (!ignore_polarity) v = pos ? v : -v;
   }
   const double sc = ignore_polarity ? __dadd_rn(__dmul_rn(v, 255.0), 0.0)
@@ -3564,30 +3526,20 @@ __device__ __forceinline__ bool fast_has_run(uint32_t mask16) {
   return (rn & 0xffffu) != 0;
 }
 
-constexpr int kFastTileW = 64, kFastTileH = 4, kFastLdsStride = kFastTileW + 8;
+constexpr int kFastTileW = 64, kFastTileH = 4;
 
-template <int N, bool LDS>
+template <int N>
 __global__ __launch_bounds__(256) void k_fast_score(FastArgs a) {
   constexpr int dx[16] = {0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1};
   constexpr int dy[16] = {3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1, 0, 1, 2, 3};
-  __shared__ uint8_t tile[LDS ? (kFastTileH + 6) * kFastLdsStride : 1];
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
   const int x = blockIdx.x * kFastTileW + tx, y = blockIdx.y * kFastTileH + ty;
   const int W = a.W, H = a.H;
-  if (LDS) {  // tile + 3-pixel halo; positions outside the image are clamped (no border pixel reads them)
-    const int x0 = blockIdx.x * kFastTileW - 3, y0 = blockIdx.y * kFastTileH - 3;
-    for (int i = threadIdx.x; i < (kFastTileH + 6) * (kFastTileW + 6); i += 256) {
-      const int r = i / (kFastTileW + 6), col = i - r * (kFastTileW + 6);
-      const int gx = min(max(x0 + col, 0), W - 1), gy = min(max(y0 + r, 0), H - 1);
-      tile[r * kFastLdsStride + col] = a.img[(size_t)gy * a.stride + gx];
-    }
-    __syncthreads();
-  }
   if (x >= W || y >= H) return;
   uint32_t out = 0;
   if (x >= 3 && x < W - 3 && y >= 3 && y < H - 3) {
-    const uint8_t* p = LDS ? tile + (ty + 3) * kFastLdsStride + tx + 3 : a.img + (size_t)y * a.stride + x;
-    const int ps = LDS ? kFastLdsStride : a.stride;
+    const uint8_t* p = a.img + (size_t)y * a.stride + x;
+    const int ps = a.stride;
     const int c = p[0], b = a.barrier;
     int d[16];
 #pragma unroll
@@ -3637,13 +3589,8 @@ __global__ __launch_bounds__(256) void k_fast_score(FastArgs a) {
 
 void launch_fast_score(hipStream_t s, const FastArgs& a) {
   const dim3 grid((a.W + kFastTileW - 1) / kFastTileW, (a.H + kFastTileH - 1) / kFastTileH);
-  if (a.arc == 9) {
-    if (a.lds) launch_k(k_fast_score<9, true>, grid, dim3(256), 0, s, a);
-    else launch_k(k_fast_score<9, false>, grid, dim3(256), 0, s, a);
-  } else {
-    if (a.lds) launch_k(k_fast_score<10, true>, grid, dim3(256), 0, s, a);
-    else launch_k(k_fast_score<10, false>, grid, dim3(256), 0, s, a);
-  }
+  if (a.arc == 9) launch_k(k_fast_score<9>, grid, dim3(256), 0, s, a);
+  else launch_k(k_fast_score<10>, grid, dim3(256), 0, s, a);
 }
 
 // m > 0 only inside the 3-pixel border, so a corner's eight neighbours are always inside the image
@@ -4984,18 +4931,14 @@ __global__ __launch_bounds__(kAedatTile) void k_aedat_emit(AedatArgs a) {
     total = c.res->events;
   }
   // the run: the last table entry whose first record is at or in front of this one (runs[0].first == 0)
-  // (wave_lookup, the measured alternative: one search per wave for its first record, then every lane steps forward)
-  const uint32_t key = c.wave_lookup ? (i & ~63u) : i;
   uint32_t lo = 0, hi = c.n_runs;
   while (hi - lo > 1) {
     const uint32_t mid = (lo + hi) >> 1;
-    if (c.runs[mid].first <= key)
+    if (c.runs[mid].first <= i)
       lo = mid;
     else
       hi = mid;
   }
-  if (c.wave_lookup)
-    while (lo + 1 < c.n_runs && c.runs[lo + 1].first <= i) lo++;
   const int32_t overflow = c.runs[lo].overflow, ts = (int32_t)w.y;
   // BAD first for ts64 >= 2^53; below it ts64 * 1000 + t_offset, modulo 2^64, is the exact sum when that is not negative
   // and lies at or above 2^63 when it is (|t_offset| <= 2^62): one unsigned comparison decides (fe_aedat.h: stamp)
@@ -5026,34 +4969,16 @@ void launch_aedat_emit(hipStream_t s, const AedatArgs& a) {
 }
 
 // ============================================================================ rosbag v2.0 wire events
-// dvs_msgs/EventArray wire events, 13 packed bytes each -> event records (fe_kernels.h has the two forms of the load,
+// dvs_msgs/EventArray wire events, 13 packed bytes each -> event records (fe_kernels.h has the load,
 // include/esvio_fe.h the rule; the record walk is the host's, fe_bag.h).  One event per lane: 13 bytes in, 16 bytes out.
 __global__ __launch_bounds__(kBagTile) void k_bag_emit(BagArgs a) {
-  __shared__ uint4 stage[kBagTile * kBagEventBytes / 16];  // per wave 52 dwordx4 = its 64 events
   const uint32_t b = blockIdx.x;
   const uint32_t tile = b < a.cam[0].tiles ? b : b - a.cam[0].tiles;
   const BagCam& c = b < a.cam[0].tiles ? a.cam[0] : a.cam[1];
   const uint32_t i = tile * kBagTile + threadIdx.x;
   const bool active = i < c.n;
   uint32_t xy = 0, sec = 0, nsec = 0, pol = 0;
-  if (a.wave_loads) {
-    const uint32_t wave = threadIdx.x >> 6, lane = lane_id();
-    const uint32_t w_first = tile * kBagTile + wave * 64u;  // the wave's first event: its span begins 64-byte aligned
-    const uint32_t w_cnt = w_first < c.n ? min(64u, c.n - w_first) : 0u;
-    const uint32_t w_vec = (w_cnt * kBagEventBytes + 15u) / 16u;  // (the last one may reach into the base's padding)
-    if (lane < w_vec) stage[wave * 52u + lane] = ((const uint4*)(c.src + (size_t)w_first * kBagEventBytes))[lane];
-    __syncthreads();
-    if (active) {
-      // the lane's 13 bytes begin at byte 13 * lane of the wave's 832: four dwords from the aligned one below hold them
-      const uint32_t* lw = (const uint32_t*)stage + wave * 208u;
-      const uint32_t o = kBagEventBytes * lane, k = o >> 2, sh = (o & 3u) * 8u;
-      const uint32_t w0 = lw[k], w1 = lw[k + 1], w2 = lw[k + 2], w3 = lw[k + 3];  // (k + 3 <= 207)
-      xy = (uint32_t)((((uint64_t)w1 << 32) | w0) >> sh);
-      sec = (uint32_t)((((uint64_t)w2 << 32) | w1) >> sh);
-      nsec = (uint32_t)((((uint64_t)w3 << 32) | w2) >> sh);
-      pol = (w3 >> sh) & 0xffu;
-    }
-  } else if (active) {
+  if (active) {
     const uint8_t* p = c.src + (size_t)i * kBagEventBytes;
     xy = (uint32_t)ld_any<uint16_t>(p) | (uint32_t)ld_any<uint16_t>(p + 2) << 16;
     sec = ld_any<uint32_t>(p + 4), nsec = ld_any<uint32_t>(p + 8), pol = p[12];
@@ -5825,8 +5750,8 @@ KernelId launch_select(hipStream_t s, const SelectArgs& a, size_t lds_bytes) {
 }
 
 // ============================================================================ rosbag images
-// sensor_msgs/Image payloads -> dense gray images (fe_kernels.h has the lay-out of the work and the two forms of the
-// load, include/esvio_fe.h the rule).
+// sensor_msgs/Image payloads -> dense gray images (fe_kernels.h has the lay-out of the work and the load,
+// include/esvio_fe.h the rule).
 __device__ __forceinline__ uint32_t image_gray(uint32_t r, uint32_t g, uint32_t b) {
   return (r * 9798u + g * 19235u + b * 3735u + (1u << 14)) >> 15;
 }
@@ -5840,48 +5765,14 @@ __device__ __forceinline__ uint32_t image_gray4(uint32_t q0, uint32_t q1, uint32
   return image_gray3(q0, cls) | image_gray3(q0 >> 24 | q1 << 8, cls) << 8 | image_gray3(q1 >> 16 | q2 << 16, cls) << 16 |
          image_gray3(q2 >> 8, cls) << 24;
 }
-__device__ __forceinline__ uint32_t image_funnel(uint32_t lo, uint32_t hi, uint32_t sh) {
-  return (uint32_t)((((uint64_t)hi << 32) | lo) >> sh);
-}
 
 __global__ __launch_bounds__(256) void k_image_emit(ImageArgs a, uint32_t first_image) {
-  __shared__ uint4 stage[4 * 64];  // per wave 64 dwordx4, of which its span fills 50 at the most
   const ImageDesc d = a.desc[first_image + blockIdx.y];
   const int W = (int)a.width, N = (int)(a.width * a.height);
   const uint32_t bpp = d.cls == 1u ? 1u : 3u;
   const int shift = (int)((uintptr_t)d.dst & 3u);
-  const uint32_t wave = threadIdx.x >> 6, lane = lane_id();
   const int p0 = (int)((blockIdx.x * 256u + threadIdx.x) * 4u) - shift;  // the lane's first pixel in the dense image (< 0: in front of it)
-  bool staged = false;
-  uint32_t off = 0;
-  if (a.wave_loads) {
-    const int w0 = (int)((blockIdx.x * 256u + wave * 64u) * 4u) - shift, w1 = w0 + 255;  // the wave's first and last pixel
-    if (w0 >= 0 && w1 < N) {
-      const int row = w0 / W;
-      if (w1 / W == row) {
-        const uint8_t* s0 = d.src + (size_t)row * d.step + (size_t)(w0 - row * W) * bpp;
-        off = (uint32_t)((uintptr_t)s0 & 15u);
-        const uint32_t n_vec = (off + 256u * bpp + 15u) >> 4;  // the dwordx4 that overlap the span
-        if (lane < n_vec) stage[wave * 64u + lane] = ((const uint4*)(s0 - off))[lane];
-        staged = true;
-      }
-    }
-    __syncthreads();
-  }
   if (p0 >= N) return;
-  if (staged) {
-    const uint32_t* lw = (const uint32_t*)stage + wave * 256u;
-    const uint32_t o = off + lane * 4u * bpp, k = o >> 2, sh = (o & 3u) * 8u;
-    uint32_t v;
-    if (bpp == 1u) {
-      v = image_funnel(lw[k], lw[k + 1], sh);  // (k + 1 <= 67)
-    } else {
-      const uint32_t x0 = lw[k], x1 = lw[k + 1], x2 = lw[k + 2], x3 = lw[k + 3];  // (k + 3 <= 195)
-      v = image_gray4(image_funnel(x0, x1, sh), image_funnel(x1, x2, sh), image_funnel(x2, x3, sh), d.cls);
-    }
-    *(uint32_t*)(d.dst + p0) = v;
-    return;
-  }
   const int row = p0 >= 0 ? p0 / W : 0;
   if (p0 >= 0 && p0 + 3 < N && (p0 + 3) / W == row) {  // a whole dword of one row
     const uint8_t* sp = d.src + (size_t)row * d.step + (size_t)(p0 - row * W) * bpp;

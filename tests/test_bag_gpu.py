@@ -1,9 +1,8 @@
 """GPU: esvio_fe_decode_bag, esvio_fe_bag_side and esvio_fe_feed_push_bag against the sequential reading
 tests/bag_ref.py.  Integers only: every byte of every record, every row of the message table and every info field are
 compared for equality (the IMU samples' doubles bit for bit), with guard bytes behind dst_cap records.  T = the kernel's
-tile.  The decode cases run once per form of k_bag_emit's load (per-lane, wave-cooperative)."""
+tile.  The decode cases run once: k_bag_emit has one form of its load."""
 import ctypes as C
-import os
 import struct
 
 import numpy as np
@@ -44,13 +43,8 @@ def body(messages, **kw):
 class Bg:
     """a handle and the reading's two walkers, advanced together"""
 
-    def __init__(self, form=None):
-        if form is not None:
-            os.environ["ESVIO_FE_BAG_WAVE_LOADS"] = str(form)
-        try:
-            self.ft = FE.FeatureTracker(FE.make_config(64, 48, max_cnt=40))
-        finally:
-            os.environ.pop("ESVIO_FE_BAG_WAVE_LOADS", None)
+    def __init__(self):
+        self.ft = FE.FeatureTracker(FE.make_config(64, 48, max_cnt=40))
         self.L, self.h = self.ft._hd.L, self.ft._hd.h
         self.hip = C.CDLL("libamdhip64.so")
         self.fresh()
@@ -132,9 +126,9 @@ class Bg:
         return o
 
 
-@pytest.fixture(scope="module", params=[0, 1], ids=["per-lane loads", "wave loads"])
-def bg(request):
-    d = Bg(request.param)
+@pytest.fixture(scope="module")
+def bg():
+    d = Bg()
     yield d
     d.close()
 

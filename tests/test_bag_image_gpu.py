@@ -1,10 +1,9 @@
 """GPU: esvio_fe_convert_image, esvio_fe_decode_bag_images and esvio_fe_track_image_space against the sequential reading
 tests/bag_image_ref.py.  Integers only: every byte of every gray image, every row of the image table and every info field
-are compared for equality, with guard bytes around every destination.  The conversion and decode cases run once per form
-of k_image_emit's load (per-lane, wave-cooperative)."""
+are compared for equality, with guard bytes around every destination.  The conversion and decode cases run once: k_image_emit
+has one form of its load."""
 import ctypes as C
 import itertools
-import os
 
 import numpy as np
 import pytest
@@ -55,14 +54,9 @@ class Mem:
 class Im:
     """a handle and the reading's image walker, advanced together"""
 
-    def __init__(self, form=None, W=W0, H=H0, **kw):
-        if form is not None:
-            os.environ["ESVIO_FE_IMAGE_WAVE_LOADS"] = str(form)
-        try:
-            self.ft = FE.FeatureTracker(FE.make_config(W, H, max_cnt=kw.pop("max_cnt", 40), **kw))
-        finally:
-            os.environ.pop("ESVIO_FE_IMAGE_WAVE_LOADS", None)
-        self.form, self.W, self.H, self.L, self.h = form, W, H, self.ft._hd.L, self.ft._hd.h
+    def __init__(self, W=W0, H=H0, **kw):
+        self.ft = FE.FeatureTracker(FE.make_config(W, H, max_cnt=kw.pop("max_cnt", 40), **kw))
+        self.W, self.H, self.L, self.h = W, H, self.ft._hd.L, self.ft._hd.h
         self.fresh()
 
     def fresh(self, topics=I.IMAGE_TOPICS):
@@ -129,9 +123,9 @@ class Im:
         return o
 
 
-@pytest.fixture(scope="module", params=[0, 1], ids=["per-lane loads", "wave loads"])
-def im(request):
-    d = Im(request.param)
+@pytest.fixture(scope="module")
+def im():
+    d = Im()
     yield d
     d.close()
 
@@ -214,8 +208,8 @@ def lean_bag(w=W0, h=H0):
     return I.write_bag(msgs, per_chunk=5, header_total=None)
 
 
-def test_left_rgb8_right_mono8_and_a_bgr8_message_at_346x260_in_one_launch(im):
-    d = Im(im.form, 346, 260)
+def test_left_rgb8_right_mono8_and_a_bgr8_message_at_346x260_in_one_launch():
+    d = Im(346, 260)
     try:
         msgs = [image_msg(I.LEFT_IMAGE, 1, 3, "rgb8", 346, 260, 2, 71), image_msg(I.RIGHT_IMAGE, 1, 1, "mono8", 346, 260, 0, 72),
                 image_msg(I.LEFT_IMAGE, 2, 2, "bgr8", 346, 260, 7, 73), image_msg(I.RIGHT_IMAGE, 2, 2, "8UC3", 346, 260, 0, 74)]
@@ -367,7 +361,7 @@ def test_the_image_call_the_event_call_and_the_side_call_on_the_same_bytes_in_al
 
 def test_reserve_covers_the_scratch_and_a_second_call_allocates_nothing():
     W, H = 346, 260
-    d = Im(None, W, H)
+    d = Im(W, H)
     try:
         pair = I.write_bag([image_msg(I.LEFT_IMAGE, 1, 3, "rgb8", W, H, 0, 75), image_msg(I.RIGHT_IMAGE, 1, 3, "rgb8", W, H, 0, 76)], per_chunk=2)[13:]
         tiny = I.write_bag([image_msg(I.LEFT_IMAGE, 1, 1, "mono8", W, H, 0, 77)])[13:]

@@ -4,8 +4,8 @@ batch size (640x480, 5 Mev/s), written as libcaer polarity packets of 4096 event
 the gathering one — what the call runs before any device work); each launch of the chain from the LIBRARY'S OWN TIMERS
 (esvio_fe_get_kernel_stats: HIP events around each launch); the whole call's wall time from pageable memory into device
 memory, dropping invalid events (three launches) and keeping them (one); the emit's record stores as a share of the
-measured copy rate; the run look-up both ways (ESVIO_FE_AEDAT_WAVE_LOOKUP=1: one search per wave and a forward step) on
-the batch as it is (one run) and with eventTSOverflow alternating between 3-event packets (a run per 3 records).  Beside
+measured copy rate; the run look-up on the batch as it is (one run) and with eventTSOverflow alternating between 3-event
+packets (a run per 3 records: the stress case of the table search).  Beside
 it the bridge the call replaces: tools/aedat_seq_decode.cpp on one core, then esvio_fe_mem_upload of its records.  Per
 figure: the median of BLOCKS blocks after a warm-up block, and the blocks' min - max.  One process, one pass, no retries;
 run it under a time limit:
@@ -133,21 +133,17 @@ def main():
         ddst = C.c_void_p()
         assert L.esvio_fe_mem_alloc(FE.DEVICE, 16 * n, C.byref(ddst)) == 0
         row = dict(batch=tag, n=n, packet_bytes=len(data), count_walk_us=cw, gather_walk_us=gw)
-        for lookup in (0, 1):
-            os.environ["ESVIO_FE_AEDAT_WAVE_LOOKUP"] = str(lookup)
-            ft = FE.FeatureTracker(FE.make_config(W, H))
-            del os.environ["ESVIO_FE_AEDAT_WAVE_LOOKUP"]
-            for name, src, flags in (("drop invalid", data, 0), ("keep invalid", data, FE.AEDAT_KEEP_INVALID), ("a run per 3 records", runs3, 0)):
-                want = rec if name != "a run per 3 records" else None
-                c, k = call_bench(L, ft, src, base * 1000 if want is not None else 0, flags, ddst, n, want)
-                emit_gbs = 16 * n / (k["k_aedat_emit"][0] * 1e-6) / 1e9
-                print("    %-20s lookup per %-4s count %6.1f us | scan %5.1f us | emit %6.1f us (%.1f - %.1f; the stores %5.0f GB/s = %4.1f %% of the copy rate)"
-                      " | call %7.1f us (%.1f - %.1f) = %6.1f Mev/s"
-                      % (name, "wave" if lookup else "lane", k["k_aedat_count"][0], k["k_aedat_scan"][0], k["k_aedat_emit"][0], k["k_aedat_emit"][1],
-                         k["k_aedat_emit"][2], emit_gbs, 100 * emit_gbs / HBM_GBS, c[0], c[1], c[2], n / c[0]))
-                row["%s, lookup per %s" % (name, "wave" if lookup else "lane")] = dict(kernels_us=k, call_us=c, emit_store_gbs=emit_gbs,
-                                                                                        emit_copy_frac=emit_gbs / HBM_GBS, mev_s_call=n / c[0])
-            ft.close()
+        ft = FE.FeatureTracker(FE.make_config(W, H))
+        for name, src, flags in (("drop invalid", data, 0), ("keep invalid", data, FE.AEDAT_KEEP_INVALID), ("a run per 3 records", runs3, 0)):
+            want = rec if name != "a run per 3 records" else None
+            c, k = call_bench(L, ft, src, base * 1000 if want is not None else 0, flags, ddst, n, want)
+            emit_gbs = 16 * n / (k["k_aedat_emit"][0] * 1e-6) / 1e9
+            print("    %-20s count %6.1f us | scan %5.1f us | emit %6.1f us (%.1f - %.1f; the stores %5.0f GB/s = %4.1f %% of the copy rate)"
+                  " | call %7.1f us (%.1f - %.1f) = %6.1f Mev/s"
+                  % (name, k["k_aedat_count"][0], k["k_aedat_scan"][0], k["k_aedat_emit"][0], k["k_aedat_emit"][1],
+                     k["k_aedat_emit"][2], emit_gbs, 100 * emit_gbs / HBM_GBS, c[0], c[1], c[2], n / c[0]))
+            row[name] = dict(kernels_us=k, call_us=c, emit_store_gbs=emit_gbs, emit_copy_frac=emit_gbs / HBM_GBS, mev_s_call=n / c[0])
+        ft.close()
         if os.path.exists(SEQ):  # the bridge: one core walks and decodes, then the records are uploaded
             with tempfile.NamedTemporaryFile(suffix=".aedat") as f:
                 f.write(data)

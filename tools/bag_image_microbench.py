@@ -3,8 +3,8 @@
 (tests/bag_image_ref.py's writer).  Per shape: the host walks alone (esvio_fe_bag_image_walk_tap, which runs the counting
 walk and then the gathering one as the call does; without room for the payloads both passes only count, so the counting
 walk is half of that call and the gathering walk is the full call less that half); the copy of the gathered bytes from
-pinned memory (esvio_fe_mem_upload, with its wait); k_image_emit in both forms of its load (ESVIO_FE_IMAGE_WAVE_LOADS=0 /
-1) from the LIBRARY'S OWN TIMERS (esvio_fe_get_kernel_stats: HIP events around the launch), its bytes — read and written
+pinned memory (esvio_fe_mem_upload, with its wait); k_image_emit from the LIBRARY'S OWN TIMERS
+(esvio_fe_get_kernel_stats: HIP events around the launch), its bytes — read and written
 — as a share of the measured copy rate; the whole call's wall time from pageable memory into device memory.  Beside it
 the bridge the call replaces: tools/bag_image_seq_decode.cpp on one core, then esvio_fe_mem_upload of its gray images.
 Per figure: the median of BLOCKS blocks of REPS after a warm-up block, and the blocks' min - max.  One process, one pass,
@@ -59,7 +59,6 @@ def emit_stats(ft):
 def main():
     L = FE.load_library()
     hip = C.CDLL("libamdhip64.so")
-    emit = {}
     for tag, W, H, cls, name in SHAPES:
         data = pair_bag(W, H, cls, name)
         buf = np.frombuffer(data, np.uint8)
@@ -104,47 +103,40 @@ def main():
             assert L.esvio_fe_mem_alloc(FE.DEVICE, wh, C.byref(ddst[cam])) == 0
         dptr, caps = (C.c_void_p * 2)(ddst[0].value, ddst[1].value), (C.c_size_t * 2)(1, 1)
         msgs, info = np.zeros(2, FE.BAG_IMAGE_DTYPE), FE.BagImageInfo()
-        calls = {}
-        for form in (0, 1):
-            os.environ["ESVIO_FE_IMAGE_WAVE_LOADS"] = str(form)
-            ft = FE.FeatureTracker(FE.make_config(W, H))
-            del os.environ["ESVIO_FE_IMAGE_WAVE_LOADS"]
-            ft.bag_set_image_topics(*I.IMAGE_TOPICS)
+        ft = FE.FeatureTracker(FE.make_config(W, H))
+        ft.bag_set_image_topics(*I.IMAGE_TOPICS)
 
-            def call():
-                assert L.esvio_fe_decode_bag_images(ft._hd.h, FE._p(buf), len(buf), 0, C.byref(dptr), C.byref(caps), FE.DEVICE, FE._p(msgs), 2, C.byref(info)) == 0
+        def call():
+            assert L.esvio_fe_decode_bag_images(ft._hd.h, FE._p(buf), len(buf), 0, C.byref(dptr), C.byref(caps), FE.DEVICE, FE._p(msgs), 2, C.byref(info)) == 0
 
+        for _ in range(REPS):
+            call()
+        assert (info.cam[0].images, info.cam[1].images) == (1, 1)
+        for cam in range(2):
+            back = np.zeros(wh, np.uint8)
+            assert hip.hipMemcpy(C.c_void_p(back.ctypes.data), ddst[cam], C.c_size_t(wh), 2) == 0
+            assert back.tobytes() == want[cam][0].tobytes()
+        emit_us = []
+        for _ in range(BLOCKS):
+            ft.set_profiling(True)
+            ft.reset_kernel_stats()
             for _ in range(REPS):
                 call()
-            assert (info.cam[0].images, info.cam[1].images) == (1, 1)
-            for cam in range(2):
-                back = np.zeros(wh, np.uint8)
-                assert hip.hipMemcpy(C.c_void_p(back.ctypes.data), ddst[cam], C.c_size_t(wh), 2) == 0
-                assert back.tobytes() == want[cam][0].tobytes()
-            emit_us = []
-            for _ in range(BLOCKS):
-                ft.set_profiling(True)
-                ft.reset_kernel_stats()
-                for _ in range(REPS):
-                    call()
-                ms, launches = emit_stats(ft)
-                ft.set_profiling(False)
-                assert launches == REPS  # one launch per call
-                emit_us.append(ms / max(launches, 1) * 1e3)
-            plain = []  # the call's wall time without the timers' events
-            for _ in range(BLOCKS):
-                t0 = time.perf_counter()
-                for _ in range(REPS):
-                    call()
-                plain.append((time.perf_counter() - t0) / REPS * 1e6)
-            e, c = med(emit_us), med(plain)
-            gbs = 2 * wh * (bpp + 1) / (e[0] * 1e-6) / 1e9  # the pixels' bytes in, a byte per pixel out
-            label = "wave loads through LDS" if form else "per-lane loads"
-            print("    %-22s k_image_emit %7.1f us (%.1f - %.1f; %5.0f GB/s = %4.1f %% of the copy rate) | call %8.1f us (%.1f - %.1f) = %6.1f frame pairs/s"
-                  % (label, e[0], e[1], e[2], gbs, 100 * gbs / HBM_GBS, c[0], c[1], c[2], 1e6 / c[0]))
-            calls[label] = c[0]
-            emit[(tag, form)] = e
-            ft.close()
+            ms, launches = emit_stats(ft)
+            ft.set_profiling(False)
+            assert launches == REPS  # one launch per call
+            emit_us.append(ms / max(launches, 1) * 1e3)
+        plain = []  # the call's wall time without the timers' events
+        for _ in range(BLOCKS):
+            t0 = time.perf_counter()
+            for _ in range(REPS):
+                call()
+            plain.append((time.perf_counter() - t0) / REPS * 1e6)
+        e, c = med(emit_us), med(plain)
+        gbs = 2 * wh * (bpp + 1) / (e[0] * 1e-6) / 1e9  # the pixels' bytes in, a byte per pixel out
+        print("    k_image_emit %7.1f us (%.1f - %.1f; %5.0f GB/s = %4.1f %% of the copy rate) | call %8.1f us (%.1f - %.1f) = %6.1f frame pairs/s"
+              % (e[0], e[1], e[2], gbs, 100 * gbs / HBM_GBS, c[0], c[1], c[2], 1e6 / c[0]))
+        ft.close()
         if os.path.exists(SEQ):  # the bridge: one core walks and converts, then the gray images are uploaded
             with tempfile.NamedTemporaryFile(suffix=".bagbytes") as f:
                 f.write(data)
@@ -163,13 +155,9 @@ def main():
             total = float(seq["us_median"]) + u[0]
             print("    the bridge: walk and per-pixel conversion on one core %.0f us (%s - %s) + esvio_fe_mem_upload of both gray images %.0f us (%.0f - %.0f) = %.0f us"
                   % (float(seq["us_median"]), seq["us_min"], seq["us_max"], u[0], u[1], u[2], total))
-            for label, c in calls.items():
-                print("    the bridge / the call, %s: %.2f" % (label, total / c))
+            print("    the bridge / the call: %.2f" % (total / c[0]))
         for cam in range(2):
             L.esvio_fe_mem_free(FE.DEVICE, ddst[cam])
-    a, b = emit[("DSEC", 0)], emit[("DSEC", 1)]
-    print("the default form of ESVIO_FE_IMAGE_WAVE_LOADS is the one this run measures faster at 1440x1080 rgb8: %s (per-lane %.1f us (%.1f - %.1f), wave loads %.1f us (%.1f - %.1f))"
-          % (("0, per-lane loads" if a[0] <= b[0] else "1, wave loads through LDS"), a[0], a[1], a[2], b[0], b[1], b[2]))
 
 
 if __name__ == "__main__":

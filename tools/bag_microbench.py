@@ -3,9 +3,8 @@
 sensor_msgs/Imu at 1 kHz and one image-like message of W x H bytes on a foreign topic, three messages per chunk
 (tests/bag_ref.py's writer).  Per batch: the host walks alone (esvio_fe_bag_walk_tap: the counting walk, then the
 gathering one — what the call runs before any device work); the copy of the gathered bytes from pinned memory
-(esvio_fe_mem_upload, with its wait); k_bag_emit in both forms of its load (ESVIO_FE_BAG_WAVE_LOADS=0 / 1) from the
-LIBRARY'S OWN TIMERS (esvio_fe_get_kernel_stats: HIP events around the launch), its bytes as a share of the measured copy
-rate; the whole call's wall time from pageable memory into device memory.  Beside it the bridge the call replaces:
+(esvio_fe_mem_upload, with its wait); k_bag_emit from the LIBRARY'S OWN TIMERS (esvio_fe_get_kernel_stats: HIP events
+around the launch), its bytes as a share of the measured copy rate; the whole call's wall time from pageable memory into device memory.  Beside it the bridge the call replaces:
 tools/bag_seq_decode.cpp on one core, then esvio_fe_mem_upload of its records.  Per figure: the median of BLOCKS blocks
 of REPS after a warm-up block, and the blocks' min - max.  One process, one pass, no retries; run it under a time limit:
 
@@ -116,48 +115,44 @@ def main():
         dptr = (C.c_void_p * 2)(ddst[0].value, ddst[1].value)
         msgs, info = np.zeros(8, FE.BAG_MESSAGE_DTYPE), FE.BagInfo()
         row = dict(batch=tag, n=n, bag_bytes=len(data), count_walk_us=cw, gather_walk_us=gw, copy_us=cp)
-        for form in (0, 1):
-            os.environ["ESVIO_FE_BAG_WAVE_LOADS"] = str(form)
-            ft = FE.FeatureTracker(FE.make_config(W, H))
-            del os.environ["ESVIO_FE_BAG_WAVE_LOADS"]
-            ft.bag_set_topics(*B.TOPICS)
+        ft = FE.FeatureTracker(FE.make_config(W, H))
+        ft.bag_set_topics(*B.TOPICS)
 
-            def call():
-                ft.decode_reset()
-                assert L.esvio_fe_decode_bag(ft._hd.h, FE._p(buf), len(buf), 0, C.byref(dptr), C.byref(caps), FE.DEVICE, FE._p(msgs), 8, C.byref(info)) == 0
+        def call():
+            ft.decode_reset()
+            assert L.esvio_fe_decode_bag(ft._hd.h, FE._p(buf), len(buf), 0, C.byref(dptr), C.byref(caps), FE.DEVICE, FE._p(msgs), 8, C.byref(info)) == 0
 
+        for _ in range(REPS):
+            call()
+        assert [info.cam[0].events, info.cam[1].events] == n and info.cam[0].bad == 0
+        for cam in range(2):
+            back = np.zeros(n[cam], want[cam].dtype)
+            assert hip.hipMemcpy(C.c_void_p(back.ctypes.data), ddst[cam], C.c_size_t(16 * n[cam]), 2) == 0
+            assert back.tobytes() == want[cam].tobytes()
+        emit_us, call_us = [], []
+        for _ in range(BLOCKS):
+            ft.set_profiling(True)
+            ft.reset_kernel_stats()
+            t0 = time.perf_counter()
             for _ in range(REPS):
                 call()
-            assert [info.cam[0].events, info.cam[1].events] == n and info.cam[0].bad == 0
-            for cam in range(2):
-                back = np.zeros(n[cam], want[cam].dtype)
-                assert hip.hipMemcpy(C.c_void_p(back.ctypes.data), ddst[cam], C.c_size_t(16 * n[cam]), 2) == 0
-                assert back.tobytes() == want[cam].tobytes()
-            emit_us, call_us = [], []
-            for _ in range(BLOCKS):
-                ft.set_profiling(True)
-                ft.reset_kernel_stats()
-                t0 = time.perf_counter()
-                for _ in range(REPS):
-                    call()
-                call_us.append((time.perf_counter() - t0) / REPS * 1e6)
-                ms, launches = emit_stats(ft)
-                ft.set_profiling(False)
-                emit_us.append(ms / max(launches, 1) * 1e3)
-            # the call's wall time without the timers' events
-            plain = []
-            for _ in range(BLOCKS):
-                t0 = time.perf_counter()
-                for _ in range(REPS):
-                    call()
-                plain.append((time.perf_counter() - t0) / REPS * 1e6)
-            e, c = med(emit_us), med(plain)
-            gbs = 29 * sum(n) / (e[0] * 1e-6) / 1e9  # 13 bytes in, 16 out
-            name = "wave loads through LDS" if form else "per-lane loads"
-            print("    %-22s k_bag_emit %6.1f us (%.1f - %.1f; %5.0f GB/s = %4.1f %% of the copy rate) | call %7.1f us (%.1f - %.1f) = %6.1f Mev/s"
-                  % (name, e[0], e[1], e[2], gbs, 100 * gbs / HBM_GBS, c[0], c[1], c[2], sum(n) / c[0]))
-            row[name] = dict(emit_us=e, emit_gbs=gbs, emit_copy_frac=gbs / HBM_GBS, call_us=c, call_us_profiled=med(call_us), mev_s_call=sum(n) / c[0])
-            ft.close()
+            call_us.append((time.perf_counter() - t0) / REPS * 1e6)
+            ms, launches = emit_stats(ft)
+            ft.set_profiling(False)
+            emit_us.append(ms / max(launches, 1) * 1e3)
+        # the call's wall time without the timers' events
+        plain = []
+        for _ in range(BLOCKS):
+            t0 = time.perf_counter()
+            for _ in range(REPS):
+                call()
+            plain.append((time.perf_counter() - t0) / REPS * 1e6)
+        e, c = med(emit_us), med(plain)
+        gbs = 29 * sum(n) / (e[0] * 1e-6) / 1e9  # 13 bytes in, 16 out
+        print("    k_bag_emit %6.1f us (%.1f - %.1f; %5.0f GB/s = %4.1f %% of the copy rate) | call %7.1f us (%.1f - %.1f) = %6.1f Mev/s"
+              % (e[0], e[1], e[2], gbs, 100 * gbs / HBM_GBS, c[0], c[1], c[2], sum(n) / c[0]))
+        row["k_bag_emit"] = dict(emit_us=e, emit_gbs=gbs, emit_copy_frac=gbs / HBM_GBS, call_us=c, call_us_profiled=med(call_us), mev_s_call=sum(n) / c[0])
+        ft.close()
         if os.path.exists(SEQ):  # the bridge: one core walks and deserializes, then the records are uploaded
             with tempfile.NamedTemporaryFile(suffix=".bagbytes") as f:
                 f.write(data)
@@ -177,9 +172,8 @@ def main():
                                  total_us=total, mev_s=sum(n) / total)
             print("    the bridge: walk and deserialization on one core %.0f us (%s - %s) + esvio_fe_mem_upload of both cameras' records %.0f us (%.0f - %.0f) = %.0f us = %.1f Mev/s"
                   % (float(seq["us_median"]), seq["us_min"], seq["us_max"], u[0], u[1], u[2], total, sum(n) / total))
-            for name in ("per-lane loads", "wave loads through LDS"):
-                print("    the bridge / the call, %s: %.2f" % (name, total / row[name]["call_us"][0]))
-                row[name]["bridge_over_call"] = total / row[name]["call_us"][0]
+            print("    the bridge / the call: %.2f" % (total / row["k_bag_emit"]["call_us"][0]))
+            row["k_bag_emit"]["bridge_over_call"] = total / row["k_bag_emit"]["call_us"][0]
         for cam in range(2):
             L.esvio_fe_mem_free(FE.DEVICE, ddst[cam])
         rows.append(row)

@@ -5,7 +5,6 @@ that is.  One process, one pass, no retries; run it under a time limit:
 
     timeout -k 10 300 python tools/fast_microbench.py [--json out.json]
 
-ESVIO_FE_FAST_LDS=1 in the environment measures k_fast_score's LDS-tiled form instead of the direct reads.
 The reference's one-core CPU time (plain C++, from tests/golden/fast_ref_*.npz: another machine, context only) is
 printed beside each size."""
 import json
@@ -57,7 +56,7 @@ def main():
             nblk = (P + 255) // 256
             by = {"k_fast_score": 2 * P, "k_fast_collect": P + 8 * n + 4 * nblk, "k_compact": 16 * n + 4 * nblk}
             row = dict(W=W, H=H, arc=arc, nonmax=int(nonmax), corners=int(n), detected=int(nd), call_us=call_us,
-                       lds=int("ESVIO_FE_FAST_LDS" in os.environ), cpu_ref_ms=[float(v) for v in cpu])
+                       cpu_ref_ms=[float(v) for v in cpu])
             line = "  arc %2d nonmax %d: %6d corners (%6d detected)" % (arc, nonmax, n, nd)
             for k in us:
                 gbs = by[k] / (us[k] * 1e-6) / 1e9 if us[k] > 0 else 0.0
