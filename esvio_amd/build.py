@@ -73,8 +73,26 @@ TOOL_SRC = os.path.join(HERE, "..", "tools", "replay_node.cpp")
 TOOL_BIN = os.path.join(HERE, "..", "tools", "replay_node")
 
 
+FRAME_SEQ_SRC = os.path.join(HERE, "..", "tools", "aedat_frame_seq.cpp")
+FRAME_SEQ_BIN = os.path.join(HERE, "..", "tools", "_bin", "aedat_frame_seq")
+
+
+def build_frame_seq(force=False):
+    """tools/_bin/aedat_frame_seq: the driver's per-pixel frame loop on one core over the project's own host walk
+    (tools/aedat_frame_microbench.py runs it), plain g++, no device code"""
+    src, out = os.path.abspath(FRAME_SEQ_SRC), os.path.abspath(FRAME_SEQ_BIN)
+    deps = [src, os.path.join(CSRC, "fe_aedat.h"), os.path.join(HERE, "..", "include", "esvio_fe.h")]
+    if not force and os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(d) for d in deps):
+        return out
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    subprocess.check_call([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-Wall", "-I" + CSRC, src, "-o", out])
+    return out
+
+
 def build_tools(force=False):
-    """tools/replay_node: the C++ host harness (handle_stereo_event over the C ABI), plain g++"""
+    """tools/replay_node: the C++ host harness (handle_stereo_event over the C ABI), plain g++; and, beside it,
+    tools/_bin/aedat_frame_seq (build_frame_seq)"""
+    build_frame_seq(force)
     src, out = os.path.abspath(TOOL_SRC), os.path.abspath(TOOL_BIN)
     if not force and os.path.exists(out) and os.path.getmtime(out) >= max(
             os.path.getmtime(src), os.path.getmtime(LIB), os.path.getmtime(os.path.join(HERE, "..", "include", "esvio_fe.h"))):

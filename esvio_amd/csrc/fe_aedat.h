@@ -6,11 +6,17 @@
 // cache line per packet.  The event walk gathers the polarity records of a chunk, and nothing else, into one packed array
 // and writes a run table beside it (per run of records with one eventTSOverflow: the index of its first record); the
 // device decodes that array one record per lane.  The side walk decodes special and IMU6 packets where they lie: they
-// are few.  A record cut by the chunk's end waits in the state and is completed by the next chunk.
+// are few.  A record cut by the chunk's end waits in the state and is completed by the next chunk.  The frame walk
+// ("AEDAT 3.1 frames") gathers each emitted frame event's pixel bytes, and nothing else, each from a 16-byte boundary, and
+// lists the frames; the pixel bytes of a frame that the call's end cuts wait in a carry buffer beside the state (Carry),
+// the way fe_bag.h's image mode keeps an Image payload.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <string.h>
+
+#include <vector>
 
 #include "../../include/esvio_fe.h"
 
@@ -19,10 +25,12 @@ namespace aedat {
 
 constexpr uint32_t kHeaderBytes = 28, kMaxRecordBytes = 36;
 constexpr int kSpecial = 0, kPolarity = 1, kImu6 = 3;
+constexpr int kFrame = 2;
+constexpr uint32_t kFrameHead = 36;  // a frame event's head: info, four stamps, lengthX/Y, positionX/Y
 constexpr uint64_t kStampLimitNs = 4294967296ull * 1000000000ull;  // sec >= 2^32
 
-// One walker's state (a handle has two per camera: the event call's and the side call's).  Between packets
-// payload_left == 0; all zero is the fresh state.
+// One walker's state (a handle has three per camera: the event call's, the side call's and the frame call's).  Between
+// packets payload_left == 0; all zero is the fresh state.
 struct Walk {
   uint8_t hdr[kHeaderBytes];     // the header bytes collected so far
   uint32_t hdr_have;             // 0..27
@@ -32,6 +40,22 @@ struct Walk {
   uint64_t payload_left;         // payload bytes still to come, records and padding
   uint8_t rec[kMaxRecordBytes];  // the bytes of a record cut by the chunk's end
   uint32_t rec_have;             // 0..ev_size-1
+  // the frame walk alone (rec holds the open frame event's head, which stays until the event ends)
+  uint32_t ev_off;               // bytes of the open frame event that have come, 0..ev_size-1
+  uint32_t slot;                 // its position within its packet
+  uint32_t emit;                 // it is emitted when its last pixel byte comes (else: dropped, BAD, or its pixels are behind us)
+  uint32_t f_sec, f_nsec;        // ... with this stamp
+  uint32_t carry_buf;            // which of the Carry's two buffers holds its pixel bytes so far
+  uint64_t pix_left;             // its pixel bytes still to come
+  uint64_t carry_len;            // ... and how many wait in the Carry
+};
+
+// The pixel bytes of a frame that a call's end cut, beside the frame walker's state (Walk::carry_buf, carry_len say which
+// buffer and how much of it counts).  Two buffers, used as fe_bag.h's Carry is: a call whose first frame was waiting in
+// one puts what it leaves waiting into the other, so a call that fails after its gathering walk has overwritten nothing
+// of the state it goes back to.  A frame still open at the call's end grows in place, behind the bytes that count.
+struct Carry {
+  std::vector<uint8_t> buf[2];
 };
 
 struct Run {  // the records from `first` on (up to the next run's first) have this eventTSOverflow
@@ -82,12 +106,22 @@ struct Out {
   size_t trig_cap = 0;
   uint64_t n_imu = 0, n_trig = 0, resets = 0, other_specials = 0, invalid = 0, bad = 0;
   uint64_t special_packets = 0, imu_packets = 0;
-  // both
+  // the frame walk: want_w x want_h the only size taken (0: any); pix null: counted only; carry null: nothing waits
+  uint32_t want_w = 0, want_h = 0;
+  Carry* carry = nullptr;
+  uint8_t* pix = nullptr;  // room for pix_cap bytes: the emitted frames' pixel bytes, each from a 16-byte boundary
+  size_t pix_cap = 0;
+  esvio_fe_aedat_frame* frames = nullptr;
+  size_t frames_cap = 0;
+  uint64_t n_pix_bytes = 0, n_frames = 0, frame_packets = 0;  // counted whether stored or not
+  uint32_t first_stamp[2] = {0, 0}, last_stamp[2] = {0, 0};   // (sec, nsec) of the first / last emitted frame
+  // all
   uint64_t other_packets = 0;
-  const char* why = nullptr;  // a malformed header: which rule it breaks
+  const char* why = nullptr;  // a malformed header or event, or a refused frame: which rule it breaks
+  char why_buf[160];
 };
 
-enum Mode { kEvents = 0, kSide = 1 };
+enum Mode { kEvents = 0, kSide = 1, kFrames = 2 };
 
 // a complete header -> the open packet; false: malformed (out->why says how)
 inline bool open_packet(Walk* w, Mode mode, Out* out) {
@@ -101,8 +135,13 @@ inline bool open_packet(Walk* w, Mode mode, Out* out) {
     if (size != (type == kImu6 ? 36 : 8)) return out->why = "eventSize differs from the type's", false;
     if (ts_off != 4) return out->why = "eventTSOffset differs from the type's", false;
   }
+  if (mode == kFrames && type == kFrame) {
+    if (size < (int32_t)kFrameHead) return out->why = "a frame packet's eventSize is below 36", false;
+    if ((size - (int32_t)kFrameHead) & 1) return out->why = "a frame packet's eventSize - 36 is odd", false;
+    if (ts_off != 12) return out->why = "a frame packet's eventTSOffset is not 12", false;
+  }
   w->type = type, w->ev_size = size, w->overflow = overflow;
-  w->decoded = mode == kEvents ? type == kPolarity : (type == kSpecial || type == kImu6);
+  w->decoded = mode == kEvents ? type == kPolarity : mode == kSide ? (type == kSpecial || type == kImu6) : type == kFrame;
   w->events_left = w->decoded ? (uint64_t)number : 0;
   w->payload_left = (uint64_t)capacity * (uint64_t)size;
   if (type == kPolarity)
@@ -111,6 +150,8 @@ inline bool open_packet(Walk* w, Mode mode, Out* out) {
     out->special_packets++;
   else if (type == kImu6)
     out->imu_packets++;
+  else if (mode == kFrames && type == kFrame)
+    out->frame_packets++, w->slot = 0;
   else
     out->other_packets++;
   return true;
@@ -173,10 +214,110 @@ inline void take_records(const Walk& w, Mode mode, const uint8_t* p, uint64_t co
   }
 }
 
-// The walk: *w advanced by the n bytes at `bytes`.  Returns false at a malformed header; the caller works on a copy of
+// ---- the frame walk (the rule: include/esvio_fe.h "AEDAT 3.1 frames") ----
+// The open frame event's head is complete (w->rec): what becomes of the event.  false: malformed or refused (out->why).
+inline bool frame_head(Walk* w, int64_t t_offset_ns, uint32_t flags, Out* out) {
+  const uint32_t info = rd_u32(w->rec);
+  w->emit = 0, w->pix_left = 0;
+  if (!(info & 1u) && !(flags & ESVIO_FE_AEDAT_KEEP_INVALID)) {
+    out->invalid++;
+    return true;
+  }
+  const int64_t lx = rd_i32(w->rec + 20), ly = rd_i32(w->rec + 24), ch = (info >> 1) & 7u;
+  const uint64_t room = (uint64_t)((uint32_t)w->ev_size - kFrameHead);
+  if (lx < 1) return out->why = "a frame event's lengthX is below 1", false;
+  if (ly < 1) return out->why = "a frame event's lengthY is below 1", false;
+  // lengthX * lengthY * channels * 2 > eventSize - 36 in exact integers: the first product is below 2^62
+  if (ch && (uint64_t)(lx * ly) > room / (uint64_t)(2 * ch)) return out->why = "a frame event's lengthX * lengthY * channels * 2 exceeds eventSize - 36", false;
+  if (ch != 1 && ch != 3) {
+    snprintf(out->why_buf, sizeof out->why_buf, "a frame event with %d channels: 1 (mono8) and 3 (rgb8) are taken", (int)ch);
+    return out->why = out->why_buf, false;
+  }
+  if (out->want_w && (lx != (int64_t)out->want_w || ly != (int64_t)out->want_h)) {
+    snprintf(out->why_buf, sizeof out->why_buf, "a frame event of %d x %d, the handle's size is %u x %u: cv::resize is out of scope", (int)lx, (int)ly,
+             out->want_w, out->want_h);
+    return out->why = out->why_buf, false;
+  }
+  const int64_t s = rd_i32(w->rec + 12), e = rd_i32(w->rec + 16);
+  const int64_t ts = s + (e - s) / 2;  // (between s and e: an int32)
+  uint64_t ticks;
+  if (!stamp((int32_t)ts, w->overflow, t_offset_ns, &w->f_sec, &w->f_nsec, &ticks)) {
+    out->bad++;
+    return true;
+  }
+  w->emit = 1, w->pix_left = (uint64_t)(lx * ly) * (uint64_t)(2 * ch);
+  return true;
+}
+
+// `take` pixel bytes of the open frame event at p.  The event's last ones: the frame, the waiting bytes in front, goes to
+// out->pix at the next 16-byte boundary and is listed.  Else the call ends inside it: they wait.
+inline void frame_pixels(Walk* w, const uint8_t* p, uint64_t take, uint32_t start_buf, Out* out) {
+  if (take < w->pix_left) {
+    if (w->carry_len == 0) w->carry_buf = start_buf ^ 1u;  // (never the buffer the call's first frame waited in)
+    if (out->carry) {
+      std::vector<uint8_t>& b = out->carry->buf[w->carry_buf & 1u];
+      if (b.size() < w->carry_len + take) b.resize((size_t)(w->carry_len + take));
+      memcpy(b.data() + w->carry_len, p, (size_t)take);
+    }
+    w->carry_len += take, w->pix_left -= take;
+    return;
+  }
+  const uint64_t total = w->carry_len + take;
+  if (out->pix && out->carry && out->n_pix_bytes + total <= out->pix_cap) {
+    if (w->carry_len) memcpy(out->pix + out->n_pix_bytes, out->carry->buf[w->carry_buf & 1u].data(), (size_t)w->carry_len);
+    memcpy(out->pix + out->n_pix_bytes + w->carry_len, p, (size_t)take);
+  }
+  out->n_pix_bytes += (total + 15) & ~(uint64_t)15;
+  if (out->frames && out->n_frames < out->frames_cap) {
+    static_assert(sizeof(esvio_fe_aedat_frame) == 80 && offsetof(esvio_fe_aedat_frame, exposure_us) == 24 && offsetof(esvio_fe_aedat_frame, index) == 72,
+                  "esvio_fe_aedat_frame layout");
+    const uint32_t info = rd_u32(w->rec);
+    esvio_fe_aedat_frame f;
+    memset(&f, 0, sizeof f);
+    f.stamp_sec = w->f_sec, f.stamp_nsec = w->f_nsec;
+    f.ts_startframe = rd_i32(w->rec + 4), f.ts_endframe = rd_i32(w->rec + 8);
+    f.ts_startexposure = rd_i32(w->rec + 12), f.ts_endexposure = rd_i32(w->rec + 16);
+    f.exposure_us = (int64_t)f.ts_endexposure - (int64_t)f.ts_startexposure;
+    f.length_x = rd_i32(w->rec + 20), f.length_y = rd_i32(w->rec + 24), f.position_x = rd_i32(w->rec + 28), f.position_y = rd_i32(w->rec + 32);
+    f.channels = (int32_t)((info >> 1) & 7u), f.color_filter = (int32_t)((info >> 4) & 15u), f.roi = (int32_t)((info >> 8) & 127u);
+    f.valid = (int32_t)(info & 1u), f.slot = (int32_t)w->slot, f.ts_overflow = w->overflow;
+    f.index = out->n_frames;
+    out->frames[out->n_frames] = f;
+  }
+  if (out->n_frames == 0) out->first_stamp[0] = w->f_sec, out->first_stamp[1] = w->f_nsec;
+  out->last_stamp[0] = w->f_sec, out->last_stamp[1] = w->f_nsec;
+  out->n_frames++;
+  w->carry_len = 0, w->pix_left = 0, w->emit = 0;
+}
+
+// the bytes at bytes[*pos .. n) that belong to the open frame event: its head, its pixels, what lies behind them
+inline bool frame_bytes(Walk* w, const uint8_t* bytes, size_t n, size_t* pos, uint32_t start_buf, int64_t t_offset_ns, uint32_t flags, Out* out) {
+  if (w->ev_off < kFrameHead) {
+    const size_t take = n - *pos < kFrameHead - w->ev_off ? n - *pos : kFrameHead - w->ev_off;
+    memcpy(w->rec + w->ev_off, bytes + *pos, take);
+    w->ev_off += (uint32_t)take, *pos += take, w->payload_left -= take;
+    if (w->ev_off < kFrameHead) return true;
+    if (!frame_head(w, t_offset_ns, flags, out)) return false;
+  }
+  if (w->pix_left) {
+    if (*pos == n) return true;
+    const uint64_t take = w->pix_left < n - *pos ? w->pix_left : n - *pos;
+    frame_pixels(w, bytes + *pos, take, start_buf, out);
+    *pos += (size_t)take, w->ev_off += (uint32_t)take, w->payload_left -= take;
+    if (w->pix_left) return true;
+  }
+  const uint64_t rest = (uint32_t)w->ev_size - w->ev_off, skip = rest < n - *pos ? rest : n - *pos;
+  *pos += (size_t)skip, w->ev_off += (uint32_t)skip, w->payload_left -= skip;
+  if (w->ev_off == (uint32_t)w->ev_size) w->ev_off = 0, w->events_left--, w->slot++;
+  return true;
+}
+
+// The walk: *w advanced by the n bytes at `bytes`.  Returns false at a malformed header (in the frame walk: or event, or
+// a refused frame); the caller works on a copy of
 // the state and takes it over when the whole call succeeds.  Reads bytes[0 .. n) and nothing else.
 inline bool walk(Walk* w, Mode mode, const uint8_t* bytes, size_t n, int64_t t_offset_ns, uint32_t flags, Out* out) {
   size_t pos = 0;
+  const uint32_t start_buf = w->carry_len ? w->carry_buf : w->carry_buf ^ 1u;  // the Carry buffer whose bytes count at the call's start
   while (pos < n) {
     if (w->payload_left == 0) {  // between packets: the header
       const size_t take = n - pos < kHeaderBytes - w->hdr_have ? n - pos : kHeaderBytes - w->hdr_have;
@@ -185,6 +326,10 @@ inline bool walk(Walk* w, Mode mode, const uint8_t* bytes, size_t n, int64_t t_o
       if (w->hdr_have < kHeaderBytes) break;
       if (!open_packet(w, mode, out)) return false;
       w->hdr_have = 0;
+      continue;
+    }
+    if (w->events_left && mode == kFrames) {
+      if (!frame_bytes(w, bytes, n, &pos, start_buf, t_offset_ns, flags, out)) return false;
       continue;
     }
     if (w->events_left) {

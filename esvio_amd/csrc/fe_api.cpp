@@ -2313,7 +2313,7 @@ int aedat_reserve(esvio_fe_ctx* c, const size_t events[2]) {
   return 0;
 }
 void aedat_state_reset(esvio_fe_ctx* c) {
-  for (int cam = 0; cam < 2; cam++) c->aedat.ev_st[cam] = c->aedat.side_st[cam] = ae::Walk{};
+  for (int cam = 0; cam < 2; cam++) c->aedat.ev_st[cam] = c->aedat.side_st[cam] = c->aedat.frame_st[cam] = ae::Walk{};
 }
 // The gathering walk and the chain of one camera (job[1].n_bytes == 0) or of both on the current stream, and the copies
 // that bring the result blocks to the host; nothing is waited for.  dc[k].d, cap: where job[k]'s records go.  A camera
@@ -2741,9 +2741,10 @@ int esvio_fe_bag_walk_tap(void* state, size_t state_bytes, const esvio_fe_bag_to
 }
 int esvio_fe_bag_walk_state_bytes(void) { return (int)sizeof(bg::Walk); }
 
-// (the rosbag image stage stands at the end of the file)
+// (the rosbag image stage and the AEDAT frame stage stand at the end of the file)
 namespace {
 int bag_image_reserve(esvio_fe_ctx* c);
+int aedat_frame_reserve(esvio_fe_ctx* c);
 void bag_image_state_reset(esvio_fe_ctx* c);
 void decode_state_reset(esvio_fe_ctx* c) { raw_state_reset(c), aedat_state_reset(c), bag_state_reset(c), bag_image_state_reset(c); }
 }  // namespace
@@ -4185,6 +4186,7 @@ int esvio_fe_reserve(esvio_fe_handle c, size_t max_left, size_t max_right, int h
   if (int rc = aedat_reserve(c, events)) return rc;
   if (int rc = bag_reserve(c, events)) return rc;
   if (int rc = bag_image_reserve(c)) return rc;
+  if (int rc = aedat_frame_reserve(c)) return rc;
   // a handle with an open feed: per camera both buffers for 2 * max_events records (the one that holds records is left alone)
   if (c->feed.open) {
     const size_t ev[2] = {max_left, max_right};
@@ -4475,6 +4477,178 @@ int esvio_fe_bag_image_walk_tap(void* state, size_t state_bytes, const char* lef
   }
   const uint64_t v[12] = {cnt.n_imgs, cnt.n_cam_imgs[0], cnt.n_cam_imgs[1], cnt.n_pix_bytes, cnt.other_messages, cnt.other_records,
                           cnt.chunks, cnt.connections, ok ? st.carry_len : 0, 0, 0, 0};
+  memcpy(counts, v, sizeof v);
+  if (!ok) {  // (the caller's state and carry are as they were)
+    if (why && why_cap) snprintf(why, why_cap, "%s", cnt.why ? cnt.why : "carry_cap is too small for the bytes that wait");
+    return ESVIO_FE_EINVAL;
+  }
+  if (st.carry_len) memcpy(carry, cy.buf[st.carry_buf & 1u].data(), (size_t)st.carry_len);
+  memcpy(state, &st, sizeof st);
+  return 0;
+}
+
+// ---- AEDAT 3.1 frames (the rule: include/esvio_fe.h "AEDAT 3.1 frames"; the host walk: fe_aedat.h; the kernel: fe_kernels.h)
+namespace {
+size_t frame_slot(size_t pixel_bytes) { return (pixel_bytes + 15) & ~(size_t)15; }
+// the scratch of pix_bytes gathered pixel bytes (padding included) and n_frames descriptors, and gray_bytes behind a host dst
+int aedat_frame_ensure(esvio_fe_ctx* c, size_t pix_bytes, size_t n_frames, size_t gray_bytes) {
+  esvio_fe_ctx::Aedat& A = c->aedat;
+  A.frm_used = true;
+  const size_t bytes = frame_slot(pix_bytes) + n_frames * sizeof(Frame16Desc);
+  if (int rc = A.h_frm.grow(c, bytes)) return rc;
+  if (int rc = A.d_frm.grow(c, bytes)) return rc;
+  return gray_bytes ? A.d_gray.grow(c, gray_bytes) : 0;
+}
+// esvio_fe_reserve for a handle that decodes frames: the scratch of one rgb frame of its size
+int aedat_frame_reserve(esvio_fe_ctx* c) {
+  return c->aedat.frm_used ? aedat_frame_ensure(c, frame_slot((size_t)c->W * c->H * 6), 1, (size_t)c->W * c->H) : 0;
+}
+// the copy of the gathered bytes and the table, and the launch, on the current stream; nothing is waited for
+int aedat_frame_enqueue(esvio_fe_ctx* c, size_t table_at, uint32_t n_frames, uint32_t width, uint32_t height, uint64_t alg_bytes) {
+  esvio_fe_ctx::Aedat& A = c->aedat;
+  hipStream_t s = cur_stream(c);
+  HIPCHK(c, hipMemcpyAsync(A.d_frm, A.h_frm, table_at + n_frames * sizeof(Frame16Desc), hipMemcpyHostToDevice, s));
+  Frame16Args a{};
+  a.desc = (const Frame16Desc*)(A.d_frm.p + table_at), a.n_frames = n_frames, a.width = width, a.height = height;
+  ScopedKernel k(c, K_FRAME16_EMIT, alg_bytes);
+  launch_frame16_emit(s, a);
+  return 0;
+}
+}  // namespace
+
+int esvio_fe_frame16_tile_pixels(void) { return (int)kFrame16Tile; }
+
+int esvio_fe_aedat_frame_kernel_stats(esvio_fe_handle c, double* total_ms, uint64_t* launches, uint64_t* alg_bytes) {
+  if (!c) return ESVIO_FE_EINVAL;
+  HIPCHK(c, hipSetDevice(c->dev));
+  HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  resolve_profile(c);
+  const KStat& s = c->stats[K_FRAME16_EMIT];
+  if (total_ms) *total_ms = s.ms;
+  if (launches) *launches = s.launches;
+  if (alg_bytes) *alg_bytes = s.bytes;
+  return 0;
+}
+
+int esvio_fe_decode_aedat_frames(esvio_fe_handle c, int cam, const void* bytes, size_t n_bytes, int64_t t_offset_ns, uint32_t flags,
+                                 uint8_t* dst, size_t dst_cap, int dst_space, esvio_fe_aedat_frame* frames, size_t frames_cap,
+                                 esvio_fe_aedat_frame_info* info) {
+  if (!c) return ESVIO_FE_EINVAL;
+  if (info) *info = esvio_fe_aedat_frame_info{};
+  const char* who = "decode_aedat_frames";
+  if (cam != 0 && cam != 1) return fail(c, ESVIO_FE_EINVAL, "%s: cam must be 0 or 1 (got %d)", who, cam);
+  if (int rc = aedat_args_check(c, who, bytes, n_bytes, t_offset_ns, flags)) return rc;
+  if (dst_space != ESVIO_FE_HOST && dst_space != ESVIO_FE_DEVICE) return fail(c, ESVIO_FE_EINVAL, "%s: bad memory space", who);
+  if (dst_cap && !dst) return fail(c, ESVIO_FE_EINVAL, "%s: dst is null", who);
+  if (frames_cap && !frames) return fail(c, ESVIO_FE_EINVAL, "%s: frames is null", who);
+  if (!n_bytes) return 0;
+  esvio_fe_ctx::Aedat& A = c->aedat;
+  const uint32_t W = (uint32_t)c->W, H = (uint32_t)c->H;
+  const size_t wh = (size_t)W * H;
+  // the counting walk: everything in the chunk checked, the frames and their bytes counted, nothing stored or moved
+  ae::Out cnt;
+  cnt.want_w = W, cnt.want_h = H;
+  {
+    ae::Walk probe = A.frame_st[cam];
+    if (!ae::walk(&probe, ae::kFrames, (const uint8_t*)bytes, n_bytes, t_offset_ns, flags, &cnt))
+      return fail(c, ESVIO_FE_EINVAL, "%s: malformed packet or refused frame (%s); the camera's state is as it was", who, cnt.why);
+  }
+  if (info) {
+    info->frames = cnt.n_frames, info->invalid = cnt.invalid, info->bad = cnt.bad;
+    info->frame_packets = cnt.frame_packets, info->other_packets = cnt.other_packets;
+    info->first_sec = cnt.first_stamp[0], info->first_nsec = cnt.first_stamp[1], info->last_sec = cnt.last_stamp[0], info->last_nsec = cnt.last_stamp[1];
+  }
+  if (cnt.bad)
+    return fail(c, ESVIO_FE_EINVAL, "%s: %llu frames have a stamp outside [0, 2^32 s); the camera's state is as it was", who, (unsigned long long)cnt.bad);
+  if (cnt.n_frames > dst_cap || cnt.n_frames > frames_cap)
+    return fail(c, ESVIO_FE_EINVAL, "%s: the chunk completes %llu frames, dst has room for %zu and frames for %zu; the camera's state is as it was", who,
+                (unsigned long long)cnt.n_frames, dst_cap, frames_cap);
+  const size_t n_all = (size_t)cnt.n_frames, table_at = (size_t)cnt.n_pix_bytes;
+  if (n_all) {
+    HIPCHK(c, hipSetDevice(c->dev));
+    if (int rc = aedat_frame_ensure(c, table_at, n_all, dst_space == ESVIO_FE_HOST ? n_all * wh : 0)) return rc;
+  }
+  // the gathering walk (checked by the counting walk): the emitted frames' pixel bytes into the pinned scratch, what the
+  // call's end cuts into the carry; the state it leaves is taken over at the end
+  ae::Out o;
+  o.want_w = W, o.want_h = H, o.carry = &A.carry[cam];
+  o.pix = n_all ? A.h_frm.p : nullptr, o.pix_cap = table_at, o.frames = frames, o.frames_cap = frames_cap;
+  ae::Walk st = A.frame_st[cam];
+  ae::walk(&st, ae::kFrames, (const uint8_t*)bytes, n_bytes, t_offset_ns, flags, &o);
+  if (n_all) {
+    Frame16Desc* desc = (Frame16Desc*)(A.h_frm.p + table_at);
+    uint8_t* base = dst_space == ESVIO_FE_HOST ? A.d_gray.p : dst;
+    size_t at = 0;
+    uint64_t alg = 0;
+    for (size_t k = 0; k < n_all; k++) {
+      const uint32_t ch = (uint32_t)frames[k].channels;
+      desc[k] = Frame16Desc{A.d_frm.p + at, base + k * wh, ch, 0u};
+      at += frame_slot(wh * ch * 2);
+      alg += (uint64_t)wh * (ch * 2 + 1);
+    }
+    if (int rc = aedat_frame_enqueue(c, table_at, (uint32_t)n_all, W, H, alg)) return rc;
+    if (dst_space == ESVIO_FE_HOST) HIPCHK(c, hipMemcpyAsync(dst, A.d_gray.p, n_all * wh, hipMemcpyDeviceToHost, cur_stream(c)));
+    HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+    if (c->prof_on) resolve_profile(c);
+  }
+  A.frame_st[cam] = st;
+  return 0;
+}
+
+int esvio_fe_convert_frame16(esvio_fe_handle c, const uint16_t* src, int src_space, uint32_t height, uint32_t width, int32_t channels,
+                             uint8_t* dst, int dst_space) {
+  if (!c) return ESVIO_FE_EINVAL;
+  const char* who = "convert_frame16";
+  if (!src || !dst) return fail(c, ESVIO_FE_EINVAL, "%s: src or dst is null", who);
+  if ((src_space != ESVIO_FE_HOST && src_space != ESVIO_FE_DEVICE) || (dst_space != ESVIO_FE_HOST && dst_space != ESVIO_FE_DEVICE))
+    return fail(c, ESVIO_FE_EINVAL, "%s: bad memory space", who);
+  if (height < 1 || height > kImageMaxSide || width < 1 || width > kImageMaxSide)
+    return fail(c, ESVIO_FE_EINVAL, "%s: height and width must be 1 .. %u", who, kImageMaxSide);
+  if (channels != 1 && channels != 3) return fail(c, ESVIO_FE_EINVAL, "%s: channels must be 1 (mono8) or 3 (rgb8), got %d", who, channels);
+  if ((uintptr_t)src & 1u) return fail(c, ESVIO_FE_EINVAL, "%s: src must be 2-byte aligned", who);
+  const size_t wh = (size_t)width * height, need = wh * (size_t)channels * 2;
+  esvio_fe_ctx::Aedat& A = c->aedat;
+  HIPCHK(c, hipSetDevice(c->dev));
+  const size_t table_at = frame_slot(src_space == ESVIO_FE_HOST ? need : 0);
+  if (int rc = aedat_frame_ensure(c, table_at, 1, dst_space == ESVIO_FE_HOST ? wh : 0)) return rc;
+  if (src_space == ESVIO_FE_HOST) memcpy(A.h_frm.p, src, need);
+  Frame16Desc* desc = (Frame16Desc*)(A.h_frm.p + table_at);
+  desc[0] = Frame16Desc{src_space == ESVIO_FE_HOST ? A.d_frm.p : (const uint8_t*)src, dst_space == ESVIO_FE_HOST ? A.d_gray.p : dst, (uint32_t)channels, 0u};
+  if (int rc = aedat_frame_enqueue(c, table_at, 1, width, height, (uint64_t)wh * (channels * 2 + 1))) return rc;
+  if (dst_space == ESVIO_FE_HOST) HIPCHK(c, hipMemcpyAsync(dst, A.d_gray.p, wh, hipMemcpyDeviceToHost, cur_stream(c)));
+  HIPCHK(c, hipStreamSynchronize(cur_stream(c)));
+  if (c->prof_on) resolve_profile(c);
+  return 0;
+}
+
+// the frame walk tap (include/esvio_fe_test.h): the host walk alone, no handle, no device
+int esvio_fe_aedat_frame_walk_tap(void* state, size_t state_bytes, uint32_t width, uint32_t height, const void* bytes, size_t n_bytes,
+                                  int64_t t_offset_ns, uint32_t flags, uint8_t* carry, size_t carry_cap, uint8_t* pix, size_t pix_cap,
+                                  esvio_fe_aedat_frame* frames, size_t frames_cap, uint64_t counts[8], char* why, size_t why_cap) {
+  if (why && why_cap) why[0] = 0;
+  if (!state || state_bytes != sizeof(ae::Walk) || (n_bytes && !bytes) || !counts) return ESVIO_FE_EINVAL;
+  ae::Walk st;
+  memcpy(&st, state, sizeof st);
+  if (st.carry_len > carry_cap || (st.carry_len && !carry)) return ESVIO_FE_EINVAL;
+  ae::Carry cy;
+  if (st.carry_len) cy.buf[st.carry_buf & 1u].assign(carry, carry + st.carry_len);
+  ae::Out cnt, o;
+  cnt.want_w = o.want_w = width, cnt.want_h = o.want_h = height;
+  ae::Walk probe = st;
+  bool ok = ae::walk(&probe, ae::kFrames, (const uint8_t*)bytes, n_bytes, t_offset_ns, flags, &cnt);  // the counting walk, as the library's call does
+  char bad_text[64];
+  if (ok && cnt.bad) {
+    snprintf(bad_text, sizeof bad_text, "%llu frames have a BAD stamp", (unsigned long long)cnt.bad);
+    cnt.why = bad_text, ok = false;
+  }
+  if (ok) {
+    o.carry = &cy;
+    if (pix && cnt.n_pix_bytes <= pix_cap) o.pix = pix, o.pix_cap = pix_cap;
+    o.frames = frames, o.frames_cap = frames ? frames_cap : 0;
+    ae::walk(&st, ae::kFrames, (const uint8_t*)bytes, n_bytes, t_offset_ns, flags, &o);
+    ok = st.carry_len <= carry_cap && (!st.carry_len || carry);
+  }
+  const uint64_t v[8] = {cnt.n_frames, cnt.n_pix_bytes, cnt.invalid, cnt.bad, cnt.frame_packets, cnt.other_packets, ok ? st.carry_len : 0, 0};
   memcpy(counts, v, sizeof v);
   if (!ok) {  // (the caller's state and carry are as they were)
     if (why && why_cap) snprintf(why, why_cap, "%s", cnt.why ? cnt.why : "carry_cap is too small for the bytes that wait");

@@ -109,11 +109,12 @@ struct PhaseClock {
 // and ingest tables (whose ends tests pin) stay as they are
 // ... and behind them the keyframe stage's three (esvio_fe_kf_kernel_count / _name / _stats, include/esvio_fe_test.h)
 // ... and behind those loop detection's four (esvio_fe_bow_kernel_count / _name / _stats)
+// ... and behind those the AEDAT frames' one, k_frame16_emit (esvio_fe_aedat_frame_kernel_stats)
 enum { K_EVIMG_MARK = K_INGEST_COUNT, K_EVIMG_EMIT, K_KF_BLUR, K_KF_BRIEF, K_KF_MATCH, K_BOW_WALK, K_BOW_VECTOR, K_BOW_SCORE,
-       K_BOW_SELECT, K_ALL_COUNT };
+       K_BOW_SELECT, K_FRAME16_EMIT, K_ALL_COUNT };
 constexpr int kKfKernels = K_BOW_WALK - K_KF_BLUR;
 const char* const kKfKernelNames[kKfKernels] = {"k_kf_blur", "k_kf_brief", "k_kf_match"};
-constexpr int kBowKernels = K_ALL_COUNT - K_BOW_WALK;
+constexpr int kBowKernels = K_FRAME16_EMIT - K_BOW_WALK;
 const char* const kBowKernelNames[kBowKernels] = {"k_bow_walk", "k_bow_vector", "k_bow_score", "k_bow_select"};
 
 struct KStat {
@@ -560,11 +561,12 @@ struct esvio_fe_ctx {
   } rawdec;
 
   // ---- esvio_fe_decode_aedat / esvio_fe_aedat_side / esvio_fe_track_aedat: libcaer packet streams (include/esvio_fe.h
-  // has the rule, fe_aedat.h the host walk, fe_kernels.h the chain).  ev_st / side_st: each camera's two walker states,
-  // on the HOST: a call walks a copy and takes it over only once it is known to succeed.  Per camera, allocated on first
-  // use and the stage's own (main stream only): h_pack, the pinned scratch the walk gathers into — the packed polarity
-  // records, the run table behind them at a 16-byte boundary —, d_pack its device copy (one transfer), sums the tiles'
-  // counts; res, the two result blocks.  The records behind a host dst, and in front of a filter, are rawdec.dec's.
+  // has the rule, fe_aedat.h the host walk, fe_kernels.h the chain).  ev_st / side_st: each camera's two walker states
+  // (frame_st: the third, below), on the HOST: a call walks a copy and takes it over only once it is known to succeed.
+  // Per camera, allocated on first use and the stage's own (main stream only): h_pack, the pinned scratch the walk
+  // gathers into — the packed polarity records, the run table behind them at a 16-byte boundary —, d_pack its device
+  // copy (one transfer), sums the tiles' counts; res, the two result blocks.  The records behind a host dst, and in
+  // front of a filter, are rawdec.dec's.
   struct Aedat {
     esvio::aedat::Walk ev_st[2] = {}, side_st[2] = {};
     PinBuf<uint8_t> h_pack[2];
@@ -572,6 +574,16 @@ struct esvio_fe_ctx {
     DevBuf<uint32_t> sums[2];
     DevBuf<AedatResult> res;
     bool used = false;  // esvio_fe_reserve grows the scratch of a handle that has decoded AEDAT before
+    // esvio_fe_decode_aedat_frames / esvio_fe_convert_frame16 ("AEDAT 3.1 frames").  frame_st: each camera's third walker
+    // state, carry the pixel bytes of the frame a call's end cut (fe_aedat.h: Carry), both on the HOST and taken over as
+    // the others are.  The stage's own, main stream only, allocated on first use: h_frm, the pinned scratch the walk
+    // gathers the frames' pixel bytes into, each frame from a 16-byte boundary, the descriptor table behind them; d_frm
+    // its device copy (one transfer); d_gray the images behind a host dst.
+    esvio::aedat::Walk frame_st[2] = {};
+    esvio::aedat::Carry carry[2];
+    PinBuf<uint8_t> h_frm;
+    DevBuf<uint8_t> d_frm, d_gray;
+    bool frm_used = false;  // esvio_fe_reserve grows the scratch of a handle that has decoded frames before
   } aedat;
 
   // ---- esvio_fe_decode_bag / esvio_fe_bag_side / esvio_fe_feed_push_bag: rosbag v2.0 recordings (include/esvio_fe.h has

@@ -791,6 +791,32 @@ struct ImageArgs {
 };
 void launch_image_emit(hipStream_t s, const ImageArgs& a);
 
+// ---- AEDAT 3.1 frames: 16-bit DAVIS frame pixels -> dense 8-bit gray (esvio_fe_decode_aedat_frames, esvio_fe_convert_frame16) ----
+// include/esvio_fe.h "AEDAT 3.1 frames" holds the rule.  The host has walked the packets (fe_aedat.h): what arrives here
+// is a table of frame descriptors — where the frame's uint16 values lie, dense and row-major with the channels
+// interleaved, how many channels, where the dense width x height gray image goes — and one launch, k_frame16_emit,
+// writes all of them: grid.y is the frame, a lane writes ONE ALIGNED DWORD of the destination as k_image_emit does, and
+// the dwords the image's ends share with its neighbours go pixel by pixel with byte stores.  The source is dense, so a
+// group never spans a row's padding: its 8 (mono) or 24 (colour) source bytes are consecutive, at any 2-BYTE alignment —
+// the scratch is 16-byte aligned, but the group's phase follows dst's, and esvio_fe_convert_frame16 takes a device
+// source wherever it lies.  Each lane assembles them with ld_pair16: a dword load where the address is dword aligned,
+// else two 16-bit loads (KERNELS.md "AEDAT frames").  The kernel's timer slot, K_FRAME16_EMIT, lies behind every other
+// table (fe_ctx.h).
+constexpr uint32_t kFrame16Tile = 1024;  // pixels per workgroup: 256 lanes, one destination dword each
+struct Frame16Desc {
+  const uint8_t* src;  // channels * width * height uint16 values, device memory, 2-byte aligned
+  uint8_t* dst;        // [width * height], device memory, any alignment
+  uint32_t channels;   // 1: value >> 8; 3: (R, G, B) = values >> 8 -> gray
+  uint32_t reserved;
+};
+static_assert(sizeof(Frame16Desc) == 24, "Frame16Desc layout");
+struct Frame16Args {
+  const Frame16Desc* desc;  // [n_frames] device memory
+  uint32_t n_frames;
+  uint32_t width, height;  // of every frame of the launch; width * height <= 2^26
+};
+void launch_frame16_emit(hipStream_t s, const Frame16Args& a);
+
 // ---- event images: detector.cur_event_mat_left/right (esvio_fe_set_event_images) ----
 // include/esvio_fe.h holds the rule: per camera the LAST event of the call at every pixel decides its colour.  Two
 // launches behind the SAE update of the handle's own planes, on its stream:

@@ -6315,4 +6315,54 @@ void launch_bow_select(hipStream_t s, const double* score, const uint8_t* presen
   launch_k(k_bow_select, dim3(1), dim3(256), 0, s, score, present, n_entries, max_results, out_id, out_score, out_raw, out_n);
 }
 
+// ============================================================================ AEDAT 3.1 frames
+// The uint16 pixels of DAVIS frame events -> dense gray images (fe_kernels.h has the lay-out of the work and the load,
+// include/esvio_fe.h "AEDAT 3.1 frames" the rule).  (Behind every other kernel of the file, for the reason the image stage
+// gives: appended here, it moves no existing kernel's place in the code object.)
+// two consecutive uint16 at a 2-byte aligned address: the first in the low half
+__device__ __forceinline__ uint32_t ld_pair16(const uint8_t* p) {
+  if (((uintptr_t)p & 3u) == 0) return *(const uint32_t*)p;
+  return (uint32_t) * (const uint16_t*)p | (uint32_t) * (const uint16_t*)(p + 2) << 16;
+}
+// the high bytes of the two values of a pair
+__device__ __forceinline__ uint32_t hi_lo(uint32_t pair) { return (pair >> 8) & 0xffu; }
+__device__ __forceinline__ uint32_t hi_hi(uint32_t pair) { return pair >> 24; }
+
+__global__ __launch_bounds__(256) void k_frame16_emit(Frame16Args a, uint32_t first_frame) {
+  const Frame16Desc d = a.desc[first_frame + blockIdx.y];
+  const int N = (int)(a.width * a.height);
+  const int shift = (int)((uintptr_t)d.dst & 3u);
+  const int p0 = (int)((blockIdx.x * 256u + threadIdx.x) * 4u) - shift;  // the lane's first pixel in the dense image (< 0: in front of it)
+  if (p0 >= N) return;
+  if (p0 >= 0 && p0 + 3 < N) {  // a whole dword: source bytes [p0 * 2 * channels, (p0 + 4) * 2 * channels) of the frame's
+    uint32_t v;
+    if (d.channels == 1u) {
+      const uint8_t* sp = d.src + (size_t)p0 * 2u;
+      const uint32_t q0 = ld_pair16(sp), q1 = ld_pair16(sp + 4);
+      v = hi_lo(q0) | hi_hi(q0) << 8 | hi_lo(q1) << 16 | hi_hi(q1) << 24;
+    } else {
+      const uint8_t* sp = d.src + (size_t)p0 * 6u;
+      uint32_t q[6];
+#pragma unroll
+      for (int k = 0; k < 6; k++) q[k] = ld_pair16(sp + 4 * k);
+      v = image_gray(hi_lo(q[0]), hi_hi(q[0]), hi_lo(q[1])) | image_gray(hi_hi(q[1]), hi_lo(q[2]), hi_hi(q[2])) << 8 |
+          image_gray(hi_lo(q[3]), hi_hi(q[3]), hi_lo(q[4])) << 16 | image_gray(hi_hi(q[4]), hi_lo(q[5]), hi_hi(q[5])) << 24;
+    }
+    *(uint32_t*)(d.dst + p0) = v;
+    return;
+  }
+  for (int j = 0; j < 4; j++) {  // the image's ends: pixel by pixel, the values' high bytes alone
+    const int p = p0 + j;
+    if (p < 0 || p >= N) continue;
+    const uint8_t* sp = d.src + (size_t)p * 2u * d.channels;
+    d.dst[p] = (uint8_t)(d.channels == 1u ? (uint32_t)sp[1] : image_gray(sp[1], sp[3], sp[5]));
+  }
+}
+
+void launch_frame16_emit(hipStream_t s, const Frame16Args& a) {
+  const uint32_t groups = (a.width * a.height + 3u + 3u) / 4u;  // destination dwords an image touches at the most
+  for (uint32_t first = 0; first < a.n_frames; first += 65535u)
+    launch_k(k_frame16_emit, dim3((groups + 255u) / 256u, std::min(a.n_frames - first, 65535u)), dim3(256), 0, s, a, first);
+}
+
 }  // namespace esvio

@@ -190,6 +190,29 @@ class AedatHeaderInfo(C.Structure):
     _fields_ = [("payload_offset", C.c_uint64), ("version", C.c_int32), ("complete", C.c_int32)]
 
 
+class AedatFrame(C.Structure):
+    """esvio_fe_aedat_frame"""
+    _fields_ = [("stamp_sec", C.c_uint32), ("stamp_nsec", C.c_uint32), ("ts_startframe", C.c_int32), ("ts_endframe", C.c_int32),
+                ("ts_startexposure", C.c_int32), ("ts_endexposure", C.c_int32), ("exposure_us", C.c_int64), ("length_x", C.c_int32),
+                ("length_y", C.c_int32), ("position_x", C.c_int32), ("position_y", C.c_int32), ("channels", C.c_int32),
+                ("color_filter", C.c_int32), ("roi", C.c_int32), ("valid", C.c_int32), ("slot", C.c_int32), ("ts_overflow", C.c_int32),
+                ("index", C.c_uint64)]
+
+
+AEDAT_FRAME_DTYPE = np.dtype([("stamp_sec", "<u4"), ("stamp_nsec", "<u4"), ("ts_startframe", "<i4"), ("ts_endframe", "<i4"),
+                              ("ts_startexposure", "<i4"), ("ts_endexposure", "<i4"), ("exposure_us", "<i8"), ("length_x", "<i4"),
+                              ("length_y", "<i4"), ("position_x", "<i4"), ("position_y", "<i4"), ("channels", "<i4"),
+                              ("color_filter", "<i4"), ("roi", "<i4"), ("valid", "<i4"), ("slot", "<i4"), ("ts_overflow", "<i4"),
+                              ("index", "<u8")])
+
+
+class AedatFrameInfo(C.Structure):
+    """esvio_fe_aedat_frame_info"""
+    _fields_ = [("frames", C.c_uint64), ("invalid", C.c_uint64), ("bad", C.c_uint64), ("frame_packets", C.c_uint64),
+                ("other_packets", C.c_uint64), ("first_sec", C.c_uint32), ("first_nsec", C.c_uint32), ("last_sec", C.c_uint32),
+                ("last_nsec", C.c_uint32)]
+
+
 class BagTopics(C.Structure):
     """esvio_fe_bag_topics"""
     _fields_ = [("left", C.c_char_p), ("right", C.c_char_p), ("imu", C.c_char_p)]
@@ -309,6 +332,7 @@ ABI_SYMBOLS = [
     "esvio_fe_convert_events", "esvio_fe_create", "esvio_fe_decode_raw", "esvio_fe_decode_reset",
     "esvio_fe_decode_triggers", "esvio_fe_raw_header", "esvio_fe_slice_events_at",
     "esvio_fe_aedat_header", "esvio_fe_decode_aedat", "esvio_fe_aedat_side", "esvio_fe_track_aedat", "esvio_fe_feed_push_aedat",
+    "esvio_fe_decode_aedat_frames", "esvio_fe_convert_frame16",
     "esvio_fe_bag_header", "esvio_fe_bag_set_topics", "esvio_fe_decode_bag", "esvio_fe_bag_side", "esvio_fe_feed_push_bag",
     "esvio_fe_bag_set_image_topics", "esvio_fe_decode_bag_images", "esvio_fe_convert_image", "esvio_fe_track_image_space",
     "esvio_fe_create_sae", "esvio_fe_create_sae_stereo", "esvio_fe_create_sae_stereo_mc", "esvio_fe_destroy",
@@ -349,6 +373,7 @@ TEST_SYMBOLS = [
     "esvio_fe_aedat_tile_events", "esvio_fe_ingest_kernel_count", "esvio_fe_aedat_walk_tap", "esvio_fe_aedat_walk_state_bytes",
     "esvio_fe_bag_tile_events", "esvio_fe_bag_walk_tap", "esvio_fe_bag_walk_state_bytes",
     "esvio_fe_bag_image_walk_tap", "esvio_fe_image_tile_pixels", "esvio_fe_event_image_kernel_stats",
+    "esvio_fe_aedat_frame_walk_tap", "esvio_fe_aedat_frame_kernel_stats", "esvio_fe_frame16_tile_pixels",
     "esvio_fe_kf_kernel_count", "esvio_fe_kf_kernel_name", "esvio_fe_kf_kernel_stats", "esvio_fe_kf_blur_tile",
     "esvio_fe_bow_kernel_count", "esvio_fe_bow_kernel_name", "esvio_fe_bow_kernel_stats", "esvio_fe_bow_limits", "esvio_fe_bow_scores",
 ]
@@ -572,6 +597,10 @@ def load_library(build_if_missing=True):
                                        C.POINTER(Tracks), C.POINTER(BatchInfo), C.POINTER(AedatInfo * 2)]
     L.esvio_fe_feed_push_aedat.argtypes = [vp, i, vp, sz, C.c_int64, u32, C.POINTER(FeedInfo)]
     L.esvio_fe_aedat_walk_tap.argtypes = [vp, sz, vp, sz, vp, sz, vp, sz, vp]
+    L.esvio_fe_decode_aedat_frames.argtypes = [vp, i, vp, sz, C.c_int64, u32, vp, sz, i, vp, sz, C.POINTER(AedatFrameInfo)]
+    L.esvio_fe_convert_frame16.argtypes = [vp, vp, i, u32, u32, C.c_int32, vp, i]
+    L.esvio_fe_aedat_frame_walk_tap.argtypes = [vp, sz, u32, u32, vp, sz, C.c_int64, u32, vp, sz, vp, sz, vp, sz, vp, vp, sz]
+    L.esvio_fe_aedat_frame_kernel_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.esvio_fe_bag_header.argtypes = [vp, sz, C.POINTER(BagHeaderInfo)]
     L.esvio_fe_bag_set_topics.argtypes = [vp, C.POINTER(BagTopics)]
     L.esvio_fe_decode_bag.argtypes = [vp, vp, sz, u32, C.POINTER(vp * 2), C.POINTER(sz * 2), i, vp, sz, C.POINTER(BagInfo)]
@@ -1185,6 +1214,64 @@ class FeatureTracker:
             e.info = info
             raise e
         return imu[:int(info.imu)], trig[:int(info.triggers)], info
+
+    def decode_aedat_frames(self, cam, data, t_offset_ns=0, flags=0, dst_cap=None, frames_cap=None, device=False):
+        """the AEDAT 3.1 frame call (esvio_fe_decode_aedat_frames; include/esvio_fe.h "AEDAT 3.1 frames" has the rule):
+        camera `cam`'s frame walker advanced by `data`, host memory, which may end anywhere.  Returns (images, table,
+        AedatFrameInfo): a numpy uint8 array [n, height, width] of gray images, or with device=True a DeviceImages (the
+        caller frees it; `.image(k)` is the pointer trackImage(..., device=True) takes); table a numpy AEDAT_FRAME_DTYPE
+        array whose `index` is the frame's image.  dst_cap, frames_cap None: what the chunk and the bytes that wait can
+        complete at the most.  A failed call raises FrontendError with `.info`."""
+        L = self._hd.L
+        W, H = self.cfg.width, self.cfg.height
+        buf = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data)
+        most = buf.nbytes // (2 * W * H) + 1  # (an emitted frame brings 2 * width * height pixel bytes at the least; one may have waited)
+        dst_cap = most if dst_cap is None else int(dst_cap)
+        frames_cap = most if frames_cap is None else int(frames_cap)
+        table, info = np.zeros(max(frames_cap, 1), AEDAT_FRAME_DTYPE), AedatFrameInfo()
+        if device:
+            d = C.c_void_p()
+            rc = L.esvio_fe_mem_alloc(DEVICE, W * H * max(dst_cap, 1), C.byref(d))
+            if rc:
+                raise FrontendError("esvio_fe_mem_alloc rc=%d" % rc)
+            out, dp = d, d
+        else:
+            out = np.zeros((max(dst_cap, 1), H, W), np.uint8)
+            dp = _p(out)
+        rc = L.esvio_fe_decode_aedat_frames(self._hd.h, int(cam), _p(buf) if buf.nbytes else None, buf.nbytes, int(t_offset_ns), int(flags),
+                                            dp, dst_cap, DEVICE if device else HOST, _p(table), frames_cap, C.byref(info))
+        if rc:
+            if device:
+                L.esvio_fe_mem_free(DEVICE, out)
+            e = FrontendError("rc=%d: %s" % (rc, L.esvio_fe_last_error(self._hd.h).decode()))
+            e.info = info
+            raise e
+        n = int(info.frames)
+        return (DeviceImages(out, n, W, H) if device else out[:n]), table[:n], info
+
+    def convert_frame16(self, src, height, width, channels, src_space=HOST, device=False):
+        """the driver's per-frame conversion alone (esvio_fe_convert_frame16): `src` a numpy uint16 array (host) or a
+        device pointer (src_space=DEVICE, 2-byte aligned) of height x width pixels of `channels` (1 or 3) values each.
+        Returns the gray image [height, width], or with device=True a DeviceImages of one image (the caller frees it)."""
+        L = self._hd.L
+        if isinstance(src, np.ndarray):
+            src = np.ascontiguousarray(src, "<u2")
+        sp = _p(src) if isinstance(src, np.ndarray) else C.c_void_p(int(src))
+        if device:
+            d = C.c_void_p()
+            rc = L.esvio_fe_mem_alloc(DEVICE, max(int(height) * int(width), 1), C.byref(d))
+            if rc:
+                raise FrontendError("esvio_fe_mem_alloc rc=%d" % rc)
+            out, dp = DeviceImages(d, 1, int(width), int(height)), d
+        else:
+            out = np.zeros((int(height), int(width)), np.uint8)
+            dp = _p(out)
+        rc = L.esvio_fe_convert_frame16(self._hd.h, sp, int(src_space), int(height), int(width), int(channels), dp, DEVICE if device else HOST)
+        if rc:
+            if device:
+                out.free()
+            raise FrontendError("rc=%d: %s" % (rc, L.esvio_fe_last_error(self._hd.h).decode()))
+        return out
 
     def track_aedat(self, left, right, t_offset_ns=0, flags=0, pub=True, params=None, measurements=None, copy=True):
         """one chunk of AEDAT 3.1 bytes per camera through esvio_fe_track_aedat (host memory).  Returns
@@ -2177,7 +2264,7 @@ class FilteredEvents:
 
 class DeviceImages:
     """n dense width x height gray images side by side in device memory of the library's runtime (what
-    esvio_fe_decode_bag_images and esvio_fe_convert_image write): `.image(k)` is the k-th one's address, which
+    esvio_fe_decode_bag_images, esvio_fe_decode_aedat_frames and the two conversions write): `.image(k)` is the k-th one's address, which
     trackImage(..., device=True) takes; `.download()` brings them to the host"""
 
     def __init__(self, ptr, n, width, height):
@@ -2402,6 +2489,31 @@ def bag_walk_tap(state, data, topics=(None, None, None), side=False, events_cap=
     c = tuple(int(v) for v in counts)
     return (st.tobytes(), tuple(pay[k][:13 * min(c[k], events_cap)].tobytes() for k in range(2)), msgs[:min(c[4], msgs_cap)].copy(),
             imu[:min(c[5], imu_cap)].copy(), c)
+
+
+def aedat_frame_walk_tap(state, data, size=(0, 0), t_offset_ns=0, flags=0, pix_cap=None, frames_cap=None):
+    """the AEDAT host walk in its frame mode alone (esvio_fe_aedat_frame_walk_tap; include/esvio_fe_test.h): `state` a
+    (walker bytes, waiting pixel bytes) pair (None: the fresh state), size = (width, height) the only size taken ((0, 0):
+    any).  Returns (state, pix, table, counts): the gathered pixel bytes, each frame from a 16-byte boundary, as bytes, a
+    numpy AEDAT_FRAME_DTYPE array (what there was room for), the eight counts.  A malformed stream, a refused frame or a
+    BAD stamp raises FrontendError whose text is the broken rule."""
+    L = load_library()
+    nst = L.esvio_fe_aedat_walk_state_bytes()
+    st = np.zeros(nst, np.uint8) if state is None else np.frombuffer(bytes(state[0]), np.uint8).copy()
+    waiting = b"" if state is None else bytes(state[1])
+    buf = np.frombuffer(bytes(data), np.uint8)
+    carry = np.zeros(len(waiting) + buf.nbytes + 1, np.uint8)
+    carry[:len(waiting)] = np.frombuffer(waiting, np.uint8)
+    pix_cap = len(waiting) + buf.nbytes + 16 * (buf.nbytes // 38 + 2) if pix_cap is None else int(pix_cap)
+    frames_cap = buf.nbytes // 38 + 1 if frames_cap is None else int(frames_cap)
+    pix, table, counts = np.zeros(max(pix_cap, 1), np.uint8), np.zeros(max(frames_cap, 1), AEDAT_FRAME_DTYPE), np.zeros(8, np.uint64)
+    why = C.create_string_buffer(256)
+    rc = L.esvio_fe_aedat_frame_walk_tap(_p(st), nst, int(size[0]), int(size[1]), _p(buf) if buf.nbytes else None, buf.nbytes, int(t_offset_ns),
+                                         int(flags), _p(carry), len(carry), _p(pix), pix_cap, _p(table), frames_cap, _p(counts), why, len(why))
+    if rc:
+        raise FrontendError("esvio_fe_aedat_frame_walk_tap rc=%d: %s" % (rc, why.value.decode()))
+    c = tuple(int(v) for v in counts)
+    return (st.tobytes(), carry[:c[6]].tobytes()), pix[:c[1]].tobytes() if c[1] <= pix_cap else b"", table[:min(c[0], frames_cap)], c
 
 
 def bag_image_walk_tap(state, data, topics=(None, None), size=(0, 0), pix_cap=None, imgs_cap=None):

@@ -299,6 +299,20 @@ class StereoImageTrackerNode:
                 i, j = i + 1, j + 1
         return pairs
 
+    @staticmethod
+    def merge_frame_tables(left, right):
+        """the two cameras' AEDAT frame tables (frontend.AEDAT_FRAME_DTYPE rows, each camera's in its stream order, what
+        decode_aedat_frames returns call by call) as one table with a `cam` column in front, the left rows first: what
+        pair_images takes, which reads each camera's rows as a queue of its own"""
+        rows = [(0, m) for m in left] + [(1, m) for m in right]
+        base = left.dtype if len(left) else right.dtype
+        out = np.zeros(len(rows), np.dtype([("cam", "<i4")] + [(n, base.fields[n][0]) for n in base.names]))
+        for k, (cam, m) in enumerate(rows):
+            out["cam"][k] = cam
+            for n in base.names:
+                out[n][k] = m[n]
+        return out
+
     def handle(self, img_left, img_right, msg_timestamp, device=False):
         self.restart_flag = False
         if self.first_image_flag:  # :58-64

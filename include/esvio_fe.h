@@ -868,8 +868,10 @@ int esvio_fe_raw_header(const void* bytes, size_t n, esvio_fe_raw_header_info* o
  * pinned scratch with a table of the runs of equal eventTSOverflow, and the device decodes that array one record per
  * lane (KERNELS.md "AEDAT 3.1").  A stream that lies in device memory would have to come back first.
  *
- * Out of scope: AEDAT 2.0 and AEDAT 4, frame packets' pixels, IMU samples or triggers inside the feed (the side call
- * beside it is the way). */
+ * Frame packets (type 2) are decoded by a third call with a walker of its own: "AEDAT 3.1 frames" below.  To the two
+ * calls of this section they stay other_packets.
+ *
+ * Out of scope: AEDAT 2.0 and AEDAT 4, IMU samples or triggers inside the feed (the side call beside it is the way). */
 #define ESVIO_FE_AEDAT_KEEP_INVALID 1u
 typedef struct esvio_fe_aedat_info {
   uint64_t events, invalid, bad;             /* emitted (a too small dst_cap: the number needed); dropped; BAD */
@@ -930,6 +932,110 @@ int esvio_fe_track_aedat(esvio_fe_handle h, const void* left, size_t left_bytes,
                          int64_t t_offset_ns, uint32_t flags, int pub_this_frame, const esvio_fe_filter_params* filter,
                          const esvio_fe_motion* motion, esvio_fe_tracks* out, esvio_fe_batch_info* info,
                          esvio_fe_aedat_info aedat[2]);
+
+/* ---- AEDAT 3.1 frames: the DAVIS frame packets of the same stream -> trackImage's 8-bit gray, on the device ---- */
+/* Five of the shipped parameter sets are DAVIS rigs, and in ESVIO mode the second feature stream is that sensor's own APS
+ * frames: type-2 packets between the polarity, special and IMU6 packets of the stream above.  WHAT IS CITED: the
+ * per-frame arithmetic is the driver's FRAME_EVENT branch, davis_ros_driver/src/driver.cpp:778-823 — the channel number
+ * gives the encoding, 1 -> "mono8", 3 -> "rgb8", and nothing else gets one (:788-804); the pixel array is read linearly
+ * and each 16-bit value becomes value >> 8 (:807-814); the stamp is reset_time_ + Duration().fromNSec(ts64 * 1000)
+ * (:817-818); the exposure length is published beside it (:823).  An "rgb8" frame then goes through getImageFromMsg's
+ * cv::COLOR_RGB2GRAY (feature_tracker/src/stereo_image_tracker_node.cpp:296-301), which is exactly the 15-bit rule that
+ * "rosbag images" below states for class 3, on the byte triple (R, G, B) of value >> 8.  WHAT IS RESTATED FROM RECALL AND
+ * UNPINNED, as for the other AEDAT types: libcaer's accessors are not in the reference's tree, so THE FRAME PACKET AND
+ * FRAME EVENT LAYOUTS BELOW ARE RECALLED, not claimed to be bit-equal to libcaer, and THIS TEXT IS THE SPECIFICATION;
+ * tests/aedat_frame_ref.py is its sequential reading, and the library equals it exactly.
+ *
+ * Packet.  Type 2, FRAME, with eventTSOffset 12.  The header's common checks are those of the section above.  A type-2
+ * header is also MALFORMED when eventSize < 36, eventSize - 36 is odd, or eventTSOffset != 12.  Packets of types 0 / 1 / 3
+ * get the table's checks of the section above and are skipped whole; every other type is skipped whole and counted in
+ * other_packets.  A packet is counted (frame_packets, other_packets) by the call in which its header's last byte arrives.
+ *
+ * Frame event: eventSize bytes, little-endian.  A 36-byte head
+ *   uint32 info; int32 ts_startframe, ts_endframe, ts_startexposure, ts_endexposure, lengthX, lengthY, positionX, positionY
+ * and behind it uint16 pixels, row-major with the channels interleaved, up to eventSize - 36 bytes.  info: bit 0 valid,
+ * bits 1-3 the channel number, bits 4-7 the colour filter, bits 8-14 the ROI id.  An emitted event is MALFORMED when
+ * lengthX < 1, lengthY < 1, or lengthX * lengthY * channels * 2 > eventSize - 36, decided in exact integers (lengthX *
+ * lengthY is below 2^62; an implementation may compare it with (eventSize - 36) / (2 * channels) rounded down, and a
+ * channel number of 0 passes this check).  Then, REFUSED BY NAME like the bag images, the message naming the value: a
+ * channel number other than 1 or 3 (the driver gives that frame no encoding), and a lengthX x lengthY that is not the
+ * handle's width x height (no cv::resize, as stated there).  positionX / positionY, the colour filter and the ROI id are
+ * recorded and otherwise ignored, as the driver ignores them.  Malformed and refused fail the call with ESVIO_FE_EINVAL
+ * before any device work, the state as it was; they are decided, in this order, in the call that brings the head's last
+ * byte.
+ *
+ * Pixels.  The frame's lengthX * lengthY * channels values are the first that many uint16 behind the head; bytes behind
+ * them in the event are never read.  One channel: gray = value >> 8.  Three: (R, G, B) = the pixel's three values >> 8,
+ * gray = (R * 9798 + G * 19235 + B * 3735 + (1 << 14)) >> 15.
+ *
+ * Stamp.  The frame's ts is the mid-exposure stamp, ts_startexposure + (ts_endexposure - ts_startexposure) / 2, computed
+ * in 64-bit integers with the division truncating toward zero (caerFrameEventGetTimestamp, recalled).  ts64 and the
+ * stamp then follow the polarity events' rule with the packet's eventTSOverflow, BAD included: ticks_ns = ts64 * 1000 +
+ * t_offset_ns, BAD when ts < 0, eventTSOverflow < 0, ticks_ns < 0 or sec >= 2^32.  The stamp is taken, and BAD decided
+ * (behind malformed and refused), with the t_offset_ns of the call that brings the head's last byte.  A BAD frame fails
+ * the call: info->bad is exact, nothing is stored, the state is as it was.  exposure_us = ts_endexposure -
+ * ts_startexposure in 64 bits.
+ *
+ * Validity, as for events: by default an event with valid == 0 is dropped and counted in `invalid`; it is not examined
+ * further and is never BAD, malformed or refused.  With ESVIO_FE_AEDAT_KEEP_INVALID every one of the eventNumber events
+ * is emitted.  The driver looks only at event 0 of a packet (caerFrameEventPacketGetEvent(frame, 0), :781) and never at
+ * the valid bit; this call emits EVERY event in stream order and records each one's position within its packet in
+ * `slot`.  THE ROWS WITH slot == 0 UNDER ESVIO_FE_AEDAT_KEEP_INVALID ARE EXACTLY THE DRIVER'S FRAMES.
+ *
+ * State.  Per handle and camera there is a THIRD walker state for esvio_fe_decode_aedat_frames, so the same chunks may go
+ * through the event call, the side call and the frame call in any order.  A chunk may end anywhere, inside the 36-byte
+ * head or inside the pixels; a frame is emitted by the call that brings its last PIXEL byte.  The pixel bytes of a cut
+ * frame wait in a carry buffer the handle owns; a failed call leaves state and carry as they were.  esvio_fe_decode_reset
+ * and esvio_fe_reset clear the frame walkers too.  In ESVIO mode the frame call is made on the image tracker's handle,
+ * whose width and height are the sensor's.
+ *
+ * Source.  Host memory, as above.  The counting walk checks everything; the gathering walk copies each emitted frame's
+ * lengthX * lengthY * channels * 2 pixel bytes, and nothing else, into pinned scratch, each frame from a 16-byte boundary;
+ * one copy brings them and the descriptor table to the device and ONE launch of k_frame16_emit (KERNELS.md "AEDAT
+ * frames") writes all frames of the call.
+ *
+ * Out of scope: the driver's auto-exposure (computeNewExposure), frames inside the feed, the node harnesses, and sizes
+ * other than the handle's. */
+typedef struct esvio_fe_aedat_frame { /* one emitted frame event */
+  uint32_t stamp_sec, stamp_nsec;           /* the mid-exposure stamp: what the node pairs left and right by */
+  int32_t ts_startframe, ts_endframe, ts_startexposure, ts_endexposure; /* the head's four raw stamps */
+  int64_t exposure_us;                      /* ts_endexposure - ts_startexposure */
+  int32_t length_x, length_y, position_x, position_y;
+  int32_t channels, color_filter, roi;      /* info bits 1-3, 4-7, 8-14 */
+  int32_t valid, slot;                      /* info bit 0; the event's position within its packet */
+  int32_t ts_overflow;                      /* its packet's eventTSOverflow */
+  uint64_t index;                           /* its image in dst, counted per call */
+} esvio_fe_aedat_frame;
+typedef struct esvio_fe_aedat_frame_info {
+  uint64_t frames, invalid, bad;            /* emitted (too small a capacity: the number needed); dropped; BAD */
+  uint64_t frame_packets, other_packets;    /* headers completed by this call: type 2; none of 0, 1, 2, 3 */
+  uint32_t first_sec, first_nsec, last_sec, last_nsec; /* the first / last emitted frame's stamp; 0 if none */
+} esvio_fe_aedat_frame_info;
+/* the frame call: camera `cam`'s frame walker advanced by the n_bytes at `bytes`; the k-th emitted frame of the call
+ * becomes the dense width * height gray image at dst + k * width * height (room for dst_cap IMAGES; dst_space:
+ * ESVIO_FE_DEVICE, any alignment, or ESVIO_FE_HOST), and an esvio_fe_aedat_frame per emitted frame, in stream order, goes
+ * to the HOST array frames (room for frames_cap).  More frames than dst_cap or frames_cap: ESVIO_FE_EINVAL, info->frames
+ * holds the exact number needed, nothing is stored, the state is as it was.  n_bytes == 0 succeeds and touches nothing;
+ * n_bytes <= 2^28.  info is optional.  Orders itself on the main stream, waits for its own result and touches nothing of
+ * the tracker.  Its scratch — the pixel bytes pinned and on the device, the images behind a host dst — grows on first use
+ * and with esvio_fe_reserve (one rgb frame of the handle's size) for a handle that has decoded frames before: a second
+ * call of a given size allocates nothing.  ESVIO_FE_EINVAL with a message, before any device work: cam outside 0..1,
+ * unknown bits in flags, null bytes with n_bytes > 0, a null dst with dst_cap > 0, null frames with frames_cap > 0, a bad
+ * dst_space, |t_offset_ns| > 2^62, n_bytes > 2^28, a malformed header or event, a refused channel number or size, a BAD
+ * stamp.
+ * Tracking frame pairs: merge the two cameras' tables (esvio_amd.node.StereoImageTrackerNode.merge_frame_tables), pair
+ * them as the node does (pair_images) and hand dst + index * width * height to
+ * esvio_fe_track_image_space(..., ESVIO_FE_DEVICE, ...). */
+int esvio_fe_decode_aedat_frames(esvio_fe_handle h, int cam, const void* bytes, size_t n_bytes, int64_t t_offset_ns,
+                                 uint32_t flags, uint8_t* dst, size_t dst_cap, int dst_space, esvio_fe_aedat_frame* frames,
+                                 size_t frames_cap, esvio_fe_aedat_frame_info* info);
+/* the conversion alone, for a host that holds caerFrameEventGetPixelArrayUnsafe's array of a live device: height x width
+ * pixels (each 1 .. 8192, whatever the handle's size) of `channels` (1 or 3) uint16 values each, dense and row-major at
+ * src (src_space ESVIO_FE_HOST: copied to the device first; ESVIO_FE_DEVICE: read in place, at any 2-byte alignment), to
+ * the dense gray image dst (dst_space likewise; any alignment) by the pixel rule above.  Argument errors are
+ * ESVIO_FE_EINVAL before any device work. */
+int esvio_fe_convert_frame16(esvio_fe_handle h, const uint16_t* src, int src_space, uint32_t height, uint32_t width,
+                             int32_t channels, uint8_t* dst, int dst_space);
 
 /* ---- rosbag v2.0 recordings: dvs_msgs/EventArray events of both cameras, sensor_msgs/Imu samples ---- */
 /* The reference is run on ROS bags and nothing else: its README ("3. Run on Dataset") says `rosbag play`, and the HKU

@@ -209,6 +209,23 @@ int esvio_fe_ingest_kernel_count(void);
 int esvio_fe_aedat_walk_tap(void* state, size_t state_bytes, const void* bytes, size_t n_bytes, uint32_t* runs, size_t runs_cap,
                             uint8_t* payload, size_t events_cap, uint64_t counts[4]);
 int esvio_fe_aedat_walk_state_bytes(void);
+/* The AEDAT host walk in its frame mode alone ("AEDAT 3.1 frames"), no handle and no device: a frame walker's state in
+ * and out (as above), the only size taken (width 0: any), the n_bytes of a chunk in.  `carry` holds the pixel bytes of
+ * the open frame that earlier calls left waiting (the state says how many) and takes, on success, those that wait behind
+ * this call (room for carry_cap; it needs the waiting bytes + n_bytes at the most).  Out come the emitted frames' pixel
+ * bytes, each frame from a 16-byte boundary of pix (nothing is stored unless all fit pix_cap bytes), the frame table (at
+ * most frames_cap rows) and counts = {frames, pixel bytes with their padding, invalid, BAD, frame packets, other packets,
+ * bytes waiting behind the call, 0}.  pix and frames may be null.  A malformed header or event, a refused frame or a BAD
+ * stamp: ESVIO_FE_EINVAL, state and carry as they were, the broken rule as text in `why` (room for why_cap; optional). */
+int esvio_fe_aedat_frame_walk_tap(void* state, size_t state_bytes, uint32_t width, uint32_t height, const void* bytes,
+                                  size_t n_bytes, int64_t t_offset_ns, uint32_t flags, uint8_t* carry, size_t carry_cap,
+                                  uint8_t* pix, size_t pix_cap, esvio_fe_aedat_frame* frames, size_t frames_cap,
+                                  uint64_t counts[8], char* why, size_t why_cap);
+/* k_frame16_emit (esvio_fe_decode_aedat_frames, esvio_fe_convert_frame16), booked in a timer slot of its own behind
+ * every other table — the stage and ingest tables, whose ends tests pin, stay as they are; as esvio_fe_get_kernel_stats
+ * otherwise.  esvio_fe_frame16_tile_pixels: pixels per workgroup of the kernel. */
+int esvio_fe_aedat_frame_kernel_stats(esvio_fe_handle h, double* total_ms, uint64_t* launches, uint64_t* alg_bytes);
+int esvio_fe_frame16_tile_pixels(void);
 /* the bag stage: events per tile of k_bag_emit, whose timer id is appended to the ingest range above */
 int esvio_fe_bag_tile_events(void);
 /* The bag host walk alone (esvio_amd/csrc/fe_bag.h), no handle and no device: a walker's state in and out (state_bytes ==
