@@ -4666,3 +4666,6 @@ int esvio_fe_aedat_frame_walk_tap(void* state, size_t state_bytes, uint32_t widt
 
 // ---- loop detection: DBoW2 words, database, L1 query (the rules: include/esvio_fe.h "loop detection")
 #include "fe_bow.h"
+
+// ---- creating a vocabulary: k-means++, the tree, the word weights (the rule: include/esvio_fe.h "C")
+#include "fe_voc.h"

@@ -110,12 +110,20 @@ struct PhaseClock {
 // ... and behind them the keyframe stage's three (esvio_fe_kf_kernel_count / _name / _stats, include/esvio_fe_test.h)
 // ... and behind those loop detection's four (esvio_fe_bow_kernel_count / _name / _stats)
 // ... and behind those the AEDAT frames' one, k_frame16_emit (esvio_fe_aedat_frame_kernel_stats)
+// ... and behind that vocabulary creation's (esvio_fe_bow_create_kernel_count / _name / _stats)
 enum { K_EVIMG_MARK = K_INGEST_COUNT, K_EVIMG_EMIT, K_KF_BLUR, K_KF_BRIEF, K_KF_MATCH, K_BOW_WALK, K_BOW_VECTOR, K_BOW_SCORE,
-       K_BOW_SELECT, K_FRAME16_EMIT, K_ALL_COUNT };
+       K_BOW_SELECT, K_FRAME16_EMIT, K_VOC_FIRST, K_VOC_MINDIST, K_VOC_SCAN_REDUCE, K_VOC_SCAN_TOP, K_VOC_SCAN_DOWN, K_VOC_DRAW,
+       K_VOC_PICK, K_VOC_ASSIGN, K_VOC_COUNT_BIG, K_VOC_MEAN_BIG, K_VOC_MEAN_SMALL, K_VOC_CHILD_COUNT, K_VOC_REGROUP_KEYS,
+       K_VOC_DOC_COUNT, K_ALL_COUNT };
 constexpr int kKfKernels = K_BOW_WALK - K_KF_BLUR;
 const char* const kKfKernelNames[kKfKernels] = {"k_kf_blur", "k_kf_brief", "k_kf_match"};
 constexpr int kBowKernels = K_FRAME16_EMIT - K_BOW_WALK;
 const char* const kBowKernelNames[kBowKernels] = {"k_bow_walk", "k_bow_vector", "k_bow_score", "k_bow_select"};
+constexpr int kVocKernels = K_ALL_COUNT - K_VOC_FIRST;
+const char* const kVocKernelNames[kVocKernels] = {
+    "k_voc_first", "k_voc_mindist", "k_voc_scan_reduce", "k_voc_scan_top", "k_voc_scan_down", "k_voc_draw", "k_voc_pick",
+    "k_voc_assign", "k_voc_count_big", "k_voc_mean_big", "k_voc_mean_small", "k_voc_child_count", "k_voc_regroup_keys",
+    "k_voc_doc_count"};
 
 struct KStat {
   double ms = 0;
@@ -751,6 +759,23 @@ struct esvio_fe_ctx {
     DevBuf<uint8_t> present;
     DevBuf<int32_t> res_id;
   } bow;
+
+  // ---- esvio_fe_bow_create_vocabulary (include/esvio_fe.h "C, creating a vocabulary", fe_voc.h): `image` is the file
+  // image of the last successful create, kept by esvio_fe_reset and read by esvio_fe_bow_get_created; everything else is
+  // scratch of a create, apart from loop detection's (the vocabulary that is set and the database are not touched):
+  // fe_kernels.h VocArgs names the per-level arrays, tree_* is the finished tree in loop detection's layout for the
+  // document counts' walk.
+  struct Voc {
+    std::vector<uint8_t> image;
+    DevBuf<uint32_t> desc, keys[2], vals[2], sort, min_dist, assign, seg_off, seg_slot, km_start, km_end, big_km, ncent, draws,
+        stopped, changed, centres, pick, counts, slot_size, slot_map, ni;
+    DevBuf<int32_t> seg_km, km_big, err, word, tree_word;
+    DevBuf<uint64_t> run, tile_sum, km_key;
+    DevBuf<double> cut_d, weight, tree_weight;
+    DevBuf<int64_t> doc_off;
+    DevBuf<uint4> tree_desc;
+    DevBuf<uint2> tree_kids;
+  } voc;
 };
 
 namespace esvio {

@@ -1004,5 +1004,101 @@ void launch_bow_score(hipStream_t s, const uint32_t* q_word, const double* q_val
 void launch_bow_select(hipStream_t s, const double* score, const uint8_t* present, uint32_t n_entries, int max_results,
                        int32_t* out_id, double* out_score, double* out_raw, uint32_t* out_n);
 
+// ---- vocabulary creation: k-means++ seeding, k-means passes, regrouping, document counts (esvio_fe_bow_create_*) ----
+// include/esvio_fe.h "C, creating a vocabulary" holds the rule: Hamming distances, integer sums and counts, and in C5 one
+// double division and one product per draw (__ddiv_rn / __dmul_rn, nothing to contract).  The tree grows breadth first,
+// one level's nodes together (fe_voc.h drives it).  A level's features are `na` POSITIONS: perm[i] the feature at position
+// i, segof[i] its segment (= a node of the level that is split), ascending, a segment's positions in feature order.  A
+// segment with more than k features is a K-MEANS NODE x (seg_km[s] = x, else -1) and owns ncent[x] <= k centres of 8
+// words at centres[(x k + c) 8]; one with at most k features has one cluster per feature and needs no centre.  A k-means
+// node with at least kVocBigNode features is BIG (km_big[x] = its index among them, else -1).
+//   k_voc_first        C2's first centre: one lane per k-means node, draw 0, RandomInt.
+//   k_voc_mindist      one lane per position: min_dist against the node's newest centre (first != 0: against the first,
+//                      stored as it is); a min_dist of 0 stays (C2's `if(*dit > 0)`).
+//   k_voc_scan_reduce, k_voc_scan_top, k_voc_scan_down: the inclusive u64 running sums run[] of min_dist over ALL
+//                      positions, kVocScanTile per workgroup — a node's running sum at i is run[i] - run[start - 1], so no
+//                      scan knows of segments.  Three launches, no workgroup waits for another.
+//   k_voc_draw         one lane per k-means node: dist_sum = run[end - 1] - run[start - 1]; 0 stops the node's seeding
+//                      (stopped[x] = 1, cut_d[x] = -1), else cut_d[x] by C5, drawn again while it is 0.0.
+//   k_voc_pick         one lane per segment: the first position whose (double)(running sum) >= cut_d by bisection (run[]
+//                      ascends), the last one if none; with take != 0 the feature there becomes the node's next centre.
+//   k_voc_assign       one lane per position: the least distance's lowest cluster; centres from LDS where the workgroup's
+//                      256 positions lie in one node, from memory otherwise.  changed[x] = 1 where a lane's cluster
+//                      differs from the one it held.  m <= k segments: the cluster is the position's rank in its segment.
+//   k_voc_count_big    C3's counts of the big nodes: 8 lanes per feature (one word each), kVocScanTile positions per
+//                      workgroup, LDS counters [k][257] (256 bits and the group's size) flushed by integer atomics.  A big
+//                      node holds more positions than a tile, so only a tile's first and last segment can be big: the
+//                      tile counts its part of each, one after the other.
+//   k_voc_mean_big     one lane per (big node, cluster, word): bit set iff its count > size / 2.
+//   k_voc_mean_small   one workgroup per k-means node that is not big: counts in LDS, then the centres.
+//   k_voc_child_count  slot_size[seg_slot[s] + cluster] += 1 per position: the sizes of the level's children (through
+//                      <= 32 LDS counters where the workgroup's 256 positions lie in one k-means node).
+//   k_voc_regroup_keys the stable sort's input for the next level: key = slot_map[child slot] (the child's segment on the
+//                      next level, or the `dead` key of a child that is not split), value = the feature; digit histograms.
+//   k_voc_doc_count    behind k_bow_walk and the stable sort by word: Ni[word] += 1 at every position where the word or
+//                      the document (bisection in doc_offsets) differs from the position before.
+constexpr uint32_t kVocBigNode = 4096;
+constexpr int kVocScanTile = 2048;
+struct VocArgs {
+  const uint32_t* desc;     // [n][8], 16-byte aligned
+  uint32_t na, n_seg, n_km, n_big;
+  int k;
+  const uint32_t* perm;     // [na]
+  const uint32_t* segof;    // [na]
+  const uint32_t* seg_off;  // [n_seg + 1]
+  const int32_t* seg_km;    // [n_seg]
+  const uint32_t* seg_slot; // [n_seg] the segment's first child slot
+  const uint32_t* km_start; // [n_km] first position, and one behind the last
+  const uint32_t* km_end;
+  const uint64_t* km_key;   // [n_km] C5's key of the node
+  const int32_t* km_big;    // [n_km]
+  const uint32_t* big_km;   // [n_big]
+  uint32_t* ncent;          // [n_km] each: centres so far, draws taken, seeding stopped short, assignment changed
+  uint32_t* draws;
+  uint32_t* stopped;
+  uint32_t* changed;
+  uint32_t* centres;        // [n_km][k][8]
+  double* cut_d;            // [n_km]
+  uint32_t* pick;           // [n_km]
+  uint32_t* min_dist;       // [na]
+  uint64_t* run;            // [na]
+  uint64_t* tile_sum;       // [tiles of na]
+  uint32_t* assign;         // [na]
+  uint32_t* counts;         // [n_big][k][257]
+  uint32_t* slot_size;      // [slots]
+};
+// splitmix64 (C5)
+inline __host__ __device__ uint64_t voc_mix(uint64_t z) {
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+inline __host__ __device__ uint32_t voc_draw(uint64_t key, uint32_t j) { return (uint32_t)(voc_mix(key ^ ((uint64_t)(j + 1u) << 32)) >> 33); }
+inline uint32_t voc_tiles(uint32_t n) { return (n + kVocScanTile - 1) / kVocScanTile; }
+void launch_voc_first(hipStream_t s, const VocArgs& a);
+void launch_voc_mindist(hipStream_t s, const VocArgs& a, int first);
+// run[i] = min_dist[0] + ... + min_dist[i] for i < n; tile_sum: voc_tiles(n) words.  n >= 1
+void launch_voc_scan_reduce(hipStream_t s, const uint32_t* min_dist, uint32_t n, uint64_t* tile_sum);
+void launch_voc_scan_top(hipStream_t s, uint64_t* tile_sum, uint32_t tiles);
+void launch_voc_scan_down(hipStream_t s, const uint32_t* min_dist, uint32_t n, const uint64_t* tile_sum, uint64_t* run);
+void launch_voc_draw(hipStream_t s, const VocArgs& a);
+// start / end / cut_d / pick [n_seg]; a cut_d that is not >= 0 or an empty segment gives pick 0xffffffff; take: a's
+// centres grow by the picked feature (n_seg = a.n_km then)
+void launch_voc_pick(hipStream_t s, const uint64_t* run, const uint32_t* start, const uint32_t* end, const double* cut_d,
+                     uint32_t n_seg, uint32_t* pick, const VocArgs& a, int take);
+void launch_voc_assign(hipStream_t s, const VocArgs& a, int first);
+void launch_voc_count_big(hipStream_t s, const VocArgs& a);
+void launch_voc_mean_big(hipStream_t s, const VocArgs& a);
+void launch_voc_mean_small(hipStream_t s, const VocArgs& a);
+void launch_voc_child_count(hipStream_t s, const VocArgs& a);
+// keys / vals [a.na]; ghist: the sort scratch's, cleared
+void launch_voc_regroup_keys(hipStream_t s, const VocArgs& a, const uint32_t* slot_map, int passes, uint32_t* keys,
+                             uint32_t* vals, uint32_t* ghist);
+// keys (words) sorted stably, vals the features; doc_off [n_docs + 1] with doc_off[0] = 0 and doc_off[n_docs] > every
+// feature; ni [n_words] cleared
+void launch_voc_doc_count(hipStream_t s, const uint32_t* keys, const uint32_t* vals, uint32_t n, const int64_t* doc_off,
+                          uint32_t n_docs, uint32_t n_words, uint32_t* ni);
+
 
 }  // namespace esvio

@@ -6365,4 +6365,367 @@ void launch_frame16_emit(hipStream_t s, const Frame16Args& a) {
     launch_k(k_frame16_emit, dim3((groups + 255u) / 256u, std::min(a.n_frames - first, 65535u)), dim3(256), 0, s, a, first);
 }
 
+// ============================================================================ vocabulary creation (esvio_fe_bow_create_*)
+// TemplatedVocabulary::create (pose_graph/src/ThirdParty/DBoW/TemplatedVocabulary.h:639-995) a level at a time;
+// fe_kernels.h has the layout of a level and what each kernel does, include/esvio_fe.h "C" the rule.  (Appended behind the
+// AEDAT frames' kernel for the reason given there: no existing kernel's place in the code object moves.)
+__device__ __forceinline__ uint32_t voc_dist(const uint4 a, const uint4 b, const uint4 t0, const uint4 t1) {  // FBrief.cpp:53-57
+  return __popc(a.x ^ t0.x) + __popc(a.y ^ t0.y) + __popc(a.z ^ t0.z) + __popc(a.w ^ t0.w) + __popc(b.x ^ t1.x) +
+         __popc(b.y ^ t1.y) + __popc(b.z ^ t1.z) + __popc(b.w ^ t1.w);
+}
+__device__ __forceinline__ void voc_take(const VocArgs& a, uint32_t x, uint32_t nc, uint32_t pos) {
+  const uint4* f = (const uint4*)a.desc + (size_t)a.perm[pos] * 2;
+  uint4* c = (uint4*)a.centres + ((size_t)x * a.k + nc) * 2;
+  c[0] = f[0], c[1] = f[1];
+}
+
+__global__ __launch_bounds__(256) void k_voc_first(VocArgs a) {
+  const uint32_t x = blockIdx.x * 256u + threadIdx.x;
+  if (x >= a.n_km) return;
+  const uint32_t b = a.km_start[x], m = a.km_end[x] - b;
+  // RandomInt(0, m - 1), DUtils/Random.cpp:47-50
+  uint32_t i = (uint32_t)(int)__dmul_rn(__ddiv_rn((double)voc_draw(a.km_key[x], 0u), 2147483648.0), (double)m);
+  i = min(i, m - 1u);  // (r < 2^31: never taken)
+  voc_take(a, x, 0u, b + i);
+  a.ncent[x] = 1u, a.draws[x] = 1u, a.stopped[x] = 0u, a.changed[x] = 0u;
+}
+
+__global__ __launch_bounds__(256) void k_voc_mindist(VocArgs a, int first) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= a.na) return;
+  const int32_t x = a.seg_km[a.segof[i]];
+  if (x < 0) {
+    if (first) a.min_dist[i] = 0u;
+    return;
+  }
+  const uint32_t md = first ? 0xffffffffu : a.min_dist[i];
+  if (md == 0u) return;  // TemplatedVocabulary.h:874
+  const uint4* f = (const uint4*)a.desc + (size_t)a.perm[i] * 2;
+  const uint4* c = (const uint4*)a.centres + ((size_t)x * a.k + (a.ncent[x] - 1u)) * 2;
+  const uint32_t d = voc_dist(f[0], f[1], c[0], c[1]);
+  if (d < md) a.min_dist[i] = d;
+}
+
+// exclusive sums over the workgroup's 256 lanes; *total (LDS) the sum of all
+__device__ __forceinline__ uint64_t voc_block_scan(uint64_t v, uint64_t* wave_sum) {
+  uint64_t inc = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint64_t t = __shfl_up((unsigned long long)inc, o);
+    if (lane_id() >= o) inc += t;
+  }
+  if (lane_id() == 63) wave_sum[threadIdx.x >> 6] = inc;
+  __syncthreads();
+  uint64_t base = 0;
+  for (int w = 0; w < (int)(threadIdx.x >> 6); w++) base += wave_sum[w];
+  return base + inc - v;
+}
+
+constexpr int kVocPerLane = kVocScanTile / 256;
+__global__ __launch_bounds__(256) void k_voc_scan_reduce(const uint32_t* __restrict__ min_dist, uint32_t n,
+                                                         uint64_t* __restrict__ tile_sum) {
+  __shared__ uint64_t wave_sum[4];
+  const uint32_t i0 = blockIdx.x * (uint32_t)kVocScanTile + threadIdx.x * (uint32_t)kVocPerLane;
+  uint64_t v = 0;
+  for (int j = 0; j < kVocPerLane; j++)
+    if (i0 + j < n) v += min_dist[i0 + j];
+  const uint64_t ex = voc_block_scan(v, wave_sum);
+  if (threadIdx.x == 255) tile_sum[blockIdx.x] = ex + v;
+}
+// tile_sum -> the sum of the tiles in front of each, in place; one workgroup
+__global__ __launch_bounds__(256) void k_voc_scan_top(uint64_t* __restrict__ tile_sum, uint32_t tiles) {
+  __shared__ uint64_t wave_sum[4];
+  const uint32_t per = (tiles + 255u) / 256u, t0 = threadIdx.x * per;
+  uint64_t v = 0;
+  for (uint32_t j = t0; j < min(t0 + per, tiles); j++) v += tile_sum[j];
+  uint64_t run = voc_block_scan(v, wave_sum);
+  for (uint32_t j = t0; j < min(t0 + per, tiles); j++) {
+    const uint64_t t = tile_sum[j];
+    tile_sum[j] = run;
+    run += t;
+  }
+}
+__global__ __launch_bounds__(256) void k_voc_scan_down(const uint32_t* __restrict__ min_dist, uint32_t n,
+                                                       const uint64_t* __restrict__ tile_sum, uint64_t* __restrict__ run) {
+  __shared__ uint64_t wave_sum[4];
+  const uint32_t i0 = blockIdx.x * (uint32_t)kVocScanTile + threadIdx.x * (uint32_t)kVocPerLane;
+  uint32_t d[kVocPerLane];
+  uint64_t v = 0;
+  for (int j = 0; j < kVocPerLane; j++) {
+    d[j] = i0 + j < n ? min_dist[i0 + j] : 0u;
+    v += d[j];
+  }
+  uint64_t r = voc_block_scan(v, wave_sum) + tile_sum[blockIdx.x];
+  for (int j = 0; j < kVocPerLane; j++) {
+    r += d[j];
+    if (i0 + j < n) run[i0 + j] = r;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_voc_draw(VocArgs a) {
+  const uint32_t x = blockIdx.x * 256u + threadIdx.x;
+  if (x >= a.n_km) return;
+  a.cut_d[x] = -1.0;
+  if (a.stopped[x]) return;
+  const uint32_t b = a.km_start[x], e = a.km_end[x];
+  const uint64_t sum = a.run[e - 1u] - (b ? a.run[b - 1u] : 0ull);
+  if (!sum) {  // TemplatedVocabulary.h:907-908
+    a.stopped[x] = 1u;
+    return;
+  }
+  const uint64_t key = a.km_key[x];
+  uint32_t j = a.draws[x];
+  double cut;
+  do  // RandomValue<double>(0, dist_sum), DUtils/Random.h:56-68; 0.0 only for r = 0
+    cut = __dmul_rn(__ddiv_rn((double)voc_draw(key, j++), 2147483647.0), (double)sum);
+  while (cut == 0.0);
+  a.draws[x] = j;
+  a.cut_d[x] = cut;
+}
+
+__global__ __launch_bounds__(256) void k_voc_pick(const uint64_t* __restrict__ run, const uint32_t* __restrict__ start,
+                                                  const uint32_t* __restrict__ end, const double* __restrict__ cut_d,
+                                                  uint32_t n_seg, uint32_t* __restrict__ pick, VocArgs a, int take) {
+  const uint32_t x = blockIdx.x * 256u + threadIdx.x;
+  if (x >= n_seg) return;
+  const double cut = cut_d[x];
+  const uint32_t b = start[x], e = end[x];
+  if (!(cut >= 0.0) || e <= b) {
+    pick[x] = 0xffffffffu;
+    return;
+  }
+  const uint64_t base = b ? run[b - 1u] : 0ull;
+  uint32_t lo = b, hi = e;  // the first position of [b, e) with (double)(run - base) >= cut; e if none
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo) / 2u;
+    if ((double)(run[mid] - base) >= cut) hi = mid;
+    else lo = mid + 1u;
+  }
+  const uint32_t p = lo < e ? lo : e - 1u;  // TemplatedVocabulary.h:899-902
+  pick[x] = p - b;
+  if (take) {
+    const uint32_t nc = a.ncent[x];
+    if (nc < (uint32_t)a.k) {
+      voc_take(a, x, nc, p);
+      a.ncent[x] = nc + 1u;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_voc_assign(VocArgs a, int first) {
+  __shared__ uint4 cs[64];  // k <= 32 centres
+  const uint32_t i0 = blockIdx.x * 256u, i = i0 + threadIdx.x;
+  const uint32_t s0 = a.segof[i0], s1 = a.segof[min(i0 + 255u, a.na - 1u)];  // (i0 < na: the grid)
+  const bool uni = s0 == s1;
+  if (uni) {
+    const int32_t x0 = a.seg_km[s0];
+    if (x0 >= 0 && threadIdx.x < a.ncent[x0] * 2u) cs[threadIdx.x] = ((const uint4*)a.centres)[(size_t)x0 * a.k * 2 + threadIdx.x];
+  }
+  __syncthreads();
+  if (i >= a.na) return;
+  const uint32_t s = uni ? s0 : a.segof[i];
+  const int32_t x = a.seg_km[s];
+  if (x < 0) {  // TemplatedVocabulary.h:657-667
+    a.assign[i] = i - a.seg_off[s];
+    return;
+  }
+  const uint32_t nc = a.ncent[x];
+  const uint4* f = (const uint4*)a.desc + (size_t)a.perm[i] * 2;
+  const uint4 f0 = f[0], f1 = f[1];
+  const uint4* cg = (const uint4*)a.centres + (size_t)x * a.k * 2;
+  uint32_t best = 0u, bd = 0xffffffffu;
+  for (uint32_t c = 0; c < nc; c++) {  // ascending clusters and a strict <: the lowest of the least (:731-742)
+    const uint4 t0 = uni ? cs[2 * c] : cg[2 * c], t1 = uni ? cs[2 * c + 1] : cg[2 * c + 1];
+    const uint32_t d = voc_dist(f0, f1, t0, t1);
+    if (d < bd) bd = d, best = c;
+  }
+  const uint32_t old = first ? best : a.assign[i];
+  a.assign[i] = best;
+  if (old != best) a.changed[x] = 1u;  // (every writer writes 1)
+}
+
+// one word of one feature into counters [cluster][257]
+constexpr int kVocAhead = 4;  // features a lane loads before it counts them: the loads are two dependent gathers
+__device__ __forceinline__ void voc_count_word(uint32_t* cnt, uint32_t v, uint32_t w) {
+  if (w == 0u) atomicAdd(cnt + 256, 1u);
+  while (v) {
+    const uint32_t b = (uint32_t)__ffs((int)v) - 1u;
+    v &= v - 1u;
+    atomicAdd(cnt + w * 32u + b, 1u);
+  }
+}
+
+// the counts of positions [b, e), all of one node, one cluster's 257 counters after another in LDS
+__device__ __forceinline__ void voc_count_range(const VocArgs& a, uint32_t* cnt, uint32_t b, uint32_t e) {
+  const uint32_t w = threadIdx.x & 7u;
+  for (uint32_t j0 = b + (threadIdx.x >> 3); j0 < e; j0 += 32u * kVocAhead) {  // kVocAhead features' loads, then their counts
+    uint32_t c[kVocAhead], v[kVocAhead];
+#pragma unroll
+    for (int u = 0; u < kVocAhead; u++) {
+      const uint32_t j = j0 + 32u * u;
+      if (j >= e) continue;
+      c[u] = a.assign[j];
+      v[u] = a.desc[(size_t)a.perm[j] * 8u + w];
+    }
+#pragma unroll
+    for (int u = 0; u < kVocAhead; u++)
+      if (j0 + 32u * u < e) voc_count_word(cnt + c[u] * 257u, v[u], w);
+  }
+}
+
+static_assert(kVocBigNode > (uint32_t)kVocScanTile, "a big node spans a tile: only a tile's first and last segment can be big");
+__global__ __launch_bounds__(256) void k_voc_count_big(VocArgs a) {
+  extern __shared__ uint32_t voc_cnt[];  // [k][257]
+  const uint32_t i0 = blockIdx.x * (uint32_t)kVocScanTile, i1 = min(i0 + (uint32_t)kVocScanTile, a.na);
+  const uint32_t s0 = a.segof[i0], s1 = a.segof[i1 - 1u];
+  for (int part = 0; part < 2; part++) {  // (every condition is the same for all lanes of the workgroup)
+    if (part == 1 && s1 == s0) break;
+    const uint32_t s = part ? s1 : s0;
+    const int32_t x = a.seg_km[s];
+    const int32_t bx = x < 0 ? -1 : a.km_big[x];
+    if (bx < 0) continue;
+    for (uint32_t t = threadIdx.x; t < (uint32_t)a.k * 257u; t += 256u) voc_cnt[t] = 0u;
+    __syncthreads();
+    voc_count_range(a, voc_cnt, max(i0, a.seg_off[s]), min(i1, a.seg_off[s + 1u]));
+    __syncthreads();
+    uint32_t* dst = a.counts + (size_t)bx * a.k * 257u;
+    for (uint32_t t = threadIdx.x; t < (uint32_t)a.k * 257u; t += 256u)
+      if (voc_cnt[t]) atomicAdd(dst + t, voc_cnt[t]);
+    __syncthreads();
+  }
+}
+
+// FBrief::meanValue (FBrief.cpp:22-49) of one word from its 32 counts and the group's size
+__device__ __forceinline__ uint32_t voc_mean_word(const uint32_t* cnt, uint32_t w) {
+  const uint32_t half = cnt[256] >> 1;
+  uint32_t v = 0u;
+  for (uint32_t b = 0; b < 32u; b++) v |= (uint32_t)(cnt[w * 32u + b] > half) << b;
+  return v;
+}
+
+__global__ __launch_bounds__(256) void k_voc_mean_big(VocArgs a) {
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+  if (t >= a.n_big * (uint32_t)a.k * 8u) return;
+  const uint32_t w = t & 7u, c = (t >> 3) % (uint32_t)a.k, bx = (t >> 3) / (uint32_t)a.k, x = a.big_km[bx];
+  if (c >= a.ncent[x]) return;
+  a.centres[((size_t)x * a.k + c) * 8u + w] = voc_mean_word(a.counts + ((size_t)bx * a.k + c) * 257u, w);
+}
+
+__global__ __launch_bounds__(256) void k_voc_mean_small(VocArgs a) {
+  extern __shared__ uint32_t voc_cnt[];  // [k][257]
+  const uint32_t x = blockIdx.x;
+  if (a.km_big[x] >= 0) return;
+  for (uint32_t t = threadIdx.x; t < (uint32_t)a.k * 257u; t += 256u) voc_cnt[t] = 0u;
+  __syncthreads();
+  voc_count_range(a, voc_cnt, a.km_start[x], a.km_end[x]);
+  __syncthreads();
+  const uint32_t nc = a.ncent[x];
+  for (uint32_t t = threadIdx.x; t < nc * 8u; t += 256u)
+    a.centres[((size_t)x * a.k + (t >> 3)) * 8u + (t & 7u)] = voc_mean_word(voc_cnt + (t >> 3) * 257u, t & 7u);
+}
+
+__global__ __launch_bounds__(256) void k_voc_child_count(VocArgs a) {
+  __shared__ uint32_t h[32];  // where the workgroup's positions lie in one k-means node: its <= 32 children
+  const uint32_t i0 = blockIdx.x * 256u, i = i0 + threadIdx.x;
+  const uint32_t s0 = a.segof[i0], s1 = a.segof[min(i0 + 255u, a.na - 1u)];  // (i0 < na: the grid)
+  const bool uni = s0 == s1 && a.seg_km[s0] >= 0;
+  if (uni) {
+    if (threadIdx.x < 32u) h[threadIdx.x] = 0u;
+    __syncthreads();
+    if (i < a.na) atomicAdd(&h[a.assign[i]], 1u);
+    __syncthreads();
+    if (threadIdx.x < (uint32_t)a.k && h[threadIdx.x]) atomicAdd(a.slot_size + a.seg_slot[s0] + threadIdx.x, h[threadIdx.x]);
+    return;
+  }
+  if (i >= a.na) return;
+  atomicAdd(a.slot_size + a.seg_slot[a.segof[i]] + a.assign[i], 1u);
+}
+
+__global__ __launch_bounds__(256) void k_voc_regroup_keys(VocArgs a, const uint32_t* __restrict__ slot_map, int passes,
+                                                          uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
+                                                          uint32_t* __restrict__ ghist) {
+  __shared__ uint32_t h[kRadixMaxPasses << kRadixMaxBits];
+  for (int i = threadIdx.x; i < (kRadixMaxPasses << kRadixMaxBits); i += 256) h[i] = 0;
+  __syncthreads();
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i < a.na) {
+    const uint32_t key = slot_map[a.seg_slot[a.segof[i]] + a.assign[i]];
+    keys[i] = key;
+    vals[i] = a.perm[i];
+    for (int p = 0; p < passes; p++) atomicAdd(&h[(p << kRadixMaxBits) + ((key >> (p * kRadixMaxBits)) & 255u)], 1u);
+  }
+  __syncthreads();
+  for (int i2 = threadIdx.x; i2 < (passes << kRadixMaxBits); i2 += 256)
+    if (h[i2]) atomicAdd(&ghist[i2], h[i2]);
+}
+
+// the document of feature f: the last d with doc_off[d] <= f (empty documents hold nothing)
+__device__ __forceinline__ uint32_t voc_doc(const int64_t* __restrict__ doc_off, uint32_t n_docs, uint32_t f) {
+  uint32_t lo = 0u, hi = n_docs;
+  while (hi - lo > 1u) {
+    const uint32_t mid = lo + (hi - lo) / 2u;
+    if (doc_off[mid] <= (int64_t)f) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+__global__ __launch_bounds__(256) void k_voc_doc_count(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
+                                                       uint32_t n, const int64_t* __restrict__ doc_off, uint32_t n_docs,
+                                                       uint32_t n_words, uint32_t* __restrict__ ni) {
+  const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+  if (j >= n) return;
+  const uint32_t key = keys[j];
+  if (key >= n_words) return;
+  if (j == 0u || keys[j - 1u] != key || voc_doc(doc_off, n_docs, vals[j - 1u]) != voc_doc(doc_off, n_docs, vals[j])) atomicAdd(ni + key, 1u);
+}
+
+namespace {
+dim3 voc_grid(uint32_t n, uint32_t per = 256u) { return dim3((n + per - 1u) / per); }
+}  // namespace
+void launch_voc_first(hipStream_t s, const VocArgs& a) {
+  if (a.n_km) launch_k(k_voc_first, voc_grid(a.n_km), dim3(256), 0, s, a);
+}
+void launch_voc_mindist(hipStream_t s, const VocArgs& a, int first) {
+  if (a.na) launch_k(k_voc_mindist, voc_grid(a.na), dim3(256), 0, s, a, first);
+}
+void launch_voc_scan_reduce(hipStream_t s, const uint32_t* min_dist, uint32_t n, uint64_t* tile_sum) {
+  if (n) launch_k(k_voc_scan_reduce, dim3(voc_tiles(n)), dim3(256), 0, s, min_dist, n, tile_sum);
+}
+void launch_voc_scan_top(hipStream_t s, uint64_t* tile_sum, uint32_t tiles) {
+  if (tiles) launch_k(k_voc_scan_top, dim3(1), dim3(256), 0, s, tile_sum, tiles);
+}
+void launch_voc_scan_down(hipStream_t s, const uint32_t* min_dist, uint32_t n, const uint64_t* tile_sum, uint64_t* run) {
+  if (n) launch_k(k_voc_scan_down, dim3(voc_tiles(n)), dim3(256), 0, s, min_dist, n, tile_sum, run);
+}
+void launch_voc_draw(hipStream_t s, const VocArgs& a) {
+  if (a.n_km) launch_k(k_voc_draw, voc_grid(a.n_km), dim3(256), 0, s, a);
+}
+void launch_voc_pick(hipStream_t s, const uint64_t* run, const uint32_t* start, const uint32_t* end, const double* cut_d,
+                     uint32_t n_seg, uint32_t* pick, const VocArgs& a, int take) {
+  if (n_seg) launch_k(k_voc_pick, voc_grid(n_seg), dim3(256), 0, s, run, start, end, cut_d, n_seg, pick, a, take);
+}
+void launch_voc_assign(hipStream_t s, const VocArgs& a, int first) {
+  if (a.na) launch_k(k_voc_assign, voc_grid(a.na), dim3(256), 0, s, a, first);
+}
+void launch_voc_count_big(hipStream_t s, const VocArgs& a) {
+  if (a.na && a.n_big) launch_k(k_voc_count_big, dim3(voc_tiles(a.na)), dim3(256), (unsigned)a.k * 257u * 4u, s, a);
+}
+void launch_voc_mean_big(hipStream_t s, const VocArgs& a) {
+  if (a.n_big) launch_k(k_voc_mean_big, voc_grid(a.n_big * (uint32_t)a.k * 8u), dim3(256), 0, s, a);
+}
+void launch_voc_mean_small(hipStream_t s, const VocArgs& a) {
+  if (a.n_km > a.n_big) launch_k(k_voc_mean_small, dim3(a.n_km), dim3(256), (unsigned)a.k * 257u * 4u, s, a);
+}
+void launch_voc_child_count(hipStream_t s, const VocArgs& a) {
+  if (a.na) launch_k(k_voc_child_count, voc_grid(a.na), dim3(256), 0, s, a);
+}
+void launch_voc_regroup_keys(hipStream_t s, const VocArgs& a, const uint32_t* slot_map, int passes, uint32_t* keys,
+                             uint32_t* vals, uint32_t* ghist) {
+  if (a.na) launch_k(k_voc_regroup_keys, voc_grid(a.na), dim3(256), 0, s, a, slot_map, passes, keys, vals, ghist);
+}
+void launch_voc_doc_count(hipStream_t s, const uint32_t* keys, const uint32_t* vals, uint32_t n, const int64_t* doc_off,
+                          uint32_t n_docs, uint32_t n_words, uint32_t* ni) {
+  if (n) launch_k(k_voc_doc_count, voc_grid(n), dim3(256), 0, s, keys, vals, n, doc_off, n_docs, n_words, ni);
+}
+
 }  // namespace esvio

@@ -357,6 +357,7 @@ ABI_SYMBOLS = [
     "esvio_fe_kf_describe",
     "esvio_fe_bow_vocabulary_header", "esvio_fe_bow_set_vocabulary", "esvio_fe_bow_transform", "esvio_fe_bow_add",
     "esvio_fe_bow_query", "esvio_fe_bow_detect_loop", "esvio_fe_bow_clear", "esvio_fe_bow_entries", "esvio_fe_bow_reserve",
+    "esvio_fe_bow_create_vocabulary", "esvio_fe_bow_get_created",
 ]
 # test / measurement taps: include/esvio_fe_test.h (not part of the boundary)
 TEST_SYMBOLS = [
@@ -376,6 +377,7 @@ TEST_SYMBOLS = [
     "esvio_fe_aedat_frame_walk_tap", "esvio_fe_aedat_frame_kernel_stats", "esvio_fe_frame16_tile_pixels",
     "esvio_fe_kf_kernel_count", "esvio_fe_kf_kernel_name", "esvio_fe_kf_kernel_stats", "esvio_fe_kf_blur_tile",
     "esvio_fe_bow_kernel_count", "esvio_fe_bow_kernel_name", "esvio_fe_bow_kernel_stats", "esvio_fe_bow_limits", "esvio_fe_bow_scores",
+    "esvio_fe_bow_create_kernel_count", "esvio_fe_bow_create_kernel_name", "esvio_fe_bow_create_kernel_stats", "esvio_fe_bow_create_pick",
 ]
 
 LATENCY_PHASES = 16
@@ -404,6 +406,17 @@ class BowVocabularyInfo(C.Structure):  # esvio_fe_bow_vocabulary_info
 
 class BowResult(C.Structure):  # esvio_fe_bow_result
     _fields_ = [("id", C.c_int32), ("score", C.c_double)]
+
+
+class BowCreateParams(C.Structure):  # esvio_fe_bow_create_params
+    _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("weighting", C.c_int32), ("scoring", C.c_int32), ("max_passes", C.c_int32),
+                ("reserved", C.c_int32), ("seed", C.c_uint64)]
+
+
+class BowCreateInfo(C.Structure):  # esvio_fe_bow_create_info
+    _fields_ = [("nodes", C.c_int32), ("words", C.c_int32), ("depth", C.c_int32), ("max_children", C.c_int32),
+                ("kmeans_nodes", C.c_int32), ("passes", C.c_int32), ("empty_clusters", C.c_int32), ("short_seedings", C.c_int32),
+                ("bytes", C.c_uint64), ("message", C.c_char * 188)]
 
 
 class BowLimits(C.Structure):  # esvio_fe_bow_limits_info
@@ -668,6 +681,12 @@ def load_library(build_if_missing=True):
     L.esvio_fe_bow_kernel_stats.argtypes = [vp, i, C.POINTER(d), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.esvio_fe_bow_limits.argtypes = [C.POINTER(BowLimits)]
     L.esvio_fe_bow_scores.argtypes = [vp, vp, i, i, i, vp, vp]
+    L.esvio_fe_bow_create_vocabulary.argtypes = [vp, vp, C.c_int64, i, vp, C.c_int32, C.POINTER(BowCreateParams), C.POINTER(BowCreateInfo)]
+    L.esvio_fe_bow_get_created.argtypes = [vp, vp, C.c_size_t]
+    L.esvio_fe_bow_create_kernel_name.restype = C.c_char_p
+    L.esvio_fe_bow_create_kernel_name.argtypes = [i]
+    L.esvio_fe_bow_create_kernel_stats.argtypes = [vp, i, C.POINTER(d), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.esvio_fe_bow_create_pick.argtypes = [vp, vp, C.c_int64, vp, C.c_int32, vp, vp]
     _lib = L
     return L
 
@@ -2040,6 +2059,46 @@ class FeatureTracker:
             ms, n, b = C.c_double(0), C.c_uint64(0), C.c_uint64(0)
             self._hd.check(L.esvio_fe_bow_kernel_stats(self._hd.h, k, C.byref(ms), C.byref(n), C.byref(b)))
             out[L.esvio_fe_bow_kernel_name(k).decode()] = dict(ms=ms.value, launches=n.value, alg_bytes=b.value)
+        return out
+
+    # ---- creating a vocabulary (esvio_fe_bow_create_*; include/esvio_fe.h "C, creating a vocabulary" has the rule)
+    def bow_create_vocabulary(self, desc, doc_offsets, k, L, weighting=0, scoring=0, seed=0, max_passes=0, n=None, check=True):
+        """esvio_fe_bow_create_vocabulary -> (return code, dict of the info struct); desc as _bow_desc takes it,
+        doc_offsets n_docs + 1 ascending offsets.  check: raise on a non-zero return code"""
+        ptr, n, space, keep = self._bow_desc(desc, n)
+        off = np.ascontiguousarray(doc_offsets, np.int64)
+        par = BowCreateParams(int(k), int(L), int(weighting), int(scoring), int(max_passes), 0, int(seed) & 0xffffffffffffffff)
+        info = BowCreateInfo()
+        rc = self._hd.L.esvio_fe_bow_create_vocabulary(self._hd.h, ptr, n, space, _p(off), len(off) - 1, C.byref(par), C.byref(info))
+        if check:
+            self._hd.check(rc)
+        out = {f: getattr(info, f) for f, _ in BowCreateInfo._fields_ if f != "message"}
+        out["message"] = info.message.decode()
+        return rc, out
+
+    def bow_get_created(self, n_bytes):
+        """the file image of the last successful create (esvio_fe_bow_get_created); n_bytes: info's `bytes`"""
+        buf = np.empty(max(int(n_bytes), 1), np.uint8)
+        self._hd.check(self._hd.L.esvio_fe_bow_get_created(self._hd.h, _p(buf), int(n_bytes)))
+        return buf[:int(n_bytes)].tobytes()
+
+    def bow_create_pick(self, min_dist, seg_off, cut_d):
+        """C2's pick alone on the device (esvio_fe_bow_create_pick, a test tap) -> uint32[n_seg] ranks"""
+        md = np.ascontiguousarray(min_dist, np.uint32)
+        so = np.ascontiguousarray(seg_off, np.uint32)
+        cd = np.ascontiguousarray(cut_d, np.float64)
+        out = np.zeros(len(cd), np.uint32)
+        self._hd.check(self._hd.L.esvio_fe_bow_create_pick(self._hd.h, _p(md), len(md), _p(so), len(so) - 1, _p(cd), _p(out)))
+        return out
+
+    def bow_create_kernel_stats(self):
+        """vocabulary creation's own kernel table (esvio_fe_bow_create_kernel_*): name -> dict(ms, launches, alg_bytes)"""
+        L = self._hd.L
+        out = {}
+        for k in range(L.esvio_fe_bow_create_kernel_count()):
+            ms, n, b = C.c_double(0), C.c_uint64(0), C.c_uint64(0)
+            self._hd.check(L.esvio_fe_bow_create_kernel_stats(self._hd.h, k, C.byref(ms), C.byref(n), C.byref(b)))
+            out[L.esvio_fe_bow_create_kernel_name(k).decode()] = dict(ms=ms.value, launches=n.value, alg_bytes=b.value)
         return out
 
     # ---- camera split (right camera on another GPU)

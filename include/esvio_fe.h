@@ -1633,13 +1633,13 @@ int esvio_fe_kf_describe(esvio_fe_handle h, int cam, const uint8_t* img, int spa
  * scores that names the loop candidate or -1.  These calls are that step, so that a keyframe's way from the frame
  * (esvio_fe_kf_describe, descriptors left in device memory) to the candidate (esvio_fe_kf_match) stays on the device.
  * PnP, the 4-DoF optimisation and the DEBUG_IMAGE canvases stay with the host; so do the direct index / FeatureVector
- * (use_di is false, pose_graph.cpp:49), scorings other than L1, vocabulary creation, delete_entry and the text
- * vocabulary format.  This text is the specification.  Everything is integer arithmetic plus IEEE double additions,
+ * (use_di is false, pose_graph.cpp:49), scorings other than L1, delete_entry and the text vocabulary format
+ * (creating a vocabulary is the group after this one, "C").  This text is the specification.  Everything is integer arithmetic plus IEEE double additions,
  * subtractions and one division in a stated order; no rule has a product.
  * WHAT IS PINNED: BowVector's addWeight / addIfNotExist / normalize(L1) (ThirdParty/DBoW/BowVector.cpp:34-84) are held
  * to outputs of that file compiled unchanged (tests/golden/bow_vector_ref.npz).  The rest of DBoW2 includes OpenCV and
- * boost; its rules are CITED BY LINE AND RESTATED here, unpinned.  Every vocabulary in the tests and measurements is
- * synthetic: the shipped brief_k10L6.bin is not at hand.
+ * boost; its rules are CITED BY LINE AND RESTATED here, unpinned.  Every vocabulary in these calls' own tests and
+ * measurements is synthetic: the shipped brief_k10L6.bin is not at hand ("C" below trains one from descriptors).
  *
  * V, the vocabulary file — ThirdParty/VocabularyBinary.hpp:12-45, VocabularyBinary.cpp:29-37, TemplatedVocabulary.h:
  *   1509-1561 (loadBin): 24 bytes {k, L, scoringType, weightingType, nNodes, nWords}, little-endian int32; nNodes records
@@ -1736,6 +1736,90 @@ int esvio_fe_bow_detect_loop(esvio_fe_handle h, const uint32_t* desc, int n, int
 int esvio_fe_bow_clear(esvio_fe_handle h);
 int esvio_fe_bow_entries(esvio_fe_handle h);
 int esvio_fe_bow_reserve(esvio_fe_handle h, int64_t entries, int64_t words);
+
+/* ---- C, creating a vocabulary: k-means++, the tree, the word weights (DBoW2) ------------------ */
+/* The input every call above depends on: TemplatedVocabulary::create with HKmeansStep, initiateClustersKMpp,
+ * createWords, setNodeWeights and FBrief::meanValue / distance, from training descriptors to a file image in format V.
+ * Paths are under pose_graph/src/ThirdParty/.  Integer arithmetic on 256-bit descriptors throughout; doubles only in the
+ * draws (C5) and the weights (C4).  CITED BY LINE AND RESTATED, unpinned, like W to L; this text is the specification.
+ * The claim is "equal to create() given the draws of C5 in place of rand()" — not equal to any particular run of the
+ * reference, which seeds rand() from the clock.
+ *
+ * Input: n descriptors of 8 words, grouped into n_docs documents (images) by doc_offsets[0..n_docs]: ascending,
+ *   doc_offsets[0] = 0, doc_offsets[n_docs] = n.  Empty documents are allowed and count in NDocs.  The flat order is
+ *   document order (getFeatures, DBoW/TemplatedVocabulary.h:618-634).  Parameters: k, L, weighting 0..3, scoring (0
+ *   only), seed, max_passes.
+ * C1, a node's step — HKmeansStep, TemplatedVocabulary.h:639-816, for a node with m features in order (m = 0 never
+ *   occurs: :642 returns at once, and only nodes with features are made).  m <= k (:657-667): one cluster per feature, in
+ *   order, the centre the feature itself; duplicates stay duplicates.  m > k: the centres are seeded by C2, then passes
+ *   repeat.  A pass after the first recomputes every centre by C3 from the previous pass's groups; every pass assigns each
+ *   feature to the centre with the least popcount(f xor c), of equal distances the lowest cluster index (`dist <
+ *   best_dist` is strict, :731-742).  The loop ends after the first pass, the very first not counted, whose assignment
+ *   equals the previous pass's (:753-769); the clusters are the centres that pass used, the groups its assignment, a
+ *   group in the node's feature order.  Every cluster becomes a child of the node in cluster order, its id
+ *   m_nodes.size() at the push (:783-790).  If current_level < L, each child whose group has more than one feature is
+ *   split in turn, child 0's whole subtree first (:793-815).  So: ids are the depth-first creation order; a child with
+ *   one feature, or with none, is a leaf at any depth; a node has 1..k children.
+ * C2, k-means++ seeding — initiateClustersKMpp, :831-912.  The first centre is feature RandomInt(0, m - 1).
+ *   min_dist[i] starts as the distance to it.  While fewer than k centres exist: every feature with min_dist > 0 takes
+ *   the minimum with its distance to the newest centre (the first time round that is the first centre again and changes
+ *   nothing — stated, not imitated); dist_sum = the sum, exact, the terms being integers; dist_sum == 0 ends the seeding
+ *   with fewer than k centres (:907-908); else cut_d = RandomValue<double>(0, dist_sum), drawn again while cut_d == 0.0;
+ *   the new centre is the first feature whose running sum of min_dist in feature order, as a double, is >= cut_d, or the
+ *   last feature if none (:892-904).
+ * C3, the mean — DBoW/FBrief.cpp:22-49: bit i of the centre is set iff more than floor(m_c / 2) of the group's m_c
+ *   features have it set; an empty group gives the all-zero descriptor (:25-27).  Empty groups are common on clustered
+ *   descriptors: centres that collapse onto one majority pattern lose every feature but the first's.
+ * C4, words and weights — createWords :917-937, setNodeWeights :942-995, Node().  Word ids go to the leaves in ascending
+ *   node id.  Nodes with children weigh 0.0.  TF and BINARY: every word weighs 1.0.  TF_IDF and IDF: Ni[w] = the documents
+ *   with at least one feature whose walk W (above, on the finished tree) ends in word w; the weight is log((double)NDocs
+ *   / (double)Ni) by the host's libm, or 0.0 where Ni == 0 (empty clusters; the later of two equal features of an m <= k
+ *   node).
+ * C5, the draws — the project's own rule: a draw is a function of (seed, node, index), so that any order of evaluating
+ *   the nodes sees the same numbers.  mix(z) is splitmix64's step: z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) *
+ *   0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31, all modulo 2^64.  key(root) = mix(seed);
+ *   key(child c of n) = mix(key(n) ^ (uint64)(c + 1)), c the cluster index.  Draw j = 0, 1, ... of node n in the order C2
+ *   takes them: r = mix(key(n) ^ ((uint64)(j + 1) << 32)) >> 33, 31 bits, glibc's rand() range.  RandomInt(0, m - 1) =
+ *   (int)(((double)r / 2147483648.0) * (double)m) (DUtils/Random.cpp:47-50); RandomValue<double>(0, s) = ((double)r /
+ *   2147483647.0) * s (DUtils/Random.h:56-68), as IEEE double operations.
+ * C6, the output: a file image in format V that loadBin reads and esvio_fe_bow_vocabulary_header accepts; node records
+ *   in ascending nodeId (which is child order), word records in ascending wordId; k, L, scoring, weighting as given.
+ * C7, refused with ESVIO_FE_EINVAL and a message, before any device work: n < 1 or n > 2^24; k outside 2..32; L outside
+ *   1..10; a weighting outside 0..3; offsets that are not as stated; a misaligned device pointer; a negative max_passes.
+ *   A scoring other than 0: ESVIO_FE_ENOTIMPL.
+ * The project's own guard: the reference's loop has no bound.  If a node has not settled after max_passes assignment
+ *   passes (0 means 100) the call fails with ESVIO_FE_EINVAL, the message naming how many nodes of the first level that
+ *   has any; nothing is stored.
+ *
+ * esvio_fe_bow_create_vocabulary: desc in ESVIO_FE_HOST memory is copied first, in ESVIO_FE_DEVICE memory it is read in
+ *   place (16-byte aligned); doc_offsets, params and info are host memory.  The call orders itself on the main stream and
+ *   waits for its own result.  It touches neither the tracker nor the vocabulary that is set nor the database: made
+ *   between two track calls, batches announced or not, it changes no later result.  On failure info holds the message
+ *   and zeros.
+ * esvio_fe_bow_get_created: the image of the last successful create, info.bytes bytes, into host memory of `cap` bytes
+ *   (ESVIO_FE_EINVAL if there is none or cap is too small).  The image lives until the next successful create or
+ *   esvio_fe_destroy; esvio_fe_reset keeps it.  Using it is the caller's esvio_fe_bow_set_vocabulary on the bytes.
+ *   Where a maintainer calls this, offline: INTEGRATION.md. */
+typedef struct esvio_fe_bow_create_params {
+  int32_t k, L;
+  int32_t weighting;  /* 0..3: TF_IDF, TF, IDF, BINARY */
+  int32_t scoring;    /* 0: L1_NORM */
+  int32_t max_passes; /* 0: 100 */
+  int32_t reserved;
+  uint64_t seed;
+} esvio_fe_bow_create_params;
+typedef struct esvio_fe_bow_create_info {
+  int32_t nodes, words, depth, max_children; /* as esvio_fe_bow_vocabulary_info has them */
+  int32_t kmeans_nodes;   /* nodes with more than k features */
+  int32_t passes;         /* the most assignment passes any node needed under C1 (0 without a k-means node) */
+  int32_t empty_clusters; /* final clusters of k-means nodes without a feature */
+  int32_t short_seedings; /* nodes whose seeding stopped at dist_sum == 0 */
+  uint64_t bytes;         /* size of the file image */
+  char message[188];      /* "" or why the call failed */
+} esvio_fe_bow_create_info;
+int esvio_fe_bow_create_vocabulary(esvio_fe_handle h, const uint32_t* desc, int64_t n, int space, const int64_t* doc_offsets,
+                                   int32_t n_docs, const esvio_fe_bow_create_params* params, esvio_fe_bow_create_info* info);
+int esvio_fe_bow_get_created(esvio_fe_handle h, void* out, size_t cap);
 
 /* ---- camera split across GPUs (BASELINE config C4) ----------------------- */
 /* The left and right cameras have disjoint SAE state (sae_/sae_latest_ vs sae_right/

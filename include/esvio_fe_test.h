@@ -289,6 +289,18 @@ const char* esvio_fe_bow_kernel_name(int which);
 int esvio_fe_bow_kernel_stats(esvio_fe_handle h, int which, double* total_ms, uint64_t* launches, uint64_t* alg_bytes);
 int esvio_fe_bow_limits(esvio_fe_bow_limits_info* out);
 int esvio_fe_bow_scores(esvio_fe_handle h, const uint32_t* desc, int n, int space, int max_id, double* score, uint8_t* present);
+/* vocabulary creation's kernels (esvio_fe_bow_create_vocabulary), a table of their own in timer slots behind every other;
+ * the other tables stay as they are (the stable sorts are booked as k_radix_pass of the TRACK table, the document counts'
+ * walk as k_bow_walk of loop detection's).  esvio_fe_bow_create_kernel_name: "" for any other id.
+ * esvio_fe_bow_create_pick: C2's pick alone, on the device, with chosen numbers — min_dist [n] (n in 1..2^24), n_seg
+ * segments seg_off[0..n_seg] ascending inside 0..n, one cut_d per segment; pick[s] = the first rank inside segment s
+ * whose running sum of min_dist, as a double, is >= cut_d[s], the segment's last rank if none, 0xffffffff for an empty
+ * segment or a cut_d that is not >= 0.  Host arrays. */
+int esvio_fe_bow_create_kernel_count(void);
+const char* esvio_fe_bow_create_kernel_name(int which);
+int esvio_fe_bow_create_kernel_stats(esvio_fe_handle h, int which, double* total_ms, uint64_t* launches, uint64_t* alg_bytes);
+int esvio_fe_bow_create_pick(esvio_fe_handle h, const uint32_t* min_dist, int64_t n, const uint32_t* seg_off, int32_t n_seg,
+                             const double* cut_d, uint32_t* pick);
 /* the events one workgroup of the slicing chain takes (esvio_fe_slice_events): where its tile edges lie */
 int esvio_fe_slice_tile_events(void);
 /* the hipStream_t the handle launches on (as void*) */
