@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libesvio_fe.so")
 SOURCES = ["fe_kernels.hip", "fe_stages.cpp", "fe_track.cpp", "fe_image.cpp", "fe_api.cpp", "fe_host.cpp", "fe_evstage.cpp"]
-HEADERS = ["fe_kernels.h", "fe_aedat.h", "fe_bag.h", "fe_host.h", "fe_ctx.h", "fe_res.h", "fe_internal.h", "fe_layout.h", "fe_mc.h", "fe_kf.h", "fe_bow.h", "fe_voc.h", os.path.join("..", "..", "include", "esvio_fe.h"),
+HEADERS = ["fe_kernels.h", "fe_aedat.h", "fe_bag.h", "fe_host.h", "fe_ctx.h", "fe_res.h", "fe_internal.h", "fe_layout.h", "fe_mc.h", "fe_kf.h", "fe_bow.h", "fe_voc.h", "fe_text.h", os.path.join("..", "..", "include", "esvio_fe.h"),
            os.path.join("..", "..", "include", "esvio_fe_test.h")]
 FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
@@ -104,11 +104,29 @@ def build_voc_seq(force=False):
     return out
 
 
+TEXT_SEQ_SRC = os.path.join(HERE, "..", "tools", "text_seq_decode.cpp")
+TEXT_SEQ_BIN = os.path.join(HERE, "..", "tools", "_bin", "text_seq_decode")
+
+
+def build_text_seq(force=False):
+    """tools/_bin/text_seq_decode: a text event file read line by line on one core over the project's own sequential
+    reading (tools/text_microbench.py runs it), plain g++, no device code"""
+    src, out = os.path.abspath(TEXT_SEQ_SRC), os.path.abspath(TEXT_SEQ_BIN)
+    deps = [src, os.path.join(CSRC, "fe_text.h")]
+    if not force and os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(d) for d in deps):
+        return out
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    subprocess.check_call([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-Wall", "-I" + CSRC, src, "-o", out])
+    return out
+
+
 def build_tools(force=False):
     """tools/replay_node: the C++ host harness (handle_stereo_event over the C ABI), plain g++; and, beside it,
-    tools/_bin/aedat_frame_seq (build_frame_seq) and tools/_bin/voc_create_seq (build_voc_seq)"""
+    tools/_bin/aedat_frame_seq (build_frame_seq), tools/_bin/voc_create_seq (build_voc_seq) and tools/_bin/text_seq_decode
+    (build_text_seq)"""
     build_frame_seq(force)
     build_voc_seq(force)
+    build_text_seq(force)
     src, out = os.path.abspath(TOOL_SRC), os.path.abspath(TOOL_BIN)
     if not force and os.path.exists(out) and os.path.getmtime(out) >= max(
             os.path.getmtime(src), os.path.getmtime(LIB), os.path.getmtime(os.path.join(HERE, "..", "include", "esvio_fe.h"))):

@@ -2264,6 +2264,277 @@ int esvio_fe_track_raw(esvio_fe_handle c, int format, const void* left, size_t l
   });
 }
 
+// ---- text event files (the rule: include/esvio_fe.h; the classifier and the carry step: fe_text.h; the chain: fe_kernels.h)
+namespace {
+namespace tx = esvio::text;
+static_assert(sizeof(tx::ImuSample) == sizeof(esvio_fe_imu_sample) && offsetof(tx::ImuSample, gyr) == offsetof(esvio_fe_imu_sample, gyr),
+              "fe_text.h writes esvio_fe_imu_sample's bytes");
+static_assert(ESVIO_FE_TEXT_TXYP == tx::kTxyp && ESVIO_FE_TEXT_XYPT == tx::kXypt && ESVIO_FE_TEXT_SEC_DECIMAL == tx::kSecDecimal &&
+                  ESVIO_FE_TEXT_INT_US == tx::kIntUs && ESVIO_FE_TEXT_INT_NS == tx::kIntNs && ESVIO_FE_TEXT_END == tx::kEnd &&
+                  ESVIO_FE_TEXT_SKIP_MALFORMED == tx::kSkipMalformed,
+              "fe_text.h's constants are the header's");
+struct TextJob {  // one camera's part of a call
+  const void* bytes = nullptr;
+  size_t n_bytes = 0;
+  bool active = false;
+  tx::State st{};  // the camera's state behind the chunk: taken over when the call succeeds
+};
+
+int text_args_check(esvio_fe_ctx* c, const char* who, const esvio_fe_text_format* fmt, const void* bytes, size_t n_bytes, int space,
+                    int64_t t_offset_ns) {
+  if (!fmt) return fail(c, ESVIO_FE_EINVAL, "%s: fmt is null", who);
+  if (fmt->order != ESVIO_FE_TEXT_TXYP && fmt->order != ESVIO_FE_TEXT_XYPT)
+    return fail(c, ESVIO_FE_EINVAL, "%s: order must be ESVIO_FE_TEXT_TXYP or ESVIO_FE_TEXT_XYPT (got %d)", who, fmt->order);
+  if (fmt->time != ESVIO_FE_TEXT_SEC_DECIMAL && fmt->time != ESVIO_FE_TEXT_INT_US && fmt->time != ESVIO_FE_TEXT_INT_NS)
+    return fail(c, ESVIO_FE_EINVAL, "%s: time must be ESVIO_FE_TEXT_SEC_DECIMAL, _INT_US or _INT_NS (got %d)", who, fmt->time);
+  if (fmt->flags & ~(ESVIO_FE_TEXT_END | ESVIO_FE_TEXT_SKIP_MALFORMED)) return fail(c, ESVIO_FE_EINVAL, "%s: unknown bits in flags (0x%x)", who, fmt->flags);
+  if (fmt->reserved != 0) return fail(c, ESVIO_FE_EINVAL, "%s: reserved must be 0", who);
+  if (space != ESVIO_FE_HOST && space != ESVIO_FE_DEVICE) return fail(c, ESVIO_FE_EINVAL, "%s: bad memory space", who);
+  const int64_t lim = (int64_t)1 << 62;
+  if (t_offset_ns > lim || t_offset_ns < -lim) return fail(c, ESVIO_FE_EINVAL, "%s: |t_offset_ns| must be <= 2^62", who);
+  if (n_bytes > kRawMaxBytes) return fail(c, ESVIO_FE_EINVAL, "%s: a chunk holds at most 2^28 bytes", who);
+  if (n_bytes && !bytes) return fail(c, ESVIO_FE_EINVAL, "%s: bytes is null", who);
+  return 0;
+}
+size_t text_bound(size_t n_bytes) { return (n_bytes + tx::kMaxTail) / 8 + 1; }  // the shortest event line is 8 bytes
+uint32_t text_tiles(size_t virt_bytes) { return (uint32_t)std::max<size_t>((virt_bytes + kTextTileBytes - 1) / kTextTileBytes, 1); }
+// has the call anything to do?  Bytes, or with END a state that is not fresh
+bool text_active(const esvio_fe_ctx* c, int cam, const esvio_fe_text_format& fmt, size_t n_bytes) {
+  return n_bytes || ((fmt.flags & ESVIO_FE_TEXT_END) && (c->text.st[cam].len || c->text.st[cam].skip));
+}
+
+int text_ensure(esvio_fe_ctx* c, int cam, size_t n_bytes, bool copied_src) {
+  esvio_fe_ctx::Text& t = c->text;
+  t.used = true;
+  if (!t.res)
+    if (int rc = t.res.alloc(c, 2)) return rc;
+  if (int rc = t.sums[cam].grow(c, text_tiles(n_bytes + tx::kMaxTail))) return rc;
+  return copied_src ? t.src[cam].grow(c, std::max<size_t>(n_bytes, 1)) : 0;
+}
+// esvio_fe_reserve for a handle that decodes text: per camera the scratch of a file of up to 16 bytes per event (include/esvio_fe.h)
+int text_reserve(esvio_fe_ctx* c, const size_t events[2], bool host_batches) {
+  for (int cam = 0; cam < 2 && c->text.used; cam++)
+    if (int rc = text_ensure(c, cam, events[cam] * 16, host_batches)) return rc;
+  return 0;
+}
+void text_state_reset(esvio_fe_ctx* c) { c->text.st[0] = c->text.st[1] = tx::State(); }
+
+TextCarry text_carry_of(const tx::State& st) {
+  TextCarry k{};
+  memcpy(k.tail_w, st.tail, st.len);
+  k.len = st.len, k.skip = st.skip, k.skip_len = st.skip_len;
+  return k;
+}
+void text_state_of(const TextCarry& k, tx::State* st) {
+  *st = tx::State();
+  st->len = std::min<uint32_t>(k.len, tx::kMaxTail), st->skip = k.skip ? 1 : 0, st->skip_len = k.skip_len;
+  memcpy(st->tail, k.tail_w, st->len);
+}
+void text_info_clear(esvio_fe_text_info* info, const tx::State& st) {
+  if (!info) return;
+  info->events = info->lines = info->comments = info->blank = info->malformed = info->bad = 0;
+  info->carried = st.len, info->reserved = 0;
+}
+void text_info_fill(esvio_fe_text_info* info, const TextResult& r) {  // the counts: exact whether the call succeeds or not
+  if (!info) return;
+  info->events = r.events, info->comments = r.comments, info->blank = r.blank, info->malformed = r.malformed, info->bad = r.bad;
+  info->lines = r.events + r.comments + r.blank + r.malformed;
+  if (r.malformed) info->first_malformed = r.first_malformed;
+}
+void text_info_done(esvio_fe_text_info* info, const TextResult& r, const tx::State& st) {  // what a call that succeeded adds
+  if (!info) return;
+  if (r.events) info->first_t_ns = r.first_t, info->last_t_ns = r.last_t;
+  info->carried = st.len;
+}
+
+// The decode step of one camera (job[1].active == false) or of both: place(want, dc) says where job[k]'s records go —
+// want[k] is the bound, so no emit is ever repeated —, the chain runs on the current stream and is waited for.  r[k],
+// dc[k]: the result block and the records of job[k]; job[k].st: the state behind the chunk; the cameras' states are as
+// they were.
+extern "C++" template <class Place>
+int text_run(esvio_fe_ctx* c, const esvio_fe_text_format& fmt, int space, int64_t t_offset_ns, TextJob job[2], const int cam_of[2],
+             Place place, TextResult r[2], DecodedCam dc[2]) {
+  esvio_fe_ctx::Text& t = c->text;
+  const size_t want[2] = {job[0].active ? text_bound(job[0].n_bytes) : 0, job[1].active ? text_bound(job[1].n_bytes) : 0};
+  if (int rc = place(want, dc)) return rc;
+  hipStream_t s = cur_stream(c);
+  TextArgs a{};
+  a.order = fmt.order, a.time = fmt.time;
+  uint64_t bytes = 0, cap_bytes = 0;
+  for (int k = 0; k < 2; k++) {
+    if (!job[k].active) continue;
+    const int cam = cam_of[k];
+    const uint8_t* d_bytes = (const uint8_t*)job[k].bytes;
+    if (space == ESVIO_FE_HOST && job[k].n_bytes) {
+      const bool in_place = c->rawdec.pinned_copy < 0 ? job[k].n_bytes <= kRawPinnedInPlaceBytes : c->rawdec.pinned_copy == 0;
+      d_bytes = in_place ? pinned_device_ptr((const uint8_t*)job[k].bytes, job[k].n_bytes) : nullptr;
+      if (!d_bytes) {
+        if (int rc = text_ensure(c, cam, job[k].n_bytes, true)) return rc;
+        HIPCHK(c, hipMemcpyAsync(t.src[cam], job[k].bytes, job[k].n_bytes, hipMemcpyHostToDevice, s));
+        d_bytes = t.src[cam];
+      }
+    }
+    if (int rc = text_ensure(c, cam, job[k].n_bytes, false)) return rc;
+    TextCam& tc = a.cam[k];
+    tc.bytes = d_bytes, tc.n_bytes = (uint32_t)job[k].n_bytes;
+    tc.carry = text_carry_of(t.st[cam]);
+    tc.tiles = text_tiles((size_t)tc.carry.len + job[k].n_bytes);
+    tc.end = fmt.flags & ESVIO_FE_TEXT_END ? 1u : 0u, tc.t_offset = t_offset_ns;
+    tc.sums = t.sums[cam], tc.dst = dc[k].d, tc.dst_cap = (uint32_t)std::min<size_t>(dc[k].cap, 0xffffffffu);
+    tc.res = t.res + cam;
+    bytes += tc.carry.len + job[k].n_bytes;
+    cap_bytes += std::min(dc[k].cap, want[k]) * 16;
+  }
+  const uint64_t tile_bytes = (uint64_t)(a.cam[0].tiles + a.cam[1].tiles) * sizeof(TextTile);
+  {
+    ScopedKernel k(c, K_TEXT_COUNT, bytes + tile_bytes);
+    launch_text_count(s, a);
+  }
+  {
+    ScopedKernel k(c, K_TEXT_PLACE, 2 * tile_bytes);
+    launch_text_place(s, a);
+  }
+  {  // (booked as if every record the buffers have room for were written: the count is not known here)
+    ScopedKernel k(c, K_TEXT_EMIT, bytes + cap_bytes);
+    launch_text_emit(s, a);
+  }
+  for (int k = 0; k < 2; k++)
+    if (job[k].active) HIPCHK(c, hipMemcpyAsync(&r[k], a.cam[k].res, sizeof(TextResult), hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  if (c->prof_on) resolve_profile(c);
+  for (int k = 0; k < 2; k++) {
+    if (!job[k].active) continue;
+    dc[k].events = (size_t)r[k].events, dc[k].bad = r[k].bad;
+    dc[k].sec = r[k].last_sec, dc[k].nsec = r[k].last_nsec;
+    if (fmt.flags & ESVIO_FE_TEXT_END) {
+      job[k].st = tx::State();
+    } else if (space == ESVIO_FE_HOST) {  // the host can read the chunk: the carry step
+      job[k].st = t.st[cam_of[k]];
+      tx::carry(&job[k].st, (const uint8_t*)job[k].bytes, job[k].n_bytes);
+    } else {
+      text_state_of(r[k].state, &job[k].st);
+    }
+  }
+  return 0;
+}
+// a malformed line without SKIP_MALFORMED refuses the call
+int text_malformed_check(esvio_fe_ctx* c, const char* who, const esvio_fe_text_format& fmt, const TextResult r[2], int n, const char* states) {
+  if (fmt.flags & ESVIO_FE_TEXT_SKIP_MALFORMED) return 0;
+  for (int k = 0; k < n; k++)
+    if (r[k].malformed)
+      return fail(c, ESVIO_FE_EINVAL, "%s: %llu malformed line(s)%s, the first at byte offset %lld of the chunk; %s as before the call", who,
+                  r[k].malformed, n > 1 ? (k ? " in the right camera" : " in the left camera") : "", r[k].first_malformed, states);
+  return 0;
+}
+}  // namespace
+
+int esvio_fe_decode_text(esvio_fe_handle c, int cam, const esvio_fe_text_format* fmt, const void* bytes, size_t n_bytes, int space,
+                         int64_t t_offset_ns, esvio_fe_event* dst, size_t dst_cap, int dst_space, esvio_fe_text_info* info) {
+  if (!c) return ESVIO_FE_EINVAL;
+  const char* who = "decode_text";
+  if (cam != 0 && cam != 1) return fail(c, ESVIO_FE_EINVAL, "%s: cam must be 0 or 1 (got %d)", who, cam);
+  text_info_clear(info, c->text.st[cam]);
+  if (int rc = text_args_check(c, who, fmt, bytes, n_bytes, space, t_offset_ns)) return rc;
+  if (int rc = dst_check(c, who, "dst", dst, dst_cap, dst_space)) return rc;
+  if (!text_active(c, cam, *fmt, n_bytes)) return 0;
+  HIPCHK(c, hipSetDevice(c->dev));
+  TextJob job[2];
+  job[0].bytes = bytes, job[0].n_bytes = n_bytes, job[0].active = true;
+  auto place = [&](const size_t want[2], DecodedCam dc[2]) -> int {
+    const size_t room = std::min(dst_cap, want[0]);
+    if (dst_space == ESVIO_FE_DEVICE) {  // the caller's own buffer, as it is
+      dc[0].d = (EventRec*)dst, dc[0].cap = room;
+      return 0;
+    }
+    if (int rc = dec_scratch(c, cam, std::max<size_t>(room, 1), &dc[0])) return rc;
+    dc[0].cap = room;
+    return 0;
+  };
+  const int cam_of[2] = {cam, cam};
+  TextResult r[2] = {};
+  DecodedCam dc[2];
+  if (int rc = text_run(c, *fmt, space, t_offset_ns, job, cam_of, place, r, dc)) return rc;
+  text_info_fill(info, r[0]);
+  if (int rc = text_malformed_check(c, who, *fmt, r, 1, "the camera's state is")) return rc;
+  if (dc[0].bad)
+    return fail(c, ESVIO_FE_EINVAL, "%s: %llu of %zu events have a stamp outside [0, 2^32 s); the camera's state is as it was", who, dc[0].bad,
+                dc[0].events);
+  if (dc[0].events > dst_cap)
+    return fail(c, ESVIO_FE_EINVAL, "%s: the chunk holds %zu events, dst has room for %zu; the camera's state is as it was", who, dc[0].events,
+                dst_cap);
+  if (dst_space == ESVIO_FE_HOST) {
+    void* to = dst;
+    if (int rc = deliver_host(c, 1, &to, dc)) return rc;
+  }
+  c->text.st[cam] = job[0].st;
+  text_info_done(info, r[0], job[0].st);
+  return 0;
+}
+
+int esvio_fe_track_text(esvio_fe_handle c, const esvio_fe_text_format* fmt, const void* left, size_t left_bytes, const void* right,
+                        size_t right_bytes, int space, int64_t t_offset_ns, int pub_this_frame, const esvio_fe_filter_params* filter,
+                        const esvio_fe_motion* motion, esvio_fe_tracks* out, esvio_fe_batch_info* info_out, esvio_fe_text_info text[2]) {
+  if (!c) return ESVIO_FE_EINVAL;
+  if (info_out) *info_out = esvio_fe_batch_info{};
+  const void* src[2] = {left, right};
+  const size_t nb[2] = {left_bytes, right_bytes};
+  for (int cam = 0; cam < 2; cam++) {
+    if (text) text_info_clear(&text[cam], c->text.st[cam]);
+    if (int rc = text_args_check(c, cam ? "track_text (right)" : "track_text (left)", fmt, src[cam], nb[cam], space, t_offset_ns)) return rc;
+  }
+  if (filter)
+    if (int rc = baf_prm_check(c, filter, "track_text")) return rc;
+  if (!c->announced.empty() || !c->inflight.empty())
+    return fail(c, ESVIO_FE_EINVAL, "track_text: batches are announced on this handle (decode into memory of your own)");
+  TextJob job[2];
+  for (int cam = 0; cam < 2; cam++) job[cam].bytes = src[cam], job[cam].n_bytes = nb[cam], job[cam].active = text_active(c, cam, *fmt, nb[cam]);
+  if (!job[0].active && !job[1].active) return 0;  // nothing to decode: no left event, nothing tracked
+  HIPCHK(c, hipSetDevice(c->dev));
+  auto place = [&](const size_t want[2], DecodedCam dc[2]) { return track_place(c, filter != nullptr, want, dc); };
+  const int cam_of[2] = {0, 1};
+  TextResult r[2] = {};
+  DecodedCam dc[2];
+  if (int rc = text_run(c, *fmt, space, t_offset_ns, job, cam_of, place, r, dc)) return rc;
+  for (int cam = 0; cam < 2; cam++)
+    if (text && job[cam].active) text_info_fill(&text[cam], r[cam]);
+  if (int rc = text_malformed_check(c, "track_text", *fmt, r, 2, "nothing was tracked, both cameras' states are")) return rc;
+  return track_decoded(c, "track_text", "text states", dc, filter, motion, pub_this_frame, out, info_out, [&] {
+    for (int cam = 0; cam < 2; cam++)
+      if (job[cam].active) {
+        c->text.st[cam] = job[cam].st;
+        if (text) text_info_done(&text[cam], r[cam], job[cam].st);
+      }
+  });
+}
+
+int esvio_fe_text_imu(const void* bytes, size_t n, int64_t t_offset_ns, esvio_fe_imu_sample* out, size_t cap, size_t* n_out) {
+  const int64_t lim = (int64_t)1 << 62;
+  if (!n_out || (n && !bytes) || (cap && !out) || t_offset_ns > lim || t_offset_ns < -lim) return ESVIO_FE_EINVAL;
+  return tx::parse_imu((const uint8_t*)bytes, n, t_offset_ns, (tx::ImuSample*)out, cap, n_out) ? ESVIO_FE_EINVAL : ESVIO_FE_OK;
+}
+int esvio_fe_text_images(const void* bytes, size_t n, int64_t t_offset_ns, int64_t* stamps_ns, uint64_t* path_off, uint32_t* path_len,
+                         size_t cap, size_t* n_out) {
+  const int64_t lim = (int64_t)1 << 62;
+  if (!n_out || (n && !bytes) || (cap && (!stamps_ns || !path_off || !path_len)) || t_offset_ns > lim || t_offset_ns < -lim) return ESVIO_FE_EINVAL;
+  return tx::parse_images((const uint8_t*)bytes, n, t_offset_ns, stamps_ns, path_off, path_len, cap, n_out) ? ESVIO_FE_EINVAL : ESVIO_FE_OK;
+}
+int esvio_fe_text_limits(esvio_fe_text_limits_info* out) {
+  if (!out) return ESVIO_FE_EINVAL;
+  *out = esvio_fe_text_limits_info{(int32_t)kTextTileBytes, (int32_t)tx::kMaxBody, (int32_t)tx::kMaxTail, 0};
+  return 0;
+}
+int esvio_fe_text_kernel_count(void) { return kTextKernels; }
+const char* esvio_fe_text_kernel_name(int which) { return which >= 0 && which < kTextKernels ? kTextKernelNames[which] : ""; }
+int esvio_fe_text_kernel_stats(esvio_fe_handle c, int which, double* total_ms, uint64_t* launches, uint64_t* alg_bytes) {
+  if (!c || which < 0 || which >= kTextKernels) return ESVIO_FE_EINVAL;
+  if (c->prof_on) resolve_profile(c);
+  const KStat& s = c->stats[K_TEXT_COUNT + which];
+  if (total_ms) *total_ms = s.ms;
+  if (launches) *launches = s.launches;
+  if (alg_bytes) *alg_bytes = s.bytes;
+  return 0;
+}
+
 // ---- libcaer / AEDAT 3.1 packet streams (the rule: include/esvio_fe.h; the host walk: fe_aedat.h; the chain: fe_kernels.h)
 namespace {
 namespace ae = esvio::aedat;
@@ -2746,7 +3017,7 @@ namespace {
 int bag_image_reserve(esvio_fe_ctx* c);
 int aedat_frame_reserve(esvio_fe_ctx* c);
 void bag_image_state_reset(esvio_fe_ctx* c);
-void decode_state_reset(esvio_fe_ctx* c) { raw_state_reset(c), aedat_state_reset(c), bag_state_reset(c), bag_image_state_reset(c); }
+void decode_state_reset(esvio_fe_ctx* c) { raw_state_reset(c), aedat_state_reset(c), bag_state_reset(c), bag_image_state_reset(c), text_state_reset(c); }
 }  // namespace
 
 int esvio_fe_decode_reset(esvio_fe_handle c) {
@@ -3161,7 +3432,7 @@ void feed_info_fill(esvio_fe_feed_info* info, const FeedCam& fc, uint64_t append
   info->appended = appended, info->rejected = rejected, info->bad = bad, info->closed = closed, info->queued = fc.win.size();
 }
 
-enum FeedKind { FEED_EVENTS, FEED_FIELDS, FEED_RAW, FEED_AEDAT };
+enum FeedKind { FEED_EVENTS, FEED_FIELDS, FEED_RAW, FEED_AEDAT, FEED_TEXT };
 struct FeedSrc {
   FeedKind kind;
   const esvio_fe_event* ev = nullptr;
@@ -3170,8 +3441,9 @@ struct FeedSrc {
   int format = 0;
   const void* words = nullptr;
   size_t n_bytes = 0;
-  int64_t t_offset_us = 0;  // FEED_AEDAT: nanoseconds
+  int64_t t_offset_us = 0;  // FEED_AEDAT, FEED_TEXT: nanoseconds
   uint32_t flags = 0;       // FEED_AEDAT
+  const esvio_fe_text_format* text = nullptr;  // FEED_TEXT
   int space = 0;
 };
 
@@ -3190,12 +3462,14 @@ int feed_push(esvio_fe_ctx* c, const char* who, int cam, const FeedSrc& src, esv
     if (int rc = fields_check(c, src.fields, src.n, who)) return rc;
   } else if (src.kind == FEED_AEDAT) {
     if (int rc = aedat_args_check(c, who, src.words, src.n_bytes, src.t_offset_us, src.flags)) return rc;
+  } else if (src.kind == FEED_TEXT) {
+    if (int rc = text_args_check(c, who, src.text, src.words, src.n_bytes, src.space, src.t_offset_us)) return rc;
   } else if (int rc = raw_args_check(c, who, src.format, src.words, src.n_bytes, src.space, src.t_offset_us)) {
     return rc;
   }
-  const bool byte_src = src.kind == FEED_RAW || src.kind == FEED_AEDAT;
+  const bool byte_src = src.kind == FEED_RAW || src.kind == FEED_AEDAT || src.kind == FEED_TEXT;
   if (!byte_src && src.n >= (1ull << 30)) return fail(c, ESVIO_FE_EINVAL, "%s: chunk too large", who);
-  if (byte_src ? !src.n_bytes : !src.n) return 0;
+  if (src.kind == FEED_TEXT ? !text_active(c, cam, *src.text, src.n_bytes) : byte_src ? !src.n_bytes : !src.n) return 0;
   AedatJob ajob[2];
   if (src.kind == FEED_AEDAT) {  // (every header checked before any device work)
     ajob[0].bytes = src.words, ajob[0].n_bytes = src.n_bytes;
@@ -3233,6 +3507,14 @@ int feed_push(esvio_fe_ctx* c, const char* who, int cam, const FeedSrc& src, esv
     auto place = [&](const size_t want[2], DecodedCam to[2]) { return put(want[0], &to[0]); };
     AedatResult ar[2] = {};
     if (int rc = aedat_run(c, src.t_offset_us, src.flags, ajob, cam_of, place, ar, dc)) return rc;
+  }
+  TextJob tjob[2];
+  if (src.kind == FEED_TEXT) {
+    tjob[0].bytes = src.words, tjob[0].n_bytes = src.n_bytes, tjob[0].active = true;
+    auto place = [&](const size_t want[2], DecodedCam to[2]) { return put(want[0], &to[0]); };
+    TextResult tr[2] = {};
+    if (int rc = text_run(c, *src.text, src.space, src.t_offset_us, tjob, cam_of, place, tr, dc)) return rc;
+    if (int rc = text_malformed_check(c, who, *src.text, tr, 1, "nothing was appended, the camera's state is")) return rc;
   }
   if (byte_src) {
     if (dc[0].bad) {
@@ -3294,6 +3576,7 @@ int feed_push(esvio_fe_ctx* c, const char* who, int cam, const FeedSrc& src, esv
   }
   if (src.kind == FEED_RAW) raw_commit(c, cam, raw_res[0]);
   if (src.kind == FEED_AEDAT) c->aedat.ev_st[cam] = ajob[0].st;
+  if (src.kind == FEED_TEXT) c->text.st[cam] = tjob[0].st;
   const uint64_t at = fc.pos0 + fc.len;
   for (uint64_t j = 0; j < si.closed; j++) {
     const SliceBound e = slice_bound(c, cam, first_window + j);
@@ -3355,6 +3638,14 @@ int esvio_fe_feed_push_raw(esvio_fe_handle c, int cam, int format, const void* w
   FeedSrc src{FEED_RAW};
   src.format = format, src.words = words, src.n_bytes = n_bytes, src.t_offset_us = t_offset_us, src.space = space;
   return feed_push(c, "feed_push_raw", cam, src, info);
+}
+
+int esvio_fe_feed_push_text(esvio_fe_handle c, int cam, const esvio_fe_text_format* fmt, const void* bytes, size_t n_bytes, int space,
+                            int64_t t_offset_ns, esvio_fe_feed_info* info) {
+  if (!c) return ESVIO_FE_EINVAL;
+  FeedSrc src{FEED_TEXT};
+  src.text = fmt, src.words = bytes, src.n_bytes = n_bytes, src.t_offset_us = t_offset_ns, src.space = space;
+  return feed_push(c, "feed_push_text", cam, src, info);
 }
 
 int esvio_fe_feed_push_aedat(esvio_fe_handle c, int cam, const void* bytes, size_t n_bytes, int64_t t_offset_ns, uint32_t flags,
@@ -4183,6 +4474,7 @@ int esvio_fe_reserve(esvio_fe_handle c, size_t max_left, size_t max_right, int h
   // a handle that has used an ingest stage: the stage's scratch for chunks of max_left and max_right events
   const size_t events[2] = {max_left, max_right};
   if (int rc = raw_reserve(c, events, host_batches != 0)) return rc;
+  if (int rc = text_reserve(c, events, host_batches != 0)) return rc;
   if (int rc = aedat_reserve(c, events)) return rc;
   if (int rc = bag_reserve(c, events)) return rc;
   if (int rc = bag_image_reserve(c)) return rc;

@@ -36,6 +36,7 @@
 #include "fe_layout.h"
 #include "fe_mc.h"
 #include "fe_res.h"
+#include "fe_text.h"
 
 using namespace esvio;
 
@@ -111,19 +112,22 @@ struct PhaseClock {
 // ... and behind those loop detection's four (esvio_fe_bow_kernel_count / _name / _stats)
 // ... and behind those the AEDAT frames' one, k_frame16_emit (esvio_fe_aedat_frame_kernel_stats)
 // ... and behind that vocabulary creation's (esvio_fe_bow_create_kernel_count / _name / _stats)
+// ... and behind those the text stage's three (esvio_fe_text_kernel_count / _name / _stats)
 enum { K_EVIMG_MARK = K_INGEST_COUNT, K_EVIMG_EMIT, K_KF_BLUR, K_KF_BRIEF, K_KF_MATCH, K_BOW_WALK, K_BOW_VECTOR, K_BOW_SCORE,
        K_BOW_SELECT, K_FRAME16_EMIT, K_VOC_FIRST, K_VOC_MINDIST, K_VOC_SCAN_REDUCE, K_VOC_SCAN_TOP, K_VOC_SCAN_DOWN, K_VOC_DRAW,
        K_VOC_PICK, K_VOC_ASSIGN, K_VOC_COUNT_BIG, K_VOC_MEAN_BIG, K_VOC_MEAN_SMALL, K_VOC_CHILD_COUNT, K_VOC_REGROUP_KEYS,
-       K_VOC_DOC_COUNT, K_ALL_COUNT };
+       K_VOC_DOC_COUNT, K_TEXT_COUNT, K_TEXT_PLACE, K_TEXT_EMIT, K_ALL_COUNT };
 constexpr int kKfKernels = K_BOW_WALK - K_KF_BLUR;
 const char* const kKfKernelNames[kKfKernels] = {"k_kf_blur", "k_kf_brief", "k_kf_match"};
 constexpr int kBowKernels = K_FRAME16_EMIT - K_BOW_WALK;
 const char* const kBowKernelNames[kBowKernels] = {"k_bow_walk", "k_bow_vector", "k_bow_score", "k_bow_select"};
-constexpr int kVocKernels = K_ALL_COUNT - K_VOC_FIRST;
+constexpr int kVocKernels = K_TEXT_COUNT - K_VOC_FIRST;
 const char* const kVocKernelNames[kVocKernels] = {
     "k_voc_first", "k_voc_mindist", "k_voc_scan_reduce", "k_voc_scan_top", "k_voc_scan_down", "k_voc_draw", "k_voc_pick",
     "k_voc_assign", "k_voc_count_big", "k_voc_mean_big", "k_voc_mean_small", "k_voc_child_count", "k_voc_regroup_keys",
     "k_voc_doc_count"};
+constexpr int kTextKernels = K_ALL_COUNT - K_TEXT_COUNT;
+const char* const kTextKernelNames[kTextKernels] = {"k_text_count", "k_text_place", "k_text_emit"};
 
 struct KStat {
   double ms = 0;
@@ -619,6 +623,21 @@ struct esvio_fe_ctx {
     DevBuf<uint8_t> d_img, d_gray;
     bool img_used = false;    // esvio_fe_reserve grows the scratch of a handle that has decoded images before
   } bag;
+
+  // ---- esvio_fe_decode_text / esvio_fe_track_text / esvio_fe_feed_push_text: text event files (include/esvio_fe.h has
+  // the rule, fe_text.h the classifier and the carry step, fe_kernels.h the chain).  st: each camera's state — the
+  // unterminated tail, or "inside an overlong line" — on the HOST: it travels to the launches as an argument; the state
+  // behind a call comes from the carry step for a host chunk and from the camera's result block for a device chunk, and
+  // is taken over only once the call is known to succeed.  Allocated on first use and the stage's own (main stream
+  // only), one per camera: src, the copy of a host source that is not read in place; sums, the tiles' counts; res, the
+  // two result blocks.  The records behind a host dst, and in front of a filter, are rawdec.dec's.
+  struct Text {
+    esvio::text::State st[2];
+    DevBuf<uint8_t> src[2];
+    DevBuf<TextTile> sums[2];
+    DevBuf<TextResult> res;
+    bool used = false;  // esvio_fe_reserve grows the scratch of a handle that has decoded text before
+  } text;
 
   // ---- esvio_fe_slice_events: a record stream cut into fixed-rate windows (include/esvio_fe.h has the rule,
   // fe_kernels.h the chain).  st: each camera's state, kept on the HOST like the decoder's: the device works on counts

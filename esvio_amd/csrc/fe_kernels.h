@@ -766,6 +766,65 @@ struct BagArgs {
 };
 void launch_bag_emit(hipStream_t s, const BagArgs& a);
 
+// ---- text event files: "t x y p" / "x y p t" lines -> event records (esvio_fe_decode_text, esvio_fe_track_text) ----
+// include/esvio_fe.h "text event files" holds the rule, fe_text.h the line classifier both sides share.  The VIRTUAL
+// STREAM of a camera is its carried tail (at most 65 bytes, a by-value argument) followed by the chunk; a line belongs
+// to the tile of kTextTileBytes virtual bytes in which it STARTS, and a byte starts a line when the byte in front of it
+// is '\n' (virtual byte 0: unless the carried state is "inside an overlong line").  The chain is the raw decoder's:
+//   k_text_count  stages the tile, one byte in front of it and a halo of one maximal line (kTextHalo) in LDS with
+//                 16-byte loads, compacts the tile's line starts with ballots, one lane classifies one line out of LDS;
+//                 per tile the classes' counts, the least malformed line start and the tile's last '\n'
+//   k_text_place  one workgroup per camera: the tiles' exclusive event prefixes, the totals, the corrections only the
+//                 whole stream can decide (the line an earlier call left overlong; an overlong line no '\n' follows),
+//                 the state behind the call
+//   k_text_emit   the same staging and the same classifier; an event line's rank among the tile's event lines by
+//                 ballots, one 16-byte store at dst[prefix + rank]
+// Three launches for one camera or for both: both cameras' tiles share each grid.  No workgroup waits for another.
+// Their timer slots lie behind every other table (fe_ctx.h).
+constexpr uint32_t kTextTileBytes = 4096;  // 256 lanes x 16 bytes
+constexpr uint32_t kTextHalo = 66;         // a body of 64 bytes, '\r', '\n'
+struct TextTile {      // k_text_count per tile; k_text_place turns `events` into the exclusive prefix
+  uint32_t events;     // event lines, the BAD ones among them
+  uint32_t comments, blank, malformed, bad;
+  uint32_t last_nl;    // the virtual position behind the tile's last '\n'; 0: it holds none
+  uint32_t first_mal;  // the virtual position of the tile's first malformed line; 0xffffffff: none
+  uint32_t pad;
+};
+static_assert(sizeof(TextTile) == 32, "TextTile layout");
+struct TextCarry {  // the state between two calls (fe_text.h: State) as the kernels take and leave it
+  unsigned long long tail_w[9];  // the tail's bytes, little-endian in 64-bit words (72 >= 65)
+  unsigned long long skip_len;
+  uint32_t len, skip;
+};
+static_assert(sizeof(TextCarry) == 88, "TextCarry layout");
+struct TextResult {  // k_text_place; first_t .. last_nsec: k_text_emit (untouched if no event or a BAD first / last one)
+  unsigned long long events, comments, blank, malformed, bad;
+  long long first_malformed;  // relative to the chunk's first byte; valid if malformed
+  long long first_t, last_t;  // ticks, nanoseconds
+  uint32_t last_sec, last_nsec;
+  TextCarry state;            // behind the call
+};
+static_assert(sizeof(TextResult) == 160, "TextResult layout");
+struct TextCam {
+  const uint8_t* bytes;  // the chunk, device-readable, any alignment
+  uint32_t n_bytes;
+  uint32_t tiles;        // max(1, ceil((carry.len + n_bytes) / kTextTileBytes)); 0: the camera takes no part
+  TextCarry carry;       // the state in front of the call
+  uint32_t end;          // ESVIO_FE_TEXT_END: an unterminated last line is a line
+  uint32_t dst_cap;
+  long long t_offset;    // nanoseconds
+  TextTile* sums;        // [tiles]
+  EventRec* dst;         // [dst_cap]; nothing is stored when the call's events exceed dst_cap
+  TextResult* res;
+};
+struct TextArgs {
+  int order, time;  // esvio::text::kTxyp / kXypt, kSecDecimal / kIntUs / kIntNs
+  TextCam cam[2];   // the grid's blocks: cam[0].tiles, then cam[1].tiles
+};
+void launch_text_count(hipStream_t s, const TextArgs& a);
+void launch_text_place(hipStream_t s, const TextArgs& a);
+void launch_text_emit(hipStream_t s, const TextArgs& a);
+
 // ---- rosbag images: sensor_msgs/Image payloads -> dense 8-bit gray (esvio_fe_decode_bag_images, esvio_fe_convert_image) ----
 // include/esvio_fe.h holds the rule.  The host has walked the records (fe_bag.h): what arrives here is a table of image
 // descriptors — where the payload's first row lies, its row stride, its encoding class, where the dense width x height

@@ -7,6 +7,7 @@
 // tree); OpenCV-internal arithmetic is marked [OpenCV].
 #include "fe_kernels.h"
 #include "fe_mc.h"
+#include "fe_text.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -6726,6 +6727,280 @@ void launch_voc_regroup_keys(hipStream_t s, const VocArgs& a, const uint32_t* sl
 void launch_voc_doc_count(hipStream_t s, const uint32_t* keys, const uint32_t* vals, uint32_t n, const int64_t* doc_off,
                           uint32_t n_docs, uint32_t n_words, uint32_t* ni) {
   if (n) launch_k(k_voc_doc_count, voc_grid(n), dim3(256), 0, s, keys, vals, n, doc_off, n_docs, n_words, ni);
+}
+
+// ============================================================================ text event files
+// "t x y p" / "x y p t" lines -> event records (fe_kernels.h has the chain, include/esvio_fe.h the rule, fe_text.h the
+// classifier).  Positions are VIRTUAL: the carried tail's bytes, then the chunk's.
+//   text_tail_byte   a byte of the carried tail: the by-value argument's words, picked with constant indices
+//   text_byte        a virtual byte from wherever it lies (k_text_place: the few bytes of the new tail)
+//   text_tile_lines  stages the tile in LDS and compacts its line starts: what count and emit share
+//   text_line        one lane, one line: where it ends, its class, its fields
+namespace {
+constexpr uint32_t kTextLdsBytes = (kTextTileBytes + kTextHalo + 16 + 15 + 15) / 16 * 16;  // the byte in front, both alignments' slack
+constexpr int kTextNoLine = -1;  // an unterminated last line without END: the tail, no line of this call
+struct TextLds {
+  uint4 bytes[kTextLdsBytes / 16];
+  uint16_t starts[kTextTileBytes];  // the tile's line starts, relative to the tile, ascending
+  uint32_t cnt[64];                 // line starts per (round, wave); then their exclusive prefixes
+  uint32_t n_lines;
+};
+__device__ __forceinline__ uint32_t text_tail_byte(const TextCarry& t, uint32_t i) {
+  unsigned long long w = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < 9; k++)
+    if ((i >> 3) == k) w = t.tail_w[k];
+  return (uint32_t)(w >> ((i & 7u) * 8u)) & 0xffu;
+}
+__device__ __forceinline__ uint32_t text_byte(const TextCam& c, uint32_t v) {
+  return v < c.carry.len ? text_tail_byte(c.carry, v) : (uint32_t)c.bytes[v - c.carry.len];
+}
+__device__ __forceinline__ const TextCam& text_block_cam(const TextArgs& a, uint32_t* tile) {
+  const uint32_t b = blockIdx.x;
+  *tile = b < a.cam[0].tiles ? b : b - a.cam[0].tiles;
+  return b < a.cam[0].tiles ? a.cam[0] : a.cam[1];
+}
+// Behind it (and its barriers): L.bytes holds the virtual bytes [*lds0, *lds0 + kTextLdsBytes) that exist (zeros where
+// the stream has none), *lds0 <= tile_base - 1; L.starts[0, L.n_lines) the tile's line starts.  The window begins at a
+// 16-byte boundary of the chunk's ADDRESSES, so every vector that lies inside the chunk is one aligned 16-byte load.
+__device__ __forceinline__ void text_tile_lines(const TextCam& c, uint32_t tile, TextLds& L, int32_t* lds0) {
+  const uint32_t N = c.carry.len + c.n_bytes, base = tile * kTextTileBytes;
+  const uint32_t tid = threadIdx.x, wave = tid >> 6;
+  const long long first = (long long)base - 1 - (long long)c.carry.len;  // the chunk offset of the byte in front of the tile
+  const uintptr_t g = (uintptr_t)c.bytes + (uintptr_t)first;              // (modulo 2^64: only its low bits are used)
+  const long long w0 = first - (long long)(g & 15u);                      // the window's first byte as a chunk offset
+  *lds0 = (int32_t)(w0 + (long long)c.carry.len);
+  for (uint32_t j = tid; j < kTextLdsBytes / 16; j += 256) {
+    const long long cc = w0 + 16ll * j;
+    uint4 q = make_uint4(0u, 0u, 0u, 0u);
+    if (cc >= 0 && cc + 16 <= (long long)c.n_bytes) {
+      q = *(const uint4*)(c.bytes + cc);
+    } else if (cc + 16 > -(long long)c.carry.len && cc < (long long)c.n_bytes) {  // the chunk's ends, the tail
+      uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+      for (int k = 0; k < 16; k++) {
+        const long long at = cc + k;
+        uint32_t byte = 0;
+        if (at >= 0 && at < (long long)c.n_bytes)
+          byte = c.bytes[at];
+        else if (at < 0 && at + (long long)c.carry.len >= 0)
+          byte = text_tail_byte(c.carry, (uint32_t)(at + (long long)c.carry.len));
+        w[k >> 2] |= byte << ((k & 3) * 8);
+      }
+      q = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+    L.bytes[j] = q;
+  }
+  __syncthreads();
+  const uint8_t* lds = (const uint8_t*)L.bytes;
+  const uint32_t stop = min(base + kTextTileBytes, N);
+  uint32_t mine = 0;  // bit r: this lane's byte of round r starts a line
+#pragma unroll
+  for (uint32_t r = 0; r < kTextTileBytes / 256; r++) {
+    const uint32_t v = base + r * 256 + tid;
+    const bool start = v < stop && (v == 0 ? c.carry.skip == 0 : lds[(int32_t)v - 1 - *lds0] == '\n');
+    const lanemask_t m = bal(start);
+    if (start) mine |= 1u << r;
+    if (lane_id() == 0) L.cnt[r * 4 + wave] = (uint32_t)__popcll(m);
+  }
+  __syncthreads();
+  if (wave == 0) {  // the 64 counts' exclusive prefixes, in position order
+    const uint32_t own = L.cnt[tid];
+    uint32_t incl = own;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint32_t up = __shfl_up(incl, o);
+      if ((int)tid >= o) incl += up;
+    }
+    L.cnt[tid] = incl - own;
+    if (tid == 63) L.n_lines = incl;
+  }
+  __syncthreads();
+#pragma unroll
+  for (uint32_t r = 0; r < kTextTileBytes / 256; r++) {
+    const bool start = (mine >> r) & 1u;
+    const lanemask_t m = bal(start);
+    if (start) L.starts[L.cnt[r * 4 + wave] + (uint32_t)__popcll(m & (((lanemask_t)1 << lane_id()) - 1))] = (uint16_t)(r * 256 + tid);
+  }
+  __syncthreads();
+}
+// the line that starts at virtual position s: its class (kTextNoLine: the unterminated tail), its fields
+__device__ __forceinline__ int text_line(const TextArgs& a, const TextCam& c, const uint8_t* p, uint32_t s, esvio::text::Line* out) {
+  const uint32_t N = c.carry.len + c.n_bytes;
+  const uint32_t room = min(kTextHalo, N - s);
+  uint32_t j = 0;
+  while (j < room && p[j] != '\n') j++;
+  if (j == room) {                                             // no terminator in sight
+    if (N - s >= kTextHalo) return esvio::text::kMalformed;     // the body has passed 64 bytes
+    if (!c.end) return kTextNoLine;
+  } else if (j && p[j - 1] == '\r') {
+    j--;
+  }
+  return esvio::text::classify(p, j, a.order, a.time, c.t_offset, out);
+}
+}  // namespace
+
+__global__ __launch_bounds__(256) void k_text_count(TextArgs a) {
+  __shared__ TextLds L;
+  __shared__ uint32_t tot[8];  // events, comments, blank, malformed, bad, last_nl, first_mal
+  uint32_t tile;
+  const TextCam& c = text_block_cam(a, &tile);
+  const uint32_t tid = threadIdx.x;
+  if (tid < 8) tot[tid] = tid == 6 ? 0xffffffffu : 0u;
+  int32_t lds0;
+  text_tile_lines(c, tile, L, &lds0);
+  const uint8_t* lds = (const uint8_t*)L.bytes;
+  const uint32_t N = c.carry.len + c.n_bytes, base = tile * kTextTileBytes, stop = min(base + kTextTileBytes, N);
+  uint32_t last_nl = 0;
+  for (uint32_t v = base + tid; v < stop; v += 256)
+    if (lds[(int32_t)v - lds0] == '\n') last_nl = v + 1;
+  if (last_nl) atomicMax(&tot[5], last_nl);
+  const uint32_t n_lines = L.n_lines;
+  for (uint32_t i = tid; i < n_lines; i += 256) {
+    const uint32_t s = base + L.starts[i];
+    esvio::text::Line l;
+    const int cls = text_line(a, c, lds + ((int32_t)s - lds0), s, &l);
+    if (cls == kTextNoLine) continue;
+    atomicAdd(&tot[cls <= esvio::text::kBad ? 0 : cls - 1], 1u);  // (a BAD line is an event line)
+    if (cls == esvio::text::kBad) atomicAdd(&tot[4], 1u);
+    if (cls == esvio::text::kMalformed) atomicMin(&tot[6], s);
+  }
+  __syncthreads();
+  if (tid == 0) {
+    TextTile t;
+    t.events = tot[0], t.comments = tot[1], t.blank = tot[2], t.malformed = tot[3], t.bad = tot[4];
+    t.last_nl = tot[5], t.first_mal = tot[6], t.pad = 0;
+    c.sums[tile] = t;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_text_place(TextArgs a) {
+  __shared__ unsigned long long tot[4];  // comments, blank, malformed, bad
+  __shared__ uint32_t part[4], last_nl_s, first_mal_s, tail_from, tail_len;
+  const TextCam& c = a.cam[blockIdx.x];
+  if (!c.tiles) return;
+  const uint32_t tid = threadIdx.x;
+  if (tid < 4) tot[tid] = 0;
+  if (tid == 0) last_nl_s = 0, first_mal_s = 0xffffffffu, tail_from = 0, tail_len = 0;
+  __syncthreads();
+  const uint32_t per = (c.tiles + 255u) / 256u;
+  const uint32_t lo = min(tid * per, c.tiles), hi = min(lo + per, c.tiles);
+  uint32_t sum = 0, last_nl = 0, first_mal = 0xffffffffu;
+  unsigned long long cnt[4] = {0, 0, 0, 0};
+  for (uint32_t j = lo; j < hi; j++) {
+    const TextTile t = c.sums[j];
+    sum += t.events;
+    cnt[0] += t.comments, cnt[1] += t.blank, cnt[2] += t.malformed, cnt[3] += t.bad;
+    last_nl = max(last_nl, t.last_nl), first_mal = min(first_mal, t.first_mal);
+  }
+#pragma unroll
+  for (int k = 0; k < 4; k++)
+    if (cnt[k]) atomicAdd(&tot[k], cnt[k]);
+  if (last_nl) atomicMax(&last_nl_s, last_nl);
+  if (first_mal != 0xffffffffu) atomicMin(&first_mal_s, first_mal);
+  uint32_t incl = sum;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t v = __shfl_up(incl, o);
+    if (lane_id() >= o) incl += v;
+  }
+  if (lane_id() == 63) part[tid >> 6] = incl;
+  __syncthreads();
+  uint32_t run = incl - sum;
+  for (int wv = 0; wv < (int)(tid >> 6); wv++) run += part[wv];
+  for (uint32_t j = lo; j < hi; j++) {
+    const uint32_t e = c.sums[j].events;
+    c.sums[j].events = run;
+    run += e;
+  }
+  TextResult* r = c.res;
+  if (tid == 255) r->events = run;  // (the chunks behind the last tile are empty: this lane's run is the whole call)
+  if (tid == 0) {  // what only the whole stream decides, and the state behind the call
+    const uint32_t N = c.carry.len + c.n_bytes, from = last_nl_s;
+    const bool still_skipping = c.carry.skip && from == 0;  // the overlong line of an earlier call has not ended yet
+    unsigned long long malformed = tot[2];
+    long long first = (long long)first_mal_s - (long long)c.carry.len;
+    if (c.carry.skip && (from != 0 || c.end)) malformed++, first = -(long long)c.carry.skip_len;  // it ends here
+    const uint32_t Lr = N - from;
+    const uint32_t last = Lr ? text_byte(c, N - 1) : 0u;
+    uint32_t skip = 0, len = 0;
+    unsigned long long skip_len = 0;
+    if (!c.end) {
+      if (still_skipping) {
+        skip = 1, skip_len = c.carry.skip_len + N;
+      } else if (esvio::text::overlong(Lr, (uint8_t)last)) {
+        skip = 1, skip_len = Lr;
+        if (Lr >= kTextHalo) malformed--;  // its tile counted it: no '\n' follows, it is no line of this call yet
+      } else {
+        len = Lr;
+      }
+    }
+    r->comments = tot[0], r->blank = tot[1], r->malformed = malformed, r->bad = tot[3];
+    r->first_malformed = first;
+    r->state.len = len, r->state.skip = skip, r->state.skip_len = skip_len;
+    tail_from = from, tail_len = len;
+  }
+  __syncthreads();
+  if (tid < 9) {  // the new tail, a word per lane
+    unsigned long long w = 0;
+    for (uint32_t k = 0; k < 8; k++) {
+      const uint32_t i = tid * 8 + k;
+      if (i < tail_len) w |= (unsigned long long)text_byte(c, tail_from + i) << (k * 8);
+    }
+    r->state.tail_w[tid] = w;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_text_emit(TextArgs a) {
+  __shared__ TextLds L;
+  __shared__ uint32_t part[2][4];
+  uint32_t tile;
+  const TextCam& c = text_block_cam(a, &tile);
+  const uint32_t tid = threadIdx.x, wave = tid >> 6;
+  int32_t lds0;
+  text_tile_lines(c, tile, L, &lds0);
+  const uint8_t* lds = (const uint8_t*)L.bytes;
+  const uint32_t base = tile * kTextTileBytes, n_lines = L.n_lines;
+  const unsigned long long total = c.res->events;
+  uint32_t run = c.sums[tile].events;  // the rank of the tile's first event line
+  for (uint32_t i0 = 0, pass = 0; i0 < n_lines; i0 += 256, pass++) {  // (uniform: the barrier inside is reached by all)
+    const uint32_t i = i0 + tid;
+    esvio::text::Line l{};
+    int cls = kTextNoLine;
+    if (i < n_lines) {
+      const uint32_t s = base + L.starts[i];
+      cls = text_line(a, c, lds + ((int32_t)s - lds0), s, &l);
+    }
+    const bool ev = cls == esvio::text::kEvent || cls == esvio::text::kBad;
+    const lanemask_t m = bal(ev);
+    if (lane_id() == 0) part[pass & 1][wave] = (uint32_t)__popcll(m);
+    __syncthreads();
+    uint32_t rank = run + (uint32_t)__popcll(m & (((lanemask_t)1 << lane_id()) - 1));
+#pragma unroll
+    for (uint32_t w = 0; w < 4; w++) {
+      if (w < wave) rank += part[pass & 1][w];
+      run += part[pass & 1][w];
+    }
+    if (!ev) continue;
+    if (cls == esvio::text::kEvent) {
+      if (rank == 0) c.res->first_t = l.ticks;
+      if (rank + 1ull == total) c.res->last_t = l.ticks, c.res->last_sec = l.sec, c.res->last_nsec = l.nsec;
+    } else {
+      l.sec = l.nsec = 0;
+    }
+    if (total <= c.dst_cap) ((uint4*)c.dst)[rank] = make_uint4(l.x | l.y << 16, l.sec, l.nsec, l.pol);
+  }
+}
+
+static uint32_t text_grid(const TextArgs& a) { return a.cam[0].tiles + a.cam[1].tiles; }
+void launch_text_count(hipStream_t s, const TextArgs& a) {
+  if (text_grid(a)) launch_k(k_text_count, dim3(text_grid(a)), dim3(256), 0, s, a);
+}
+void launch_text_place(hipStream_t s, const TextArgs& a) {
+  if (text_grid(a)) launch_k(k_text_place, dim3(2), dim3(256), 0, s, a);
+}
+void launch_text_emit(hipStream_t s, const TextArgs& a) {
+  if (text_grid(a)) launch_k(k_text_emit, dim3(text_grid(a)), dim3(256), 0, s, a);
 }
 
 }  // namespace esvio

@@ -141,6 +141,41 @@ def raw_bound(fmt, nbytes):
     return nbytes // 2 * 12 if fmt == RAW_EVT3 else nbytes * 4 if fmt == RAW_EVT21 else nbytes // 4
 
 
+class TextFormat(C.Structure):
+    """esvio_fe_text_format"""
+    _fields_ = [("order", C.c_int32), ("time", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class TextInfo(C.Structure):
+    """esvio_fe_text_info"""
+    _fields_ = [("events", C.c_uint64), ("lines", C.c_uint64), ("comments", C.c_uint64), ("blank", C.c_uint64),
+                ("malformed", C.c_uint64), ("bad", C.c_uint64), ("first_malformed", C.c_int64), ("first_t_ns", C.c_int64),
+                ("last_t_ns", C.c_int64), ("carried", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class TextLimits(C.Structure):
+    """esvio_fe_text_limits_info (include/esvio_fe_test.h)"""
+    _fields_ = [("tile_bytes", C.c_int32), ("max_body", C.c_int32), ("max_tail", C.c_int32), ("reserved", C.c_int32)]
+
+
+TEXT_TXYP, TEXT_XYPT = 1, 2                          # esvio_fe_text_format.order
+TEXT_SEC_DECIMAL, TEXT_INT_US, TEXT_INT_NS = 1, 2, 3  # .time
+TEXT_END, TEXT_SKIP_MALFORMED = 1, 2                  # .flags
+
+
+def text_bound(nbytes):
+    """the records a text chunk of nbytes can hold at the most, whatever tail is carried (include/esvio_fe.h)"""
+    return (nbytes + 65) // 8 + 1
+
+
+def _text_src(data):
+    """(pointer, n_bytes, space, keep-alive) of a text chunk: bytes, a contiguous numpy array or a (device_ptr, n_bytes) tuple"""
+    if isinstance(data, tuple):
+        return C.c_void_p(data[0]), int(data[1]), DEVICE, None
+    buf = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data)
+    return (_p(buf) if buf.nbytes else None), buf.nbytes, HOST, buf
+
+
 class Trigger(C.Structure):
     """esvio_fe_trigger"""
     _fields_ = [("sec", C.c_uint32), ("nsec", C.c_uint32), ("id", C.c_uint8), ("value", C.c_uint8), ("_pad", C.c_uint8 * 6)]
@@ -358,6 +393,7 @@ ABI_SYMBOLS = [
     "esvio_fe_bow_vocabulary_header", "esvio_fe_bow_set_vocabulary", "esvio_fe_bow_transform", "esvio_fe_bow_add",
     "esvio_fe_bow_query", "esvio_fe_bow_detect_loop", "esvio_fe_bow_clear", "esvio_fe_bow_entries", "esvio_fe_bow_reserve",
     "esvio_fe_bow_create_vocabulary", "esvio_fe_bow_get_created",
+    "esvio_fe_decode_text", "esvio_fe_track_text", "esvio_fe_feed_push_text", "esvio_fe_text_imu", "esvio_fe_text_images",
 ]
 # test / measurement taps: include/esvio_fe_test.h (not part of the boundary)
 TEST_SYMBOLS = [
@@ -378,6 +414,7 @@ TEST_SYMBOLS = [
     "esvio_fe_kf_kernel_count", "esvio_fe_kf_kernel_name", "esvio_fe_kf_kernel_stats", "esvio_fe_kf_blur_tile",
     "esvio_fe_bow_kernel_count", "esvio_fe_bow_kernel_name", "esvio_fe_bow_kernel_stats", "esvio_fe_bow_limits", "esvio_fe_bow_scores",
     "esvio_fe_bow_create_kernel_count", "esvio_fe_bow_create_kernel_name", "esvio_fe_bow_create_kernel_stats", "esvio_fe_bow_create_pick",
+    "esvio_fe_text_limits", "esvio_fe_text_kernel_count", "esvio_fe_text_kernel_name", "esvio_fe_text_kernel_stats",
 ]
 
 LATENCY_PHASES = 16
@@ -602,6 +639,16 @@ def load_library(build_if_missing=True):
     L.esvio_fe_feed_push_fields.argtypes = [vp, i, C.POINTER(EventFieldsDesc), sz, i, C.POINTER(FeedInfo)]
     L.esvio_fe_feed_push_raw.argtypes = [vp, i, i, vp, sz, i, C.c_int64, C.POINTER(FeedInfo)]
     L.esvio_fe_feed_peek.argtypes = [vp, C.POINTER(FeedWindow)]
+    L.esvio_fe_decode_text.argtypes = [vp, i, C.POINTER(TextFormat), vp, sz, i, C.c_int64, vp, sz, i, C.POINTER(TextInfo)]
+    L.esvio_fe_track_text.argtypes = [vp, C.POINTER(TextFormat), vp, sz, vp, sz, i, C.c_int64, i, C.POINTER(FilterParams),
+                                      C.POINTER(Motion), C.POINTER(Tracks), C.POINTER(BatchInfo), C.POINTER(TextInfo * 2)]
+    L.esvio_fe_feed_push_text.argtypes = [vp, i, C.POINTER(TextFormat), vp, sz, i, C.c_int64, C.POINTER(FeedInfo)]
+    L.esvio_fe_text_imu.argtypes = [vp, sz, C.c_int64, vp, sz, C.POINTER(sz)]
+    L.esvio_fe_text_images.argtypes = [vp, sz, C.c_int64, vp, vp, vp, sz, C.POINTER(sz)]
+    L.esvio_fe_text_limits.argtypes = [C.POINTER(TextLimits)]
+    L.esvio_fe_text_kernel_name.argtypes = [i]
+    L.esvio_fe_text_kernel_name.restype = C.c_char_p
+    L.esvio_fe_text_kernel_stats.argtypes = [vp, i, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     u32 = C.c_uint32
     L.esvio_fe_aedat_header.argtypes = [vp, sz, C.POINTER(AedatHeaderInfo)]
     L.esvio_fe_decode_aedat.argtypes = [vp, i, vp, sz, C.c_int64, u32, vp, sz, i, C.POINTER(AedatInfo)]
@@ -1128,6 +1175,63 @@ class FeatureTracker:
         k = int(info.events)
         return (FilteredEvents(dst, k, None) if device else out[:k]), info
 
+    def decode_text(self, cam, order, time, data, flags=0, t_offset_ns=0, dst_cap=None, device=False):
+        """the text decode stage (esvio_fe_decode_text; include/esvio_fe.h "text event files" has the rule): camera
+        `cam`'s text state advanced by `data` — bytes, a contiguous numpy array or a (device_ptr, n_bytes) tuple; the
+        chunk may end anywhere — of a file with columns `order` (TEXT_TXYP / TEXT_XYPT) and stamps `time`
+        (TEXT_SEC_DECIMAL / TEXT_INT_US / TEXT_INT_NS); flags: TEXT_END | TEXT_SKIP_MALFORMED.  Returns (records,
+        TextInfo) as decode_raw does.  dst_cap None: text_bound(n_bytes).  A failed call raises FrontendError with `.info`."""
+        from .events import EVENT_DTYPE
+        L = self._hd.L
+        ptr, nbytes, space, keep = _text_src(data)
+        if dst_cap is None:
+            dst_cap = text_bound(nbytes)
+        fmt, info = TextFormat(int(order), int(time), int(flags), 0), TextInfo()
+        if device:
+            dst = C.c_void_p()
+            rc = L.esvio_fe_mem_alloc(DEVICE, 16 * max(dst_cap, 1), C.byref(dst))
+            if rc:
+                raise FrontendError("esvio_fe_mem_alloc rc=%d" % rc)
+            out = None
+        else:
+            out = np.zeros(max(int(dst_cap), 1), EVENT_DTYPE)
+            dst = _p(out)
+        rc = L.esvio_fe_decode_text(self._hd.h, int(cam), C.byref(fmt), ptr, nbytes, space, int(t_offset_ns), dst, int(dst_cap),
+                                    DEVICE if device else HOST, C.byref(info))
+        if rc:
+            if device:
+                L.esvio_fe_mem_free(DEVICE, dst)
+            e = FrontendError("rc=%d: %s" % (rc, L.esvio_fe_last_error(self._hd.h).decode()))
+            e.info = info
+            raise e
+        k = int(info.events)
+        return (FilteredEvents(dst, k, None) if device else out[:k]), info
+
+    def track_text(self, order, time, left, right, flags=0, t_offset_ns=0, pub=True, params=None, measurements=None, copy=True):
+        """one chunk of text per camera through esvio_fe_track_text: left / right as decode_text takes them (both in
+        one memory space); params: a FilterParams or None; measurements: an esvio_fe_motion or None.  Returns
+        (BatchInfo, (TextInfo, TextInfo)); a failed call raises FrontendError with `.info` and `.text`."""
+        args, spaces, keep = [], [], []
+        for w in (left, right):
+            ptr, nbytes, space, k = _text_src(w)
+            keep.append(k)
+            args += [ptr, nbytes]
+            if nbytes:
+                spaces.append(space)
+        assert len(set(spaces)) <= 1, "both cameras' chunks lie in one memory space"
+        fmt, info, text = TextFormat(int(order), int(time), int(flags), 0), BatchInfo(), (TextInfo * 2)()
+        rc = self._hd.L.esvio_fe_track_text(self._hd.h, C.byref(fmt), *args, spaces[0] if spaces else HOST, int(t_offset_ns), int(pub),
+                                            C.byref(params) if params is not None else None,
+                                            C.byref(measurements) if measurements is not None else None,
+                                            C.byref(self._tr), C.byref(info), C.byref(text))
+        if rc:
+            e = FrontendError("rc=%d: %s" % (rc, self._hd.L.esvio_fe_last_error(self._hd.h).decode()))
+            e.info, e.text = info, text
+            raise e
+        if info.tracked:
+            self._take(copy)
+        return info, (text[0], text[1])
+
     def decode_reset(self):
         """both cameras' raw-stream decoder states — the event decoder's and the trigger decoder's — back to the fresh
         state (esvio_fe_decode_reset)"""
@@ -1544,6 +1648,13 @@ class FeatureTracker:
         info = FeedInfo()
         return self._feed_pushed(self._hd.L.esvio_fe_feed_push_raw(self._hd.h, int(cam), int(fmt), ptr, nbytes, space, int(t_offset_us),
                                                                    C.byref(info)), info)
+
+    def feed_push_text(self, cam, order, time, data, flags=0, t_offset_ns=0):
+        """append the event lines of a chunk of a text event file (as decode_text takes it); the chunk may end anywhere"""
+        ptr, nbytes, space, keep = _text_src(data)
+        fmt, info = TextFormat(int(order), int(time), int(flags), 0), FeedInfo()
+        return self._feed_pushed(self._hd.L.esvio_fe_feed_push_text(self._hd.h, int(cam), C.byref(fmt), ptr, nbytes, space,
+                                                                    int(t_offset_ns), C.byref(info)), info)
 
     def feed_peek(self):
         """the oldest window closed in both cameras and not yet tracked, as a FeedWindow (.index, .end_sec / .end_nsec =
@@ -2463,6 +2574,43 @@ def raw_header(data):
     if rc:
         raise FrontendError("esvio_fe_raw_header rc=%d" % rc)
     return info
+
+
+def text_imu(data, t_offset_ns=0, cap=None):
+    """an imu.txt of the davis extractor, "t ax ay az gx gy gz" (esvio_fe_text_imu; host only, no handle): the whole
+    file's bytes.  Returns a numpy IMU_DTYPE array; cap None: one sample per 14 bytes.  A line that does not read raises
+    FrontendError with `.n` = the samples in front of it (too small a cap: the number needed)."""
+    buf = bytes(data)
+    cap = len(buf) // 14 + 1 if cap is None else int(cap)
+    out, n = np.zeros(max(cap, 1), IMU_DTYPE), C.c_size_t(0)
+    rc = load_library().esvio_fe_text_imu(buf if buf else None, len(buf), int(t_offset_ns), _p(out), cap, C.byref(n))
+    if rc:
+        e = FrontendError("esvio_fe_text_imu rc=%d" % rc)
+        e.n = int(n.value)
+        raise e
+    return out[:n.value]
+
+
+def text_images(data, t_offset_ns=0, cap=None):
+    """an images.txt of the davis extractor, "t path" (esvio_fe_text_images; host only, no handle).  Returns (stamps_ns, paths):
+    an int64 numpy array and a list of bytes.  Failures as text_imu's."""
+    buf = bytes(data)
+    cap = len(buf) // 4 + 1 if cap is None else int(cap)
+    st, off, ln, n = np.zeros(max(cap, 1), np.int64), np.zeros(max(cap, 1), np.uint64), np.zeros(max(cap, 1), np.uint32), C.c_size_t(0)
+    rc = load_library().esvio_fe_text_images(buf if buf else None, len(buf), int(t_offset_ns), _p(st), _p(off), _p(ln), cap, C.byref(n))
+    if rc:
+        e = FrontendError("esvio_fe_text_images rc=%d" % rc)
+        e.n = int(n.value)
+        raise e
+    k = int(n.value)
+    return st[:k], [buf[int(o):int(o) + int(m)] for o, m in zip(off[:k], ln[:k])]
+
+
+def text_limits():
+    """esvio_fe_text_limits (include/esvio_fe_test.h): .tile_bytes, .max_body, .max_tail"""
+    out = TextLimits()
+    load_library().esvio_fe_text_limits(C.byref(out))
+    return out
 
 
 def lift_projective(cam, u, v):

@@ -1271,6 +1271,117 @@ int esvio_fe_convert_image(esvio_fe_handle h, const void* src, int src_space, ui
 int esvio_fe_track_image_space(esvio_fe_handle h, double cur_time, const uint8_t* img_left, const uint8_t* img_right,
                                int space, int pub_this_frame, esvio_fe_tracks* out);
 
+/* ---- text event files: "t x y p" / "x y p t" lines -> event records, on the device ---------- */
+/* The third container the reference's own tooling writes events in, beside rosbag and the libcaer stream.  Its tree
+ * ships three writers, and their lines are the formats below:
+ *   dvs_file_writer/scripts/extract_davis_bag_files.py  events.txt: "<secs>.<nsecs, 9 digits> <x> <y> <0|1>\n"
+ *                                                       (timestamp_str, and the loop over msg.events) — the Event
+ *                                                       Camera Dataset's events.txt; beside it imu.txt
+ *                                                       "t ax ay az gx gy gz" and images.txt "t path"
+ *   dvs_file_writer/scripts/extract_dvs_bag_files.py    "<x> <y> <p> <t_us>\n" (to_nsec() / 1000, integer division)
+ *   dvs_file_writer/src/writer.cpp                      "<x> <y> <p> <t_us>" and std::endl
+ * The second form, with commas, is also what a Prophesee CSV export holds ("x,y,p,t", microseconds).  A stamp is two
+ * integers printed in decimal, so the decode is exact integer arithmetic; THIS TEXT IS THE SPECIFICATION, tests/text_ref.py
+ * is its sequential reading, and Python's int() and decimal.Decimal are the oracle of its numbers.
+ *
+ * Format.  esvio_fe_text_format: order = ESVIO_FE_TEXT_TXYP or _XYPT; time = ESVIO_FE_TEXT_SEC_DECIMAL, _INT_US or
+ * _INT_NS; flags = ESVIO_FE_TEXT_END (this chunk ends the stream) | ESVIO_FE_TEXT_SKIP_MALFORMED (malformed lines are
+ * dropped and counted instead of failing the call); reserved = 0.  The davis extractor is {TXYP, SEC_DECIMAL}; the dvs
+ * extractor, writer.cpp and a Prophesee CSV are {XYPT, INT_US}.
+ *
+ * Lines.  A line ends at '\n'; a '\r' directly before the '\n' belongs to the terminator; the body is what lies before
+ * the terminator.  The body is classified in this order:
+ *   1. more than 64 bytes: MALFORMED;
+ *   2. leading and trailing separator bytes — space, tab, comma — are stripped; nothing left: BLANK;
+ *   3. first byte '#' or '%': COMMENT;
+ *   4. split on runs of one or more separator bytes; anything other than exactly four tokens: MALFORMED;
+ *   5. the tokens, in the format's order; any byte not listed here, in any token, is MALFORMED ('+', 'e', 'E', NUL ...):
+ *        x, y   1 to 5 decimal digits, value <= 65535
+ *        p      exactly "0", "1" or "-1"; "-1" gives polarity 0
+ *        t, SEC_DECIMAL       1 to 10 digits I, optionally followed by '.' and at least one digit F:
+ *                             ns = I * 10^9 + (the first nine digits of F, padded on the right with zeros); digits
+ *                             behind the ninth must be digits and are dropped — truncation, not rounding (the cited
+ *                             writer never emits them)
+ *        t, INT_US / INT_NS   1 to 19 digits, read in exact integers: ns = v * 1000 (INT_US), ns = v (INT_NS)
+ * Stamps.  ticks = ns + t_offset_ns (signed, |t_offset_ns| <= 2^62); sec = ticks / 10^9, nsec = ticks % 10^9.  An event
+ * line is BAD when ticks < 0 or sec >= 2^32, decided in exact integers: a 19-digit value never wraps, it is BAD.
+ * Records.  x, y, sec, nsec, polarity 0 or 1, the padding bytes 0 — byte for byte what esvio_amd.events.make_events
+ * builds —, in line order.  x and y are not compared with the sensor size: that stays the SAE update's business, as in
+ * the other decoders.
+ *
+ * State.  Per handle and camera: the unterminated tail of the stream so far — at most 65 bytes: 64 of body and one
+ * '\r' — or the flag "inside a line whose body has already passed 64 bytes", with the number of that line's bytes so
+ * far; the rest of such a line is discarded up to its terminator.  A line is classified and counted in the call that
+ * holds its terminator.  With ESVIO_FE_TEXT_END a non-empty tail is a line (a '\r' at its end, no '\n' behind it, is a
+ * byte of its body), a line still being discarded is a malformed line, and the state is fresh afterwards.  The state is
+ * cleared by esvio_fe_decode_reset and esvio_fe_reset.
+ *
+ * Failures.  ESVIO_FE_EINVAL for a malformed line without SKIP_MALFORMED, for any BAD line, for more events than dst_cap
+ * (a BAD line counts among `events`).  In all three every count of info is exact and `events` holds the number needed,
+ * dst is unspecified — records beyond the first min(events, dst_cap) are never touched, and nothing at all is stored
+ * when events > dst_cap —, THE CAMERA'S STATE IS AS IT WAS BEFORE THE CALL and the next call works normally.
+ * first_t_ns and last_t_ns are filled by a call that succeeds; carried is the tail's length behind such a call, and
+ * on a refused call — an argument error included — the tail's length as before the call.
+ * Sizes.  n_bytes <= 2^28; n_bytes == 0 without END touches nothing; (n_bytes + 65) / 8 + 1 records always suffice (the
+ * shortest event line is 8 bytes).
+ * Out of scope: exponent notation (numpy's default savetxt format), a missing integer part (".5"), more than four
+ * columns, quoted fields, header lines that are neither blank nor comments (without SKIP_MALFORMED they fail the call,
+ * with it they are counted), compressed text. */
+#define ESVIO_FE_TEXT_TXYP 1
+#define ESVIO_FE_TEXT_XYPT 2
+#define ESVIO_FE_TEXT_SEC_DECIMAL 1
+#define ESVIO_FE_TEXT_INT_US 2
+#define ESVIO_FE_TEXT_INT_NS 3
+#define ESVIO_FE_TEXT_END 1u
+#define ESVIO_FE_TEXT_SKIP_MALFORMED 2u
+typedef struct esvio_fe_text_format {
+  int32_t order, time;
+  uint32_t flags, reserved;
+} esvio_fe_text_format;
+typedef struct esvio_fe_text_info {
+  uint64_t events, lines, comments, blank, malformed, bad; /* lines = events + comments + blank + malformed */
+  int64_t first_malformed;       /* byte offset of the first malformed line's first byte, relative to this call's `bytes`:
+                                    negative when the line began in the carried state; untouched if there is none; filled
+                                    with SKIP_MALFORMED too */
+  int64_t first_t_ns, last_t_ns; /* ticks of the first / last event; untouched if none */
+  uint32_t carried;              /* the length of the tail after the call */
+  uint32_t reserved;
+} esvio_fe_text_info;
+/* the decode stage: camera `cam`'s state advanced by the n_bytes of `bytes`, the records written to dst.  The source's
+ * three paths are esvio_fe_decode_raw's: ESVIO_FE_DEVICE is read in place, at any alignment; ESVIO_FE_HOST: page-locked
+ * memory the library's runtime knows is read in place up to 256 KiB and copied first beyond that (every byte is read
+ * twice), pageable memory is copied once into the handle's scratch.  dst, dst_space, info as esvio_fe_decode_raw's.
+ * Orders itself on the main stream, waits for its own result and touches nothing of the tracker.  Its scratch — 32 bytes
+ * per 4096 bytes of text, the copy of a pageable source, the records behind a host dst (min(dst_cap, the bound above) of
+ * them) — grows on first use, and with esvio_fe_reserve for a handle that has decoded text before (there for lines of
+ * 16 bytes and more).  ESVIO_FE_EINVAL with a message, before any device work: a null or unknown format, reserved != 0,
+ * unknown flags, cam outside 0..1, a bad space, null bytes with n_bytes > 0, a null dst with dst_cap > 0, a misaligned
+ * device dst, |t_offset_ns| > 2^62, n_bytes > 2^28. */
+int esvio_fe_decode_text(esvio_fe_handle h, int cam, const esvio_fe_text_format* fmt, const void* bytes, size_t n_bytes,
+                         int space, int64_t t_offset_ns, esvio_fe_event* dst, size_t dst_cap, int dst_space,
+                         esvio_fe_text_info* info);
+/* esvio_fe_track_raw's contract for text: both cameras' chains are enqueued first — three launches for the two of them
+ * —, the host waits once, cur_time comes from the last LEFT record, the cameras' states move only when the call returns
+ * ESVIO_FE_OK; a malformed line (without SKIP_MALFORMED) or a BAD line in either camera: ESVIO_FE_EINVAL, nothing
+ * tracked, both states as they were.  text[cam] (optional) as esvio_fe_decode_text's info.  Refused while batches are
+ * announced. */
+int esvio_fe_track_text(esvio_fe_handle h, const esvio_fe_text_format* fmt, const void* left, size_t left_bytes,
+                        const void* right, size_t right_bytes, int space, int64_t t_offset_ns, int pub_this_frame,
+                        const esvio_fe_filter_params* filter, const esvio_fe_motion* motion, esvio_fe_tracks* out,
+                        esvio_fe_batch_info* info, esvio_fe_text_info text[2]);
+/* the side files of the davis extractor, whole files in host memory, no handle, no device work.  Lines, blank lines and
+ * comments as above (a last line may lack its terminator; a line holds up to 4096 bytes); the stamp is the SEC_DECIMAL
+ * token with t_offset_ns applied, BAD as above.
+ * imu.txt, "t ax ay az gx gy gz": acc = (ax, ay, az), gyr = (gx, gy, gz), each the double nearest to its decimal text,
+ * read independently of the locale (a fixed or exponent form, "inf", "nan"; no leading '+').
+ * images.txt, "t path": stamps_ns[i] = ticks; the path is bytes[path_off[i], path_off[i] + path_len[i]): what follows the
+ * stamp and its spaces or tabs, up to the line's end without trailing separator bytes.
+ * ESVIO_FE_EINVAL: a line that does not read or is BAD (*n_out: the entries in front of it), more entries than cap
+ * (*n_out: the number needed; the first cap are written), null pointers. */
+int esvio_fe_text_imu(const void* bytes, size_t n, int64_t t_offset_ns, esvio_fe_imu_sample* out, size_t cap, size_t* n_out);
+int esvio_fe_text_images(const void* bytes, size_t n, int64_t t_offset_ns, int64_t* stamps_ns, uint64_t* path_off,
+                         uint32_t* path_len, size_t cap, size_t* n_out);
+
 /* ---- stream slicing: a record stream cut into fixed-rate windows, on the device ------------ */
 /* trackEvent takes one batch per camera and call; a recording or a sensor transfer is a long stream whose batch edges
  * are points in time.  The reference cuts its streams off line, dependences/events_repacking_helper/src/
@@ -1453,6 +1564,11 @@ int esvio_fe_feed_push_aedat(esvio_fe_handle h, int cam, const void* bytes, size
  * the feed with an explicit origin.  Failures as esvio_fe_feed_push_aedat's, for both cameras together: nothing is
  * appended to either, the walker is as it was.  Refused while batches are announced. */
 int esvio_fe_feed_push_bag(esvio_fe_handle h, const void* bytes, size_t n_bytes, uint32_t flags, esvio_fe_feed_info info[2]);
+/* esvio_fe_feed_push_raw for a chunk of a text event file ("text event files" above; it may end anywhere): the event
+ * lines' records are appended; failures as esvio_fe_decode_text's (a malformed line without SKIP_MALFORMED, a BAD
+ * line), with nothing appended and the camera's text state as it was */
+int esvio_fe_feed_push_text(esvio_fe_handle h, int cam, const esvio_fe_text_format* fmt, const void* bytes, size_t n_bytes,
+                            int space, int64_t t_offset_ns, esvio_fe_feed_info* info);
 int esvio_fe_feed_peek(esvio_fe_handle h, esvio_fe_feed_window* out);
 int esvio_fe_feed_track(esvio_fe_handle h, int pub_this_frame, const esvio_fe_motion* motion, esvio_fe_tracks* out,
                         esvio_fe_batch_info* info);

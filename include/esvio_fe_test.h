@@ -301,6 +301,20 @@ const char* esvio_fe_bow_create_kernel_name(int which);
 int esvio_fe_bow_create_kernel_stats(esvio_fe_handle h, int which, double* total_ms, uint64_t* launches, uint64_t* alg_bytes);
 int esvio_fe_bow_create_pick(esvio_fe_handle h, const uint32_t* min_dist, int64_t n, const uint32_t* seg_off, int32_t n_seg,
                              const double* cut_d, uint32_t* pick);
+/* the text stage (esvio_fe_decode_text): tile_bytes, the bytes of the virtual stream — the carried tail, then the chunk —
+ * one workgroup owns the line starts of; max_body, the longest body that is not malformed; max_tail, the longest tail a
+ * call leaves.  Its three kernels, k_text_count, k_text_place, k_text_emit, have a table of their own in timer slots
+ * behind every other; esvio_fe_text_kernel_name: "" for any other id; _stats as esvio_fe_get_kernel_stats. */
+typedef struct esvio_fe_text_limits_info {
+  int32_t tile_bytes;
+  int32_t max_body;
+  int32_t max_tail;
+  int32_t reserved;
+} esvio_fe_text_limits_info;
+int esvio_fe_text_limits(esvio_fe_text_limits_info* out);
+int esvio_fe_text_kernel_count(void);
+const char* esvio_fe_text_kernel_name(int which);
+int esvio_fe_text_kernel_stats(esvio_fe_handle h, int which, double* total_ms, uint64_t* launches, uint64_t* alg_bytes);
 /* the events one workgroup of the slicing chain takes (esvio_fe_slice_events): where its tile edges lie */
 int esvio_fe_slice_tile_events(void);
 /* the hipStream_t the handle launches on (as void*) */
