@@ -2523,6 +2523,12 @@ int esvio_fe_text_limits(esvio_fe_text_limits_info* out) {
   *out = esvio_fe_text_limits_info{(int32_t)kTextTileBytes, (int32_t)tx::kMaxBody, (int32_t)tx::kMaxTail, 0};
   return 0;
 }
+int esvio_fe_scan_lanes(esvio_fe_scan_lanes_info* out) {
+  if (!out) return ESVIO_FE_EINVAL;
+  *out = esvio_fe_scan_lanes_info{(int32_t)kRawScanLanes,   (int32_t)kAedatScanLanes, (int32_t)kTextScanLanes, (int32_t)kSliceScanLanes,
+                                  (int32_t)kBafScanThreads, (int32_t)kVocScanLanes,   (int32_t)kBafBlock,      (int32_t)kVocScanTile};
+  return 0;
+}
 int esvio_fe_text_kernel_count(void) { return kTextKernels; }
 const char* esvio_fe_text_kernel_name(int which) { return which >= 0 && which < kTextKernels ? kTextKernelNames[which] : ""; }
 int esvio_fe_text_kernel_stats(esvio_fe_handle c, int which, double* total_ms, uint64_t* launches, uint64_t* alg_bytes) {

@@ -565,6 +565,8 @@ struct BafResult {  // zeroed by the host in front of the chain; one per camera
 };
 static_assert(sizeof(BafResult) == 48 && offsetof(BafResult, last) == 16, "BafResult layout");
 constexpr uint32_t kBafBlock = 1024;  // events per block of the ordered compaction (four flags per lane)
+// lanes of k_baf_scan's one workgroup: each owns ceil(blocks / lanes) consecutive blocks' counts (esvio_fe_scan_lanes)
+constexpr int kBafScanThreads = 1024;
 inline uint32_t baf_blocks(uint32_t n) { return (n + kBafBlock - 1) / kBafBlock; }
 struct BafArgs {
   const EventRec* ev;    // [n] the call's events, device memory (the fields form: not read)
@@ -650,6 +652,8 @@ void launch_hot_pick(hipStream_t s, const uint32_t* keys, const uint32_t* vals, 
 // k_trig_emit — over the same RawXf: only the time base and the counts are used, a trigger word counts as one "event",
 // and the records stored are esvio_fe_trigger's 16 bytes.
 constexpr uint32_t kRawTileBytes = 4096;  // 256 lanes x 16 bytes: 2048 EVT3 words, 1024 EVT2 words, 512 EVT2.1 words
+// lanes of k_raw_scan's workgroup (one per camera): each owns ceil(tiles / lanes) consecutive tiles' transformers
+constexpr uint32_t kRawScanLanes = 256;
 constexpr int kRawEvt2 = 2, kRawEvt3 = 3, kRawEvt21 = 21;
 constexpr uint32_t kRawHasTh = 1u, kRawHasTl = 2u, kRawHasY = 4u, kRawHasBx = 8u, kRawBp = 16u;
 constexpr int kRawTlShift = 8, kRawYShift = 20;  // flags: tl in bits 8..19, y in bits 20..30
@@ -707,6 +711,7 @@ void launch_trig_emit(hipStream_t s, const RawArgs& a);
 // table, whose end a test pins, stays as it is.
 enum IngestKernelId { K_AEDAT_COUNT = K_COUNT, K_AEDAT_SCAN, K_AEDAT_EMIT, K_BAG_EMIT, K_IMAGE_EMIT, K_INGEST_COUNT };
 constexpr uint32_t kAedatTile = 1024;  // records per workgroup: 1024 lanes, one record each
+constexpr uint32_t kAedatScanLanes = 256;  // lanes of k_aedat_scan's workgroup: each owns ceil(tiles / lanes) consecutive tiles' counts
 struct AedatRun {                      // (fe_aedat.h: esvio::aedat::Run)
   uint32_t first;
   int32_t overflow;
@@ -782,6 +787,7 @@ void launch_bag_emit(hipStream_t s, const BagArgs& a);
 // Three launches for one camera or for both: both cameras' tiles share each grid.  No workgroup waits for another.
 // Their timer slots lie behind every other table (fe_ctx.h).
 constexpr uint32_t kTextTileBytes = 4096;  // 256 lanes x 16 bytes
+constexpr uint32_t kTextScanLanes = 256;   // lanes of k_text_place's workgroup: each owns ceil(tiles / lanes) consecutive tiles' summaries
 constexpr uint32_t kTextHalo = 66;         // a body of 64 bytes, '\r', '\n'
 struct TextTile {      // k_text_count per tile; k_text_place turns `events` into the exclusive prefix
   uint32_t events;     // event lines, the BAD ones among them
@@ -913,6 +919,7 @@ void launch_evimg_canvas(hipStream_t s, const uint8_t* left, const uint8_t* righ
 // in one grid, as the raw chain's do; the entry points there are so far run ONE camera per chain (a slice call and a
 // feed push are per camera): cam[1].tiles is 0 and the scan is one workgroup.  No launch waits on the device for another workgroup.  Every count is RELATIVE to the windows closed before the call.
 constexpr uint32_t kSliceTile = 1024;        // events per workgroup: 256 lanes x 4 consecutive records
+constexpr uint32_t kSliceScanLanes = 256;    // lanes of k_slice_scan's workgroup: each owns ceil(tiles / lanes) consecutive tiles' maxima
 constexpr uint32_t kSliceMaxWindows = 4096;  // ESVIO_FE_SLICE_MAX_WINDOWS
 struct SliceResult {  // written by k_slice_scan (first_of_last: k_slice_cuts); one per camera, the cuts behind it
   uint32_t closed;         // windows the call closes (the maximum of c over its events)
@@ -1098,6 +1105,7 @@ void launch_bow_select(hipStream_t s, const double* score, const uint8_t* presen
 //                      the document (bisection in doc_offsets) differs from the position before.
 constexpr uint32_t kVocBigNode = 4096;
 constexpr int kVocScanTile = 2048;
+constexpr uint32_t kVocScanLanes = 256;  // lanes of k_voc_scan_top's one workgroup: each owns ceil(tiles / lanes) consecutive tiles' sums
 struct VocArgs {
   const uint32_t* desc;     // [n][8], 16-byte aligned
   uint32_t na, n_seg, n_km, n_big;

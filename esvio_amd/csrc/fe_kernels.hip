@@ -3998,7 +3998,6 @@ __global__ __launch_bounds__(256) void k_baf_count(BafArgs a) {
   }
 }
 
-constexpr int kBafScanThreads = 1024;
 __global__ __launch_bounds__(kBafScanThreads) void k_baf_scan(BafArgs a, uint32_t nblk) {
   __shared__ uint32_t wsum[kBafScanThreads / 64];
   const uint32_t per = (nblk + kBafScanThreads - 1) / kBafScanThreads;
@@ -4589,12 +4588,12 @@ __global__ __launch_bounds__(256) void k_raw_reduce(RawArgs a) {
     c.sums[tile] = raw_combine(raw_combine(part[0], part[1], kHalf), raw_combine(part[2], part[3], kHalf), kHalf);
 }
 
-__global__ __launch_bounds__(256) void k_raw_scan(RawArgs a) {
-  __shared__ RawXf part[4];
+__global__ __launch_bounds__(kRawScanLanes) void k_raw_scan(RawArgs a) {
+  __shared__ RawXf part[kRawScanLanes / 64];
   const RawCam& c = a.cam[blockIdx.x];
   if (!c.tiles) return;
   const uint32_t half = a.format == kRawEvt3 ? 2048u : 1u << 27;
-  const uint32_t per = (c.tiles + 255u) / 256u;
+  const uint32_t per = (c.tiles + kRawScanLanes - 1u) / kRawScanLanes;
   const uint32_t lo = min(threadIdx.x * per, c.tiles), hi = min(lo + per, c.tiles);
   RawXf sum = raw_identity();
   for (uint32_t j = lo; j < hi; j++) sum = raw_combine(sum, c.sums[j], half);
@@ -4610,7 +4609,7 @@ __global__ __launch_bounds__(256) void k_raw_scan(RawArgs a) {
     c.sums[j] = run;
     run = raw_combine(run, s, half);
   }
-  if (threadIdx.x == 255) {  // (the chunks behind the last tile are empty: this lane's run is the whole call)
+  if (threadIdx.x == kRawScanLanes - 1u) {  // (the chunks behind the last tile are empty: this lane's run is the whole call)
     RawResult* r = c.res;
     r->events = run.after, r->untimed = run.before, r->other = run.other, r->wraps = run.wraps;
     r->state = run;
@@ -4823,7 +4822,7 @@ void launch_raw_reduce(hipStream_t s, const RawArgs& a) {
     launch_k(k_raw_reduce<kRawEvt2>, dim3(raw_grid(a)), dim3(256), 0, s, a);
 }
 void launch_raw_scan(hipStream_t s, const RawArgs& a) {
-  if (raw_grid(a)) launch_k(k_raw_scan, dim3(2), dim3(256), 0, s, a);
+  if (raw_grid(a)) launch_k(k_raw_scan, dim3(2), dim3(kRawScanLanes), 0, s, a);
 }
 void launch_raw_emit(hipStream_t s, const RawArgs& a) {
   if (!raw_grid(a)) return;
@@ -4883,11 +4882,11 @@ __global__ __launch_bounds__(kAedatTile) void k_aedat_count(AedatArgs a) {
   }
 }
 
-__global__ __launch_bounds__(256) void k_aedat_scan(AedatArgs a) {
-  __shared__ uint32_t part[4];
+__global__ __launch_bounds__(kAedatScanLanes) void k_aedat_scan(AedatArgs a) {
+  __shared__ uint32_t part[kAedatScanLanes / 64];
   const AedatCam& c = a.cam[blockIdx.x];
   if (!c.tiles) return;
-  const uint32_t per = (c.tiles + 255u) / 256u;
+  const uint32_t per = (c.tiles + kAedatScanLanes - 1u) / kAedatScanLanes;
   const uint32_t lo = min(threadIdx.x * per, c.tiles), hi = min(lo + per, c.tiles);
   uint32_t sum = 0;
   for (uint32_t j = lo; j < hi; j++) sum += c.sums[j];
@@ -4906,7 +4905,7 @@ __global__ __launch_bounds__(256) void k_aedat_scan(AedatArgs a) {
     c.sums[j] = run;
     run += s;
   }
-  if (threadIdx.x == 255) {  // (the chunks behind the last tile are empty: this lane's run is the whole call)
+  if (threadIdx.x == kAedatScanLanes - 1u) {  // (the chunks behind the last tile are empty: this lane's run is the whole call)
     AedatResult* r = c.res;
     r->events = run, r->invalid = c.n - run;
     r->bad = 0;
@@ -4963,7 +4962,7 @@ void launch_aedat_count(hipStream_t s, const AedatArgs& a) {
   if (aedat_grid(a)) launch_k(k_aedat_count, dim3(aedat_grid(a)), dim3(kAedatTile), 0, s, a);
 }
 void launch_aedat_scan(hipStream_t s, const AedatArgs& a) {
-  if (aedat_grid(a)) launch_k(k_aedat_scan, dim3(2), dim3(256), 0, s, a);
+  if (aedat_grid(a)) launch_k(k_aedat_scan, dim3(2), dim3(kAedatScanLanes), 0, s, a);
 }
 void launch_aedat_emit(hipStream_t s, const AedatArgs& a) {
   if (aedat_grid(a)) launch_k(k_aedat_emit, dim3(aedat_grid(a)), dim3(kAedatTile), 0, s, a);
@@ -5061,11 +5060,11 @@ __global__ __launch_bounds__(256) void k_slice_reduce(SliceArgs a) {
   if (threadIdx.x == 0) c.tmax[tile] = max(max(part[0], part[1]), max(part[2], part[3]));
 }
 
-__global__ __launch_bounds__(256) void k_slice_scan(SliceArgs a) {
-  __shared__ uint32_t part[4];
+__global__ __launch_bounds__(kSliceScanLanes) void k_slice_scan(SliceArgs a) {
+  __shared__ uint32_t part[kSliceScanLanes / 64];
   const SliceCam& c = a.cam[blockIdx.x];
   if (!c.tiles) return;
-  const uint32_t per = (c.tiles + 255u) / 256u;
+  const uint32_t per = (c.tiles + kSliceScanLanes - 1u) / kSliceScanLanes;
   const uint32_t lo = min(threadIdx.x * per, c.tiles), hi = min(lo + per, c.tiles);
   uint32_t mine = 0;
   for (uint32_t j = lo; j < hi; j++) mine = max(mine, c.tmax[j]);
@@ -5081,7 +5080,7 @@ __global__ __launch_bounds__(256) void k_slice_scan(SliceArgs a) {
     c.tmax[j] = run;
     run = max(run, t);
   }
-  if (threadIdx.x == 255) {  // (the chunks behind the last tile are empty: this lane's run is the whole call)
+  if (threadIdx.x == kSliceScanLanes - 1u) {  // (the chunks behind the last tile are empty: this lane's run is the whole call)
     c.res->closed = run;
     c.res->overflow = run >= c.n_bounds ? 1u : 0u;
   }
@@ -5116,7 +5115,7 @@ void launch_slice_reduce(hipStream_t s, const SliceArgs& a) {
   if (slice_grid(a)) launch_k(k_slice_reduce, dim3(slice_grid(a)), dim3(256), 0, s, a);
 }
 void launch_slice_scan(hipStream_t s, const SliceArgs& a) {
-  if (slice_grid(a)) launch_k(k_slice_scan, dim3(a.cam[1].tiles ? 2 : 1), dim3(256), 0, s, a);  // (cam[0] alone: one workgroup)
+  if (slice_grid(a)) launch_k(k_slice_scan, dim3(a.cam[1].tiles ? 2 : 1), dim3(kSliceScanLanes), 0, s, a);  // (cam[0] alone: one workgroup)
 }
 void launch_slice_cuts(hipStream_t s, const SliceArgs& a) {
   if (slice_grid(a)) launch_k(k_slice_cuts, dim3(slice_grid(a)), dim3(256), 0, s, a);
@@ -6434,9 +6433,10 @@ __global__ __launch_bounds__(256) void k_voc_scan_reduce(const uint32_t* __restr
   if (threadIdx.x == 255) tile_sum[blockIdx.x] = ex + v;
 }
 // tile_sum -> the sum of the tiles in front of each, in place; one workgroup
-__global__ __launch_bounds__(256) void k_voc_scan_top(uint64_t* __restrict__ tile_sum, uint32_t tiles) {
-  __shared__ uint64_t wave_sum[4];
-  const uint32_t per = (tiles + 255u) / 256u, t0 = threadIdx.x * per;
+static_assert(kVocScanLanes == 256u, "voc_block_scan sums four waves");
+__global__ __launch_bounds__(kVocScanLanes) void k_voc_scan_top(uint64_t* __restrict__ tile_sum, uint32_t tiles) {
+  __shared__ uint64_t wave_sum[kVocScanLanes / 64];
+  const uint32_t per = (tiles + kVocScanLanes - 1u) / kVocScanLanes, t0 = threadIdx.x * per;
   uint64_t v = 0;
   for (uint32_t j = t0; j < min(t0 + per, tiles); j++) v += tile_sum[j];
   uint64_t run = voc_block_scan(v, wave_sum);
@@ -6693,7 +6693,7 @@ void launch_voc_scan_reduce(hipStream_t s, const uint32_t* min_dist, uint32_t n,
   if (n) launch_k(k_voc_scan_reduce, dim3(voc_tiles(n)), dim3(256), 0, s, min_dist, n, tile_sum);
 }
 void launch_voc_scan_top(hipStream_t s, uint64_t* tile_sum, uint32_t tiles) {
-  if (tiles) launch_k(k_voc_scan_top, dim3(1), dim3(256), 0, s, tile_sum, tiles);
+  if (tiles) launch_k(k_voc_scan_top, dim3(1), dim3(kVocScanLanes), 0, s, tile_sum, tiles);
 }
 void launch_voc_scan_down(hipStream_t s, const uint32_t* min_dist, uint32_t n, const uint64_t* tile_sum, uint64_t* run) {
   if (n) launch_k(k_voc_scan_down, dim3(voc_tiles(n)), dim3(256), 0, s, min_dist, n, tile_sum, run);
@@ -6874,16 +6874,16 @@ __global__ __launch_bounds__(256) void k_text_count(TextArgs a) {
   }
 }
 
-__global__ __launch_bounds__(256) void k_text_place(TextArgs a) {
+__global__ __launch_bounds__(kTextScanLanes) void k_text_place(TextArgs a) {
   __shared__ unsigned long long tot[4];  // comments, blank, malformed, bad
-  __shared__ uint32_t part[4], last_nl_s, first_mal_s, tail_from, tail_len;
+  __shared__ uint32_t part[kTextScanLanes / 64], last_nl_s, first_mal_s, tail_from, tail_len;
   const TextCam& c = a.cam[blockIdx.x];
   if (!c.tiles) return;
   const uint32_t tid = threadIdx.x;
   if (tid < 4) tot[tid] = 0;
   if (tid == 0) last_nl_s = 0, first_mal_s = 0xffffffffu, tail_from = 0, tail_len = 0;
   __syncthreads();
-  const uint32_t per = (c.tiles + 255u) / 256u;
+  const uint32_t per = (c.tiles + kTextScanLanes - 1u) / kTextScanLanes;
   const uint32_t lo = min(tid * per, c.tiles), hi = min(lo + per, c.tiles);
   uint32_t sum = 0, last_nl = 0, first_mal = 0xffffffffu;
   unsigned long long cnt[4] = {0, 0, 0, 0};
@@ -6914,7 +6914,7 @@ __global__ __launch_bounds__(256) void k_text_place(TextArgs a) {
     run += e;
   }
   TextResult* r = c.res;
-  if (tid == 255) r->events = run;  // (the chunks behind the last tile are empty: this lane's run is the whole call)
+  if (tid == kTextScanLanes - 1u) r->events = run;  // (the chunks behind the last tile are empty: this lane's run is the whole call)
   if (tid == 0) {  // what only the whole stream decides, and the state behind the call
     const uint32_t N = c.carry.len + c.n_bytes, from = last_nl_s;
     const bool still_skipping = c.carry.skip && from == 0;  // the overlong line of an earlier call has not ended yet
@@ -6997,7 +6997,7 @@ void launch_text_count(hipStream_t s, const TextArgs& a) {
   if (text_grid(a)) launch_k(k_text_count, dim3(text_grid(a)), dim3(256), 0, s, a);
 }
 void launch_text_place(hipStream_t s, const TextArgs& a) {
-  if (text_grid(a)) launch_k(k_text_place, dim3(2), dim3(256), 0, s, a);
+  if (text_grid(a)) launch_k(k_text_place, dim3(2), dim3(kTextScanLanes), 0, s, a);
 }
 void launch_text_emit(hipStream_t s, const TextArgs& a) {
   if (text_grid(a)) launch_k(k_text_emit, dim3(text_grid(a)), dim3(256), 0, s, a);

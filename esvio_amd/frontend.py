@@ -158,6 +158,12 @@ class TextLimits(C.Structure):
     _fields_ = [("tile_bytes", C.c_int32), ("max_body", C.c_int32), ("max_tail", C.c_int32), ("reserved", C.c_int32)]
 
 
+class ScanLanes(C.Structure):
+    """esvio_fe_scan_lanes_info (include/esvio_fe_test.h)"""
+    _fields_ = [("raw", C.c_int32), ("aedat", C.c_int32), ("text", C.c_int32), ("slice", C.c_int32), ("filter", C.c_int32),
+                ("pick", C.c_int32), ("filter_block_events", C.c_int32), ("pick_tile_values", C.c_int32)]
+
+
 TEXT_TXYP, TEXT_XYPT = 1, 2                          # esvio_fe_text_format.order
 TEXT_SEC_DECIMAL, TEXT_INT_US, TEXT_INT_NS = 1, 2, 3  # .time
 TEXT_END, TEXT_SKIP_MALFORMED = 1, 2                  # .flags
@@ -415,6 +421,7 @@ TEST_SYMBOLS = [
     "esvio_fe_bow_kernel_count", "esvio_fe_bow_kernel_name", "esvio_fe_bow_kernel_stats", "esvio_fe_bow_limits", "esvio_fe_bow_scores",
     "esvio_fe_bow_create_kernel_count", "esvio_fe_bow_create_kernel_name", "esvio_fe_bow_create_kernel_stats", "esvio_fe_bow_create_pick",
     "esvio_fe_text_limits", "esvio_fe_text_kernel_count", "esvio_fe_text_kernel_name", "esvio_fe_text_kernel_stats",
+    "esvio_fe_scan_lanes",
 ]
 
 LATENCY_PHASES = 16
@@ -646,6 +653,7 @@ def load_library(build_if_missing=True):
     L.esvio_fe_text_imu.argtypes = [vp, sz, C.c_int64, vp, sz, C.POINTER(sz)]
     L.esvio_fe_text_images.argtypes = [vp, sz, C.c_int64, vp, vp, vp, sz, C.POINTER(sz)]
     L.esvio_fe_text_limits.argtypes = [C.POINTER(TextLimits)]
+    L.esvio_fe_scan_lanes.argtypes = [C.POINTER(ScanLanes)]
     L.esvio_fe_text_kernel_name.argtypes = [i]
     L.esvio_fe_text_kernel_name.restype = C.c_char_p
     L.esvio_fe_text_kernel_stats.argtypes = [vp, i, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -2610,6 +2618,14 @@ def text_limits():
     """esvio_fe_text_limits (include/esvio_fe_test.h): .tile_bytes, .max_body, .max_tail"""
     out = TextLimits()
     load_library().esvio_fe_text_limits(C.byref(out))
+    return out
+
+
+def scan_lanes():
+    """esvio_fe_scan_lanes (include/esvio_fe_test.h): the lanes of each ingest chain's top scan, .raw, .aedat, .text, .slice,
+    .filter, .pick, and the two tile sizes no other tap returns, .filter_block_events, .pick_tile_values"""
+    out = ScanLanes()
+    assert load_library().esvio_fe_scan_lanes(C.byref(out)) == 0
     return out
 
 

@@ -317,6 +317,24 @@ const char* esvio_fe_text_kernel_name(int which);
 int esvio_fe_text_kernel_stats(esvio_fe_handle h, int which, double* total_ms, uint64_t* launches, uint64_t* alg_bytes);
 /* the events one workgroup of the slicing chain takes (esvio_fe_slice_events): where its tile edges lie */
 int esvio_fe_slice_tile_events(void);
+/* The ingest chains' top scans: reduce per tile -> ONE workgroup scans the tiles' summaries -> emit per tile.  A lane of that
+ * workgroup owns ceil(tiles / lanes) consecutive tiles, so a call of more tiles than lanes is where a lane folds several
+ * summaries, lanes own none, and the last lane's run must still be the whole call.  Per chain, the lanes: raw, k_raw_scan
+ * (esvio_fe_decode_raw, _decode_triggers, _track_raw; tile: esvio_fe_raw_tile_bytes); aedat, k_aedat_scan (tile:
+ * esvio_fe_aedat_tile_events); text, k_text_place (tile: esvio_fe_text_limits); slice, k_slice_scan (tile:
+ * esvio_fe_slice_tile_events); filter, k_baf_scan, over blocks of filter_block_events events; pick, k_voc_scan_top
+ * (esvio_fe_bow_create_pick), over tiles of pick_tile_values values. */
+typedef struct esvio_fe_scan_lanes_info {
+  int32_t raw;
+  int32_t aedat;
+  int32_t text;
+  int32_t slice;
+  int32_t filter;
+  int32_t pick;
+  int32_t filter_block_events;
+  int32_t pick_tile_values;
+} esvio_fe_scan_lanes_info;
+int esvio_fe_scan_lanes(esvio_fe_scan_lanes_info* out);
 /* the hipStream_t the handle launches on (as void*) */
 void* esvio_fe_stream(esvio_fe_handle h);
 /* hipMemGetInfo on the handle's device, through the HIP runtime the library itself is linked to */

@@ -345,3 +345,23 @@ def uniform(n, seed):
 
 def even_docs(n, n_docs):
     return [int(round(i * n / n_docs)) for i in range(n_docs + 1)]
+
+
+def pick_ref(md, seg_off, cut_d):
+    """C2's pick alone, as esvio_fe_bow_create_pick states it (include/esvio_fe_test.h): per segment the first rank whose
+    running sum of md, as a double, is >= the segment's cut; the last rank if none; 0xffffffff for an empty segment or a
+    cut that is not >= 0.  One value after the other."""
+    out = []
+    for s, cut in enumerate(cut_d):
+        b, e = int(seg_off[s]), int(seg_off[s + 1])
+        if e <= b or not cut >= 0.0:
+            out.append(0xffffffff)
+            continue
+        run, pick = 0, e - b - 1
+        for i in range(b, e):
+            run += int(md[i])
+            if float(run) >= cut:
+                pick = i - b
+                break
+        out.append(pick)
+    return np.array(out, np.uint32)

@@ -138,23 +138,6 @@ def test_descriptors_in_device_memory_are_read_in_place(ft):
 
 
 # ---- the pick --------------------------------------------------------------------------------------------------------
-def pick_ref(md, seg_off, cut_d):
-    out = []
-    for s, cut in enumerate(cut_d):
-        b, e = int(seg_off[s]), int(seg_off[s + 1])
-        if e <= b or not cut >= 0.0:
-            out.append(0xffffffff)
-            continue
-        run, pick = 0, e - b - 1
-        for i in range(b, e):
-            run += int(md[i])
-            if float(run) >= cut:
-                pick = i - b
-                break
-        out.append(pick)
-    return np.array(out, np.uint32)
-
-
 def test_the_seeding_pick_at_its_boundaries(ft):
     rng = np.random.default_rng(4)
     edges = [0, 1, 63, 64, 255, 256, 257, 300, 300, 2047, 2048, 2049, 4096, 4100, 5000]
@@ -182,7 +165,7 @@ def test_the_seeding_pick_at_its_boundaries(ft):
             else:
                 cut.append(float(total) + 1.0)  # none reaches it: the last feature
         cut = np.array(cut)
-        want = pick_ref(md, seg_off, cut)
+        want = R.pick_ref(md, seg_off, cut)
         assert np.array_equal(ft.bow_create_pick(md, seg_off, cut), want), kind
     assert want[7] == 0xffffffff and want[0] == 0  # the empty segment, the segment of one
 
