@@ -2529,6 +2529,55 @@ int esvio_fe_scan_lanes(esvio_fe_scan_lanes_info* out) {
                                   (int32_t)kBafScanThreads, (int32_t)kVocScanLanes,   (int32_t)kBafBlock,      (int32_t)kVocScanTile};
   return 0;
 }
+// the shared sort alone, in device memory of the call's own (include/esvio_fe_test.h); the driver is radix_sort_pairs as it is
+int esvio_fe_sort_pairs(esvio_fe_handle c, const uint32_t* keys, const uint32_t* vals, int64_t n, int passes, int bits,
+                        int64_t n_dev, uint32_t* out_keys, uint32_t* out_vals, int32_t* out_err, uint32_t* out_tickets) {
+  if (!c) return ESVIO_FE_EINVAL;
+  const char* who = "sort_pairs";
+  if (bits < 1 || bits > kRadixMaxBits || passes < 1 || passes > kRadixMaxPasses)
+    return fail(c, ESVIO_FE_EINVAL, "%s: bits must be in 1..%d and passes in 1..%d (got %d, %d)", who, kRadixMaxBits, kRadixMaxPasses, bits, passes);
+  if (n < 0 || n >= ((int64_t)1 << 30) || n_dev < -1 || n_dev > 0xffffffffll)
+    return fail(c, ESVIO_FE_EINVAL, "%s: n must be in 0..2^30 - 1 and n_dev -1 or a 32-bit count (got %lld, %lld)", who, (long long)n, (long long)n_dev);
+  if (!out_err || !out_tickets || (n && (!keys || !vals || !out_keys || !out_vals))) return fail(c, ESVIO_FE_EINVAL, "%s: a null array", who);
+  HIPCHK(c, hipSetDevice(c->dev));
+  hipStream_t s = cur_stream(c);
+  const uint32_t n32 = (uint32_t)n, m = n_dev < 0 ? n32 : (uint32_t)std::min<int64_t>(n, n_dev);  // the pairs that take part
+  DevBuf<uint32_t> dk[2], dv[2], scratch, count;
+  for (int k = 0; k < 2; k++) {
+    if (int rc = dk[k].alloc(c, n32)) return rc;
+    if (int rc = dv[k].alloc(c, n32)) return rc;
+  }
+  const size_t words = sort_scratch_words(n32);
+  if (int rc = scratch.alloc(c, words)) return rc;
+  if (int rc = count.alloc(c, 1)) return rc;
+  std::vector<uint32_t> h(words, 0u);  // the digit counts of the pairs that take part; tickets and look-back words clear
+  for (int p = 0; p < passes; p++)
+    for (uint32_t i = 0; i < m; i++) h[((size_t)p << bits) + ((keys[i] >> (p * bits)) & ((1u << bits) - 1u))]++;
+  HIPCHK(c, hipMemcpyAsync(scratch, h.data(), words * 4, hipMemcpyHostToDevice, s));
+  if (n32) {
+    // the first buffer of each pair holds the whole input, the second the caller's out_*: a position no pass writes keeps
+    // what it held
+    HIPCHK(c, hipMemcpyAsync(dk[0], keys, (size_t)n32 * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(dv[0], vals, (size_t)n32 * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(dk[1], out_keys, (size_t)n32 * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(dv[1], out_vals, (size_t)n32 * 4, hipMemcpyHostToDevice, s));
+  }
+  const uint32_t count_value = (uint32_t)std::max<int64_t>(n_dev, 0);
+  HIPCHK(c, hipMemcpyAsync(count, &count_value, 4, hipMemcpyHostToDevice, s));
+  const int32_t err_before = c->pin[0].counts[3];  // (the passes raise the handle's word: given back as it was)
+  c->pin[0].counts[3] = 0;
+  const int cur = radix_sort_pairs(c, SortBufs{{dk[0], dk[1]}, {dv[0], dv[1]}, scratch, n_dev < 0 ? nullptr : count.p}, n32, passes, bits, false);
+  if (n32) {
+    HIPCHK(c, hipMemcpyAsync(out_keys, dk[cur], (size_t)n32 * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(out_vals, dv[cur], (size_t)n32 * 4, hipMemcpyDeviceToHost, s));
+  }
+  HIPCHK(c, hipMemcpyAsync(out_tickets, sort_scratch(scratch).tickets, (size_t)passes * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  HIPCHK(c, hipGetLastError());
+  *out_err = c->pin[0].counts[3];
+  c->pin[0].counts[3] = err_before;
+  return 0;
+}
 int esvio_fe_text_kernel_count(void) { return kTextKernels; }
 const char* esvio_fe_text_kernel_name(int which) { return which >= 0 && which < kTextKernels ? kTextKernelNames[which] : ""; }
 int esvio_fe_text_kernel_stats(esvio_fe_handle c, int which, double* total_ms, uint64_t* launches, uint64_t* alg_bytes) {

@@ -421,7 +421,7 @@ TEST_SYMBOLS = [
     "esvio_fe_bow_kernel_count", "esvio_fe_bow_kernel_name", "esvio_fe_bow_kernel_stats", "esvio_fe_bow_limits", "esvio_fe_bow_scores",
     "esvio_fe_bow_create_kernel_count", "esvio_fe_bow_create_kernel_name", "esvio_fe_bow_create_kernel_stats", "esvio_fe_bow_create_pick",
     "esvio_fe_text_limits", "esvio_fe_text_kernel_count", "esvio_fe_text_kernel_name", "esvio_fe_text_kernel_stats",
-    "esvio_fe_scan_lanes",
+    "esvio_fe_scan_lanes", "esvio_fe_sort_pairs",
 ]
 
 LATENCY_PHASES = 16
@@ -742,6 +742,7 @@ def load_library(build_if_missing=True):
     L.esvio_fe_bow_create_kernel_name.argtypes = [i]
     L.esvio_fe_bow_create_kernel_stats.argtypes = [vp, i, C.POINTER(d), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.esvio_fe_bow_create_pick.argtypes = [vp, vp, C.c_int64, vp, C.c_int32, vp, vp]
+    L.esvio_fe_sort_pairs.argtypes = [vp, vp, vp, C.c_int64, i, i, C.c_int64, vp, vp, C.POINTER(C.c_int32), vp]
     _lib = L
     return L
 
@@ -2209,6 +2210,21 @@ class FeatureTracker:
         out = np.zeros(len(cd), np.uint32)
         self._hd.check(self._hd.L.esvio_fe_bow_create_pick(self._hd.h, _p(md), len(md), _p(so), len(so) - 1, _p(cd), _p(out)))
         return out
+
+    def sort_pairs(self, keys, vals, passes, bits, n_dev=-1, fill_keys=0, fill_vals=0):
+        """the shared stable sort alone (esvio_fe_sort_pairs, a test tap): `passes` passes of `bits` bits over the low bits of
+        keys, in device memory of the call's own; n_dev >= 0: passed as the device-side count.  fill_keys / fill_vals: what
+        both device buffers hold where no pass writes.  -> (rc, keys, vals, err, tickets[passes])"""
+        k = np.ascontiguousarray(keys, np.uint32)
+        v = np.ascontiguousarray(vals, np.uint32)
+        assert k.shape == v.shape and k.ndim == 1
+        ok = np.full(max(len(k), 1), fill_keys, np.uint32)
+        ov = np.full(max(len(k), 1), fill_vals, np.uint32)
+        err = C.c_int32(-1)
+        tickets = np.full(max(int(passes), 1), 0xffffffff, np.uint32)
+        rc = self._hd.L.esvio_fe_sort_pairs(self._hd.h, _p(k), _p(v), len(k), int(passes), int(bits), int(n_dev), _p(ok), _p(ov),
+                                            C.byref(err), _p(tickets))
+        return rc, ok[:len(k)], ov[:len(k)], err.value, tickets
 
     def bow_create_kernel_stats(self):
         """vocabulary creation's own kernel table (esvio_fe_bow_create_kernel_*): name -> dict(ms, launches, alg_bytes)"""

@@ -335,6 +335,19 @@ typedef struct esvio_fe_scan_lanes_info {
   int32_t pick_tile_values;
 } esvio_fe_scan_lanes_info;
 int esvio_fe_scan_lanes(esvio_fe_scan_lanes_info* out);
+/* The shared stable sort alone (k_radix_pass through the one driver every stage's passes follow): keys[n] / vals[n] (host)
+ * sorted by the low passes * bits bits of the keys in `passes` stable passes of `bits` bits each — bits in 1..8, passes in
+ * 1..4, n below 2^30, else ESVIO_FE_EINVAL.  n_dev = -1: n is the count.  n_dev >= 0: the value is placed in device memory
+ * and passed as the device-side count, the launch stays sized for n and the first min(n, n_dev) pairs take part.  The
+ * pairs and the sort scratch are the call's own device memory, freed before it returns; the digit histograms are counted
+ * on the host from the keys that take part, the tickets and look-back words cleared.  The passes go to and fro between
+ * two device buffers per array: the first starts as the whole input, the second as the caller's out_keys / out_vals, so
+ * a position no pass wrote comes back as it went in — at and beyond a device count the result holds the caller's out_*
+ * values behind an odd number of passes, the input pairs where they lay behind an even one.  out_keys / out_vals [n]: the
+ * buffer that holds the result; *out_err: the expired-wait flag the passes raise; out_tickets[passes]: the blocks that
+ * took a ticket in each pass.  n = 0 launches nothing. */
+int esvio_fe_sort_pairs(esvio_fe_handle h, const uint32_t* keys, const uint32_t* vals, int64_t n, int passes, int bits,
+                        int64_t n_dev, uint32_t* out_keys, uint32_t* out_vals, int32_t* out_err, uint32_t* out_tickets);
 /* the hipStream_t the handle launches on (as void*) */
 void* esvio_fe_stream(esvio_fe_handle h);
 /* hipMemGetInfo on the handle's device, through the HIP runtime the library itself is linked to */

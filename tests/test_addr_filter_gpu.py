@@ -398,6 +398,44 @@ def test_learning_and_the_four_selections(farenas, way):
         ft.close()
 
 
+def test_selections_in_turn_on_a_sensor_of_several_sort_tiles():
+    """the selection sorts one key per PIXEL, 4 x 8 bits, in scratch of the stage's own that a memset clears whole before
+    every call: the sort's size and digit width are the sensor's and cannot change within a handle.  What changes from
+    call to call is the keys — at 96 x 72 (6912 keys: three full sort tiles and a partial one) a selection over many
+    counted pixels, one over five (every other key is 0xffffffff, next to the last tile's padding lanes), one over none,
+    and the first again, each as the restatement's: equal counts in pixel order."""
+    w, h = 96, 72
+    ft = FE.FeatureTracker(FE.make_config(w, h, max_cnt=40))
+    try:
+        hot = RA.Hot(w, h)
+        big = K.uniform_events(20000, w, h, 50_000, seed=71)
+        few = K.uniform_events(5, w, h, 50, seed=72, t0_us=1_000_100_000)
+
+        def learn(ev):
+            hot.learn(ev)
+            ft.hot_learn(0, ev)
+
+        def selections(tag):
+            for kw in (dict(max_pixels=4096, min_count=1), dict(max_pixels=4096, min_count=4), dict(max_pixels=7, min_count=1)):
+                same_selection(ft, 0, hot, (tag, kw), **kw)
+
+        learn(big)
+        assert same_selection(ft, 0, hot, "many", max_pixels=4096, min_count=1)[2].above > 4096
+        selections("many")
+        ft.hot_reset()
+        hot = RA.Hot(w, h)
+        learn(few)
+        assert same_selection(ft, 0, hot, "five", max_pixels=4096, min_count=1)[2].selected in (4, 5)
+        selections("five")
+        ft.hot_reset()
+        hot = RA.Hot(w, h)
+        selections("none")
+        learn(big)
+        selections("many again")
+    finally:
+        ft.close()
+
+
 def test_out_of_sensor_events_and_a_bad_stamp():
     ft = FE.FeatureTracker(FE.make_config(W, H, max_cnt=40))
     try:

@@ -183,6 +183,24 @@ def test_hot_pixel(f42, arenas):
     f42.check(arenas, 0, ev, 2000, 2, "device", FE.HOST, "hot pixel, support 2, on the plane it left")
 
 
+@pytest.mark.parametrize("w,h,window", [(K.W, K.H, MS), (346, 260, 40 * MS)])
+def test_call_sizes_big_small_big_on_one_handle(arenas, w, h, window):
+    """the stage's sort scratch is the handle's own (baf.sort): its keys kernel clears the look-back words of THIS call's
+    tile count, its heads kernel the histograms and tickets for the next.  Calls of 4 sort tiles, one tile, one event and
+    the first size again on one handle, flags and records as the restatement's on the planes the
+    calls before left.  The digit width follows the sensor (2 x 6 bits at 42 x 42, 3 x 6 at 346 x 260) and cannot
+    change within a handle: the second sensor is a second handle."""
+    f = Filtered(w, h)
+    try:
+        for k, n in enumerate((6500, 300, 6500, 1, 2049, 6500)):
+            ev = K.uniform_events(n, w, h, 8 * n, seed=300 + k, t0_us=1_000_000_000 + k * 20_000)
+            frac = f.check(arenas, 0, ev, window, 1, "device", FE.DEVICE, ("sizes", w, n, k))
+            if n >= 6500:
+                _in_range(frac, (w, n, k))
+    finally:
+        f.close()
+
+
 # ---- the plane from call to call ----------------------------------------------------------------------------------
 def _three_batches(w, h, n=3000, seed=40):
     return [K.uniform_events(n, w, h, 8 * n, seed + b, t0_us=1_000_000_000 + b * 8 * n) for b in range(3)]

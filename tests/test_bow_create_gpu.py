@@ -101,6 +101,18 @@ def test_the_widest_node_and_a_node_at_the_size_where_counts_go_through_memory(f
         check(ft, "big edge %d" % n, R.prototypes(n, 6, 0.1, n), R.even_docs(n, 3), 4, 2, seed=n)
 
 
+def test_create_sizes_big_small_big_on_one_handle(ft):
+    """both regroupings (the features by node after every level, the words by document at the end) sort in scratch of
+    the stage's own, of which a memset clears what each sort's tile and pass count use: 6149 descriptors (four sort
+    tiles), 300 (one), 3 (no k-means at all) and 6149 again on one handle, the file image byte for byte each time.
+    The digits are 8 bits wide always; the pass count follows the node and word counts of the level."""
+    big = dict(desc=R.prototypes(6149, 6, 0.1, 6149), docs=R.even_docs(6149, 3), k=4, L=2, seed=6149)
+    small = dict(desc=np.tile(R.uniform(1, 9), (300, 1)), docs=R.even_docs(300, 3), k=4, L=5, seed=2)
+    tiny = dict(desc=R.uniform(3, 103), docs=R.even_docs(3, 3), k=3, L=2, seed=3)
+    for name, kw in (("big edge 6149", big), ("identical", small), ("big edge 6149", big), ("edges 3", tiny), ("big edge 6149", big)):
+        check(ft, name, **kw)
+
+
 def test_the_deepest_tree(ft):
     desc = R.uniform(2048, 4)
     _, info = check(ft, "k 2 L 10", desc, R.even_docs(2048, 7), 2, 10, seed=11)

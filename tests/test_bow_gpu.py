@@ -138,6 +138,23 @@ def test_walk_equals_the_rule(ft, name):
         dev.free()
 
 
+@pytest.mark.parametrize("name", ["k 10, L 3", "k 3, L 2"])
+def test_transform_sizes_big_small_big_on_one_handle(ft, name):
+    """the sort between the walk and the vector runs in scratch of the group's own, of which a memset clears what THIS
+    call's tile count and pass count use (two passes for 1000 words, one for 9; the digits are 8 bits wide always):
+    4100 descriptors (three sort tiles), 5, one, and 4100 again on one handle — words, weights and the vector as the
+    rule's.  With 9 words every tile holds hundreds of each digit."""
+    voc = use(ft, WALK_TREES[name])
+    qs = walk_queries(voc, 4100, 13)
+    want = [voc.word(d) for d in qs]
+    for n in (4100, 5, 4100, 1, 2049, 4100):
+        got = ft.bow_transform(B.descs_array(qs[:n]))
+        assert got["word"].tolist() == [w for w, _ in want[:n]], (name, n)
+        vec = voc.vector(qs[:n])
+        assert got["n_bow"] == len(vec) and got["bow_word"].tolist() == [w for w, _ in vec], (name, n)
+        assert got["bow_value"].tobytes() == bits([v for _, v in vec]), (name, n)
+
+
 # ---- vector ----------------------------------------------------------------------------------------------------------
 def check_vector(ft, voc, qs, what):
     want = voc.vector(qs)

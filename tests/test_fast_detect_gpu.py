@@ -102,6 +102,26 @@ def test_stage_tap_equals_restatement(name):
     assert n_uncut > 0 and (n_cut > 0 or max(N_CANDIDATES[name]) < 2)
 
 
+def test_list_pass_counts_big_small_big_on_one_handle():
+    """the list pass sorts in scratch of the detector's own (fastc[].hist), its launch sized for the sensor's bound and
+    the count read on the device: k_fast_keys clears the look-back words, a memset the histograms and the ticket.  On
+    one handle the time surface at barrier 0 (5330 candidates: three sort tiles), at 60 (1646: one), a constant image
+    (none), and barrier 0 again; positions and scores as the restatement's, in order.  One digit width (1 x 8 bits) and
+    one launch size per handle: neither can change within one."""
+    img = _tap_images()["ts346"]
+    H, W = img.shape
+    flat = np.full_like(img, 90)
+    ft = FE.FeatureTracker(FE.make_config(W, H, max_cnt=TAP_MAX_CNT, min_dist=3))
+    try:
+        for k, (im, b) in enumerate([(img, 0), (img, 60), (img, 0), (flat, 20), (img, 0), (img, 60)]):
+            wxy, wsc, wn = R.select(im, b, TAP_MAX_CNT, 3, None)
+            gxy, gsc, gn = ft.features_to_track_fast(im, barrier=b, maxCorners=TAP_MAX_CNT, mask=None, want_count=True)
+            assert gn == wn == (0 if im is flat else N_CANDIDATES["ts346"][BARRIERS.index(b)]), (k, gn, wn)
+            assert np.array_equal(gxy, wxy) and np.array_equal(gsc, wsc), (k, b)
+    finally:
+        ft.close()
+
+
 def test_tap_rejects_bad_arguments_and_needs_no_detector_setting():
     ft = FE.FeatureTracker(FE.make_config(64, 48, max_cnt=50))
     hd, L = ft._hd, ft._hd.L

@@ -198,7 +198,58 @@ def test_sort_scratch_shared_with_the_sae_update(oracle, want, cases, monkeypatc
                 for name, a, b in zip(("L0", "L1", "S0", "S1"), ft.detector.get_sae(cam), det.get_sae(cam)):
                     assert np.array_equal(a, b), "round %d, camera %d: plane %s differs at %d pixels" % (k, cam, name, (a != b).sum())
             assert len(check(ft, want, checker, "round %d" % k)) >= 3 * 2048
-            check(ft, want, dots, "round %d" % k)
+            assert 1 < len(check(ft, want, dots, "round %d" % k)) <= 2048   # (three sort tiles and more, one tile, and again)
+    finally:
+        ft.close()
+
+
+def test_sae_gftt_and_fast_in_turn_on_one_handle(oracle, want, monkeypatch):
+    """The radix-sort form of the SAE update and goodFeaturesToTrack sort in the handle's one scratch (hist, keys, vals);
+    each leaves the histograms and tickets clear for whoever comes next and clears the look-back words of its OWN tile
+    count and digit width (3 x 6 bits against 4 x 8) itself.  The FAST list pass sorts in scratch of the detector's own
+    and runs between them.  One handle: SAE big, goodFeaturesToTrack, FAST, SAE small, FAST, goodFeaturesToTrack, SAE
+    big — planes as the oracle's, corners as the oracle's, FAST corners as tests/fast_select_ref.py's, at every step."""
+    import os
+
+    import fast_select_ref as FR
+    monkeypatch.setenv("ESVIO_FE_SAE_SORT", "1")
+    ts = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "fast_ref_ts_346x260.npz"))["ts346_img"]
+    H, W = ts.shape
+    many = GC.Case("noise", GC.mask_noise(W, H), None, 0.01, 3, 3000)
+    few = GC.Case("sparse dots", GC.dot_lattice(W, H, pitch=24), None, 0.01, 3, 3000)
+    rng = np.random.default_rng(23)
+    ft = FE.FeatureTracker(FE.make_config(W, H, max_cnt=6000, min_dist=3))
+    det = oracle.Detector(W, H)
+    t0, step = 1_700_000_000_000_000, [0]
+
+    def sae(nL, nR):
+        L = uniform_batch(W, H, nL, t0 + step[0] * 33333, 33333, rng)
+        R = uniform_batch(W, H, nR, t0 + step[0] * 33333, 33333, rng)
+        step[0] += 1
+        assert ft.detector.createSAE_stereo(L, R) == 0
+        det.create_sae(0, L)
+        det.create_sae(1, R)
+        for cam in (0, 1):
+            for name, a, b in zip(("L0", "L1", "S0", "S1"), ft.detector.get_sae(cam), det.get_sae(cam)):
+                assert np.array_equal(a, b), "step %d, camera %d: plane %s differs at %d pixels" % (step[0], cam, name, (a != b).sum())
+
+    def fast(barrier, n_tiles):
+        wxy, wsc, wn = FR.select(ts, barrier, 6000, 3, None)
+        gxy, gsc, gn = ft.features_to_track_fast(ts, barrier=barrier, maxCorners=6000, mask=None, want_count=True)
+        assert gn == wn and (wn + 2047) // 2048 == n_tiles, (barrier, gn, wn)
+        assert np.array_equal(gxy, wxy) and np.array_equal(gsc, wsc), barrier
+
+    try:
+        sae(7000, 4100)
+        n_many = len(oracle.good_features_to_track(many.img, 1 << 20, 0.01, 1, None))
+        assert n_many > 2 * 2048   # (the whole list, before the distance rule: what the sort is given; 5955)
+        check(ft, want, many, "behind the big update")
+        fast(0, 3)
+        sae(300, 0)
+        fast(60, 1)
+        assert 1 < len(check(ft, want, few, "behind the small update")) <= 2048
+        sae(7000, 4100)
+        check(ft, want, many, "again")
     finally:
         ft.close()
 

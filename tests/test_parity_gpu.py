@@ -155,6 +155,31 @@ def test_sae_partition_block_boundaries(oracle, nL, nR):
     ft.close()
 
 
+@pytest.mark.parametrize("path", ["sort_walk", "sort_per_event"])
+@pytest.mark.parametrize("W,H", [(346, 260), (64, 48)])
+def test_sae_sort_path_call_sizes_big_small_big_on_one_handle(oracle, path, W, H, monkeypatch):
+    """the radix-sort form of the update keeps its digit histograms, tickets and look-back words in the handle's sort
+    scratch, cleared by its own kernels for the NEXT call, and the look-back layout depends on the call's tile count:
+    calls of 4 + 2 sort tiles, of one tile, of one pair, and the first size again on one handle, planes as the oracle's
+    after each.  The digit width follows the sensor (3 x 6 bits at 346 x 260, 2 x 7 at 64 x 48) and is fixed for a
+    handle, as its scratch is: the second sensor is a second handle."""
+    for k, v in SAE_PATHS[path].items():
+        monkeypatch.setenv(k, v)
+    rng = np.random.default_rng(31 + W)
+    ft = _mk(W, H)
+    det = oracle.Detector(W, H)
+    t0 = 1_700_000_000_000_000
+    for b, (nL, nR) in enumerate([(7000, 4100), (300, 0), (1, 1), (7000, 4100), (0, 2049), (7000, 4100)]):
+        L = uniform_batch(W, H, nL, t0 + b * 33333, 33333, rng)
+        R = uniform_batch(W, H, nR, t0 + b * 33333, 33333, rng)
+        assert ft.detector.createSAE_stereo(L, R) == 0
+        det.create_sae(0, L)
+        det.create_sae(1, R)
+        for cam in (0, 1):
+            _planes_equal(ft.detector.get_sae(cam), det.get_sae(cam))
+    ft.close()
+
+
 @pytest.mark.parametrize("case", ["span_below", "span_at", "span_above", "big_nsec", "forced_wide", "reversed"])
 def test_sae_partition_record_formats(oracle, case, monkeypatch):
     """the tiled update partitions 8-byte records (tile-local pixel, polarity, seconds relative to the
